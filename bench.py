@@ -3,6 +3,7 @@
 
     python bench.py                                   # 1 GPU, defaults finish in ~1-2 min
     python bench.py --gpus N                          # starts N fresh rank processes itself (torch.distributed.run)
+    python bench.py --dump-outputs DIR                # + the last timed step's outputs as DIR/<name>.npy (build vs build)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -221,6 +222,32 @@ def sensor_block(sens, before, during, after):
             "power_cap_w": sens.power_cap_w(), "before": before, "during": during, "after": after}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as <path>/<name>.npy: float32 and float64
+    stay as they are, integers of up to 16 bits become float32, wider ones float64 (exact either way).  Above DUMP_LIMIT_BYTES
+    in all, each array of more than 1 MB keeps a fixed, seeded sample of its rows (first axis; indices from default_rng(0),
+    ascending), so that two builds run with the same arguments are compared on the same rows."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.kind == "f" or a.dtype.itemsize <= 2 else np.float64)
+        host[name] = a
+    small = sum(a.nbytes for a in host.values() if a.nbytes <= 1 << 20)          # kept whole
+    large = sum(a.nbytes for a in host.values()) - small
+    budget = DUMP_LIMIT_BYTES - 4096 * len(host) - small                         # room for the .npy headers
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        if large > budget and a.nbytes > 1 << 20 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * budget / large))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def step_stats(events, torch):
     """Per-launch times from an event recorded after every step: average over the region, minimum, median."""
     import statistics
@@ -267,6 +294,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         plan = dsp_amd.MfccPlan(dsp_amd.default_config(frame_length=FRAME, hop_length=FRAME), local)
         out = torch.empty((n, 1, 13), device=dev)
         step = lambda: plan.clips_pcm16(pcm, 1, out=out)       # noqa: E731
+        out_names = ("mfcc",)
         units, unit, bytes_per = n, "frames/s", FRAME * 2 + 52
         what = f"{n} x 512-sample int16 mono frames (PCM16 ingestion in the kernel's load, SURVEY 8f-1), otherwise configs[1]"
         kernel = "mfcc512_wave_kernel<IN=1>"
@@ -285,14 +313,17 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
 
         def step():
             if lab_pipe is None:
-                sj(clips, 500, fused=True)
-                return
+                return sj(clips, 500, fused=True)
+            res = []
 
             def compute(block):
-                labels, _dec, p1, _feat = sj(clips, 500, fused=True)
+                res.extend(sj(clips, 500, fused=True))
+                labels, _dec, p1, _feat = res
                 block[:, 0].copy_(labels)
                 block[:, 1].copy_(p1.view(torch.int32))
             lab_pipe.submit(compute)
+            return tuple(res)
+        out_names = ("labels", "decision", "probability", "features")
         side_finish = lab_pipe.drain if lab_pipe is not None else None
         settle_step = lambda: sj(clips, 500, fused=True)       # noqa: E731  (a gather in the time-based settle loop would hang: unequal counts)
         units, unit, bytes_per = n, "clips/s", 64_000 + 8      # label + probability out
@@ -322,6 +353,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
             flat = torch.rand(total, device=dev, generator=gen) * 2 - 1
             sj = ScrubJay(dict(np.load(os.path.join(ROOT, "tests", "golden", "scrubjay_svm.npz"))), local, n_mfcc=20)
             step = lambda: sj.ragged(flat, c_off, 500)        # noqa: E731
+            out_names = ("labels", "decision", "probability", "features")
             units, unit, bytes_per = n, "clips/s", 4.0 * total / n + 8
             what = (f"{n} fp32 clips of 0.5 - 1.5 s ({total} samples in one buffer, offsets[n + 1]) -> MFCC(20) -> mean|std -> Scaler -> RBF-SVM in ONE launch "
                     "of the fused clip kernel (dsp_scrubjay_fused_ragged_device); config5's bytes, ragged")
@@ -336,6 +368,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
                 flat[int(off[c]):int(off[c]) + m] = seg + flat[int(off[c]):int(off[c]) + m] * 0.01
             labels = torch.empty(n, dtype=torch.int32, device=dev)
             step = lambda: dsp_amd.classify_device_ragged(flat, c_off, labels)   # noqa: E731
+            out_names = ("labels",)
             units, unit, bytes_per = n, "clips/s", 4.0 * total / n + 4
             what = (f"{n} fp32 clips of 0.5 - 1.5 s ({total} samples in one buffer, offsets[n + 1]; every fourth with the call pattern) through classify() "
                     "in ONE call (dsp_classify_batch_ragged_device); classify's bytes, ragged")
@@ -347,6 +380,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         net = dsp_amd.StopModel(dict(np.load(os.path.join(ROOT, "tests", "golden", "stop_model.npz"))), local)
         plan = dsp_amd.MfccPlan(dsp_amd.default_config(), local)
         step = lambda: net.classify_signal_batch(plan, clips)   # noqa: E731
+        out_names = ("probability",)
         units, unit, bytes_per = n, "clips/s", 64_000 + 4      # probability out
         two = bool(os.environ.get("DSP_AMD_STOP_TWO_KERNELS"))
         what = (f"classify_signal (stop_detector.c:12-55) on {n} x 1 s 16 kHz fp32 clips: MFCC(13) -> StandardScaler -> 6500-4-2-2-1 net -> P(stop), "
@@ -360,6 +394,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         plan = dsp_amd.MfccPlan(dsp_amd.default_config(n_fft=1024, frame_length=1024, hop_length=1024, n_mels=128, prefilter=2), local)
         out = torch.empty((n, 13), device=dev)
         step = lambda: plan.frames(frames, out)               # noqa: E731
+        out_names = ("mfcc",)
         units, unit, bytes_per = n, "frames/s", 4096 + 52      # 4 148 B per frame
         what = (f"BASELINE configs[2] at {n} frames: float64 Butterworth 3000-7500 Hz per 1024-sample frame from zero state "
                 "-> Hann(1024) -> 1024-pt FFT -> 128 HTK mel -> dB -> 13 coeffs")
@@ -370,6 +405,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         plan = dsp_amd.MfccPlan(dsp_amd.default_config(), local)
         out = torch.empty((n, 98, 13), device=dev)
         step = lambda: plan.clips(clips, 500, out)            # noqa: E731
+        out_names = ("mfcc",)
         units, unit, bytes_per = n * 98, "frames/s", 64_000 + 98 * 52    # 69 096 B per clip
         what = f"BASELINE configs[3] per-GPU share: {n} x 1 s 16 kHz fp32 clips, frame 400 / hop 160 -> [98][13] per clip"
         kernel = "mfcc512_wave_kernel"
@@ -384,6 +420,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         call = torch.from_numpy(S.classify_cases()["scrub_a"]).to(dev).double()
         clips[::4] = call + clips[::4] * 0.1
         labels = torch.empty(n, dtype=torch.int32, device=dev)
+        out_names = ("labels",)
         kernel = ("iir2_screen_f64_kernel (both recurrences, restart states, bf16-MFMA screening of the loud bins) + spec_f64_from_ckpt_kernel<flags> "
                   "(undecided segments) + classify_f64_midpoints_kernel + spec_f64_from_ckpt_kernel<maps> + classify_f64_bands_kernel")
         if args.workload == "classify_f64_pcm16":
@@ -408,6 +445,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         del clips
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         step = lambda: dsp_amd.classify_device_pcm16(pcm, labels)   # noqa: E731
+        out_names = ("labels",)
         units, unit, bytes_per = n, "clips/s", 32_000 + 4
         what = (f"{n} x 1 s 16 kHz int16 mono clips (25 % with a call-like burst pattern), pcmSample / 32768.0 in the kernels' loads, through classify() "
                 "(2 x IIR, 2 x spectrogram, rule), bit-exact with the reference")
@@ -423,6 +461,7 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         clips[::4] = call + clips[::4] * 0.01
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         step = lambda: dsp_amd.classify_device(clips, labels)   # noqa: E731
+        out_names = ("labels",)
         units, unit, bytes_per = n, "clips/s", 64_000 + 4
         what = (f"{n} x 1 s 16 kHz fp32 clips (25 % with a call-like burst pattern, label 1) through classify() "
                 "(2 x IIR, 2 x spectrogram, rule), bit-exact with the reference")
@@ -436,13 +475,13 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    steps = max(1, args.steps // 10) if args.workload.startswith("classify") else args.steps
+    steps = args.steps
     s_before = sens.read() if sens else None
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(steps):
-        step()
+        last = step()
         evs[i + 1].record()
     s_during = sens.read() if sens else None
     if side_finish:
@@ -458,6 +497,8 @@ def side_workload(args, torch, dist, dsp_amd, dev, local, rank, world):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(out_names, last if isinstance(last, tuple) else (last,))))
     if rank == 0:
         achieved = bytes_per * n / (ms * 1e-3) / 1e9
         print(json.dumps({
@@ -591,6 +632,10 @@ def main():
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--no-config4", action="store_true", help="skip the config-4 (clips + all-gather) measurement of the frames workload's line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, rank 0's "
+                         "view; at most 64 MB in all, a fixed seeded sample of rows beyond that): inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -682,6 +727,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     s_after = sens.read() if sens else None
+    if rank == 0 and args.dump_outputs:     # what a caller of the step receives: this rank's features, or all ranks' after the gather
+        dump_outputs(args.dump_outputs, {"mfcc": pipe.result((pipe.k - 1) % pipe.depth) if pipe is not None else out})
     kernel_ms = evs[0].elapsed_time(evs[-1]) / args.steps    # back-to-back launches: avg launch duration
     kstats = step_stats(evs, torch) if every else None
     if world > 1:

@@ -97,3 +97,10 @@ def classify_cases() -> dict:
         c[tag] = x.astype(np.float32)
     c["silence"] = np.zeros(n, np.float32)
     return c
+
+
+def fft_entry_frames(rng: np.random.Generator) -> list:
+    """The 400-sample frames tests/test_gpu_mfcc.py hands fft_real_forward (tests/golden/fft_ref.npz holds the compiled
+    reference's spectra of them); draws from `rng`, which the test goes on using."""
+    return [uniform_pm1(400, 3), uniform_pm1(400, 4) * np.float32(1e-3), np.zeros(400, np.float32),
+            np.sin(2 * np.pi * 1000 * np.arange(400) / 16000).astype(np.float32), rng.standard_normal(400).astype(np.float32) * 5]

@@ -3,8 +3,9 @@
 classifier.cpp + PlainFFT.cpp (what sync/sync.cpp:202 needs).
 
 CPU tier: the export list is exactly include/dsp_amd.h + include/dsp_amd_classifier.h; examples/main_classify.cpp
-compiles with g++ against /root/reference/sync/lib/classifier.h (where present) and against
-include/dsp_amd_classifier.h, links with -ldsp_amd only, and fails loudly without a GPU.
+compiled against include/dsp_amd_classifier.h references exactly the names it references when compiled against the reference's
+sync/lib/classifier.h (tests/golden/cxx_abi_ref.npz; also live where the reference checkout is present), links with -ldsp_amd
+only, and fails loudly without a GPU.
 GPU tier: the binary's six entry points reproduce the goldens of the reference's compiled classifier.cpp bit for bit."""
 import os
 import shutil
@@ -41,14 +42,37 @@ def test_export_list_is_exactly_the_two_headers():
     assert exported == sorted(dl.SYMBOLS + list(dl.CXX_SYMBOLS.values()))
 
 
+def classifier_refs(include_args) -> list:
+    """Mangled names of the classifier.h functions an object of examples/main_classify.cpp leaves for the linker."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        obj = os.path.join(d, "main_classify.o")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-c", *include_args, os.path.join(ROOT, "examples", "main_classify.cpp"), "-o", obj],
+                       check=True, capture_output=True, text=True)
+        names = [line.split()[-1] for line in subprocess.run(["nm", "-u", obj], check=True, capture_output=True, text=True).stdout.splitlines()]
+    plain = subprocess.run(["c++filt"], input="\n".join(names), check=True, capture_output=True, text=True).stdout.splitlines()
+    return sorted(m for m, p in zip(names, plain) if p.split("(")[0] in dl.CXX_SYMBOLS)
+
+
 @needs_gxx
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sync/lib")), reason="needs the reference checkout")
-def test_caller_compiled_against_the_reference_header_links_the_library(tmp_path):
-    """No classifier.cpp, no PlainFFT.cpp on the link line: every symbol classifier.h declares resolves in libdsp_amd.so."""
-    exe = _gxx(str(tmp_path / "main_classify_ref"), against_reference=True)
-    undefined = subprocess.run(["nm", "-u", "-C", exe], check=True, capture_output=True, text=True).stdout
-    for name in dl.CXX_SYMBOLS:
-        assert f" {name}(" in undefined, name                         # bound at load time ...
+def test_caller_compiled_against_the_reference_header_links_the_library(tmp_path, golden):
+    """No classifier.cpp, no PlainFFT.cpp on the link line: every symbol classifier.h declares resolves in libdsp_amd.so.
+    The reference's side is tests/golden/cxx_abi_ref.npz (make_golden_boundary.py: the names a caller compiled against the
+    reference's own classifier.h references); include/dsp_amd_classifier.h must make a caller reference exactly those, and
+    where the reference checkout is present the caller is also compiled against its header here."""
+    want = sorted(str(s) for s in golden("cxx_abi_ref.npz")["undefined"])
+    assert len(want) == len(dl.CXX_SYMBOLS)
+    assert classifier_refs([f"-I{os.path.join(ROOT, 'include')}"]) == want
+    against_reference = os.path.isdir(os.path.join(REF, "sync/lib"))
+    if against_reference:
+        assert classifier_refs(["-DUSE_REFERENCE_HEADER", f"-I{os.path.join(REF, 'sync/lib')}"]) == want
+    exported = subprocess.run(["nm", "-D", "--defined-only", os.path.join(LIBDIR, "libdsp_amd.so")], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in exported.splitlines() if line.strip()}
+    assert set(want) <= exported
+    exe = _gxx(str(tmp_path / "main_classify_ref"), against_reference=against_reference)
+    undefined = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout.split()
+    for name in want:
+        assert name in undefined, name                                 # bound at load time ...
     ldd = subprocess.run(["ldd", exe], capture_output=True, text=True).stdout
     assert "libdsp_amd.so" in ldd                                      # ... from this library
 
