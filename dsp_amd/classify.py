@@ -74,27 +74,53 @@ def classify_config(values=None) -> "_lib.ClassifyConfig":
     return c
 
 
-def classify_batch(clips: np.ndarray, with_trace: bool = False, config=None):
-    """clips [n_clips][n] float32 (host) -> labels int32 [n_clips] (+ per-clip midpoints / band sums).
-    config: None (sync/lib thresholds) or a 6-tuple / ClassifyConfig (dsp_classify_batch_host_cfg)."""
-    clips = np.ascontiguousarray(np.atleast_2d(clips), np.float32)
-    n_clips, n = clips.shape
+STEREO_CHANNEL0, STEREO_AVERAGE = 0, 1       # dsp_amd.h: how interleaved stereo PCM becomes mono
+
+
+# ---- the calls both precisions share: f64 picks the float64 entry point (name + "_f64"), its config and trace types ----------------
+
+def _config(config, f64: bool):
+    """None (the library's defaults), a 6-tuple or a config struct -> the config argument of an entry point."""
+    if config is None:
+        return None
+    if f64:
+        cfg = config if isinstance(config, _lib.ClassifyConfigF64) else _lib.ClassifyConfigF64(*[float(v) for v in config])
+    else:
+        cfg = config if isinstance(config, _lib.ClassifyConfig) else classify_config(config)
+    return C.byref(cfg)
+
+
+def _traces(tr, n_clips: int, dtype):
+    """trace records -> [(midpoints[k], band sums[k][3])] per clip."""
+    return [(np.array(t.midpoints[:t.n_midpoints], dtype), np.array([t.sums[i][:] for i in range(t.n_midpoints)], dtype).reshape(-1, 3))
+            for t in tr[:n_clips]]
+
+
+def _host(name: str, f64: bool, signal: np.ndarray, n_clips: int, with_trace: bool, config, *args):
+    """One host entry point: (config, signal, n_clips, *args, labels, trace) -> labels (+ traces)."""
+    name += "_f64" if f64 else ""
     labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTrace * n_clips)() if with_trace else None
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    _lib.check(_lib.load().dsp_classify_batch_host_cfg(C.byref(cfg) if cfg is not None else None, clips.ctypes.data, n_clips, n, n,
-                                                        labels.ctypes.data, C.byref(tr) if with_trace else None), "dsp_classify_batch_host_cfg")
-    if not with_trace:
-        return labels
-    out = []
-    for t in tr:
-        k = t.n_midpoints
-        out.append((np.array(t.midpoints[:k], np.float32),
-                    np.array([[t.sums[i][j] for j in range(3)] for i in range(k)], np.float32).reshape(-1, 3)))
-    return labels, out
+    tr = ((_lib.ClassifyTraceF64 if f64 else _lib.ClassifyTrace) * max(n_clips, 1))() if with_trace else None
+    _lib.check(getattr(_lib.load(), name)(_config(config, f64), signal.ctypes.data, n_clips, *args, labels.ctypes.data,
+                                          C.byref(tr) if with_trace else None), name)
+    return (labels, _traces(tr, n_clips, np.float64 if f64 else np.float32)) if with_trace else labels
 
 
-def _pcm_shape(pcm):
+def _device(name: str, f64: bool, signal, n_clips: int, labels, config, *args):
+    """One device entry point: (config, signal, n_clips, *args, labels, [trace,] stream) on torch's current stream -> cuda int32 labels."""
+    import torch
+    name += "_f64" if f64 else ""
+    if labels is None:
+        labels = torch.empty(n_clips, dtype=torch.int32, device=signal.device)
+    st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
+    trace = (None,) if f64 else ()
+    _lib.check(getattr(_lib.load(), name)(_config(config, f64), signal.data_ptr(), n_clips, *args, labels.data_ptr(), *trace, st), name)
+    return labels
+
+
+def _pcm_host(pcm):
+    """int16 [n], [n_clips][n] or [n_clips][n][2] -> (contiguous [n_clips][n](...), channels)."""
+    pcm = np.ascontiguousarray(pcm, np.int16)
     if pcm.ndim == 1:
         pcm = pcm[None, :]
     if pcm.ndim not in (2, 3) or (pcm.ndim == 3 and pcm.shape[2] != 2):
@@ -102,99 +128,102 @@ def _pcm_shape(pcm):
     return pcm, (2 if pcm.ndim == 3 else 1)
 
 
-def classify_batch_pcm16(pcm: np.ndarray, stereo_mode: int = 0, with_trace: bool = False, config=None):
-    """dsp_classify_batch_pcm16_host: the float32 classify() on int16 PCM [n_clips][n] (mono) or [n_clips][n][2] (interleaved stereo:
-    channel 0 or the channels' average), converted in the kernels' loads as sync/sync.cpp:237-242 does (pcmSample / 32768.0)."""
-    pcm, channels = _pcm_shape(np.ascontiguousarray(pcm, np.int16))
-    n_clips, n = pcm.shape[:2]
-    labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTrace * n_clips)() if with_trace else None
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    _lib.check(_lib.load().dsp_classify_batch_pcm16_host(C.byref(cfg) if cfg is not None else None, pcm.ctypes.data, n_clips, n, n, channels, int(stereo_mode),
-                                                          labels.ctypes.data, C.byref(tr) if with_trace else None), "dsp_classify_batch_pcm16_host")
-    if not with_trace:
-        return labels
-    out = []
-    for t in tr:
-        k = t.n_midpoints
-        out.append((np.array(t.midpoints[:k], np.float32),
-                    np.array([[t.sums[i][j] for j in range(3)] for i in range(k)], np.float32).reshape(-1, 3)))
-    return labels, out
-
-
-def classify_device_pcm16(pcm, labels=None, stereo_mode: int = 0, config=None):
-    """pcm: cuda int16 [n_clips][n] or [n_clips][n][2] -> cuda int32 labels (dsp_classify_batch_pcm16_device), stream-ordered."""
+def _pcm_device(pcm):
+    """cuda int16 [n_clips][n] or interleaved [n_clips][n][2] -> (channels, clip stride in samples per channel)."""
     import torch
     if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (2, 3) and pcm.stride(-1) == 1):
         raise ValueError("pcm must be an int16 CUDA tensor [n_clips][n] or [n_clips][n][2] with unit inner stride")
     channels = 2 if pcm.dim() == 3 else 1
     if channels == 2 and (pcm.shape[2] != 2 or pcm.stride(1) != 2 or pcm.stride(0) % 2):
         raise ValueError("stereo pcm must be interleaved [n_clips][n][2]")
+    return channels, pcm.stride(0) // channels
+
+
+def _clips_device(clips, f64: bool):
+    import torch
+    dt = torch.float64 if f64 else torch.float32
+    if not (clips.is_cuda and clips.dtype == dt and clips.dim() == 2 and clips.stride(1) == 1):
+        raise ValueError(f"clips must be a {'float64' if f64 else 'float32'} CUDA tensor [n_clips][n] with unit inner stride")
+    return clips
+
+
+def _ragged_host(f64: bool, signal, offsets, stereo_mode, with_trace, config):
+    signal = np.ascontiguousarray(signal)
+    off, n_clips = _lib.c_offsets(offsets)
+    if off[n_clips] > signal.shape[0]:
+        raise ValueError("offsets run past the end of the signal")
+    if signal.dtype == np.int16:
+        if signal.ndim not in (1, 2):
+            raise ValueError("int16 signal must be [total] or interleaved [total][2]")
+        return _host("dsp_classify_batch_ragged_pcm16_host", f64, signal, n_clips, with_trace, config, off, signal.ndim, int(stereo_mode))
+    signal = np.ascontiguousarray(signal, np.float64 if f64 else np.float32)
+    if signal.ndim != 1:
+        raise ValueError("float signal must be one flat buffer [total]")
+    return _host("dsp_classify_batch_ragged_host", f64, signal, n_clips, with_trace, config, off)
+
+
+def _ragged_device(f64: bool, signal, offsets, labels, stereo_mode, config):
+    import torch
+    off, n_clips = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
+    if not (signal.is_cuda and signal.stride(-1) == 1 and off[n_clips] <= signal.shape[0]):
+        raise ValueError("signal must be a CUDA tensor with unit inner stride that holds every clip of offsets")
+    if signal.dtype == torch.int16:
+        if signal.dim() not in (1, 2):
+            raise ValueError("int16 signal must be [total] or interleaved [total][2]")
+        return _device("dsp_classify_batch_ragged_pcm16_device", f64, signal, n_clips, labels, config, off, signal.dim(), int(stereo_mode))
+    if signal.dtype != (torch.float64 if f64 else torch.float32) or signal.dim() != 1:
+        raise ValueError(f"signal must be {'float64' if f64 else 'float32'} [total], int16 [total] or int16 [total][2]")
+    return _device("dsp_classify_batch_ragged_device", f64, signal, n_clips, labels, config, off)
+
+
+# ---- float32: sync/lib/classifier.cpp ---------------------------------------------------------------------------------------------
+
+def classify_batch(clips: np.ndarray, with_trace: bool = False, config=None):
+    """clips [n_clips][n] float32 (host) -> labels int32 [n_clips] (+ per-clip midpoints / band sums).
+    config: None (sync/lib thresholds) or a 6-tuple / ClassifyConfig (dsp_classify_batch_host_cfg)."""
+    clips = np.ascontiguousarray(np.atleast_2d(clips), np.float32)
+    n_clips, n = clips.shape
+    return _host("dsp_classify_batch_host_cfg", False, clips, n_clips, with_trace, config, n, n)
+
+
+def classify_batch_pcm16(pcm: np.ndarray, stereo_mode: int = 0, with_trace: bool = False, config=None):
+    """dsp_classify_batch_pcm16_host: the float32 classify() on int16 PCM [n_clips][n] (mono) or [n_clips][n][2] (interleaved stereo:
+    channel 0 or the channels' average), converted in the kernels' loads as sync/sync.cpp:237-242 does (pcmSample / 32768.0)."""
+    pcm, channels = _pcm_host(pcm)
     n_clips, n = pcm.shape[:2]
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=pcm.device)
-    st = C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    _lib.check(_lib.load().dsp_classify_batch_pcm16_device(C.byref(cfg) if cfg is not None else None, pcm.data_ptr(), n_clips, n, pcm.stride(0) // channels,
-                                                            channels, int(stereo_mode), labels.data_ptr(), st), "dsp_classify_batch_pcm16_device")
-    return labels
+    return _host("dsp_classify_batch_pcm16_host", False, pcm, n_clips, with_trace, config, n, n, channels, int(stereo_mode))
 
 
-def _traces(tr):
-    out = []
-    for t in tr:
-        k = t.n_midpoints
-        out.append((np.array(t.midpoints[:k], np.float32),
-                    np.array([[t.sums[i][j] for j in range(3)] for i in range(k)], np.float32).reshape(-1, 3)))
-    return out
+def classify_device(clips, labels=None, config=None):
+    """clips: cuda float32 [n_clips][n] -> cuda int32 labels; runs on torch's current stream."""
+    n_clips, n = _clips_device(clips, False).shape
+    return _device("dsp_classify_batch_device_cfg", False, clips, n_clips, labels, config, n, clips.stride(0))
+
+
+def classify_device_pcm16(pcm, labels=None, stereo_mode: int = 0, config=None):
+    """pcm: cuda int16 [n_clips][n] or [n_clips][n][2] -> cuda int32 labels (dsp_classify_batch_pcm16_device), stream-ordered."""
+    channels, stride = _pcm_device(pcm)
+    n_clips, n = pcm.shape[:2]
+    return _device("dsp_classify_batch_pcm16_device", False, pcm, n_clips, labels, config, n, stride, channels, int(stereo_mode))
 
 
 def classify_ragged(signal: np.ndarray, offsets, stereo_mode: int = 0, with_trace: bool = False, config=None):
     """Clips of different lengths in ONE call (dsp_classify_batch_ragged_host / _pcm16_host): `signal` is a flat host buffer -- float32
     [total], int16 [total] or interleaved stereo int16 [total][2] -- and clip c is samples [offsets[c], offsets[c + 1]).  Labels (and
     traces) as one classify() per clip gives them."""
-    signal = np.ascontiguousarray(signal)
-    off, n_clips = _lib.c_offsets(offsets)
-    assert int(offsets[-1]) <= signal.shape[0]
-    labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTrace * max(n_clips, 1))() if with_trace else None
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    cp = C.byref(cfg) if cfg is not None else None
-    if signal.dtype == np.int16:
-        assert signal.ndim in (1, 2)
-        _lib.check(_lib.load().dsp_classify_batch_ragged_pcm16_host(cp, signal.ctypes.data, n_clips, off, signal.ndim, int(stereo_mode), labels.ctypes.data,
-                                                                     C.byref(tr) if with_trace else None), "dsp_classify_batch_ragged_pcm16_host")
-    else:
-        signal = np.ascontiguousarray(signal, np.float32)
-        assert signal.ndim == 1
-        _lib.check(_lib.load().dsp_classify_batch_ragged_host(cp, signal.ctypes.data, n_clips, off, labels.ctypes.data, C.byref(tr) if with_trace else None),
-                   "dsp_classify_batch_ragged_host")
-    return (labels, _traces(tr)[:n_clips]) if with_trace else labels
+    return _ragged_host(False, signal, offsets, stereo_mode, with_trace, config)
 
 
 def classify_device_ragged(signal, offsets, labels=None, stereo_mode: int = 0, config=None):
     """The same on a flat cuda buffer (float32 [total], int16 [total] or [total][2]) -> cuda int32 labels, stream-ordered."""
-    import torch
-    off, n_clips = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
-    assert signal.is_cuda and signal.stride(-1) == 1 and int(off[n_clips]) <= signal.shape[0]
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=signal.device)
-    st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    cp = C.byref(cfg) if cfg is not None else None
-    if signal.dtype == torch.int16:
-        assert signal.dim() in (1, 2)
-        _lib.check(_lib.load().dsp_classify_batch_ragged_pcm16_device(cp, signal.data_ptr(), n_clips, off, signal.dim(), int(stereo_mode), labels.data_ptr(), st),
-                   "dsp_classify_batch_ragged_pcm16_device")
-    else:
-        assert signal.dtype == torch.float32 and signal.dim() == 1
-        _lib.check(_lib.load().dsp_classify_batch_ragged_device(cp, signal.data_ptr(), n_clips, off, labels.data_ptr(), st), "dsp_classify_batch_ragged_device")
-    return labels
+    return _ragged_device(False, signal, offsets, labels, stereo_mode, config)
 
 
 def classify_release(device: int = -1) -> None:
     _lib.check(_lib.load().dsp_classify_release(int(device)), "dsp_classify_release")
 
+
+# ---- float64: donut-classifier/classifier.c ---------------------------------------------------------------------------------------
 
 def classify_batch_f64(clips: np.ndarray, with_trace: bool = False, config=None):
     """The float64 classifier of donut-classifier/classifier.c (:83-192) on the GPU: clips [n_clips][n] float64 (host) -> labels
@@ -202,122 +231,42 @@ def classify_batch_f64(clips: np.ndarray, with_trace: bool = False, config=None)
     6-tuple (keep_lo, keep_hi, midpoint_db, middle_max, above_min, below_min) of doubles."""
     clips = np.ascontiguousarray(np.atleast_2d(clips), np.float64)
     n_clips, n = clips.shape
-    labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTraceF64 * n_clips)() if with_trace else None
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    _lib.check(_lib.load().dsp_classify_batch_host_f64(C.byref(cfg) if cfg is not None else None, clips.ctypes.data, n_clips, n, n,
-                                                        labels.ctypes.data, C.byref(tr) if with_trace else None), "dsp_classify_batch_host_f64")
-    return (labels, _trace_f64(tr)) if with_trace else labels
+    return _host("dsp_classify_batch_host", True, clips, n_clips, with_trace, config, n, n)
 
 
 def classify_device_f64(clips, labels=None, config=None):
     """clips: cuda float64 [n_clips][n] -> cuda int32 labels (dsp_classify_batch_device_f64); runs on torch's current stream."""
-    import torch
-    if not (clips.is_cuda and clips.dtype == torch.float64 and clips.dim() == 2 and clips.stride(1) == 1):
-        raise ValueError("clips must be a float64 CUDA tensor [n_clips][n] with unit inner stride")
-    n_clips, n = clips.shape
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=clips.device)
-    st = C.c_void_p(torch.cuda.current_stream(clips.device).cuda_stream)
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    _lib.check(_lib.load().dsp_classify_batch_device_f64(C.byref(cfg) if cfg is not None else None, clips.data_ptr(), n_clips, n,
-                                                          clips.stride(0), labels.data_ptr(), None, st), "dsp_classify_batch_device_f64")
-    return labels
-
-
-STEREO_CHANNEL0, STEREO_AVERAGE = 0, 1       # dsp_amd.h: how interleaved stereo PCM becomes mono
-
-
-def _trace_f64(tr):
-    out = []
-    for t in tr:
-        k = t.n_midpoints
-        out.append((np.array(t.midpoints[:k], np.float64),
-                    np.array([[t.sums[i][j] for j in range(3)] for i in range(k)], np.float64).reshape(-1, 3)))
-    return out
+    n_clips, n = _clips_device(clips, True).shape
+    return _device("dsp_classify_batch_device", True, clips, n_clips, labels, config, n, clips.stride(0))
 
 
 def classify_batch_f64_pcm16(pcm: np.ndarray, stereo_mode: int = STEREO_CHANNEL0, with_trace: bool = False, config=None):
     """dsp_classify_batch_pcm16_host_f64: pcm int16 [n_clips][n] (mono) or [n_clips][n][2] (interleaved stereo; channel 0 as
     donut-classifier/classifier.c:286-297 or the channels' average) -> labels (+ midpoints / band sums), the samples converted in the
     kernels' loads exactly like classifier.c:55-59 (s / 32768.0)."""
-    pcm = np.ascontiguousarray(pcm, np.int16)
-    if pcm.ndim == 1:
-        pcm = pcm[None, :]
-    channels = 2 if pcm.ndim == 3 else 1
-    if pcm.ndim not in (2, 3) or (pcm.ndim == 3 and pcm.shape[2] != 2):
-        raise ValueError("pcm must be int16 [n_clips][n] or [n_clips][n][2]")
+    pcm, channels = _pcm_host(pcm)
     n_clips, n = pcm.shape[:2]
-    labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTraceF64 * n_clips)() if with_trace else None
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    _lib.check(_lib.load().dsp_classify_batch_pcm16_host_f64(C.byref(cfg) if cfg is not None else None, pcm.ctypes.data, n_clips, n, n, channels,
-                                                              int(stereo_mode), labels.ctypes.data, C.byref(tr) if with_trace else None),
-               "dsp_classify_batch_pcm16_host_f64")
-    return (labels, _trace_f64(tr)) if with_trace else labels
+    return _host("dsp_classify_batch_pcm16_host", True, pcm, n_clips, with_trace, config, n, n, channels, int(stereo_mode))
 
 
 def classify_device_f64_pcm16(pcm, labels=None, stereo_mode: int = STEREO_CHANNEL0, config=None):
     """pcm: cuda int16 [n_clips][n] or [n_clips][n][2] -> cuda int32 labels (dsp_classify_batch_pcm16_device_f64), stream-ordered on
     torch's current stream."""
-    import torch
-    if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (2, 3) and pcm.stride(-1) == 1):
-        raise ValueError("pcm must be an int16 CUDA tensor [n_clips][n] or [n_clips][n][2] with unit inner stride")
-    channels = 2 if pcm.dim() == 3 else 1
-    if channels == 2 and (pcm.shape[2] != 2 or pcm.stride(1) != 2 or pcm.stride(0) % 2):
-        raise ValueError("stereo pcm must be interleaved [n_clips][n][2]")
+    channels, stride = _pcm_device(pcm)
     n_clips, n = pcm.shape[:2]
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=pcm.device)
-    st = C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    _lib.check(_lib.load().dsp_classify_batch_pcm16_device_f64(C.byref(cfg) if cfg is not None else None, pcm.data_ptr(), n_clips, n,
-                                                                pcm.stride(0) // channels, channels, int(stereo_mode), labels.data_ptr(), None, st),
-               "dsp_classify_batch_pcm16_device_f64")
-    return labels
+    return _device("dsp_classify_batch_pcm16_device", True, pcm, n_clips, labels, config, n, stride, channels, int(stereo_mode))
 
 
 def classify_ragged_f64(signal: np.ndarray, offsets, stereo_mode: int = STEREO_CHANNEL0, with_trace: bool = False, config=None):
     """The float64 classifier on clips of different lengths in ONE call (dsp_classify_batch_ragged_host_f64 / _pcm16_host_f64): `signal`
     is a flat host buffer -- float64 [total], int16 [total] or interleaved stereo int16 [total][2] -- and clip c is samples
     [offsets[c], offsets[c + 1])."""
-    signal = np.ascontiguousarray(signal)
-    off, n_clips = _lib.c_offsets(offsets)
-    assert int(offsets[-1]) <= signal.shape[0]
-    labels = np.zeros(n_clips, np.int32)
-    tr = (_lib.ClassifyTraceF64 * max(n_clips, 1))() if with_trace else None
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    cp = C.byref(cfg) if cfg is not None else None
-    if signal.dtype == np.int16:
-        assert signal.ndim in (1, 2)
-        _lib.check(_lib.load().dsp_classify_batch_ragged_pcm16_host_f64(cp, signal.ctypes.data, n_clips, off, signal.ndim, int(stereo_mode), labels.ctypes.data,
-                                                                         C.byref(tr) if with_trace else None), "dsp_classify_batch_ragged_pcm16_host_f64")
-    else:
-        signal = np.ascontiguousarray(signal, np.float64)
-        assert signal.ndim == 1
-        _lib.check(_lib.load().dsp_classify_batch_ragged_host_f64(cp, signal.ctypes.data, n_clips, off, labels.ctypes.data, C.byref(tr) if with_trace else None),
-                   "dsp_classify_batch_ragged_host_f64")
-    return (labels, _trace_f64(tr)[:n_clips]) if with_trace else labels
+    return _ragged_host(True, signal, offsets, stereo_mode, with_trace, config)
 
 
 def classify_device_ragged_f64(signal, offsets, labels=None, stereo_mode: int = STEREO_CHANNEL0, config=None):
     """The same on a flat cuda buffer (float64 [total], int16 [total] or [total][2]) -> cuda int32 labels, stream-ordered."""
-    import torch
-    off, n_clips = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
-    assert signal.is_cuda and signal.stride(-1) == 1 and int(off[n_clips]) <= signal.shape[0]
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=signal.device)
-    st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
-    cfg = None if config is None else _lib.ClassifyConfigF64(*[float(v) for v in config])
-    cp = C.byref(cfg) if cfg is not None else None
-    if signal.dtype == torch.int16:
-        assert signal.dim() in (1, 2)
-        _lib.check(_lib.load().dsp_classify_batch_ragged_pcm16_device_f64(cp, signal.data_ptr(), n_clips, off, signal.dim(), int(stereo_mode), labels.data_ptr(), None, st),
-                   "dsp_classify_batch_ragged_pcm16_device_f64")
-    else:
-        assert signal.dtype == torch.float64 and signal.dim() == 1
-        _lib.check(_lib.load().dsp_classify_batch_ragged_device_f64(cp, signal.data_ptr(), n_clips, off, labels.data_ptr(), None, st), "dsp_classify_batch_ragged_device_f64")
-    return labels
+    return _ragged_device(True, signal, offsets, labels, stereo_mode, config)
 
 
 def classify_stats_f64(device: int = 0):
@@ -337,18 +286,3 @@ def find_midpoints(data: np.ndarray, fs: int = 16000) -> np.ndarray:
     out = np.zeros(64, np.float32)
     n = _lib.check(_lib.load().dsp_find_midpoints(data.ctypes.data, data.size, int(fs), out.ctypes.data, out.size), "dsp_find_midpoints")
     return out[:n].copy()
-
-
-def classify_device(clips, labels=None, config=None):
-    """clips: cuda float32 [n_clips][n] -> cuda int32 labels; runs on torch's current stream."""
-    import torch
-    if not (clips.is_cuda and clips.dtype == torch.float32 and clips.dim() == 2 and clips.stride(1) == 1):
-        raise ValueError("clips must be a float32 CUDA tensor [n_clips][n] with unit inner stride")
-    n_clips, n = clips.shape
-    if labels is None:
-        labels = torch.empty(n_clips, dtype=torch.int32, device=clips.device)
-    st = C.c_void_p(torch.cuda.current_stream(clips.device).cuda_stream)
-    cfg = None if config is None else (config if isinstance(config, _lib.ClassifyConfig) else classify_config(config))
-    _lib.check(_lib.load().dsp_classify_batch_device_cfg(C.byref(cfg) if cfg is not None else None, clips.data_ptr(), n_clips, n,
-                                                          clips.stride(0), labels.data_ptr(), st), "dsp_classify_batch_device_cfg")
-    return labels

@@ -1,4 +1,5 @@
-// capi.cpp -- the C ABI of libdsp_amd.so (include/dsp_amd.h).
+// capi.cpp -- the C ABI of libdsp_amd.so (include/dsp_amd.h): the MFCC plans, the SVM and the fused paths.  The donut classifiers
+// are capi_classify_f32.cpp and capi_classify_f64.cpp.
 //
 // Host side of the drop-in boundary: owns plans (device tables + staging
 // buffers), validates arguments the way the reference does, and enqueues the
@@ -10,12 +11,9 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstddef>
 #include <cstring>
-#include <chrono>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <string>
 #include <vector>
 
@@ -664,355 +662,6 @@ int dsp_mfcc_clips_host(dsp_mfcc_plan *p, const float *signal, long n_clips, int
     return t;
 }
 
-}  // extern "C"
-
-// ---- donut classifier path ------------------------------------------------------------
-
-namespace {
-
-struct ClassifyCtx {
-    int device = -1;
-    dsp::SpecTables *d_tab = nullptr;
-    // workspace for one sub-batch
-    float *d_x = nullptr, *d_sbp = nullptr;                // staged input (host entry points), 3000-7500 Hz PSD maps [clip][T][129]
-    float *d_ck_bp = nullptr, *d_ck_mp = nullptr;          // [clip][T][kCkPerSegBp / Mp][8]: delay line of each filter at every segment start (3000-7500 Hz: and middle)
-    float *d_mean_mp = nullptr;                            // [clip][T]: segment means of the 1000-3000 Hz output
-    int *d_labels = nullptr, *d_hits = nullptr;            // d_hits: work list of clips with midpoints
-    int *d_loud = nullptr;                                 // [clip][T]: time bins of the 1000-3000 Hz map above 70 dB; after the midpoints kernel: rows of the 3000-7500 Hz map the band sums read
-    unsigned *d_minmax = nullptr;                          // [clip][2]: float bits of the smallest / largest positive cell of the 3000-7500 Hz map
-    int *d_simd = nullptr;                                 // iir2_ckpt_kernel's per-CU SIMD load table (launch_iir2_ckpt)
-    int *d_gate = nullptr;                                 // work list of the segments whose energy does not rule a loud cell out (IIR kernel)
-    dsp::ClassifyTrace *d_trace = nullptr;
-    long cap_clips = 0;                                    // per-clip arrays (labels, hits, trace, minmax)
-    long cap_segs = 0;                                     // per-segment arrays: clips x segments per clip of the largest pass so far
-    long cap_x_floats = 0;                                 // staging buffer of the host entry points, in floats (0: none)
-    float keep_min_db = 70.0f;                             // the midpoint threshold d_tab->mp_keep_min was computed for
-    bool gate_ok = false;                                  // SpecTables::gate_ok of d_tab
-    std::mutex mu;
-    hipEvent_t done = nullptr;                             // recorded behind the last call's work: the workspace is free once it has fired
-    bool pending = false;
-    dsp::SpanRing spans;                                   // ragged batches: the clips' spans on their way to the GPU (capi_util.hpp)
-    void wait_idle()
-    {
-        if (pending && done) (void)hipEventSynchronize(done);
-        pending = false;
-    }
-};
-// One context (tables + grow-only workspace + mutex) PER DEVICE: threads that drive different GPUs from one process share nothing, and
-// a device entry point returns once its work is enqueued -- the next call on that device makes its stream wait for the event this one
-// leaves behind.  (Round 3: one process-wide context that moved between GPUs and blocked until the stream was idle.)
-constexpr int kMaxDevices = 64;
-ClassifyCtx g_cls_ctx[kMaxDevices];
-
-// leaves the "workspace busy until here" event behind the call's work on every exit
-struct ClsBusyMark {
-    ClassifyCtx &c;
-    hipStream_t st;
-    ~ClsBusyMark()
-    {
-        if (c.done && hipEventRecord(c.done, st) == hipSuccess) c.pending = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize(st); c.pending = false; }
-    }
-};
-
-// 957 columns = 13.4 s: a midpoint needs a cluster of >= 12 columns (0.15 s at 14 ms per column) followed by a gap of >= 4
-// (0.05 s), so 64 * 15 - 3 columns cannot hold more than the kMaxMidpoints = 64 a trace record has room for
-constexpr int kMaxSpecColumns = 957;
-
-bool valid_classify_cfg(const dsp_classify_config &c)
-{
-    auto fin = [](float v) { return v == v && v - v == 0.0f; };
-    return fin(c.keep_lo) && fin(c.keep_hi) && fin(c.midpoint_db) && fin(c.middle_max) && fin(c.above_min) && fin(c.below_min) &&
-           c.keep_lo < c.keep_hi;
-}
-
-dsp_classify_config default_classify_cfg()
-{
-    // sync/lib/classifier.cpp:67-68 (0.65 / 0.80), :436 (70 dB), :109 (100 / 200 / 80)
-    return dsp_classify_config{0.65f, 0.80f, 70.0f, 100.0f, 200.0f, 80.0f};
-}
-
-static_assert(sizeof(dsp::ClassifyTrace) == sizeof(dsp_classify_trace), "trace layouts must match");
-
-// the device of the host entry points: DSP_AMD_DEVICE or 0
-int cls_host_device(int &device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
-    const char *dev = std::getenv("DSP_AMD_DEVICE");
-    device = dev ? std::atoi(dev) : 0;
-    if (device < 0 || device >= n || device >= kMaxDevices) return fail(DSP_EINVAL, "device index out of range");
-    return DSP_OK;
-}
-
-// tables of the context of `device` (the caller holds g_cls.mu and has made the device current)
-int cls_init(ClassifyCtx &g_cls, int device)
-{
-    if (g_cls.d_tab) return DSP_OK;
-    g_cls.device = device;
-    if (!g_cls.done) DSP_HIP(hipEventCreateWithFlags(&g_cls.done, hipEventDisableTiming));
-    dsp::SpecTables t;
-    dsp::build_spec_tables(16000, t);
-    DSP_HIP(hipMalloc(&g_cls.d_tab, sizeof(t)));
-    DSP_HIP(hipMemcpy(g_cls.d_tab, &t, sizeof(t), hipMemcpyHostToDevice));
-    g_cls.gate_ok = t.gate_ok != 0;
-    g_cls.keep_min_db = 70.0f;
-    DSP_HIP(dsp::launch_spec_threshold(g_cls.d_tab, g_cls.keep_min_db, nullptr));
-    {   // the recompute kernel's three-instruction PSD division is switched on only after it has been checked against the real
-        // division on every float of its range, for this table's U, on this device (~1e9 values: a fraction of a millisecond)
-        unsigned long long *d_bad = nullptr, bad = 1;
-        DSP_HIP(hipMalloc(&d_bad, sizeof(bad)));
-        hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(bad), nullptr);
-        if (e == hipSuccess) e = dsp::launch_spec_div_verify(g_cls.d_tab, d_bad, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-        hipFree(d_bad);
-        if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-        const int on = bad == 0 && !std::getenv("DSP_AMD_SPEC_EXACT_DIV") ? 1 : 0;
-        DSP_HIP(hipMemcpy(reinterpret_cast<char *>(g_cls.d_tab) + offsetof(dsp::SpecTables, div_fast), &on, sizeof(on), hipMemcpyHostToDevice));
-    }
-    DSP_HIP(hipStreamSynchronize(nullptr));
-    return DSP_OK;
-}
-
-int spec_bins(int n) { return n < dsp::kSpecSeg ? 0 : (n - dsp::kSpecSeg) / dsp::kSpecHop + 1; }
-long cls_row(int n) { return ((long)n + 3) & ~3L; }      // workspace row: n floats rounded up to 16 bytes
-
-void cls_free_workspace(ClassifyCtx &g_cls)
-{
-    for (void *p : {(void *)g_cls.d_x, (void *)g_cls.d_sbp, (void *)g_cls.d_ck_bp, (void *)g_cls.d_ck_mp, (void *)g_cls.d_loud, (void *)g_cls.d_gate, (void *)g_cls.d_simd,
-                    (void *)g_cls.d_mean_mp, (void *)g_cls.d_labels, (void *)g_cls.d_hits, (void *)g_cls.d_trace, (void *)g_cls.d_minmax})
-        if (p) hipFree(p);
-    g_cls.d_x = g_cls.d_sbp = g_cls.d_ck_bp = g_cls.d_ck_mp = g_cls.d_mean_mp = nullptr;
-    g_cls.d_labels = g_cls.d_hits = g_cls.d_loud = g_cls.d_gate = g_cls.d_simd = nullptr; g_cls.d_trace = nullptr; g_cls.d_minmax = nullptr;
-    g_cls.cap_clips = 0; g_cls.cap_segs = 0; g_cls.cap_x_floats = 0;
-}
-
-void cls_release(ClassifyCtx &g_cls)      // (on g_cls.device, made current by the caller)
-{
-    g_cls.wait_idle();
-    cls_free_workspace(g_cls);
-    if (g_cls.d_tab) hipFree(g_cls.d_tab);
-    g_cls.d_tab = nullptr;
-    if (g_cls.done) (void)hipEventDestroy(g_cls.done);
-    g_cls.done = nullptr;
-    g_cls.spans.release();
-    g_cls.device = -1;
-}
-
-// workspace of one sub-batch; need_x: also a staging buffer for the clips themselves (host entry points).  The per-segment arrays
-// are [clip][T(n)] with the pass's own T, so what a pass needs of them is its PRODUCT clips x T: a ragged batch's pass of few long
-// clips and its pass of many short ones share one allocation (sized by each dimension's maximum it would be their outer product --
-// 32 GB of maps for 65 536 clips of which one is 13 s long).
-int cls_reserve(ClassifyCtx &g_cls, long clips, int n, bool need_x)
-{
-    const long T = std::max(1, spec_bins(n));
-    const long x_floats = need_x ? clips * cls_row(n) : 0;
-    if (clips <= g_cls.cap_clips && clips * T <= g_cls.cap_segs && x_floats <= g_cls.cap_x_floats) return DSP_OK;
-    g_cls.wait_idle();
-    const long rows = std::max(clips, g_cls.cap_clips), segs = std::max(clips * T, g_cls.cap_segs), xf = std::max(x_floats, g_cls.cap_x_floats);
-    cls_free_workspace(g_cls);
-    if (xf > 0) DSP_HIP(hipMalloc(&g_cls.d_x, (size_t)xf * sizeof(float)));      // (staged int16 rows are at most as long)
-    DSP_HIP(hipMalloc(&g_cls.d_sbp, (size_t)segs * dsp::kSpecBins * sizeof(float)));
-    DSP_HIP(hipMalloc(&g_cls.d_ck_bp, (size_t)segs * dsp::kCkPerSegBp * 8 * sizeof(float)));
-    DSP_HIP(hipMalloc(&g_cls.d_ck_mp, (size_t)segs * dsp::kCkPerSegMp * 8 * sizeof(float)));
-    DSP_HIP(hipMalloc(&g_cls.d_loud, (size_t)segs * sizeof(int)));
-    DSP_HIP(hipMalloc(&g_cls.d_minmax, (size_t)rows * 2 * sizeof(unsigned)));
-    DSP_HIP(hipMalloc(&g_cls.d_simd, sizeof(int) * dsp::kSimdLoadCus * dsp::kSimdLoadStride));
-    DSP_HIP(hipMalloc(&g_cls.d_gate, ((size_t)segs + 1) * sizeof(int)));      // work list of gated-in frames: count + frame numbers
-    DSP_HIP(hipMalloc(&g_cls.d_mean_mp, (size_t)segs * sizeof(float)));
-    DSP_HIP(hipMalloc(&g_cls.d_labels, (size_t)rows * sizeof(int)));
-    DSP_HIP(hipMalloc(&g_cls.d_hits, (size_t)(rows + 1) * sizeof(int)));
-    DSP_HIP(hipMalloc(&g_cls.d_trace, (size_t)rows * sizeof(dsp::ClassifyTrace)));
-    g_cls.cap_clips = rows; g_cls.cap_segs = segs; g_cls.cap_x_floats = xf;
-    return DSP_OK;
-}
-
-dsp::IirCoef coef_f32(double lo, double hi)
-{
-    double b[9], a[9];
-    dsp_butter_bandpass(lo, hi, b, a);
-    dsp::IirCoef c;
-    for (int i = 0; i < 9; ++i) { c.b[i] = (float)b[i]; c.a[i] = (float)a[i]; }   // classifier.cpp:140-183: float literals
-    return c;
-}
-
-// one sub-batch already resident at d_x (input kind `in`: 0 float, 1 / 2 / 3 int16 mono / stereo channel 0 / stereo average; row
-// stride in samples per channel): labels (+ trace) into the workspace
-// spans != nullptr: a ragged sub-batch (clip c at spans[c].off samples from d_x with spans[c].frames whole segments; n = the longest
-// clip of the BATCH, total = samples in the buffer)
-int cls_run(ClassifyCtx &g_cls, const dsp_classify_config &cfg, const void *d_x, int in, long clips, int n, long stride, hipStream_t st, bool want_trace,
-            const dsp::ClipSpan *spans = nullptr, long total = 0)
-{
-    const dsp::IirCoef bp = coef_f32(3000, 7500), mp = coef_f32(1000, 3000);   // classifier.cpp:14-19, 438-442
-    if (cfg.midpoint_db != g_cls.keep_min_db) {      // the table's threshold PSD value follows the configured dB threshold
-        // (earlier calls on this context are ordered before this one by its event)
-        DSP_HIP(dsp::launch_spec_threshold(g_cls.d_tab, cfg.midpoint_db, st));
-        g_cls.keep_min_db = cfg.midpoint_db;
-    }
-    const dsp::ClassifyRule rule{cfg.keep_lo, cfg.keep_hi, cfg.middle_max, cfg.above_min, cfg.below_min};
-    // ONE pass over the clips: both recurrences, the delay lines at every segment start, the 1000-3000 Hz segment means and
-    // the energy gate.  No filtered signal is written; the spectrogram kernels recompute the segments they transform.
-    DSP_HIP(dsp::launch_iir2_ckpt(d_x, clips, n, stride, bp, mp, g_cls.d_ck_bp, g_cls.d_ck_mp, g_cls.d_mean_mp, g_cls.d_gate, g_cls.d_tab, st, g_cls.d_simd, in, spans, total));
-    // midpoints first (1000-3000 Hz map, as flags, gated frames only); the 3000-7500 Hz spectrogram and its band sums only for
-    // clips that have midpoints
-    DSP_HIP(dsp::launch_spec_from_ckpt(d_x, clips, n, stride, mp, g_cls.d_ck_mp, g_cls.d_mean_mp, g_cls.d_gate, nullptr, g_cls.d_tab,
-                                       reinterpret_cast<float *>(g_cls.d_loud), true, st, nullptr, nullptr, in, spans));
-    // DSP_AMD_CLASSIFY_FULL_MAPS=1: every row of the listed clips' maps is stored and read (the form before the need / minmax hand-over)
-    static const bool full_maps = [] { const char *e = std::getenv("DSP_AMD_CLASSIFY_FULL_MAPS"); return e && std::atoi(e) != 0; }();
-    unsigned *mm = full_maps ? nullptr : g_cls.d_minmax;
-    const int *need = full_maps ? nullptr : g_cls.d_loud;
-    DSP_HIP(dsp::launch_classify_midpoints(g_cls.d_loud, clips, n, 16000, g_cls.d_labels, g_cls.d_trace, g_cls.d_hits, st, want_trace, mm, spans));
-    DSP_HIP(dsp::launch_spec_from_ckpt(d_x, clips, n, stride, bp, g_cls.d_ck_bp, nullptr, nullptr, g_cls.d_hits, g_cls.d_tab, g_cls.d_sbp, false, st, need, mm, in, spans));
-    DSP_HIP(dsp::launch_classify_bands(g_cls.d_sbp, clips, n, 16000, g_cls.d_labels, g_cls.d_trace, g_cls.d_hits, st, rule, need, mm, spans));
-    return DSP_OK;
-}
-
-// clips per pass through the workspace (42 KB per 1 s clip): 1024 blocks of 64 clips = the four IIR blocks a CU holds
-constexpr long kClsSubBatch = 65536;
-
-}  // namespace
-
-extern "C" {
-
-int dsp_classify_division_check(long long *mismatches)
-{
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    unsigned long long *d_bad = nullptr, bad = 0;
-    int on = 0;
-    DSP_HIP(hipMalloc(&d_bad, sizeof(bad)));
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(bad), nullptr);
-    if (e == hipSuccess) e = dsp::launch_spec_div_verify(g_cls.d_tab, d_bad, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&on, reinterpret_cast<const char *>(g_cls.d_tab) + offsetof(dsp::SpecTables, div_fast), sizeof(on), hipMemcpyDeviceToHost);
-    hipFree(d_bad);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    if (mismatches) *mismatches = (long long)bad;
-    return on ? 1 : 0;
-}
-
-int dsp_butter_bandpass_filter_f32(const float *data, long n_clips, int n, long stride, const float *b,
-                                   const float *a, float *output)
-{
-    if (!data || !output || !b || !a || n_clips < 0 || n < 0 || (n_clips > 1 && stride < n)) return fail(DSP_EINVAL, "bad argument");
-    if (n_clips == 0 || n == 0) return DSP_OK;
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    float *dx = nullptr, *dy = nullptr;
-    const size_t bytes = (size_t)n_clips * n * sizeof(float);
-    DSP_HIP(hipMalloc(&dx, bytes));
-    if (hipMalloc(&dy, bytes) != hipSuccess) { hipFree(dx); return fail(DSP_ENOMEM, "hipMalloc"); }
-    dsp::IirCoef c;
-    for (int i = 0; i < 9; ++i) { c.b[i] = b[i]; c.a[i] = a[i]; }
-    hipError_t e = hipMemcpy2D(dx, (size_t)n * sizeof(float), data, (size_t)stride * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_iir_f32(dx, n_clips, n, n, c, dy, c, nullptr, nullptr);
-    if (e == hipSuccess) e = hipMemcpy2D(output, (size_t)stride * sizeof(float), dy, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dy);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    return DSP_OK;
-}
-
-int dsp_butter_bandpass_filter_f64(const double *data, long n_clips, int n, long stride, const double *b,
-                                   const double *a, double *output)
-{
-    if (!data || !output || !b || !a || n_clips < 0 || n < 0 || (n_clips > 1 && stride < n)) return fail(DSP_EINVAL, "bad argument");
-    if (n_clips == 0 || n == 0) return DSP_OK;
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    double *dx = nullptr, *dy = nullptr;
-    const size_t bytes = (size_t)n_clips * n * sizeof(double);
-    DSP_HIP(hipMalloc(&dx, bytes));
-    if (hipMalloc(&dy, bytes) != hipSuccess) { hipFree(dx); return fail(DSP_ENOMEM, "hipMalloc"); }
-    dsp::IirCoefD c;
-    for (int i = 0; i < 9; ++i) { c.b[i] = b[i]; c.a[i] = a[i]; }
-    hipError_t e = hipMemcpy2D(dx, (size_t)n * sizeof(double), data, (size_t)stride * sizeof(double), (size_t)n * sizeof(double), n_clips, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_iir_f64(dx, n_clips, n, n, c, dy, nullptr);
-    if (e == hipSuccess) e = hipMemcpy2D(output, (size_t)stride * sizeof(double), dy, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n_clips, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(dy);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    return DSP_OK;
-}
-
-int dsp_compute_spectrogram_f32(const float *signal, int n, int fs, float *frequencies, float *times, float *sxx)
-{
-    if (!signal || !sxx || n < 0 || fs <= 0) return fail(DSP_EINVAL, "bad argument");
-    const int T = spec_bins(n);
-    if (frequencies)
-        for (int k = 0; k < dsp::kSpecBins; ++k) frequencies[k] = (float)k * (float)fs / (float)dsp::kSpecSeg;   // classifier.cpp:248-251
-    if (times)
-        for (int t = 0; t < T; ++t) times[t] = ((float)(t * dsp::kSpecHop + dsp::kSpecSeg / 2)) / (float)fs;     // :254-258
-    if (T == 0) return 0;
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    float *dx = nullptr, *ds = nullptr;
-    dsp::SpecTables *dt = nullptr;               // fs enters only through the PSD scale U = fs * sum w^2 (classifier.cpp:296-301)
-    DSP_HIP(hipMalloc(&dx, (size_t)n * sizeof(float)));
-    const size_t sb = (size_t)dsp::kSpecBins * T * sizeof(float);
-    if (hipMalloc(&ds, sb) != hipSuccess) { hipFree(dx); return fail(DSP_ENOMEM, "hipMalloc"); }
-    hipError_t e = hipSuccess;
-    if (fs != 16000) {
-        dsp::SpecTables t;
-        dsp::build_spec_tables(fs, t);
-        e = hipMalloc(&dt, sizeof(t));
-        if (e == hipSuccess) e = hipMemcpy(dt, &t, sizeof(t), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(dx, signal, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_spectrogram_f32(dx, 1, n, n, dt ? dt : g_cls.d_tab, ds, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(sxx, ds, sb, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(ds);
-    if (dt) hipFree(dt);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    return T;
-}
-
-int dsp_compute_spectrogram_f64(const double *signal, int n, int fs, double *frequencies, double *times, double *sxx)
-{
-    if (!signal || !sxx || n < 0 || fs <= 0) return fail(DSP_EINVAL, "bad argument");
-    const int T = spec_bins(n);
-    if (frequencies)
-        for (int k = 0; k < dsp::kSpecBins; ++k) frequencies[k] = (double)k * fs / dsp::kSpecSeg;                      // classifier.c:468-471
-    if (times)
-        for (int t = 0; t < T; ++t) times[t] = (double)(t * dsp::kSpecHop + dsp::kSpecSeg / 2) / fs;                    // :474-478
-    if (T == 0) return 0;
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    double *dx = nullptr, *ds = nullptr;
-    DSP_HIP(hipMalloc(&dx, (size_t)n * sizeof(double)));
-    const size_t sb = (size_t)dsp::kSpecBins * T * sizeof(double);
-    if (hipMalloc(&ds, sb) != hipSuccess) { hipFree(dx); return fail(DSP_ENOMEM, "hipMalloc"); }
-    hipError_t e = hipMemcpy(dx, signal, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_spectrogram_f64(dx, 1, n, n, fs, ds, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(sxx, ds, sb, hipMemcpyDeviceToHost);
-    hipFree(dx); hipFree(ds);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    return T;
-}
-
 #ifdef DSP_PF_STAMPS
 __attribute__((visibility("default"))) int dsp_debug_pf_stamps(unsigned long long *out, int count)     // tools/pf_stamps.py
 {
@@ -1035,420 +684,6 @@ __attribute__((visibility("default"))) int dsp_debug_bd_stamps(unsigned long lon
     return DSP_OK;
 }
 #endif
-
-int dsp_sum_intense_f32(float lower, float upper, float half_range, const float *frequencies, int freq_bins,
-                        const float *times, int time_bins, const float *db, float midpoint, float *out)
-{
-    if (!frequencies || !times || !db || !out || freq_bins <= 0 || time_bins <= 0) return fail(DSP_EINVAL, "bad argument");
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    const size_t nf = freq_bins, nt = time_bins, total = nf + nt + nf * nt + 1;
-    float *d = nullptr;
-    DSP_HIP(hipMalloc(&d, total * sizeof(float)));
-    hipError_t e = hipMemcpy(d, frequencies, nf * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + nf, times, nt * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + nf + nt, db, nf * nt * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_sum_intense(lower, upper, half_range, d, freq_bins, d + nf, time_bins, d + nf + nt, midpoint, d + nf + nt + nf * nt, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d + nf + nt + nf * nt, sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
-    return DSP_OK;
-}
-
-void dsp_classify_default_config(dsp_classify_config *cfg)
-{
-    if (cfg) *cfg = default_classify_cfg();
-}
-
-namespace {
-
-int cls_bytes(int in) { return in == 0 ? 4 : (in == 1 ? 2 : 4); }     // bytes per sample, all channels
-
-int cls_input_kind(int channels, int stereo_mode, int &in)
-{
-    if (channels != 1 && channels != 2) return fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
-    in = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return DSP_OK;
-}
-
-int cls_host_entry(const dsp_classify_config *cfgp, const void *signal, int in, long n_clips, int n, long stride, int *labels, dsp_classify_trace *trace)
-{
-    if (!signal || !labels || n_clips < 0 || n < 0 || (n_clips > 1 && stride < n)) return fail(DSP_EINVAL, "bad argument");
-    const dsp_classify_config cfg = cfgp ? *cfgp : default_classify_cfg();
-    if (!valid_classify_cfg(cfg)) return fail(DSP_EINVAL, "classify config: thresholds must be finite with keep_lo < keep_hi");
-    if (spec_bins(n) > kMaxSpecColumns) return fail(DSP_EINVAL, "clip too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
-    if (spec_bins(n) == 0) {      // clips shorter than one segment cannot fire the rule
-        for (long c = 0; c < n_clips; ++c) labels[c] = 0;
-        if (trace) std::memset(trace, 0, sizeof(*trace) * (size_t)n_clips);
-        return DSP_OK;
-    }
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    if ((rc = cls_init(g_cls, device)) < 0) return rc;
-    const int bps = cls_bytes(in);
-    const long row = (((long)n * bps + 15) & ~15L) / bps;            // staged rows start on 16 bytes
-    if ((rc = cls_reserve(g_cls, std::min(kClsSubBatch, n_clips), n, true)) < 0) return rc;
-    g_cls.wait_idle();                                               // the staging buffer is written by copies on the null stream
-    ClsBusyMark mark{g_cls, nullptr};
-    for (long c0 = 0; c0 < n_clips; c0 += kClsSubBatch) {
-        const long cnt = std::min(kClsSubBatch, n_clips - c0);
-        DSP_HIP(hipMemcpy2DAsync(g_cls.d_x, (size_t)row * bps, static_cast<const unsigned char *>(signal) + (size_t)c0 * stride * bps, (size_t)stride * bps,
-                                 (size_t)n * bps, cnt, hipMemcpyHostToDevice, nullptr));
-        if ((rc = cls_run(g_cls, cfg, g_cls.d_x, in, cnt, n, row, nullptr, trace != nullptr)) < 0) return rc;
-        DSP_HIP(hipMemcpyAsync(labels + c0, g_cls.d_labels, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-        if (trace) DSP_HIP(hipMemcpyAsync(trace + c0, g_cls.d_trace, (size_t)cnt * sizeof(dsp::ClassifyTrace), hipMemcpyDeviceToHost, nullptr));
-        DSP_HIP(hipStreamSynchronize(nullptr));
-    }
-    return DSP_OK;
-}
-
-int cls_device_entry(const dsp_classify_config *cfgp, const void *d_signal, int in, long n_clips, int n, long stride, int *d_labels, void *stream,
-                     ClassifyCtx *own = nullptr)
-{
-    if (!d_signal || !d_labels || n_clips < 0 || n < 0 || (n_clips > 1 && stride < n)) return fail(DSP_EINVAL, "bad argument");
-    const dsp_classify_config cfg = cfgp ? *cfgp : default_classify_cfg();
-    if (!valid_classify_cfg(cfg)) return fail(DSP_EINVAL, "classify config: thresholds must be finite with keep_lo < keep_hi");
-    if (spec_bins(n) > kMaxSpecColumns) return fail(DSP_EINVAL, "clip too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
-    if (n_clips == 0) return DSP_OK;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_signal) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(DSP_EINVAL, "signal is not a device pointer");
-    }
-    if (attr.device < 0 || attr.device >= kMaxDevices) return fail(DSP_EINVAL, "device index out of range");
-    if (own && own->device >= 0 && own->device != attr.device) return fail(DSP_EINVAL, "the context belongs to another device than the signal");
-    ClassifyCtx &g_cls = own ? *own : g_cls_ctx[attr.device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(attr.device);
-    int rc = cls_init(g_cls, attr.device);
-    if (rc < 0) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (spec_bins(n) == 0) { DSP_HIP(hipMemsetAsync(d_labels, 0, (size_t)n_clips * sizeof(int), st)); return DSP_OK; }
-    if ((rc = cls_reserve(g_cls, std::min(kClsSubBatch, n_clips), n, false)) < 0) return rc;
-    if (g_cls.pending) DSP_HIP(hipStreamWaitEvent(st, g_cls.done, 0));      // the previous call's work on this workspace (any stream)
-    ClsBusyMark mark{g_cls, st};
-    for (long c0 = 0; c0 < n_clips; c0 += kClsSubBatch) {
-        const long cnt = std::min(kClsSubBatch, n_clips - c0);
-        const void *src = static_cast<const unsigned char *>(d_signal) + (size_t)c0 * stride * cls_bytes(in);
-        if ((rc = cls_run(g_cls, cfg, src, in, cnt, n, stride, st, false)) < 0) return rc;
-        DSP_HIP(hipMemcpyAsync(d_labels + c0, g_cls.d_labels, (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, st));
-    }
-    return DSP_OK;
-}
-
-// Ragged batches (donut-classifier/classifier.c:286-297 reads one file of any length per run; its callers loop over files): the clips'
-// spans from the host's offsets[n_clips + 1] (samples per channel from the buffer's start), every clip with the segments ITS length
-// holds.  d_signal: the whole buffer on the GPU.  labels / trace (host, optional) are copied back when given, d_labels (device) otherwise.
-int cls_ragged(const dsp_classify_config *cfgp, const void *d_signal, int device, int in, long n_clips, const long *offsets, int *d_labels, int *labels,
-               dsp_classify_trace *trace, void *stream)
-{
-    const dsp_classify_config cfg = cfgp ? *cfgp : default_classify_cfg();
-    if (!valid_classify_cfg(cfg)) return fail(DSP_EINVAL, "classify config: thresholds must be finite with keep_lo < keep_hi");
-    int n_max = 0;
-    for (long c = 0; c < n_clips; ++c) {
-        const long n = offsets[c + 1] - offsets[c];
-        if (offsets[c] < 0 || n < 0 || n > INT32_MAX) return fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples");
-        if (spec_bins((int)n) > kMaxSpecColumns) return fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
-        n_max = std::max(n_max, (int)n);
-    }
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    DSP_ON_DEVICE(device);
-    int rc = cls_init(g_cls, device);
-    if (rc < 0) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (spec_bins(n_max) == 0) {                        // no clip holds a segment: no midpoints, label 0 (classifier.cpp:93-114)
-        if (d_labels) DSP_HIP(hipMemsetAsync(d_labels, 0, (size_t)n_clips * sizeof(int), st));
-        if (labels) std::memset(labels, 0, (size_t)n_clips * sizeof(int));
-        if (trace) std::memset(trace, 0, (size_t)n_clips * sizeof(dsp_classify_trace));
-        return DSP_OK;
-    }
-    // The clips run in order of length, longest first: the kernels take 64 clips per block and walk to the block's longest, so a block of
-    // alike clips wastes nothing (measured on clips of 0.5 - 1.5 s in the caller's order: +54 % over the same samples in equal clips).
-    // order[i] = the caller's index of the i-th clip as run; results go home through it (launch_scatter_records / on the host).
-    if (n_clips >= (1L << 31)) return fail(DSP_EINVAL, "too many clips");
-    std::vector<int> order((size_t)n_clips), segs((size_t)n_clips);
-    for (long c = 0; c < n_clips; ++c) segs[c] = spec_bins((int)(offsets[c + 1] - offsets[c]));
-    dsp::order_by_key_desc(segs.data(), n_clips, spec_bins(n_max), order.data());
-    const size_t span_bytes = (size_t)n_clips * sizeof(dsp::ClipSpan), perm_bytes = (size_t)n_clips * sizeof(int);
-    dsp::SpanRing::Slot *slot = nullptr;
-    DSP_HIP(g_cls.spans.acquire(span_bytes + perm_bytes, &slot));
-    dsp::ClipSpan *h = static_cast<dsp::ClipSpan *>(slot->h);
-    for (long i = 0; i < n_clips; ++i) {
-        const long c = order[i];
-        h[i] = dsp::ClipSpan{offsets[c], (int)(offsets[c + 1] - offsets[c]), spec_bins((int)(offsets[c + 1] - offsets[c])), c, 0};
-    }
-    std::memcpy(static_cast<char *>(slot->h) + span_bytes, order.data(), perm_bytes);
-    if (g_cls.pending) DSP_HIP(hipStreamWaitEvent(st, g_cls.done, 0));      // the previous call's work on this workspace (any stream)
-    DSP_HIP(dsp::SpanRing::upload(slot, span_bytes + perm_bytes, st));
-    const int *d_perm = reinterpret_cast<const int *>(static_cast<const char *>(slot->d) + span_bytes);
-    std::vector<int> h_labels;
-    std::vector<dsp::ClassifyTrace> h_trace;
-    // Passes: as many clips as a pass of equal 1 s clips has SEGMENTS for (the workspaces are [clip][segments of the pass's longest clip]):
-    // few clips per pass while they are long, the full 65 536 once they are short
-    // (four times that before a pass is cut short: a small remainder pass costs a whole clip's sequential chain for few clips -- 0.5 - 1.5 s
-    // clips in two passes measured 3.6 ms against 3.1 ms in one; the bound is there for batches with very long clips, ~11 GB of workspace)
-    constexpr long kPassSegs = 4 * kClsSubBatch * 71;
-    struct Pass { long c0, cnt; int n_row; };
-    std::vector<Pass> passes;
-    for (long c0 = 0; c0 < n_clips;) {
-        const int t_row = std::max(1, h[c0].frames);                            // sorted: the pass's longest clip comes first
-        const long cnt = std::min({kClsSubBatch, n_clips - c0, std::max(64L, kPassSegs / t_row)});
-        passes.push_back(Pass{c0, cnt, (t_row - 1) * dsp::kSpecHop + dsp::kSpecSeg});
-        c0 += cnt;
-    }
-    for (const Pass &ps : passes)
-        if ((rc = cls_reserve(g_cls, ps.cnt, ps.n_row, false)) < 0) { dsp::SpanRing::mark(slot, st); return rc; }
-    struct SlotMark { dsp::SpanRing::Slot *s; hipStream_t st; ~SlotMark() { dsp::SpanRing::mark(s, st); } } slot_mark{slot, st};
-    ClsBusyMark mark{g_cls, st};
-    const dsp::ClipSpan *d_spans = static_cast<const dsp::ClipSpan *>(slot->d);
-    for (const Pass &ps : passes) {
-        const long c0 = ps.c0, cnt = ps.cnt;
-        if ((rc = cls_run(g_cls, cfg, d_signal, in, cnt, ps.n_row, 0, st, trace != nullptr, d_spans + c0, offsets[n_clips])) < 0) return rc;
-        if (d_labels) DSP_HIP(dsp::launch_scatter_records(g_cls.d_labels, d_perm + c0, cnt, sizeof(int), d_labels, st));
-        if (labels) {
-            h_labels.resize((size_t)cnt);
-            DSP_HIP(hipMemcpyAsync(h_labels.data(), g_cls.d_labels, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, st));
-        }
-        if (trace) {
-            h_trace.resize((size_t)cnt);
-            DSP_HIP(hipMemcpyAsync(h_trace.data(), g_cls.d_trace, (size_t)cnt * sizeof(dsp::ClassifyTrace), hipMemcpyDeviceToHost, st));
-        }
-        if (labels || trace) {
-            DSP_HIP(hipStreamSynchronize(st));
-            for (long i = 0; i < cnt; ++i) {
-                if (labels) labels[order[c0 + i]] = h_labels[i];
-                if (trace) std::memcpy(&trace[order[c0 + i]], &h_trace[i], sizeof(dsp_classify_trace));
-            }
-        }
-    }
-    return DSP_OK;
-}
-
-int cls_ragged_device_entry(const dsp_classify_config *cfgp, const void *d_signal, int in, long n_clips, const long *offsets, int *d_labels, void *stream)
-{
-    if (!d_signal || !d_labels || !offsets || n_clips < 0) return fail(DSP_EINVAL, "bad argument");
-    if (n_clips == 0) return DSP_OK;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_signal) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(DSP_EINVAL, "signal is not a device pointer");
-    }
-    if (attr.device < 0 || attr.device >= kMaxDevices) return fail(DSP_EINVAL, "device index out of range");
-    return cls_ragged(cfgp, d_signal, attr.device, in, n_clips, offsets, d_labels, nullptr, nullptr, stream);
-}
-
-int cls_ragged_host_entry(const dsp_classify_config *cfgp, const void *signal, int in, long n_clips, const long *offsets, int *labels, dsp_classify_trace *trace)
-{
-    if (!signal || !labels || !offsets || n_clips < 0) return fail(DSP_EINVAL, "bad argument");
-    if (n_clips == 0) return DSP_OK;
-    if (offsets[n_clips] < offsets[0] || offsets[0] < 0) return fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples");
-    int device = 0;
-    int rc = cls_host_device(device);
-    if (rc < 0) return rc;
-    // the whole buffer travels once (a buffer of its own: the contexts' staging rows are laid out for equal clips)
-    void *d_flat = nullptr;
-    const size_t bytes = (size_t)offsets[n_clips] * cls_bytes(in);
-    {
-        DSP_ON_DEVICE(device);
-        DSP_HIP(hipMalloc(&d_flat, bytes + 16));
-        const hipError_t e = hipMemcpy(d_flat, signal, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_flat); DSP_HIP(e); }
-    }
-    rc = cls_ragged(cfgp, d_flat, device, in, n_clips, offsets, nullptr, labels, trace, nullptr);
-    {
-        dsp::DeviceScope on(device);
-        (void)hipStreamSynchronize(nullptr);
-        (void)hipFree(d_flat);
-    }
-    return rc;
-}
-
-}  // namespace
-
-int dsp_classify_batch_host_cfg(const dsp_classify_config *cfgp, const float *signal, long n_clips, int n, long stride, int *labels,
-                                dsp_classify_trace *trace)
-{
-    return cls_host_entry(cfgp, signal, 0, n_clips, n, stride, labels, trace);
-}
-
-int dsp_classify_batch_pcm16_host(const dsp_classify_config *cfgp, const int16_t *pcm, long n_clips, int n, long stride, int channels, int stereo_mode,
-                                  int *labels, dsp_classify_trace *trace)
-{
-    int in = 0;
-    const int rc = cls_input_kind(channels, stereo_mode, in);
-    return rc < 0 ? rc : cls_host_entry(cfgp, pcm, in, n_clips, n, stride, labels, trace);
-}
-
-int dsp_classify_batch_pcm16_device(const dsp_classify_config *cfgp, const int16_t *d_pcm, long n_clips, int n, long stride, int channels,
-                                    int stereo_mode, int *d_labels, void *stream)
-{
-    int in = 0;
-    const int rc = cls_input_kind(channels, stereo_mode, in);
-    return rc < 0 ? rc : cls_device_entry(cfgp, d_pcm, in, n_clips, n, stride, d_labels, stream);
-}
-
-int dsp_classify_batch_ragged_device(const dsp_classify_config *cfgp, const float *d_signal, long n_clips, const long *offsets, int *d_labels, void *stream)
-{
-    return cls_ragged_device_entry(cfgp, d_signal, 0, n_clips, offsets, d_labels, stream);
-}
-
-int dsp_classify_batch_ragged_pcm16_device(const dsp_classify_config *cfgp, const int16_t *d_pcm, long n_clips, const long *offsets, int channels,
-                                           int stereo_mode, int *d_labels, void *stream)
-{
-    int in = 0;
-    const int rc = cls_input_kind(channels, stereo_mode, in);
-    return rc < 0 ? rc : cls_ragged_device_entry(cfgp, d_pcm, in, n_clips, offsets, d_labels, stream);
-}
-
-int dsp_classify_batch_ragged_host(const dsp_classify_config *cfgp, const float *signal, long n_clips, const long *offsets, int *labels,
-                                   dsp_classify_trace *trace)
-{
-    return cls_ragged_host_entry(cfgp, signal, 0, n_clips, offsets, labels, trace);
-}
-
-int dsp_classify_batch_ragged_pcm16_host(const dsp_classify_config *cfgp, const int16_t *pcm, long n_clips, const long *offsets, int channels,
-                                         int stereo_mode, int *labels, dsp_classify_trace *trace)
-{
-    int in = 0;
-    const int rc = cls_input_kind(channels, stereo_mode, in);
-    return rc < 0 ? rc : cls_ragged_host_entry(cfgp, pcm, in, n_clips, offsets, labels, trace);
-}
-
-/* A context of the caller's own: the default entry points share one workspace per device, so two calls on one device run one behind
- * the other; calls through different contexts (on different streams) may overlap. */
-struct dsp_classify_ctx { ClassifyCtx c; int device; };
-
-int dsp_classify_ctx_create(int device, dsp_classify_ctx **out)
-{
-    if (!out) return fail(DSP_EINVAL, "bad argument");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
-    if (device < 0 || device >= n || device >= kMaxDevices) return fail(DSP_EINVAL, "device index out of range");
-    auto *ctx = new (std::nothrow) dsp_classify_ctx;
-    if (!ctx) return fail(DSP_ENOMEM, "out of memory");
-    ctx->device = device;
-    {
-        std::lock_guard<std::mutex> lock(ctx->c.mu);
-        DSP_ON_DEVICE(device);
-        const int rc = cls_init(ctx->c, device);
-        if (rc < 0) { cls_release(ctx->c); delete ctx; return rc; }
-    }
-    *out = ctx;
-    return DSP_OK;
-}
-
-void dsp_classify_ctx_destroy(dsp_classify_ctx *ctx)
-{
-    if (!ctx) return;
-    {
-        std::lock_guard<std::mutex> lock(ctx->c.mu);
-        dsp::DeviceScope on(ctx->device);
-        cls_release(ctx->c);
-    }
-    delete ctx;
-}
-
-int dsp_classify_batch_device_ctx(dsp_classify_ctx *ctx, const dsp_classify_config *cfgp, const float *d_signal, long n_clips, int n, long stride,
-                                  int *d_labels, void *stream)
-{
-    if (!ctx) return fail(DSP_EINVAL, "bad argument");
-    return cls_device_entry(cfgp, d_signal, 0, n_clips, n, stride, d_labels, stream, &ctx->c);
-}
-
-/* Test hook (no HIP call): holds the default classifier context of `device` for hold_ms milliseconds.  tests/test_capi_cpu.py runs it
- * from two threads: on two devices the holds overlap, on one device they queue. */
-int dsp_debug_hold_classify_ctx(int device, int hold_ms)
-{
-    if (device < 0 || device >= kMaxDevices || hold_ms < 0 || hold_ms > 10000) return fail(DSP_EINVAL, "bad argument");
-    std::lock_guard<std::mutex> lock(g_cls_ctx[device].mu);
-    std::this_thread::sleep_for(std::chrono::milliseconds(hold_ms));
-    return DSP_OK;
-}
-
-int dsp_classify_stats(int device, long *gated_segments, long *listed_clips)
-{
-    if (device < 0 || device >= kMaxDevices) return fail(DSP_EINVAL, "device index out of range");
-    ClassifyCtx &g_cls = g_cls_ctx[device];
-    std::lock_guard<std::mutex> lock(g_cls.mu);
-    if (g_cls.device < 0 || !g_cls.d_gate) return fail(DSP_EINVAL, "no classifier pass has run on this device");
-    DSP_ON_DEVICE(device);
-    g_cls.wait_idle();
-    int ng = 0, nh = 0;
-    DSP_HIP(hipMemcpy(&ng, g_cls.d_gate, sizeof(int), hipMemcpyDeviceToHost));
-    DSP_HIP(hipMemcpy(&nh, g_cls.d_hits, sizeof(int), hipMemcpyDeviceToHost));
-    if (gated_segments) *gated_segments = ng;
-    if (listed_clips) *listed_clips = nh;
-    return DSP_OK;
-}
-
-int dsp_classify_release(int device)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
-    for (int d = 0; d < kMaxDevices && d < count; ++d) {
-        if (device >= 0 && d != device) continue;
-        ClassifyCtx &g_cls = g_cls_ctx[d];
-        std::lock_guard<std::mutex> lock(g_cls.mu);
-        if (g_cls.device < 0) continue;
-        DSP_ON_DEVICE(d);
-        cls_release(g_cls);
-    }
-    return DSP_OK;
-}
-
-int dsp_classify_batch_host(const float *signal, long n_clips, int n, long stride, int *labels, dsp_classify_trace *trace)
-{
-    return dsp_classify_batch_host_cfg(nullptr, signal, n_clips, n, stride, labels, trace);
-}
-
-int dsp_classify_batch_device_cfg(const dsp_classify_config *cfgp, const float *d_signal, long n_clips, int n, long stride,
-                                  int *d_labels, void *stream)
-{
-    return cls_device_entry(cfgp, d_signal, 0, n_clips, n, stride, d_labels, stream);
-}
-
-int dsp_classify_batch_device(const float *d_signal, long n_clips, int n, long stride, int *d_labels, void *stream)
-{
-    return dsp_classify_batch_device_cfg(nullptr, d_signal, n_clips, n, stride, d_labels, stream);
-}
-
-// sync/lib/classifier.h:18 (find_midpoints): the midpoints are a by-product of the classify pipeline (its trace record)
-int dsp_find_midpoints(const float *data, int num_frames, int fs, float *midpoints, int max_midpoints)
-{
-    if (!data || num_frames <= 0 || max_midpoints < 0 || (max_midpoints > 0 && !midpoints)) return fail(DSP_EINVAL, "bad argument");
-    if (fs != 16000) return fail(DSP_EINVAL, "find_midpoints: only 16000 Hz has filter coefficients (classifier.cpp:138-191)");
-    int label = 0;
-    dsp_classify_trace tr;
-    const int rc = dsp_classify_batch_host(data, 1, num_frames, num_frames, &label, &tr);
-    if (rc < 0) return rc;
-    for (int i = 0; i < tr.n_midpoints && i < max_midpoints; ++i) midpoints[i] = tr.midpoints[i];
-    return tr.n_midpoints;
-}
-
-// sync/lib/classifier.h:19.  Same contract: 0/1, 0 also on failure (reason in dsp_last_error()).
-int dsp_classify(float *data, int data_size)
-{
-    int label = 0;
-    if (!data || data_size <= 0) { fail(DSP_EINVAL, "bad argument"); return 0; }
-    const int rc = dsp_classify_batch_host(data, 1, data_size, data_size, &label, nullptr);
-    if (rc < 0) {
-        std::fprintf(stderr, "libdsp_amd: classify: %s\n", dsp_last_error());
-        return 0;
-    }
-    return label;
-}
 
 }  // extern "C"
 

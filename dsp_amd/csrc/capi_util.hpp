@@ -1,4 +1,5 @@
-// capi_util.hpp -- error reporting shared by the translation units of the C ABI.
+// capi_util.hpp -- error reporting, device scopes and the ragged-span ring shared by the translation units of the C ABI (capi.cpp,
+// capi_consumers.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>

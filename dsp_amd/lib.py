@@ -256,7 +256,8 @@ def c_offsets(offsets):
     """offsets[n_clips + 1] (any integer sequence) -> (ctypes long array, n_clips) for the *_ragged_* entry points."""
     import numpy as np
     a = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    assert a.ndim == 1 and a.size >= 1, "offsets must hold n_clips + 1 positions"
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError("offsets must hold n_clips + 1 positions")
     return (C.c_long * a.size)(*a.tolist()), a.size - 1
 
 

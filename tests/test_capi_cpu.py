@@ -209,3 +209,71 @@ def test_ragged_batches_are_ordered_for_an_even_deal():
     lab = (C.c_int * 2)()
     assert lib.dsp_classify_batch_ragged_host(None, None, 2, c_back, lab, None) == -1
     assert lib.dsp_classify_batch_ragged_host_f64(None, None, 2, c_back, lab, None) == -1
+
+
+CLASSIFY_BATCH_ENTRIES = [
+    "dsp_classify_batch_host", "dsp_classify_batch_host_cfg", "dsp_classify_batch_pcm16_host", "dsp_classify_batch_device",
+    "dsp_classify_batch_device_cfg", "dsp_classify_batch_device_ctx", "dsp_classify_batch_pcm16_device", "dsp_classify_batch_ragged_device",
+    "dsp_classify_batch_ragged_pcm16_device", "dsp_classify_batch_ragged_host", "dsp_classify_batch_ragged_pcm16_host",
+    "dsp_classify_batch_host_f64", "dsp_classify_batch_device_f64", "dsp_classify_batch_pcm16_host_f64", "dsp_classify_batch_pcm16_device_f64",
+    "dsp_classify_batch_ragged_device_f64", "dsp_classify_batch_ragged_pcm16_device_f64", "dsp_classify_batch_ragged_host_f64",
+    "dsp_classify_batch_ragged_pcm16_host_f64",
+]
+
+
+def _classify_batch_call(name, signal, n_clips, n=16000, cfg=None, channels=1, stereo_mode=0):
+    """Calls one dsp_classify_batch_* entry with its argument list assembled from the name (NULL context, trace and stream)."""
+    off, _ = dl.c_offsets(np.arange(n_clips + 1, dtype=np.int64) * n)
+    labels = (C.c_int * max(n_clips, 1))()
+    device, f64 = "_device" in name, name.endswith("_f64")
+    args = [None] if name.endswith("_ctx") else []
+    if name not in ("dsp_classify_batch_host", "dsp_classify_batch_device"):
+        args.append(None if cfg is None else C.byref(cfg))
+    args += [signal, n_clips] + ([off] if "_ragged" in name else [n, n])
+    args += [channels, stereo_mode] if "_pcm16" in name else []
+    args += [labels] + ([None] if f64 or not device else []) + ([None] if device else [])
+    return getattr(dl.load(), name)(*args)
+
+
+def test_classify_batch_entries_refuse_bad_arguments_before_any_device_call():
+    assert len(CLASSIFY_BATCH_ENTRIES) == 19
+    buf = np.zeros(16000 * 2 * 2, np.float64)                  # room for two clips of any input kind
+    for name in CLASSIFY_BATCH_ENTRIES:
+        assert _classify_batch_call(name, None, 1) == -1, name
+        if name not in ("dsp_classify_batch_host", "dsp_classify_batch_device"):
+            bad = dl.ClassifyConfigF64(0.9, 0.8, 45.0, 75.0, 300.0, 100.0) if name.endswith("_f64") else dsp_amd.classify_config((0.9, 0.8, 70.0, 100.0, 200.0, 80.0))
+            assert _classify_batch_call(name, buf.ctypes.data, 1, cfg=bad) == -1, name
+            if not name.endswith("_ctx"):                      # (a NULL context is refused first)
+                assert "keep_lo" in dl.last_error(), (name, dl.last_error())
+        if "_pcm16" in name:
+            assert _classify_batch_call(name, buf.ctypes.data, 1, channels=3) == -1 and "channels" in dl.last_error(), name
+            assert _classify_batch_call(name, buf.ctypes.data, 1, channels=2, stereo_mode=7) == -1 and "stereo_mode" in dl.last_error(), name
+
+
+def test_classify_host_entries_take_zero_clips_without_a_device():
+    buf = np.zeros(16, np.float64)
+    hosts = [name for name in CLASSIFY_BATCH_ENTRIES if "_device" not in name]
+    assert len(hosts) == 9
+    for name in hosts:
+        assert _classify_batch_call(name, buf.ctypes.data, 0) == 0, (name, dl.last_error())
+
+
+def test_ragged_wrappers_refuse_offsets_past_the_buffer_under_python_optimize():
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np, dsp_amd\n"
+            "assert not __debug__\n"
+            "for fn, dt in ((dsp_amd.classify_ragged, np.float32), (dsp_amd.classify_ragged_f64, np.float64), (dsp_amd.classify_ragged, np.int16)):\n"
+            "    try:\n"
+            "        fn(np.zeros(1000, dt), [0, 600, 1200])\n"
+            "    except ValueError as e:\n"
+            "        assert 'past the end' in str(e), e\n"
+            "    else:\n"
+            "        raise SystemExit('no ValueError from ' + fn.__name__)\n"
+            "try:\n"
+            "    dsp_amd.classify_ragged(np.zeros(1000, np.float32), [[0, 600]])\n"
+            "except ValueError:\n"
+            "    print('ok')\n") % ROOT
+    r = subprocess.run([sys.executable, "-O", "-s", "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
