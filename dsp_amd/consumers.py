@@ -158,6 +158,26 @@ class SpeakerModel:
                                                   _stream(mfcc)), "dsp_speaker_llr_device")
         return (mean, label, lt, lu) if per_frame else (mean, label)
 
+    def llr_ragged(self, mfcc, frame_offsets, per_frame: bool = False):
+        """The same per clip of a ragged MFCC matrix (MfccPlan.clips_ragged): mfcc cuda float32 [F][d], clip c = rows
+        [frame_offsets[c], frame_offsets[c + 1]), every clip >= 1 row -> (llr_mean int64 [n], label int32 [n][, ll_target, ll_ubm int64 [F]])."""
+        import torch
+        fo = np.ascontiguousarray(np.asarray(frame_offsets, dtype=np.int64))
+        if fo.ndim != 1 or fo.size < 1:
+            raise ValueError("frame_offsets must hold n_clips + 1 rows")
+        if mfcc.dim() != 2 or mfcc.shape[1] != self.d or int(fo[-1]) > mfcc.shape[0]:
+            raise ValueError(f"mfcc must be [F][{self.d}] with F >= frame_offsets[-1]")
+        mfcc = mfcc.contiguous()
+        n, rows = fo.size - 1, int(fo[-1])
+        mean = torch.empty(n, dtype=torch.int64, device=mfcc.device)
+        label = torch.empty(n, dtype=torch.int32, device=mfcc.device)
+        lt = torch.empty(rows, dtype=torch.int64, device=mfcc.device) if per_frame else None
+        lu = torch.empty(rows, dtype=torch.int64, device=mfcc.device) if per_frame else None
+        _lib.check(self._L.dsp_speaker_llr_ragged_device(self._h, mfcc.data_ptr(), n, fo.ctypes.data_as(C.POINTER(C.c_long)), mean.data_ptr(),
+                                                         label.data_ptr(), lt.data_ptr() if per_frame else None,
+                                                         lu.data_ptr() if per_frame else None, _stream(mfcc)), "dsp_speaker_llr_ragged_device")
+        return (mean, label, lt, lu) if per_frame else (mean, label)
+
 
 def upsample_linear(x, new_size: int):
     """x: cuda float32 [n_clips][old] (or [old]) -> [n_clips][new_size]; numpy input goes through the host entry point."""

@@ -438,41 +438,89 @@ static int reserve(float **buf, size_t *cap, size_t need)
     return DSP_OK;
 }
 
+// A ragged batch for run(): clip c = samples [offsets[c], offsets[c + 1]) per channel, frame_offsets[c] its first output row (prefix sums of
+// the clips' frame counts), n_spans the clips with at least one frame.
+struct RaggedBatch {
+    const long *offsets, *frame_offsets;
+    long n_clips, n_spans;
+};
+
+// ragged: the spans (caller's order, clips of >= 1 frame, ClipSpan::frame0 = first output row) and behind them the chunk table of the
+// kernels' RaggedCursor (built on the device for `chunk`), in a ring slot; *slot is set once the upload is enqueued (mark it after the
+// last kernel that reads it)
+static int ragged_mfcc_spans(dsp_mfcc_plan *p, const RaggedBatch &rg, long n_frames, int chunk, dsp::SpanRing::Slot **slot, void *stream)
+{
+    const size_t span_bytes = (size_t)rg.n_spans * sizeof(dsp::ClipSpan);
+    const long n_chunks = (n_frames + chunk - 1) / chunk;
+    dsp::SpanRing::Slot *s = nullptr;
+    DSP_HIP(p->spans.acquire(span_bytes + (size_t)n_chunks * sizeof(int), &s));
+    auto *h = static_cast<dsp::ClipSpan *>(s->h);
+    long j = 0;
+    for (long c = 0; c < rg.n_clips; ++c) {
+        const int frames = (int)(rg.frame_offsets[c + 1] - rg.frame_offsets[c]);
+        if (frames > 0) h[j++] = dsp::ClipSpan{rg.offsets[c], (int)(rg.offsets[c + 1] - rg.offsets[c]), frames, c, rg.frame_offsets[c]};
+    }
+    DSP_HIP(dsp::SpanRing::upload(s, span_bytes, (hipStream_t)stream));
+    *slot = s;
+    auto *d = static_cast<const dsp::ClipSpan *>(s->d);
+    DSP_HIP(dsp::launch_ragged_chunk_map(d, rg.n_spans, chunk, reinterpret_cast<int *>(static_cast<char *>(s->d) + span_bytes), (hipStream_t)stream));
+    return DSP_OK;
+}
+
+// marks a ring slot on every exit once it is set
+struct SlotMark {
+    dsp::SpanRing::Slot *slot = nullptr;
+    hipStream_t stream;
+    explicit SlotMark(void *st) : stream((hipStream_t)st) {}
+    ~SlotMark() { if (slot) dsp::SpanRing::mark(slot, stream); }
+};
+
+// rg != nullptr: a ragged batch (frames_per_clip = 0, clip_stride unused): the clip-mode kernels with the RaggedCursor
 static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, int frames_per_clip,
-               long clip_stride, void *stream, int in_kind = 0, bool fused_prefilter = false, int samples_per_clip = 0)
+               long clip_stride, void *stream, int in_kind = 0, bool fused_prefilter = false, int samples_per_clip = 0,
+               const RaggedBatch *rg = nullptr)
 {
     if (n_frames == 0) return DSP_OK;
     DSP_ON_DEVICE(p->device);       // the caller's current device may be another GPU: tables and workspaces live on the plan's
+    const bool clip_mode = frames_per_clip > 0 || rg;
     const bool single_clip = frames_per_clip > 0 && n_frames == frames_per_clip;   // stride unused
     if ((reinterpret_cast<uintptr_t>(d_in) & (in_kind == 1 ? 3 : 7)) || (!single_clip && (clip_stride & 1)))
         return fail(DSP_EINVAL, "input must be 8-byte aligned (4 for mono int16) with an even clip stride");
     const bool aub2048 = p->cfg.n_fft == 2048 && (p->cfg.spectrum != DSP_SPECTRUM_POWER || p->cfg.log_mode == DSP_LOG_LOG10_FLOOR || p->cfg.framing == DSP_FRAMING_STREAM);
-    if (in_kind != 0 && !(aub2048 && frames_per_clip > 0) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
+    if (in_kind != 0 && !(aub2048 && clip_mode) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
         return fail(DSP_EINVAL, "PCM16 ingestion runs on the 512-point wave-per-frame kernel (per-frame log mode) and on the 2048-point scrubjay_infer.c front end");
+    SlotMark span_slot(stream);
     if (p->cfg.n_fft == 2048) {
         dsp::Mfcc512Args a{};
         a.in = d_in; a.in_kind = in_kind; a.out = d_out; a.n_frames = n_frames; a.clip_stride = clip_stride; a.frames_per_clip = frames_per_clip;
         a.hop = p->cfg.hop_length; a.frame_len = p->cfg.frame_length; a.chunk = p->chunk > 0 ? p->chunk : 8;
         a.n_mels = p->cfg.n_mels; a.n_mfcc = p->cfg.n_mfcc; a.amin = p->cfg.amin; a.top_db = p->cfg.top_db;
         a.spectrum = p->cfg.spectrum;
-        a.stream_framing = frames_per_clip > 0 && p->cfg.framing == DSP_FRAMING_STREAM;
+        a.stream_framing = clip_mode && p->cfg.framing == DSP_FRAMING_STREAM;
         a.samples_per_clip = samples_per_clip;
-        if (a.stream_framing && samples_per_clip <= 0) return fail(DSP_EINVAL, "internal: stream framing without the clip length");
+        if (a.stream_framing && samples_per_clip <= 0 && !rg) return fail(DSP_EINVAL, "internal: stream framing without the clip length");
+        if (rg) {
+            int rc;
+            if ((rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, &span_slot.slot, stream)) < 0) return rc;
+            a.spans = static_cast<const dsp::ClipSpan *>(span_slot.slot->d);
+            a.n_clips = rg->n_spans;
+        }
         const int per_cu = p->blocks_per_cu > 0 ? p->blocks_per_cu : p->resident_blocks_2048;
         const long chunks = (n_frames + a.chunk - 1) / a.chunk;
         const long blocks = std::max(1L, std::min((long)p->n_cu * per_cu, (chunks + 3) / 4));
         a.log_mode = p->cfg.log_mode;
-        if (a.log_mode == DSP_LOG_GLOBAL_REF1 && frames_per_clip > 0) {
+        if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) {
             // clip-global top_db, as for n_fft = 512 below: pass 1 writes each frame's maximum, a tiny kernel turns them into one
             // floor per clip, pass 2 is the normal kernel clipping at that floor
-            const long n_clips = n_frames / frames_per_clip;
+            const long n_clips = rg ? rg->n_spans : n_frames / frames_per_clip;
             int rc;
             std::lock_guard<std::recursive_mutex> lock(p->mu);
             if ((rc = reserve(&p->d_frame_max, &p->frame_max_cap, (size_t)n_frames * sizeof(float))) < 0) return rc;
             if ((rc = reserve(&p->d_clip_floor, &p->clip_floor_cap, (size_t)n_clips * sizeof(float))) < 0) return rc;
             a.frame_max = p->d_frame_max;
             DSP_HIP(dsp::launch_mfcc2048(a, p->d_tables2048, (int)blocks, (hipStream_t)stream, false));
-            DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
+            if (rg) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, (hipStream_t)stream));
+            else DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
             a.frame_max = nullptr;
             a.clip_floor = p->d_clip_floor;
         }
@@ -513,6 +561,12 @@ static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, 
     a.log_mode = p->cfg.log_mode;
     a.frame_max = nullptr;
     a.clip_floor = nullptr;
+    if (rg) {
+        int rc;
+        if ((rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, &span_slot.slot, stream)) < 0) return rc;
+        a.spans = static_cast<const dsp::ClipSpan *>(span_slot.slot->d);
+        a.n_clips = rg->n_spans;
+    }
     // persistent-style grid: exactly the 4-wave blocks the chip holds at once (one
     // extra block per CU would run as a second, mostly idle round: measured +14 %),
     // never more blocks than there are chunks of work
@@ -522,17 +576,18 @@ static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, 
     long blocks = (long)p->n_cu * per_cu;
     const long chunks = (n_frames + a.chunk - 1) / a.chunk;
     blocks = std::max(1L, std::min(blocks, (chunks + 3) / 4));
-    if (a.log_mode == DSP_LOG_GLOBAL_REF1 && frames_per_clip > 0) {
+    if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) {
         // clip-global top_db: pass 1 writes each frame's maximum, a tiny kernel turns them into one
         // floor per clip, pass 2 is the normal kernel clipping at that floor
-        const long n_clips = n_frames / frames_per_clip;
+        const long n_clips = rg ? rg->n_spans : n_frames / frames_per_clip;
         int rc;
         std::lock_guard<std::recursive_mutex> lock(p->mu);
         if ((rc = reserve(&p->d_frame_max, &p->frame_max_cap, (size_t)n_frames * sizeof(float))) < 0) return rc;
         if ((rc = reserve(&p->d_clip_floor, &p->clip_floor_cap, (size_t)n_clips * sizeof(float))) < 0) return rc;
         a.frame_max = p->d_frame_max;
         DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, false));
-        DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
+        if (rg) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, (hipStream_t)stream));
+        else DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
         a.frame_max = nullptr;
         a.clip_floor = p->d_clip_floor;
         DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, false));
@@ -617,6 +672,68 @@ int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, long n_c
     return rc < 0 ? rc : t;
 }
 
+// ---- ragged MFCC matrices: clips of different lengths in one launch, their matrices back to back ----
+
+// host only: frame_offsets[c + 1] = frame_offsets[c] + the frames of clip c; the total, or < 0 (offsets not non-decreasing)
+static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets, long n_clips, int max_frames, long *frame_offsets, int *t_max)
+{
+    frame_offsets[0] = 0;
+    int tm = 0;
+    for (long c = 0; c < n_clips; ++c) {
+        const long n = offsets[c + 1] - offsets[c];
+        if (offsets[c] < 0 || n < 0 || n > INT32_MAX)
+            return fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples (clip " + std::to_string(c) + ")");
+        const int t = dsp_mfcc_frames_for(&cfg, (int)n, max_frames);
+        frame_offsets[c + 1] = frame_offsets[c] + t;
+        tm = std::max(tm, t);
+    }
+    if (t_max) *t_max = tm;
+    return frame_offsets[n_clips];
+}
+
+long dsp_mfcc_ragged_frame_offsets(const dsp_mfcc_config *cfg, const long *offsets, long n_clips, int max_frames, long *frame_offsets)
+{
+    if (!cfg || !offsets || !frame_offsets || n_clips < 0) return fail(DSP_EINVAL, "bad argument (cfg, offsets, frame_offsets non-NULL, n_clips >= 0)");
+    std::string why;
+    if (!valid_cfg(*cfg, why)) return fail(DSP_EINVAL, why);
+    return ragged_frame_offsets(*cfg, offsets, n_clips, max_frames, frame_offsets, nullptr);
+}
+
+// in_kind as run(); returns the frames of the longest clip
+static int mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, const long *offsets, int max_frames, float *d_out,
+                             void *stream)
+{
+    if (!p || n_clips < 0 || !offsets) return fail(DSP_EINVAL, "bad argument");
+    if (p->cfg.prefilter != DSP_PREFILTER_NONE) return fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
+    if (p->cfg.n_fft == 1024) return fail(DSP_EINVAL, "ragged MFCC matrices run on the 512- and 2048-point kernels: n_fft 1024 is not supported");
+    if (p->cfg.n_fft == 512 && p->kernel != DSP_KERNEL_WAVE && p->kernel != DSP_KERNEL_WAVE_FRAME)
+        return fail(DSP_EINVAL, "ragged MFCC matrices run on the wave-per-frame kernels (DSP_KERNEL_WAVE / DSP_KERNEL_WAVE_FRAME)");
+    if (n_clips >= (1L << 31)) return fail(DSP_EINVAL, "too many clips");
+    std::vector<long> fo((size_t)n_clips + 1);
+    int t_max = 0;
+    const long total = ragged_frame_offsets(p->cfg, offsets, n_clips, max_frames, fo.data(), &t_max);
+    if (total < 0) return (int)total;
+    if (total == 0) return 0;
+    if (!d_in || !d_out) return fail(DSP_EINVAL, "NULL buffer");
+    RaggedBatch rg{offsets, fo.data(), n_clips, 0};
+    for (long c = 0; c < n_clips; ++c) rg.n_spans += fo[(size_t)c + 1] > fo[(size_t)c];
+    const int rc = run(p, d_in, d_out, total, 0, 0, stream, in_kind, false, 0, &rg);
+    return rc < 0 ? rc : t_max;
+}
+
+int dsp_mfcc_clips_ragged_device(dsp_mfcc_plan *p, const float *d_signal, long n_clips, const long *offsets, int max_frames, float *d_out, void *stream)
+{
+    return mfcc_clips_ragged(p, d_signal, 0, n_clips, offsets, max_frames, d_out, stream);
+}
+
+int dsp_mfcc_clips_ragged_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, long n_clips, const long *offsets, int channels, int stereo_mode,
+                                       int max_frames, float *d_out, void *stream)
+{
+    if (channels != 1 && channels != 2) return fail(DSP_EINVAL, "bad argument (channels 1 or 2)");
+    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
+    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
+    return mfcc_clips_ragged(p, d_pcm, kind, n_clips, offsets, max_frames, d_out, stream);
+}
 
 int dsp_mfcc_frames_host(dsp_mfcc_plan *p, const float *frames, long n_frames, float *out)
 {

@@ -41,6 +41,7 @@ struct dsp_speaker_model {
     int device = 0;
     dsp::GmmDev target{}, ubm{};
     void *d_blob = nullptr;
+    dsp::SpanRing rows;      // dsp_speaker_llr_ragged_device: the frame offsets on their way to the GPU (capi_util.hpp)
 };
 
 extern "C" {
@@ -304,6 +305,7 @@ void dsp_speaker_model_destroy(dsp_speaker_model *m)
     if (!m) return;
     dsp::DeviceScope dsp_device_scope_(m->device);
     if (m->d_blob) hipFree(m->d_blob);
+    m->rows.release();
     delete m;
 }
 
@@ -315,6 +317,31 @@ int dsp_speaker_llr_device(dsp_speaker_model *m, const float *d_mfcc, long n_cli
     DSP_CAPI_HIP(dsp::launch_speaker_llr(m->target, m->ubm, d_mfcc, n_clips, frames_per_clip, threshold,
                                          reinterpret_cast<long long *>(d_llr_mean), d_labels, reinterpret_cast<long long *>(d_ll_target),
                                          reinterpret_cast<long long *>(d_ll_ubm), (hipStream_t)stream));
+    return DSP_OK;
+}
+
+int dsp_speaker_llr_ragged_device(dsp_speaker_model *m, const float *d_mfcc, long n_clips, const long *frame_offsets, int64_t *d_llr_mean,
+                                  int *d_labels, int64_t *d_ll_target, int64_t *d_ll_ubm, void *stream)
+{
+    if (!m || n_clips < 0 || (n_clips > 0 && (!frame_offsets || !d_mfcc || !d_llr_mean))) return capi_fail(DSP_EINVAL, "bad argument");
+    if (n_clips == 0) return DSP_OK;
+    if (frame_offsets[0] < 0) return capi_fail(DSP_EINVAL, "frame_offsets must be non-negative");
+    for (long c = 0; c < n_clips; ++c)
+        if (frame_offsets[c + 1] <= frame_offsets[c])
+            return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " of the ragged MFCC matrix has no frames (the LLR is a mean over the clip's frames)");
+    DSP_ON_DEVICE(m->device);
+    const size_t bytes = (size_t)(n_clips + 1) * sizeof(long);
+    dsp::SpanRing::Slot *slot = nullptr;
+    DSP_CAPI_HIP(m->rows.acquire(bytes, &slot));
+    std::memcpy(slot->h, frame_offsets, bytes);
+    const hipError_t up = dsp::SpanRing::upload(slot, bytes, (hipStream_t)stream);
+    const long long threshold = (long long)(-0.7 * (1 << 8));                              // speaker_gmm.c:124-125
+    const hipError_t e = up != hipSuccess ? up
+                         : dsp::launch_speaker_llr_ragged(m->target, m->ubm, d_mfcc, n_clips, static_cast<const long *>(slot->d), threshold,
+                                                          reinterpret_cast<long long *>(d_llr_mean), d_labels, reinterpret_cast<long long *>(d_ll_target),
+                                                          reinterpret_cast<long long *>(d_ll_ubm), (hipStream_t)stream);
+    dsp::SpanRing::mark(slot, (hipStream_t)stream);
+    DSP_CAPI_HIP(e);
     return DSP_OK;
 }
 

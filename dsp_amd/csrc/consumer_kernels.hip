@@ -148,6 +148,55 @@ hipError_t launch_speaker_llr(const GmmDev &target, const GmmDev &ubm, const flo
     return hipGetLastError();
 }
 
+// ragged MFCC matrix (dsp_mfcc_clips_ragged_device): clip c is rows [frame_offsets[c], frame_offsets[c + 1]) of mfcc, every clip >= 1 row
+// (the host checked); one wave per clip, the same integer arithmetic and truncating mean as speaker_llr_kernel, per-frame outputs by row
+__global__ __launch_bounds__(256) void speaker_llr_ragged_kernel(const GmmDev target, const GmmDev ubm, const float *__restrict__ mfcc,
+                                                                 long n_clips, const long *__restrict__ frame_offsets, long long threshold,
+                                                                 long long *__restrict__ llr_mean, int *__restrict__ labels,
+                                                                 long long *__restrict__ ll_target, long long *__restrict__ ll_ubm)
+{
+    __shared__ GmmLds gt, gu;
+    for (int i = threadIdx.x; i < target.k * target.d; i += 256) {
+        gt.means[i] = target.means[i]; gt.inv_covs[i] = target.inv_covs[i];
+        gu.means[i] = ubm.means[i]; gu.inv_covs[i] = ubm.inv_covs[i];
+    }
+    for (int i = threadIdx.x; i < target.k; i += 256) { gt.log_consts[i] = target.log_consts[i]; gu.log_consts[i] = ubm.log_consts[i]; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long clip = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (clip >= n_clips) return;
+    const int d_n = target.d;
+    const long r0 = frame_offsets[clip], r1 = frame_offsets[clip + 1];
+    long long sum = 0;
+    for (long r = r0 + lane; r < r1; r += 64) {
+        const float *f = mfcc + r * d_n;
+        int x[kGmmMaxD];
+#pragma unroll
+        for (int d = 0; d < kGmmMaxD; ++d) x[d] = d < d_n ? (int)(short)(int)(f[d] * 64.0f) : 0;   // low 16 bits of the int32 truncation
+        const long long lt = gmm_ll(gt, target.k, d_n, x), lu = gmm_ll(gu, ubm.k, d_n, x);
+        if (ll_target) ll_target[r] = lt;
+        if (ll_ubm) ll_ubm[r] = lu;
+        sum += lt - lu;                                                                           // :104-108
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) {
+        const long long mean = sum / (long long)(r1 - r0);                                        // :135
+        llr_mean[clip] = mean;
+        if (labels) labels[clip] = mean > threshold ? 1 : 0;                                      // :138-141
+    }
+}
+
+hipError_t launch_speaker_llr_ragged(const GmmDev &target, const GmmDev &ubm, const float *mfcc, long n_clips, const long *frame_offsets,
+                                     long long threshold, long long *llr_mean, int *labels, long long *ll_target, long long *ll_ubm,
+                                     hipStream_t stream)
+{
+    if (n_clips <= 0) return hipSuccess;
+    if (target.d != ubm.d || target.k != ubm.k || target.d > kGmmMaxD || target.k > kGmmMaxK) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(speaker_llr_ragged_kernel, dim3((unsigned)((n_clips + 3) / 4)), dim3(256), 0, stream, target, ubm, mfcc, n_clips,
+                       frame_offsets, threshold, llr_mean, labels, ll_target, ll_ubm);
+    return hipGetLastError();
+}
+
 // ---- linear resampler ----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void upsample_linear_kernel(const float *__restrict__ in, long n_clips, int old_size, long in_stride,
                                                               float *__restrict__ out, int new_size, long out_stride)

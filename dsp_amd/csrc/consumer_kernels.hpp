@@ -42,6 +42,12 @@ hipError_t launch_speaker_llr(const GmmDev &target, const GmmDev &ubm, const flo
                               long long threshold, long long *llr_mean, int *labels, long long *ll_target,
                               long long *ll_ubm, hipStream_t stream);
 
+// the same per clip of a ragged MFCC matrix: clip c = rows [frame_offsets[c], frame_offsets[c + 1]) (device array, every clip >= 1 row);
+// ll_target / ll_ubm [frame_offsets[n_clips]] by row
+hipError_t launch_speaker_llr_ragged(const GmmDev &target, const GmmDev &ubm, const float *mfcc, long n_clips, const long *frame_offsets,
+                                     long long threshold, long long *llr_mean, int *labels, long long *ll_target, long long *ll_ubm,
+                                     hipStream_t stream);
+
 // out[c][i] = in[c][lo] + (in[c][hi] - in[c][lo]) * frac, the reference's fp32 operation order
 hipError_t launch_upsample_linear(const float *in, long n_clips, int old_size, long in_stride, float *out, int new_size,
                                   long out_stride, hipStream_t stream);

@@ -109,10 +109,12 @@ __device__ __forceinline__ float load_one_2048(const void *base, long i)
     else return (float)((int)static_cast<const short *>(base)[2 * i] + (int)static_cast<const short *>(base)[2 * i + 1]) * (1.0f / 65536.0f);
 }
 
-template <bool CLIPS, bool POOL, bool AUB = false, int IN = 0>
+// RAGGED (CLIPS, !POOL): clips of different lengths, frame g of the batch to out[g]; clip, t and samples from args.spans (RaggedCursor)
+template <bool CLIPS, bool POOL, bool AUB = false, int IN = 0, bool RAGGED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mfcc2048_kernel(const Mfcc512Args args, const GenTables2048 *__restrict__ G)
 {
     static_assert(!POOL || CLIPS, "pooling is per clip");
+    static_assert(!RAGGED || (CLIPS && !POOL), "ragged batches: clip mode, coefficients stored");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -185,8 +187,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
     (void)feat;
 
     // (the fused clip kernel walks whole clips, uniform or ragged: ClipCursor)
-    std::conditional_t<POOL, ClipCursor, WaveCursor<CLIPS>> cur;
+    // (ragged clips: RaggedCursor)
+    std::conditional_t<POOL, ClipCursor, std::conditional_t<RAGGED, RaggedCursor, WaveCursor<CLIPS>>> cur;
     if constexpr (POOL) cur.init(wave, n_waves, args.n_clips, args.frames_per_clip, args.hop, args.clip_stride, args.spans, args.samples_per_clip);
+    else if constexpr (RAGGED) cur.init(wave, n_waves, args.chunk, args.n_frames, args.hop, args.spans, args.n_clips);
     else cur.init(wave, n_waves, args.chunk, args.n_frames, args.frames_per_clip, CLIPS ? args.hop : frame_len, args.clip_stride);
     if (!cur.valid()) return;
 
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
             src += args.hop - frame_len;                                 // cur.off = clip_off + t * hop
             lo_i = start < 0 ? -start : 0;
             int n_clip = args.samples_per_clip;                          // ragged batches: the clip's own length
-            if constexpr (POOL) n_clip = cur.n_samples;
+            if constexpr (POOL || RAGGED) n_clip = cur.n_samples;
             hi_i = min(frame_len, n_clip - start);
         }
 #pragma unroll
@@ -503,11 +507,11 @@ static size_t lds_bytes_2048(int n_mels, bool pool, bool aub) { return (size_t)q
 
 hipError_t launch_mfcc2048(const Mfcc512Args &args, const GenTables2048 *tables, int blocks, hipStream_t stream, bool pool)
 {
-    const bool clips = args.frames_per_clip > 0;
+    const bool clips = args.frames_per_clip > 0 || args.spans;
     const dim3 g(blocks), b(256);
     const bool aub = args.spectrum != 0 || args.log_mode == 2 || args.stream_framing != 0;
     const size_t Q_BLOCK_BYTES = lds_bytes_2048(args.n_mels, pool, aub);
-    if (args.stream_framing && (!clips || (args.samples_per_clip <= 0 && !(pool && args.spans)) || args.hop > args.frame_len)) return hipErrorInvalidConfiguration;      // (ragged: lengths in the spans)
+    if (args.stream_framing && (!clips || (args.samples_per_clip <= 0 && !args.spans) || args.hop > args.frame_len)) return hipErrorInvalidConfiguration;      // (ragged: lengths in the spans)
     if (args.in_kind != 0 && (!aub || !clips || args.in_kind < 0 || args.in_kind > 3)) return hipErrorInvalidConfiguration;      // int16: the scrubjay_infer.c front end, clips
     if (pool) {
         if (!clips || args.chunk != args.frames_per_clip || !args.pool.labels || args.pool.svm.n_features != 2 * args.n_mfcc ||
@@ -518,6 +522,13 @@ hipError_t launch_mfcc2048(const Mfcc512Args &args, const GenTables2048 *tables,
         else if (aub && args.in_kind == 3) hipLaunchKernelGGL((mfcc2048_kernel<true, true, true, 3>), g, b, Q_BLOCK_BYTES, stream, args, tables);
         else if (aub) hipLaunchKernelGGL((mfcc2048_kernel<true, true, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
         else hipLaunchKernelGGL((mfcc2048_kernel<true, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+    } else if (args.spans) {
+        if (args.n_clips <= 0) return hipErrorInvalidConfiguration;
+        if (aub && args.in_kind == 1) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 1, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        else if (aub && args.in_kind == 2) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 2, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        else if (aub && args.in_kind == 3) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 3, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        else if (aub) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 0, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        else hipLaunchKernelGGL((mfcc2048_kernel<true, false, false, 0, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
     } else if (clips) {
         if (aub && args.in_kind == 1) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 1>), g, b, Q_BLOCK_BYTES, stream, args, tables);
         else if (aub && args.in_kind == 2) hipLaunchKernelGGL((mfcc2048_kernel<true, false, true, 2>), g, b, Q_BLOCK_BYTES, stream, args, tables);

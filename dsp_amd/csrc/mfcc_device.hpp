@@ -252,6 +252,61 @@ struct WaveCursor {
     }
 };
 
+// Cursor of the wave-per-frame kernels over a RAGGED batch (dsp_mfcc_clips_ragged_device): the same deal of chunks of global frames to
+// the waves as WaveCursor, so frame g still goes to out[g]; what changes is the map from g to (clip, t, first sample), which comes from
+// the clips' spans (caller's order, clips of >= 1 frame only, ClipSpan::frame0 = first output frame) instead of arithmetic on a uniform
+// clip.  At a chunk's start ONE entry of chunk_span (the span frame chunk_k * chunk lies in, built on the device before the launch:
+// launch_ragged_chunk_map) and that span; inside a chunk a compare per frame, and the next span's load when the clip ends.  No division,
+// no search; every member is wave-uniform (SGPRs).  Same members as WaveCursor where the kernels read them, and the clip's samples as
+// ClipCursor has them (stream framing).
+struct RaggedCursor {
+    long f, off, clip;           // frame, its first sample, its span; meaningful while valid()
+    const ClipSpan *spans;
+    const int *chunk_span;
+    int chunk_k, n_waves;        // index of the current chunk (first frame chunk_k * chunk); chunks advance by n_waves
+    int remaining;               // frames this wave still has to visit, f included
+    int left, chunk;             // frames of the chunk still to come after f
+    int t, clip_left;            // frame in clip; frames of the clip still to come after f
+    int hop, n_samples;          // samples between frames; samples of the clip
+    __device__ __forceinline__ void enter(const ClipSpan &s)
+    {
+        t = (int)(f - s.frame0);
+        off = s.off + (long)t * hop;
+        clip_left = s.frames - 1 - t;
+        n_samples = s.n;
+    }
+    __device__ __forceinline__ void init(long wave, long n_waves_, int chunk_, long n, int hop_, const ClipSpan *spans_, long n_spans)
+    {
+        chunk = chunk_; hop = hop_; n_waves = (int)n_waves_; spans = spans_;
+        chunk_span = reinterpret_cast<const int *>(spans_ + n_spans);       // the chunk table lies behind the spans
+        chunk_k = (int)wave;
+        left = chunk - 1;
+        const long n_chunks = (n + chunk - 1) / chunk;
+        const long mine = wave < n_chunks ? (n_chunks - 1 - wave) / n_waves_ + 1 : 0;
+        const bool owns_last = mine > 0 && (n_chunks - 1 - wave) % n_waves_ == 0;
+        remaining = (int)(mine * chunk - (owns_last ? n_chunks * chunk - n : 0));
+        f = (long)chunk_k * chunk; off = 0; clip = 0; t = 0; clip_left = 0; n_samples = 0;
+        if (remaining > 0) { clip = chunk_span[chunk_k]; enter(spans[clip]); }
+    }
+    __device__ __forceinline__ bool valid() const { return remaining > 0; }
+    __device__ __forceinline__ void next()
+    {
+        if (--remaining <= 0) return;              // (no load past the batch's last span)
+        if (left > 0 && clip_left > 0) {           // the common step: next frame of the clip
+            --left; ++f; --clip_left; ++t; off += hop;
+            return;
+        }
+        if (left > 0) { --left; ++f; ++clip; }     // frame 0 of the next clip (compacted: it has one)
+        else {                                     // the wave's next chunk
+            left = chunk - 1;
+            chunk_k += n_waves;
+            f = (long)chunk_k * chunk;
+            clip = chunk_span[chunk_k];
+        }
+        enter(spans[clip]);
+    }
+};
+
 // Cursor of the fused clip kernels (one wavefront walks one clip from its first frame to its last; clips dealt round-robin to the
 // waves).  Uniform batches: clip c starts at c * clip_stride and has fpc frames; ragged batches (spans != nullptr): start, samples and
 // frame count come from the clip's ClipSpan, one scalar load per clip -- the HOST has put the spans in an order that makes the fixed

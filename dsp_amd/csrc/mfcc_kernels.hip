@@ -171,13 +171,16 @@ __device__ __forceinline__ c32 unpack_pcm16(c32 raw)
 // POOL (TILE, CLIPS, chunk = frames per clip: one wavefront walks one clip): instead of storing the coefficients the
 // tile epilogue pools them per clip and the clip ends with the SVM (PoolSvmArgs) -- BASELINE config 5 in one kernel.
 // POOL = 2: the epilogue feeds the stop-word net instead (StopNetArgs): classify_signal (stop_detector.c:12-55) in one kernel.
-template <int DCT_SPLIT, int DCT_LEN, int GATHER, int FLEN, int IN, int TILE, bool CLIPS, int POOL = 0>
+// RAGGED (CLIPS, POOL = 0): clips of different lengths, frame g of the batch to out[g] as in clip mode; the frames' clips and samples
+// come from args.spans (RaggedCursor) -- dsp_mfcc_clips_ragged_device.
+template <int DCT_SPLIT, int DCT_LEN, int GATHER, int FLEN, int IN, int TILE, bool CLIPS, int POOL = 0, bool RAGGED = false>
 #ifndef DSP_WAVES_PER_EU
 #define DSP_WAVES_PER_EU 4
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_PER_EU))) void mfcc512_wave_kernel(const Mfcc512Args args)
 {
     static_assert(!POOL || (TILE && CLIPS), "pooling lives in the tile epilogue of the clip-mode kernel");
+    static_assert(!RAGGED || (CLIPS && !POOL), "ragged batches: clip mode, coefficients stored");
     constexpr int KS = DCT_SPLIT == 2 ? DCT_LEN / 2 : DCT_LEN;    // MFMA k-steps (4 mel filters each)
     constexpr int CT = DCT_SPLIT == 2 ? 2 : 1;                    // 16-coefficient output tiles
     constexpr int WAVE_BYTES = LDS_WAVE_BYTES + (TILE ? LDS_TILE_BYTES : 0) + (POOL == 1 ? LDS_POOL_BYTES : (POOL == 2 ? LDS_STOP_BYTES : 0));
@@ -281,8 +284,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
     // and issues their loads; the frame index (and clip) of each ring buffer waits in `fq`
     // until the frame is consumed, so the consumer side needs no cursor of its own.
     // (the fused clip kernels walk whole clips, uniform or ragged: ClipCursor)
-    std::conditional_t<POOL != 0, ClipCursor, WaveCursor<CLIPS>> pre;
+    // (ragged clips: RaggedCursor)
+    std::conditional_t<POOL != 0, ClipCursor, std::conditional_t<RAGGED, RaggedCursor, WaveCursor<CLIPS>>> pre;
     if constexpr (POOL != 0) pre.init(wave, n_waves, args.n_clips, args.frames_per_clip, args.hop, args.clip_stride, args.spans, args.samples_per_clip);
+    else if constexpr (RAGGED) pre.init(wave, n_waves, args.chunk, n_frames, args.hop, args.spans, args.n_clips);
     else pre.init(wave, n_waves, args.chunk, n_frames, args.frames_per_clip, CLIPS ? args.hop : frame_len, args.clip_stride);
     c32 ring[PF][4] = {};
     long fq[PF], cq[PF];
@@ -890,7 +895,8 @@ static int flen_of(int frame_len) { return frame_len == 512 ? 512 : (frame_len =
 template <int S, int L, int G, int FLEN, int IN, int TILE>
 static void launch_flen(const Mfcc512Args &args, bool clips, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
-    if (IN == 0 && !clips) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, FLEN, 0, TILE, false>), g, b, lds, stream, args);
+    if (args.spans) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, FLEN, IN, TILE, true, 0, true>), g, b, lds, stream, args);
+    else if (IN == 0 && !clips) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, FLEN, 0, TILE, false>), g, b, lds, stream, args);
     else hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, FLEN, IN, TILE, true>), g, b, lds, stream, args);
 }
 
@@ -991,8 +997,9 @@ hipError_t launch_mfcc512_stop(const Mfcc512Args &args, int dct_split, int dct_l
 hipError_t launch_mfcc512(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks,
                           hipStream_t stream, bool tile)
 {
-    const bool clips = args.frames_per_clip > 0;
+    const bool clips = args.frames_per_clip > 0 || args.spans;
     if (tile && (args.log_mode != 0 || args.chunk % 8 != 0)) return hipErrorInvalidConfiguration;
+    if (args.spans && args.n_clips <= 0) return hipErrorInvalidConfiguration;
     if (args.in_kind != 0) {
         if (!(dct_split == 4 && dct_len == 10 && gather == 3) || !tile || !clips) return hipErrorInvalidConfiguration;
         if (args.in_kind == 1) return launch_one<4, 10, 3, 1, 1>(args, true, blocks, stream);
@@ -1025,6 +1032,44 @@ hipError_t launch_clip_floor(const float *frame_max, long n_clips, int frames_pe
     if (n_clips <= 0) return hipSuccess;
     hipLaunchKernelGGL(clip_floor_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, frame_max, n_clips,
                        frames_per_clip, top_db, clip_floor);
+    return hipGetLastError();
+}
+
+// ragged: clip_floor[s] = max over span s's frames [frame0, frame0 + frames) - top_db
+__global__ void clip_floor_ragged_kernel(const float *__restrict__ frame_max, const ClipSpan *__restrict__ spans, long n_spans, float top_db,
+                                         float *__restrict__ clip_floor)
+{
+    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_spans) return;
+    const ClipSpan s = spans[c];
+    float m = -INFINITY;
+    for (int t = 0; t < s.frames; ++t) m = fmaxf(m, frame_max[s.frame0 + t]);
+    clip_floor[c] = m - top_db;
+}
+
+hipError_t launch_clip_floor_ragged(const float *frame_max, const ClipSpan *spans, long n_spans, float top_db, float *clip_floor, hipStream_t stream)
+{
+    if (n_spans <= 0) return hipSuccess;
+    hipLaunchKernelGGL(clip_floor_ragged_kernel, dim3((unsigned)((n_spans + 255) / 256)), dim3(256), 0, stream, frame_max, spans, n_spans,
+                       top_db, clip_floor);
+    return hipGetLastError();
+}
+
+// chunk_span[k] = the span that frame k * chunk lies in, for every chunk of the batch: span s writes the chunks that start inside it
+// (spans of >= 1 frame, back to back in the output: every chunk start lies in exactly one)
+__global__ void ragged_chunk_map_kernel(const ClipSpan *__restrict__ spans, long n_spans, int chunk, int *__restrict__ chunk_span)
+{
+    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_spans) return;
+    const ClipSpan s = spans[c];
+    for (long k = (s.frame0 + chunk - 1) / chunk; k * chunk < s.frame0 + s.frames; ++k) chunk_span[k] = (int)c;
+}
+
+hipError_t launch_ragged_chunk_map(const ClipSpan *spans, long n_spans, int chunk, int *chunk_span, hipStream_t stream)
+{
+    if (n_spans <= 0) return hipSuccess;
+    if (chunk <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ragged_chunk_map_kernel, dim3((unsigned)((n_spans + 255) / 256)), dim3(256), 0, stream, spans, n_spans, chunk, chunk_span);
     return hipGetLastError();
 }
 

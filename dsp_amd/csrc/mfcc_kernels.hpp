@@ -56,7 +56,9 @@ struct Mfcc512Args {
     float *frame_max;
     const float *clip_floor;
     // the fused clip kernels (POOL; one wavefront walks one clip): the clip count, and for a ragged batch the clips' spans
-    // (spans == nullptr: clip c starts at c * clip_stride and has frames_per_clip frames of samples_per_clip samples)
+    // (spans == nullptr: clip c starts at c * clip_stride and has frames_per_clip frames of samples_per_clip samples).
+    // Ragged MFCC matrices (launch_mfcc512 / launch_mfcc2048 with spans set): n_clips spans of >= 1 frame in the caller's order, their
+    // ClipSpan::frame0 the first output frame, and behind them the int chunk table of launch_ragged_chunk_map
     long n_clips = 0;
     const ClipSpan *spans = nullptr;
     PoolSvmArgs pool;              // only read by the POOL instantiations (launch_mfcc512_pool)
@@ -66,6 +68,11 @@ struct Mfcc512Args {
 // clip_floor[c] = max_t frame_max[c][t] - top_db
 hipError_t launch_clip_floor(const float *frame_max, long n_clips, int frames_per_clip, float top_db, float *clip_floor,
                              hipStream_t stream);
+
+// ragged (args.spans): clip_floor[s] = max over span s's frames of frame_max - top_db
+hipError_t launch_clip_floor_ragged(const float *frame_max, const ClipSpan *spans, long n_spans, float top_db, float *clip_floor, hipStream_t stream);
+// ragged: chunk_span[k] = the span holding frame k * chunk, k < ceil(total frames / chunk) -- the table RaggedCursor starts its chunks from
+hipError_t launch_ragged_chunk_map(const ClipSpan *spans, long n_spans, int chunk, int *chunk_span, hipStream_t stream);
 
 // tile: 16-frame log + MFMA-DCT epilogue (per-frame log mode, chunk % 8 == 0); false: per-frame epilogue
 hipError_t launch_mfcc512(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks,

@@ -101,6 +101,7 @@ SYMBOLS = [
     "dsp_debug_fused_spans", "dsp_scrubjay_fused_ragged_device", "dsp_scrubjay_fused_ragged_pcm16_device", "dsp_classify_signal_batch_ragged_device", "dsp_classify_signal_batch_ragged_pcm16_device",
     "dsp_scrubjay_fused_device", "dsp_scrubjay_fused_pcm16_device", "dsp_classify_signal_batch_pcm16_device", "dsp_stop_model_create", "dsp_stop_model_destroy", "dsp_stop_predict_device", "dsp_classify_signal_batch_device",
     "dsp_classify_signal", "dsp_speaker_model_create", "dsp_speaker_model_destroy", "dsp_speaker_llr_device",
+    "dsp_mfcc_ragged_frame_offsets", "dsp_mfcc_clips_ragged_device", "dsp_mfcc_clips_ragged_pcm16_device", "dsp_speaker_llr_ragged_device",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
@@ -209,6 +210,10 @@ def load() -> C.CDLL:
     L.dsp_speaker_model_create.argtypes = [C.POINTER(GmmParams), C.POINTER(GmmParams), ip, C.POINTER(vp)]; L.dsp_speaker_model_create.restype = ip
     L.dsp_speaker_model_destroy.argtypes = [vp]; L.dsp_speaker_model_destroy.restype = None
     L.dsp_speaker_llr_device.argtypes = [vp, vp, C.c_long, ip, vp, vp, vp, vp, vp]; L.dsp_speaker_llr_device.restype = ip
+    L.dsp_mfcc_ragged_frame_offsets.argtypes = [cfgp, lp, C.c_long, ip, lp]; L.dsp_mfcc_ragged_frame_offsets.restype = C.c_long
+    L.dsp_mfcc_clips_ragged_device.argtypes = [vp, vp, C.c_long, lp, ip, vp, vp]; L.dsp_mfcc_clips_ragged_device.restype = ip
+    L.dsp_mfcc_clips_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, ip, vp, vp]; L.dsp_mfcc_clips_ragged_pcm16_device.restype = ip
+    L.dsp_speaker_llr_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_speaker_llr_ragged_device.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip

@@ -30,6 +30,16 @@ def frames_for(cfg: MfccConfig, num_samples: int, max_frames: int) -> int:
     return _lib.load().dsp_mfcc_frames_for(C.byref(cfg), int(num_samples), int(max_frames))
 
 
+def ragged_frame_offsets(cfg: MfccConfig, offsets, max_frames: int) -> np.ndarray:
+    """Host only: int64 [n_clips + 1] prefix sums of frames_for(cfg, offsets[c + 1] - offsets[c], max_frames) -- the first row of each
+    clip in the matrix clips_ragged returns (dsp_mfcc_ragged_frame_offsets)."""
+    off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
+    fo = np.empty(n + 1, np.int64)
+    _lib.check(_lib.load().dsp_mfcc_ragged_frame_offsets(C.byref(cfg), off, n, int(max_frames), fo.ctypes.data_as(C.POINTER(C.c_long))),
+               "dsp_mfcc_ragged_frame_offsets")
+    return fo
+
+
 def compute_mfcc(signal: np.ndarray, max_frames: int) -> np.ndarray:
     """The reference entry point itself: `int compute_mfcc(signal, n, out, max_frames)`
     called through the C ABI with host buffers.  Returns out[:T] (frame-major [T][13])."""
@@ -150,3 +160,37 @@ class MfccPlan:
                                                             int(max_frames), self._stream()), "dsp_mfcc_clips_device")
             assert got == t
         return out
+
+    def clips_ragged(self, signal, offsets, max_frames: int, stereo_mode: int = 0, out=None):
+        """A ragged batch -- signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (interleaved stereo; stereo_mode as
+        clips_pcm16), clip c = samples [offsets[c], offsets[c + 1]) per channel -- in one launch.  Returns (mfcc, frame_offsets):
+        cuda float32 [F][n_mfcc] with clip c's frames in rows [frame_offsets[c], frame_offsets[c + 1]) (numpy int64 [n_clips + 1]),
+        each row bit for bit what a one-clip clips / clips_pcm16 call gives; clips shorter than a frame have no rows."""
+        import torch
+        off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
+        fo = ragged_frame_offsets(self.cfg, (off, n), max_frames)
+        total = int(fo[-1])
+        if not (signal.is_cuda and signal.is_contiguous()):
+            raise ValueError("signal must be a contiguous CUDA tensor")
+        if signal.dtype == torch.float32:
+            if signal.dim() != 1:
+                raise ValueError("float32 signal must be 1-D [total]")
+        elif signal.dtype == torch.int16:
+            if not (signal.dim() == 1 or (signal.dim() == 2 and signal.shape[1] == 2)):
+                raise ValueError("int16 signal must be [total] (mono) or [total][2] (interleaved stereo)")
+        else:
+            raise ValueError("signal must be float32 or int16")
+        if n and int(off[n]) > signal.shape[0]:
+            raise ValueError("offsets run past the end of the signal")
+        if out is None:
+            out = torch.empty((total, self.cfg.n_mfcc), dtype=torch.float32, device=signal.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total * self.cfg.n_mfcc):
+            raise ValueError(f"out must be a contiguous float32 CUDA tensor of at least [{total}][{self.cfg.n_mfcc}]")
+        if total:
+            if signal.dtype == torch.float32:
+                _lib.check(self._L.dsp_mfcc_clips_ragged_device(self._h, signal.data_ptr(), n, off, int(max_frames), out.data_ptr(), self._stream()),
+                           "dsp_mfcc_clips_ragged_device")
+            else:
+                _lib.check(self._L.dsp_mfcc_clips_ragged_pcm16_device(self._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode), int(max_frames),
+                                                                      out.data_ptr(), self._stream()), "dsp_mfcc_clips_ragged_pcm16_device")
+        return out, fo

@@ -156,6 +156,25 @@ int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long 
                                 long clip_stride, int channels, int stereo_mode, float *d_out, int max_frames,
                                 void *stream);
 
+/* RAGGED MFCC matrices: clips of different lengths in ONE launch (the reference's callers run compute_mfcc once per file:
+ * 2fa/audio/word/c/main_test.c:254-331, cepstrum/scrubjay_infer.c:158-176).  offsets is a HOST array of n_clips + 1 sample positions
+ * (per channel) into the device buffer, the contract of dsp_scrubjay_fused_ragged_device: clip c is [offsets[c], offsets[c + 1]),
+ * non-decreasing, any parity (the buffer itself 8-byte aligned, 4 for mono int16), read before the call returns.  Clip c gets the
+ * frames its own length gives; clips with ZERO frames are legal (compute_mfcc returns 0 for them, mfcc.c:117-119) and add no rows.
+ * The matrices lie back to back, frame-major: clip c's frames are d_out[frame_offsets[c] .. frame_offsets[c + 1])[n_mfcc], each row
+ * bit for bit what dsp_mfcc_clips_device (_pcm16_device) returns for that clip alone with the same plan and max_frames; under
+ * DSP_LOG_GLOBAL_REF1 the top_db floor is taken over each clip's own frames.  Plans: n_fft 512 (wave-per-frame kernels, both log
+ * modes) and n_fft 2048 (dsp_mfcc_scrubjay_infer_config and the variants dsp_mfcc_clips_device accepts); PCM16 where
+ * dsp_mfcc_clips_pcm16_device takes it.  n_fft 1024 and prefilter plans: DSP_EINVAL.  Returns the frame count of the longest clip.
+ *
+ * dsp_mfcc_ragged_frame_offsets (host only, no GPU): frame_offsets[n_clips + 1] = prefix sums of
+ * dsp_mfcc_frames_for(cfg, offsets[c + 1] - offsets[c], max_frames); returns the total frame count (>= 0) or a negative DSP_E* code. */
+long dsp_mfcc_ragged_frame_offsets(const dsp_mfcc_config *cfg, const long *offsets, long n_clips, int max_frames, long *frame_offsets);
+int dsp_mfcc_clips_ragged_device(dsp_mfcc_plan *plan, const float *d_signal, long n_clips, const long *offsets,
+                                 int max_frames, float *d_out, void *stream);
+int dsp_mfcc_clips_ragged_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long n_clips, const long *offsets,
+                                       int channels, int stereo_mode, int max_frames, float *d_out, void *stream);
+
 /* --- host-pointer conveniences: copy in, run, copy out, synchronise. -------- */
 int dsp_mfcc_frames_host(dsp_mfcc_plan *plan, const float *frames, long n_frames, float *out);
 int dsp_mfcc_clips_host(dsp_mfcc_plan *plan, const float *signal, long n_clips,
@@ -466,6 +485,12 @@ void dsp_speaker_model_destroy(dsp_speaker_model *model);
  * Bit-exact integer results.  HBM pointers; d_labels, d_ll_* may be NULL.                        */
 int dsp_speaker_llr_device(dsp_speaker_model *model, const float *d_mfcc, long n_clips, int frames_per_clip,
                            int64_t *d_llr_mean, int *d_labels, int64_t *d_ll_target, int64_t *d_ll_ubm, void *stream);
+/* The same per clip of a ragged MFCC matrix (dsp_mfcc_clips_ragged_device): clip c is rows [frame_offsets[c], frame_offsets[c + 1])
+ * of d_mfcc[..][d], frame_offsets a HOST array of n_clips + 1 rows as dsp_mfcc_ragged_frame_offsets returns it, read before the call
+ * returns.  Every clip must hold at least one frame (the reference would divide by zero, speaker_gmm.c:135): DSP_EINVAL names the
+ * first that does not.  d_ll_target / d_ll_ubm, if given, are [frame_offsets[n_clips]], by row.                                  */
+int dsp_speaker_llr_ragged_device(dsp_speaker_model *model, const float *d_mfcc, long n_clips, const long *frame_offsets,
+                                  int64_t *d_llr_mean, int *d_labels, int64_t *d_ll_target, int64_t *d_ll_ubm, void *stream);
 
 /* upsampleLinear (sync/particle/main.cpp:62-77) over a batch: d_out[c][i] for i < new_size from
  * d_in[c][0..old_size), the reference's fp32 operation order (bit-identical).  new_size >= 2.     */
