@@ -4,6 +4,7 @@
                                                               audio_classifier_inference.c:38-90
   SpeakerModel   mfcc_target_speaker_llr_mean / classify_speaker   2fa/audio/pico-audio/src/speaker_gmm.c:127-141
   upsample_linear   upsampleLinear                             sync/particle/main.cpp:62-77
+  Scanner        both per sliding window of long recordings     sync/sync.cpp:188-213 (one 1 s buffer at a time)
 
 Trained parameters are passed in as arrays (the reference compiles them in from model_params.h / gmm_params.inc).
 Tensors are HBM-resident torch tensors; Python only moves pointers.
@@ -15,12 +16,50 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .mfcc import MfccPlan, default_config
+from .mfcc import MfccPlan, default_config, ragged_frame_offsets
 
 
 def _stream(t):
     import torch
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _scan_config(window_frames, hop_frames):
+    window_frames, hop_frames = int(window_frames), int(hop_frames)
+    if window_frames < 1 or hop_frames < 1:
+        raise ValueError("window_frames and hop_frames must be >= 1")
+    return _lib.ScanConfig(window_frames, hop_frames)
+
+
+def _frame_offsets(frame_offsets):
+    fo = np.ascontiguousarray(np.asarray(frame_offsets, dtype=np.int64))
+    if fo.ndim != 1 or fo.size < 1:
+        raise ValueError("frame_offsets must hold n_recordings + 1 rows")
+    if fo[0] < 0 or (fo.size > 1 and (np.diff(fo) < 0).any()):
+        raise ValueError("frame_offsets must be non-negative and non-decreasing")
+    return fo
+
+
+def scan_window_offsets(frame_offsets, window_frames: int, hop_frames: int) -> np.ndarray:
+    """Host only: int64 [n_recordings + 1], the prefix sums of the window counts of recordings of frame_offsets[r + 1] - frame_offsets[r]
+    MFCC rows (dsp_scan_window_offsets): R >= window_frames rows give 1 + (R - window_frames) // hop_frames windows, fewer rows one."""
+    cfg = _scan_config(window_frames, hop_frames)
+    fo = _frame_offsets(frame_offsets)
+    wo = np.zeros(fo.size, np.int64)
+    lp = C.POINTER(C.c_long)
+    _lib.check(_lib.load().dsp_scan_window_offsets(C.byref(cfg), fo.ctypes.data_as(lp), fo.size - 1, wo.ctypes.data_as(lp)), "dsp_scan_window_offsets")
+    return wo
+
+
+def _scan_mfcc(mfcc, fo, d):
+    if not (hasattr(mfcc, "is_cuda") and mfcc.is_cuda and mfcc.dim() == 2 and mfcc.shape[1] == d):
+        raise ValueError(f"mfcc must be a CUDA tensor [F][{d}]")
+    if int(fo[-1]) > mfcc.shape[0]:
+        raise ValueError("frame_offsets run past the end of mfcc")
+    import torch
+    if mfcc.dtype != torch.float32:
+        raise ValueError("mfcc must be float32")
+    return mfcc.contiguous()
 
 
 class StopModel:
@@ -108,6 +147,19 @@ class StopModel:
                                                                              prob.data_ptr(), _stream(signal)), "dsp_classify_signal_batch_ragged_pcm16_device")
         return prob
 
+    def scan(self, mfcc, frame_offsets, window_frames: int, hop_frames: int):
+        """P("stop") per sliding window of rows of a ragged MFCC matrix (MfccPlan.clips_ragged with no frame cap): recording r = rows
+        [frame_offsets[r], frame_offsets[r + 1]) -> (window_offsets int64 [n + 1], prob cuda float32 [window_offsets[-1]])."""
+        import torch
+        wo = scan_window_offsets(frame_offsets, window_frames, hop_frames)
+        fo = _frame_offsets(frame_offsets)
+        mfcc = _scan_mfcc(mfcc, fo, self.n_coef)
+        prob = torch.empty(int(wo[-1]), dtype=torch.float32, device=mfcc.device)
+        _lib.check(self._L.dsp_stop_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
+                                                C.byref(_scan_config(window_frames, hop_frames)), prob.data_ptr(), _stream(mfcc)),
+                   "dsp_stop_scan_device")
+        return wo, prob
+
     def classify_signal(self, signal: np.ndarray) -> float:
         """The reference's classify_signal(signal, num_samples) on a host buffer."""
         signal = np.ascontiguousarray(signal, np.float32)
@@ -178,6 +230,82 @@ class SpeakerModel:
                                                          lu.data_ptr() if per_frame else None, _stream(mfcc)), "dsp_speaker_llr_ragged_device")
         return (mean, label, lt, lu) if per_frame else (mean, label)
 
+    def scan(self, mfcc, frame_offsets, window_frames: int, hop_frames: int):
+        """The speaker LLR per sliding window of rows of a ragged MFCC matrix (as StopModel.scan), every recording >= 1 row
+        -> (window_offsets int64 [n + 1], llr_mean cuda int64, labels cuda int32 [window_offsets[-1]])."""
+        import torch
+        wo = scan_window_offsets(frame_offsets, window_frames, hop_frames)
+        fo = _frame_offsets(frame_offsets)
+        mfcc = _scan_mfcc(mfcc, fo, self.d)
+        nw = int(wo[-1])
+        mean = torch.empty(nw, dtype=torch.int64, device=mfcc.device)
+        label = torch.empty(nw, dtype=torch.int32, device=mfcc.device)
+        _lib.check(self._L.dsp_speaker_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
+                                                   C.byref(_scan_config(window_frames, hop_frames)), mean.data_ptr(), label.data_ptr(), _stream(mfcc)),
+                   "dsp_speaker_scan_device")
+        return wo, mean, label
+
+
+class Scanner:
+    """dsp_scanner: recordings back to back in HBM -> ragged MFCC matrix -> P("stop") and / or the speaker LLR per window of
+    window_frames rows every hop_frames rows.  One stream at a time per scanner."""
+
+    def __init__(self, plan: MfccPlan, stop: StopModel | None = None, speaker: SpeakerModel | None = None, window_frames: int = 98,
+                 hop_frames: int = 10):
+        self._L = _lib.load()
+        if stop is None and speaker is None:
+            raise ValueError("a Scanner needs a stop model, a speaker model or both")
+        self.cfg = _scan_config(window_frames, hop_frames)
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_scanner_create(plan._h, stop._h if stop else None, speaker._h if speaker else None, C.byref(self.cfg), C.byref(h)),
+                   "dsp_scanner_create")
+        self._h, self.plan, self.stop, self.speaker = h, plan, stop, speaker      # (the scanner borrows them: keep them alive)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_scanner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def run(self, signal, offsets, stereo_mode: int = 0):
+        """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (stereo), recording r = samples [offsets[r], offsets[r + 1])
+        per channel -> (window_offsets int64 [n + 1], prob float32 | None, llr_mean int64 | None, labels int32 | None), one entry per window."""
+        import torch
+        off, n = _lib.c_offsets(offsets)
+        if not (hasattr(signal, "is_cuda") and signal.is_cuda and signal.is_contiguous()):
+            raise ValueError("signal must be a contiguous CUDA tensor")
+        if signal.dtype == torch.float32:
+            if signal.dim() != 1:
+                raise ValueError("float32 signal must be 1-D [total]")
+        elif signal.dtype == torch.int16:
+            if not (signal.dim() == 1 or (signal.dim() == 2 and signal.shape[1] == 2)):
+                raise ValueError("int16 signal must be [total] (mono) or [total][2] (interleaved stereo)")
+            if stereo_mode not in (0, 1):
+                raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
+        else:
+            raise ValueError("signal must be float32 or int16")
+        if n and int(off[n]) > signal.shape[0]:
+            raise ValueError("offsets run past the end of the signal")
+        fo = ragged_frame_offsets(self.plan.cfg, (off, n), 2**31 - 1)
+        wo = scan_window_offsets(fo, self.cfg.window_frames, self.cfg.hop_frames)
+        nw, dev = int(wo[-1]), signal.device
+        prob = torch.empty(nw, dtype=torch.float32, device=dev) if self.stop else None
+        mean = torch.empty(nw, dtype=torch.int64, device=dev) if self.speaker else None
+        label = torch.empty(nw, dtype=torch.int32, device=dev) if self.speaker else None
+        ptrs = [t.data_ptr() if t is not None else None for t in (prob, mean, label)]
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if signal.dtype == torch.float32:
+            _lib.check(self._L.dsp_scanner_run_device(self._h, signal.data_ptr(), n, off, *ptrs, st), "dsp_scanner_run_device")
+        else:
+            _lib.check(self._L.dsp_scanner_run_pcm16_device(self._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode), *ptrs, st),
+                       "dsp_scanner_run_pcm16_device")
+        return wo, prob, mean, label
+
 
 def upsample_linear(x, new_size: int):
     """x: cuda float32 [n_clips][old] (or [old]) -> [n_clips][new_size]; numpy input goes through the host entry point."""
@@ -197,4 +325,4 @@ def upsample_linear(x, new_size: int):
     return out[0] if squeeze else out
 
 
-__all__ = ["StopModel", "SpeakerModel", "upsample_linear", "MfccPlan", "default_config"]
+__all__ = ["StopModel", "SpeakerModel", "Scanner", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]

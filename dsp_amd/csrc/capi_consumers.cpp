@@ -3,6 +3,7 @@
 // device copies of their parameters, there is no CPU fallback.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,13 +36,18 @@ struct dsp_stop_model {
     size_t mfcc_cap = 0, sig_cap = 0;
     dsp_mfcc_plan *plan = nullptr;     // default plan of dsp_classify_signal
     std::mutex mu;
+    dsp::SpanRing scan;      // dsp_stop_scan_device: the per-recording offsets on their way to the GPU
 };
 
 struct dsp_speaker_model {
     int device = 0;
     dsp::GmmDev target{}, ubm{};
     void *d_blob = nullptr;
-    dsp::SpanRing rows;      // dsp_speaker_llr_ragged_device: the frame offsets on their way to the GPU (capi_util.hpp)
+    dsp::SpanRing rows;      // dsp_speaker_llr_ragged_device, dsp_speaker_scan_device: the offsets on their way to the GPU (capi_util.hpp)
+    // workspace of dsp_speaker_scan_device: the prefix sums of the per-row LLR (one stream at a time, include/dsp_amd.h)
+    unsigned long long *d_scan = nullptr;
+    size_t scan_cap = 0;
+    std::mutex mu;
 };
 
 extern "C" {
@@ -134,6 +140,7 @@ void dsp_stop_model_destroy(dsp_stop_model *m)
     if (!m) return;
     dsp::DeviceScope dsp_device_scope_(m->device);
     if (m->plan) dsp_mfcc_plan_destroy(m->plan);
+    m->scan.release();
     for (void *p : {(void *)m->d_blob, (void *)m->d_mfcc, (void *)m->d_sig, (void *)m->d_prob})
         if (p) hipFree(p);
     delete m;
@@ -305,6 +312,7 @@ void dsp_speaker_model_destroy(dsp_speaker_model *m)
     if (!m) return;
     dsp::DeviceScope dsp_device_scope_(m->device);
     if (m->d_blob) hipFree(m->d_blob);
+    if (m->d_scan) hipFree(m->d_scan);
     m->rows.release();
     delete m;
 }
@@ -402,6 +410,240 @@ void fft_real_forward(const float *in_time, float *out_freq)
         std::fprintf(stderr, "libdsp_amd: fft_real_forward: %s\n", dsp_last_error());
         for (int i = 0; i < 1024; ++i) out_freq[i] = 0.0f;
     }
+}
+
+}  // extern "C"
+
+// ---- scanning long recordings: P(stop) and the speaker LLR per sliding window of MFCC rows -------------------------------------------
+// In the reference's MFCC shape (per-frame log reference, complete frames, no prefilter) a row depends on its own samples only, so window
+// w of a recording is rows [w hop, w hop + window_frames) of the recording's ragged MFCC matrix, and each row is computed once.
+
+// the host planner: wo[r + 1] = wo[r] + windows of recording r, to[r + 1] = to[r] + ceil(windows / tw) (to may be NULL); total windows or < 0
+static int scan_args(const dsp_scan_config *cfg, long n)
+{
+    if (!cfg || cfg->window_frames < 1 || cfg->hop_frames < 1) return capi_fail(DSP_EINVAL, "dsp_scan_config: window_frames and hop_frames must be >= 1");
+    if (n < 0) return capi_fail(DSP_EINVAL, "n_recordings < 0");
+    return DSP_OK;
+}
+
+static long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, long n, long *wo, long *to, int tw)
+{
+    if (const int rc = scan_args(cfg, n)) return rc;
+    if (n == 0) {
+        if (wo) wo[0] = 0;
+        if (to) to[0] = 0;
+        return 0;
+    }
+    if (!frame_offsets || !wo) return capi_fail(DSP_EINVAL, "frame_offsets and window_offsets must not be NULL");
+    if (frame_offsets[0] < 0) return capi_fail(DSP_EINVAL, "frame_offsets must be non-negative");
+    wo[0] = 0;
+    if (to) to[0] = 0;
+    for (long r = 0; r < n; ++r) {
+        const long rows = frame_offsets[r + 1] - frame_offsets[r];
+        if (rows < 0) return capi_fail(DSP_EINVAL, "frame_offsets decrease at recording " + std::to_string(r));
+        const long w = rows >= cfg->window_frames ? 1 + (rows - cfg->window_frames) / cfg->hop_frames : 1;
+        wo[r + 1] = wo[r] + w;
+        if (to) to[r + 1] = to[r] + (w + tw - 1) / tw;
+    }
+    return wo[n];
+}
+
+// per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to], n + 1 longs each, into a ring slot, uploaded
+static hipError_t scan_upload(dsp::SpanRing &ring, const long *frame_offsets, long n, const long *wo, const long *to, dsp::SpanRing::Slot **out,
+                              void *stream)
+{
+    const size_t one = (size_t)(n + 1) * sizeof(long), bytes = (to ? 3 : 2) * one;
+    dsp::SpanRing::Slot *slot = nullptr;
+    const hipError_t e = ring.acquire(bytes, &slot);
+    if (e != hipSuccess) return e;
+    long *h = static_cast<long *>(slot->h);
+    for (long r = 0; r <= n; ++r) h[r] = frame_offsets[r] - frame_offsets[0];
+    std::memcpy(h + (n + 1), wo, one);
+    if (to) std::memcpy(h + 2 * (n + 1), to, one);
+    *out = slot;
+    return dsp::SpanRing::upload(slot, bytes, (hipStream_t)stream);
+}
+
+extern "C" {
+
+long dsp_scan_window_offsets(const dsp_scan_config *cfg, const long *frame_offsets, long n_recordings, long *window_offsets)
+{
+    return scan_plan(cfg, frame_offsets, n_recordings, window_offsets, nullptr, 1);
+}
+
+int dsp_stop_scan_device(dsp_stop_model *m, const float *d_mfcc, long n_recordings, const long *frame_offsets, const dsp_scan_config *cfg,
+                         float *d_prob, void *stream)
+{
+    if (!m) return capi_fail(DSP_EINVAL, "model is NULL");
+    long rc = scan_args(cfg, n_recordings);
+    if (rc < 0 || n_recordings == 0) return (int)rc;
+    if (!frame_offsets || !d_prob) return capi_fail(DSP_EINVAL, "frame_offsets and d_prob must not be NULL");
+    const int tw = dsp::stop_scan_tile(m->m, cfg->window_frames, cfg->hop_frames);
+    if (tw == 0) return capi_fail(DSP_EINVAL, "the stop model's window (min(window_frames, max_frames) rows of n_coef) does not fit the scan kernel's LDS");
+    std::vector<long> wo((size_t)n_recordings + 1), to((size_t)n_recordings + 1);
+    if ((rc = scan_plan(cfg, frame_offsets, n_recordings, wo.data(), to.data(), tw)) < 0) return (int)rc;
+    const long rows = frame_offsets[n_recordings] - frame_offsets[0];
+    if (rows > 0 && !d_mfcc) return capi_fail(DSP_EINVAL, "d_mfcc is NULL");
+    DSP_ON_DEVICE(m->device);
+    dsp::SpanRing::Slot *slot = nullptr;
+    hipError_t e = scan_upload(m->scan, frame_offsets, n_recordings, wo.data(), to.data(), &slot, stream);
+    if (e == hipSuccess) {
+        const long *d = static_cast<const long *>(slot->d);
+        e = dsp::launch_stop_scan(m->m, rows > 0 ? d_mfcc + frame_offsets[0] * m->m.n_coef : d_mfcc, n_recordings, d, d + (n_recordings + 1),
+                                  d + 2 * (n_recordings + 1), to[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, tw, d_prob,
+                                  (hipStream_t)stream);
+    }
+    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
+    DSP_CAPI_HIP(e);
+    return DSP_OK;
+}
+
+int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_recordings, const long *frame_offsets, const dsp_scan_config *cfg,
+                            int64_t *d_llr_mean, int *d_labels, void *stream)
+{
+    if (!m) return capi_fail(DSP_EINVAL, "model is NULL");
+    long rc = scan_args(cfg, n_recordings);
+    if (rc < 0 || n_recordings == 0) return (int)rc;
+    if (!frame_offsets || !d_mfcc || !d_llr_mean) return capi_fail(DSP_EINVAL, "frame_offsets, d_mfcc and d_llr_mean must not be NULL");
+    std::vector<long> wo((size_t)n_recordings + 1);
+    if ((rc = scan_plan(cfg, frame_offsets, n_recordings, wo.data(), nullptr, 1)) < 0) return (int)rc;
+    for (long r = 0; r < n_recordings; ++r)
+        if (frame_offsets[r + 1] == frame_offsets[r])
+            return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + " has no MFCC rows (the LLR is a mean over a window's rows)");
+    const long rows = frame_offsets[n_recordings] - frame_offsets[0];
+    std::lock_guard<std::mutex> lock(m->mu);
+    DSP_ON_DEVICE(m->device);
+    const size_t need = (size_t)(rows + (rows + dsp::kLlrScanChunk - 1) / dsp::kLlrScanChunk) * sizeof(unsigned long long);
+    if (m->scan_cap < need) {
+        if (m->d_scan) { hipFree(m->d_scan); m->d_scan = nullptr; m->scan_cap = 0; }
+        if (hipMalloc(&m->d_scan, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (speaker scan workspace)");
+        m->scan_cap = need;
+    }
+    dsp::SpanRing::Slot *slot = nullptr;
+    hipError_t e = scan_upload(m->rows, frame_offsets, n_recordings, wo.data(), nullptr, &slot, stream);
+    if (e == hipSuccess) {
+        const long *d = static_cast<const long *>(slot->d);
+        const long long threshold = (long long)(-0.7 * (1 << 8));                              // speaker_gmm.c:124-125
+        e = dsp::launch_speaker_scan(m->target, m->ubm, d_mfcc + frame_offsets[0] * m->target.d, rows, n_recordings, d, d + (n_recordings + 1),
+                                     wo[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, threshold, m->d_scan,
+                                     reinterpret_cast<long long *>(d_llr_mean), d_labels, (hipStream_t)stream);
+    }
+    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
+    DSP_CAPI_HIP(e);
+    return DSP_OK;
+}
+
+}  // extern "C"
+
+// A scanner: PCM -> ragged MFCC matrix in its own workspace -> the models' window scans, all on the caller's stream.
+struct dsp_scanner {
+    dsp_mfcc_plan *plan = nullptr;
+    dsp_stop_model *stop = nullptr;
+    dsp_speaker_model *spk = nullptr;
+    dsp_scan_config cfg{};
+    int device = 0, n_mfcc = 0;
+    float *d_mfcc = nullptr;
+    size_t mfcc_cap = 0;
+    std::vector<long> fo;
+    std::mutex mu;
+};
+
+// in_kind 0 float samples, 1 int16 (channels / stereo_mode as dsp_mfcc_clips_ragged_pcm16_device)
+static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int channels, int stereo_mode, long n, const long *offsets, float *d_prob,
+                       int64_t *d_llr_mean, int *d_labels, void *stream)
+{
+    if (!s || n < 0) return capi_fail(DSP_EINVAL, "bad argument (scanner, n_recordings >= 0)");
+    if (n == 0) return DSP_OK;
+    if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");
+    if (s->stop && !d_prob) return capi_fail(DSP_EINVAL, "the scanner has a stop model: d_prob must not be NULL");
+    if (s->spk && !d_llr_mean) return capi_fail(DSP_EINVAL, "the scanner has a speaker model: d_llr_mean must not be NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    dsp_mfcc_config pcfg;
+    dsp_mfcc_plan_config(s->plan, &pcfg);
+    s->fo.resize((size_t)n + 1);
+    const long rows = dsp_mfcc_ragged_frame_offsets(&pcfg, offsets, n, INT_MAX, s->fo.data());     // no cap: every row of every recording
+    if (rows < 0) return (int)rows;
+    if (s->spk)
+        for (long r = 0; r < n; ++r)
+            if (s->fo[(size_t)r + 1] == s->fo[(size_t)r])
+                return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + " is shorter than one frame: the speaker LLR is a mean over a window's rows");
+    if (rows > 0) {
+        if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
+        DSP_ON_DEVICE(s->device);
+        const size_t need = (size_t)rows * s->n_mfcc * sizeof(float);
+        if (s->mfcc_cap < need) {
+            if (s->d_mfcc) { hipFree(s->d_mfcc); s->d_mfcc = nullptr; s->mfcc_cap = 0; }
+            if (hipMalloc(&s->d_mfcc, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
+            s->mfcc_cap = need;
+        }
+        const int rc = in_kind == 0 ? dsp_mfcc_clips_ragged_device(s->plan, static_cast<const float *>(d_signal), n, offsets, INT_MAX, s->d_mfcc, stream)
+                                    : dsp_mfcc_clips_ragged_pcm16_device(s->plan, static_cast<const int16_t *>(d_signal), n, offsets, channels, stereo_mode,
+                                                                         INT_MAX, s->d_mfcc, stream);
+        if (rc < 0) return rc;
+    }
+    if (s->stop) {
+        const int rc = dsp_stop_scan_device(s->stop, s->d_mfcc, n, s->fo.data(), &s->cfg, d_prob, stream);
+        if (rc < 0) return rc;
+    }
+    if (s->spk) {
+        const int rc = dsp_speaker_scan_device(s->spk, s->d_mfcc, n, s->fo.data(), &s->cfg, d_llr_mean, d_labels, stream);
+        if (rc < 0) return rc;
+    }
+    return DSP_OK;
+}
+
+extern "C" {
+
+int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_model *speaker, const dsp_scan_config *cfg, dsp_scanner **out)
+{
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!plan) return capi_fail(DSP_EINVAL, "plan is NULL");
+    if (!stop && !speaker) return capi_fail(DSP_EINVAL, "a scanner needs a stop model, a speaker model or both");
+    if (const int rc = scan_args(cfg, 0)) return rc;
+    dsp_mfcc_config pcfg;
+    dsp_mfcc_plan_config(plan, &pcfg);
+    if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
+        return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
+                                     "no prefilter");
+    const int device = dsp::plan_device(plan);
+    if (stop && (pcfg.n_mfcc != stop->m.n_coef || stop->device != device))
+        return capi_fail(DSP_EINVAL, "the stop model needs n_coef = the plan's n_mfcc, on the plan's device");
+    if (speaker && (pcfg.n_mfcc != speaker->target.d || speaker->device != device))
+        return capi_fail(DSP_EINVAL, "the speaker model needs d = the plan's n_mfcc, on the plan's device");
+    if (stop && dsp::stop_scan_tile(stop->m, cfg->window_frames, cfg->hop_frames) == 0)
+        return capi_fail(DSP_EINVAL, "the stop model's window (min(window_frames, max_frames) rows of n_coef) does not fit the scan kernel's LDS");
+    auto *s = new dsp_scanner;
+    s->plan = plan;
+    s->stop = stop;
+    s->spk = speaker;
+    s->cfg = *cfg;
+    s->device = device;
+    s->n_mfcc = pcfg.n_mfcc;
+    *out = s;
+    return DSP_OK;
+}
+
+void dsp_scanner_destroy(dsp_scanner *s)
+{
+    if (!s) return;
+    dsp::DeviceScope dsp_device_scope_(s->device);
+    if (s->d_mfcc) hipFree(s->d_mfcc);
+    delete s;
+}
+
+int dsp_scanner_run_device(dsp_scanner *s, const float *d_signal, long n_recordings, const long *offsets, float *d_prob, int64_t *d_llr_mean,
+                           int *d_labels, void *stream)
+{
+    return scanner_run(s, d_signal, 0, 1, 0, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
+}
+
+int dsp_scanner_run_pcm16_device(dsp_scanner *s, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels, int stereo_mode,
+                                 float *d_prob, int64_t *d_llr_mean, int *d_labels, void *stream)
+{
+    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
+    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
+    return scanner_run(s, d_pcm, 1, channels, stereo_mode, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
 }
 
 }  // extern "C"

@@ -266,4 +266,241 @@ hipError_t launch_fft_real_forward(const float *in, long n_frames, int frame_len
     return hipGetLastError();
 }
 
+// ---- scanning long recordings (dsp_stop_scan_device, dsp_speaker_scan_device) ----------------------------------------------------
+// Recording r is rows [fo[r], fo[r + 1]) of a ragged MFCC matrix; its windows are wo[r] .. wo[r + 1) of the scan (host planner,
+// capi_consumers.cpp).  Window w of a recording with R >= window_frames rows covers rows [w hop, w hop + window_frames); a recording with
+// fewer rows has one window over all of them.  Only these per-recording arrays travel to the GPU: a block or a wave finds its recording
+// by a uniform binary search.
+
+// the r with off[r] <= key < off[r + 1] (off non-decreasing over n + 1 entries, off[0] <= key < off[n])
+__device__ __forceinline__ long scan_find(const long *__restrict__ off, long n, long key)
+{
+    long lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if (off[mid] <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Stop-word net over windows.  One block of 256 threads per tile of TW consecutive windows of one recording (tiles per recording
+// to[r] .. to[r + 1)): the rows the tile's windows cover are staged in LDS once, then thread (slot = tid % TW, stripe = tid / TW) sums
+// layer 1 of window slot over the inputs p = stripe, stripe + 256 / TW, ... -- the same per-input arithmetic as stop_tail_kernel
+// (fl((x - mean) / div), float64 products and partial sums, pad[Tc]), the partial sums added in stripe order through LDS.  With TW = 64
+// a wave's 64 lanes are 64 windows at one input position, so mean / div / W1 are wave-uniform (scalar) loads.  Layers 2-4 and the
+// sigmoid on thread `slot` in stop_tail_kernel's order.
+template <int TW>
+__global__ __launch_bounds__(256) void stop_scan_kernel(const StopModelDev m, const float *__restrict__ mfcc, long n_rec, const long *__restrict__ fo,
+                                                        const long *__restrict__ wo, const long *__restrict__ to, int window_frames, int hop,
+                                                        float *__restrict__ prob)
+{
+    extern __shared__ double scan_lds[];
+    float *rows = reinterpret_cast<float *>(scan_lds);
+    const long r = scan_find(to, n_rec, (long)blockIdx.x);
+    const long w0 = ((long)blockIdx.x - to[r]) * TW;
+    const long n_win = wo[r + 1] - wo[r];
+    const int nw = (int)(n_win - w0 < TW ? n_win - w0 : TW);
+    const long n_rows = fo[r + 1] - fo[r];
+    const int len = n_rows < window_frames ? (int)n_rows : window_frames;
+    const int Tc = len < m.max_frames ? len : m.max_frames;                // stop_detector.c:26-30
+    const int nc = m.n_coef, u1 = m.units[0];
+    // stage rows [w0 hop, w0 hop + (nw - 1) hop + Tc) of the recording: inside it (the planner's window count)
+    const long n_stage = ((long)(nw - 1) * hop + Tc) * nc;
+    const float *src = mfcc + (fo[r] + w0 * hop) * nc;
+    for (long i = threadIdx.x; i < n_stage; i += 256) rows[i] = src[i];
+    __syncthreads();
+    const int slot = (int)threadIdx.x % TW;
+    const int stripe = TW == 64 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / TW) : (int)threadIdx.x / TW;
+    constexpr int S = 256 / TW;
+    double acc[kStopMaxUnits];
+#pragma unroll
+    for (int j = 0; j < kStopMaxUnits; ++j) acc[j] = 0.0;
+    if (slot < nw) {
+        const float *x = rows + (long)slot * hop * nc;
+        const int live = Tc * nc;
+        for (int p = stripe; p < live; p += S) {
+            const int t = p / nc, c = p - t * nc;
+            const int i = c * m.max_frames + t;                          // stop_detector.c:48: coefficient-major index
+            const float xs = (x[p] - m.mean[i]) / m.div[i];              // audio_classifier_inference.c:46
+            const float *w = m.kernel[0] + (long)i * u1;
+#pragma unroll
+            for (int j = 0; j < kStopMaxUnits; ++j)
+                if (j < u1) acc[j] += (double)w[j] * (double)xs;
+        }
+    }
+    __syncthreads();                                                     // the rows are dead: the same LDS takes the partial sums
+    double *part = scan_lds;                                             // [S][TW][u1]
+    for (int j = 0; j < u1; ++j) part[((long)stripe * TW + slot) * u1 + j] = acc[j];
+    __syncthreads();
+    if ((int)threadIdx.x >= nw) return;
+    float h[2][kStopMaxUnits];
+    for (int j = 0; j < u1; ++j) {
+        double a = 0.0;
+        for (int s = 0; s < S; ++s) a += part[((long)s * TW + threadIdx.x) * u1 + j];
+        const float v = (float)((double)m.bias[0][j] + m.pad[(long)Tc * u1 + j] + a);
+        h[0][j] = v > 0.0f ? v : 0.0f;
+    }
+    int n_in = u1;
+    for (int l = 1; l < 4; ++l) {                                        // dense_forward, :18-35
+        const int n_out = m.units[l];
+        const float *in = h[(l - 1) & 1];
+        float *out = h[l & 1];
+        for (int j = 0; j < n_out; ++j) {
+            float s = m.bias[l][j];
+            for (int i = 0; i < n_in; ++i) s = s + m.kernel[l][i * n_out + j] * in[i];
+            out[j] = (l < 3 && !(s > 0.0f)) ? 0.0f : s;
+        }
+        n_in = n_out;
+    }
+    prob[wo[r] + w0 + threadIdx.x] = 1.0f / (1.0f + expf(-h[1][0]));   // :13-15
+}
+
+// LDS bytes of a tile of tw windows: its rows, or the partial sums after them
+static long stop_scan_lds(const StopModelDev &m, int window_frames, int hop, int tw)
+{
+    const long len = window_frames < m.max_frames ? window_frames : m.max_frames;
+    const long row_bytes = ((long)(tw - 1) * hop + len) * m.n_coef * (long)sizeof(float);
+    const long part_bytes = 256L * m.units[0] * (long)sizeof(double);
+    return row_bytes > part_bytes ? row_bytes : part_bytes;
+}
+
+int stop_scan_tile(const StopModelDev &m, int window_frames, int hop)
+{
+    for (int tw : {64, 16, 4, 1})
+        if (stop_scan_lds(m, window_frames, hop, tw) <= kScanLdsBytes) return tw;
+    return 0;
+}
+
+hipError_t launch_stop_scan(const StopModelDev &m, const float *mfcc, long n_rec, const long *fo, const long *wo, const long *to, long n_tiles,
+                            int window_frames, int hop, int tw, float *prob, hipStream_t stream)
+{
+    if (n_tiles <= 0) return hipSuccess;
+    for (int l = 0; l < 4; ++l)
+        if (m.units[l] <= 0 || m.units[l] > kStopMaxUnits) return hipErrorInvalidValue;
+    if (window_frames < 1 || hop < 1 || n_tiles >= (1L << 31) || tw != stop_scan_tile(m, window_frames, hop)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)stop_scan_lds(m, window_frames, hop, tw);
+    const dim3 grid((unsigned)n_tiles), block(256);
+    switch (tw) {
+    case 64: hipLaunchKernelGGL(stop_scan_kernel<64>, grid, block, lds, stream, m, mfcc, n_rec, fo, wo, to, window_frames, hop, prob); break;
+    case 16: hipLaunchKernelGGL(stop_scan_kernel<16>, grid, block, lds, stream, m, mfcc, n_rec, fo, wo, to, window_frames, hop, prob); break;
+    case 4: hipLaunchKernelGGL(stop_scan_kernel<4>, grid, block, lds, stream, m, mfcc, n_rec, fo, wo, to, window_frames, hop, prob); break;
+    default: hipLaunchKernelGGL(stop_scan_kernel<1>, grid, block, lds, stream, m, mfcc, n_rec, fo, wo, to, window_frames, hop, prob); break;
+    }
+    return hipGetLastError();
+}
+
+// Speaker LLR over windows: the per-row values v = LL_target - LL_ubm (gmm_ll, as speaker_llr_ragged_kernel) once per row, an inclusive
+// scan of them in uint64 (wrapping: a window's difference of prefix sums is the int64 sum the reference accumulates, wrapped the same
+// way, with no signed overflow here), then per window the truncating mean of that sum (speaker_gmm.c:135) and the label.
+// Pass 1: block b scans rows [b kLlrScanChunk, (b + 1) kLlrScanChunk) -- loc[row] = inclusive sum within the chunk, chunk_sum[b] = its total.
+__global__ __launch_bounds__(256) void speaker_rows_scan_kernel(const GmmDev target, const GmmDev ubm, const float *__restrict__ mfcc, long n_rows,
+                                                                unsigned long long *__restrict__ loc, unsigned long long *__restrict__ chunk_sum)
+{
+    __shared__ GmmLds gt, gu;
+    __shared__ unsigned long long wave_sum[4];
+    for (int i = threadIdx.x; i < target.k * target.d; i += 256) {
+        gt.means[i] = target.means[i]; gt.inv_covs[i] = target.inv_covs[i];
+        gu.means[i] = ubm.means[i]; gu.inv_covs[i] = ubm.inv_covs[i];
+    }
+    for (int i = threadIdx.x; i < target.k; i += 256) { gt.log_consts[i] = target.log_consts[i]; gu.log_consts[i] = ubm.log_consts[i]; }
+    __syncthreads();
+    constexpr int kPer = kLlrScanChunk / 256;
+    const int d_n = target.d, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row0 = (long)blockIdx.x * kLlrScanChunk + (long)threadIdx.x * kPer;
+    unsigned long long v[kPer], run = 0;
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+        v[q] = 0;
+        if (row0 + q < n_rows) {
+            const float *f = mfcc + (row0 + q) * d_n;
+            int x[kGmmMaxD];
+#pragma unroll
+            for (int d = 0; d < kGmmMaxD; ++d) x[d] = d < d_n ? (int)(short)(int)(f[d] * 64.0f) : 0;   // low 16 bits of the int32 truncation
+            v[q] = (unsigned long long)gmm_ll(gt, target.k, d_n, x) - (unsigned long long)gmm_ll(gu, ubm.k, d_n, x);   // :104-108, wrapping
+        }
+        run += v[q];
+        v[q] = run;
+    }
+    unsigned long long incl = run;                                       // inclusive scan of the threads' totals in the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    unsigned long long base = incl - run;
+    for (int k = 0; k < wave; ++k) base += wave_sum[k];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q)
+        if (row0 + q < n_rows) loc[row0 + q] = base + v[q];
+    if (threadIdx.x == 255) chunk_sum[blockIdx.x] = base + run;
+}
+
+// Pass 2: one block turns chunk_sum[n_chunks] into its exclusive prefix sums
+__global__ __launch_bounds__(256) void scan_chunk_sums_kernel(unsigned long long *__restrict__ chunk_sum, long n_chunks)
+{
+    __shared__ unsigned long long wave_sum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0;
+    for (long c0 = 0; c0 < n_chunks; c0 += 256) {
+        const long c = c0 + threadIdx.x;
+        const unsigned long long x = c < n_chunks ? chunk_sum[c] : 0;
+        unsigned long long incl = x;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        unsigned long long base = carry + incl - x;
+        for (int k = 0; k < wave; ++k) base += wave_sum[k];
+        const unsigned long long total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+        __syncthreads();
+        if (c < n_chunks) chunk_sum[c] = base;
+        carry += total;
+    }
+}
+
+// Pass 3: thread per window.  Q(k) = sum of the first k rows = loc[k - 1] + chunk_sum[(k - 1) / kLlrScanChunk]; window sum = Q(e) - Q(s).
+// The wave finds its first window's recording by binary search; a lane walks on from there (a wave spans at most 64 recordings).
+__global__ __launch_bounds__(256) void speaker_window_kernel(long n_rec, const long *__restrict__ fo, const long *__restrict__ wo, long n_windows,
+                                                             int window_frames, int hop, const unsigned long long *__restrict__ loc,
+                                                             const unsigned long long *__restrict__ chunk_sum, long long threshold,
+                                                             long long *__restrict__ llr_mean, int *__restrict__ labels)
+{
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    const long g0 = (long)blockIdx.x * 256 + (threadIdx.x & ~63);
+    if (g0 >= n_windows) return;
+    long r = scan_find(wo, n_rec, g0);
+    if (g >= n_windows) return;
+    while (wo[r + 1] <= g) ++r;
+    const long n_rows = fo[r + 1] - fo[r];
+    const long n = n_rows < window_frames ? n_rows : window_frames;       // >= 1: the host refused recordings without rows
+    const long s = fo[r] + (g - wo[r]) * hop, e = s + n;
+    const unsigned long long qs = s == 0 ? 0ull : loc[s - 1] + chunk_sum[(s - 1) / kLlrScanChunk];
+    const unsigned long long qe = loc[e - 1] + chunk_sum[(e - 1) / kLlrScanChunk];
+    const long long mean = (long long)(qe - qs) / (long long)n;          // :135
+    llr_mean[g] = mean;
+    if (labels) labels[g] = mean > threshold ? 1 : 0;                     // :138-141
+}
+
+hipError_t launch_speaker_scan(const GmmDev &target, const GmmDev &ubm, const float *mfcc, long n_rows, long n_rec, const long *fo, const long *wo,
+                               long n_windows, int window_frames, int hop, long long threshold, unsigned long long *work, long long *llr_mean,
+                               int *labels, hipStream_t stream)
+{
+    if (n_windows <= 0 || n_rows <= 0) return hipSuccess;
+    if (target.d != ubm.d || target.k != ubm.k || target.d > kGmmMaxD || target.k > kGmmMaxK || window_frames < 1 || hop < 1) return hipErrorInvalidValue;
+    const long n_chunks = (n_rows + kLlrScanChunk - 1) / kLlrScanChunk;
+    if (n_chunks >= (1L << 31) || (n_windows + 255) / 256 >= (1L << 31)) return hipErrorInvalidValue;
+    unsigned long long *loc = work, *chunk_sum = work + n_rows;
+    hipLaunchKernelGGL(speaker_rows_scan_kernel, dim3((unsigned)n_chunks), dim3(256), 0, stream, target, ubm, mfcc, n_rows, loc, chunk_sum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(scan_chunk_sums_kernel, dim3(1), dim3(256), 0, stream, chunk_sum, n_chunks);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(speaker_window_kernel, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, stream, n_rec, fo, wo, n_windows, window_frames,
+                       hop, loc, chunk_sum, threshold, llr_mean, labels);
+    return hipGetLastError();
+}
+
 }  // namespace dsp

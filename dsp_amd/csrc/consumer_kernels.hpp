@@ -48,6 +48,23 @@ hipError_t launch_speaker_llr_ragged(const GmmDev &target, const GmmDev &ubm, co
                                      long long threshold, long long *llr_mean, int *labels, long long *ll_target, long long *ll_ubm,
                                      hipStream_t stream);
 
+// ---- scanning long recordings: windows of rows of a ragged MFCC matrix ----
+// fo[n_rec + 1]: the recordings' first rows (relative to mfcc), wo[n_rec + 1]: their first windows, to[n_rec + 1]: their first tiles of
+// stop_scan_tile() windows -- device arrays, prefix sums; the host planner (capi_consumers.cpp) made them.
+constexpr long kScanLdsBytes = 64 * 1024;    // LDS of one stop-scan block (two blocks per CU)
+constexpr int kLlrScanChunk = 1024;             // rows per block of the speaker scan's first pass
+
+// windows per stop-scan block for this model and window shape: 64, 16, 4 or 1 (the largest whose rows fit kScanLdsBytes), 0 if none fits
+int stop_scan_tile(const StopModelDev &m, int window_frames, int hop);
+// prob[wo[r] + w] = the net on window w of recording r (classify_signal of the window's clip); n_tiles = to[n_rec], tw = stop_scan_tile()
+hipError_t launch_stop_scan(const StopModelDev &m, const float *mfcc, long n_rec, const long *fo, const long *wo, const long *to, long n_tiles,
+                            int window_frames, int hop, int tw, float *prob, hipStream_t stream);
+// llr_mean[g], labels[g] (may be NULL) per window of n_windows = wo[n_rec], every recording >= 1 row; work: n_rows + ceil(n_rows /
+// kLlrScanChunk) uint64 of scratch, n_rows = fo[n_rec]
+hipError_t launch_speaker_scan(const GmmDev &target, const GmmDev &ubm, const float *mfcc, long n_rows, long n_rec, const long *fo, const long *wo,
+                               long n_windows, int window_frames, int hop, long long threshold, unsigned long long *work, long long *llr_mean,
+                               int *labels, hipStream_t stream);
+
 // out[c][i] = in[c][lo] + (in[c][hi] - in[c][lo]) * frac, the reference's fp32 operation order
 hipError_t launch_upsample_linear(const float *in, long n_clips, int old_size, long in_stride, float *out, int new_size,
                                   long out_stride, hipStream_t stream);

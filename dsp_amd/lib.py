@@ -54,6 +54,12 @@ class GmmParams(C.Structure):
     _fields_ = [("k", C.c_int), ("d", C.c_int), ("means", C.c_void_p), ("inv_covs", C.c_void_p), ("log_consts", C.c_void_p)]
 
 
+class ScanConfig(C.Structure):
+    """dsp_scan_config (include/dsp_amd.h): windows of MFCC rows."""
+
+    _fields_ = [("window_frames", C.c_int), ("hop_frames", C.c_int)]
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -102,6 +108,8 @@ SYMBOLS = [
     "dsp_scrubjay_fused_device", "dsp_scrubjay_fused_pcm16_device", "dsp_classify_signal_batch_pcm16_device", "dsp_stop_model_create", "dsp_stop_model_destroy", "dsp_stop_predict_device", "dsp_classify_signal_batch_device",
     "dsp_classify_signal", "dsp_speaker_model_create", "dsp_speaker_model_destroy", "dsp_speaker_llr_device",
     "dsp_mfcc_ragged_frame_offsets", "dsp_mfcc_clips_ragged_device", "dsp_mfcc_clips_ragged_pcm16_device", "dsp_speaker_llr_ragged_device",
+    "dsp_scan_window_offsets", "dsp_stop_scan_device", "dsp_speaker_scan_device",
+    "dsp_scanner_create", "dsp_scanner_destroy", "dsp_scanner_run_device", "dsp_scanner_run_pcm16_device",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
@@ -214,6 +222,14 @@ def load() -> C.CDLL:
     L.dsp_mfcc_clips_ragged_device.argtypes = [vp, vp, C.c_long, lp, ip, vp, vp]; L.dsp_mfcc_clips_ragged_device.restype = ip
     L.dsp_mfcc_clips_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, ip, vp, vp]; L.dsp_mfcc_clips_ragged_pcm16_device.restype = ip
     L.dsp_speaker_llr_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_speaker_llr_ragged_device.restype = ip
+    scp = C.POINTER(ScanConfig)
+    L.dsp_scan_window_offsets.argtypes = [scp, lp, C.c_long, lp]; L.dsp_scan_window_offsets.restype = C.c_long
+    L.dsp_stop_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp]; L.dsp_stop_scan_device.restype = ip
+    L.dsp_speaker_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp, vp]; L.dsp_speaker_scan_device.restype = ip
+    L.dsp_scanner_create.argtypes = [vp, vp, vp, scp, C.POINTER(vp)]; L.dsp_scanner_create.restype = ip
+    L.dsp_scanner_destroy.argtypes = [vp]; L.dsp_scanner_destroy.restype = None
+    L.dsp_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp]; L.dsp_scanner_run_device.restype = ip
+    L.dsp_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp]; L.dsp_scanner_run_pcm16_device.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip

@@ -492,6 +492,48 @@ int dsp_speaker_llr_device(dsp_speaker_model *model, const float *d_mfcc, long n
 int dsp_speaker_llr_ragged_device(dsp_speaker_model *model, const float *d_mfcc, long n_clips, const long *frame_offsets,
                                   int64_t *d_llr_mean, int *d_labels, int64_t *d_ll_target, int64_t *d_ll_ubm, void *stream);
 
+/* SCANNING LONG RECORDINGS: P("stop") and the speaker LLR per sliding window (the firmware scores one 1 s buffer at a time,
+ * sync/sync.cpp:188-213).  Windows are runs of MFCC rows: recording r is rows [frame_offsets[r], frame_offsets[r + 1]) of a ragged
+ * MFCC matrix (dsp_mfcc_clips_ragged_device, no frame cap), R rows.  R >= window_frames: W = 1 + (R - window_frames) / hop_frames
+ * windows, window w = rows [w hop_frames, w hop_frames + window_frames); R < window_frames (R = 0 included): one window of all R rows.
+ * In samples, window w is the clip [w hop_frames hop_length, + frame_length + (window_frames - 1) hop_length), clipped to the
+ * recording when W = 1: each result is the per-clip entry's on that clip -- classify_signal (rows past max_frames dropped, missing
+ * rows zero-padded), mfcc_target_speaker_llr_mean / classify_speaker (Q8 int64 mean, C truncating division by the window's rows).
+ * The windows of all recordings lie back to back: window_offsets[n_recordings + 1] = prefix sums of W.
+ *
+ * dsp_scan_window_offsets (host only, no GPU): fills window_offsets, returns the total window count or a negative DSP_E* code
+ * (window_frames, hop_frames >= 1; frame_offsets non-negative, non-decreasing); n_recordings = 0 returns 0.                          */
+typedef struct dsp_scan_config {
+    int window_frames;           /* rows per window (98: one second of the reference's framing) */
+    int hop_frames;              /* rows between window starts (10: 100 ms)                    */
+} dsp_scan_config;
+long dsp_scan_window_offsets(const dsp_scan_config *cfg, const long *frame_offsets, long n_recordings, long *window_offsets);
+/* The stop-word net on every window: d_mfcc[..][n_coef] the ragged matrix, frame_offsets a HOST array of n_recordings + 1 rows (read
+ * before the call returns), d_prob[total windows].  Each MFCC row is read once per tile of consecutive windows.  Uses a ring of
+ * upload buffers in the model, no workspace: any stream.                                                                           */
+int dsp_stop_scan_device(dsp_stop_model *model, const float *d_mfcc, long n_recordings, const long *frame_offsets,
+                         const dsp_scan_config *cfg, float *d_prob, void *stream);
+/* The speaker LLR on every window, bit-exact: d_llr_mean[total windows] (Q8), d_labels (may be NULL) = llr_mean > (int64)(-0.7 * 256).
+ * Every recording must hold at least one row: DSP_EINVAL names the first that does not.  The per-row LLR is scanned into a grow-only
+ * workspace of the model (8 bytes per row): calls on one speaker model serve ONE stream at a time.                                 */
+int dsp_speaker_scan_device(dsp_speaker_model *model, const float *d_mfcc, long n_recordings, const long *frame_offsets,
+                            const dsp_scan_config *cfg, int64_t *d_llr_mean, int *d_labels, void *stream);
+/* A scanner runs the whole chain: recordings back to back in HBM (offsets as dsp_mfcc_clips_ragged_device: a HOST array of
+ * n_recordings + 1 sample positions per channel; a recording longer than INT_MAX samples is DSP_EINVAL) -> ragged MFCC matrix in the
+ * scanner's grow-only workspace (DSP_ENOMEM if it cannot grow) -> the scans of the models it was given, all enqueued on `stream`
+ * without a host synchronisation.  The plan must be n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, no prefilter, with n_mfcc
+ * equal to the models' n_coef / d (elsewhere rows depend on the window: DSP_EINVAL); stop and speaker may each be NULL, not both.
+ * The outputs of a model not given may be NULL.  The scanner borrows plan and models (destroy it first) and owns its workspace: ONE
+ * stream at a time per scanner (and per speaker model), as for the stop model's own workspace.  Zero recordings: DSP_OK, no launch.  */
+typedef struct dsp_scanner dsp_scanner;
+int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_model *speaker, const dsp_scan_config *cfg,
+                       dsp_scanner **out);
+void dsp_scanner_destroy(dsp_scanner *scanner);
+int dsp_scanner_run_device(dsp_scanner *scanner, const float *d_signal, long n_recordings, const long *offsets, float *d_prob,
+                           int64_t *d_llr_mean, int *d_labels, void *stream);
+int dsp_scanner_run_pcm16_device(dsp_scanner *scanner, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels,
+                                 int stereo_mode, float *d_prob, int64_t *d_llr_mean, int *d_labels, void *stream);
+
 /* upsampleLinear (sync/particle/main.cpp:62-77) over a batch: d_out[c][i] for i < new_size from
  * d_in[c][0..old_size), the reference's fp32 operation order (bit-identical).  new_size >= 2.     */
 int dsp_upsample_linear_device(const float *d_in, long n_clips, int old_size, long in_stride, float *d_out,
