@@ -128,23 +128,9 @@ def _pcm_host(pcm):
     return pcm, (2 if pcm.ndim == 3 else 1)
 
 
-def _pcm_device(pcm):
-    """cuda int16 [n_clips][n] or interleaved [n_clips][n][2] -> (channels, clip stride in samples per channel)."""
+def _float(f64: bool):
     import torch
-    if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (2, 3) and pcm.stride(-1) == 1):
-        raise ValueError("pcm must be an int16 CUDA tensor [n_clips][n] or [n_clips][n][2] with unit inner stride")
-    channels = 2 if pcm.dim() == 3 else 1
-    if channels == 2 and (pcm.shape[2] != 2 or pcm.stride(1) != 2 or pcm.stride(0) % 2):
-        raise ValueError("stereo pcm must be interleaved [n_clips][n][2]")
-    return channels, pcm.stride(0) // channels
-
-
-def _clips_device(clips, f64: bool):
-    import torch
-    dt = torch.float64 if f64 else torch.float32
-    if not (clips.is_cuda and clips.dtype == dt and clips.dim() == 2 and clips.stride(1) == 1):
-        raise ValueError(f"clips must be a {'float64' if f64 else 'float32'} CUDA tensor [n_clips][n] with unit inner stride")
-    return clips
+    return torch.float64 if f64 else torch.float32
 
 
 def _ragged_host(f64: bool, signal, offsets, stereo_mode, with_trace, config):
@@ -163,16 +149,9 @@ def _ragged_host(f64: bool, signal, offsets, stereo_mode, with_trace, config):
 
 
 def _ragged_device(f64: bool, signal, offsets, labels, stereo_mode, config):
-    import torch
-    off, n_clips = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
-    if not (signal.is_cuda and signal.stride(-1) == 1 and off[n_clips] <= signal.shape[0]):
-        raise ValueError("signal must be a CUDA tensor with unit inner stride that holds every clip of offsets")
-    if signal.dtype == torch.int16:
-        if signal.dim() not in (1, 2):
-            raise ValueError("int16 signal must be [total] or interleaved [total][2]")
-        return _device("dsp_classify_batch_ragged_pcm16_device", f64, signal, n_clips, labels, config, off, signal.dim(), int(stereo_mode))
-    if signal.dtype != (torch.float64 if f64 else torch.float32) or signal.dim() != 1:
-        raise ValueError(f"signal must be {'float64' if f64 else 'float32'} [total], int16 [total] or int16 [total][2]")
+    off, n_clips, channels, _ = _lib.ragged_signal(signal, offsets, _float(f64))
+    if channels:
+        return _device("dsp_classify_batch_ragged_pcm16_device", f64, signal, n_clips, labels, config, off, channels, int(stereo_mode))
     return _device("dsp_classify_batch_ragged_device", f64, signal, n_clips, labels, config, off)
 
 
@@ -196,13 +175,13 @@ def classify_batch_pcm16(pcm: np.ndarray, stereo_mode: int = 0, with_trace: bool
 
 def classify_device(clips, labels=None, config=None):
     """clips: cuda float32 [n_clips][n] -> cuda int32 labels; runs on torch's current stream."""
-    n_clips, n = _clips_device(clips, False).shape
+    n_clips, n = _lib.clips_device(clips, _float(False)).shape
     return _device("dsp_classify_batch_device_cfg", False, clips, n_clips, labels, config, n, clips.stride(0))
 
 
 def classify_device_pcm16(pcm, labels=None, stereo_mode: int = 0, config=None):
     """pcm: cuda int16 [n_clips][n] or [n_clips][n][2] -> cuda int32 labels (dsp_classify_batch_pcm16_device), stream-ordered."""
-    channels, stride = _pcm_device(pcm)
+    channels, stride = _lib.pcm_device(pcm)
     n_clips, n = pcm.shape[:2]
     return _device("dsp_classify_batch_pcm16_device", False, pcm, n_clips, labels, config, n, stride, channels, int(stereo_mode))
 
@@ -236,7 +215,7 @@ def classify_batch_f64(clips: np.ndarray, with_trace: bool = False, config=None)
 
 def classify_device_f64(clips, labels=None, config=None):
     """clips: cuda float64 [n_clips][n] -> cuda int32 labels (dsp_classify_batch_device_f64); runs on torch's current stream."""
-    n_clips, n = _clips_device(clips, True).shape
+    n_clips, n = _lib.clips_device(clips, _float(True)).shape
     return _device("dsp_classify_batch_device", True, clips, n_clips, labels, config, n, clips.stride(0))
 
 
@@ -252,7 +231,7 @@ def classify_batch_f64_pcm16(pcm: np.ndarray, stereo_mode: int = STEREO_CHANNEL0
 def classify_device_f64_pcm16(pcm, labels=None, stereo_mode: int = STEREO_CHANNEL0, config=None):
     """pcm: cuda int16 [n_clips][n] or [n_clips][n][2] -> cuda int32 labels (dsp_classify_batch_pcm16_device_f64), stream-ordered on
     torch's current stream."""
-    channels, stride = _pcm_device(pcm)
+    channels, stride = _lib.pcm_device(pcm)
     n_clips, n = pcm.shape[:2]
     return _device("dsp_classify_batch_pcm16_device", True, pcm, n_clips, labels, config, n, stride, channels, int(stereo_mode))
 

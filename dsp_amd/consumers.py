@@ -111,7 +111,7 @@ class StopModel:
     def classify_signal_batch(self, plan: MfccPlan, clips):
         """clips: cuda float32 [n_clips][samples] -> P("stop") float32 [n_clips] (classify_signal per clip)."""
         import torch
-        assert clips.dim() == 2 and clips.dtype == torch.float32
+        _lib.clips_device(clips, torch.float32)
         prob = torch.empty(clips.shape[0], dtype=torch.float32, device=clips.device)
         _lib.check(self._L.dsp_classify_signal_batch_device(plan._h, self._h, clips.data_ptr(), clips.shape[0], clips.shape[1],
                                                             clips.stride(0), prob.data_ptr(), _stream(clips)),
@@ -122,10 +122,9 @@ class StopModel:
         """pcm: cuda int16 [n_clips][samples] or [n_clips][samples][2] -> P("stop") (dsp_classify_signal_batch_pcm16_device: what
         main_test.c:198-217 decodes in front of classify_signal, converted in the kernel's load)."""
         import torch
-        assert pcm.dim() in (2, 3) and pcm.dtype == torch.int16 and pcm.stride(-1) == 1
-        channels = 2 if pcm.dim() == 3 else 1
+        channels, stride = _lib.pcm_device(pcm)
         prob = torch.empty(pcm.shape[0], dtype=torch.float32, device=pcm.device)
-        _lib.check(self._L.dsp_classify_signal_batch_pcm16_device(plan._h, self._h, pcm.data_ptr(), pcm.shape[0], pcm.shape[1], pcm.stride(0) // channels,
+        _lib.check(self._L.dsp_classify_signal_batch_pcm16_device(plan._h, self._h, pcm.data_ptr(), pcm.shape[0], pcm.shape[1], stride,
                                                                   channels, int(stereo_mode), prob.data_ptr(), _stream(pcm)),
                    "dsp_classify_signal_batch_pcm16_device")
         return prob
@@ -134,17 +133,14 @@ class StopModel:
         """Clips of different lengths in ONE launch (the files main_test.c:254-331 loops over): `signal` is a flat cuda buffer (float32
         [total], int16 [total] or stereo int16 [total][2]), clip c = samples [offsets[c], offsets[c + 1]) -> P("stop") per clip."""
         import torch
-        off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
-        assert signal.is_cuda and signal.stride(-1) == 1 and int(off[n]) <= signal.shape[0]
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
         prob = torch.empty(n, dtype=torch.float32, device=signal.device)
-        if signal.dtype == torch.float32:
-            assert signal.dim() == 1
-            _lib.check(self._L.dsp_classify_signal_batch_ragged_device(plan._h, self._h, signal.data_ptr(), n, off, prob.data_ptr(), _stream(signal)),
-                       "dsp_classify_signal_batch_ragged_device")
+        if channels:
+            _lib.check(self._L.dsp_classify_signal_batch_ragged_pcm16_device(plan._h, self._h, ptr, n, off, channels, int(stereo_mode), prob.data_ptr(),
+                                                                             _stream(signal)), "dsp_classify_signal_batch_ragged_pcm16_device")
         else:
-            assert signal.dtype == torch.int16 and signal.dim() in (1, 2)
-            _lib.check(self._L.dsp_classify_signal_batch_ragged_pcm16_device(plan._h, self._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode),
-                                                                             prob.data_ptr(), _stream(signal)), "dsp_classify_signal_batch_ragged_pcm16_device")
+            _lib.check(self._L.dsp_classify_signal_batch_ragged_device(plan._h, self._h, ptr, n, off, prob.data_ptr(), _stream(signal)),
+                       "dsp_classify_signal_batch_ragged_device")
         return prob
 
     def scan(self, mfcc, frame_offsets, window_frames: int, hop_frames: int):
@@ -276,21 +272,9 @@ class Scanner:
         """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (stereo), recording r = samples [offsets[r], offsets[r + 1])
         per channel -> (window_offsets int64 [n + 1], prob float32 | None, llr_mean int64 | None, labels int32 | None), one entry per window."""
         import torch
-        off, n = _lib.c_offsets(offsets)
-        if not (hasattr(signal, "is_cuda") and signal.is_cuda and signal.is_contiguous()):
-            raise ValueError("signal must be a contiguous CUDA tensor")
-        if signal.dtype == torch.float32:
-            if signal.dim() != 1:
-                raise ValueError("float32 signal must be 1-D [total]")
-        elif signal.dtype == torch.int16:
-            if not (signal.dim() == 1 or (signal.dim() == 2 and signal.shape[1] == 2)):
-                raise ValueError("int16 signal must be [total] (mono) or [total][2] (interleaved stereo)")
-            if stereo_mode not in (0, 1):
-                raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
-        else:
-            raise ValueError("signal must be float32 or int16")
-        if n and int(off[n]) > signal.shape[0]:
-            raise ValueError("offsets run past the end of the signal")
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
+        if channels and stereo_mode not in (0, 1):
+            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
         fo = ragged_frame_offsets(self.plan.cfg, (off, n), 2**31 - 1)
         wo = scan_window_offsets(fo, self.cfg.window_frames, self.cfg.hop_frames)
         nw, dev = int(wo[-1]), signal.device
@@ -299,11 +283,10 @@ class Scanner:
         label = torch.empty(nw, dtype=torch.int32, device=dev) if self.speaker else None
         ptrs = [t.data_ptr() if t is not None else None for t in (prob, mean, label)]
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if signal.dtype == torch.float32:
-            _lib.check(self._L.dsp_scanner_run_device(self._h, signal.data_ptr(), n, off, *ptrs, st), "dsp_scanner_run_device")
+        if channels:
+            _lib.check(self._L.dsp_scanner_run_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), *ptrs, st), "dsp_scanner_run_pcm16_device")
         else:
-            _lib.check(self._L.dsp_scanner_run_pcm16_device(self._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode), *ptrs, st),
-                       "dsp_scanner_run_pcm16_device")
+            _lib.check(self._L.dsp_scanner_run_device(self._h, ptr, n, off, *ptrs, st), "dsp_scanner_run_device")
         return wo, prob, mean, label
 
 
@@ -318,7 +301,8 @@ def upsample_linear(x, new_size: int):
     import torch
     squeeze = x.dim() == 1
     x2 = x[None] if squeeze else x
-    assert x2.stride(1) == 1
+    if x2.stride(1) != 1:
+        raise ValueError("x must have unit inner stride")
     out = torch.empty((x2.shape[0], new_size), dtype=torch.float32, device=x.device)
     _lib.check(L.dsp_upsample_linear_device(x2.data_ptr(), x2.shape[0], x2.shape[1], x2.stride(0), out.data_ptr(), new_size,
                                             new_size, _stream(x)), "dsp_upsample_linear_device")

@@ -116,6 +116,7 @@ struct dsp_mfcc_plan {
     float *d_frame_max = nullptr, *d_clip_floor = nullptr;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
     size_t frame_max_cap = 0, clip_floor_cap = 0;
     int kernel = DSP_KERNEL_WAVE;
+    bool aub = false;                             // n_fft = 2048 with aubio's semantics (magnitude spectrum, log10 floor or stream framing)
     int resident_blocks_row = 3;
     // staging for the host-pointer entry points
     float *d_in = nullptr, *d_out = nullptr;
@@ -353,10 +354,10 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
         return fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
     }
     p->n_cu = prop.multiProcessorCount;
+    p->aub = cfg->n_fft == 2048 && (cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM);
     if (cfg->n_fft == 2048) {
-        const bool aub = cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM;
-        p->resident_blocks_2048 = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, false, aub);
-        p->resident_blocks_2048_pool = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, true, aub);
+        p->resident_blocks_2048 = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, false, p->aub);
+        p->resident_blocks_2048_pool = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, true, p->aub);
     } else if (cfg->n_fft == 512) {
         p->resident_blocks_frame = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
                                                               cfg->frame_length == 512, false);
@@ -429,14 +430,7 @@ int dsp_mfcc_plan_set_launch(dsp_mfcc_plan *p, int blocks_per_cu, int frames_per
     return DSP_OK;
 }
 
-static int reserve(float **buf, size_t *cap, size_t need)
-{
-    if (*cap >= need) return DSP_OK;
-    if (*buf) { hipFree(*buf); *buf = nullptr; *cap = 0; }
-    DSP_HIP(hipMalloc(buf, need));
-    *cap = need;
-    return DSP_OK;
-}
+}  // extern "C"
 
 // A ragged batch for run(): clip c = samples [offsets[c], offsets[c + 1]) per channel, frame_offsets[c] its first output row (prefix sums of
 // the clips' frame counts), n_spans the clips with at least one frame.
@@ -446,34 +440,67 @@ struct RaggedBatch {
 };
 
 // ragged: the spans (caller's order, clips of >= 1 frame, ClipSpan::frame0 = first output row) and behind them the chunk table of the
-// kernels' RaggedCursor (built on the device for `chunk`), in a ring slot; *slot is set once the upload is enqueued (mark it after the
-// last kernel that reads it)
-static int ragged_mfcc_spans(dsp_mfcc_plan *p, const RaggedBatch &rg, long n_frames, int chunk, dsp::SpanRing::Slot **slot, void *stream)
+// kernels' RaggedCursor (built on the device for `chunk`), in the leased ring slot
+static int ragged_mfcc_spans(dsp_mfcc_plan *p, const RaggedBatch &rg, long n_frames, int chunk, dsp::SpanRing::Lease &slot, hipStream_t st)
 {
     const size_t span_bytes = (size_t)rg.n_spans * sizeof(dsp::ClipSpan);
     const long n_chunks = (n_frames + chunk - 1) / chunk;
-    dsp::SpanRing::Slot *s = nullptr;
-    DSP_HIP(p->spans.acquire(span_bytes + (size_t)n_chunks * sizeof(int), &s));
-    auto *h = static_cast<dsp::ClipSpan *>(s->h);
+    DSP_HIP(p->spans.acquire(span_bytes + (size_t)n_chunks * sizeof(int), slot));
+    auto *h = static_cast<dsp::ClipSpan *>(slot.h());
     long j = 0;
     for (long c = 0; c < rg.n_clips; ++c) {
         const int frames = (int)(rg.frame_offsets[c + 1] - rg.frame_offsets[c]);
         if (frames > 0) h[j++] = dsp::ClipSpan{rg.offsets[c], (int)(rg.offsets[c + 1] - rg.offsets[c]), frames, c, rg.frame_offsets[c]};
     }
-    DSP_HIP(dsp::SpanRing::upload(s, span_bytes, (hipStream_t)stream));
-    *slot = s;
-    auto *d = static_cast<const dsp::ClipSpan *>(s->d);
-    DSP_HIP(dsp::launch_ragged_chunk_map(d, rg.n_spans, chunk, reinterpret_cast<int *>(static_cast<char *>(s->d) + span_bytes), (hipStream_t)stream));
+    DSP_HIP(slot.upload(span_bytes, st));
+    DSP_HIP(dsp::launch_ragged_chunk_map(static_cast<const dsp::ClipSpan *>(slot.d()), rg.n_spans, chunk,
+                                         reinterpret_cast<int *>(static_cast<char *>(slot.d()) + span_bytes), st));
     return DSP_OK;
 }
 
-// marks a ring slot on every exit once it is set
-struct SlotMark {
-    dsp::SpanRing::Slot *slot = nullptr;
-    hipStream_t stream;
-    explicit SlotMark(void *st) : stream((hipStream_t)st) {}
-    ~SlotMark() { if (slot) dsp::SpanRing::mark(slot, stream); }
-};
+// the launch fields every path takes from the plan (clip_mode: stream framing applies to clips; independent frames are whole frames)
+static dsp::Mfcc512Args plan_args(const dsp_mfcc_plan *p, const void *d_in, int in_kind, bool clip_mode)
+{
+    dsp::Mfcc512Args a{};
+    a.in = d_in;
+    a.in_kind = in_kind;
+    a.tables = p->d_tables;
+    a.hop = p->cfg.hop_length;
+    a.frame_len = p->cfg.frame_length;
+    a.n_mels = p->cfg.n_mels;
+    a.n_mfcc = p->cfg.n_mfcc;
+    a.amin = p->cfg.amin;
+    a.top_db = p->cfg.top_db;
+    a.log_mode = p->cfg.log_mode;
+    a.spectrum = p->cfg.spectrum;
+    a.stream_framing = clip_mode && p->cfg.framing == DSP_FRAMING_STREAM;
+    return a;
+}
+
+// persistent-style grid: exactly the 4-wave blocks the chip holds at once (per_cu per CU unless dsp_mfcc_plan_set_launch says otherwise;
+// one extra block per CU would run as a second, mostly idle round: measured +14 %), never more blocks than `items` of work fill
+static int grid(const dsp_mfcc_plan *p, int per_cu, long items)
+{
+    return (int)std::max(1L, std::min((long)p->n_cu * (p->blocks_per_cu > 0 ? p->blocks_per_cu : per_cu), (items + 3) / 4));
+}
+
+// DSP_LOG_GLOBAL_REF1 over clips (clip-global top_db): pass 1 writes each frame's maximum, a tiny kernel turns them into one floor per
+// clip, pass 2 is the normal kernel clipping at that floor.  launch(args) enqueues the plan's MFCC kernel.
+template <class Launch> static int two_pass_floor(dsp_mfcc_plan *p, dsp::Mfcc512Args &a, hipStream_t st, const Launch &launch)
+{
+    const long n_clips = a.spans ? a.n_clips : a.n_frames / a.frames_per_clip;
+    std::lock_guard<std::recursive_mutex> lock(p->mu);
+    DSP_HIP(dsp::reserve(p->d_frame_max, p->frame_max_cap, (size_t)a.n_frames * sizeof(float)));
+    DSP_HIP(dsp::reserve(p->d_clip_floor, p->clip_floor_cap, (size_t)n_clips * sizeof(float)));
+    a.frame_max = p->d_frame_max;
+    DSP_HIP(launch(a));
+    if (a.spans) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, st));
+    else DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, a.frames_per_clip, a.top_db, p->d_clip_floor, st));
+    a.frame_max = nullptr;
+    a.clip_floor = p->d_clip_floor;
+    DSP_HIP(launch(a));
+    return DSP_OK;
+}
 
 // rg != nullptr: a ragged batch (frames_per_clip = 0, clip_stride unused): the clip-mode kernels with the RaggedCursor
 static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, int frames_per_clip,
@@ -482,62 +509,20 @@ static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, 
 {
     if (n_frames == 0) return DSP_OK;
     DSP_ON_DEVICE(p->device);       // the caller's current device may be another GPU: tables and workspaces live on the plan's
+    hipStream_t st = (hipStream_t)stream;
     const bool clip_mode = frames_per_clip > 0 || rg;
     const bool single_clip = frames_per_clip > 0 && n_frames == frames_per_clip;   // stride unused
     if ((reinterpret_cast<uintptr_t>(d_in) & (in_kind == 1 ? 3 : 7)) || (!single_clip && (clip_stride & 1)))
         return fail(DSP_EINVAL, "input must be 8-byte aligned (4 for mono int16) with an even clip stride");
-    const bool aub2048 = p->cfg.n_fft == 2048 && (p->cfg.spectrum != DSP_SPECTRUM_POWER || p->cfg.log_mode == DSP_LOG_LOG10_FLOOR || p->cfg.framing == DSP_FRAMING_STREAM);
-    if (in_kind != 0 && !(aub2048 && clip_mode) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
+    if (in_kind != 0 && !(p->aub && clip_mode) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
         return fail(DSP_EINVAL, "PCM16 ingestion runs on the 512-point wave-per-frame kernel (per-frame log mode) and on the 2048-point scrubjay_infer.c front end");
-    SlotMark span_slot(stream);
-    if (p->cfg.n_fft == 2048) {
-        dsp::Mfcc512Args a{};
-        a.in = d_in; a.in_kind = in_kind; a.out = d_out; a.n_frames = n_frames; a.clip_stride = clip_stride; a.frames_per_clip = frames_per_clip;
-        a.hop = p->cfg.hop_length; a.frame_len = p->cfg.frame_length; a.chunk = p->chunk > 0 ? p->chunk : 8;
-        a.n_mels = p->cfg.n_mels; a.n_mfcc = p->cfg.n_mfcc; a.amin = p->cfg.amin; a.top_db = p->cfg.top_db;
-        a.spectrum = p->cfg.spectrum;
-        a.stream_framing = clip_mode && p->cfg.framing == DSP_FRAMING_STREAM;
-        a.samples_per_clip = samples_per_clip;
-        if (a.stream_framing && samples_per_clip <= 0 && !rg) return fail(DSP_EINVAL, "internal: stream framing without the clip length");
-        if (rg) {
-            int rc;
-            if ((rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, &span_slot.slot, stream)) < 0) return rc;
-            a.spans = static_cast<const dsp::ClipSpan *>(span_slot.slot->d);
-            a.n_clips = rg->n_spans;
-        }
-        const int per_cu = p->blocks_per_cu > 0 ? p->blocks_per_cu : p->resident_blocks_2048;
-        const long chunks = (n_frames + a.chunk - 1) / a.chunk;
-        const long blocks = std::max(1L, std::min((long)p->n_cu * per_cu, (chunks + 3) / 4));
-        a.log_mode = p->cfg.log_mode;
-        if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) {
-            // clip-global top_db, as for n_fft = 512 below: pass 1 writes each frame's maximum, a tiny kernel turns them into one
-            // floor per clip, pass 2 is the normal kernel clipping at that floor
-            const long n_clips = rg ? rg->n_spans : n_frames / frames_per_clip;
-            int rc;
-            std::lock_guard<std::recursive_mutex> lock(p->mu);
-            if ((rc = reserve(&p->d_frame_max, &p->frame_max_cap, (size_t)n_frames * sizeof(float))) < 0) return rc;
-            if ((rc = reserve(&p->d_clip_floor, &p->clip_floor_cap, (size_t)n_clips * sizeof(float))) < 0) return rc;
-            a.frame_max = p->d_frame_max;
-            DSP_HIP(dsp::launch_mfcc2048(a, p->d_tables2048, (int)blocks, (hipStream_t)stream, false));
-            if (rg) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, (hipStream_t)stream));
-            else DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
-            a.frame_max = nullptr;
-            a.clip_floor = p->d_clip_floor;
-        }
-        DSP_HIP(dsp::launch_mfcc2048(a, p->d_tables2048, (int)blocks, (hipStream_t)stream, false));
-        return DSP_OK;
-    }
-    dsp::Mfcc512Args a;
-    a.in = d_in;
-    a.in_kind = in_kind;
+    dsp::Mfcc512Args a = plan_args(p, d_in, in_kind, clip_mode);
     a.out = d_out;
-    a.tables = p->d_tables;
     a.n_frames = n_frames;
     a.clip_stride = clip_stride;
     a.frames_per_clip = frames_per_clip;
-    a.hop = p->cfg.hop_length;
-    a.frame_len = p->cfg.frame_length;
-    const bool gen = p->cfg.n_fft == 1024;
+    a.samples_per_clip = samples_per_clip;
+    const bool fft2048 = p->cfg.n_fft == 2048, gen = p->cfg.n_fft == 1024;
 #ifdef DSP_AMD_EXPERIMENTS
     const bool row = !gen && p->kernel == DSP_KERNEL_ROW && p->cfg.n_fft == 512;
     // two frames per wavefront step (experiment): the reference shape on independent full frames only, else the default form
@@ -551,68 +536,45 @@ static int run(dsp_mfcc_plan *p, const void *d_in, float *d_out, long n_frames, 
     // 1024-point: the register-resident wave kernel when the filterbank fits two chunk slots per lane (DSP_KERNEL_ROW selects
     // the general Stockham kernel for A/B)
     const bool gen_wave = gen && p->gen_slots <= 3 && p->kernel != DSP_KERNEL_ROW;
-    const int nf = gen ? (gen_wave ? 8 : 1) : (pair ? 16 : (row ? 4 : (tile ? 8 : 1)));
-    a.chunk = p->chunk > 0 ? p->chunk : (pair ? 16 : 8);
-    a.chunk = ((a.chunk + nf - 1) / nf) * nf;   // whole items (tile: half-tiles of 8 frames) per chunk
-    a.n_mels = p->cfg.n_mels;
-    a.n_mfcc = p->cfg.n_mfcc;
-    a.amin = p->cfg.amin;
-    a.top_db = p->cfg.top_db;
-    a.log_mode = p->cfg.log_mode;
-    a.frame_max = nullptr;
-    a.clip_floor = nullptr;
+    int per_cu;
+    if (fft2048) {
+        if (a.stream_framing && samples_per_clip <= 0 && !rg) return fail(DSP_EINVAL, "internal: stream framing without the clip length");
+        a.chunk = p->chunk > 0 ? p->chunk : 8;
+        per_cu = p->resident_blocks_2048;
+    } else {
+        const int nf = gen ? (gen_wave ? 8 : 1) : (pair ? 16 : (row ? 4 : (tile ? 8 : 1)));
+        a.chunk = p->chunk > 0 ? p->chunk : (pair ? 16 : 8);
+        a.chunk = ((a.chunk + nf - 1) / nf) * nf;   // whole items (tile: half-tiles of 8 frames) per chunk
+        per_cu = gen ? (gen_wave ? (fused_prefilter ? p->resident_blocks_gen_pre : p->resident_blocks_gen_wave) : p->resident_blocks_gen)
+                     : (pair ? p->resident_blocks_pair : (row ? p->resident_blocks_row : (tile ? p->resident_blocks : p->resident_blocks_frame)));
+    }
+    dsp::SpanRing::Lease slot;
     if (rg) {
-        int rc;
-        if ((rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, &span_slot.slot, stream)) < 0) return rc;
-        a.spans = static_cast<const dsp::ClipSpan *>(span_slot.slot->d);
+        const int rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, slot, st);
+        if (rc < 0) return rc;
+        a.spans = static_cast<const dsp::ClipSpan *>(slot.d());
         a.n_clips = rg->n_spans;
     }
-    // persistent-style grid: exactly the 4-wave blocks the chip holds at once (one
-    // extra block per CU would run as a second, mostly idle round: measured +14 %),
-    // never more blocks than there are chunks of work
-    const int per_cu = p->blocks_per_cu > 0 ? p->blocks_per_cu
-                       : (gen ? (gen_wave ? (fused_prefilter ? p->resident_blocks_gen_pre : p->resident_blocks_gen_wave) : p->resident_blocks_gen)
-                              : (pair ? p->resident_blocks_pair : (row ? p->resident_blocks_row : (tile ? p->resident_blocks : p->resident_blocks_frame))));
-    long blocks = (long)p->n_cu * per_cu;
-    const long chunks = (n_frames + a.chunk - 1) / a.chunk;
-    blocks = std::max(1L, std::min(blocks, (chunks + 3) / 4));
-    if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) {
-        // clip-global top_db: pass 1 writes each frame's maximum, a tiny kernel turns them into one
-        // floor per clip, pass 2 is the normal kernel clipping at that floor
-        const long n_clips = rg ? rg->n_spans : n_frames / frames_per_clip;
-        int rc;
-        std::lock_guard<std::recursive_mutex> lock(p->mu);
-        if ((rc = reserve(&p->d_frame_max, &p->frame_max_cap, (size_t)n_frames * sizeof(float))) < 0) return rc;
-        if ((rc = reserve(&p->d_clip_floor, &p->clip_floor_cap, (size_t)n_clips * sizeof(float))) < 0) return rc;
-        a.frame_max = p->d_frame_max;
-        DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, false));
-        if (rg) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, (hipStream_t)stream));
-        else DSP_HIP(dsp::launch_clip_floor(p->d_frame_max, n_clips, frames_per_clip, a.top_db, p->d_clip_floor, (hipStream_t)stream));
-        a.frame_max = nullptr;
-        a.clip_floor = p->d_clip_floor;
-        DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, false));
-        return DSP_OK;
-    }
-    if (a.log_mode == DSP_LOG_GLOBAL_REF1) {      // independent frames: one pass, wave-per-frame kernel only
-        DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, false));
-        return DSP_OK;
-    }
+    const int blocks = grid(p, per_cu, (n_frames + a.chunk - 1) / a.chunk);
     if (fused_prefilter && !(gen_wave && p->d_scan)) return fail(DSP_EINVAL, "internal: fused prefilter without its tables");
-    if (gen_wave)
-        DSP_HIP(dsp::launch_mfcc1024_wave(a, p->d_gen_tables, (int)blocks, (hipStream_t)stream, fused_prefilter ? p->d_scan : nullptr, p->scan_steps));
-    else if (gen)
-        DSP_HIP(dsp::launch_mfcc1024(a, p->d_gen_tables, (int)blocks, (hipStream_t)stream));
+    auto launch = [&](const dsp::Mfcc512Args &x) {
+        if (fft2048) return dsp::launch_mfcc2048(x, p->d_tables2048, blocks, st, false);
+        if (x.log_mode == DSP_LOG_GLOBAL_REF1)      // the wave-per-frame kernel's per-frame epilogue
+            return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, false);
+        if (gen_wave) return dsp::launch_mfcc1024_wave(x, p->d_gen_tables, blocks, st, fused_prefilter ? p->d_scan : nullptr, p->scan_steps);
+        if (gen) return dsp::launch_mfcc1024(x, p->d_gen_tables, blocks, st);
 #ifdef DSP_AMD_EXPERIMENTS
-    else if (pair)
-        DSP_HIP(dsp::launch_mfcc512_pair(a, p->d_pair, (int)blocks, (hipStream_t)stream));
-    else if (row)
-        DSP_HIP(dsp::launch_mfcc512_row(a, p->d_row_tables, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks,
-                                        (hipStream_t)stream));
+        if (pair) return dsp::launch_mfcc512_pair(x, p->d_pair, blocks, st);
+        if (row) return dsp::launch_mfcc512_row(x, p->d_row_tables, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st);
 #endif
-    else
-        DSP_HIP(dsp::launch_mfcc512(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream, tile));
+        return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, tile);
+    };
+    if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) return two_pass_floor(p, a, st, launch);
+    DSP_HIP(launch(a));      // (DSP_LOG_GLOBAL_REF1 on independent frames: one pass, every frame its own clip)
     return DSP_OK;
 }
+
+extern "C" {
 
 int dsp_mfcc_frames_device(dsp_mfcc_plan *p, const float *d_frames, long n_frames, float *d_out, void *stream)
 {
@@ -631,15 +593,15 @@ int dsp_mfcc_frames_device(dsp_mfcc_plan *p, const float *d_frames, long n_frame
     DSP_ON_DEVICE(p->device);
     const int fl = p->cfg.frame_length;
     const long sub = std::min<long>(n_frames, 1L << 20);
-    int rc;
-    if ((rc = reserve(&p->d_filtered, &p->filtered_cap, (size_t)sub * fl * sizeof(float))) < 0) return rc;
+    DSP_HIP(dsp::reserve(p->d_filtered, p->filtered_cap, (size_t)sub * fl * sizeof(float)));
     dsp::IirCoefD c;
     dsp_butter_bandpass(p->cfg.prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
                         p->cfg.prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, c.b, c.a);
     for (long f0 = 0; f0 < n_frames; f0 += sub) {
         const long cnt = std::min(sub, n_frames - f0);
         DSP_HIP(dsp::launch_iir_f64_on_f32(d_frames + f0 * fl, cnt, fl, fl, c, p->d_filtered, (hipStream_t)stream));
-        if ((rc = run(p, p->d_filtered, d_out + f0 * p->cfg.n_mfcc, cnt, 0, 0, stream)) < 0) return rc;
+        const int rc = run(p, p->d_filtered, d_out + f0 * p->cfg.n_mfcc, cnt, 0, 0, stream);
+        if (rc < 0) return rc;
     }
     return DSP_OK;
 }
@@ -660,14 +622,14 @@ int dsp_mfcc_clips_device(dsp_mfcc_plan *p, const float *d_signal, long n_clips,
 int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, long n_clips, int samples_per_clip,
                                 long clip_stride, int channels, int stereo_mode, float *d_out, int max_frames, void *stream)
 {
-    if (!p || n_clips < 0 || (channels != 1 && channels != 2)) return fail(DSP_EINVAL, "bad argument");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
+    const int kind = dsp::pcm16_kind(channels, stereo_mode);
+    if (kind < 0) return kind;
+    if (!p || n_clips < 0) return fail(DSP_EINVAL, "bad argument");
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return fail(DSP_EINVAL, "the per-frame prefilter applies to independent float frames only");
     const int t = dsp_mfcc_frames_for(&p->cfg, samples_per_clip, max_frames);
     if (t == 0 || n_clips == 0) return 0;
     if (!d_pcm || !d_out) return fail(DSP_EINVAL, "NULL buffer");
     if (n_clips > 1 && clip_stride < samples_per_clip) return fail(DSP_EINVAL, "clip_stride < samples_per_clip");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
     const int rc = run(p, d_pcm, d_out, n_clips * (long)t, t, clip_stride, stream, kind, false, samples_per_clip);
     return rc < 0 ? rc : t;
 }
@@ -680,9 +642,8 @@ static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets
     frame_offsets[0] = 0;
     int tm = 0;
     for (long c = 0; c < n_clips; ++c) {
-        const long n = offsets[c + 1] - offsets[c];
-        if (offsets[c] < 0 || n < 0 || n > INT32_MAX)
-            return fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples (clip " + std::to_string(c) + ")");
+        const long n = dsp::ragged_clip_length(offsets, c);
+        if (n < 0) return n;
         const int t = dsp_mfcc_frames_for(&cfg, (int)n, max_frames);
         frame_offsets[c + 1] = frame_offsets[c] + t;
         tm = std::max(tm, t);
@@ -703,6 +664,7 @@ long dsp_mfcc_ragged_frame_offsets(const dsp_mfcc_config *cfg, const long *offse
 static int mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, const long *offsets, int max_frames, float *d_out,
                              void *stream)
 {
+    if (in_kind < 0) return in_kind;
     if (!p || n_clips < 0 || !offsets) return fail(DSP_EINVAL, "bad argument");
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
     if (p->cfg.n_fft == 1024) return fail(DSP_EINVAL, "ragged MFCC matrices run on the 512- and 2048-point kernels: n_fft 1024 is not supported");
@@ -729,10 +691,7 @@ int dsp_mfcc_clips_ragged_device(dsp_mfcc_plan *p, const float *d_signal, long n
 int dsp_mfcc_clips_ragged_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, long n_clips, const long *offsets, int channels, int stereo_mode,
                                        int max_frames, float *d_out, void *stream)
 {
-    if (channels != 1 && channels != 2) return fail(DSP_EINVAL, "bad argument (channels 1 or 2)");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return mfcc_clips_ragged(p, d_pcm, kind, n_clips, offsets, max_frames, d_out, stream);
+    return mfcc_clips_ragged(p, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, max_frames, d_out, stream);
 }
 
 int dsp_mfcc_frames_host(dsp_mfcc_plan *p, const float *frames, long n_frames, float *out)
@@ -743,9 +702,9 @@ int dsp_mfcc_frames_host(dsp_mfcc_plan *p, const float *frames, long n_frames, f
     DSP_ON_DEVICE(p->device);
     const size_t in_b = (size_t)n_frames * p->cfg.frame_length * sizeof(float);
     const size_t out_b = (size_t)n_frames * p->cfg.n_mfcc * sizeof(float);
+    DSP_HIP(dsp::reserve(p->d_in, p->in_cap, in_b));
+    DSP_HIP(dsp::reserve(p->d_out, p->out_cap, out_b));
     int rc;
-    if ((rc = reserve(&p->d_in, &p->in_cap, in_b)) < 0) return rc;
-    if ((rc = reserve(&p->d_out, &p->out_cap, out_b)) < 0) return rc;
     DSP_HIP(hipMemcpyAsync(p->d_in, frames, in_b, hipMemcpyHostToDevice, nullptr));
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return fail(DSP_EINVAL, "prefiltered plans take device buffers (dsp_mfcc_frames_device)");
     if ((rc = run(p, p->d_in, p->d_out, n_frames, 0, 0, nullptr)) < 0) return rc;
@@ -768,9 +727,9 @@ int dsp_mfcc_clips_host(dsp_mfcc_plan *p, const float *signal, long n_clips, int
     const long dstride = samples_per_clip + (samples_per_clip & 1);
     const size_t in_b = (size_t)n_clips * dstride * sizeof(float);
     const size_t out_b = (size_t)n_clips * t * p->cfg.n_mfcc * sizeof(float);
+    DSP_HIP(dsp::reserve(p->d_in, p->in_cap, in_b));
+    DSP_HIP(dsp::reserve(p->d_out, p->out_cap, out_b));
     int rc;
-    if ((rc = reserve(&p->d_in, &p->in_cap, in_b)) < 0) return rc;
-    if ((rc = reserve(&p->d_out, &p->out_cap, out_b)) < 0) return rc;
     DSP_HIP(hipMemcpy2DAsync(p->d_in, dstride * sizeof(float), signal, clip_stride * sizeof(float),
                              (size_t)samples_per_clip * sizeof(float), (size_t)n_clips, hipMemcpyHostToDevice, nullptr));
     if ((rc = run(p, p->d_in, p->d_out, n_clips * (long)t, t, dstride, nullptr, 0, false, samples_per_clip)) < 0) return rc;
@@ -877,8 +836,8 @@ static int build_fused_spans(const dsp_mfcc_config &cfg, const long *offsets, lo
     std::vector<int> frames((size_t)n_clips), order((size_t)n_clips);
     int tm = 0;
     for (long c = 0; c < n_clips; ++c) {
-        const long n = offsets[c + 1] - offsets[c];
-        if (offsets[c] < 0 || n < 0 || n > INT32_MAX) return fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples");
+        const long n = dsp::ragged_clip_length(offsets, c);
+        if (n < 0) return (int)n;
         const int t = dsp_mfcc_frames_for(&cfg, (int)n, max_frames);
         if (t == 0) return fail(DSP_EINVAL, "clip " + std::to_string(c) + " of the ragged batch is shorter than one frame");
         frames[c] = t;
@@ -897,14 +856,15 @@ static int build_fused_spans(const dsp_mfcc_config &cfg, const long *offsets, lo
     return DSP_OK;
 }
 
-static int ragged_spans(dsp_mfcc_plan *p, const long *offsets, long n_clips, int max_frames, long n_waves, dsp::SpanRing::Slot **slot, int *t_max, void *stream)
+// the fused kernels' spans in the leased ring slot, uploaded on st
+static int ragged_spans(dsp_mfcc_plan *p, const long *offsets, long n_clips, int max_frames, long n_waves, dsp::SpanRing::Lease &slot, int *t_max, hipStream_t st)
 {
     if (!offsets) return fail(DSP_EINVAL, "offsets is NULL");
     if (n_clips >= (1L << 31)) return fail(DSP_EINVAL, "too many clips");
     DSP_HIP(p->spans.acquire((size_t)n_clips * sizeof(dsp::ClipSpan), slot));
-    const int rc = build_fused_spans(p->cfg, offsets, n_clips, max_frames, n_waves, static_cast<dsp::ClipSpan *>((*slot)->h), t_max);
+    const int rc = build_fused_spans(p->cfg, offsets, n_clips, max_frames, n_waves, static_cast<dsp::ClipSpan *>(slot.h()), t_max);
     if (rc < 0) return rc;
-    DSP_HIP(dsp::SpanRing::upload(*slot, (size_t)n_clips * sizeof(dsp::ClipSpan), (hipStream_t)stream));
+    DSP_HIP(slot.upload((size_t)n_clips * sizeof(dsp::ClipSpan), st));
     return DSP_OK;
 }
 
@@ -927,12 +887,12 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
                           long clip_stride, int max_frames, int *d_labels, float *d_decision, float *d_prob1, float *d_feat, void *stream,
                           const long *offsets = nullptr)
 {
+    if (in_kind < 0) return in_kind;
     if (!p || !s || n_clips < 0) return fail(DSP_EINVAL, "bad argument");
     if ((p->cfg.n_fft != 512 && p->cfg.n_fft != 2048) || (p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX && p->cfg.log_mode != DSP_LOG_LOG10_FLOOR) ||
         p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE)
         return fail(DSP_EINVAL, "the fused clip -> label path runs on the 512- and 2048-point wave-per-frame kernels, per-frame log modes");
-    const bool aub2048 = p->cfg.n_fft == 2048 && (p->cfg.spectrum != DSP_SPECTRUM_POWER || p->cfg.log_mode == DSP_LOG_LOG10_FLOOR || p->cfg.framing == DSP_FRAMING_STREAM);
-    if (in_kind != 0 && !aub2048 && (p->cfg.n_fft != 512 || p->cfg.frame_length != 400 || p->host.mel_gather != 3 ||
+    if (in_kind != 0 && !p->aub && (p->cfg.n_fft != 512 || p->cfg.frame_length != 400 || p->host.mel_gather != 3 ||
                                      !((p->host.dct_split == 4 && p->host.dct_len == 10) || (p->host.dct_split == 2 && p->host.dct_len == 20))))
         return fail(DSP_EINVAL, "int16 input of the fused clip -> label kernel: the reference framing (n_fft 512, frame 400, 40 mel filters, up to 20 coefficients) "
                                 "or the scrubjay_infer.c front end (dsp_mfcc_scrubjay_infer_config)");
@@ -947,48 +907,26 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
         return fail(DSP_EINVAL, "input must be 8-byte aligned (4 for mono int16) with an even clip stride");
     if (s->device != p->device) return fail(DSP_EINVAL, "plan and SVM live on different devices");
     DSP_ON_DEVICE(p->device);
-    const int per_cu_f = p->cfg.n_fft == 2048 ? (p->blocks_per_cu > 0 ? p->blocks_per_cu : p->resident_blocks_2048_pool)
-                                              : (p->blocks_per_cu > 0 ? p->blocks_per_cu : p->resident_blocks);
-    const long blocks_f = std::max(1L, std::min((long)p->n_cu * per_cu_f, (n_clips + 3) / 4));
-    dsp::SpanRing::Slot *slot = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = grid(p, p->cfg.n_fft == 2048 ? p->resident_blocks_2048_pool : p->resident_blocks, n_clips);
+    dsp::SpanRing::Lease slot;
     if (ragged) {
-        const int rc = ragged_spans(p, offsets, n_clips, max_frames, 4 * blocks_f, &slot, &t, stream);
+        const int rc = ragged_spans(p, offsets, n_clips, max_frames, 4L * blocks, slot, &t, st);
         if (rc < 0) return rc;
     }
-    dsp::Mfcc512Args a{};
-    a.in = d_signal;
-    a.in_kind = in_kind;
-    a.out = nullptr;
-    a.tables = p->d_tables;
+    dsp::Mfcc512Args a = plan_args(p, d_signal, in_kind, true);
     a.n_frames = n_clips * (long)t;
     a.n_clips = n_clips;
-    a.spans = ragged ? static_cast<const dsp::ClipSpan *>(slot->d) : nullptr;
+    a.spans = ragged ? static_cast<const dsp::ClipSpan *>(slot.d()) : nullptr;
     a.clip_stride = ragged ? 0 : clip_stride;
     a.frames_per_clip = t;
-    a.hop = p->cfg.hop_length;
-    a.frame_len = p->cfg.frame_length;
     a.chunk = t;                                  // one wavefront walks one clip
-    a.n_mels = p->cfg.n_mels;
-    a.n_mfcc = p->cfg.n_mfcc;
-    a.amin = p->cfg.amin;
-    a.top_db = p->cfg.top_db;
-    a.log_mode = p->cfg.log_mode;
-    a.spectrum = p->cfg.spectrum;
-    a.stream_framing = p->cfg.framing == DSP_FRAMING_STREAM;
     a.samples_per_clip = ragged ? 0 : samples_per_clip;
-    a.pool.svm = s->m;
-    a.pool.labels = d_labels;
-    a.pool.decision = d_decision;
-    a.pool.prob1 = d_prob1;
-    a.pool.feat = d_feat;
-    hipError_t e;
-    if (p->cfg.n_fft == 2048) {      // scrubjay_infer.c's own framing (WIN_SIZE 2048, HOP_SIZE 1024): mfcc2048_kernel<POOL>
-        e = dsp::launch_mfcc2048(a, p->d_tables2048, (int)blocks_f, (hipStream_t)stream, true);
-    } else {
-        e = dsp::launch_mfcc512_pool(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks_f, (hipStream_t)stream);
-    }
-    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
-    DSP_HIP(e);
+    a.pool = dsp::PoolSvmArgs{s->m, d_labels, d_decision, d_prob1, d_feat};
+    if (p->cfg.n_fft == 2048)      // scrubjay_infer.c's own framing (WIN_SIZE 2048, HOP_SIZE 1024): mfcc2048_kernel<POOL>
+        DSP_HIP(dsp::launch_mfcc2048(a, p->d_tables2048, blocks, st, true));
+    else
+        DSP_HIP(dsp::launch_mfcc512_pool(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st));
     return t;
 }
 
@@ -1005,10 +943,7 @@ int dsp_scrubjay_fused_pcm16_device(dsp_mfcc_plan *p, dsp_svm *s, const int16_t 
                                     int channels, int stereo_mode, int max_frames, int *d_labels, float *d_decision, float *d_prob1, float *d_feat,
                                     void *stream)
 {
-    if (channels != 1 && channels != 2) return fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return scrubjay_fused(p, s, d_pcm, kind, n_clips, samples_per_clip, clip_stride, max_frames, d_labels, d_decision, d_prob1, d_feat, stream);
+    return scrubjay_fused(p, s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, samples_per_clip, clip_stride, max_frames, d_labels, d_decision, d_prob1, d_feat, stream);
 }
 
 int dsp_scrubjay_fused_ragged_device(dsp_mfcc_plan *p, dsp_svm *s, const float *d_signal, long n_clips, const long *offsets, int max_frames,
@@ -1023,10 +958,7 @@ int dsp_scrubjay_fused_ragged_pcm16_device(dsp_mfcc_plan *p, dsp_svm *s, const i
                                            void *stream)
 {
     if (!offsets) return fail(DSP_EINVAL, "offsets is NULL");
-    if (channels != 1 && channels != 2) return fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return fail(DSP_EINVAL, "bad stereo_mode");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return scrubjay_fused(p, s, d_pcm, kind, n_clips, 0, 0, max_frames, d_labels, d_decision, d_prob1, d_feat, stream, offsets);
+    return scrubjay_fused(p, s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, 0, 0, max_frames, d_labels, d_decision, d_prob1, d_feat, stream, offsets);
 }
 
 }  // extern "C"
@@ -1034,10 +966,9 @@ int dsp_scrubjay_fused_ragged_pcm16_device(dsp_mfcc_plan *p, dsp_svm *s, const i
 int dsp::plan_device(const dsp_mfcc_plan *plan) { return plan ? plan->device : -1; }
 
 // capi_util.hpp: the fused form of dsp_classify_signal_batch_device (capi_consumers.cpp)
-int dsp::stop_fused_device(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *d_signal, long n_clips, int samples_per_clip,
-                           long clip_stride, int t, float *d_prob, void *stream, int in_kind, const long *offsets)
+int dsp::stop_fused_device(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *d_signal, long n_clips, long clip_stride, int t,
+                           float *d_prob, void *stream, int in_kind, const long *offsets)
 {
-    (void)samples_per_clip;
     const bool ragged = offsets != nullptr;
     if (ragged) { t = 1; clip_stride = 0; }
     // the reference's shape on the default kernel: 512-point, per-frame log, 13 coefficients of 40 mel energies, complete frames
@@ -1049,37 +980,22 @@ int dsp::stop_fused_device(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const v
     if (in_kind != 0 && (p->host.mel_gather != 3 || p->cfg.frame_length != 400)) return 0;
     if (m.max_frames <= 0) return fail(DSP_EINVAL, "stop model without frames");
     DSP_ON_DEVICE(p->device);
-    dsp::SpanRing::Slot *slot = nullptr;
-    const int per_cu = p->blocks_per_cu > 0 ? p->blocks_per_cu : p->resident_blocks;
-    long blocks = std::max(1L, std::min((long)p->n_cu * per_cu, (n_clips + 3) / 4));
-    blocks = dsp::mfcc512_stop_grid((int)blocks, m, in_kind, p->host.mel_gather, p->cfg.frame_length);      // what the launcher will start
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = dsp::mfcc512_stop_grid(grid(p, p->resident_blocks, n_clips), m, in_kind, p->host.mel_gather, p->cfg.frame_length);      // what the launcher will start
+    dsp::SpanRing::Lease slot;
     if (ragged) {      // frames past the model's max_frames are dropped (stop_detector.c:26-30): a clip's walk ends there
-        const int rc = ragged_spans(p, offsets, n_clips, m.max_frames, 4 * blocks, &slot, &t, stream);
+        const int rc = ragged_spans(p, offsets, n_clips, m.max_frames, 4L * blocks, slot, &t, st);
         if (rc < 0) return rc;
     }
-    dsp::Mfcc512Args a{};
-    a.in = d_signal;
-    a.in_kind = in_kind;
-    a.out = nullptr;
-    a.tables = p->d_tables;
+    dsp::Mfcc512Args a = plan_args(p, d_signal, in_kind, true);
     a.n_frames = n_clips * (long)t;
     a.n_clips = n_clips;
-    a.spans = ragged ? static_cast<const dsp::ClipSpan *>(slot->d) : nullptr;
+    a.spans = ragged ? static_cast<const dsp::ClipSpan *>(slot.d()) : nullptr;
     a.clip_stride = clip_stride;
     a.frames_per_clip = t;
-    a.hop = p->cfg.hop_length;
-    a.frame_len = p->cfg.frame_length;
     a.chunk = t;                                  // one wavefront walks one clip
-    a.n_mels = p->cfg.n_mels;
-    a.n_mfcc = p->cfg.n_mfcc;
-    a.amin = p->cfg.amin;
-    a.top_db = p->cfg.top_db;
-    a.log_mode = 0;
-    a.stop.m = m;
-    a.stop.prob = d_prob;
-    const hipError_t e = dsp::launch_mfcc512_stop(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, (int)blocks, (hipStream_t)stream);
-    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
-    DSP_HIP(e);
+    a.stop = dsp::StopNetArgs{m, d_prob};
+    DSP_HIP(dsp::launch_mfcc512_stop(a, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st));
     return 1;
 }
 

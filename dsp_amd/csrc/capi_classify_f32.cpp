@@ -353,7 +353,7 @@ int dsp_classify_batch_host_cfg(const dsp_classify_config *cfgp, const float *si
 int dsp_classify_batch_pcm16_host(const dsp_classify_config *cfgp, const int16_t *pcm, long n_clips, int n, long stride, int channels, int stereo_mode,
                                   int *labels, dsp_classify_trace *trace)
 {
-    return front::host_entry<ClassifyCtx>(cfgp, pcm, front::pcm16_kind(channels, stereo_mode), n_clips, n, stride, labels, trace);
+    return front::host_entry<ClassifyCtx>(cfgp, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, n, stride, labels, trace);
 }
 
 int dsp_classify_batch_device(const float *d_signal, long n_clips, int n, long stride, int *d_labels, void *stream)
@@ -370,7 +370,7 @@ int dsp_classify_batch_device_cfg(const dsp_classify_config *cfgp, const float *
 int dsp_classify_batch_pcm16_device(const dsp_classify_config *cfgp, const int16_t *d_pcm, long n_clips, int n, long stride, int channels,
                                     int stereo_mode, int *d_labels, void *stream)
 {
-    return front::device_entry<ClassifyCtx>(cfgp, d_pcm, front::pcm16_kind(channels, stereo_mode), n_clips, n, stride, d_labels, nullptr, stream);
+    return front::device_entry<ClassifyCtx>(cfgp, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, n, stride, d_labels, nullptr, stream);
 }
 
 int dsp_classify_batch_ragged_device(const dsp_classify_config *cfgp, const float *d_signal, long n_clips, const long *offsets, int *d_labels, void *stream)
@@ -381,7 +381,7 @@ int dsp_classify_batch_ragged_device(const dsp_classify_config *cfgp, const floa
 int dsp_classify_batch_ragged_pcm16_device(const dsp_classify_config *cfgp, const int16_t *d_pcm, long n_clips, const long *offsets, int channels,
                                            int stereo_mode, int *d_labels, void *stream)
 {
-    return front::ragged_device_entry<ClassifyCtx>(cfgp, d_pcm, front::pcm16_kind(channels, stereo_mode), n_clips, offsets, d_labels, nullptr, stream);
+    return front::ragged_device_entry<ClassifyCtx>(cfgp, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, d_labels, nullptr, stream);
 }
 
 int dsp_classify_batch_ragged_host(const dsp_classify_config *cfgp, const float *signal, long n_clips, const long *offsets, int *labels,
@@ -393,7 +393,7 @@ int dsp_classify_batch_ragged_host(const dsp_classify_config *cfgp, const float 
 int dsp_classify_batch_ragged_pcm16_host(const dsp_classify_config *cfgp, const int16_t *pcm, long n_clips, const long *offsets, int channels,
                                          int stereo_mode, int *labels, dsp_classify_trace *trace)
 {
-    return front::ragged_host_entry<ClassifyCtx>(cfgp, pcm, front::pcm16_kind(channels, stereo_mode), n_clips, offsets, labels, trace);
+    return front::ragged_host_entry<ClassifyCtx>(cfgp, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, labels, trace);
 }
 
 /* A context of the caller's own: the default entry points share one workspace per device, so two calls on one device run one behind

@@ -240,13 +240,13 @@ int dsp_classify_batch_host_f64(const dsp_classify_config_f64 *cfgp, const doubl
 int dsp_classify_batch_pcm16_device_f64(const dsp_classify_config_f64 *cfgp, const int16_t *d_pcm, long n_clips, int n, long stride, int channels,
                                         int stereo_mode, int *d_labels, dsp_classify_trace_f64 *d_trace, void *stream)
 {
-    return front::device_entry<Scratch>(cfgp, d_pcm, front::pcm16_kind(channels, stereo_mode), n_clips, n, stride, d_labels, d_trace, stream);
+    return front::device_entry<Scratch>(cfgp, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, n, stride, d_labels, d_trace, stream);
 }
 
 int dsp_classify_batch_pcm16_host_f64(const dsp_classify_config_f64 *cfgp, const int16_t *pcm, long n_clips, int n, long stride, int channels,
                                       int stereo_mode, int *labels, dsp_classify_trace_f64 *trace)
 {
-    return front::host_entry<Scratch>(cfgp, pcm, front::pcm16_kind(channels, stereo_mode), n_clips, n, stride, labels, trace);
+    return front::host_entry<Scratch>(cfgp, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, n, stride, labels, trace);
 }
 
 int dsp_classify_batch_ragged_device_f64(const dsp_classify_config_f64 *cfgp, const double *d_signal, long n_clips, const long *offsets, int *d_labels,
@@ -258,7 +258,7 @@ int dsp_classify_batch_ragged_device_f64(const dsp_classify_config_f64 *cfgp, co
 int dsp_classify_batch_ragged_pcm16_device_f64(const dsp_classify_config_f64 *cfgp, const int16_t *d_pcm, long n_clips, const long *offsets, int channels,
                                                int stereo_mode, int *d_labels, dsp_classify_trace_f64 *d_trace, void *stream)
 {
-    return front::ragged_device_entry<Scratch>(cfgp, d_pcm, front::pcm16_kind(channels, stereo_mode), n_clips, offsets, d_labels, d_trace, stream);
+    return front::ragged_device_entry<Scratch>(cfgp, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, d_labels, d_trace, stream);
 }
 
 int dsp_classify_batch_ragged_host_f64(const dsp_classify_config_f64 *cfgp, const double *signal, long n_clips, const long *offsets, int *labels,
@@ -270,7 +270,7 @@ int dsp_classify_batch_ragged_host_f64(const dsp_classify_config_f64 *cfgp, cons
 int dsp_classify_batch_ragged_pcm16_host_f64(const dsp_classify_config_f64 *cfgp, const int16_t *pcm, long n_clips, const long *offsets, int channels,
                                              int stereo_mode, int *labels, dsp_classify_trace_f64 *trace)
 {
-    return front::ragged_host_entry<Scratch>(cfgp, pcm, front::pcm16_kind(channels, stereo_mode), n_clips, offsets, labels, trace);
+    return front::ragged_host_entry<Scratch>(cfgp, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, labels, trace);
 }
 
 int dsp_classify_stats_f64(int device, long *segments, long *undecided, long *listed_clips)

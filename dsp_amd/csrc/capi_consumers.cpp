@@ -161,6 +161,7 @@ int dsp_stop_predict_device(dsp_stop_model *m, const float *d_mfcc, long n_clips
 static int classify_signal_batch(dsp_mfcc_plan *plan, dsp_stop_model *m, const void *d_signal, int in_kind, int channels, int stereo_mode, long n_clips,
                                  int samples_per_clip, long clip_stride, float *d_prob, void *stream)
 {
+    if (in_kind < 0) return in_kind;
     if (!plan || !m || n_clips < 0 || (n_clips > 0 && (!d_signal || !d_prob))) return capi_fail(DSP_EINVAL, "bad argument");
     dsp_mfcc_config cfg;
     dsp_mfcc_plan_config(plan, &cfg);
@@ -171,17 +172,12 @@ static int classify_signal_batch(dsp_mfcc_plan *plan, dsp_stop_model *m, const v
     if (n_clips == 0) return DSP_OK;
     const int t = dsp_mfcc_frames_for(&cfg, samples_per_clip, m->m.max_frames);          // stop_detector.c:18-21
     {   // one kernel from PCM to probability when the plan is the reference's shape: the MFCC matrix is never written
-        const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, samples_per_clip, clip_stride, t, d_prob, stream, in_kind);
+        const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, clip_stride, t, d_prob, stream, in_kind);
         if (fused != 0) return fused < 0 ? fused : DSP_OK;
     }
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
-    const size_t need = (size_t)n_clips * (t > 0 ? t : 1) * cfg.n_mfcc * sizeof(float);
-    if (m->mfcc_cap < need) {
-        if (m->d_mfcc) { hipFree(m->d_mfcc); m->d_mfcc = nullptr; m->mfcc_cap = 0; }
-        DSP_CAPI_HIP(hipMalloc(&m->d_mfcc, need));
-        m->mfcc_cap = need;
-    }
+    DSP_CAPI_HIP(dsp::reserve(m->d_mfcc, m->mfcc_cap, (size_t)n_clips * (t > 0 ? t : 1) * cfg.n_mfcc * sizeof(float)));
     if (t > 0) {
         const int rc = in_kind == 0 ? dsp_mfcc_clips_device(plan, static_cast<const float *>(d_signal), n_clips, samples_per_clip, clip_stride, m->d_mfcc, m->m.max_frames, stream)
                                     : dsp_mfcc_clips_pcm16_device(plan, static_cast<const int16_t *>(d_signal), n_clips, samples_per_clip, clip_stride, channels,
@@ -203,10 +199,7 @@ int dsp_classify_signal_batch_device(dsp_mfcc_plan *plan, dsp_stop_model *m, con
 int dsp_classify_signal_batch_pcm16_device(dsp_mfcc_plan *plan, dsp_stop_model *m, const int16_t *d_pcm, long n_clips, int samples_per_clip,
                                            long clip_stride, int channels, int stereo_mode, float *d_prob, void *stream)
 {
-    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return classify_signal_batch(plan, m, d_pcm, kind, channels, stereo_mode, n_clips, samples_per_clip, clip_stride, d_prob, stream);
+    return classify_signal_batch(plan, m, d_pcm, dsp::pcm16_kind(channels, stereo_mode), channels, stereo_mode, n_clips, samples_per_clip, clip_stride, d_prob, stream);
 }
 
 // Ragged batches (main_test.c:254-331 loops over files of different lengths): one launch of the fused kernel, every clip with the
@@ -214,13 +207,14 @@ int dsp_classify_signal_batch_pcm16_device(dsp_mfcc_plan *plan, dsp_stop_model *
 static int classify_signal_batch_ragged(dsp_mfcc_plan *plan, dsp_stop_model *m, const void *d_signal, int in_kind, long n_clips, const long *offsets,
                                         float *d_prob, void *stream)
 {
+    if (in_kind < 0) return in_kind;
     if (!plan || !m || n_clips < 0 || !offsets || (n_clips > 0 && (!d_signal || !d_prob))) return capi_fail(DSP_EINVAL, "bad argument");
     dsp_mfcc_config cfg;
     dsp_mfcc_plan_config(plan, &cfg);
     if (cfg.n_mfcc != m->m.n_coef) return capi_fail(DSP_EINVAL, "plan n_mfcc differs from the model's n_coef");
     if (dsp::plan_device(plan) != m->device) return capi_fail(DSP_EINVAL, "plan and stop model live on different devices");
     if (n_clips == 0) return DSP_OK;
-    const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, 0, 0, 1, d_prob, stream, in_kind, offsets);
+    const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, 0, 1, d_prob, stream, in_kind, offsets);
     if (fused == 0) return capi_fail(DSP_EINVAL, "ragged batches run on the fused clip -> probability kernel: the reference's MFCC shape (dsp_mfcc_default_config), "
                                                  "a model with at most 4 first-layer units, an 8-byte aligned buffer (4 for mono int16)");
     return fused < 0 ? fused : DSP_OK;
@@ -235,10 +229,7 @@ int dsp_classify_signal_batch_ragged_device(dsp_mfcc_plan *plan, dsp_stop_model 
 int dsp_classify_signal_batch_ragged_pcm16_device(dsp_mfcc_plan *plan, dsp_stop_model *m, const int16_t *d_pcm, long n_clips, const long *offsets,
                                                   int channels, int stereo_mode, float *d_prob, void *stream)
 {
-    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
-    const int kind = channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-    return classify_signal_batch_ragged(plan, m, d_pcm, kind, n_clips, offsets, d_prob, stream);
+    return classify_signal_batch_ragged(plan, m, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, d_prob, stream);
 }
 
 float dsp_classify_signal(dsp_stop_model *m, const float *signal, int num_samples)
@@ -339,17 +330,14 @@ int dsp_speaker_llr_ragged_device(dsp_speaker_model *m, const float *d_mfcc, lon
             return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " of the ragged MFCC matrix has no frames (the LLR is a mean over the clip's frames)");
     DSP_ON_DEVICE(m->device);
     const size_t bytes = (size_t)(n_clips + 1) * sizeof(long);
-    dsp::SpanRing::Slot *slot = nullptr;
-    DSP_CAPI_HIP(m->rows.acquire(bytes, &slot));
-    std::memcpy(slot->h, frame_offsets, bytes);
-    const hipError_t up = dsp::SpanRing::upload(slot, bytes, (hipStream_t)stream);
+    dsp::SpanRing::Lease slot;
+    DSP_CAPI_HIP(m->rows.acquire(bytes, slot));
+    std::memcpy(slot.h(), frame_offsets, bytes);
+    DSP_CAPI_HIP(slot.upload(bytes, (hipStream_t)stream));
     const long long threshold = (long long)(-0.7 * (1 << 8));                              // speaker_gmm.c:124-125
-    const hipError_t e = up != hipSuccess ? up
-                         : dsp::launch_speaker_llr_ragged(m->target, m->ubm, d_mfcc, n_clips, static_cast<const long *>(slot->d), threshold,
-                                                          reinterpret_cast<long long *>(d_llr_mean), d_labels, reinterpret_cast<long long *>(d_ll_target),
-                                                          reinterpret_cast<long long *>(d_ll_ubm), (hipStream_t)stream);
-    dsp::SpanRing::mark(slot, (hipStream_t)stream);
-    DSP_CAPI_HIP(e);
+    DSP_CAPI_HIP(dsp::launch_speaker_llr_ragged(m->target, m->ubm, d_mfcc, n_clips, static_cast<const long *>(slot.d()), threshold,
+                                                reinterpret_cast<long long *>(d_llr_mean), d_labels, reinterpret_cast<long long *>(d_ll_target),
+                                                reinterpret_cast<long long *>(d_ll_ubm), (hipStream_t)stream));
     return DSP_OK;
 }
 
@@ -448,20 +436,18 @@ static long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, lon
     return wo[n];
 }
 
-// per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to], n + 1 longs each, into a ring slot, uploaded
-static hipError_t scan_upload(dsp::SpanRing &ring, const long *frame_offsets, long n, const long *wo, const long *to, dsp::SpanRing::Slot **out,
+// per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to], n + 1 longs each, into a leased ring slot, uploaded
+static hipError_t scan_upload(dsp::SpanRing &ring, const long *frame_offsets, long n, const long *wo, const long *to, dsp::SpanRing::Lease &slot,
                               void *stream)
 {
     const size_t one = (size_t)(n + 1) * sizeof(long), bytes = (to ? 3 : 2) * one;
-    dsp::SpanRing::Slot *slot = nullptr;
-    const hipError_t e = ring.acquire(bytes, &slot);
+    const hipError_t e = ring.acquire(bytes, slot);
     if (e != hipSuccess) return e;
-    long *h = static_cast<long *>(slot->h);
+    long *h = static_cast<long *>(slot.h());
     for (long r = 0; r <= n; ++r) h[r] = frame_offsets[r] - frame_offsets[0];
     std::memcpy(h + (n + 1), wo, one);
     if (to) std::memcpy(h + 2 * (n + 1), to, one);
-    *out = slot;
-    return dsp::SpanRing::upload(slot, bytes, (hipStream_t)stream);
+    return slot.upload(bytes, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -485,16 +471,12 @@ int dsp_stop_scan_device(dsp_stop_model *m, const float *d_mfcc, long n_recordin
     const long rows = frame_offsets[n_recordings] - frame_offsets[0];
     if (rows > 0 && !d_mfcc) return capi_fail(DSP_EINVAL, "d_mfcc is NULL");
     DSP_ON_DEVICE(m->device);
-    dsp::SpanRing::Slot *slot = nullptr;
-    hipError_t e = scan_upload(m->scan, frame_offsets, n_recordings, wo.data(), to.data(), &slot, stream);
-    if (e == hipSuccess) {
-        const long *d = static_cast<const long *>(slot->d);
-        e = dsp::launch_stop_scan(m->m, rows > 0 ? d_mfcc + frame_offsets[0] * m->m.n_coef : d_mfcc, n_recordings, d, d + (n_recordings + 1),
-                                  d + 2 * (n_recordings + 1), to[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, tw, d_prob,
-                                  (hipStream_t)stream);
-    }
-    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
-    DSP_CAPI_HIP(e);
+    dsp::SpanRing::Lease slot;
+    DSP_CAPI_HIP(scan_upload(m->scan, frame_offsets, n_recordings, wo.data(), to.data(), slot, stream));
+    const long *d = static_cast<const long *>(slot.d());
+    DSP_CAPI_HIP(dsp::launch_stop_scan(m->m, rows > 0 ? d_mfcc + frame_offsets[0] * m->m.n_coef : d_mfcc, n_recordings, d, d + (n_recordings + 1),
+                                       d + 2 * (n_recordings + 1), to[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, tw, d_prob,
+                                       (hipStream_t)stream));
     return DSP_OK;
 }
 
@@ -514,22 +496,14 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
     const size_t need = (size_t)(rows + (rows + dsp::kLlrScanChunk - 1) / dsp::kLlrScanChunk) * sizeof(unsigned long long);
-    if (m->scan_cap < need) {
-        if (m->d_scan) { hipFree(m->d_scan); m->d_scan = nullptr; m->scan_cap = 0; }
-        if (hipMalloc(&m->d_scan, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (speaker scan workspace)");
-        m->scan_cap = need;
-    }
-    dsp::SpanRing::Slot *slot = nullptr;
-    hipError_t e = scan_upload(m->rows, frame_offsets, n_recordings, wo.data(), nullptr, &slot, stream);
-    if (e == hipSuccess) {
-        const long *d = static_cast<const long *>(slot->d);
-        const long long threshold = (long long)(-0.7 * (1 << 8));                              // speaker_gmm.c:124-125
-        e = dsp::launch_speaker_scan(m->target, m->ubm, d_mfcc + frame_offsets[0] * m->target.d, rows, n_recordings, d, d + (n_recordings + 1),
-                                     wo[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, threshold, m->d_scan,
-                                     reinterpret_cast<long long *>(d_llr_mean), d_labels, (hipStream_t)stream);
-    }
-    if (slot) dsp::SpanRing::mark(slot, (hipStream_t)stream);
-    DSP_CAPI_HIP(e);
+    if (dsp::reserve(m->d_scan, m->scan_cap, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (speaker scan workspace)");
+    dsp::SpanRing::Lease slot;
+    DSP_CAPI_HIP(scan_upload(m->rows, frame_offsets, n_recordings, wo.data(), nullptr, slot, stream));
+    const long *d = static_cast<const long *>(slot.d());
+    const long long threshold = (long long)(-0.7 * (1 << 8));                              // speaker_gmm.c:124-125
+    DSP_CAPI_HIP(dsp::launch_speaker_scan(m->target, m->ubm, d_mfcc + frame_offsets[0] * m->target.d, rows, n_recordings, d, d + (n_recordings + 1),
+                                          wo[(size_t)n_recordings], cfg->window_frames, cfg->hop_frames, threshold, m->d_scan,
+                                          reinterpret_cast<long long *>(d_llr_mean), d_labels, (hipStream_t)stream));
     return DSP_OK;
 }
 
@@ -548,10 +522,11 @@ struct dsp_scanner {
     std::mutex mu;
 };
 
-// in_kind 0 float samples, 1 int16 (channels / stereo_mode as dsp_mfcc_clips_ragged_pcm16_device)
+// in_kind 0 float samples, 1 / 2 / 3 int16 (channels / stereo_mode as dsp_mfcc_clips_ragged_pcm16_device), < 0 an error of dsp::pcm16_kind
 static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int channels, int stereo_mode, long n, const long *offsets, float *d_prob,
                        int64_t *d_llr_mean, int *d_labels, void *stream)
 {
+    if (in_kind < 0) return in_kind;
     if (!s || n < 0) return capi_fail(DSP_EINVAL, "bad argument (scanner, n_recordings >= 0)");
     if (n == 0) return DSP_OK;
     if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");
@@ -570,12 +545,8 @@ static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int ch
     if (rows > 0) {
         if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
         DSP_ON_DEVICE(s->device);
-        const size_t need = (size_t)rows * s->n_mfcc * sizeof(float);
-        if (s->mfcc_cap < need) {
-            if (s->d_mfcc) { hipFree(s->d_mfcc); s->d_mfcc = nullptr; s->mfcc_cap = 0; }
-            if (hipMalloc(&s->d_mfcc, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
-            s->mfcc_cap = need;
-        }
+        if (dsp::reserve(s->d_mfcc, s->mfcc_cap, (size_t)rows * s->n_mfcc * sizeof(float)) != hipSuccess)
+            return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
         const int rc = in_kind == 0 ? dsp_mfcc_clips_ragged_device(s->plan, static_cast<const float *>(d_signal), n, offsets, INT_MAX, s->d_mfcc, stream)
                                     : dsp_mfcc_clips_ragged_pcm16_device(s->plan, static_cast<const int16_t *>(d_signal), n, offsets, channels, stereo_mode,
                                                                          INT_MAX, s->d_mfcc, stream);
@@ -641,9 +612,7 @@ int dsp_scanner_run_device(dsp_scanner *s, const float *d_signal, long n_recordi
 int dsp_scanner_run_pcm16_device(dsp_scanner *s, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels, int stereo_mode,
                                  float *d_prob, int64_t *d_llr_mean, int *d_labels, void *stream)
 {
-    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
-    return scanner_run(s, d_pcm, 1, channels, stereo_mode, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
+    return scanner_run(s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), channels, stereo_mode, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
 }
 
 }  // extern "C"

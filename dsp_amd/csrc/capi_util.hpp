@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <climits>
+#include <condition_variable>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -19,30 +21,70 @@ struct StopModelDev;
 // Returns 1 when the fused kernel was enqueued, 0 when this plan / model shape has no fused form (the caller runs the two-kernel
 // path), < 0 on error.  t = frames per clip (already capped at the model's max_frames).
 // in_kind: 0 float samples, 1 / 2 / 3 int16 mono / stereo channel 0 / stereo average
-int stop_fused_device(dsp_mfcc_plan *plan, const StopModelDev &m, const void *d_signal, long n_clips, int samples_per_clip,
-                      long clip_stride, int t, float *d_prob, void *stream, int in_kind = 0, const long *offsets = nullptr);
-// offsets != nullptr: a ragged batch (clip c = samples [offsets[c], offsets[c + 1]) per channel; samples_per_clip, clip_stride and t unused)
+int stop_fused_device(dsp_mfcc_plan *plan, const StopModelDev &m, const void *d_signal, long n_clips, long clip_stride, int t, float *d_prob,
+                      void *stream, int in_kind = 0, const long *offsets = nullptr);
+// offsets != nullptr: a ragged batch (clip c = samples [offsets[c], offsets[c + 1]) per channel; clip_stride and t unused)
 int plan_device(const dsp_mfcc_plan *plan);          // the GPU a plan lives on
 }
 
 // Ragged batches: the clips' spans (clip_span.hpp ClipSpan: start, samples, frames, caller's index -- 32 bytes per clip) travel to the GPU through a
 // small ring of pinned host / device buffer pairs, so that a call neither waits for the stream it enqueues on nor shares a buffer with
-// the call before it (which may still be running, on this stream or another).  A slot is reused only after the event recorded behind
-// the kernels that read it.
+// the call before it (which may still be running, on this stream or another).  A call holds its slot as a Lease: fill h(), upload(),
+// enqueue the kernels that read d(), and the lease's end -- on every exit -- records the slot's event behind them on the upload's stream
+// and hands the slot back.  A slot is reused only after that event: an acquirer that lands on a slot still leased waits for the lease to
+// end, then for the event.
+// Deadlock-free because no call holds two leases of one ring at once (each user takes one lease, launches, and lets it go before
+// it could ask the ring again), and no one waits for a lease while holding a lock a lease holder takes.
 namespace dsp {
 struct ClipSpan;
 struct SpanRing {
     static constexpr int kSlots = 4;
-    struct Slot { void *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
+    struct Slot { void *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false, held = false; };
+    class Lease {
+        friend struct SpanRing;
+        SpanRing *ring = nullptr;
+        Slot *s = nullptr;
+        hipStream_t st = nullptr;
+        bool uploaded = false;
+    public:
+        Lease() = default;
+        Lease(const Lease &) = delete;
+        Lease &operator=(const Lease &) = delete;
+        ~Lease()
+        {
+            if (!s) return;
+            if (uploaded) { s->used = hipEventRecord(s->done, st) == hipSuccess; if (!s->used) (void)hipStreamSynchronize(st); }
+            std::lock_guard<std::mutex> lock(ring->mu);
+            s->held = false;
+            ring->freed.notify_all();
+        }
+        void *h() const { return s->h; }
+        void *d() const { return s->d; }
+        hipError_t upload(size_t bytes, hipStream_t stream)
+        {
+            st = stream;
+            uploaded = true;
+            return hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, stream);
+        }
+    };
     Slot slot[kSlots];
     int next = 0;
     std::mutex mu;
-    // a slot with room for `bytes`, its previous user finished; fill slot->h, then upload(), launch, then mark()
-    hipError_t acquire(size_t bytes, Slot **out)
+    std::condition_variable freed;
+    // `out` (empty) leases a slot with room for `bytes` whose previous user has finished
+    hipError_t acquire(size_t bytes, Lease &out)
     {
-        std::lock_guard<std::mutex> lock(mu);
-        Slot &s = slot[next];
-        next = (next + 1) % kSlots;
+        Slot *sp;
+        {
+            std::unique_lock<std::mutex> lock(mu);
+            sp = &slot[next];
+            next = (next + 1) % kSlots;
+            freed.wait(lock, [sp] { return !sp->held; });
+            sp->held = true;
+        }
+        out.ring = this;
+        out.s = sp;
+        Slot &s = *sp;
         hipError_t e;
         if (!s.done && (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return e;
         if (s.used && (e = hipEventSynchronize(s.done)) != hipSuccess) return e;
@@ -56,13 +98,9 @@ struct SpanRing {
             if ((e = hipMalloc(&s.d, cap)) != hipSuccess) return e;
             s.cap = cap;
         }
-        *out = &s;
         return hipSuccess;
     }
-    static hipError_t upload(Slot *s, size_t bytes, hipStream_t st) { return hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, st); }
-    // after the last kernel that reads the slot has been enqueued (also on error exits once upload() ran)
-    static void mark(Slot *s, hipStream_t st) { s->used = hipEventRecord(s->done, st) == hipSuccess; if (!s->used) (void)hipStreamSynchronize(st); }
-    void release()      // on the owner's device
+    void release()      // on the owner's device, no lease outstanding
     {
         std::lock_guard<std::mutex> lock(mu);
         for (Slot &s : slot) {
@@ -74,6 +112,35 @@ struct SpanRing {
         }
     }
 };
+
+// clip c of a ragged batch is samples [offsets[c], offsets[c + 1]) per channel: its length, or DSP_EINVAL naming the clip
+inline long ragged_clip_length(const long *offsets, long c)
+{
+    const long n = offsets[c + 1] - offsets[c];
+    if (offsets[c] < 0 || n < 0 || n > INT32_MAX)
+        return capi_fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples (clip " + std::to_string(c) + ")");
+    return n;
+}
+
+// the input kind of int16 PCM (1 / 2 / 3: mono / stereo channel 0 / stereo average), or DSP_EINVAL
+inline int pcm16_kind(int channels, int stereo_mode)
+{
+    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
+    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
+    return channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
+}
+
+// a grow-only device workspace: buf holds at least `bytes` afterwards (its contents are not kept), or is NULL on an error
+template <class T> hipError_t reserve(T *&buf, size_t &cap, size_t bytes)
+{
+    if (cap >= bytes) return hipSuccess;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc(&buf, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
 }
 
 // order[i] = index of the i-th largest key, ties in input order (what std::stable_sort gives) -- by counting: a ragged batch of 125 000

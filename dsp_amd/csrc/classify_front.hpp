@@ -100,14 +100,6 @@ template <class W> int release_devices(int device)      // device < 0: all of th
     return DSP_OK;
 }
 
-// the input kind of int16 PCM, or DSP_EINVAL: the entries below take it as `in` and return a negative one first
-inline int pcm16_kind(int channels, int stereo_mode)
-{
-    if (channels != 1 && channels != 2) return capi_fail(DSP_EINVAL, "channels must be 1 or 2");
-    if (channels == 2 && stereo_mode != DSP_STEREO_CHANNEL0 && stereo_mode != DSP_STEREO_AVERAGE) return capi_fail(DSP_EINVAL, "bad stereo_mode");
-    return channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
-}
-
 // the device of the host entries: DSP_AMD_DEVICE or 0
 inline int host_device(int &device)
 {
@@ -234,8 +226,8 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
 {
     int rc = DSP_OK, n_max = 0;
     for (long c = 0; c < n_clips; ++c) {
-        const long n = offsets[c + 1] - offsets[c];
-        if (offsets[c] < 0 || n < 0 || n > INT32_MAX) return capi_fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples");
+        const long n = ragged_clip_length(offsets, c);
+        if (n < 0) return (int)n;
         if (columns((int)n) > kMaxColumns) return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
         n_max = std::max(n_max, (int)n);
     }
@@ -261,20 +253,19 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
     for (long c = 0; c < n_clips; ++c) segs[c] = columns((int)(offsets[c + 1] - offsets[c]));
     order_by_key_desc(segs.data(), n_clips, columns(n_max), order.data());
     const size_t span_bytes = (size_t)n_clips * sizeof(ClipSpan), perm_bytes = (size_t)n_clips * sizeof(int);
-    SpanRing::Slot *slot = nullptr;
-    DSP_CAPI_HIP(w.spans.acquire(span_bytes + perm_bytes, &slot));
-    ClipSpan *h = static_cast<ClipSpan *>(slot->h);
+    SpanRing::Lease slot;
+    DSP_CAPI_HIP(w.spans.acquire(span_bytes + perm_bytes, slot));
+    ClipSpan *h = static_cast<ClipSpan *>(slot.h());
     for (long i = 0; i < n_clips; ++i) {
         const long c = order[i];
         h[i] = ClipSpan{offsets[c], (int)(offsets[c + 1] - offsets[c]), segs[c], c, 0};
     }
-    std::memcpy(static_cast<char *>(slot->h) + span_bytes, order.data(), perm_bytes);
+    std::memcpy(static_cast<char *>(slot.h()) + span_bytes, order.data(), perm_bytes);
     if (w.pending) DSP_CAPI_HIP(hipStreamWaitEvent(st, w.done, 0));         // the previous call's work on this workspace (any stream)
-    struct SlotMark { SpanRing::Slot *s; hipStream_t st; ~SlotMark() { SpanRing::mark(s, st); } } slot_mark{slot, st};
-    DSP_CAPI_HIP(SpanRing::upload(slot, span_bytes + perm_bytes, st));
+    DSP_CAPI_HIP(slot.upload(span_bytes + perm_bytes, st));
     BusyMark mark{w, st};
-    const ClipSpan *d_spans = static_cast<const ClipSpan *>(slot->d);
-    const int *d_perm = reinterpret_cast<const int *>(static_cast<const char *>(slot->d) + span_bytes);
+    const ClipSpan *d_spans = static_cast<const ClipSpan *>(slot.d());
+    const int *d_perm = reinterpret_cast<const int *>(static_cast<const char *>(slot.d()) + span_bytes);
     // Passes: as many clips as a pass of equal 1 s clips has SEGMENTS for (the workspaces are [clip][segments of the pass's longest clip]):
     // few clips per pass while they are long, the full sub-batch once they are short
     // (four times that before a pass is cut short: a small remainder pass costs a whole clip's sequential chain for few clips -- 0.5 - 1.5 s

@@ -282,6 +282,48 @@ def c_offsets(offsets):
     return (C.c_long * a.size)(*a.tolist()), a.size - 1
 
 
+def clips_device(clips, dtype):
+    """Equal clips on the GPU: a `dtype` CUDA tensor [n_clips][n] with unit inner stride, or ValueError."""
+    import torch
+    if not (isinstance(clips, torch.Tensor) and clips.is_cuda and clips.dtype == dtype and clips.dim() == 2 and clips.stride(1) == 1):
+        raise ValueError(f"clips must be a {str(dtype).replace('torch.', '')} CUDA tensor [n_clips][n] with unit inner stride")
+    return clips
+
+
+def pcm_device(pcm):
+    """cuda int16 [n_clips][n] or interleaved [n_clips][n][2] -> (channels, clip stride in samples per channel), or ValueError."""
+    import torch
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (2, 3) and pcm.stride(-1) == 1):
+        raise ValueError("pcm must be an int16 CUDA tensor [n_clips][n] or [n_clips][n][2] with unit inner stride")
+    channels = 2 if pcm.dim() == 3 else 1
+    if channels == 2 and (pcm.shape[2] != 2 or pcm.stride(1) != 2 or pcm.stride(0) % 2):
+        raise ValueError("stereo pcm must be interleaved [n_clips][n][2]")
+    return channels, pcm.stride(0) // channels
+
+
+def ragged_signal(signal, offsets, float_dtype):
+    """A ragged batch on the GPU: `signal` a contiguous CUDA tensor -- float_dtype [total], int16 [total] or interleaved int16 [total][2] --
+    and clip c = samples [offsets[c], offsets[c + 1]) per channel (offsets as c_offsets takes them, or the (array, n_clips) pair it
+    returned: no conversion per call).  -> (offsets array, n_clips, channels (0: float samples), signal pointer), or ValueError."""
+    import torch
+    off, n = offsets if isinstance(offsets, tuple) else c_offsets(offsets)
+    if not (isinstance(signal, torch.Tensor) and signal.is_cuda and signal.is_contiguous()):
+        raise ValueError("signal must be a contiguous CUDA tensor")
+    if signal.dtype == torch.int16:
+        if not (signal.dim() == 1 or (signal.dim() == 2 and signal.shape[1] == 2)):
+            raise ValueError("int16 signal must be [total] (mono) or [total][2] (interleaved stereo)")
+        channels = signal.dim()
+    elif signal.dtype == float_dtype:
+        if signal.dim() != 1:
+            raise ValueError("float signal must be 1-D [total]")
+        channels = 0
+    else:
+        raise ValueError(f"signal must be {str(float_dtype).replace('torch.', '')} or int16")
+    if n and int(off[n]) > signal.shape[0]:
+        raise ValueError("offsets run past the end of the signal")
+    return off, n, channels, signal.data_ptr()
+
+
 def check(rc: int, what: str) -> int:
     if rc < 0:
         raise DspError(f"{what} failed ({rc}): {last_error()}")

@@ -133,15 +133,13 @@ class MfccPlan:
         """pcm: cuda int16 [n_clips][samples] (mono) or [n_clips][samples][2] (interleaved stereo;
         stereo_mode 0 = channel 0, 1 = channel average) -> cuda float32 [n_clips][T][n_mfcc]."""
         import torch
-        if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.dim() in (2, 3)):
-            raise ValueError("pcm must be a contiguous int16 CUDA tensor [n_clips][samples] or [n_clips][samples][2]")
-        channels = 1 if pcm.dim() == 2 else int(pcm.shape[2])
+        channels, stride = _lib.pcm_device(pcm)
         n, s = int(pcm.shape[0]), int(pcm.shape[1])
         t = frames_for(self.cfg, s, max_frames)
         if out is None:
             out = torch.empty((n, t, self.cfg.n_mfcc), dtype=torch.float32, device=pcm.device)
         if n and t:
-            got = _lib.check(self._L.dsp_mfcc_clips_pcm16_device(self._h, pcm.data_ptr(), n, s, s, channels, int(stereo_mode),
+            got = _lib.check(self._L.dsp_mfcc_clips_pcm16_device(self._h, pcm.data_ptr(), n, s, stride, channels, int(stereo_mode),
                                                                   out.data_ptr(), int(max_frames), self._stream()), "dsp_mfcc_clips_pcm16_device")
             assert got == t
         return out
@@ -149,9 +147,7 @@ class MfccPlan:
     def clips(self, clips, max_frames: int, out=None):
         """clips: cuda float32 [n_clips][samples] -> cuda float32 [n_clips][T][n_mfcc]."""
         import torch
-        if not (clips.is_cuda and clips.dtype == torch.float32 and clips.dim() == 2 and clips.stride(1) == 1):
-            raise ValueError("clips must be a float32 CUDA tensor [n_clips][samples] with unit inner stride")
-        n, s = clips.shape
+        n, s = _lib.clips_device(clips, torch.float32).shape
         t = frames_for(self.cfg, s, max_frames)
         if out is None:
             out = torch.empty((n, t, self.cfg.n_mfcc), dtype=torch.float32, device=clips.device)
@@ -167,30 +163,17 @@ class MfccPlan:
         cuda float32 [F][n_mfcc] with clip c's frames in rows [frame_offsets[c], frame_offsets[c + 1]) (numpy int64 [n_clips + 1]),
         each row bit for bit what a one-clip clips / clips_pcm16 call gives; clips shorter than a frame have no rows."""
         import torch
-        off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
         fo = ragged_frame_offsets(self.cfg, (off, n), max_frames)
         total = int(fo[-1])
-        if not (signal.is_cuda and signal.is_contiguous()):
-            raise ValueError("signal must be a contiguous CUDA tensor")
-        if signal.dtype == torch.float32:
-            if signal.dim() != 1:
-                raise ValueError("float32 signal must be 1-D [total]")
-        elif signal.dtype == torch.int16:
-            if not (signal.dim() == 1 or (signal.dim() == 2 and signal.shape[1] == 2)):
-                raise ValueError("int16 signal must be [total] (mono) or [total][2] (interleaved stereo)")
-        else:
-            raise ValueError("signal must be float32 or int16")
-        if n and int(off[n]) > signal.shape[0]:
-            raise ValueError("offsets run past the end of the signal")
         if out is None:
             out = torch.empty((total, self.cfg.n_mfcc), dtype=torch.float32, device=signal.device)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total * self.cfg.n_mfcc):
             raise ValueError(f"out must be a contiguous float32 CUDA tensor of at least [{total}][{self.cfg.n_mfcc}]")
-        if total:
-            if signal.dtype == torch.float32:
-                _lib.check(self._L.dsp_mfcc_clips_ragged_device(self._h, signal.data_ptr(), n, off, int(max_frames), out.data_ptr(), self._stream()),
-                           "dsp_mfcc_clips_ragged_device")
-            else:
-                _lib.check(self._L.dsp_mfcc_clips_ragged_pcm16_device(self._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode), int(max_frames),
-                                                                      out.data_ptr(), self._stream()), "dsp_mfcc_clips_ragged_pcm16_device")
+        if total and channels:
+            _lib.check(self._L.dsp_mfcc_clips_ragged_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), int(max_frames), out.data_ptr(),
+                                                                  self._stream()), "dsp_mfcc_clips_ragged_pcm16_device")
+        elif total:
+            _lib.check(self._L.dsp_mfcc_clips_ragged_device(self._h, ptr, n, off, int(max_frames), out.data_ptr(), self._stream()),
+                       "dsp_mfcc_clips_ragged_device")
         return out, fo

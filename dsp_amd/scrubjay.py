@@ -25,7 +25,8 @@ class SvmModel:
         a = {k: np.ascontiguousarray(attrs[k], np.float32) for k in ("offset", "scale", "sv", "coef")}
         self.n_features = a["offset"].size
         self.n_sv = a["coef"].size
-        assert a["sv"].shape == (self.n_sv, self.n_features)
+        if a["sv"].shape != (self.n_sv, self.n_features):
+            raise ValueError(f"sv must be [n_sv][n_features] = [{self.n_sv}][{self.n_features}]")
         h = C.c_void_p()
         _lib.check(self._L.dsp_svm_create(device, self.n_features, self.n_sv, a["offset"].ctypes.data, a["scale"].ctypes.data,
                                           a["sv"].ctypes.data, a["coef"].ctypes.data,
@@ -101,13 +102,12 @@ class ScrubJay:
             feat = mfcc_stats(mfcc)
             return self.svm.predict(feat) + (feat,)
         import torch
-        n = clips.shape[0]
+        n = _lib.clips_device(clips, torch.float32).shape[0]
         labels = torch.empty(n, dtype=torch.int32, device=clips.device)
         dec = torch.empty(n, dtype=torch.float32, device=clips.device)
         p1 = torch.empty(n, dtype=torch.float32, device=clips.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=clips.device)
         st = C.c_void_p(torch.cuda.current_stream(clips.device).cuda_stream)
-        assert clips.dim() == 2 and clips.stride(1) == 1
         _lib.check(_lib.load().dsp_scrubjay_fused_device(self.plan._h, self.svm._h, clips.data_ptr(), n, clips.shape[1], clips.stride(0),
                                                          int(min(max_frames, 1 << 30)), labels.data_ptr(), dec.data_ptr(), p1.data_ptr(),
                                                          feat.data_ptr(), st), "dsp_scrubjay_fused_device")
@@ -117,15 +117,14 @@ class ScrubJay:
         """The fused clip -> label kernel on int16 PCM [n_clips][n] (mono) or [n_clips][n][2] (interleaved stereo: channel 0 or the
         channels' average), converted in the kernel's load (dsp_scrubjay_fused_pcm16_device): the float path's results, bit for bit."""
         import torch
-        assert pcm.dtype == torch.int16 and pcm.dim() in (2, 3) and pcm.stride(-1) == 1
-        channels = 2 if pcm.dim() == 3 else 1
+        channels, stride = _lib.pcm_device(pcm)
         n = pcm.shape[0]
         labels = torch.empty(n, dtype=torch.int32, device=pcm.device)
         dec = torch.empty(n, dtype=torch.float32, device=pcm.device)
         p1 = torch.empty(n, dtype=torch.float32, device=pcm.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=pcm.device)
         st = C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
-        _lib.check(_lib.load().dsp_scrubjay_fused_pcm16_device(self.plan._h, self.svm._h, pcm.data_ptr(), n, pcm.shape[1], pcm.stride(0) // channels,
+        _lib.check(_lib.load().dsp_scrubjay_fused_pcm16_device(self.plan._h, self.svm._h, pcm.data_ptr(), n, pcm.shape[1], stride,
                                                                channels, int(stereo_mode), int(min(max_frames, 1 << 30)), labels.data_ptr(), dec.data_ptr(),
                                                                p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_pcm16_device")
         return labels, dec, p1, feat
@@ -135,21 +134,18 @@ class ScrubJay:
         float32 [total], int16 [total] or interleaved stereo int16 [total][2] -- and clip c is samples [offsets[c], offsets[c + 1]).
         Results as a one-clip call per clip gives them (dsp_scrubjay_fused_ragged_device / _pcm16_device)."""
         import torch
-        off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)      # (a prepared (ctypes array, n_clips) pair: no conversion per call)
-        assert signal.is_cuda and signal.stride(-1) == 1 and int(off[n]) <= signal.shape[0]
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
         labels = torch.empty(n, dtype=torch.int32, device=signal.device)
         dec = torch.empty(n, dtype=torch.float32, device=signal.device)
         p1 = torch.empty(n, dtype=torch.float32, device=signal.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=signal.device)
         st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
         mf = int(min(max_frames, 1 << 30))
-        if signal.dtype == torch.float32:
-            assert signal.dim() == 1
-            _lib.check(_lib.load().dsp_scrubjay_fused_ragged_device(self.plan._h, self.svm._h, signal.data_ptr(), n, off, mf, labels.data_ptr(), dec.data_ptr(),
-                                                                    p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_ragged_device")
-        else:
-            assert signal.dtype == torch.int16 and signal.dim() in (1, 2)
-            _lib.check(_lib.load().dsp_scrubjay_fused_ragged_pcm16_device(self.plan._h, self.svm._h, signal.data_ptr(), n, off, signal.dim(), int(stereo_mode), mf,
+        if channels:
+            _lib.check(_lib.load().dsp_scrubjay_fused_ragged_pcm16_device(self.plan._h, self.svm._h, ptr, n, off, channels, int(stereo_mode), mf,
                                                                           labels.data_ptr(), dec.data_ptr(), p1.data_ptr(), feat.data_ptr(), st),
                        "dsp_scrubjay_fused_ragged_pcm16_device")
+        else:
+            _lib.check(_lib.load().dsp_scrubjay_fused_ragged_device(self.plan._h, self.svm._h, ptr, n, off, mf, labels.data_ptr(), dec.data_ptr(),
+                                                                    p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_ragged_device")
         return labels, dec, p1, feat

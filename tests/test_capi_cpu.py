@@ -204,7 +204,12 @@ def test_ragged_batches_are_ordered_for_an_even_deal():
     assert lib.dsp_debug_fused_spans(C.byref(cfg), c_bad, 2, 500, 4, out) == -1 and b"clip 1" in lib.dsp_last_error()
     back = np.array([0, 16000, 8000], dtype=np.int64)
     c_back, _ = L.c_offsets(back)
-    assert lib.dsp_debug_fused_spans(C.byref(cfg), c_back, 2, 500, 4, out) == -1 and b"non-decreasing" in lib.dsp_last_error()
+    assert lib.dsp_debug_fused_spans(C.byref(cfg), c_back, 2, 500, 4, out) == -1
+    assert b"non-decreasing" in lib.dsp_last_error() and b"clip 1" in lib.dsp_last_error()
+    for bad, clip in (([-4, 16000, 32000], b"clip 0"), ([0, 16000, 16000 + 2**31], b"clip 1")):      # (the offsets check of every ragged batch)
+        c_bad, _ = L.c_offsets(np.array(bad, dtype=np.int64))
+        assert lib.dsp_debug_fused_spans(C.byref(cfg), c_bad, 2, 500, 4, out) == -1
+        assert b"non-decreasing" in lib.dsp_last_error() and clip in lib.dsp_last_error()
     # the classifiers' ragged entry points refuse bad arguments before any GPU call
     lab = (C.c_int * 2)()
     assert lib.dsp_classify_batch_ragged_host(None, None, 2, c_back, lab, None) == -1
@@ -274,6 +279,37 @@ def test_ragged_wrappers_refuse_offsets_past_the_buffer_under_python_optimize():
             "try:\n"
             "    dsp_amd.classify_ragged(np.zeros(1000, np.float32), [[0, 600]])\n"
             "except ValueError:\n"
-            "    print('ok')\n") % ROOT
+            "    pass\n"
+            "else:\n"
+            "    raise SystemExit('no ValueError for 2-D offsets')\n"
+            # the device wrappers' shared checks (dsp_amd/lib.py), reached with a CPU tensor and a non-tensor: ValueError before any
+            # plan, model or device is touched (self = None)
+            "import torch\n"
+            "from dsp_amd import lib\n"
+            "from dsp_amd.scrubjay import ScrubJay\n"
+            "f32, pcm = torch.float32, torch.zeros((2, 800), dtype=torch.int16)\n"
+            "for sig in (torch.zeros(1200), np.zeros(1200, np.float32)):\n"
+            "    for call in (lambda: lib.ragged_signal(sig, [0, 600, 1200], f32), lambda: dsp_amd.classify_device_ragged(sig, [0, 600]),\n"
+            "                 lambda: dsp_amd.classify_device_ragged_f64(sig, [0, 600]), lambda: dsp_amd.MfccPlan.clips_ragged(None, sig, [0, 600], 500),\n"
+            "                 lambda: ScrubJay.ragged(None, sig, [0, 600]), lambda: dsp_amd.StopModel.classify_signal_ragged(None, None, sig, [0, 600]),\n"
+            "                 lambda: dsp_amd.Scanner.run(None, sig, [0, 600]), lambda: lib.clips_device(sig, f32), lambda: lib.pcm_device(sig),\n"
+            "                 lambda: dsp_amd.MfccPlan.clips(None, sig, 500), lambda: ScrubJay.__call__(None, sig),\n"
+            "                 lambda: dsp_amd.StopModel.classify_signal_batch(None, None, sig), lambda: dsp_amd.classify_device(sig)):\n"
+            "        try:\n"
+            "            call()\n"
+            "        except ValueError:\n"
+            "            pass\n"
+            "        else:\n"
+            "            raise SystemExit('no ValueError from a check of a ' + type(sig).__name__)\n"
+            "for call in (lambda: lib.pcm_device(pcm), lambda: dsp_amd.MfccPlan.clips_pcm16(None, pcm, 500), lambda: ScrubJay.pcm16(None, pcm),\n"
+            "             lambda: dsp_amd.StopModel.classify_signal_batch_pcm16(None, None, pcm), lambda: dsp_amd.classify_device_pcm16(pcm),\n"
+            "             lambda: dsp_amd.classify_device_f64_pcm16(pcm)):\n"
+            "    try:\n"
+            "        call()\n"
+            "    except ValueError:\n"
+            "        pass\n"
+            "    else:\n"
+            "        raise SystemExit('no ValueError for CPU PCM')\n"
+            "print('ok')\n") % ROOT
     r = subprocess.run([sys.executable, "-O", "-s", "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr

@@ -154,6 +154,44 @@ def test_many_ragged_calls_in_flight_share_no_buffer(golden):
             assert torch.equal(x, y)
 
 
+def test_two_threads_on_one_plan_get_what_one_thread_gets(golden):
+    """The plan may serve several streams at once: two threads, each on its own stream with two ragged calls on the one plan's span ring
+    (the fused clip -> label kernel and the ragged MFCC matrix), return bit for bit what the same calls return one after another."""
+    import threading
+    import torch
+    from dsp_amd.scrubjay import ScrubJay
+    sj = ScrubJay(dict(golden("scrubjay_svm.npz")))
+    rng = np.random.default_rng(83)
+    flat = torch.from_numpy((rng.standard_normal(400000) * 0.1).astype(np.float32)).cuda()
+    offs = [np.unique(np.sort(rng.integers(0, 400000 // 800, 60)) * 800) for _ in range(4)]
+
+    def calls(k):
+        return list(sj.ragged(flat, offs[2 * k], 500)) + [sj.plan.clips_ragged(flat, offs[2 * k + 1], 500)[0]]
+
+    alone = [calls(k) for k in (0, 1)]
+    torch.cuda.synchronize()
+    got, errors = [None, None], []
+
+    def worker(k):
+        try:
+            st = torch.cuda.Stream()
+            with torch.cuda.stream(st):
+                got[k] = calls(k)
+            st.synchronize()
+        except Exception as e:  # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=worker, args=(k,)) for k in (0, 1)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(120)
+    assert not any(t.is_alive() for t in threads) and not errors, errors
+    for a, g in zip(alone, got):
+        for x, y in zip(a, g):
+            assert torch.equal(x, y)
+
+
 def _trace_equal(a, b):
     return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 

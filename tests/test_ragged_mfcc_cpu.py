@@ -55,6 +55,10 @@ def test_decreasing_offsets_are_rejected():
         M.ragged_frame_offsets(cfg, [0, 16000, 15999, 32000], 500)
     off, n = dl.c_offsets([-4, 16000])
     assert L.dsp_mfcc_ragged_frame_offsets(C.byref(cfg), off, n, 500, fo) == -1
+    assert "non-decreasing" in dl.last_error() and "clip 0" in dl.last_error()
+    off, n = dl.c_offsets([0, 16000, 16000 + 2**31])           # a clip of 2^31 samples
+    assert L.dsp_mfcc_ragged_frame_offsets(C.byref(cfg), off, n, 500, fo) == -1
+    assert "non-decreasing" in dl.last_error() and "clip 1" in dl.last_error()
 
 
 def test_bad_arguments_are_rejected_without_a_gpu():
