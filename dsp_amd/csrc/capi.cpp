@@ -432,11 +432,13 @@ int dsp_mfcc_plan_set_launch(dsp_mfcc_plan *p, int blocks_per_cu, int frames_per
 
 }  // extern "C"
 
-// A ragged batch for run(): clip c = samples [offsets[c], offsets[c + 1]) per channel, frame_offsets[c] its first output row (prefix sums of
-// the clips' frame counts), n_spans the clips with at least one frame.
+// A ragged batch for run(): clip c = samples [offsets[c], offsets[c + 1]) per channel -- or [offsets[c], offsets[c] + lengths[c]) when
+// lengths is given (spans anywhere in the buffer, overlapping ones included) -- frame_offsets[c] its first output row (prefix sums of the
+// clips' frame counts), n_spans the clips with at least one frame.
 struct RaggedBatch {
     const long *offsets, *frame_offsets;
     long n_clips, n_spans;
+    const long *lengths = nullptr;
 };
 
 // ragged: the spans (caller's order, clips of >= 1 frame, ClipSpan::frame0 = first output row) and behind them the chunk table of the
@@ -450,7 +452,8 @@ static int ragged_mfcc_spans(dsp_mfcc_plan *p, const RaggedBatch &rg, long n_fra
     long j = 0;
     for (long c = 0; c < rg.n_clips; ++c) {
         const int frames = (int)(rg.frame_offsets[c + 1] - rg.frame_offsets[c]);
-        if (frames > 0) h[j++] = dsp::ClipSpan{rg.offsets[c], (int)(rg.offsets[c + 1] - rg.offsets[c]), frames, c, rg.frame_offsets[c]};
+        const long n = rg.lengths ? rg.lengths[c] : rg.offsets[c + 1] - rg.offsets[c];
+        if (frames > 0) h[j++] = dsp::ClipSpan{rg.offsets[c], (int)n, frames, c, rg.frame_offsets[c]};
     }
     DSP_HIP(slot.upload(span_bytes, st));
     DSP_HIP(dsp::launch_ragged_chunk_map(static_cast<const dsp::ClipSpan *>(slot.d()), rg.n_spans, chunk,
@@ -636,13 +639,16 @@ int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, long n_c
 
 // ---- ragged MFCC matrices: clips of different lengths in one launch, their matrices back to back ----
 
-// host only: frame_offsets[c + 1] = frame_offsets[c] + the frames of clip c; the total, or < 0 (offsets not non-decreasing)
-static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets, long n_clips, int max_frames, long *frame_offsets, int *t_max)
+// host only: frame_offsets[c + 1] = frame_offsets[c] + the frames of clip c; the total, or < 0 (offsets not non-decreasing).  lengths: clip c
+// is samples [offsets[c], offsets[c] + lengths[c]) instead (RaggedBatch)
+static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets, long n_clips, int max_frames, long *frame_offsets, int *t_max,
+                                 const long *lengths = nullptr)
 {
     frame_offsets[0] = 0;
     int tm = 0;
     for (long c = 0; c < n_clips; ++c) {
-        const long n = dsp::ragged_clip_length(offsets, c);
+        const long n = lengths ? (offsets[c] >= 0 && lengths[c] >= 0 && lengths[c] <= INT32_MAX ? lengths[c] : fail(DSP_EINVAL, "internal: bad span"))
+                               : dsp::ragged_clip_length(offsets, c);
         if (n < 0) return n;
         const int t = dsp_mfcc_frames_for(&cfg, (int)n, max_frames);
         frame_offsets[c + 1] = frame_offsets[c] + t;
@@ -660,9 +666,9 @@ long dsp_mfcc_ragged_frame_offsets(const dsp_mfcc_config *cfg, const long *offse
     return ragged_frame_offsets(*cfg, offsets, n_clips, max_frames, frame_offsets, nullptr);
 }
 
-// in_kind as run(); returns the frames of the longest clip
+// in_kind as run(); returns the frames of the longest clip.  lengths: spans [offsets[c], offsets[c] + lengths[c]) (RaggedBatch)
 static int mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, const long *offsets, int max_frames, float *d_out,
-                             void *stream)
+                             void *stream, const long *lengths = nullptr)
 {
     if (in_kind < 0) return in_kind;
     if (!p || n_clips < 0 || !offsets) return fail(DSP_EINVAL, "bad argument");
@@ -673,11 +679,11 @@ static int mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, lo
     if (n_clips >= (1L << 31)) return fail(DSP_EINVAL, "too many clips");
     std::vector<long> fo((size_t)n_clips + 1);
     int t_max = 0;
-    const long total = ragged_frame_offsets(p->cfg, offsets, n_clips, max_frames, fo.data(), &t_max);
+    const long total = ragged_frame_offsets(p->cfg, offsets, n_clips, max_frames, fo.data(), &t_max, lengths);
     if (total < 0) return (int)total;
     if (total == 0) return 0;
     if (!d_in || !d_out) return fail(DSP_EINVAL, "NULL buffer");
-    RaggedBatch rg{offsets, fo.data(), n_clips, 0};
+    RaggedBatch rg{offsets, fo.data(), n_clips, 0, lengths};
     for (long c = 0; c < n_clips; ++c) rg.n_spans += fo[(size_t)c + 1] > fo[(size_t)c];
     const int rc = run(p, d_in, d_out, total, 0, 0, stream, in_kind, false, 0, &rg);
     return rc < 0 ? rc : t_max;
@@ -769,6 +775,7 @@ struct dsp_svm {
     int device = 0;
     dsp::SvmModelDev m{};
     float *d_blob = nullptr;
+    dsp::SpanRing scan;      // dsp_svm_scan_device: the per-recording arrays on their way to the GPU (capi_util.hpp)
 };
 
 extern "C" {
@@ -820,6 +827,7 @@ void dsp_svm_destroy(dsp_svm *s)
     if (!s) return;
     dsp::DeviceScope dsp_device_scope_(s->device);
     if (s->d_blob) hipFree(s->d_blob);
+    s->scan.release();
     delete s;
 }
 
@@ -1008,6 +1016,195 @@ int dsp_svm_predict_device(dsp_svm *s, const float *d_feat, long n_clips, int *d
     DSP_ON_DEVICE(s->device);
     DSP_HIP(dsp::launch_svm_predict(s->m, d_feat, n_clips, d_labels, d_decision, d_prob1, (hipStream_t)stream));
     return DSP_OK;
+}
+
+}  // extern "C"
+
+// ---- window scans of long recordings with the SVM: label, decision, P(label 1) and the pooled features per sliding window ------------
+// Windows are runs of MFCC rows (capi_util.hpp scan_plan).  Under complete framing and a per-frame log a row depends on its own samples
+// only, so a window's rows are rows of the recording's matrix.  Under DSP_FRAMING_STREAM the first H = ceil((frame_length - hop_length) /
+// hop_length) rows of a cut-out window see zeros before the window where the recording's rows see samples: each window gets its own
+// head rows, from internal spans [start, start + min(H, rows) hop) of the recording (RaggedBatch with lengths).
+
+// the first rows of a stream-framed clip that reach before it (0 under complete framing)
+static int head_rows_of(const dsp_mfcc_config &c)
+{
+    return c.framing == DSP_FRAMING_STREAM ? (c.frame_length - c.hop_length + c.hop_length - 1) / c.hop_length : 0;
+}
+
+// host only: window g's clip in samples (absolute in the buffer), or with head_rows > 0 its head span; starts / lengths may be NULL.
+// Returns the window count or < 0.
+static long window_spans(const dsp_mfcc_config &c, const dsp_scan_config &sc, const long *offsets, long n, long *starts, long *lengths, int head_rows)
+{
+    const long wf = sc.window_frames, hf = sc.hop_frames, hop = c.hop_length;
+    long g = 0;
+    for (long r = 0; r < n; ++r) {
+        const long len = dsp::ragged_clip_length(offsets, r);
+        if (len < 0) return len;
+        const long rows = dsp_mfcc_frames_for(&c, (int)len, INT_MAX);
+        const long w_n = rows >= wf ? 1 + (rows - wf) / hf : 1;
+        const long span = head_rows > 0 ? std::min<long>(head_rows, std::min(rows, wf)) * hop
+                                        : (c.framing == DSP_FRAMING_STREAM ? wf * hop : c.frame_length + (wf - 1) * hop);
+        for (long w = 0; w < w_n; ++w, ++g) {
+            const long a = w * hf * hop;
+            if (starts) starts[g] = offsets[r] + a;
+            if (lengths) lengths[g] = std::min(span, len - a);
+        }
+    }
+    return g;
+}
+
+// dsp_svm_scan_device and the scanner: head_rows > 0 adds window g's head rows, rows [ho[r] + w hc, + hc) of d_head (ho: n + 1 HOST longs)
+static int svm_scan(dsp_svm *s, const float *d_mfcc, long n, const long *frame_offsets, const dsp_scan_config *cfg, const float *d_head, int head_rows,
+                    const long *ho, int *d_labels, float *d_decision, float *d_prob1, float *d_feat, void *stream)
+{
+    if (!s) return fail(DSP_EINVAL, "SVM is NULL");
+    long rc = dsp::scan_args(cfg, n);
+    if (rc < 0 || n == 0) return (int)rc;
+    if (!frame_offsets || !d_mfcc || !d_labels) return fail(DSP_EINVAL, "frame_offsets, d_mfcc and d_labels must not be NULL");
+    if ((s->m.n_features & 1) || s->m.n_features > 128) return fail(DSP_EINVAL, "the scan pools n_features / 2 <= 64 coefficients per row: n_features must be even, <= 128");
+    const int tw = dsp::svm_scan_tile(s->m.n_features, cfg->window_frames, cfg->hop_frames, head_rows);
+    std::vector<long> wo((size_t)n + 1), to((size_t)n + 1);
+    if ((rc = dsp::scan_plan(cfg, frame_offsets, n, wo.data(), to.data(), std::max(tw, 1))) < 0) return (int)rc;
+    for (long r = 0; r < n; ++r)
+        if (frame_offsets[r + 1] == frame_offsets[r])
+            return fail(DSP_EINVAL, "recording " + std::to_string(r) + " has no MFCC rows (mfcc_stats pools a window's rows: scrubjay_infer.c:55-59)");
+    DSP_ON_DEVICE(s->device);
+    dsp::SpanRing::Lease slot;
+    DSP_HIP(dsp::scan_upload(s->scan, frame_offsets, n, wo.data(), to.data(), slot, stream, head_rows > 0 ? ho : nullptr));
+    const long *d = static_cast<const long *>(slot.d());
+    DSP_HIP(dsp::launch_svm_scan(s->m, d_mfcc + frame_offsets[0] * (s->m.n_features / 2), d_head, n, d, d + (n + 1), d + 2 * (n + 1),
+                                 head_rows > 0 ? d + 3 * (n + 1) : nullptr, to[(size_t)n], cfg->window_frames, cfg->hop_frames, head_rows, tw, d_labels,
+                                 d_decision, d_prob1, d_feat, (hipStream_t)stream));
+    return DSP_OK;
+}
+
+// the plans whose rows do not depend on the window, on the fused clip -> label kernel's front ends (what per-window equality is against)
+static int scan_front_end(const dsp_mfcc_plan *p, const dsp_svm *s)
+{
+    const dsp_mfcc_config &c = p->cfg;
+    if (c.log_mode == DSP_LOG_GLOBAL_REF1) return fail(DSP_EINVAL, "DSP_LOG_GLOBAL_REF1 plans cannot be scanned: the top_db floor spans the window");
+    if (c.prefilter != DSP_PREFILTER_NONE || c.n_fft == 1024)
+        return fail(DSP_EINVAL, "scans run on the ragged MFCC matrix: prefilter plans and n_fft 1024 are not supported");
+    if (p->kernel != DSP_KERNEL_WAVE) return fail(DSP_EINVAL, "scans run on the wave-per-frame kernel (DSP_KERNEL_WAVE), as the fused clip -> label path");
+    if (s->m.n_features != 2 * c.n_mfcc || s->m.n_features > 64) return fail(DSP_EINVAL, "SVM n_features must equal 2 * n_mfcc (<= 64)");
+    if (s->device != p->device) return fail(DSP_EINVAL, "plan and SVM live on different devices");
+    return DSP_OK;
+}
+
+// A scrub-jay scanner: PCM -> the recordings' ragged MFCC matrix (+ the windows' head rows) in its own workspace -> svm_scan_kernel.
+struct dsp_scrubjay_scanner {
+    dsp_mfcc_plan *plan = nullptr;
+    dsp_svm *svm = nullptr;
+    dsp_scan_config cfg{};
+    int head_rows = 0;
+    float *d_mfcc = nullptr, *d_head = nullptr;
+    size_t mfcc_cap = 0, head_cap = 0;
+    std::vector<long> fo, wo, ho, starts, lengths;
+    std::mutex mu;
+};
+
+static int scrubjay_scanner_run(dsp_scrubjay_scanner *s, const void *d_signal, int in_kind, long n, const long *offsets, int *d_labels, float *d_decision,
+                                float *d_prob1, float *d_feat, void *stream)
+{
+    if (in_kind < 0) return in_kind;
+    if (!s || n < 0) return fail(DSP_EINVAL, "bad argument (scanner, n_recordings >= 0)");
+    if (n == 0) return DSP_OK;
+    if (!offsets || !d_labels) return fail(DSP_EINVAL, "offsets and d_labels must not be NULL");
+    if (n >= (1L << 31)) return fail(DSP_EINVAL, "too many recordings");
+    if (const int rc = scan_front_end(s->plan, s->svm)) return rc;
+    dsp_mfcc_plan *p = s->plan;
+    if (in_kind != 0 && !p->aub && !(p->cfg.n_fft == 512 && p->host.dct_split == 4 && p->host.dct_len == 10 && p->host.mel_gather == 3))
+        return fail(DSP_EINVAL, "int16 input of the scrub-jay scan: the ragged MFCC matrix takes it on the scrubjay_infer.c front end "
+                                "(dsp_mfcc_scrubjay_infer_config) and on the 512-point framing with up to 13 coefficients of 40 mel filters");
+    std::lock_guard<std::mutex> lock(s->mu);
+    const int nc = p->cfg.n_mfcc;
+    s->fo.resize((size_t)n + 1);
+    const long rows = ragged_frame_offsets(p->cfg, offsets, n, INT_MAX, s->fo.data(), nullptr);     // no cap: every row of every recording
+    if (rows < 0) return (int)rows;
+    for (long r = 0; r < n; ++r)
+        if (s->fo[(size_t)r + 1] == s->fo[(size_t)r])
+            return fail(DSP_EINVAL, "recording " + std::to_string(r) + " is shorter than one frame: mfcc_stats has no rows to pool (scrubjay_infer.c:55-59)");
+    if (!d_signal) return fail(DSP_EINVAL, "d_signal is NULL");
+    DSP_ON_DEVICE(p->device);
+    if (dsp::reserve(s->d_mfcc, s->mfcc_cap, (size_t)rows * nc * sizeof(float)) != hipSuccess) return fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
+    int rc = mfcc_clips_ragged(p, d_signal, in_kind, n, offsets, INT_MAX, s->d_mfcc, stream);
+    if (rc < 0) return rc;
+    if (s->head_rows > 0) {
+        // window g of recording r: its min(H, rows) head rows at ho[r] + (g - wo[r]) hc_r, computed from its own head span
+        s->wo.resize((size_t)n + 1);
+        const long n_win = dsp::scan_plan(&s->cfg, s->fo.data(), n, s->wo.data(), nullptr, 1);
+        if (n_win < 0) return (int)n_win;
+        s->starts.resize((size_t)n_win);
+        s->lengths.resize((size_t)n_win);
+        if (window_spans(p->cfg, s->cfg, offsets, n, s->starts.data(), s->lengths.data(), s->head_rows) != n_win) return fail(DSP_EINVAL, "internal: head spans");
+        s->ho.resize((size_t)n + 1);
+        s->ho[0] = 0;
+        for (long r = 0; r < n; ++r) {
+            const long hc = std::min<long>(s->head_rows, std::min<long>(s->fo[(size_t)r + 1] - s->fo[(size_t)r], s->cfg.window_frames));
+            s->ho[(size_t)r + 1] = s->ho[(size_t)r] + (s->wo[(size_t)r + 1] - s->wo[(size_t)r]) * hc;
+        }
+        if (dsp::reserve(s->d_head, s->head_cap, (size_t)s->ho[(size_t)n] * nc * sizeof(float)) != hipSuccess)
+            return fail(DSP_ENOMEM, "hipMalloc (scanner head-row workspace)");
+        if ((rc = mfcc_clips_ragged(p, d_signal, in_kind, n_win, s->starts.data(), INT_MAX, s->d_head, stream, s->lengths.data())) < 0) return rc;
+    }
+    return svm_scan(s->svm, s->d_mfcc, n, s->fo.data(), &s->cfg, s->d_head, s->head_rows, s->ho.data(), d_labels, d_decision, d_prob1, d_feat, stream);
+}
+
+extern "C" {
+
+long dsp_scan_window_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config *cfg, const long *offsets, long n_recordings, long *starts, long *lengths)
+{
+    if (!mfcc) return fail(DSP_EINVAL, "mfcc config is NULL");
+    std::string why;
+    if (!valid_cfg(*mfcc, why)) return fail(DSP_EINVAL, why);
+    if (const int rc = dsp::scan_args(cfg, n_recordings)) return rc;
+    if (n_recordings == 0) return 0;
+    if (!offsets) return fail(DSP_EINVAL, "offsets is NULL");
+    return window_spans(*mfcc, *cfg, offsets, n_recordings, starts, lengths, 0);
+}
+
+int dsp_svm_scan_device(dsp_svm *svm, const float *d_mfcc, long n_recordings, const long *frame_offsets, const dsp_scan_config *cfg, int *d_labels,
+                        float *d_decision, float *d_prob1, float *d_feat, void *stream)
+{
+    return svm_scan(svm, d_mfcc, n_recordings, frame_offsets, cfg, nullptr, 0, nullptr, d_labels, d_decision, d_prob1, d_feat, stream);
+}
+
+int dsp_scrubjay_scanner_create(dsp_mfcc_plan *plan, dsp_svm *svm, const dsp_scan_config *cfg, dsp_scrubjay_scanner **out)
+{
+    if (!out) return fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!plan || !svm) return fail(DSP_EINVAL, "plan and SVM must not be NULL");
+    if (const int rc = dsp::scan_args(cfg, 0)) return rc;
+    if (const int rc = scan_front_end(plan, svm)) return rc;
+    auto *s = new dsp_scrubjay_scanner;
+    s->plan = plan;
+    s->svm = svm;
+    s->cfg = *cfg;
+    s->head_rows = head_rows_of(plan->cfg);
+    *out = s;
+    return DSP_OK;
+}
+
+void dsp_scrubjay_scanner_destroy(dsp_scrubjay_scanner *s)
+{
+    if (!s) return;
+    dsp::DeviceScope dsp_device_scope_(s->plan->device);
+    if (s->d_mfcc) hipFree(s->d_mfcc);
+    if (s->d_head) hipFree(s->d_head);
+    delete s;
+}
+
+int dsp_scrubjay_scanner_run_device(dsp_scrubjay_scanner *s, const float *d_signal, long n_recordings, const long *offsets, int *d_labels,
+                                    float *d_decision, float *d_prob1, float *d_feat, void *stream)
+{
+    return scrubjay_scanner_run(s, d_signal, 0, n_recordings, offsets, d_labels, d_decision, d_prob1, d_feat, stream);
+}
+
+int dsp_scrubjay_scanner_run_pcm16_device(dsp_scrubjay_scanner *s, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels,
+                                          int stereo_mode, int *d_labels, float *d_decision, float *d_prob1, float *d_feat, void *stream)
+{
+    return scrubjay_scanner_run(s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_recordings, offsets, d_labels, d_decision, d_prob1, d_feat, stream);
 }
 
 }  // extern "C"

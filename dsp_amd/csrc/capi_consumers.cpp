@@ -14,6 +14,9 @@
 #include "consumer_kernels.hpp"
 
 using dsp::capi_fail;
+using dsp::scan_args;
+using dsp::scan_plan;
+using dsp::scan_upload;
 
 namespace {
 
@@ -405,50 +408,6 @@ void fft_real_forward(const float *in_time, float *out_freq)
 // ---- scanning long recordings: P(stop) and the speaker LLR per sliding window of MFCC rows -------------------------------------------
 // In the reference's MFCC shape (per-frame log reference, complete frames, no prefilter) a row depends on its own samples only, so window
 // w of a recording is rows [w hop, w hop + window_frames) of the recording's ragged MFCC matrix, and each row is computed once.
-
-// the host planner: wo[r + 1] = wo[r] + windows of recording r, to[r + 1] = to[r] + ceil(windows / tw) (to may be NULL); total windows or < 0
-static int scan_args(const dsp_scan_config *cfg, long n)
-{
-    if (!cfg || cfg->window_frames < 1 || cfg->hop_frames < 1) return capi_fail(DSP_EINVAL, "dsp_scan_config: window_frames and hop_frames must be >= 1");
-    if (n < 0) return capi_fail(DSP_EINVAL, "n_recordings < 0");
-    return DSP_OK;
-}
-
-static long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, long n, long *wo, long *to, int tw)
-{
-    if (const int rc = scan_args(cfg, n)) return rc;
-    if (n == 0) {
-        if (wo) wo[0] = 0;
-        if (to) to[0] = 0;
-        return 0;
-    }
-    if (!frame_offsets || !wo) return capi_fail(DSP_EINVAL, "frame_offsets and window_offsets must not be NULL");
-    if (frame_offsets[0] < 0) return capi_fail(DSP_EINVAL, "frame_offsets must be non-negative");
-    wo[0] = 0;
-    if (to) to[0] = 0;
-    for (long r = 0; r < n; ++r) {
-        const long rows = frame_offsets[r + 1] - frame_offsets[r];
-        if (rows < 0) return capi_fail(DSP_EINVAL, "frame_offsets decrease at recording " + std::to_string(r));
-        const long w = rows >= cfg->window_frames ? 1 + (rows - cfg->window_frames) / cfg->hop_frames : 1;
-        wo[r + 1] = wo[r] + w;
-        if (to) to[r + 1] = to[r] + (w + tw - 1) / tw;
-    }
-    return wo[n];
-}
-
-// per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to], n + 1 longs each, into a leased ring slot, uploaded
-static hipError_t scan_upload(dsp::SpanRing &ring, const long *frame_offsets, long n, const long *wo, const long *to, dsp::SpanRing::Lease &slot,
-                              void *stream)
-{
-    const size_t one = (size_t)(n + 1) * sizeof(long), bytes = (to ? 3 : 2) * one;
-    const hipError_t e = ring.acquire(bytes, slot);
-    if (e != hipSuccess) return e;
-    long *h = static_cast<long *>(slot.h());
-    for (long r = 0; r <= n; ++r) h[r] = frame_offsets[r] - frame_offsets[0];
-    std::memcpy(h + (n + 1), wo, one);
-    if (to) std::memcpy(h + 2 * (n + 1), to, one);
-    return slot.upload(bytes, (hipStream_t)stream);
-}
 
 extern "C" {
 

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <climits>
 #include <condition_variable>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -140,6 +141,57 @@ template <class T> hipError_t reserve(T *&buf, size_t &cap, size_t bytes)
     const hipError_t e = hipMalloc(&buf, bytes);
     if (e == hipSuccess) cap = bytes;
     return e;
+}
+}
+
+// ---- window scans of long recordings (capi_consumers.cpp: stop / speaker; capi.cpp: SVM) ----------------------------------------------
+// Recording r is rows [frame_offsets[r], frame_offsets[r + 1]) of a ragged MFCC matrix, R rows: R >= window_frames gives
+// 1 + (R - window_frames) / hop_frames windows, fewer rows one window of all of them.
+namespace dsp {
+inline int scan_args(const dsp_scan_config *cfg, long n)
+{
+    if (!cfg || cfg->window_frames < 1 || cfg->hop_frames < 1) return capi_fail(DSP_EINVAL, "dsp_scan_config: window_frames and hop_frames must be >= 1");
+    if (n < 0) return capi_fail(DSP_EINVAL, "n_recordings < 0");
+    return DSP_OK;
+}
+
+// the host planner: wo[r + 1] = wo[r] + windows of recording r, to[r + 1] = to[r] + ceil(windows / tw) (to may be NULL); total windows or < 0
+inline long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, long n, long *wo, long *to, int tw)
+{
+    if (const int rc = scan_args(cfg, n)) return rc;
+    if (n == 0) {
+        if (wo) wo[0] = 0;
+        if (to) to[0] = 0;
+        return 0;
+    }
+    if (!frame_offsets || !wo) return capi_fail(DSP_EINVAL, "frame_offsets and window_offsets must not be NULL");
+    if (frame_offsets[0] < 0) return capi_fail(DSP_EINVAL, "frame_offsets must be non-negative");
+    wo[0] = 0;
+    if (to) to[0] = 0;
+    for (long r = 0; r < n; ++r) {
+        const long rows = frame_offsets[r + 1] - frame_offsets[r];
+        if (rows < 0) return capi_fail(DSP_EINVAL, "frame_offsets decrease at recording " + std::to_string(r));
+        const long w = rows >= cfg->window_frames ? 1 + (rows - cfg->window_frames) / cfg->hop_frames : 1;
+        wo[r + 1] = wo[r] + w;
+        if (to) to[r + 1] = to[r] + (w + tw - 1) / tw;
+    }
+    return wo[n];
+}
+
+// per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to][, extra], n + 1 longs each, into a leased ring
+// slot, uploaded
+inline hipError_t scan_upload(SpanRing &ring, const long *frame_offsets, long n, const long *wo, const long *to, SpanRing::Lease &slot,
+                              void *stream, const long *extra = nullptr)
+{
+    const size_t one = (size_t)(n + 1) * sizeof(long), bytes = (2 + (to ? 1 : 0) + (extra ? 1 : 0)) * one;
+    const hipError_t e = ring.acquire(bytes, slot);
+    if (e != hipSuccess) return e;
+    long *h = static_cast<long *>(slot.h());
+    for (long r = 0; r <= n; ++r) h[r] = frame_offsets[r] - frame_offsets[0];
+    std::memcpy(h + (n + 1), wo, one);
+    if (to) std::memcpy(h + 2 * (n + 1), to, one);
+    if (extra) std::memcpy(h + (to ? 3 : 2) * (n + 1), extra, one);
+    return slot.upload(bytes, (hipStream_t)stream);
 }
 }
 

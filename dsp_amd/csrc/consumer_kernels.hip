@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "consumer_kernels.hpp"
+#include "scan_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -270,18 +271,7 @@ hipError_t launch_fft_real_forward(const float *in, long n_frames, int frame_len
 // Recording r is rows [fo[r], fo[r + 1]) of a ragged MFCC matrix; its windows are wo[r] .. wo[r + 1) of the scan (host planner,
 // capi_consumers.cpp).  Window w of a recording with R >= window_frames rows covers rows [w hop, w hop + window_frames); a recording with
 // fewer rows has one window over all of them.  Only these per-recording arrays travel to the GPU: a block or a wave finds its recording
-// by a uniform binary search.
-
-// the r with off[r] <= key < off[r + 1] (off non-decreasing over n + 1 entries, off[0] <= key < off[n])
-__device__ __forceinline__ long scan_find(const long *__restrict__ off, long n, long key)
-{
-    long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (off[mid] <= key) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// by a uniform binary search (scan_find, scan_device.hpp).
 
 // Stop-word net over windows.  One block of 256 threads per tile of TW consecutive windows of one recording (tiles per recording
 // to[r] .. to[r + 1)): the rows the tile's windows cover are staged in LDS once, then thread (slot = tid % TW, stripe = tid / TW) sums

@@ -65,4 +65,15 @@ hipError_t launch_mfcc_stats(const float *mfcc, long n_clips, int T, int n_coef,
 hipError_t launch_svm_predict(const SvmModelDev &m, const float *feat, long n_clips, int *labels, float *decision,
                               float *prob1, hipStream_t stream);
 
+// ---- window scans (svm_kernels.hip svm_scan_kernel): the arrays fo, wo, to, ho are the host planner's (capi_util.hpp scan_plan) ----
+constexpr long kSvmScanLdsBytes = 64 * 1024;    // LDS of one SVM-scan block (two blocks per CU)
+// windows per block for this shape: 64, 16, 4 or 1 (the largest whose rows, head rows and features fit kSvmScanLdsBytes); 0: one
+// window per block with its rows read from memory
+int svm_scan_tile(int n_features, int window_frames, int hop, int head_rows);
+// labels / decision / prob1 / feat[wo[r] + w] = mean | std of window w of recording r (head rows first) -> Scaler -> SVM, as
+// mfcc_stats_kernel + svm_kernel on the window's rows; head_rows = 0: no head rows (head, ho unused); n_tiles = to[n_rec]
+hipError_t launch_svm_scan(const SvmModelDev &m, const float *mfcc, const float *head, long n_rec, const long *fo, const long *wo, const long *to,
+                           const long *ho, long n_tiles, int window_frames, int hop, int head_rows, int tw, int *labels, float *decision,
+                           float *prob1, float *feat, hipStream_t stream);
+
 }  // namespace dsp

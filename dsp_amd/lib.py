@@ -110,6 +110,8 @@ SYMBOLS = [
     "dsp_mfcc_ragged_frame_offsets", "dsp_mfcc_clips_ragged_device", "dsp_mfcc_clips_ragged_pcm16_device", "dsp_speaker_llr_ragged_device",
     "dsp_scan_window_offsets", "dsp_stop_scan_device", "dsp_speaker_scan_device",
     "dsp_scanner_create", "dsp_scanner_destroy", "dsp_scanner_run_device", "dsp_scanner_run_pcm16_device",
+    "dsp_scan_window_spans", "dsp_svm_scan_device", "dsp_scrubjay_scanner_create", "dsp_scrubjay_scanner_destroy",
+    "dsp_scrubjay_scanner_run_device", "dsp_scrubjay_scanner_run_pcm16_device",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
@@ -230,6 +232,13 @@ def load() -> C.CDLL:
     L.dsp_scanner_destroy.argtypes = [vp]; L.dsp_scanner_destroy.restype = None
     L.dsp_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp]; L.dsp_scanner_run_device.restype = ip
     L.dsp_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp]; L.dsp_scanner_run_pcm16_device.restype = ip
+    L.dsp_scan_window_spans.argtypes = [cfgp, scp, lp, C.c_long, lp, lp]; L.dsp_scan_window_spans.restype = C.c_long
+    L.dsp_svm_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp, vp, vp, vp]; L.dsp_svm_scan_device.restype = ip
+    L.dsp_scrubjay_scanner_create.argtypes = [vp, vp, scp, C.POINTER(vp)]; L.dsp_scrubjay_scanner_create.restype = ip
+    L.dsp_scrubjay_scanner_destroy.argtypes = [vp]; L.dsp_scrubjay_scanner_destroy.restype = None
+    L.dsp_scrubjay_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_scrubjay_scanner_run_device.restype = ip
+    L.dsp_scrubjay_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp, vp]
+    L.dsp_scrubjay_scanner_run_pcm16_device.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip

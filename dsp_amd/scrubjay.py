@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .mfcc import MfccPlan, default_config
+from .consumers import _frame_offsets, _scan_config, _scan_mfcc, scan_window_offsets
+from .mfcc import MfccPlan, default_config, ragged_frame_offsets
 
 
 class SvmModel:
@@ -58,6 +59,45 @@ class SvmModel:
         _lib.check(self._L.dsp_svm_predict_device(self._h, feat.contiguous().data_ptr(), n, labels.data_ptr(), dec.data_ptr(),
                                                   p1.data_ptr(), st), "dsp_svm_predict_device")
         return labels, dec, p1
+
+    def scan(self, mfcc, frame_offsets, window_frames: int, hop_frames: int):
+        """mean | std and the SVM per sliding window of rows of a ragged MFCC matrix (dsp_svm_scan_device): mfcc cuda float32
+        [F][n_features / 2], recording r = rows [frame_offsets[r], frame_offsets[r + 1]), every recording >= 1 row -> (window_offsets
+        int64 [n + 1], labels int32, decision float32, prob1 float32 [W], feat float32 [W][n_features]).  No head rows: under stream
+        framing a window's first rows differ from its cut-out clip's (ScrubJayScanner computes those)."""
+        import torch
+        wo = scan_window_offsets(frame_offsets, window_frames, hop_frames)
+        fo = _frame_offsets(frame_offsets)
+        if self.n_features % 2:
+            raise ValueError("the scan pools n_features / 2 coefficients per row: n_features must be even")
+        mfcc = _scan_mfcc(mfcc, fo, self.n_features // 2)
+        out = _window_outputs(int(wo[-1]), self.n_features, mfcc.device)
+        st = C.c_void_p(torch.cuda.current_stream(mfcc.device).cuda_stream)
+        _lib.check(self._L.dsp_svm_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
+                                               C.byref(_scan_config(window_frames, hop_frames)), *[t.data_ptr() for t in out], st),
+                   "dsp_svm_scan_device")
+        return (wo,) + out
+
+
+def _window_outputs(n, n_features, device):
+    import torch
+    return (torch.empty(n, dtype=torch.int32, device=device), torch.empty(n, dtype=torch.float32, device=device),
+            torch.empty(n, dtype=torch.float32, device=device), torch.empty((n, n_features), dtype=torch.float32, device=device))
+
+
+def scan_window_spans(config, offsets, window_frames: int, hop_frames: int):
+    """Host only: each scan window's clip in samples (dsp_scan_window_spans) for recordings r = samples [offsets[r], offsets[r + 1]) under
+    the MfccConfig `config` -> (starts int64 [W], lengths int64 [W]), absolute positions in the buffer.  Cutting these out and running
+    them as clips gives what the scans compute per window."""
+    cfg = _scan_config(window_frames, hop_frames)
+    off, n = _lib.c_offsets(offsets)
+    L = _lib.load()
+    lp = C.POINTER(C.c_long)
+    total = _lib.check(L.dsp_scan_window_spans(C.byref(config), C.byref(cfg), off, n, None, None), "dsp_scan_window_spans")
+    starts, lengths = np.zeros(total, np.int64), np.zeros(total, np.int64)
+    _lib.check(L.dsp_scan_window_spans(C.byref(config), C.byref(cfg), off, n, starts.ctypes.data_as(lp), lengths.ctypes.data_as(lp)),
+               "dsp_scan_window_spans")
+    return starts, lengths
 
 
 def mfcc_stats(mfcc):
@@ -149,3 +189,47 @@ class ScrubJay:
             _lib.check(_lib.load().dsp_scrubjay_fused_ragged_device(self.plan._h, self.svm._h, ptr, n, off, mf, labels.data_ptr(), dec.data_ptr(),
                                                                     p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_ragged_device")
         return labels, dec, p1, feat
+
+
+class ScrubJayScanner:
+    """dsp_scrubjay_scanner: long recordings back to back in HBM -> label, decision, P(label 1) and the pooled features per window of
+    window_frames MFCC rows every hop_frames rows, each equal to ScrubJay.ragged on the window cut out (scan_window_spans).  Borrows
+    the ScrubJay's plan and SVM.  One stream at a time per scanner."""
+
+    def __init__(self, scrubjay: ScrubJay, window_frames: int = 16, hop_frames: int = 4):
+        self._L = _lib.load()
+        self.cfg = _scan_config(window_frames, hop_frames)
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_scrubjay_scanner_create(scrubjay.plan._h, scrubjay.svm._h, C.byref(self.cfg), C.byref(h)), "dsp_scrubjay_scanner_create")
+        self._h, self.scrubjay = h, scrubjay          # (the scanner borrows its plan and SVM: keep them alive)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_scrubjay_scanner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def run(self, signal, offsets, stereo_mode: int = 0):
+        """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (interleaved stereo), recording r = samples
+        [offsets[r], offsets[r + 1]) per channel -> (window_offsets int64 [n + 1], labels int32, decision float32, prob1 float32 [W],
+        feat float32 [W][n_features])."""
+        import torch
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
+        if channels and stereo_mode not in (0, 1):
+            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
+        fo = ragged_frame_offsets(self.scrubjay.plan.cfg, (off, n), 2**31 - 1)
+        wo = scan_window_offsets(fo, self.cfg.window_frames, self.cfg.hop_frames)
+        out = _window_outputs(int(wo[-1]), self.scrubjay.svm.n_features, signal.device)
+        st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
+        ptrs = [t.data_ptr() for t in out]
+        if channels:
+            _lib.check(self._L.dsp_scrubjay_scanner_run_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), *ptrs, st),
+                       "dsp_scrubjay_scanner_run_pcm16_device")
+        else:
+            _lib.check(self._L.dsp_scrubjay_scanner_run_device(self._h, ptr, n, off, *ptrs, st), "dsp_scrubjay_scanner_run_device")
+        return (wo,) + out

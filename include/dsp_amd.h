@@ -533,6 +533,40 @@ int dsp_scanner_run_device(dsp_scanner *scanner, const float *d_signal, long n_r
                            int64_t *d_llr_mean, int *d_labels, void *stream);
 int dsp_scanner_run_pcm16_device(dsp_scanner *scanner, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels,
                                  int stereo_mode, float *d_prob, int64_t *d_llr_mean, int *d_labels, void *stream);
+/* SCRUB-JAY SCANS: the SVM's label, decision value, P(label 1) and the 2 n_mfcc pooled features (mean | std) per sliding window of
+ * MFCC rows, the windows as above.  Each window's results equal, bit for bit, dsp_scrubjay_fused_ragged_device (same plan, same SVM)
+ * on the window cut out as its own clip, on the plans whose rows do not depend on the window: the fused kernel's front ends on
+ * DSP_KERNEL_WAVE, log mode DSP_LOG_PER_FRAME_MAX or DSP_LOG_LOG10_FLOOR, no prefilter, n_fft 512 or 2048 (DSP_LOG_GLOBAL_REF1: its
+ * top_db floor spans the window; prefilter and n_fft 1024 plans: the ragged matrix refuses them -- DSP_EINVAL).
+ * In samples, window w of recording r starts at offsets[r] + w hop_frames hop_length; it is frame_length + (window_frames - 1)
+ * hop_length samples long under DSP_FRAMING_COMPLETE, window_frames hop_length under DSP_FRAMING_STREAM, clipped to the recording.
+ * Under DSP_FRAMING_STREAM the first H = ceil((frame_length - hop_length) / hop_length) rows of a cut-out window see zeros before it: the
+ * scanner computes each window's own min(H, rows) head rows (from a span of that many hops at its start) and takes the rest from the
+ * recording's matrix.  Every recording must hold at least one row (mfcc_stats pools a window's rows): DSP_EINVAL names the first that
+ * does not.  d_labels is required; d_decision, d_prob1 and d_feat[total windows][n_features] may be NULL.  Zero recordings: DSP_OK.
+ *
+ * dsp_scan_window_spans (host only, no GPU): starts / lengths[total windows] = each window's clip in samples (absolute positions in the
+ * buffer; either may be NULL), for any valid MFCC config -- the 2fa scanner's windows included; returns the total window count or a
+ * negative DSP_E* code (offsets as dsp_mfcc_clips_ragged_device).                                                                   */
+long dsp_scan_window_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config *cfg, const long *offsets, long n_recordings,
+                           long *starts, long *lengths);
+/* Matrix level, like dsp_stop_scan_device: windows = runs of rows of a ragged matrix d_mfcc[..][n_features / 2], frame_offsets a HOST
+ * array (read before the call returns).  No head rows: under DSP_FRAMING_STREAM use the scanner for per-clip equality.  Uses a ring of
+ * upload buffers in the SVM, no workspace: any stream.                                                                               */
+int dsp_svm_scan_device(dsp_svm *svm, const float *d_mfcc, long n_recordings, const long *frame_offsets, const dsp_scan_config *cfg,
+                        int *d_labels, float *d_decision, float *d_prob1, float *d_feat, void *stream);
+/* The whole chain: recordings back to back in HBM (offsets, channels and stereo_mode as dsp_mfcc_clips_ragged_device / _pcm16_device)
+ * -> the ragged MFCC matrix and the windows' head rows in the scanner's grow-only workspace -> the scan, all enqueued on `stream`.  The
+ * scanner borrows plan and SVM (destroy it first; the SVM's n_features must be 2 n_mfcc) and serves ONE stream at a time.  int16
+ * input: the dsp_mfcc_scrubjay_infer_config front end and the 512-point framing's 13-coefficient shape (elsewhere DSP_EINVAL).     */
+typedef struct dsp_scrubjay_scanner dsp_scrubjay_scanner;
+int dsp_scrubjay_scanner_create(dsp_mfcc_plan *plan, dsp_svm *svm, const dsp_scan_config *cfg, dsp_scrubjay_scanner **out);
+void dsp_scrubjay_scanner_destroy(dsp_scrubjay_scanner *scanner);
+int dsp_scrubjay_scanner_run_device(dsp_scrubjay_scanner *scanner, const float *d_signal, long n_recordings, const long *offsets,
+                                    int *d_labels, float *d_decision, float *d_prob1, float *d_feat, void *stream);
+int dsp_scrubjay_scanner_run_pcm16_device(dsp_scrubjay_scanner *scanner, const int16_t *d_pcm, long n_recordings, const long *offsets,
+                                          int channels, int stereo_mode, int *d_labels, float *d_decision, float *d_prob1, float *d_feat,
+                                          void *stream);
 
 /* upsampleLinear (sync/particle/main.cpp:62-77) over a batch: d_out[c][i] for i < new_size from
  * d_in[c][0..old_size), the reference's fp32 operation order (bit-identical).  new_size >= 2.     */
