@@ -905,6 +905,9 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
         return fail(DSP_EINVAL, "int16 input of the fused clip -> label kernel: the reference framing (n_fft 512, frame 400, 40 mel filters, up to 20 coefficients) "
                                 "or the scrubjay_infer.c front end (dsp_mfcc_scrubjay_infer_config)");
     if (s->m.n_features != 2 * p->cfg.n_mfcc || s->m.n_features > 64) return fail(DSP_EINVAL, "SVM n_features must equal 2 * n_mfcc (<= 64)");
+    if (p->cfg.n_fft == 512 && s->m.n_sv > dsp::kSvmFused512MaxSv)
+        return fail(DSP_EINVAL, "the 512-point fused clip -> label kernel holds at most " + std::to_string(dsp::kSvmFused512MaxSv) +
+                                " support vectors in LDS (this SVM has " + std::to_string(s->m.n_sv) + "): use the three calls");
     const bool ragged = offsets != nullptr;
     int t = ragged ? 1 : dsp_mfcc_frames_for(&p->cfg, samples_per_clip, max_frames);
     if (n_clips == 0) return 0;

@@ -915,7 +915,7 @@ static hipError_t launch_one(const Mfcc512Args &args, bool clips, int blocks, hi
 hipError_t launch_mfcc512_pool(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream)
 {
     if (args.frames_per_clip <= 0 || args.chunk != args.frames_per_clip || args.log_mode != 0 || args.in_kind < 0 || args.in_kind > 3 || !args.pool.labels ||
-        args.pool.svm.n_features != 2 * args.n_mfcc || args.pool.svm.n_features > 64 || args.pool.svm.n_sv < 1 || args.pool.svm.n_sv > 2048)
+        args.pool.svm.n_features != 2 * args.n_mfcc || args.pool.svm.n_features > 64 || args.pool.svm.n_sv < 1 || args.pool.svm.n_sv > kSvmFused512MaxSv)
         return hipErrorInvalidConfiguration;
     const dim3 g(blocks), b(256);
     if (args.in_kind != 0) {

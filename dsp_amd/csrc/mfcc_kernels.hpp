@@ -13,6 +13,8 @@ namespace dsp {
 // BASELINE config 5 in ONE kernel (clip mode, one wavefront per clip): the MFCC matrix is never written; the
 // tile epilogue pools mean | std per coefficient (cepstrum/scrubjay_infer.c:36-66, float64 sums in frame order)
 // and the clip ends with Scaler -> RBF-SVM -> Platt (scrubjay_svm.onnx, scrubjay_infer.c:105-141).
+constexpr int kSvmFused512MaxSv = 2048;    // the 512-point fused kernel's LDS copy of the SVM's coefficients (launch_mfcc512_pool)
+
 struct PoolSvmArgs {
     SvmModelDev svm;       // n_features = 2 * n_mfcc
     int *labels;           // [n_clips]
