@@ -49,7 +49,6 @@ struct ClassifyCtx : front::Work {
     long cap_segs = 0;                                     // per-segment arrays: clips x segments per clip of the largest pass so far
     size_t cap_x = 0;                                      // staging buffer of the host entry points, in bytes (0: none)
     float keep_min_db = 70.0f;                             // the midpoint threshold d_tab->mp_keep_min was computed for
-    bool gate_ok = false;                                  // SpecTables::gate_ok of d_tab
 
     static Config default_config()
     {
@@ -73,7 +72,6 @@ struct ClassifyCtx : front::Work {
         dsp::build_spec_tables(16000, t);
         DSP_CAPI_HIP(hipMalloc(&d_tab, sizeof(t)));
         DSP_CAPI_HIP(hipMemcpy(d_tab, &t, sizeof(t), hipMemcpyHostToDevice));
-        gate_ok = t.gate_ok != 0;
         keep_min_db = 70.0f;
         DSP_CAPI_HIP(dsp::launch_spec_threshold(d_tab, keep_min_db, nullptr));
         {   // the recompute kernel's three-instruction PSD division is switched on only after it has been checked against the real
@@ -212,7 +210,7 @@ int dsp_butter_bandpass_filter_f32(const float *data, long n_clips, int n, long 
     dsp::IirCoef c;
     for (int i = 0; i < 9; ++i) { c.b[i] = b[i]; c.a[i] = a[i]; }
     hipError_t e = hipMemcpy2D(dx, (size_t)n * sizeof(float), data, (size_t)stride * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_iir_f32(dx, n_clips, n, n, c, dy, c, nullptr, nullptr);
+    if (e == hipSuccess) e = dsp::launch_iir_f32(dx, n_clips, n, n, c, dy, nullptr);
     if (e == hipSuccess) e = hipMemcpy2D(output, (size_t)stride * sizeof(float), dy, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyDeviceToHost);
     (void)hipFree(dx); (void)hipFree(dy);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));

@@ -8,7 +8,6 @@
 // with FMA contraction off, the sequential sums stay sequential, and the twiddle /
 // window tables come from the reference's own recurrences evaluated on the host.
 // Parallelism is across clips and frames (embarrassing), not inside a recurrence.
-// Round 1: correct and batched, not yet tuned.
 #include "diag_guard.hpp"
 #include <hip/hip_runtime.h>
 
@@ -27,7 +26,6 @@ namespace dsp {
 // a9: direct form II, one lane per clip, time tiles transposed through LDS so HBM sees
 // coalesced 128-byte rows although each lane walks its own clip.
 // ---------------------------------------------------------------------------------
-typedef float f4nt __attribute__((ext_vector_type(4)));     // nontemporal 16-byte stores
 constexpr int IIR_TS = 32;       // samples per tile = one full 128-byte line per float row and tile (16-sample tiles
                                  // fetch every line twice: measured memory-bound on BASELINE config 3)
 #ifndef DSP_IIR_BURST
@@ -61,11 +59,9 @@ __device__ __forceinline__ T iir_step(IirState<T> &s, const C &c, T x)
 // are converted on load and rounded once on store: BASELINE config 3's per-frame prefilter).
 // TWO: two filters over the same input, one wavefront each (128-thread block, shared input tile): the serial
 // recurrences of the two filters run side by side instead of back to back in one lane.
-// MEANS (float): also emit the spectrogram's segment means of the outputs (see classify_kernels.hpp).
-template <typename T, typename C, bool TWO, typename TIO = T, bool MEANS = false, bool EVEN_B = false>
+template <typename T, typename C, bool TWO, typename TIO = T, bool EVEN_B = false>
 __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restrict__ x, long n_clips, int n, long stride, long ystride,
-                                                             const C c1, TIO *__restrict__ y1, const C c2, TIO *__restrict__ y2,
-                                                             float *__restrict__ means1 = nullptr, float *__restrict__ means2 = nullptr)
+                                                             const C c1, TIO *__restrict__ y1, const C c2, TIO *__restrict__ y2)
 {
     constexpr int NTHR = TWO ? 128 : 64;
     __shared__ TIO tin[64 * IIR_LD];
@@ -74,7 +70,6 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restri
     const int wv = TWO ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;       // which filter this wavefront runs
     const C c = wv ? c2 : c1;
     TIO *__restrict__ y = wv ? y2 : y1;
-    float *__restrict__ means = wv ? means2 : means1;
     TIO *to = tout[wv];
     const long clip0 = (long)blockIdx.x * 64;
     const int rows = (int)((n_clips - clip0) < 64 ? (n_clips - clip0) : 64);
@@ -84,9 +79,6 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restri
     // 16-byte vector path needs every row start and every tile start 16-byte aligned
     const bool vec_ok = (stride * sizeof(TIO)) % 16 == 0 && (ystride * sizeof(TIO)) % 16 == 0 && (reinterpret_cast<uintptr_t>(x) % 16) == 0 &&
                         (reinterpret_cast<uintptr_t>(y1) % 16) == 0 && (!TWO || (reinterpret_cast<uintptr_t>(y2) % 16) == 0);
-    float cur = 0.0f, prev = 0.0f;                    // MEANS: running sums of the current and the previous segment
-    const int n_seg = n < kSpecSeg ? 0 : (n - kSpecSeg) / kSpecHop + 1;
-    (void)cur; (void)prev; (void)n_seg; (void)means;
     // Full tiles travel as 16-byte vectors (4 lanes cover one 64-byte row segment) and are software-pipelined:
     // the next tile's global loads are issued before this tile's recurrence runs, so the serial arithmetic
     // hides the HBM latency even with one wave per SIMD.
@@ -123,22 +115,7 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restri
         }
         __syncthreads();
         if (vec_ok && t0 + 2 * IIR_TS <= n) issue(t0 + IIR_TS);
-        // one sample of this lane's recurrence (+ the segment sums when MEANS)
-        // (the segment bookkeeping is derived from the wave-uniform sample index s, so it stays in scalar registers)
-        auto sample = [&](T xv, int s) -> TIO {
-            const TIO o = (TIO)iir_step<T, C, EVEN_B>(st, c, xv);
-            if (MEANS) {
-                // sample s = 224 k + pos belongs to segment k and, for pos < 32, still to segment k - 1
-                const int k = s / kSpecHop, pos = s - k * kSpecHop;
-                if (pos == 0) { prev = cur; cur = 0.0f; }
-                cur = cur + (float)o;
-                if (pos < kSpecSeg - kSpecHop && k >= 1) {
-                    prev = prev + (float)o;
-                    if (pos == kSpecSeg - kSpecHop - 1 && k - 1 < n_seg) means[(clip0 + lane) * n_seg + k - 1] = prev / (float)kSpecSeg;
-                }
-            }
-            return o;
-        };
+        auto sample = [&](T xv) -> TIO { return (TIO)iir_step<T, C, EVEN_B>(st, c, xv); };      // one sample of this lane's recurrence
         if (lane < rows && cols == IIR_TS) {
             // full tile: the row goes LDS -> registers -> LDS in bursts, so the LDS latency is paid once per
             // 16 samples and not once per sample on top of the recurrence's own dependency chain
@@ -149,14 +126,12 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restri
 #pragma unroll
                 for (int i = 0; i < IIR_BURST; ++i) xr[i] = (T)tin[lane * IIR_LD + h + i];
 #pragma unroll
-                for (int i = 0; i < IIR_BURST; ++i) orr[i] = sample(xr[i], t0 + h + i);
+                for (int i = 0; i < IIR_BURST; ++i) orr[i] = sample(xr[i]);
 #pragma unroll
                 for (int i = 0; i < IIR_BURST; ++i) to[lane * IIR_LD + h + i] = orr[i];
             }
         } else if (lane < rows) {
-            for (int i = 0; i < cols; ++i) {
-                to[lane * IIR_LD + i] = sample((T)tin[lane * IIR_LD + i], t0 + i);
-            }
+            for (int i = 0; i < cols; ++i) to[lane * IIR_LD + i] = sample((T)tin[lane * IIR_LD + i]);
         }
         __syncthreads();
         // each wavefront stores its own filter's tile
@@ -184,250 +159,21 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void iir_kernel(const TIO *__restri
 }
 
 // ---------------------------------------------------------------------------------
-// a9 for classify(): both band-pass filters of a clip batch with the recurrence and the output
-// taps on DIFFERENT wavefronts.  Direct form II is v[n] = x[n] - sum a[j] v[n-j] (serial) followed
-// by y[n] = b0 v[n] + sum b[j] v[n-j] (an FIR over v, no feedback).  With a few thousand clips the
-// lane-per-clip kernel is bound by one wavefront's issue latency (~7 cycles per dependent VALU
-// instruction), so halving the instructions each wavefront executes per sample nearly halves the
-// time: waves 0/1 run the recurrences of filter 1/2 and hand v tiles over through LDS, waves 2/3
-// run the taps one tile behind, keep the spectrogram's segment sums and store y.  Every sample
-// sees exactly the reference's operations in the reference's order (classifier.cpp:199-216).
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void iir2_split_kernel(const float *__restrict__ x, long n_clips, int n, long stride, long ystride,
-                                                         const IirCoef c1, float *__restrict__ y1, const IirCoef c2, float *__restrict__ y2,
-                                                         float *__restrict__ means1, float *__restrict__ means2,
-                                                         const SpecTables *__restrict__ tab, int *__restrict__ gate2)
-{
-    __shared__ float tin[2][64 * IIR_LD];
-    __shared__ float vbuf[2][2][64 * IIR_LD];          // [filter][tile parity]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int f = wv & 1;                               // filter
-    const bool is_r = wv < 2;                           // recurrence wave (else: taps wave)
-    const IirCoef c = f ? c2 : c1;
-    float *__restrict__ y = f ? y2 : y1;
-    float *__restrict__ means = f ? means2 : means1;
-    const long clip0 = (long)blockIdx.x * 64;
-    const int rows = (int)((n_clips - clip0) < 64 ? (n_clips - clip0) : 64);
-    const int n_tiles = (n + IIR_TS - 1) / IIR_TS;
-    const int n_seg = n < kSpecSeg ? 0 : (n - kSpecSeg) / kSpecHop + 1;
-    float d[8];                                         // v[n-1] .. v[n-8] of this lane's clip
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d[j] = 0.0f;
-    float cur = 0.0f, prev = 0.0f;                      // taps waves: running sums of the current / previous segment
-    // gate2 (filter 2, needs means2 and tab): an upper bound of each segment's windowed, mean-removed energy
-    // E = sum w^2 (y - m)^2 = A - 2 m B + m^2 C <= A + 2 |m| |B| + m^2 C with A = sum w^2 y^2, B = sum w^2 y, C = sum w^2.
-    // gate2[clip][k] = 0 when 512 E / U (Parseval bound of every PSD cell, 1 % margin for the float sums) stays below
-    // the 70 dB threshold: spectrogram_kernel<SPEC_FLAGS> then never reads that frame.
-    const bool gating = gate2 != nullptr && f == 1 && means != nullptr && tab != nullptr && tab->gate_ok != 0;
-    float ea_cur = 0.0f, eb_cur = 0.0f, ea_prev = 0.0f, eb_prev = 0.0f;
-
-    // x tiles: the 128 recurrence threads load them (4 float4 each per full tile), one tile ahead in registers
-    constexpr int CH = IIR_TS / 4, NV = 64 * CH / 128;
-    float4 pre[NV];
-    auto issue = [&](int t0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int e = tid + 128 * k, r = e / CH, cc = (e % CH) * 4;
-            pre[k] = r < rows ? *reinterpret_cast<const float4 *>(x + (clip0 + r) * stride + t0 + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto commit = [&](float *dst) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int e = tid + 128 * k, r = e / CH, cc = (e % CH) * 4;
-            dst[r * IIR_LD + cc] = pre[k].x; dst[r * IIR_LD + cc + 1] = pre[k].y;
-            dst[r * IIR_LD + cc + 2] = pre[k].z; dst[r * IIR_LD + cc + 3] = pre[k].w;
-        }
-    };
-    auto load_partial = [&](int t0, int cols, float *dst) {       // last, short tile: element-wise
-        for (int e = tid; e < 64 * IIR_TS; e += 128) {
-            const int r = e / IIR_TS, ci = e % IIR_TS;
-            dst[r * IIR_LD + ci] = (r < rows && ci < cols) ? x[(clip0 + r) * stride + t0 + ci] : 0.0f;
-        }
-    };
-    auto tile_cols = [&](int s) { const int t0 = s * IIR_TS; return n - t0 < IIR_TS ? n - t0 : IIR_TS; };
-    if (is_r) {                                                    // tile 0 into tin[0], tile 1 in flight
-        if (tile_cols(0) == IIR_TS) { issue(0); commit(tin[0]); } else load_partial(0, tile_cols(0), tin[0]);
-        if (n_tiles > 1 && tile_cols(1) == IIR_TS) issue(IIR_TS);
-    }
-    __syncthreads();
-
-    for (int s = 0; s <= n_tiles; ++s) {
-        if (is_r) {
-            if (s < n_tiles) {
-                // stage x tile s+1 for the next step, start the loads of tile s+2
-                if (s + 1 < n_tiles) {
-                    if (tile_cols(s + 1) == IIR_TS) commit(tin[(s + 1) & 1]); else load_partial((s + 1) * IIR_TS, tile_cols(s + 1), tin[(s + 1) & 1]);
-                    if (s + 2 < n_tiles && tile_cols(s + 2) == IIR_TS) issue((s + 2) * IIR_TS);
-                }
-                const float *xin = tin[s & 1];
-                float *vo = vbuf[f][s & 1];
-                const int cols = tile_cols(s);
-                auto rec = [&](float xv) {                           // classifier.cpp:199-205
-                    float v = xv;
-#pragma unroll
-                    for (int j = 1; j <= 8; ++j) v = v - c.a[j] * d[j - 1];
-#pragma unroll
-                    for (int j = 7; j > 0; --j) d[j] = d[j - 1];
-                    d[0] = v;
-                    return v;
-                };
-                if (lane < rows && cols == IIR_TS) {
-#pragma unroll
-                    for (int h = 0; h < IIR_TS; h += IIR_BURST) {
-                        float xr[IIR_BURST], vr[IIR_BURST];
-#pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) xr[i] = xin[lane * IIR_LD + h + i];
-#pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) vr[i] = rec(xr[i]);
-#pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) vo[lane * IIR_LD + h + i] = vr[i];
-                    }
-                } else if (lane < rows) {
-                    for (int i = 0; i < cols; ++i) vo[lane * IIR_LD + i] = rec(xin[lane * IIR_LD + i]);
-                }
-            }
-        } else if (s >= 1) {
-            const int t0 = (s - 1) * IIR_TS, cols = tile_cols(s - 1);
-            // y replaces v in place (each lane rewrites the row it has just read), so the taps wave needs no tile of its own:
-            // 6 tiles = 50 KB per block, three blocks per CU
-            float *yo = vbuf[f][(s - 1) & 1];
-            const float *vin = yo;
-            auto taps = [&](float v) {                               // classifier.cpp:207-216
-                float o = c.b[0] * v;
-#pragma unroll
-                for (int j = 1; j <= 8; ++j) o = o + c.b[j] * d[j - 1];
-#pragma unroll
-                for (int j = 7; j > 0; --j) d[j] = d[j - 1];
-                d[0] = v;
-                return o;
-            };
-            // The spectrogram's segments (256 samples every 224) start on tile boundaries and overlap by exactly one
-            // tile: tile 7k is the first tile of segment k and the last one of segment k-1.  Their sequential sums
-            // (classifier.cpp:329-333) are carried per tile: one add per sample, two in the shared tile.
-            static_assert(kSpecHop % IIR_TS == 0 && kSpecSeg - kSpecHop == IIR_TS, "segment sums are kept per IIR tile");
-            constexpr int kTilesPerHop = kSpecHop / IIR_TS;
-            const int ti = s - 1, seg_k = ti / kTilesPerHop;
-            const bool seg_start = means != nullptr && ti % kTilesPerHop == 0;
-            const bool seg_both = seg_start && seg_k >= 1;           // the tile also closes segment seg_k - 1
-            if (seg_start) { prev = cur; cur = 0.0f; ea_prev = ea_cur; eb_prev = eb_cur; ea_cur = eb_cur = 0.0f; }
-            if (lane < rows && cols == IIR_TS) {
-#pragma unroll
-                for (int h = 0; h < IIR_TS; h += IIR_BURST) {
-                    float vr[IIR_BURST], orr[IIR_BURST];
-#pragma unroll
-                    for (int i = 0; i < IIR_BURST; ++i) vr[i] = vin[lane * IIR_LD + h + i];
-#pragma unroll
-                    for (int i = 0; i < IIR_BURST; ++i) orr[i] = taps(vr[i]);
-                    if (seg_both) {
-#pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) { cur = cur + orr[i]; prev = prev + orr[i]; }
-                    } else if (means) {
-#pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) cur = cur + orr[i];
-                    }
-                    if (gating) {
-                        if (seg_start) {                             // tapered tile: in for the new segment, out for the old one
-#pragma unroll
-                            for (int i = 0; i < IIR_BURST; ++i) {
-                                const float wi = tab->win2_in[h + i] * orr[i], wo = tab->win2_out[h + i] * orr[i];
-                                ea_cur = fmaf(wi, orr[i], ea_cur); eb_cur = eb_cur + wi;
-                                ea_prev = fmaf(wo, orr[i], ea_prev); eb_prev = eb_prev + wo;
-                            }
-                        } else {                                     // the window is 1 here
-#pragma unroll
-                            for (int i = 0; i < IIR_BURST; ++i) { ea_cur = fmaf(orr[i], orr[i], ea_cur); eb_cur = eb_cur + orr[i]; }
-                        }
-                    }
-#pragma unroll
-                    for (int i = 0; i < IIR_BURST; ++i) yo[lane * IIR_LD + h + i] = orr[i];
-                }
-                if (seg_both && seg_k - 1 < n_seg) {
-                    const float m = prev / (float)kSpecSeg;
-                    means[(clip0 + lane) * n_seg + seg_k - 1] = m;
-                    if (gating) {
-                        const float e = ea_prev + 2.0f * fabsf(m) * fabsf(eb_prev) + m * m * tab->win2_sum;
-                        gate2[(clip0 + lane) * n_seg + seg_k - 1] = e * tab->gate_scale >= tab->mp_keep_min ? 1 : 0;
-                    }
-                }
-            } else if (lane < rows) {
-                // a short last tile lies past every whole segment: no sums to keep
-                for (int i = 0; i < cols; ++i) yo[lane * IIR_LD + i] = taps(vin[lane * IIR_LD + i]);
-            }
-            // this wave's own tile: wave-level ordering is enough before the coalesced store
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (cols == IIR_TS) {
-                for (int e = lane; e < 64 * CH; e += 64) {
-                    const int r = e / CH, cc = (e % CH) * 4;
-                    if (r < rows) {                                  // streamed out: nothing in this kernel reads it back (-10 %)
-                        const f4nt q = {yo[r * IIR_LD + cc], yo[r * IIR_LD + cc + 1], yo[r * IIR_LD + cc + 2], yo[r * IIR_LD + cc + 3]};
-                        __builtin_nontemporal_store(q, reinterpret_cast<f4nt *>(y + (clip0 + r) * ystride + t0 + cc));
-                    }
-                }
-            } else {
-                for (int e = lane; e < 64 * IIR_TS; e += 64) {
-                    const int r = e / IIR_TS, ci = e % IIR_TS;
-                    if (r < rows && ci < cols) y[(clip0 + r) * ystride + t0 + ci] = yo[r * IIR_LD + ci];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        __syncthreads();
-    }
-}
-
-hipError_t launch_iir_f32(const float *x, long n_clips, int n, long stride, const IirCoef &c1, float *y1,
-                          const IirCoef &c2, float *y2, hipStream_t stream, float *means1, float *means2,
-                          const SpecTables *tables, int *gate2, long ystride, bool gate_tables_ok)
-{
-    if (n_clips <= 0 || n <= 0) return hipSuccess;
-    if (ystride <= 0) ystride = stride;
-    const int blocks = (int)((n_clips + 63) / 64);
-    const bool aligned = stride % 4 == 0 && ystride % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
-                         reinterpret_cast<uintptr_t>(y1) % 16 == 0 && reinterpret_cast<uintptr_t>(y2) % 16 == 0;
-    // only the split kernel computes the gate, and only when the window tables allow it (SpecTables::gate_ok): otherwise
-    // every frame is "maybe" (non-zero ints)
-    if (gate2 && !(y2 && aligned && means2 && tables && gate_tables_ok)) {
-        const int n_seg = n < kSpecSeg ? 0 : (n - kSpecSeg) / kSpecHop + 1;
-        hipError_t e = hipMemsetAsync(gate2, 1, (size_t)n_clips * n_seg * sizeof(int), stream);
-        if (e != hipSuccess) return e;
-    }
-    if (y2 && aligned)       // classify(): recurrence / taps split over four wavefronts (means1 / means2 may be nullptr)
-        hipLaunchKernelGGL(iir2_split_kernel, dim3(blocks), dim3(256), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2, means1, means2, tables, gate2);
-    else if (y2 && means1 && means2)
-        hipLaunchKernelGGL((iir_kernel<float, IirCoef, true, float, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2,
-                           means1, means2);
-    else if (y2) hipLaunchKernelGGL((iir_kernel<float, IirCoef, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2, nullptr, nullptr);
-    else hipLaunchKernelGGL((iir_kernel<float, IirCoef, false>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c1, y1, nullptr, nullptr);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
 // a9 for classify(), checkpoint form: ONE pass over x runs both band-pass recurrences and writes back NEITHER filtered
 // signal.  What classify() needs from the filtered signals are spectrogram segments (256 samples every 224), and a direct
 // form II filter can be restarted anywhere from its delay line v[n-1..n-8]: the kernel stores that state at every segment
 // start and (round 3) at every segment's middle (32 bytes each; 9 KB per 1 s clip and filter at most, instead of 128 KB of
 // filtered samples), and the spectrogram kernels recompute exactly the segments they transform -- same operations on the same
 // values in the same order, so the same bits (spec_from_ckpt_kernel).  For the 1000-3000 Hz filter the output taps run here as well, because its segments'
-// sequential sums (classifier.cpp:329-333) and the energy gate (see iir2_split_kernel) come from every sample; the
+// sequential sums (classifier.cpp:329-333) and the energy gate (the taps wave, below) come from every sample; the
 // 3000-7500 Hz filter needs its taps only for clips that turn out to have midpoints, so they wait for the recompute.
 //   part 0: recurrence 3000-7500 Hz (checkpoints to HBM)   part 1: recurrence 1000-3000 Hz (checkpoints parked in LDS, v tiles to LDS)
 //   part 2: taps 1000-3000 Hz one tile behind (segment means, energy gate; writes the parked checkpoints of gated-in segments)
 // Which wave of the block runs which part follows the SIMD loads the launch measures itself (simd_load, below).
 // HBM traffic: x once + 71 x (64 + 4) B per 1 s clip + 64 + 4 B per gated-in segment.
 // ---------------------------------------------------------------------------------
-// DUAL (round 3, an experiment; default off): ONE wave runs both recurrences of its 64 clips as PACKED fp32 operations -- lane l
-// holds the pair (1000-3000 Hz, 3000-7500 Hz) of its clip's delay lines, and v = v - a[j] d[j-1] is one v_pk_mul_f32 + one
-// v_pk_add_f32 for both filters (component-wise IEEE multiply and add, no contraction: the same bits as two scalar chains; the 50
-// classify tests stay array_equal).  The block then has two waves (recurrences, taps) instead of three.  Measured on 49 152 clips
-// (tools/ab_classify.py, interleaved): three waves 2.58 ms, packed pair 2.79 ms, two SCALAR chains in one wave 2.85 ms.  What limits
-// a recurrence wave is how often ONE wave gets to issue (16 operations per ~110-cycle sample step, ~7 cycles apiece whatever their
-// dependencies); a packed operation issues for twice as long, so one wave doing both filters is slower than two waves doing one each.
+// (One wave running both recurrences as packed fp32 pairs, two waves per block, measured slower: 2.79 ms against 2.58 ms per 49 152
+// clips, profiles/HISTORY.md.)
 // ---- int16 PCM in the classifier kernels' loads (SURVEY 8f-1's second reader): IN = 0 float samples, 1 int16 mono (s / 32768,
 // sync/sync.cpp:237-242, donut-classifier/classifier.c:55-59), 2 interleaved int16 stereo, channel 0 (classifier.c:286-297), 3 stereo,
 // (L + R) / 65536 (the average of the channels' s / 32768, main_test.c:205-217: exact in float for |L + R| < 2^24).  The conversions are
@@ -463,28 +209,23 @@ __device__ __forceinline__ float cls_sample_at(const void *__restrict__ x, long 
     else return (float)((int)reinterpret_cast<const short *>(x)[2 * idx] + (int)reinterpret_cast<const short *>(x)[2 * idx + 1]) * (1.0f / 65536.0f);
 }
 
-#ifndef DSP_CKPT_DUAL
-#define DSP_CKPT_DUAL 0
-#endif
-typedef float ck_f2 __attribute__((ext_vector_type(2)));
 // RAGGED: clips of different lengths (spans[clip]: start, segments).  The workspaces keep the uniform [clip][n_seg(n)] layout, n = the
 // longest clip; a block walks as many tiles as its own longest clip's WHOLE segments cover (a multiple of the tile: a tail past the last
 // whole segment feeds nothing, see the taps wave) and a lane simply stops keeping states / means / gates at its clip's last segment --
 // what it computes past that point (the next clip's samples, zeros past the buffer's end) is never looked at.
-template <bool EVEN_B, bool DUAL, int IN = 0, bool RAGGED = false>
-__global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void *__restrict__ xv, long n_clips, int n_arg, long stride,
+template <bool EVEN_B, int IN = 0, bool RAGGED = false>
+__global__ __launch_bounds__(192) void iir2_ckpt_kernel(const void *__restrict__ xv, long n_clips, int n_arg, long stride,
                                                         const IirCoef c_bp, const IirCoef c_mp, float *__restrict__ ck_bp,
                                                         float *__restrict__ ck_mp, float *__restrict__ means_mp,
                                                         int *__restrict__ want_mp, const SpecTables *__restrict__ tab, int vec_ok, int *__restrict__ simd_load,
                                                         int blocks_per_cu, const ClipSpan *__restrict__ spans = nullptr, long total = 0)
 {
-    static_assert(!(RAGGED && DUAL), "the ragged form exists for the three-wave kernel");
     __shared__ float tin[2][64 * IIR_LD];
     __shared__ float vbuf[2][64 * IIR_LD];             // v tiles of the 1000-3000 Hz filter, [tile parity]
     // The 1000-3000 Hz restart states wait in LDS until the taps wave has the segment's energy gate: only the gated-in segments
     // (8 % in the bench workload) are ever recomputed, so only their states go to HBM (4.1 of the 4.5 KB per clip and filter
     // stay on chip).  Three entries are live at most: start of segment k (by parity), its middle, start of segment k + 1.
-    __shared__ float ckbuf[DUAL ? 1 : 3][8][64];
+    __shared__ float ckbuf[3][8][64];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // Which wave takes which part (wv: 0 = 3000-7500 Hz recurrence, 1 = 1000-3000 Hz recurrence, 2 = taps) follows the load of the
@@ -497,7 +238,7 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
     // SIMD holds taps waves and no recurrence wave has more than one neighbour.  Scheduling only: what a part computes does not
     // depend on the wave that runs it, and a block that reads the table too early merely keeps a poorer choice.
     int wv = wib;
-    if (!DUAL && simd_load != nullptr) {
+    if (simd_load != nullptr) {
         __shared__ int s_simd[3], s_taps;
         const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFu;     // HW_ID, XCC_ID
         int *row = simd_load + (((xcc << 8) | ((hw >> 8) & 0xFFu)) & (kSimdLoadCus - 1)) * kSimdLoadStride;       // (XCC, SE, SH, CU)
@@ -529,11 +270,10 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
 #endif
     if (DSP_CKPT_PRIO && wv < 2) __builtin_amdgcn_s_setprio(DSP_CKPT_PRIO);
     const int tid = wv * 64 + lane;                     // thread number by part: the 128 recurrence threads stage the x tiles
-    const bool is_r = DUAL ? wv == 0 : wv < 2;          // runs a recurrence (DUAL: both)
-    const bool is_t = DUAL ? wv == 1 : wv == 2;         // runs the 1000-3000 Hz taps
-    const bool loader = DUAL ? true : wv < 2;           // the 128 threads that stage the x tiles
-    const IirCoef c = (DUAL || wv != 0) ? c_mp : c_bp;   // the wave's (second) filter: 1000-3000 Hz except for !DUAL wave 0
-    float *__restrict__ ck = (DUAL || wv != 0) ? ck_mp : ck_bp;
+    const bool is_r = wv < 2;                           // runs a recurrence, and is one of the 128 threads that stage the x tiles
+    const bool is_t = wv == 2;                          // runs the 1000-3000 Hz taps
+    const IirCoef c = wv != 0 ? c_mp : c_bp;            // the wave's filter: 1000-3000 Hz except for wave 0
+    float *__restrict__ ck = wv != 0 ? ck_mp : ck_bp;
     const long clip0 = (long)blockIdx.x * 64;
     const int rows = (int)((n_clips - clip0) < 64 ? (n_clips - clip0) : 64);
     const int n_seg = n_arg < kSpecSeg ? 0 : (n_arg - kSpecSeg) / kSpecHop + 1;      // the workspaces' row length (RAGGED: the longest clip's)
@@ -556,13 +296,14 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
     static_assert(kSpecHop % IIR_TS == 0 && kSpecSeg - kSpecHop == IIR_TS, "segments start on tile boundaries and overlap by one tile");
     constexpr int kTilesPerHop = kSpecHop / IIR_TS;
     float d[8];                                         // v[n-1] .. v[n-8] of this lane's clip
-    ck_f2 dp[8], ap[9];                                 // DUAL: (1000-3000 Hz, 3000-7500 Hz) pairs of delay line and a[j]
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { d[j] = 0.0f; dp[j] = ck_f2{0.0f, 0.0f}; }
-#pragma unroll
-    for (int j = 0; j < 9; ++j) ap[j] = ck_f2{c_mp.a[j], c_bp.a[j]};
-    (void)dp; (void)ap;
-    float cur = 0.0f, prev = 0.0f;
+    for (int j = 0; j < 8; ++j) d[j] = 0.0f;
+    float cur = 0.0f, prev = 0.0f;                      // taps wave: running sums of the current / previous segment
+    // The energy gate (taps wave): an upper bound of each segment's windowed, mean-removed energy
+    // E = sum w^2 (y - m)^2 = A - 2 m B + m^2 C <= A + 2 |m| |B| + m^2 C with A = sum w^2 y^2, B = sum w^2 y, C = sum w^2.
+    // Every PSD cell of the segment is at most 2 |X[k]|^2 / U <= 512 E / U (Parseval), so when 512 E / U (gate_scale: with 1 % margin
+    // for the float sums) stays below the 70 dB threshold mp_keep_min no cell can reach it: the segment's flag is 0 without a
+    // transform, and it stays off the work list.  gate_ok: the window is exactly 1 between its tapers (else every segment is listed).
     const bool gating = tab->gate_ok != 0;
     float ea_cur = 0.0f, eb_cur = 0.0f, ea_prev = 0.0f, eb_prev = 0.0f;
     // The gate's B = sum w^2 y of a segment: in the six tiles where the window is 1 it is the same sum as `cur`, so only the tapered
@@ -608,14 +349,14 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
     };
     auto tile_cols = [&](int s) { const int t0 = s * IIR_TS; return n - t0 < IIR_TS ? n - t0 : IIR_TS; };
     auto fast = [&](int s) { return RAGGED || (vec_ok && tile_cols(s) == IIR_TS); };      // (RAGGED: every tile is whole)
-    if (loader) {                                                  // tile 0 into tin[0], tile 1 in flight
+    if (is_r) {                                                    // tile 0 into tin[0], tile 1 in flight
         if (fast(0)) { issue(0); commit(tin[0]); } else load_scalar(0, tile_cols(0), tin[0]);
         if (n_tiles > 1 && fast(1)) issue(IIR_TS);
     }
     __syncthreads();
 
     for (int s = 0; s <= n_tiles; ++s) {
-        if (loader && s + 1 < n_tiles) {
+        if (is_r && s + 1 < n_tiles) {
             // stage x tile s+1 for the next step, start the loads of tile s+2
             if (fast(s + 1)) commit(tin[(s + 1) & 1]); else load_scalar((s + 1) * IIR_TS, tile_cols(s + 1), tin[(s + 1) & 1]);
             if (s + 2 < n_tiles && fast(s + 2)) issue((s + 2) * IIR_TS);
@@ -627,22 +368,12 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
                 const int seg = s / kTilesPerHop, seg_tile = s % kTilesPerHop;
                 constexpr int kMidTile = kSpecSeg / 2 / IIR_TS;
                 static_assert(kSpecSeg / 2 % IIR_TS == 0 && kMidTile < kTilesPerHop, "the segment's middle lies on a tile boundary");
-                const int ck_n = (DUAL || wv != 0) ? kCkPerSegMp : kCkPerSegBp;      // states per segment of `ck`
-                const bool at_start = seg_tile == 0, at_mid = seg_tile == kMidTile && (DUAL ? (kCkPerSegBp == 2 || kCkPerSegMp == 2) : ck_n == 2);
+                const int ck_n = wv != 0 ? kCkPerSegMp : kCkPerSegBp;      // states per segment of `ck`
+                const bool at_start = seg_tile == 0, at_mid = seg_tile == kMidTile && ck_n == 2;
                 if ((at_start || at_mid) && seg < my_nseg && lane < rows) {
                     const long slot = (((clip0 + lane) * n_seg + seg) * ck_n + (at_mid ? 1 : 0)) * 8;
                     float4 *dst = reinterpret_cast<float4 *>(ck + slot);
-                    if (DUAL) {
-                        float4 *dst2 = reinterpret_cast<float4 *>(ck_bp + (((clip0 + lane) * n_seg + seg) * kCkPerSegBp + (at_mid ? 1 : 0)) * 8);
-                        if (at_start || kCkPerSegMp == 2) {
-                            dst[0] = make_float4(dp[0].x, dp[1].x, dp[2].x, dp[3].x);
-                            dst[1] = make_float4(dp[4].x, dp[5].x, dp[6].x, dp[7].x);
-                        }
-                        if (at_start || kCkPerSegBp == 2) {
-                            dst2[0] = make_float4(dp[0].y, dp[1].y, dp[2].y, dp[3].y);
-                            dst2[1] = make_float4(dp[4].y, dp[5].y, dp[6].y, dp[7].y);
-                        }
-                    } else if (wv != 0) {                            // 1000-3000 Hz: parked in LDS for the taps wave's gate
+                    if (wv != 0) {                            // 1000-3000 Hz: parked in LDS for the taps wave's gate
                         float (*e)[64] = ckbuf[at_mid ? 1 : (seg & 1) * 2];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) e[j][lane] = d[j];
@@ -663,17 +394,7 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
                     d[0] = v;
                     return v;
                 };
-                auto recp = [&](float xv) {                          // DUAL: both filters on the sample, packed (x: 1000-3000 Hz, y: 3000-7500 Hz)
-#pragma clang fp contract(off)
-                    ck_f2 v = ck_f2{xv, xv};
-#pragma unroll
-                    for (int j = 1; j <= 8; ++j) v = v - ap[j] * dp[j - 1];
-#pragma unroll
-                    for (int j = 7; j > 0; --j) dp[j] = dp[j - 1];
-                    dp[0] = v;
-                    return v.x;
-                };
-                const bool keep_v = DUAL || wv == 1;                 // the 1000-3000 Hz v tiles go to the taps wave
+                const bool keep_v = wv == 1;                         // the 1000-3000 Hz v tiles go to the taps wave
                 if (lane < rows && cols == IIR_TS) {
 #pragma unroll
                     for (int h = 0; h < IIR_TS; h += IIR_BURST) {
@@ -681,7 +402,7 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
 #pragma unroll
                         for (int i = 0; i < IIR_BURST; ++i) xr[i] = xin[lane * IIR_LD + h + i];
 #pragma unroll
-                        for (int i = 0; i < IIR_BURST; ++i) vr[i] = DUAL ? recp(xr[i]) : rec(xr[i]);
+                        for (int i = 0; i < IIR_BURST; ++i) vr[i] = rec(xr[i]);
                         if (keep_v) {
 #pragma unroll
                             for (int i = 0; i < IIR_BURST; ++i) vo[lane * IIR_LD + h + i] = vr[i];
@@ -689,8 +410,7 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
                     }
                 } else if (lane < rows) {
                     for (int i = 0; i < cols; ++i) {
-                        const float xv = xin[lane * IIR_LD + i];
-                        const float v = DUAL ? recp(xv) : rec(xv);
+                        const float v = rec(xin[lane * IIR_LD + i]);
                         if (keep_v) vo[lane * IIR_LD + i] = v;
                     }
                 }
@@ -757,15 +477,13 @@ __global__ __launch_bounds__(DUAL ? 128 : 192) void iir2_ckpt_kernel(const void 
                     // (hipcc turns the per-lane add into one atomic per wave)
                     if (g) {
                         want_mp[1 + atomicAdd(want_mp, 1)] = (int)((clip0 + lane) * n_seg + seg_k - 1);
-                        if (!DUAL) {                                 // the segment will be recomputed: its restart states leave LDS
-                            const int sg = seg_k - 1;
+                        const int sg = seg_k - 1;                    // the segment will be recomputed: its restart states leave LDS
 #pragma unroll
-                            for (int h = 0; h < kCkPerSegMp; ++h) {
-                                const float (*e)[64] = ckbuf[h ? 1 : (sg & 1) * 2];
-                                float4 *dst = reinterpret_cast<float4 *>(ck + (((clip0 + lane) * n_seg + sg) * kCkPerSegMp + h) * 8);
-                                dst[0] = make_float4(e[0][lane], e[1][lane], e[2][lane], e[3][lane]);
-                                dst[1] = make_float4(e[4][lane], e[5][lane], e[6][lane], e[7][lane]);
-                            }
+                        for (int h = 0; h < kCkPerSegMp; ++h) {
+                            const float (*e)[64] = ckbuf[h ? 1 : (sg & 1) * 2];
+                            float4 *dst = reinterpret_cast<float4 *>(ck + (((clip0 + lane) * n_seg + sg) * kCkPerSegMp + h) * 8);
+                            dst[0] = make_float4(e[0][lane], e[1][lane], e[2][lane], e[3][lane]);
+                            dst[1] = make_float4(e[4][lane], e[5][lane], e[6][lane], e[7][lane]);
                         }
                     }
                 }
@@ -808,14 +526,13 @@ hipError_t launch_iir2_ckpt(const void *x, long n_clips, int n, long stride, con
     }
     const int bytes = in_kind == 0 ? 4 : (in_kind == 1 ? 2 : 4);
     const int vec_ok = (stride * bytes) % 16 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
-    constexpr bool dual = DSP_CKPT_DUAL != 0;
-#define DSP_CKPT_LAUNCH(E, D, I)                                                                                                          \
-    hipLaunchKernelGGL((iir2_ckpt_kernel<E, D, I>), dim3(blocks), dim3(D ? 128 : 192), 0, stream, x, n_clips, n, stride, c_bp, c_mp, ck_bp, ck_mp, \
+#define DSP_CKPT_LAUNCH(E, I)                                                                                                             \
+    hipLaunchKernelGGL((iir2_ckpt_kernel<E, I>), dim3(blocks), dim3(192), 0, stream, x, n_clips, n, stride, c_bp, c_mp, ck_bp, ck_mp,    \
                        means_mp, want_mp, tables, vec_ok, simd_load, blocks / n_cu)
     const bool even = even_taps_only(c_mp);
-    if (spans) {                                                     // ragged batches: the literal tables' even numerators, three-wave form
+    if (spans) {                                                     // ragged batches: the literal tables' even numerators
 #define DSP_CKPT_LAUNCH_RAGGED(I)                                                                                                         \
-    hipLaunchKernelGGL((iir2_ckpt_kernel<true, false, I, true>), dim3(blocks), dim3(192), 0, stream, x, n_clips, n, stride, c_bp, c_mp, ck_bp, ck_mp, \
+    hipLaunchKernelGGL((iir2_ckpt_kernel<true, I, true>), dim3(blocks), dim3(192), 0, stream, x, n_clips, n, stride, c_bp, c_mp, ck_bp, ck_mp, \
                        means_mp, want_mp, tables, 1, simd_load, blocks / n_cu, spans, total)
         if (!even || in_kind < 0 || in_kind > 3) return hipErrorInvalidValue;
         if (in_kind == 0) DSP_CKPT_LAUNCH_RAGGED(0);
@@ -825,13 +542,21 @@ hipError_t launch_iir2_ckpt(const void *x, long n_clips, int n, long stride, con
 #undef DSP_CKPT_LAUNCH_RAGGED
         return hipGetLastError();
     }
-    if (in_kind == 0) { if (even) DSP_CKPT_LAUNCH(true, dual, 0); else DSP_CKPT_LAUNCH(false, dual, 0); }
+    if (in_kind == 0) { if (even) DSP_CKPT_LAUNCH(true, 0); else DSP_CKPT_LAUNCH(false, 0); }
     else if (!even) return hipErrorInvalidValue;                     // int16 input: the literal tables' even numerators only
-    else if (in_kind == 1) DSP_CKPT_LAUNCH(true, false, 1);
-    else if (in_kind == 2) DSP_CKPT_LAUNCH(true, false, 2);
-    else if (in_kind == 3) DSP_CKPT_LAUNCH(true, false, 3);
+    else if (in_kind == 1) DSP_CKPT_LAUNCH(true, 1);
+    else if (in_kind == 2) DSP_CKPT_LAUNCH(true, 2);
+    else if (in_kind == 3) DSP_CKPT_LAUNCH(true, 3);
     else return hipErrorInvalidValue;
 #undef DSP_CKPT_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_iir_f32(const float *x, long n_clips, int n, long stride, const IirCoef &c, float *y, hipStream_t stream)
+{
+    if (n_clips <= 0 || n <= 0) return hipSuccess;
+    const int blocks = (int)((n_clips + 63) / 64);
+    hipLaunchKernelGGL((iir_kernel<float, IirCoef, false>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, stride, c, y, c, y);
     return hipGetLastError();
 }
 
@@ -840,7 +565,7 @@ hipError_t launch_iir_f64_on_f32(const float *x, long n_clips, int n, long strid
 {
     if (n_clips <= 0 || n <= 0) return hipSuccess;
     const int blocks = (int)((n_clips + 63) / 64);
-    hipLaunchKernelGGL((iir_kernel<double, IirCoefD, false, float>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, stride, c, y, c, y, nullptr, nullptr);
+    hipLaunchKernelGGL((iir_kernel<double, IirCoefD, false, float>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, stride, c, y, c, y);
     return hipGetLastError();
 }
 
@@ -849,26 +574,18 @@ hipError_t launch_iir_f64(const double *x, long n_clips, int n, long stride, con
 {
     if (n_clips <= 0 || n <= 0) return hipSuccess;
     const int blocks = (int)((n_clips + 63) / 64);
-    hipLaunchKernelGGL((iir_kernel<double, IirCoefD, false>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, stride, c, y, c, y, nullptr, nullptr);
+    hipLaunchKernelGGL((iir_kernel<double, IirCoefD, false>), dim3(blocks), dim3(64), 0, stream, x, n_clips, n, stride, stride, c, y, c, y);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------
-// a10: spectrogram.  A wavefront takes 64 consecutive (clip, time bin) frames.
-//   phase 1  lane f runs the reference's SEQUENTIAL fp32 sum of frame f (classifier.cpp:329-333):
-//            the order of the 256 additions is part of the result, so it stays serial per frame
-//            and the parallelism is across the 64 frames;
-//   phase 2  frame by frame the whole wave runs the 256-point FFT: lane g owns 4 points and does
-//            two radix-2 levels of PlainFFT.cpp:50-84 per LDS round trip (4 round trips).  Every
-//            butterfly is the reference's expression with the reference's twiddle value, and the
-//            butterflies of one level are independent, so the results are bit-identical to the
-//            serial loop whatever the lane split.
+// a10: spectrogram.  One wavefront transforms one frame at a time (SpecLane, shared by the entry point's spectrogram_kernel
+// and classify()'s spec_from_ckpt_kernel): lane g owns 4 points of the 256-point FFT and does two radix-2 levels of
+// PlainFFT.cpp:50-84 per LDS round trip (4 round trips).  Every butterfly is the reference's expression with the
+// reference's twiddle value, and the butterflies of one level are independent, so the results are bit-identical to the
+// serial loop whatever the lane split.  The frame's mean is the reference's SEQUENTIAL fp32 sum (classifier.cpp:329-333):
+// the order of the 256 additions is part of the result, so it stays serial per frame, a lane per frame.
 // ---------------------------------------------------------------------------------
-#ifndef DSP_SPEC_TILE
-#define DSP_SPEC_TILE 16
-#endif
-// frames whose PSD columns are collected in LDS before they are stored as row segments (SPEC_TILE floats each)
-constexpr int SPEC_TILE = DSP_SPEC_TILE;
 __device__ __forceinline__ unsigned bitrev6(unsigned v) { return __brev(v) >> 26; }
 
 struct cpx { float x, y; };
@@ -894,127 +611,44 @@ __device__ __forceinline__ void butterfly(cpx &a, cpx &b, const cpx u)
     a.y = a.y + t2;
 }
 
-// hits (optional): work list of the clips whose map is wanted (hits[0] = count, then clip numbers, as written by
-// classify_midpoints_kernel): frame slot s of the launch is time bin s % T of clip hits[1 + s / T], so the wanted clips
-// are packed into the first wavefronts whatever their position in the batch, and the others exit at once.
-// OUT selects what leaves the kernel:
-//   SPEC_BIN_MAJOR    the reference's [bin][time] map (the spectrogram entry point)
-//   SPEC_FRAME_MAJOR  [time][bin]: one frame = 129 consecutive floats, stored straight from the registers (the band-pass
-//                     map inside classify(); classify_bands_kernel reads that layout)
-//   SPEC_FLAGS        no map at all: one int per frame, 1 when any of its 129 cells is >= SpecTables::mp_keep_min.  That
-//                     is all find_midpoints takes from the 1000-3000 Hz map (classifier.cpp:457-518), so classify() never
-//                     writes that map to HBM (36 KB per clip written and read back otherwise)
-enum { SPEC_BIN_MAJOR = 0, SPEC_FRAME_MAJOR = 1, SPEC_FLAGS = 2 };
-template <int OUT>
-__global__ __launch_bounds__(256) void spectrogram_kernel(const float *__restrict__ y, long n_clips, int n, long stride,
-                                                          const SpecTables *__restrict__ tab, float *__restrict__ sxx, int T,
-                                                          const float *__restrict__ means, const int *__restrict__ hits,
-                                                          const int *__restrict__ gate)
+// p / U in three instructions (SpecTables::rU, div_fast): q = p rU, then one Newton step on the exact residual
+__device__ __forceinline__ float div_by_u_fast(float p, float U, float rU)
 {
-    __shared__ float2 lds[4][kSpecSeg];
-    // PSD columns of SPEC_TILE consecutive frames are collected here and stored as row segments: the output is
-    // [bin][time], one frame is a COLUMN of it (129 scattered dwords if stored directly)
-    constexpr bool TILED = OUT == SPEC_BIN_MAJOR;
-    __shared__ float psd_tile[TILED ? 4 : 1][TILED ? kSpecBins * (SPEC_TILE + 1) : 1];
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float2 *buf = lds[wib];
-    float *tile = psd_tile[TILED ? wib : 0];
-    const long total = (hits ? (long)hits[0] : n_clips) * T;
-    const long gid0 = ((long)blockIdx.x * 4 + wib) * 64;
-    if (gid0 >= total) return;
-    auto clip_of = [&](long slot) { return hits ? (long)hits[1 + slot] : slot; };
-    // SPEC_FLAGS with a gate (written by the IIR kernel, [clip][T]): 0 = the frame's energy proves that no cell can reach
-    // the threshold (max_k PSD[k] <= 2 |X[k]|^2 / U <= 512 sum v_n^2 / U, Parseval), so its flag is 0 without a transform
-    unsigned long long todo = ~0ull;
-    if (OUT == SPEC_FLAGS && gate) {
-        const bool maybe = gid0 + lane < total && gate[gid0 + lane] != 0;
-        todo = __ballot(maybe);
-        if (todo == 0) {
-            if (gid0 + lane < total) reinterpret_cast<int *>(sxx)[gid0 + lane] = 0;
-            return;
-        }
-    }
+    const float q = p * rU;
+    return fmaf(fmaf(-q, U, p), rU, q);
+}
 
-    // ---- phase 1: sequential mean of this lane's frame
-    float mean = 0.0f;
-    {
-        const long gid = gid0 + lane;
-        if (gid < total) {
-            const long slot = gid / T;
-            const int t = (int)(gid - slot * T);
-            const long clip = clip_of(slot);
-            if (means) {              // already summed, in the same order, by the IIR kernel's lanes
-                mean = means[clip * T + t];
-            } else {
-                const float *seg = y + clip * stride + (long)t * kSpecHop;
-                float sum = 0.0f;
-                for (int i = 0; i < kSpecSeg; ++i) sum = sum + seg[i];
-                mean = sum / (float)kSpecSeg;
-            }
-        }
-    }
-
-    // ---- per-lane constants of phase 2
-    // level pair (l, l+1), l1 = 2^l: lane g owns i_j = base + j l1, base = ((g >> l) << (l + 2)) | (g & (l1 - 1));
-    // level l uses tw[l1 - 1 + m] for both its butterflies, level l+1 tw[2 l1 - 1 + m] and tw[2 l1 - 1 + m + l1], m = g & (l1 - 1)
+struct SpecLane {                             // per-lane constants of the 256-point FFT, and the transform of one frame
     int pos[4][4];
     cpx ua[4], ub0[4], ub1[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int l = 2 * p, l1 = 1 << l, m = lane & (l1 - 1);
-        const int base = ((lane >> l) << (l + 2)) | m;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pos[p][j] = spec_swz(base + (j << l));
-        ua[p] = {tab->tw_re[l1 - 1 + m], tab->tw_im[l1 - 1 + m]};
-        ub0[p] = {tab->tw_re[2 * l1 - 1 + m], tab->tw_im[2 * l1 - 1 + m]};
-        ub1[p] = {tab->tw_re[2 * l1 - 1 + m + l1], tab->tw_im[2 * l1 - 1 + m + l1]};
-    }
-    // first pair works on bit-reversed positions 4g + j, i.e. on samples 64 bitrev2(j) + bitrev6(g) (PlainFFT.cpp:33-47)
     int src[4];
     float win[4];
+    // level pair (l, l+1), l1 = 2^l: lane g owns i_j = base + j l1, base = ((g >> l) << (l + 2)) | (g & (l1 - 1));
+    // level l uses tw[l1 - 1 + m] for both its butterflies, level l+1 tw[2 l1 - 1 + m] and tw[2 l1 - 1 + m + l1], m = g & (l1 - 1).
+    // The first pair works on bit-reversed positions 4g + j, i.e. on samples 64 bitrev2(j) + bitrev6(g) (PlainFFT.cpp:33-47).
+    __device__ __forceinline__ void init(int lane, const SpecTables *__restrict__ tab)
+    {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        src[j] = 64 * (((j & 1) << 1) | (j >> 1)) + (int)bitrev6(lane);
-        win[j] = tab->window[src[j]];
+        for (int p = 0; p < 4; ++p) {
+            const int l = 2 * p, l1 = 1 << l, m = lane & (l1 - 1);
+            const int base = ((lane >> l) << (l + 2)) | m;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) pos[p][j] = spec_swz(base + (j << l));
+            ua[p] = {tab->tw_re[l1 - 1 + m], tab->tw_im[l1 - 1 + m]};
+            ub0[p] = {tab->tw_re[2 * l1 - 1 + m], tab->tw_im[2 * l1 - 1 + m]};
+            ub1[p] = {tab->tw_re[2 * l1 - 1 + m + l1], tab->tw_im[2 * l1 - 1 + m + l1]};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            src[j] = 64 * (((j & 1) << 1) | (j >> 1)) + (int)bitrev6(lane);
+            win[j] = tab->window[src[j]];
+        }
     }
-    const float U = tab->U;
-    const bool trivial01 = tab->trivial_first_levels != 0;
-    const float keep_min = tab->mp_keep_min;
-    int flag = 0;
-
-    // ---- phase 2
-    const int n_here = (int)(total - gid0 < 64 ? total - gid0 : 64);
-    long slot = gid0 / T;
-    int t = (int)(gid0 - slot * T);
-    long clip = clip_of(slot);
-    // the four samples of the NEXT frame are requested before the current one is transformed: a frame is ~0.4 us of
-    // arithmetic behind ~1.5 us of load latency otherwise (three wavefronts per SIMD do not cover that)
-    float raw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    bool have_raw = false;                                  // raw holds the samples of the frame about to be transformed
-    for (int f = 0; f < n_here; ++f) {
-        if (OUT == SPEC_FLAGS && !((todo >> f) & 1)) {      // gated out: flag 0
-            have_raw = false;
-            if (++t == T) { t = 0; ++slot; if (f + 1 < n_here) clip = clip_of(slot); }
-            continue;
-        }
-        const float mean_f = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mean), f));
-        if (!have_raw) {
-            const float *seg = y + clip * stride + (long)t * kSpecHop;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) raw[j] = seg[src[j]];
-        }
-        float cur[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cur[j] = raw[j];
-        have_raw = f + 1 < n_here && ((todo >> (f + 1)) & 1);
-        if (have_raw) {
-            const bool wrap = t + 1 == T;
-            const long nclip = wrap ? clip_of(slot + 1) : clip;
-            const float *seg = y + nclip * stride + (long)(wrap ? 0 : t + 1) * kSpecHop;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) raw[j] = seg[src[j]];
-        }
+    // cur[j] = sample src[j] of the frame; returns the PSD cells lane, lane + 64 and (lane 0) 128.  div_fast: only with the rU of a
+    // table that launch_spec_div_verify has passed (SpecTables::div_fast)
+    __device__ __forceinline__ void psd(const float (&cur)[4], float mean_f, float U, bool trivial01, float2 *buf, int lane,
+                                        float &p0, float &p1, float &p2, float rU = 0.0f, bool div_fast = false) const
+    {
         cpx v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = {(cur[j] - mean_f) * win[j], 0.0f};          // classifier.cpp:336-346
@@ -1048,152 +682,7 @@ __global__ __launch_bounds__(256) void spectrogram_kernel(const float *__restric
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
         }
-        // lane g now holds X[g], X[g + 64], X[g + 128], X[g + 192]; classifier.cpp:350-365
-        float p0 = (v[0].x * v[0].x + v[0].y * v[0].y) / U;
-        if (lane >= 1) p0 = p0 * 2.0f;
-        float p1 = (v[1].x * v[1].x + v[1].y * v[1].y) / U;
-        p1 = p1 * 2.0f;
-        const float p2 = (v[2].x * v[2].x + v[2].y * v[2].y) / U;      // bin 128, lane 0 only
-        if (OUT == SPEC_FLAGS) {
-            const bool loud = p0 >= keep_min || p1 >= keep_min || (lane == 0 && p2 >= keep_min);
-            if (__ballot(loud) != 0 && lane == f) flag = 1;             // lane f keeps the flag of frame f
-        } else if (OUT == SPEC_FRAME_MAJOR) {
-            float *out = sxx + (clip * T + t) * (long)kSpecBins;
-            out[lane] = p0;
-            out[lane + 64] = p1;
-            if (lane == 0) out[128] = p2;
-        } else {
-            const int col = f & (SPEC_TILE - 1);
-            tile[lane * (SPEC_TILE + 1) + col] = p0;
-            tile[(lane + 64) * (SPEC_TILE + 1) + col] = p1;
-            if (lane == 0) tile[128 * (SPEC_TILE + 1) + col] = p2;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if ((f & (SPEC_TILE - 1)) == SPEC_TILE - 1 || f == n_here - 1) {
-                // flush frames [f & ~(SPEC_TILE - 1), f]: lane -> column lane % SPEC_TILE (one frame, one division), rows lane / SPEC_TILE + k 64 / SPEC_TILE
-                const int col2 = lane & (SPEC_TILE - 1), ff = (f & ~(SPEC_TILE - 1)) + col2;
-                if (ff <= f) {
-                    const long g = gid0 + ff;
-                    const long sl = g / T;
-                    const int tt = (int)(g - sl * T);
-                    float *out = sxx + clip_of(sl) * (long)kSpecBins * T + tt;
-                    for (int row = lane / SPEC_TILE; row < kSpecBins; row += 64 / SPEC_TILE) out[(long)row * T] = tile[row * (SPEC_TILE + 1) + col2];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
-        if (++t == T) { t = 0; ++slot; if (f + 1 < n_here) clip = clip_of(slot); }
-    }
-    if (OUT == SPEC_FLAGS && lane < n_here) reinterpret_cast<int *>(sxx)[gid0 + lane] = flag;      // [clip][T] (no work list here)
-}
-
-// ---------------------------------------------------------------------------------
-// a10 from checkpoints: the spectrogram of segments that were never written to HBM.  A 512-thread block takes 60 frame
-// slots ((clip, time bin) pairs); for the wanted ones it
-//   L  loads the segments' 256 input samples into its LDS rows (all waves, coalesced 1 KB rows);
-//   R  recomputes the recurrence v over the segment's 256 samples, lane per frame (wave 0), from the delay line
-//      iir2_ckpt_kernel stored at the segment start: classifier.cpp:199-205 on the same x with the same state;
-//   T  applies the output taps y[n] = b0 v[n] + sum b[j] v[n-j] (classifier.cpp:207-216): no feedback, so the eight waves
-//      take an eighth of every segment each, and y overwrites v in place;
-//   M  (3000-7500 Hz map only) sums each segment in order for its mean (classifier.cpp:329-333), lane per frame;
-//   F  runs the 256-point PlainFFT of each wanted frame, a wave per frame, 7 or 8 frames per wave, exactly as
-//      spectrogram_kernel does, reading the samples from the block's LDS rows.
-// OUT = SPEC_FLAGS: slot = clip * T + t over all clips, wanted = gate != 0, output one flag per slot (0 for the others);
-// OUT = SPEC_FRAME_MAJOR: slots walk the work list `hits`, every frame is wanted, output [time][bin] PSD rows.
-// ---------------------------------------------------------------------------------
-// 512 threads and 60 frame slots per block: 60 rows + 8 FFT buffers = 80.5 KB, so TWO blocks of eight waves fit a CU's 160 KB
-// (64 slots would be 84.7 KB: one block per CU).  The recompute is lane-per-frame on one wave (~9 us whatever the lane
-// count), so what a CU delivers is frames in flight / block latency: 2 x 60 frames over (1 + 9 + 1 + 1 + 3.4) us instead of
-// 2 x 64 over (2 + 9 + 2 + 1 + 7) us with four waves per block.
-constexpr int RC_THREADS = 512, RC_WAVES = RC_THREADS / 64, RC_FRAMES = 60;
-static_assert((kSpecSeg / RC_WAVES) % IIR_BURST == 0 && RC_FRAMES <= 64, "taps split evenly over the waves; a frame per lane");
-constexpr int RC_ROW = 8 + kSpecSeg + 1;      // v[-8..-1] | 256 samples | pad: odd stride, lane l <-> row l is conflict free
-
-// p / U in three instructions (SpecTables::rU, div_fast): q = p rU, then one Newton step on the exact residual
-__device__ __forceinline__ float div_by_u_fast(float p, float U, float rU)
-{
-    const float q = p * rU;
-    return fmaf(fmaf(-q, U, p), rU, q);
-}
-
-__global__ __launch_bounds__(256) void spec_div_verify_kernel(const SpecTables *__restrict__ tab, unsigned long long *__restrict__ mismatches)
-{
-    const float U = tab->U, rU = tab->rU;
-    const unsigned lo = __float_as_uint(kDivFastLo), hi = __float_as_uint(kDivFastHi);
-    unsigned long long bad = 0;
-    for (unsigned long long b = lo + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b <= hi; b += (unsigned long long)gridDim.x * blockDim.x) {
-        const float p = __uint_as_float((unsigned)b);
-        const float exact = p / U;
-        bad += __float_as_uint(div_by_u_fast(p, U, rU)) != __float_as_uint(exact);
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
-hipError_t launch_spec_div_verify(const SpecTables *tables, unsigned long long *mismatches, hipStream_t stream)
-{
-    hipLaunchKernelGGL(spec_div_verify_kernel, dim3(4096), dim3(256), 0, stream, tables, mismatches);
-    return hipGetLastError();
-}
-
-struct SpecLane {                             // per-lane constants of the 256-point FFT (see spectrogram_kernel)
-    int pos[4][4];
-    cpx ua[4], ub0[4], ub1[4];
-    int src[4];
-    float win[4];
-    __device__ __forceinline__ void init(int lane, const SpecTables *__restrict__ tab)
-    {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int l = 2 * p, l1 = 1 << l, m = lane & (l1 - 1);
-            const int base = ((lane >> l) << (l + 2)) | m;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pos[p][j] = spec_swz(base + (j << l));
-            ua[p] = {tab->tw_re[l1 - 1 + m], tab->tw_im[l1 - 1 + m]};
-            ub0[p] = {tab->tw_re[2 * l1 - 1 + m], tab->tw_im[2 * l1 - 1 + m]};
-            ub1[p] = {tab->tw_re[2 * l1 - 1 + m + l1], tab->tw_im[2 * l1 - 1 + m + l1]};
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            src[j] = 64 * (((j & 1) << 1) | (j >> 1)) + (int)bitrev6(lane);
-            win[j] = tab->window[src[j]];
-        }
-    }
-    // cur[j] = sample src[j] of the frame; returns the PSD cells lane, lane + 64 and (lane 0) 128
-    __device__ __forceinline__ void psd(const float (&cur)[4], float mean_f, float U, bool trivial01, float2 *buf, int lane,
-                                        float &p0, float &p1, float &p2, float rU = 0.0f, bool div_fast = false) const
-    {
-        cpx v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = {(cur[j] - mean_f) * win[j], 0.0f};          // classifier.cpp:336-346
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            if (p > 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { const float2 q = buf[pos[p][j]]; v[j] = {q.x, q.y}; }
-            }
-            if (p == 0 && trivial01) {
-                const float a0 = v[0].x + v[1].x, a1 = v[0].x - v[1].x, a2 = v[2].x + v[3].x, a3 = v[2].x - v[3].x;
-                v[0] = {a0 + a2, 0.0f};
-                v[2] = {a0 - a2, 0.0f};
-                v[1] = {a1, -a3};
-                v[3] = {a1, a3};
-            } else {
-                butterfly(v[0], v[1], ua[p]);
-                butterfly(v[2], v[3], ua[p]);
-                butterfly(v[0], v[2], ub0[p]);
-                butterfly(v[1], v[3], ub1[p]);
-            }
-            if (p < 3) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) buf[pos[p][j]] = make_float2(v[j].x, v[j].y);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
+        // lane g now holds X[g], X[g + 64], X[g + 128], X[g + 192]
         const float s0 = v[0].x * v[0].x + v[0].y * v[0].y, s1 = v[1].x * v[1].x + v[1].y * v[1].y, s2 = v[2].x * v[2].x + v[2].y * v[2].y;
         // classifier.cpp:350-365.  A frame whose every cell lies in the verified range takes the three-instruction division (the
         // same bits, SpecTables::div_fast); silent, denormal, huge or non-finite cells send the whole frame through the real one.
@@ -1215,6 +704,138 @@ struct SpecLane {                             // per-lane constants of the 256-p
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 };
+
+// The spectrogram entry point: the reference's [bin][time] map of clip rows in HBM.  A wavefront takes 64 consecutive
+// (clip, time bin) frames: phase 1 is each lane's sequential mean of its own frame, phase 2 the transforms, frame by frame.
+#ifndef DSP_SPEC_TILE
+#define DSP_SPEC_TILE 16
+#endif
+// frames whose PSD columns are collected in LDS before they are stored as row segments (SPEC_TILE floats each)
+constexpr int SPEC_TILE = DSP_SPEC_TILE;
+__global__ __launch_bounds__(256) void spectrogram_kernel(const float *__restrict__ y, long n_clips, long stride,
+                                                          const SpecTables *__restrict__ tab, float *__restrict__ sxx, int T)
+{
+    __shared__ float2 lds[4][kSpecSeg];
+    // PSD columns of SPEC_TILE consecutive frames are collected here and stored as row segments: the output is
+    // [bin][time], one frame is a COLUMN of it (129 scattered dwords if stored directly)
+    __shared__ float psd_tile[4][kSpecBins * (SPEC_TILE + 1)];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float2 *buf = lds[wib];
+    float *tile = psd_tile[wib];
+    const long total = n_clips * T;
+    const long gid0 = ((long)blockIdx.x * 4 + wib) * 64;
+    if (gid0 >= total) return;
+
+    // ---- phase 1: sequential mean of this lane's frame
+    float mean = 0.0f;
+    if (gid0 + lane < total) {
+        const long clip = (gid0 + lane) / T;
+        const int t = (int)(gid0 + lane - clip * T);
+        const float *seg = y + clip * stride + (long)t * kSpecHop;
+        float sum = 0.0f;
+        for (int i = 0; i < kSpecSeg; ++i) sum = sum + seg[i];
+        mean = sum / (float)kSpecSeg;
+    }
+
+    // ---- phase 2 (the exact division: any fs reaches this kernel, and the three-instruction form is verified for the context's table only)
+    SpecLane K;
+    K.init(lane, tab);
+    const float U = tab->U;
+    const bool trivial01 = tab->trivial_first_levels != 0;
+    const int n_here = (int)(total - gid0 < 64 ? total - gid0 : 64);
+    long clip = gid0 / T;
+    int t = (int)(gid0 - clip * T);
+    // the four samples of the NEXT frame are requested before the current one is transformed: a frame is ~0.4 us of
+    // arithmetic behind ~1.5 us of load latency otherwise (three wavefronts per SIMD do not cover that)
+    float raw[4];
+    auto request = [&](long rclip, int rt) {
+        const float *seg = y + rclip * stride + (long)rt * kSpecHop;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) raw[j] = seg[K.src[j]];
+    };
+    request(clip, t);
+    for (int f = 0; f < n_here; ++f) {
+        const float mean_f = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mean), f));
+        float cur[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cur[j] = raw[j];
+        if (f + 1 < n_here) {
+            const bool wrap = t + 1 == T;
+            request(wrap ? clip + 1 : clip, wrap ? 0 : t + 1);
+        }
+        float p0, p1, p2;
+        K.psd(cur, mean_f, U, trivial01, buf, lane, p0, p1, p2);
+        const int col = f & (SPEC_TILE - 1);
+        tile[lane * (SPEC_TILE + 1) + col] = p0;
+        tile[(lane + 64) * (SPEC_TILE + 1) + col] = p1;
+        if (lane == 0) tile[128 * (SPEC_TILE + 1) + col] = p2;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (col == SPEC_TILE - 1 || f == n_here - 1) {
+            // flush frames [f & ~(SPEC_TILE - 1), f]: lane -> column lane % SPEC_TILE (one frame, one division), rows lane / SPEC_TILE + k 64 / SPEC_TILE
+            const int col2 = lane & (SPEC_TILE - 1), ff = (f & ~(SPEC_TILE - 1)) + col2;
+            if (ff <= f) {
+                const long g = gid0 + ff;
+                const long fclip = g / T;
+                const int ft = (int)(g - fclip * T);
+                float *out = sxx + fclip * (long)kSpecBins * T + ft;
+                for (int row = lane / SPEC_TILE; row < kSpecBins; row += 64 / SPEC_TILE) out[(long)row * T] = tile[row * (SPEC_TILE + 1) + col2];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        if (++t == T) { t = 0; ++clip; }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// a10 from checkpoints: the spectrogram of segments that were never written to HBM.  A 512-thread block takes 60 frame
+// slots ((clip, time bin) pairs); for the wanted ones it
+//   L  loads the segments' 256 input samples into its LDS rows (all waves, coalesced 1 KB rows);
+//   R  recomputes the recurrence v over the segment's 256 samples, lane per frame (wave 0), from the delay line
+//      iir2_ckpt_kernel stored at the segment start: classifier.cpp:199-205 on the same x with the same state;
+//   T  applies the output taps y[n] = b0 v[n] + sum b[j] v[n-j] (classifier.cpp:207-216): no feedback, so the eight waves
+//      take an eighth of every segment each, and y overwrites v in place;
+//   M  (3000-7500 Hz map only) sums each segment in order for its mean (classifier.cpp:329-333), lane per frame;
+//   F  runs the 256-point PlainFFT of each wanted frame (SpecLane::psd), a wave per frame, 7 or 8 frames per wave, reading the
+//      samples from the block's LDS rows.
+// OUT selects what leaves the kernel:
+//   SPEC_FLAGS        slots walk the work list of gated-in frames; no map at all: one int per frame, 1 when any of its 129 cells
+//                     is >= SpecTables::mp_keep_min.  That is all find_midpoints takes from the 1000-3000 Hz map
+//                     (classifier.cpp:457-518), so classify() never writes that map to HBM (36 KB per clip otherwise)
+//   SPEC_FRAME_MAJOR  slots walk the work list `hits`, every frame is wanted; [time][bin] PSD rows, one frame = 129 consecutive
+//                     floats stored straight from the registers (the layout classify_bands_kernel reads)
+// ---------------------------------------------------------------------------------
+enum { SPEC_FRAME_MAJOR = 1, SPEC_FLAGS = 2 };      // (the values are part of the kernel names the recorded profiles carry)
+// 512 threads and 60 frame slots per block: 60 rows + 8 FFT buffers = 80.5 KB, so TWO blocks of eight waves fit a CU's 160 KB
+// (64 slots would be 84.7 KB: one block per CU).  The recompute is lane-per-frame on one wave (~9 us whatever the lane
+// count), so what a CU delivers is frames in flight / block latency: 2 x 60 frames over (1 + 9 + 1 + 1 + 3.4) us instead of
+// 2 x 64 over (2 + 9 + 2 + 1 + 7) us with four waves per block.
+constexpr int RC_THREADS = 512, RC_WAVES = RC_THREADS / 64, RC_FRAMES = 60;
+static_assert((kSpecSeg / RC_WAVES) % IIR_BURST == 0 && RC_FRAMES <= 64, "taps split evenly over the waves; a frame per lane");
+constexpr int RC_ROW = 8 + kSpecSeg + 1;      // v[-8..-1] | 256 samples | pad: odd stride, lane l <-> row l is conflict free
+
+__global__ __launch_bounds__(256) void spec_div_verify_kernel(const SpecTables *__restrict__ tab, unsigned long long *__restrict__ mismatches)
+{
+    const float U = tab->U, rU = tab->rU;
+    const unsigned lo = __float_as_uint(kDivFastLo), hi = __float_as_uint(kDivFastHi);
+    unsigned long long bad = 0;
+    for (unsigned long long b = lo + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; b <= hi; b += (unsigned long long)gridDim.x * blockDim.x) {
+        const float p = __uint_as_float((unsigned)b);
+        const float exact = p / U;
+        bad += __float_as_uint(div_by_u_fast(p, U, rU)) != __float_as_uint(exact);
+    }
+    if (bad) atomicAdd(mismatches, bad);
+}
+
+hipError_t launch_spec_div_verify(const SpecTables *tables, unsigned long long *mismatches, hipStream_t stream)
+{
+    hipLaunchKernelGGL(spec_div_verify_kernel, dim3(4096), dim3(256), 0, stream, tables, mismatches);
+    return hipGetLastError();
+}
 
 // Diagnostic build only (-DDSP_RC_STAMPS, never shipped): s_memtime at the phase boundaries of the first 2048 blocks, written to a
 // buffer of their own that no kernel reads (cdna_hip_programming.md 7, in-kernel stamps); tools/rc_stamps.py prints the medians.
@@ -1594,9 +1215,9 @@ hipError_t launch_iir2_f64(const double *x, long n_clips, int n, long stride, lo
     const int blocks = (int)((n_clips + 63) / 64);
     auto even = [](const IirCoefD &c) { return c.b[1] == 0.0 && c.b[3] == 0.0 && c.b[5] == 0.0 && c.b[7] == 0.0; };
     if (even(c1) && even(c2))                 // a Butterworth band-pass numerator is (1 - z^-2)^4 scaled: the designs of dsp_butter_bandpass have exact zeros there
-        hipLaunchKernelGGL((iir_kernel<double, IirCoefD, true, double, false, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2, nullptr, nullptr);
+        hipLaunchKernelGGL((iir_kernel<double, IirCoefD, true, double, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2);
     else
-        hipLaunchKernelGGL((iir_kernel<double, IirCoefD, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2, nullptr, nullptr);
+        hipLaunchKernelGGL((iir_kernel<double, IirCoefD, true>), dim3(blocks), dim3(128), 0, stream, x, n_clips, n, stride, ystride, c1, y1, c2, y2);
     return hipGetLastError();
 }
 
@@ -1662,28 +1283,12 @@ hipError_t launch_spectrogram_f64(const double *y, long n_clips, int n, long str
     return hipGetLastError();
 }
 
-hipError_t launch_spectrogram_f32(const float *y, long n_clips, int n, long stride, const SpecTables *tables,
-                                  float *sxx, hipStream_t stream, const float *means, const int *hits, bool frame_major)
+hipError_t launch_spectrogram_f32(const float *y, long n_clips, int n, long stride, const SpecTables *tables, float *sxx, hipStream_t stream)
 {
     const int T = n < kSpecSeg ? 0 : (n - kSpecSeg) / kSpecHop + 1;
     if (n_clips <= 0 || T <= 0) return hipSuccess;
     const long total = n_clips * T;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (frame_major)
-        hipLaunchKernelGGL(spectrogram_kernel<SPEC_FRAME_MAJOR>, grid, dim3(256), 0, stream, y, n_clips, n, stride, tables, sxx, T, means, hits, (const int *)nullptr);
-    else
-        hipLaunchKernelGGL(spectrogram_kernel<SPEC_BIN_MAJOR>, grid, dim3(256), 0, stream, y, n_clips, n, stride, tables, sxx, T, means, hits, (const int *)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_spectrogram_flags(const float *y, long n_clips, int n, long stride, const SpecTables *tables, int *flags,
-                                    hipStream_t stream, const float *means, const int *gate)
-{
-    const int T = n < kSpecSeg ? 0 : (n - kSpecSeg) / kSpecHop + 1;
-    if (n_clips <= 0 || T <= 0) return hipSuccess;
-    const long total = n_clips * T;
-    hipLaunchKernelGGL(spectrogram_kernel<SPEC_FLAGS>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, y, n_clips, n, stride, tables,
-                       reinterpret_cast<float *>(flags), T, means, (const int *)nullptr, gate);
+    hipLaunchKernelGGL(spectrogram_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, y, n_clips, stride, tables, sxx, T);
     return hipGetLastError();
 }
 
@@ -2299,7 +1904,7 @@ void build_spec_tables(int fs, SpecTables &t)
         c1 = (float)std::sqrt((1.0 + (double)c1) / 2.0);
         l1 <<= 1;
     }
-    // energy gate of the IIR kernel: the taper covers exactly the first and the last 32 samples of a segment
+    // energy gate of iir2_ckpt_kernel's taps wave: the taper covers exactly the first and the last 32 samples of a segment
     t.gate_ok = 1;
     for (int i = kSpecSeg - kSpecHop; i < kSpecHop; ++i) t.gate_ok &= t.window[i] == 1.0f;
     float c = 0.0f;
@@ -2310,7 +1915,7 @@ void build_spec_tables(int fs, SpecTables &t)
     }
     t.win2_sum = c * 1.0001f;
     t.gate_scale = 2.0f * (float)kSpecSeg / t.U * 1.01f;
-    // the spectrogram kernel's short form of levels 0 and 1 (real input) is valid for exactly these twiddles
+    // SpecLane::psd's short form of levels 0 and 1 (real input) is valid for exactly these twiddles
     t.trivial_first_levels = t.tw_re[0] == 1.0f && t.tw_im[0] == 0.0f && t.tw_re[1] == 1.0f && t.tw_im[1] == 0.0f &&
                              t.tw_re[2] == 0.0f && t.tw_im[2] == -1.0f;
 }

@@ -35,7 +35,7 @@ struct SpecTables {
     float tw_re[255], tw_im[255];   // level l starts at (1<<l) - 1
     float mp_keep_min;              // smallest float s with (float)(10 log10(s / 1e-12)) > 70 (filled on the device)
     int trivial_first_levels;       // 1 when the twiddles of FFT levels 0 and 1 are exactly (1,0), (1,0), (0,-1) (they are)
-    // energy gate (iir2_split_kernel -> spectrogram_kernel<SPEC_FLAGS>): squared taper of the first / last 32 samples of
+    // energy gate (iir2_ckpt_kernel's taps wave: which segments go on want_mp): squared taper of the first / last 32 samples of
     // a segment, sum of the squared window, 2 N / U with 1 % margin, 1 when the window is exactly 1 in between
     float win2_in[kSpecSeg - kSpecHop], win2_out[kSpecSeg - kSpecHop];
     float win2_sum, gate_scale;
@@ -53,22 +53,16 @@ constexpr float kDivFastLo = 8.673617379884035e-19f, kDivFastHi = 1.152921504606
 struct IirCoef { float b[9], a[9]; };
 struct IirCoefD { double b[9], a[9]; };
 
-// y[c][i] for n_clips clips of n samples (row stride `stride` floats), direct form II from
-// zero state per clip.  Two filters are run in one pass over x when y2 != nullptr.
-// With y2 and means1 / means2 != nullptr the lanes also keep the spectrogram's per-segment sequential sums of
-// their own outputs (classifier.cpp:329-333: 256 samples from 224 t, added in order) and store the segment
-// means means[c][t], so the spectrogram kernel need not walk the samples serially again.
-// ystride: row stride of y1 / y2 (0 = the input's); gate_tables_ok: the host's SpecTables::gate_ok (when false, or when the
-// launch falls back to a kernel that does not compute the gate, gate2 is filled with "maybe").
-hipError_t launch_iir_f32(const float *x, long n_clips, int n, long stride, const IirCoef &c1, float *y1,
-                          const IirCoef &c2, float *y2, hipStream_t stream, float *means1 = nullptr, float *means2 = nullptr,
-                          const SpecTables *tables = nullptr, int *gate2 = nullptr, long ystride = 0, bool gate_tables_ok = true);
+// y[c][i] for n_clips clips of n samples (row stride `stride` elements, of x and of y), direct form II from
+// zero state per clip.
+hipError_t launch_iir_f32(const float *x, long n_clips, int n, long stride, const IirCoef &c, float *y,
+                          hipStream_t stream);
 hipError_t launch_iir_f64(const double *x, long n_clips, int n, long stride, const IirCoefD &c, double *y,
                           hipStream_t stream);
-// float rows, recurrence in double, one rounding on store (per-frame prefilter of BASELINE config 3)
 // both band-pass filters of the float64 classifier over one read of x: one wavefront per filter and 64 clips (rows of y1 / y2: ystride doubles)
 hipError_t launch_iir2_f64(const double *x, long n_clips, int n, long stride, long ystride, const IirCoefD &c1, double *y1,
                            const IirCoefD &c2, double *y2, hipStream_t stream);
+// float rows, recurrence in double, one rounding on store (per-frame prefilter of BASELINE config 3)
 hipError_t launch_iir_f64_on_f32(const float *x, long n_clips, int n, long stride, const IirCoefD &c, float *y,
                                  hipStream_t stream);
 
@@ -98,32 +92,23 @@ hipError_t launch_spec_from_ckpt(const void *x, long n_clips, int n, long stride
                                  const int *wantlist, const int *hits, const SpecTables *tables, float *out, bool flags, hipStream_t stream,
                                  const int *need = nullptr, unsigned *minmax = nullptr, int in_kind = 0, const ClipSpan *spans = nullptr);
 
-// sxx[c][129][T] (T = (n-256)/224+1) of clip rows y[c][0..n)
 struct ClassifyTrace {           // per clip, for parity tests
     int n_midpoints;
     float midpoints[kMaxMidpoints];
     float sums[kMaxMidpoints][3];
 };
 
-// means (optional): segment means [c][T] already computed by launch_iir_f32.  hits (optional, device): work list
-// (hits[0] = count, then clip numbers) of the clips whose map is wanted; the maps of the other clips are not written.
-// frame_major: sxx[c][T][129] instead of the reference's [c][129][T] -- the layout launch_classify_midpoints / _bands read.
+// sxx[c][129][T] (T = (n-256)/224+1, the reference's layout) of clip rows y[c][0..n) in HBM: the spectrogram entry point.  Always the
+// IEEE division by U (SpecTables::div_fast is not consulted: the tables of any fs come here)
 hipError_t launch_spectrogram_f32(const float *y, long n_clips, int n, long stride, const SpecTables *tables,
-                                  float *sxx, hipStream_t stream, const float *means = nullptr, const int *hits = nullptr,
-                                  bool frame_major = false);
-
+                                  float *sxx, hipStream_t stream);
 
 // float64 twin (donut-classifier/classifier.c:448-592): sxx[c][129][T] in double, direct DFT per frame (tolerance parity: FFTW
 // is unvendored)
 hipError_t launch_spectrogram_f64(const double *y, long n_clips, int n, long stride, int fs, double *sxx, hipStream_t stream);
 
-// The 1000-3000 Hz spectrogram reduced to what find_midpoints reads from it (classifier.cpp:457-518): loud[c][T] = 1 for
-// the time bins with a cell above 70 dB.  The map itself is not written.
-hipError_t launch_spectrogram_flags(const float *y, long n_clips, int n, long stride, const SpecTables *tables, int *loud,
-                                    hipStream_t stream, const float *means = nullptr, const int *gate = nullptr);
-
 // classify() after the spectrograms (classifier.cpp:35-135), two kernels: midpoints from the loud time bins (records in
-// `trace`, label 0 when there are none), then the band sums + rule from the frame_major 3000-7500 Hz map for the clips that
+// `trace`, label 0 when there are none), then the band sums + rule from the [time][bin] 3000-7500 Hz map for the clips that
 // have midpoints (sxx_bp is overwritten with its dB map when it does not fit LDS).  `trace` is required (it carries the
 // midpoints); `hits` (1 + n_clips ints) is the work list between the two: hits[0] = clips with midpoints, then their numbers.
 // full_records = false: only what the band kernel reads (count + midpoints) is written, not the zero-filled remainder of the
