@@ -12,9 +12,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dsp_amd.h"
@@ -98,29 +100,26 @@ struct dsp_mfcc_plan {
     int blocks_per_cu = 0;   // 0 = default (= resident_blocks)
     int chunk = 0;           // 0 = default
     dsp::LaneTables512 host;
-    dsp::LaneTables512 *d_tables = nullptr;
-    dsp::RowTables512 *d_row_tables = nullptr;
-    dsp::GenTables1024 *d_gen_tables = nullptr;   // n_fft = 1024
-    dsp::GenTables2048 *d_tables2048 = nullptr;   // n_fft = 2048
-    dsp::PairExtra512 *d_pair = nullptr;          // n_fft = 512: extra constants of the two-frames-per-wave kernel (DSP_KERNEL_PAIR)
+    dsp::DeviceBuf<dsp::LaneTables512> d_tables;
+    dsp::DeviceBuf<dsp::RowTables512> d_row_tables;
+    dsp::DeviceBuf<dsp::GenTables1024> d_gen_tables;   // n_fft = 1024
+    dsp::DeviceBuf<dsp::GenTables2048> d_tables2048;   // n_fft = 2048
+    dsp::DeviceBuf<dsp::PairExtra512> d_pair;          // n_fft = 512: extra constants of the two-frames-per-wave kernel (DSP_KERNEL_PAIR)
     int resident_blocks_pair = 3;
     int resident_blocks_2048 = 2, resident_blocks_2048_pool = 2;
     int resident_blocks_gen = 3;
     int gen_slots = 0;                            // mel chunk slots per lane the 1024-point tables use (<= 3: wave kernel)
     int resident_blocks_gen_wave = 2;
-    dsp::PrefilterScan *d_scan = nullptr;         // prefilter fused into the 1024-point wave kernel (full frames): its tables
+    dsp::DeviceBuf<dsp::PrefilterScan> d_scan;    // prefilter fused into the 1024-point wave kernel (full frames): its tables
     int scan_steps[4] = {6, 6, 6, 6};             // host copy of PrefilterScan::c_steps (picks the kernel instantiation)
     int resident_blocks_gen_pre = 2;
-    float *d_filtered = nullptr;                  // per-frame prefilter output (sub-batch)
-    size_t filtered_cap = 0;
-    float *d_frame_max = nullptr, *d_clip_floor = nullptr;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
-    size_t frame_max_cap = 0, clip_floor_cap = 0;
+    dsp::DeviceBuf<float> d_filtered;             // per-frame prefilter output (sub-batch)
+    dsp::DeviceBuf<float> d_frame_max, d_clip_floor;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
     int kernel = DSP_KERNEL_WAVE;
     bool aub = false;                             // n_fft = 2048 with aubio's semantics (magnitude spectrum, log10 floor or stream framing)
     int resident_blocks_row = 3;
     // staging for the host-pointer entry points
-    float *d_in = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
+    dsp::DeviceBuf<float> d_in, d_out;
     // Guards the plan's workspaces (d_filtered, d_frame_max / d_clip_floor, d_in / d_out) while a call reserves them and
     // enqueues the kernels that use them.  The kernels themselves run after the lock is released: a plan whose path uses
     // a workspace (prefilter, DSP_LOG_GLOBAL_REF1 over clips, the *_host entry points) serves ONE stream at a time;
@@ -285,48 +284,41 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     *out = nullptr;
     std::string why;
     if (!valid_cfg(*cfg, why)) return fail(DSP_EINVAL, why);
-    auto *p = new dsp_mfcc_plan;
-    p->cfg = *cfg;
-    dsp::GenTables1024 *gen = nullptr;
-    dsp::GenTables2048 *g2k = nullptr;
+    auto host_side = std::make_unique<dsp_mfcc_plan>();
+    host_side->cfg = *cfg;
+    std::unique_ptr<dsp::GenTables1024> gen;
+    std::unique_ptr<dsp::GenTables2048> g2k;
     if (cfg->n_fft == 2048) {
-        g2k = new dsp::GenTables2048;
-        if (!dsp::build_gen_tables_2048(*cfg, *g2k, why)) { delete g2k; delete p; return fail(DSP_EINVAL, why); }
+        g2k = std::make_unique<dsp::GenTables2048>();
+        if (!dsp::build_gen_tables_2048(*cfg, *g2k, why)) return fail(DSP_EINVAL, why);
     } else if (cfg->n_fft == 1024) {
-        gen = new dsp::GenTables1024;
-        if (!dsp::build_gen_tables_1024(*cfg, *gen, why)) { delete gen; delete p; return fail(DSP_EINVAL, why); }
-    } else if (!dsp::build_lane_tables_512(*cfg, p->host, why)) { delete p; return fail(DSP_EINVAL, why); }
+        gen = std::make_unique<dsp::GenTables1024>();
+        if (!dsp::build_gen_tables_1024(*cfg, *gen, why)) return fail(DSP_EINVAL, why);
+    } else if (!dsp::build_lane_tables_512(*cfg, host_side->host, why)) return fail(DSP_EINVAL, why);
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { delete gen; delete g2k; delete p; return fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback"); }
-    if (device < 0 || device >= n) { delete gen; delete g2k; delete p; return fail(DSP_EINVAL, "device index out of range"); }
-    p->device = device;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
+    if (device < 0 || device >= n) return fail(DSP_EINVAL, "device index out of range");
     dsp::DeviceScope dsp_device_scope_(device);      // the caller's current device is put back on return
+    // the plan gets device buffers from here on: its owner is declared after the scope, so that every exit below lets them go
+    // while the plan's device is current
+    std::unique_ptr<dsp_mfcc_plan> p = std::move(host_side);
+    p->device = device;
     hipError_t e = dsp_device_scope_.err;
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tables, sizeof(dsp::LaneTables512));
-    if (e == hipSuccess) e = hipMemcpy(p->d_tables, &p->host, sizeof(dsp::LaneTables512), hipMemcpyHostToDevice);
-    if (e == hipSuccess && gen) {
-        e = hipMalloc(&p->d_gen_tables, sizeof(dsp::GenTables1024));
-        if (e == hipSuccess) e = hipMemcpy(p->d_gen_tables, gen, sizeof(*gen), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && g2k) {
-        e = hipMalloc(&p->d_tables2048, sizeof(dsp::GenTables2048));
-        if (e == hipSuccess) e = hipMemcpy(p->d_tables2048, g2k, sizeof(*g2k), hipMemcpyHostToDevice);
-    }
-    delete g2k;
+    if (e == hipSuccess) e = dsp::upload(p->d_tables, p->host);
+    if (e == hipSuccess && gen) e = dsp::upload(p->d_gen_tables, *gen);
+    if (e == hipSuccess && g2k) e = dsp::upload(p->d_tables2048, *g2k);
     if (gen) p->gen_slots = gen->n_chunk_slots;
-    delete gen;
     if (e == hipSuccess && cfg->n_fft == 1024 && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->gen_slots <= 3) {
         // BASELINE config 3 in ONE pass: the per-frame Butterworth as a scan inside the MFCC kernel (tables.hpp PrefilterScan)
         double b[9], a[9];
         dsp_butter_bandpass(cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
                             cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, b, a);
         dsp::PrefilterScan sc;
-        if (!dsp::build_prefilter_scan(b, a, sc, why)) { dsp_mfcc_plan_destroy(p); return fail(DSP_EINVAL, why); }
+        if (!dsp::build_prefilter_scan(b, a, sc, why)) return fail(DSP_EINVAL, why);
         if (sc.c_ok && (!DSP_PRE_ROWSCAN || sc.c_row_ok)) {      // the kernel runs the cascade form (its scan in row form); coefficients without it (none of the two literal sets) take the two-pass path
-            e = hipMalloc(&p->d_scan, sizeof(sc));
-            if (e == hipSuccess) e = hipMemcpy(p->d_scan, &sc, sizeof(sc), hipMemcpyHostToDevice);
+            e = dsp::upload(p->d_scan, sc);
             for (int k = 0; k < 4; ++k) p->scan_steps[k] = sc.c_steps[k];
         }
     }
@@ -334,25 +326,17 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     // measured dead ends kept buildable (python -m dsp_amd.build with DSP_AMD_EXPERIMENTS=1): the row-per-frame kernel and
     // the two-frames-per-wave kernel; the default library does not carry them
     if (e == hipSuccess && cfg->n_fft == 512) {
-        e = hipMalloc(&p->d_row_tables, sizeof(dsp::RowTables512));
-        if (e == hipSuccess) {
-            auto *rt = new dsp::RowTables512;
-            dsp::build_row_tables_512(*cfg, *rt);
-            e = hipMemcpy(p->d_row_tables, rt, sizeof(*rt), hipMemcpyHostToDevice);
-            delete rt;
-        }
+        auto rt = std::make_unique<dsp::RowTables512>();
+        dsp::build_row_tables_512(*cfg, *rt);
+        e = dsp::upload(p->d_row_tables, *rt);
     }
     if (e == hipSuccess && cfg->n_fft == 512) {
         dsp::PairExtra512 px;
         dsp::build_pair_extra_512(px);
-        e = hipMalloc(&p->d_pair, sizeof(px));
-        if (e == hipSuccess) e = hipMemcpy(p->d_pair, &px, sizeof(px), hipMemcpyHostToDevice);
+        e = dsp::upload(p->d_pair, px);
     }
 #endif
-    if (e != hipSuccess) {
-        dsp_mfcc_plan_destroy(p);          // frees every member that was allocated
-        return fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
     p->n_cu = prop.multiProcessorCount;
     p->aub = cfg->n_fft == 2048 && (cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM);
     if (cfg->n_fft == 2048) {
@@ -376,10 +360,10 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     if (const char *k = std::getenv("DSP_AMD_KERNEL")) {
         // an A/B switch, not a requirement: a value this build (or this plan's n_fft) has no kernel for is reported and ignored --
         // an environment left over from an experiments build must not make every plan_create fail
-        if (dsp_mfcc_plan_set_kernel(p, std::atoi(k)) != DSP_OK)
+        if (dsp_mfcc_plan_set_kernel(p.get(), std::atoi(k)) != DSP_OK)
             std::fprintf(stderr, "libdsp_amd: DSP_AMD_KERNEL=%s ignored (%s); using the default kernel\n", k, dsp_last_error());
     }
-    *out = p;
+    *out = p.release();
     return DSP_OK;
 }
 
@@ -387,17 +371,6 @@ void dsp_mfcc_plan_destroy(dsp_mfcc_plan *p)
 {
     if (!p) return;
     dsp::DeviceScope dsp_device_scope_(p->device);
-    if (p->d_tables) hipFree(p->d_tables);
-    if (p->d_row_tables) hipFree(p->d_row_tables);
-    if (p->d_gen_tables) hipFree(p->d_gen_tables);
-    if (p->d_tables2048) hipFree(p->d_tables2048);
-    if (p->d_pair) hipFree(p->d_pair);
-    if (p->d_scan) hipFree(p->d_scan);
-    if (p->d_filtered) hipFree(p->d_filtered);
-    if (p->d_frame_max) hipFree(p->d_frame_max);
-    if (p->d_clip_floor) hipFree(p->d_clip_floor);
-    if (p->d_in) hipFree(p->d_in);
-    if (p->d_out) hipFree(p->d_out);
     p->spans.release();
     delete p;
 }
@@ -493,8 +466,8 @@ template <class Launch> static int two_pass_floor(dsp_mfcc_plan *p, dsp::Mfcc512
 {
     const long n_clips = a.spans ? a.n_clips : a.n_frames / a.frames_per_clip;
     std::lock_guard<std::recursive_mutex> lock(p->mu);
-    DSP_HIP(dsp::reserve(p->d_frame_max, p->frame_max_cap, (size_t)a.n_frames * sizeof(float)));
-    DSP_HIP(dsp::reserve(p->d_clip_floor, p->clip_floor_cap, (size_t)n_clips * sizeof(float)));
+    DSP_HIP(p->d_frame_max.reserve((size_t)a.n_frames * sizeof(float)));
+    DSP_HIP(p->d_clip_floor.reserve((size_t)n_clips * sizeof(float)));
     a.frame_max = p->d_frame_max;
     DSP_HIP(launch(a));
     if (a.spans) DSP_HIP(dsp::launch_clip_floor_ragged(p->d_frame_max, a.spans, n_clips, a.top_db, p->d_clip_floor, st));
@@ -596,7 +569,7 @@ int dsp_mfcc_frames_device(dsp_mfcc_plan *p, const float *d_frames, long n_frame
     DSP_ON_DEVICE(p->device);
     const int fl = p->cfg.frame_length;
     const long sub = std::min<long>(n_frames, 1L << 20);
-    DSP_HIP(dsp::reserve(p->d_filtered, p->filtered_cap, (size_t)sub * fl * sizeof(float)));
+    DSP_HIP(p->d_filtered.reserve((size_t)sub * fl * sizeof(float)));
     dsp::IirCoefD c;
     dsp_butter_bandpass(p->cfg.prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
                         p->cfg.prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, c.b, c.a);
@@ -708,8 +681,8 @@ int dsp_mfcc_frames_host(dsp_mfcc_plan *p, const float *frames, long n_frames, f
     DSP_ON_DEVICE(p->device);
     const size_t in_b = (size_t)n_frames * p->cfg.frame_length * sizeof(float);
     const size_t out_b = (size_t)n_frames * p->cfg.n_mfcc * sizeof(float);
-    DSP_HIP(dsp::reserve(p->d_in, p->in_cap, in_b));
-    DSP_HIP(dsp::reserve(p->d_out, p->out_cap, out_b));
+    DSP_HIP(p->d_in.reserve(in_b));
+    DSP_HIP(p->d_out.reserve(out_b));
     int rc;
     DSP_HIP(hipMemcpyAsync(p->d_in, frames, in_b, hipMemcpyHostToDevice, nullptr));
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return fail(DSP_EINVAL, "prefiltered plans take device buffers (dsp_mfcc_frames_device)");
@@ -733,8 +706,8 @@ int dsp_mfcc_clips_host(dsp_mfcc_plan *p, const float *signal, long n_clips, int
     const long dstride = samples_per_clip + (samples_per_clip & 1);
     const size_t in_b = (size_t)n_clips * dstride * sizeof(float);
     const size_t out_b = (size_t)n_clips * t * p->cfg.n_mfcc * sizeof(float);
-    DSP_HIP(dsp::reserve(p->d_in, p->in_cap, in_b));
-    DSP_HIP(dsp::reserve(p->d_out, p->out_cap, out_b));
+    DSP_HIP(p->d_in.reserve(in_b));
+    DSP_HIP(p->d_out.reserve(out_b));
     int rc;
     DSP_HIP(hipMemcpy2DAsync(p->d_in, dstride * sizeof(float), signal, clip_stride * sizeof(float),
                              (size_t)samples_per_clip * sizeof(float), (size_t)n_clips, hipMemcpyHostToDevice, nullptr));
@@ -774,7 +747,7 @@ __attribute__((visibility("default"))) int dsp_debug_bd_stamps(unsigned long lon
 struct dsp_svm {
     int device = 0;
     dsp::SvmModelDev m{};
-    float *d_blob = nullptr;
+    dsp::DeviceBuf<float> d_blob;
     dsp::SpanRing scan;      // dsp_svm_scan_device: the per-recording arrays on their way to the GPU (capi_util.hpp)
 };
 
@@ -807,18 +780,18 @@ int dsp_svm_create(int device, int n_features, int n_sv, const float *offset, co
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
     if (device < 0 || device >= n) return fail(DSP_EINVAL, "device index out of range");
     DSP_ON_DEVICE(device);
-    auto *s = new dsp_svm;
+    auto s = std::make_unique<dsp_svm>();
     s->device = device;
     const size_t nf = n_features, ns = n_sv, total = 2 * nf + ns * nf + ns;
-    if (hipMalloc(&s->d_blob, total * sizeof(float)) != hipSuccess) { delete s; return fail(DSP_ENOMEM, "hipMalloc"); }
+    if (s->d_blob.alloc(total * sizeof(float)) != hipSuccess) return fail(DSP_ENOMEM, "hipMalloc");
     float *p = s->d_blob;
     hipError_t e = hipMemcpy(p, offset, nf * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p + nf, scale, nf * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p + 2 * nf, support_vectors, ns * nf * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p + 2 * nf + ns * nf, coefficients, ns * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(s->d_blob); delete s; return fail(DSP_EHIP, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(DSP_EHIP, hipGetErrorString(e));
     s->m = {n_features, n_sv, gamma, rho, prob_a, prob_b, p, p + nf, p + 2 * nf, p + 2 * nf + ns * nf};
-    *out = s;
+    *out = s.release();
     return DSP_OK;
 }
 
@@ -826,7 +799,6 @@ void dsp_svm_destroy(dsp_svm *s)
 {
     if (!s) return;
     dsp::DeviceScope dsp_device_scope_(s->device);
-    if (s->d_blob) hipFree(s->d_blob);
     s->scan.release();
     delete s;
 }
@@ -1101,8 +1073,7 @@ struct dsp_scrubjay_scanner {
     dsp_svm *svm = nullptr;
     dsp_scan_config cfg{};
     int head_rows = 0;
-    float *d_mfcc = nullptr, *d_head = nullptr;
-    size_t mfcc_cap = 0, head_cap = 0;
+    dsp::DeviceBuf<float> d_mfcc, d_head;
     std::vector<long> fo, wo, ho, starts, lengths;
     std::mutex mu;
 };
@@ -1130,7 +1101,7 @@ static int scrubjay_scanner_run(dsp_scrubjay_scanner *s, const void *d_signal, i
             return fail(DSP_EINVAL, "recording " + std::to_string(r) + " is shorter than one frame: mfcc_stats has no rows to pool (scrubjay_infer.c:55-59)");
     if (!d_signal) return fail(DSP_EINVAL, "d_signal is NULL");
     DSP_ON_DEVICE(p->device);
-    if (dsp::reserve(s->d_mfcc, s->mfcc_cap, (size_t)rows * nc * sizeof(float)) != hipSuccess) return fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
+    if (s->d_mfcc.reserve((size_t)rows * nc * sizeof(float)) != hipSuccess) return fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
     int rc = mfcc_clips_ragged(p, d_signal, in_kind, n, offsets, INT_MAX, s->d_mfcc, stream);
     if (rc < 0) return rc;
     if (s->head_rows > 0) {
@@ -1147,7 +1118,7 @@ static int scrubjay_scanner_run(dsp_scrubjay_scanner *s, const void *d_signal, i
             const long hc = std::min<long>(s->head_rows, std::min<long>(s->fo[(size_t)r + 1] - s->fo[(size_t)r], s->cfg.window_frames));
             s->ho[(size_t)r + 1] = s->ho[(size_t)r] + (s->wo[(size_t)r + 1] - s->wo[(size_t)r]) * hc;
         }
-        if (dsp::reserve(s->d_head, s->head_cap, (size_t)s->ho[(size_t)n] * nc * sizeof(float)) != hipSuccess)
+        if (s->d_head.reserve((size_t)s->ho[(size_t)n] * nc * sizeof(float)) != hipSuccess)
             return fail(DSP_ENOMEM, "hipMalloc (scanner head-row workspace)");
         if ((rc = mfcc_clips_ragged(p, d_signal, in_kind, n_win, s->starts.data(), INT_MAX, s->d_head, stream, s->lengths.data())) < 0) return rc;
     }
@@ -1193,8 +1164,6 @@ void dsp_scrubjay_scanner_destroy(dsp_scrubjay_scanner *s)
 {
     if (!s) return;
     dsp::DeviceScope dsp_device_scope_(s->plan->device);
-    if (s->d_mfcc) hipFree(s->d_mfcc);
-    if (s->d_head) hipFree(s->d_head);
     delete s;
 }
 

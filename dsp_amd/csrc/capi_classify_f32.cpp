@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <new>
 #include <thread>
+#include <utility>
 
 #include "classify_front.hpp"
 
@@ -28,26 +29,40 @@ dsp::IirCoef coef_f32(double lo, double hi)
     return c;
 }
 
-struct ClassifyCtx : front::Work {
+// counts the floats of its range on which the recompute kernel's three-instruction PSD division differs from the real division, for
+// this table's U, on the current device (~1e9 values: a fraction of a millisecond)
+hipError_t spec_div_mismatches(const dsp::SpecTables *d_tab, unsigned long long &bad)
+{
+    dsp::DeviceBuf<unsigned long long> d_bad;
+    hipError_t e = d_bad.alloc(sizeof(bad));
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(bad), nullptr);
+    if (e == hipSuccess) e = dsp::launch_spec_div_verify(d_tab, d_bad, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
+    return e;
+}
+
+// the workspace for one sub-batch: allocated together, let go together (ClassifyCtx::reserve)
+struct ClassifyBufs {
+    dsp::DeviceBuf<void> x;                                // staged input (host entry points); none until a host entry asks
+    dsp::DeviceBuf<float> d_sbp;                           // 3000-7500 Hz PSD maps [clip][T][129]
+    dsp::DeviceBuf<float> d_ck_bp, d_ck_mp;                // [clip][T][kCkPerSegBp / Mp][8]: delay line of each filter at every segment start (3000-7500 Hz: and middle)
+    dsp::DeviceBuf<float> d_mean_mp;                       // [clip][T]: segment means of the 1000-3000 Hz output
+    dsp::DeviceBuf<int> labels, d_hits;                    // d_hits: work list of clips with midpoints
+    dsp::DeviceBuf<int> d_loud;                            // [clip][T]: time bins of the 1000-3000 Hz map above 70 dB; after the midpoints kernel: rows of the 3000-7500 Hz map the band sums read
+    dsp::DeviceBuf<unsigned> d_minmax;                     // [clip][2]: float bits of the smallest / largest positive cell of the 3000-7500 Hz map
+    dsp::DeviceBuf<int> d_simd;                            // iir2_ckpt_kernel's per-CU SIMD load table (launch_iir2_ckpt)
+    dsp::DeviceBuf<int> d_gate;                            // work list of the segments whose energy does not rule a loud cell out (IIR kernel)
+    dsp::DeviceBuf<dsp::ClassifyTrace> trace;
+    long cap_clips = 0;                                    // per-clip arrays (labels, hits, trace, minmax)
+    long cap_segs = 0;                                     // per-segment arrays: clips x segments per clip of the largest pass so far
+};
+
+struct ClassifyCtx : front::Work, ClassifyBufs {
     using Config = dsp_classify_config;
     using Trace = dsp_classify_trace;
     static constexpr int kFloatBytes = 4;
 
-    dsp::SpecTables *d_tab = nullptr;
-    // workspace for one sub-batch
-    void *x = nullptr;                                     // staged input (host entry points)
-    float *d_sbp = nullptr;                                // 3000-7500 Hz PSD maps [clip][T][129]
-    float *d_ck_bp = nullptr, *d_ck_mp = nullptr;          // [clip][T][kCkPerSegBp / Mp][8]: delay line of each filter at every segment start (3000-7500 Hz: and middle)
-    float *d_mean_mp = nullptr;                            // [clip][T]: segment means of the 1000-3000 Hz output
-    int *labels = nullptr, *d_hits = nullptr;              // d_hits: work list of clips with midpoints
-    int *d_loud = nullptr;                                 // [clip][T]: time bins of the 1000-3000 Hz map above 70 dB; after the midpoints kernel: rows of the 3000-7500 Hz map the band sums read
-    unsigned *d_minmax = nullptr;                          // [clip][2]: float bits of the smallest / largest positive cell of the 3000-7500 Hz map
-    int *d_simd = nullptr;                                 // iir2_ckpt_kernel's per-CU SIMD load table (launch_iir2_ckpt)
-    int *d_gate = nullptr;                                 // work list of the segments whose energy does not rule a loud cell out (IIR kernel)
-    dsp::ClassifyTrace *trace = nullptr;
-    long cap_clips = 0;                                    // per-clip arrays (labels, hits, trace, minmax)
-    long cap_segs = 0;                                     // per-segment arrays: clips x segments per clip of the largest pass so far
-    size_t cap_x = 0;                                      // staging buffer of the host entry points, in bytes (0: none)
+    dsp::DeviceBuf<dsp::SpecTables> d_tab;                 // held = the workspace is initialised (init())
     float keep_min_db = 70.0f;                             // the midpoint threshold d_tab->mp_keep_min was computed for
 
     static Config default_config()
@@ -68,42 +83,29 @@ struct ClassifyCtx : front::Work {
     int init()
     {
         if (d_tab) return DSP_OK;
+        // built in a local and handed to d_tab after the last step that can fail: a failed init() leaves the workspace unopened
         dsp::SpecTables t;
         dsp::build_spec_tables(16000, t);
-        DSP_CAPI_HIP(hipMalloc(&d_tab, sizeof(t)));
-        DSP_CAPI_HIP(hipMemcpy(d_tab, &t, sizeof(t), hipMemcpyHostToDevice));
-        keep_min_db = 70.0f;
-        DSP_CAPI_HIP(dsp::launch_spec_threshold(d_tab, keep_min_db, nullptr));
-        {   // the recompute kernel's three-instruction PSD division is switched on only after it has been checked against the real
-            // division on every float of its range, for this table's U, on this device (~1e9 values: a fraction of a millisecond)
-            unsigned long long *d_bad = nullptr, bad = 1;
-            DSP_CAPI_HIP(hipMalloc(&d_bad, sizeof(bad)));
-            hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(bad), nullptr);
-            if (e == hipSuccess) e = dsp::launch_spec_div_verify(d_tab, d_bad, nullptr);
-            if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-            (void)hipFree(d_bad);
-            if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
-            const int on = bad == 0 && !std::getenv("DSP_AMD_SPEC_EXACT_DIV") ? 1 : 0;
-            DSP_CAPI_HIP(hipMemcpy(reinterpret_cast<char *>(d_tab) + offsetof(dsp::SpecTables, div_fast), &on, sizeof(on), hipMemcpyHostToDevice));
-        }
+        dsp::DeviceBuf<dsp::SpecTables> tab;
+        DSP_CAPI_HIP(dsp::upload(tab, t));
+        DSP_CAPI_HIP(dsp::launch_spec_threshold(tab, 70.0f, nullptr));
+        // the recompute kernel's three-instruction PSD division is switched on only after it has been checked against the real one
+        unsigned long long bad = 1;
+        const hipError_t e = spec_div_mismatches(tab, bad);
+        if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
+        const int on = bad == 0 && !std::getenv("DSP_AMD_SPEC_EXACT_DIV") ? 1 : 0;
+        DSP_CAPI_HIP(hipMemcpy(reinterpret_cast<char *>(tab.get()) + offsetof(dsp::SpecTables, div_fast), &on, sizeof(on), hipMemcpyHostToDevice));
         DSP_CAPI_HIP(hipStreamSynchronize(nullptr));
+        d_tab = std::move(tab);
+        keep_min_db = 70.0f;
         return DSP_OK;
     }
 
-    void free_workspace()
-    {
-        for (void *p : {x, (void *)d_sbp, (void *)d_ck_bp, (void *)d_ck_mp, (void *)d_loud, (void *)d_gate, (void *)d_simd, (void *)d_mean_mp,
-                        (void *)labels, (void *)d_hits, (void *)trace, (void *)d_minmax})
-            if (p) (void)hipFree(p);
-        x = nullptr; d_sbp = d_ck_bp = d_ck_mp = d_mean_mp = nullptr;
-        labels = d_hits = d_loud = d_gate = d_simd = nullptr; trace = nullptr; d_minmax = nullptr;
-        cap_clips = 0; cap_segs = 0; cap_x = 0;
-    }
+    void free_workspace() { static_cast<ClassifyBufs &>(*this) = ClassifyBufs{}; }
     void free_all()
     {
         free_workspace();
-        if (d_tab) (void)hipFree(d_tab);
-        d_tab = nullptr;
+        d_tab.reset();
     }
 
     // The per-segment arrays are [clip][T(n)] with the pass's own T, so what a pass needs of them is its PRODUCT clips x T: a ragged
@@ -112,24 +114,24 @@ struct ClassifyCtx : front::Work {
     int reserve(int, long clips, int n, size_t x_bytes)
     {
         const long T = std::max(1, front::columns(n));
-        if (clips <= cap_clips && clips * T <= cap_segs && x_bytes <= cap_x) return DSP_OK;
+        if (clips <= cap_clips && clips * T <= cap_segs && x_bytes <= x.bytes()) return DSP_OK;
         wait_idle();
         const long rows = std::max(clips, cap_clips), segs = std::max(clips * T, cap_segs);
-        const size_t xb = std::max(x_bytes, cap_x);
-        free_workspace();
-        if (xb > 0) DSP_CAPI_HIP(hipMalloc(&x, xb));
-        DSP_CAPI_HIP(hipMalloc(&d_sbp, (size_t)segs * dsp::kSpecBins * sizeof(float)));
-        DSP_CAPI_HIP(hipMalloc(&d_ck_bp, (size_t)segs * dsp::kCkPerSegBp * 8 * sizeof(float)));
-        DSP_CAPI_HIP(hipMalloc(&d_ck_mp, (size_t)segs * dsp::kCkPerSegMp * 8 * sizeof(float)));
-        DSP_CAPI_HIP(hipMalloc(&d_loud, (size_t)segs * sizeof(int)));
-        DSP_CAPI_HIP(hipMalloc(&d_minmax, (size_t)rows * 2 * sizeof(unsigned)));
-        DSP_CAPI_HIP(hipMalloc(&d_simd, sizeof(int) * dsp::kSimdLoadCus * dsp::kSimdLoadStride));
-        DSP_CAPI_HIP(hipMalloc(&d_gate, ((size_t)segs + 1) * sizeof(int)));      // work list of gated-in frames: count + frame numbers
-        DSP_CAPI_HIP(hipMalloc(&d_mean_mp, (size_t)segs * sizeof(float)));
-        DSP_CAPI_HIP(hipMalloc(&labels, (size_t)rows * sizeof(int)));
-        DSP_CAPI_HIP(hipMalloc(&d_hits, (size_t)(rows + 1) * sizeof(int)));
-        DSP_CAPI_HIP(hipMalloc(&trace, (size_t)rows * sizeof(dsp::ClassifyTrace)));
-        cap_clips = rows; cap_segs = segs; cap_x = xb;
+        const size_t xb = std::max(x_bytes, x.bytes());
+        free_workspace();      // (cap_clips and cap_segs stay 0 if an allocation below fails: the next call starts over)
+        if (xb > 0) DSP_CAPI_HIP(x.alloc(xb));
+        DSP_CAPI_HIP(d_sbp.alloc((size_t)segs * dsp::kSpecBins * sizeof(float)));
+        DSP_CAPI_HIP(d_ck_bp.alloc((size_t)segs * dsp::kCkPerSegBp * 8 * sizeof(float)));
+        DSP_CAPI_HIP(d_ck_mp.alloc((size_t)segs * dsp::kCkPerSegMp * 8 * sizeof(float)));
+        DSP_CAPI_HIP(d_loud.alloc((size_t)segs * sizeof(int)));
+        DSP_CAPI_HIP(d_minmax.alloc((size_t)rows * 2 * sizeof(unsigned)));
+        DSP_CAPI_HIP(d_simd.alloc(sizeof(int) * dsp::kSimdLoadCus * dsp::kSimdLoadStride));
+        DSP_CAPI_HIP(d_gate.alloc(((size_t)segs + 1) * sizeof(int)));      // work list of gated-in frames: count + frame numbers
+        DSP_CAPI_HIP(d_mean_mp.alloc((size_t)segs * sizeof(float)));
+        DSP_CAPI_HIP(labels.alloc((size_t)rows * sizeof(int)));
+        DSP_CAPI_HIP(d_hits.alloc((size_t)(rows + 1) * sizeof(int)));
+        DSP_CAPI_HIP(trace.alloc((size_t)rows * sizeof(dsp::ClassifyTrace)));
+        cap_clips = rows; cap_segs = segs;
         return DSP_OK;
     }
 
@@ -152,18 +154,18 @@ struct ClassifyCtx : front::Work {
         // midpoints first (1000-3000 Hz map, as flags, gated frames only); the 3000-7500 Hz spectrogram and its band sums only for
         // clips that have midpoints
         DSP_CAPI_HIP(dsp::launch_spec_from_ckpt(d_x, clips, n, stride, mp, d_ck_mp, d_mean_mp, d_gate, nullptr, d_tab,
-                                                reinterpret_cast<float *>(d_loud), true, st, nullptr, nullptr, in, spans));
+                                                reinterpret_cast<float *>(d_loud.get()), true, st, nullptr, nullptr, in, spans));
         // DSP_AMD_CLASSIFY_FULL_MAPS=1: every row of the listed clips' maps is stored and read (no need / minmax hand-over)
         static const bool full_maps = [] { const char *e = std::getenv("DSP_AMD_CLASSIFY_FULL_MAPS"); return e && std::atoi(e) != 0; }();
-        unsigned *mm = full_maps ? nullptr : d_minmax;
-        const int *need = full_maps ? nullptr : d_loud;
+        unsigned *mm = full_maps ? nullptr : d_minmax.get();
+        const int *need = full_maps ? nullptr : d_loud.get();
         DSP_CAPI_HIP(dsp::launch_classify_midpoints(d_loud, clips, n, 16000, labels, trace, d_hits, st, want_trace, mm, spans));
         DSP_CAPI_HIP(dsp::launch_spec_from_ckpt(d_x, clips, n, stride, bp, d_ck_bp, nullptr, nullptr, d_hits, d_tab, d_sbp, false, st, need, mm, in, spans));
         DSP_CAPI_HIP(dsp::launch_classify_bands(d_sbp, clips, n, 16000, labels, trace, d_hits, st, rule, need, mm, spans));
         return DSP_OK;
     }
 };
-ClassifyCtx (&g_cls_ctx)[front::kMaxDevices] = front::workspaces<ClassifyCtx>;
+ClassifyCtx *const g_cls_ctx = front::workspaces<ClassifyCtx>();
 
 }  // namespace
 
@@ -178,14 +180,10 @@ int dsp_classify_division_check(long long *mismatches)
     std::lock_guard<std::mutex> lock(g_cls.mu);
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
-    unsigned long long *d_bad = nullptr, bad = 0;
+    unsigned long long bad = 0;
     int on = 0;
-    DSP_CAPI_HIP(hipMalloc(&d_bad, sizeof(bad)));
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(bad), nullptr);
-    if (e == hipSuccess) e = dsp::launch_spec_div_verify(g_cls.d_tab, d_bad, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&on, reinterpret_cast<const char *>(g_cls.d_tab) + offsetof(dsp::SpecTables, div_fast), sizeof(on), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
+    hipError_t e = spec_div_mismatches(g_cls.d_tab, bad);
+    if (e == hipSuccess) e = hipMemcpy(&on, reinterpret_cast<const char *>(g_cls.d_tab.get()) + offsetof(dsp::SpecTables, div_fast), sizeof(on), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     if (mismatches) *mismatches = (long long)bad;
     return on ? 1 : 0;
@@ -203,16 +201,15 @@ int dsp_butter_bandpass_filter_f32(const float *data, long n_clips, int n, long 
     std::lock_guard<std::mutex> lock(g_cls.mu);
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
-    float *dx = nullptr, *dy = nullptr;
+    dsp::DeviceBuf<float> dx, dy;
     const size_t bytes = (size_t)n_clips * n * sizeof(float);
-    DSP_CAPI_HIP(hipMalloc(&dx, bytes));
-    if (hipMalloc(&dy, bytes) != hipSuccess) { (void)hipFree(dx); return dsp::capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    DSP_CAPI_HIP(dx.alloc(bytes));
+    if (dy.alloc(bytes) != hipSuccess) return dsp::capi_fail(DSP_ENOMEM, "hipMalloc");
     dsp::IirCoef c;
     for (int i = 0; i < 9; ++i) { c.b[i] = b[i]; c.a[i] = a[i]; }
     hipError_t e = hipMemcpy2D(dx, (size_t)n * sizeof(float), data, (size_t)stride * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_iir_f32(dx, n_clips, n, n, c, dy, nullptr);
     if (e == hipSuccess) e = hipMemcpy2D(output, (size_t)stride * sizeof(float), dy, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n_clips, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(dy);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     return DSP_OK;
 }
@@ -229,16 +226,15 @@ int dsp_butter_bandpass_filter_f64(const double *data, long n_clips, int n, long
     std::lock_guard<std::mutex> lock(g_cls.mu);
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
-    double *dx = nullptr, *dy = nullptr;
+    dsp::DeviceBuf<double> dx, dy;
     const size_t bytes = (size_t)n_clips * n * sizeof(double);
-    DSP_CAPI_HIP(hipMalloc(&dx, bytes));
-    if (hipMalloc(&dy, bytes) != hipSuccess) { (void)hipFree(dx); return dsp::capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    DSP_CAPI_HIP(dx.alloc(bytes));
+    if (dy.alloc(bytes) != hipSuccess) return dsp::capi_fail(DSP_ENOMEM, "hipMalloc");
     dsp::IirCoefD c;
     for (int i = 0; i < 9; ++i) { c.b[i] = b[i]; c.a[i] = a[i]; }
     hipError_t e = hipMemcpy2D(dx, (size_t)n * sizeof(double), data, (size_t)stride * sizeof(double), (size_t)n * sizeof(double), n_clips, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_iir_f64(dx, n_clips, n, n, c, dy, nullptr);
     if (e == hipSuccess) e = hipMemcpy2D(output, (size_t)stride * sizeof(double), dy, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n_clips, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(dy);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     return DSP_OK;
 }
@@ -259,23 +255,20 @@ int dsp_compute_spectrogram_f32(const float *signal, int n, int fs, float *frequ
     std::lock_guard<std::mutex> lock(g_cls.mu);
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
-    float *dx = nullptr, *ds = nullptr;
-    dsp::SpecTables *dt = nullptr;               // fs enters only through the PSD scale U = fs * sum w^2 (classifier.cpp:296-301)
-    DSP_CAPI_HIP(hipMalloc(&dx, (size_t)n * sizeof(float)));
+    dsp::DeviceBuf<float> dx, ds;
+    dsp::DeviceBuf<dsp::SpecTables> dt;          // fs enters only through the PSD scale U = fs * sum w^2 (classifier.cpp:296-301)
+    DSP_CAPI_HIP(dx.alloc((size_t)n * sizeof(float)));
     const size_t sb = (size_t)dsp::kSpecBins * T * sizeof(float);
-    if (hipMalloc(&ds, sb) != hipSuccess) { (void)hipFree(dx); return dsp::capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    if (ds.alloc(sb) != hipSuccess) return dsp::capi_fail(DSP_ENOMEM, "hipMalloc");
     hipError_t e = hipSuccess;
     if (fs != 16000) {
         dsp::SpecTables t;
         dsp::build_spec_tables(fs, t);
-        e = hipMalloc(&dt, sizeof(t));
-        if (e == hipSuccess) e = hipMemcpy(dt, &t, sizeof(t), hipMemcpyHostToDevice);
+        e = dsp::upload(dt, t);
     }
     if (e == hipSuccess) e = hipMemcpy(dx, signal, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dsp::launch_spectrogram_f32(dx, 1, n, n, dt ? dt : g_cls.d_tab, ds, nullptr);
+    if (e == hipSuccess) e = dsp::launch_spectrogram_f32(dx, 1, n, n, dt ? dt.get() : g_cls.d_tab.get(), ds, nullptr);
     if (e == hipSuccess) e = hipMemcpy(sxx, ds, sb, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(ds);
-    if (dt) (void)hipFree(dt);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     return T;
 }
@@ -296,14 +289,13 @@ int dsp_compute_spectrogram_f64(const double *signal, int n, int fs, double *fre
     std::lock_guard<std::mutex> lock(g_cls.mu);
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
-    double *dx = nullptr, *ds = nullptr;
-    DSP_CAPI_HIP(hipMalloc(&dx, (size_t)n * sizeof(double)));
+    dsp::DeviceBuf<double> dx, ds;
+    DSP_CAPI_HIP(dx.alloc((size_t)n * sizeof(double)));
     const size_t sb = (size_t)dsp::kSpecBins * T * sizeof(double);
-    if (hipMalloc(&ds, sb) != hipSuccess) { (void)hipFree(dx); return dsp::capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    if (ds.alloc(sb) != hipSuccess) return dsp::capi_fail(DSP_ENOMEM, "hipMalloc");
     hipError_t e = hipMemcpy(dx, signal, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_spectrogram_f64(dx, 1, n, n, fs, ds, nullptr);
     if (e == hipSuccess) e = hipMemcpy(sxx, ds, sb, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(ds);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     return T;
 }
@@ -320,14 +312,13 @@ int dsp_sum_intense_f32(float lower, float upper, float half_range, const float 
     DSP_ON_DEVICE(device);
     if ((rc = front::open(g_cls, device)) < 0) return rc;
     const size_t nf = freq_bins, nt = time_bins, total = nf + nt + nf * nt + 1;
-    float *d = nullptr;
-    DSP_CAPI_HIP(hipMalloc(&d, total * sizeof(float)));
+    dsp::DeviceBuf<float> d;
+    DSP_CAPI_HIP(d.alloc(total * sizeof(float)));
     hipError_t e = hipMemcpy(d, frequencies, nf * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + nf, times, nt * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + nf + nt, db, nf * nt * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_sum_intense(lower, upper, half_range, d, freq_bins, d + nf, time_bins, d + nf + nt, midpoint, d + nf + nt + nf * nt, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d + nf + nt + nf * nt, sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return dsp::capi_fail(DSP_EHIP, hipGetErrorString(e));
     return DSP_OK;
 }

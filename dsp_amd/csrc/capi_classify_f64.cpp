@@ -16,6 +16,7 @@
 
 #include <cstring>
 #include <memory>
+#include <utility>
 
 #include "classify_front.hpp"
 
@@ -38,28 +39,33 @@ void coefficients(dsp::IirCoefD &c_bp, dsp::IirCoefD &c_mp)
     for (int i = 0; i < 9; ++i) { c_mp.b[i] = b[i]; c_mp.a[i] = a[i]; }
 }
 
-struct Scratch : front::Work {
+// per pass: `cap_clips` clips, `cap_cells` = clips x columns of the largest pass; allocated together, let go together (Scratch::reserve)
+struct PassBufs {
+    dsp::DeviceBuf<double> ck_bp, ck_mp, s_bp, mids;
+    dsp::DeviceBuf<int> labels, loud, want, n_mids, hits;
+    dsp::DeviceBuf<dsp::ClassifyTraceD> trace;
+    dsp::DeviceBuf<unsigned long long> minmax;  // [clip][2]: smallest / largest positive cell of a listed clip's map (double bits)
+    long cap_clips = 0;
+    size_t cap_cells = 0;
+};
+
+// the yardstick pipelines' filtered signals (doubles per row) and second map; allocated together, let go together
+struct YardstickBufs {
+    dsp::DeviceBuf<double> y_bp, y_mp, s_mp;
+    long cap_y_clips = 0, cap_y_row = 0;
+    int cap_y_T = 0;
+};
+
+struct Scratch : front::Work, PassBufs, YardstickBufs {
     using Config = dsp_classify_config_f64;
     using Trace = dsp_classify_trace_f64;
     static constexpr int kFloatBytes = 8;
 
-    dsp::SpecTablesD *tab = nullptr;
-    dsp::ScreenTablesD *scr = nullptr;
-    unsigned long long *minmax = nullptr;  // [clip][2]: smallest / largest positive cell of a listed clip's map (double bits)
-    int *cu_table = nullptr;               // launch_iir2_screen_f64's per-CU arrival counters
+    dsp::DeviceBuf<dsp::SpecTablesD> tab;  // held = the workspace is initialised (init())
+    dsp::DeviceBuf<dsp::ScreenTablesD> scr;
+    dsp::DeviceBuf<int> cu_table;          // launch_iir2_screen_f64's per-CU arrival counters
     double U = 0.0;
-    // per pass: `cap_clips` clips, `cap_cells` = clips x columns of the largest pass
-    double *ck_bp = nullptr, *ck_mp = nullptr, *s_bp = nullptr, *mids = nullptr;
-    int *labels = nullptr, *loud = nullptr, *want = nullptr, *n_mids = nullptr, *hits = nullptr;
-    dsp::ClassifyTraceD *trace = nullptr;
-    long cap_clips = 0;
-    size_t cap_cells = 0;
-    // staging of host input (bytes) and the yardstick pipelines' filtered signals (doubles per row)
-    void *x = nullptr;
-    size_t cap_x = 0;
-    double *y_bp = nullptr, *y_mp = nullptr, *s_mp = nullptr;
-    long cap_y_clips = 0, cap_y_row = 0;
-    int cap_y_T = 0;
+    dsp::DeviceBuf<void> x;                // staging of host input
     long last_segments = 0;                // clips x columns of the last pass (dsp_classify_stats_f64)
 
     static Config default_config()
@@ -98,39 +104,30 @@ struct Scratch : front::Work {
         auto s = std::make_unique<dsp::ScreenTablesD>();
         dsp::build_spec_tables_f64(16000, *t);
         if (!dsp::build_screen_tables_f64(*t, 16000, *s)) return dsp::capi_fail(DSP_EINVAL, "screening tables: the window is not flat between its tapers");
-        DSP_CAPI_HIP(hipMalloc(&tab, sizeof(*t)));
-        DSP_CAPI_HIP(hipMemcpy(tab, t.get(), sizeof(*t), hipMemcpyHostToDevice));
-        DSP_CAPI_HIP(hipMalloc(&cu_table, sizeof(int) * (dsp::kSimdLoadCus + 16 * 4096)));      // (+ the diagnostic build's per-block records)
-        DSP_CAPI_HIP(hipMalloc(&scr, sizeof(*s)));
-        DSP_CAPI_HIP(hipMemcpy(scr, s.get(), sizeof(*s), hipMemcpyHostToDevice));
+        // built in locals and handed to the members after the last step that can fail: a failed init() leaves the workspace unopened
+        dsp::DeviceBuf<dsp::SpecTablesD> new_tab;
+        dsp::DeviceBuf<dsp::ScreenTablesD> new_scr;
+        dsp::DeviceBuf<int> new_cu_table;
+        DSP_CAPI_HIP(dsp::upload(new_tab, *t));
+        DSP_CAPI_HIP(new_cu_table.alloc(sizeof(int) * (dsp::kSimdLoadCus + 16 * 4096)));      // (+ the diagnostic build's per-block records)
+        DSP_CAPI_HIP(dsp::upload(new_scr, *s));
+        tab = std::move(new_tab);
+        scr = std::move(new_scr);
+        cu_table = std::move(new_cu_table);
         U = t->U;
         return DSP_OK;
     }
 
-    void free_pass()
-    {
-        for (void *p : {(void *)ck_bp, (void *)ck_mp, (void *)s_bp, (void *)mids, (void *)labels, (void *)loud, (void *)want, (void *)n_mids, (void *)hits, (void *)trace, (void *)minmax})
-            if (p) (void)hipFree(p);
-        minmax = nullptr;
-        ck_bp = ck_mp = s_bp = mids = nullptr; labels = loud = want = n_mids = hits = nullptr; trace = nullptr;
-        cap_clips = 0; cap_cells = 0;
-    }
-    void free_yardstick()
-    {
-        for (void *p : {(void *)y_bp, (void *)y_mp, (void *)s_mp})
-            if (p) (void)hipFree(p);
-        y_bp = y_mp = s_mp = nullptr; cap_y_clips = cap_y_row = 0; cap_y_T = 0;
-    }
+    void free_pass() { static_cast<PassBufs &>(*this) = PassBufs{}; }
+    void free_yardstick() { static_cast<YardstickBufs &>(*this) = YardstickBufs{}; }
     void free_all()
     {
         free_pass();
         free_yardstick();
-        if (x) (void)hipFree(x);
-        x = nullptr; cap_x = 0;
-        if (tab) (void)hipFree(tab);
-        if (scr) (void)hipFree(scr);
-        if (cu_table) (void)hipFree(cu_table);
-        tab = nullptr; scr = nullptr; cu_table = nullptr;
+        x.reset();
+        tab.reset();
+        scr.reset();
+        cu_table.reset();
     }
 
     // the workspace for passes of `clips` clips of n samples; grows, never shrinks
@@ -144,36 +141,33 @@ struct Scratch : front::Work {
             wait_idle();
             clips = std::max(clips, cap_clips);
             const size_t cells = std::max(cells_needed, cap_cells);
-            free_pass();
+            free_pass();      // (the capacities stay 0 if an allocation below fails: the next call starts over)
             const size_t ck = cells * dsp::kCkPerSegF64 * 8 * sizeof(double);
-            DSP_CAPI_HIP(hipMalloc(&ck_bp, ck));
-            DSP_CAPI_HIP(hipMalloc(&ck_mp, ck));
-            DSP_CAPI_HIP(hipMalloc(&s_bp, cells * dsp::kSpecBins * sizeof(double)));
-            DSP_CAPI_HIP(hipMalloc(&mids, (size_t)clips * dsp::kMaxMidpoints * sizeof(double)));
-            DSP_CAPI_HIP(hipMalloc(&loud, cells * sizeof(int)));
-            DSP_CAPI_HIP(hipMalloc(&want, (cells + 1) * sizeof(int)));
-            DSP_CAPI_HIP(hipMalloc(&n_mids, (size_t)clips * sizeof(int)));
-            DSP_CAPI_HIP(hipMalloc(&hits, ((size_t)clips + 1) * sizeof(int)));
-            DSP_CAPI_HIP(hipMalloc(&labels, (size_t)clips * sizeof(int)));
-            DSP_CAPI_HIP(hipMalloc(&trace, (size_t)clips * sizeof(dsp::ClassifyTraceD)));
-            DSP_CAPI_HIP(hipMalloc(&minmax, (size_t)clips * 2 * sizeof(unsigned long long)));
+            DSP_CAPI_HIP(ck_bp.alloc(ck));
+            DSP_CAPI_HIP(ck_mp.alloc(ck));
+            DSP_CAPI_HIP(s_bp.alloc(cells * dsp::kSpecBins * sizeof(double)));
+            DSP_CAPI_HIP(mids.alloc((size_t)clips * dsp::kMaxMidpoints * sizeof(double)));
+            DSP_CAPI_HIP(loud.alloc(cells * sizeof(int)));
+            DSP_CAPI_HIP(want.alloc((cells + 1) * sizeof(int)));
+            DSP_CAPI_HIP(n_mids.alloc((size_t)clips * sizeof(int)));
+            DSP_CAPI_HIP(hits.alloc(((size_t)clips + 1) * sizeof(int)));
+            DSP_CAPI_HIP(labels.alloc((size_t)clips * sizeof(int)));
+            DSP_CAPI_HIP(trace.alloc((size_t)clips * sizeof(dsp::ClassifyTraceD)));
+            DSP_CAPI_HIP(minmax.alloc((size_t)clips * 2 * sizeof(unsigned long long)));
             cap_clips = clips; cap_cells = cells;
         }
-        if (x_bytes > cap_x) {
+        if (x_bytes > x.bytes()) {
             wait_idle();
-            if (x) (void)hipFree(x);
-            x = nullptr; cap_x = 0;
-            DSP_CAPI_HIP(hipMalloc(&x, x_bytes));
-            cap_x = x_bytes;
+            DSP_CAPI_HIP(x.alloc(x_bytes));
         }
         if (pl != kCkpt && (clips > cap_y_clips || row_of(n) > cap_y_row || (int)T > cap_y_T)) {
             wait_idle();
             const long yc = std::max(clips, cap_y_clips), yr = std::max(row_of(n), cap_y_row);
             const size_t yT = std::max(T, (size_t)cap_y_T);
             free_yardstick();
-            DSP_CAPI_HIP(hipMalloc(&y_bp, (size_t)yc * yr * sizeof(double)));
-            DSP_CAPI_HIP(hipMalloc(&y_mp, (size_t)yc * yr * sizeof(double)));
-            DSP_CAPI_HIP(hipMalloc(&s_mp, (size_t)yc * dsp::kSpecBins * yT * sizeof(double)));
+            DSP_CAPI_HIP(y_bp.alloc((size_t)yc * yr * sizeof(double)));
+            DSP_CAPI_HIP(y_mp.alloc((size_t)yc * yr * sizeof(double)));
+            DSP_CAPI_HIP(s_mp.alloc((size_t)yc * dsp::kSpecBins * yT * sizeof(double)));
             cap_y_clips = yc; cap_y_row = yr; cap_y_T = (int)yT;
         }
         return DSP_OK;
@@ -187,7 +181,7 @@ struct Scratch : front::Work {
         dsp::IirCoefD c_bp, c_mp;
         coefficients(c_bp, c_mp);
         const dsp::ClassifyRuleD rule{cfg.keep_lo, cfg.keep_hi, cfg.midpoint_db, cfg.middle_max, cfg.above_min, cfg.below_min};
-        dsp::ClassifyTraceD *tr = want_trace ? trace : nullptr;
+        dsp::ClassifyTraceD *tr = want_trace ? trace.get() : nullptr;
         last_segments = cnt * (long)front::columns(n);
         if (pl == kCkpt) {
             const double guard = dsp::f64_threshold_guard();
@@ -214,7 +208,7 @@ struct Scratch : front::Work {
         return DSP_OK;
     }
 };
-Scratch (&g_w)[front::kMaxDevices] = front::workspaces<Scratch>;
+Scratch *const g_w = front::workspaces<Scratch>();
 
 }  // namespace
 

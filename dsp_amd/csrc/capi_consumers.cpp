@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -33,10 +34,9 @@ int check_device(int device)
 struct dsp_stop_model {
     int device = 0;
     dsp::StopModelDev m{};
-    void *d_blob = nullptr;
+    dsp::DeviceBuf<void> d_blob;
     // workspace of dsp_classify_signal_batch_device / dsp_classify_signal
-    float *d_mfcc = nullptr, *d_sig = nullptr, *d_prob = nullptr;
-    size_t mfcc_cap = 0, sig_cap = 0;
+    dsp::DeviceBuf<float> d_mfcc, d_sig, d_prob;
     dsp_mfcc_plan *plan = nullptr;     // default plan of dsp_classify_signal
     std::mutex mu;
     dsp::SpanRing scan;      // dsp_stop_scan_device: the per-recording offsets on their way to the GPU
@@ -45,11 +45,10 @@ struct dsp_stop_model {
 struct dsp_speaker_model {
     int device = 0;
     dsp::GmmDev target{}, ubm{};
-    void *d_blob = nullptr;
+    dsp::DeviceBuf<void> d_blob;
     dsp::SpanRing rows;      // dsp_speaker_llr_ragged_device, dsp_speaker_scan_device: the offsets on their way to the GPU (capi_util.hpp)
     // workspace of dsp_speaker_scan_device: the prefix sums of the per-row LLR (one stream at a time, include/dsp_amd.h)
-    unsigned long long *d_scan = nullptr;
-    size_t scan_cap = 0;
+    dsp::DeviceBuf<unsigned long long> d_scan;
     std::mutex mu;
 };
 
@@ -110,12 +109,12 @@ int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_m
     size_t fan_in = n_in;
     for (int l = 0; l < 4; ++l) { n_f += fan_in * p->units[l] + p->units[l]; fan_in = p->units[l]; }
     const size_t bytes = (pad.size() + pad_b.size() + 1) * sizeof(double) + n_f * sizeof(float);
-    auto *m = new dsp_stop_model;
+    auto m = std::make_unique<dsp_stop_model>();
     m->device = device;
-    if (hipMalloc(&m->d_blob, bytes) != hipSuccess) { delete m; return capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    if (m->d_blob.alloc(bytes) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
     std::vector<char> host(bytes);
     char *h = host.data();
-    char *d = static_cast<char *>(m->d_blob);
+    char *d = static_cast<char *>(m->d_blob.get());
     size_t off = 0;
     auto put = [&](const void *src, size_t n) { std::memcpy(h + off, src, n); const void *dev = d + off; off += n; return dev; };
     m->m.n_coef = p->n_coef;
@@ -133,8 +132,8 @@ int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_m
         m->m.bias[l] = static_cast<const float *>(put(p->bias[l], (size_t)p->units[l] * 4));
         fan_in = p->units[l];
     }
-    if (hipMemcpy(m->d_blob, h, bytes, hipMemcpyHostToDevice) != hipSuccess) { hipFree(m->d_blob); delete m; return capi_fail(DSP_EHIP, "hipMemcpy"); }
-    *out = m;
+    if (hipMemcpy(m->d_blob, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return capi_fail(DSP_EHIP, "hipMemcpy");
+    *out = m.release();
     return DSP_OK;
 }
 
@@ -144,8 +143,6 @@ void dsp_stop_model_destroy(dsp_stop_model *m)
     dsp::DeviceScope dsp_device_scope_(m->device);
     if (m->plan) dsp_mfcc_plan_destroy(m->plan);
     m->scan.release();
-    for (void *p : {(void *)m->d_blob, (void *)m->d_mfcc, (void *)m->d_sig, (void *)m->d_prob})
-        if (p) hipFree(p);
     delete m;
 }
 
@@ -180,7 +177,7 @@ static int classify_signal_batch(dsp_mfcc_plan *plan, dsp_stop_model *m, const v
     }
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
-    DSP_CAPI_HIP(dsp::reserve(m->d_mfcc, m->mfcc_cap, (size_t)n_clips * (t > 0 ? t : 1) * cfg.n_mfcc * sizeof(float)));
+    DSP_CAPI_HIP(m->d_mfcc.reserve((size_t)n_clips * (t > 0 ? t : 1) * cfg.n_mfcc * sizeof(float)));
     if (t > 0) {
         const int rc = in_kind == 0 ? dsp_mfcc_clips_device(plan, static_cast<const float *>(d_signal), n_clips, samples_per_clip, clip_stride, m->d_mfcc, m->m.max_frames, stream)
                                     : dsp_mfcc_clips_pcm16_device(plan, static_cast<const int16_t *>(d_signal), n_clips, samples_per_clip, clip_stride, channels,
@@ -249,13 +246,10 @@ float dsp_classify_signal(dsp_stop_model *m, const float *signal, int num_sample
             cfg.n_mfcc = m->m.n_coef;
             if (dsp_mfcc_plan_create(&cfg, m->device, &m->plan) < 0) return bail("plan");
         }
-        const size_t need = ((size_t)num_samples + 2) * sizeof(float);
-        if (m->sig_cap < need) {
-            if (m->d_sig) { hipFree(m->d_sig); m->d_sig = nullptr; m->sig_cap = 0; }
-            if (hipMalloc(&m->d_sig, need) != hipSuccess) { capi_fail(DSP_ENOMEM, "hipMalloc"); return bail("workspace"); }
-            m->sig_cap = need;
+        if (m->d_sig.reserve(((size_t)num_samples + 2) * sizeof(float)) != hipSuccess || m->d_prob.reserve(sizeof(float)) != hipSuccess) {
+            capi_fail(DSP_ENOMEM, "hipMalloc");
+            return bail("workspace");
         }
-        if (!m->d_prob && hipMalloc(&m->d_prob, sizeof(float)) != hipSuccess) { capi_fail(DSP_ENOMEM, "hipMalloc"); return bail("workspace"); }
         if (num_samples > 0 && hipMemcpy(m->d_sig, signal, (size_t)num_samples * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
             capi_fail(DSP_EHIP, "hipMemcpy");
             return bail("copy in");
@@ -282,10 +276,10 @@ int dsp_speaker_model_create(const dsp_gmm_params *target, const dsp_gmm_params 
     // layout: int32 inv_covs (t, u), int16 log_consts (t, u), int8 means (t, u)
     const size_t bytes = 2 * kd * 4 + 2 * k * 2 + 2 * kd;
     std::vector<char> host(bytes);
-    auto *m = new dsp_speaker_model;
+    auto m = std::make_unique<dsp_speaker_model>();
     m->device = device;
-    if (hipMalloc(&m->d_blob, bytes) != hipSuccess) { delete m; return capi_fail(DSP_ENOMEM, "hipMalloc"); }
-    char *d = static_cast<char *>(m->d_blob);
+    if (m->d_blob.alloc(bytes) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
+    char *d = static_cast<char *>(m->d_blob.get());
     size_t off = 0;
     auto put = [&](const void *src, size_t n) { std::memcpy(host.data() + off, src, n); const void *dev = d + off; off += n; return dev; };
     m->target.k = m->ubm.k = target->k;
@@ -296,8 +290,8 @@ int dsp_speaker_model_create(const dsp_gmm_params *target, const dsp_gmm_params 
     m->ubm.log_consts = static_cast<const int16_t *>(put(ubm->log_consts, k * 2));
     m->target.means = static_cast<const int8_t *>(put(target->means, kd));
     m->ubm.means = static_cast<const int8_t *>(put(ubm->means, kd));
-    if (hipMemcpy(m->d_blob, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { hipFree(m->d_blob); delete m; return capi_fail(DSP_EHIP, "hipMemcpy"); }
-    *out = m;
+    if (hipMemcpy(m->d_blob, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return capi_fail(DSP_EHIP, "hipMemcpy");
+    *out = m.release();
     return DSP_OK;
 }
 
@@ -305,8 +299,6 @@ void dsp_speaker_model_destroy(dsp_speaker_model *m)
 {
     if (!m) return;
     dsp::DeviceScope dsp_device_scope_(m->device);
-    if (m->d_blob) hipFree(m->d_blob);
-    if (m->d_scan) hipFree(m->d_scan);
     m->rows.release();
     delete m;
 }
@@ -362,14 +354,12 @@ int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_
     if (!in || !out || old_size < 1 || new_size < 2) return capi_fail(DSP_EINVAL, "bad argument (old_size >= 1, new_size >= 2)");
     int rc = check_device(0);
     if (rc < 0) return rc;
-    float *d_in = nullptr, *d_out = nullptr;
-    DSP_CAPI_HIP(hipMalloc(&d_in, (size_t)old_size * 4));
-    if (hipMalloc(&d_out, (size_t)new_size * 4) != hipSuccess) { hipFree(d_in); return capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    dsp::DeviceBuf<float> d_in, d_out;
+    DSP_CAPI_HIP(d_in.alloc((size_t)old_size * 4));
+    if (d_out.alloc((size_t)new_size * 4) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
     hipError_t e = hipMemcpy(d_in, in, (size_t)old_size * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_upsample_linear(d_in, 1, old_size, old_size, d_out, new_size, new_size, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)new_size * 4, hipMemcpyDeviceToHost);
-    hipFree(d_in);
-    hipFree(d_out);
     if (e != hipSuccess) return capi_fail(DSP_EHIP, hipGetErrorString(e));
     return DSP_OK;
 }
@@ -381,14 +371,12 @@ int dsp_fft_real_forward_host(const float *in_time, long n_frames, int frame_len
     if (n_frames == 0) return DSP_OK;
     int rc = check_device(0);
     if (rc < 0) return rc;
-    float *d_in = nullptr, *d_out = nullptr;
-    DSP_CAPI_HIP(hipMalloc(&d_in, (size_t)n_frames * frame_length * 4));
-    if (hipMalloc(&d_out, (size_t)n_frames * n_fft * 8) != hipSuccess) { hipFree(d_in); return capi_fail(DSP_ENOMEM, "hipMalloc"); }
+    dsp::DeviceBuf<float> d_in, d_out;
+    DSP_CAPI_HIP(d_in.alloc((size_t)n_frames * frame_length * 4));
+    if (d_out.alloc((size_t)n_frames * n_fft * 8) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
     hipError_t e = hipMemcpy2D(d_in, (size_t)frame_length * 4, in_time, (size_t)(n_frames > 1 ? in_stride : frame_length) * 4, (size_t)frame_length * 4, (size_t)n_frames, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = dsp::launch_fft_real_forward(d_in, n_frames, frame_length, frame_length, n_fft, d_out, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out_freq, d_out, (size_t)n_frames * n_fft * 8, hipMemcpyDeviceToHost);
-    hipFree(d_in);
-    hipFree(d_out);
     if (e != hipSuccess) return capi_fail(DSP_EHIP, hipGetErrorString(e));
     return DSP_OK;
 }
@@ -455,7 +443,7 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
     const size_t need = (size_t)(rows + (rows + dsp::kLlrScanChunk - 1) / dsp::kLlrScanChunk) * sizeof(unsigned long long);
-    if (dsp::reserve(m->d_scan, m->scan_cap, need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (speaker scan workspace)");
+    if (m->d_scan.reserve(need) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (speaker scan workspace)");
     dsp::SpanRing::Lease slot;
     DSP_CAPI_HIP(scan_upload(m->rows, frame_offsets, n_recordings, wo.data(), nullptr, slot, stream));
     const long *d = static_cast<const long *>(slot.d());
@@ -475,8 +463,7 @@ struct dsp_scanner {
     dsp_speaker_model *spk = nullptr;
     dsp_scan_config cfg{};
     int device = 0, n_mfcc = 0;
-    float *d_mfcc = nullptr;
-    size_t mfcc_cap = 0;
+    dsp::DeviceBuf<float> d_mfcc;
     std::vector<long> fo;
     std::mutex mu;
 };
@@ -504,7 +491,7 @@ static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int ch
     if (rows > 0) {
         if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
         DSP_ON_DEVICE(s->device);
-        if (dsp::reserve(s->d_mfcc, s->mfcc_cap, (size_t)rows * s->n_mfcc * sizeof(float)) != hipSuccess)
+        if (s->d_mfcc.reserve((size_t)rows * s->n_mfcc * sizeof(float)) != hipSuccess)
             return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
         const int rc = in_kind == 0 ? dsp_mfcc_clips_ragged_device(s->plan, static_cast<const float *>(d_signal), n, offsets, INT_MAX, s->d_mfcc, stream)
                                     : dsp_mfcc_clips_ragged_pcm16_device(s->plan, static_cast<const int16_t *>(d_signal), n, offsets, channels, stereo_mode,
@@ -558,7 +545,6 @@ void dsp_scanner_destroy(dsp_scanner *s)
 {
     if (!s) return;
     dsp::DeviceScope dsp_device_scope_(s->device);
-    if (s->d_mfcc) hipFree(s->d_mfcc);
     delete s;
 }
 

@@ -1,5 +1,5 @@
-// capi_util.hpp -- error reporting, device scopes and the ragged-span ring shared by the translation units of the C ABI (capi.cpp,
-// capi_consumers.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
+// capi_util.hpp -- error reporting, device scopes, the owner of device buffers and the ragged-span ring shared by the translation
+// units of the C ABI (capi.cpp, capi_consumers.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -131,16 +131,47 @@ inline int pcm16_kind(int channels, int stereo_mode)
     return channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
 }
 
-// a grow-only device workspace: buf holds at least `bytes` afterwards (its contents are not kept), or is NULL on an error
-template <class T> hipError_t reserve(T *&buf, size_t &cap, size_t bytes)
+// The owner of one hipMalloc'ed buffer and of its size: whoever holds it frees it, once, on destruction or reset().  Move-only.
+// Its holder makes the buffer's device current before the buffer is let go (the destroy functions' DeviceScope), and no object of
+// static storage holds one: at process exit the HIP runtime may already be gone.
+template <class T> class DeviceBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+public:
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DeviceBuf &operator=(DeviceBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DeviceBuf() { reset(); }
+    void reset()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // exactly `bytes`, in place of what was held; empty on an error
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes; else p = nullptr;
+        return e;
+    }
+    // a grow-only workspace: at least `bytes` afterwards (its contents are not kept), or empty on an error
+    hipError_t reserve(size_t bytes) { return cap >= bytes ? hipSuccess : alloc(bytes); }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    size_t bytes() const { return cap; }
+};
+
+// a new buffer holding a copy of the host's object
+template <class T> hipError_t upload(DeviceBuf<T> &buf, const T &host)
 {
-    if (cap >= bytes) return hipSuccess;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc(&buf, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
+    const hipError_t e = buf.alloc(sizeof(T));
+    return e == hipSuccess ? hipMemcpy(buf, &host, sizeof(T), hipMemcpyHostToDevice) : e;
 }
 }
 

@@ -10,7 +10,7 @@
 //     init()                          tables, once per workspace (the caller holds mu and has made the device current)
 //     reserve(pl, clips, n, x_bytes)  the workspace of a pass of `clips` clips of n samples (+ x_bytes of staging at x); grows only
 //     run(pl, cfg, d_x, in, clips, n, stride, want_trace, st, spans, total)    one pass: labels (+ trace) into `labels` / `trace`
-//     free_all()                      every device buffer of the workspace
+//     free_all()                      lets every device buffer of the workspace go
 // Input kinds `in`: 0 float samples, 1 / 2 / 3 int16 mono / interleaved stereo channel 0 / stereo average.
 #pragma once
 
@@ -53,7 +53,13 @@ struct Work {
         pending = false;
     }
 };
-template <class W> W workspaces[kMaxDevices];
+// Immortal: allocated at first use and never deleted, so that no destructor calls into HIP at process exit (or at interpreter
+// shutdown, under ctypes beside torch), when the runtime may already be gone.  dsp_classify_release* return the memory.
+template <class W> W *workspaces()
+{
+    static W *const all = new W[kMaxDevices];
+    return all;
+}
 
 // leaves the "workspace busy until here" event behind the call's work on EVERY exit, so that a failed call cannot hand a workspace
 // with kernels still running on it to the next one
@@ -91,7 +97,7 @@ template <class W> int release_devices(int device)      // device < 0: all of th
     if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
     for (int d = 0; d < kMaxDevices && d < count; ++d) {
         if (device >= 0 && d != device) continue;
-        W &w = workspaces<W>[d];
+        W &w = workspaces<W>()[d];
         std::lock_guard<std::mutex> lock(w.mu);
         if (w.device < 0) continue;
         DSP_ON_DEVICE(d);
@@ -161,7 +167,7 @@ template <class W> int device_entry(const typename W::Config *cfgp, const void *
         return DSP_OK;
     }
     if (n_clips == 1) stride = n;
-    W &w = own ? *own : workspaces<W>[device];
+    W &w = own ? *own : workspaces<W>()[device];
     std::lock_guard<std::mutex> lock(w.mu);
     if ((rc = open(w, device)) < 0) return rc;
     const int pl = W::pipeline(in, false);
@@ -196,7 +202,7 @@ template <class W> int host_entry(const typename W::Config *cfgp, const void *si
     if ((rc = host_device(device)) < 0) return rc;
     DSP_ON_DEVICE(device);
     if (n_clips == 1) stride = n;
-    W &w = workspaces<W>[device];
+    W &w = workspaces<W>()[device];
     std::lock_guard<std::mutex> lock(w.mu);
     if ((rc = open(w, device)) < 0) return rc;
     const int pl = W::pipeline(in, false);
@@ -241,7 +247,7 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
         return DSP_OK;
     }
     if (n_clips >= (1L << 31)) return capi_fail(DSP_EINVAL, "too many clips");
-    W &w = workspaces<W>[device];
+    W &w = workspaces<W>()[device];
     std::lock_guard<std::mutex> lock(w.mu);
     if ((rc = open(w, device)) < 0) return rc;
     const int pl = W::pipeline(in, true);
@@ -332,20 +338,13 @@ template <class W> int ragged_host_entry(const typename W::Config *cfgp, const v
     int device = 0;
     if ((rc = host_device(device)) < 0) return rc;
     // the whole buffer travels once (a buffer of its own: the workspaces' staging rows are laid out for equal clips)
-    void *d_flat = nullptr;
+    DSP_ON_DEVICE(device);
+    DeviceBuf<void> d_flat;
     const size_t bytes = (size_t)offsets[n_clips] * sample_bytes<W>(in);
-    {
-        DSP_ON_DEVICE(device);
-        DSP_CAPI_HIP(hipMalloc(&d_flat, bytes + 16));
-        const hipError_t e = hipMemcpy(d_flat, signal, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_flat); DSP_CAPI_HIP(e); }
-    }
+    DSP_CAPI_HIP(d_flat.alloc(bytes + 16));
+    DSP_CAPI_HIP(hipMemcpy(d_flat, signal, bytes, hipMemcpyHostToDevice));
     rc = ragged<W>(cfg, d_flat, device, in, n_clips, offsets, nullptr, nullptr, labels, trace, nullptr);
-    {
-        DeviceScope on(device);
-        (void)hipStreamSynchronize(nullptr);
-        (void)hipFree(d_flat);
-    }
+    (void)hipStreamSynchronize(nullptr);      // the pass's kernels read d_flat: they end before it is let go
     return rc;
 }
 
