@@ -5,6 +5,7 @@
   SpeakerModel   mfcc_target_speaker_llr_mean / classify_speaker   2fa/audio/pico-audio/src/speaker_gmm.c:127-141
   upsample_linear   upsampleLinear                             sync/particle/main.cpp:62-77
   Scanner        both per sliding window of long recordings     sync/sync.cpp:188-213 (one 1 s buffer at a time)
+  StreamSession  the same for audio that is still arriving       sync/sync.cpp:188-213 (the capture loop itself, many feeds)
 
 Trained parameters are passed in as arrays (the reference compiles them in from model_params.h / gmm_params.inc).
 Tensors are HBM-resident torch tensors; Python only moves pointers.
@@ -290,6 +291,142 @@ class Scanner:
         return wo, prob, mean, label
 
 
+def _long_array(a, size, what):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+    if a.ndim != 1 or a.size != size:
+        raise ValueError(f"{what} must hold {size} entries")
+    return a
+
+
+def _chunk_offsets(chunk_offsets, n_streams):
+    co = _long_array(chunk_offsets, n_streams + 1, "chunk_offsets")
+    if co[0] < 0 or (np.diff(co) < 0).any():
+        raise ValueError("chunk_offsets must be non-negative and non-decreasing")
+    return co
+
+
+_LP = C.POINTER(C.c_long)
+
+
+def stream_push_plan(cfg, received, chunk_offsets, window_frames=None, hop_frames=None):
+    """Host only (dsp_stream_push_plan): what a push of chunks [chunk_offsets[s], chunk_offsets[s + 1]) emits for streams that have
+    received `received[s]` samples so far (None: none) -> (row_offsets int64 [n + 1], window_offsets int64 [n + 1] | None), the prefix
+    sums of the new MFCC rows and, when window_frames / hop_frames are given, of the new windows."""
+    if (window_frames is None) != (hop_frames is None):
+        raise ValueError("window_frames and hop_frames go together")
+    co = np.ascontiguousarray(np.asarray(chunk_offsets, dtype=np.int64))
+    if co.ndim != 1 or co.size < 1:
+        raise ValueError("chunk_offsets must hold n_streams + 1 positions")
+    n = co.size - 1
+    co = _chunk_offsets(co, n)
+    rec = None
+    if received is not None:
+        rec = _long_array(received, n, "received")
+        if (rec < 0).any():
+            raise ValueError("received must be non-negative")
+    scan = None
+    if window_frames is not None:
+        scan = _scan_config(window_frames, hop_frames)
+        if scan.hop_frames > scan.window_frames:
+            raise ValueError("hop_frames must not exceed window_frames")
+    ro = np.zeros(n + 1, np.int64)
+    wo = np.zeros(n + 1, np.int64) if scan is not None else None
+    _lib.check(_lib.load().dsp_stream_push_plan(C.byref(cfg), C.byref(scan) if scan is not None else None,
+                                                rec.ctypes.data_as(_LP) if rec is not None else None, co.ctypes.data_as(_LP), n,
+                                                ro.ctypes.data_as(_LP), wo.ctypes.data_as(_LP) if wo is not None else None), "dsp_stream_push_plan")
+    return ro, wo
+
+
+class StreamSession:
+    """dsp_stream_session: n_streams live streams on one GPU.  Every push hands over the next chunk of each stream (any length) and
+    returns the MFCC rows and the window scores that became complete with it; concatenated over the pushes they are, bit for bit,
+    MfccPlan.clips_ragged and Scanner.run on the whole recording -- except that a stream has no window before it holds window_frames
+    rows.  dtype: torch.float32 samples, or torch.int16 PCM ([total] mono, [total][2] interleaved stereo with stereo_mode 0 = channel
+    0 / 1 = average; channels=2 selects stereo).  One stream at a time per session."""
+
+    def __init__(self, plan: MfccPlan, n_streams: int, stop: StopModel | None = None, speaker: SpeakerModel | None = None,
+                 window_frames: int = 98, hop_frames: int = 10, dtype=None, stereo_mode: int = 0, channels: int = 1):
+        import torch
+        self._L = _lib.load()
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError("dtype must be torch.float32 or torch.int16")
+        if int(n_streams) < 0:
+            raise ValueError("n_streams must be >= 0")
+        if channels not in (1, 2) or (channels == 2 and dtype != torch.int16):
+            raise ValueError("channels must be 1, or 2 for int16 PCM")
+        if stereo_mode not in (0, 1):
+            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
+        self.cfg = _scan_config(window_frames, hop_frames) if (stop or speaker) else None
+        if self.cfg is not None and self.cfg.hop_frames > self.cfg.window_frames:
+            raise ValueError("hop_frames must not exceed window_frames")
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_stream_session_create(plan._h, stop._h if stop else None, speaker._h if speaker else None,
+                                                     C.byref(self.cfg) if self.cfg is not None else None, int(n_streams), int(channels),
+                                                     int(stereo_mode), int(dtype == torch.int16), C.byref(h)), "dsp_stream_session_create")
+        self._h, self.plan, self.stop, self.speaker = h, plan, stop, speaker      # (the session borrows them: keep them alive)
+        self.n_streams, self.dtype, self.channels, self.device = int(n_streams), dtype, int(channels), plan.device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_stream_session_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def counts(self):
+        """-> (samples received, rows emitted, windows emitted), int64 [n_streams] each."""
+        out = [np.zeros(self.n_streams, np.int64) for _ in range(3)]
+        _lib.check(self._L.dsp_stream_session_counts(self._h, *[a.ctypes.data_as(_LP) for a in out]), "dsp_stream_session_counts")
+        return tuple(out)
+
+    def reset(self, streams=None):
+        """Forget the named streams' samples, rows and counters (None: all of them, which also revives a broken session)."""
+        if streams is None:
+            _lib.check(self._L.dsp_stream_session_reset(self._h, None, 0, None), "dsp_stream_session_reset")
+            return
+        idx = np.ascontiguousarray(np.asarray(streams, dtype=np.int64))
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.n_streams)):
+            raise ValueError(f"streams must name streams 0 .. {self.n_streams - 1}")
+        _lib.check(self._L.dsp_stream_session_reset(self._h, idx.ctypes.data_as(_LP), idx.size, None), "dsp_stream_session_reset")
+
+    def push(self, chunks, chunk_offsets, want_rows: bool = True):
+        """chunks: a contiguous CUDA tensor of the session's dtype on the plan's device ([total], or [total][2] for stereo), stream s's
+        chunk = sample frames [chunk_offsets[s], chunk_offsets[s + 1]) -> (row_offsets int64 [n + 1], rows float32 [new rows][n_mfcc] | None,
+        window_offsets int64 [n + 1], prob float32 | None, llr_mean int64 | None, label int32 | None), one entry per new window."""
+        import torch
+        if not (isinstance(chunks, torch.Tensor) and chunks.is_cuda and chunks.is_contiguous()):
+            raise ValueError("chunks must be a contiguous CUDA tensor")
+        if chunks.dtype != self.dtype:
+            raise ValueError(f"chunks must be {str(self.dtype).replace('torch.', '')}, as the session was created")
+        if chunks.device.index != self.device:
+            raise ValueError(f"chunks must live on the session's device (cuda:{self.device})")
+        if not (chunks.dim() == 1 if self.channels == 1 else (chunks.dim() == 2 and chunks.shape[1] == 2)):
+            raise ValueError("chunks must be [total] (mono) or [total][2] (interleaved stereo), as the session was created")
+        co = _chunk_offsets(chunk_offsets, self.n_streams)
+        if int(co[-1]) > chunks.shape[0]:
+            raise ValueError("chunk_offsets run past the end of chunks")
+        ro, wo = stream_push_plan(self.plan.cfg, self.counts()[0], co, *((self.cfg.window_frames, self.cfg.hop_frames) if self.cfg is not None else ()))
+        if wo is None:
+            wo = np.zeros(self.n_streams + 1, np.int64)
+        nr, nw, dev = int(ro[-1]), int(wo[-1]), chunks.device
+        rows = torch.empty((nr, self.plan.cfg.n_mfcc), dtype=torch.float32, device=dev) if want_rows else None
+        prob = torch.empty(nw, dtype=torch.float32, device=dev) if self.stop else None
+        mean = torch.empty(nw, dtype=torch.int64, device=dev) if self.speaker else None
+        label = torch.empty(nw, dtype=torch.int32, device=dev) if self.speaker else None
+        ptrs = [t.data_ptr() if t is not None else None for t in (rows, prob, mean, label)]
+        ro2, wo2 = np.zeros_like(ro), np.zeros_like(wo)
+        _lib.check(self._L.dsp_stream_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_LP), *ptrs, ro2.ctypes.data_as(_LP),
+                                                  wo2.ctypes.data_as(_LP), _stream(chunks)), "dsp_stream_push_device")
+        if not (np.array_equal(ro, ro2) and np.array_equal(wo, wo2)):
+            raise _lib.DspError("dsp_stream_push_device emitted other rows / windows than dsp_stream_push_plan announced")
+        return ro2, rows, wo2, prob, mean, label
+
+
 def upsample_linear(x, new_size: int):
     """x: cuda float32 [n_clips][old] (or [old]) -> [n_clips][new_size]; numpy input goes through the host entry point."""
     L = _lib.load()
@@ -309,4 +446,4 @@ def upsample_linear(x, new_size: int):
     return out[0] if squeeze else out
 
 
-__all__ = ["StopModel", "SpeakerModel", "Scanner", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]
+__all__ = ["StopModel", "SpeakerModel", "Scanner", "StreamSession", "stream_push_plan", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]

@@ -948,6 +948,16 @@ int dsp_scrubjay_fused_ragged_pcm16_device(dsp_mfcc_plan *p, dsp_svm *s, const i
 
 int dsp::plan_device(const dsp_mfcc_plan *plan) { return plan ? plan->device : -1; }
 
+// capi_util.hpp: the ragged MFCC path over spans given by start and length (capi_stream.cpp: one span per stream with new rows)
+int dsp::mfcc_spans_device(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_spans, const long *starts, const long *lengths, float *d_out,
+                           void *stream)
+{
+    if (!lengths) return fail(DSP_EINVAL, "internal: spans without lengths");
+    if (p && in_kind > 0 && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))     // as run() would, before any launch
+        return fail(DSP_EINVAL, "PCM16 ingestion runs on the 512-point wave-per-frame kernel (per-frame log mode) and on the 2048-point scrubjay_infer.c front end");
+    return mfcc_clips_ragged(p, d_in, in_kind, n_spans, starts, INT_MAX, d_out, stream, lengths);
+}
+
 // capi_util.hpp: the fused form of dsp_classify_signal_batch_device (capi_consumers.cpp)
 int dsp::stop_fused_device(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *d_signal, long n_clips, long clip_stride, int t,
                            float *d_prob, void *stream, int in_kind, const long *offsets)

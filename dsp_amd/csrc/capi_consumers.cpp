@@ -456,6 +456,24 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
 
 }  // extern "C"
 
+// capi_util.hpp: the front end and the models of a scanner / a stream session
+int dsp::scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg)
+{
+    dsp_mfcc_config pcfg;
+    dsp_mfcc_plan_config(plan, &pcfg);
+    if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
+        return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
+                                     "no prefilter");
+    const int device = dsp::plan_device(plan);
+    if (stop && (pcfg.n_mfcc != stop->m.n_coef || stop->device != device))
+        return capi_fail(DSP_EINVAL, "the stop model needs n_coef = the plan's n_mfcc, on the plan's device");
+    if (speaker && (pcfg.n_mfcc != speaker->target.d || speaker->device != device))
+        return capi_fail(DSP_EINVAL, "the speaker model needs d = the plan's n_mfcc, on the plan's device");
+    if (stop && dsp::stop_scan_tile(stop->m, cfg->window_frames, cfg->hop_frames) == 0)
+        return capi_fail(DSP_EINVAL, "the stop model's window (min(window_frames, max_frames) rows of n_coef) does not fit the scan kernel's LDS");
+    return DSP_OK;
+}
+
 // A scanner: PCM -> ragged MFCC matrix in its own workspace -> the models' window scans, all on the caller's stream.
 struct dsp_scanner {
     dsp_mfcc_plan *plan = nullptr;
@@ -518,24 +536,15 @@ int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_mo
     if (!plan) return capi_fail(DSP_EINVAL, "plan is NULL");
     if (!stop && !speaker) return capi_fail(DSP_EINVAL, "a scanner needs a stop model, a speaker model or both");
     if (const int rc = scan_args(cfg, 0)) return rc;
+    if (const int rc = dsp::scan_front_check(plan, stop, speaker, cfg)) return rc;
     dsp_mfcc_config pcfg;
     dsp_mfcc_plan_config(plan, &pcfg);
-    if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
-        return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
-                                     "no prefilter");
-    const int device = dsp::plan_device(plan);
-    if (stop && (pcfg.n_mfcc != stop->m.n_coef || stop->device != device))
-        return capi_fail(DSP_EINVAL, "the stop model needs n_coef = the plan's n_mfcc, on the plan's device");
-    if (speaker && (pcfg.n_mfcc != speaker->target.d || speaker->device != device))
-        return capi_fail(DSP_EINVAL, "the speaker model needs d = the plan's n_mfcc, on the plan's device");
-    if (stop && dsp::stop_scan_tile(stop->m, cfg->window_frames, cfg->hop_frames) == 0)
-        return capi_fail(DSP_EINVAL, "the stop model's window (min(window_frames, max_frames) rows of n_coef) does not fit the scan kernel's LDS");
     auto *s = new dsp_scanner;
     s->plan = plan;
     s->stop = stop;
     s->spk = speaker;
     s->cfg = *cfg;
-    s->device = device;
+    s->device = dsp::plan_device(plan);
     s->n_mfcc = pcfg.n_mfcc;
     *out = s;
     return DSP_OK;

@@ -1,5 +1,5 @@
 // capi_util.hpp -- error reporting, device scopes, the owner of device buffers and the ragged-span ring shared by the translation
-// units of the C ABI (capi.cpp, capi_consumers.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
+// units of the C ABI (capi.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -15,6 +15,14 @@
 #include "../../include/dsp_amd.h"
 
 struct dsp_mfcc_plan;
+struct dsp_stop_model;
+struct dsp_speaker_model;
+namespace dsp {
+// capi_consumers.cpp (owner of the models): what dsp_scanner_create and dsp_stream_session_create ask of a plan and of the models they
+// borrow -- rows that depend on their own samples only, n_coef / d = the plan's n_mfcc on the plan's device, a stop window that fits the
+// scan kernel's LDS.  stop / speaker may be NULL (cfg is read only when one is given).  DSP_OK or DSP_EINVAL.
+int scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg);
+}
 namespace dsp {
 int capi_fail(int code, const std::string &msg);   // sets dsp_last_error() for this thread, returns code
 struct StopModelDev;
@@ -26,6 +34,11 @@ int stop_fused_device(dsp_mfcc_plan *plan, const StopModelDev &m, const void *d_
                       void *stream, int in_kind = 0, const long *offsets = nullptr);
 // offsets != nullptr: a ragged batch (clip c = samples [offsets[c], offsets[c + 1]) per channel; clip_stride and t unused)
 int plan_device(const dsp_mfcc_plan *plan);          // the GPU a plan lives on
+// capi.cpp: the ragged MFCC path of dsp_mfcc_clips_ragged_device (no frame cap) over spans anywhere in d_in: span c = sample frames
+// [starts[c], starts[c] + lengths[c]), its rows behind those of span c - 1 in d_out.  in_kind as above.  n_spans = 0 checks the plan
+// and launches nothing.  Returns the rows of the longest span or < 0.
+int mfcc_spans_device(dsp_mfcc_plan *plan, const void *d_in, int in_kind, long n_spans, const long *starts, const long *lengths, float *d_out,
+                      void *stream);
 }
 
 // Ragged batches: the clips' spans (clip_span.hpp ClipSpan: start, samples, frames, caller's index -- 32 bytes per clip) travel to the GPU through a

@@ -112,6 +112,8 @@ SYMBOLS = [
     "dsp_scanner_create", "dsp_scanner_destroy", "dsp_scanner_run_device", "dsp_scanner_run_pcm16_device",
     "dsp_scan_window_spans", "dsp_svm_scan_device", "dsp_scrubjay_scanner_create", "dsp_scrubjay_scanner_destroy",
     "dsp_scrubjay_scanner_run_device", "dsp_scrubjay_scanner_run_pcm16_device",
+    "dsp_stream_push_plan", "dsp_stream_session_create", "dsp_stream_session_destroy", "dsp_stream_session_reset",
+    "dsp_stream_session_counts", "dsp_stream_push_device",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
@@ -239,6 +241,12 @@ def load() -> C.CDLL:
     L.dsp_scrubjay_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_scrubjay_scanner_run_device.restype = ip
     L.dsp_scrubjay_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp, vp]
     L.dsp_scrubjay_scanner_run_pcm16_device.restype = ip
+    L.dsp_stream_push_plan.argtypes = [cfgp, scp, lp, lp, C.c_long, lp, lp]; L.dsp_stream_push_plan.restype = C.c_long
+    L.dsp_stream_session_create.argtypes = [vp, vp, vp, scp, C.c_long, ip, ip, ip, C.POINTER(vp)]; L.dsp_stream_session_create.restype = ip
+    L.dsp_stream_session_destroy.argtypes = [vp]; L.dsp_stream_session_destroy.restype = None
+    L.dsp_stream_session_reset.argtypes = [vp, lp, C.c_long, vp]; L.dsp_stream_session_reset.restype = ip
+    L.dsp_stream_session_counts.argtypes = [vp, lp, lp, lp]; L.dsp_stream_session_counts.restype = ip
+    L.dsp_stream_push_device.argtypes = [vp, vp, lp, vp, vp, vp, vp, lp, lp, vp]; L.dsp_stream_push_device.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip

@@ -569,6 +569,57 @@ int dsp_scrubjay_scanner_run_pcm16_device(dsp_scrubjay_scanner *scanner, const i
                                           int channels, int stereo_mode, int *d_labels, float *d_decision, float *d_prob1, float *d_feat,
                                           void *stream);
 
+/* LIVE STREAMS: audio that is still arriving (the firmware's capture loop, sync/sync.cpp:188-213, for many feeds at once).  A stream
+ * session holds N independent streams on one GPU.  Each push hands over the next chunk of every stream -- any length, zero included --
+ * and returns the MFCC rows that became complete with it and the scores of the windows that became complete with those rows.
+ * Concatenated over all pushes a stream's outputs are, bit for bit, what the entries above give on the whole recording: the rows of
+ * dsp_mfcc_clips_ragged_device (no frame cap), and P("stop"), the Q8 speaker LLR mean and the label of dsp_scanner_run_device for every
+ * stream that holds at least one full window.  How the audio was cut into chunks shows in no output bit.
+ *
+ * With FL = frame_length, H = hop_length, WF = window_frames, HF = hop_frames, per stream:
+ *   N samples received so far give R(N) = N >= FL ? 1 + (N - FL) / H : 0 rows; row k is samples [k H, k H + FL) of the stream.  A push
+ *   emits rows R(N before) .. R(N after) - 1.  The session carries the samples from R(N) H on to the next push: N - R(N) H of them,
+ *   fewer than FL.
+ *   E rows give W(E) = E >= WF ? 1 + (E - WF) / HF : 0 windows; window w is rows [w HF, w HF + WF).  A push emits windows
+ *   W(E before) .. W(E after) - 1.  The session carries the rows from W(E) HF on: fewer than WF.
+ * ONE DIFFERENCE from the scanner: a finished recording with fewer than WF rows gets one short window; a stream never ends, so it has
+ * no window until it holds WF rows.  There is no "finish" call.
+ *
+ * Accepted: the plans dsp_scanner_create accepts (n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, no prefilter; DSP_EINVAL with
+ * the scanner's wording otherwise) with hop_length <= frame_length; hop_frames <= window_frames (a stream skips no input); stop model,
+ * speaker model, both (n_coef / d = the plan's n_mfcc, on the plan's device, a stop window that fits the scan kernel) or neither -- then
+ * the session yields rows only and `scan` is not read.  pcm16 = 0: float samples (channels must be 1); pcm16 != 0: int16 PCM, channels
+ * and stereo_mode as dsp_mfcc_clips_ragged_pcm16_device (mono, stereo channel 0, stereo average).  The format is fixed at creation: the
+ * carried samples stay in the caller's format and are decoded by the kernel that decodes a whole recording.
+ *
+ * dsp_stream_push_plan (host only, no GPU, no session): what a push would emit.  received[n_streams] = samples per stream before the
+ * push (NULL: all zero), chunk_offsets[n_streams + 1] = the chunks back to back (as dsp_mfcc_clips_ragged_device's offsets).  Fills
+ * row_offsets and window_offsets [n_streams + 1], the prefix sums of the new rows / new windows (scan NULL: no windows; window_offsets
+ * may be NULL).  Returns the new rows in total or a negative DSP_E* code.
+ *
+ * dsp_stream_push_device: d_chunks float or int16 (interleaved if stereo) as the session was created, chunk c = sample frames
+ * [chunk_offsets[c], chunk_offsets[c + 1]).  d_mfcc[new rows][n_mfcc] in stream order, may be NULL when the caller wants scores only.
+ * d_prob / d_llr_mean / d_labels[new windows] as dsp_scanner_run_device.  row_offsets / window_offsets: HOST arrays of n_streams + 1,
+ * filled before a successful call returns (may be NULL).  Everything is enqueued on `stream`, no host synchronisation.  A refused push
+ * leaves the session exactly as it was.  If a HIP call fails behind a push's first launch the session is broken: every later push
+ * returns DSP_EHIP until dsp_stream_session_reset(session, NULL, ...).  Zero streams, or a push that completes no row and no window:
+ * DSP_OK, no MFCC and no scan launch.
+ * dsp_stream_session_reset: streams == NULL: all; else streams[n] name the streams whose samples, rows and counters are forgotten (a
+ * new feed takes the slot).  Ordered with the pushes like any call on the session.  dsp_stream_session_counts: the host counters per
+ * stream -- samples received, rows emitted, windows emitted; any may be NULL.
+ * The session borrows plan and models (destroy it first) and owns its buffers; ONE stream at a time per session (and per speaker
+ * model), as for a scanner.                                                                                                        */
+typedef struct dsp_stream_session dsp_stream_session;
+long dsp_stream_push_plan(const dsp_mfcc_config *mfcc, const dsp_scan_config *scan, const long *received, const long *chunk_offsets,
+                          long n_streams, long *row_offsets, long *window_offsets);
+int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_model *speaker, const dsp_scan_config *scan,
+                              long n_streams, int channels, int stereo_mode, int pcm16, dsp_stream_session **out);
+void dsp_stream_session_destroy(dsp_stream_session *session);
+int dsp_stream_session_reset(dsp_stream_session *session, const long *streams, long n, void *stream);
+int dsp_stream_session_counts(const dsp_stream_session *session, long *samples, long *rows, long *windows);
+int dsp_stream_push_device(dsp_stream_session *session, const void *d_chunks, const long *chunk_offsets, float *d_mfcc, float *d_prob,
+                           int64_t *d_llr_mean, int *d_labels, long *row_offsets, long *window_offsets, void *stream);
+
 /* upsampleLinear (sync/particle/main.cpp:62-77) over a batch: d_out[c][i] for i < new_size from
  * d_in[c][0..old_size), the reference's fp32 operation order (bit-identical).  new_size >= 2.     */
 int dsp_upsample_linear_device(const float *d_in, long n_clips, int old_size, long in_stride, float *d_out,

@@ -2,7 +2,7 @@
 # Sanitizer tier of the CPU-testable code (reference precedent 2fa/audio/CMakeLists.txt:9).  Never on the GPU box.
 #   leg 1  oracle/*.c under gcc's AddressSanitizer + UBSan (make -C oracle asan), driven by the oracle's own tests
 #   leg 2  the product's HOST code -- tables.cpp (bipartite matching, chunk packing, Durand-Kerner), the argument handling of capi*.cpp,
-#          the planner -- as a build of libdsp_amd.so with -Xarch_host -fsanitize=address,undefined (device code untouched), driven
+#          the planners (MFCC tables, stream pushes) -- as a build of libdsp_amd.so with -Xarch_host -fsanitize=address,undefined (device code untouched), driven
 #          by the CPU tests of the C ABI
 # -fno-sanitize-recover=all: the first finding aborts the run.  Usage: tools/asan_host.sh [oracle|product|all]
 set -e
@@ -24,6 +24,7 @@ if [ "$WHAT" = product ] || [ "$WHAT" = all ]; then
         DSP_AMD_EXTRA_LDFLAGS="-fsanitize=address,undefined -shared-libsan" python -m dsp_amd.build > /dev/null
     RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
     LD_PRELOAD="$RT" DSP_AMD_LIB="$ROOT/variants/asan_host.so" \
-        python -m pytest -x -q -p no:cacheprovider tests/test_capi_cpu.py tests/test_planner_cpu.py tests/test_tables_grid_cpu.py -k "not oracle_tables and not product_never"
+        python -m pytest -x -q -p no:cacheprovider tests/test_capi_cpu.py tests/test_planner_cpu.py tests/test_tables_grid_cpu.py tests/test_stream_cpu.py \
+        -k "not oracle_tables and not product_never and not stream_symbols and not stream_wrapper_checks"
     echo "ASAN-PRODUCT-OK"
 fi
