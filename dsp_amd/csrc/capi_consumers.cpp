@@ -11,25 +11,13 @@
 #include <mutex>
 #include <vector>
 
-#include "capi_util.hpp"
 #include "consumer_kernels.hpp"
+#include "mfcc_plan.hpp"
 
 using dsp::capi_fail;
 using dsp::scan_args;
 using dsp::scan_plan;
 using dsp::scan_upload;
-
-namespace {
-
-int check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return capi_fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
-    if (device < 0 || device >= n) return capi_fail(DSP_EINVAL, "device index out of range");
-    return DSP_OK;
-}
-
-}  // namespace
 
 struct dsp_stop_model {
     int device = 0;
@@ -63,8 +51,7 @@ int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_m
         if (p->units[l] <= 0 || p->units[l] > dsp::kStopMaxUnits || !p->kernel[l] || !p->bias[l])
             return capi_fail(DSP_EINVAL, "stop-model layers must have 1..16 units and non-NULL parameters");
     if (p->units[3] != 1) return capi_fail(DSP_EINVAL, "the last layer must have one unit (sigmoid output)");
-    int rc = check_device(device);
-    if (rc < 0) return rc;
+    if (const int rc = dsp::check_device(device)) return rc;
     DSP_ON_DEVICE(device);
     const size_t n_in = (size_t)p->n_coef * p->max_frames, u1 = p->units[0];
     // divisor with the reference's zero guard (audio_classifier_inference.c:44-45)
@@ -156,32 +143,52 @@ int dsp_stop_predict_device(dsp_stop_model *m, const float *d_mfcc, long n_clips
 
 }  // extern "C"
 
+// classify_signal in one kernel -- clip -> MFCC -> stop-word net, the MFCC matrix never written.  Returns 1 when the fused
+// kernel was enqueued, 0 when this plan / model shape has no fused form (the caller runs the two-kernel path), < 0 on error.
+// t = frames per clip (already capped at the model's max_frames).  offsets != nullptr: a ragged batch (clip c = samples [offsets[c],
+// offsets[c + 1]) per channel; clip_stride and t unused)
+static int stop_fused(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *d_signal, int in_kind, long n_clips, long clip_stride, int t,
+                      const long *offsets, float *d_prob, void *stream)
+{
+    if (offsets) { t = 1; clip_stride = 0; }
+    // the reference's shape on the default kernel: 512-point, per-frame log, 13 coefficients of 40 mel energies, complete frames
+    if (p->cfg.n_fft != 512 || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX || p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE ||
+        p->host.dct_split != 4 || p->host.dct_len != 10 || m.n_coef != p->cfg.n_mfcc || m.units[0] > dsp::kStopFusedUnits || !m.fold_a || t <= 0 ||
+        std::getenv("DSP_AMD_STOP_TWO_KERNELS"))
+        return 0;
+    if (!dsp::input_aligned(d_signal, in_kind, n_clips > 1, clip_stride)) return 0;      // the two-kernel path reports it
+    if (in_kind != 0 && (p->host.mel_gather != 3 || p->cfg.frame_length != 400)) return 0;
+    if (m.max_frames <= 0) return capi_fail(DSP_EINVAL, "stop model without frames");
+    // ragged: frames past the model's max_frames are dropped (stop_detector.c:26-30): a clip's walk ends there
+    const dsp::FusedClips c{.in = d_signal, .in_kind = in_kind, .n_clips = n_clips, .t = t, .clip_stride = clip_stride, .offsets = offsets,
+                            .max_frames = m.max_frames, .per_cu = p->resident_blocks, .stream = stream};
+    const dsp::StopNetArgs stop{m, d_prob};
+    const int rc = dsp::launch_fused_clips(p, c, nullptr, &stop);
+    return rc < 0 ? rc : 1;
+}
+
 // classify_signal over a batch; in_kind 0 = float samples, 1 / 2 / 3 = int16 mono / stereo channel 0 / stereo average (what
 // main_test.c:198-217 decodes in front of classify_signal, converted in the kernel's load)
-static int classify_signal_batch(dsp_mfcc_plan *plan, dsp_stop_model *m, const void *d_signal, int in_kind, int channels, int stereo_mode, long n_clips,
-                                 int samples_per_clip, long clip_stride, float *d_prob, void *stream)
+static int classify_signal_batch(dsp_mfcc_plan *plan, dsp_stop_model *m, const void *d_signal, int in_kind, long n_clips, int samples_per_clip,
+                                 long clip_stride, float *d_prob, void *stream)
 {
     if (in_kind < 0) return in_kind;
     if (!plan || !m || n_clips < 0 || (n_clips > 0 && (!d_signal || !d_prob))) return capi_fail(DSP_EINVAL, "bad argument");
-    dsp_mfcc_config cfg;
-    dsp_mfcc_plan_config(plan, &cfg);
+    const dsp_mfcc_config &cfg = plan->cfg;
     if (cfg.n_mfcc != m->m.n_coef) return capi_fail(DSP_EINVAL, "plan n_mfcc differs from the model's n_coef");
     // (the fused kernel is the default path: it must refuse what the two-kernel path refuses)
     if (n_clips > 1 && clip_stride < samples_per_clip) return capi_fail(DSP_EINVAL, "clip_stride < samples_per_clip");
-    if (dsp::plan_device(plan) != m->device) return capi_fail(DSP_EINVAL, "plan and stop model live on different devices");
+    if (plan->device != m->device) return capi_fail(DSP_EINVAL, "plan and stop model live on different devices");
     if (n_clips == 0) return DSP_OK;
     const int t = dsp_mfcc_frames_for(&cfg, samples_per_clip, m->m.max_frames);          // stop_detector.c:18-21
-    {   // one kernel from PCM to probability when the plan is the reference's shape: the MFCC matrix is never written
-        const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, clip_stride, t, d_prob, stream, in_kind);
-        if (fused != 0) return fused < 0 ? fused : DSP_OK;
-    }
+    // one kernel from PCM to probability when the plan is the reference's shape
+    if (const int fused = stop_fused(plan, m->m, d_signal, in_kind, n_clips, clip_stride, t, nullptr, d_prob, stream); fused != 0)
+        return fused < 0 ? fused : DSP_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
     DSP_CAPI_HIP(m->d_mfcc.reserve((size_t)n_clips * (t > 0 ? t : 1) * cfg.n_mfcc * sizeof(float)));
     if (t > 0) {
-        const int rc = in_kind == 0 ? dsp_mfcc_clips_device(plan, static_cast<const float *>(d_signal), n_clips, samples_per_clip, clip_stride, m->d_mfcc, m->m.max_frames, stream)
-                                    : dsp_mfcc_clips_pcm16_device(plan, static_cast<const int16_t *>(d_signal), n_clips, samples_per_clip, clip_stride, channels,
-                                                                  stereo_mode, m->d_mfcc, m->m.max_frames, stream);
+        const int rc = dsp::mfcc_clips(plan, d_signal, in_kind, n_clips, samples_per_clip, clip_stride, m->d_mfcc, m->m.max_frames, stream);
         if (rc < 0) return rc;
     }
     DSP_CAPI_HIP(dsp::launch_stop_tail(m->m, m->d_mfcc, n_clips, t, d_prob, (hipStream_t)stream));
@@ -193,13 +200,13 @@ extern "C" {
 int dsp_classify_signal_batch_device(dsp_mfcc_plan *plan, dsp_stop_model *m, const float *d_signal, long n_clips,
                                      int samples_per_clip, long clip_stride, float *d_prob, void *stream)
 {
-    return classify_signal_batch(plan, m, d_signal, 0, 1, 0, n_clips, samples_per_clip, clip_stride, d_prob, stream);
+    return classify_signal_batch(plan, m, d_signal, 0, n_clips, samples_per_clip, clip_stride, d_prob, stream);
 }
 
 int dsp_classify_signal_batch_pcm16_device(dsp_mfcc_plan *plan, dsp_stop_model *m, const int16_t *d_pcm, long n_clips, int samples_per_clip,
                                            long clip_stride, int channels, int stereo_mode, float *d_prob, void *stream)
 {
-    return classify_signal_batch(plan, m, d_pcm, dsp::pcm16_kind(channels, stereo_mode), channels, stereo_mode, n_clips, samples_per_clip, clip_stride, d_prob, stream);
+    return classify_signal_batch(plan, m, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, samples_per_clip, clip_stride, d_prob, stream);
 }
 
 // Ragged batches (main_test.c:254-331 loops over files of different lengths): one launch of the fused kernel, every clip with the
@@ -209,12 +216,10 @@ static int classify_signal_batch_ragged(dsp_mfcc_plan *plan, dsp_stop_model *m, 
 {
     if (in_kind < 0) return in_kind;
     if (!plan || !m || n_clips < 0 || !offsets || (n_clips > 0 && (!d_signal || !d_prob))) return capi_fail(DSP_EINVAL, "bad argument");
-    dsp_mfcc_config cfg;
-    dsp_mfcc_plan_config(plan, &cfg);
-    if (cfg.n_mfcc != m->m.n_coef) return capi_fail(DSP_EINVAL, "plan n_mfcc differs from the model's n_coef");
-    if (dsp::plan_device(plan) != m->device) return capi_fail(DSP_EINVAL, "plan and stop model live on different devices");
+    if (plan->cfg.n_mfcc != m->m.n_coef) return capi_fail(DSP_EINVAL, "plan n_mfcc differs from the model's n_coef");
+    if (plan->device != m->device) return capi_fail(DSP_EINVAL, "plan and stop model live on different devices");
     if (n_clips == 0) return DSP_OK;
-    const int fused = dsp::stop_fused_device(plan, m->m, d_signal, n_clips, 0, 1, d_prob, stream, in_kind, offsets);
+    const int fused = stop_fused(plan, m->m, d_signal, in_kind, n_clips, 0, 1, offsets, d_prob, stream);
     if (fused == 0) return capi_fail(DSP_EINVAL, "ragged batches run on the fused clip -> probability kernel: the reference's MFCC shape (dsp_mfcc_default_config), "
                                                  "a model with at most 4 first-layer units, an 8-byte aligned buffer (4 for mono int16)");
     return fused < 0 ? fused : DSP_OK;
@@ -269,8 +274,7 @@ int dsp_speaker_model_create(const dsp_gmm_params *target, const dsp_gmm_params 
         if (!g || g->k <= 0 || g->k > 64 || g->d <= 0 || g->d > 16 || !g->means || !g->inv_covs || !g->log_consts)
             return capi_fail(DSP_EINVAL, "bad GMM parameters (k <= 64, d <= 16)");
     if (target->k != ubm->k || target->d != ubm->d) return capi_fail(DSP_EINVAL, "target and UBM must have the same shape");
-    int rc = check_device(device);
-    if (rc < 0) return rc;
+    if (const int rc = dsp::check_device(device)) return rc;
     DSP_ON_DEVICE(device);
     const size_t kd = (size_t)target->k * target->d, k = target->k;
     // layout: int32 inv_covs (t, u), int16 log_consts (t, u), int8 means (t, u)
@@ -352,8 +356,7 @@ int dsp_upsample_linear_device(const float *d_in, long n_clips, int old_size, lo
 int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_size)
 {
     if (!in || !out || old_size < 1 || new_size < 2) return capi_fail(DSP_EINVAL, "bad argument (old_size >= 1, new_size >= 2)");
-    int rc = check_device(0);
-    if (rc < 0) return rc;
+    if (const int rc = dsp::check_device(0)) return rc;
     dsp::DeviceBuf<float> d_in, d_out;
     DSP_CAPI_HIP(d_in.alloc((size_t)old_size * 4));
     if (d_out.alloc((size_t)new_size * 4) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
@@ -369,8 +372,7 @@ int dsp_fft_real_forward_host(const float *in_time, long n_frames, int frame_len
     if (!in_time || !out_freq || n_frames < 0 || (n_frames > 1 && in_stride < frame_length)) return capi_fail(DSP_EINVAL, "bad argument");
     if (n_fft < 2 || (n_fft & (n_fft - 1)) || n_fft > 4096 || frame_length < 1 || frame_length > n_fft) return capi_fail(DSP_EINVAL, "n_fft: a power of two <= 4096, 1 <= frame_length <= n_fft");
     if (n_frames == 0) return DSP_OK;
-    int rc = check_device(0);
-    if (rc < 0) return rc;
+    if (const int rc = dsp::check_device(0)) return rc;
     dsp::DeviceBuf<float> d_in, d_out;
     DSP_CAPI_HIP(d_in.alloc((size_t)n_frames * frame_length * 4));
     if (d_out.alloc((size_t)n_frames * n_fft * 8) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
@@ -436,9 +438,7 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
     if (!frame_offsets || !d_mfcc || !d_llr_mean) return capi_fail(DSP_EINVAL, "frame_offsets, d_mfcc and d_llr_mean must not be NULL");
     std::vector<long> wo((size_t)n_recordings + 1);
     if ((rc = scan_plan(cfg, frame_offsets, n_recordings, wo.data(), nullptr, 1)) < 0) return (int)rc;
-    for (long r = 0; r < n_recordings; ++r)
-        if (frame_offsets[r + 1] == frame_offsets[r])
-            return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + " has no MFCC rows (the LLR is a mean over a window's rows)");
+    if ((rc = dsp::refuse_rowless(frame_offsets, n_recordings, " has no MFCC rows (the LLR is a mean over a window's rows)")) < 0) return (int)rc;
     const long rows = frame_offsets[n_recordings] - frame_offsets[0];
     std::lock_guard<std::mutex> lock(m->mu);
     DSP_ON_DEVICE(m->device);
@@ -456,15 +456,14 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
 
 }  // extern "C"
 
-// capi_util.hpp: the front end and the models of a scanner / a stream session
+// mfcc_plan.hpp: the front end and the models of a scanner / a stream session
 int dsp::scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg)
 {
-    dsp_mfcc_config pcfg;
-    dsp_mfcc_plan_config(plan, &pcfg);
+    const dsp_mfcc_config &pcfg = plan->cfg;
     if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
         return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
                                      "no prefilter");
-    const int device = dsp::plan_device(plan);
+    const int device = plan->device;
     if (stop && (pcfg.n_mfcc != stop->m.n_coef || stop->device != device))
         return capi_fail(DSP_EINVAL, "the stop model needs n_coef = the plan's n_mfcc, on the plan's device");
     if (speaker && (pcfg.n_mfcc != speaker->target.d || speaker->device != device))
@@ -474,21 +473,31 @@ int dsp::scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop,
     return DSP_OK;
 }
 
+// every row of every recording of a scanner (mfcc_plan.hpp)
+long dsp::ScannerCore::mfcc(const void *d_signal, int in_kind, long n, const long *offsets, const char *rowless_tail, void *stream)
+{
+    fo.resize((size_t)n + 1);
+    const long rows = dsp_mfcc_ragged_frame_offsets(&plan->cfg, offsets, n, INT_MAX, fo.data());     // no cap: every row of every recording
+    if (rows < 0) return rows;
+    if (const int rc = rowless_tail ? dsp::refuse_rowless(fo.data(), n, rowless_tail) : DSP_OK) return rc;
+    if (rows == 0) return 0;
+    if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
+    DSP_ON_DEVICE(device);
+    if (d_mfcc.reserve((size_t)rows * plan->cfg.n_mfcc * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
+    const int rc = mfcc_clips_ragged(plan, d_signal, in_kind, n, offsets, INT_MAX, d_mfcc, stream);
+    return rc < 0 ? rc : rows;
+}
+
 // A scanner: PCM -> ragged MFCC matrix in its own workspace -> the models' window scans, all on the caller's stream.
 struct dsp_scanner {
-    dsp_mfcc_plan *plan = nullptr;
+    dsp::ScannerCore core;
     dsp_stop_model *stop = nullptr;
     dsp_speaker_model *spk = nullptr;
-    dsp_scan_config cfg{};
-    int device = 0, n_mfcc = 0;
-    dsp::DeviceBuf<float> d_mfcc;
-    std::vector<long> fo;
-    std::mutex mu;
 };
 
-// in_kind 0 float samples, 1 / 2 / 3 int16 (channels / stereo_mode as dsp_mfcc_clips_ragged_pcm16_device), < 0 an error of dsp::pcm16_kind
-static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int channels, int stereo_mode, long n, const long *offsets, float *d_prob,
-                       int64_t *d_llr_mean, int *d_labels, void *stream)
+// in_kind 0 float samples, 1 / 2 / 3 int16, < 0 an error of dsp::pcm16_kind
+static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, long n, const long *offsets, float *d_prob, int64_t *d_llr_mean, int *d_labels,
+                       void *stream)
 {
     if (in_kind < 0) return in_kind;
     if (!s || n < 0) return capi_fail(DSP_EINVAL, "bad argument (scanner, n_recordings >= 0)");
@@ -496,32 +505,16 @@ static int scanner_run(dsp_scanner *s, const void *d_signal, int in_kind, int ch
     if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");
     if (s->stop && !d_prob) return capi_fail(DSP_EINVAL, "the scanner has a stop model: d_prob must not be NULL");
     if (s->spk && !d_llr_mean) return capi_fail(DSP_EINVAL, "the scanner has a speaker model: d_llr_mean must not be NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    dsp_mfcc_config pcfg;
-    dsp_mfcc_plan_config(s->plan, &pcfg);
-    s->fo.resize((size_t)n + 1);
-    const long rows = dsp_mfcc_ragged_frame_offsets(&pcfg, offsets, n, INT_MAX, s->fo.data());     // no cap: every row of every recording
+    std::lock_guard<std::mutex> lock(s->core.mu);
+    const long rows = s->core.mfcc(d_signal, in_kind, n, offsets,
+                                   s->spk ? " is shorter than one frame: the speaker LLR is a mean over a window's rows" : nullptr, stream);
     if (rows < 0) return (int)rows;
-    if (s->spk)
-        for (long r = 0; r < n; ++r)
-            if (s->fo[(size_t)r + 1] == s->fo[(size_t)r])
-                return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + " is shorter than one frame: the speaker LLR is a mean over a window's rows");
-    if (rows > 0) {
-        if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
-        DSP_ON_DEVICE(s->device);
-        if (s->d_mfcc.reserve((size_t)rows * s->n_mfcc * sizeof(float)) != hipSuccess)
-            return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
-        const int rc = in_kind == 0 ? dsp_mfcc_clips_ragged_device(s->plan, static_cast<const float *>(d_signal), n, offsets, INT_MAX, s->d_mfcc, stream)
-                                    : dsp_mfcc_clips_ragged_pcm16_device(s->plan, static_cast<const int16_t *>(d_signal), n, offsets, channels, stereo_mode,
-                                                                         INT_MAX, s->d_mfcc, stream);
-        if (rc < 0) return rc;
-    }
     if (s->stop) {
-        const int rc = dsp_stop_scan_device(s->stop, s->d_mfcc, n, s->fo.data(), &s->cfg, d_prob, stream);
+        const int rc = dsp_stop_scan_device(s->stop, s->core.d_mfcc, n, s->core.fo.data(), &s->core.cfg, d_prob, stream);
         if (rc < 0) return rc;
     }
     if (s->spk) {
-        const int rc = dsp_speaker_scan_device(s->spk, s->d_mfcc, n, s->fo.data(), &s->cfg, d_llr_mean, d_labels, stream);
+        const int rc = dsp_speaker_scan_device(s->spk, s->core.d_mfcc, n, s->core.fo.data(), &s->core.cfg, d_llr_mean, d_labels, stream);
         if (rc < 0) return rc;
     }
     return DSP_OK;
@@ -537,15 +530,12 @@ int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_mo
     if (!stop && !speaker) return capi_fail(DSP_EINVAL, "a scanner needs a stop model, a speaker model or both");
     if (const int rc = scan_args(cfg, 0)) return rc;
     if (const int rc = dsp::scan_front_check(plan, stop, speaker, cfg)) return rc;
-    dsp_mfcc_config pcfg;
-    dsp_mfcc_plan_config(plan, &pcfg);
     auto *s = new dsp_scanner;
-    s->plan = plan;
+    s->core.plan = plan;
+    s->core.device = plan->device;
+    s->core.cfg = *cfg;
     s->stop = stop;
     s->spk = speaker;
-    s->cfg = *cfg;
-    s->device = dsp::plan_device(plan);
-    s->n_mfcc = pcfg.n_mfcc;
     *out = s;
     return DSP_OK;
 }
@@ -553,20 +543,20 @@ int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_mo
 void dsp_scanner_destroy(dsp_scanner *s)
 {
     if (!s) return;
-    dsp::DeviceScope dsp_device_scope_(s->device);
+    dsp::DeviceScope dsp_device_scope_(s->core.device);
     delete s;
 }
 
 int dsp_scanner_run_device(dsp_scanner *s, const float *d_signal, long n_recordings, const long *offsets, float *d_prob, int64_t *d_llr_mean,
                            int *d_labels, void *stream)
 {
-    return scanner_run(s, d_signal, 0, 1, 0, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
+    return scanner_run(s, d_signal, 0, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
 }
 
 int dsp_scanner_run_pcm16_device(dsp_scanner *s, const int16_t *d_pcm, long n_recordings, const long *offsets, int channels, int stereo_mode,
                                  float *d_prob, int64_t *d_llr_mean, int *d_labels, void *stream)
 {
-    return scanner_run(s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), channels, stereo_mode, n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
+    return scanner_run(s, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_recordings, offsets, d_prob, d_llr_mean, d_labels, stream);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "capi_util.hpp"
+#include "mfcc_plan.hpp"
 #include "stream_kernels.hpp"
 
 using dsp::capi_fail;
@@ -92,7 +92,7 @@ struct dsp_stream_session {
     dsp_scan_config scfg{};
     StreamRule rule;
     bool scans = false;                   // a model was given: windows exist
-    int device = 0, n_mfcc = 0, in_kind = 0;
+    int device = 0, in_kind = 0;      // device: the plan's, kept for the session's destruction
     long n_streams = 0;
     long es = 4;                          // bytes per sample frame: 4 float, 2 mono int16, 4 stereo int16
     long carry_stride = 0, row_stride = 0;      // bytes per stream in d_carry / d_rowcarry (multiples of 16)
@@ -137,12 +137,11 @@ int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_spe
         return capi_fail(DSP_EINVAL, "float samples are mono: channels must be 1");
     }
     if (const int rc = dsp::scan_front_check(plan, stop, speaker, scan)) return rc;
-    dsp_mfcc_config pcfg;
-    dsp_mfcc_plan_config(plan, &pcfg);
+    const dsp_mfcc_config &pcfg = plan->cfg;
     StreamRule rule;
     if (const int rc = stream_rule(&pcfg, scans ? scan : nullptr, rule)) return rc;
-    const long none = 0;
-    if (const int rc = dsp::mfcc_spans_device(plan, nullptr, kind, 0, &none, &none, nullptr, nullptr); rc < 0) return rc;      // the plan's kernel takes this input
+    if (const int rc = dsp::pcm16_check(plan, kind, true)) return rc;      // the plan's kernel takes this input, as a ragged batch
+    if (const int rc = dsp::ragged_plan_check(plan)) return rc;
     auto s = std::make_unique<dsp_stream_session>();
     s->plan = plan;
     s->stop = stop;
@@ -150,8 +149,7 @@ int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_spe
     s->scans = scans;
     if (scans) s->scfg = *scan;
     s->rule = rule;
-    s->device = dsp::plan_device(plan);
-    s->n_mfcc = pcfg.n_mfcc;
+    s->device = plan->device;
     s->in_kind = kind;
     s->n_streams = n_streams;
     s->es = kind == 1 ? 2 : 4;
@@ -159,7 +157,7 @@ int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_spe
     s->row_stride = scans ? round_up((rule.wf - 1) * (long)pcfg.n_mfcc * 4, 16) : 0;
     s->received.assign((size_t)n_streams, 0);
     for (std::vector<long> *v : {&s->ro, &s->wo, &s->fo, &s->starts, &s->lengths}) v->assign((size_t)n_streams + 1, 0);
-    DSP_ON_DEVICE(s->device);
+    DSP_ON_DEVICE(plan->device);
     if (n_streams > 0 && s->carry_stride > 0 && s->d_carry.alloc((size_t)n_streams * s->carry_stride) != hipSuccess)
         return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
     if (n_streams > 0 && s->row_stride > 0 && s->d_rowcarry.alloc((size_t)n_streams * s->row_stride) != hipSuccess)
@@ -237,7 +235,7 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
     }
     if (total_win > 0 && s->stop && !d_prob) return capi_fail(DSP_EINVAL, "the session has a stop model: d_prob must not be NULL");
     if (total_win > 0 && s->spk && !d_llr_mean) return capi_fail(DSP_EINVAL, "the session has a speaker model: d_llr_mean must not be NULL");
-    const long es = s->es, align = 16 / es, rb = (long)s->n_mfcc * 4;
+    const long es = s->es, align = 16 / es, rb = (long)s->plan->cfg.n_mfcc * 4;
     for (auto &v : s->runs) v.clear();
     long pos = 0, n_spans = 0, n_scan = 0, scan_win = 0;
     fo[0] = 0;
@@ -272,7 +270,7 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
     size_t n_runs = 0;
     for (const auto &v : s->runs) n_runs += v.size();
     if (n_runs > 0) {
-        DSP_ON_DEVICE(s->device);
+        DSP_ON_DEVICE(s->plan->device);
         hipStream_t st = (hipStream_t)stream;
         if (s->d_stage.reserve((size_t)(pos * es) + 64) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (stream staging)");
         if (!d_mfcc && s->d_new.reserve((size_t)(total_rows * rb) + 16) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (new rows)");
@@ -296,7 +294,9 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
         const int g = es == 2 ? 2 : 4;
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[0], (long)s->runs[0].size(), s->d_carry, d_chunks, s->d_stage, g, st));
         if (n_spans > 0) {
-            const int rc = dsp::mfcc_spans_device(s->plan, s->d_stage, s->in_kind, n_spans, s->starts.data(), s->lengths.data(), rows_out, stream);
+            // the ragged MFCC path (no frame cap) over spans of the staging buffer: span c = sample frames [starts[c], starts[c] + lengths[c])
+            int rc = dsp::pcm16_check(s->plan, s->in_kind, true);      // (a kernel switched since the session was created)
+            if (rc == DSP_OK) rc = dsp::mfcc_clips_ragged(s->plan, s->d_stage, s->in_kind, n_spans, s->starts.data(), INT_MAX, rows_out, stream, s->lengths.data());
             if (rc < 0) { s->broken = true; return rc; }
         }
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[1], (long)s->runs[1].size(), s->d_stage, d_chunks, s->d_carry, g, st));

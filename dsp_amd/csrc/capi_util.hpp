@@ -1,5 +1,6 @@
-// capi_util.hpp -- error reporting, device scopes, the owner of device buffers and the ragged-span ring shared by the translation
-// units of the C ABI (capi.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the classifiers' front end classify_front.hpp).
+// capi_util.hpp -- error reporting, device scopes, the owner of device buffers, the ragged-span ring and the scans' host planner shared
+// by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
+// classifiers' front end classify_front.hpp).  Nothing here knows a plan: what reads one is mfcc_plan.hpp.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -14,31 +15,8 @@
 
 #include "../../include/dsp_amd.h"
 
-struct dsp_mfcc_plan;
-struct dsp_stop_model;
-struct dsp_speaker_model;
-namespace dsp {
-// capi_consumers.cpp (owner of the models): what dsp_scanner_create and dsp_stream_session_create ask of a plan and of the models they
-// borrow -- rows that depend on their own samples only, n_coef / d = the plan's n_mfcc on the plan's device, a stop window that fits the
-// scan kernel's LDS.  stop / speaker may be NULL (cfg is read only when one is given).  DSP_OK or DSP_EINVAL.
-int scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg);
-}
 namespace dsp {
 int capi_fail(int code, const std::string &msg);   // sets dsp_last_error() for this thread, returns code
-struct StopModelDev;
-// capi.cpp (owner of dsp_mfcc_plan): classify_signal in one kernel -- clip -> MFCC -> stop-word net, the MFCC matrix never written.
-// Returns 1 when the fused kernel was enqueued, 0 when this plan / model shape has no fused form (the caller runs the two-kernel
-// path), < 0 on error.  t = frames per clip (already capped at the model's max_frames).
-// in_kind: 0 float samples, 1 / 2 / 3 int16 mono / stereo channel 0 / stereo average
-int stop_fused_device(dsp_mfcc_plan *plan, const StopModelDev &m, const void *d_signal, long n_clips, long clip_stride, int t, float *d_prob,
-                      void *stream, int in_kind = 0, const long *offsets = nullptr);
-// offsets != nullptr: a ragged batch (clip c = samples [offsets[c], offsets[c + 1]) per channel; clip_stride and t unused)
-int plan_device(const dsp_mfcc_plan *plan);          // the GPU a plan lives on
-// capi.cpp: the ragged MFCC path of dsp_mfcc_clips_ragged_device (no frame cap) over spans anywhere in d_in: span c = sample frames
-// [starts[c], starts[c] + lengths[c]), its rows behind those of span c - 1 in d_out.  in_kind as above.  n_spans = 0 checks the plan
-// and launches nothing.  Returns the rows of the longest span or < 0.
-int mfcc_spans_device(dsp_mfcc_plan *plan, const void *d_in, int in_kind, long n_spans, const long *starts, const long *lengths, float *d_out,
-                      void *stream);
 }
 
 // Ragged batches: the clips' spans (clip_span.hpp ClipSpan: start, samples, frames, caller's index -- 32 bytes per clip) travel to the GPU through a
@@ -127,6 +105,15 @@ struct SpanRing {
     }
 };
 
+// a device index the HIP runtime knows, or why not
+inline int check_device(int device)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return capi_fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
+    if (device < 0 || device >= n) return capi_fail(DSP_EINVAL, "device index out of range");
+    return DSP_OK;
+}
+
 // clip c of a ragged batch is samples [offsets[c], offsets[c + 1]) per channel: its length, or DSP_EINVAL naming the clip
 inline long ragged_clip_length(const long *offsets, long c)
 {
@@ -188,7 +175,7 @@ template <class T> hipError_t upload(DeviceBuf<T> &buf, const T &host)
 }
 }
 
-// ---- window scans of long recordings (capi_consumers.cpp: stop / speaker; capi.cpp: SVM) ----------------------------------------------
+// ---- window scans of long recordings (capi_consumers.cpp: stop / speaker; capi_scrubjay.cpp: SVM) ----------------------------------------------
 // Recording r is rows [frame_offsets[r], frame_offsets[r + 1]) of a ragged MFCC matrix, R rows: R >= window_frames gives
 // 1 + (R - window_frames) / hop_frames windows, fewer rows one window of all of them.
 namespace dsp {
@@ -220,6 +207,14 @@ inline long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, lon
         if (to) to[r + 1] = to[r] + (w + tw - 1) / tw;
     }
     return wo[n];
+}
+
+// a scan that pools or averages a window's rows: DSP_EINVAL "recording r<tail>" for the first recording without rows
+inline int refuse_rowless(const long *frame_offsets, long n, const char *tail)
+{
+    for (long r = 0; r < n; ++r)
+        if (frame_offsets[r + 1] == frame_offsets[r]) return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + tail);
+    return DSP_OK;
 }
 
 // per-recording arrays for the kernels, rows relative to frame_offsets[0]: fo, wo[, to][, extra], n + 1 longs each, into a leased ring
