@@ -115,6 +115,9 @@ SYMBOLS = [
     "dsp_stream_push_plan", "dsp_stream_session_create", "dsp_stream_session_destroy", "dsp_stream_session_reset",
     "dsp_stream_session_counts", "dsp_stream_push_device",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
+    "dsp_resample_ratio", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
+    "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device", "dsp_resample_clips_pcm16_device",
+    "dsp_resample_host",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -249,6 +252,16 @@ def load() -> C.CDLL:
     L.dsp_stream_push_device.argtypes = [vp, vp, lp, vp, vp, vp, vp, lp, lp, vp]; L.dsp_stream_push_device.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
+    L.dsp_resample_ratio.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]; L.dsp_resample_ratio.restype = ip
+    L.dsp_resample_taps.argtypes = [ip, ip, C.POINTER(C.c_double), ip]; L.dsp_resample_taps.restype = ip
+    L.dsp_resample_offsets.argtypes = [ip, ip, lp, C.c_long, lp]; L.dsp_resample_offsets.restype = C.c_long
+    L.dsp_resampler_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_resampler_create.restype = ip
+    L.dsp_resampler_destroy.argtypes = [vp]; L.dsp_resampler_destroy.restype = None
+    L.dsp_resample_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_resample_ragged_device.restype = ip
+    L.dsp_resample_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_resample_ragged_pcm16_device.restype = ip
+    L.dsp_resample_clips_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, C.c_long, vp]; L.dsp_resample_clips_device.restype = ip
+    L.dsp_resample_clips_pcm16_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, C.c_long, vp]; L.dsp_resample_clips_pcm16_device.restype = ip
+    L.dsp_resample_host.argtypes = [ip, ip, vp, C.c_long, vp]; L.dsp_resample_host.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

@@ -1,0 +1,134 @@
+"""Recordings at another rate: the polyphase FIR resampler of include/dsp_amd.h (dsp_resample_*) --
+scipy.signal.resample_poly's defaults as one HIP launch over a ragged or uniform batch, float or int16 in HBM."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _lib
+
+
+def _rates(rate_in, rate_out):
+    if isinstance(rate_in, bool) or isinstance(rate_out, bool) or not isinstance(rate_in, (int, np.integer)) or not isinstance(rate_out, (int, np.integer)):
+        raise ValueError("rate_in and rate_out must be integers")
+    if rate_in < 1 or rate_out < 1 or rate_in > 2**31 - 1 or rate_out > 2**31 - 1:
+        raise ValueError("rate_in and rate_out must be >= 1 (and fit an int)")
+    return int(rate_in), int(rate_out)
+
+
+def resample_ratio(rate_in: int, rate_out: int):
+    """-> (up, down, half): the reduced ratio and the filter's half length (2 half + 1 taps).  DspError: up or down above 1024."""
+    rate_in, rate_out = _rates(rate_in, rate_out)
+    up, down, half = C.c_int(), C.c_int(), C.c_int()
+    _lib.check(_lib.load().dsp_resample_ratio(rate_in, rate_out, C.byref(up), C.byref(down), C.byref(half)), "dsp_resample_ratio")
+    return up.value, down.value, half.value
+
+
+def resample_taps(rate_in: int, rate_out: int) -> np.ndarray:
+    """The float64 taps h[2 half + 1] (= scipy.signal.firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up)."""
+    rate_in, rate_out = _rates(rate_in, rate_out)
+    L = _lib.load()
+    n = _lib.check(L.dsp_resample_taps(rate_in, rate_out, None, 0), "dsp_resample_taps")
+    h = np.empty(n, np.float64)
+    _lib.check(L.dsp_resample_taps(rate_in, rate_out, h.ctypes.data_as(C.POINTER(C.c_double)), n), "dsp_resample_taps")
+    return h
+
+
+def resample_offsets(rate_in: int, rate_out: int, offsets) -> np.ndarray:
+    """offsets[n + 1] of a ragged batch at rate_in -> int64 [n + 1]: where each resampled recording starts (prefix sums of
+    ceil(len up / down) from 0).  `offsets` as lib.c_offsets takes them, or the pair it returned."""
+    rate_in, rate_out = _rates(rate_in, rate_out)
+    off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
+    out = (C.c_long * (n + 1))()
+    _lib.check(_lib.load().dsp_resample_offsets(rate_in, rate_out, off, n, out), "dsp_resample_offsets")
+    return np.frombuffer(out, dtype=np.int64).copy()
+
+
+class Resampler:
+    """dsp_resampler: the taps of rate_in -> rate_out on one GPU."""
+
+    def __init__(self, rate_in: int, rate_out: int, device: int = 0):
+        self.rate_in, self.rate_out = _rates(rate_in, rate_out)
+        self.up, self.down, self.half = resample_ratio(rate_in, rate_out)
+        self._L = _lib.load()
+        self.device = int(device)
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_resampler_create(self.device, self.rate_in, self.rate_out, C.byref(h)), "dsp_resampler_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def out_samples(self, n: int) -> int:
+        """ceil(n up / down): the output length of a recording of n samples."""
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        return -((-int(n) * self.up) // self.down)
+
+    def ragged(self, signal, offsets, stereo_mode: int = 0, out=None):
+        """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (interleaved stereo; stereo_mode 0 = channel 0,
+        1 = channel average), recording c = samples [offsets[c], offsets[c + 1]) per channel.  Returns (out, out_offsets): cuda float32
+        [out_offsets[-1]] with recording c at [out_offsets[c], out_offsets[c + 1]) (numpy int64) -- what every *_ragged entry, Scanner and
+        StreamSession-free per-clip call takes as (signal, offsets).  Async on torch's current stream."""
+        import torch
+        if stereo_mode not in (0, 1):
+            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (channel average)")
+        off, n, channels, ptr = _lib.ragged_signal(signal, offsets, torch.float32)
+        oo = resample_offsets(self.rate_in, self.rate_out, (off, n))
+        total = int(oo[-1])
+        if out is None:
+            out = torch.empty((total,), dtype=torch.float32, device=signal.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= total):
+            raise ValueError(f"out must be a contiguous float32 CUDA tensor of at least {total} samples")
+        if total and channels:
+            _lib.check(self._L.dsp_resample_ragged_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), out.data_ptr(), self._stream()),
+                       "dsp_resample_ragged_pcm16_device")
+        elif total:
+            _lib.check(self._L.dsp_resample_ragged_device(self._h, ptr, n, off, out.data_ptr(), self._stream()), "dsp_resample_ragged_device")
+        return out, oo
+
+    def clips(self, clips, stereo_mode: int = 0, out=None):
+        """clips: cuda float32 [n][samples], int16 [n][samples] or interleaved int16 [n][samples][2] -> cuda float32 [n][n_out],
+        row c bit for bit what ragged() gives for that clip."""
+        import torch
+        if stereo_mode not in (0, 1):
+            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (channel average)")
+        if not (isinstance(clips, torch.Tensor) and clips.is_cuda and clips.dtype in (torch.float32, torch.int16)):
+            raise ValueError("clips must be a float32 or int16 CUDA tensor")
+        if clips.dim() >= 2 and clips.numel() == 0:             # no clips, or clips without samples: the strides of an empty tensor say nothing
+            if not (clips.dim() == 2 or (clips.dim() == 3 and clips.dtype == torch.int16 and clips.shape[2] == 2)):
+                raise ValueError("clips must be [n][samples], or interleaved int16 [n][samples][2]")
+            channels, stride = 0, int(clips.shape[1])
+        elif clips.dtype == torch.int16:
+            channels, stride = _lib.pcm_device(clips)
+        else:
+            channels, stride = 0, _lib.clips_device(clips, torch.float32).stride(0)
+        n, s = int(clips.shape[0]), int(clips.shape[1])
+        n_out = self.out_samples(s)
+        if out is None:
+            out = torch.empty((n, n_out), dtype=torch.float32, device=clips.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape == (n, n_out) and (out.numel() == 0 or out.stride(1) == 1)):
+            raise ValueError(f"out must be a float32 CUDA tensor [{n}][{n_out}] with unit inner stride")
+        if n and n_out:
+            if channels:
+                got = _lib.check(self._L.dsp_resample_clips_pcm16_device(self._h, clips.data_ptr(), n, s, stride, channels, int(stereo_mode), out.data_ptr(),
+                                                                         out.stride(0), self._stream()), "dsp_resample_clips_pcm16_device")
+            else:
+                got = _lib.check(self._L.dsp_resample_clips_device(self._h, clips.data_ptr(), n, s, stride, out.data_ptr(), out.stride(0), self._stream()),
+                                 "dsp_resample_clips_device")
+            if got != n_out:
+                raise _lib.DspError(f"the library resampled {s} samples to {got}, the wrapper expected {n_out}")
+        return out

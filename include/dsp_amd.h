@@ -626,6 +626,45 @@ int dsp_upsample_linear_device(const float *d_in, long n_clips, int old_size, lo
                                int new_size, long out_stride, void *stream);
 int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_size);
 
+/* --- recordings at another rate: rational-ratio polyphase FIR resampling ---
+ * What scipy.signal.resample_poly(x, up, down) computes at its defaults (Kaiser beta = 5 window, zero padding, zero phase), so that audio
+ * captured at 9 / 10 / 44.1 / 48 / 96 kHz reaches the 16 kHz the models run at without a host pass per file.  With g = gcd(rate_in,
+ * rate_out): up = rate_out / g, down = rate_in / g, m = max(up, down), half = 10 m, and 2 half + 1 taps
+ *   h[n] = up v[n] / sum_j v[j],   v[n] = sinc((n - half) / m) / m * I0(5 sqrt(1 - ((n - half) / half)^2)) / I0(5),   sinc(t) = sin(pi t) / (pi t)
+ * (= firwin(2 half + 1, 1 / m, window=("kaiser", 5.0)) * up).  A recording x[0..n) gives ceil(n up / down) outputs
+ *   y[k] = sum_i x[i] h[k down + half - i up]      over 0 <= i < n, 0 <= k down + half - i up <= 2 half.
+ * The taps are computed in float64 on the host and rounded once to float32; products and sums are float32 (FMA), in ascending i -- an
+ * order that depends on the recording and k only, never on the batch, the launch or the entry point.  up = down = 1 copies the input bit
+ * for bit; n = 0 gives no output.  After reduction up and down must each be <= 1024 (DSP_EINVAL otherwise); a recording holds at most
+ * INT_MAX samples.  Not covered: a filter-history carry for live streams (dsp_stream_push_device takes the models' rate).
+ *
+ * Host only, no GPU: dsp_resample_ratio (any pointer may be NULL); dsp_resample_taps (returns 2 half + 1; h may be NULL, else n >= that);
+ * dsp_resample_offsets: offsets[n + 1] as dsp_mfcc_clips_ragged_device takes them -> out_offsets[n + 1], the prefix sums of the output
+ * lengths from 0; returns their total.  Each returns a negative DSP_E* code on error.
+ *
+ * A dsp_resampler holds the taps of one ratio on one GPU.  dsp_resample_ragged_device: recording c = samples [offsets[c], offsets[c + 1])
+ * per channel of d_in (`offsets` a HOST array, read before the call returns) -> d_out + out_offsets[c], back to back: d_out and those
+ * offsets go unchanged into every *_ragged_* entry, scanner and per-clip entry above.  The pcm16 forms decode int16 in the load (mono
+ * s / 32768; interleaved stereo: DSP_STEREO_CHANNEL0 / DSP_STEREO_AVERAGE as dsp_mfcc_clips_pcm16_device) and give, bit for bit, what
+ * the float form gives on the decoded samples.  dsp_resample_clips_*: equal clips `stride` samples (per channel) apart ->
+ * d_out[c * out_stride + k]; returns the output length of a clip.  Everything is enqueued on `stream`, no host synchronisation; ONE
+ * stream at a time per resampler.  Zero recordings (or none with a sample): DSP_OK, no launch.
+ * dsp_resample_host: one recording from host memory on GPU 0 (copy in, run, copy out); out holds ceil(n up / down) floats.            */
+int dsp_resample_ratio(int rate_in, int rate_out, int *up, int *down, int *half_len);
+int dsp_resample_taps(int rate_in, int rate_out, double *h, int n);
+long dsp_resample_offsets(int rate_in, int rate_out, const long *offsets, long n, long *out_offsets);
+typedef struct dsp_resampler dsp_resampler;
+int dsp_resampler_create(int device, int rate_in, int rate_out, dsp_resampler **out);
+void dsp_resampler_destroy(dsp_resampler *r);
+int dsp_resample_ragged_device(dsp_resampler *r, const float *d_in, long n, const long *offsets, float *d_out, void *stream);
+int dsp_resample_ragged_pcm16_device(dsp_resampler *r, const int16_t *d_pcm, long n, const long *offsets, int channels, int stereo_mode,
+                                     float *d_out, void *stream);
+int dsp_resample_clips_device(dsp_resampler *r, const float *d_in, long n_clips, int samples, long stride, float *d_out, long out_stride,
+                              void *stream);
+int dsp_resample_clips_pcm16_device(dsp_resampler *r, const int16_t *d_pcm, long n_clips, int samples, long stride, int channels,
+                                    int stereo_mode, float *d_out, long out_stride, void *stream);
+int dsp_resample_host(int rate_in, int rate_out, const float *in, long n, float *out);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
