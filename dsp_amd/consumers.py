@@ -6,6 +6,8 @@
   upsample_linear   upsampleLinear                             sync/particle/main.cpp:62-77
   Scanner        both per sliding window of long recordings     sync/sync.cpp:188-213 (one 1 s buffer at a time)
   StreamSession  the same for audio that is still arriving       sync/sync.cpp:188-213 (the capture loop itself, many feeds)
+  Cmvn           sliding_cmvn                                   2fa/audio/speaker/gmm_utils.py:14-25
+  SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
 
 Trained parameters are passed in as arrays (the reference compiles them in from model_params.h / gmm_params.inc).
 Tensors are HBM-resident torch tensors; Python only moves pointers.
@@ -427,6 +429,115 @@ class StreamSession:
         return ro2, rows, wo2, prob, mean, label
 
 
+class Cmvn:
+    """dsp_cmvn: sliding cepstral mean and variance normalisation of a ragged MFCC matrix -- row t of a recording by the mean and the
+    population standard deviation of rows [t - window // 2, t + window // 2) of its own recording (the UBM's feature space)."""
+
+    def __init__(self, d: int, window: int = 300, device: int = 0):
+        d, window = int(d), int(window)
+        if not 1 <= d <= 16:
+            raise ValueError("d must be 1 .. 16")
+        if window < 2:
+            raise ValueError("window must be >= 2")
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_cmvn_create(int(device), d, window, C.byref(h)), "dsp_cmvn_create")
+        self._h, self.d, self.window, self.device = h, d, window, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_cmvn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def apply(self, mfcc, frame_offsets):
+        """mfcc: cuda float32 [F][d], recording r = rows [frame_offsets[r], frame_offsets[r + 1]) -> a new cuda float32 [F][d]; rows of
+        no recording are zeros."""
+        import torch
+        fo = _frame_offsets(frame_offsets)
+        mfcc = _scan_mfcc(mfcc, fo, self.d)
+        out = torch.zeros_like(mfcc)
+        if fo.size > 1 and mfcc.numel():
+            _lib.check(self._L.dsp_cmvn_ragged_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_LP), out.data_ptr(), _stream(mfcc)),
+                       "dsp_cmvn_ragged_device")
+        return out
+
+
+class SpeakerEnroller:
+    """dsp_speaker_enroller: MAP adaptation of a float UBM's means to each speaker of a ragged matrix of (CMVN'd) feature rows."""
+
+    MODES = {"relevance": _lib.MAP_RELEVANCE, "fixed_alpha": _lib.MAP_FIXED_ALPHA}
+
+    def __init__(self, ubm_float: dict, device: int = 0):
+        """ubm_float: log_consts [k], means [k][d], inv_covs [k][d] -- the DOUBLE_GMM arrays of gmm_params.inc (log_consts = log w -
+        0.5 sum log(2 pi var), inv_covs = 1 / var)."""
+        keep = {key: np.ascontiguousarray(ubm_float[key], np.float64) for key in ("log_consts", "means", "inv_covs")}
+        if keep["means"].ndim != 2 or keep["inv_covs"].shape != keep["means"].shape or keep["log_consts"].shape != keep["means"].shape[:1]:
+            raise ValueError("ubm_float: means and inv_covs must be [k][d], log_consts [k]")
+        k, d = keep["means"].shape
+        if not (1 <= k <= 64 and 1 <= d <= 16):
+            raise ValueError("ubm_float: k must be 1 .. 64 and d 1 .. 16")
+        p = _lib.GmmFloatParams()
+        p.k, p.d = k, d
+        p.log_consts, p.means, p.inv_covs = (keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_speaker_enroller_create(C.byref(p), int(device), C.byref(h)), "dsp_speaker_enroller_create")
+        self._h, self.k, self.d, self.device = h, k, d, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_speaker_enroller_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def enroll(self, feats, frame_offsets, mode: str = "relevance", relevance_factor: float = 16.0, fixed_alpha: float = 0.7):
+        """feats: cuda float32 [F][d], speaker s = rows [frame_offsets[s], frame_offsets[s + 1]), every speaker >= 1 row -> a dict of cuda
+        tensors: means float32 [S][k][d], means_q6 int8 [S][k][d], counts float32 [S][k], ll_mean float32 [S], saturated int32 [S]."""
+        import torch
+        if mode not in self.MODES:
+            raise ValueError("mode must be 'relevance' or 'fixed_alpha'")
+        relevance_factor, fixed_alpha = float(relevance_factor), float(fixed_alpha)
+        if mode == "relevance" and not (0.0 < relevance_factor < float("inf")):
+            raise ValueError("relevance_factor must be > 0 and finite")
+        if mode == "fixed_alpha" and not (0.0 <= fixed_alpha <= 1.0):
+            raise ValueError("fixed_alpha must lie in [0, 1]")
+        fo = _frame_offsets(frame_offsets)
+        feats = _scan_mfcc(feats, fo, self.d)
+        if (np.diff(fo) == 0).any():
+            raise ValueError(f"speaker {int(np.flatnonzero(np.diff(fo) == 0)[0])} has no rows")
+        n, dev = fo.size - 1, feats.device
+        out = {"means": torch.empty((n, self.k, self.d), dtype=torch.float32, device=dev),
+               "means_q6": torch.empty((n, self.k, self.d), dtype=torch.int8, device=dev),
+               "counts": torch.empty((n, self.k), dtype=torch.float32, device=dev),
+               "ll_mean": torch.empty(n, dtype=torch.float32, device=dev),
+               "saturated": torch.empty(n, dtype=torch.int32, device=dev)}
+        cfg = _lib.EnrollConfig(self.MODES[mode], relevance_factor, fixed_alpha)
+        _lib.check(self._L.dsp_speaker_enroll_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_LP), C.byref(cfg),
+                                                            *[out[key].data_ptr() for key in ("means", "means_q6", "counts", "ll_mean", "saturated")],
+                                                            _stream(feats)), "dsp_speaker_enroll_ragged_device")
+        return out
+
+    @staticmethod
+    def speaker_model(means_q6, ubm_int: dict, device: int = 0) -> SpeakerModel:
+        """The SpeakerModel of one enrolled speaker: means_q6 int8 [k][d] (a row of enroll()'s means_q6, tensor or array) as the target's
+        means, the UBM's own inv_covs (Q11) and log_consts (Q8) as the target's, against ubm_int (means, inv_covs, log_consts)."""
+        q6 = means_q6.cpu().numpy() if hasattr(means_q6, "cpu") else np.asarray(means_q6)
+        if q6.dtype != np.int8 or q6.shape != np.shape(ubm_int["means"]):
+            raise ValueError("means_q6 must be int8 [k][d], the shape of the UBM's means")
+        return SpeakerModel({"means": q6, "inv_covs": ubm_int["inv_covs"], "log_consts": ubm_int["log_consts"]}, ubm_int, device)
+
+
 def upsample_linear(x, new_size: int):
     """x: cuda float32 [n_clips][old] (or [old]) -> [n_clips][new_size]; numpy input goes through the host entry point."""
     L = _lib.load()
@@ -446,4 +557,4 @@ def upsample_linear(x, new_size: int):
     return out[0] if squeeze else out
 
 
-__all__ = ["StopModel", "SpeakerModel", "Scanner", "StreamSession", "stream_push_plan", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]
+__all__ = ["StopModel", "SpeakerModel", "Scanner", "StreamSession", "Cmvn", "SpeakerEnroller", "stream_push_plan", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]

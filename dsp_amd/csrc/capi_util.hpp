@@ -209,11 +209,21 @@ inline long scan_plan(const dsp_scan_config *cfg, const long *frame_offsets, lon
     return wo[n];
 }
 
-// a scan that pools or averages a window's rows: DSP_EINVAL "recording r<tail>" for the first recording without rows
-inline int refuse_rowless(const long *frame_offsets, long n, const char *tail)
+// a scan that pools or averages a window's rows: DSP_EINVAL "recording r<tail>" for the first recording (or `what`) without rows
+inline int refuse_rowless(const long *frame_offsets, long n, const char *tail, const char *what = "recording")
 {
     for (long r = 0; r < n; ++r)
-        if (frame_offsets[r + 1] == frame_offsets[r]) return capi_fail(DSP_EINVAL, "recording " + std::to_string(r) + tail);
+        if (frame_offsets[r + 1] == frame_offsets[r]) return capi_fail(DSP_EINVAL, what + (" " + std::to_string(r)) + tail);
+    return DSP_OK;
+}
+
+// frame_offsets[n + 1] of a ragged matrix outside a scan (n >= 1): non-negative and non-decreasing, or DSP_EINVAL naming the first
+// recording (or `what`) at which they decrease
+inline int check_frame_offsets(const long *frame_offsets, long n, const char *what = "recording")
+{
+    if (frame_offsets[0] < 0) return capi_fail(DSP_EINVAL, "frame_offsets must be non-negative");
+    for (long r = 0; r < n; ++r)
+        if (frame_offsets[r + 1] < frame_offsets[r]) return capi_fail(DSP_EINVAL, std::string("frame_offsets decrease at ") + what + " " + std::to_string(r));
     return DSP_OK;
 }
 

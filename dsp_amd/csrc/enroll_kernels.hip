@@ -1,0 +1,298 @@
+// enroll_kernels.hip -- sliding CMVN of a ragged MFCC matrix and MAP enrolment of speakers against a float UBM.
+//
+// CMVN (sliding_cmvn of the reference's speaker/gmm_utils.py): row t of a recording of n rows is normalised by the mean and the population
+// standard deviation of rows [max(0, t - half), min(n, t + half)), half = window / 2, per coefficient, in the two-pass form:
+//   mu = sum x / c,  sigma = sqrt(sum (x - mu)^2 / c),  y = (x[t] - mu) / (sigma + 1e-8)
+// A block takes kCmvnTileRows consecutive rows of one recording and stages them and `half` rows each side in LDS; a lane takes one
+// (row, coefficient) and runs both passes from LDS in ascending row order, float32.  Nothing a row reads lies outside its recording.
+//
+// Enrolment (map_adapt_gmm of the reference's adapt_ubm.py scripts, means only): per row the posteriors of the k components under the
+// UBM, per speaker N_k = sum_t p_k and F_k = sum_t p_k x, then mean_k = alpha_k F_k / N'_k + (1 - alpha_k) mu_k.
+//   statistics  one block per chunk of kEnrollChunkRows rows of one speaker.  Lane k of a wave owns component k -- mu_k, 1 / var_k and the
+//               accumulators N_k, F_k[d] in registers; the four waves take interleaved rows of the chunk from an LDS image (every lane
+//               reads the same address: a broadcast), max and sum over the lanes by DPP / permlane moves, and combine through LDS in
+//               wave order.  The chunk's partial goes to the workspace with plain stores: no atomics anywhere.
+//   finalise    one block per speaker sums its chunks' partials in ascending chunk order in float64 and does the MAP update, the Q6
+//               rounding, the saturation count and the mean of ll.
+// The chunks of a speaker depend on its own row count alone and every sum has a fixed order, so a speaker's outputs are the same bits
+// whatever the batch around it.
+//
+// Out of scope: UBM training (EM); variance or weight adaptation; the n_fft-400 librosa front end (these kernels take whatever MFCC
+// matrix the existing entries wrote and leave every front end alone); CMVN inside scanners or stream sessions (a stream needs a 150-row
+// look-ahead); a float log-sum-exp scorer; CMVN fused into the statistics pass.  No existing speaker scoring entry, nor any result of
+// one, changes: the enrolled Q6 means go to dsp_speaker_model_create as any other target's.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "enroll_kernels.hpp"
+#include "mfcc_device.hpp"
+
+namespace dsp {
+namespace {
+
+constexpr int kThreads = 256;
+
+// the recording / speaker that owns unit u: the last one whose first unit is <= u (those without rows own no unit)
+__device__ inline long owner_of_unit(const RowSpan *spans, long n, long u)
+{
+    long lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if (spans[mid].unit0 <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kThreads) void cmvn_kernel(const float *__restrict__ in, const RowSpan *__restrict__ spans, long n_rec, long tile_base,
+                                                        int d, int half, float *__restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) float xs[];      // [shift + staged rows * d]
+    const long t = tile_base + blockIdx.x;
+    const RowSpan sp = spans[owner_of_unit(spans, n_rec, t)];
+    const long t0 = (t - sp.unit0) * kCmvnTileRows;                 // the tile's first row within the recording (< n)
+    const long lo = t0 - half > 0 ? t0 - half : 0;
+    const long hi = t0 + kCmvnTileRows + half < sp.n ? t0 + kCmvnTileRows + half : sp.n;
+    const float *src = in + (sp.row0 + lo) * d;
+    const int total = (int)(hi - lo) * d;                           // <= (kCmvnTileRows + 2 half) * d floats
+    // 16-byte loads of the aligned chunks that lie wholly inside the staged rows, single floats at both ends: xs[shift + i] = src[i]
+    const int shift = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+    const int chunks = (shift + total + 3) >> 2;
+    for (int c = threadIdx.x; c < chunks; c += kThreads) {
+        const int first = 4 * c - shift;
+        if (first >= 0 && first + 4 <= total) {
+            *reinterpret_cast<float4 *>(xs + 4 * c) = *reinterpret_cast<const float4 *>(src + first);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (first + e >= 0 && first + e < total) xs[4 * c + e] = src[first + e];
+        }
+    }
+    __syncthreads();
+    const long left = sp.n - t0;
+    const int rows = left < kCmvnTileRows ? (int)left : kCmvnTileRows;
+    float *o = out + (sp.row0 + t0) * d;
+    for (int it = threadIdx.x; it < rows * d; it += kThreads) {
+        const int r = it / d, j = it - r * d;
+        const long row = t0 + r;
+        const long s = row - half > 0 ? row - half : 0;
+        const long e = row + half < sp.n ? row + half : sp.n;
+        const int cnt = (int)(e - s);                               // >= 1: half >= 1
+        const float *p = xs + shift + (int)(s - lo) * d + j;
+        const float fc = (float)cnt;
+        float sum = 0.0f;
+#pragma unroll 4
+        for (int i = 0; i < cnt; ++i) sum += p[i * d];
+        const float mu = sum / fc;
+        float var = 0.0f;
+#pragma unroll 4
+        for (int i = 0; i < cnt; ++i) {
+            const float dv = p[i * d] - mu;
+            var = __builtin_fmaf(dv, dv, var);
+        }
+        const float sigma = sqrtf(var / fc);
+        o[it] = (xs[shift + (int)(row - lo) * d + j] - mu) / (sigma + 1e-8f);
+    }
+}
+
+// the wave's max / sum in every lane: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror (after each step the lanes of a group
+// hold the group's value, so the mirrored lane's is the other group's), then the neighbouring 16-lane row and the other half-wave by
+// permlane swaps.  Both operands of every step are the same pair in both lanes: every lane ends with the same bits.
+__device__ __forceinline__ float wave_max(float v)
+{
+    v = fmaxf(v, dpp<DPP_QUAD_1032>(v));
+    v = fmaxf(v, dpp<DPP_QUAD_2301>(v));
+    v = fmaxf(v, dpp<DPP_ROW_HALF_MIRROR>(v));
+    v = fmaxf(v, dpp<DPP_ROW_MIRROR>(v));
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v += dpp<DPP_QUAD_1032>(v);
+    v += dpp<DPP_QUAD_2301>(v);
+    v += dpp<DPP_ROW_HALF_MIRROR>(v);
+    v += dpp<DPP_ROW_MIRROR>(v);
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);               // (even row) + (odd row) in both
+    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);            // (lower half) + (upper half) in both
+}
+
+constexpr int kRowLd = 16;       // floats per staged row: 16-byte reads of a row, whatever d
+
+template <int D>
+__global__ __launch_bounds__(kThreads) void enroll_stats_kernel(const float *__restrict__ feats, const RowSpan *__restrict__ spans, long n_spk,
+                                                                long chunk_base, EnrollUbm ubm, float *__restrict__ partials)
+{
+    constexpr int W = kThreads / 64, Q = (D + 3) / 4, P = 64 * (D + 1);
+    __shared__ __attribute__((aligned(16))) float xs[kEnrollChunkRows * kRowLd];
+    __shared__ float part[W * P];                                    // per wave: [lane][D + 1]
+    __shared__ double ll_part[W];                                    // per wave: its rows' sum of ll (wave-uniform, kept in float64)
+    const long c = chunk_base + blockIdx.x;
+    const RowSpan sp = spans[owner_of_unit(spans, n_spk, c)];
+    const long r0 = (c - sp.unit0) * kEnrollChunkRows;
+    const long left = sp.n - r0;
+    const int cnt = left < kEnrollChunkRows ? (int)left : kEnrollChunkRows;
+    const float *src = feats + (sp.row0 + r0) * D;
+    for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
+        const int r = i / D;
+        xs[r * kRowLd + (i - r * D)] = src[i];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = ubm.k;
+    const bool live = lane < k;
+    float mu[D], ic[D], F[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        mu[j] = live ? ubm.means[lane * D + j] : 0.0f;
+        ic[j] = live ? ubm.inv_covs[lane * D + j] : 0.0f;
+        F[j] = 0.0f;
+    }
+    const float lc = live ? ubm.log_consts[lane] : -INFINITY;         // lanes at or above k: l = -inf, e = 0
+    float N = 0.0f;
+    double ll_sum = 0.0;
+    __syncthreads();
+    for (int r = wave; r < cnt; r += W) {
+        float x[4 * Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const float4 v = *reinterpret_cast<const float4 *>(xs + r * kRowLd + 4 * q);
+            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+        }
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {                                // ascending d
+            const float dv = x[j] - mu[j];
+            s = __builtin_fmaf(dv * dv, ic[j], s);
+        }
+        const float l = __builtin_fmaf(-0.5f, s, lc);
+        const float m = wave_max(l);
+        const float e = expf(l - m);
+        const float S = wave_sum(e);
+        const float p = e / S;
+        ll_sum += (double)(m + logf(S));
+        N += p;
+#pragma unroll
+        for (int j = 0; j < D; ++j) F[j] = __builtin_fmaf(p, x[j], F[j]);
+    }
+    float *mine = part + wave * P + lane * (D + 1);
+    mine[0] = N;
+#pragma unroll
+    for (int j = 0; j < D; ++j) mine[1 + j] = F[j];
+    if (lane == 0) ll_part[wave] = ll_sum;
+    __syncthreads();
+    float *dst = partials + (size_t)c * ((size_t)k * (D + 1) + 1);
+    const int n_stats = k * (D + 1);
+    for (int i = threadIdx.x; i < n_stats; i += kThreads) {
+        float v = part[i];
+#pragma unroll
+        for (int w = 1; w < W; ++w) v += part[w * P + i];             // wave order
+        dst[i] = v;
+    }
+    if (threadIdx.x == 0) {
+        double v = ll_part[0];
+#pragma unroll
+        for (int w = 1; w < W; ++w) v += ll_part[w];
+        dst[n_stats] = (float)v;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const RowSpan *__restrict__ spans, EnrollUbm ubm, const float *__restrict__ partials,
+                                                                   int map_fixed, float param, float *__restrict__ means, int8_t *__restrict__ means_q6,
+                                                                   float *__restrict__ counts, float *__restrict__ ll_mean, int *__restrict__ saturated)
+{
+    __shared__ double sums[kEnrollMaxK * (kEnrollMaxD + 1) + 1];
+    __shared__ int clamped;
+    const long spk = blockIdx.x;
+    const RowSpan sp = spans[spk];
+    const int k = ubm.k, d = ubm.d, n_stats = k * (d + 1);
+    const long n_chunks = (sp.n + kEnrollChunkRows - 1) / kEnrollChunkRows;
+    const float *src = partials + (size_t)sp.unit0 * (size_t)(n_stats + 1);
+    if (threadIdx.x == 0) clamped = 0;
+    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
+        double acc = 0.0;
+        for (long c = 0; c < n_chunks; ++c) acc += (double)src[(size_t)c * (size_t)(n_stats + 1) + i];      // ascending chunk
+        sums[i] = acc;
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < k * d; i += kThreads) {
+        const int kk = i / d, j = i - kk * d;
+        const double n1 = sums[kk * (d + 1)] + 1e-8;
+        const double alpha = map_fixed ? (double)param : n1 / (n1 + (double)param);
+        const double mean = alpha * (sums[kk * (d + 1) + 1 + j] / n1) + (1.0 - alpha) * (double)ubm.means[i];
+        const float mean32 = (float)mean;
+        const size_t at = (size_t)spk * (size_t)(k * d) + i;
+        if (means) means[at] = mean32;
+        const float q = rintf(mean32 * 64.0f);                        // ties to even
+        mine += q < -128.0f || q > 127.0f;
+        if (means_q6) means_q6[at] = (int8_t)(int)fminf(fmaxf(q, -128.0f), 127.0f);
+    }
+    if (counts)
+        for (int kk = threadIdx.x; kk < k; kk += kThreads) counts[(size_t)spk * k + kk] = (float)sums[kk * (d + 1)];
+    if (threadIdx.x == 0 && ll_mean) ll_mean[spk] = (float)(sums[n_stats] / (double)sp.n);
+    if (saturated) {
+        if (mine) atomicAdd(&clamped, mine);                          // (an integer count in LDS: any order, one value)
+        __syncthreads();
+        if (threadIdx.x == 0) saturated[spk] = clamped;
+    }
+}
+
+template <int D>
+void launch_stats(const float *feats, const RowSpan *spans, long n_spk, long base, unsigned blocks, const EnrollUbm &ubm, float *partials, hipStream_t stream)
+{
+    hipLaunchKernelGGL(enroll_stats_kernel<D>, dim3(blocks), dim3(kThreads), 0, stream, feats, spans, n_spk, base, ubm, partials);
+}
+
+}  // namespace
+
+hipError_t prepare_cmvn()
+{
+    // images above 64 KiB (windows from about 960 rows at d = 16) need the kernel's dynamic LDS limit raised: to the widest image, the
+    // rows and the 4 floats of the alignment shift.  Idempotent, per device.
+    constexpr int kMaxLds = ((kCmvnTileRows + kCmvnMaxWindow) * kEnrollMaxD + 4) * 4;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(cmvn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+}
+
+hipError_t launch_cmvn(const float *d_in, const RowSpan *d_spans, long n_rec, long total_tiles, int d, int window, float *d_out, hipStream_t stream)
+{
+    constexpr long kMaxBlocks = 1L << 30;
+    if (d < 1 || d > kEnrollMaxD || window < 2 || window > kCmvnMaxWindow) return hipErrorInvalidValue;
+    const int half = window / 2;
+    const size_t lds = ((size_t)(kCmvnTileRows + 2 * half) * d + 4) * 4;
+    for (long base = 0; base < total_tiles; base += kMaxBlocks) {
+        const unsigned blocks = (unsigned)(total_tiles - base < kMaxBlocks ? total_tiles - base : kMaxBlocks);
+        hipLaunchKernelGGL(cmvn_kernel, dim3(blocks), dim3(kThreads), lds, stream, d_in, d_spans, n_rec, base, d, half, d_out);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_enroll(const float *d_feats, const RowSpan *d_spans, long n_speakers, long total_chunks, const EnrollUbm &ubm, float *d_partials,
+                         int map_fixed, float param, float *d_means, int8_t *d_means_q6, float *d_counts, float *d_ll_mean, int *d_saturated,
+                         hipStream_t stream)
+{
+    constexpr long kMaxBlocks = 1L << 30;
+    if (ubm.k < 1 || ubm.k > kEnrollMaxK || n_speakers > kMaxBlocks) return hipErrorInvalidValue;
+    for (long base = 0; base < total_chunks; base += kMaxBlocks) {
+        const unsigned blocks = (unsigned)(total_chunks - base < kMaxBlocks ? total_chunks - base : kMaxBlocks);
+        switch (ubm.d) {
+#define DSP_ENROLL_D(D) case D: launch_stats<D>(d_feats, d_spans, n_speakers, base, blocks, ubm, d_partials, stream); break;
+        DSP_ENROLL_D(1) DSP_ENROLL_D(2) DSP_ENROLL_D(3) DSP_ENROLL_D(4) DSP_ENROLL_D(5) DSP_ENROLL_D(6) DSP_ENROLL_D(7) DSP_ENROLL_D(8)
+        DSP_ENROLL_D(9) DSP_ENROLL_D(10) DSP_ENROLL_D(11) DSP_ENROLL_D(12) DSP_ENROLL_D(13) DSP_ENROLL_D(14) DSP_ENROLL_D(15) DSP_ENROLL_D(16)
+#undef DSP_ENROLL_D
+        default: return hipErrorInvalidValue;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(enroll_finalize_kernel, dim3((unsigned)n_speakers), dim3(kThreads), 0, stream, d_spans, ubm, d_partials, map_fixed, param, d_means,
+                       d_means_q6, d_counts, d_ll_mean, d_saturated);
+    return hipGetLastError();
+}
+
+}  // namespace dsp

@@ -54,6 +54,18 @@ class GmmParams(C.Structure):
     _fields_ = [("k", C.c_int), ("d", C.c_int), ("means", C.c_void_p), ("inv_covs", C.c_void_p), ("log_consts", C.c_void_p)]
 
 
+class GmmFloatParams(C.Structure):
+    """dsp_gmm_float_params (include/dsp_amd.h): the float UBM, double arrays."""
+
+    _fields_ = [("k", C.c_int), ("d", C.c_int), ("log_consts", C.c_void_p), ("means", C.c_void_p), ("inv_covs", C.c_void_p)]
+
+
+class EnrollConfig(C.Structure):
+    """dsp_enroll_config (include/dsp_amd.h)."""
+
+    _fields_ = [("map_mode", C.c_int), ("relevance_factor", C.c_float), ("fixed_alpha", C.c_float)]
+
+
 class ScanConfig(C.Structure):
     """dsp_scan_config (include/dsp_amd.h): windows of MFCC rows."""
 
@@ -88,6 +100,7 @@ MELNORM_NONE, MELNORM_SLANEY, MELNORM_LIBROSA, MELNORM_AUBIO_SLANEY = 0, 1, 2, 3
 LOG_PER_FRAME_MAX, LOG_GLOBAL_REF1, LOG_LOG10_FLOOR = 0, 1, 2
 SPECTRUM_POWER, SPECTRUM_MAGNITUDE = 0, 1
 FRAMING_COMPLETE, FRAMING_STREAM = 0, 1
+MAP_RELEVANCE, MAP_FIXED_ALPHA = 0, 1
 PREFILTER_NONE, PREFILTER_BUTTER_1000_3000, PREFILTER_BUTTER_3000_7500 = 0, 1, 2
 
 # every symbol include/dsp_amd.h declares (tests check the library exports them all)
@@ -118,6 +131,8 @@ SYMBOLS = [
     "dsp_resample_ratio", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
     "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device", "dsp_resample_clips_pcm16_device",
     "dsp_resample_host",
+    "dsp_cmvn_create", "dsp_cmvn_destroy", "dsp_cmvn_ragged_device",
+    "dsp_speaker_enroller_create", "dsp_speaker_enroller_destroy", "dsp_speaker_enroll_ragged_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -262,6 +277,13 @@ def load() -> C.CDLL:
     L.dsp_resample_clips_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, C.c_long, vp]; L.dsp_resample_clips_device.restype = ip
     L.dsp_resample_clips_pcm16_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, C.c_long, vp]; L.dsp_resample_clips_pcm16_device.restype = ip
     L.dsp_resample_host.argtypes = [ip, ip, vp, C.c_long, vp]; L.dsp_resample_host.restype = ip
+    L.dsp_cmvn_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_cmvn_create.restype = ip
+    L.dsp_cmvn_destroy.argtypes = [vp]; L.dsp_cmvn_destroy.restype = None
+    L.dsp_cmvn_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_cmvn_ragged_device.restype = ip
+    L.dsp_speaker_enroller_create.argtypes = [C.POINTER(GmmFloatParams), ip, C.POINTER(vp)]; L.dsp_speaker_enroller_create.restype = ip
+    L.dsp_speaker_enroller_destroy.argtypes = [vp]; L.dsp_speaker_enroller_destroy.restype = None
+    L.dsp_speaker_enroll_ragged_device.argtypes = [vp, vp, C.c_long, lp, C.POINTER(EnrollConfig), vp, vp, vp, vp, vp, vp]
+    L.dsp_speaker_enroll_ragged_device.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

@@ -665,6 +665,57 @@ int dsp_resample_clips_pcm16_device(dsp_resampler *r, const int16_t *d_pcm, long
                                     int stereo_mode, float *d_out, long out_stride, void *stream);
 int dsp_resample_host(int rate_in, int rate_out, const float *in, long n, float *out);
 
+/* --- enrolling speakers: sliding CMVN and MAP-adapted GMM means ---
+ * The step in front of dsp_speaker_model_create: a person's speech -> the target GMM's int8 means.  Both entries work on a ragged MFCC
+ * matrix as dsp_mfcc_clips_ragged_device writes it, whatever front end produced it; frame_offsets is a HOST array of n + 1 rows, read
+ * before the call returns.  Everything is enqueued on `stream`.
+ *
+ * Sliding CMVN (sliding_cmvn of the reference's speaker/gmm_utils.py:14-25, the feature space its UBM was trained in): recording r is
+ * rows [frame_offsets[r], frame_offsets[r + 1]) of d_in[..][d], n rows.  With half = window / 2, row t uses rows [s, e) =
+ * [max(0, t - half), min(n, t + half)) of its own recording -- rows t - 150 .. t + 149 at window 300 -- and, per coefficient j, in float32:
+ *   mu = mean of x[s..e)[j],  sigma = sqrt(mean of (x[.][j] - mu)^2)  (two passes),  y[t][j] = (x[t][j] - mu) / (sigma + 1e-8)
+ * A one-row recording and all-zero rows give exact zeros; recordings without rows give nothing; a row's output depends on its own
+ * recording only.  d <= 16; window 2 .. 2048 (what one block's LDS image holds, 135 184 bytes at d = 16: DSP_EINVAL names the limit).  d_out must not be d_in.
+ * No workspace and no host synchronisation: any stream.  Zero recordings: DSP_OK.                                                      */
+typedef struct dsp_cmvn dsp_cmvn;
+int dsp_cmvn_create(int device, int d, int window, dsp_cmvn **out);
+void dsp_cmvn_destroy(dsp_cmvn *c);
+int dsp_cmvn_ragged_device(dsp_cmvn *c, const float *d_in, long n_recordings, const long *frame_offsets, float *d_out, void *stream);
+
+/* MAP enrolment of many speakers against one UBM (map_adapt_gmm of the reference's 2fa/audio/speaker/adapt_ubm.py:72-86 and
+ * 2fa/audio/adapt_ubm.py:97-110; means only).  The float UBM is handed over once, as the DOUBLE_GMM arrays of gmm_params.inc:
+ * log_consts[k] = log w_k - 0.5 sum_d log(2 pi var_kd), means[k][d], inv_covs[k][d] = 1 / var_kd; each is rounded once to float32.
+ * Speaker s is rows [frame_offsets[s], frame_offsets[s + 1]) of d_feats[..][d] (CMVN'd rows: the offsets of several recordings of one
+ * person are a subset of the recordings' boundaries).  Per row, in float32:
+ *   l_k = log_const_k - 0.5 sum_d (x_d - mu_kd)^2 inv_cov_kd,   m = max_k l_k,  e_k = exp(l_k - m),  S = sum_k e_k,  p_k = e_k / S,  ll = m + log S
+ * per speaker N_k = sum_t p_k, F_kd = sum_t p_k x_d, N'_k = N_k + 1e-8, alpha_k = N'_k / (N'_k + relevance_factor) or fixed_alpha, and
+ *   mean_kd = alpha_k F_kd / N'_k + (1 - alpha_k) mu_kd.
+ * Outputs (device pointers; any may be NULL, not all): d_means[S][k][d] float32; d_means_q6[S][k][d] = rint(mean * 64), ties to even,
+ * saturated to [-128, 127] -- the Q6 means dsp_gmm_params takes, the target's inv_covs and log_consts being the UBM's own;
+ * d_saturated[S] the entries so clamped; d_counts[S][k] = N_k; d_ll_mean[S] the mean of ll over the speaker's rows (sklearn's score).
+ * A speaker without rows: DSP_EINVAL naming the first.  Zero speakers: DSP_OK, no launch.  There are no float atomics: a speaker's rows
+ * are summed in chunks of 256 rows cut by its own row count and combined in a fixed order, so every output of a speaker is bit-identical
+ * whatever the batch around it.  The enroller owns a grow-only workspace: ONE stream at a time per enroller.
+ * Not covered: UBM training (EM), variance or weight adaptation, a float log-sum-exp scorer, CMVN inside scanners or stream sessions. */
+typedef struct dsp_gmm_float_params {
+    int k, d;                    /* k <= 64, d <= 16, as dsp_gmm_params */
+    const double *log_consts;    /* [k]    */
+    const double *means;         /* [k][d] */
+    const double *inv_covs;      /* [k][d] */
+} dsp_gmm_float_params;
+enum { DSP_MAP_RELEVANCE = 0, DSP_MAP_FIXED_ALPHA = 1 };
+typedef struct dsp_enroll_config {
+    int map_mode;                /* DSP_MAP_RELEVANCE (alpha_k = N'_k / (N'_k + r)) or DSP_MAP_FIXED_ALPHA */
+    float relevance_factor;      /* r > 0 (read in DSP_MAP_RELEVANCE); 16 in 2fa/audio/adapt_ubm.py        */
+    float fixed_alpha;           /* in [0, 1] (read in DSP_MAP_FIXED_ALPHA); 0.7 in speaker/adapt_ubm.py   */
+} dsp_enroll_config;
+typedef struct dsp_speaker_enroller dsp_speaker_enroller;
+int dsp_speaker_enroller_create(const dsp_gmm_float_params *ubm, int device, dsp_speaker_enroller **out);
+void dsp_speaker_enroller_destroy(dsp_speaker_enroller *e);
+int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_feats, long n_speakers, const long *frame_offsets,
+                                     const dsp_enroll_config *cfg, float *d_means, int8_t *d_means_q6, float *d_counts, float *d_ll_mean,
+                                     int *d_saturated, void *stream);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
