@@ -8,6 +8,8 @@
   StreamSession  the same for audio that is still arriving       sync/sync.cpp:188-213 (the capture loop itself, many feeds)
   Cmvn           sliding_cmvn                                   2fa/audio/speaker/gmm_utils.py:14-25
   SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
+  UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
+  quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
 Trained parameters are passed in as arrays (the reference compiles them in from model_params.h / gmm_params.inc).
 Tensors are HBM-resident torch tensors; Python only moves pointers.
@@ -538,6 +540,113 @@ class SpeakerEnroller:
         return SpeakerModel({"means": q6, "inv_covs": ubm_int["inv_covs"], "log_consts": ubm_int["log_consts"]}, ubm_int, device)
 
 
+class UbmTrainer:
+    """dsp_ubm_trainer: EM for a diagonal GMM of k components on a matrix of (CMVN'd) feature rows [n][d] -- sklearn's M-step and stopping
+    rule; the float UBM SpeakerEnroller takes, and through quantize_gmm the integer tables SpeakerModel takes."""
+
+    def __init__(self, k: int, d: int, device: int = 0):
+        k, d = int(k), int(d)
+        if not (1 <= k <= 64 and 1 <= d <= 16):
+            raise ValueError("k must be 1 .. 64 and d 1 .. 16")
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_ubm_trainer_create(int(device), k, d, C.byref(h)), "dsp_ubm_trainer_create")
+        self._h, self.k, self.d, self.device = h, k, d, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_ubm_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _rows(self, feats):
+        import torch
+        if not (hasattr(feats, "is_cuda") and feats.is_cuda and feats.dim() == 2 and feats.shape[1] == self.d and feats.dtype == torch.float32):
+            raise ValueError(f"feats must be a float32 CUDA tensor [n][{self.d}]")
+        if feats.shape[0] < self.k:
+            raise ValueError(f"feats must hold at least k = {self.k} rows")
+        return feats.contiguous()
+
+    @staticmethod
+    def _reg_covar(reg_covar):
+        reg_covar = float(reg_covar)
+        if not (0.0 <= reg_covar < float("inf")):
+            raise ValueError("reg_covar must be >= 0 and finite")
+        return reg_covar
+
+    def init_rows(self, feats, reg_covar: float = 1e-6) -> dict:
+        """The library's deterministic start on feats (cuda float32 [n][d]): means = rows floor((i + 0.5) n / k), variances = the rows'
+        global variance per dimension + reg_covar, weights 1 / k -> dict of float64 arrays weights [k], means [k][d], variances [k][d]."""
+        reg_covar = self._reg_covar(reg_covar)
+        feats = self._rows(feats)
+        out = {"weights": np.empty(self.k), "means": np.empty((self.k, self.d)), "variances": np.empty((self.k, self.d))}
+        _lib.check(self._L.dsp_ubm_init_rows_device(self._h, feats.data_ptr(), feats.shape[0], reg_covar,
+                                                    *[out[key].ctypes.data for key in ("weights", "means", "variances")], _stream(feats)),
+                   "dsp_ubm_init_rows_device")
+        return out
+
+    def fit(self, feats, init: dict | None = None, max_iter: int = 300, tol: float = 1e-3, reg_covar: float = 1e-6) -> dict:
+        """EM on feats (cuda float32 [n][d], n >= k) from init (weights [k], means [k][d], variances [k][d]; None: init_rows) until the
+        lower bound changes by less than tol or max_iter iterations -> dict of float64 arrays weights [k], means, variances, inv_covs [k][d],
+        log_consts [k], lower_bounds [n_iter], and n_iter, converged.  The dict is a SpeakerEnroller's ubm_float as it is."""
+        max_iter, tol = int(max_iter), float(tol)
+        if max_iter < 1:
+            raise ValueError("max_iter must be >= 1")
+        if not tol >= 0.0:
+            raise ValueError("tol must be >= 0")
+        reg_covar = self._reg_covar(reg_covar)
+        k, d = self.k, self.d
+        start = None
+        if init is not None:
+            keep = {key: np.ascontiguousarray(init[key], np.float64) for key in ("weights", "means", "variances")}
+            if keep["weights"].shape != (k,) or keep["means"].shape != (k, d) or keep["variances"].shape != (k, d):
+                raise ValueError(f"init: weights must be [{k}], means and variances [{k}][{d}]")
+            if not all(np.isfinite(v).all() for v in keep.values()):
+                raise ValueError("init: weights, means and variances must be finite")
+            if not ((keep["weights"] > 0).all() and abs(keep["weights"].sum() - 1.0) <= 1e-6):
+                raise ValueError("init: weights must be > 0 and sum to 1")
+            if not (keep["variances"] > 0).all():
+                raise ValueError("init: variances must be > 0")
+            start = _lib.UbmInit(*[keep[key].ctypes.data for key in ("weights", "means", "variances")])
+        feats = self._rows(feats)
+        out = {"weights": np.empty(k), "means": np.empty((k, d)), "variances": np.empty((k, d)), "log_consts": np.empty(k),
+               "inv_covs": np.empty((k, d)), "lower_bounds": np.full(max_iter, np.nan)}
+        res = _lib.UbmResult()
+        res.gmm.log_consts, res.gmm.means, res.gmm.inv_covs = (out[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+        res.weights, res.variances, res.lower_bounds = (out[key].ctypes.data for key in ("weights", "variances", "lower_bounds"))
+        cfg = _lib.UbmConfig(max_iter, tol, reg_covar)
+        _lib.check(self._L.dsp_ubm_train_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(start) if start is not None else None,
+                                                C.byref(cfg), C.byref(res), _stream(feats)), "dsp_ubm_train_device")
+        out["lower_bounds"] = out["lower_bounds"][:res.n_iter].copy()
+        out["n_iter"], out["converged"] = int(res.n_iter), bool(res.converged)
+        return out
+
+
+def quantize_gmm(float_params: dict):
+    """Host only (dsp_gmm_quantize): a float GMM (log_consts [k], means [k][d], inv_covs [k][d]; a UbmTrainer.fit result as it is) ->
+    (ubm_int, saturated): the integer scorer's tables means int8 = rint(64 mean), inv_covs int32 = rint(2048 inv_cov), log_consts int16 =
+    rint(256 log_const), ties to even, each saturated to its type, and the number of entries clamped per table in that order."""
+    keep = {key: np.ascontiguousarray(float_params[key], np.float64) for key in ("log_consts", "means", "inv_covs")}
+    if keep["means"].ndim != 2 or keep["inv_covs"].shape != keep["means"].shape or keep["log_consts"].shape != keep["means"].shape[:1]:
+        raise ValueError("float_params: means and inv_covs must be [k][d], log_consts [k]")
+    k, d = keep["means"].shape
+    if not (1 <= k <= 64 and 1 <= d <= 16):
+        raise ValueError("float_params: k must be 1 .. 64 and d 1 .. 16")
+    p = _lib.GmmFloatParams()
+    p.k, p.d = k, d
+    p.log_consts, p.means, p.inv_covs = (keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+    out = {"means": np.empty((k, d), np.int8), "inv_covs": np.empty((k, d), np.int32), "log_consts": np.empty(k, np.int16)}
+    sat = (C.c_int * 3)()
+    _lib.check(_lib.load().dsp_gmm_quantize(C.byref(p), out["means"].ctypes.data, out["inv_covs"].ctypes.data, out["log_consts"].ctypes.data, sat),
+               "dsp_gmm_quantize")
+    return out, {"means": int(sat[0]), "inv_covs": int(sat[1]), "log_consts": int(sat[2])}
+
+
 def upsample_linear(x, new_size: int):
     """x: cuda float32 [n_clips][old] (or [old]) -> [n_clips][new_size]; numpy input goes through the host entry point."""
     L = _lib.load()
@@ -557,4 +666,4 @@ def upsample_linear(x, new_size: int):
     return out[0] if squeeze else out
 
 
-__all__ = ["StopModel", "SpeakerModel", "Scanner", "StreamSession", "Cmvn", "SpeakerEnroller", "stream_push_plan", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]
+__all__ = ["StopModel", "SpeakerModel", "Scanner", "StreamSession", "Cmvn", "SpeakerEnroller", "UbmTrainer", "quantize_gmm", "stream_push_plan", "scan_window_offsets", "upsample_linear", "MfccPlan", "default_config"]

@@ -1,0 +1,261 @@
+// capi_ubm.cpp -- the C ABI of UBM training and of the GMM quantiser (include/dsp_amd.h dsp_ubm_*, dsp_gmm_quantize):
+// argument checks, the trainer's grow-only workspace, the initial model, the enqueueing of the EM iterations of ubm_kernels.hip and the
+// one synchronisation that reads the result back.
+#include <cmath>
+#include <cstdint>
+#include <limits>
+#include <memory>
+
+#include "capi_util.hpp"
+#include "ubm_kernels.hpp"
+
+using dsp::capi_fail;
+
+struct dsp_ubm_trainer {
+    int device = 0, k = 0, d = 0;
+    dsp::DeviceBuf<double> partials;     // grow-only: the groups' partials, the supers' behind them
+    dsp::DeviceBuf<double> state;        // grow-only: the float64 parameters, lower_bounds[max_iter] behind them
+    dsp::DeviceBuf<float> model;         // the float32 E-step model
+    dsp::DeviceBuf<dsp::UbmCtrl> ctrl;
+};
+
+namespace {
+
+// iterations enqueued between two looks at the stop flag: a fit that stops early wastes at most this many empty iterations
+constexpr int kIterationsPerLook = 32;
+constexpr long kMaxRows = 1L << 40;
+
+struct HostModel {
+    std::vector<double> params;          // w[k], mu[k][d], var[k][d], log_const[k]
+    std::vector<float> model;            // log_const[k], c[k][d], ic[k][d]
+};
+
+HostModel host_model(int k, int d, const double *w, const double *mu, const double *var)
+{
+    HostModel m;
+    m.params.resize(dsp::ubm_param_doubles(k, d));
+    m.model.resize(dsp::ubm_model_floats(k, d));
+    const size_t kd = (size_t)k * d;
+    for (int i = 0; i < k; ++i) {
+        double log_det = 0.0;
+        for (int j = 0; j < d; ++j) log_det += std::log(2.0 * M_PI * var[(size_t)i * d + j]);
+        const double lc = std::log(w[i]) - 0.5 * log_det;
+        m.params[i] = w[i];
+        m.params[(size_t)k + 2 * kd + i] = lc;
+        m.model[i] = (float)lc;
+    }
+    for (size_t i = 0; i < kd; ++i) {
+        m.params[(size_t)k + i] = mu[i];
+        m.params[(size_t)k + kd + i] = var[i];
+        m.model[(size_t)k + i] = (float)mu[i];
+        m.model[(size_t)k + kd + i] = (float)(1.0 / var[i]);
+    }
+    return m;
+}
+
+// EM from (w, mu, var) on the trainer's device (current): up to max_iter iterations, the parameters after the last one into `params`
+// (ubm_param_doubles), lower_bounds[0 .. n_iter) into `lower_bounds`.  k may be below the trainer's (the k = 1 pass of the row start).
+int run_em(dsp_ubm_trainer *t, int k, const float *d_feats, long n, const double *w, const double *mu, const double *var, int max_iter, double tol,
+           double reg_covar, double *params, double *lower_bounds, int *n_iter, int *converged, hipStream_t stream)
+{
+    const int d = t->d;
+    const size_t stride = dsp::ubm_partial_doubles(k, d), n_params = dsp::ubm_param_doubles(k, d);
+    const long n_groups = dsp::ubm_groups(n), n_supers = dsp::ubm_supers(n);
+    if (t->partials.reserve((size_t)(n_groups + n_supers) * stride * sizeof(double)) != hipSuccess ||
+        t->state.reserve((n_params + (size_t)max_iter) * sizeof(double)) != hipSuccess ||
+        t->model.reserve(dsp::ubm_model_floats(t->k, d) * sizeof(float)) != hipSuccess || t->ctrl.reserve(sizeof(dsp::UbmCtrl)) != hipSuccess)
+        return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's workspace");
+    const HostModel m = host_model(k, d, w, mu, var);
+    const dsp::UbmCtrl start{0, 0, 0, 0, -std::numeric_limits<double>::infinity()};
+    DSP_CAPI_HIP(hipMemcpyAsync(t->state, m.params.data(), n_params * sizeof(double), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(t->model, m.model.data(), m.model.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(t->ctrl, &start, sizeof(start), hipMemcpyHostToDevice, stream));
+    dsp::UbmFit fit{d_feats, n, k, d, t->state, t->model, t->partials, t->partials.get() + (size_t)n_groups * stride, t->state.get() + n_params,
+                    t->ctrl, tol, reg_covar};
+    dsp::UbmCtrl end = start;
+    for (int first = 0; first < max_iter && !end.done; first += kIterationsPerLook) {
+        const int count = max_iter - first < kIterationsPerLook ? max_iter - first : kIterationsPerLook;
+        DSP_CAPI_HIP(dsp::launch_ubm_iterations(fit, first, count, stream));
+        DSP_CAPI_HIP(hipMemcpyAsync(&end, t->ctrl, sizeof(end), hipMemcpyDeviceToHost, stream));
+        DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    }
+    DSP_CAPI_HIP(hipMemcpyAsync(params, t->state, n_params * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (lower_bounds) DSP_CAPI_HIP(hipMemcpyAsync(lower_bounds, fit.lower_bounds, (size_t)end.n_iter * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    *n_iter = end.n_iter;
+    *converged = end.converged;
+    return DSP_OK;
+}
+
+int check_rows(const dsp_ubm_trainer *t, const float *d_feats, long n)
+{
+    if (!t) return capi_fail(DSP_EINVAL, "trainer is NULL");
+    if (!d_feats) return capi_fail(DSP_EINVAL, "d_feats is NULL");
+    if (n < t->k) return capi_fail(DSP_EINVAL, "n must be at least k = " + std::to_string(t->k) + " rows, got " + std::to_string(n));
+    if (n > kMaxRows) return capi_fail(DSP_EINVAL, "n: at most 2^40 rows per call");
+    return DSP_OK;
+}
+
+int check_reg_covar(double reg_covar)
+{
+    if (!(reg_covar >= 0.0) || !std::isfinite(reg_covar)) return capi_fail(DSP_EINVAL, "reg_covar must be >= 0 and finite");
+    return DSP_OK;
+}
+
+// the library's start: means = rows floor((i + 0.5) n / k), variances = the rows' global variance + reg_covar (one k = 1 iteration from
+// the k = 1 start: the middle row, variance 1), weights 1 / k
+int init_rows(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means, double *variances, hipStream_t stream)
+{
+    const int k = t->k, d = t->d;
+    // centred on the middle row (the k = 1 start's own mean), not on 0: rows far from the origin would lose their variance to float32
+    std::vector<float> middle((size_t)d);
+    DSP_CAPI_HIP(hipMemcpyAsync(middle.data(), d_feats + (size_t)(n / 2) * d, (size_t)d * sizeof(float), hipMemcpyDeviceToHost, stream));
+    DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    std::vector<double> one_mu(middle.begin(), middle.end()), one_var((size_t)d, 1.0), params(dsp::ubm_param_doubles(1, d));
+    const double one_w = 1.0;
+    int n_iter = 0, converged = 0;
+    if (const int rc = run_em(t, 1, d_feats, n, &one_w, one_mu.data(), one_var.data(), 1, 0.0, reg_covar, params.data(), nullptr, &n_iter, &converged, stream))
+        return rc;
+    std::vector<float> rows((size_t)k * d);
+    for (int i = 0; i < k; ++i) {
+        const long row = (long)(((__int128)(2 * i + 1) * n) / (2 * k));
+        DSP_CAPI_HIP(hipMemcpyAsync(rows.data() + (size_t)i * d, d_feats + (size_t)row * d, (size_t)d * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < k; ++i) {
+        weights[i] = 1.0 / k;
+        for (int j = 0; j < d; ++j) {
+            means[(size_t)i * d + j] = (double)rows[(size_t)i * d + j];
+            variances[(size_t)i * d + j] = params[1 + (size_t)d + j];
+        }
+    }
+    return DSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsp_ubm_trainer_create(int device, int k, int d, dsp_ubm_trainer **out)
+{
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (k < 1 || k > dsp::kUbmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(k));
+    if (d < 1 || d > dsp::kUbmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(d));
+    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
+    // nothing is allocated here and no device is touched: the workspace grows in the first call that trains, which is also where a
+    // device that does not exist is reported
+    auto t = std::make_unique<dsp_ubm_trainer>();
+    t->device = device;
+    t->k = k;
+    t->d = d;
+    *out = t.release();
+    return DSP_OK;
+}
+
+void dsp_ubm_trainer_destroy(dsp_ubm_trainer *t)
+{
+    if (!t) return;
+    dsp::DeviceScope scope(t->device);
+    delete t;
+}
+
+int dsp_ubm_init_rows_device(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means, double *variances,
+                             void *stream)
+{
+    if (const int rc = check_rows(t, d_feats, n)) return rc;
+    if (const int rc = check_reg_covar(reg_covar)) return rc;
+    if (!weights || !means || !variances) return capi_fail(DSP_EINVAL, "weights, means and variances must not be NULL");
+    if (const int rc = dsp::check_device(t->device)) return rc;
+    DSP_ON_DEVICE(t->device);
+    return init_rows(t, d_feats, n, reg_covar, weights, means, variances, (hipStream_t)stream);
+}
+
+int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_ubm_init *init, const dsp_ubm_config *cfg, dsp_ubm_result *result,
+                         void *stream)
+{
+    if (const int rc = check_rows(t, d_feats, n)) return rc;
+    if (!cfg) return capi_fail(DSP_EINVAL, "dsp_ubm_config is NULL");
+    if (cfg->max_iter < 1) return capi_fail(DSP_EINVAL, "dsp_ubm_config: max_iter must be >= 1, got " + std::to_string(cfg->max_iter));
+    if (!(cfg->tol >= 0.0)) return capi_fail(DSP_EINVAL, "dsp_ubm_config: tol must be >= 0");
+    if (const int rc = check_reg_covar(cfg->reg_covar)) return rc;
+    const int k = t->k, d = t->d;
+    const size_t kd = (size_t)k * d;
+    if (init) {
+        if (!init->weights || !init->means || !init->variances) return capi_fail(DSP_EINVAL, "dsp_ubm_init: weights, means and variances must not be NULL");
+        double sum = 0.0;
+        for (int i = 0; i < k; ++i) {
+            if (!std::isfinite(init->weights[i])) return capi_fail(DSP_EINVAL, "dsp_ubm_init: weights must be finite");
+            if (!(init->weights[i] > 0.0)) return capi_fail(DSP_EINVAL, "dsp_ubm_init: weights must be > 0 (component " + std::to_string(i) + ")");
+            sum += init->weights[i];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-6)) return capi_fail(DSP_EINVAL, "dsp_ubm_init: weights must sum to 1 within 1e-6");
+        for (size_t i = 0; i < kd; ++i) {
+            if (!std::isfinite(init->means[i]) || !std::isfinite(init->variances[i])) return capi_fail(DSP_EINVAL, "dsp_ubm_init: means and variances must be finite");
+            if (!(init->variances[i] > 0.0)) return capi_fail(DSP_EINVAL, "dsp_ubm_init: variances must be > 0 (component " + std::to_string(i / d) + ")");
+        }
+    }
+    if (!result || !result->weights || !result->variances || !result->lower_bounds || !result->gmm.log_consts || !result->gmm.means || !result->gmm.inv_covs)
+        return capi_fail(DSP_EINVAL, "dsp_ubm_result and its arrays must not be NULL");
+    if (const int rc = dsp::check_device(t->device)) return rc;
+    DSP_ON_DEVICE(t->device);
+    std::vector<double> start;
+    const double *w, *mu, *var;
+    if (init) {
+        w = init->weights; mu = init->means; var = init->variances;
+    } else {
+        start.resize((size_t)k + 2 * kd);
+        if (const int rc = init_rows(t, d_feats, n, cfg->reg_covar, start.data(), start.data() + k, start.data() + k + kd, (hipStream_t)stream)) return rc;
+        w = start.data(); mu = w + k; var = mu + kd;
+    }
+    std::vector<double> params(dsp::ubm_param_doubles(k, d));
+    int n_iter = 0, converged = 0;
+    if (const int rc = run_em(t, k, d_feats, n, w, mu, var, cfg->max_iter, cfg->tol, cfg->reg_covar, params.data(), result->lower_bounds, &n_iter, &converged,
+                              (hipStream_t)stream))
+        return rc;
+    // the caller's arrays behind the const pointers of dsp_gmm_float_params are the result's to write
+    double *log_consts = const_cast<double *>(result->gmm.log_consts), *means = const_cast<double *>(result->gmm.means);
+    double *inv_covs = const_cast<double *>(result->gmm.inv_covs);
+    for (int i = 0; i < k; ++i) {
+        result->weights[i] = params[i];
+        log_consts[i] = params[(size_t)k + 2 * kd + i];
+    }
+    for (size_t i = 0; i < kd; ++i) {
+        means[i] = params[(size_t)k + i];
+        result->variances[i] = params[(size_t)k + kd + i];
+        inv_covs[i] = 1.0 / params[(size_t)k + kd + i];
+    }
+    result->gmm.k = k;
+    result->gmm.d = d;
+    result->n_iter = n_iter;
+    result->converged = converged;
+    return DSP_OK;
+}
+
+int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_covs, int16_t *log_consts, int saturated[3])
+{
+    if (!g || !g->log_consts || !g->means || !g->inv_covs) return capi_fail(DSP_EINVAL, "the float GMM and its arrays must not be NULL");
+    if (g->k < 1 || g->k > dsp::kUbmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(g->k));
+    if (g->d < 1 || g->d > dsp::kUbmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(g->d));
+    if (!means || !inv_covs || !log_consts || !saturated) return capi_fail(DSP_EINVAL, "means, inv_covs, log_consts and saturated must not be NULL");
+    const size_t kd = (size_t)g->k * g->d;
+    for (size_t i = 0; i < kd; ++i)
+        if (std::isnan(g->means[i]) || std::isnan(g->inv_covs[i])) return capi_fail(DSP_EINVAL, "means and inv_covs must not be NaN");
+    for (int i = 0; i < g->k; ++i)
+        if (std::isnan(g->log_consts[i])) return capi_fail(DSP_EINVAL, "log_consts must not be NaN");
+    // rint: to nearest, ties to even (the default rounding mode); each table saturates to its type and counts what it clamped
+    auto quantise = [](double v, double scale, double lo, double hi, int &clamped) {
+        const double q = std::rint(v * scale);
+        clamped += q < lo || q > hi;
+        return q < lo ? lo : q > hi ? hi : q;
+    };
+    saturated[0] = saturated[1] = saturated[2] = 0;
+    for (size_t i = 0; i < kd; ++i) {
+        means[i] = (int8_t)quantise(g->means[i], 64.0, -128.0, 127.0, saturated[0]);
+        inv_covs[i] = (int32_t)quantise(g->inv_covs[i], 2048.0, -2147483648.0, 2147483647.0, saturated[1]);
+    }
+    for (int i = 0; i < g->k; ++i) log_consts[i] = (int16_t)quantise(g->log_consts[i], 256.0, -32768.0, 32767.0, saturated[2]);
+    return DSP_OK;
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 // The chunks of a speaker depend on its own row count alone and every sum has a fixed order, so a speaker's outputs are the same bits
 // whatever the batch around it.
 //
-// Out of scope: UBM training (EM); variance or weight adaptation; the n_fft-400 librosa front end (these kernels take whatever MFCC
+// Out of scope: variance or weight adaptation (the UBM itself: ubm_kernels.hip); the n_fft-400 librosa front end (these kernels take whatever MFCC
 // matrix the existing entries wrote and leave every front end alone); CMVN inside scanners or stream sessions (a stream needs a 150-row
 // look-ahead); a float log-sum-exp scorer; CMVN fused into the statistics pass.  No existing speaker scoring entry, nor any result of
 // one, changes: the enrolled Q6 means go to dsp_speaker_model_create as any other target's.
@@ -28,6 +28,7 @@
 
 #include "enroll_kernels.hpp"
 #include "mfcc_device.hpp"
+#include "wave_reduce.hpp"
 
 namespace dsp {
 namespace {
@@ -94,32 +95,6 @@ __global__ __launch_bounds__(kThreads) void cmvn_kernel(const float *__restrict_
         const float sigma = sqrtf(var / fc);
         o[it] = (xs[shift + (int)(row - lo) * d + j] - mu) / (sigma + 1e-8f);
     }
-}
-
-// the wave's max / sum in every lane: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror (after each step the lanes of a group
-// hold the group's value, so the mirrored lane's is the other group's), then the neighbouring 16-lane row and the other half-wave by
-// permlane swaps.  Both operands of every step are the same pair in both lanes: every lane ends with the same bits.
-__device__ __forceinline__ float wave_max(float v)
-{
-    v = fmaxf(v, dpp<DPP_QUAD_1032>(v));
-    v = fmaxf(v, dpp<DPP_QUAD_2301>(v));
-    v = fmaxf(v, dpp<DPP_ROW_HALF_MIRROR>(v));
-    v = fmaxf(v, dpp<DPP_ROW_MIRROR>(v));
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += dpp<DPP_QUAD_1032>(v);
-    v += dpp<DPP_QUAD_2301>(v);
-    v += dpp<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp<DPP_ROW_MIRROR>(v);
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);               // (even row) + (odd row) in both
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);            // (lower half) + (upper half) in both
 }
 
 constexpr int kRowLd = 16;       // floats per staged row: 16-byte reads of a row, whatever d

@@ -1,0 +1,237 @@
+// ubm_kernels.hip -- EM for a diagonal GMM on a device matrix of feature rows: the UBM that enrolment and the integer scorer start from
+// (GaussianMixture(covariance_type="diag") of the reference's 2fa/audio/speaker/train_ubm.py, its M-step and its stop).
+//
+// Per iteration, from the float64 parameters w, mu, var the float32 E-step model log_const, c = float32(mu), ic = float32(1 / var); then
+//   statistics  one block per group of kUbmGroupChunks chunks of kUbmChunkRows rows.  Lane k of a wave owns component k -- c_k, ic_k and the
+//               accumulators N_k, F_k[d], G_k[d] in registers; per row the posteriors exactly as enroll_stats_kernel takes them, then
+//               N += p, F += p (x - c), G += (p (x - c)) (x - c): moments centred on c (E[x^2] - mean^2 in float32 goes negative at the
+//               variance floor).  Per chunk the four waves combine through LDS in wave order and every thread adds the chunk's float32
+//               sums it owns to float64 accumulators; the group's partial leaves with plain stores.
+//   supers      block s adds groups [s S, (s + 1) S) in ascending order, float64
+//   M-step      one block adds the supers in ascending order and does sklearn's _estimate_gaussian_parameters (diag) in float64, writes
+//               the next parameters, the next float32 model, lower_bounds[i] and the stop decision
+// The tree depends on n alone (ubm_kernels.hpp) and there are no atomics: a fit is the same bits whatever the grid or the workspace.
+// Every kernel tests UbmCtrl::done first, so max_iter iterations are enqueued without a host round trip and those after the stop do nothing.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "ubm_kernels.hpp"
+#include "wave_reduce.hpp"
+
+namespace dsp {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kRowLd = 16;       // floats per staged row: 16-byte reads of a row, whatever d
+
+template <int D>
+__global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__restrict__ feats, long n, const float *__restrict__ model, int k,
+                                                             const UbmCtrl *__restrict__ ctrl, double *__restrict__ groups)
+{
+    constexpr int W = kThreads / 64, Q = (D + 3) / 4, T = 2 * D + 1, S = (kUbmMaxK * T + kThreads - 1) / kThreads;
+    __shared__ __attribute__((aligned(16))) float xs[kUbmChunkRows * kRowLd];
+    extern __shared__ float part[];                                  // per wave: [k][T] (dynamic: W k T floats, so that k = 32 keeps 4 blocks per CU)
+    __shared__ double ll_part[W];                                    // per wave: its rows' sum of ll (wave-uniform)
+    if (ctrl->done) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool live = lane < k;
+    float c[D], ic[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        c[j] = live ? model[k + lane * D + j] : 0.0f;
+        ic[j] = live ? model[k + k * D + lane * D + j] : 0.0f;
+    }
+    const float lc = live ? model[lane] : -INFINITY;                  // lanes at or above k: l = -inf, e = 0
+    const int n_stats = k * T, P = n_stats;
+    double acc[S], ll_acc = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) acc[s] = 0.0;
+    const long row0 = (long)blockIdx.x * kUbmGroupChunks * kUbmChunkRows;
+    for (int cc = 0; cc < kUbmGroupChunks; ++cc) {
+        const long r0 = row0 + (long)cc * kUbmChunkRows;
+        if (r0 >= n) break;
+        const long left = n - r0;
+        const int cnt = left < kUbmChunkRows ? (int)left : kUbmChunkRows;
+        const float *src = feats + r0 * D;
+        for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
+            const int r = i / D;
+            xs[r * kRowLd + (i - r * D)] = src[i];
+        }
+        float N = 0.0f, F[D], G[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) F[j] = G[j] = 0.0f;
+        double ll_sum = 0.0;
+        __syncthreads();
+        for (int r = wave; r < cnt; r += W) {
+            float x[4 * Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const float4 v = *reinterpret_cast<const float4 *>(xs + r * kRowLd + 4 * q);
+                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+            }
+            float s = 0.0f;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {                            // ascending d
+                const float dv = x[j] - c[j];
+                s = __builtin_fmaf(dv * dv, ic[j], s);
+            }
+            const float l = __builtin_fmaf(-0.5f, s, lc);
+            const float m = wave_max(l);
+            const float e = expf(l - m);
+            const float sum = wave_sum(e);
+            const float p = e / sum;
+            ll_sum += (double)(m + logf(sum));
+            N += p;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const float dv = x[j] - c[j];
+                const float pd = p * dv;
+                F[j] += pd;
+                G[j] = __builtin_fmaf(pd, dv, G[j]);
+            }
+        }
+        float *mine = part + wave * P + lane * T;
+        if (live) {
+            mine[0] = N;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                mine[1 + j] = F[j];
+                mine[1 + D + j] = G[j];
+            }
+        }
+        if (lane == 0) ll_part[wave] = ll_sum;
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const int i = threadIdx.x + s * kThreads;
+            if (i < n_stats) {
+                float v = part[i];
+#pragma unroll
+                for (int w = 1; w < W; ++w) v += part[w * P + i];     // wave order
+                acc[s] += (double)v;                                  // ascending chunk
+            }
+        }
+        if (threadIdx.x == 0) {
+            double v = ll_part[0];
+#pragma unroll
+            for (int w = 1; w < W; ++w) v += ll_part[w];
+            ll_acc += v;
+        }
+        // the next chunk's rows may be staged at once: every wave left xs before the barrier above, and `part` is written again only
+        // behind the next one
+    }
+    double *dst = groups + (size_t)blockIdx.x * ((size_t)n_stats + 1);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int i = threadIdx.x + s * kThreads;
+        if (i < n_stats) dst[i] = acc[s];
+    }
+    if (threadIdx.x == 0) dst[n_stats] = ll_acc;
+}
+
+__global__ __launch_bounds__(kThreads) void ubm_supers_kernel(const double *__restrict__ groups, long n_groups, int n_stats, const UbmCtrl *__restrict__ ctrl,
+                                                              double *__restrict__ supers)
+{
+    if (ctrl->done) return;
+    const long g0 = (long)blockIdx.x * kUbmSuperGroups;
+    const long g1 = g0 + kUbmSuperGroups < n_groups ? g0 + kUbmSuperGroups : n_groups;
+    const size_t stride = (size_t)n_stats + 1;
+    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
+        double acc = 0.0;
+        for (long g = g0; g < g1; ++g) acc += groups[(size_t)g * stride + i];         // ascending group
+        supers[(size_t)blockIdx.x * stride + i] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__restrict__ supers, long n_supers, long n, int k, int d, int iter, double tol,
+                                                             double reg_covar, double *__restrict__ params, float *__restrict__ model,
+                                                             double *__restrict__ lower_bounds, UbmCtrl *__restrict__ ctrl)
+{
+    __shared__ double sums[kUbmMaxK * (2 * kUbmMaxD + 1) + 1];
+    __shared__ double n_total;
+    if (ctrl->done) return;
+    const int T = 2 * d + 1, n_stats = k * T;
+    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
+        double acc = 0.0;
+        for (long s = 0; s < n_supers; ++s) acc += supers[(size_t)s * ((size_t)n_stats + 1) + i];      // ascending super
+        sums[i] = acc;
+    }
+    __syncthreads();
+    constexpr double kTiny = 10.0 * DBL_EPSILON;                      // sklearn: nk = resp.sum(axis=0) + 10 * np.finfo(resp.dtype).eps
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int kk = 0; kk < k; ++kk) t += sums[kk * T] + kTiny;
+        n_total = t;
+    }
+    __syncthreads();
+    double *w = params, *mu = params + k, *var = mu + (size_t)k * d, *lcd = var + (size_t)k * d;
+    float *lc = model, *c = model + k, *ic = c + (size_t)k * d;
+    if (threadIdx.x < k) {
+        const int kk = threadIdx.x;
+        const double *st = sums + kk * T;
+        const double n1 = st[0] + kTiny, r = st[0] / n1;
+        double log_det = 0.0;
+        for (int j = 0; j < d; ++j) {                                 // ascending d
+            const double cj = (double)c[kk * d + j];                  // what the statistics were centred on
+            const double delta = st[1 + j] / n1;
+            const double mean = r * cj + delta;
+            const double e2 = st[1 + d + j] / n1 + 2.0 * cj * delta + r * cj * cj;
+            const double v = e2 - mean * mean + reg_covar;
+            mu[kk * d + j] = mean;
+            var[kk * d + j] = v;
+            c[kk * d + j] = (float)mean;
+            ic[kk * d + j] = (float)(1.0 / v);
+            log_det += log(2.0 * M_PI * v);
+        }
+        const double wk = n1 / n_total;
+        const double l = log(wk) - 0.5 * log_det;
+        w[kk] = wk;
+        lcd[kk] = l;
+        lc[kk] = (float)l;
+    }
+    if (threadIdx.x == 0) {
+        const double lb = sums[n_stats] / (double)n;
+        lower_bounds[iter] = lb;
+        ctrl->n_iter = iter + 1;
+        if (fabs(lb - ctrl->prev_lower_bound) < tol) {                // (-inf before the first iteration: never below tol)
+            ctrl->converged = 1;
+            ctrl->done = 1;
+        }
+        ctrl->prev_lower_bound = lb;
+    }
+}
+
+template <int D>
+void launch_stats(const UbmFit &f, unsigned blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(ubm_stats_kernel<D>, dim3(blocks), dim3(kThreads), (size_t)(kThreads / 64) * f.k * (2 * D + 1) * sizeof(float), stream, f.feats, f.n, f.model, f.k, f.ctrl, f.groups);
+}
+
+}  // namespace
+
+hipError_t launch_ubm_iterations(const UbmFit &f, int first, int count, hipStream_t stream)
+{
+    const long n_groups = ubm_groups(f.n), n_supers = ubm_supers(f.n);
+    if (f.k < 1 || f.k > kUbmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
+    const int n_stats = f.k * (2 * f.d + 1);
+    for (int it = first; it < first + count; ++it) {
+        switch (f.d) {
+#define DSP_UBM_D(D) case D: launch_stats<D>(f, (unsigned)n_groups, stream); break;
+        DSP_UBM_D(1) DSP_UBM_D(2) DSP_UBM_D(3) DSP_UBM_D(4) DSP_UBM_D(5) DSP_UBM_D(6) DSP_UBM_D(7) DSP_UBM_D(8)
+        DSP_UBM_D(9) DSP_UBM_D(10) DSP_UBM_D(11) DSP_UBM_D(12) DSP_UBM_D(13) DSP_UBM_D(14) DSP_UBM_D(15) DSP_UBM_D(16)
+#undef DSP_UBM_D
+        default: return hipErrorInvalidValue;
+        }
+        hipLaunchKernelGGL(ubm_supers_kernel, dim3((unsigned)n_supers), dim3(kThreads), 0, stream, f.groups, n_groups, n_stats, f.ctrl, f.supers);
+        hipLaunchKernelGGL(ubm_mstep_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, f.n, f.k, f.d, it, f.tol, f.reg_covar, f.params,
+                           f.model, f.lower_bounds, f.ctrl);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace dsp

@@ -66,6 +66,25 @@ class EnrollConfig(C.Structure):
     _fields_ = [("map_mode", C.c_int), ("relevance_factor", C.c_float), ("fixed_alpha", C.c_float)]
 
 
+class UbmInit(C.Structure):
+    """dsp_ubm_init (include/dsp_amd.h): the caller's start, double arrays."""
+
+    _fields_ = [("weights", C.c_void_p), ("means", C.c_void_p), ("variances", C.c_void_p)]
+
+
+class UbmConfig(C.Structure):
+    """dsp_ubm_config (include/dsp_amd.h)."""
+
+    _fields_ = [("max_iter", C.c_int), ("tol", C.c_double), ("reg_covar", C.c_double)]
+
+
+class UbmResult(C.Structure):
+    """dsp_ubm_result (include/dsp_amd.h): the caller's double arrays and what the fit did."""
+
+    _fields_ = [("gmm", GmmFloatParams), ("weights", C.c_void_p), ("variances", C.c_void_p), ("lower_bounds", C.c_void_p),
+                ("n_iter", C.c_int), ("converged", C.c_int)]
+
+
 class ScanConfig(C.Structure):
     """dsp_scan_config (include/dsp_amd.h): windows of MFCC rows."""
 
@@ -133,6 +152,7 @@ SYMBOLS = [
     "dsp_resample_host",
     "dsp_cmvn_create", "dsp_cmvn_destroy", "dsp_cmvn_ragged_device",
     "dsp_speaker_enroller_create", "dsp_speaker_enroller_destroy", "dsp_speaker_enroll_ragged_device",
+    "dsp_ubm_trainer_create", "dsp_ubm_trainer_destroy", "dsp_ubm_init_rows_device", "dsp_ubm_train_device", "dsp_gmm_quantize",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -284,6 +304,12 @@ def load() -> C.CDLL:
     L.dsp_speaker_enroller_destroy.argtypes = [vp]; L.dsp_speaker_enroller_destroy.restype = None
     L.dsp_speaker_enroll_ragged_device.argtypes = [vp, vp, C.c_long, lp, C.POINTER(EnrollConfig), vp, vp, vp, vp, vp, vp]
     L.dsp_speaker_enroll_ragged_device.restype = ip
+    L.dsp_ubm_trainer_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_ubm_trainer_create.restype = ip
+    L.dsp_ubm_trainer_destroy.argtypes = [vp]; L.dsp_ubm_trainer_destroy.restype = None
+    L.dsp_ubm_init_rows_device.argtypes = [vp, vp, C.c_long, C.c_double, vp, vp, vp, vp]; L.dsp_ubm_init_rows_device.restype = ip
+    L.dsp_ubm_train_device.argtypes = [vp, vp, C.c_long, C.POINTER(UbmInit), C.POINTER(UbmConfig), C.POINTER(UbmResult), vp]
+    L.dsp_ubm_train_device.restype = ip
+    L.dsp_gmm_quantize.argtypes = [C.POINTER(GmmFloatParams), vp, vp, vp, C.POINTER(C.c_int)]; L.dsp_gmm_quantize.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

@@ -696,7 +696,8 @@ int dsp_cmvn_ragged_device(dsp_cmvn *c, const float *d_in, long n_recordings, co
  * A speaker without rows: DSP_EINVAL naming the first.  Zero speakers: DSP_OK, no launch.  There are no float atomics: a speaker's rows
  * are summed in chunks of 256 rows cut by its own row count and combined in a fixed order, so every output of a speaker is bit-identical
  * whatever the batch around it.  The enroller owns a grow-only workspace: ONE stream at a time per enroller.
- * Not covered: UBM training (EM), variance or weight adaptation, a float log-sum-exp scorer, CMVN inside scanners or stream sessions. */
+ * Not covered: variance or weight adaptation, a float log-sum-exp scorer, CMVN inside scanners or stream sessions (the UBM itself is
+ * trained by dsp_ubm_train_device below). */
 typedef struct dsp_gmm_float_params {
     int k, d;                    /* k <= 64, d <= 16, as dsp_gmm_params */
     const double *log_consts;    /* [k]    */
@@ -715,6 +716,76 @@ void dsp_speaker_enroller_destroy(dsp_speaker_enroller *e);
 int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_feats, long n_speakers, const long *frame_offsets,
                                      const dsp_enroll_config *cfg, float *d_means, int8_t *d_means_q6, float *d_counts, float *d_ll_mean,
                                      int *d_saturated, void *stream);
+
+/* --- training the UBM: EM for a diagonal GMM, and its integer tables ---
+ * The step in front of dsp_speaker_enroller_create and dsp_speaker_model_create: feature rows of a population -> the float UBM the
+ * enroller takes and the Q6 / Q11 / Q8 tables the integer scorer takes.  GaussianMixture(covariance_type="diag") of the reference's
+ * 2fa/audio/speaker/train_ubm.py: sklearn's M-step (_estimate_gaussian_parameters) and its stopping rule, from a start the caller gives
+ * or the library's deterministic one.
+ *
+ * Input: rows d_feats[n][d], float32 on the device, one flat matrix (CMVN'd rows of all recordings, stacked); k <= 64, d <= 16, n >= k.
+ * The parameters w[k], mu[k][d], var[k][d] are float64 on the device between iterations.  Iteration i = 1, 2, ...:
+ *   1. the E-step model, rounded once to float32: log_const_k = log w_k - 0.5 sum_d log(2 pi var_kd) (float64, then rounded),
+ *      c_kd = float32(mu_kd), ic_kd = float32(1 / var_kd);
+ *   2. per row, in float32, as the enroller: l_k = log_const_k - 0.5 sum_d (x_d - c_kd)^2 ic_kd (ascending d), m = max_k l_k,
+ *      e_k = exp(l_k - m), S = sum_k e_k, p_k = e_k / S, ll = m + log S;
+ *   3. over all rows, centred on c: N_k = sum_t p_k, F_kd = sum_t p_k (x_d - c_kd), G_kd = sum_t p_k (x_d - c_kd)^2, L = sum_t ll;
+ *   4. in float64: N'_k = N_k + 10 DBL_EPSILON, r_k = N_k / N'_k, delta_kd = F_kd / N'_k, mean_kd = r_k c_kd + delta_kd,
+ *      E2_kd = G_kd / N'_k + 2 c_kd delta_kd + r_k c_kd^2, var_kd = E2_kd - mean_kd^2 + reg_covar, w_k = N'_k / sum_j N'_j
+ *      (a component no row visits gets mean 0, variance reg_covar and a weight of about 1e-15 / n, as in sklearn);
+ *   5. lower_bound_i = L / n; stop after iteration i when | lower_bound_i - lower_bound_(i-1) | < tol (lower_bound_0 = -inf): converged = 1,
+ *      n_iter = i; otherwise after max_iter iterations with converged = 0.  The model returned is the one AFTER the last M-step.
+ * Sums: float32 inside a chunk of 256 rows (chunk c = rows [256 c, min(n, 256 c + 256)), the four waves' interleaved rows combined in
+ * wave order), float64 above it in a fixed tree -- 16 consecutive chunks to a group, 32 consecutive groups to a super, the supers in
+ * ascending order, every level in ascending order.  The tree depends on n alone: there are no float atomics, and a fit is bit-identical
+ * whatever the grid, the device's CU count, the rows' address or what the workspace held before.  L is summed in float64 throughout.
+ * The iterations are enqueued on `stream` without a host round trip each (every launch tests a stop flag on the device first); the host
+ * looks at the flag every 32 iterations, and the call returns when the result is in the caller's arrays.
+ *
+ * The start: dsp_ubm_init (weights > 0 that sum to 1 within 1e-6, means, variances > 0, all finite), or DSP_UBM_INIT_ROWS (NULL) for
+ * the library's own, which dsp_ubm_init_rows_device also writes out: means_i = row floor((i + 0.5) n / k), variances = the rows' global
+ * variance per dimension + reg_covar (one k = 1 iteration of the same kernels from mean = row floor(n / 2), variance 1), weights 1 / k.
+ * sklearn's k-means initialisation and its n_init restarts are not built: restart by calling again with another dsp_ubm_init and keep
+ * the fit with the larger last lower bound.
+ *
+ * dsp_ubm_result: the caller's arrays.  gmm is the dsp_gmm_float_params of the trained model (k and d are set, log_consts[k], means[k][d]
+ * and inv_covs[k][d] = 1 / variances are written through the pointers, which must point at writable doubles): &result.gmm goes to
+ * dsp_speaker_enroller_create and dsp_gmm_quantize unchanged.  lower_bounds[max_iter]: entries [0, n_iter) are written, the rest untouched.
+ * dsp_ubm_trainer_create touches no device and allocates nothing; the trainer's workspace is grow-only: ONE stream at a time per trainer.
+ *
+ * dsp_gmm_quantize (host only, no GPU): any float GMM -> the tables of dsp_gmm_params in the integer scorer's formats,
+ *   means = rint(64 mean) -> int8,  inv_covs = rint(2048 inv_cov) -> int32,  log_consts = rint(256 log_const) -> int16,
+ * ties to even, each table saturated to its type; saturated[3] = the entries clamped in means, inv_covs, log_consts.  2048 / 1e-6 fits
+ * int32; a reg_covar below about 9.6e-7 may not, which is what the count is for.
+ * Not covered: k-means initialisation and n_init restarts, full or tied covariances, variance and weight adaptation at enrolment,
+ * multi-GPU training (the statistics are summable, the tree is not defined across devices), the n_fft-400 librosa front end, CMVN
+ * inside scanners or streams. */
+typedef struct dsp_ubm_init {
+    const double *weights;       /* [k]    */
+    const double *means;         /* [k][d] */
+    const double *variances;     /* [k][d] */
+} dsp_ubm_init;
+#define DSP_UBM_INIT_ROWS ((const dsp_ubm_init *)0)
+typedef struct dsp_ubm_config {
+    int max_iter;                /* >= 1; 300 in train_ubm.py            */
+    double tol;                  /* >= 0; sklearn's default 1e-3         */
+    double reg_covar;            /* >= 0, finite; sklearn's default 1e-6 */
+} dsp_ubm_config;
+typedef struct dsp_ubm_result {
+    dsp_gmm_float_params gmm;    /* k, d (set), log_consts[k], means[k][d], inv_covs[k][d] (written) */
+    double *weights;             /* [k]        */
+    double *variances;           /* [k][d]     */
+    double *lower_bounds;        /* [max_iter] */
+    int n_iter, converged;
+} dsp_ubm_result;
+typedef struct dsp_ubm_trainer dsp_ubm_trainer;
+int dsp_ubm_trainer_create(int device, int k, int d, dsp_ubm_trainer **out);
+void dsp_ubm_trainer_destroy(dsp_ubm_trainer *t);
+int dsp_ubm_init_rows_device(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means,
+                             double *variances, void *stream);
+int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_ubm_init *init, const dsp_ubm_config *cfg,
+                         dsp_ubm_result *result, void *stream);
+int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_covs, int16_t *log_consts, int saturated[3]);
 
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
