@@ -470,6 +470,17 @@ class Cmvn:
         return out
 
 
+def _gmm_float_params(params: dict, name: str):
+    """float GMM dict -> (GmmFloatParams, k, d, the float64 arrays its pointers point into: to be kept until the struct has been read)"""
+    keep = {key: np.ascontiguousarray(params[key], np.float64) for key in ("log_consts", "means", "inv_covs")}
+    if keep["means"].ndim != 2 or keep["inv_covs"].shape != keep["means"].shape or keep["log_consts"].shape != keep["means"].shape[:1]:
+        raise ValueError(f"{name}: means and inv_covs must be [k][d], log_consts [k]")
+    k, d = keep["means"].shape
+    if not (1 <= k <= 64 and 1 <= d <= 16):
+        raise ValueError(f"{name}: k must be 1 .. 64 and d 1 .. 16")
+    return _lib.GmmFloatParams(k, d, *(keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))), k, d, keep
+
+
 class SpeakerEnroller:
     """dsp_speaker_enroller: MAP adaptation of a float UBM's means to each speaker of a ragged matrix of (CMVN'd) feature rows."""
 
@@ -478,15 +489,7 @@ class SpeakerEnroller:
     def __init__(self, ubm_float: dict, device: int = 0):
         """ubm_float: log_consts [k], means [k][d], inv_covs [k][d] -- the DOUBLE_GMM arrays of gmm_params.inc (log_consts = log w -
         0.5 sum log(2 pi var), inv_covs = 1 / var)."""
-        keep = {key: np.ascontiguousarray(ubm_float[key], np.float64) for key in ("log_consts", "means", "inv_covs")}
-        if keep["means"].ndim != 2 or keep["inv_covs"].shape != keep["means"].shape or keep["log_consts"].shape != keep["means"].shape[:1]:
-            raise ValueError("ubm_float: means and inv_covs must be [k][d], log_consts [k]")
-        k, d = keep["means"].shape
-        if not (1 <= k <= 64 and 1 <= d <= 16):
-            raise ValueError("ubm_float: k must be 1 .. 64 and d 1 .. 16")
-        p = _lib.GmmFloatParams()
-        p.k, p.d = k, d
-        p.log_consts, p.means, p.inv_covs = (keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+        p, k, d, _keep = _gmm_float_params(ubm_float, "ubm_float")
         self._L = _lib.load()
         h = C.c_void_p()
         _lib.check(self._L.dsp_speaker_enroller_create(C.byref(p), int(device), C.byref(h)), "dsp_speaker_enroller_create")
@@ -631,15 +634,7 @@ def quantize_gmm(float_params: dict):
     """Host only (dsp_gmm_quantize): a float GMM (log_consts [k], means [k][d], inv_covs [k][d]; a UbmTrainer.fit result as it is) ->
     (ubm_int, saturated): the integer scorer's tables means int8 = rint(64 mean), inv_covs int32 = rint(2048 inv_cov), log_consts int16 =
     rint(256 log_const), ties to even, each saturated to its type, and the number of entries clamped per table in that order."""
-    keep = {key: np.ascontiguousarray(float_params[key], np.float64) for key in ("log_consts", "means", "inv_covs")}
-    if keep["means"].ndim != 2 or keep["inv_covs"].shape != keep["means"].shape or keep["log_consts"].shape != keep["means"].shape[:1]:
-        raise ValueError("float_params: means and inv_covs must be [k][d], log_consts [k]")
-    k, d = keep["means"].shape
-    if not (1 <= k <= 64 and 1 <= d <= 16):
-        raise ValueError("float_params: k must be 1 .. 64 and d 1 .. 16")
-    p = _lib.GmmFloatParams()
-    p.k, p.d = k, d
-    p.log_consts, p.means, p.inv_covs = (keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+    p, k, d, _keep = _gmm_float_params(float_params, "float_params")
     out = {"means": np.empty((k, d), np.int8), "inv_covs": np.empty((k, d), np.int32), "log_consts": np.empty(k, np.int16)}
     sat = (C.c_int * 3)()
     _lib.check(_lib.load().dsp_gmm_quantize(C.byref(p), out["means"].ctypes.data, out["inv_covs"].ctypes.data, out["log_consts"].ctypes.data, sat),

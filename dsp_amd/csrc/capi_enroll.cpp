@@ -1,6 +1,6 @@
 // capi_enroll.cpp -- the C ABI of sliding CMVN and of MAP speaker enrolment (include/dsp_amd.h dsp_cmvn_*, dsp_speaker_enroll*; DESIGN.md
-// 3.11): argument checks, the spans of a ragged batch through the handle's ring, the enroller's grow-only workspace, and the launches of
-// enroll_kernels.hip.
+// 3.11): argument checks, the spans of a ragged batch through the handle's ring, the enroller's grow-only workspace (the UBM: a GmmModel of
+// gmm_model.hpp), and the launches of enroll_kernels.hip.
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -51,7 +51,7 @@ int dsp_cmvn_create(int device, int d, int window, dsp_cmvn **out)
 {
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
-    if (d < 1 || d > dsp::kEnrollMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16");
+    if (d < 1 || d > dsp::kGmmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16");
     if (window < 2 || window > dsp::kCmvnMaxWindow)
         return capi_fail(DSP_EINVAL, "window must be 2 .. " + std::to_string(dsp::kCmvnMaxWindow) + " rows (what one block's LDS image holds), got " + std::to_string(window));
     if (const int rc = dsp::check_device(device)) return rc;
@@ -92,16 +92,9 @@ int dsp_speaker_enroller_create(const dsp_gmm_float_params *ubm, int device, dsp
 {
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
-    if (!ubm || !ubm->log_consts || !ubm->means || !ubm->inv_covs) return capi_fail(DSP_EINVAL, "ubm and its arrays must not be NULL");
-    if (ubm->k < 1 || ubm->k > dsp::kEnrollMaxK) return capi_fail(DSP_EINVAL, "ubm: k must be 1 .. 64, got " + std::to_string(ubm->k));
-    if (ubm->d < 1 || ubm->d > dsp::kEnrollMaxD) return capi_fail(DSP_EINVAL, "ubm: d must be 1 .. 16, got " + std::to_string(ubm->d));
+    if (const int rc = dsp::check_gmm_float_params(ubm, "ubm", "ubm: ")) return rc;
     const int k = ubm->k, d = ubm->d;
-    std::vector<float> host((size_t)k * (2 * d + 1));
-    for (int i = 0; i < k; ++i) host[(size_t)i] = (float)ubm->log_consts[i];
-    for (int i = 0; i < k * d; ++i) {
-        host[(size_t)k + i] = (float)ubm->means[i];
-        host[(size_t)k + (size_t)k * d + i] = (float)ubm->inv_covs[i];
-    }
+    const std::vector<float> host = dsp::pack_gmm_model(k, d, ubm->log_consts, ubm->means, ubm->inv_covs);
     for (const float v : host)
         if (!std::isfinite(v)) return capi_fail(DSP_EINVAL, "ubm: log_consts, means and inv_covs must be finite in float32");
     if (const int rc = dsp::check_device(device)) return rc;
@@ -150,9 +143,7 @@ int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_fea
     if (e->partials.reserve((size_t)chunks * dsp::enroll_partial_floats(e->k, e->d) * sizeof(float)) != hipSuccess)
         return capi_fail(DSP_ENOMEM, "hipMalloc of the enroller's workspace");
     DSP_CAPI_HIP(slot.upload((size_t)n_speakers * sizeof(dsp::RowSpan), (hipStream_t)stream));
-    const float *m = e->model;
-    const dsp::EnrollUbm ubm{m, m + e->k, m + e->k + (size_t)e->k * e->d, e->k, e->d};
-    DSP_CAPI_HIP(dsp::launch_enroll(d_feats, static_cast<const dsp::RowSpan *>(slot.d()), n_speakers, chunks, ubm, e->partials,
+    DSP_CAPI_HIP(dsp::launch_enroll(d_feats, static_cast<const dsp::RowSpan *>(slot.d()), n_speakers, chunks, dsp::GmmModel{e->model, e->k, e->d}, e->partials,
                                     cfg->map_mode == DSP_MAP_FIXED_ALPHA, param, d_means, d_means_q6, d_counts, d_ll_mean, d_saturated, (hipStream_t)stream));
     return DSP_OK;
 }

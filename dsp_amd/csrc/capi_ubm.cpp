@@ -1,6 +1,6 @@
 // capi_ubm.cpp -- the C ABI of UBM training and of the GMM quantiser (include/dsp_amd.h dsp_ubm_*, dsp_gmm_quantize):
 // argument checks, the trainer's grow-only workspace, the initial model, the enqueueing of the EM iterations of ubm_kernels.hip and the
-// one synchronisation that reads the result back.
+// one synchronisation that reads the result back.  The E-step model is a GmmModel (gmm_model.hpp), as capi_enroll.cpp's UBM is.
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -34,22 +34,21 @@ HostModel host_model(int k, int d, const double *w, const double *mu, const doub
 {
     HostModel m;
     m.params.resize(dsp::ubm_param_doubles(k, d));
-    m.model.resize(dsp::ubm_model_floats(k, d));
     const size_t kd = (size_t)k * d;
+    std::vector<double> inv_var(kd);
     for (int i = 0; i < k; ++i) {
         double log_det = 0.0;
         for (int j = 0; j < d; ++j) log_det += std::log(2.0 * M_PI * var[(size_t)i * d + j]);
         const double lc = std::log(w[i]) - 0.5 * log_det;
         m.params[i] = w[i];
         m.params[(size_t)k + 2 * kd + i] = lc;
-        m.model[i] = (float)lc;
     }
     for (size_t i = 0; i < kd; ++i) {
         m.params[(size_t)k + i] = mu[i];
         m.params[(size_t)k + kd + i] = var[i];
-        m.model[(size_t)k + i] = (float)mu[i];
-        m.model[(size_t)k + kd + i] = (float)(1.0 / var[i]);
+        inv_var[i] = 1.0 / var[i];
     }
+    m.model = dsp::pack_gmm_model(k, d, m.params.data() + k + 2 * kd, mu, inv_var.data());
     return m;
 }
 
@@ -63,14 +62,14 @@ int run_em(dsp_ubm_trainer *t, int k, const float *d_feats, long n, const double
     const long n_groups = dsp::ubm_groups(n), n_supers = dsp::ubm_supers(n);
     if (t->partials.reserve((size_t)(n_groups + n_supers) * stride * sizeof(double)) != hipSuccess ||
         t->state.reserve((n_params + (size_t)max_iter) * sizeof(double)) != hipSuccess ||
-        t->model.reserve(dsp::ubm_model_floats(t->k, d) * sizeof(float)) != hipSuccess || t->ctrl.reserve(sizeof(dsp::UbmCtrl)) != hipSuccess)
+        t->model.reserve(dsp::gmm_model_floats(t->k, d) * sizeof(float)) != hipSuccess || t->ctrl.reserve(sizeof(dsp::UbmCtrl)) != hipSuccess)
         return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's workspace");
     const HostModel m = host_model(k, d, w, mu, var);
     const dsp::UbmCtrl start{0, 0, 0, 0, -std::numeric_limits<double>::infinity()};
     DSP_CAPI_HIP(hipMemcpyAsync(t->state, m.params.data(), n_params * sizeof(double), hipMemcpyHostToDevice, stream));
     DSP_CAPI_HIP(hipMemcpyAsync(t->model, m.model.data(), m.model.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     DSP_CAPI_HIP(hipMemcpyAsync(t->ctrl, &start, sizeof(start), hipMemcpyHostToDevice, stream));
-    dsp::UbmFit fit{d_feats, n, k, d, t->state, t->model, t->partials, t->partials.get() + (size_t)n_groups * stride, t->state.get() + n_params,
+    dsp::UbmFit fit{d_feats, n, t->state, dsp::GmmModelOut{t->model, k, d}, t->partials, t->partials.get() + (size_t)n_groups * stride, t->state.get() + n_params,
                     t->ctrl, tol, reg_covar};
     dsp::UbmCtrl end = start;
     for (int first = 0; first < max_iter && !end.done; first += kIterationsPerLook) {
@@ -140,8 +139,8 @@ int dsp_ubm_trainer_create(int device, int k, int d, dsp_ubm_trainer **out)
 {
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
-    if (k < 1 || k > dsp::kUbmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(k));
-    if (d < 1 || d > dsp::kUbmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(d));
+    if (k < 1 || k > dsp::kGmmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(k));
+    if (d < 1 || d > dsp::kGmmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(d));
     if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
     // nothing is allocated here and no device is touched: the workspace grows in the first call that trains, which is also where a
     // device that does not exist is reported
@@ -195,8 +194,8 @@ int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const
             if (!(init->variances[i] > 0.0)) return capi_fail(DSP_EINVAL, "dsp_ubm_init: variances must be > 0 (component " + std::to_string(i / d) + ")");
         }
     }
-    if (!result || !result->weights || !result->variances || !result->lower_bounds || !result->gmm.log_consts || !result->gmm.means || !result->gmm.inv_covs)
-        return capi_fail(DSP_EINVAL, "dsp_ubm_result and its arrays must not be NULL");
+    if (!result || !result->weights || !result->variances || !result->lower_bounds) return capi_fail(DSP_EINVAL, "dsp_ubm_result and its arrays must not be NULL");
+    if (const int rc = dsp::check_gmm_float_arrays(&result->gmm, "dsp_ubm_result")) return rc;      // (k and d are the call's to write)
     if (const int rc = dsp::check_device(t->device)) return rc;
     DSP_ON_DEVICE(t->device);
     std::vector<double> start;
@@ -234,9 +233,7 @@ int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const
 
 int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_covs, int16_t *log_consts, int saturated[3])
 {
-    if (!g || !g->log_consts || !g->means || !g->inv_covs) return capi_fail(DSP_EINVAL, "the float GMM and its arrays must not be NULL");
-    if (g->k < 1 || g->k > dsp::kUbmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(g->k));
-    if (g->d < 1 || g->d > dsp::kUbmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(g->d));
+    if (const int rc = dsp::check_gmm_float_params(g, "the float GMM", "")) return rc;
     if (!means || !inv_covs || !log_consts || !saturated) return capi_fail(DSP_EINVAL, "means, inv_covs, log_consts and saturated must not be NULL");
     const size_t kd = (size_t)g->k * g->d;
     for (size_t i = 0; i < kd; ++i)

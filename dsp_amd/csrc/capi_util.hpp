@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/dsp_amd.h"
+#include "gmm_model.hpp"
 
 namespace dsp {
 int capi_fail(int code, const std::string &msg);   // sets dsp_last_error() for this thread, returns code
@@ -111,6 +112,19 @@ inline int check_device(int device)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return capi_fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
     if (device < 0 || device >= n) return capi_fail(DSP_EINVAL, "device index out of range");
+    return DSP_OK;
+}
+
+// a caller's float GMM: DSP_EINVAL "<who> and its arrays must not be NULL"; handed in as a model, then "<prefix>k must be 1 .. 64, got <k>", and d
+inline int check_gmm_float_arrays(const dsp_gmm_float_params *g, const char *who)
+{
+    return g && g->log_consts && g->means && g->inv_covs ? DSP_OK : capi_fail(DSP_EINVAL, std::string(who) + " and its arrays must not be NULL");
+}
+inline int check_gmm_float_params(const dsp_gmm_float_params *g, const char *who, const char *prefix)
+{
+    if (const int rc = check_gmm_float_arrays(g, who)) return rc;
+    if (g->k < 1 || g->k > kGmmMaxK) return capi_fail(DSP_EINVAL, std::string(prefix) + "k must be 1 .. 64, got " + std::to_string(g->k));
+    if (g->d < 1 || g->d > kGmmMaxD) return capi_fail(DSP_EINVAL, std::string(prefix) + "d must be 1 .. 16, got " + std::to_string(g->d));
     return DSP_OK;
 }
 

@@ -8,16 +8,16 @@
 //
 // Enrolment (map_adapt_gmm of the reference's adapt_ubm.py scripts, means only): per row the posteriors of the k components under the
 // UBM, per speaker N_k = sum_t p_k and F_k = sum_t p_k x, then mean_k = alpha_k F_k / N'_k + (1 - alpha_k) mu_k.
-//   statistics  one block per chunk of kEnrollChunkRows rows of one speaker.  Lane k of a wave owns component k -- mu_k, 1 / var_k and the
-//               accumulators N_k, F_k[d] in registers; the four waves take interleaved rows of the chunk from an LDS image (every lane
-//               reads the same address: a broadcast), max and sum over the lanes by DPP / permlane moves, and combine through LDS in
-//               wave order.  The chunk's partial goes to the workspace with plain stores: no atomics anywhere.
+//   statistics  one block per chunk of kEnrollChunkRows rows of one speaker.  The E-step is gmm_estep.hpp's: lane k of a wave owns
+//               component k and the accumulators N_k, F_k[d] in registers; the four waves take interleaved rows of the chunk from an LDS
+//               image and combine through LDS in wave order.  The chunk's partial goes to the workspace with plain stores: no atomics
+//               anywhere.
 //   finalise    one block per speaker sums its chunks' partials in ascending chunk order in float64 and does the MAP update, the Q6
 //               rounding, the saturation count and the mean of ll.
 // The chunks of a speaker depend on its own row count alone and every sum has a fixed order, so a speaker's outputs are the same bits
 // whatever the batch around it.
 //
-// Out of scope: variance or weight adaptation (the UBM itself: ubm_kernels.hip); the n_fft-400 librosa front end (these kernels take whatever MFCC
+// Out of scope: variance or weight adaptation (the UBM itself is trained by ubm_kernels.hip); the n_fft-400 librosa front end (these kernels take whatever MFCC
 // matrix the existing entries wrote and leave every front end alone); CMVN inside scanners or stream sessions (a stream needs a 150-row
 // look-ahead); a float log-sum-exp scorer; CMVN fused into the statistics pass.  No existing speaker scoring entry, nor any result of
 // one, changes: the enrolled Q6 means go to dsp_speaker_model_create as any other target's.
@@ -27,13 +27,10 @@
 #include <cstdint>
 
 #include "enroll_kernels.hpp"
-#include "mfcc_device.hpp"
-#include "wave_reduce.hpp"
+#include "gmm_estep.hpp"
 
 namespace dsp {
 namespace {
-
-constexpr int kThreads = 256;
 
 // the recording / speaker that owns unit u: the last one whose first unit is <= u (those without rows own no unit)
 __device__ inline long owner_of_unit(const RowSpan *spans, long n, long u)
@@ -97,13 +94,11 @@ __global__ __launch_bounds__(kThreads) void cmvn_kernel(const float *__restrict_
     }
 }
 
-constexpr int kRowLd = 16;       // floats per staged row: 16-byte reads of a row, whatever d
-
 template <int D>
 __global__ __launch_bounds__(kThreads) void enroll_stats_kernel(const float *__restrict__ feats, const RowSpan *__restrict__ spans, long n_spk,
-                                                                long chunk_base, EnrollUbm ubm, float *__restrict__ partials)
+                                                                long chunk_base, GmmModel ubm, float *__restrict__ partials)
 {
-    constexpr int W = kThreads / 64, Q = (D + 3) / 4, P = 64 * (D + 1);
+    constexpr int W = kThreads / 64, P = 64 * (D + 1);
     __shared__ __attribute__((aligned(16))) float xs[kEnrollChunkRows * kRowLd];
     __shared__ float part[W * P];                                    // per wave: [lane][D + 1]
     __shared__ double ll_part[W];                                    // per wave: its rows' sum of ll (wave-uniform, kept in float64)
@@ -112,43 +107,18 @@ __global__ __launch_bounds__(kThreads) void enroll_stats_kernel(const float *__r
     const long r0 = (c - sp.unit0) * kEnrollChunkRows;
     const long left = sp.n - r0;
     const int cnt = left < kEnrollChunkRows ? (int)left : kEnrollChunkRows;
-    const float *src = feats + (sp.row0 + r0) * D;
-    for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
-        const int r = i / D;
-        xs[r * kRowLd + (i - r * D)] = src[i];
-    }
+    stage_rows<D>(xs, feats + (sp.row0 + r0) * D, cnt);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = ubm.k;
-    const bool live = lane < k;
-    float mu[D], ic[D], F[D];
+    const LaneGmm<D> g(ubm, lane);
+    float N = 0.0f, F[D];
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-        mu[j] = live ? ubm.means[lane * D + j] : 0.0f;
-        ic[j] = live ? ubm.inv_covs[lane * D + j] : 0.0f;
-        F[j] = 0.0f;
-    }
-    const float lc = live ? ubm.log_consts[lane] : -INFINITY;         // lanes at or above k: l = -inf, e = 0
-    float N = 0.0f;
+    for (int j = 0; j < D; ++j) F[j] = 0.0f;
     double ll_sum = 0.0;
     __syncthreads();
     for (int r = wave; r < cnt; r += W) {
-        float x[4 * Q];
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const float4 v = *reinterpret_cast<const float4 *>(xs + r * kRowLd + 4 * q);
-            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-        }
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < D; ++j) {                                // ascending d
-            const float dv = x[j] - mu[j];
-            s = __builtin_fmaf(dv * dv, ic[j], s);
-        }
-        const float l = __builtin_fmaf(-0.5f, s, lc);
-        const float m = wave_max(l);
-        const float e = expf(l - m);
-        const float S = wave_sum(e);
-        const float p = e / S;
-        ll_sum += (double)(m + logf(S));
+        float x[4 * ((D + 3) / 4)], ll;
+        const float p = row_posterior<D>(xs, r, g, x, ll);
+        ll_sum += (double)ll;
         N += p;
 #pragma unroll
         for (int j = 0; j < D; ++j) F[j] = __builtin_fmaf(p, x[j], F[j]);
@@ -161,25 +131,15 @@ __global__ __launch_bounds__(kThreads) void enroll_stats_kernel(const float *__r
     __syncthreads();
     float *dst = partials + (size_t)c * ((size_t)k * (D + 1) + 1);
     const int n_stats = k * (D + 1);
-    for (int i = threadIdx.x; i < n_stats; i += kThreads) {
-        float v = part[i];
-#pragma unroll
-        for (int w = 1; w < W; ++w) v += part[w * P + i];             // wave order
-        dst[i] = v;
-    }
-    if (threadIdx.x == 0) {
-        double v = ll_part[0];
-#pragma unroll
-        for (int w = 1; w < W; ++w) v += ll_part[w];
-        dst[n_stats] = (float)v;
-    }
+    for (int i = threadIdx.x; i < n_stats; i += kThreads) dst[i] = sum_waves(part, P, i);
+    if (threadIdx.x == 0) dst[n_stats] = (float)sum_waves(ll_part, 1, 0);
 }
 
-__global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const RowSpan *__restrict__ spans, EnrollUbm ubm, const float *__restrict__ partials,
+__global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const RowSpan *__restrict__ spans, GmmModel ubm, const float *__restrict__ partials,
                                                                    int map_fixed, float param, float *__restrict__ means, int8_t *__restrict__ means_q6,
                                                                    float *__restrict__ counts, float *__restrict__ ll_mean, int *__restrict__ saturated)
 {
-    __shared__ double sums[kEnrollMaxK * (kEnrollMaxD + 1) + 1];
+    __shared__ double sums[kGmmMaxK * (kGmmMaxD + 1) + 1];
     __shared__ int clamped;
     const long spk = blockIdx.x;
     const RowSpan sp = spans[spk];
@@ -187,18 +147,14 @@ __global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const RowSpan
     const long n_chunks = (sp.n + kEnrollChunkRows - 1) / kEnrollChunkRows;
     const float *src = partials + (size_t)sp.unit0 * (size_t)(n_stats + 1);
     if (threadIdx.x == 0) clamped = 0;
-    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
-        double acc = 0.0;
-        for (long c = 0; c < n_chunks; ++c) acc += (double)src[(size_t)c * (size_t)(n_stats + 1) + i];      // ascending chunk
-        sums[i] = acc;
-    }
+    sum_partials(src, n_chunks, (size_t)(n_stats + 1), n_stats + 1, sums);      // ascending chunk
     __syncthreads();
     int mine = 0;
     for (int i = threadIdx.x; i < k * d; i += kThreads) {
         const int kk = i / d, j = i - kk * d;
         const double n1 = sums[kk * (d + 1)] + 1e-8;
         const double alpha = map_fixed ? (double)param : n1 / (n1 + (double)param);
-        const double mean = alpha * (sums[kk * (d + 1) + 1 + j] / n1) + (1.0 - alpha) * (double)ubm.means[i];
+        const double mean = alpha * (sums[kk * (d + 1) + 1 + j] / n1) + (1.0 - alpha) * (double)ubm.means()[i];
         const float mean32 = (float)mean;
         const size_t at = (size_t)spk * (size_t)(k * d) + i;
         if (means) means[at] = mean32;
@@ -216,26 +172,20 @@ __global__ __launch_bounds__(kThreads) void enroll_finalize_kernel(const RowSpan
     }
 }
 
-template <int D>
-void launch_stats(const float *feats, const RowSpan *spans, long n_spk, long base, unsigned blocks, const EnrollUbm &ubm, float *partials, hipStream_t stream)
-{
-    hipLaunchKernelGGL(enroll_stats_kernel<D>, dim3(blocks), dim3(kThreads), 0, stream, feats, spans, n_spk, base, ubm, partials);
-}
-
 }  // namespace
 
 hipError_t prepare_cmvn()
 {
     // images above 64 KiB (windows from about 960 rows at d = 16) need the kernel's dynamic LDS limit raised: to the widest image, the
     // rows and the 4 floats of the alignment shift.  Idempotent, per device.
-    constexpr int kMaxLds = ((kCmvnTileRows + kCmvnMaxWindow) * kEnrollMaxD + 4) * 4;
+    constexpr int kMaxLds = ((kCmvnTileRows + kCmvnMaxWindow) * kGmmMaxD + 4) * 4;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(cmvn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 }
 
 hipError_t launch_cmvn(const float *d_in, const RowSpan *d_spans, long n_rec, long total_tiles, int d, int window, float *d_out, hipStream_t stream)
 {
     constexpr long kMaxBlocks = 1L << 30;
-    if (d < 1 || d > kEnrollMaxD || window < 2 || window > kCmvnMaxWindow) return hipErrorInvalidValue;
+    if (d < 1 || d > kGmmMaxD || window < 2 || window > kCmvnMaxWindow) return hipErrorInvalidValue;
     const int half = window / 2;
     const size_t lds = ((size_t)(kCmvnTileRows + 2 * half) * d + 4) * 4;
     for (long base = 0; base < total_tiles; base += kMaxBlocks) {
@@ -247,22 +197,18 @@ hipError_t launch_cmvn(const float *d_in, const RowSpan *d_spans, long n_rec, lo
     return hipSuccess;
 }
 
-hipError_t launch_enroll(const float *d_feats, const RowSpan *d_spans, long n_speakers, long total_chunks, const EnrollUbm &ubm, float *d_partials,
+hipError_t launch_enroll(const float *d_feats, const RowSpan *d_spans, long n_speakers, long total_chunks, const GmmModel &ubm, float *d_partials,
                          int map_fixed, float param, float *d_means, int8_t *d_means_q6, float *d_counts, float *d_ll_mean, int *d_saturated,
                          hipStream_t stream)
 {
     constexpr long kMaxBlocks = 1L << 30;
-    if (ubm.k < 1 || ubm.k > kEnrollMaxK || n_speakers > kMaxBlocks) return hipErrorInvalidValue;
+    if (ubm.k < 1 || ubm.k > kGmmMaxK || n_speakers > kMaxBlocks) return hipErrorInvalidValue;
     for (long base = 0; base < total_chunks; base += kMaxBlocks) {
         const unsigned blocks = (unsigned)(total_chunks - base < kMaxBlocks ? total_chunks - base : kMaxBlocks);
-        switch (ubm.d) {
-#define DSP_ENROLL_D(D) case D: launch_stats<D>(d_feats, d_spans, n_speakers, base, blocks, ubm, d_partials, stream); break;
-        DSP_ENROLL_D(1) DSP_ENROLL_D(2) DSP_ENROLL_D(3) DSP_ENROLL_D(4) DSP_ENROLL_D(5) DSP_ENROLL_D(6) DSP_ENROLL_D(7) DSP_ENROLL_D(8)
-        DSP_ENROLL_D(9) DSP_ENROLL_D(10) DSP_ENROLL_D(11) DSP_ENROLL_D(12) DSP_ENROLL_D(13) DSP_ENROLL_D(14) DSP_ENROLL_D(15) DSP_ENROLL_D(16)
-#undef DSP_ENROLL_D
-        default: return hipErrorInvalidValue;
-        }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = dispatch_d(ubm.d, [&](auto dc) {
+            hipLaunchKernelGGL(enroll_stats_kernel<decltype(dc)::value>, dim3(blocks), dim3(kThreads), 0, stream, d_feats, d_spans, n_speakers, base, ubm, d_partials);
+            return hipGetLastError();
+        });
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(enroll_finalize_kernel, dim3((unsigned)n_speakers), dim3(kThreads), 0, stream, d_spans, ubm, d_partials, map_fixed, param, d_means,

@@ -3,7 +3,7 @@
 //
 // Per iteration, from the float64 parameters w, mu, var the float32 E-step model log_const, c = float32(mu), ic = float32(1 / var); then
 //   statistics  one block per group of kUbmGroupChunks chunks of kUbmChunkRows rows.  Lane k of a wave owns component k -- c_k, ic_k and the
-//               accumulators N_k, F_k[d], G_k[d] in registers; per row the posteriors exactly as enroll_stats_kernel takes them, then
+//               accumulators N_k, F_k[d], G_k[d] in registers; per row the posterior p of gmm_estep.hpp's E-step, then
 //               N += p, F += p (x - c), G += (p (x - c)) (x - c): moments centred on c (E[x^2] - mean^2 in float32 goes negative at the
 //               variance floor).  Per chunk the four waves combine through LDS in wave order and every thread adds the chunk's float32
 //               sums it owns to float64 accumulators; the group's partial leaves with plain stores.
@@ -16,35 +16,25 @@
 
 #include <cfloat>
 #include <cmath>
-#include <cstdint>
 
+#include "gmm_estep.hpp"
 #include "ubm_kernels.hpp"
-#include "wave_reduce.hpp"
 
 namespace dsp {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRowLd = 16;       // floats per staged row: 16-byte reads of a row, whatever d
-
 template <int D>
-__global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__restrict__ feats, long n, const float *__restrict__ model, int k,
+__global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__restrict__ feats, long n, GmmModel model,
                                                              const UbmCtrl *__restrict__ ctrl, double *__restrict__ groups)
 {
-    constexpr int W = kThreads / 64, Q = (D + 3) / 4, T = 2 * D + 1, S = (kUbmMaxK * T + kThreads - 1) / kThreads;
+    constexpr int W = kThreads / 64, T = 2 * D + 1, S = (kGmmMaxK * T + kThreads - 1) / kThreads;
     __shared__ __attribute__((aligned(16))) float xs[kUbmChunkRows * kRowLd];
     extern __shared__ float part[];                                  // per wave: [k][T] (dynamic: W k T floats, so that k = 32 keeps 4 blocks per CU)
     __shared__ double ll_part[W];                                    // per wave: its rows' sum of ll (wave-uniform)
     if (ctrl->done) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = model.k;
     const bool live = lane < k;
-    float c[D], ic[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        c[j] = live ? model[k + lane * D + j] : 0.0f;
-        ic[j] = live ? model[k + k * D + lane * D + j] : 0.0f;
-    }
-    const float lc = live ? model[lane] : -INFINITY;                  // lanes at or above k: l = -inf, e = 0
+    const LaneGmm<D> g(model, lane);
     const int n_stats = k * T, P = n_stats;
     double acc[S], ll_acc = 0.0;
 #pragma unroll
@@ -55,39 +45,20 @@ __global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__r
         if (r0 >= n) break;
         const long left = n - r0;
         const int cnt = left < kUbmChunkRows ? (int)left : kUbmChunkRows;
-        const float *src = feats + r0 * D;
-        for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
-            const int r = i / D;
-            xs[r * kRowLd + (i - r * D)] = src[i];
-        }
+        stage_rows<D>(xs, feats + r0 * D, cnt);
         float N = 0.0f, F[D], G[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) F[j] = G[j] = 0.0f;
         double ll_sum = 0.0;
         __syncthreads();
         for (int r = wave; r < cnt; r += W) {
-            float x[4 * Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const float4 v = *reinterpret_cast<const float4 *>(xs + r * kRowLd + 4 * q);
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-            }
-            float s = 0.0f;
-#pragma unroll
-            for (int j = 0; j < D; ++j) {                            // ascending d
-                const float dv = x[j] - c[j];
-                s = __builtin_fmaf(dv * dv, ic[j], s);
-            }
-            const float l = __builtin_fmaf(-0.5f, s, lc);
-            const float m = wave_max(l);
-            const float e = expf(l - m);
-            const float sum = wave_sum(e);
-            const float p = e / sum;
-            ll_sum += (double)(m + logf(sum));
+            float x[4 * ((D + 3) / 4)], ll;
+            const float p = row_posterior<D>(xs, r, g, x, ll);
+            ll_sum += (double)ll;
             N += p;
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                const float dv = x[j] - c[j];
+                const float dv = x[j] - g.c[j];
                 const float pd = p * dv;
                 F[j] += pd;
                 G[j] = __builtin_fmaf(pd, dv, G[j]);
@@ -107,19 +78,9 @@ __global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__r
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             const int i = threadIdx.x + s * kThreads;
-            if (i < n_stats) {
-                float v = part[i];
-#pragma unroll
-                for (int w = 1; w < W; ++w) v += part[w * P + i];     // wave order
-                acc[s] += (double)v;                                  // ascending chunk
-            }
+            if (i < n_stats) acc[s] += (double)sum_waves(part, P, i);      // ascending chunk
         }
-        if (threadIdx.x == 0) {
-            double v = ll_part[0];
-#pragma unroll
-            for (int w = 1; w < W; ++w) v += ll_part[w];
-            ll_acc += v;
-        }
+        if (threadIdx.x == 0) ll_acc += sum_waves(ll_part, 1, 0);
         // the next chunk's rows may be staged at once: every wave left xs before the barrier above, and `part` is written again only
         // behind the next one
     }
@@ -139,26 +100,18 @@ __global__ __launch_bounds__(kThreads) void ubm_supers_kernel(const double *__re
     const long g0 = (long)blockIdx.x * kUbmSuperGroups;
     const long g1 = g0 + kUbmSuperGroups < n_groups ? g0 + kUbmSuperGroups : n_groups;
     const size_t stride = (size_t)n_stats + 1;
-    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
-        double acc = 0.0;
-        for (long g = g0; g < g1; ++g) acc += groups[(size_t)g * stride + i];         // ascending group
-        supers[(size_t)blockIdx.x * stride + i] = acc;
-    }
+    sum_partials(groups + (size_t)g0 * stride, g1 - g0, stride, n_stats + 1, supers + (size_t)blockIdx.x * stride);      // ascending group
 }
 
-__global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__restrict__ supers, long n_supers, long n, int k, int d, int iter, double tol,
-                                                             double reg_covar, double *__restrict__ params, float *__restrict__ model,
+__global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__restrict__ supers, long n_supers, long n, int iter, double tol,
+                                                             double reg_covar, double *__restrict__ params, GmmModelOut model,
                                                              double *__restrict__ lower_bounds, UbmCtrl *__restrict__ ctrl)
 {
-    __shared__ double sums[kUbmMaxK * (2 * kUbmMaxD + 1) + 1];
+    __shared__ double sums[kGmmMaxK * (2 * kGmmMaxD + 1) + 1];
     __shared__ double n_total;
     if (ctrl->done) return;
-    const int T = 2 * d + 1, n_stats = k * T;
-    for (int i = threadIdx.x; i <= n_stats; i += kThreads) {
-        double acc = 0.0;
-        for (long s = 0; s < n_supers; ++s) acc += supers[(size_t)s * ((size_t)n_stats + 1) + i];      // ascending super
-        sums[i] = acc;
-    }
+    const int k = model.k, d = model.d, T = 2 * d + 1, n_stats = k * T;
+    sum_partials(supers, n_supers, (size_t)n_stats + 1, n_stats + 1, sums);      // ascending super
     __syncthreads();
     constexpr double kTiny = 10.0 * DBL_EPSILON;                      // sklearn: nk = resp.sum(axis=0) + 10 * np.finfo(resp.dtype).eps
     if (threadIdx.x == 0) {
@@ -168,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__res
     }
     __syncthreads();
     double *w = params, *mu = params + k, *var = mu + (size_t)k * d, *lcd = var + (size_t)k * d;
-    float *lc = model, *c = model + k, *ic = c + (size_t)k * d;
+    float *lc = model.log_consts(), *c = model.means(), *ic = model.inv_covs();
     if (threadIdx.x < k) {
         const int kk = threadIdx.x;
         const double *st = sums + kk * T;
@@ -204,31 +157,23 @@ __global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__res
     }
 }
 
-template <int D>
-void launch_stats(const UbmFit &f, unsigned blocks, hipStream_t stream)
-{
-    hipLaunchKernelGGL(ubm_stats_kernel<D>, dim3(blocks), dim3(kThreads), (size_t)(kThreads / 64) * f.k * (2 * D + 1) * sizeof(float), stream, f.feats, f.n, f.model, f.k, f.ctrl, f.groups);
-}
-
 }  // namespace
 
 hipError_t launch_ubm_iterations(const UbmFit &f, int first, int count, hipStream_t stream)
 {
     const long n_groups = ubm_groups(f.n), n_supers = ubm_supers(f.n);
-    if (f.k < 1 || f.k > kUbmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
-    const int n_stats = f.k * (2 * f.d + 1);
+    const int k = f.model.k, d = f.model.d, n_stats = k * (2 * d + 1);
+    if (k < 1 || k > kGmmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
     for (int it = first; it < first + count; ++it) {
-        switch (f.d) {
-#define DSP_UBM_D(D) case D: launch_stats<D>(f, (unsigned)n_groups, stream); break;
-        DSP_UBM_D(1) DSP_UBM_D(2) DSP_UBM_D(3) DSP_UBM_D(4) DSP_UBM_D(5) DSP_UBM_D(6) DSP_UBM_D(7) DSP_UBM_D(8)
-        DSP_UBM_D(9) DSP_UBM_D(10) DSP_UBM_D(11) DSP_UBM_D(12) DSP_UBM_D(13) DSP_UBM_D(14) DSP_UBM_D(15) DSP_UBM_D(16)
-#undef DSP_UBM_D
-        default: return hipErrorInvalidValue;
-        }
+        hipError_t e = dispatch_d(d, [&](auto dc) {
+            hipLaunchKernelGGL(ubm_stats_kernel<decltype(dc)::value>, dim3((unsigned)n_groups), dim3(kThreads), (size_t)(kThreads / 64) * n_stats * sizeof(float), stream,
+                               f.feats, f.n, GmmModel{f.model.block, k, d}, f.ctrl, f.groups);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(ubm_supers_kernel, dim3((unsigned)n_supers), dim3(kThreads), 0, stream, f.groups, n_groups, n_stats, f.ctrl, f.supers);
-        hipLaunchKernelGGL(ubm_mstep_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, f.n, f.k, f.d, it, f.tol, f.reg_covar, f.params,
-                           f.model, f.lower_bounds, f.ctrl);
-        const hipError_t e = hipGetLastError();
+        hipLaunchKernelGGL(ubm_mstep_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, f.n, it, f.tol, f.reg_covar, f.params, f.model, f.lower_bounds, f.ctrl);
+        e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

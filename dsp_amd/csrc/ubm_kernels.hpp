@@ -6,9 +6,9 @@
 
 #include <cstddef>
 
-namespace dsp {
+#include "gmm_model.hpp"
 
-constexpr int kUbmMaxK = 64, kUbmMaxD = 16;
+namespace dsp {
 
 // The reduction tree of one E-step, a function of the row count n alone:
 //   chunk c  = rows [c C, min(n, (c + 1) C)), C = kUbmChunkRows: float32, the four waves' interleaved rows combined in wave order
@@ -26,8 +26,6 @@ inline long ubm_supers(long n) { return (ubm_groups(n) + kUbmSuperGroups - 1) / 
 inline size_t ubm_partial_doubles(int k, int d) { return (size_t)k * (2 * d + 1) + 1; }
 // the float64 parameters between iterations: w[k], mu[k][d], var[k][d], log_const[k]
 inline size_t ubm_param_doubles(int k, int d) { return (size_t)k * (2 * d + 2); }
-// the float32 E-step model: log_const[k], c[k][d], ic[k][d]
-inline size_t ubm_model_floats(int k, int d) { return (size_t)k * (2 * d + 1); }
 
 // what the launches of one fit share on the device: `done` is tested first by every kernel of every later iteration
 struct UbmCtrl {
@@ -38,9 +36,8 @@ struct UbmCtrl {
 struct UbmFit {
     const float *feats;      // [n][d]
     long n;
-    int k, d;
     double *params;          // ubm_param_doubles
-    float *model;            // ubm_model_floats
+    GmmModelOut model;       // the float32 E-step model of the next iteration: log_const, c = float32(mu), ic = float32(1 / var)
     double *groups;          // [ubm_groups(n)][ubm_partial_doubles]
     double *supers;          // [ubm_supers(n)][ubm_partial_doubles]
     double *lower_bounds;    // [max_iter]

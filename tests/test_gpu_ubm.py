@@ -101,6 +101,22 @@ def test_parity_with_float64_on_the_edges_of_the_tree(torch_cuda, k, d, rows):
         _same(tr.fit(xd, max_iter=2, tol=0.0), tr.fit(xd, init=start, max_iter=2, tol=0.0), "init None")
 
 
+@pytest.mark.parametrize("d", range(1, 17))
+def test_every_d_of_the_dispatch(torch_cuda, d):
+    """every d the statistics kernel is instantiated for, at k = 5 on one chunk and one row: one iteration at tol = 0 from a caller's
+    start against float64, and twice the same bits"""
+    import dsp_amd
+    k, n = 5, U.CHUNK_ROWS + 1
+    x, given = _case(k, d, n)
+    xd = _cuda(torch_cuda, x)
+    tr = dsp_amd.UbmTrainer(k, d)
+    got = tr.fit(xd, init=given, max_iter=1, tol=0.0)
+    want = U.fit(x, given, max_iter=1, tol=0.0, history=True)
+    model = U.fit(x, given, max_iter=1, tol=0.0, dtype=np.float32, history=True)
+    _check(got, _prefix(want, 1), _prefix(model, 1), f"k {k} d {d} n {n}")
+    _same(tr.fit(xd, init=given, max_iter=1, tol=0.0), got, "every d twice")
+
+
 @pytest.mark.parametrize("tag", ["iter1", "iter10", "tol"])
 def test_fixture_against_sklearns_recorded_answers(torch_cuda, golden, tag):
     import dsp_amd

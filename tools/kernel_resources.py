@@ -8,7 +8,7 @@ import re
 import subprocess
 import sys
 
-KEYS = ("VGPRs", "AGPRs", "VGPRs Spill", "SGPRs", "SGPRs Spill", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]")
+KEYS = ("VGPRs", "AGPRs", "VGPRs Spill", "TotalSGPRs", "SGPRs Spill", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]")
 
 
 def main():
@@ -31,11 +31,11 @@ def main():
     names = list(rows)
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines() if names else []
     for k, d in zip(names, dem):
-        d = re.sub(r"\(.*", "", d)
+        d = re.sub(r"\((?!anonymous namespace\)).*", "", d)      # the arguments go, an anonymous namespace stays
         if sub in d:
             v = rows[k]
             g = lambda key: v.get(key, -1)      # noqa: E731
-            print(f"{d[:110]:110s} vgpr {g('VGPRs'):3d} spill {g('VGPRs Spill'):2d} sgpr {g('SGPRs'):3d} sspill {g('SGPRs Spill'):2d} "
+            print(f"{d[:110]:110s} vgpr {g('VGPRs'):3d} spill {g('VGPRs Spill'):2d} sgpr {g('TotalSGPRs'):3d} sspill {g('SGPRs Spill'):2d} "
                   f"scratch {g('ScratchSize [bytes/lane]'):3d} occ {g('Occupancy [waves/SIMD]')} lds {g('LDS Size [bytes/block]')}")
 
 
