@@ -8,14 +8,14 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.environ.get("DSP_AMD_LIB") or os.path.join(PKG, "libdsp_amd.so")
-SOURCES = ["capi.cpp", "capi_scrubjay.cpp", "capi_consumers.cpp", "capi_stream.cpp", "capi_classifier_cxx.cpp", "capi_classify_f32.cpp", "capi_classify_f64.cpp", "capi_gather.cpp", "capi_resample.cpp", "capi_enroll.cpp", "capi_ubm.cpp", "classify_f64_kernels.hip", "classify_f64_ckpt_kernels.hip", "tables.cpp", "mfcc_kernels.hip", "mfcc1024_kernel.hip", "mfcc1024_wave_kernel.hip", "mfcc2048_kernel.hip", "classify_kernels.hip",
-           "svm_kernels.hip", "consumer_kernels.hip", "stream_kernels.hip", "resample_kernels.hip", "enroll_kernels.hip", "ubm_kernels.hip"]
+SOURCES = ["capi.cpp", "capi_scrubjay.cpp", "capi_consumers.cpp", "capi_stream.cpp", "capi_classifier_cxx.cpp", "capi_classify_f32.cpp", "capi_classify_f64.cpp", "capi_gather.cpp", "capi_resample.cpp", "capi_enroll.cpp", "capi_ubm.cpp", "capi_verify.cpp", "classify_f64_kernels.hip", "classify_f64_ckpt_kernels.hip", "tables.cpp", "mfcc_kernels.hip", "mfcc1024_kernel.hip", "mfcc1024_wave_kernel.hip", "mfcc2048_kernel.hip", "classify_kernels.hip",
+           "svm_kernels.hip", "consumer_kernels.hip", "stream_kernels.hip", "resample_kernels.hip", "enroll_kernels.hip", "ubm_kernels.hip", "verify_kernels.hip"]
 # Measured dead ends of the 512-point kernel (row per frame: 0.537 ms, two frames per wavefront step: 0.44-0.45 ms against 0.41 for
 # the default kernel; A/B records in profiles/r02_wave_priority_ab.txt): kept buildable, outside the product library.
 # DSP_AMD_EXPERIMENTS=1 python -m dsp_amd.build adds them (dsp_version() then carries "+experiments", DSP_KERNEL_ROW / _PAIR work).
 EXPERIMENT_SOURCES = ["mfcc_row_kernel.hip", "mfcc512_pair_kernel.hip"]
 EXPERIMENTS = os.environ.get("DSP_AMD_EXPERIMENTS", "") not in ("", "0")
-HEADERS = ["exports.map", "tables.hpp", "clip_span.hpp", "mfcc_kernels.hpp", "mfcc_device.hpp", "classify_kernels.hpp", "svm_kernels.hpp", "classify_f64_device.hpp", "diag_guard.hpp", "consumer_kernels.hpp", "scan_device.hpp", "stream_kernels.hpp", "capi_util.hpp", "mfcc_plan.hpp", "classify_front.hpp", "resample_kernels.hpp", "enroll_kernels.hpp", "ubm_kernels.hpp", "gmm_model.hpp", "gmm_estep.hpp",
+HEADERS = ["exports.map", "tables.hpp", "clip_span.hpp", "mfcc_kernels.hpp", "mfcc_device.hpp", "classify_kernels.hpp", "svm_kernels.hpp", "classify_f64_device.hpp", "diag_guard.hpp", "consumer_kernels.hpp", "scan_device.hpp", "stream_kernels.hpp", "capi_util.hpp", "mfcc_plan.hpp", "classify_front.hpp", "resample_kernels.hpp", "enroll_kernels.hpp", "ubm_kernels.hpp", "verify_kernels.hpp", "gmm_model.hpp", "gmm_estep.hpp",
            os.path.join("..", "..", "include", "dsp_amd.h"), os.path.join("..", "..", "include", "dsp_amd_classifier.h")]
 
 

@@ -8,6 +8,7 @@
   StreamSession  the same for audio that is still arriving       sync/sync.cpp:188-213 (the capture loop itself, many feeds)
   Cmvn           sliding_cmvn                                   2fa/audio/speaker/gmm_utils.py:14-25
   SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
+  SpeakerVerifier   score_models / evaluate_dir (float GMMs)      2fa/audio/speaker/gmm_utils.py:99-126, evaluate_gmm.py
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
@@ -541,6 +542,58 @@ class SpeakerEnroller:
         if q6.dtype != np.int8 or q6.shape != np.shape(ubm_int["means"]):
             raise ValueError("means_q6 must be int8 [k][d], the shape of the UBM's means")
         return SpeakerModel({"means": q6, "inv_covs": ubm_int["inv_covs"], "log_consts": ubm_int["log_consts"]}, ubm_int, device)
+
+
+class SpeakerVerifier:
+    """dsp_speaker_verifier: every clip of a ragged matrix of (CMVN'd) feature rows against a float UBM and S enrolled speakers -- the
+    mean log-sum-exp log-likelihood of each model and target.score - ubm.score per (clip, speaker)."""
+
+    OUTPUTS = ("llr", "ll_ubm", "ll_target", "best", "best_llr")
+
+    def __init__(self, ubm_float: dict, device: int = 0):
+        """ubm_float: log_consts [k], means [k][d], inv_covs [k][d], as SpeakerEnroller takes them.  No device is touched here."""
+        p, k, d, _keep = _gmm_float_params(ubm_float, "ubm_float")
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_speaker_verifier_create(C.byref(p), int(device), C.byref(h)), "dsp_speaker_verifier_create")
+        self._h, self.k, self.d, self.device = h, k, d, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_speaker_verifier_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def verify(self, feats, frame_offsets, means, want=("llr", "ll_ubm", "best", "best_llr")):
+        """feats: cuda float32 [F][d], clip c = rows [frame_offsets[c], frame_offsets[c + 1]), every clip >= 1 row; means: cuda float32
+        [S][k][d] (SpeakerEnroller.enroll(...)["means"] as it is) -> a dict of cuda tensors, those named in `want` of: llr float32 [C][S],
+        ll_ubm float32 [C], ll_target float32 [C][S], best int32 [C] (the smallest s with the largest llr), best_llr float32 [C]."""
+        import torch
+        want = tuple(want)
+        if not want or any(key not in self.OUTPUTS for key in want):
+            raise ValueError(f"want must name at least one of {self.OUTPUTS}")
+        fo = _frame_offsets(frame_offsets)
+        feats = _scan_mfcc(feats, fo, self.d)
+        if (np.diff(fo) == 0).any():
+            raise ValueError(f"clip {int(np.flatnonzero(np.diff(fo) == 0)[0])} has no rows")
+        if not (isinstance(means, torch.Tensor) and means.is_cuda and means.dtype == torch.float32 and means.dim() == 3
+                and tuple(means.shape[1:]) == (self.k, self.d)):
+            raise ValueError(f"means must be a float32 CUDA tensor [S][{self.k}][{self.d}]")
+        if means.device != feats.device:
+            raise ValueError("means and feats must be on the same device")
+        means = means.contiguous()
+        n, n_spk, dev = fo.size - 1, means.shape[0], feats.device
+        shape = {"llr": (n, n_spk), "ll_ubm": (n,), "ll_target": (n, n_spk), "best": (n,), "best_llr": (n,)}
+        out = {key: torch.empty(shape[key], dtype=torch.int32 if key == "best" else torch.float32, device=dev) for key in want}
+        _lib.check(self._L.dsp_speaker_verify_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_LP), means.data_ptr(), n_spk,
+                                                            *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
+                   "dsp_speaker_verify_ragged_device")
+        return out
 
 
 class UbmTrainer:

@@ -19,7 +19,7 @@
 //
 // Out of scope: variance or weight adaptation (the UBM itself is trained by ubm_kernels.hip); the n_fft-400 librosa front end (these kernels take whatever MFCC
 // matrix the existing entries wrote and leave every front end alone); CMVN inside scanners or stream sessions (a stream needs a 150-row
-// look-ahead); a float log-sum-exp scorer; CMVN fused into the statistics pass.  No existing speaker scoring entry, nor any result of
+// look-ahead); the float log-sum-exp scorer (verify_kernels.hip); CMVN fused into the statistics pass.  No existing speaker scoring entry, nor any result of
 // one, changes: the enrolled Q6 means go to dsp_speaker_model_create as any other target's.
 #include <hip/hip_runtime.h>
 
@@ -31,17 +31,6 @@
 
 namespace dsp {
 namespace {
-
-// the recording / speaker that owns unit u: the last one whose first unit is <= u (those without rows own no unit)
-__device__ inline long owner_of_unit(const RowSpan *spans, long n, long u)
-{
-    long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (spans[mid].unit0 <= u) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(kThreads) void cmvn_kernel(const float *__restrict__ in, const RowSpan *__restrict__ spans, long n_rec, long tile_base,
                                                         int d, int half, float *__restrict__ out)

@@ -1,6 +1,7 @@
 // gmm_estep.hpp -- the float32 E-step of a diagonal GMM for the statistics kernels of enroll_kernels.hip and ubm_kernels.hip (DESIGN.md
 // 3.11): a chunk of rows staged in LDS, lane k of a wave owning component k of a GmmModel, per row the lane's posterior and the row's
-// log-likelihood.  What is accumulated from them is each kernel's own.  Also the D dispatch, the wave-order and the ascending float64 sums.
+// log-likelihood.  What is accumulated from them is each kernel's own.  Also the D dispatch, the owner of a ragged launch's unit, the
+// wave-order and the ascending float64 sums (verify_kernels.hip, a row per lane, takes those and restates l_k).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +36,19 @@ __device__ __forceinline__ float wave_all(float v, Op op)
 }
 __device__ __forceinline__ float wave_max(float v) { return wave_all(v, [](float a, float b) { return fmaxf(a, b); }); }
 __device__ __forceinline__ float wave_sum(float v) { return wave_all(v, [](float a, float b) { return a + b; }); }
+
+// the recording / speaker / clip that owns unit u of a ragged launch (spans[n] with a first unit `unit0` each, enroll_kernels.hpp RowSpan):
+// the last one whose first unit is <= u (those without rows own no unit)
+template <class Span>
+__device__ inline long owner_of_unit(const Span *spans, long n, long u)
+{
+    long lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if (spans[mid].unit0 <= u) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // rows [0, cnt) of src[cnt][D] into the block's LDS image xs[rows of the chunk][kRowLd]; a barrier follows before any row is read
 template <int D>

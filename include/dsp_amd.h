@@ -696,8 +696,8 @@ int dsp_cmvn_ragged_device(dsp_cmvn *c, const float *d_in, long n_recordings, co
  * A speaker without rows: DSP_EINVAL naming the first.  Zero speakers: DSP_OK, no launch.  There are no float atomics: a speaker's rows
  * are summed in chunks of 256 rows cut by its own row count and combined in a fixed order, so every output of a speaker is bit-identical
  * whatever the batch around it.  The enroller owns a grow-only workspace: ONE stream at a time per enroller.
- * Not covered: variance or weight adaptation, a float log-sum-exp scorer, CMVN inside scanners or stream sessions (the UBM itself is
- * trained by dsp_ubm_train_device below). */
+ * Not covered: variance or weight adaptation, CMVN inside scanners or stream sessions (the UBM itself is trained by
+ * dsp_ubm_train_device below, and the enrolled float means are scored by dsp_speaker_verify_ragged_device below that). */
 typedef struct dsp_gmm_float_params {
     int k, d;                    /* k <= 64, d <= 16, as dsp_gmm_params */
     const double *log_consts;    /* [k]    */
@@ -786,6 +786,47 @@ int dsp_ubm_init_rows_device(dsp_ubm_trainer *t, const float *d_feats, long n, d
 int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_ubm_init *init, const dsp_ubm_config *cfg,
                          dsp_ubm_result *result, void *stream);
 int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_covs, int16_t *log_consts, int saturated[3]);
+
+/* --- verifying speakers with the float GMMs: every clip against every speaker ---
+ * The step behind enrolment: target.score(feats) - ubm.score(feats) of the reference's 2fa/audio/speaker/gmm_utils.py:99-126
+ * (score_models, evaluate_dir) and evaluate_gmm.py, both terms the mean log-sum-exp log-likelihood of a float GMM -- for C clips against
+ * S speakers in one call, in the arithmetic the models were trained and adapted in.
+ *
+ * Inputs: the float UBM (handed over once, each value rounded once to float32: lc[k], mu[k][d], ic[k][d]); clip c = rows
+ * [frame_offsets[c], frame_offsets[c + 1]) of d_feats[..][d], rows that are already CMVN'd (frame_offsets: a HOST array of n_clips + 1
+ * rows, read before the call returns); d_means[S][k][d], the float32 means of S enrolled speakers on the device, exactly what
+ * dsp_speaker_enroll_ragged_device writes.  Speaker s is the model (lc, d_means[s], ic): mean-only MAP shares the UBM's log_consts and
+ * inv_covs.  k <= 64, d <= 16.
+ *
+ * Per row x and model with centres c (the UBM: c = mu), in float32:
+ *   s = 0; for ascending j: dv = x_j - c_kj, s = fma(dv * dv, ic_kj, s);   l_k = fma(-0.5, s, lc_k)       (the enroller's l_k, bit for bit)
+ *   m = max_k l_k,   S = sum_k expf(l_k - m) over ASCENDING k,   ll = m + logf(S)
+ * Per clip of n rows and model, L = sum_t (double) ll_t in an order fixed by n alone: the rows are cut into tiles of 64 from the clip's
+ * first row; inside a tile the sum is the adjacent pairwise tree (1, 2, 4, ... 32 apart, absent rows 0); the tiles are added in
+ * ascending order.  There are no atomics.  With L_u the UBM's sum and L_s speaker s's:
+ *   d_ll_ubm[c] = float(L_u / n),  d_ll_target[c][s] = float(L_s / n),  d_llr[c][s] = float((L_s - L_u) / n)   (the difference in float64)
+ *   d_best[c] = the smallest s with the largest d_llr[c][s],  d_best_llr[c] = that value
+ * Every output of a (clip, speaker) pair is bit-identical whatever the batch around the clip, the other speakers of the call, the
+ * speaker's position in d_means, the grid and what the workspace held before.
+ *
+ * Any output may be NULL, not all.  A clip without rows: DSP_EINVAL naming the first.  n_clips == 0 or n_speakers == 0: DSP_OK, no
+ * launch.  At most 2^30 clips and 2^19 speakers per call.  Every argument check comes before a device is touched;
+ * dsp_speaker_verifier_create touches none (the UBM is uploaded by the first call that scores).  The verifier owns a grow-only
+ * workspace of tile sums, [tiles][1 + S] doubles: ONE stream at a time per verifier.  A call whose workspace would pass 256 MiB is split
+ * over runs of clips internally, on the same stream; the outputs do not change.
+ * Not covered: per-speaker variances or weights (mean-only MAP is what enrolment writes), a trial LIST instead of the full C x S
+ * matrix, CMVN inside the call (dsp_cmvn_ragged_device in front), multi-GPU (split the clips or the speakers across verifiers). */
+typedef struct dsp_speaker_verifier dsp_speaker_verifier;
+int dsp_speaker_verifier_create(const dsp_gmm_float_params *ubm, int device, dsp_speaker_verifier **out);
+void dsp_speaker_verifier_destroy(dsp_speaker_verifier *v);
+int dsp_speaker_verify_ragged_device(dsp_speaker_verifier *v, const float *d_feats, long n_clips, const long *frame_offsets,
+                                     const float *d_means, long n_speakers,
+                                     float *d_llr,        /* [C][S]                       */
+                                     float *d_ll_ubm,     /* [C]      may be NULL         */
+                                     float *d_ll_target,  /* [C][S]   may be NULL         */
+                                     int *d_best,         /* [C]      may be NULL         */
+                                     float *d_best_llr,   /* [C]      may be NULL         */
+                                     void *stream);
 
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
