@@ -10,11 +10,6 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.environ.get("DSP_AMD_LIB") or os.path.join(PKG, "libdsp_amd.so")
 SOURCES = ["capi.cpp", "capi_scrubjay.cpp", "capi_consumers.cpp", "capi_stream.cpp", "capi_classifier_cxx.cpp", "capi_classify_f32.cpp", "capi_classify_f64.cpp", "capi_gather.cpp", "capi_resample.cpp", "capi_enroll.cpp", "capi_ubm.cpp", "capi_verify.cpp", "classify_f64_kernels.hip", "classify_f64_ckpt_kernels.hip", "tables.cpp", "mfcc_kernels.hip", "mfcc1024_kernel.hip", "mfcc1024_wave_kernel.hip", "mfcc2048_kernel.hip", "classify_kernels.hip",
            "svm_kernels.hip", "consumer_kernels.hip", "stream_kernels.hip", "resample_kernels.hip", "enroll_kernels.hip", "ubm_kernels.hip", "verify_kernels.hip"]
-# Measured dead ends of the 512-point kernel (row per frame: 0.537 ms, two frames per wavefront step: 0.44-0.45 ms against 0.41 for
-# the default kernel; A/B records in profiles/r02_wave_priority_ab.txt): kept buildable, outside the product library.
-# DSP_AMD_EXPERIMENTS=1 python -m dsp_amd.build adds them (dsp_version() then carries "+experiments", DSP_KERNEL_ROW / _PAIR work).
-EXPERIMENT_SOURCES = ["mfcc_row_kernel.hip", "mfcc512_pair_kernel.hip"]
-EXPERIMENTS = os.environ.get("DSP_AMD_EXPERIMENTS", "") not in ("", "0")
 HEADERS = ["exports.map", "tables.hpp", "clip_span.hpp", "mfcc_kernels.hpp", "mfcc_device.hpp", "classify_kernels.hpp", "svm_kernels.hpp", "classify_f64_device.hpp", "diag_guard.hpp", "consumer_kernels.hpp", "scan_device.hpp", "stream_kernels.hpp", "capi_util.hpp", "mfcc_plan.hpp", "classify_front.hpp", "resample_kernels.hpp", "enroll_kernels.hpp", "ubm_kernels.hpp", "verify_kernels.hpp", "gmm_model.hpp", "gmm_estep.hpp",
            os.path.join("..", "..", "include", "dsp_amd.h"), os.path.join("..", "..", "include", "dsp_amd_classifier.h")]
 
@@ -24,8 +19,7 @@ def source_hash() -> str:
     binary can be checked against the tree it claims to come from."""
     import hashlib
     h = hashlib.sha256()
-    h.update(b"+experiments" if EXPERIMENTS else b"")
-    for name in sorted(SOURCES + (EXPERIMENT_SOURCES if EXPERIMENTS else []) + HEADERS):
+    for name in sorted(SOURCES + HEADERS):
         h.update(name.encode())
         with open(os.path.join(CSRC, name), "rb") as f:
             h.update(f.read())
@@ -52,7 +46,7 @@ def is_stale() -> bool:
     except OSError:
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + (EXPERIMENT_SOURCES if EXPERIMENTS else []) + HEADERS]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -84,10 +78,6 @@ def _build_locked(verbose: bool) -> str:
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
              "-fno-slp-vectorize", "-Wno-unused-value", f'-DDSP_AMD_SRC_HASH="{source_hash()}"']
     flags += os.environ.get("DSP_AMD_EXTRA_FLAGS", "").split()
-    sources = list(SOURCES)
-    if EXPERIMENTS:
-        flags.append("-DDSP_AMD_EXPERIMENTS")
-        sources += EXPERIMENT_SOURCES
     if verbose:
         flags.append("-Rpass-analysis=kernel-resource-usage")
     # one hipcc -c per source, side by side (the kernels dominate: ~50 s in sequence, ~20 s on 8 cores), then one link
@@ -102,9 +92,9 @@ def _build_locked(verbose: bool) -> str:
             r = subprocess.run([_hipcc(), "-c", *flags, "-o", obj, os.path.join(CSRC, src)], cwd=CSRC, capture_output=True, text=True)
             return src, obj, r
 
-        jobs = int(os.environ.get("DSP_AMD_BUILD_JOBS", "0")) or min(len(sources), max(1, (os.cpu_count() or 2)))
+        jobs = int(os.environ.get("DSP_AMD_BUILD_JOBS", "0")) or min(len(SOURCES), max(1, (os.cpu_count() or 2)))
         with ThreadPoolExecutor(jobs) as pool:
-            results = list(pool.map(compile_one, sources))
+            results = list(pool.map(compile_one, SOURCES))
         log = "".join(f"---- {src}\n{r.stdout}{r.stderr}" for src, _, r in results if r.stdout or r.stderr)
         if verbose and log:
             print(log)

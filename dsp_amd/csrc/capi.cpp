@@ -85,12 +85,7 @@ const char *dsp_last_error(void) { return g_err.c_str(); }
 #ifndef DSP_AMD_SRC_HASH
 #define DSP_AMD_SRC_HASH "unknown"
 #endif
-#ifdef DSP_AMD_EXPERIMENTS
-#define DSP_AMD_EXPERIMENTS_TAG " +experiments"
-#else
-#define DSP_AMD_EXPERIMENTS_TAG ""
-#endif
-const char *dsp_version(void) { return "dsp_amd 0.3 (gfx950)" DSP_AMD_EXPERIMENTS_TAG " src:" DSP_AMD_SRC_HASH; }
+const char *dsp_version(void) { return "dsp_amd 0.3 (gfx950) src:" DSP_AMD_SRC_HASH; }
 
 int dsp_abi_sizeof(int which)
 {
@@ -266,25 +261,11 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
                             cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, b, a);
         dsp::PrefilterScan sc;
         if (!dsp::build_prefilter_scan(b, a, sc, why)) return capi_fail(DSP_EINVAL, why);
-        if (sc.c_ok && (!DSP_PRE_ROWSCAN || sc.c_row_ok)) {      // the kernel runs the cascade form (its scan in row form); coefficients without it (none of the two literal sets) take the two-pass path
+        if (sc.c_ok && sc.c_row_ok) {      // the kernel runs the cascade form (its scan in row form); coefficients without it (none of the two literal sets) take the two-pass path
             e = dsp::upload(p->d_scan, sc);
             for (int k = 0; k < 4; ++k) p->scan_steps[k] = sc.c_steps[k];
         }
     }
-#ifdef DSP_AMD_EXPERIMENTS
-    // measured dead ends kept buildable (python -m dsp_amd.build with DSP_AMD_EXPERIMENTS=1): the row-per-frame kernel and
-    // the two-frames-per-wave kernel; the default library does not carry them
-    if (e == hipSuccess && cfg->n_fft == 512) {
-        auto rt = std::make_unique<dsp::RowTables512>();
-        dsp::build_row_tables_512(*cfg, *rt);
-        e = dsp::upload(p->d_row_tables, *rt);
-    }
-    if (e == hipSuccess && cfg->n_fft == 512) {
-        dsp::PairExtra512 px;
-        dsp::build_pair_extra_512(px);
-        e = dsp::upload(p->d_pair, px);
-    }
-#endif
     if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
     p->n_cu = prop.multiProcessorCount;
     p->aub = cfg->n_fft == 2048 && (cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM);
@@ -296,19 +277,14 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
                                                               cfg->frame_length == 512, false);
         p->resident_blocks = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
                                                         cfg->frame_length == 512, true);
-#ifdef DSP_AMD_EXPERIMENTS
-        p->resident_blocks_row = dsp::mfcc512_row_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
-                                                                cfg->frame_length == 512);
-        p->resident_blocks_pair = dsp::mfcc512_pair_blocks_per_cu();
-#endif
     } else {
         p->resident_blocks_gen = dsp::mfcc1024_blocks_per_cu(cfg->frame_length == 1024);
         p->resident_blocks_gen_wave = dsp::mfcc1024_wave_blocks_per_cu(cfg->frame_length == 1024);
         if (p->d_scan) p->resident_blocks_gen_pre = dsp::mfcc1024_wave_blocks_per_cu(true, true);
     }
     if (const char *k = std::getenv("DSP_AMD_KERNEL")) {
-        // an A/B switch, not a requirement: a value this build (or this plan's n_fft) has no kernel for is reported and ignored --
-        // an environment left over from an experiments build must not make every plan_create fail
+        // an A/B switch, not a requirement: a value this plan's n_fft has no kernel for is reported and ignored -- an
+        // environment left over from the removed 512-point experiments must not make every plan_create fail
         if (dsp_mfcc_plan_set_kernel(p.get(), std::atoi(k)) != DSP_OK)
             std::fprintf(stderr, "libdsp_amd: DSP_AMD_KERNEL=%s ignored (%s); using the default kernel\n", k, dsp_last_error());
     }
@@ -334,12 +310,11 @@ int dsp_mfcc_plan_config(const dsp_mfcc_plan *p, dsp_mfcc_config *cfg)
 int dsp_mfcc_plan_set_kernel(dsp_mfcc_plan *p, int kernel)
 {
     if (!p || (kernel != DSP_KERNEL_WAVE && kernel != DSP_KERNEL_ROW && kernel != DSP_KERNEL_WAVE_FRAME && kernel != DSP_KERNEL_PAIR)) return capi_fail(DSP_EINVAL, "bad kernel id");
-#ifndef DSP_AMD_EXPERIMENTS
     // DSP_KERNEL_ROW on a 1024-point plan selects the general Stockham kernel (a product path: the fallback for filterbanks
-    // the wave kernel's tables do not hold); the 512-point row / pair kernels are experiments outside the default build
+    // the wave kernel's tables do not hold); the 512-point row / pair kernels were measured dead ends (0.537 ms and 0.44-0.45 ms
+    // against 0.41 ms for the default kernel, profiles/r02_wave_priority_ab.txt) and have been removed
     if (kernel == DSP_KERNEL_PAIR || (kernel == DSP_KERNEL_ROW && p->cfg.n_fft != 1024))
-        return capi_fail(DSP_EINVAL, "DSP_KERNEL_ROW / DSP_KERNEL_PAIR (512-point experiments) are not in this build: rebuild with DSP_AMD_EXPERIMENTS=1");
-#endif
+        return capi_fail(DSP_EINVAL, "DSP_KERNEL_ROW / DSP_KERNEL_PAIR: the 512-point row and pair kernels were removed (measured slower than the default kernel)");
     p->kernel = kernel;
     return DSP_OK;
 }
@@ -418,16 +393,8 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
     a.frames_per_clip = frames_per_clip;
     a.samples_per_clip = job.samples_per_clip;
     const bool fft2048 = p->cfg.n_fft == 2048, gen = p->cfg.n_fft == 1024;
-#ifdef DSP_AMD_EXPERIMENTS
-    const bool row = !gen && p->kernel == DSP_KERNEL_ROW && p->cfg.n_fft == 512;
-    // two frames per wavefront step (experiment): the reference shape on independent full frames only, else the default form
-    const bool pair = !gen && p->kernel == DSP_KERNEL_PAIR && p->d_pair && in_kind == 0 && frames_per_clip == 0 && p->cfg.frame_length == 512 &&
-                      p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX && p->host.dct_split == 4 && p->host.dct_len == 10 && p->host.mel_gather == 3;
-#else
-    const bool row = false, pair = false;
-#endif
     // 16-frame tile epilogue: per-frame log mode on the wave-per-frame kernel
-    const bool tile = !gen && (p->kernel == DSP_KERNEL_WAVE || p->kernel == DSP_KERNEL_PAIR) && p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX;
+    const bool tile = !gen && p->kernel == DSP_KERNEL_WAVE && p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX;
     // 1024-point: the register-resident wave kernel when the filterbank fits two chunk slots per lane (DSP_KERNEL_ROW selects
     // the general Stockham kernel for A/B)
     const bool gen_wave = gen && p->gen_slots <= 3 && p->kernel != DSP_KERNEL_ROW;
@@ -437,11 +404,11 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
         a.chunk = p->chunk > 0 ? p->chunk : 8;
         per_cu = p->resident_blocks_2048;
     } else {
-        const int nf = gen ? (gen_wave ? 8 : 1) : (pair ? 16 : (row ? 4 : (tile ? 8 : 1)));
-        a.chunk = p->chunk > 0 ? p->chunk : (pair ? 16 : 8);
+        const int nf = gen ? (gen_wave ? 8 : 1) : (tile ? 8 : 1);
+        a.chunk = p->chunk > 0 ? p->chunk : 8;
         a.chunk = ((a.chunk + nf - 1) / nf) * nf;   // whole items (tile: half-tiles of 8 frames) per chunk
         per_cu = gen ? (gen_wave ? (job.fused_prefilter ? p->resident_blocks_gen_pre : p->resident_blocks_gen_wave) : p->resident_blocks_gen)
-                     : (pair ? p->resident_blocks_pair : (row ? p->resident_blocks_row : (tile ? p->resident_blocks : p->resident_blocks_frame)));
+                     : (tile ? p->resident_blocks : p->resident_blocks_frame);
     }
     dsp::SpanRing::Lease slot;
     if (rg) {
@@ -458,10 +425,6 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
             return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, false);
         if (gen_wave) return dsp::launch_mfcc1024_wave(x, p->d_gen_tables, blocks, st, job.fused_prefilter ? p->d_scan : nullptr, p->scan_steps);
         if (gen) return dsp::launch_mfcc1024(x, p->d_gen_tables, blocks, st);
-#ifdef DSP_AMD_EXPERIMENTS
-        if (pair) return dsp::launch_mfcc512_pair(x, p->d_pair, blocks, st);
-        if (row) return dsp::launch_mfcc512_row(x, p->d_row_tables, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st);
-#endif
         return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, tile);
     };
     if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) return two_pass_floor(p, a, st, launch);
@@ -511,8 +474,6 @@ int dsp::ragged_plan_check(const dsp_mfcc_plan *p)
 {
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return capi_fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
     if (p->cfg.n_fft == 1024) return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the 512- and 2048-point kernels: n_fft 1024 is not supported");
-    if (p->cfg.n_fft == 512 && p->kernel != DSP_KERNEL_WAVE && p->kernel != DSP_KERNEL_WAVE_FRAME)
-        return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the wave-per-frame kernels (DSP_KERNEL_WAVE / DSP_KERNEL_WAVE_FRAME)");
     return DSP_OK;
 }
 

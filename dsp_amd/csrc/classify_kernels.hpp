@@ -17,15 +17,9 @@ constexpr int kMaxMidpoints = 64;
 // (sample 128), so the recompute of a segment runs as TWO 128-sample chains on two wavefronts instead of one 256-sample chain on
 // one (spec_from_ckpt_kernel, phase R).  Per filter, measured on 49 152 clips (profiles/r03_classify_session2.txt): both filters
 // 2.485 ms, the 3000-7500 Hz filter only 2.521 ms, neither 2.586 ms; each second state is 2.3 KB more traffic per clip.
-// DSP_CK_HALF = 0 / DSP_CK_HALF_MP = 0: segment starts only (A/B builds).
-#ifndef DSP_CK_HALF
-#define DSP_CK_HALF 1
-#endif
-#ifndef DSP_CK_HALF_MP
-#define DSP_CK_HALF_MP DSP_CK_HALF
-#endif
-constexpr int kCkPerSegBp = DSP_CK_HALF ? 2 : 1;       // 3000-7500 Hz (the map of the clips with midpoints)
-constexpr int kCkPerSegMp = DSP_CK_HALF_MP ? 2 : 1;    // 1000-3000 Hz (the flags of the gated-in frames)
+// (The builds with segment starts only, for one filter or both, were removed with that record.)
+constexpr int kCkPerSegBp = 2;      // 3000-7500 Hz (the map of the clips with midpoints)
+constexpr int kCkPerSegMp = 2;      // 1000-3000 Hz (the flags of the gated-in frames)
 
 struct SpecTables {
     float window[kSpecSeg];      // periodic Tukey(0.25), evaluated on the host like classifier.cpp:259-293

@@ -3,7 +3,7 @@
 // (tools/mkvariant.sh NAME -DDSP_AMD_DIAG -D<probe>).  A product build cannot switch one on by accident.
 #pragma once
 #if !defined(DSP_AMD_DIAG)
-#if defined(DSP_IIR_DIAG_NO_STORE) || (defined(DSP_PRE_DIAG) && DSP_PRE_DIAG != 0) || (defined(DSP_PAIR_DIAG) && DSP_PAIR_DIAG != 0) ||            \
+#if defined(DSP_IIR_DIAG_NO_STORE) || (defined(DSP_PRE_DIAG) && DSP_PRE_DIAG != 0) || \
     (defined(DSP_DIAG_MODE) && DSP_DIAG_MODE != 0) || defined(DSP_DIAG_NO_POOL) || defined(DSP_DIAG_NO_SVM) || defined(DSP_DIAG_NO_SVMTAIL) ||     \
     defined(DSP_DIAG_NO_POOLTILE) || defined(DSP_DIAG_NO_POOLFINISH) || defined(DSP_DIAG_SNOPS) || defined(DSP_DIAG_VNOPS) ||                      \
     defined(DSP_PF_STAMPS) || defined(DSP_RC_STAMPS) || defined(SC_DIAG) || (defined(SC_ROLES) && SC_ROLES != 7) || defined(SC_PRIO)

@@ -48,22 +48,19 @@ constexpr int kWaveZero = 192;                      // partial slot that always 
 // block-shared LDS copies behind the four per-wave carves (round 3):
 //   the MFMA A operand of the tile epilogue (32 k-steps x 64 lanes): a global re-read in the rolled k loop sat latency-exposed
 //   in front of every MFMA (the 512-point kernel's larger shapes had the same cure);
-//   PRE only: the mel weights (3 slots x 12 taps x 64 lanes) as float4 rows [slot][quad][lane] -- the PRE variant has no registers
-//   for them, and 36 dword re-reads per frame from L1 made the kernel's speed hang on how many of them hipcc kept in flight
-//   (2.58 .. 3.64 ms per 1 M frames between builds that differed in nothing else).
-// DSP_PRE_W3 = 1 (PRE variant, an experiment): THREE waves per SIMD -- <= 168 VGPRs (mel gather slots and window starts packed
-// into three registers, the window folded into the prefilter's output gain from a chunk-order table instead of living in 16
-// registers: still 14 spilled) and three blocks' LDS per CU (8-frame tiles: the MFMA epilogue then runs half empty, twice as
-// often).  Measured 2.55 ms against 2.44 at two waves (profiles/r03_config3_ab.txt): not adopted.
-#ifndef DSP_PRE_W3
-#define DSP_PRE_W3 0
-#endif
-constexpr int W_WAVE_BYTES_T8 = W_ETILE + 128 * 8 * 4;
-constexpr int wave_bytes(bool t8) { return t8 ? W_WAVE_BYTES_T8 : W_WAVE_BYTES; }
-constexpr int b_dcta(bool t8) { return 4 * wave_bytes(t8); }
-constexpr int b_melw(bool t8) { return b_dcta(t8) + kGenDctSteps * 64 * 4; }
-constexpr int B_BYTES_PLAIN = b_melw(false);
-constexpr int B_BYTES_PRE = b_melw(DSP_PRE_W3 != 0) + kWaveSlots * kMelChunk * 64 * 4;
+//   PRE only: the mel weights (3 slots x 12 taps x 64 lanes) as float4 rows [slot][quad][lane].  Round 3 first read them from here
+//   per frame (2.50 ms per 1 M frames, after 36 dword re-reads from L1 at 2.58 .. 3.64); back in registers, 226 VGPRs at two waves
+//   per SIMD either way, it was 2.40 against 2.43 - 2.44 (profiles/r03_config3_ab.txt), and the per-frame reads were removed.  The
+//   copy is still written and its 9 KB still part of the PRE launch: dropping it changes the kernels' code and LDS footprint, which
+//   needs a measurement of its own.
+// Tried for the PRE variant: THREE waves per SIMD -- <= 168 VGPRs (mel gather slots and window starts packed into three registers,
+// the window folded into the prefilter's output gain from a chunk-order table instead of living in 16 registers: still 14 spilled)
+// and three blocks' LDS per CU (8-frame tiles: the MFMA epilogue then runs half empty, twice as often).  Measured 2.55 ms against
+// 2.44 at two waves (profiles/r03_config3_ab.txt): removed.
+constexpr int B_DCTA = 4 * W_WAVE_BYTES;
+constexpr int B_MELW = B_DCTA + kGenDctSteps * 64 * 4;
+constexpr int B_BYTES_PLAIN = B_MELW;
+constexpr int B_BYTES_PRE = B_MELW + kWaveSlots * kMelChunk * 64 * 4;
 
 // forward radix-8 butterfly: u[q] = sum_a v[a] W8^(a q)
 __device__ __forceinline__ void radix8w(c32 (&v)[8])
@@ -81,95 +78,19 @@ __device__ __forceinline__ void radix8w(c32 (&v)[8])
     v[3] = cadd(e[3], t3);   v[7] = csub(e[3], t3);
 }
 
-__device__ __forceinline__ double shfl_up_f64(double v, int byte_addr)
-{
-    const long long bits = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_ds_bpermute(byte_addr, (int)bits), hi = __builtin_amdgcn_ds_bpermute(byte_addr, (int)(bits >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-
 // Per-frame Butterworth prefilter (BASELINE config 3) on the wave that owns the frame: lane l holds samples [16 l, 16 l + 16).
-// Parallel form + scan over the lanes, float64 (PrefilterScan, tables.hpp); y = the filtered samples rounded to float, as
-// the two-pass path stores them.  ~500 v_fma_f64 per lane and frame, no HBM traffic.
-__device__ __forceinline__ void prefilter_scan(const float (&x)[kScanChunk], float (&y)[kScanChunk], const PrefilterScan *__restrict__ S, int lane)
-{
-    double t0[4], t1[4];
-    // pass 1: each section over the chunk from zero state -> the chunk's own contribution to the state at its end
-#pragma unroll
-    for (int sc = 0; sc < 4; ++sc) { t0[sc] = 0.0; t1[sc] = 0.0; }
-#pragma unroll
-    for (int i = 0; i < kScanChunk; ++i) {
-        const double xi = (double)x[i];
-#pragma unroll
-        for (int sc = 0; sc < 4; ++sc) {
-            const double w0 = xi - S->a1[sc] * t0[sc] - S->a2[sc] * t1[sc];
-            t1[sc] = t0[sc];
-            t0[sc] = w0;
-        }
-    }
-    // inclusive scan: after step d lane l holds the contribution of chunks (l - 2^(d+1), l] to the state at the end of chunk l
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-        const int from = ((lane - (1 << d)) & 63) << 2;
-        const bool on = lane >= (1 << d);
-#pragma unroll
-        for (int sc = 0; sc < 4; ++sc) {
-            if (d >= S->steps[sc]) continue;          // wave-uniform: this section's older chunks are damped below 1e-14
-            const double u0 = shfl_up_f64(t0[sc], from), u1 = shfl_up_f64(t1[sc], from);
-            const double *m = S->pw[d][sc];
-            const double n0 = t0[sc] + m[0] * u0 + m[1] * u1, n1 = t1[sc] + m[2] * u0 + m[3] * u1;
-            t0[sc] = on ? n0 : t0[sc];
-            t1[sc] = on ? n1 : t1[sc];
-        }
-    }
-    // the state a chunk starts from is the scan value of the lane before it (zero for lane 0)
-    {
-        const int from = ((lane - 1) & 63) << 2;
-#pragma unroll
-        for (int sc = 0; sc < 4; ++sc) {
-            const double u0 = shfl_up_f64(t0[sc], from), u1 = shfl_up_f64(t1[sc], from);
-            t0[sc] = lane ? u0 : 0.0;
-            t1[sc] = lane ? u1 : 0.0;
-        }
-    }
-    // pass 2: the chunk again from its true state, with the output taps
-#pragma unroll
-    for (int i = 0; i < kScanChunk; ++i) {
-        const double xi = (double)x[i];
-        double acc = S->k0 * xi;
-#pragma unroll
-        for (int sc = 0; sc < 4; ++sc) {
-            const double w0 = xi - S->a1[sc] * t0[sc] - S->a2[sc] * t1[sc];
-            acc += S->b0[sc] * w0 + S->b1[sc] * t0[sc];
-            t1[sc] = t0[sc];
-            t0[sc] = w0;
-        }
-        y[i] = (float)acc;
-    }
-}
+// The filter runs as a CASCADE of four second-order sections (PrefilterScan::c_*, tables.hpp).  Section s maps the lane's 16 samples
+// u -> y in place: w[n] = u[n] - a1 w[n-1] - a2 w[n-2], y[n] = w[n] - w[n-2] (the literal numerators are g (1 - z^-2)^4).
+// Lane-parallel: the chunk from zero state, a scan over the lanes with powers of M^16, the chunk again from its true state.
+// T = double for the first two sections (they see the unattenuated stop-band energy), float for the last two: no cancellation
+// between sections of a cascade, so float32 there costs 1e-5 of the parity gate's 1e-4 on stop-band-only frames
+// (tools/emulate_prefilter_cascade.py).
+// Round 2 ran the filter in PARALLEL FORM, float64 throughout (PrefilterScan's first fields; 552 float64 instructions per lane and
+// frame against ~210 float64 + ~210 float32): 2.75 - 2.83 ms per 1 M frames against 2.43 for the cascade
+// (profiles/r03_config3_ab.txt).  Removed; coefficients without a cascade take the two-pass path (capi.cpp).
 
-// The same filter as a CASCADE of four second-order sections (PrefilterScan::c_*, tables.hpp), the form this kernel runs since
-// round 3.  Section s maps the lane's 16 samples u -> y in place: w[n] = u[n] - a1 w[n-1] - a2 w[n-2], y[n] = w[n] - w[n-2]
-// (the literal numerators are g (1 - z^-2)^4).  Lane-parallel like the parallel form: the chunk from zero state, a Kogge-Stone
-// scan over the lanes with M^(16 * 2^d), the chunk again from its true state.  T = double for the first two sections (they see
-// the unattenuated stop-band energy), float for the last two: no cancellation between sections of a cascade, so float32 there
-// costs 1e-5 of the parity gate's 1e-4 on stop-band-only frames (tools/emulate_prefilter_cascade.py) and half the issue cycles
-// of the float64 parallel form (552 float64 instructions per lane and frame -> ~210 float64 + ~210 float32).
-template <typename T>
-__device__ __forceinline__ T shfl_lane(T v, int byte_addr);
-template <>
-__device__ __forceinline__ double shfl_lane<double>(double v, int byte_addr) { return shfl_up_f64(v, byte_addr); }
-template <>
-__device__ __forceinline__ float shfl_lane<float>(float v, int byte_addr)
-{
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
-}
-
-// lane l <- lane l - 1 (lane 0 <- 0) without the LDS crossbar: v_mov_b32_dpp wave_shr:1.  DSP_PRE_DPP1 = 1 uses it for the scan's
-// first step and for the final one-lane shift of every section (24 of the 44 ds_bpermute_b32 per frame).
-#ifndef DSP_PRE_DPP1
-#define DSP_PRE_DPP1 1
-#endif
+// lane l <- lane l - 1 without the LDS crossbar: v_mov_b32_dpp wave_shr:1, the final one-lane shift of every section
+// (as ds_bpermute_b32: 2.43 - 2.44 ms against 2.35, profiles/r03_config3_ab.txt (2); removed)
 // (bound_ctrl: lane 0, which has no source lane, reads 0 -- no v_mov of an `old` value in front of every move)
 __device__ __forceinline__ int dpp_up1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
 template <typename T>
@@ -213,7 +134,7 @@ __device__ __forceinline__ float fma_t(float a, float b, float c) { return __bui
 // instantiation each; more steps than the poles need multiply by matrices below the tolerance and are harmless): the section is
 // straight-line code without a branch, so that it can share a scheduling region with the transform of the previous frame.
 template <typename T, int STEPS>
-__device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, const T (*pw)[4][4], int sc, int lane, const T (&rowm)[4])
+__device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, const T (*pw)[4][4], int sc, const T (&rowm)[4])
 {
     // pass 1: the chunk from zero state -> its own contribution to the state (w[n-1], w[n-2]) at its end
     T t0 = 0, t1 = 0;
@@ -223,10 +144,11 @@ __device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, 
         t1 = t0;
         t0 = w0;
     }
-#if DSP_PRE_ROWSCAN
     // Row form of the inclusive scan (tables.hpp): Kogge-Stone inside each 16-lane row with DPP row_shr moves -- no LDS crossbar,
     // no select (a lane without a source reads 0: n = t + 0 exactly) --, then lane (r, j) adds M^(16 (j + 1)) (rowm, per lane) times
     // lane 15 of row r - 1 (DPP row_bcast:15; row 0 reads 0).  A second such step reaches two rows back (sections of 5 steps).
+    // (The wave-wide Kogge-Stone scan over ds_bpermute that this replaced: 1.86 ms against 1.79 - 1.81, profiles/r03_config3_ab.txt (6);
+    // removed.)
     {
         constexpr int RS = scan_row_steps(STEPS), RR = scan_row_rounds(STEPS);
         auto step = [&](T u0, T u1, const T *m) {
@@ -245,30 +167,9 @@ __device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, 
             t1 = fma_t(rowm[3], c1, fma_t(rowm[2], c0, w1));
         }
     }
-#else
-    // inclusive scan over the lanes
-#pragma unroll
-    for (int d = 0; d < STEPS; ++d) {
-        const int from = ((lane - (1 << d)) & 63) << 2;
-        const bool on = lane >= (1 << d);
-        const T u0 = (DSP_PRE_DPP1 && d == 0) ? shfl_up1<T>(t0) : shfl_lane<T>(t0, from), u1 = (DSP_PRE_DPP1 && d == 0) ? shfl_up1<T>(t1) : shfl_lane<T>(t1, from);
-        const T *m = pw[d][sc];
-        const T n0 = fma_t(m[1], u1, fma_t(m[0], u0, t0)), n1 = fma_t(m[3], u1, fma_t(m[2], u0, t1));
-        if (DSP_PRE_DPP1 && d == 0) {      // lane 0 received zeros (the DPP move's `old`): n0 = t0 + 0, n1 = t1 + 0 exactly, no select
-            t0 = n0; t1 = n1;
-        } else {
-            t0 = on ? n0 : t0;
-            t1 = on ? n1 : t1;
-        }
-    }
-#endif
-    // a chunk starts from the scan value of the lane before it (zero for lane 0)
-    {
-        const int from = ((lane - 1) & 63) << 2;
-        const T u0 = DSP_PRE_DPP1 ? shfl_up1<T>(t0) : shfl_lane<T>(t0, from), u1 = DSP_PRE_DPP1 ? shfl_up1<T>(t1) : shfl_lane<T>(t1, from);
-        t0 = (DSP_PRE_DPP1 || lane) ? u0 : (T)0;      // DPP: lane 0 already holds the move's `old` = 0
-        t1 = (DSP_PRE_DPP1 || lane) ? u1 : (T)0;
-    }
+    // a chunk starts from the scan value of the lane before it (lane 0: the DPP move's `old` = 0)
+    t0 = shfl_up1<T>(t0);
+    t1 = shfl_up1<T>(t1);
     // pass 2: the chunk again from its true state, output y = w[n] - w[n-2]
 #pragma unroll
     for (int i = 0; i < kScanChunk; ++i) {
@@ -283,7 +184,6 @@ __device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, 
 #ifndef DSP_PRE_DIAG
 #define DSP_PRE_DIAG 0
 #endif
-// wc != nullptr: the lane's 16 window values in chunk order (GenTables1024::win_chunk), multiplied into the output here
 // the per-lane matrices of the row form's cross-row step (PrefilterScan::c_rowm / c_rowmf at j = lane % 16): 24 VGPRs, loaded once
 // DSP_PRE_F64_SECTIONS: cascade sections that run in float64 (2, the default: the two that see the unattenuated stop-band energy;
 // 1 is an A/B build: section 1 in float32 as well -- measured faster and closer to the gate, see profiles/r03_config3_ab.txt)
@@ -292,8 +192,8 @@ __device__ __forceinline__ void cascade_section(T (&u)[kScanChunk], T a1, T a2, 
 #endif
 struct RowMats { double d[2][4]; float f[2][4]; float f1[4]; };
 template <int S0, int S1, int S2, int S3>
-__device__ __forceinline__ void prefilter_cascade(const float (&x)[kScanChunk], float (&y)[kScanChunk], const PrefilterScan *__restrict__ S, int lane,
-                                                  const RowMats &rm, const float *__restrict__ wc = nullptr)
+__device__ __forceinline__ void prefilter_cascade(const float (&x)[kScanChunk], float (&y)[kScanChunk], const PrefilterScan *__restrict__ S,
+                                                  const RowMats &rm)
 {
 #if DSP_PRE_DIAG == 1
     for (int i = 0; i < kScanChunk; ++i) y[i] = x[i];
@@ -302,48 +202,29 @@ __device__ __forceinline__ void prefilter_cascade(const float (&x)[kScanChunk], 
     double ud[kScanChunk];
 #pragma unroll
     for (int i = 0; i < kScanChunk; ++i) ud[i] = (double)x[i];
-    cascade_section<double, S0>(ud, S->c_a1[0], S->c_a2[0], S->c_pw, 0, lane, rm.d[0]);
-    if (DSP_PRE_F64_SECTIONS >= 2) cascade_section<double, S1>(ud, S->c_a1[1], S->c_a2[1], S->c_pw, 1, lane, rm.d[1]);
+    cascade_section<double, S0>(ud, S->c_a1[0], S->c_a2[0], S->c_pw, 0, rm.d[0]);
+    if (DSP_PRE_F64_SECTIONS >= 2) cascade_section<double, S1>(ud, S->c_a1[1], S->c_a2[1], S->c_pw, 1, rm.d[1]);
     float uf[kScanChunk];
 #pragma unroll
     for (int i = 0; i < kScanChunk; ++i) uf[i] = (float)ud[i];
-    if (DSP_PRE_F64_SECTIONS < 2) cascade_section<float, S1>(uf, S->c_a1f[1], S->c_a2f[1], S->c_pwf, 1, lane, rm.f1);
-    cascade_section<float, S2>(uf, S->c_a1f[2], S->c_a2f[2], S->c_pwf, 2, lane, rm.f[0]);
-    cascade_section<float, S3>(uf, S->c_a1f[3], S->c_a2f[3], S->c_pwf, 3, lane, rm.f[1]);
-    const float g = (float)S->c_gain;
-    if (wc) {
-        f4v w4[4];
+    if (DSP_PRE_F64_SECTIONS < 2) cascade_section<float, S1>(uf, S->c_a1f[1], S->c_a2f[1], S->c_pwf, 1, rm.f1);
+    cascade_section<float, S2>(uf, S->c_a1f[2], S->c_a2f[2], S->c_pwf, 2, rm.f[0]);
+    cascade_section<float, S3>(uf, S->c_a1f[3], S->c_a2f[3], S->c_pwf, 3, rm.f[1]);
+    // the cascade's gain rides in the window the kernel multiplies with anyway (win[] below)
 #pragma unroll
-        for (int a = 0; a < 4; ++a) w4[a] = reinterpret_cast<const f4v *>(wc)[a];
-#pragma unroll
-        for (int i = 0; i < kScanChunk; ++i) y[i] = (uf[i] * g) * w4[i >> 2][i & 3];
-    } else {
-        (void)g;                                     // the cascade's gain rides in the window the kernel multiplies with anyway (win[] below)
-#pragma unroll
-        for (int i = 0; i < kScanChunk; ++i) y[i] = uf[i];
-    }
+    for (int i = 0; i < kScanChunk; ++i) y[i] = uf[i];
 }
 
 }  // namespace
-
-// Prefilter form of the PRE variant: 1 = cascade (default where the tables allow it), 0 = the float64 parallel form of round 2
-#ifndef DSP_PRE_CASCADE
-#define DSP_PRE_CASCADE 1
-#endif
 
 // PRE: independent full frames run through the Butterworth prefilter in this kernel (lane-contiguous loads, scan, one LDS
 // transpose into the FFT's sample order) instead of a separate pass that writes a filtered copy to HBM.
 // Two waves per SIMD for every instantiation, stated: VGPRs + AGPRs share one 512-entry file per lane, and left alone hipcc
 // parks spills in AGPRs (a build with 256 VGPRs + 25 AGPRs ran at ONE wave per SIMD: 3.9 ms instead of 2.5 per 1 M config-3
 // frames; SQ_WAVES 1024 instead of 2048 was what gave it away).
-#define DSP_PRE_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(PRE && DSP_PRE_W3 ? 3 : 2, PRE && DSP_PRE_W3 ? 3 : 2)))
 // PS0..PS3 (PRE): scan steps of the four cascade sections (cascade_section)
-// PRE: mel weights in registers (1) like the plain kernel, or re-read per frame from the block-shared LDS copy (0)
-#ifndef DSP_PRE_MELW_REGS
-#define DSP_PRE_MELW_REGS 1
-#endif
 template <bool FULL, bool CLIPS, bool PRE = false, int PS0 = 6, int PS1 = 6, int PS2 = 6, int PS3 = 6>
-__global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(const Mfcc512Args args, const GenTables1024 *__restrict__ G,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void mfcc1024_wave_kernel(const Mfcc512Args args, const GenTables1024 *__restrict__ G,
                                                             const PrefilterScan *__restrict__ S = nullptr)
 {
     static_assert(!PRE || (FULL && !CLIPS), "the fused prefilter runs on independent 1024-sample frames");
@@ -351,17 +232,15 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr bool W3 = PRE && DSP_PRE_W3 != 0;
-    constexpr int TF = W3 ? 8 : 16;                   // frames per tile
-    char *wl = smem + wib * wave_bytes(W3);
+    constexpr int TF = 16;                            // frames per tile
+    char *wl = smem + wib * W_WAVE_BYTES;
     float2 *zbuf = reinterpret_cast<float2 *>(wl + W_ZBUF);
     float *pbuf = reinterpret_cast<float *>(wl + W_ZBUF);
     float *part = reinterpret_cast<float *>(wl + W_PART);
     float *etile = reinterpret_cast<float *>(wl + W_ETILE);
 
-    float *dcta_lds = reinterpret_cast<float *>(smem + b_dcta(W3));
-    f4v *melw_lds = reinterpret_cast<f4v *>(smem + b_melw(W3));
-    (void)melw_lds;
+    float *dcta_lds = reinterpret_cast<float *>(smem + B_DCTA);
+    f4v *melw_lds = reinterpret_cast<f4v *>(smem + B_MELW);      // written below, no longer read (see B_MELW above)
     for (int i = threadIdx.x; i < kGenDctSteps * 64; i += 256) dcta_lds[i] = (&G->dct_a[0][0])[i];
     if (PRE)
         for (int i = threadIdx.x; i < kWaveSlots * 3 * 64; i += 256) {      // row (slot c, quad qd), lane l: taps 4 qd .. 4 qd + 3
@@ -372,12 +251,10 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
 
     // ---- per-lane constants ------------------------------------------------------------------------------------
     float win[16];
-    if (!W3) {
-        // PRE (cascade form): the filter's output gain g = b0 is folded into the window here, once per kernel, instead of 16 multiplies per frame
-        const float wg = (PRE && DSP_PRE_CASCADE) ? (float)S->c_gain : 1.0f;
+    // PRE: the filter's output gain g = b0 is folded into the window here, once per kernel, instead of 16 multiplies per frame
+    const float wg = PRE ? (float)S->c_gain : 1.0f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) win[i] = G->win[i][lane] * wg;
-    }
+    for (int i = 0; i < 16; ++i) win[i] = G->win[i][lane] * wg;
     c32 tw1[7], tw2[7], twp[4];
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
@@ -386,36 +263,23 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) twp[t] = {G->twp[2 * t][lane], G->twp[2 * t + 1][lane]};
-    // mel weights: in registers (36 VGPRs), except in the PRE variant, whose float64 scan needs the room: there they are
-    // re-read per frame (coalesced dwords, L1-resident 9 KB table)
+    // mel weights: in registers (36 VGPRs), in the PRE variant as well
     float melw[kWaveSlots][kMelChunk];
     int mel_k0[kWaveSlots];
 #pragma unroll
     for (int c = 0; c < kWaveSlots; ++c) {
         mel_k0[c] = G->mel_k0[c][lane];
-        if (!PRE || DSP_PRE_MELW_REGS) {
 #pragma unroll
-            for (int i = 0; i < kMelChunk; ++i) melw[c][i] = G->mel_w[c][i][lane];
-        }
+        for (int i = 0; i < kMelChunk; ++i) melw[c][i] = G->mel_w[c][i][lane];
     }
     int gat[kGenMelsPerLane][kGenGather];           // partial slots of filters lane and lane + 64 (slots >= 128 read the zero slot)
-    unsigned gatp[kGenMelsPerLane][2] = {};          // W3: the same six slots (< 256 each) in two registers per filter
-    static_assert(kGenGather == 6 && kWaveZero < 256, "packed gather slots");
 #pragma unroll
     for (int i = 0; i < kGenMelsPerLane; ++i)
 #pragma unroll
         for (int g = 0; g < kGenGather; ++g) {
             const int sidx = G->mel_src[i][g][lane];
-            const int v = sidx < kWaveSlots * 64 ? sidx : kWaveZero;
-            if (W3) gatp[i][g >> 2] |= (unsigned)v << (8 * (g & 3));
-            else gat[i][g] = v;
+            gat[i][g] = sidx < kWaveSlots * 64 ? sidx : kWaveZero;
         }
-    unsigned k0p = 0;                                  // W3: the three window starts (< 1024 each) in one register
-    if (W3) {
-#pragma unroll
-        for (int c = 0; c < kWaveSlots; ++c) k0p |= (unsigned)mel_k0[c] << (10 * c);
-    }
-    (void)gatp; (void)k0p;
     const int n_mels = args.n_mels, n_mfcc = args.n_mfcc;
     const int l_hi = lane >> 3, l_lo = lane & 7;
     const int partner = ((64 - lane) & 63) << 2;     // byte index for ds_bpermute
@@ -482,7 +346,7 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
         const float rinv = __builtin_amdgcn_rcpf(__uint_as_float(mx));
         f4v acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
         auto kstep = [&](int s, f4v &acc) {
-            const float e_s = etile[TF * (4 * s + q) + ((n ^ (2 * s + (q >> 1))) & (TF - 1))];      // TF = 8: columns 8 .. 15 repeat 0 .. 7 and are not stored
+            const float e_s = etile[TF * (4 * s + q) + ((n ^ (2 * s + (q >> 1))) & (TF - 1))];
             const float ec = __uint_as_float(max(__float_as_uint(e_s), amin_u));
             float db = 3.01029995663981195f * __builtin_amdgcn_logf(ec * rinv);
             db = __builtin_amdgcn_fmed3f(db, neg_top_db, 0.0f);
@@ -493,7 +357,7 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
         for (int s = 0; s < kGenDctSteps; s += 2) { kstep(s, acc0); kstep(s + 1, acc1); }
         const f4v d = acc0 + acc1;
         const long fl = (n < 8 ? fb0 : fb1 - 8) + n;
-        const bool ok = n < count && n < TF && fl < n_frames;
+        const bool ok = n < count && fl < n_frames;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int c = 4 * q + j;
@@ -502,18 +366,14 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
         wave_lds_sync();
     };
 
-    // PRE: an iteration transforms frame k from its filtered samples `ys` (in the lanes' chunk order) and filters frame k + 1 --
-    // after the transform (default), or (DSP_PRE_PIPE = 1, an experiment) in front of it in the same branch-free scheduling region,
-    // in the hope that the scheduler overlaps the two latency-bound chains.  The last iteration filters a frame nobody uses.
-// DSP_PRE_PIPE = 1 was built and measured: hipcc does not interleave the two chains, it only stretches the live ranges (256 VGPRs,
-// 16 spilled): 3.52 ms against 2.43 for the plain order (profiles/r03_config3_ab.txt).  The plain order is the default.
-#ifndef DSP_PRE_PIPE
-#define DSP_PRE_PIPE 0
-#endif
+    // PRE: an iteration transforms frame k from its filtered samples `ys` (in the lanes' chunk order) and then filters frame k + 1.
+    // The last iteration filters a frame nobody uses.  Tried: the filter in front of the transform in the same branch-free
+    // scheduling region, in the hope that the scheduler overlaps the two latency-bound chains -- hipcc does not interleave them, it
+    // only stretches the live ranges (256 VGPRs, 16 spilled): 3.52 ms against 2.43 for this order (profiles/r03_config3_ab.txt).
     float ys[kScanChunk];
     (void)ys;
     RowMats rowm = {};
-    if (PRE && DSP_PRE_ROWSCAN) {
+    if (PRE) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             rowm.d[0][k] = S->c_rowm[0][lane & 15][k]; rowm.d[1][k] = S->c_rowm[1][lane & 15][k];
@@ -521,32 +381,18 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
             rowm.f1[k] = DSP_PRE_F64_SECTIONS < 2 ? S->c_rowmf[1][lane & 15][k] : 0.0f;
         }
     }
-// DSP_PRE_EARLY_LOAD = 1 (an experiment): the loads of the frame after next are issued as soon as the filter has taken `nxt`, not
-// after the filter: in flight during the filter AND the next transform (sixteen more live VGPRs across the filter, still 238 in all).
-// Measured 1 % slower (1.82 vs 1.80 ms, profiles/r03_config3_ab.txt): this kernel does not wait for its loads.
-#ifndef DSP_PRE_EARLY_LOAD
-#define DSP_PRE_EARLY_LOAD 0
-#endif
+    // filter_next: filters the frame in `nxt`, then starts the load of the frame after it (f_next = -1: nothing is left).  Tried: its loads issued as soon as the filter has taken `nxt`, in flight
+    // during the filter and the next transform (sixteen more live VGPRs across the filter, still 238 in all): 1 % slower (1.82 vs
+    // 1.80 ms, profiles/r03_config3_ab.txt) -- this kernel does not wait for its loads.
     auto filter_next = [&](float (&out)[kScanChunk]) {
         float xs[kScanChunk];
 #pragma unroll
         for (int a = 0; a < 8; ++a) { xs[2 * a] = nxt[a].x; xs[2 * a + 1] = nxt[a].y; }
-        if (DSP_PRE_EARLY_LOAD) {
-#pragma unroll
-            for (int a = 0; a < kScanChunk; ++a) asm volatile("" : "+v"(xs[a]));       // the copy is real: nxt is free from here
-            if (pre.valid()) { f_next = pre.f; load_frame8(pre.off, nxt); pre.next(); } else f_next = -1;
-        }
-#if DSP_PRE_CASCADE
-        prefilter_cascade<PS0, PS1, PS2, PS3>(xs, out, S, lane, rowm, W3 ? &G->win_chunk[lane][0] : nullptr);
-#else
-        prefilter_scan(xs, out, S, lane);
-#endif
+        prefilter_cascade<PS0, PS1, PS2, PS3>(xs, out, S, rowm);
+        if (pre.valid()) { f_next = pre.f; load_frame8(pre.off, nxt); pre.next(); } else f_next = -1;
     };
     long f_cur = f_next;
-    if (PRE) {                      // prologue: frame 0 filtered, frame 1 in flight
-        filter_next(ys);
-        if (!DSP_PRE_EARLY_LOAD) { if (pre.valid()) { f_next = pre.f; load_frame8(pre.off, nxt); pre.next(); } else f_next = -1; }
-    }
+    if (PRE) filter_next(ys);       // prologue: frame 0 filtered, frame 1 in flight
 
     while (true) {
         const long f = PRE ? f_cur : f_next;
@@ -564,16 +410,13 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
 #pragma unroll
             for (int a = 0; a < 8; ++a) {
                 const float2 q = zbuf[lane + 64 * a];
-                if (W3) v[a] = {q.x, q.y};                      // the window went in with the prefilter's gain
-                else v[a] = {q.x * win[2 * a], q.y * win[2 * a + 1]};
+                v[a] = {q.x * win[2 * a], q.y * win[2 * a + 1]};
             }
             wave_lds_sync();
             // the next frame: its samples are in `nxt` (or nothing is left: then what `nxt` still holds is filtered for nobody);
             // the frame after it starts loading behind the filter's reads of `nxt`
             more = f_next >= 0;
             f_cur = f_next;
-            if (DSP_PRE_PIPE) filter_next(ys_next);
-            if (DSP_PRE_PIPE) { if (pre.valid()) { f_next = pre.f; load_frame8(pre.off, nxt); pre.next(); } else f_next = -1; }
         } else {
 #pragma unroll
             for (int a = 0; a < 8; ++a) v[a] = {nxt[a].x * win[2 * a], nxt[a].y * win[2 * a + 1]};
@@ -654,22 +497,13 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
 
         // ---- sparse mel: two chunk slots per lane, weights in registers ---------------------------------------------
         int wl_lane = lane;
-        if (PRE) asm volatile("" : "+v"(wl_lane));       // opaque per frame: the weight reads stay in the loop (not hoisted back into registers)
+        if (PRE) asm volatile("" : "+v"(wl_lane));       // left from the per-frame LDS weight reads (their index): emits nothing, but the PRE kernels' schedule depends on it
 #pragma unroll
         for (int c = 0; c < kWaveSlots; ++c) {
-            const float *rd = pbuf + (W3 ? (int)((k0p >> (10 * c)) & 1023u) : mel_k0[c]);
+            const float *rd = pbuf + mel_k0[c];
             float acc = 0.0f;
-            if (PRE && !DSP_PRE_MELW_REGS) {
 #pragma unroll
-                for (int qd = 0; qd < 3; ++qd) {
-                    const f4v w = melw_lds[(c * 3 + qd) * 64 + wl_lane];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc = fmaf(w[j], rd[4 * qd + j], acc);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < kMelChunk; ++i) acc = fmaf(melw[c][i], rd[i], acc);
-            }
+            for (int i = 0; i < kMelChunk; ++i) acc = fmaf(melw[c][i], rd[i], acc);
             part[c * 64 + lane] = acc;
         }
         wave_lds_sync();
@@ -678,7 +512,7 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
         for (int i = 0; i < kGenMelsPerLane; ++i) {
             float s = 0.0f;
 #pragma unroll
-            for (int g = 0; g < kGenGather; ++g) s += part[W3 ? (int)((gatp[i][g >> 2] >> (8 * (g & 3))) & 255u) : gat[i][g]];
+            for (int g = 0; g < kGenGather; ++g) s += part[gat[i][g]];
             const int m = lane + 64 * i;
             if (m >= n_mels) s = 0.0f;
             etile[TF * m + ((slot ^ (m >> 1)) & (TF - 1))] = s;
@@ -687,10 +521,7 @@ __global__ __launch_bounds__(256) DSP_PRE_WAVES_ATTR void mfcc1024_wave_kernel(c
         else wave_lds_sync();
         if (!more) return;
         if (PRE) {
-            if (!DSP_PRE_PIPE) {        // not pipelined: the next frame is filtered here, after this one's transform
-                filter_next(ys_next);
-                if (!DSP_PRE_EARLY_LOAD) { if (pre.valid()) { f_next = pre.f; load_frame8(pre.off, nxt); pre.next(); } else f_next = -1; }
-            }
+            filter_next(ys_next);        // the next frame is filtered here, after this one's transform
 #pragma unroll
             for (int i = 0; i < kScanChunk; ++i) ys[i] = ys_next[i];
         }

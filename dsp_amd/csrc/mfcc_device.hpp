@@ -57,53 +57,15 @@ __device__ __forceinline__ void swap_odd16(float &a, float &b)
     b = __uint_as_float(r[1]);
 }
 
-// 2x2 block transposes between a register pair (a: slot bit 0, b: slot bit 1) and
-// one lane bit: afterwards a[bit=1] holds the partner lane's old b, b[bit=0] the
-// partner lane's old a.
-template <int CTRL, int BANKS>
-__device__ __forceinline__ float dpp_into(float old, float src);
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v);
-__device__ __forceinline__ void swap_lane8(float &a, float &b);
-__device__ __forceinline__ void swap_lane4(float &a, float &b);
-
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-// masked DPP move: lanes whose bank (lane%16/4) is in BANKS take src[perm], others keep old
-template <int CTRL, int BANKS>
-__device__ __forceinline__ float dpp_into(float old, float src)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xF, BANKS, false));
-}
-constexpr int DPP_ROW_SHL4 = 0x104, DPP_ROW_SHR4 = 0x114, DPP_ROW_ROR8 = 0x128;
 constexpr int DPP_QUAD_1032 = 0xB1;   // quad_perm:[1,0,3,2]
 constexpr int DPP_QUAD_2301 = 0x4E;   // quad_perm:[2,3,0,1]
 constexpr int DPP_ROW_HALF_MIRROR = 0x141;
 constexpr int DPP_ROW_MIRROR = 0x140;
-
-__device__ __forceinline__ void swap_lane8(float &a, float &b)
-{   // lane ^ 8 = rotate the 16-lane row by 8; banks 0,1 have bit3 = 0, banks 2,3 bit3 = 1
-    const float nb = dpp_into<DPP_ROW_ROR8, 0x3>(b, a);
-    a = dpp_into<DPP_ROW_ROR8, 0xC>(a, b);
-    b = nb;
-}
-__device__ __forceinline__ void swap_lane4(float &a, float &b)
-{   // lane ^ 4: banks 0,2 (bit2 = 0) read lane+4, banks 1,3 read lane-4
-    const float nb = dpp_into<DPP_ROW_SHL4, 0x5>(b, a);
-    a = dpp_into<DPP_ROW_SHR4, 0xA>(a, b);
-    b = nb;
-}
-// lane bits 1 and 0 have no DPP write mask: quad permute + select on the lane bit
-template <int CTRL>
-__device__ __forceinline__ void swap_quad(float &a, float &b, bool bit_set)
-{
-    const float pa = dpp<CTRL>(a), pb = dpp<CTRL>(b);
-    b = bit_set ? b : pa;
-    a = bit_set ? pb : a;
-}
 
 // max over the wave of NON-NEGATIVE floats: their bit patterns order like
 // unsigned integers, so the reduction runs on v_max_u32 (fuses with DPP, needs no

@@ -11,9 +11,11 @@
 //             1: v_permlane32/16_swap (lane bits 5:4); 2 and 3 (lane bits 3:2,
 //             1:0): a 2 KiB per-wave LDS tile with XOR swizzles (bank-conflict
 //             free; the last one also restores natural bin order).
-//             DSP_X2_LDS / DSP_X3_LDS = 0 switch 2 / 3 to DPP register moves
-//             (measured slower: DPP and v_cndmask issue at ~half rate, see
-//             DESIGN.md; dataflow model of all forms: tools/emulate_wave_fft.py)
+//             Tried and removed: 1 through LDS +7 %, 2 + 3 as DPP register moves
+//             +5 % (DPP and v_cndmask issue at ~half rate), 2 by DPP with the
+//             untangling through one b128 LDS round trip -1.2 %, inside the +-1.5 %
+//             of the measurement (profiles/HISTORY.md, "Exchanges"; dataflow model
+//             of all forms: tools/emulate_wave_fft.py)
 //   untangle  conjugate-pair split with ds_bpermute from the partner lane (packed real FFT)
 //   power     |X[k]|^2, k = 0..256                                     mfcc.c:151-155
 //   mel       sparse HTK triangles: <= 12 bins per lane + 3-way gather  mfcc.c:158-164
@@ -38,14 +40,6 @@
 // Outputs are wrong in all of them; only the time is read.
 #ifndef DSP_DIAG_MODE
 #define DSP_DIAG_MODE 0
-#endif
-// exchange 1 (slot <-> lane bits 5:4): 1 = through the LDS tile, 0 = v_permlane32/16_swap
-#ifndef DSP_X1_LDS
-#define DSP_X1_LDS 0
-#endif
-// conjugate partner of the untangling step: 1 = one b128 LDS round trip, 0 = 4 ds_bpermute_b32
-#ifndef DSP_UNT_LDS
-#define DSP_UNT_LDS 0
 #endif
 // frames in flight per wave (software prefetch ring); each costs 8 VGPRs
 #ifndef DSP_PREFETCH
@@ -256,9 +250,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
     const int d0 = lane & 3, d1 = (lane >> 2) & 3, d2 = lane >> 4;
     const int w3base = 64 * d2 + 4 * (d0 ^ d2) + d1;        // + 16 o
     const int r3base = 64 * d0 + 16 * d2 + d1;              // + 4 (d ^ beta),  beta = d0
-    (void)w3base; (void)r3base;
-    const bool bit1 = lane & 2, bit0 = lane & 1;
-    (void)bit1; (void)bit0;
     const int kap = T->kappa[lane];                 // this lane ends up with bins 64 t + kap
     const int partner = T->partner[lane] << 2;      // byte index for ds_bpermute
     const bool self_paired = kap == 0;              // bins 0/256, 64/192 and 128 pair inside lane 0
@@ -658,29 +649,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
         radix4(s);                                             // digit a (bits 7:6)
 #pragma unroll
         for (int q = 1; q < 4; ++q) s[q] = cmul(s[q], tw1[q - 1]);
-#if DSP_X1_LDS
-        // exchange 1: slot a <-> lane bits 5:4 through LDS.  A1 = 64 a + ((16 h + r) ^ 16 (a & 1)):
-        // writer lane (h, r) slot a, reader lane (h, r) slot a' takes lane (a', r) slot h
-#pragma unroll
-        for (int a = 0; a < 4; ++a) xchg[64 * a + (lane ^ (16 * (a & 1)))] = {s[a].x, s[a].y};
-        wave_lds_sync();
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const float2 v = xchg[64 * d2 + ((16 * a + (lane & 15)) ^ (16 * (d2 & 1)))];
-            s[a] = {v.x, v.y};
-        }
-        wave_lds_sync();
-#else
         // exchange 1: slot <-> lane bits 5:4, in registers
         swap_hi32(s[0].x, s[2].x); swap_hi32(s[0].y, s[2].y);
         swap_hi32(s[1].x, s[3].x); swap_hi32(s[1].y, s[3].y);
         swap_odd16(s[0].x, s[1].x); swap_odd16(s[0].y, s[1].y);
         swap_odd16(s[2].x, s[3].x); swap_odd16(s[2].y, s[3].y);
-#endif
         radix4(s);                                             // digit b (bits 5:4)
 #pragma unroll
         for (int q = 1; q < 4; ++q) s[q] = cmul(s[q], tw2[q - 1]);
-#if DSP_X2_LDS
         // exchange 2: slot <-> lane bits 3:2, through LDS
 #pragma unroll
         for (int p = 0; p < 4; ++p) xchg[(lane ^ (4 * p)) + 64 * p] = {s[p].x, s[p].y};
@@ -691,13 +667,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
             s[c] = {v.x, v.y};
         }
         wave_lds_sync();
-#else
-        // exchange 2: slot <-> lane bits 3:2, DPP row moves
-        swap_lane8(s[0].x, s[2].x); swap_lane8(s[0].y, s[2].y);
-        swap_lane8(s[1].x, s[3].x); swap_lane8(s[1].y, s[3].y);
-        swap_lane4(s[0].x, s[1].x); swap_lane4(s[0].y, s[1].y);
-        swap_lane4(s[2].x, s[3].x); swap_lane4(s[2].y, s[3].y);
-#endif
         DSP_SETPRIO(DSP_PRIO_FFT, DSP_PRIO_FFT2);
 #ifdef DSP_DIAG_SNOPS      // timing-only probe: extra scalar / vector issue slots per frame (is the kernel bound by instruction issue?)
 #pragma unroll
@@ -710,7 +679,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
         radix4(s);                                             // digit c (bits 3:2)
 #pragma unroll
         for (int q = 1; q < 4; ++q) s[q] = cmul(s[q], tw3[q - 1]);
-#if DSP_X3_LDS
         // exchange 3: slot <-> lane bits 1:0, through LDS; reader lane = k mod 64
 #pragma unroll
         for (int o = 0; o < 4; ++o) xchg[w3base + 16 * o] = {s[o].x, s[o].y};
@@ -721,13 +689,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
             s[dd] = {v.x, v.y};
         }
         wave_lds_sync();
-#else
-        // exchange 3: slot <-> lane bits 1:0, DPP quad permutes
-        swap_quad<DPP_QUAD_2301>(s[0].x, s[2].x, bit1); swap_quad<DPP_QUAD_2301>(s[0].y, s[2].y, bit1);
-        swap_quad<DPP_QUAD_2301>(s[1].x, s[3].x, bit1); swap_quad<DPP_QUAD_2301>(s[1].y, s[3].y, bit1);
-        swap_quad<DPP_QUAD_1032>(s[0].x, s[1].x, bit0); swap_quad<DPP_QUAD_1032>(s[0].y, s[1].y, bit0);
-        swap_quad<DPP_QUAD_1032>(s[2].x, s[3].x, bit0); swap_quad<DPP_QUAD_1032>(s[2].y, s[3].y, bit0);
-#endif
 
         // ---- last butterfly, packed-real untangling, power spectrum ----------------
         // the lane with bins kap, kap+64 pairs them with 256-kap and 192-kap; both live
@@ -735,22 +696,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
         DSP_SETPRIO(DSP_PRIO_FFT2, DSP_PRIO_UNT);
         radix4(s);                                             // digit d: s[t] = Z[64 t + kap] / 2
         c32 b, d;
-#if DSP_UNT_LDS
-        {
-            float4 *pt = reinterpret_cast<float4 *>(xchg);
-            pt[lane] = make_float4(s[2].x, s[2].y, s[3].x, s[3].y);
-            wave_lds_sync();
-            const float4 v = pt[partner >> 2];
-            wave_lds_sync();
-            d = {v.x, v.y};
-            b = {v.z, v.w};
-        }
-#else
         b.x = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(s[3].x)));
         b.y = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(s[3].y)));
         d.x = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(s[2].x)));
         d.y = __int_as_float(__builtin_amdgcn_ds_bpermute(partner, __float_as_int(s[2].y)));
-#endif
         // selects, not a branch: lane 0 exists in every wave, so a branch is always taken
         b.x = self_paired ? s[0].x : b.x; b.y = self_paired ? s[0].y : b.y;
         d.x = self_paired ? s[3].x : d.x; d.y = self_paired ? s[3].y : d.y;

@@ -84,9 +84,6 @@ hipError_t launch_mfcc512_pool(const Mfcc512Args &args, int dct_split, int dct_l
 // fused clip -> stop-word probability (reference shape only: 13 coefficients, 40 mel): args.chunk == args.frames_per_clip, args.stop set
 int mfcc512_stop_grid(int blocks, const StopModelDev &m, int in_kind, int gather, int frame_len);      // the grid launch_mfcc512_stop starts for a caller's count
 hipError_t launch_mfcc512_stop(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream);
-hipError_t launch_mfcc512_row(const Mfcc512Args &args, const RowTables512 *row_tables, int dct_split, int dct_len,
-                              int gather, int blocks, hipStream_t stream);
-int mfcc512_row_blocks_per_cu(int dct_split, int dct_len, int gather, bool full);
 hipError_t launch_mfcc1024(const Mfcc512Args &args, const GenTables1024 *tables, int blocks, hipStream_t stream);
 int mfcc1024_blocks_per_cu(bool full);
 // register-resident wave-per-frame form (mfcc1024_wave_kernel.hip): tables->n_chunk_slots <= 3, chunk % 8 == 0
@@ -99,10 +96,6 @@ int mfcc1024_wave_blocks_per_cu(bool full, bool prefilter = false);
 int mfcc512_lds_bytes_per_block(bool tile);
 // n_fft = 2048 (mfcc2048_kernel.hip); pool: the fused clip -> label form (args.chunk == args.frames_per_clip, args.pool set)
 struct GenTables2048;
-struct PairExtra512;
-// two frames per wavefront step, reference shape, independent 512-sample frames (mfcc512_pair_kernel.hip; DSP_KERNEL_PAIR)
-hipError_t launch_mfcc512_pair(const Mfcc512Args &args, const PairExtra512 *extra, int blocks, hipStream_t stream);
-int mfcc512_pair_blocks_per_cu();
 hipError_t launch_mfcc2048(const Mfcc512Args &args, const GenTables2048 *tables, int blocks, hipStream_t stream, bool pool);
 int mfcc2048_blocks_per_cu(int n_mels, bool pool, bool aub = false);      // aub: the aubio-semantics kernels (spectrum / log10 / stream framing) and their LDS
 int mfcc512_blocks_per_cu(int dct_split, int dct_len, int gather, bool full, bool tile);

@@ -23,11 +23,8 @@ struct dsp_mfcc_plan {
     int chunk = 0;           // 0 = default
     dsp::LaneTables512 host;
     dsp::DeviceBuf<dsp::LaneTables512> d_tables;
-    dsp::DeviceBuf<dsp::RowTables512> d_row_tables;
     dsp::DeviceBuf<dsp::GenTables1024> d_gen_tables;   // n_fft = 1024
     dsp::DeviceBuf<dsp::GenTables2048> d_tables2048;   // n_fft = 2048
-    dsp::DeviceBuf<dsp::PairExtra512> d_pair;          // n_fft = 512: extra constants of the two-frames-per-wave kernel (DSP_KERNEL_PAIR)
-    int resident_blocks_pair = 3;
     int resident_blocks_2048 = 2, resident_blocks_2048_pool = 2;
     int resident_blocks_gen = 3;
     int gen_slots = 0;                            // mel chunk slots per lane the 1024-point tables use (<= 3: wave kernel)
@@ -39,7 +36,6 @@ struct dsp_mfcc_plan {
     dsp::DeviceBuf<float> d_frame_max, d_clip_floor;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
     int kernel = DSP_KERNEL_WAVE;
     bool aub = false;                             // n_fft = 2048 with aubio's semantics (magnitude spectrum, log10 floor or stream framing)
-    int resident_blocks_row = 3;
     // staging for the host-pointer entry points
     dsp::DeviceBuf<float> d_in, d_out;
     // Guards the plan's workspaces (d_filtered, d_frame_max / d_clip_floor, d_in / d_out) while a call reserves them and

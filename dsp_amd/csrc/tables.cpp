@@ -428,8 +428,6 @@ bool build_gen_tables_1024(const dsp_mfcc_config &cfg, GenTables1024 &t, std::st
             t.win[2 * a][l] = 0.5f * win[2 * n];
             t.win[2 * a + 1][l] = 0.5f * win[2 * n + 1];
         }
-    for (int l = 0; l < kLanes; ++l)
-        for (int i = 0; i < 16; ++i) t.win_chunk[l][i] = 0.5f * win[16 * l + i];
     for (int i = 0; i < 512; ++i) unit((double)i / 512.0, t.w512[0][i], t.w512[1][i]);
     for (int k = 0; k < 256; ++k) unit((double)k / 1024.0, t.w1024[0][k], t.w1024[1][k]);
 
@@ -528,35 +526,6 @@ bool build_gen_tables_1024(const dsp_mfcc_config &cfg, GenTables1024 &t, std::st
     return true;
 }
 
-void build_pair_extra_512(PairExtra512 &t)
-{
-    std::memset(&t, 0, sizeof(t));
-    for (int l = 0; l < kLanes; ++l) {
-        const int f = (l >> 2) & 1, j = (l & 3) + 4 * (l >> 3);
-        for (int p = 1; p < 8; ++p) unit((double)((l % 8) * p) / 64.0, t.tw2[2 * (p - 1)][l], t.tw2[2 * (p - 1) + 1][l]);
-        for (int tt = 0; tt < 4; ++tt) unit((double)(j + 32 * tt) / 512.0, t.twp[2 * tt][l], t.twp[2 * tt + 1][l]);
-        const int jp = (32 - j) & 31;
-        t.partner[l] = (jp & 3) | (f << 2) | ((jp >> 2) << 3);
-    }
-}
-
-void build_row_tables_512(const dsp_mfcc_config &cfg, RowTables512 &t)
-{
-    std::memset(&t, 0, sizeof(t));
-    std::vector<float> win = make_frame_window(cfg);
-    win.resize(512, 0.0f);
-    for (int l = 0; l < kLanes; ++l) {
-        const int j = l & 15;
-        for (int k = 0; k < 16; ++k) {
-            const int n = j + 16 * k;
-            t.win[2 * k][l] = 0.5f * win[2 * n];          // x0.5: see build_lane_tables_512
-            t.win[2 * k + 1][l] = 0.5f * win[2 * n + 1];
-        }
-        for (int q = 1; q <= 15; ++q) unit((double)(j * q) / 256.0, t.tw[2 * (q - 1)][l], t.tw[2 * (q - 1) + 1][l]);
-        for (int m = 0; m < 8; ++m) unit((double)(j + 16 * m) / 512.0, t.twp[2 * m][l], t.twp[2 * m + 1][l]);
-    }
-}
-
 bool build_lane_tables_512(const dsp_mfcc_config &cfg, LaneTables512 &t, std::string &why)
 {
     std::memset(&t, 0, sizeof(t));
@@ -586,13 +555,12 @@ bool build_lane_tables_512(const dsp_mfcc_config &cfg, LaneTables512 &t, std::st
             unit((double)((l & 3) * q) / 16.0, t.tw3[2 * (q - 1)][l], t.tw3[2 * (q - 1) + 1][l]);
         }
     }
-    // After the FFT lane l holds bins 64 t + kappa(l).  With exchange 3 through LDS
-    // the reader lanes are chosen so that kappa = l; with the register-only (DPP)
-    // exchange lane l = (beta, p, o) (base-4 digits) ends with kappa = 16 o + 4 p + beta.  The
-    // conjugate partner of bin k is bin 256 - k, i.e. kappa' = (64 - kappa) mod 64.
+    // After the FFT lane l holds bins 64 t + kappa(l); exchange 3 goes through LDS and its reader lanes are chosen so that
+    // kappa = l (the register-only DPP exchange, which ended with the base-4 digits of l reversed, measured +5 % and
+    // was removed: profiles/HISTORY.md, "Exchanges").  The conjugate partner of bin k is bin 256 - k, i.e. kappa' = (64 - kappa) mod 64.
     int lane_of[kLanes];
     for (int l = 0; l < kLanes; ++l) {
-        t.kappa[l] = DSP_X3_LDS ? l : 16 * (l & 3) + 4 * ((l >> 2) & 3) + (l >> 4);
+        t.kappa[l] = l;
         lane_of[t.kappa[l]] = l;
     }
     for (int l = 0; l < kLanes; ++l) {

@@ -12,16 +12,6 @@
 
 #include "../../include/dsp_amd.h"
 
-// Exchange implementation of the last two FFT stage boundaries (A/B switches,
-// see DESIGN.md "FFT exchanges"): 1 = through the per-wave LDS tile with XOR
-// swizzles, 0 = DPP register moves.  The final lane -> bin map depends on exchange 3.
-#ifndef DSP_X2_LDS
-#define DSP_X2_LDS 1
-#endif
-#ifndef DSP_X3_LDS
-#define DSP_X3_LDS 1
-#endif
-
 namespace dsp {
 
 // ---- plain tables (reference layouts) --------------------------------------
@@ -49,7 +39,7 @@ struct LaneTables512 {
     float tw2[6][kLanes];   // W64^((l%16) q)
     float tw3[6][kLanes];   // W16^((l%4) q)
     float twp[4][kLanes];   // W512^kappa, W512^(kappa+64); kappa(l) = the bin (mod 64) lane l ends up with
-    int32_t kappa[kLanes];  // l (exchange 3 through LDS) or 16*(l&3) + 4*((l>>2)&3) + (l>>4) (DPP)
+    int32_t kappa[kLanes];  // = l (exchange 3 goes through LDS; its reader lanes are chosen so)
     int32_t partner[kLanes];// lane that holds bin (64 - kappa) mod 64
     // sparse mel: lane owns bins [k0, k0+12) of one filter
     int32_t mel_k0[kLanes];
@@ -68,27 +58,6 @@ struct LaneTables512 {
     // k-step s holds D[16 ct + c][4 s + q] (0 outside n_mfcc x n_mels)
     float dct_a[2][kDctSteps][kLanes];
 };
-
-// ---- extra per-lane constants of the two-frames-per-wave kernel (mfcc512_pair_kernel.hip) ------------------------------------
-// Two 512-sample frames ride the radix-8 pipeline of the 1024-point kernel as eight independent 64-point transforms: slots
-// q = q' + 4 f (f = frame, q' = output of the frame's first radix-4 butterfly).  Lane l ends with bins j + 32 r (r = 0..7) of
-// frame f = (l >> 2) & 1, j = (l & 3) + 4 (l >> 3).
-struct PairExtra512 {
-    float tw2[14][kLanes];      // W64^((l % 8) p), p = 1..7 (cos, sin): after the second stage
-    float twp[8][kLanes];       // W512^(j + 32 t), t = 0..3: untangling the packed real transform
-    int32_t partner[kLanes];    // lane of the same frame that holds bins (32 - j) + 32 r
-};
-void build_pair_extra_512(PairExtra512 &t);
-
-// ---- per-lane layout of the FFT front end of the row-per-frame kernel -------------
-// (4 frames per wave: lane = 16 g + j, row g = frame, 16 complex points per lane; the
-// tail -- mel, log, DCT -- reuses LaneTables512).
-struct RowTables512 {
-    float win[32][kLanes];   // x0.5 window for samples 2(j+16k), 2(j+16k)+1 at [2k], [2k+1]
-    float tw[30][kLanes];    // W256^(j q), q = 1..15: (cos, sin) at [2(q-1)], [2(q-1)+1]
-    float twp[16][kLanes];   // W512^(j+16m), m = 0..7: (cos, sin) at [2m], [2m+1]
-};
-void build_row_tables_512(const dsp_mfcc_config &cfg, RowTables512 &t);
 
 // ---- tables of the general 1024-point kernel (mfcc1024_kernel.hip) ------------------
 constexpr int kGenChunks = 4;      // mel chunks (12 bins) per lane  -> up to 256 chunks
@@ -111,7 +80,6 @@ struct GenTables1024 {
     float tw2[14][kLanes];                 // W64^((l % 8) p),   p = 1..7: after the second stage
     float twp[8][kLanes];                  // W1024^(l + 64 t),  t = 0..3: untangling the packed real transform
     float dct_a[kGenDctSteps][kLanes];     // MFMA A operand of the tile epilogue: lane (c = l % 16, q = l / 16), step s: D[c][4 s + q]
-    float win_chunk[kLanes][16];           // the x0.5 window in the prefilter's chunk order: lane l, samples 16 l .. 16 l + 15 (full 1024-sample frames)
 };
 constexpr int kGenZeroSlot = kGenChunks * kLanes;   // partial slot that always reads 0
 bool build_gen_tables_1024(const dsp_mfcc_config &cfg, GenTables1024 &t, std::string &why);
@@ -152,6 +120,9 @@ bool build_gen_tables_2048(const dsp_mfcc_config &cfg, GenTables2048 &t, std::st
 // chunk boundaries (state_out = M_s^16 state_in + local; step d multiplies by pw[d][s] = M_s^(16 * 2^d), M_s = [[-a1, -a2],
 // [1, 0]]), and the lane reruns its chunk from its true initial state.  float64 throughout; equals the direct-form-II
 // recurrence to ~1e-13 (checked at plan creation on 1024 random samples), i.e. to the last bit or so of the float result.
+// The kernels no longer read the parallel-form fields (k0 .. steps): round 2's form, 2.75 - 2.83 ms per 1 M frames against 2.43 for
+// the cascade below (profiles/r03_config3_ab.txt), was removed from mfcc1024_wave_kernel.hip.  They keep their place so that the
+// fields the kernels do read stay where they are; build_prefilter_scan still fills and checks them.
 struct PrefilterScan {
     double k0;
     double b0[4], b1[4], a1[4], a2[4];
@@ -175,8 +146,9 @@ struct PrefilterScan {
     float c_a1f[4], c_a2f[4];
     float c_pwf[6][4][4];
     int32_t c_steps[4];            // scan steps per section: float64 sections to 1e-13, float32 sections to 1e-9
-    int32_t c_ok;                  // 0: the numerator is not g (1 - z^-2)^4 -> the kernel runs the parallel form
-    // Row form of the same scan (the kernel's DSP_PRE_ROWSCAN): Kogge-Stone steps of 1, 2, 4, 8 lanes INSIDE each 16-lane row
+    int32_t c_ok;                  // 0: the numerator is not g (1 - z^-2)^4 -> no fused prefilter, the plan filters in a pass of its own
+    // Row form of the same scan (the form the kernel runs; the wave-wide scan over ds_bpermute, 1.86 ms against 1.79 - 1.81, was
+    // removed: profiles/r03_config3_ab.txt): Kogge-Stone steps of 1, 2, 4, 8 lanes INSIDE each 16-lane row
     // (DPP row_shr moves: no LDS crossbar, lanes without a source read 0), then one "cross-row" step per row that still matters:
     // lane (r, j) adds c_rowm[s][j] = M_s^(16 (j + 1)) times the value of lane 15 of row r - 1 (DPP row_bcast:15).  After the first
     // such step lane 15 of a row holds its row's total plus M^256 times the previous row's, so a second step reaches two rows back.
@@ -184,10 +156,6 @@ struct PrefilterScan {
     float c_rowmf[4][16][4];
     int32_t c_row_ok;              // the row form reproduces the direct form (self-check of the algebra in double)
 };
-// 1: mfcc1024_wave_kernel<PRE> runs the row form (plans need c_row_ok); 0: the wave-wide Kogge-Stone scan (A/B builds)
-#ifndef DSP_PRE_ROWSCAN
-#define DSP_PRE_ROWSCAN 1
-#endif
 // steps inside a row and cross-row steps of the row form for a section whose lane scan needs `steps` Kogge-Stone steps
 constexpr int scan_row_steps(int steps) { return steps < 4 ? steps : 4; }
 constexpr int scan_row_rounds(int steps) { return steps <= 4 ? 1 : steps - 3; }      // 5 -> 2 (32 chunks back), 6 -> 3 (the whole wave)

@@ -82,8 +82,8 @@ class MfccPlan:
             pass
 
     def set_kernel(self, kernel: int):
-        """0 = one wavefront per frame (default), 1 = one 16-lane row per frame (4 frames per wavefront), 2 = wave per frame with the
-        per-frame epilogue, 3 = two frames per wavefront step (reference shape, independent full frames; an experiment)."""
+        """0 = one wavefront per frame (default), 1 = the general Stockham kernel (1024-point plans only), 2 = wave per frame with the
+        per-frame epilogue.  3, and 1 on other plans, named 512-point kernels that were removed: DspError."""
         _lib.check(self._L.dsp_mfcc_plan_set_kernel(self._h, int(kernel)), "dsp_mfcc_plan_set_kernel")
 
     def set_launch(self, blocks_per_cu: int = 0, frames_per_chunk: int = 0):

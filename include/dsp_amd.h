@@ -183,11 +183,12 @@ int dsp_mfcc_clips_host(dsp_mfcc_plan *plan, const float *signal, long n_clips,
 /* Launch geometry knobs for tuning / profiling (0 = library default). */
 int dsp_mfcc_plan_set_launch(dsp_mfcc_plan *plan, int blocks_per_cu, int frames_per_chunk);
 /* Kernel form: DSP_KERNEL_WAVE = one wavefront per frame, log + DCT once per 16-frame tile
- * (default); DSP_KERNEL_ROW = one 16-lane row per frame (4 frames per wavefront);
- * DSP_KERNEL_WAVE_FRAME = one wavefront per frame with the per-frame log + DCT epilogue (what
- * DSP_LOG_GLOBAL_REF1 plans always run); DSP_KERNEL_PAIR = two frames per wavefront step for independent
- * 512-sample frames of the reference shape (an experiment, slower than the default: DESIGN.md 3; other
- * shapes and clip mode run the default form).  Same results to rounding; DESIGN.md has the numbers. */
+ * (default); DSP_KERNEL_WAVE_FRAME = one wavefront per frame with the per-frame log + DCT epilogue (what
+ * DSP_LOG_GLOBAL_REF1 plans always run); DSP_KERNEL_ROW = on a 1024-point plan, the general Stockham kernel
+ * instead of the register-resident wave kernel.  Same results to rounding; DESIGN.md has the numbers.
+ * The 512-point forms that DSP_KERNEL_ROW (one 16-lane row per frame) and DSP_KERNEL_PAIR (two frames per
+ * wavefront step) named were measured slower than the default and removed: the ids keep their values,
+ * DSP_KERNEL_PAIR on any plan and DSP_KERNEL_ROW on a plan whose n_fft is not 1024 return DSP_EINVAL. */
 enum { DSP_KERNEL_WAVE = 0, DSP_KERNEL_ROW = 1, DSP_KERNEL_WAVE_FRAME = 2, DSP_KERNEL_PAIR = 3 };
 int dsp_mfcc_plan_set_kernel(dsp_mfcc_plan *plan, int kernel);
 

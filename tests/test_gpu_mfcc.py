@@ -208,14 +208,12 @@ def test_config4_clips_at_scale(dsp, torch_cuda):
         gate(out[i].cpu().numpy(), ref, f"config4 12500 clips, clip {i}")
 
 
-def test_experiment_kernels_are_not_in_the_default_library(dsp, torch_cuda):
+def test_removed_512_point_kernels_are_refused(dsp, torch_cuda):
     """The row-per-frame and two-frames-per-wave forms of the 512-point kernel are measured dead ends (profiles/r02_wave_priority_ab.txt):
-    the product library does not carry them and says so; DSP_KERNEL_ROW stays valid on 1024-point plans (the Stockham fallback)."""
-    if b"+experiments" in dsp.load().dsp_version():
-        pytest.skip("library built with DSP_AMD_EXPERIMENTS=1")
+    the library no longer has them and says so; DSP_KERNEL_ROW stays valid on 1024-point plans (the Stockham fallback)."""
     plan = dsp.MfccPlan()
     for kern in (1, 3):
-        with pytest.raises(dsp.DspError, match="DSP_AMD_EXPERIMENTS"):
+        with pytest.raises(dsp.DspError, match="row and pair kernels were removed"):
             plan.set_kernel(kern)
     plan.set_kernel(2)
     dsp.MfccPlan(dsp.default_config(n_fft=1024, frame_length=1024, hop_length=1024, n_mels=128)).set_kernel(1)
