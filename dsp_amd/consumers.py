@@ -7,6 +7,7 @@
   Scanner        both per sliding window of long recordings     sync/sync.cpp:188-213 (one 1 s buffer at a time)
   StreamSession  the same for audio that is still arriving       sync/sync.cpp:188-213 (the capture loop itself, many feeds)
   Cmvn           sliding_cmvn                                   2fa/audio/speaker/gmm_utils.py:14-25
+  SpeakerFrontEnd   extract_features_from_array, a batch at once  2fa/audio/speaker/gmm_utils.py:47-61
   SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
   SpeakerVerifier   score_models / evaluate_dir (float GMMs)      2fa/audio/speaker/gmm_utils.py:99-126, evaluate_gmm.py
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
@@ -22,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .mfcc import MfccPlan, default_config, ragged_frame_offsets
+from .mfcc import MfccPlan, default_config, ragged_frame_offsets, speaker_config
 
 
 def _stream(t):
@@ -469,6 +470,51 @@ class Cmvn:
             _lib.check(self._L.dsp_cmvn_ragged_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_LP), out.data_ptr(), _stream(mfcc)),
                        "dsp_cmvn_ragged_device")
         return out
+
+
+class SpeakerFrontEnd:
+    """extract_features_from_array (gmm_utils.py:47-61) for a whole batch: librosa.feature.mfcc(n_mfcc 13, n_fft 400, hop 160) as
+    speaker_config() states it, then sliding_cmvn over a window of 300 rows -- the rows the float GMMs are trained and scored on."""
+
+    CMVN_WINDOW = 300      # gmm_utils.py:14
+
+    def __init__(self, device: int = 0):
+        self.device = int(device)
+        self.plan = MfccPlan(speaker_config(), self.device)
+        self.cmvn = Cmvn(self.plan.cfg.n_mfcc, self.CMVN_WINDOW, self.device)
+
+    def close(self):
+        for part in ("cmvn", "plan"):
+            if getattr(self, part, None):
+                getattr(self, part).close()
+                setattr(self, part, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def features(self, signal, offsets):
+        """signal: cuda float32 [total] at 16 kHz, clip c = samples [offsets[c], offsets[c + 1]) -> (feats, frame_offsets): cuda float32
+        [F][13] with clip c's rows in [frame_offsets[c], frame_offsets[c + 1]) (numpy int64), 1 + n // 160 of them for n samples.  As it
+        is, the input of UbmTrainer.fit, SpeakerEnroller.enroll and SpeakerVerifier.verify."""
+        off = np.asarray(offsets, np.int64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("offsets must be a 1-d array of n_clips + 1 sample positions")
+        n_fft = self.plan.cfg.n_fft
+        short = np.flatnonzero(np.diff(off) < n_fft)
+        if short.size:      # gmm_utils.py:49-50 returns no rows for such a clip
+            c = int(short[0])
+            raise ValueError(f"clip {c} has {int(off[c + 1] - off[c])} samples: extract_features_from_array yields no rows below n_fft = {n_fft}")
+        mfcc, fo = self.plan.clips_ragged(signal, off, 2**31 - 1)
+        return self.cmvn.apply(mfcc, fo), fo
 
 
 def _gmm_float_params(params: dict, name: str):

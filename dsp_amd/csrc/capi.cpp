@@ -47,6 +47,22 @@ using dsp::MfccJob;
 using dsp::RaggedBatch;
 using dsp::valid_cfg;
 
+// n_fft 400 (mfcc400_kernel.hip): librosa.feature.mfcc(n_fft = 400) of gmm_utils.py:52-58 and its neighbours; every refusal names the field
+static bool valid_cfg_400(const dsp_mfcc_config &c, std::string &why)
+{
+    if (c.frame_length != 400) { why = "frame_length must be 400 for n_fft = 400"; return false; }
+    if (c.win_length != 0) { why = "win_length must be 0 for n_fft = 400"; return false; }
+    if (c.n_mels > dsp::k400MaxMels) { why = "n_mels must be in [1, 128] for n_fft = 400"; return false; }
+    if (c.n_mfcc > std::min(c.n_mels, dsp::k400MaxMfcc)) { why = "n_mfcc must be in [1, min(n_mels, 32)] for n_fft = 400"; return false; }
+    if (c.mel_norm == DSP_MELNORM_AUBIO_SLANEY) { why = "mel_norm: DSP_MELNORM_AUBIO_SLANEY is implemented for n_fft = 2048"; return false; }
+    if (c.log_mode == DSP_LOG_LOG10_FLOOR) { why = "log_mode: DSP_LOG_LOG10_FLOOR is implemented for n_fft = 2048"; return false; }
+    if (c.spectrum != DSP_SPECTRUM_POWER) { why = "spectrum: DSP_SPECTRUM_MAGNITUDE is implemented for n_fft = 2048"; return false; }
+    if (c.framing == DSP_FRAMING_STREAM) { why = "framing: DSP_FRAMING_STREAM is implemented for n_fft = 2048"; return false; }
+    if (c.prefilter != DSP_PREFILTER_NONE) { why = "prefilter: the per-frame prefilter is implemented for n_fft = 512 and 1024"; return false; }
+    if (c.fmax > 0.5f * (float)c.sample_rate) { why = "fmax must not exceed sample_rate / 2 for n_fft = 400"; return false; }
+    return true;
+}
+
 bool dsp::valid_cfg(const dsp_mfcc_config &c, std::string &why)
 {
     if (c.sample_rate <= 0) { why = "sample_rate must be positive"; return false; }
@@ -60,7 +76,9 @@ bool dsp::valid_cfg(const dsp_mfcc_config &c, std::string &why)
     if (c.log_mode != DSP_LOG_PER_FRAME_MAX && c.log_mode != DSP_LOG_GLOBAL_REF1 && c.log_mode != DSP_LOG_LOG10_FLOOR) { why = "unknown log_mode"; return false; }
     if (c.mel_norm != DSP_MELNORM_NONE && c.mel_norm != DSP_MELNORM_SLANEY && c.mel_norm != DSP_MELNORM_LIBROSA && c.mel_norm != DSP_MELNORM_AUBIO_SLANEY) { why = "unknown mel_norm"; return false; }
     if (c.spectrum != DSP_SPECTRUM_POWER && c.spectrum != DSP_SPECTRUM_MAGNITUDE) { why = "unknown spectrum"; return false; }
-    if (c.framing != DSP_FRAMING_COMPLETE && c.framing != DSP_FRAMING_STREAM) { why = "unknown framing"; return false; }
+    if (c.framing != DSP_FRAMING_COMPLETE && c.framing != DSP_FRAMING_STREAM && c.framing != DSP_FRAMING_CENTER) { why = "unknown framing"; return false; }
+    if (c.framing == DSP_FRAMING_CENTER && c.n_fft != 400) { why = "framing: DSP_FRAMING_CENTER is implemented for n_fft = 400"; return false; }
+    if (c.n_fft == 400) return valid_cfg_400(c, why);
     // the aubio-semantics options of cepstrum/scrubjay_infer.c's front end live on the 2048-point kernel
     if (c.n_fft != 2048 && (c.mel_norm == DSP_MELNORM_AUBIO_SLANEY || c.log_mode == DSP_LOG_LOG10_FLOOR || c.spectrum != DSP_SPECTRUM_POWER ||
                             c.framing != DSP_FRAMING_COMPLETE)) {
@@ -75,7 +93,7 @@ bool dsp::valid_cfg(const dsp_mfcc_config &c, std::string &why)
     if (c.win_length < 0 || c.win_length > c.frame_length) { why = "win_length must be in [0, frame_length]"; return false; }
     if (c.prefilter != DSP_PREFILTER_NONE && c.prefilter != DSP_PREFILTER_BUTTER_1000_3000 &&
         c.prefilter != DSP_PREFILTER_BUTTER_3000_7500) { why = "unknown prefilter"; return false; }
-    if (c.n_fft != 512 && c.n_fft != 1024 && c.n_fft != 2048) { why = "n_fft must be 512, 1024 or 2048"; return false; }
+    if (c.n_fft != 512 && c.n_fft != 1024 && c.n_fft != 2048) { why = "n_fft must be 400, 512, 1024 or 2048"; return false; }
     return true;
 }
 
@@ -145,9 +163,38 @@ void dsp_mfcc_scrubjay_infer_config(dsp_mfcc_config *c, int sample_rate)
     c->fmax = 0.5f * (float)sample_rate;         // not used by the aubio bank
 }
 
+void dsp_mfcc_speaker_config(dsp_mfcc_config *c)
+{
+    // 2fa/audio/speaker/gmm_utils.py:8-11 (SAMPLE_RATE 16000, N_MFCC 13, N_FFT 400, HOP_LENGTH 160), :52-58 (librosa.feature.mfcc
+    // with librosa's defaults for everything else: center = True, 128 Slaney mel filters, power_to_db(ref = 1, top_db = 80))
+    dsp_mfcc_default_config(c);
+    c->sample_rate = 16000;
+    c->n_fft = 400;
+    c->frame_length = 400;
+    c->hop_length = 160;
+    c->n_mels = 128;
+    c->n_mfcc = 13;
+    c->window = DSP_WINDOW_HANN;
+    c->mel_norm = DSP_MELNORM_LIBROSA;
+    c->log_mode = DSP_LOG_GLOBAL_REF1;
+    c->spectrum = DSP_SPECTRUM_POWER;
+    c->framing = DSP_FRAMING_CENTER;
+    c->win_length = 0;
+    c->prefilter = DSP_PREFILTER_NONE;
+    c->fmin = 0.0f;
+    c->fmax = 8000.0f;
+    c->amin = 1e-10f;
+    c->top_db = 80.0f;
+}
+
 int dsp_mfcc_frames_for(const dsp_mfcc_config *cfg, int num_samples, int max_frames)
 {
     if (!cfg || max_frames <= 0) return 0;
+    if (cfg->framing == DSP_FRAMING_CENTER) {
+        // librosa.util.frame over the clip padded by n_fft / 2 zeros at both ends: 1 + n / hop frames
+        if (num_samples <= 0 || cfg->hop_length <= 0) return 0;
+        return (int)std::min<long>(1L + num_samples / cfg->hop_length, max_frames);
+    }
     if (cfg->framing == DSP_FRAMING_STREAM) {
         // cepstrum/scrubjay_infer.c:39-53: a frame per aubio_source_do that returned samples
         if (num_samples <= 0) return 0;
@@ -198,6 +245,7 @@ int dsp_prefilter_scan_check(int prefilter, int *steps4)
 int dsp_mfcc_lane_tables(const dsp_mfcc_config *cfg, void *out, int size)
 {
     if (!cfg) return capi_fail(DSP_EINVAL, "cfg is NULL");
+    if (cfg->n_fft == 400) return capi_fail(DSP_EINVAL, "dsp_mfcc_lane_tables holds the 512-point kernel's tables: n_fft 400 has dsp_mfcc400_tables");
     if (!out) return (int)sizeof(dsp::LaneTables512);
     if (size != (int)sizeof(dsp::LaneTables512)) return capi_fail(DSP_EINVAL, "size != sizeof(LaneTables512)");
     std::string why;
@@ -206,6 +254,18 @@ int dsp_mfcc_lane_tables(const dsp_mfcc_config *cfg, void *out, int size)
     if (ok) std::memcpy(out, t, sizeof(*t));
     delete t;
     return ok ? DSP_OK : capi_fail(DSP_EINVAL, why);
+}
+
+int dsp_mfcc400_tables(const dsp_mfcc_config *cfg, void *out, int size)
+{
+    if (!cfg) return capi_fail(DSP_EINVAL, "cfg is NULL");
+    if (!out) return (int)sizeof(dsp::Tables400);
+    if (size != (int)sizeof(dsp::Tables400)) return capi_fail(DSP_EINVAL, "size != sizeof(Tables400)");
+    std::string why;
+    auto t = std::make_unique<dsp::Tables400>();
+    if (!valid_cfg(*cfg, why) || !dsp::build_tables_400(*cfg, *t, why)) return capi_fail(DSP_EINVAL, why);
+    std::memcpy(out, t.get(), sizeof(*t));
+    return DSP_OK;
 }
 
 int dsp_butter_bandpass(double lowcut, double highcut, double *b, double *a)
@@ -234,13 +294,18 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     host_side->cfg = *cfg;
     std::unique_ptr<dsp::GenTables1024> gen;
     std::unique_ptr<dsp::GenTables2048> g2k;
-    if (cfg->n_fft == 2048) {
+    std::unique_ptr<dsp::Tables400> t400;
+    if (cfg->n_fft == 400) {
+        t400 = std::make_unique<dsp::Tables400>();
+        if (!dsp::build_tables_400(*cfg, *t400, why)) return capi_fail(DSP_EINVAL, why);
+    } else if (cfg->n_fft == 2048) {
         g2k = std::make_unique<dsp::GenTables2048>();
         if (!dsp::build_gen_tables_2048(*cfg, *g2k, why)) return capi_fail(DSP_EINVAL, why);
     } else if (cfg->n_fft == 1024) {
         gen = std::make_unique<dsp::GenTables1024>();
         if (!dsp::build_gen_tables_1024(*cfg, *gen, why)) return capi_fail(DSP_EINVAL, why);
-    } else if (!dsp::build_lane_tables_512(*cfg, host_side->host, why)) return capi_fail(DSP_EINVAL, why);
+    } else if (cfg->n_fft != 512) return capi_fail(DSP_EINVAL, "internal: no tables for this n_fft");
+    else if (!dsp::build_lane_tables_512(*cfg, host_side->host, why)) return capi_fail(DSP_EINVAL, why);
     if (const int rc = dsp::check_device(device)) return rc;
     dsp::DeviceScope dsp_device_scope_(device);      // the caller's current device is put back on return
     // the plan gets device buffers from here on: its owner is declared after the scope, so that every exit below lets them go
@@ -253,6 +318,7 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     if (e == hipSuccess) e = dsp::upload(p->d_tables, p->host);
     if (e == hipSuccess && gen) e = dsp::upload(p->d_gen_tables, *gen);
     if (e == hipSuccess && g2k) e = dsp::upload(p->d_tables2048, *g2k);
+    if (e == hipSuccess && t400) e = dsp::upload(p->d_tables400, *t400);
     if (gen) p->gen_slots = gen->n_chunk_slots;
     if (e == hipSuccess && cfg->n_fft == 1024 && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->gen_slots <= 3) {
         // BASELINE config 3 in ONE pass: the per-frame Butterworth as a scan inside the MFCC kernel (tables.hpp PrefilterScan)
@@ -269,7 +335,9 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
     p->n_cu = prop.multiProcessorCount;
     p->aub = cfg->n_fft == 2048 && (cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM);
-    if (cfg->n_fft == 2048) {
+    if (cfg->n_fft == 400) {
+        p->resident_blocks_400 = dsp::mfcc400_blocks_per_cu(cfg->n_mels);
+    } else if (cfg->n_fft == 2048) {
         p->resident_blocks_2048 = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, false, p->aub);
         p->resident_blocks_2048_pool = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, true, p->aub);
     } else if (cfg->n_fft == 512) {
@@ -277,7 +345,7 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
                                                               cfg->frame_length == 512, false);
         p->resident_blocks = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
                                                         cfg->frame_length == 512, true);
-    } else {
+    } else if (cfg->n_fft == 1024) {
         p->resident_blocks_gen = dsp::mfcc1024_blocks_per_cu(cfg->frame_length == 1024);
         p->resident_blocks_gen_wave = dsp::mfcc1024_wave_blocks_per_cu(cfg->frame_length == 1024);
         if (p->d_scan) p->resident_blocks_gen_pre = dsp::mfcc1024_wave_blocks_per_cu(true, true);
@@ -313,6 +381,7 @@ int dsp_mfcc_plan_set_kernel(dsp_mfcc_plan *p, int kernel)
     // DSP_KERNEL_ROW on a 1024-point plan selects the general Stockham kernel (a product path: the fallback for filterbanks
     // the wave kernel's tables do not hold); the 512-point row / pair kernels were measured dead ends (0.537 ms and 0.44-0.45 ms
     // against 0.41 ms for the default kernel, profiles/r02_wave_priority_ab.txt) and have been removed
+    if (kernel != DSP_KERNEL_WAVE) if (const int rc = dsp::refuse_400(p, "dsp_mfcc_plan_set_kernel with anything but DSP_KERNEL_WAVE")) return rc;
     if (kernel == DSP_KERNEL_PAIR || (kernel == DSP_KERNEL_ROW && p->cfg.n_fft != 1024))
         return capi_fail(DSP_EINVAL, "DSP_KERNEL_ROW / DSP_KERNEL_PAIR: the 512-point row and pair kernels were removed (measured slower than the default kernel)");
     p->kernel = kernel;
@@ -369,6 +438,7 @@ template <class Launch> static int two_pass_floor(dsp_mfcc_plan *p, dsp::Mfcc512
 
 int dsp::pcm16_check(const dsp_mfcc_plan *p, int in_kind, bool clip_mode)
 {
+    if (in_kind != 0) if (const int rc = dsp::refuse_400(p, "PCM16 ingestion")) return rc;
     if (in_kind != 0 && !(p->aub && clip_mode) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
         return capi_fail(DSP_EINVAL, "PCM16 ingestion runs on the 512-point wave-per-frame kernel (per-frame log mode) and on the 2048-point scrubjay_infer.c front end");
     return DSP_OK;
@@ -392,14 +462,19 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
     a.clip_stride = job.clip_stride;
     a.frames_per_clip = frames_per_clip;
     a.samples_per_clip = job.samples_per_clip;
-    const bool fft2048 = p->cfg.n_fft == 2048, gen = p->cfg.n_fft == 1024;
+    const bool fft2048 = p->cfg.n_fft == 2048, gen = p->cfg.n_fft == 1024, fft400 = p->cfg.n_fft == 400;
+    if (!fft2048 && !gen && !fft400 && p->cfg.n_fft != 512) return capi_fail(DSP_EINVAL, "internal: no kernel for this n_fft");
     // 16-frame tile epilogue: per-frame log mode on the wave-per-frame kernel
-    const bool tile = !gen && p->kernel == DSP_KERNEL_WAVE && p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX;
+    const bool tile = !gen && !fft400 && p->kernel == DSP_KERNEL_WAVE && p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX;
     // 1024-point: the register-resident wave kernel when the filterbank fits two chunk slots per lane (DSP_KERNEL_ROW selects
     // the general Stockham kernel for A/B)
     const bool gen_wave = gen && p->gen_slots <= 3 && p->kernel != DSP_KERNEL_ROW;
     int per_cu;
-    if (fft2048) {
+    if (fft400) {
+        if (a.center_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: centred framing without the clip length");
+        a.chunk = p->chunk > 0 ? p->chunk : 8;
+        per_cu = p->resident_blocks_400;
+    } else if (fft2048) {
         if (a.stream_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: stream framing without the clip length");
         a.chunk = p->chunk > 0 ? p->chunk : 8;
         per_cu = p->resident_blocks_2048;
@@ -420,6 +495,7 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
     const int blocks = dsp::grid(p, per_cu, (n_frames + a.chunk - 1) / a.chunk);
     if (job.fused_prefilter && !(gen_wave && p->d_scan)) return capi_fail(DSP_EINVAL, "internal: fused prefilter without its tables");
     auto launch = [&](const dsp::Mfcc512Args &x) {
+        if (fft400) return dsp::launch_mfcc400(x, p->d_tables400, blocks, st);
         if (fft2048) return dsp::launch_mfcc2048(x, p->d_tables2048, blocks, st, false);
         if (x.log_mode == DSP_LOG_GLOBAL_REF1)      // the wave-per-frame kernel's per-frame epilogue
             return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, false);
@@ -473,7 +549,8 @@ static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets
 int dsp::ragged_plan_check(const dsp_mfcc_plan *p)
 {
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return capi_fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
-    if (p->cfg.n_fft == 1024) return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the 512- and 2048-point kernels: n_fft 1024 is not supported");
+    if (p->cfg.n_fft != 400 && p->cfg.n_fft != 512 && p->cfg.n_fft != 2048)
+        return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the 400-, 512- and 2048-point kernels: n_fft 1024 is not supported");
     return DSP_OK;
 }
 

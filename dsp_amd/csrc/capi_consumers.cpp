@@ -151,6 +151,7 @@ static int stop_fused(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *
                       const long *offsets, float *d_prob, void *stream)
 {
     if (offsets) { t = 1; clip_stride = 0; }
+    if (const int rc = dsp::refuse_400(p, "classify_signal (the fused clip -> probability kernel and its two-kernel form)")) return rc;
     // the reference's shape on the default kernel: 512-point, per-frame log, 13 coefficients of 40 mel energies, complete frames
     if (p->cfg.n_fft != 512 || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX || p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE ||
         p->host.dct_split != 4 || p->host.dct_len != 10 || m.n_coef != p->cfg.n_mfcc || m.units[0] > dsp::kStopFusedUnits || !m.fold_a || t <= 0 ||
@@ -460,6 +461,7 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
 int dsp::scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg)
 {
     const dsp_mfcc_config &pcfg = plan->cfg;
+    if (const int rc = dsp::refuse_400(plan, "a scanner or stream session")) return rc;
     if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
         return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
                                      "no prefilter");

@@ -169,6 +169,7 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
 {
     if (in_kind < 0) return in_kind;
     if (!p || !s || n_clips < 0) return capi_fail(DSP_EINVAL, "bad argument");
+    if (const int rc = dsp::refuse_400(p, "the fused clip -> label path")) return rc;
     if ((p->cfg.n_fft != 512 && p->cfg.n_fft != 2048) || (p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX && p->cfg.log_mode != DSP_LOG_LOG10_FLOOR) ||
         p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE)
         return capi_fail(DSP_EINVAL, "the fused clip -> label path runs on the 512- and 2048-point wave-per-frame kernels, per-frame log modes");
@@ -289,6 +290,7 @@ static int svm_scan(dsp_svm *s, const float *d_mfcc, long n, const long *frame_o
 static int scan_front_end(const dsp_mfcc_plan *p, const dsp_svm *s)
 {
     const dsp_mfcc_config &c = p->cfg;
+    if (const int rc = dsp::refuse_400(p, "a scrub-jay scan")) return rc;
     if (c.log_mode == DSP_LOG_GLOBAL_REF1) return capi_fail(DSP_EINVAL, "DSP_LOG_GLOBAL_REF1 plans cannot be scanned: the top_db floor spans the window");
     if (c.prefilter != DSP_PREFILTER_NONE || c.n_fft == 1024)
         return capi_fail(DSP_EINVAL, "scans run on the ragged MFCC matrix: prefilter plans and n_fft 1024 are not supported");
@@ -355,6 +357,7 @@ long dsp_scan_window_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config *c
     if (!mfcc) return capi_fail(DSP_EINVAL, "mfcc config is NULL");
     std::string why;
     if (!dsp::valid_cfg(*mfcc, why)) return capi_fail(DSP_EINVAL, why);
+    if (mfcc->framing == DSP_FRAMING_CENTER) return capi_fail(DSP_EINVAL, "framing: windows are not cut under DSP_FRAMING_CENTER (n_fft 400 plans are not scanned)");
     if (const int rc = dsp::scan_args(cfg, n_recordings)) return rc;
     if (n_recordings == 0) return 0;
     if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");

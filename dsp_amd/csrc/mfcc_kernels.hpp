@@ -54,6 +54,9 @@ struct Mfcc512Args {
     // stream_framing: frame t of a clip covers samples [(t + 1) hop - frame_len, (t + 1) hop), zeros outside [0, samples_per_clip)
     int spectrum = 0;
     int stream_framing = 0;
+    // n_fft 400 only (DSP_FRAMING_CENTER, clips): frame t covers samples [t hop - frame_len / 2, t hop + frame_len / 2), zeros outside
+    // [0, samples_per_clip)
+    int center_framing = 0;
     int samples_per_clip = 0;
     float *frame_max;
     const float *clip_floor;
@@ -99,5 +102,9 @@ struct GenTables2048;
 hipError_t launch_mfcc2048(const Mfcc512Args &args, const GenTables2048 *tables, int blocks, hipStream_t stream, bool pool);
 int mfcc2048_blocks_per_cu(int n_mels, bool pool, bool aub = false);      // aub: the aubio-semantics kernels (spectrum / log10 / stream framing) and their LDS
 int mfcc512_blocks_per_cu(int dct_split, int dct_len, int gather, bool full, bool tile);
+// n_fft = 400 (mfcc400_kernel.hip): float frames, clips (complete or centred framing) and ragged batches, both log modes
+struct Tables400;
+hipError_t launch_mfcc400(const Mfcc512Args &args, const Tables400 *tables, int blocks, hipStream_t stream);
+int mfcc400_blocks_per_cu(int n_mels);
 
 }  // namespace dsp

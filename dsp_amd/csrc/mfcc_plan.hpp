@@ -26,6 +26,8 @@ struct dsp_mfcc_plan {
     dsp::DeviceBuf<dsp::GenTables1024> d_gen_tables;   // n_fft = 1024
     dsp::DeviceBuf<dsp::GenTables2048> d_tables2048;   // n_fft = 2048
     int resident_blocks_2048 = 2, resident_blocks_2048_pool = 2;
+    dsp::DeviceBuf<dsp::Tables400> d_tables400;        // n_fft = 400
+    int resident_blocks_400 = 4;
     int resident_blocks_gen = 3;
     int gen_slots = 0;                            // mel chunk slots per lane the 1024-point tables use (<= 3: wave kernel)
     int resident_blocks_gen_wave = 2;
@@ -95,6 +97,13 @@ int ragged_plan_check(const dsp_mfcc_plan *p);      // the plans mfcc_clips_ragg
 // int16 input on a plan whose kernel has no PCM16 load: DSP_EINVAL (clip_mode: clips or a ragged batch, not independent frames)
 int pcm16_check(const dsp_mfcc_plan *p, int in_kind, bool clip_mode);
 
+// n_fft 400 plans (dsp_mfcc_speaker_config) run float frames, clips and ragged batches on their own kernel and nothing else: `what` names
+// the entry that refuses one.  DSP_OK for every other plan
+inline int refuse_400(const dsp_mfcc_plan *p, const char *what)
+{
+    return p->cfg.n_fft != 400 ? DSP_OK : capi_fail(DSP_EINVAL, std::string(what) + " is not implemented for n_fft 400 plans (float frames, clips and ragged batches only)");
+}
+
 // the kernels' 8-byte frame loads (4-byte for mono int16); strided: clip starts clip_stride apart are read
 inline bool input_aligned(const void *d_in, int in_kind, bool strided, long clip_stride)
 {
@@ -112,7 +121,8 @@ inline Mfcc512Args plan_args(const dsp_mfcc_plan *p, const void *d_in, int in_ki
     const dsp_mfcc_config &c = p->cfg;
     return {.in = d_in, .in_kind = in_kind, .tables = p->d_tables, .hop = c.hop_length, .frame_len = c.frame_length, .n_mels = c.n_mels,
             .n_mfcc = c.n_mfcc, .amin = c.amin, .top_db = c.top_db, .log_mode = c.log_mode, .spectrum = c.spectrum,
-            .stream_framing = clip_mode && c.framing == DSP_FRAMING_STREAM};
+            .stream_framing = clip_mode && c.framing == DSP_FRAMING_STREAM,
+            .center_framing = clip_mode && c.framing == DSP_FRAMING_CENTER};
 }
 
 // persistent-style grid: exactly the 4-wave blocks the chip holds at once (per_cu per CU unless dsp_mfcc_plan_set_launch says otherwise;

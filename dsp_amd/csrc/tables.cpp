@@ -202,6 +202,61 @@ bool build_gen_tables_2048(const dsp_mfcc_config &cfg, GenTables2048 &t, std::st
     return true;
 }
 
+bool build_tables_400(const dsp_mfcc_config &cfg, Tables400 &t, std::string &why)
+{
+    std::memset(&t, 0, sizeof(t));
+    const int n_fft = k400Fft, n_bins = k400Bins;
+    if (cfg.n_fft != n_fft) { why = "n_fft must be 400 for this kernel"; return false; }
+    if (cfg.frame_length != n_fft) { why = "frame_length must be 400 for n_fft = 400"; return false; }
+    if (cfg.win_length != 0) { why = "win_length must be 0 for n_fft = 400"; return false; }
+    if (cfg.n_mels < 1 || cfg.n_mels > k400MaxMels) { why = "n_mels must be in [1, 128] for n_fft = 400"; return false; }
+    if (cfg.n_mfcc < 1 || cfg.n_mfcc > std::min(cfg.n_mels, k400MaxMfcc)) { why = "n_mfcc must be in [1, min(n_mels, 32)] for n_fft = 400"; return false; }
+    t.n_mels = cfg.n_mels;
+    t.n_mfcc = cfg.n_mfcc;
+    const std::vector<float> win = make_frame_window(cfg);
+    for (int l = 0; l < 40; ++l)
+        for (int a = 0; a < 5; ++a) {
+            const int n = l + 40 * a;
+            t.win[2 * a][l] = 0.5f * win[2 * n];
+            t.win[2 * a + 1][l] = 0.5f * win[2 * n + 1];
+        }
+    for (int l = 0; l < kLanes; ++l) {
+        for (int q = 1; q < 5; ++q) unit((double)((q * (l % 5)) % 25) / 25.0, t.tw1[2 * (q - 1)][l], t.tw1[2 * (q - 1) + 1][l]);
+        for (int q = 1; q < 8; ++q) unit((double)((q * l) % 200) / 200.0, t.tw2[2 * (q - 1)][l], t.tw2[2 * (q - 1) + 1][l]);
+        unit((double)l / 400.0, t.twu[0][l], t.twu[1][l]);
+        unit((double)(l + 64) / 400.0, t.twu[2][l], t.twu[3][l]);
+    }
+    const std::vector<float> fb = make_mel_filterbank(cfg.sample_rate, n_fft, cfg.n_mels, cfg.fmin, cfg.fmax, cfg.mel_norm);
+    int off = 0;
+    for (int m = 0; m < cfg.n_mels; ++m) {
+        const float *row = &fb[(size_t)m * n_bins];
+        int first = -1, last = -1;
+        for (int k = 0; k < n_bins; ++k)
+            if (row[k] != 0.0f) { if (first < 0) first = k; last = k; }
+        t.mel_off[m] = off;
+        if (first < 0) continue;               // an empty filter (HTK scale, 128 filters: four of them): lo = len = 0, its energy is 0
+        const int len = last - first + 1;
+        if (off + len > k400MaxWeights) { why = "mel filterbank has too many non-zero weights for the 400-point kernel"; return false; }
+        t.mel_lo[m] = first;
+        t.mel_len[m] = len;
+        for (int k = 0; k < len; ++k) t.mel_w[off + k] = row[first + k];       // ascending bins
+        off += len;
+    }
+    t.n_weights = off;
+    const std::vector<float> dct = make_dct_ortho(cfg.n_mfcc, cfg.n_mels);
+    for (int c = 0; c < cfg.n_mfcc; ++c)
+        for (int m = 0; m < cfg.n_mels; ++m) t.dct[c][m] = dct[(size_t)c * cfg.n_mels + m];
+    const int half = (cfg.n_mels + 1) / 2;
+    for (int l = 0; l < kLanes; ++l) {
+        const int c = l >> 1, h = l & 1;
+        for (int i = 0; i < half; ++i) {
+            const int m = h * half + i;
+            t.dct_t[i][l] = (c < cfg.n_mfcc && m < cfg.n_mels) ? t.dct[c][m] : 0.0f;
+        }
+    }
+    return true;
+}
+
 // ---- prefilter in parallel form -------------------------------------------------------------------------------------
 bool build_prefilter_scan(const double b[9], const double a[9], PrefilterScan &out, std::string &why)
 {

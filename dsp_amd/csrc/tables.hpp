@@ -111,6 +111,27 @@ struct GenTables2048 {
 };
 bool build_gen_tables_2048(const dsp_mfcc_config &cfg, GenTables2048 &t, std::string &why);
 
+// ---- n_fft = 400 (librosa.feature.mfcc(n_fft = 400, hop_length = 160) of 2fa/audio/speaker/gmm_utils.py:52-58; dsp_mfcc_speaker_config)
+// Tables of mfcc400_kernel.hip.  The 400 real samples are packed into 200 complex points z[n] = x[2n] + i x[2n+1] and transformed as
+// 200 = 5 x 5 x 8 (Stockham autosort: radix 5 on lanes j < 40 twice, radix 8 on lanes j < 25); every twiddle is a table entry computed
+// in double and rounded once, per lane, so the kernel keeps them in registers.  All (cos, sin) pairs are exp(-2 pi i x).
+constexpr int k400Fft = 400, k400Bins = 201, k400MaxMels = 128, k400MaxMfcc = 32;
+constexpr int k400MaxWeights = 416;        // a bin lies inside at most two triangles: <= 402 non-zero weights whatever the bank
+struct Tables400 {
+    float win[10][kLanes];                 // x0.5 window for samples 2(l + 40 t), 2(l + 40 t) + 1 at [2t], [2t+1], t < 5; lanes >= 40 hold 0
+    float tw1[8][kLanes];                  // pass 1 (radix 5, 5 points done): W25^(t (l % 5)), t = 1..4 at [2(t-1)], [2(t-1)+1]
+    float tw2[14][kLanes];                 // pass 2 (radix 8, 25 points done): W200^(t l), t = 1..7 at [2(t-1)], [2(t-1)+1]; lanes < 25
+    float twu[4][kLanes];                  // untangling the packed real transform: W400^l at [0], [1], W400^(l + 64) at [2], [3]
+    int32_t mel_lo[k400MaxMels], mel_len[k400MaxMels], mel_off[k400MaxMels];   // filter m: bins [lo, lo+len), weights at mel_w[off ..]; len 0 = an empty filter
+    float mel_w[k400MaxWeights];
+    float dct[k400MaxMfcc][k400MaxMels];   // DCT-II rows
+    // DCT rows as the kernel's lanes read them: lane 2 c + h dots log-mels [h half, h half + half), half = ceil(n_mels / 2),
+    // with dct_t[i][lane] = D[c][h half + i] (0 past the row / past n_mfcc)
+    float dct_t[(k400MaxMels + 1) / 2][kLanes];
+    int32_t n_mels, n_mfcc, n_weights;
+};
+bool build_tables_400(const dsp_mfcc_config &cfg, Tables400 &t, std::string &why);
+
 // ---- per-frame Butterworth prefilter as a wave-parallel scan (BASELINE config 3 inside the 1024-point kernel) ----------
 // The 8th-order filter H(z) = B(z^-1) / A(z^-1) (donut-classifier/classifier.c:342-401) in PARALLEL FORM: a direct term
 // plus four second-order sections, one per conjugate pole pair,

@@ -118,7 +118,7 @@ WINDOW_HANN, WINDOW_HAMMING, WINDOW_RECT = 0, 1, 2
 MELNORM_NONE, MELNORM_SLANEY, MELNORM_LIBROSA, MELNORM_AUBIO_SLANEY = 0, 1, 2, 3
 LOG_PER_FRAME_MAX, LOG_GLOBAL_REF1, LOG_LOG10_FLOOR = 0, 1, 2
 SPECTRUM_POWER, SPECTRUM_MAGNITUDE = 0, 1
-FRAMING_COMPLETE, FRAMING_STREAM = 0, 1
+FRAMING_COMPLETE, FRAMING_STREAM, FRAMING_CENTER = 0, 1, 2
 MAP_RELEVANCE, MAP_FIXED_ALPHA = 0, 1
 PREFILTER_NONE, PREFILTER_BUTTER_1000_3000, PREFILTER_BUTTER_3000_7500 = 0, 1, 2
 
@@ -131,7 +131,7 @@ SYMBOLS = [
     "dsp_butter_bandpass_filter_f32", "dsp_butter_bandpass_filter_f64", "dsp_compute_spectrogram_f32", "dsp_compute_spectrogram_f64",
     "dsp_classify_batch_host", "dsp_classify_batch_device", "dsp_classify_batch_pcm16_host", "dsp_classify_batch_pcm16_device", "dsp_classify_release", "dsp_classify_stats", "dsp_classify_ctx_create", "dsp_classify_ctx_destroy", "dsp_classify_batch_device_ctx", "dsp_debug_hold_classify_ctx", "dsp_find_midpoints", "dsp_classify_division_check",
     "dsp_mfcc_stats_device", "dsp_svm_create", "dsp_svm_destroy", "dsp_svm_predict_device",
-    "dsp_mfcc_default_config", "dsp_mfcc_scrubjay_infer_config", "dsp_mfcc_plan_create", "dsp_mfcc_plan_destroy", "dsp_mfcc_plan_config",
+    "dsp_mfcc_default_config", "dsp_mfcc_scrubjay_infer_config", "dsp_mfcc_speaker_config", "dsp_mfcc400_tables", "dsp_mfcc_plan_create", "dsp_mfcc_plan_destroy", "dsp_mfcc_plan_config",
     "dsp_mfcc_frames_for", "dsp_mfcc_frames_device", "dsp_mfcc_clips_device", "dsp_mfcc_frames_host",
     "dsp_mfcc_clips_host", "dsp_mfcc_clips_pcm16_device", "dsp_mfcc_plan_set_launch", "dsp_mfcc_plan_set_kernel", "dsp_butter_bandpass", "dsp_mfcc_tables", "dsp_mfcc_lane_tables", "dsp_prefilter_scan_check",
     "dsp_classify_batch_ragged_device_f64", "dsp_classify_batch_ragged_pcm16_device_f64", "dsp_classify_batch_ragged_host_f64", "dsp_classify_batch_ragged_pcm16_host_f64",
@@ -207,6 +207,8 @@ def load() -> C.CDLL:
     L.dsp_fft_real_forward_host.argtypes = [vp, C.c_long, ip, C.c_long, ip, vp]; L.dsp_fft_real_forward_host.restype = ip
     L.dsp_mfcc_default_config.argtypes = [cfgp]; L.dsp_mfcc_default_config.restype = None
     L.dsp_mfcc_scrubjay_infer_config.argtypes = [cfgp, ip]; L.dsp_mfcc_scrubjay_infer_config.restype = None
+    L.dsp_mfcc_speaker_config.argtypes = [cfgp]; L.dsp_mfcc_speaker_config.restype = None
+    L.dsp_mfcc400_tables.argtypes = [cfgp, vp, ip]; L.dsp_mfcc400_tables.restype = ip
     L.dsp_mfcc_plan_create.argtypes = [cfgp, ip, C.POINTER(vp)]; L.dsp_mfcc_plan_create.restype = ip
     L.dsp_mfcc_plan_destroy.argtypes = [vp]; L.dsp_mfcc_plan_destroy.restype = None
     L.dsp_mfcc_plan_config.argtypes = [vp, cfgp]; L.dsp_mfcc_plan_config.restype = ip

@@ -26,6 +26,18 @@ def default_config(**over) -> MfccConfig:
     return cfg
 
 
+def speaker_config(**over) -> MfccConfig:
+    """dsp_mfcc_speaker_config() -- librosa.feature.mfcc(sr 16000, n_mfcc 13, n_fft 400, hop_length 160) of
+    2fa/audio/speaker/gmm_utils.py:52-58 -- with keyword overrides."""
+    cfg = MfccConfig()
+    _lib.load().dsp_mfcc_speaker_config(C.byref(cfg))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(f"dsp_mfcc_config has no field {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
 def frames_for(cfg: MfccConfig, num_samples: int, max_frames: int) -> int:
     return _lib.load().dsp_mfcc_frames_for(C.byref(cfg), int(num_samples), int(max_frames))
 

@@ -10,7 +10,10 @@
  *
  *   gcc -O2 -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include examples/main_enroll.c -Ldsp_amd -ldsp_amd -Wl,-rpath,$PWD/dsp_amd \
  *       -L/opt/rocm/lib -lamdhip64 -lm -o main_enroll
- *   ./main_enroll [-a alpha | -r relevance] ubm.txt a.wav b.wav ...
+ *   ./main_enroll [-l] [-a alpha | -r relevance] ubm.txt a.wav b.wav ...
+ *
+ * -l: the rows the reference's float GMMs are trained on (dsp_mfcc_speaker_config: librosa.feature.mfcc with n_fft 400, 128 mel filters,
+ * centred frames; 2fa/audio/speaker/gmm_utils.py:52-58) instead of the firmware's 512-point front end (dsp_mfcc_default_config).
  *
  * Out of scope here as in the library: UBM training, variance or weight adaptation, CMVN for live streams.
  */
@@ -86,11 +89,12 @@ static double *read_ubm(const char *path, int *k, int *d)
 int main(int argc, char **argv)
 {
     dsp_enroll_config ecfg = {DSP_MAP_RELEVANCE, 16.0f, 0.7f};
-    int first = 1;
-    if (argc > 2 && !strcmp(argv[1], "-a")) { ecfg.map_mode = DSP_MAP_FIXED_ALPHA; ecfg.fixed_alpha = (float)atof(argv[2]); first = 3; }
-    else if (argc > 2 && !strcmp(argv[1], "-r")) { ecfg.relevance_factor = (float)atof(argv[2]); first = 3; }
+    int first = 1, librosa_rows = 0;
+    if (argc > 1 && !strcmp(argv[1], "-l")) { librosa_rows = 1; first = 2; }
+    if (argc > first + 1 && !strcmp(argv[first], "-a")) { ecfg.map_mode = DSP_MAP_FIXED_ALPHA; ecfg.fixed_alpha = (float)atof(argv[first + 1]); first += 2; }
+    else if (argc > first + 1 && !strcmp(argv[first], "-r")) { ecfg.relevance_factor = (float)atof(argv[first + 1]); first += 2; }
     const int n_files = argc - first - 1;
-    if (n_files <= 0) { fprintf(stderr, "usage: %s [-a alpha | -r relevance] ubm.txt file.wav ...\n", argv[0]); return 2; }
+    if (n_files <= 0) { fprintf(stderr, "usage: %s [-l] [-a alpha | -r relevance] ubm.txt file.wav ...\n", argv[0]); return 2; }
     int k = 0, d = 0;
     double *ubm = read_ubm(argv[first], &k, &d);
     if (!ubm) { fprintf(stderr, "%s: expected k d, k log constants, k * d means, k * d inverse covariances\n", argv[first]); return 1; }
@@ -110,7 +114,8 @@ int main(int argc, char **argv)
     }
 
     dsp_mfcc_config cfg;
-    dsp_mfcc_default_config(&cfg);
+    if (librosa_rows) dsp_mfcc_speaker_config(&cfg);
+    else dsp_mfcc_default_config(&cfg);
     if (cfg.n_mfcc != d) { fprintf(stderr, "the UBM has d = %d, the MFCC front end %d coefficients\n", d, cfg.n_mfcc); return 1; }
     dsp_resampler *rs = NULL;
     dsp_mfcc_plan *plan = NULL;

@@ -78,16 +78,19 @@ enum { DSP_LOG_PER_FRAME_MAX = 0,    /* mfcc.c:169-206: reference = the frame's 
 enum { DSP_SPECTRUM_POWER = 0,       /* mfcc.c:151-155: |X[k]|^2 into the filterbank                                             */
        DSP_SPECTRUM_MAGNITUDE = 1 }; /* aubio: the phase vocoder's norm |X[k]| (aubio_fft_get_norm), filterbank power 1; n_fft 2048 */
 enum { DSP_FRAMING_COMPLETE = 0,     /* mfcc.c:132-139: frames that lie completely inside the clip, T = 1 + (n - frame) / hop    */
-       DSP_FRAMING_STREAM = 1 };     /* aubio_source_do + aubio_pvoc_do as cepstrum/scrubjay_infer.c:39-53 drives them: one frame per
+       DSP_FRAMING_STREAM = 1,       /* aubio_source_do + aubio_pvoc_do as cepstrum/scrubjay_infer.c:39-53 drives them: one frame per
                                         hop of NEW samples, T = ceil(n / hop); frame t ends with hop t and starts frame_length - hop
                                         samples earlier (zeros before the clip), the last partial hop is zero padded; clips, n_fft 2048 */
+       DSP_FRAMING_CENTER = 2 };     /* librosa's center = True, pad_mode = "constant" (librosa >= 0.10): frame t is samples
+                                        [t hop - n_fft / 2, t hop + n_fft / 2) of the clip, zeros outside it, T = 1 + n / hop for n >= 1;
+                                        clips, n_fft 400.  librosa's older pad_mode = "reflect" is out of scope                       */
 enum { DSP_PREFILTER_NONE = 0, DSP_PREFILTER_BUTTER_1000_3000 = 1, DSP_PREFILTER_BUTTER_3000_7500 = 2 };
 
 /* Compile-time constants of the reference (mfcc_params.h:6-12, mfcc.c:172-173)
  * turned into a POD; dsp_mfcc_default_config() fills in the reference values. */
 typedef struct dsp_mfcc_config {
     int sample_rate;  /* 16000 */
-    int n_fft;        /* 512   (supported: 512, 1024, 2048; one wavefront per frame)  */
+    int n_fft;        /* 512   (supported: 400, 512, 1024, 2048; one wavefront per frame)  */
     int frame_length; /* 400   (<= n_fft) */
     int hop_length;   /* 160 */
     int n_mels;       /* 40 */
@@ -110,6 +113,17 @@ void dsp_mfcc_default_config(dsp_mfcc_config *cfg);
  * the 40-filter Slaney bank, log10, orthonormal DCT-II, 20 coefficients.  sample_rate: the file's own (aubio_source with
  * samplerate 0).  aubio is an unvendored dependency of the reference: restated from its published algorithm, parity unpinned. */
 void dsp_mfcc_scrubjay_infer_config(dsp_mfcc_config *cfg, int sample_rate);
+/* The rows the speaker GMMs are trained and scored on (2fa/audio/speaker/gmm_utils.py:8-11,52-58):
+ * librosa.feature.mfcc(y, sr = 16000, n_mfcc = 13, n_fft = 400, hop_length = 160) with librosa's defaults -- centred frames of 400
+ * samples with zero padding (DSP_FRAMING_CENTER), periodic Hann, a 400-point transform (201 bins), 128 unit-area filters on
+ * Slaney's mel scale over 0 - 8 kHz (DSP_MELNORM_LIBROSA), power_to_db(ref = 1, amin = 1e-10, top_db = 80) over the clip
+ * (DSP_LOG_GLOBAL_REF1), orthonormal DCT-II.  The sliding CMVN that follows is dsp_cmvn_*.  librosa is an unvendored dependency of
+ * the reference: restated from its published algorithm, parity unpinned.
+ * A 400-point plan (n_fft = frame_length = 400, win_length 0, n_mels <= 128, n_mfcc <= min(n_mels, 32), mel norm NONE / SLANEY /
+ * LIBROSA, log mode PER_FRAME_MAX / GLOBAL_REF1, power spectrum, framing COMPLETE / CENTER, no prefilter) runs float frames, clips
+ * and ragged batches and their host forms; PCM16 input, the fused clip kernels, scanners, stream sessions, dsp_mfcc_lane_tables and
+ * non-default kernels refuse it (DSP_EINVAL).                                                                                      */
+void dsp_mfcc_speaker_config(dsp_mfcc_config *cfg);
 
 typedef struct dsp_mfcc_plan dsp_mfcc_plan; /* opaque: device tables for one config on one GPU */
 
@@ -120,7 +134,8 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
 void dsp_mfcc_plan_destroy(dsp_mfcc_plan *plan);
 int dsp_mfcc_plan_config(const dsp_mfcc_plan *plan, dsp_mfcc_config *cfg);
 
-/* Number of frames compute_mfcc produces for an n-sample clip (mfcc.c:132-139). */
+/* Number of frames compute_mfcc produces for an n-sample clip (mfcc.c:132-139); under DSP_FRAMING_STREAM / _CENTER that framing's
+ * count (see the enum).  Host only.                                              */
 int dsp_mfcc_frames_for(const dsp_mfcc_config *cfg, int num_samples, int max_frames);
 
 /* --- device-resident entry points: pointers are HBM addresses on the plan's
@@ -164,7 +179,7 @@ int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long 
  * The matrices lie back to back, frame-major: clip c's frames are d_out[frame_offsets[c] .. frame_offsets[c + 1])[n_mfcc], each row
  * bit for bit what dsp_mfcc_clips_device (_pcm16_device) returns for that clip alone with the same plan and max_frames; under
  * DSP_LOG_GLOBAL_REF1 the top_db floor is taken over each clip's own frames.  Plans: n_fft 512 (wave-per-frame kernels, both log
- * modes) and n_fft 2048 (dsp_mfcc_scrubjay_infer_config and the variants dsp_mfcc_clips_device accepts); PCM16 where
+ * modes), n_fft 2048 (dsp_mfcc_scrubjay_infer_config and the variants dsp_mfcc_clips_device accepts) and n_fft 400; PCM16 where
  * dsp_mfcc_clips_pcm16_device takes it.  n_fft 1024 and prefilter plans: DSP_EINVAL.  Returns the frame count of the longest clip.
  *
  * dsp_mfcc_ragged_frame_offsets (host only, no GPU): frame_offsets[n_clips + 1] = prefix sums of
@@ -759,8 +774,8 @@ int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_fea
  * ties to even, each table saturated to its type; saturated[3] = the entries clamped in means, inv_covs, log_consts.  2048 / 1e-6 fits
  * int32; a reg_covar below about 9.6e-7 may not, which is what the count is for.
  * Not covered: k-means initialisation and n_init restarts, full or tied covariances, variance and weight adaptation at enrolment,
- * multi-GPU training (the statistics are summable, the tree is not defined across devices), the n_fft-400 librosa front end, CMVN
- * inside scanners or streams. */
+ * multi-GPU training (the statistics are summable, the tree is not defined across devices), CMVN inside scanners or streams.  (The
+ * rows the reference trains on come from dsp_mfcc_speaker_config.) */
 typedef struct dsp_ubm_init {
     const double *weights;       /* [k]    */
     const double *means;         /* [k][d] */
@@ -838,6 +853,8 @@ int dsp_mfcc_tables(const dsp_mfcc_config *cfg, float *window, float *mel, float
  * dsp_amd/csrc/tables.hpp, `size` must equal its sizeof; returns that size when
  * out is NULL).  Host-only introspection used by the CPU tests of the planner. */
 int dsp_mfcc_lane_tables(const dsp_mfcc_config *cfg, void *out, int size);
+/* the same for a 400-point configuration: dsp::Tables400 (csrc/tables.hpp), the tables mfcc400_kernel.hip reads; tools/emulate_400_fft.py */
+int dsp_mfcc400_tables(const dsp_mfcc_config *cfg, void *out, int size);
 
 /* classify()'s spectrogram divides every PSD cell by U = fs * sum(window^2) (classifier.cpp:350-365).  The recompute kernel takes a
  * three-instruction form of that division for cells in [2^-60, 2^60] -- but only after the classifier context has compared it with
