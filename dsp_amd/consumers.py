@@ -692,15 +692,76 @@ class UbmTrainer:
                    "dsp_ubm_init_rows_device")
         return out
 
-    def fit(self, feats, init: dict | None = None, max_iter: int = 300, tol: float = 1e-3, reg_covar: float = 1e-6) -> dict:
+    def kmeans_seed(self, feats, seed: int = 0) -> np.ndarray:
+        """Greedy k-means++ on feats (cuda float32 [n][d]), deterministic from the 64-bit seed (the draws are defined in include/dsp_amd.h)
+        -> int64 [k], the chosen rows in the order chosen.  DspError when feats holds fewer than k distinct rows."""
+        seed = self._seed(seed)
+        feats = self._rows(feats)
+        rows = np.empty(self.k, np.int64)
+        _lib.check(self._L.dsp_kmeans_seed_device(self._h, feats.data_ptr(), feats.shape[0], seed, rows.ctypes.data, _stream(feats)), "dsp_kmeans_seed_device")
+        return rows
+
+    @staticmethod
+    def _seed(seed):
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        return seed
+
+    @staticmethod
+    def _kmeans_numbers(max_iter, tol):
+        max_iter, tol = int(max_iter), float(tol)
+        if max_iter < 1:
+            raise ValueError("max_iter must be >= 1")
+        if not (0.0 <= tol < float("inf")):
+            raise ValueError("tol must be >= 0 and finite")
+        return max_iter, tol
+
+    def kmeans(self, feats, centres, max_iter: int = 300, tol: float = 1e-4, reg_covar: float = 1e-6, want_labels: bool = False) -> dict:
+        """Lloyd on feats (cuda float32 [n][d]) from centres [k][d] (sklearn's stop rules; an empty cluster keeps its centre) and the GMM of
+        the final labels -> dict: centres [k][d], counts [k], inertia, n_iter, stop ("max_iter" / "tol" / "strict"), n_empty, the GMM start
+        weights [k], means, variances [k][d] (fit's init as it is), and with want_labels the labels (cuda int32 [n])."""
+        import torch
+        max_iter, tol = self._kmeans_numbers(max_iter, tol)
+        reg_covar = self._reg_covar(reg_covar)
+        k, d = self.k, self.d
+        start = np.ascontiguousarray(centres, np.float64)
+        if start.shape != (k, d):
+            raise ValueError(f"centres must be [{k}][{d}]")
+        if not np.isfinite(start).all():
+            raise ValueError("centres must be finite")
+        feats = self._rows(feats)
+        out = {"centres": np.empty((k, d)), "counts": np.empty(k, np.int64), "weights": np.empty(k), "means": np.empty((k, d)), "variances": np.empty((k, d))}
+        labels = torch.empty(feats.shape[0], dtype=torch.int32, device=feats.device) if want_labels else None
+        res = _lib.KmeansResult(*[out[key].ctypes.data for key in ("centres", "counts", "weights", "means", "variances")],
+                                labels.data_ptr() if want_labels else None)
+        cfg = _lib.KmeansConfig(max_iter, tol, reg_covar)
+        _lib.check(self._L.dsp_kmeans_fit_device(self._h, feats.data_ptr(), feats.shape[0], start.ctypes.data, C.byref(cfg), C.byref(res), _stream(feats)),
+                   "dsp_kmeans_fit_device")
+        out.update(inertia=float(res.inertia), n_iter=int(res.n_iter), stop=_lib.KMEANS_STOP[res.stop], n_empty=int(res.n_empty))
+        if want_labels:
+            out["labels"] = labels
+        return out
+
+    def fit(self, feats, init: dict | str | None = None, max_iter: int = 300, tol: float = 1e-3, reg_covar: float = 1e-6, n_init: int = 1, seed: int = 0,
+            kmeans_max_iter: int = 300, kmeans_tol: float = 1e-4) -> dict:
         """EM on feats (cuda float32 [n][d], n >= k) from init (weights [k], means [k][d], variances [k][d]; None: init_rows) until the
         lower bound changes by less than tol or max_iter iterations -> dict of float64 arrays weights [k], means, variances, inv_covs [k][d],
-        log_consts [k], lower_bounds [n_iter], and n_iter, converged.  The dict is a SpeakerEnroller's ubm_float as it is."""
+        log_consts [k], lower_bounds [n_iter], and n_iter, converged.  The dict is a SpeakerEnroller's ubm_float as it is.
+        init="kmeans": sklearn's own start and restarts (dsp_kmeans_train_ubm_device) -- n_init times k-means++ seeding from `seed`, Lloyd
+        (kmeans_max_iter, kmeans_tol), the GMM of the labels, EM; the restart with the largest last lower bound is returned, and the dict
+        also carries "report": winner and per restart rows, kmeans_n_iter, kmeans_stop, kmeans_n_empty, em_n_iter, em_converged, lower_bound."""
         max_iter, tol = int(max_iter), float(tol)
         if max_iter < 1:
             raise ValueError("max_iter must be >= 1")
         if not tol >= 0.0:
             raise ValueError("tol must be >= 0")
+        if isinstance(init, str):
+            if init != "kmeans":
+                raise ValueError('init must be None, a dict or "kmeans"')
+            return self._fit_kmeans(feats, max_iter, tol, self._reg_covar(reg_covar), n_init, seed, kmeans_max_iter, kmeans_tol)
+        if int(n_init) != 1:
+            raise ValueError('n_init restarts need init="kmeans"')
         reg_covar = self._reg_covar(reg_covar)
         k, d = self.k, self.d
         start = None
@@ -716,16 +777,41 @@ class UbmTrainer:
                 raise ValueError("init: variances must be > 0")
             start = _lib.UbmInit(*[keep[key].ctypes.data for key in ("weights", "means", "variances")])
         feats = self._rows(feats)
-        out = {"weights": np.empty(k), "means": np.empty((k, d)), "variances": np.empty((k, d)), "log_consts": np.empty(k),
-               "inv_covs": np.empty((k, d)), "lower_bounds": np.full(max_iter, np.nan)}
-        res = _lib.UbmResult()
-        res.gmm.log_consts, res.gmm.means, res.gmm.inv_covs = (out[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
-        res.weights, res.variances, res.lower_bounds = (out[key].ctypes.data for key in ("weights", "variances", "lower_bounds"))
+        out, res = self._result_arrays(max_iter)
         cfg = _lib.UbmConfig(max_iter, tol, reg_covar)
         _lib.check(self._L.dsp_ubm_train_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(start) if start is not None else None,
                                                 C.byref(cfg), C.byref(res), _stream(feats)), "dsp_ubm_train_device")
         out["lower_bounds"] = out["lower_bounds"][:res.n_iter].copy()
         out["n_iter"], out["converged"] = int(res.n_iter), bool(res.converged)
+        return out
+
+    def _result_arrays(self, max_iter):
+        k, d = self.k, self.d
+        out = {"weights": np.empty(k), "means": np.empty((k, d)), "variances": np.empty((k, d)), "log_consts": np.empty(k),
+               "inv_covs": np.empty((k, d)), "lower_bounds": np.full(max_iter, np.nan)}
+        res = _lib.UbmResult()
+        res.gmm.log_consts, res.gmm.means, res.gmm.inv_covs = (out[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))
+        res.weights, res.variances, res.lower_bounds = (out[key].ctypes.data for key in ("weights", "variances", "lower_bounds"))
+        return out, res
+
+    def _fit_kmeans(self, feats, max_iter, tol, reg_covar, n_init, seed, kmeans_max_iter, kmeans_tol):
+        n_init, seed = int(n_init), self._seed(seed)
+        if n_init < 1:
+            raise ValueError("n_init must be >= 1")
+        kmeans_max_iter, kmeans_tol = self._kmeans_numbers(kmeans_max_iter, kmeans_tol)
+        feats = self._rows(feats)
+        out, res = self._result_arrays(max_iter)
+        restarts = (_lib.KmeansRestart * n_init)()
+        report = _lib.KmeansUbmReport(restarts, -1)
+        cfg = _lib.KmeansUbmConfig(n_init, seed, kmeans_max_iter, kmeans_tol, _lib.UbmConfig(max_iter, tol, reg_covar))
+        _lib.check(self._L.dsp_kmeans_train_ubm_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(cfg), C.byref(res), C.byref(report), _stream(feats)),
+                   "dsp_kmeans_train_ubm_device")
+        out["lower_bounds"] = out["lower_bounds"][:res.n_iter].copy()
+        out["n_iter"], out["converged"] = int(res.n_iter), bool(res.converged)
+        out["report"] = {"winner": int(report.winner),
+                         "restarts": [{"rows": np.array(r.rows[:self.k], np.int64), "kmeans_n_iter": int(r.kmeans_n_iter), "kmeans_stop": _lib.KMEANS_STOP[r.kmeans_stop],
+                                       "kmeans_n_empty": int(r.kmeans_n_empty), "em_n_iter": int(r.em_n_iter), "em_converged": bool(r.em_converged),
+                                       "lower_bound": float(r.lower_bound)} for r in restarts]}
         return out
 
 

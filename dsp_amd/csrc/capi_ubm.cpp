@@ -1,12 +1,14 @@
 // capi_ubm.cpp -- the C ABI of UBM training and of the GMM quantiser (include/dsp_amd.h dsp_ubm_*, dsp_gmm_quantize):
 // argument checks, the trainer's grow-only workspace, the initial model, the enqueueing of the EM iterations of ubm_kernels.hip and the
 // one synchronisation that reads the result back.  The E-step model is a GmmModel (gmm_model.hpp), as capi_enroll.cpp's UBM is.
+// Behind it the k-means start on the same trainer (dsp_kmeans_*): seeding, Lloyd and the restarts, kmeans_kernels.hip.
 #include <cmath>
 #include <cstdint>
 #include <limits>
 #include <memory>
 
 #include "capi_util.hpp"
+#include "kmeans_kernels.hpp"
 #include "ubm_kernels.hpp"
 
 using dsp::capi_fail;
@@ -17,6 +19,13 @@ struct dsp_ubm_trainer {
     dsp::DeviceBuf<double> state;        // grow-only: the float64 parameters, lower_bounds[max_iter] behind them
     dsp::DeviceBuf<float> model;         // the float32 E-step model
     dsp::DeviceBuf<dsp::UbmCtrl> ctrl;
+    // k-means (grow-only as well)
+    dsp::DeviceBuf<double> km_centres;   // the float64 centres [k][d], the final counts [k] behind them
+    dsp::DeviceBuf<int> km_labels;       // [n], where the caller asks for none
+    dsp::DeviceBuf<dsp::KmeansCtrl> km_ctrl;
+    dsp::DeviceBuf<float> km_m;          // seeding: [n] nearest squared distances
+    dsp::DeviceBuf<double> km_sums;      // seeding: the draws, then per trial the chunks', groups' and supers' sums
+    dsp::DeviceBuf<dsp::KmeansSeedCtrl> km_seed_ctrl;
 };
 
 namespace {
@@ -52,22 +61,25 @@ HostModel host_model(int k, int d, const double *w, const double *mu, const doub
     return m;
 }
 
-// EM from (w, mu, var) on the trainer's device (current): up to max_iter iterations, the parameters after the last one into `params`
-// (ubm_param_doubles), lower_bounds[0 .. n_iter) into `lower_bounds`.  k may be below the trainer's (the k = 1 pass of the row start).
-int run_em(dsp_ubm_trainer *t, int k, const float *d_feats, long n, const double *w, const double *mu, const double *var, int max_iter, double tol,
-           double reg_covar, double *params, double *lower_bounds, int *n_iter, int *converged, hipStream_t stream)
+int reserve_em(dsp_ubm_trainer *t, int k, long n, int max_iter, size_t stride)
+{
+    const size_t n_params = dsp::ubm_param_doubles(k, t->d);
+    if (t->partials.reserve((size_t)(dsp::ubm_groups(n) + dsp::ubm_supers(n)) * stride * sizeof(double)) != hipSuccess ||
+        t->state.reserve((n_params + (size_t)max_iter) * sizeof(double)) != hipSuccess ||
+        t->model.reserve(dsp::gmm_model_floats(t->k, t->d) * sizeof(float)) != hipSuccess || t->ctrl.reserve(sizeof(dsp::UbmCtrl)) != hipSuccess)
+        return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's workspace");
+    return DSP_OK;
+}
+
+// EM from the parameters and the float32 model that the trainer's workspace holds (reserve_em went before): up to max_iter iterations,
+// the parameters after the last one into `params` (ubm_param_doubles), lower_bounds[0 .. n_iter) into `lower_bounds`
+int run_em_from_device(dsp_ubm_trainer *t, int k, const float *d_feats, long n, int max_iter, double tol, double reg_covar, double *params, double *lower_bounds,
+                       int *n_iter, int *converged, hipStream_t stream)
 {
     const int d = t->d;
     const size_t stride = dsp::ubm_partial_doubles(k, d), n_params = dsp::ubm_param_doubles(k, d);
-    const long n_groups = dsp::ubm_groups(n), n_supers = dsp::ubm_supers(n);
-    if (t->partials.reserve((size_t)(n_groups + n_supers) * stride * sizeof(double)) != hipSuccess ||
-        t->state.reserve((n_params + (size_t)max_iter) * sizeof(double)) != hipSuccess ||
-        t->model.reserve(dsp::gmm_model_floats(t->k, d) * sizeof(float)) != hipSuccess || t->ctrl.reserve(sizeof(dsp::UbmCtrl)) != hipSuccess)
-        return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's workspace");
-    const HostModel m = host_model(k, d, w, mu, var);
+    const long n_groups = dsp::ubm_groups(n);
     const dsp::UbmCtrl start{0, 0, 0, 0, -std::numeric_limits<double>::infinity()};
-    DSP_CAPI_HIP(hipMemcpyAsync(t->state, m.params.data(), n_params * sizeof(double), hipMemcpyHostToDevice, stream));
-    DSP_CAPI_HIP(hipMemcpyAsync(t->model, m.model.data(), m.model.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     DSP_CAPI_HIP(hipMemcpyAsync(t->ctrl, &start, sizeof(start), hipMemcpyHostToDevice, stream));
     dsp::UbmFit fit{d_feats, n, t->state, dsp::GmmModelOut{t->model, k, d}, t->partials, t->partials.get() + (size_t)n_groups * stride, t->state.get() + n_params,
                     t->ctrl, tol, reg_covar};
@@ -86,6 +98,18 @@ int run_em(dsp_ubm_trainer *t, int k, const float *d_feats, long n, const double
     return DSP_OK;
 }
 
+// EM from (w, mu, var) on the trainer's device (current).  k may be below the trainer's (the k = 1 pass of the row start).
+int run_em(dsp_ubm_trainer *t, int k, const float *d_feats, long n, const double *w, const double *mu, const double *var, int max_iter, double tol,
+           double reg_covar, double *params, double *lower_bounds, int *n_iter, int *converged, hipStream_t stream)
+{
+    const int d = t->d;
+    if (const int rc = reserve_em(t, k, n, max_iter, dsp::ubm_partial_doubles(k, d))) return rc;
+    const HostModel m = host_model(k, d, w, mu, var);
+    DSP_CAPI_HIP(hipMemcpyAsync(t->state, m.params.data(), dsp::ubm_param_doubles(k, d) * sizeof(double), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(t->model, m.model.data(), m.model.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    return run_em_from_device(t, k, d_feats, n, max_iter, tol, reg_covar, params, lower_bounds, n_iter, converged, stream);
+}
+
 int check_rows(const dsp_ubm_trainer *t, const float *d_feats, long n)
 {
     if (!t) return capi_fail(DSP_EINVAL, "trainer is NULL");
@@ -101,11 +125,10 @@ int check_reg_covar(double reg_covar)
     return DSP_OK;
 }
 
-// the library's start: means = rows floor((i + 0.5) n / k), variances = the rows' global variance + reg_covar (one k = 1 iteration from
-// the k = 1 start: the middle row, variance 1), weights 1 / k
-int init_rows(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means, double *variances, hipStream_t stream)
+// the rows' global variance per dimension + reg_covar: one k = 1 iteration from the k = 1 start (the middle row, variance 1)
+int global_variance(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, std::vector<double> &variance, hipStream_t stream)
 {
-    const int k = t->k, d = t->d;
+    const int d = t->d;
     // centred on the middle row (the k = 1 start's own mean), not on 0: rows far from the origin would lose their variance to float32
     std::vector<float> middle((size_t)d);
     DSP_CAPI_HIP(hipMemcpyAsync(middle.data(), d_feats + (size_t)(n / 2) * d, (size_t)d * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -115,6 +138,16 @@ int init_rows(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar
     int n_iter = 0, converged = 0;
     if (const int rc = run_em(t, 1, d_feats, n, &one_w, one_mu.data(), one_var.data(), 1, 0.0, reg_covar, params.data(), nullptr, &n_iter, &converged, stream))
         return rc;
+    variance.assign(params.begin() + 1 + d, params.begin() + 1 + 2 * d);
+    return DSP_OK;
+}
+
+// the library's start: means = rows floor((i + 0.5) n / k), variances = the rows' global variance + reg_covar, weights 1 / k
+int init_rows(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means, double *variances, hipStream_t stream)
+{
+    const int k = t->k, d = t->d;
+    std::vector<double> variance;
+    if (const int rc = global_variance(t, d_feats, n, reg_covar, variance, stream)) return rc;
     std::vector<float> rows((size_t)k * d);
     for (int i = 0; i < k; ++i) {
         const long row = (long)(((__int128)(2 * i + 1) * n) / (2 * k));
@@ -125,10 +158,130 @@ int init_rows(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar
         weights[i] = 1.0 / k;
         for (int j = 0; j < d; ++j) {
             means[(size_t)i * d + j] = (double)rows[(size_t)i * d + j];
-            variances[(size_t)i * d + j] = params[1 + (size_t)d + j];
+            variances[(size_t)i * d + j] = variance[(size_t)j];
         }
     }
     return DSP_OK;
+}
+
+// --- the k-means start (include/dsp_amd.h dsp_kmeans_*) ---
+
+int check_kmeans_numbers(int max_iter, double tol, double reg_covar, const char *who)
+{
+    if (max_iter < 1) return capi_fail(DSP_EINVAL, std::string(who) + "max_iter must be >= 1, got " + std::to_string(max_iter));
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return capi_fail(DSP_EINVAL, std::string(who) + "tol must be >= 0 and finite");
+    return check_reg_covar(reg_covar);
+}
+
+// greedy k-means++ on the trainer's device (current) -> rows[k]
+int seed_rows(dsp_ubm_trainer *t, const float *d_feats, long n, uint64_t seed, long *rows, hipStream_t stream)
+{
+    const int k = t->k, d = t->d, trials = dsp::kmeans_trials(k);
+    const long n_chunks = dsp::kmeans_chunks(n), n_groups = dsp::ubm_groups(n), n_supers = dsp::ubm_supers(n);
+    const size_t n_u = (size_t)k * dsp::kKmeansMaxTrials;
+    if (t->km_m.reserve((size_t)n * sizeof(float)) != hipSuccess ||
+        t->km_sums.reserve((n_u + (size_t)trials * (size_t)(n_chunks + n_groups + n_supers)) * sizeof(double)) != hipSuccess ||
+        t->km_seed_ctrl.reserve(sizeof(dsp::KmeansSeedCtrl)) != hipSuccess)
+        return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's seeding workspace");
+    std::vector<double> u(n_u, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int tr = 0; tr < trials; ++tr) u[(size_t)j * dsp::kKmeansMaxTrials + tr] = dsp::kmeans_draw(seed, j, tr);
+    long row0 = (long)(u[0] * (double)n);
+    if (row0 >= n) row0 = n - 1;
+    dsp::KmeansSeedCtrl ctrl{};
+    ctrl.cand[0] = row0;
+    DSP_CAPI_HIP(hipMemcpyAsync(t->km_sums, u.data(), n_u * sizeof(double), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(t->km_seed_ctrl, &ctrl, sizeof(ctrl), hipMemcpyHostToDevice, stream));
+    double *chunks = t->km_sums.get() + n_u, *groups = chunks + (size_t)trials * n_chunks, *supers = groups + (size_t)trials * n_groups;
+    DSP_CAPI_HIP(dsp::launch_kmeans_seeding(dsp::KmeansSeed{d_feats, n, k, d, trials, t->km_m, chunks, groups, supers, t->km_sums, t->km_seed_ctrl}, row0, stream));
+    dsp::KmeansSeedCtrl end{};
+    DSP_CAPI_HIP(hipMemcpyAsync(&end, t->km_seed_ctrl, sizeof(end), hipMemcpyDeviceToHost, stream));
+    DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    if (end.failed == 1)
+        return capi_fail(DSP_EINVAL, "d_feats holds fewer than k = " + std::to_string(k) + " distinct rows: " + std::to_string(end.failed_step) +
+                                         " centres chosen, every row sits on one of them");
+    if (end.failed) return capi_fail(DSP_EHIP, "k-means++ seeding: no row under a positive sum at step " + std::to_string(end.failed_step));
+    for (int i = 0; i < k; ++i) rows[i] = end.rows[i];
+    return DSP_OK;
+}
+
+int reserve_kmeans(dsp_ubm_trainer *t, long n, int em_max_iter, bool own_labels)
+{
+    const int k = t->k, d = t->d;
+    if (const int rc = reserve_em(t, k, n, em_max_iter, dsp::kmeans_partial_doubles(k, d))) return rc;
+    if (t->km_centres.reserve(((size_t)k * d + k) * sizeof(double)) != hipSuccess || t->km_ctrl.reserve(sizeof(dsp::KmeansCtrl)) != hipSuccess ||
+        (own_labels && t->km_labels.reserve((size_t)n * sizeof(int)) != hipSuccess))
+        return capi_fail(DSP_ENOMEM, "hipMalloc of the trainer's k-means workspace");
+    return DSP_OK;
+}
+
+// Lloyd from centres0 (reserve_kmeans went before) and the final pass: the GMM start is left in the trainer's device parameters and
+// float32 model, the centres and counts in km_centres; `end` says how it stopped
+int run_lloyd(dsp_ubm_trainer *t, const float *d_feats, long n, const double *centres0, int max_iter, double shift_limit, double reg_covar, int *d_labels,
+              dsp::KmeansCtrl *end, hipStream_t stream)
+{
+    const int k = t->k, d = t->d;
+    const size_t kd = (size_t)k * d, stride = dsp::kmeans_partial_doubles(k, d);
+    const long n_groups = dsp::ubm_groups(n);
+    std::vector<float> c(centres0, centres0 + kd);                   // each rounded once
+    const dsp::GmmModelOut model{t->model, k, d};
+    int *labels = d_labels ? d_labels : t->km_labels.get();
+    const dsp::KmeansCtrl start{};
+    DSP_CAPI_HIP(hipMemcpyAsync(t->km_centres, centres0, kd * sizeof(double), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(model.means(), c.data(), kd * sizeof(float), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(t->km_ctrl, &start, sizeof(start), hipMemcpyHostToDevice, stream));
+    DSP_CAPI_HIP(hipMemsetAsync(labels, 0xff, (size_t)n * sizeof(int), stream));      // -1: every row changes in the first iteration
+    const dsp::KmeansFit fit{d_feats, n, t->km_centres, model, labels, t->partials, t->partials.get() + (size_t)n_groups * stride, t->km_ctrl, shift_limit, max_iter,
+                             reg_covar, t->state, t->km_centres.get() + kd};
+    *end = start;
+    for (int first = 0; first < max_iter && !end->done; first += kIterationsPerLook) {
+        const int count = max_iter - first < kIterationsPerLook ? max_iter - first : kIterationsPerLook;
+        DSP_CAPI_HIP(dsp::launch_kmeans_iterations(fit, first, count, stream));
+        DSP_CAPI_HIP(hipMemcpyAsync(end, t->km_ctrl, sizeof(*end), hipMemcpyDeviceToHost, stream));
+        DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    }
+    DSP_CAPI_HIP(dsp::launch_kmeans_final(fit, stream));
+    DSP_CAPI_HIP(hipMemcpyAsync(end, t->km_ctrl, sizeof(*end), hipMemcpyDeviceToHost, stream));
+    DSP_CAPI_HIP(hipStreamSynchronize(stream));                       // (also: `c` and `start` are read by then)
+    return DSP_OK;
+}
+
+// tol * mean_d var_d(x): sklearn's _tolerance
+int shift_limit_of(dsp_ubm_trainer *t, const float *d_feats, long n, double tol, double *limit, hipStream_t stream)
+{
+    std::vector<double> variance;
+    if (const int rc = global_variance(t, d_feats, n, 0.0, variance, stream)) return rc;
+    double sum = 0.0;
+    for (double v : variance) sum += v;
+    *limit = tol * (sum / (double)variance.size());
+    return DSP_OK;
+}
+
+int check_ubm_result(const dsp_ubm_result *result)
+{
+    if (!result || !result->weights || !result->variances || !result->lower_bounds) return capi_fail(DSP_EINVAL, "dsp_ubm_result and its arrays must not be NULL");
+    return dsp::check_gmm_float_arrays(&result->gmm, "dsp_ubm_result");      // (k and d are the call's to write)
+}
+
+void write_ubm_result(dsp_ubm_result *result, int k, int d, const std::vector<double> &params, int n_iter, int converged)
+{
+    const size_t kd = (size_t)k * d;
+    // the caller's arrays behind the const pointers of dsp_gmm_float_params are the result's to write
+    double *log_consts = const_cast<double *>(result->gmm.log_consts), *means = const_cast<double *>(result->gmm.means);
+    double *inv_covs = const_cast<double *>(result->gmm.inv_covs);
+    for (int i = 0; i < k; ++i) {
+        result->weights[i] = params[i];
+        log_consts[i] = params[(size_t)k + 2 * kd + i];
+    }
+    for (size_t i = 0; i < kd; ++i) {
+        means[i] = params[(size_t)k + i];
+        result->variances[i] = params[(size_t)k + kd + i];
+        inv_covs[i] = 1.0 / params[(size_t)k + kd + i];
+    }
+    result->gmm.k = k;
+    result->gmm.d = d;
+    result->n_iter = n_iter;
+    result->converged = converged;
 }
 
 }  // namespace
@@ -194,8 +347,7 @@ int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const
             if (!(init->variances[i] > 0.0)) return capi_fail(DSP_EINVAL, "dsp_ubm_init: variances must be > 0 (component " + std::to_string(i / d) + ")");
         }
     }
-    if (!result || !result->weights || !result->variances || !result->lower_bounds) return capi_fail(DSP_EINVAL, "dsp_ubm_result and its arrays must not be NULL");
-    if (const int rc = dsp::check_gmm_float_arrays(&result->gmm, "dsp_ubm_result")) return rc;      // (k and d are the call's to write)
+    if (const int rc = check_ubm_result(result)) return rc;
     if (const int rc = dsp::check_device(t->device)) return rc;
     DSP_ON_DEVICE(t->device);
     std::vector<double> start;
@@ -212,22 +364,113 @@ int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const
     if (const int rc = run_em(t, k, d_feats, n, w, mu, var, cfg->max_iter, cfg->tol, cfg->reg_covar, params.data(), result->lower_bounds, &n_iter, &converged,
                               (hipStream_t)stream))
         return rc;
-    // the caller's arrays behind the const pointers of dsp_gmm_float_params are the result's to write
-    double *log_consts = const_cast<double *>(result->gmm.log_consts), *means = const_cast<double *>(result->gmm.means);
-    double *inv_covs = const_cast<double *>(result->gmm.inv_covs);
+    write_ubm_result(result, k, d, params, n_iter, converged);
+    return DSP_OK;
+}
+
+int dsp_kmeans_seed_device(dsp_ubm_trainer *t, const float *d_feats, long n, uint64_t seed, long *rows, void *stream)
+{
+    if (const int rc = check_rows(t, d_feats, n)) return rc;
+    if (!rows) return capi_fail(DSP_EINVAL, "rows is NULL");
+    if (const int rc = dsp::check_device(t->device)) return rc;
+    DSP_ON_DEVICE(t->device);
+    return seed_rows(t, d_feats, n, seed, rows, (hipStream_t)stream);
+}
+
+int dsp_kmeans_fit_device(dsp_ubm_trainer *t, const float *d_feats, long n, const double *centres0, const dsp_kmeans_config *cfg, dsp_kmeans_result *result,
+                          void *stream)
+{
+    if (const int rc = check_rows(t, d_feats, n)) return rc;
+    if (!centres0) return capi_fail(DSP_EINVAL, "centres0 is NULL");
+    if (!cfg) return capi_fail(DSP_EINVAL, "dsp_kmeans_config is NULL");
+    if (const int rc = check_kmeans_numbers(cfg->max_iter, cfg->tol, cfg->reg_covar, "dsp_kmeans_config: ")) return rc;
+    const int k = t->k, d = t->d;
+    const size_t kd = (size_t)k * d;
+    for (size_t i = 0; i < kd; ++i)
+        if (!std::isfinite(centres0[i]) || std::fabs(centres0[i]) > (double)std::numeric_limits<float>::max())
+            return capi_fail(DSP_EINVAL, "centres0 must be finite (centre " + std::to_string(i / d) + ")");
+    if (!result || !result->centres || !result->counts || !result->weights || !result->means || !result->variances)
+        return capi_fail(DSP_EINVAL, "dsp_kmeans_result and its centres, counts, weights, means and variances must not be NULL");
+    if (const int rc = dsp::check_device(t->device)) return rc;
+    DSP_ON_DEVICE(t->device);
+    hipStream_t s = (hipStream_t)stream;
+    double limit = 0.0;
+    if (const int rc = shift_limit_of(t, d_feats, n, cfg->tol, &limit, s)) return rc;
+    if (const int rc = reserve_kmeans(t, n, 1, !result->d_labels)) return rc;
+    dsp::KmeansCtrl end{};
+    if (const int rc = run_lloyd(t, d_feats, n, centres0, cfg->max_iter, limit, cfg->reg_covar, result->d_labels, &end, s)) return rc;
+    std::vector<double> params(dsp::ubm_param_doubles(k, d)), counts((size_t)k);
+    DSP_CAPI_HIP(hipMemcpyAsync(result->centres, t->km_centres, kd * sizeof(double), hipMemcpyDeviceToHost, s));
+    DSP_CAPI_HIP(hipMemcpyAsync(counts.data(), t->km_centres.get() + kd, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
+    DSP_CAPI_HIP(hipMemcpyAsync(params.data(), t->state, params.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    DSP_CAPI_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < k; ++i) {
+        result->counts[i] = (long)counts[i];
         result->weights[i] = params[i];
-        log_consts[i] = params[(size_t)k + 2 * kd + i];
     }
     for (size_t i = 0; i < kd; ++i) {
-        means[i] = params[(size_t)k + i];
+        result->means[i] = params[(size_t)k + i];
         result->variances[i] = params[(size_t)k + kd + i];
-        inv_covs[i] = 1.0 / params[(size_t)k + kd + i];
     }
-    result->gmm.k = k;
-    result->gmm.d = d;
-    result->n_iter = n_iter;
-    result->converged = converged;
+    result->inertia = end.inertia;
+    result->n_iter = end.n_iter;
+    result->stop = end.reason;
+    result->n_empty = end.n_empty;
+    return DSP_OK;
+}
+
+int dsp_kmeans_train_ubm_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_kmeans_ubm_config *cfg, dsp_ubm_result *result,
+                                dsp_kmeans_ubm_report *report, void *stream)
+{
+    if (const int rc = check_rows(t, d_feats, n)) return rc;
+    if (!cfg) return capi_fail(DSP_EINVAL, "dsp_kmeans_ubm_config is NULL");
+    if (cfg->n_init < 1) return capi_fail(DSP_EINVAL, "dsp_kmeans_ubm_config: n_init must be >= 1, got " + std::to_string(cfg->n_init));
+    if (const int rc = check_kmeans_numbers(cfg->kmeans_max_iter, cfg->kmeans_tol, cfg->em.reg_covar, "dsp_kmeans_ubm_config: kmeans_")) return rc;
+    if (cfg->em.max_iter < 1) return capi_fail(DSP_EINVAL, "dsp_kmeans_ubm_config: em.max_iter must be >= 1, got " + std::to_string(cfg->em.max_iter));
+    if (!(cfg->em.tol >= 0.0)) return capi_fail(DSP_EINVAL, "dsp_kmeans_ubm_config: em.tol must be >= 0");
+    if (const int rc = check_ubm_result(result)) return rc;
+    if (!report || !report->restarts) return capi_fail(DSP_EINVAL, "dsp_kmeans_ubm_report and its restarts must not be NULL");
+    if (const int rc = dsp::check_device(t->device)) return rc;
+    DSP_ON_DEVICE(t->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int k = t->k, d = t->d;
+    const size_t kd = (size_t)k * d;
+    double limit = 0.0;
+    if (const int rc = shift_limit_of(t, d_feats, n, cfg->kmeans_tol, &limit, s)) return rc;
+    // everything both halves need, before the first of them: the GMM start must survive in the workspace from Lloyd's final pass to EM
+    if (const int rc = reserve_kmeans(t, n, cfg->em.max_iter, true)) return rc;
+    std::vector<double> params(dsp::ubm_param_doubles(k, d)), best_params, bounds((size_t)cfg->em.max_iter), best_bounds, centres0(kd);
+    std::vector<float> picked(kd);
+    int best = -1, best_iter = 0, best_converged = 0;
+    for (int r = 0; r < cfg->n_init; ++r) {
+        dsp_kmeans_restart &rep = report->restarts[r];
+        if (const int rc = seed_rows(t, d_feats, n, dsp::kmeans_restart_seed(cfg->seed, r), rep.rows, s)) return rc;
+        for (int i = 0; i < k; ++i)
+            DSP_CAPI_HIP(hipMemcpyAsync(picked.data() + (size_t)i * d, d_feats + (size_t)rep.rows[i] * d, (size_t)d * sizeof(float), hipMemcpyDeviceToHost, s));
+        DSP_CAPI_HIP(hipStreamSynchronize(s));
+        for (size_t i = 0; i < kd; ++i) centres0[i] = (double)picked[i];
+        dsp::KmeansCtrl end{};
+        if (const int rc = run_lloyd(t, d_feats, n, centres0.data(), cfg->kmeans_max_iter, limit, cfg->em.reg_covar, nullptr, &end, s)) return rc;
+        int n_iter = 0, converged = 0;
+        if (const int rc = run_em_from_device(t, k, d_feats, n, cfg->em.max_iter, cfg->em.tol, cfg->em.reg_covar, params.data(), bounds.data(), &n_iter, &converged, s))
+            return rc;
+        rep.kmeans_n_iter = end.n_iter;
+        rep.kmeans_stop = end.reason;
+        rep.kmeans_n_empty = end.n_empty;
+        rep.em_n_iter = n_iter;
+        rep.em_converged = converged;
+        rep.lower_bound = bounds[(size_t)n_iter - 1];
+        if (best < 0 || rep.lower_bound > report->restarts[best].lower_bound) {      // ties to the first
+            best = r;
+            best_params = params;
+            best_bounds.assign(bounds.begin(), bounds.begin() + n_iter);
+            best_iter = n_iter;
+            best_converged = converged;
+        }
+    }
+    for (int i = 0; i < best_iter; ++i) result->lower_bounds[i] = best_bounds[(size_t)i];
+    write_ubm_result(result, k, d, best_params, best_iter, best_converged);
+    report->winner = best;
     return DSP_OK;
 }
 

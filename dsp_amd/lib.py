@@ -85,6 +85,41 @@ class UbmResult(C.Structure):
                 ("n_iter", C.c_int), ("converged", C.c_int)]
 
 
+class KmeansConfig(C.Structure):
+    """dsp_kmeans_config (include/dsp_amd.h)."""
+
+    _fields_ = [("max_iter", C.c_int), ("tol", C.c_double), ("reg_covar", C.c_double)]
+
+
+class KmeansResult(C.Structure):
+    """dsp_kmeans_result (include/dsp_amd.h): the caller's arrays and how Lloyd stopped."""
+
+    _fields_ = [("centres", C.c_void_p), ("counts", C.c_void_p), ("weights", C.c_void_p), ("means", C.c_void_p), ("variances", C.c_void_p),
+                ("d_labels", C.c_void_p), ("inertia", C.c_double), ("n_iter", C.c_int), ("stop", C.c_int), ("n_empty", C.c_int)]
+
+
+class KmeansUbmConfig(C.Structure):
+    """dsp_kmeans_ubm_config (include/dsp_amd.h)."""
+
+    _fields_ = [("n_init", C.c_int), ("seed", C.c_uint64), ("kmeans_max_iter", C.c_int), ("kmeans_tol", C.c_double), ("em", UbmConfig)]
+
+
+class KmeansRestart(C.Structure):
+    """dsp_kmeans_restart (include/dsp_amd.h): what one restart did."""
+
+    _fields_ = [("rows", C.c_long * 64), ("kmeans_n_iter", C.c_int), ("kmeans_stop", C.c_int), ("kmeans_n_empty", C.c_int),
+                ("em_n_iter", C.c_int), ("em_converged", C.c_int), ("lower_bound", C.c_double)]
+
+
+class KmeansUbmReport(C.Structure):
+    """dsp_kmeans_ubm_report (include/dsp_amd.h)."""
+
+    _fields_ = [("restarts", C.POINTER(KmeansRestart)), ("winner", C.c_int)]
+
+
+KMEANS_STOP = ("max_iter", "tol", "strict")      # DSP_KMEANS_STOP_*
+
+
 class ScanConfig(C.Structure):
     """dsp_scan_config (include/dsp_amd.h): windows of MFCC rows."""
 
@@ -153,6 +188,7 @@ SYMBOLS = [
     "dsp_cmvn_create", "dsp_cmvn_destroy", "dsp_cmvn_ragged_device",
     "dsp_speaker_enroller_create", "dsp_speaker_enroller_destroy", "dsp_speaker_enroll_ragged_device",
     "dsp_ubm_trainer_create", "dsp_ubm_trainer_destroy", "dsp_ubm_init_rows_device", "dsp_ubm_train_device", "dsp_gmm_quantize",
+    "dsp_kmeans_seed_device", "dsp_kmeans_fit_device", "dsp_kmeans_train_ubm_device",
     "dsp_speaker_verifier_create", "dsp_speaker_verifier_destroy", "dsp_speaker_verify_ragged_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
@@ -312,6 +348,10 @@ def load() -> C.CDLL:
     L.dsp_ubm_init_rows_device.argtypes = [vp, vp, C.c_long, C.c_double, vp, vp, vp, vp]; L.dsp_ubm_init_rows_device.restype = ip
     L.dsp_ubm_train_device.argtypes = [vp, vp, C.c_long, C.POINTER(UbmInit), C.POINTER(UbmConfig), C.POINTER(UbmResult), vp]
     L.dsp_ubm_train_device.restype = ip
+    L.dsp_kmeans_seed_device.argtypes = [vp, vp, C.c_long, C.c_uint64, vp, vp]; L.dsp_kmeans_seed_device.restype = ip
+    L.dsp_kmeans_fit_device.argtypes = [vp, vp, C.c_long, vp, C.POINTER(KmeansConfig), C.POINTER(KmeansResult), vp]; L.dsp_kmeans_fit_device.restype = ip
+    L.dsp_kmeans_train_ubm_device.argtypes = [vp, vp, C.c_long, C.POINTER(KmeansUbmConfig), C.POINTER(UbmResult), C.POINTER(KmeansUbmReport), vp]
+    L.dsp_kmeans_train_ubm_device.restype = ip
     L.dsp_gmm_quantize.argtypes = [C.POINTER(GmmFloatParams), vp, vp, vp, C.POINTER(C.c_int)]; L.dsp_gmm_quantize.restype = ip
     L.dsp_speaker_verifier_create.argtypes = [C.POINTER(GmmFloatParams), ip, C.POINTER(vp)]; L.dsp_speaker_verifier_create.restype = ip
     L.dsp_speaker_verifier_destroy.argtypes = [vp]; L.dsp_speaker_verifier_destroy.restype = None

@@ -15,7 +15,8 @@
  * -l: the rows the reference's float GMMs are trained on (dsp_mfcc_speaker_config: librosa.feature.mfcc with n_fft 400, 128 mel filters,
  * centred frames; 2fa/audio/speaker/gmm_utils.py:52-58) instead of the firmware's 512-point front end (dsp_mfcc_default_config).
  *
- * Out of scope here as in the library: UBM training, variance or weight adaptation, CMVN for live streams.
+ * Out of scope here: UBM training (examples/main_train_ubm.c).  Out of scope in the library too: variance or weight adaptation, CMVN for
+ * live streams.
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>

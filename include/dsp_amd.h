@@ -761,8 +761,8 @@ int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_fea
  * The start: dsp_ubm_init (weights > 0 that sum to 1 within 1e-6, means, variances > 0, all finite), or DSP_UBM_INIT_ROWS (NULL) for
  * the library's own, which dsp_ubm_init_rows_device also writes out: means_i = row floor((i + 0.5) n / k), variances = the rows' global
  * variance per dimension + reg_covar (one k = 1 iteration of the same kernels from mean = row floor(n / 2), variance 1), weights 1 / k.
- * sklearn's k-means initialisation and its n_init restarts are not built: restart by calling again with another dsp_ubm_init and keep
- * the fit with the larger last lower bound.
+ * sklearn's own start -- k-means++ seeding, Lloyd, the GMM of the labels, and n_init restarts of all of it -- is dsp_kmeans_* below, on
+ * the same trainer: dsp_kmeans_train_ubm_device is the reference's whole GaussianMixture(...).fit call.
  *
  * dsp_ubm_result: the caller's arrays.  gmm is the dsp_gmm_float_params of the trained model (k and d are set, log_consts[k], means[k][d]
  * and inv_covs[k][d] = 1 / variances are written through the pointers, which must point at writable doubles): &result.gmm goes to
@@ -773,9 +773,10 @@ int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_fea
  *   means = rint(64 mean) -> int8,  inv_covs = rint(2048 inv_cov) -> int32,  log_consts = rint(256 log_const) -> int16,
  * ties to even, each table saturated to its type; saturated[3] = the entries clamped in means, inv_covs, log_consts.  2048 / 1e-6 fits
  * int32; a reg_covar below about 9.6e-7 may not, which is what the count is for.
- * Not covered: k-means initialisation and n_init restarts, full or tied covariances, variance and weight adaptation at enrolment,
- * multi-GPU training (the statistics are summable, the tree is not defined across devices), CMVN inside scanners or streams.  (The
- * rows the reference trains on come from dsp_mfcc_speaker_config.) */
+ * Covered below (dsp_kmeans_*): the k-means start and the n_init restarts.  Not covered: sklearn's random stream (the seeding draws
+ * are this library's own, defined below), relocation of empty clusters, init_params="random", sample weights, mini-batch k-means,
+ * full or tied covariances, variance and weight adaptation at enrolment, multi-GPU training (the statistics are summable, the tree is
+ * not defined across devices), CMVN inside scanners or streams.  (The rows the reference trains on come from dsp_mfcc_speaker_config.) */
 typedef struct dsp_ubm_init {
     const double *weights;       /* [k]    */
     const double *means;         /* [k][d] */
@@ -802,6 +803,102 @@ int dsp_ubm_init_rows_device(dsp_ubm_trainer *t, const float *d_feats, long n, d
 int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_ubm_init *init, const dsp_ubm_config *cfg,
                          dsp_ubm_result *result, void *stream);
 int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_covs, int16_t *log_consts, int saturated[3]);
+
+/* --- the k-means start of UBM training: k-means++ seeding, Lloyd, n_init restarts ---
+ * What GaussianMixture(n_components=32, covariance_type="diag", max_iter=300, n_init=2) of the reference's train_ubm.py does before and
+ * around EM (sklearn: init_params="kmeans"): three steps on a dsp_ubm_trainer, each usable on its own.  Rows, k, d and n as above; ONE
+ * stream at a time per trainer.  The sums of all three go through the tree of dsp_ubm_train_device: chunk c = rows [256 c, 256 c + 256),
+ * 16 consecutive chunks to a group, 32 consecutive groups to a super, the supers in ascending order -- a function of n alone, no float
+ * atomics: every result below is the same bits whatever the grid, the CU count, the rows' address or what the workspace held before.
+ *
+ * 1. dsp_kmeans_seed_device: greedy k-means++, deterministic from a 64-bit seed -> rows[k], the chosen rows in the order chosen.
+ *   Draws (counter-based: no state, recomputable anywhere):  mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+ *     0x94D049BB133111EB, z ^ z >> 31 (splitmix64's finaliser, 64-bit wrap-around);  u(seed, j, t) = (mix(seed + (8 j + t + 1) *
+ *     0x9E3779B97F4A7C15) >> 11) * 2^-53, in [0, 1): j the step, t the trial.
+ *   Trials: T = 2 + floor(ln k) per step (sklearn's n_local_trials; at most 6).
+ *   Step 0: row floor(u(seed, 0, 0) n).
+ *   m_i: the float32 squared distance of row i to the nearest chosen centre, sum_d (x_d - c_d)^2 over ascending d by fused
+ *     multiply-add, kept in a device array.
+ *   Sums of m: float64 from the row up.  Inside a chunk 16 segments of 16 consecutive rows, ascending in a segment and over the
+ *     segments; then the tree above.
+ *   Step j >= 1: pot = sum m_i.  Trial t proposes a row by walking r = u(seed, j, t) pot down the tree -- supers, then the super's
+ *     groups, the group's chunks, the chunk's rows, each level ascending: the first child whose sum v exceeds r, else r -= v; a child
+ *     with v = 0 is never taken (so never a row with m_i = 0, never a chosen row or a copy of one); where rounding walks r past the last
+ *     child, the last child with v > 0, and likewise below it.  The trial whose new potential sum_i min(m_i, |x_i - x_cand|^2) is
+ *     smallest wins, ties to the lowest t.
+ *   pot = 0 with centres left to choose: the matrix has fewer than k distinct rows; the call fails with DSP_EINVAL and a message that
+ *     says so (a flag on the device, read at the end), and the trainer stays usable.
+ *   The whole seeding is enqueued without a host round trip; per step one pass over the rows (fold the last winner into m, evaluate
+ *   the T proposals, leave T sets of sums) and one small launch (the winner; its sums are the next step's tree; the next proposals).
+ *
+ * 2. dsp_kmeans_fit_device: Lloyd from centres0[k][d] (host float64, finite; typically the seed rows), and the GMM the labels give.
+ *   Iteration i = 1, 2, ... from the float64 centres:
+ *   1. c = float32(centre), rounded once;
+ *   2. per row, in float32: s_k = sum_d (x_d - c_kd)^2 (ascending d, fused multiply-add); label = the k of the smallest s_k, ties to
+ *      the lowest k;
+ *   3. over the rows labelled k, centred on c: N_k, F_kd = sum (x_d - c_kd), G_kd = sum (x_d - c_kd)^2; the inertia sum s_label;
+ *      and the number of rows whose label differs from the previous iteration's (all of them in iteration 1).  float32 inside a chunk
+ *      (the four waves' interleaved rows combined in wave order), float64 above it, as EM's;
+ *   4. in float64: centre'_kd = c_kd + F_kd / N_k.  A cluster with N_k = 0 keeps its centre: sklearn relocates such a cluster to the
+ *      row farthest from its centre, this library does not (n_empty reports them);
+ *   5. stop after iteration i when no label changed (DSP_KMEANS_STOP_STRICT, tested first, as in sklearn), else when
+ *      sum_kd (centre' - centre)^2 <= tol * mean_d var_d(x) (DSP_KMEANS_STOP_TOL; var_d: the rows' global variance, computed once per
+ *      call as dsp_ubm_init_rows_device does), else after max_iter iterations (DSP_KMEANS_STOP_MAX_ITER);
+ *   6. after the stop one more pass labels the rows against the final centres (sklearn does so unless the stop was strict, where it
+ *      changes nothing) and takes N, F, G and the inertia; step 4 of dsp_ubm_train_device on them, with p in {0, 1}, gives the GMM
+ *      start: weights, means and variances + reg_covar -- sklearn's _initialize for init_params="kmeans".  An empty cluster is that
+ *      step's component no row visits.
+ *   The iterations are enqueued as EM's are: every launch tests a stop flag first, the host looks every 32 iterations.
+ *   dsp_kmeans_result: centres[k][d] (the final centres, float64), counts[k], the GMM start weights[k], means[k][d], variances[k][d]
+ *   (the caller's arrays, none NULL; the three are a dsp_ubm_init as they are), inertia, n_iter, stop, n_empty;  d_labels[n] (int32
+ *   on the device) may be NULL.
+ *
+ * 3. dsp_kmeans_train_ubm_device: the reference's call.  For r = 0 .. n_init - 1: seed with seed_r = mix((seed ^ 0xD1B54A32D192ED03)
+ *   + (r + 1) * 0x9E3779B97F4A7C15); Lloyd from those rows (kmeans_max_iter, kmeans_tol, em.reg_covar), whose final pass writes the
+ *   GMM start straight into the trainer's device parameters and float32 model -- no host copy between k-means and EM; EM exactly as
+ *   dsp_ubm_train_device runs it (em).  The model returned in dsp_ubm_result (unchanged) is the restart whose last lower bound is the
+ *   largest, ties to the first: sklearn's rule.  report->restarts[n_init] (the caller's array) says what each restart did,
+ *   report->winner which one was kept. */
+#define DSP_KMEANS_STOP_MAX_ITER 0
+#define DSP_KMEANS_STOP_TOL 1
+#define DSP_KMEANS_STOP_STRICT 2
+typedef struct dsp_kmeans_config {
+    int max_iter;                /* >= 1; sklearn's default 300          */
+    double tol;                  /* >= 0, finite; sklearn's default 1e-4 */
+    double reg_covar;            /* >= 0, finite; of the GMM start       */
+} dsp_kmeans_config;
+typedef struct dsp_kmeans_result {
+    double *centres;             /* [k][d] */
+    long *counts;                /* [k]    */
+    double *weights;             /* [k]    the GMM start */
+    double *means;               /* [k][d] */
+    double *variances;           /* [k][d] */
+    int *d_labels;               /* [n] on the device, may be NULL */
+    double inertia;
+    int n_iter, stop, n_empty;
+} dsp_kmeans_result;
+typedef struct dsp_kmeans_ubm_config {
+    int n_init;                  /* >= 1; 2 in train_ubm.py */
+    uint64_t seed;
+    int kmeans_max_iter;         /* >= 1; sklearn's 300     */
+    double kmeans_tol;           /* >= 0, finite; 1e-4      */
+    dsp_ubm_config em;
+} dsp_kmeans_ubm_config;
+typedef struct dsp_kmeans_restart {
+    long rows[64];               /* the seed rows, [0, k) written */
+    int kmeans_n_iter, kmeans_stop, kmeans_n_empty;
+    int em_n_iter, em_converged;
+    double lower_bound;          /* EM's last */
+} dsp_kmeans_restart;
+typedef struct dsp_kmeans_ubm_report {
+    dsp_kmeans_restart *restarts;        /* [n_init], the caller's */
+    int winner;
+} dsp_kmeans_ubm_report;
+int dsp_kmeans_seed_device(dsp_ubm_trainer *t, const float *d_feats, long n, uint64_t seed, long *rows, void *stream);
+int dsp_kmeans_fit_device(dsp_ubm_trainer *t, const float *d_feats, long n, const double *centres0, const dsp_kmeans_config *cfg,
+                          dsp_kmeans_result *result, void *stream);
+int dsp_kmeans_train_ubm_device(dsp_ubm_trainer *t, const float *d_feats, long n, const dsp_kmeans_ubm_config *cfg, dsp_ubm_result *result,
+                                dsp_kmeans_ubm_report *report, void *stream);
 
 /* --- verifying speakers with the float GMMs: every clip against every speaker ---
  * The step behind enrolment: target.score(feats) - ubm.score(feats) of the reference's 2fa/audio/speaker/gmm_utils.py:99-126
