@@ -620,25 +620,47 @@ class SpeakerVerifier:
         [S][k][d] (SpeakerEnroller.enroll(...)["means"] as it is) -> a dict of cuda tensors, those named in `want` of: llr float32 [C][S],
         ll_ubm float32 [C], ll_target float32 [C][S], best int32 [C] (the smallest s with the largest llr), best_llr float32 [C]."""
         import torch
-        want = tuple(want)
-        if not want or any(key not in self.OUTPUTS for key in want):
-            raise ValueError(f"want must name at least one of {self.OUTPUTS}")
-        fo = _frame_offsets(frame_offsets)
-        feats = _scan_mfcc(feats, fo, self.d)
-        if (np.diff(fo) == 0).any():
-            raise ValueError(f"clip {int(np.flatnonzero(np.diff(fo) == 0)[0])} has no rows")
-        if not (isinstance(means, torch.Tensor) and means.is_cuda and means.dtype == torch.float32 and means.dim() == 3
-                and tuple(means.shape[1:]) == (self.k, self.d)):
-            raise ValueError(f"means must be a float32 CUDA tensor [S][{self.k}][{self.d}]")
-        if means.device != feats.device:
-            raise ValueError("means and feats must be on the same device")
-        means = means.contiguous()
+        feats, fo, means, want = self._inputs(feats, frame_offsets, means, want, "clip")
         n, n_spk, dev = fo.size - 1, means.shape[0], feats.device
         shape = {"llr": (n, n_spk), "ll_ubm": (n,), "ll_target": (n, n_spk), "best": (n,), "best_llr": (n,)}
         out = {key: torch.empty(shape[key], dtype=torch.int32 if key == "best" else torch.float32, device=dev) for key in want}
         _lib.check(self._L.dsp_speaker_verify_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_LP), means.data_ptr(), n_spk,
                                                             *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
                    "dsp_speaker_verify_ragged_device")
+        return out
+
+    def _inputs(self, feats, frame_offsets, means, want, what):
+        """the argument checks verify and scan share -> (feats, fo, means, want)"""
+        import torch
+        want = tuple(want)
+        if not want or any(key not in self.OUTPUTS for key in want):
+            raise ValueError(f"want must name at least one of {self.OUTPUTS}")
+        fo = _frame_offsets(frame_offsets)
+        if (np.diff(fo) == 0).any():
+            raise ValueError(f"{what} {int(np.flatnonzero(np.diff(fo) == 0)[0])} has no rows")
+        feats = _scan_mfcc(feats, fo, self.d)
+        if not (isinstance(means, torch.Tensor) and means.is_cuda and means.dtype == torch.float32 and means.dim() == 3
+                and tuple(means.shape[1:]) == (self.k, self.d)):
+            raise ValueError(f"means must be a float32 CUDA tensor [S][{self.k}][{self.d}]")
+        if means.device != feats.device:
+            raise ValueError("means and feats must be on the same device")
+        return feats, fo, means.contiguous(), want
+
+    def scan(self, feats, frame_offsets, means, window_frames: int, hop_frames: int, want=("llr", "ll_ubm", "best", "best_llr")):
+        """The same scores per sliding window of window_frames rows every hop_frames rows (dsp_speaker_float_scan_device): feats cuda
+        float32 [F][d], recording r = rows [frame_offsets[r], frame_offsets[r + 1]), CMVN'd over the recording, every recording >= 1
+        row; means as verify takes them -> a dict of cuda tensors with the Wt windows of all recordings leading, recording r's at
+        scan_window_offsets(frame_offsets, window_frames, hop_frames)[r : r + 2]: llr float32 [Wt][S], ll_ubm float32 [Wt], ll_target
+        float32 [Wt][S], best int32 [Wt], best_llr float32 [Wt].  Each equals verify on the window's rows as a clip, bit for bit."""
+        import torch
+        cfg = _scan_config(window_frames, hop_frames)
+        feats, fo, means, want = self._inputs(feats, frame_offsets, means, want, "recording")
+        nw, n_spk, dev = int(scan_window_offsets(fo, window_frames, hop_frames)[-1]), means.shape[0], feats.device
+        shape = {"llr": (nw, n_spk), "ll_ubm": (nw,), "ll_target": (nw, n_spk), "best": (nw,), "best_llr": (nw,)}
+        out = {key: torch.empty(shape[key], dtype=torch.int32 if key == "best" else torch.float32, device=dev) for key in want}
+        _lib.check(self._L.dsp_speaker_float_scan_device(self._h, feats.data_ptr(), fo.size - 1, fo.ctypes.data_as(_LP), C.byref(cfg), means.data_ptr(),
+                                                         n_spk, *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
+                   "dsp_speaker_float_scan_device")
         return out
 
 

@@ -190,6 +190,7 @@ SYMBOLS = [
     "dsp_ubm_trainer_create", "dsp_ubm_trainer_destroy", "dsp_ubm_init_rows_device", "dsp_ubm_train_device", "dsp_gmm_quantize",
     "dsp_kmeans_seed_device", "dsp_kmeans_fit_device", "dsp_kmeans_train_ubm_device",
     "dsp_speaker_verifier_create", "dsp_speaker_verifier_destroy", "dsp_speaker_verify_ragged_device",
+    "dsp_speaker_float_scan_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -357,6 +358,8 @@ def load() -> C.CDLL:
     L.dsp_speaker_verifier_destroy.argtypes = [vp]; L.dsp_speaker_verifier_destroy.restype = None
     L.dsp_speaker_verify_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
     L.dsp_speaker_verify_ragged_device.restype = ip
+    L.dsp_speaker_float_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
+    L.dsp_speaker_float_scan_device.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

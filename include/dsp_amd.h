@@ -928,7 +928,8 @@ int dsp_kmeans_train_ubm_device(dsp_ubm_trainer *t, const float *d_feats, long n
  * workspace of tile sums, [tiles][1 + S] doubles: ONE stream at a time per verifier.  A call whose workspace would pass 256 MiB is split
  * over runs of clips internally, on the same stream; the outputs do not change.
  * Not covered: per-speaker variances or weights (mean-only MAP is what enrolment writes), a trial LIST instead of the full C x S
- * matrix, CMVN inside the call (dsp_cmvn_ragged_device in front), multi-GPU (split the clips or the speakers across verifiers). */
+ * matrix, CMVN inside the call (dsp_cmvn_ragged_device in front), multi-GPU (split the clips or the speakers across verifiers).  Long
+ * recordings are scanned window by window by dsp_speaker_float_scan_device below. */
 typedef struct dsp_speaker_verifier dsp_speaker_verifier;
 int dsp_speaker_verifier_create(const dsp_gmm_float_params *ubm, int device, dsp_speaker_verifier **out);
 void dsp_speaker_verifier_destroy(dsp_speaker_verifier *v);
@@ -940,6 +941,38 @@ int dsp_speaker_verify_ragged_device(dsp_speaker_verifier *v, const float *d_fea
                                      int *d_best,         /* [C]      may be NULL         */
                                      float *d_best_llr,   /* [C]      may be NULL         */
                                      void *stream);
+
+/* SCANNING LONG RECORDINGS with the float GMMs: the same scores per sliding window and speaker -- who speaks when.
+ * Recording r is rows [frame_offsets[r], frame_offsets[r + 1]) of d_feats[..][d] (frame_offsets: a HOST array of n_recordings + 1 rows,
+ * read before the call returns), rows that are already CMVN'd over the RECORDING, not over a window (dsp_cmvn_ragged_device in front).
+ * The windows are those of dsp_scan_config / dsp_scan_window_offsets above: R >= window_frames rows give 1 + (R - window_frames) /
+ * hop_frames windows, window w = rows [w hop_frames, w hop_frames + window_frames); fewer rows one window of all R.  The windows of all
+ * recordings lie back to back, Wt in all.  d_means[S][k][d] as dsp_speaker_verify_ragged_device takes them.
+ *
+ * Per row and model, ll is dsp_speaker_verify_ragged_device's, bit for bit, computed ONCE per row of a run (not once per window it
+ * lies in).  Per window of n rows and model, L is the float64 sum of the window's ll in the per-clip entry's order, applied to the
+ * window as if it were a clip: tiles of 64 rows cut from the WINDOW's first row, the adjacent pairwise tree inside a tile (absent rows
+ * 0), the tiles added in ascending order.  The five outputs are formed from L_u, L_s and n as above.  So every output of window w
+ * equals, bit for bit, what dsp_speaker_verify_ragged_device gives for the same rows handed over as a clip of their own -- whatever the
+ * batch, the other speakers, a speaker's position, the grid, the split and what the workspace held.  There are no atomics.
+ *
+ * Any output may be NULL, not all.  DSP_EINVAL, before a device is touched: cfg NULL or window_frames / hop_frames < 1; a NULL d_feats,
+ * d_means or frame_offsets; offsets that are negative or decrease; a recording without rows (the first is named); more than 2^19
+ * speakers or 2^30 recordings.  n_recordings == 0 or n_speakers == 0: DSP_OK, no launch, no device.  The verifier's grow-only
+ * workspace, shared with the per-clip entry, holds float ll[1 + S][rows of a run]: ONE stream at a time per verifier.  A call whose
+ * ll would pass 256 MiB is cut into runs of consecutive windows (a window is never cut; rows shared by two runs are scored in both),
+ * on the same stream; the outputs do not change.  Rows that lie in no window (hop_frames > window_frames, the tail behind a
+ * recording's last window) are not scored.
+ * Not covered: stream sessions (sliding CMVN looks ahead) and a scanner from audio (under the speaker plan a recording's rows depend
+ * on the whole recording: compute its features, then scan -- INTEGRATION.md 6i), thresholds and segments on top of the scores. */
+int dsp_speaker_float_scan_device(dsp_speaker_verifier *v, const float *d_feats, long n_recordings, const long *frame_offsets,
+                                  const dsp_scan_config *cfg, const float *d_means, long n_speakers,
+                                  float *d_llr,        /* [Wt][S]                 */
+                                  float *d_ll_ubm,     /* [Wt]     may be NULL    */
+                                  float *d_ll_target,  /* [Wt][S]  may be NULL    */
+                                  int *d_best,         /* [Wt]     may be NULL    */
+                                  float *d_best_llr,   /* [Wt]     may be NULL    */
+                                  void *stream);
 
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
