@@ -10,6 +10,8 @@ only in the order of their float64 layer-1 sums (and, on the fused path, in the 
 
 The fused and ragged fused paths run on every model with units[0] <= 4 and n_coef <= 16 -- the n_coef 13 ones and, beyond the
 reference's shape, the n_coef 1 ones, since the library accepts plans of up to 16 coefficients there; the others must be refused.
+The fused epilogue's other float instantiations (gather 6; gather 3 at a run-time frame length) run in
+test_fused_ragged_on_other_instantiations.
 
 GMMs span K 1 / 2 / 31 / 64 and D 1 / 7 / 13 / 16 (seed 100 K + D); every speaker result must equal the reference exactly."""
 import numpy as np
@@ -283,6 +285,43 @@ def test_outside_the_fused_shape(torch_cuda, i):
     got = net.classify_signal_batch(plan, torch.from_numpy(np.stack(clips)).cuda()).cpu().numpy()
     want = [ref.prob(x) for x in mats]
     _check_p(got, [p for p, _b in want], [b for _p, b in want], f"model {i} {STOP_MODELS[i]} uniform batch")
+
+
+# the fused epilogue's other two float instantiations (stop_kernel_of, mfcc_kernels.hip): gather 6 and gather 3 with the run-time
+# frame length -- name -> (default_config overrides, (dct_split, dct_len, mel_gather) the plan must select)
+FUSED_OTHER_SHAPES = {"mels32": (dict(n_mels=32), (4, 10, 6)), "flen320": (dict(frame_length=320), (4, 10, 3))}
+
+
+@pytest.mark.parametrize("which", list(FUSED_OTHER_SHAPES))
+def test_fused_ragged_on_other_instantiations(torch_cuda, which):
+    """classify_signal_ragged -- it refuses rather than falling back, so the fused epilogue ran -- with a 13-coefficient model on a
+    32-filter bank (<4,10,6,0,...,2>) and on the default bank at frame length 320 (<4,10,3,0,...,2>): clips of max_frames - 1 ..
+    max_frames + 3 frames and one of a single frame, in seeded order; the reference runs on plan.clips' MFCC"""
+    import ctypes as C
+    import dsp_amd
+    from dsp_amd import lib as L
+    torch = torch_cuda
+    over, shape = FUSED_OTHER_SHAPES[which]
+    nc, mf, units = 13, 17, (4, 3, 2, 1)
+    plan = dsp_amd.MfccPlan(dsp_amd.default_config(**over))
+    t = L.LaneTables512()
+    assert plan._L.dsp_mfcc_lane_tables(C.byref(plan.cfg), C.byref(t), C.sizeof(t)) == 0
+    assert (t.dct_split, t.dct_len, t.mel_gather) == shape
+    frame = plan.cfg.frame_length
+    rng = np.random.default_rng(2100 + len(which))
+    lens = [frame + (k - 1) * HOP + int(rng.integers(0, HOP)) for k in (mf - 1, mf, mf, mf + 3, 1, mf + 1)]
+    clips = _noise_clips(rng, lens)
+    mats = [plan.clips(torch.from_numpy(c).cuda()[None], mf)[0].cpu().numpy() for c in clips]
+    assert [x.shape[0] for x in mats] == [mf - 1, mf, mf, mf, 1, mf]
+    allm = np.concatenate(mats)
+    m = R.random_stop_model(rng, nc, mf, units, allm.mean(axis=0), allm.std(axis=0) + 1e-3)
+    m = R.fit_biases(rng, m, mats)
+    net, ref = dsp_amd.StopModel(m), R.StopNet(m)
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    got = net.classify_signal_ragged(plan, torch.from_numpy(np.concatenate(clips)).cuda(), offsets).cpu().numpy()
+    want = [ref.prob(x) for x in mats]
+    _check_p(got, [p for p, _b in want], [b for _p, b in want], f"fused ragged on {which} {shape}")
+    _not_vacuous([got])
 
 
 # ---- speaker GMM ------------------------------------------------------------------------------------------------------------

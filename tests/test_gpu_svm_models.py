@@ -167,6 +167,48 @@ def test_fused512_float_and_ragged(torch_cuda, n_mfcc, n_sv):
     _check("fused512 ragged", attrs, feat, labels, dec, p1, f"fused 512 ragged n_mfcc {n_mfcc} n_sv {n_sv}")
 
 
+# launch_mfcc512_pool expands every shape of DSP_FOR_SHAPES; default_config(n_mfcc=...) reaches (4,10,3) and (2,20,3) only.
+# name -> (default_config overrides, (dct_split, dct_len, mel_gather) the plan must select)
+FUSED512_SHAPES = {"mels41": (dict(n_mels=41, n_mfcc=13), (4, 16, 3)), "mels32": (dict(n_mels=32), (4, 10, 6)),
+                   "mels17_mfcc17": (dict(n_mels=17, n_mfcc=17), (2, 20, 6))}
+
+
+@pytest.mark.parametrize("which", list(FUSED512_SHAPES))
+def test_fused512_other_instantiations(torch_cuda, which):
+    """the clip -> label kernel on an LDS-resident DCT operand (4,16,3), on gather 6 (4,10,6) and on both with two coefficient
+    tiles (2,20,6), against the two-step chain plan.clips -> mfcc_stats -> predict: its features, labels, decisions and P(1) are
+    the chain's bit for bit (as tests/test_gpu_scrubjay.py holds for the default bank), and both are within the reference's bound"""
+    torch = torch_cuda
+    import dsp_amd
+    from dsp_amd import lib as L
+    from dsp_amd import scrubjay
+    over, shape = FUSED512_SHAPES[which]
+    cfg = dsp_amd.default_config(**over)
+    t = L.LaneTables512()
+    assert dsp_amd.load().dsp_mfcc_lane_tables(C.byref(cfg), C.byref(t), C.sizeof(t)) == 0
+    assert (t.dct_split, t.dct_len, t.mel_gather) == shape and 2 * cfg.n_mfcc <= 64
+    rng = np.random.default_rng(5120 + 131 * cfg.n_mels + cfg.n_mfcc)
+    clips = torch.from_numpy(np.stack(_noise(rng, [8000] * 40))).cuda()
+    attrs = R.svm_from_features(rng, _plan_features(torch, cfg, clips), 65)
+    sj = scrubjay.ScrubJay(attrs, config=cfg)
+    fused = [a.cpu().numpy() for a in sj(clips)]
+    chain = [a.cpu().numpy() for a in sj(clips, fused=False)]
+    for a, b, what in zip(fused, chain, ("labels", "decision", "P(1)", "features")):
+        assert np.array_equal(a, b), f"fused 512 {which}: {what} differ from the two-step chain's"
+    labels, dec, p1, feat = fused
+    _check("fused512 shapes", attrs, feat, labels, dec, p1, f"fused 512 {which} {shape}")
+    sig, off = _ragged(torch, _noise(rng, rng.integers(400, 16000, 24).tolist()))
+    pre = scrubjay.ScrubJay(R.random_svm(rng, 2 * cfg.n_mfcc, 1, 0.1), config=cfg).ragged(sig, off)[3].cpu().numpy()
+    attrs = R.svm_from_features(rng, pre, 65)
+    sj = scrubjay.ScrubJay(attrs, config=cfg)
+    labels, dec, p1, feat = (a.cpu().numpy() for a in sj.ragged(sig, off))
+    _check("fused512 shapes ragged", attrs, feat, labels, dec, p1, f"fused 512 ragged {which} {shape}")
+    for c in (0, 11, 23):                                    # and clip by clip against the chain
+        one = [a.cpu().numpy() for a in sj(sig[off[c]:off[c + 1]].clone()[None], fused=False)]
+        for a, b in zip((labels, dec, p1, feat), one):
+            assert np.array_equal(a[c], b[0]), f"fused 512 ragged {which} clip {c}"
+
+
 @pytest.mark.parametrize("n_mfcc", [13, 20])
 def test_fused512_int16(torch_cuda, n_mfcc):
     """the two int16 shapes: mono, stereo channel 0, stereo average; equal-length and ragged batches"""
