@@ -10,6 +10,7 @@
   SpeakerFrontEnd   extract_features_from_array, a batch at once  2fa/audio/speaker/gmm_utils.py:47-61
   SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
   SpeakerVerifier   score_models / evaluate_dir (float GMMs)      2fa/audio/speaker/gmm_utils.py:99-126, evaluate_gmm.py
+  Segmenter      segments on top of any scan's window scores (no counterpart in the reference: its callers threshold one window)
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
@@ -662,6 +663,100 @@ class SpeakerVerifier:
                                                          n_spk, *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
                    "dsp_speaker_float_scan_device")
         return out
+
+
+def _segment_config(on, off, min_windows, max_gap, exclusive):
+    on = float(on)
+    off = on if off is None else float(off)
+    min_windows, max_gap = int(min_windows), int(max_gap)
+    if on != on or off != off or off > on:
+        raise ValueError("on and off must not be NaN, and off <= on")
+    if min_windows < 1 or max_gap < 0:
+        raise ValueError("min_windows must be >= 1 and max_gap >= 0")
+    return _lib.SegmentConfig(on, off, min_windows, max_gap, _lib.SEG_EXCLUSIVE if exclusive else _lib.SEG_INDEPENDENT)
+
+
+def _window_offsets(window_offsets):
+    wo = np.ascontiguousarray(np.asarray(window_offsets, dtype=np.int64))
+    if wo.ndim != 1 or wo.size < 1:
+        raise ValueError("window_offsets must hold n_recordings + 1 windows")
+    if wo[0] < 0 or (wo.size > 1 and (np.diff(wo) < 0).any()):
+        raise ValueError("window_offsets must be non-negative and non-decreasing")
+    return wo
+
+
+def segments_capacity(window_offsets, n_columns: int = 1, min_windows: int = 1, max_gap: int = 0) -> int:
+    """Host only: the most segments Segmenter.segments can find (dsp_segments_capacity): n_columns times the sum over recordings of
+    (W_r + max_gap + 1) // (min_windows + max_gap + 1)."""
+    cfg = _segment_config(0.0, 0.0, min_windows, max_gap, False)
+    wo = _window_offsets(window_offsets)
+    return _lib.check(_lib.load().dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_LP), wo.size - 1, int(n_columns)), "dsp_segments_capacity")
+
+
+def segment_sample_spans(cfg, offsets, segments, window_frames: int, hop_frames: int):
+    """Host only: (starts, lengths) int64 [n_segments], each segment in samples from its first window's start to its last window's end
+    (dsp_segment_sample_spans): cfg the MfccConfig of the plan that made the rows, offsets the recordings' sample offsets, segments
+    what Segmenter.segments returned (the numpy records)."""
+    scan = _scan_config(window_frames, hop_frames)
+    off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
+    segs = np.ascontiguousarray(segments, dtype=np.dtype(_lib.SEGMENT_DTYPE))
+    starts, lengths = np.zeros(segs.size, np.int64), np.zeros(segs.size, np.int64)
+    _lib.check(_lib.load().dsp_segment_sample_spans(C.byref(cfg), C.byref(scan), off, n, segs.ctypes.data, segs.size, starts.ctypes.data_as(_LP),
+                                                    lengths.ctypes.data_as(_LP)), "dsp_segment_sample_spans")
+    return starts, lengths
+
+
+class Segmenter:
+    """dsp_segmenter: segments from the window scores of any scan -- hysteresis between two thresholds, runs joined over short gaps,
+    short segments dropped -- found on the GPU in (recording, column, first_window) order.  One stream at a time per segmenter."""
+
+    CAP = 1 << 20          # segments the first call makes room for at most; a second call follows when more are found
+
+    def __init__(self, device: int = 0):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_segmenter_create(int(device), C.byref(h)), "dsp_segmenter_create")
+        self._h, self.device = h, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_segmenter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def segments(self, scores, window_offsets, on, off=None, min_windows: int = 1, max_gap: int = 0, exclusive: bool = False, as_tensor: bool = False):
+        """scores: cuda float32 [Wt] or [Wt][S] (a scan's prob, prob1, decision or llr as it is), recording r = windows [window_offsets[r],
+        window_offsets[r + 1]) (scan_window_offsets); a window with score >= on switches its track on, one with not (score >= off) off
+        (off defaults to on); runs at most max_gap windows apart are joined, spans below min_windows dropped; exclusive: only the best
+        column of a window counts -> numpy records (recording, column, first_window, n_windows, n_active, peak_window, peak, mean), or
+        with as_tensor the same 32 bytes per segment as a cuda int32 [n][8] (peak and mean: .view(torch.float32) of columns 6 and 7)."""
+        import torch
+        cfg = _segment_config(on, off, min_windows, max_gap, exclusive)
+        wo = _window_offsets(window_offsets)
+        scores, n_col = _lib.scores_device(scores, self.device)
+        if int(wo[-1]) > scores.shape[0]:
+            raise ValueError("window_offsets run past the end of scores")
+        dev, n = scores.device, wo.size - 1
+        if n == 0 or wo[-1] == wo[0]:                       # (no window: nothing to launch, and an empty tensor has no address)
+            out = torch.zeros((0, 8), dtype=torch.int32, device=dev)
+            return out if as_tensor else np.zeros(0, np.dtype(_lib.SEGMENT_DTYPE))
+        total = torch.zeros(2, dtype=torch.int64, device=dev)
+        room = min(_lib.check(self._L.dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_LP), n, n_col), "dsp_segments_capacity"), self.CAP)
+        for _ in range(2):
+            out = torch.empty((room, 8), dtype=torch.int32, device=dev)
+            _lib.check(self._L.dsp_segments_device(self._h, scores.data_ptr(), n, wo.ctypes.data_as(_LP), n_col, C.byref(cfg), out.data_ptr(), room, None,
+                                                   total.data_ptr(), _stream(scores)), "dsp_segments_device")
+            found = int(total[0])
+            if found <= room:
+                break
+            room = found
+        out = out[:found]
+        return out if as_tensor else out.cpu().numpy().view(np.dtype(_lib.SEGMENT_DTYPE)).reshape(-1)
 
 
 class UbmTrainer:

@@ -126,6 +126,24 @@ class ScanConfig(C.Structure):
     _fields_ = [("window_frames", C.c_int), ("hop_frames", C.c_int)]
 
 
+class SegmentConfig(C.Structure):
+    """dsp_segment_config (include/dsp_amd.h): thresholds, minimum length, gap and mode of dsp_segments_device."""
+
+    _fields_ = [("on", C.c_float), ("off", C.c_float), ("min_windows", C.c_int), ("max_gap", C.c_int), ("mode", C.c_int)]
+
+
+class Segment(C.Structure):
+    """dsp_segment (include/dsp_amd.h), 32 bytes; SEGMENT_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("recording", C.c_int), ("column", C.c_int), ("first_window", C.c_int), ("n_windows", C.c_int), ("n_active", C.c_int),
+                ("peak_window", C.c_int), ("peak", C.c_float), ("mean", C.c_float)]
+
+
+SEG_INDEPENDENT, SEG_EXCLUSIVE = 0, 1
+SEGMENT_DTYPE = [("recording", "<i4"), ("column", "<i4"), ("first_window", "<i4"), ("n_windows", "<i4"), ("n_active", "<i4"), ("peak_window", "<i4"),
+                 ("peak", "<f4"), ("mean", "<f4")]
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -191,6 +209,7 @@ SYMBOLS = [
     "dsp_kmeans_seed_device", "dsp_kmeans_fit_device", "dsp_kmeans_train_ubm_device",
     "dsp_speaker_verifier_create", "dsp_speaker_verifier_destroy", "dsp_speaker_verify_ragged_device",
     "dsp_speaker_float_scan_device",
+    "dsp_segmenter_create", "dsp_segmenter_destroy", "dsp_segments_capacity", "dsp_segments_device", "dsp_segment_sample_spans",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -360,6 +379,12 @@ def load() -> C.CDLL:
     L.dsp_speaker_verify_ragged_device.restype = ip
     L.dsp_speaker_float_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
     L.dsp_speaker_float_scan_device.restype = ip
+    sgp = C.POINTER(SegmentConfig)
+    L.dsp_segmenter_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_segmenter_create.restype = ip
+    L.dsp_segmenter_destroy.argtypes = [vp]; L.dsp_segmenter_destroy.restype = None
+    L.dsp_segments_capacity.argtypes = [sgp, lp, C.c_long, C.c_long]; L.dsp_segments_capacity.restype = C.c_long
+    L.dsp_segments_device.argtypes = [vp, vp, C.c_long, lp, C.c_long, sgp, vp, C.c_long, vp, vp, vp]; L.dsp_segments_device.restype = ip
+    L.dsp_segment_sample_spans.argtypes = [cfgp, scp, lp, C.c_long, vp, C.c_long, lp, lp]; L.dsp_segment_sample_spans.restype = C.c_long
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip
@@ -450,6 +475,20 @@ def ragged_signal(signal, offsets, float_dtype):
     if n and int(off[n]) > signal.shape[0]:
         raise ValueError("offsets run past the end of the signal")
     return off, n, channels, signal.data_ptr()
+
+
+def scores_device(scores, device: int):
+    """Window scores on the GPU: a float32 CUDA tensor [Wt] or [Wt][S] (S >= 1) on GPU `device`, made contiguous -> (scores, S), or
+    ValueError."""
+    import torch
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() in (1, 2)):
+        raise ValueError("scores must be a float32 CUDA tensor [Wt] or [Wt][S]")
+    if scores.device.index != device:
+        raise ValueError(f"scores are on GPU {scores.device.index}, the segmenter on GPU {device}")
+    n_col = scores.shape[1] if scores.dim() == 2 else 1
+    if n_col < 1:
+        raise ValueError("scores must have at least one column")
+    return scores.contiguous(), n_col
 
 
 def check(rc: int, what: str) -> int:

@@ -964,7 +964,8 @@ int dsp_speaker_verify_ragged_device(dsp_speaker_verifier *v, const float *d_fea
  * on the same stream; the outputs do not change.  Rows that lie in no window (hop_frames > window_frames, the tail behind a
  * recording's last window) are not scored.
  * Not covered: stream sessions (sliding CMVN looks ahead) and a scanner from audio (under the speaker plan a recording's rows depend
- * on the whole recording: compute its features, then scan -- INTEGRATION.md 6i), thresholds and segments on top of the scores. */
+ * on the whole recording: compute its features, then scan -- INTEGRATION.md 6i).  Thresholds and segments on top of the scores:
+ * dsp_segments_device below. */
 int dsp_speaker_float_scan_device(dsp_speaker_verifier *v, const float *d_feats, long n_recordings, const long *frame_offsets,
                                   const dsp_scan_config *cfg, const float *d_means, long n_speakers,
                                   float *d_llr,        /* [Wt][S]                 */
@@ -973,6 +974,71 @@ int dsp_speaker_float_scan_device(dsp_speaker_verifier *v, const float *d_feats,
                                   int *d_best,         /* [Wt]     may be NULL    */
                                   float *d_best_llr,   /* [Wt]     may be NULL    */
                                   void *stream);
+
+/* SEGMENTS FROM WINDOW SCORES: hysteresis, gap merge, minimum length -- "speaker 17, recording 4, windows 7510 .. 7780" instead of one
+ * number per window.  Every scan above feeds it unchanged: d_scores[Wt][S] float32, row-major, the
+ * windows of all recordings back to back as window_offsets (the HOST array dsp_scan_window_offsets fills, read before the call returns)
+ * says -- S = 1 for d_prob of the stop scans and d_prob1 / d_decision of the SVM scan, S = n_speakers for d_llr of the float scan.
+ *
+ * A track is one (recording r, column s): x[w], w = 0 .. W_r - 1.
+ *   1. e[w] = x[w] (DSP_SEG_INDEPENDENT), or x[w] where s is the row's best column and -inf elsewhere (DSP_SEG_EXCLUSIVE).  The best
+ *      column is the smallest that attains the maximum of the row's non-NaN entries -- the scan's d_best; a row of NaN has none.
+ *   2. state[-1] = 0; state[w] = 1 if e[w] >= on; 0 if !(e[w] >= off) (NaN lands here); else state[w - 1].
+ *   3. A run is a maximal stretch of state 1.
+ *   4. Consecutive runs with at most max_gap windows between them are joined, the gap included -- once, before anything is dropped.
+ *   5. What spans n_windows = last - first + 1 < min_windows is dropped; its neighbours are not joined again.
+ *   6. Per survivor, over its ACTIVE windows (state 1: never NaN, never masked): n_active, peak = max x, peak_window = the first window
+ *      that attains it (an index within the recording), mean = (float)(float64 sum of x / n_active).
+ * The output is ordered by (recording, column, first_window) through prefix sums of the per-track counts: no atomic places a segment,
+ * and every field of every segment is the same bits whatever the batch, the recording's position in it, the other columns
+ * (DSP_SEG_INDEPENDENT), max_segments, the outputs asked for, the stream and what the workspace held.  The float64 sum is taken in an
+ * order that depends on the segment alone.
+ *
+ * d_segments may be NULL (max_segments ignored): count only.  When more segments are found than max_segments, the first max_segments
+ * in output order are written and nothing behind them; d_total[0] = segments found, d_total[1] = segments written, both on the device.
+ * d_track_counts[n_recordings][n_columns] (may be NULL) = survivors per track.  Everything is enqueued on `stream`; nothing waits.
+ * The segmenter owns a grow-only workspace (Wt S / 4 bytes and 24 bytes per 512 windows of a track): ONE stream at a time per segmenter.
+ *
+ * DSP_EINVAL, before a device is touched: cfg NULL; on or off NaN, or off > on; min_windows < 1; max_gap < 0; an unknown mode; a NULL
+ * d_scores, window_offsets or d_total; offsets that are negative or decrease; n_columns < 1 or > 2^19; a non-NULL d_segments with
+ * max_segments < 0; a recording of 2^31 windows or more; 2^31 tracks or more.  n_recordings == 0: DSP_OK, no launch, and d_total is
+ * NOT written (nothing is enqueued: zero it beforehand where it is read regardless).  A recording without windows is legal and
+ * yields nothing.
+ *
+ * dsp_segments_capacity (host only): the most segments a call can find, sum over recordings of S floor((W_r + max_gap + 1) /
+ * (min_windows + max_gap + 1)) -- k survivors of one track need k min_windows + (k - 1) (max_gap + 1) <= W_r windows; < 0: DSP_E*.
+ * dsp_segment_sample_spans (host only): starts / lengths[n_segments] (either may be NULL) = each segment in samples, from the start of
+ * its first window to the end of its last, absolute positions in the buffer (offsets as dsp_mfcc_clips_ragged_device).  The windows
+ * are dsp_scan_window_spans' under DSP_FRAMING_COMPLETE and DSP_FRAMING_STREAM; under DSP_FRAMING_CENTER (the speaker plan, which
+ * dsp_scan_window_spans refuses) row i covers samples [i hop_length - frame_length / 2, i hop_length + frame_length / 2) and a window its
+ * rows' union, clipped to the recording.  A segment outside its recording's windows is DSP_EINVAL; returns n_segments.
+ * Not covered: a threshold per column, int64 Q8 scores (dsp_speaker_scan_device's: convert to float, exact below 2^24), segments
+ * carried across the pushes of a stream session.                                                                                    */
+#define DSP_SEG_INDEPENDENT 0
+#define DSP_SEG_EXCLUSIVE 1
+typedef struct dsp_segment_config {
+    float on;            /* a window with score >= on switches its track on                          */
+    float off;           /* a window with !(score >= off) switches it off; off <= on                 */
+    int   min_windows;   /* >= 1: segments spanning fewer windows are dropped                        */
+    int   max_gap;       /* >= 0: runs of one track separated by <= max_gap off windows are joined   */
+    int   mode;          /* DSP_SEG_INDEPENDENT | DSP_SEG_EXCLUSIVE                                  */
+} dsp_segment_config;
+typedef struct dsp_segment {          /* 32 bytes */
+    int recording, column, first_window, n_windows, n_active, peak_window;
+    float peak, mean;
+} dsp_segment;
+typedef struct dsp_segmenter dsp_segmenter;
+int dsp_segmenter_create(int device, dsp_segmenter **out);
+void dsp_segmenter_destroy(dsp_segmenter *s);
+long dsp_segments_capacity(const dsp_segment_config *cfg, const long *window_offsets, long n_recordings, long n_columns);
+int dsp_segments_device(dsp_segmenter *s, const float *d_scores, long n_recordings, const long *window_offsets, long n_columns,
+                        const dsp_segment_config *cfg,
+                        dsp_segment *d_segments, long max_segments,   /* may be NULL / 0: count only            */
+                        int *d_track_counts,                          /* [n_recordings][n_columns], may be NULL */
+                        long *d_total,                                /* [2]: segments found, segments written  */
+                        void *stream);
+long dsp_segment_sample_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config *scan, const long *offsets, long n_recordings,
+                              const dsp_segment *segments, long n_segments, long *starts, long *lengths);
 
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
