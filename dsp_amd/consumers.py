@@ -11,6 +11,7 @@
   SpeakerEnroller   map_adapt_gmm (means only)                  2fa/audio/speaker/adapt_ubm.py:72-86, 2fa/audio/adapt_ubm.py:97-110
   SpeakerVerifier   score_models / evaluate_dir (float GMMs)      2fa/audio/speaker/gmm_utils.py:99-126, evaluate_gmm.py
   Segmenter      segments on top of any scan's window scores (no counterpart in the reference: its callers threshold one window)
+  TrialEvaluator   the threshold sweep, roc_curve and auc         2fa/audio/speaker/evaluate_gmm.py:73-81, generate_charts.py:52-54,68-69
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
@@ -757,6 +758,130 @@ class Segmenter:
             room = found
         out = out[:found]
         return out if as_tensor else out.cpu().numpy().view(np.dtype(_lib.SEGMENT_DTYPE)).reshape(-1)
+
+
+class TrialEvaluator:
+    """dsp_trial_evaluator: labelled trials on the GPU -- per column of a score matrix and pooled, the reference's threshold sweep
+    (evaluate_gmm.py:77-81), the exact ROC step curve as counts and the AUC (generate_charts.py:68-69).  One stream at a time per
+    evaluator."""
+
+    WANT = ("columns", "sweep", "roc")
+
+    def __init__(self, device: int = 0):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_trial_evaluator_create(int(device), C.byref(h)), "dsp_trial_evaluator_create")
+        self._h, self.device = h, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_trial_evaluator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def evaluate(self, scores, truth, n_thresholds: int = 200, want=("columns", "sweep", "roc")):
+        """scores: cuda float32 [T] or [T][S] (SpeakerVerifier.verify(...)["llr"] or .scan(...)["llr"] as it is); truth: T integers on
+        the host, the column that is the row's true speaker or -1 -> a dict with n_thresholds and, as `want` names them,
+          "columns": columns, numpy records [S + 1] (TRIAL_COLUMN_DTYPE), the last one pooled;
+          "sweep":   sweep_tp, sweep_fp int64 [S + 1][n_thresholds] (the thresholds: trial_thresholds(lo, hi, n_thresholds));
+          "roc":     target_offsets int64 [S + 1], target_rows int64 [targets], target_scores float32 [targets], fa_above and fa_equal
+                     int32 [targets] (roc_points turns a column's into a curve).
+        A matrix without rows is a ValueError here (there is nothing to return), where dsp_trials_evaluate_device answers DSP_OK and
+        launches nothing."""
+        import torch
+        want = tuple(want)
+        if not want or any(key not in self.WANT for key in want):
+            raise ValueError(f"want must name at least one of {self.WANT}")
+        n = int(n_thresholds)
+        if n < 2 or n > 1024:
+            raise ValueError("n_thresholds must be 2 .. 1024")
+        scores, n_col = _lib.scores_device(scores, self.device, "evaluator")
+        n_rows = scores.shape[0]
+        if n_rows < 1:
+            raise ValueError("scores hold no trial")
+        tr = np.ascontiguousarray(np.asarray(truth), dtype=np.intc)
+        if tr.ndim != 1 or tr.size != n_rows:
+            raise ValueError(f"truth must hold one column index (or -1) per row of scores: {n_rows}")
+        if ((tr < -1) | (tr >= n_col)).any():
+            raise ValueError(f"truth[{int(np.flatnonzero((tr < -1) | (tr >= n_col))[0])}] is neither -1 nor a column")
+        tp = tr.ctypes.data_as(C.POINTER(C.c_int))
+        dev, out, ptr = scores.device, {"n_thresholds": n}, {}
+        if "columns" in want:
+            cols = torch.empty((n_col + 1, 10), dtype=torch.int64, device=dev)
+            ptr["columns"] = cols.data_ptr()
+        if "sweep" in want:
+            tps, fps = (torch.empty((n_col + 1, n), dtype=torch.int64, device=dev) for _ in range(2))
+            ptr["tp"], ptr["fp"] = tps.data_ptr(), fps.data_ptr()
+        if "roc" in want:
+            offsets = np.zeros(n_col + 1, np.int64)
+            n_tgt = _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, offsets.ctypes.data_as(_LP), None), "dsp_trials_target_offsets")
+            rows = np.zeros(n_tgt, np.int64)
+            _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, None, rows.ctypes.data_as(_LP)), "dsp_trials_target_offsets")
+            above, equal = (torch.empty(max(n_tgt, 1), dtype=torch.int32, device=dev) for _ in range(2))   # (an empty tensor has no address)
+            ptr["above"], ptr["equal"] = above.data_ptr(), equal.data_ptr()
+        cfg = _lib.TrialsConfig(n)
+        _lib.check(self._L.dsp_trials_evaluate_device(self._h, scores.data_ptr(), n_rows, n_col, tp, C.byref(cfg),
+                                                      *[ptr.get(key) for key in ("columns", "tp", "fp", "above", "equal")], _stream(scores)),
+                   "dsp_trials_evaluate_device")
+        if "columns" in want:
+            out["columns"] = cols.cpu().numpy().view(np.dtype(_lib.TRIAL_COLUMN_DTYPE)).reshape(-1)
+        if "sweep" in want:
+            out["sweep_tp"], out["sweep_fp"] = tps.cpu().numpy(), fps.cpu().numpy()
+        if "roc" in want:
+            flat = scores.reshape(n_rows, n_col)
+            at = torch.from_numpy(rows).to(dev)
+            out.update(target_offsets=offsets, target_rows=rows, fa_above=above[:n_tgt].cpu().numpy(), fa_equal=equal[:n_tgt].cpu().numpy(),
+                       target_scores=flat[at, torch.from_numpy(tr[rows].astype(np.int64)).to(dev)].cpu().numpy())
+        return out
+
+
+def trial_thresholds(lo, hi, n: int) -> np.ndarray:
+    """Host only: the n thresholds of the sweep between a column's lo and hi, float64 -- np.linspace(lo, hi, n) as
+    evaluate_gmm.py:77 calls it: i * ((hi - lo) / (n - 1)) + lo in two roundings, the last one hi itself."""
+    n = int(n)
+    if n < 2 or n > 1024:
+        raise ValueError("n must be 2 .. 1024")
+    lo, hi = np.float64(lo), np.float64(hi)
+    with np.errstate(invalid="ignore"):
+        t = np.arange(n, dtype=np.float64) * ((hi - lo) / np.float64(n - 1)) + lo
+    t[-1] = hi
+    return t
+
+
+def roc_points(result: dict, column: int):
+    """Host only: (fpr, tpr, thresholds) of one column from TrialEvaluator.evaluate(..., want=("columns", "roc")), laid out as
+    sklearn.metrics.roc_curve(labels, scores, drop_intermediate=False) returns them -- thresholds descending from inf, the point (0, 0)
+    first, "accept when x >= threshold" -- with the corners of the exact step curve only.  Every distinct target score v gives the
+    point (above + equal, targets >= v) at threshold v, and where non-targets lie between v and the target score before it, the
+    corner (above, targets > v) in front of it, at the float32 next above v ("accept when x > v").  sklearn's further points, at
+    scores that only non-targets have, lie on the horizontal stretches between these and carry no area.  Where the last point is not
+    (1, 1) already, (1, 1) at -inf closes the curve.  A column without targets or without non-targets has rates of NaN, as sklearn's."""
+    for key in ("columns", "target_offsets", "fa_above", "fa_equal", "target_scores"):
+        if key not in result:
+            raise ValueError('roc_points needs a result of want=("columns", "roc")')
+    column = int(column)
+    if column < 0 or column >= result["target_offsets"].size - 1:
+        raise ValueError("no such column")
+    a, b = (int(v) for v in result["target_offsets"][column:column + 2])
+    x, above, equal = result["target_scores"][a:b], result["fa_above"][a:b].astype(np.int64), result["fa_equal"][a:b].astype(np.int64)
+    keep = x == x
+    x, above, equal = x[keep].astype(np.float32), above[keep], equal[keep]
+    n_tgt, n_non = int(result["columns"]["n_target"][column]), int(result["columns"]["n_nontarget"][column])
+    neg, first, count = np.unique(-x.astype(np.float64), return_index=True, return_counts=True)      # descending scores
+    tps, fps, thr = [0], [0], [np.inf]
+    for v, j, c in zip(-neg, first, count):
+        if above[j] > fps[-1]:
+            tps, fps, thr = tps + [tps[-1]], fps + [int(above[j])], thr + [float(np.nextafter(np.float32(v), np.float32(np.inf)))]
+        tps, fps, thr = tps + [tps[-1] + int(c)], fps + [int(above[j] + equal[j])], thr + [float(v)]
+    if fps[-1] < n_non or len(thr) == 1:
+        tps, fps, thr = tps + [n_tgt], fps + [n_non], thr + [-np.inf]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.array(fps, np.float64) / np.float64(n_non), np.array(tps, np.float64) / np.float64(n_tgt), np.array(thr, np.float64)
 
 
 class UbmTrainer:

@@ -144,6 +144,24 @@ SEGMENT_DTYPE = [("recording", "<i4"), ("column", "<i4"), ("first_window", "<i4"
                  ("peak", "<f4"), ("mean", "<f4")]
 
 
+class TrialsConfig(C.Structure):
+    """dsp_trials_config (include/dsp_amd.h): the thresholds of the sweep of dsp_trials_evaluate_device."""
+
+    _fields_ = [("n_thresholds", C.c_int)]
+
+
+class TrialColumn(C.Structure):
+    """dsp_trial_column (include/dsp_amd.h), 80 bytes; TRIAL_COLUMN_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("n_target", C.c_long), ("n_nontarget", C.c_long), ("n_nan", C.c_long), ("lo", C.c_double), ("hi", C.c_double),
+                ("best_threshold", C.c_double), ("best_correct", C.c_long), ("auc_u2", C.c_long), ("auc", C.c_double), ("best_index", C.c_int),
+                ("reserved", C.c_int)]
+
+
+TRIAL_COLUMN_DTYPE = [("n_target", "<i8"), ("n_nontarget", "<i8"), ("n_nan", "<i8"), ("lo", "<f8"), ("hi", "<f8"), ("best_threshold", "<f8"),
+                      ("best_correct", "<i8"), ("auc_u2", "<i8"), ("auc", "<f8"), ("best_index", "<i4"), ("reserved", "<i4")]
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -210,6 +228,7 @@ SYMBOLS = [
     "dsp_speaker_verifier_create", "dsp_speaker_verifier_destroy", "dsp_speaker_verify_ragged_device",
     "dsp_speaker_float_scan_device",
     "dsp_segmenter_create", "dsp_segmenter_destroy", "dsp_segments_capacity", "dsp_segments_device", "dsp_segment_sample_spans",
+    "dsp_trials_target_offsets", "dsp_trials_pairs", "dsp_trial_evaluator_create", "dsp_trial_evaluator_destroy", "dsp_trials_evaluate_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -385,6 +404,13 @@ def load() -> C.CDLL:
     L.dsp_segments_capacity.argtypes = [sgp, lp, C.c_long, C.c_long]; L.dsp_segments_capacity.restype = C.c_long
     L.dsp_segments_device.argtypes = [vp, vp, C.c_long, lp, C.c_long, sgp, vp, C.c_long, vp, vp, vp]; L.dsp_segments_device.restype = ip
     L.dsp_segment_sample_spans.argtypes = [cfgp, scp, lp, C.c_long, vp, C.c_long, lp, lp]; L.dsp_segment_sample_spans.restype = C.c_long
+    tip = C.POINTER(C.c_int)
+    L.dsp_trials_target_offsets.argtypes = [tip, C.c_long, C.c_long, lp, lp]; L.dsp_trials_target_offsets.restype = C.c_long
+    L.dsp_trials_pairs.argtypes = [tip, C.c_long, C.c_long]; L.dsp_trials_pairs.restype = C.c_long
+    L.dsp_trial_evaluator_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_trial_evaluator_create.restype = ip
+    L.dsp_trial_evaluator_destroy.argtypes = [vp]; L.dsp_trial_evaluator_destroy.restype = None
+    L.dsp_trials_evaluate_device.argtypes = [vp, vp, C.c_long, C.c_long, tip, C.POINTER(TrialsConfig), vp, vp, vp, vp, vp, vp]
+    L.dsp_trials_evaluate_device.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip
@@ -477,14 +503,14 @@ def ragged_signal(signal, offsets, float_dtype):
     return off, n, channels, signal.data_ptr()
 
 
-def scores_device(scores, device: int):
+def scores_device(scores, device: int, who: str = "segmenter"):
     """Window scores on the GPU: a float32 CUDA tensor [Wt] or [Wt][S] (S >= 1) on GPU `device`, made contiguous -> (scores, S), or
-    ValueError."""
+    ValueError.  `who` names the owner in the message: the segmenter, or the evaluator, whose rows are trials (Wt = T)."""
     import torch
     if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() in (1, 2)):
         raise ValueError("scores must be a float32 CUDA tensor [Wt] or [Wt][S]")
     if scores.device.index != device:
-        raise ValueError(f"scores are on GPU {scores.device.index}, the segmenter on GPU {device}")
+        raise ValueError(f"scores are on GPU {scores.device.index}, the {who} on GPU {device}")
     n_col = scores.shape[1] if scores.dim() == 2 else 1
     if n_col < 1:
         raise ValueError("scores must have at least one column")

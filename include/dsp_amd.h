@@ -1040,6 +1040,73 @@ int dsp_segments_device(dsp_segmenter *s, const float *d_scores, long n_recordin
 long dsp_segment_sample_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config *scan, const long *offsets, long n_recordings,
                               const dsp_segment *segments, long n_segments, long *starts, long *lengths);
 
+/* LABELLED TRIALS: threshold sweep, ROC counts, AUC -- the number every consumer of the scores above needs and none of them produces
+ * (2fa/audio/speaker/evaluate_gmm.py:73-81, generate_charts.py:52-54,68-69).  d_scores[T][S]
+ * float32, row-major, on the device: d_llr of dsp_speaker_verify_ragged_device (T clips) or of dsp_speaker_float_scan_device (T = Wt).
+ * truth[T] is a HOST array read before the call returns: truth[r] = the column that is row r's true speaker, -1: none of the enrolled.
+ *
+ * Trial (r, s) is a target trial when truth[r] == s and a non-target trial otherwise.  A NaN score takes its trial out of everything
+ * (it is counted in n_nan).  Per column s, P targets and N non-targets, both without the NaN ones:
+ *   1. Sweep.  lo / hi = min / max of the column's FINITE scores as float64, NaN without one (of -0 and +0, lo takes -0 and hi +0).
+ *      step = (hi - lo) / (n - 1); t_i = i step + lo for i < n - 1, two roundings, never a fused multiply-add; t_(n-1) = hi --
+ *      np.linspace(lo, hi, n), n = n_thresholds.  tp_i = the targets with (double)x > t_i, fp_i the non-targets (NaN thresholds:
+ *      zeros; +inf is above every threshold, -inf above none).  correct_i = tp_i + (N - fp_i); best_index = the smallest i that
+ *      attains the maximum (np.argmax), best_threshold = t_best_index, best_correct = that maximum.
+ *   2. ROC counts.  The target trials of all columns lie back to back in (column, row) order, column s at [target_offsets[s],
+ *      target_offsets[s + 1]) (dsp_trials_target_offsets; a NaN target keeps its place).  For target j of column s: fa_above[j] =
+ *      the non-targets of the column with x > x_j, fa_equal[j] = those with x == x_j; -1 and -1 for a NaN target.  That is the
+ *      exact step curve: at "accept when x >= x_j" the false accepts are above + equal.
+ *   3. AUC.  auc_u2 = sum over the non-NaN targets of 2 (N - above - equal) + equal -- twice the wins plus the ties, an int64;
+ *      auc = (double)auc_u2 / (double)(2 P N), NaN when P N == 0.
+ * Row S of d_columns and of the sweep is the POOLED row: lo / hi over every finite score of the matrix and the sweep over all T S
+ * trials (one threshold for the whole system); auc_u2 = the sum of the columns', auc = auc_u2 / (2 sum_s P_s N_s), the within-speaker
+ * AUC weighted by pairs.
+ *
+ * Every output is an integer count or one correctly rounded float64 operation on such counts and on lo / hi: all of them are the
+ * same bits whatever the other columns, the batch, the grid, the outputs asked for, the stream and what the workspace held.  The
+ * kernels add with integer atomics only.
+ *
+ * Any output may be NULL, not all of them; what no output needs is not launched: the sweep outputs alone count no pairs, the ROC
+ * arrays alone take no min / max and no histogram, d_columns needs both (and fills auc without the ROC arrays).  Everything is
+ * enqueued on `stream`; nothing waits.  The evaluator owns a grow-only workspace (32 bytes and 8 (n + 1) + 16 bytes per column, 12
+ * bytes per target): ONE stream at a time per evaluator.  dsp_trial_evaluator_create touches no device.
+ *
+ * DSP_EINVAL, before a device is touched, the first of: e NULL; cfg NULL; n_thresholds outside 2 .. 1024; n_columns outside
+ * 1 .. 2^19; n_rows < 0 or >= 2^31; every output NULL; (n_rows == 0: DSP_OK here, no launch, nothing written;) d_scores NULL; truth
+ * NULL; the first truth[r] < -1 or >= n_columns, named; 2^45 trials or more; and, where d_columns or a ROC array is asked for, more
+ * than 2^46 pairs of a target and a non-target (sum_s P_s (T - P_s), dsp_trials_pairs), with the number.  Pair counting is exact and
+ * its time grows with the pairs: the cap only bounds it, and nobody has measured a call at the cap -- tools/time_trials.py records
+ * the time per pair at the sizes it runs.
+ *
+ * dsp_trials_target_offsets (host only): target_offsets[S + 1] and target_rows[targets] (either may be NULL), the rows of column
+ * s's targets ascending; returns the number of targets (rows with truth >= 0).  dsp_trials_pairs (host only): sum_s P_s N_s before
+ * any NaN is known.  Both < 0: DSP_E*.
+ * The caps above bound the kernels' indices, not the memory a call takes; that is the caller's to size.  Per call the workspace holds
+ * and clears 8 S (n + 1) bytes of histograms -- 1.6 MB at 1 000 speakers and 200 thresholds, but 4.3 GB at S = 2^19 with n = 1024 --
+ * and the labels travel through 4 (T + targets) + 8 (S + 1) bytes of pinned host memory and as many on the device: 0.8 MB at 100 000
+ * clips, 16 GB near T = 2^31.  A workspace the device cannot give is DSP_ENOMEM, a pinned buffer the host cannot give DSP_EHIP.
+ * Not covered: a threshold per column in the segmenter, the duration calibration A llr + B + C log n of adapt_ubm.py:97-99, the
+ * equal error rate, pair counts pooled across columns.                                                                             */
+typedef struct dsp_trials_config { int n_thresholds; } dsp_trials_config;           /* 2 .. 1024; 200 = evaluate_gmm.py */
+typedef struct dsp_trial_column {                                                   /* 80 bytes: one per column, and one pooled */
+    long n_target, n_nontarget, n_nan;
+    double lo, hi, best_threshold;
+    long best_correct, auc_u2;
+    double auc;
+    int best_index, reserved;
+} dsp_trial_column;
+typedef struct dsp_trial_evaluator dsp_trial_evaluator;
+long dsp_trials_target_offsets(const int *truth, long n_rows, long n_columns, long *target_offsets, long *target_rows);
+long dsp_trials_pairs(const int *truth, long n_rows, long n_columns);
+int dsp_trial_evaluator_create(int device, dsp_trial_evaluator **out);
+void dsp_trial_evaluator_destroy(dsp_trial_evaluator *e);
+int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, long n_rows, long n_columns, const int *truth,
+                               const dsp_trials_config *cfg,
+                               dsp_trial_column *d_columns,           /* [S + 1]                        may be NULL */
+                               long *d_sweep_tp, long *d_sweep_fp,    /* [S + 1][n_thresholds]          may be NULL */
+                               int *d_fa_above, int *d_fa_equal,      /* [targets in all]               may be NULL */
+                               void *stream);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
