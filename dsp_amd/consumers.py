@@ -12,6 +12,8 @@
   SpeakerVerifier   score_models / evaluate_dir (float GMMs)      2fa/audio/speaker/gmm_utils.py:99-126, evaluate_gmm.py
   Segmenter      segments on top of any scan's window scores (no counterpart in the reference: its callers threshold one window)
   TrialEvaluator   the threshold sweep, roc_curve and auc         2fa/audio/speaker/evaluate_gmm.py:73-81, generate_charts.py:52-54,68-69
+  ScoreCalibrator   CAL_A * raw_score + CAL_B + CAL_C * log(n_frames), and the fit the reference leaves "to be learned on dev set"
+                                                              2fa/audio/speaker/adapt_ubm.py:27-28,97-99
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
@@ -882,6 +884,115 @@ def roc_points(result: dict, column: int):
         tps, fps, thr = tps + [n_tgt], fps + [n_non], thr + [-np.inf]
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.array(fps, np.float64) / np.float64(n_non), np.array(tps, np.float64) / np.float64(n_tgt), np.array(thr, np.float64)
+
+
+class ScoreCalibrator:
+    """dsp_calibrator: c = A x + B + C log(n_frames) on a score matrix on the GPU -- fit by prior-weighted logistic regression (damped
+    Newton, every pass and solve on the device) on labelled trials, and apply.  One stream at a time per calibrator."""
+
+    def __init__(self, device: int = 0):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_calibrator_create(int(device), C.byref(h)), "dsp_calibrator_create")
+        self._h, self.device = h, int(device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_calibrator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    @staticmethod
+    def duration_term(n_frames) -> np.ndarray:
+        """Host only: log(n_frames + 1e-8) as float64, exactly the values fit and apply use (dsp_calibration_duration_term)."""
+        nf = _frames(n_frames, None)
+        out = np.empty(nf.size, np.float64)
+        _lib.check(_lib.load().dsp_calibration_duration_term(nf.ctypes.data_as(_LP), nf.size, out.ctypes.data_as(C.POINTER(C.c_double))),
+                   "dsp_calibration_duration_term")
+        return out
+
+    def fit(self, scores, truth, n_frames=None, prior: float = 0.5, tol: float = 1e-10, max_iter: int = 100, init=None) -> dict:
+        """scores: cuda float32 [T] or [T][S]; truth: T integers on the host, the row's true column or -1; n_frames: T frame counts on
+        the host, or None for the two-parameter model (C stays 0); init: (a, b, c) or a dict with those keys, None: 1, 0, 0 -> the
+        report as a dict: a, b, c, params = (a, b, c), n_target, n_nontarget, n_excluded, objective_start, objective, last_step,
+        n_iter, n_rejected, status (lib.CAL_*) and status_name.  Waits for the stream once."""
+        if not (0.0 < float(prior) < 1.0):
+            raise ValueError("prior must lie inside (0, 1)")
+        if not float(tol) > 0.0:
+            raise ValueError("tol must be > 0")
+        if int(max_iter) < 1 or int(max_iter) > 10000:
+            raise ValueError("max_iter must be 1 .. 10000")
+        scores, n_col = _lib.scores_device(scores, self.device, "calibrator")
+        n_rows = scores.shape[0]
+        if n_rows < 1:
+            raise ValueError("scores hold no trial")
+        tr = np.ascontiguousarray(np.asarray(truth), dtype=np.intc)
+        if tr.ndim != 1 or tr.size != n_rows:
+            raise ValueError(f"truth must hold one column index (or -1) per row of scores: {n_rows}")
+        if ((tr < -1) | (tr >= n_col)).any():
+            raise ValueError(f"truth[{int(np.flatnonzero((tr < -1) | (tr >= n_col))[0])}] is neither -1 nor a column")
+        nf = _frames(n_frames, n_rows)
+        start = _calibration(init, nf is not None)
+        cfg, rep = _lib.CalibrationConfig(float(prior), float(tol), int(max_iter), 0), _lib.CalibrationReport()
+        _lib.check(self._L.dsp_calibration_fit_device(self._h, scores.data_ptr(), n_rows, n_col, tr.ctypes.data_as(C.POINTER(C.c_int)),
+                                                      nf.ctypes.data_as(_LP) if nf is not None else None, C.byref(cfg), C.byref(start), C.byref(rep),
+                                                      _stream(scores)), "dsp_calibration_fit_device")
+        out = {name: getattr(rep, name) for name, _ in _lib.CalibrationReport._fields_ if name not in ("params", "reserved")}
+        out.update(a=rep.params.a, b=rep.params.b, c=rep.params.c, params=(rep.params.a, rep.params.b, rep.params.c),
+                   status_name=_lib.CAL_STATUS[rep.status])
+        return out
+
+    def apply(self, scores, params, n_frames=None, out=None):
+        """scores: cuda float32 [T] or [T][S]; params: (a, b, c) or what fit returned; n_frames as in fit (None needs c == 0) -> the
+        calibrated scores, float32 of the same shape: a new tensor, or `out` (which may be `scores` itself).  Only enqueues."""
+        import torch
+        x, n_col = _lib.scores_device(scores, self.device, "calibrator")
+        n_rows = x.shape[0]
+        nf = _frames(n_frames, n_rows)
+        p = _calibration(params, nf is not None)
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+                  and out.device == x.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of the shape of scores, on their GPU")
+        if out is scores and x is not scores:
+            raise ValueError("scores must be contiguous to be calibrated in place")
+        if n_rows:
+            _lib.check(self._L.dsp_calibration_apply_device(self._h, x.data_ptr(), n_rows, n_col, nf.ctypes.data_as(_LP) if nf is not None else None,
+                                                            C.byref(p), out.data_ptr(), _stream(x)), "dsp_calibration_apply_device")
+        return out
+
+
+def _frames(n_frames, n_rows):
+    """n_frames as a contiguous int64 array (None stays None), or ValueError"""
+    if n_frames is None:
+        return None
+    nf = np.ascontiguousarray(np.asarray(n_frames), dtype=np.int64)
+    if nf.ndim != 1 or (n_rows is not None and nf.size != n_rows):
+        raise ValueError("n_frames must hold one frame count per row of scores")
+    if (nf < 0).any():
+        raise ValueError(f"n_frames[{int(np.flatnonzero(nf < 0)[0])}] is negative")
+    return nf
+
+
+def _calibration(params, with_frames: bool):
+    """(a, b, c), a dict with those keys (what ScoreCalibrator.fit returned) or None (1, 0, 0) -> lib.Calibration, or ValueError"""
+    if params is None:
+        a, b, c = 1.0, 0.0, 0.0
+    elif isinstance(params, dict):
+        a, b, c = (float(params[key]) for key in ("a", "b", "c"))
+    else:
+        a, b, c = (float(v) for v in params)
+    if not all(np.isfinite(v) for v in (a, b, c)):
+        raise ValueError("the calibration's parameters must be finite")
+    if c != 0.0 and not with_frames:
+        raise ValueError("c != 0 needs n_frames")
+    return _lib.Calibration(a, b, c)
 
 
 class UbmTrainer:

@@ -162,6 +162,29 @@ TRIAL_COLUMN_DTYPE = [("n_target", "<i8"), ("n_nontarget", "<i8"), ("n_nan", "<i
                       ("best_correct", "<i8"), ("auc_u2", "<i8"), ("auc", "<f8"), ("best_index", "<i4"), ("reserved", "<i4")]
 
 
+class Calibration(C.Structure):
+    """dsp_calibration (include/dsp_amd.h): c = a x + b + c log(n_frames); 1, 0, 0 are the reference's constants."""
+
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("c", C.c_double)]
+
+
+class CalibrationConfig(C.Structure):
+    """dsp_calibration_config (include/dsp_amd.h): the prior, the stopping tolerance and the passes of dsp_calibration_fit_device."""
+
+    _fields_ = [("prior", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int), ("reserved", C.c_int)]
+
+
+class CalibrationReport(C.Structure):
+    """dsp_calibration_report (include/dsp_amd.h), 88 bytes."""
+
+    _fields_ = [("params", Calibration), ("n_target", C.c_long), ("n_nontarget", C.c_long), ("n_excluded", C.c_long), ("objective_start", C.c_double),
+                ("objective", C.c_double), ("last_step", C.c_double), ("n_iter", C.c_int), ("n_rejected", C.c_int), ("status", C.c_int), ("reserved", C.c_int)]
+
+
+CAL_CONVERGED, CAL_MAX_ITER, CAL_STALLED, CAL_SINGULAR, CAL_NO_CLASS = 0, 1, 2, 3, 4
+CAL_STATUS = ("converged", "max_iter", "stalled", "singular", "no_class")
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -229,6 +252,7 @@ SYMBOLS = [
     "dsp_speaker_float_scan_device",
     "dsp_segmenter_create", "dsp_segmenter_destroy", "dsp_segments_capacity", "dsp_segments_device", "dsp_segment_sample_spans",
     "dsp_trials_target_offsets", "dsp_trials_pairs", "dsp_trial_evaluator_create", "dsp_trial_evaluator_destroy", "dsp_trials_evaluate_device",
+    "dsp_calibrator_create", "dsp_calibrator_destroy", "dsp_calibration_duration_term", "dsp_calibration_fit_device", "dsp_calibration_apply_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -411,6 +435,13 @@ def load() -> C.CDLL:
     L.dsp_trial_evaluator_destroy.argtypes = [vp]; L.dsp_trial_evaluator_destroy.restype = None
     L.dsp_trials_evaluate_device.argtypes = [vp, vp, C.c_long, C.c_long, tip, C.POINTER(TrialsConfig), vp, vp, vp, vp, vp, vp]
     L.dsp_trials_evaluate_device.restype = ip
+    L.dsp_calibrator_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_calibrator_create.restype = ip
+    L.dsp_calibrator_destroy.argtypes = [vp]; L.dsp_calibrator_destroy.restype = None
+    L.dsp_calibration_duration_term.argtypes = [lp, C.c_long, C.POINTER(C.c_double)]; L.dsp_calibration_duration_term.restype = ip
+    L.dsp_calibration_fit_device.argtypes = [vp, vp, C.c_long, C.c_long, tip, lp, C.POINTER(CalibrationConfig), C.POINTER(Calibration),
+                                             C.POINTER(CalibrationReport), vp]
+    L.dsp_calibration_fit_device.restype = ip
+    L.dsp_calibration_apply_device.argtypes = [vp, vp, C.c_long, C.c_long, lp, C.POINTER(Calibration), vp, vp]; L.dsp_calibration_apply_device.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

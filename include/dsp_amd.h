@@ -1085,8 +1085,7 @@ long dsp_segment_sample_spans(const dsp_mfcc_config *mfcc, const dsp_scan_config
  * and clears 8 S (n + 1) bytes of histograms -- 1.6 MB at 1 000 speakers and 200 thresholds, but 4.3 GB at S = 2^19 with n = 1024 --
  * and the labels travel through 4 (T + targets) + 8 (S + 1) bytes of pinned host memory and as many on the device: 0.8 MB at 100 000
  * clips, 16 GB near T = 2^31.  A workspace the device cannot give is DSP_ENOMEM, a pinned buffer the host cannot give DSP_EHIP.
- * Not covered: a threshold per column in the segmenter, the duration calibration A llr + B + C log n of adapt_ubm.py:97-99, the
- * equal error rate, pair counts pooled across columns.                                                                             */
+ * Not covered: a threshold per column in the segmenter, the equal error rate, pair counts pooled across columns.                   */
 typedef struct dsp_trials_config { int n_thresholds; } dsp_trials_config;           /* 2 .. 1024; 200 = evaluate_gmm.py */
 typedef struct dsp_trial_column {                                                   /* 80 bytes: one per column, and one pooled */
     long n_target, n_nontarget, n_nan;
@@ -1106,6 +1105,84 @@ int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, lo
                                long *d_sweep_tp, long *d_sweep_fp,    /* [S + 1][n_thresholds]          may be NULL */
                                int *d_fa_above, int *d_fa_equal,      /* [targets in all]               may be NULL */
                                void *stream);
+
+/* SCORE CALIBRATION: fit c = A x + B + C log(n_frames) on labelled trials, apply it -- the duration calibration of
+ * 2fa/audio/speaker/adapt_ubm.py:97-99, whose constants (CAL_A, CAL_B, CAL_C = 1, 0, 0, "to be learned on dev set", :27-28) the
+ * reference never learns.  d_scores[T][S] and truth[T] are those of dsp_trials_evaluate_device;
+ * n_frames[T] is a HOST array, the rows a trial's score was averaged over (the differences of frame_offsets behind
+ * dsp_speaker_verify_ragged_device, the window length behind dsp_speaker_float_scan_device), or NULL: the two-parameter model, C = 0
+ * and not fitted.  truth and n_frames are read before the call returns.
+ *
+ * Duration term.  l_r = log((double)n_frames[r] + 1e-8), the C library's log on the host; dsp_calibration_duration_term (host only)
+ * writes exactly the values the library uses to out[T].
+ * Model.  For trial (r, s) with score x: c = A x + B + C l_r.  A trial whose score is NaN or +-inf takes no part in the fit and is
+ * counted in n_excluded; P targets and N non-targets remain.
+ * Objective.  With tau = log(prior / (1 - prior)):
+ *   J = prior / P sum_targets softplus(-(c + tau)) + (1 - prior) / N sum_nontargets softplus(c + tau)
+ * (softplus(z) = max(z, 0) + log1p(exp(-|z|)); at prior = 0.5, J / ln 2 is Cllr).
+ * Iteration.  Damped Newton; one pass over the matrix gives J, the gradient g and the Hessian H at theta = (A, B[, C]).
+ *   1. theta = init (NULL: 1, 0, 0); no step is pending.
+ *   2. After a pass at theta: if a step is pending and !(J <= J_base), the pass is rejected: h += 1, theta = base - d / 2^h; more than
+ *      30 halvings end the fit, DSP_CAL_STALLED, theta = base.
+ *   3. Else the pass is accepted.  If a step was pending and max |theta - base| <= tol: DSP_CAL_CONVERGED at this theta.
+ *   4. Else base = theta, J_base = J, h = 0, and H d = g is solved by Cholesky in float64.  A pivot <= 0 or a non-finite J, g, H or d:
+ *      DSP_CAL_SINGULAR, theta = base.
+ *   5. Else theta = base - d, which is pending.
+ *   6. Rejected passes count among max_iter; running out: DSP_CAL_MAX_ITER, theta = base.
+ *   7. P == 0 or N == 0 after the first pass: DSP_CAL_NO_CLASS, theta = init, objective and objective_start NaN.
+ * The report: params = theta at the end; objective = J there; objective_start = J at init; last_step = max |theta - base| of the last
+ * accepted step (NaN: none); n_iter = passes made, n_rejected those rejected.
+ * Every sum is float64 over a tree that depends on (T, S) alone, without float atomics: a report is the same bits whatever the
+ * stream, the repeats and what the workspace held.
+ *
+ * dsp_calibration_fit_device enqueues max_iter passes without a host round trip (those behind the end leave at once), waits for the
+ * stream ONCE and returns with *report filled.  dsp_calibration_apply_device only enqueues:
+ *   d_out[r][s] = (float)(A (double)x + B + C l_r), float64 products and sums from left to right, never fused, rounded once;
+ * without n_frames the last term is left out.  NaN stays NaN.  d_out == d_scores is allowed.  The output is a score matrix like its
+ * input: dsp_trials_evaluate_device and dsp_segments_device take it unchanged.
+ * The calibrator owns a grow-only workspace (184 bytes per 1 024 trials of a matrix below 32 columns, per 16 384 from there on) and
+ * the labels travel through 12 T bytes of pinned host memory and as many on the device: ONE stream at a time per calibrator.
+ * dsp_calibrator_create touches no device.
+ *
+ * DSP_EINVAL, before a device is touched, the first of -- fit: c NULL; cfg NULL; prior not inside (0, 1); tol not > 0; max_iter
+ * outside 1 .. 10 000; report NULL; n_columns outside 1 .. 2^19; n_rows < 0 or >= 2^31; a non-finite init; init->c != 0 without
+ * n_frames; (n_rows == 0: DSP_OK here, no launch, the report DSP_CAL_NO_CLASS with n_iter 0;) d_scores NULL; truth NULL; the first
+ * truth[r] < -1 or >= n_columns, named; the first n_frames[r] < 0, named; 2^45 trials or more.  apply: c NULL; params NULL or
+ * non-finite; n_columns, n_rows as above; params->c != 0 without n_frames; (n_rows == 0: DSP_OK, no launch;) d_scores NULL; d_out
+ * NULL; the first n_frames[r] < 0, named; 2^45 trials or more.  dsp_calibration_duration_term: n_rows < 0; n_frames or out NULL with
+ * n_rows > 0; the first n_frames[r] < 0, named.
+ * Not covered: a calibration per column (one theta serves the matrix), regularisation of theta (separable scores end
+ * DSP_CAL_SINGULAR or DSP_CAL_MAX_ITER with a large finite A), the equal error rate.                                              */
+#define DSP_CAL_CONVERGED 0
+#define DSP_CAL_MAX_ITER 1
+#define DSP_CAL_STALLED 2
+#define DSP_CAL_SINGULAR 3
+#define DSP_CAL_NO_CLASS 4
+typedef struct dsp_calibration { double a, b, c; } dsp_calibration;                 /* 1, 0, 0: the reference's constants */
+typedef struct dsp_calibration_config {
+    double prior;        /* inside (0, 1): the weight of the target class; 0.5 = Cllr */
+    double tol;          /* > 0: the fit ends when an accepted step moves no parameter by more */
+    int    max_iter;     /* 1 .. 10 000 passes over the matrix */
+    int    reserved;
+} dsp_calibration_config;
+typedef struct dsp_calibration_report {                                             /* 88 bytes */
+    dsp_calibration params;
+    long n_target, n_nontarget, n_excluded;
+    double objective_start, objective, last_step;
+    int n_iter, n_rejected, status, reserved;
+} dsp_calibration_report;
+typedef struct dsp_calibrator dsp_calibrator;
+int dsp_calibrator_create(int device, dsp_calibrator **out);
+void dsp_calibrator_destroy(dsp_calibrator *c);
+int dsp_calibration_duration_term(const long *n_frames, long n_rows, double *out);
+int dsp_calibration_fit_device(dsp_calibrator *c, const float *d_scores, long n_rows, long n_columns, const int *truth,
+                               const long *n_frames,                  /* [T] on the host, may be NULL: A and B only */
+                               const dsp_calibration_config *cfg,
+                               const dsp_calibration *init,           /* may be NULL: 1, 0, 0 */
+                               dsp_calibration_report *report,        /* on the HOST */
+                               void *stream);
+int dsp_calibration_apply_device(dsp_calibrator *c, const float *d_scores, long n_rows, long n_columns, const long *n_frames,
+                                 const dsp_calibration *params, float *d_out, void *stream);
 
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
