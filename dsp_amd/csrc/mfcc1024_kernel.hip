@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mfcc_device.hpp"
+#include "stream_load.hpp"
 
 namespace dsp {
 
@@ -40,7 +41,9 @@ __device__ __forceinline__ void radix8(c32 (&v)[8])
 
 }  // namespace
 
-template <bool FULL>
+// CLIPS (= args.frames_per_clip > 0, chosen by the launcher): overlapping frames of clips, cacheable loads; back-to-back frames
+// stream.  A template constant: selected by the run-time field itself the two loads merged into one without the hint (stream_load.hpp).
+template <bool FULL, bool CLIPS = false>
 __global__ __launch_bounds__(256) void mfcc1024_kernel(const Mfcc512Args args, const GenTables1024 *__restrict__ G)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -87,8 +90,7 @@ __global__ __launch_bounds__(256) void mfcc1024_kernel(const Mfcc512Args args, c
         for (int a = 0; a < 8; ++a) {
             const int i = 2 * (lane + 64 * a);
             if (FULL || i + 1 < frame_len) {
-                const f2v x = args.frames_per_clip > 0 ? *reinterpret_cast<const f2v *>(src + i)      // clips re-read samples: cacheable
-                                                       : __builtin_nontemporal_load(reinterpret_cast<const f2v *>(src + i));
+                const f2v x = load_frame_word<!CLIPS>(reinterpret_cast<const f2v *>(src + i));      // clips re-read samples: cacheable
                 z[a] = {x.x, x.y};
             } else if (i < frame_len) {
                 z[a] = {src[i], 0.0f};
@@ -221,8 +223,11 @@ __global__ __launch_bounds__(256) void mfcc1024_kernel(const Mfcc512Args args, c
 
 hipError_t launch_mfcc1024(const Mfcc512Args &args, const GenTables1024 *tables, int blocks, hipStream_t stream)
 {
-    if (args.frame_len == 1024) hipLaunchKernelGGL((mfcc1024_kernel<true>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
-    else hipLaunchKernelGGL((mfcc1024_kernel<false>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
+    const bool full = args.frame_len == 1024, clips = args.frames_per_clip > 0;
+    if (full && clips) hipLaunchKernelGGL((mfcc1024_kernel<true, true>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
+    else if (full) hipLaunchKernelGGL((mfcc1024_kernel<true, false>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
+    else if (clips) hipLaunchKernelGGL((mfcc1024_kernel<false, true>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
+    else hipLaunchKernelGGL((mfcc1024_kernel<false, false>), dim3(blocks), dim3(256), G_BLOCK_BYTES, stream, args, tables);
     return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mfcc_device.hpp"
+#include "stream_load.hpp"
 #include "svm_kernels.hpp"
 #include "tables.hpp"
 
@@ -84,12 +85,12 @@ __device__ __host__ constexpr int q_dct(bool pre) { return q_win(pre) + 16 * 64 
 // kernels keep their code and registers.
 // IN: 0 float samples; 1 int16 mono, 2 interleaved int16 stereo channel 0, 3 stereo (L + R) / 65536 -- converted
 // in the load (exact: the float path's values), instantiated for the scrubjay_infer.c front end (AUB), whose callers decode int16 files.
-template <int IN>
-__device__ __forceinline__ void load_pair_2048(const void *base, long i, bool cached, float &x0, float &x1)
+// CACHED: a template constant, never a run-time flag (stream_load.hpp: the optimiser merges the two loads and drops the hint)
+template <int IN, bool CACHED>
+__device__ __forceinline__ void load_pair_2048(const void *base, long i, float &x0, float &x1)
 {
     if constexpr (IN == 0) {
-        const f2v x = cached ? *reinterpret_cast<const f2v *>(static_cast<const float *>(base) + i)
-                             : __builtin_nontemporal_load(reinterpret_cast<const f2v *>(static_cast<const float *>(base) + i));
+        const f2v x = load_frame_word<!CACHED>(reinterpret_cast<const f2v *>(static_cast<const float *>(base) + i));
         x0 = x.x; x1 = x.y;
     } else if constexpr (IN == 1) {
         const unsigned q = *reinterpret_cast<const unsigned *>(static_cast<const short *>(base) + i);
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
             const int i = 2 * (lane + 64 * a);
             float x0 = 0.0f, x1 = 0.0f;
             if (i + 1 < hi_i && (!AUB || i >= lo_i)) {                   // lo_i is even: a pair never straddles it
-                load_pair_2048<IN>(args.in, src + i, CLIPS, x0, x1);     // clips re-read samples: cacheable
+                load_pair_2048<IN, CLIPS>(args.in, src + i, x0, x1);     // clips re-read samples: cacheable
             } else if (i < hi_i && (!AUB || i >= lo_i)) {
                 x0 = load_one_2048<IN>(args.in, src + i);
             }

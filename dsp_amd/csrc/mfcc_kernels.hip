@@ -4,7 +4,9 @@
 // 13 cepstral coefficients; nothing but the input frame and the coefficients
 // touches HBM.  Per frame (reference chain: 2fa/audio/word/c/mfcc.c:142-221):
 //
-//   load      4 x global_load_dwordx2 per lane: z[l+64a] = x[2n] + i x[2n+1]
+//   load      4 x global_load_dwordx2 per lane: z[l+64a] = x[2n] + i x[2n+1]; with the `nt` modifier where frames lie back to
+//             back (CLIPS = false), plain in clip mode -- a template constant down to the load (stream_load.hpp), checked in
+//             the built code object by tests/test_stream_loads_cpu.py: handed down as a run-time flag the hint was lost
 //   window    8 v_mul (window pre-scaled by 1/2, tables.cpp)           mfcc.c:142-144
 //   FFT       512-point real FFT as a 256-point complex radix-4 DIF:    mfcc.c:16-95
 //             every butterfly stage in registers; inter-stage exchanges:
@@ -34,6 +36,7 @@
 #include <algorithm>
 
 #include "mfcc_device.hpp"
+#include "stream_load.hpp"
 
 // Timing-only diagnostic builds (never shipped), -DDSP_DIAG_MODE=<bit mask>:
 //   1 loads + store only, no arithmetic      2 arithmetic only, loads just the first frame
@@ -94,9 +97,9 @@ namespace {
 // STREAM: frames lie back to back and every sample is read exactly once -> nontemporal loads (nothing is displaced in L2).
 // Clip mode reads every sample 2.5 times (frames of 400 every 160): those loads must stay cacheable, or the re-reads go
 // out to the fabric again (measured with nontemporal loads: 1.96 x the algorithmic bytes; FETCH_SIZE, profiles/r02b).
-template <typename V>
-__device__ __forceinline__ V ld_frame(const V *p, bool stream) { return stream ? __builtin_nontemporal_load(p) : *p; }
-
+// The policy is a template constant all the way down to the load (stream_load.hpp).  From the commit that introduced the
+// cacheable clip loads until this helper it was handed to the load as a run-time `bool stream`: the optimiser merged the
+// two loads and dropped the hint, and EVERY instantiation shipped cacheable (0 `nt` in the code object).
 template <int FLEN, int IN, bool STREAM>
 __device__ __forceinline__ void load_frame(const void *__restrict__ base, long off, int lane, int frame_len, c32 (&z)[4])
 {
@@ -109,7 +112,7 @@ __device__ __forceinline__ void load_frame(const void *__restrict__ base, long o
         if (IN == 0) {
             const float *src = static_cast<const float *>(base) + off;
             if (both) {
-                const f2v v = ld_frame(reinterpret_cast<const f2v *>(src + i), STREAM);
+                const f2v v = load_frame_word<STREAM>(reinterpret_cast<const f2v *>(src + i));
                 z[a] = {v.x, v.y};
             } else if (one) {
                 z[a] = {src[i], 0.0f};
@@ -121,14 +124,14 @@ __device__ __forceinline__ void load_frame(const void *__restrict__ base, long o
             // is consumed (unpack_pcm16): 4 VGPRs per frame in flight instead of 8
             const short *src = static_cast<const short *>(base) + off;
             int v = 0;
-            if (both) v = ld_frame(reinterpret_cast<const int *>(src + i), STREAM);                  // samples i, i+1
+            if (both) v = load_frame_word<STREAM>(reinterpret_cast<const int *>(src + i));                  // samples i, i+1
             else if (one) v = (int)(unsigned short)src[i];
             z[a] = {__int_as_float(v), 0.0f};
         } else {
             // interleaved stereo: the ring keeps the two raw L|R dwords, unpack_pcm16 converts at consumption
             const short *src = static_cast<const short *>(base) + 2 * off;
             i2v v = {0, 0};
-            if (both) v = ld_frame(reinterpret_cast<const i2v *>(src + 2 * i), STREAM);               // L0 R0 | L1 R1
+            if (both) v = load_frame_word<STREAM>(reinterpret_cast<const i2v *>(src + 2 * i));               // L0 R0 | L1 R1
             else if (one) v.x = *reinterpret_cast<const int *>(src + 2 * i);
             z[a] = {__int_as_float(v.x), __int_as_float(v.y)};
         }
