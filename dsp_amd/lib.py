@@ -185,6 +185,39 @@ CAL_CONVERGED, CAL_MAX_ITER, CAL_STALLED, CAL_SINGULAR, CAL_NO_CLASS = 0, 1, 2, 
 CAL_STATUS = ("converged", "max_iter", "stalled", "singular", "no_class")
 
 
+class SvmTrainProblem(C.Structure):
+    """dsp_svm_train_problem (include/dsp_amd.h), 40 bytes: rows on the host, a box bound per label, gamma."""
+
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_long), ("c_label0", C.c_double), ("c_label1", C.c_double), ("gamma", C.c_double)]
+
+
+class SvmTrainConfig(C.Structure):
+    """dsp_svm_train_config (include/dsp_amd.h)."""
+
+    _fields_ = [("eps", C.c_double), ("max_iter", C.c_int), ("q_float32", C.c_int)]
+
+
+class SvmTrainResult(C.Structure):
+    """dsp_svm_train_result (include/dsp_amd.h), 40 bytes; SVM_TRAIN_RESULT_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("rho", C.c_double), ("objective", C.c_double), ("gap", C.c_double), ("n_iter", C.c_int), ("n_sv", C.c_int),
+                ("n_bounded", C.c_int), ("status", C.c_int)]
+
+
+SVM_TRAIN_RESULT_DTYPE = [("rho", "<f8"), ("objective", "<f8"), ("gap", "<f8"), ("n_iter", "<i4"), ("n_sv", "<i4"), ("n_bounded", "<i4"), ("status", "<i4")]
+SVM_TRAIN_CONVERGED, SVM_TRAIN_MAX_ITER, SVM_TRAIN_ONE_CLASS, SVM_TRAIN_EMPTY = 0, 1, 2, 3
+SVM_TRAIN_STATUS = ("converged", "max_iter", "one_class", "empty")
+SVM_TRAIN_MAX_ROWS = 8192
+
+
+class SvmFitModel(C.Structure):
+    """dsp_svm_fit_model (include/dsp_amd.h), 112 bytes: the caller's arrays and what dsp_svm_fit_device found."""
+
+    _fields_ = [("offset", C.c_void_p), ("scale", C.c_void_p), ("sv", C.c_void_p), ("coef", C.c_void_p), ("n_sv", C.c_long), ("n_sv_label0", C.c_long),
+                ("rho", C.c_float), ("prob_a", C.c_float), ("prob_b", C.c_float), ("gamma", C.c_float), ("platt_iter", C.c_int), ("reserved", C.c_int),
+                ("final", SvmTrainResult)]
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -253,6 +286,8 @@ SYMBOLS = [
     "dsp_segmenter_create", "dsp_segmenter_destroy", "dsp_segments_capacity", "dsp_segments_device", "dsp_segment_sample_spans",
     "dsp_trials_target_offsets", "dsp_trials_pairs", "dsp_trial_evaluator_create", "dsp_trial_evaluator_destroy", "dsp_trials_evaluate_device",
     "dsp_calibrator_create", "dsp_calibrator_destroy", "dsp_calibration_duration_term", "dsp_calibration_fit_device", "dsp_calibration_apply_device",
+    "dsp_svm_trainer_create", "dsp_svm_trainer_destroy", "dsp_svm_train_set_device", "dsp_svm_train_rows_host", "dsp_svm_train_problems_device",
+    "dsp_svm_platt_fit_device", "dsp_svm_folds", "dsp_svm_balanced_weights", "dsp_svm_model_from_training", "dsp_svm_fit_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -442,6 +477,20 @@ def load() -> C.CDLL:
                                              C.POINTER(CalibrationReport), vp]
     L.dsp_calibration_fit_device.restype = ip
     L.dsp_calibration_apply_device.argtypes = [vp, vp, C.c_long, C.c_long, lp, C.POINTER(Calibration), vp, vp]; L.dsp_calibration_apply_device.restype = ip
+    dp = C.POINTER(C.c_double)
+    L.dsp_svm_trainer_create.argtypes = [ip, ip, C.POINTER(vp)]; L.dsp_svm_trainer_create.restype = ip
+    L.dsp_svm_trainer_destroy.argtypes = [vp]; L.dsp_svm_trainer_destroy.restype = None
+    L.dsp_svm_train_set_device.argtypes = [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp, vp]; L.dsp_svm_train_set_device.restype = ip
+    L.dsp_svm_train_rows_host.argtypes = [vp, vp, vp]; L.dsp_svm_train_rows_host.restype = ip
+    L.dsp_svm_train_problems_device.argtypes = [vp, C.POINTER(SvmTrainProblem), C.c_long, C.POINTER(SvmTrainConfig), vp, vp, vp, vp, vp]
+    L.dsp_svm_train_problems_device.restype = ip
+    L.dsp_svm_platt_fit_device.argtypes = [vp, vp, vp, vp, C.c_long, dp, dp, C.POINTER(ip), vp]; L.dsp_svm_platt_fit_device.restype = ip
+    L.dsp_svm_folds.argtypes = [C.c_long, ip, C.c_uint64, vp]; L.dsp_svm_folds.restype = ip
+    L.dsp_svm_balanced_weights.argtypes = [vp, vp, C.c_long, C.c_double, dp, dp]; L.dsp_svm_balanced_weights.restype = ip
+    L.dsp_svm_model_from_training.argtypes = [vp, vp, vp, C.c_long, ip, vp, vp, C.c_long, lp]; L.dsp_svm_model_from_training.restype = C.c_long
+    L.dsp_svm_fit_device.argtypes = [vp, vp, C.c_long, vp, vp, ip, C.c_uint64, C.c_double, C.c_double, C.c_double, C.POINTER(SvmTrainConfig),
+                                     C.POINTER(SvmFitModel), vp]
+    L.dsp_svm_fit_device.restype = ip
     L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
     L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
     L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip

@@ -134,6 +134,21 @@ class ScrubJay:
         self.plan = MfccPlan(config if config is not None else default_config(n_mfcc=n_mfcc), device)
         self.svm = SvmModel(svm_attrs, device)
 
+    @classmethod
+    def train(cls, clips_or_features, labels, device: int = 0, n_mfcc: int = 20, config=None, max_frames: int = 1 << 20, **fit_args):
+        """Trains the SVM (SvmTrainer.fit, which takes fit_args) and returns (the ScrubJay built on it, the fit's report).  A float32 CUDA
+        tensor [n][2 n_mfcc] is taken as pooled features; anything else as clips [n][samples], pooled by this front end first."""
+        cfg = config if config is not None else default_config(n_mfcc=n_mfcc)
+        x = clips_or_features
+        if not (x.dim() == 2 and x.shape[1] == 2 * cfg.n_mfcc):
+            x = mfcc_stats(MfccPlan(cfg, device).clips(x, max_frames))
+        trainer = SvmTrainer(2 * cfg.n_mfcc, device)
+        try:
+            attrs, report = trainer.fit(x, labels, **fit_args)
+        finally:
+            trainer.close()
+        return cls(attrs, device, config=cfg), report
+
     def __call__(self, clips, max_frames: int = 1 << 20, fused: bool = True):
         """-> (labels int32, decision float32, prob1 float32, features float32 [n][2 n_mfcc]).  fused: one kernel from PCM to
         label (dsp_scrubjay_fused_device, BASELINE config 5); otherwise MFCC -> pooling -> SVM as three kernels."""
@@ -189,6 +204,223 @@ class ScrubJay:
             _lib.check(_lib.load().dsp_scrubjay_fused_ragged_device(self.plan._h, self.svm._h, ptr, n, off, mf, labels.data_ptr(), dec.data_ptr(),
                                                                     p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_ragged_device")
         return labels, dec, p1, feat
+
+
+def svm_folds(n: int, k: int, seed: int = 0):
+    """Host only: fold ids int32 [n] in 0 .. k - 1 by libsvm's shuffle on the library's own draws (dsp_svm_folds)."""
+    ids = np.empty(int(n), np.int32)
+    _lib.check(_lib.load().dsp_svm_folds(int(n), int(k), int(seed) & (2**64 - 1), ids.ctypes.data), "dsp_svm_folds")
+    return ids
+
+
+def svm_balanced_weights(labels, c: float = 1.0, rows=None):
+    """Host only: sklearn's class_weight="balanced" as box bounds, C n / (2 n_label) over `rows` (default: all) -> (C_label0, C_label1)."""
+    labels = np.ascontiguousarray(labels, np.int32)
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    c0, c1 = C.c_double(), C.c_double()
+    _lib.check(_lib.load().dsp_svm_balanced_weights(labels.ctypes.data, None if rows is None else rows.ctypes.data,
+                                                    labels.size if rows is None else rows.size, float(c), C.byref(c0), C.byref(c1)),
+               "dsp_svm_balanced_weights")
+    return c0.value, c1.value
+
+
+def svm_model_from_training(z, labels, coef):
+    """Host only: the support vectors of a solved problem in libsvm's order (dsp_svm_model_from_training): z float32 [n][nf], labels [n],
+    coef float64 [n] -> (sv float32 [n_sv][nf], coef float32 [n_sv], how many carry label 0)."""
+    z = np.ascontiguousarray(z, np.float32)
+    labels = np.ascontiguousarray(labels, np.int32)
+    coef = np.ascontiguousarray(coef, np.float64)
+    n, nf = z.shape
+    sv, c32, n0 = np.empty((n, nf), np.float32), np.empty(n, np.float32), C.c_long()
+    n_sv = _lib.check(_lib.load().dsp_svm_model_from_training(z.ctypes.data, labels.ctypes.data, coef.ctypes.data, n, nf, sv.ctypes.data,
+                                                               c32.ctypes.data, n, C.byref(n0)), "dsp_svm_model_from_training")
+    return sv[:n_sv].copy(), c32[:n_sv].copy(), n0.value
+
+
+class SvmTrainer:
+    """dsp_svm_trainer: the scrub-jay RBF-SVM from pooled features, cepstrum/train.py:66-85 on the GPU -- the Scaler, batched SMO over one
+    shared distance matrix, libsvm's Platt fit, cross-validation over a (C, gamma) grid.  Features are cuda float32 [n][n_features]
+    (mfcc_stats, or the features ScrubJay returns), labels 0 / 1 on the host.  One stream at a time per trainer."""
+
+    def __init__(self, n_features: int, device: int = 0):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_svm_trainer_create(device, int(n_features), C.byref(h)), "dsp_svm_trainer_create")
+        self._h, self.n_features, self.device, self.n = h, int(n_features), device, 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_svm_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _features(self, feat):
+        import torch
+        if not (isinstance(feat, torch.Tensor) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 2 and feat.shape[1] == self.n_features):
+            raise ValueError(f"feat must be a float32 CUDA tensor [n][{self.n_features}]")
+        if feat.device.index != self.device:
+            raise ValueError(f"feat is on GPU {feat.device.index}, the trainer on GPU {self.device}")
+        return feat.contiguous()
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set(self, feat, scaler_rows=None, offset=None, scale=None):
+        """The dataset of the calls that follow (dsp_svm_train_set_device): fits the Scaler on `scaler_rows` (default: all rows) or takes
+        the caller's offset / scale, standardises and builds the distance matrix -> (offset, scale) float32 [n_features]."""
+        feat = self._features(feat)
+        rows = None if scaler_rows is None else np.ascontiguousarray(scaler_rows, np.int32)
+        given = None if offset is None else (np.ascontiguousarray(offset, np.float32), np.ascontiguousarray(scale, np.float32))
+        if given is not None and (given[0].size != self.n_features or given[1].size != self.n_features):
+            raise ValueError("offset and scale must hold n_features values")
+        off, scl = np.empty(self.n_features, np.float32), np.empty(self.n_features, np.float32)
+        self.n = 0
+        _lib.check(self._L.dsp_svm_train_set_device(self._h, feat.data_ptr(), feat.shape[0], None if rows is None else rows.ctypes.data,
+                                                    0 if rows is None else rows.size, None if given is None else given[0].ctypes.data,
+                                                    None if given is None else given[1].ctypes.data, off.ctypes.data, scl.ctypes.data, self._stream()),
+                   "dsp_svm_train_set_device")
+        self.n = feat.shape[0]
+        return off, scl
+
+    def rows(self):
+        """the standardised rows of the dataset, float32 [n][n_features] on the host"""
+        z = np.empty((self.n, self.n_features), np.float32)
+        _lib.check(self._L.dsp_svm_train_rows_host(self._h, z.ctypes.data, self._stream()), "dsp_svm_train_rows_host")
+        return z
+
+    def problems(self, problems, labels, eps: float = 1e-3, max_iter: int = 0, decisions: bool = True, q_float32: bool = False):
+        """Solves problems = [(rows, C_label0, C_label1, gamma), ...] on the dataset in ONE launch (dsp_svm_train_problems_device) ->
+        (results: numpy records of SVM_TRAIN_RESULT_DTYPE [P], coef cuda float64 [P][n], dec cuda float64 [P][n] or None).  q_float32:
+        the solver rounds its kernel values to float32 as libsvm rounds the Q it caches, which gives libsvm's answer rather than float64's."""
+        import torch
+        labels = np.ascontiguousarray(labels, np.int32)
+        if labels.size != self.n:
+            raise ValueError(f"labels must hold the dataset's {self.n} rows")
+        keep = [np.ascontiguousarray(p[0], np.int32) for p in problems]
+        table = (_lib.SvmTrainProblem * max(1, len(problems)))()
+        for k, (p, r) in enumerate(zip(problems, keep)):
+            table[k] = _lib.SvmTrainProblem(r.ctypes.data if r.size else None, r.size, float(p[1]), float(p[2]), float(p[3]))
+        results = np.zeros(len(problems), _lib.SVM_TRAIN_RESULT_DTYPE)
+        dev = torch.device("cuda", self.device)
+        coef = torch.empty((len(problems), self.n), dtype=torch.float64, device=dev)
+        dec = torch.empty((len(problems), self.n), dtype=torch.float64, device=dev) if decisions else None
+        cfg = _lib.SvmTrainConfig(float(eps), int(max_iter), int(bool(q_float32)))
+        _lib.check(self._L.dsp_svm_train_problems_device(self._h, table, len(problems), C.byref(cfg), labels.ctypes.data, results.ctypes.data,
+                                                         coef.data_ptr(), dec.data_ptr() if decisions else None, self._stream()),
+                   "dsp_svm_train_problems_device")
+        return results, coef, dec
+
+    def platt(self, dec_cv, labels, rows=None):
+        """libsvm's sigmoid_train on (dec_cv[r], labels[r]), dec_cv cuda float64 [n] (dsp_svm_platt_fit_device) -> (A, B, n_iter)."""
+        import torch
+        if not (isinstance(dec_cv, torch.Tensor) and dec_cv.is_cuda and dec_cv.dtype == torch.float64 and dec_cv.numel() == self.n):
+            raise ValueError(f"dec_cv must be a float64 CUDA tensor [{self.n}]")
+        labels = np.ascontiguousarray(labels, np.int32)
+        if labels.size != self.n:
+            raise ValueError(f"labels must hold the dataset's {self.n} rows")
+        rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+        a, b, it = C.c_double(), C.c_double(), C.c_int()
+        _lib.check(self._L.dsp_svm_platt_fit_device(self._h, dec_cv.contiguous().data_ptr(), labels.ctypes.data, None if rows is None else rows.ctypes.data,
+                                                    0 if rows is None else rows.size, C.byref(a), C.byref(b), C.byref(it), self._stream()),
+                   "dsp_svm_platt_fit_device")
+        return a.value, b.value, it.value
+
+    @staticmethod
+    def _box(labels, c, class_weight, rows=None):
+        if class_weight == "balanced":
+            return svm_balanced_weights(labels, c, rows)
+        if class_weight is None:
+            return float(c), float(c)
+        return float(c) * float(class_weight[0]), float(c) * float(class_weight[1])
+
+    @staticmethod
+    def _scale_gamma(z) -> float:
+        """sklearn's gamma="scale", 1 / (n_features var(z)) over every element of the standardised training rows, as the float the model holds"""
+        return float(np.float32(1.0 / (z.shape[1] * float(z.double().var(unbiased=False)))))
+
+    def fit(self, feat, labels, C=10.0, gamma="scale", class_weight="balanced", probability_folds: int = 5, fold_ids=None, seed: int = 0,
+            eps: float = 1e-3, max_iter: int = 0, q_float32: bool = False):
+        """The reference's clf.fit (dsp_svm_fit_device): the Scaler on all rows, `probability_folds` inner problems and the final one in one
+        launch, the Platt fit -> (attrs: the dict SvmModel takes, report: dict).  gamma "scale" is 1 / (n_features var(z)) computed with
+        torch on the standardised rows; every gamma is rounded to the float32 the model holds before it is trained with.  q_float32: the
+        solver rounds its kernel values to float32 as libsvm rounds the Q it caches (the answer sklearn gives, not float64's)."""
+        import ctypes                                                # (the parameter C, sklearn's name, hides this module's alias)
+        import torch
+        feat = self._features(feat)
+        labels = np.ascontiguousarray(labels, np.int32)
+        n, nf = feat.shape
+        if labels.size != n:
+            raise ValueError("labels must hold one label per row")
+        if gamma == "scale":
+            x = feat.double()
+            mean = x.mean(dim=0)
+            std = ((x - mean) ** 2).mean(dim=0).sqrt()
+            scl = torch.where(std > 0, 1.0 / torch.where(std > 0, std, torch.ones_like(std)), torch.ones_like(std)).float()
+            gamma = self._scale_gamma((feat - mean.float()) * scl)
+        else:
+            gamma = float(np.float32(gamma))
+        c0, c1 = self._box(labels, C, class_weight)
+        ids = None if fold_ids is None else np.ascontiguousarray(fold_ids, np.int32)
+        if ids is not None and ids.size != n:
+            raise ValueError("fold_ids must hold one id per row")
+        out = {"offset": np.empty(nf, np.float32), "scale": np.empty(nf, np.float32), "sv": np.empty((n, nf), np.float32), "coef": np.empty(n, np.float32)}
+        model = _lib.SvmFitModel(*[out[k].ctypes.data for k in ("offset", "scale", "sv", "coef")])
+        cfg = _lib.SvmTrainConfig(float(eps), int(max_iter), int(bool(q_float32)))
+        self.n = 0
+        _lib.check(self._L.dsp_svm_fit_device(self._h, feat.data_ptr(), n, labels.ctypes.data, None if ids is None else ids.ctypes.data,
+                                              int(probability_folds), int(seed) & (2**64 - 1), c0, c1, gamma, ctypes.byref(cfg), ctypes.byref(model),
+                                              self._stream()), "dsp_svm_fit_device")
+        self.n = n
+        n_sv, n0 = int(model.n_sv), int(model.n_sv_label0)
+        attrs = {"offset": out["offset"], "scale": out["scale"], "sv": out["sv"][:n_sv].copy(), "coef": out["coef"][:n_sv].copy(),
+                 "kernel_params": np.array([model.gamma, 0.0, 3.0], np.float32), "rho": np.array([model.rho], np.float32),
+                 "prob_a": np.array([model.prob_a], np.float32), "prob_b": np.array([model.prob_b], np.float32),
+                 "vectors_per_class": np.array([n0, n_sv - n0], np.int64)}
+        f = model.final
+        report = {"gamma": gamma, "C": (c0, c1), "n_sv": n_sv, "n_iter": f.n_iter, "n_bounded": f.n_bounded, "objective": f.objective, "gap": f.gap,
+                  "rho": f.rho, "status": _lib.SVM_TRAIN_STATUS[f.status], "platt_iter": int(model.platt_iter)}
+        return attrs, report
+
+    def cross_validate(self, feat, labels, fold_ids, Cs, gammas, class_weight="balanced", eps: float = 1e-3, max_iter: int = 0, q_float32: bool = False):
+        """The reference's cross-validation over a grid: per outer fold the Scaler is fitted on the fold's training rows, and all
+        len(Cs) len(gammas) problems (grid point g = index of C times len(gammas) + index of gamma) run in ONE launch; a row's held-out
+        decision comes from the fold it was left out of.  gammas may hold "scale".  -> dict: dec cuda float64 [grid][n], precision,
+        recall, f1 cuda float64 [grid] of label 1, status int [folds][grid], grid [(C, gamma)] (gamma "scale" stays "scale")."""
+        import torch
+        feat = self._features(feat)
+        labels = np.ascontiguousarray(labels, np.int32)
+        ids = np.ascontiguousarray(fold_ids, np.int32)
+        n = feat.shape[0]
+        if labels.size != n or ids.size != n:
+            raise ValueError("labels and fold_ids must hold one value per row")
+        grid = [(c, g) for c in Cs for g in gammas]
+        held = torch.zeros((len(grid), n), dtype=torch.float64, device=feat.device)
+        status = []
+        for f in np.unique(ids):
+            train = np.nonzero(ids != f)[0].astype(np.int32)
+            test = torch.from_numpy(np.nonzero(ids == f)[0]).to(feat.device)
+            self.set(feat, scaler_rows=train)
+            scale_gamma = self._scale_gamma(torch.from_numpy(self.rows()[train])) if any(g == "scale" for g in gammas) else None
+            problems = []
+            for c, g in grid:
+                c0, c1 = self._box(labels, c, class_weight, train)
+                problems.append((train, c0, c1, scale_gamma if g == "scale" else float(g)))
+            results, _coef, dec = self.problems(problems, labels, eps, max_iter, q_float32=q_float32)
+            held[:, test] = dec[:, test]
+            status.append(results["status"].copy())
+        truth = torch.from_numpy(labels).to(feat.device)[None, :] == 1
+        pred = held <= 0                                             # label 1 where dec is not above 0 (dsp_svm_predict_device's vote)
+        tp = (pred & truth).sum(dim=1).double()
+        precision = tp / pred.sum(dim=1).clamp(min=1)
+        recall = tp / truth.sum(dim=1).clamp(min=1)
+        f1 = 2 * precision * recall / (precision + recall).clamp(min=1e-300)
+        return {"dec": held, "precision": precision, "recall": recall, "f1": f1, "status": np.stack(status), "grid": grid}
 
 
 class ScrubJayScanner:

@@ -1184,6 +1184,118 @@ int dsp_calibration_fit_device(dsp_calibrator *c, const float *d_scores, long n_
 int dsp_calibration_apply_device(dsp_calibrator *c, const float *d_scores, long n_rows, long n_columns, const long *n_frames,
                                  const dsp_calibration *params, float *d_out, void *stream);
 
+/* SVM TRAINING: the scrub-jay RBF-SVM from pooled features -- cepstrum/train.py:66-85 (StandardScaler, SVC(kernel="rbf",
+ * probability=True, class_weight="balanced"), cross-validation) as batched SMO on the GPU.
+ * d_feat[n][n_features] is float32 on the trainer's device (what dsp_mfcc_stats_device writes); labels[n] is a HOST array of 0 / 1,
+ * read before a call returns.  Label 0 is libsvm's positive side, y = +1, as dsp_svm_predict_device votes (label 0 where dec > 0).
+ *
+ * Dataset.  dsp_svm_train_set_device fits the Scaler -- offset = mean, scale = 1 / population std (std 0: scale 1) per feature over
+ * scaler_rows[n_scaler_rows] (HOST, NULL: all n rows), float64 sums, written as float32 -- or takes the caller's offset and scale (both
+ * given: nothing is fitted), standardises z = fl32(fl32(x - offset) * scale) and builds D2[n][n] = sum_f ((double)z_if - (double)z_jf)^2
+ * in float64, features ascending, symmetric bit for bit.  The trainer keeps z and D2 until the next dataset: every problem on this
+ * Scaler shares them, across all gammas.  offset_out / scale_out (HOST [n_features], may be NULL) receive the Scaler; with either given
+ * the call waits for the stream.  n is 2 .. 8192 (DSP_SVM_TRAIN_MAX_ROWS: D2 takes 8 n^2 bytes, 512 MB at the cap).
+ *
+ * Problems.  A problem is rows[n_rows] of the dataset (HOST, strictly ascending), a box bound per label and gamma; with K_ij =
+ * exp(-gamma D2_ij) it is libsvm's C-SVC dual: min 1/2 a'Qa - e'a, Q_ij = y_i y_j K_ij, 0 <= a_i <= C(label_i), y'a = 0.
+ * dsp_svm_train_problems_device solves n_problems of them in ONE launch, one workgroup each, by libsvm's Solver without shrinking:
+ *   i = the member maximising -y G over I_up = {y = +1, a < C} u {y = -1, a > 0};
+ *   j = the member of I_low = {y = +1, a > 0} u {y = -1, a < C} with -y_j G_j < -y_i G_i minimising -(b^2) / max(K_ii + K_jj - 2 K_ij,
+ *       1e-12 where that is <= 0), b = -y_i G_i + y_j G_j;
+ *   of equal candidates the one earliest in rows[] wins, in both selections (libsvm keeps the latest);
+ *   the analytic two-variable step with libsvm's box clipping; G += Q_i da_i + Q_j da_j;
+ *   stop when max over I_up of -y G plus max over I_low of y G is < eps (no j: stop), or after max_iter steps.
+ * Q is float64 throughout; libsvm rounds the rows of Q it caches to float32 (svm.cpp Qfloat), and cfg->q_float32 = 1 does the same to
+ * every kernel value the solver reads -- the selection, the step and the gradient -- which reproduces libsvm's decision values to
+ * its own convergence instead of to its rounding (1e-8 against 1e-7 .. 3e-6 of a decision).  The decision pass is float64 either way,
+ * as libsvm's prediction is.  results[p] on the HOST: rho = -(libsvm's rho: the mean of
+ * y G over the free alphas, without any the midpoint of the bounds), so that dec = sum_i coef_i K_i + rho as dsp_svm_create takes it;
+ * n_iter; n_sv = alphas > 0; n_bounded = alphas at C; objective = 1/2 a'Qa - e'a; gap = the violation at the end; status.
+ * d_coef[P][n] (device, float64) = a_i y_i on the problem's rows and 0 elsewhere; d_dec[P][n] (device, float64, may be NULL) = the
+ * decision of EVERY row of the dataset under problem p: its own rows' are the training decisions, the others' the held-out ones, which
+ * is the cross-validation prediction.  Degenerate problems are reported, never a fault: rows of one label only is
+ * DSP_SVM_TRAIN_ONE_CLASS -- nothing is solved, coef is 0 and every decision +1 (label 0) or -1 (label 1), as libsvm's
+ * svm_binary_svc_probability sets them; n_rows == 0 is DSP_SVM_TRAIN_EMPTY, every decision 0; running out of steps is
+ * DSP_SVM_TRAIN_MAX_ITER, with the alphas, rho and gap of the last step.  A problem's coef, dec and result are the same bits whatever
+ * other problems share the launch and in whatever order.  The call enqueues everything, waits for the stream ONCE and returns with
+ * results filled.  cfg NULL: eps 1e-3 (libsvm's), max_iter 1 000 000; max_iter 0 in a cfg means that default too.
+ *
+ * Platt.  dsp_svm_platt_fit_device is libsvm's sigmoid_train on the pairs (d_dec_cv[r], labels[r]) for r in rows[n_rows] (HOST, NULL:
+ * all rows of the dataset): prior-smoothed targets, A = 0, B = log((prior0 + 1) / (prior1 + 1)) to start, Newton with backtracking,
+ * 100 iterations, min_step 1e-10, sigma 1e-12, eps 1e-5; prior1 counts label 0, the positive side.  One block, float64 sums in a fixed
+ * order: the same bits on every run.  P(label 0 | dec) = 1 / (1 + exp(A dec + B)): prob_a, prob_b of dsp_svm_create.
+ *
+ * Host helpers (no device).  dsp_svm_folds: fold_ids[n] in 0 .. k - 1 by libsvm's rule -- perm = 0 .. n - 1, for i ascending swap
+ * perm[i] with perm[i + draw_i % (n - i)], fold f takes perm[f n / k .. (f + 1) n / k) -- on the library's own draws, draw_i =
+ * mix(seed + (i + 1) 0x9E3779B97F4A7C15) with splitmix64's finaliser as for dsp_kmeans_*.  dsp_svm_balanced_weights: sklearn's
+ * class_weight = "balanced", C_k = C n_rows / (2 n_k) over rows[n_rows] (NULL: labels[0 .. n_rows)); DSP_EINVAL when a label has no
+ * row.  dsp_svm_model_from_training: the support vectors -- rows with coef != 0 -- of z[n][n_features], label 0's first and each
+ * label's in row order (libsvm's order), as sv[][n_features] and (float)coef; returns their number (sv and coef_out may be NULL to
+ * count), n_sv_label0 (may be NULL) how many carry label 0; more than `capacity`: DSP_EINVAL.
+ *
+ * dsp_svm_fit_device is the reference's clf.fit: the Scaler on all rows, k_prob problems without fold f = 0 .. k_prob - 1 and the
+ * final one on all rows in ONE problems launch, the Platt fit on dec_cv[i] = dec[fold_ids[i]][i], the compacted model.  fold_ids
+ * (HOST [n], NULL: dsp_svm_folds(n, k_prob, seed)); the model's arrays are the caller's: offset, scale [n_features], sv [n][n_features]
+ * and coef [n] at most.  rho, prob_a, prob_b and gamma are rounded to float as dsp_svm_create takes them.
+ *
+ * One stream at a time per trainer; the workspace (z, D2, the launch's problem table) is grow-only.  dsp_svm_trainer_create touches
+ * no device.  DSP_EINVAL, before a device is touched and naming the argument: a NULL that may not be; n_features < 1; n < 2 or above
+ * the cap; a scaler row or problem row outside 0 .. n - 1, problem rows not strictly ascending; a label other than 0 / 1; C_label0,
+ * C_label1 not finite or not > 0; gamma not finite or < 0; eps not finite or not > 0; max_iter outside 0 .. 100 000 000; q_float32 other than 0 / 1; only one of
+ * offset / scale; a problems or Platt call before a dataset; k_prob outside 2 .. 64 or above n; a fold id outside 0 .. k_prob - 1.
+ * Not covered: shrinking and a kernel cache (every step reads two rows of D2), kernels other than RBF, more than two classes.        */
+#define DSP_SVM_TRAIN_MAX_ROWS 8192
+#define DSP_SVM_TRAIN_CONVERGED 0
+#define DSP_SVM_TRAIN_MAX_ITER 1
+#define DSP_SVM_TRAIN_ONE_CLASS 2
+#define DSP_SVM_TRAIN_EMPTY 3
+typedef struct dsp_svm_train_problem {
+    const int *rows;     /* [n_rows] on the HOST, strictly ascending */
+    long   n_rows;
+    double c_label0, c_label1, gamma;
+} dsp_svm_train_problem;
+typedef struct dsp_svm_train_config {
+    double eps;          /* > 0: the violation below which a problem has converged; 1e-3 = libsvm's */
+    int    max_iter;     /* 0: 1 000 000 */
+    int    q_float32;    /* 0: Q in float64; 1: the solver's kernel values rounded to float32, as libsvm caches Q */
+} dsp_svm_train_config;
+typedef struct dsp_svm_train_result {                                               /* 40 bytes */
+    double rho, objective, gap;
+    int n_iter, n_sv, n_bounded, status;
+} dsp_svm_train_result;
+typedef struct dsp_svm_fit_model {
+    float *offset, *scale;                 /* [n_features]           the caller's */
+    float *sv, *coef;                      /* [n][n_features], [n]   the caller's; the first n_sv are written */
+    long   n_sv, n_sv_label0;
+    float  rho, prob_a, prob_b, gamma;
+    int    platt_iter, reserved;
+    dsp_svm_train_result final;            /* the problem on all rows */
+} dsp_svm_fit_model;
+typedef struct dsp_svm_trainer dsp_svm_trainer;
+int dsp_svm_trainer_create(int device, int n_features, dsp_svm_trainer **out);
+void dsp_svm_trainer_destroy(dsp_svm_trainer *t);
+int dsp_svm_train_set_device(dsp_svm_trainer *t, const float *d_feat, long n, const int *scaler_rows, long n_scaler_rows,
+                             const float *offset, const float *scale,   /* HOST [n_features], both or neither: the caller's Scaler */
+                             float *offset_out, float *scale_out,       /* HOST [n_features], may be NULL */
+                             void *stream);
+int dsp_svm_train_problems_device(dsp_svm_trainer *t, const dsp_svm_train_problem *problems, long n_problems, const dsp_svm_train_config *cfg,
+                                  const int *labels,                    /* HOST [n] */
+                                  dsp_svm_train_result *results,        /* HOST [n_problems] */
+                                  double *d_coef,                       /* [n_problems][n] */
+                                  double *d_dec,                        /* [n_problems][n], may be NULL */
+                                  void *stream);
+int dsp_svm_platt_fit_device(dsp_svm_trainer *t, const double *d_dec_cv, const int *labels, const int *rows, long n_rows, double *a, double *b,
+                             int *n_iter, void *stream);
+int dsp_svm_folds(long n, int k, unsigned long long seed, int *fold_ids);
+int dsp_svm_balanced_weights(const int *labels, const int *rows, long n_rows, double c, double *c_label0, double *c_label1);
+long dsp_svm_model_from_training(const float *z, const int *labels, const double *coef, long n, int n_features, float *sv, float *coef_out,
+                                 long capacity, long *n_sv_label0);
+int dsp_svm_fit_device(dsp_svm_trainer *t, const float *d_feat, long n, const int *labels, const int *fold_ids, int k_prob,
+                       unsigned long long seed, double c_label0, double c_label1, double gamma, const dsp_svm_train_config *cfg,
+                       dsp_svm_fit_model *model, void *stream);
+/* the trainer's standardised rows z[n][n_features] of the current dataset, copied to the HOST (waits for the stream) */
+int dsp_svm_train_rows_host(dsp_svm_trainer *t, float *z, void *stream);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
