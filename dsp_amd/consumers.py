@@ -15,6 +15,7 @@
   ScoreCalibrator   CAL_A * raw_score + CAL_B + CAL_C * log(n_frames), and the fit the reference leaves "to be learned on dev set"
                                                               2fa/audio/speaker/adapt_ubm.py:27-28,97-99
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
+  StopTrainer    the stop-word net's Keras fit, many seeds at once  2fa/audio/word/python/keyword_classifier.py:155-232
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
 
 Trained parameters are passed in as arrays (the reference compiles them in from model_params.h / gmm_params.inc).
@@ -171,6 +172,184 @@ class StopModel:
         """The reference's classify_signal(signal, num_samples) on a host buffer."""
         signal = np.ascontiguousarray(signal, np.float32)
         return float(self._L.dsp_classify_signal(self._h, signal.ctypes.data, signal.size))
+
+    @classmethod
+    def train(cls, plan: MfccPlan, clips, labels, train_rows=None, val_rows=None, seeds=range(8), device: int = 0, max_frames: int = 500,
+              units=(4, 2, 2, 1), **hyper):
+        """Trains the net from audio (StopTrainer.fit, which takes `hyper`) and returns (the StopModel built on the best run, the fit's
+        report).  clips: cuda float32 [n][samples]; labels 0 / 1 on the host; train_rows / val_rows default to every row (the validation
+        loss is then the training rows' without dropout)."""
+        mfcc = plan.clips(clips, max_frames)
+        n, t, n_coef = mfcc.shape
+        rows = np.arange(n, dtype=np.int32)
+        trainer = StopTrainer(n_coef, max_frames, units, device)
+        try:
+            trainer.set(mfcc.reshape(n * t, n_coef), np.arange(n + 1, dtype=np.int64) * t, scaler_rows=train_rows)
+            params, report = trainer.fit(labels, rows if train_rows is None else train_rows, rows if val_rows is None else val_rows, seeds=seeds, **hyper)
+        finally:
+            trainer.close()
+        return cls(params, device), report
+
+
+def stop_train_param_count(n_coef: int, max_frames: int, units) -> int:
+    """Host only: the number of parameters of a model shape (dsp_stop_train_param_count)."""
+    u = (C.c_int * 4)(*[int(v) for v in units])
+    return _lib.check(_lib.load().dsp_stop_train_param_count(int(n_coef), int(max_frames), u), "dsp_stop_train_param_count")
+
+
+def stop_train_uniform(seed: int, stream: int, counter: int) -> float:
+    """Host only: the library's draw u in [0, 1) (dsp_stop_train_uniform)."""
+    return float(_lib.load().dsp_stop_train_uniform(int(seed), int(stream), int(counter)))
+
+
+def stop_train_order(n: int, seed: int, epoch: int) -> np.ndarray:
+    """Host only: the permutation of 0 .. n - 1 an epoch's training rows come in (dsp_stop_train_order)."""
+    order = np.empty(max(int(n), 0), np.int32)
+    _lib.check(_lib.load().dsp_stop_train_order(int(n), int(seed), int(epoch), order.ctypes.data), "dsp_stop_train_order")
+    return order
+
+
+def stop_train_init(n_coef: int, max_frames: int, units, seed: int) -> np.ndarray:
+    """Host only: the initial weights of a run, float64 [n_params] (dsp_stop_train_init)."""
+    u = (C.c_int * 4)(*[int(v) for v in units])
+    params = np.empty(stop_train_param_count(n_coef, max_frames, units), np.float64)
+    _lib.check(_lib.load().dsp_stop_train_init(int(n_coef), int(max_frames), u, int(seed), params.ctypes.data), "dsp_stop_train_init")
+    return params
+
+
+def stop_model_from_training(n_coef: int, max_frames: int, units, params, mean, scale) -> dict:
+    """Host only: flat float64 parameters plus the Scaler -> the dict StopModel takes, float32 (dsp_stop_model_from_training)."""
+    u = (C.c_int * 4)(*[int(v) for v in units])
+    n_in = int(n_coef) * int(max_frames)
+    params = np.ascontiguousarray(params, np.float64).reshape(-1)
+    mean, scale = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(scale, np.float32).reshape(-1)
+    if params.size != stop_train_param_count(n_coef, max_frames, units) or mean.size != n_in or scale.size != n_in:
+        raise ValueError("params must hold n_params values, mean and scale n_coef * max_frames")
+    arrays = np.empty(2 * n_in + params.size, np.float32)
+    m = _lib.StopModelParams()
+    _lib.check(_lib.load().dsp_stop_model_from_training(int(n_coef), int(max_frames), u, params.ctypes.data, mean.ctypes.data, scale.ctypes.data,
+                                                        arrays.ctypes.data, C.byref(m)), "dsp_stop_model_from_training")
+    out = {"n_coef": int(n_coef), "max_frames": int(max_frames), "scaler_mean": arrays[:n_in].copy(), "scaler_scale": arrays[n_in:2 * n_in].copy()}
+    fan = n_in
+    for l in range(4):
+        k0, b0 = (m.kernel[l] - arrays.ctypes.data) // 4, (m.bias[l] - arrays.ctypes.data) // 4
+        out[f"kernel{l}"], out[f"bias{l}"] = arrays[k0:k0 + fan * int(units[l])].copy(), arrays[b0:b0 + int(units[l])].copy()
+        fan = int(units[l])
+    return out
+
+
+class StopTrainer:
+    """dsp_stop_trainer: the stop-word net from labelled MFCC matrices, keyword_classifier.py:155-232 on the GPU -- the Scaler and many
+    Keras-style fits (seeds, folds, dropout or learning rates) per launch over one standardised matrix.  One stream at a time per trainer."""
+
+    HYPER = {"learning_rate": 1e-3, "dropout": (0.3, 0.3, 0.2), "batch_size": 32, "epochs": 50, "patience": 10, "restore_best": True}
+
+    def __init__(self, n_coef: int = 13, max_frames: int = 500, units=(4, 2, 2, 1), device: int = 0):
+        self._L = _lib.load()
+        self.units = tuple(int(u) for u in units)
+        if len(self.units) != 4:
+            raise ValueError("units must hold four layer widths")
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_stop_trainer_create(device, int(n_coef), int(max_frames), (C.c_int * 4)(*self.units), C.byref(h)), "dsp_stop_trainer_create")
+        self._h, self.n_coef, self.max_frames, self.device, self.n, self.f_used = h, int(n_coef), int(max_frames), device, 0, 0
+        self.n_params = stop_train_param_count(n_coef, max_frames, self.units)
+        self.mean = self.scale = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_stop_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set(self, mfcc, frame_offsets, scaler_rows=None, mean=None, scale=None):
+        """The dataset of the calls that follow (dsp_stop_train_set_device): clip i is rows [frame_offsets[i], frame_offsets[i + 1]) of the
+        ragged matrix mfcc (cuda float32 [F][n_coef]); fits the Scaler on `scaler_rows` (default: all clips) or takes the caller's mean /
+        scale -> (mean, scale) float32 [n_coef * max_frames]."""
+        fo = _frame_offsets(frame_offsets)
+        if fo.size < 2:
+            raise ValueError("frame_offsets must hold at least one clip")
+        mfcc = _scan_mfcc(mfcc, fo, self.n_coef)
+        if mfcc.device.index != self.device:
+            raise ValueError(f"mfcc is on GPU {mfcc.device.index}, the trainer on GPU {self.device}")
+        if (mean is None) != (scale is None):
+            raise ValueError("mean and scale must be given together")
+        n_in = self.n_coef * self.max_frames
+        rows = None if scaler_rows is None else np.ascontiguousarray(scaler_rows, np.int32)
+        given = None if mean is None else (np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(scale, np.float32).reshape(-1))
+        if given is not None and (given[0].size != n_in or given[1].size != n_in):
+            raise ValueError("mean and scale must hold n_coef * max_frames values")
+        m, s = np.empty(n_in, np.float32), np.empty(n_in, np.float32)
+        self.n = 0
+        _lib.check(self._L.dsp_stop_train_set_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data, None if rows is None else rows.ctypes.data,
+                                                     0 if rows is None else rows.size, None if given is None else given[0].ctypes.data,
+                                                     None if given is None else given[1].ctypes.data, m.ctypes.data, s.ctypes.data, self._stream()),
+                   "dsp_stop_train_set_device")
+        self.n, self.f_used = fo.size - 1, int(self._L.dsp_stop_train_used_features(self._h))
+        self.mean, self.scale = m, s
+        return m, s
+
+    def rows(self):
+        """the standardised rows of the dataset, float32 [n][F_used] on the host (used feature c * T_used + t is input c * max_frames + t)"""
+        z = np.empty((self.n, self.f_used), np.float32)
+        _lib.check(self._L.dsp_stop_train_rows_host(self._h, z.ctypes.data, self._stream()), "dsp_stop_train_rows_host")
+        return z
+
+    def train(self, runs, labels, prob: bool = True):
+        """Trains runs = [dict(train_rows=, val_rows=, seed=, and any of HYPER), ...] together (dsp_stop_train_runs_device) -> (results:
+        numpy records of STOP_TRAIN_RESULT_DTYPE [P], history cuda float64 [P][max epochs][2], prob cuda float64 [P][n] or None, params
+        cuda float64 [P][n_params])."""
+        import torch
+        labels = np.ascontiguousarray(labels, np.int32)
+        if labels.size != self.n:
+            raise ValueError(f"labels must hold the dataset's {self.n} clips")
+        table = (_lib.StopTrainRun * max(1, len(runs)))()
+        keep, max_epochs = [], 1
+        for k, r in enumerate(runs):
+            unknown = set(r) - set(self.HYPER) - {"train_rows", "val_rows", "seed"}
+            if unknown:
+                raise ValueError(f"runs[{k}]: unknown keys {sorted(unknown)}")
+            h = {**self.HYPER, **r}
+            tr = np.ascontiguousarray(h["train_rows"], np.int32).reshape(-1)
+            va = np.ascontiguousarray(h["val_rows"] if h.get("val_rows") is not None else [], np.int32).reshape(-1)
+            keep += [tr, va]
+            drop = tuple(float(d) for d in h["dropout"])
+            if len(drop) != 3:
+                raise ValueError(f"runs[{k}]: dropout must hold three rates")
+            table[k] = _lib.StopTrainRun(tr.ctypes.data if tr.size else None, va.ctypes.data if va.size else None, tr.size, va.size, int(h.get("seed", 0)),
+                                         float(h["learning_rate"]), (C.c_double * 3)(*drop), int(h["batch_size"]), int(h["epochs"]), int(h["patience"]),
+                                         int(bool(h["restore_best"])))
+            max_epochs = max(max_epochs, int(h["epochs"]))
+        results = np.zeros(len(runs), _lib.STOP_TRAIN_RESULT_DTYPE)
+        dev = torch.device("cuda", self.device)
+        history = torch.empty((len(runs), max_epochs, 2), dtype=torch.float64, device=dev)
+        params = torch.empty((len(runs), self.n_params), dtype=torch.float64, device=dev)
+        p = torch.empty((len(runs), self.n), dtype=torch.float64, device=dev) if prob else None
+        _lib.check(self._L.dsp_stop_train_runs_device(self._h, table, len(runs), labels.ctypes.data, results.ctypes.data, history.data_ptr(),
+                                                      p.data_ptr() if prob else None, params.data_ptr(), self._stream()), "dsp_stop_train_runs_device")
+        return results, history, p, params
+
+    def fit(self, labels, train_rows, val_rows, seeds=range(8), **hyper):
+        """All seeds in one call -> (the parameter dict StopModel takes for the run with the lowest best_val_loss, ties to the earliest
+        seed; report: dict with every run's result, so that a caller sees how many seeds died)."""
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("seeds must hold at least one seed")
+        runs = [dict(train_rows=train_rows, val_rows=val_rows, seed=s, **hyper) for s in seeds]
+        results, history, _p, params = self.train(runs, labels, prob=False)
+        loss = np.where(np.isnan(results["best_val_loss"]), np.inf, results["best_val_loss"])
+        best = int(np.argmin(loss))                                  # (argmin: the first of equals)
+        model = stop_model_from_training(self.n_coef, self.max_frames, self.units, params[best].cpu().numpy(), self.mean, self.scale)
+        return model, {"best": best, "seed": seeds[best], "seeds": seeds, "results": results, "history": history.cpu().numpy(),
+                       "params": params[best].cpu().numpy(), "n_dead_runs": int((results["n_dead_units"] > 0).sum())}
 
 
 def _gmm_params(g: dict):

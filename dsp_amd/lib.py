@@ -218,6 +218,28 @@ class SvmFitModel(C.Structure):
                 ("final", SvmTrainResult)]
 
 
+class StopTrainRun(C.Structure):
+    """dsp_stop_train_run (include/dsp_amd.h), 88 bytes: the run's rows on the host and its hyperparameters."""
+
+    _fields_ = [("train_rows", C.c_void_p), ("val_rows", C.c_void_p), ("n_train", C.c_long), ("n_val", C.c_long), ("seed", C.c_uint64),
+                ("learning_rate", C.c_double), ("dropout", C.c_double * 3), ("batch_size", C.c_int), ("epochs", C.c_int), ("patience", C.c_int),
+                ("restore_best", C.c_int)]
+
+
+class StopTrainResult(C.Structure):
+    """dsp_stop_train_result (include/dsp_amd.h), 40 bytes; STOP_TRAIN_RESULT_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("best_val_loss", C.c_double), ("last_loss", C.c_double), ("n_epochs", C.c_int), ("best_epoch", C.c_int), ("status", C.c_int),
+                ("val_correct", C.c_int), ("n_dead_units", C.c_int), ("reserved", C.c_int)]
+
+
+STOP_TRAIN_RESULT_DTYPE = [("best_val_loss", "<f8"), ("last_loss", "<f8"), ("n_epochs", "<i4"), ("best_epoch", "<i4"), ("status", "<i4"),
+                           ("val_correct", "<i4"), ("n_dead_units", "<i4"), ("reserved", "<i4")]
+STOP_TRAIN_CONVERGED_EARLY, STOP_TRAIN_MAX_EPOCHS, STOP_TRAIN_NO_VALIDATION, STOP_TRAIN_EMPTY = 0, 1, 2, 3
+STOP_TRAIN_STATUS = ("converged_early", "max_epochs", "no_validation", "empty")
+STOP_TRAIN_CAP_ROWS, STOP_TRAIN_CAP_UNITS, STOP_TRAIN_CAP_BATCH, STOP_TRAIN_CAP_EPOCHS, STOP_TRAIN_CAP_RUNS = 65536, 16, 256, 10000, 4096
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -288,6 +310,9 @@ SYMBOLS = [
     "dsp_calibrator_create", "dsp_calibrator_destroy", "dsp_calibration_duration_term", "dsp_calibration_fit_device", "dsp_calibration_apply_device",
     "dsp_svm_trainer_create", "dsp_svm_trainer_destroy", "dsp_svm_train_set_device", "dsp_svm_train_rows_host", "dsp_svm_train_problems_device",
     "dsp_svm_platt_fit_device", "dsp_svm_folds", "dsp_svm_balanced_weights", "dsp_svm_model_from_training", "dsp_svm_fit_device",
+    "dsp_stop_trainer_create", "dsp_stop_trainer_destroy", "dsp_stop_train_set_device", "dsp_stop_train_used_features", "dsp_stop_train_rows_host",
+    "dsp_stop_train_runs_device", "dsp_stop_train_param_count", "dsp_stop_train_uniform", "dsp_stop_train_order", "dsp_stop_train_init",
+    "dsp_stop_model_from_training",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -478,6 +503,17 @@ def load() -> C.CDLL:
     L.dsp_calibration_fit_device.restype = ip
     L.dsp_calibration_apply_device.argtypes = [vp, vp, C.c_long, C.c_long, lp, C.POINTER(Calibration), vp, vp]; L.dsp_calibration_apply_device.restype = ip
     dp = C.POINTER(C.c_double)
+    L.dsp_stop_trainer_create.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(vp)]; L.dsp_stop_trainer_create.restype = ip
+    L.dsp_stop_trainer_destroy.argtypes = [vp]; L.dsp_stop_trainer_destroy.restype = None
+    L.dsp_stop_train_set_device.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, vp, vp, vp, vp, vp]; L.dsp_stop_train_set_device.restype = ip
+    L.dsp_stop_train_used_features.argtypes = [vp]; L.dsp_stop_train_used_features.restype = C.c_long
+    L.dsp_stop_train_rows_host.argtypes = [vp, vp, vp]; L.dsp_stop_train_rows_host.restype = ip
+    L.dsp_stop_train_runs_device.argtypes = [vp, C.POINTER(StopTrainRun), C.c_long, vp, vp, vp, vp, vp, vp]; L.dsp_stop_train_runs_device.restype = ip
+    L.dsp_stop_train_param_count.argtypes = [ip, ip, C.POINTER(ip)]; L.dsp_stop_train_param_count.restype = C.c_long
+    L.dsp_stop_train_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]; L.dsp_stop_train_uniform.restype = C.c_double
+    L.dsp_stop_train_order.argtypes = [C.c_long, C.c_uint64, C.c_long, vp]; L.dsp_stop_train_order.restype = ip
+    L.dsp_stop_train_init.argtypes = [ip, ip, C.POINTER(ip), C.c_uint64, vp]; L.dsp_stop_train_init.restype = ip
+    L.dsp_stop_model_from_training.argtypes = [ip, ip, C.POINTER(ip), vp, vp, vp, vp, C.POINTER(StopModelParams)]; L.dsp_stop_model_from_training.restype = ip
     L.dsp_svm_trainer_create.argtypes = [ip, ip, C.POINTER(vp)]; L.dsp_svm_trainer_create.restype = ip
     L.dsp_svm_trainer_destroy.argtypes = [vp]; L.dsp_svm_trainer_destroy.restype = None
     L.dsp_svm_train_set_device.argtypes = [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp, vp]; L.dsp_svm_train_set_device.restype = ip

@@ -1296,6 +1296,116 @@ int dsp_svm_fit_device(dsp_svm_trainer *t, const float *d_feat, long n, const in
 /* the trainer's standardised rows z[n][n_features] of the current dataset, copied to the HOST (waits for the stream) */
 int dsp_svm_train_rows_host(dsp_svm_trainer *t, float *z, void *stream);
 
+/* STOP-NET TRAINING: the net behind classify_signal from labelled MFCC matrices -- 2fa/audio/word/python/keyword_classifier.py:155-232
+ * (StandardScaler, Dense 4-2-2-1 with dropout, Adam, binary cross-entropy, EarlyStopping(patience=10, restore_best_weights=True)) as
+ * MANY Keras-style fits per launch over one standardised feature matrix: seeds, folds, dropout
+ * and learning rates side by side, the best kept by validation loss.  The helpers below are the definition of every draw.
+ *
+ * Dataset.  dsp_stop_train_set_device takes a ragged matrix d_mfcc[..][n_coef] (float32, the trainer's device) with HOST
+ * frame_offsets[n + 1] as dsp_stop_scan_device does; clip i is rows [frame_offsets[i], frame_offsets[i + 1]), T_i of them.  Feature
+ * j = c max_frames + t of clip i is mfcc[off_i + t][c] for t < min(T_i, max_frames) and 0 otherwise (stop_detector.c:36-50).  The
+ * Scaler is, per feature over scaler_rows[n_scaler_rows] (HOST, NULL: all n rows), mean and scale = population std (std 0: 1, as
+ * sklearn's StandardScaler.scale_): float64 sums with a centred second pass, a lane's rows ascending (lane l of 256 takes rows l, l +
+ * 256, ...), the 256 partials by a 6-level xor butterfly per wavefront and the four wavefronts as (0 + 1) + (2 + 3); written as float32
+ * in the layout dsp_stop_model_params reads.  The caller may give mean and scale (HOST [n_coef max_frames], both or neither) instead.
+ * The trainer keeps Z[n][F_used] = fl32(fl32(x - mean) / (scale == 0 ? 1 : scale)), the inference kernels' expression, with
+ * T_used = min(max_frames, max_i T_i), F_used = n_coef T_used and used feature c T_used + t = feature c max_frames + t.  Features past
+ * it are 0 for every clip: their gradients are exactly 0, under Adam their weights stay at the initial draw, the kernels skip them and
+ * the returned layer-1 kernel carries their initial values.  mean_out / scale_out (HOST [n_coef max_frames], may be NULL) receive the
+ * Scaler; with either given the call waits for the stream.  dsp_stop_train_used_features returns F_used (0: no dataset),
+ * dsp_stop_train_rows_host copies Z to the HOST.
+ *
+ * Runs.  dsp_stop_train_runs_device trains n_runs of them together, one workgroup each, one launch per epoch.  A run follows Keras's
+ * fit.  Init: kernels Glorot-uniform, w = (2 u - 1) sqrt(6 / (fan_in + fan_out)), fan_in of layer 1 the full n_coef max_frames; biases
+ * 0.  Each epoch: the training rows in the order train_rows[order[k]] of the epoch's keyed permutation, ceil(n_train / batch) steps, the
+ * last batch the short remainder averaged over its own size.  Forward: ReLU hidden layers with inverted dropout (kept when u >= rate,
+ * kept values times 1 / (1 - rate); rate 0: no draw), a sigmoid output.  Loss: binary cross-entropy from the logit a, max(a, 0) - a y +
+ * log1p(exp(-|a|)); its gradient (p - y) / B; the ReLU derivative is 1 only where the pre-activation is > 0.  Adam in Keras's form, t =
+ * 1, 2, ..., beta1 0.9, beta2 0.999, eps 1e-7: lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), m = beta1 m + (1 - beta1) g, v = beta2 v +
+ * (1 - beta2) g^2, w -= lr_t m / (sqrt(v) + eps).  After each epoch val_loss is the mean loss over val_rows without dropout; val_loss <
+ * best (strict; NaN never improves) snapshots the weights, sets best_epoch and wait = 0, otherwise ++wait and wait >= patience stops
+ * the run.  Returned are the best snapshot when restore_best is set and there is one (Keras 3's on_train_end), else the last weights;
+ * without validation rows there is no early stop and the last weights are returned.  Weights, moments, activations, losses and every
+ * sum are float64, Z is widened as it is read; no float atomics, nothing passes between runs, and every sum over features, a batch or
+ * the validation rows has an order fixed by the shapes alone: a run's outputs are the same bits alone, among hundreds of others,
+ * reordered, and after the workspace has grown.
+ *
+ * results[p] on the HOST: n_epochs run; best_epoch (0-based, -1: none) and best_val_loss (NaN: none); last_loss, the last epoch's
+ * training loss; status; val_correct, the validation rows on the right side of P > 0.5 at the returned weights; n_dead_units, the
+ * hidden units whose activation is 0 on every training row at the returned weights (the all-ReLUs-dead plateau, as a number).
+ * d_history[P][max_p epochs_p][2] (device, float64): the training loss as Keras reports it (the sample-weighted mean of the batch
+ * losses, dropout on) and val_loss; epochs not run hold NaN.  d_prob[P][n] (device, float64, may be NULL): P(stop) of EVERY row of the
+ * dataset under run p's returned weights, dropout off; rows outside train_rows are held-out predictions.  d_params[P][n_params]
+ * (device, float64): the returned weights flat, kernel1, bias1, ..., kernel4, bias4, kernels (in, out) row-major.  n_train == 0 is
+ * DSP_STOP_TRAIN_EMPTY: nothing is trained, the initial weights are returned with n_epochs 0; n_val == 0 is DSP_STOP_TRAIN_NO_VALIDATION.
+ * The call enqueues the epochs without a host round trip, looks at the runs' stop flags every 8 epochs and returns with results filled.
+ *
+ * Random numbers, the library's own (Keras's cannot be reproduced): mix = splitmix64's finaliser as for dsp_kmeans_*, G =
+ * 0x9E3779B97F4A7C15, draw(seed, stream, counter) = mix(mix(seed + (stream + 1) G) + (counter + 1) G), u = (draw >> 11) 2^-53.  Stream
+ * 0: initial weights, counter = flat parameter index.  Stream 1: the epoch order, a 4-round Feistel network on the smallest even number
+ * of bits (at least 2) covering n_train, (L, R) <- (R, L ^ (mix(key_epoch + (r + 1) G + R) & mask)) for r = 0 .. 3, cycle-walked until
+ * the value is < n_train, key_epoch = draw(seed, 1, epoch).  Stream 2: dropout, counter = ((global_step 3 + layer) 256 + slot) 16 +
+ * unit with global_step counting the run's optimiser steps from 0, layer 0 .. 2 and slot the sample's place in its batch.
+ *
+ * Host helpers (no device).  dsp_stop_train_param_count; dsp_stop_train_uniform; dsp_stop_train_order (order[n] of an epoch);
+ * dsp_stop_train_init (params[n_params], the initial weights); dsp_stop_model_from_training: float64 parameters plus the Scaler as the
+ * float32 arrays of dsp_stop_model_params in the caller's `arrays` (2 n_coef max_frames + n_params floats), `model` pointing into them.
+ *
+ * One stream at a time per trainer; the workspace (Z, the runs' slabs and tables) is grow-only.  dsp_stop_trainer_create touches no
+ * device.  DSP_EINVAL, before a device is touched and naming the argument: a NULL that may not be; n_coef, max_frames < 1, a unit
+ * count outside 1 .. 16 or units[3] != 1; n outside 1 .. 65536; frame_offsets negative or decreasing; a scaler, training or validation
+ * row outside 0 .. n - 1, run rows not strictly ascending; a label other than 0 / 1; only one of mean / scale, or a value not finite;
+ * a runs call before a dataset; n_runs above 4096; batch_size outside 1 .. 256, epochs outside 1 .. 10000, patience < 0, a dropout
+ * rate outside [0, 1), a learning rate not finite or not > 0, restore_best other than 0 / 1.
+ * Not covered: an LDS-resident variant for short clips, float32 training arithmetic, other optimisers, class weights.                */
+#define DSP_STOP_TRAIN_CAP_ROWS 65536
+#define DSP_STOP_TRAIN_CAP_UNITS 16
+#define DSP_STOP_TRAIN_CAP_BATCH 256
+#define DSP_STOP_TRAIN_CAP_EPOCHS 10000
+#define DSP_STOP_TRAIN_CAP_RUNS 4096
+#define DSP_STOP_TRAIN_CONVERGED_EARLY 0
+#define DSP_STOP_TRAIN_MAX_EPOCHS 1
+#define DSP_STOP_TRAIN_NO_VALIDATION 2
+#define DSP_STOP_TRAIN_EMPTY 3
+typedef struct dsp_stop_train_run {                                                 /* 88 bytes */
+    const int *train_rows, *val_rows;    /* HOST, strictly ascending; val_rows may be NULL with n_val 0 */
+    long   n_train, n_val;
+    unsigned long long seed;
+    double learning_rate;                /* 1e-3 */
+    double dropout[3];                   /* 0.3, 0.3, 0.2 */
+    int    batch_size;                   /* 32 */
+    int    epochs;                       /* 50 */
+    int    patience;                     /* 10 */
+    int    restore_best;                 /* 1 */
+} dsp_stop_train_run;
+typedef struct dsp_stop_train_result {                                              /* 40 bytes */
+    double best_val_loss, last_loss;
+    int n_epochs, best_epoch, status, val_correct, n_dead_units, reserved;
+} dsp_stop_train_result;
+typedef struct dsp_stop_trainer dsp_stop_trainer;
+int dsp_stop_trainer_create(int device, int n_coef, int max_frames, const int *units /* [4] */, dsp_stop_trainer **out);
+void dsp_stop_trainer_destroy(dsp_stop_trainer *t);
+int dsp_stop_train_set_device(dsp_stop_trainer *t, const float *d_mfcc, long n, const long *frame_offsets /* HOST [n + 1] */,
+                              const int *scaler_rows, long n_scaler_rows,
+                              const float *mean, const float *scale,         /* HOST [n_coef max_frames], both or neither */
+                              float *mean_out, float *scale_out,             /* HOST [n_coef max_frames], may be NULL */
+                              void *stream);
+long dsp_stop_train_used_features(const dsp_stop_trainer *t);
+int dsp_stop_train_rows_host(dsp_stop_trainer *t, float *z /* HOST [n][F_used] */, void *stream);
+int dsp_stop_train_runs_device(dsp_stop_trainer *t, const dsp_stop_train_run *runs, long n_runs,
+                               const int *labels,                            /* HOST [n], 0 / 1 */
+                               dsp_stop_train_result *results,               /* HOST [n_runs] */
+                               double *d_history,                            /* [n_runs][max epochs][2] */
+                               double *d_prob,                               /* [n_runs][n], may be NULL */
+                               double *d_params,                             /* [n_runs][n_params] */
+                               void *stream);
+long dsp_stop_train_param_count(int n_coef, int max_frames, const int *units);
+double dsp_stop_train_uniform(unsigned long long seed, unsigned long long stream, unsigned long long counter);
+int dsp_stop_train_order(long n, unsigned long long seed, long epoch, int *order);
+int dsp_stop_train_init(int n_coef, int max_frames, const int *units, unsigned long long seed, double *params);
+int dsp_stop_model_from_training(int n_coef, int max_frames, const int *units, const double *params, const float *mean, const float *scale,
+                                 float *arrays, dsp_stop_model_params *model);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
