@@ -480,11 +480,7 @@ class Scanner:
         return wo, prob, mean, label
 
 
-def _long_array(a, size, what):
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
-    if a.ndim != 1 or a.size != size:
-        raise ValueError(f"{what} must hold {size} entries")
-    return a
+_long_array = _lib.long_array
 
 
 def _chunk_offsets(chunk_offsets, n_streams):
@@ -531,10 +527,12 @@ class StreamSession:
     returns the MFCC rows and the window scores that became complete with it; concatenated over the pushes they are, bit for bit,
     MfccPlan.clips_ragged and Scanner.run on the whole recording -- except that a stream has no window before it holds window_frames
     rows.  dtype: torch.float32 samples, or torch.int16 PCM ([total] mono, [total][2] interleaved stereo with stereo_mode 0 = channel
-    0 / 1 = average; channels=2 selects stereo).  One stream at a time per session."""
+    0 / 1 = average; channels=2 selects stereo).  rate_in: the feeds arrive at this rate instead of the plan's -- the session puts a
+    StreamResampler (rate_in -> the plan's sample_rate, same dtype / channels / stereo_mode) in front of itself, push() takes chunks at
+    rate_in, and counts() keeps counting samples at the plan's rate.  One stream at a time per session."""
 
     def __init__(self, plan: MfccPlan, n_streams: int, stop: StopModel | None = None, speaker: SpeakerModel | None = None,
-                 window_frames: int = 98, hop_frames: int = 10, dtype=None, stereo_mode: int = 0, channels: int = 1):
+                 window_frames: int = 98, hop_frames: int = 10, dtype=None, stereo_mode: int = 0, channels: int = 1, rate_in: int | None = None):
         import torch
         self._L = _lib.load()
         dtype = torch.float32 if dtype is None else dtype
@@ -549,17 +547,27 @@ class StreamSession:
         self.cfg = _scan_config(window_frames, hop_frames) if (stop or speaker) else None
         if self.cfg is not None and self.cfg.hop_frames > self.cfg.window_frames:
             raise ValueError("hop_frames must not exceed window_frames")
+        self.resampler = None
+        if rate_in is not None:      # the resampler decodes the caller's format; the session behind it takes its float mono output
+            from .resample import StreamResampler
+            self.resampler = StreamResampler(rate_in, plan.cfg.sample_rate, n_streams, dtype, stereo_mode, channels, plan.device)
+        own = (1, 0, 0) if self.resampler is not None else (int(channels), int(stereo_mode), int(dtype == torch.int16))
         h = C.c_void_p()
         _lib.check(self._L.dsp_stream_session_create(plan._h, stop._h if stop else None, speaker._h if speaker else None,
-                                                     C.byref(self.cfg) if self.cfg is not None else None, int(n_streams), int(channels),
-                                                     int(stereo_mode), int(dtype == torch.int16), C.byref(h)), "dsp_stream_session_create")
+                                                     C.byref(self.cfg) if self.cfg is not None else None, int(n_streams), *own, C.byref(h)),
+                   "dsp_stream_session_create")
         self._h, self.plan, self.stop, self.speaker = h, plan, stop, speaker      # (the session borrows them: keep them alive)
         self.n_streams, self.dtype, self.channels, self.device = int(n_streams), dtype, int(channels), plan.device
+        if self.resampler is not None:
+            _lib.check(self._L.dsp_stream_session_attach_resampler(self._h, self.resampler._h), "dsp_stream_session_attach_resampler")
 
     def close(self):
         if getattr(self, "_h", None):
             self._L.dsp_stream_session_destroy(self._h)
             self._h = None
+        if getattr(self, "resampler", None) is not None:
+            self.resampler.close()
+            self.resampler = None
 
     def __del__(self):
         try:
@@ -599,7 +607,9 @@ class StreamSession:
         co = _chunk_offsets(chunk_offsets, self.n_streams)
         if int(co[-1]) > chunks.shape[0]:
             raise ValueError("chunk_offsets run past the end of chunks")
-        ro, wo = stream_push_plan(self.plan.cfg, self.counts()[0], co, *((self.cfg.window_frames, self.cfg.hop_frames) if self.cfg is not None else ()))
+        rs = getattr(self, "resampler", None)
+        at_rate = rs.plan(co) if rs is not None else co      # the chunks as the MFCC front end will see them
+        ro, wo = stream_push_plan(self.plan.cfg, self.counts()[0], at_rate, *((self.cfg.window_frames, self.cfg.hop_frames) if self.cfg is not None else ()))
         if wo is None:
             wo = np.zeros(self.n_streams + 1, np.int64)
         nr, nw, dev = int(ro[-1]), int(wo[-1]), chunks.device

@@ -1,6 +1,7 @@
 // capi_resample.cpp -- the C ABI of the polyphase FIR resampler (include/dsp_amd.h dsp_resample_*): the ratio, the
 // Kaiser-windowed sinc taps in float64 (scipy.signal.resample_poly's defaults), the output offsets, and the entries that put a ragged or
-// uniform batch of recordings through resample_kernels.hip.
+// uniform batch of recordings through resample_kernels.hip; behind them the streaming resampler (dsp_stream_resample*),
+// which emits the same outputs from feeds that arrive in chunks.
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -8,6 +9,8 @@
 
 #include "capi_util.hpp"
 #include "resample_kernels.hpp"
+#include "stream_kernels.hpp"
+#include "stream_resample.hpp"
 
 using dsp::capi_fail;
 
@@ -101,6 +104,22 @@ dsp::ResampleShape make_shape(const Ratio &r)
     s.span = span_of(s.tile);
     s.lds_bytes = s.staged ? bytes_of(s.tile) : s.tile * 4;
     return s;
+}
+
+// the device table [up][row] on the current device: the taps rounded once to float32; branch p = taps p, p + up, ... reversed and zero
+// filled to `row`
+int upload_taps(const Ratio &ratio, const dsp::ResampleShape &s, dsp::DeviceBuf<float> &taps)
+{
+    const std::vector<double> h = make_taps(ratio);
+    std::vector<float> table((size_t)s.up * s.row, 0.0f);
+    for (int p = 0; p < s.up; ++p)
+        for (int jj = 0; jj < s.taps; ++jj) {
+            const long idx = p + (long)(s.taps - 1 - jj) * s.up;
+            if (idx <= 2L * s.half) table[(size_t)p * s.row + jj] = (float)h[(size_t)idx];
+        }
+    if (taps.alloc(table.size() * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc of the taps");
+    DSP_CAPI_HIP(hipMemcpy(taps, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DSP_OK;
 }
 
 }  // namespace
@@ -219,18 +238,8 @@ int dsp_resampler_create(int device, int rate_in, int rate_out, dsp_resampler **
     r->device = device;
     r->ratio = ratio;
     r->shape = make_shape(ratio);
-    const dsp::ResampleShape &s = r->shape;
-    // rounded once to float32; branch p = taps p, p + up, ... reversed and zero filled to `row`
-    const std::vector<double> h = make_taps(ratio);
-    std::vector<float> table((size_t)s.up * s.row, 0.0f);
-    for (int p = 0; p < s.up; ++p)
-        for (int jj = 0; jj < s.taps; ++jj) {
-            const long idx = p + (long)(s.taps - 1 - jj) * s.up;
-            if (idx <= 2L * s.half) table[(size_t)p * s.row + jj] = (float)h[(size_t)idx];
-        }
     DSP_ON_DEVICE(device);
-    if (r->taps.alloc(table.size() * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc of the taps");
-    DSP_CAPI_HIP(hipMemcpy(r->taps, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (const int rc = upload_taps(ratio, r->shape, r->taps)) return rc;
     *out = r.release();
     return DSP_OK;
 }
@@ -283,6 +292,341 @@ int dsp_resample_host(int rate_in, int rate_out, const float *in, long n, float 
     const long offsets[2] = {0, n};
     if (const int rc = dsp_resample_ragged_device(r, d_in, 1, offsets, d_out, nullptr)) return rc;
     DSP_CAPI_HIP(hipMemcpy(out, d_out, (size_t)n_out * 4, hipMemcpyDeviceToHost));      // (the null stream: ordered behind the kernel)
+    return DSP_OK;
+}
+
+}  // extern "C"
+
+// ---- live streams: the same outputs from a feed that arrives in chunks (include/dsp_amd.h dsp_stream_resample*) ----
+// A stream's state is ONE host counter, the sample frames received (N): outputs emitted = K(N), first carried sample = c(N).  The carry
+// buffer holds samples [c(N), N) of every stream in the caller's own format and nothing else, so a reset is a store to the counter.
+namespace {
+
+constexpr long kMaxReceived = LONG_MAX / 4096;      // N up + half and K(N) down + half stay far inside a long (up, down <= 1024)
+
+struct StreamRatio {
+    Ratio r{};
+    int taps = 1;                                   // T
+    bool copy() const { return r.up == 1 && r.down == 1; }
+    long emitted(long n) const                      // K(N)
+    {
+        if (copy()) return n;
+        const long a = n * r.up - 1 - r.half;
+        return a >= 0 ? a / r.down + 1 : 0;
+    }
+    long carry_start(long n) const                  // c(N) = max(0, i_max(K(N)) - (T - 1))
+    {
+        if (copy()) return n;
+        return std::max(0L, (emitted(n) * r.down + r.half) / r.up - (long)(taps - 1));
+    }
+    long whole(long n) const { return (n * r.up + r.down - 1) / r.down; }      // ceil(N up / down)
+};
+
+StreamRatio stream_ratio(const Ratio &r)
+{
+    StreamRatio s;
+    s.r = r;
+    s.taps = (2 * r.half + r.up) / r.up;
+    return s;
+}
+
+// oo[n + 1] = prefix sums of K(received + chunk) - K(received); the total, or < 0
+long plan_stream_push(const StreamRatio &sr, const long *received, const long *co, long n, long *oo)
+{
+    oo[0] = 0;
+    for (long s = 0; s < n; ++s) {
+        const long len = co[s + 1] - co[s], n0 = received ? received[s] : 0;
+        if (co[s] < 0 || len < 0)
+            return capi_fail(DSP_EINVAL, "chunk_offsets must be non-negative and non-decreasing (stream " + std::to_string(s) + ")");
+        if (n0 < 0) return capi_fail(DSP_EINVAL, "received must be non-negative (stream " + std::to_string(s) + ")");
+        if (len > INT32_MAX) return capi_fail(DSP_EINVAL, "a chunk must be shorter than 2^31 sample frames (stream " + std::to_string(s) + ")");
+        if (n0 > kMaxReceived - len) return capi_fail(DSP_EINVAL, "the sample counter of stream " + std::to_string(s) + " would overflow");
+        oo[s + 1] = oo[s] + (sr.emitted(n0 + len) - sr.emitted(n0));
+    }
+    return oo[n];
+}
+
+long round_up16(long x) { return (x + 15) / 16 * 16; }
+
+}  // namespace
+
+struct dsp_stream_resampler {
+    int device = 0, rate_in = 0, rate_out = 0, in_kind = 0;
+    StreamRatio sr;
+    dsp::ResampleShape shape{};
+    long n_streams = 0;
+    long es = 4;                          // bytes per sample frame: 4 float, 2 mono int16, 4 stereo int16
+    long half_stride = 0;                 // bytes of one half of a stream's carry slot (T - 1 sample frames, rounded up to 16)
+    std::vector<long> received;           // THE state
+    // which half of its slot a stream's carry lies in: a push that keeps part of the old carry and moves it forward writes the new
+    // carry into the other half, so that no run of the copy launch reads what another writes
+    std::vector<char> side, next_side;
+    bool broken = false;
+    dsp::DeviceBuf<float> taps;
+    dsp::DeviceBuf<char> d_carry;         // [n_streams][2][half_stride]
+    std::vector<long> oo;
+    std::vector<dsp::StreamResampleSpan> spans;
+    std::vector<dsp::ResampleSpan> copy_spans;
+    std::vector<dsp::CopyRun> runs;
+    dsp::SpanRing ring;                   // a push's span table and run table on their way to the GPU
+    std::mutex mu;
+};
+
+namespace dsp {
+
+StreamResamplerInfo stream_resampler_info(const dsp_stream_resampler *rs) { return StreamResamplerInfo{rs->device, rs->rate_out, rs->n_streams}; }
+
+long stream_resampler_plan(dsp_stream_resampler *rs, const long *chunk_offsets, long *out_offsets)
+{
+    std::lock_guard<std::mutex> lock(rs->mu);
+    return plan_stream_push(rs->sr, rs->received.data(), chunk_offsets, rs->n_streams, out_offsets);
+}
+
+bool stream_resampler_broken(dsp_stream_resampler *rs)
+{
+    std::lock_guard<std::mutex> lock(rs->mu);
+    return rs->broken;
+}
+
+}  // namespace dsp
+
+namespace {
+
+// the table of spans (and of copy runs behind it) into a leased slot, uploaded; d_spans / d_runs: where they lie on the GPU
+template <class Span>
+int upload_tables(dsp_stream_resampler *rs, const std::vector<Span> &spans, dsp::SpanRing::Lease &slot, const Span *&d_spans, const dsp::CopyRun *&d_runs,
+                  hipStream_t st)
+{
+    static_assert(sizeof(Span) % 8 == 0, "the run table behind the spans stays 8-byte aligned");
+    const size_t sb = spans.size() * sizeof(Span), rb = rs->runs.size() * sizeof(dsp::CopyRun);
+    DSP_CAPI_HIP(rs->ring.acquire(sb + rb, slot));
+    if (sb) std::memcpy(slot.h(), spans.data(), sb);
+    if (rb) std::memcpy(static_cast<char *>(slot.h()) + sb, rs->runs.data(), rb);
+    DSP_CAPI_HIP(slot.upload(sb + rb, st));
+    d_spans = static_cast<const Span *>(slot.d());
+    d_runs = reinterpret_cast<const dsp::CopyRun *>(static_cast<const char *>(slot.d()) + sb);
+    return DSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long dsp_stream_resample_plan(int rate_in, int rate_out, const long *received, const long *chunk_offsets, long n_streams, long *out_offsets)
+{
+    Ratio r;
+    if (const int rc = reduce(rate_in, rate_out, r)) return rc;
+    if (n_streams < 0) return capi_fail(DSP_EINVAL, "n_streams < 0");
+    if (!out_offsets || (n_streams > 0 && !chunk_offsets)) return capi_fail(DSP_EINVAL, "chunk_offsets and out_offsets must not be NULL");
+    return plan_stream_push(stream_ratio(r), received, chunk_offsets, n_streams, out_offsets);
+}
+
+int dsp_stream_resampler_create(int device, int rate_in, int rate_out, long n_streams, int channels, int stereo_mode, int pcm16, dsp_stream_resampler **out)
+{
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    int kind = 0;
+    if (pcm16) {
+        if ((kind = dsp::pcm16_kind(channels, stereo_mode)) < 0) return kind;
+    } else if (channels != 1) {
+        return capi_fail(DSP_EINVAL, "float samples are mono: channels must be 1");
+    }
+    Ratio ratio;
+    if (const int rc = reduce(rate_in, rate_out, ratio)) return rc;
+    const dsp::ResampleShape shape = make_shape(ratio);
+    if (!shape.staged)
+        return capi_fail(DSP_EINVAL, "resampling " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " has " + std::to_string(shape.taps) +
+                                         " taps per output: a stream would carry more samples than a block stages (not a live-feed ratio)");
+    if (n_streams < 0 || n_streams >= (1L << 31)) return capi_fail(DSP_EINVAL, "n_streams must be in [0, 2^31)");
+    if (const int rc = dsp::check_device(device)) return rc;
+    auto rs = std::make_unique<dsp_stream_resampler>();
+    rs->device = device;
+    rs->rate_in = rate_in;
+    rs->rate_out = rate_out;
+    rs->in_kind = kind;
+    rs->sr = stream_ratio(ratio);
+    rs->shape = shape;
+    rs->n_streams = n_streams;
+    rs->es = kind == 1 ? 2 : 4;
+    rs->half_stride = rs->sr.copy() ? 0 : round_up16((long)(shape.taps - 1) * rs->es);
+    rs->received.assign((size_t)n_streams, 0);
+    rs->side.assign((size_t)n_streams, 0);
+    rs->next_side.assign((size_t)n_streams, 0);
+    rs->oo.assign((size_t)n_streams + 1, 0);
+    DSP_ON_DEVICE(device);
+    if (!rs->sr.copy())
+        if (const int rc = upload_taps(ratio, shape, rs->taps)) return rc;
+    if (n_streams > 0 && rs->half_stride > 0 && rs->d_carry.alloc((size_t)n_streams * 2 * (size_t)rs->half_stride) != hipSuccess)
+        return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
+    *out = rs.release();
+    return DSP_OK;
+}
+
+void dsp_stream_resampler_destroy(dsp_stream_resampler *rs)
+{
+    if (!rs) return;
+    dsp::DeviceScope scope(rs->device);
+    rs->ring.release();
+    delete rs;
+}
+
+int dsp_stream_resampler_reset(dsp_stream_resampler *rs, const long *streams, long n, void *stream)
+{
+    (void)stream;      // nothing to enqueue: what a stream carries is defined by its counter
+    if (!rs) return capi_fail(DSP_EINVAL, "resampler is NULL");
+    std::lock_guard<std::mutex> lock(rs->mu);
+    if (!streams) {
+        std::fill(rs->received.begin(), rs->received.end(), 0L);
+        rs->broken = false;
+        return DSP_OK;
+    }
+    if (n < 0) return capi_fail(DSP_EINVAL, "n < 0");
+    for (long i = 0; i < n; ++i)
+        if (streams[i] < 0 || streams[i] >= rs->n_streams) return capi_fail(DSP_EINVAL, "no stream " + std::to_string(streams[i]) + " in this resampler");
+    for (long i = 0; i < n; ++i) rs->received[(size_t)streams[i]] = 0;
+    return DSP_OK;
+}
+
+int dsp_stream_resampler_counts(dsp_stream_resampler *rs, long *samples_in, long *samples_out)
+{
+    if (!rs) return capi_fail(DSP_EINVAL, "resampler is NULL");
+    std::lock_guard<std::mutex> lock(rs->mu);
+    for (long i = 0; i < rs->n_streams; ++i) {
+        if (samples_in) samples_in[i] = rs->received[(size_t)i];
+        if (samples_out) samples_out[i] = rs->sr.emitted(rs->received[(size_t)i]);
+    }
+    return DSP_OK;
+}
+
+int dsp_stream_resample_push_device(dsp_stream_resampler *rs, const void *d_chunks, const long *chunk_offsets, float *d_out, long *out_offsets, void *stream)
+{
+    if (!rs) return capi_fail(DSP_EINVAL, "resampler is NULL");
+    std::lock_guard<std::mutex> lock(rs->mu);
+    if (rs->broken)
+        return capi_fail(DSP_EHIP, "an earlier push failed on the GPU half way: dsp_stream_resampler_reset(resampler, NULL, ...) starts every stream afresh");
+    const long n = rs->n_streams, es = rs->es;
+    const StreamRatio &sr = rs->sr;
+    const dsp::ResampleShape &s = rs->shape;
+    long *oo = rs->oo.data();
+    // ---- validate and plan: nothing below this block changes the object before the last launch is enqueued
+    if (n > 0 && !chunk_offsets) return capi_fail(DSP_EINVAL, "chunk_offsets is NULL");
+    const long total = n > 0 ? plan_stream_push(sr, rs->received.data(), chunk_offsets, n, oo) : (oo[0] = 0);
+    if (total < 0) return (int)total;
+    if (n > 0 && chunk_offsets[n] > chunk_offsets[0]) {
+        if (!d_chunks) return capi_fail(DSP_EINVAL, "d_chunks is NULL");
+        if (reinterpret_cast<uintptr_t>(d_chunks) % (rs->in_kind == 0 ? 4u : 2u)) return capi_fail(DSP_EINVAL, "d_chunks must be aligned to one sample");
+    }
+    if (total > 0 && (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4)) return capi_fail(DSP_EINVAL, "d_out must not be NULL (and aligned to a float)");
+    hipStream_t st = (hipStream_t)stream;
+    rs->runs.clear();
+    if (sr.copy()) {      // K(N) = N, nothing carried: the one-shot's copy over the chunks
+        rs->copy_spans.clear();
+        long tiles = 0;
+        for (long c = 0; c < n; ++c) {
+            const long len = chunk_offsets[c + 1] - chunk_offsets[c];
+            if (len == 0) continue;
+            rs->copy_spans.push_back(dsp::ResampleSpan{chunk_offsets[c], oo[c], tiles, len, (int)len, 0});
+            tiles += (len + s.tile - 1) / s.tile;
+        }
+        if (tiles > 0) {
+            DSP_ON_DEVICE(rs->device);
+            dsp::SpanRing::Lease slot;
+            const dsp::ResampleSpan *d_spans;
+            const dsp::CopyRun *d_runs;
+            if (const int rc = upload_tables(rs, rs->copy_spans, slot, d_spans, d_runs, st)) return rc;
+            DSP_CAPI_HIP(dsp::launch_resample(d_chunks, rs->in_kind, d_spans, (long)rs->copy_spans.size(), tiles, s, nullptr, d_out, st));
+        }
+    } else {
+        rs->spans.clear();
+        long tiles = 0;
+        for (long c = 0; c < n; ++c) {
+            const long len = chunk_offsets[c + 1] - chunk_offsets[c], n0 = rs->received[(size_t)c], n1 = n0 + len;
+            const long k0 = sr.emitted(n0), k1 = sr.emitted(n1), c0 = sr.carry_start(n0), c1 = sr.carry_start(n1);
+            const int cur = rs->side[(size_t)c];
+            const long here = (2 * c + cur) * rs->half_stride, there = (2 * c + 1 - cur) * rs->half_stride;      // bytes into d_carry
+            rs->next_side[(size_t)c] = (char)cur;
+            if (c0 > n0 || c1 > n1 || c1 < c0 || (n1 - c1) * es > rs->half_stride)
+                return capi_fail(DSP_EINVAL, "internal: the carry of stream " + std::to_string(c) + " would not fit its slot");
+            if (k1 > k0) {
+                rs->spans.push_back(dsp::StreamResampleSpan{k0, oo[c], tiles, k1 - k0, c0, n0, n1, here / es, chunk_offsets[c]});
+                tiles += (k1 - k0 + s.tile - 1) / s.tile;
+            }
+            if (len == 0) continue;
+            if (c1 >= n0) {              // the new carry lies in the chunk
+                dsp::add_copy_runs(rs->runs, (chunk_offsets[c] + (c1 - n0)) * es, here, (n1 - c1) * es, 1);
+            } else if (c1 == c0) {       // nothing leaves the carry: the chunk goes behind it
+                dsp::add_copy_runs(rs->runs, chunk_offsets[c] * es, here + (n0 - c0) * es, len * es, 1);
+            } else {                     // the carry's tail moves to the front of the other half, the chunk behind it
+                dsp::add_copy_runs(rs->runs, here + (c1 - c0) * es, there, (n0 - c1) * es, 0);
+                dsp::add_copy_runs(rs->runs, chunk_offsets[c] * es, there + (n0 - c1) * es, len * es, 1);
+                rs->next_side[(size_t)c] = (char)(1 - cur);
+            }
+        }
+        if (tiles > 0 || !rs->runs.empty()) {
+            DSP_ON_DEVICE(rs->device);
+            dsp::SpanRing::Lease slot;
+            const dsp::StreamResampleSpan *d_spans;
+            const dsp::CopyRun *d_runs;
+            if (const int rc = upload_tables(rs, rs->spans, slot, d_spans, d_runs, st)) return rc;
+            // ---- the launches: the filter only reads the carry, the copy behind it writes the new one
+            if (tiles > 0)
+                DSP_CAPI_HIP(dsp::launch_resample_stream(rs->d_carry, d_chunks, rs->in_kind, d_spans, (long)rs->spans.size(), tiles, s, rs->taps, d_out, st));
+            // interleaved stereo at an odd int16 is copied in int16 units
+            const int granule = es == 2 || reinterpret_cast<uintptr_t>(d_chunks) % 4 ? 2 : 4;
+            const hipError_t e = dsp::launch_stream_copy(d_runs, (long)rs->runs.size(), rs->d_carry, d_chunks, rs->d_carry, granule, st);
+            if (e != hipSuccess) {
+                rs->broken = tiles > 0;      // (behind the first launch: the caller's output is written, the carry is not)
+                return capi_fail(DSP_EHIP, std::string("launch_stream_copy: ") + hipGetErrorString(e));
+            }
+        }
+        rs->side.swap(rs->next_side);
+    }
+    // ---- commit
+    for (long c = 0; c < n; ++c) rs->received[(size_t)c] += chunk_offsets[c + 1] - chunk_offsets[c];
+    if (out_offsets) std::memcpy(out_offsets, oo, (size_t)(n + 1) * sizeof(long));
+    return DSP_OK;
+}
+
+int dsp_stream_resample_finish_device(dsp_stream_resampler *rs, const long *streams, long n, float *d_out, long *out_offsets, void *stream)
+{
+    if (!rs) return capi_fail(DSP_EINVAL, "resampler is NULL");
+    std::lock_guard<std::mutex> lock(rs->mu);
+    if (rs->broken)
+        return capi_fail(DSP_EHIP, "an earlier push failed on the GPU half way: dsp_stream_resampler_reset(resampler, NULL, ...) starts every stream afresh");
+    if (n < 0) return capi_fail(DSP_EINVAL, "n < 0");
+    if (n > 0 && !streams) return capi_fail(DSP_EINVAL, "streams is NULL");
+    const StreamRatio &sr = rs->sr;
+    const dsp::ResampleShape &s = rs->shape;
+    for (long i = 0; i < n; ++i)
+        if (streams[i] < 0 || streams[i] >= rs->n_streams) return capi_fail(DSP_EINVAL, "no stream " + std::to_string(streams[i]) + " in this resampler");
+    rs->spans.clear();
+    std::vector<long> oo((size_t)n + 1, 0);
+    std::vector<char> named((size_t)rs->n_streams, 0);
+    long tiles = 0;
+    for (long i = 0; i < n; ++i) {
+        const long c = streams[i], n0 = rs->received[(size_t)c], k0 = sr.emitted(n0), k1 = sr.whole(n0);
+        if (named[(size_t)c]) return capi_fail(DSP_EINVAL, "stream " + std::to_string(c) + " is named twice");
+        named[(size_t)c] = 1;
+        oo[(size_t)i + 1] = oo[(size_t)i] + (k1 - k0);
+        if (k1 > k0) {
+            const long here = (2 * c + rs->side[(size_t)c]) * rs->half_stride;
+            rs->spans.push_back(dsp::StreamResampleSpan{k0, oo[(size_t)i], tiles, k1 - k0, sr.carry_start(n0), n0, n0, here / rs->es, 0});
+            tiles += (k1 - k0 + s.tile - 1) / s.tile;
+        }
+    }
+    if (tiles > 0) {
+        if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4) return capi_fail(DSP_EINVAL, "d_out must not be NULL (and aligned to a float)");
+        DSP_ON_DEVICE(rs->device);
+        hipStream_t st = (hipStream_t)stream;
+        rs->runs.clear();
+        dsp::SpanRing::Lease slot;
+        const dsp::StreamResampleSpan *d_spans;
+        const dsp::CopyRun *d_runs;
+        if (const int rc = upload_tables(rs, rs->spans, slot, d_spans, d_runs, st)) return rc;
+        DSP_CAPI_HIP(dsp::launch_resample_stream(rs->d_carry, rs->d_carry, rs->in_kind, d_spans, (long)rs->spans.size(), tiles, s, rs->taps, d_out, st));
+    }
+    for (long i = 0; i < n; ++i) rs->received[(size_t)streams[i]] = 0;
+    if (out_offsets) std::memcpy(out_offsets, oo.data(), (size_t)(n + 1) * sizeof(long));
     return DSP_OK;
 }
 

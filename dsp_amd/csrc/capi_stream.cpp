@@ -7,6 +7,9 @@
 // A stream's state is a function of ONE host counter, the samples it has received: rows = R(received), windows = W(rows), carried
 // samples = received - rows hop_length, carried rows = rows - windows hop_frames.  The device buffers hold what those numbers say and
 // nothing else, so a reset is a store to the counter.
+//
+// Feeds at another rate: dsp_stream_session_attach_resampler puts a streaming resampler (capi_resample.cpp, stream_resample.hpp) in
+// front.  A push then resamples the caller's chunks into d_resampled and runs the same push on the result.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -19,6 +22,7 @@
 
 #include "mfcc_plan.hpp"
 #include "stream_kernels.hpp"
+#include "stream_resample.hpp"
 
 using dsp::capi_fail;
 using dsp::CopyRun;
@@ -76,13 +80,6 @@ long plan_push(const StreamRule &r, const long *received, const long *co, long n
 
 long round_up(long x, long to) { return (x + to - 1) / to * to; }
 
-// a run of the gather, cut into the kernel's slices
-void add_runs(std::vector<CopyRun> &v, long src, long dst, long bytes, int from)
-{
-    for (long o = 0; o < bytes; o += dsp::kStreamCopySlice)
-        v.push_back(CopyRun{src + o, dst + o, (int)std::min<long>(dsp::kStreamCopySlice, bytes - o), from});
-}
-
 }  // namespace
 
 struct dsp_stream_session {
@@ -105,6 +102,11 @@ struct dsp_stream_session {
     std::vector<long> ro, wo, fo, starts, lengths;     // the host planner's tables (allocated once)
     std::vector<CopyRun> runs[4];         // stitch, sample tails, scan matrix, row tails
     dsp::SpanRing ring;                   // the four run tables of a push on their way to the GPU
+    // a resampler in front (dsp_stream_session_attach_resampler; borrowed): pushes arrive at its rate_in and in its format
+    dsp_stream_resampler *rs = nullptr;
+    bool pushed = false;                  // a push was accepted: too late to attach
+    dsp::DeviceBuf<char> d_resampled;     // per push, grow-only: the chunks at the models' rate, back to back
+    std::vector<long> roo;                // their offsets
     mutable std::mutex mu;
 };
 
@@ -180,6 +182,8 @@ int dsp_stream_session_reset(dsp_stream_session *s, const long *streams, long n,
     if (!s) return capi_fail(DSP_EINVAL, "session is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     if (!streams) {
+        if (s->rs)
+            if (const int rc = dsp_stream_resampler_reset(s->rs, nullptr, 0, stream)) return rc;
         std::fill(s->received.begin(), s->received.end(), 0L);
         s->broken = false;
         return DSP_OK;
@@ -187,6 +191,8 @@ int dsp_stream_session_reset(dsp_stream_session *s, const long *streams, long n,
     if (n < 0) return capi_fail(DSP_EINVAL, "n < 0");
     for (long i = 0; i < n; ++i)
         if (streams[i] < 0 || streams[i] >= s->n_streams) return capi_fail(DSP_EINVAL, "no stream " + std::to_string(streams[i]) + " in this session");
+    if (s->rs)
+        if (const int rc = dsp_stream_resampler_reset(s->rs, streams, n, stream)) return rc;
     for (long i = 0; i < n; ++i) s->received[(size_t)streams[i]] = 0;
     return DSP_OK;
 }
@@ -214,7 +220,7 @@ int dsp_stream_session_counts(const dsp_stream_session *s, long *samples, long *
         }                                                                                                                         \
     } while (0)
 
-int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const long *chunk_offsets, float *d_mfcc, float *d_prob,
+int dsp_stream_push_device(dsp_stream_session *s, const void *d_pushed, const long *pushed_offsets, float *d_mfcc, float *d_prob,
                            int64_t *d_llr_mean, int *d_labels, long *row_offsets, long *window_offsets, void *stream)
 {
     if (!s) return capi_fail(DSP_EINVAL, "session is NULL");
@@ -225,7 +231,25 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
     const StreamRule &r = s->rule;
     long *ro = s->ro.data(), *wo = s->wo.data(), *fo = s->fo.data();
     // ---- validate and plan: nothing below this block changes the session before the last launch is enqueued
-    if (n > 0 && !chunk_offsets) return capi_fail(DSP_EINVAL, "chunk_offsets is NULL");
+    if (n > 0 && !pushed_offsets) return capi_fail(DSP_EINVAL, "chunk_offsets is NULL");
+    // d_chunks / chunk_offsets: the chunks at the models' rate -- the caller's, or what the resampler in front will make of them
+    const void *d_chunks = d_pushed;
+    const long *chunk_offsets = pushed_offsets;
+    if (s->rs) {
+        const long total = dsp::stream_resampler_plan(s->rs, pushed_offsets, s->roo.data());
+        if (total < 0) return (int)total;
+        DSP_ON_DEVICE(s->device);
+        if (s->d_resampled.reserve((size_t)total * 4 + 16) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (resampled chunks)");
+        d_chunks = s->d_resampled.get();
+        chunk_offsets = s->roo.data();
+    }
+    // the resampler's push: behind every check of this one, in front of its first launch.  Refused, it has changed nothing.
+    auto resample = [&]() -> int {
+        if (!s->rs) return DSP_OK;
+        const int rc = dsp_stream_resample_push_device(s->rs, d_pushed, pushed_offsets, reinterpret_cast<float *>(s->d_resampled.get()), nullptr, stream);
+        if (rc < 0 && dsp::stream_resampler_broken(s->rs)) s->broken = true;
+        return rc;
+    };
     const long total_rows = n > 0 ? plan_push(r, s->received.data(), chunk_offsets, n, ro, wo) : (ro[0] = wo[0] = 0);
     if (total_rows < 0) return (int)total_rows;
     const long total_win = wo[n];
@@ -246,24 +270,24 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
             s->starts[(size_t)n_spans] = pos;
             s->lengths[(size_t)n_spans] = c0 + len;
             ++n_spans;
-            add_runs(s->runs[0], st * s->carry_stride, pos * es, c0 * es, 0);
-            add_runs(s->runs[0], chunk_offsets[st] * es, (pos + c0) * es, len * es, 1);
-            add_runs(s->runs[1], (pos + nr * r.h) * es, st * s->carry_stride, (n1 - e1 * r.h) * es, 0);
+            dsp::add_copy_runs(s->runs[0], st * s->carry_stride, pos * es, c0 * es, 0);
+            dsp::add_copy_runs(s->runs[0], chunk_offsets[st] * es, (pos + c0) * es, len * es, 1);
+            dsp::add_copy_runs(s->runs[1], (pos + nr * r.h) * es, st * s->carry_stride, (n1 - e1 * r.h) * es, 0);
             pos += round_up(c0 + len, align);
         } else if (len > 0) {      // no row yet: the chunk goes behind what is carried
-            add_runs(s->runs[1], chunk_offsets[st] * es, st * s->carry_stride + c0 * es, len * es, 1);
+            dsp::add_copy_runs(s->runs[1], chunk_offsets[st] * es, st * s->carry_stride + c0 * es, len * es, 1);
         }
         if (!s->scans || nr == 0) continue;
         const long w0 = r.windows(e0), w1 = r.windows(e1), k0 = e0 - w0 * r.hf;
         if (w1 > w0) {      // [carried rows | new rows] is one recording of the scans; the rows from window w1's start on are the new carry
             const long base = fo[n_scan], k1 = e1 - w1 * r.hf;
-            add_runs(s->runs[2], st * s->row_stride, base * rb, k0 * rb, 0);
-            add_runs(s->runs[2], ro[st] * rb, (base + k0) * rb, nr * rb, 1);
-            add_runs(s->runs[3], (base + k0 + nr - k1) * rb, st * s->row_stride, k1 * rb, 0);
+            dsp::add_copy_runs(s->runs[2], st * s->row_stride, base * rb, k0 * rb, 0);
+            dsp::add_copy_runs(s->runs[2], ro[st] * rb, (base + k0) * rb, nr * rb, 1);
+            dsp::add_copy_runs(s->runs[3], (base + k0 + nr - k1) * rb, st * s->row_stride, k1 * rb, 0);
             fo[++n_scan] = base + k0 + nr;
             scan_win += k0 + nr >= r.wf ? 1 + (k0 + nr - r.wf) / r.hf : 1;      // what the scans' own planner gives these rows (scan_plan)
         } else {            // no window: a stream with fewer rows than a window must not reach the scans (they would give it a short one)
-            add_runs(s->runs[3], ro[st] * rb, st * s->row_stride + k0 * rb, nr * rb, 1);
+            dsp::add_copy_runs(s->runs[3], ro[st] * rb, st * s->row_stride + k0 * rb, nr * rb, 1);
         }
     }
     if (scan_win != total_win) return capi_fail(DSP_EINVAL, "internal: the scans would write other windows than the push announced");
@@ -290,6 +314,7 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
             }
         }
         DSP_CAPI_HIP(slot.upload(n_runs * sizeof(CopyRun), st));
+        if (const int rc = resample()) return rc;
         // ---- the launches: from here on a failure breaks the session
         const int g = es == 2 ? 2 : 4;
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[0], (long)s->runs[0].size(), s->d_carry, d_chunks, s->d_stage, g, st));
@@ -308,11 +333,33 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_chunks, const lo
             if (rc < 0) { s->broken = true; return rc; }
         }
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[3], (long)s->runs[3].size(), s->d_scanmat, rows_out, s->d_rowcarry, 4, st));
+    } else if (const int rc = resample()) {
+        return rc;
     }
     // ---- commit
+    s->pushed = true;
     for (long st = 0; st < n; ++st) s->received[(size_t)st] += chunk_offsets[st + 1] - chunk_offsets[st];
     if (row_offsets) std::memcpy(row_offsets, ro, (size_t)(n + 1) * sizeof(long));
     if (window_offsets) std::memcpy(window_offsets, wo, (size_t)(n + 1) * sizeof(long));
+    return DSP_OK;
+}
+
+int dsp_stream_session_attach_resampler(dsp_stream_session *s, dsp_stream_resampler *rs)
+{
+    if (!s) return capi_fail(DSP_EINVAL, "session is NULL");
+    if (!rs) return capi_fail(DSP_EINVAL, "resampler is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->pushed) return capi_fail(DSP_EINVAL, "a resampler is attached before the session's first push");
+    if (s->rs) return capi_fail(DSP_EINVAL, "the session has a resampler already");
+    if (s->in_kind != 0) return capi_fail(DSP_EINVAL, "a resampler writes float mono samples: create the session with pcm16 = 0 (the resampler decodes the int16)");
+    const dsp::StreamResamplerInfo info = dsp::stream_resampler_info(rs);
+    if (info.n_streams != s->n_streams)
+        return capi_fail(DSP_EINVAL, "the resampler has " + std::to_string(info.n_streams) + " streams, the session " + std::to_string(s->n_streams));
+    if (info.device != s->device) return capi_fail(DSP_EINVAL, "the resampler and the session's plan live on different devices");
+    if (info.rate_out != s->plan->cfg.sample_rate)
+        return capi_fail(DSP_EINVAL, "the resampler writes " + std::to_string(info.rate_out) + " Hz, the session's plan runs at " + std::to_string(s->plan->cfg.sample_rate));
+    s->roo.assign((size_t)s->n_streams + 1, 0);
+    s->rs = rs;
     return DSP_OK;
 }
 

@@ -37,4 +37,25 @@ struct ResampleShape {
 hipError_t launch_resample(const void *d_in, int in_kind, const ResampleSpan *d_spans, long n_rec, long total_tiles, const ResampleShape &s,
                            const float *d_taps, float *d_out, hipStream_t stream);
 
+// ---- live streams (include/dsp_amd.h dsp_stream_resample*) ----
+// One stream of a push (or of a finish) that emits outputs: k0 .. k0 + n_out - 1 of the stream, written at out_off.  The samples they read
+// come from two places: [c0, n0) from the stream's carry, carry_off sample frames into the carry buffer, and [n0, n1) from the chunk,
+// chunk_off sample frames into the chunk buffer.  Samples before c0 are read by no output of the span; samples from n1 on have not
+// arrived (or, in a finish, never will): both are zeros.
+struct StreamResampleSpan {
+    long k0;
+    long out_off;
+    long tile0;
+    long n_out;
+    long c0, n0, n1;
+    long carry_off;
+    long chunk_off;
+};
+static_assert(sizeof(StreamResampleSpan) == 72, "nine aligned 8-byte words");
+
+// Tiles [0, total_tiles) of d_spans[n_spans], every span with n_out >= 1; a staged shape that is not the copy (s.staged, up or down > 1).
+// d_carry and d_chunks in the stream's own format (in_kind as above); the kernel only reads them.
+hipError_t launch_resample_stream(const void *d_carry, const void *d_chunks, int in_kind, const StreamResampleSpan *d_spans, long n_spans,
+                                  long total_tiles, const ResampleShape &s, const float *d_taps, float *d_out, hipStream_t stream);
+
 }  // namespace dsp

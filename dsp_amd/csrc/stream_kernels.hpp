@@ -5,6 +5,9 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace dsp {
 
 // One run of the gather: `bytes` from src0 + src (from = 0) or src1 + src (from = 1) to dst + dst.  Offsets and sizes in bytes, all
@@ -16,6 +19,12 @@ struct CopyRun {
 };
 static_assert(sizeof(CopyRun) == 24, "three 8-byte scalar loads per run");
 constexpr int kStreamCopySlice = 16384;
+
+// a run of the gather, cut into the kernel's slices
+inline void add_copy_runs(std::vector<CopyRun> &v, long src, long dst, long bytes, int from)
+{
+    for (long o = 0; o < bytes; o += kStreamCopySlice) v.push_back(CopyRun{src + o, dst + o, (int)std::min<long>(kStreamCopySlice, bytes - o), from});
+}
 
 // No run's source may overlap a run's destination within one launch (the session reads a carry in one launch and writes it in another).
 // granule: 2 or 4.  n_runs = 0: no launch.

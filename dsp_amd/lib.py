@@ -295,6 +295,8 @@ SYMBOLS = [
     "dsp_scrubjay_scanner_run_device", "dsp_scrubjay_scanner_run_pcm16_device",
     "dsp_stream_push_plan", "dsp_stream_session_create", "dsp_stream_session_destroy", "dsp_stream_session_reset",
     "dsp_stream_session_counts", "dsp_stream_push_device",
+    "dsp_stream_resample_plan", "dsp_stream_resampler_create", "dsp_stream_resampler_destroy", "dsp_stream_resampler_reset",
+    "dsp_stream_resampler_counts", "dsp_stream_resample_push_device", "dsp_stream_resample_finish_device", "dsp_stream_session_attach_resampler",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
     "dsp_resample_ratio", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
     "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device", "dsp_resample_clips_pcm16_device",
@@ -447,6 +449,14 @@ def load() -> C.CDLL:
     L.dsp_stream_session_reset.argtypes = [vp, lp, C.c_long, vp]; L.dsp_stream_session_reset.restype = ip
     L.dsp_stream_session_counts.argtypes = [vp, lp, lp, lp]; L.dsp_stream_session_counts.restype = ip
     L.dsp_stream_push_device.argtypes = [vp, vp, lp, vp, vp, vp, vp, lp, lp, vp]; L.dsp_stream_push_device.restype = ip
+    L.dsp_stream_resample_plan.argtypes = [ip, ip, lp, lp, C.c_long, lp]; L.dsp_stream_resample_plan.restype = C.c_long
+    L.dsp_stream_resampler_create.argtypes = [ip, ip, ip, C.c_long, ip, ip, ip, C.POINTER(vp)]; L.dsp_stream_resampler_create.restype = ip
+    L.dsp_stream_resampler_destroy.argtypes = [vp]; L.dsp_stream_resampler_destroy.restype = None
+    L.dsp_stream_resampler_reset.argtypes = [vp, lp, C.c_long, vp]; L.dsp_stream_resampler_reset.restype = ip
+    L.dsp_stream_resampler_counts.argtypes = [vp, lp, lp]; L.dsp_stream_resampler_counts.restype = ip
+    L.dsp_stream_resample_push_device.argtypes = [vp, vp, lp, vp, lp, vp]; L.dsp_stream_resample_push_device.restype = ip
+    L.dsp_stream_resample_finish_device.argtypes = [vp, lp, C.c_long, vp, lp, vp]; L.dsp_stream_resample_finish_device.restype = ip
+    L.dsp_stream_session_attach_resampler.argtypes = [vp, vp]; L.dsp_stream_session_attach_resampler.restype = ip
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_resample_ratio.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]; L.dsp_resample_ratio.restype = ip
@@ -594,6 +604,53 @@ def pcm_device(pcm):
     if channels == 2 and (pcm.shape[2] != 2 or pcm.stride(1) != 2 or pcm.stride(0) % 2):
         raise ValueError("stereo pcm must be interleaved [n_clips][n][2]")
     return channels, pcm.stride(0) // channels
+
+
+def long_array(a, size, what):
+    """Any integer sequence -> a contiguous int64 array of exactly `size` entries, or ValueError."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+    if a.ndim != 1 or a.size != size:
+        raise ValueError(f"{what} must hold {size} entries")
+    return a
+
+
+def stream_chunks(chunks, chunk_offsets, n_streams, dtype, channels, device):
+    """The chunks of one push on the GPU: a contiguous CUDA tensor of `dtype` on cuda:`device`, [total] (channels 1) or interleaved
+    [total][2] (channels 2), stream s's chunk = sample frames [chunk_offsets[s], chunk_offsets[s + 1]).  -> chunk_offsets as a contiguous
+    int64 array of n_streams + 1, or ValueError."""
+    import numpy as np
+    import torch
+    if not (isinstance(chunks, torch.Tensor) and chunks.is_cuda and chunks.is_contiguous()):
+        raise ValueError("chunks must be a contiguous CUDA tensor")
+    if chunks.dtype != dtype:
+        raise ValueError(f"chunks must be {str(dtype).replace('torch.', '')}, as the object was created")
+    if chunks.device.index != device:
+        raise ValueError(f"chunks must live on the object's device (cuda:{device})")
+    if not (chunks.dim() == 1 if channels == 1 else (chunks.dim() == 2 and chunks.shape[1] == 2)):
+        raise ValueError("chunks must be [total] (mono) or [total][2] (interleaved stereo), as the object was created")
+    co = long_array(chunk_offsets, n_streams + 1, "chunk_offsets")
+    if co[0] < 0 or (np.diff(co) < 0).any():
+        raise ValueError("chunk_offsets must be non-negative and non-decreasing")
+    if int(co[-1]) > chunks.shape[0]:
+        raise ValueError("chunk_offsets run past the end of chunks")
+    return co
+
+
+def stream_format(dtype, channels, stereo_mode, n_streams):
+    """The sample format of a stream object: torch.float32 mono, or torch.int16 with 1 or 2 interleaved channels.  -> (dtype, channels,
+    stereo_mode, n_streams, pcm16 flag) as ints, or ValueError."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.int16):
+        raise ValueError("dtype must be torch.float32 or torch.int16")
+    if int(n_streams) < 0:
+        raise ValueError("n_streams must be >= 0")
+    if channels not in (1, 2) or (channels == 2 and dtype != torch.int16):
+        raise ValueError("channels must be 1, or 2 for int16 PCM")
+    if stereo_mode not in (0, 1):
+        raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
+    return dtype, int(channels), int(stereo_mode), int(n_streams), int(dtype == torch.int16)
 
 
 def ragged_signal(signal, offsets, float_dtype):

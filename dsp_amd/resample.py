@@ -1,5 +1,6 @@
 """Recordings at another rate: the polyphase FIR resampler of include/dsp_amd.h (dsp_resample_*) --
-scipy.signal.resample_poly's defaults as one HIP launch over a ragged or uniform batch, float or int16 in HBM."""
+scipy.signal.resample_poly's defaults as one HIP launch over a ragged or uniform batch, float or int16 in HBM -- and the same
+outputs from feeds that are still arriving (dsp_stream_resample*)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -132,3 +133,125 @@ class Resampler:
             if got != n_out:
                 raise _lib.DspError(f"the library resampled {s} samples to {got}, the wrapper expected {n_out}")
         return out
+
+
+_LP = C.POINTER(C.c_long)
+
+
+def stream_resample_plan(rate_in: int, rate_out: int, received, chunk_offsets) -> np.ndarray:
+    """Host only (dsp_stream_resample_plan): streams that have received `received[s]` sample frames (None: none) and now get chunks
+    [chunk_offsets[s], chunk_offsets[s + 1]) -> int64 [n + 1], the prefix sums of the outputs that become complete."""
+    rate_in, rate_out = _rates(rate_in, rate_out)
+    co = np.ascontiguousarray(np.asarray(chunk_offsets, dtype=np.int64))
+    if co.ndim != 1 or co.size < 1:
+        raise ValueError("chunk_offsets must hold n_streams + 1 positions")
+    n = co.size - 1
+    if co[0] < 0 or (np.diff(co) < 0).any():
+        raise ValueError("chunk_offsets must be non-negative and non-decreasing")
+    rec = None
+    if received is not None:
+        rec = _lib.long_array(received, n, "received")
+        if (rec < 0).any():
+            raise ValueError("received must be non-negative")
+    oo = np.zeros(n + 1, np.int64)
+    _lib.check(_lib.load().dsp_stream_resample_plan(rate_in, rate_out, rec.ctypes.data_as(_LP) if rec is not None else None, co.ctypes.data_as(_LP), n,
+                                                    oo.ctypes.data_as(_LP)), "dsp_stream_resample_plan")
+    return oo
+
+
+class StreamResampler:
+    """dsp_stream_resampler: n_streams live feeds at rate_in on one GPU.  Every push hands over the next chunk of each feed (any length)
+    and returns the outputs at rate_out that became complete with it; concatenated over the pushes they are, bit for bit, the first
+    outputs of Resampler.ragged on the whole feed, and finish() emits the rest.  dtype: torch.float32 samples, or torch.int16 PCM
+    ([total] mono, [total][2] interleaved stereo with stereo_mode 0 = channel 0 / 1 = average; channels=2 selects stereo).  One stream
+    at a time per object."""
+
+    def __init__(self, rate_in: int, rate_out: int, n_streams: int, dtype=None, stereo_mode: int = 0, channels: int = 1, device: int = 0):
+        self.rate_in, self.rate_out = _rates(rate_in, rate_out)
+        self.dtype, self.channels, self.stereo_mode, self.n_streams, pcm16 = _lib.stream_format(dtype, channels, stereo_mode, n_streams)
+        self.up, self.down, self.half = resample_ratio(rate_in, rate_out)
+        self._L = _lib.load()
+        self.device = int(device)
+        h = C.c_void_p()
+        _lib.check(self._L.dsp_stream_resampler_create(self.device, self.rate_in, self.rate_out, self.n_streams, self.channels, self.stereo_mode, pcm16,
+                                                       C.byref(h)), "dsp_stream_resampler_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dsp_stream_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def counts(self):
+        """-> (sample frames received, outputs emitted), int64 [n_streams] each."""
+        out = [np.zeros(self.n_streams, np.int64) for _ in range(2)]
+        _lib.check(self._L.dsp_stream_resampler_counts(self._h, *[a.ctypes.data_as(_LP) for a in out]), "dsp_stream_resampler_counts")
+        return tuple(out)
+
+    def plan(self, chunk_offsets) -> np.ndarray:
+        """What a push of these chunks would emit now: int64 [n_streams + 1], the prefix sums of the new outputs."""
+        co = _lib.long_array(chunk_offsets, self.n_streams + 1, "chunk_offsets")
+        return stream_resample_plan(self.rate_in, self.rate_out, self.counts()[0], co)
+
+    def _named(self, streams):
+        idx = np.ascontiguousarray(np.asarray(streams, dtype=np.int64))
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.n_streams)):
+            raise ValueError(f"streams must name streams 0 .. {self.n_streams - 1}")
+        return idx
+
+    def reset(self, streams=None):
+        """Forget the named streams' samples and counters (None: all of them, which also revives a broken object)."""
+        if streams is None:
+            _lib.check(self._L.dsp_stream_resampler_reset(self._h, None, 0, None), "dsp_stream_resampler_reset")
+            return
+        idx = self._named(streams)
+        _lib.check(self._L.dsp_stream_resampler_reset(self._h, idx.ctypes.data_as(_LP), idx.size, None), "dsp_stream_resampler_reset")
+
+    def _out(self, out, total, dev):
+        import torch
+        if out is None:
+            return torch.empty((total,), dtype=torch.float32, device=dev)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 1 and out.numel() >= total):
+            raise ValueError(f"out must be a contiguous float32 CUDA tensor of at least {total} samples")
+        return out
+
+    def push(self, chunks, chunk_offsets, out=None):
+        """chunks: a contiguous CUDA tensor of the object's dtype on its device ([total], or [total][2] for stereo), stream s's chunk =
+        sample frames [chunk_offsets[s], chunk_offsets[s + 1]) -> (out float32 [new outputs], out_offsets int64 [n + 1]): stream s's new
+        outputs are out[out_offsets[s] : out_offsets[s + 1]].  Async on torch's current stream."""
+        co = _lib.stream_chunks(chunks, chunk_offsets, self.n_streams, self.dtype, self.channels, self.device)
+        oo = stream_resample_plan(self.rate_in, self.rate_out, self.counts()[0], co)
+        out = self._out(out, int(oo[-1]), chunks.device)
+        oo2 = np.zeros_like(oo)
+        _lib.check(self._L.dsp_stream_resample_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_LP), out.data_ptr(), oo2.ctypes.data_as(_LP),
+                                                           self._stream()), "dsp_stream_resample_push_device")
+        if not np.array_equal(oo, oo2):
+            raise _lib.DspError("dsp_stream_resample_push_device emitted other outputs than dsp_stream_resample_plan announced")
+        return out[:int(oo2[-1])], oo2
+
+    def finish(self, streams=None, out=None):
+        """End the named streams (None: all): -> (out float32, out_offsets int64 [len(streams) + 1]) with the outputs a whole recording
+        has beyond those the pushes emitted, in the order named; the streams start afresh."""
+        import torch
+        idx = self._named(np.arange(self.n_streams) if streams is None else streams)
+        if np.unique(idx).size != idx.size:
+            raise ValueError("a stream may be named once")
+        n_in, n_out = self.counts()
+        total = int(sum(-((-int(n_in[s]) * self.up) // self.down) - int(n_out[s]) for s in idx))
+        out = self._out(out, total, torch.device("cuda", self.device))
+        oo = np.zeros(idx.size + 1, np.int64)
+        _lib.check(self._L.dsp_stream_resample_finish_device(self._h, idx.ctypes.data_as(_LP), idx.size, out.data_ptr(), oo.ctypes.data_as(_LP),
+                                                             self._stream()), "dsp_stream_resample_finish_device")
+        if int(oo[-1]) != total:
+            raise _lib.DspError(f"the library finished with {int(oo[-1])} outputs, the wrapper expected {total}")
+        return out[:total], oo

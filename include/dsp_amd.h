@@ -636,6 +636,55 @@ int dsp_stream_session_counts(const dsp_stream_session *session, long *samples, 
 int dsp_stream_push_device(dsp_stream_session *session, const void *d_chunks, const long *chunk_offsets, float *d_mfcc, float *d_prob,
                            int64_t *d_llr_mean, int *d_labels, long *row_offsets, long *window_offsets, void *stream);
 
+/* LIVE STREAMS AT ANOTHER RATE: the polyphase resampler below ("recordings at another rate") for feeds that are still arriving, on its
+ * own or in front of a stream session.  With (up, down, half) as dsp_resample_ratio gives them, T = (2 half + up) / up
+ * the taps of one polyphase branch, and N the sample frames a stream has received so far:
+ *   output k reads input samples up to i_max(k) = (k down + half) div up, and no sample before i_max(k) - (T - 1);
+ *   the stream has emitted K(N) = N up - 1 - half >= 0 ? (N up - 1 - half) div down + 1 : 0 outputs: exactly the k with i_max(k) <= N - 1.
+ *   A push emits outputs K(N before) .. K(N after) - 1.  The stream carries the input frames from max(0, i_max(K(N)) - (T - 1)) on to
+ *   the next push: at most T - 1 of them, in the caller's own format.
+ * up = down = 1 copies: K(N) = N, nothing is carried, float bits pass through.
+ * THE CONTRACT: concatenated over the pushes a stream's outputs are, bit for bit, the first K(N) outputs dsp_resample_ragged_device /
+ * dsp_resample_ragged_pcm16_device give on the whole feed, for finite samples, whatever the chunk lengths, the other streams or the
+ * batch.  (Both sum one float32 FMA chain per output in ascending input sample.  The chain's last slots multiply samples behind i_max
+ * by zero taps; a stream that does not hold them yet uses 0.0 there, which changes no bit of a finite sum -- the one exception being a
+ * sum every product of which underflows to -0.0, out of reach of int16 input.)
+ * dsp_stream_resample_finish_device ends the named streams: it emits their outputs K(N) .. ceil(N up / down) - 1, with zeros for the
+ * samples past the end as on a whole recording, and forgets the streams; pushes plus finish give the one-shot output in full.
+ *
+ * dsp_stream_resample_plan (host only, no GPU, no object): received[n_streams] (NULL: all zero) and chunk_offsets[n_streams + 1] (the
+ * chunks back to back, as dsp_stream_push_plan's) -> out_offsets[n_streams + 1], the prefix sums of the new outputs; returns their total
+ * or a negative DSP_E* code.  n_streams = 0: chunk_offsets may be NULL.
+ * dsp_stream_resampler_create refuses, in this order and before it touches a GPU: out NULL; a bad PCM layout (pcm16 = 0: float
+ * samples, channels must be 1; pcm16 != 0: channels and stereo_mode as dsp_resample_ragged_pcm16_device); rates below 1 or up / down
+ * above 1024; a ratio whose branch is too long for the kernel to stage (down past ~450 with up = 1: thousands of carried samples per
+ * stream are no live-feed shape; the one-shot entries take such ratios); n_streams outside [0, 2^31); then the device index.
+ * dsp_stream_resample_push_device: d_chunks float or int16 (interleaved if stereo; int16 needs 2-byte alignment only), chunk c = sample
+ * frames [chunk_offsets[c], chunk_offsets[c + 1]) -> the new outputs at d_out + out_offsets[c], back to back.  out_offsets: a HOST array
+ * of n_streams + 1, filled before a successful call returns (may be NULL).  Everything is enqueued on `stream`, no host synchronisation:
+ * one filter launch that reads each chunk byte once (the carried samples in front of it from the carry, never a stitched copy), one
+ * copy launch that writes the new carry.  A refused push leaves the object as it was; a HIP failure behind the first launch breaks it
+ * until dsp_stream_resampler_reset(rs, NULL, ...).  Zero streams, or a push that completes no output: DSP_OK, no filter launch.
+ * _finish_device: streams[n] (each at most once), d_out / out_offsets[n + 1] in the order named.  _reset and _counts as the session's;
+ * samples_out[s] = K(samples_in[s]); either may be NULL.  ONE stream at a time per object.
+ *
+ * dsp_stream_session_attach_resampler: DSP_EINVAL unless it is called before the session's first push, the session takes float mono
+ * samples, n_streams and the device are equal and rate_out is the plan's sample_rate.  From then on dsp_stream_push_device takes chunks
+ * at rate_in in the RESAMPLER's format, resamples them into a buffer the session owns and runs the push it always ran on the result;
+ * dsp_stream_session_reset resets the same streams of the resampler, dsp_stream_session_counts keeps counting samples at the models'
+ * rate.  The session borrows the resampler (destroy the session first); do not push to an attached resampler directly.            */
+typedef struct dsp_stream_resampler dsp_stream_resampler;
+long dsp_stream_resample_plan(int rate_in, int rate_out, const long *received, const long *chunk_offsets, long n_streams, long *out_offsets);
+int dsp_stream_resampler_create(int device, int rate_in, int rate_out, long n_streams, int channels, int stereo_mode, int pcm16,
+                                dsp_stream_resampler **out);
+void dsp_stream_resampler_destroy(dsp_stream_resampler *rs);
+int dsp_stream_resampler_reset(dsp_stream_resampler *rs, const long *streams, long n, void *stream);
+int dsp_stream_resampler_counts(dsp_stream_resampler *rs, long *samples_in, long *samples_out);
+int dsp_stream_resample_push_device(dsp_stream_resampler *rs, const void *d_chunks, const long *chunk_offsets, float *d_out,
+                                    long *out_offsets, void *stream);
+int dsp_stream_resample_finish_device(dsp_stream_resampler *rs, const long *streams, long n, float *d_out, long *out_offsets, void *stream);
+int dsp_stream_session_attach_resampler(dsp_stream_session *session, dsp_stream_resampler *rs);
+
 /* upsampleLinear (sync/particle/main.cpp:62-77) over a batch: d_out[c][i] for i < new_size from
  * d_in[c][0..old_size), the reference's fp32 operation order (bit-identical).  new_size >= 2.     */
 int dsp_upsample_linear_device(const float *d_in, long n_clips, int old_size, long in_stride, float *d_out,
@@ -652,7 +701,7 @@ int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_
  * The taps are computed in float64 on the host and rounded once to float32; products and sums are float32 (FMA), in ascending i -- an
  * order that depends on the recording and k only, never on the batch, the launch or the entry point.  up = down = 1 copies the input bit
  * for bit; n = 0 gives no output.  After reduction up and down must each be <= 1024 (DSP_EINVAL otherwise); a recording holds at most
- * INT_MAX samples.  Not covered: a filter-history carry for live streams (dsp_stream_push_device takes the models' rate).
+ * INT_MAX samples.  Live feeds at another rate: dsp_stream_resample* above, which carry the filter's history between pushes.
  *
  * Host only, no GPU: dsp_resample_ratio (any pointer may be NULL); dsp_resample_taps (returns 2 half + 1; h may be NULL, else n >= that);
  * dsp_resample_offsets: offsets[n + 1] as dsp_mfcc_clips_ragged_device takes them -> out_offsets[n + 1], the prefix sums of the output
