@@ -43,22 +43,36 @@ HostModel host_model(int k, int d, const double *w, const double *mu, const doub
 {
     HostModel m;
     m.params.resize(dsp::ubm_param_doubles(k, d));
+    const dsp::UbmParams<double> p{m.params.data(), k, d};
     const size_t kd = (size_t)k * d;
     std::vector<double> inv_var(kd);
     for (int i = 0; i < k; ++i) {
         double log_det = 0.0;
         for (int j = 0; j < d; ++j) log_det += std::log(2.0 * M_PI * var[(size_t)i * d + j]);
-        const double lc = std::log(w[i]) - 0.5 * log_det;
-        m.params[i] = w[i];
-        m.params[(size_t)k + 2 * kd + i] = lc;
+        p.w()[i] = w[i];
+        p.log_const()[i] = std::log(w[i]) - 0.5 * log_det;
     }
     for (size_t i = 0; i < kd; ++i) {
-        m.params[(size_t)k + i] = mu[i];
-        m.params[(size_t)k + kd + i] = var[i];
+        p.mu()[i] = mu[i];
+        p.var()[i] = var[i];
         inv_var[i] = 1.0 / var[i];
     }
-    m.model = dsp::pack_gmm_model(k, d, m.params.data() + k + 2 * kd, mu, inv_var.data());
+    m.model = dsp::pack_gmm_model(k, d, p.log_const(), mu, inv_var.data());
     return m;
+}
+
+// kIterationsPerLook iterations at a time through launch(first, count) (a DSP_* code: the caller words its failure), after each batch
+// the device control word into *end and one synchronisation, until end->done or max_iter
+template <class Ctrl, class Launch>
+int run_until_done(int max_iter, const Ctrl *d_ctrl, Ctrl *end, hipStream_t stream, Launch &&launch)
+{
+    for (int first = 0; first < max_iter && !end->done; first += kIterationsPerLook) {
+        const int count = max_iter - first < kIterationsPerLook ? max_iter - first : kIterationsPerLook;
+        if (const int rc = launch(first, count)) return rc;
+        DSP_CAPI_HIP(hipMemcpyAsync(end, d_ctrl, sizeof(*end), hipMemcpyDeviceToHost, stream));
+        DSP_CAPI_HIP(hipStreamSynchronize(stream));
+    }
+    return DSP_OK;
 }
 
 int reserve_em(dsp_ubm_trainer *t, int k, long n, int max_iter, size_t stride)
@@ -84,12 +98,11 @@ int run_em_from_device(dsp_ubm_trainer *t, int k, const float *d_feats, long n, 
     dsp::UbmFit fit{d_feats, n, t->state, dsp::GmmModelOut{t->model, k, d}, t->partials, t->partials.get() + (size_t)n_groups * stride, t->state.get() + n_params,
                     t->ctrl, tol, reg_covar};
     dsp::UbmCtrl end = start;
-    for (int first = 0; first < max_iter && !end.done; first += kIterationsPerLook) {
-        const int count = max_iter - first < kIterationsPerLook ? max_iter - first : kIterationsPerLook;
-        DSP_CAPI_HIP(dsp::launch_ubm_iterations(fit, first, count, stream));
-        DSP_CAPI_HIP(hipMemcpyAsync(&end, t->ctrl, sizeof(end), hipMemcpyDeviceToHost, stream));
-        DSP_CAPI_HIP(hipStreamSynchronize(stream));
-    }
+    if (const int rc = run_until_done(max_iter, t->ctrl.get(), &end, stream, [&](int first, int count) -> int {
+            DSP_CAPI_HIP(dsp::launch_ubm_iterations(fit, first, count, stream));
+            return DSP_OK;
+        }))
+        return rc;
     DSP_CAPI_HIP(hipMemcpyAsync(params, t->state, n_params * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (lower_bounds) DSP_CAPI_HIP(hipMemcpyAsync(lower_bounds, fit.lower_bounds, (size_t)end.n_iter * sizeof(double), hipMemcpyDeviceToHost, stream));
     DSP_CAPI_HIP(hipStreamSynchronize(stream));
@@ -138,7 +151,8 @@ int global_variance(dsp_ubm_trainer *t, const float *d_feats, long n, double reg
     int n_iter = 0, converged = 0;
     if (const int rc = run_em(t, 1, d_feats, n, &one_w, one_mu.data(), one_var.data(), 1, 0.0, reg_covar, params.data(), nullptr, &n_iter, &converged, stream))
         return rc;
-    variance.assign(params.begin() + 1 + d, params.begin() + 1 + 2 * d);
+    const dsp::UbmParams<const double> p{params.data(), 1, d};
+    variance.assign(p.var(), p.var() + d);
     return DSP_OK;
 }
 
@@ -234,12 +248,11 @@ int run_lloyd(dsp_ubm_trainer *t, const float *d_feats, long n, const double *ce
     const dsp::KmeansFit fit{d_feats, n, t->km_centres, model, labels, t->partials, t->partials.get() + (size_t)n_groups * stride, t->km_ctrl, shift_limit, max_iter,
                              reg_covar, t->state, t->km_centres.get() + kd};
     *end = start;
-    for (int first = 0; first < max_iter && !end->done; first += kIterationsPerLook) {
-        const int count = max_iter - first < kIterationsPerLook ? max_iter - first : kIterationsPerLook;
-        DSP_CAPI_HIP(dsp::launch_kmeans_iterations(fit, first, count, stream));
-        DSP_CAPI_HIP(hipMemcpyAsync(end, t->km_ctrl, sizeof(*end), hipMemcpyDeviceToHost, stream));
-        DSP_CAPI_HIP(hipStreamSynchronize(stream));
-    }
+    if (const int rc = run_until_done(max_iter, t->km_ctrl.get(), end, stream, [&](int first, int count) -> int {
+            DSP_CAPI_HIP(dsp::launch_kmeans_iterations(fit, first, count, stream));
+            return DSP_OK;
+        }))
+        return rc;
     DSP_CAPI_HIP(dsp::launch_kmeans_final(fit, stream));
     DSP_CAPI_HIP(hipMemcpyAsync(end, t->km_ctrl, sizeof(*end), hipMemcpyDeviceToHost, stream));
     DSP_CAPI_HIP(hipStreamSynchronize(stream));                       // (also: `c` and `start` are read by then)
@@ -266,17 +279,18 @@ int check_ubm_result(const dsp_ubm_result *result)
 void write_ubm_result(dsp_ubm_result *result, int k, int d, const std::vector<double> &params, int n_iter, int converged)
 {
     const size_t kd = (size_t)k * d;
+    const dsp::UbmParams<const double> p{params.data(), k, d};
     // the caller's arrays behind the const pointers of dsp_gmm_float_params are the result's to write
     double *log_consts = const_cast<double *>(result->gmm.log_consts), *means = const_cast<double *>(result->gmm.means);
     double *inv_covs = const_cast<double *>(result->gmm.inv_covs);
     for (int i = 0; i < k; ++i) {
-        result->weights[i] = params[i];
-        log_consts[i] = params[(size_t)k + 2 * kd + i];
+        result->weights[i] = p.w()[i];
+        log_consts[i] = p.log_const()[i];
     }
     for (size_t i = 0; i < kd; ++i) {
-        means[i] = params[(size_t)k + i];
-        result->variances[i] = params[(size_t)k + kd + i];
-        inv_covs[i] = 1.0 / params[(size_t)k + kd + i];
+        means[i] = p.mu()[i];
+        result->variances[i] = p.var()[i];
+        inv_covs[i] = 1.0 / p.var()[i];
     }
     result->gmm.k = k;
     result->gmm.d = d;
@@ -355,9 +369,10 @@ int dsp_ubm_train_device(dsp_ubm_trainer *t, const float *d_feats, long n, const
     if (init) {
         w = init->weights; mu = init->means; var = init->variances;
     } else {
-        start.resize((size_t)k + 2 * kd);
-        if (const int rc = init_rows(t, d_feats, n, cfg->reg_covar, start.data(), start.data() + k, start.data() + k + kd, (hipStream_t)stream)) return rc;
-        w = start.data(); mu = w + k; var = mu + kd;
+        start.resize(dsp::ubm_param_doubles(k, d));
+        const dsp::UbmParams<double> p{start.data(), k, d};
+        if (const int rc = init_rows(t, d_feats, n, cfg->reg_covar, p.w(), p.mu(), p.var(), (hipStream_t)stream)) return rc;
+        w = p.w(); mu = p.mu(); var = p.var();
     }
     std::vector<double> params(dsp::ubm_param_doubles(k, d));
     int n_iter = 0, converged = 0;
@@ -404,13 +419,14 @@ int dsp_kmeans_fit_device(dsp_ubm_trainer *t, const float *d_feats, long n, cons
     DSP_CAPI_HIP(hipMemcpyAsync(counts.data(), t->km_centres.get() + kd, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
     DSP_CAPI_HIP(hipMemcpyAsync(params.data(), t->state, params.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     DSP_CAPI_HIP(hipStreamSynchronize(s));
+    const dsp::UbmParams<const double> p{params.data(), k, d};
     for (int i = 0; i < k; ++i) {
         result->counts[i] = (long)counts[i];
-        result->weights[i] = params[i];
+        result->weights[i] = p.w()[i];
     }
     for (size_t i = 0; i < kd; ++i) {
-        result->means[i] = params[(size_t)k + i];
-        result->variances[i] = params[(size_t)k + kd + i];
+        result->means[i] = p.mu()[i];
+        result->variances[i] = p.var()[i];
     }
     result->inertia = end.inertia;
     result->n_iter = end.n_iter;

@@ -50,13 +50,13 @@ __device__ inline long owner_of_unit(const Span *spans, long n, long u)
     return lo;
 }
 
-// rows [0, cnt) of src[cnt][D] into the block's LDS image xs[rows of the chunk][kRowLd]; a barrier follows before any row is read
-template <int D>
+// rows [0, cnt) of src[cnt][D] into the block's LDS image xs[rows of the chunk][Ld]; a barrier follows before any row is read
+template <int D, int Ld = kRowLd>
 __device__ __forceinline__ void stage_rows(float *xs, const float *__restrict__ src, int cnt)
 {
     for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
         const int r = i / D;
-        xs[r * kRowLd + (i - r * D)] = src[i];
+        xs[r * Ld + (i - r * D)] = src[i];
     }
 }
 

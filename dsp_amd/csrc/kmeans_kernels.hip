@@ -4,21 +4,20 @@
 // Lloyd: one iteration is the UBM statistics pass of ubm_kernels.hip with a hard posterior.  Lane k of a wave owns centre k; per row
 //   s_k = sum_d (x_d - c_kd)^2 in float32 (ascending d, fused multiply-add), the label is the lowest lane that holds the wave's minimum,
 //   and that lane alone adds 1, (x - c) and (x - c)^2 to its N, F, G.  The chunk / group / super tree, the float32-in-chunk and
-//   float64-above-it rule and the control word are those of the EM kernels; the inertia (float32 in the chunk) and the number of rows
-//   whose label changed (an integer, exact) ride behind the statistics in every partial.
+//   float64-above-it rule and the control word are those of the EM kernels, and the supers' kernel and the launch are gmm_stats.hpp's;
+//   the inertia (float32 in the chunk) and the number of rows whose label changed (an integer, exact) ride behind the statistics in
+//   every partial.
 //   update      one block adds the supers and moves the centres in float64: c + F / N, an empty cluster keeps its centre; then the stop
-//   final pass  the same statistics against the final centres, then the M-step of dsp_amd.h step 4 on them: the GMM start, written into
-//               the float64 parameter block and the float32 E-step model that EM reads -- restated here, so that ubm_mstep_kernel stays
-//               as it is
+//   final pass  the same statistics against the final centres, then gmm_stats.hpp's M-step on them (dsp_amd.h step 4): the GMM start,
+//               written into the float64 parameter block and the float32 E-step model that EM reads
 // Seeding (greedy k-means++): a row per thread.  Per step one pass over the rows folds the last winner into m[i], evaluates the step's
 //   proposals at once and leaves one set of chunk and group sums per proposal; one block then adds the supers, picks the winner, and
 //   walks the winner's sums top down (supers, groups, chunks, rows) to the next step's proposals.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cmath>
 
-#include "gmm_estep.hpp"
+#include "gmm_stats.hpp"
 #include "kmeans_kernels.hpp"
 
 namespace dsp {
@@ -128,15 +127,6 @@ __global__ __launch_bounds__(kThreads, 4) void kmeans_stats_kernel(const float *
 }
 static_assert(kThreads / 64 == 4, "changed_part is added as four waves");
 
-__global__ __launch_bounds__(kThreads) void kmeans_supers_kernel(const double *__restrict__ groups, long n_groups, int len, const KmeansCtrl *__restrict__ ctrl,
-                                                                 int final_pass, double *__restrict__ supers)
-{
-    if (!final_pass && ctrl->done) return;
-    const long g0 = (long)blockIdx.x * kUbmSuperGroups;
-    const long g1 = g0 + kUbmSuperGroups < n_groups ? g0 + kUbmSuperGroups : n_groups;
-    sum_partials(groups + (size_t)g0 * len, g1 - g0, (size_t)len, len, supers + (size_t)blockIdx.x * len);      // ascending group
-}
-
 __global__ __launch_bounds__(kThreads) void kmeans_update_kernel(const double *__restrict__ supers, long n_supers, int iter, int max_iter, double shift_limit,
                                                                  double *__restrict__ centres, GmmModelOut model, KmeansCtrl *__restrict__ ctrl)
 {
@@ -178,54 +168,22 @@ __global__ __launch_bounds__(kThreads) void kmeans_update_kernel(const double *_
     }
 }
 
-// the statistics of the final labels -> sklearn's _estimate_gaussian_parameters (diag): the arithmetic of ubm_mstep_kernel, with p in {0, 1}
+// the statistics of the final labels -> the GMM start: gmm_stats.hpp's M-step, with p in {0, 1}
 __global__ __launch_bounds__(kThreads) void kmeans_gmm_start_kernel(const double *__restrict__ supers, long n_supers, double reg_covar, double *__restrict__ params,
                                                                     GmmModelOut model, double *__restrict__ counts, KmeansCtrl *__restrict__ ctrl)
 {
     __shared__ double sums[kGmmMaxK * (2 * kGmmMaxD + 1) + 2];
-    __shared__ double n_total;
-    const int k = model.k, d = model.d, T = 2 * d + 1, n_stats = k * T;
-    sum_partials(supers, n_supers, (size_t)n_stats + 2, n_stats + 2, sums);
+    const int k = model.k, T = 2 * model.d + 1, n_stats = k * T;
+    sum_partials(supers, n_supers, (size_t)n_stats + 2, n_stats + 2, sums);      // ascending super
     __syncthreads();
-    constexpr double kTiny = 10.0 * DBL_EPSILON;
     if (threadIdx.x == 0) {
-        double t = 0.0;
         int empty = 0;
-        for (int kk = 0; kk < k; ++kk) {
-            t += sums[kk * T] + kTiny;
-            empty += sums[kk * T] == 0.0;
-        }
-        n_total = t;
+        for (int kk = 0; kk < k; ++kk) empty += sums[kk * T] == 0.0;
         ctrl->n_empty = empty;
         ctrl->inertia = sums[n_stats];
     }
-    __syncthreads();
-    double *w = params, *mu = params + k, *var = mu + (size_t)k * d, *lcd = var + (size_t)k * d;
-    float *lc = model.log_consts(), *c = model.means(), *ic = model.inv_covs();
-    if (threadIdx.x < k) {
-        const int kk = threadIdx.x;
-        const double *st = sums + kk * T;
-        const double n1 = st[0] + kTiny, r = st[0] / n1;
-        double log_det = 0.0;
-        for (int j = 0; j < d; ++j) {                                 // ascending d
-            const double cj = (double)c[kk * d + j];                  // what the statistics were centred on
-            const double delta = st[1 + j] / n1;
-            const double mean = r * cj + delta;
-            const double e2 = st[1 + d + j] / n1 + 2.0 * cj * delta + r * cj * cj;
-            const double v = e2 - mean * mean + reg_covar;
-            mu[kk * d + j] = mean;
-            var[kk * d + j] = v;
-            c[kk * d + j] = (float)mean;
-            ic[kk * d + j] = (float)(1.0 / v);
-            log_det += log(2.0 * M_PI * v);
-        }
-        const double wk = n1 / n_total;
-        const double l = log(wk) - 0.5 * log_det;
-        w[kk] = wk;
-        lcd[kk] = l;
-        lc[kk] = (float)l;
-        counts[kk] = st[0];
-    }
+    if (threadIdx.x < k) counts[threadIdx.x] = sums[threadIdx.x * T];
+    gmm_mstep(sums, reg_covar, UbmParams<double>{params, k, model.d}, model);
 }
 
 // --- seeding ---
@@ -286,10 +244,7 @@ __global__ __launch_bounds__(kThreads) void kmeans_seed_pass_kernel(const float 
         n_here = cc + 1;
         const long left = n - r0;
         const int cnt = left < kUbmChunkRows ? (int)left : kUbmChunkRows;
-        for (int i = threadIdx.x; i < cnt * D; i += kThreads) {
-            const int r = i / D;
-            xs[r * kSeedLd + (i - r * D)] = feats[r0 * D + i];
-        }
+        stage_rows<D, kSeedLd>(xs, feats + r0 * D, cnt);
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
             float x[D];
@@ -404,22 +359,24 @@ __global__ __launch_bounds__(kThreads) void kmeans_seed_pick_kernel(const float 
     }
 }
 
+// the labelled statistics and their supers; the final pass runs whatever KmeansCtrl::done says
+hipError_t launch_kmeans_stats(const KmeansFit &f, int final_pass, hipStream_t stream)
+{
+    return launch_group_stats(f.model.k, f.model.d, f.n, kmeans_partial_doubles(f.model.k, f.model.d), final_pass ? nullptr : &f.ctrl->done, f.groups, f.supers, stream,
+                              [&](auto dc, dim3 grid, dim3 block, size_t lds) {
+                                  hipLaunchKernelGGL(kmeans_stats_kernel<decltype(dc)::value>, grid, block, lds, stream, f.feats, f.n,
+                                                     GmmModel{f.model.block, f.model.k, f.model.d}, f.ctrl, final_pass, f.labels, f.groups);
+                              });
+}
+
 }  // namespace
 
 hipError_t launch_kmeans_iterations(const KmeansFit &f, int first, int count, hipStream_t stream)
 {
-    const long n_groups = ubm_groups(f.n), n_supers = ubm_supers(f.n);
-    const int k = f.model.k, d = f.model.d, n_stats = k * (2 * d + 1);
-    if (k < 1 || k > kGmmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
     for (int it = first; it < first + count; ++it) {
-        hipError_t e = dispatch_d(d, [&](auto dc) {
-            hipLaunchKernelGGL(kmeans_stats_kernel<decltype(dc)::value>, dim3((unsigned)n_groups), dim3(kThreads), (size_t)(kThreads / 64) * n_stats * sizeof(float), stream,
-                               f.feats, f.n, GmmModel{f.model.block, k, d}, f.ctrl, 0, f.labels, f.groups);
-            return hipGetLastError();
-        });
+        hipError_t e = launch_kmeans_stats(f, 0, stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kmeans_supers_kernel, dim3((unsigned)n_supers), dim3(kThreads), 0, stream, f.groups, n_groups, n_stats + 2, f.ctrl, 0, f.supers);
-        hipLaunchKernelGGL(kmeans_update_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, it, f.max_iter, f.shift_limit, f.centres, f.model, f.ctrl);
+        hipLaunchKernelGGL(kmeans_update_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, ubm_supers(f.n), it, f.max_iter, f.shift_limit, f.centres, f.model, f.ctrl);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -428,17 +385,9 @@ hipError_t launch_kmeans_iterations(const KmeansFit &f, int first, int count, hi
 
 hipError_t launch_kmeans_final(const KmeansFit &f, hipStream_t stream)
 {
-    const long n_groups = ubm_groups(f.n), n_supers = ubm_supers(f.n);
-    const int k = f.model.k, d = f.model.d, n_stats = k * (2 * d + 1);
-    if (k < 1 || k > kGmmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
-    hipError_t e = dispatch_d(d, [&](auto dc) {
-        hipLaunchKernelGGL(kmeans_stats_kernel<decltype(dc)::value>, dim3((unsigned)n_groups), dim3(kThreads), (size_t)(kThreads / 64) * n_stats * sizeof(float), stream,
-                           f.feats, f.n, GmmModel{f.model.block, k, d}, f.ctrl, 1, f.labels, f.groups);
-        return hipGetLastError();
-    });
+    const hipError_t e = launch_kmeans_stats(f, 1, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kmeans_supers_kernel, dim3((unsigned)n_supers), dim3(kThreads), 0, stream, f.groups, n_groups, n_stats + 2, f.ctrl, 1, f.supers);
-    hipLaunchKernelGGL(kmeans_gmm_start_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, f.reg_covar, f.params, f.model, f.counts, f.ctrl);
+    hipLaunchKernelGGL(kmeans_gmm_start_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, ubm_supers(f.n), f.reg_covar, f.params, f.model, f.counts, f.ctrl);
     return hipGetLastError();
 }
 

@@ -7,18 +7,16 @@
 //               N += p, F += p (x - c), G += (p (x - c)) (x - c): moments centred on c (E[x^2] - mean^2 in float32 goes negative at the
 //               variance floor).  Per chunk the four waves combine through LDS in wave order and every thread adds the chunk's float32
 //               sums it owns to float64 accumulators; the group's partial leaves with plain stores.
-//   supers      block s adds groups [s S, (s + 1) S) in ascending order, float64
-//   M-step      one block adds the supers in ascending order and does sklearn's _estimate_gaussian_parameters (diag) in float64, writes
-//               the next parameters, the next float32 model, lower_bounds[i] and the stop decision
+//   supers      gmm_stats.hpp's: block s adds groups [s S, (s + 1) S) in ascending order, float64
+//   M-step      one block adds the supers in ascending order, does gmm_stats.hpp's M-step (sklearn's _estimate_gaussian_parameters, diag,
+//               in float64: the next parameters and the next float32 model), and writes lower_bounds[i] and the stop decision
 // The tree depends on n alone (ubm_kernels.hpp) and there are no atomics: a fit is the same bits whatever the grid or the workspace.
 // Every kernel tests UbmCtrl::done first, so max_iter iterations are enqueued without a host round trip and those after the stop do nothing.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cmath>
 
-#include "gmm_estep.hpp"
-#include "ubm_kernels.hpp"
+#include "gmm_stats.hpp"
 
 namespace dsp {
 namespace {
@@ -93,58 +91,16 @@ __global__ __launch_bounds__(kThreads, 4) void ubm_stats_kernel(const float *__r
     if (threadIdx.x == 0) dst[n_stats] = ll_acc;
 }
 
-__global__ __launch_bounds__(kThreads) void ubm_supers_kernel(const double *__restrict__ groups, long n_groups, int n_stats, const UbmCtrl *__restrict__ ctrl,
-                                                              double *__restrict__ supers)
-{
-    if (ctrl->done) return;
-    const long g0 = (long)blockIdx.x * kUbmSuperGroups;
-    const long g1 = g0 + kUbmSuperGroups < n_groups ? g0 + kUbmSuperGroups : n_groups;
-    const size_t stride = (size_t)n_stats + 1;
-    sum_partials(groups + (size_t)g0 * stride, g1 - g0, stride, n_stats + 1, supers + (size_t)blockIdx.x * stride);      // ascending group
-}
-
 __global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__restrict__ supers, long n_supers, long n, int iter, double tol,
                                                              double reg_covar, double *__restrict__ params, GmmModelOut model,
                                                              double *__restrict__ lower_bounds, UbmCtrl *__restrict__ ctrl)
 {
     __shared__ double sums[kGmmMaxK * (2 * kGmmMaxD + 1) + 1];
-    __shared__ double n_total;
     if (ctrl->done) return;
-    const int k = model.k, d = model.d, T = 2 * d + 1, n_stats = k * T;
+    const int n_stats = model.k * (2 * model.d + 1);
     sum_partials(supers, n_supers, (size_t)n_stats + 1, n_stats + 1, sums);      // ascending super
     __syncthreads();
-    constexpr double kTiny = 10.0 * DBL_EPSILON;                      // sklearn: nk = resp.sum(axis=0) + 10 * np.finfo(resp.dtype).eps
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int kk = 0; kk < k; ++kk) t += sums[kk * T] + kTiny;
-        n_total = t;
-    }
-    __syncthreads();
-    double *w = params, *mu = params + k, *var = mu + (size_t)k * d, *lcd = var + (size_t)k * d;
-    float *lc = model.log_consts(), *c = model.means(), *ic = model.inv_covs();
-    if (threadIdx.x < k) {
-        const int kk = threadIdx.x;
-        const double *st = sums + kk * T;
-        const double n1 = st[0] + kTiny, r = st[0] / n1;
-        double log_det = 0.0;
-        for (int j = 0; j < d; ++j) {                                 // ascending d
-            const double cj = (double)c[kk * d + j];                  // what the statistics were centred on
-            const double delta = st[1 + j] / n1;
-            const double mean = r * cj + delta;
-            const double e2 = st[1 + d + j] / n1 + 2.0 * cj * delta + r * cj * cj;
-            const double v = e2 - mean * mean + reg_covar;
-            mu[kk * d + j] = mean;
-            var[kk * d + j] = v;
-            c[kk * d + j] = (float)mean;
-            ic[kk * d + j] = (float)(1.0 / v);
-            log_det += log(2.0 * M_PI * v);
-        }
-        const double wk = n1 / n_total;
-        const double l = log(wk) - 0.5 * log_det;
-        w[kk] = wk;
-        lcd[kk] = l;
-        lc[kk] = (float)l;
-    }
+    gmm_mstep(sums, reg_covar, UbmParams<double>{params, model.k, model.d}, model);
     if (threadIdx.x == 0) {
         const double lb = sums[n_stats] / (double)n;
         lower_bounds[iter] = lb;
@@ -161,18 +117,12 @@ __global__ __launch_bounds__(kThreads) void ubm_mstep_kernel(const double *__res
 
 hipError_t launch_ubm_iterations(const UbmFit &f, int first, int count, hipStream_t stream)
 {
-    const long n_groups = ubm_groups(f.n), n_supers = ubm_supers(f.n);
-    const int k = f.model.k, d = f.model.d, n_stats = k * (2 * d + 1);
-    if (k < 1 || k > kGmmMaxK || f.n < 1 || n_groups > (1L << 30)) return hipErrorInvalidValue;
     for (int it = first; it < first + count; ++it) {
-        hipError_t e = dispatch_d(d, [&](auto dc) {
-            hipLaunchKernelGGL(ubm_stats_kernel<decltype(dc)::value>, dim3((unsigned)n_groups), dim3(kThreads), (size_t)(kThreads / 64) * n_stats * sizeof(float), stream,
-                               f.feats, f.n, GmmModel{f.model.block, k, d}, f.ctrl, f.groups);
-            return hipGetLastError();
+        hipError_t e = launch_group_stats(f.model.k, f.model.d, f.n, ubm_partial_doubles(f.model.k, f.model.d), &f.ctrl->done, f.groups, f.supers, stream, [&](auto dc, dim3 grid, dim3 block, size_t lds) {
+            hipLaunchKernelGGL(ubm_stats_kernel<decltype(dc)::value>, grid, block, lds, stream, f.feats, f.n, GmmModel{f.model.block, f.model.k, f.model.d}, f.ctrl, f.groups);
         });
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ubm_supers_kernel, dim3((unsigned)n_supers), dim3(kThreads), 0, stream, f.groups, n_groups, n_stats, f.ctrl, f.supers);
-        hipLaunchKernelGGL(ubm_mstep_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, n_supers, f.n, it, f.tol, f.reg_covar, f.params, f.model, f.lower_bounds, f.ctrl);
+        hipLaunchKernelGGL(ubm_mstep_kernel, dim3(1), dim3(kThreads), 0, stream, f.supers, ubm_supers(f.n), f.n, it, f.tol, f.reg_covar, f.params, f.model, f.lower_bounds, f.ctrl);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

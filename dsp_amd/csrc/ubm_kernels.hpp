@@ -26,6 +26,14 @@ inline long ubm_supers(long n) { return (ubm_groups(n) + kUbmSuperGroups - 1) / 
 inline size_t ubm_partial_doubles(int k, int d) { return (size_t)k * (2 * d + 1) + 1; }
 // the float64 parameters between iterations: w[k], mu[k][d], var[k][d], log_const[k]
 inline size_t ubm_param_doubles(int k, int d) { return (size_t)k * (2 * d + 2); }
+template <class F> struct UbmParams {
+    F *block;                // ubm_param_doubles, on the host or the device
+    int k, d;
+    __host__ __device__ F *w() const { return block; }
+    __host__ __device__ F *mu() const { return block + k; }
+    __host__ __device__ F *var() const { return block + k + (size_t)k * d; }
+    __host__ __device__ F *log_const() const { return block + k + 2 * (size_t)k * d; }
+};
 
 // what the launches of one fit share on the device: `done` is tested first by every kernel of every later iteration
 struct UbmCtrl {

@@ -304,6 +304,24 @@ def test_n_init_restarts_are_the_separate_runs_and_the_best_is_kept(torch_cuda, 
     assert one["report"]["winner"] == 0 and np.array_equal(one["lower_bounds"], separate[0]["lower_bounds"])
 
 
+def test_one_em_iteration_from_hard_posteriors_is_the_kmeans_start(torch_cuda):
+    """three clusters 1000 apart at unit noise, 700 rows (two chunks and a partial one): from the k-means centres at variance 1 every
+    float32 posterior is exactly 0 or 1, so one EM iteration sums what Lloyd's final pass summed and the M-step both call gives the
+    same weights, means and variances, bit for bit"""
+    import dsp_amd
+    k, d, n = 3, 2, 700
+    which = np.arange(n) % k
+    x = (1000.0 * which[:, None] + np.random.default_rng(3).normal(size=(n, d))).astype(np.float32)
+    start = np.stack([x[which == i].astype(np.float64).mean(axis=0) for i in range(k)])
+    xd = _cuda(torch_cuda, x)
+    tr = dsp_amd.UbmTrainer(k, d)
+    km = tr.kmeans(xd, start, max_iter=1, tol=0.0, reg_covar=1e-6, want_labels=True)
+    assert np.array_equal(km["labels"].cpu().numpy(), which)
+    em = tr.fit(xd, init={"weights": np.full(k, 1.0 / k), "means": km["centres"], "variances": np.ones((k, d))}, max_iter=1, tol=0.0, reg_covar=1e-6)
+    for key in START_KEYS:
+        assert np.array_equal(em[key], km[key]), key
+
+
 def test_kmeans_start_then_em_is_sklearns_gaussian_mixture(torch_cuda, golden):
     """the fixture's k-means start, then 10 EM iterations, against sklearn's recorded GaussianMixture answer from its own start, within
     the gate tests/test_gpu_ubm.py's fixture test uses"""
