@@ -198,6 +198,19 @@ int dsp_resample_ratio(int rate_in, int rate_out, int *up, int *down, int *half_
     return DSP_OK;
 }
 
+int dsp_resample_geometry(int rate_in, int rate_out, int *fields, int n)
+{
+    Ratio r;
+    if (const int rc = reduce(rate_in, rate_out, r)) return rc;
+    const dsp::ResampleShape s = make_shape(r);
+    const int v[] = {s.up, s.down, s.half, s.taps, s.row, s.tile, s.items, s.span, s.staged, s.lds_bytes};
+    constexpr int count = (int)(sizeof(v) / sizeof(v[0]));
+    if (!fields) return count;
+    if (n < count) return capi_fail(DSP_EINVAL, "fields holds " + std::to_string(n) + " ints, the geometry has " + std::to_string(count) + " fields");
+    std::memcpy(fields, v, sizeof(v));
+    return count;
+}
+
 int dsp_resample_taps(int rate_in, int rate_out, double *h, int n)
 {
     Ratio r;

@@ -298,7 +298,7 @@ SYMBOLS = [
     "dsp_stream_resample_plan", "dsp_stream_resampler_create", "dsp_stream_resampler_destroy", "dsp_stream_resampler_reset",
     "dsp_stream_resampler_counts", "dsp_stream_resample_push_device", "dsp_stream_resample_finish_device", "dsp_stream_session_attach_resampler",
     "dsp_upsample_linear_device", "dsp_upsample_linear_host",
-    "dsp_resample_ratio", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
+    "dsp_resample_ratio", "dsp_resample_geometry", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
     "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device", "dsp_resample_clips_pcm16_device",
     "dsp_resample_host",
     "dsp_cmvn_create", "dsp_cmvn_destroy", "dsp_cmvn_ragged_device",
@@ -460,6 +460,7 @@ def load() -> C.CDLL:
     L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
     L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
     L.dsp_resample_ratio.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]; L.dsp_resample_ratio.restype = ip
+    L.dsp_resample_geometry.argtypes = [ip, ip, C.POINTER(ip), ip]; L.dsp_resample_geometry.restype = ip
     L.dsp_resample_taps.argtypes = [ip, ip, C.POINTER(C.c_double), ip]; L.dsp_resample_taps.restype = ip
     L.dsp_resample_offsets.argtypes = [ip, ip, lp, C.c_long, lp]; L.dsp_resample_offsets.restype = C.c_long
     L.dsp_resampler_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_resampler_create.restype = ip

@@ -26,6 +26,22 @@ def resample_ratio(rate_in: int, rate_out: int):
     return up.value, down.value, half.value
 
 
+GEOMETRY_FIELDS = ("up", "down", "half", "taps", "row", "tile", "items", "span", "staged", "lds_bytes")
+
+
+def resample_geometry(rate_in: int, rate_out: int) -> dict:
+    """Host only (dsp_resample_geometry): the block geometry the kernels run this ratio with -- taps per polyphase branch, outputs and
+    lane work items per block, the input span a block reads, whether it is staged in LDS (0: read from global memory; no live streams)."""
+    rate_in, rate_out = _rates(rate_in, rate_out)
+    L = _lib.load()
+    n = _lib.check(L.dsp_resample_geometry(rate_in, rate_out, None, 0), "dsp_resample_geometry")
+    if n != len(GEOMETRY_FIELDS):
+        raise _lib.DspError(f"the library reports {n} geometry fields, the wrapper knows {len(GEOMETRY_FIELDS)}")
+    v = (C.c_int * n)()
+    _lib.check(L.dsp_resample_geometry(rate_in, rate_out, v, n), "dsp_resample_geometry")
+    return dict(zip(GEOMETRY_FIELDS, (int(x) for x in v)))
+
+
 def resample_taps(rate_in: int, rate_out: int) -> np.ndarray:
     """The float64 taps h[2 half + 1] (= scipy.signal.firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up)."""
     rate_in, rate_out = _rates(rate_in, rate_out)

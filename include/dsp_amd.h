@@ -706,6 +706,11 @@ int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_
  * Host only, no GPU: dsp_resample_ratio (any pointer may be NULL); dsp_resample_taps (returns 2 half + 1; h may be NULL, else n >= that);
  * dsp_resample_offsets: offsets[n + 1] as dsp_mfcc_clips_ragged_device takes them -> out_offsets[n + 1], the prefix sums of the output
  * lengths from 0; returns their total.  Each returns a negative DSP_E* code on error.
+ * dsp_resample_geometry (diagnostic, for tests): the block geometry the kernels run this ratio with, a function of (up, down) alone, as
+ * ints in this order: up, down, half, taps (of one polyphase branch, T), row (T rounded up to 4), tile (consecutive outputs per block),
+ * items (lane work items per block, tile / 4), span (input samples a tile reads), staged (1: the span is staged in LDS; 0: a branch too
+ * long for it, samples read from global memory -- the ratios dsp_stream_resampler_create refuses), lds_bytes.  Returns the field count
+ * (10); fields NULL asks for the count only, else n >= that.
  *
  * A dsp_resampler holds the taps of one ratio on one GPU.  dsp_resample_ragged_device: recording c = samples [offsets[c], offsets[c + 1])
  * per channel of d_in (`offsets` a HOST array, read before the call returns) -> d_out + out_offsets[c], back to back: d_out and those
@@ -716,6 +721,7 @@ int dsp_upsample_linear_host(const float *in, int old_size, float *out, int new_
  * stream at a time per resampler.  Zero recordings (or none with a sample): DSP_OK, no launch.
  * dsp_resample_host: one recording from host memory on GPU 0 (copy in, run, copy out); out holds ceil(n up / down) floats.            */
 int dsp_resample_ratio(int rate_in, int rate_out, int *up, int *down, int *half_len);
+int dsp_resample_geometry(int rate_in, int rate_out, int *fields, int n);
 int dsp_resample_taps(int rate_in, int rate_out, double *h, int n);
 long dsp_resample_offsets(int rate_in, int rate_out, const long *offsets, long n, long *out_offsets);
 typedef struct dsp_resampler dsp_resampler;

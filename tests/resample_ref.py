@@ -43,10 +43,12 @@ def offsets(rate_in, rate_out, offs):
     return np.concatenate([[0], np.cumsum([out_len(int(n), up, down) for n in np.diff(offs)])]).astype(np.int64)
 
 
-def resample(x, rate_in, rate_out, dtype=np.float64, with_bound=False):
-    """y[ceil(n up / down)] of x[n] in `dtype` arithmetic; with_bound: also sum_i |x[i] h[.]| (float64) and the terms L_k per output."""
+def resample(x, rate_in, rate_out, dtype=np.float64, with_bound=False, h64=None):
+    """y[ceil(n up / down)] of x[n] in `dtype` arithmetic; with_bound: also sum_i |x[i] h[.]| (float64) and the terms L_k per output.
+    h64: other float64 taps than the definition's, 2 half + 1 of them (the mutants of tests/resample_shapes.py)."""
     up, down, half = ratio(rate_in, rate_out)
-    h64 = taps(rate_in, rate_out)
+    h64 = taps(rate_in, rate_out) if h64 is None else np.asarray(h64, np.float64)
+    assert h64.shape == (2 * half + 1,)
     x64 = np.asarray(x, np.float64)
     n = x64.size
     n_out = out_len(n, up, down)

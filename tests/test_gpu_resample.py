@@ -4,7 +4,9 @@
     |got[k] - ref[k]| <= (L_k + 2) 2^-24 sum_i |h x|       L_k = the terms of output k
 
 (taps rounded once to float32, L_k products and sums in float32: it holds for any summation order, with or without FMA; the sequential
-float32 model of resample_ref stays within 0.34 of it).  Then what must hold bit for bit: a recording's output does not depend on the
+float32 model of resample_ref stays within 0.34 of it; the bound grows with the branch length, so the long branches -- and every
+kernel form and tile geometry these seven ratios do not reach -- are held to the tighter rms gate of tests/resample_shapes.py in
+tests/test_gpu_resample_shapes.py).  Then what must hold bit for bit: a recording's output does not depend on the
 batch around it or on the entry it came through, int16 input is the float entry on the decoded samples, 16000 -> 16000 is the input.
 The resampler exposes no launch geometry (its tiling is a function of the ratio alone), so there is none to vary.  Last, composition
 with what follows it: MFCC rows of a resampled clip, and a Scanner run on the resampler's own (out, out_offsets)."""

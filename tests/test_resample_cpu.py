@@ -19,7 +19,7 @@ from tests.conftest import gate
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIRS = R.RATE_PAIRS + [(1, 1024), (1024, 1)]
-RESAMPLE_SYMBOLS = ["dsp_resample_ratio", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
+RESAMPLE_SYMBOLS = ["dsp_resample_ratio", "dsp_resample_geometry", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
                     "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device",
                     "dsp_resample_clips_pcm16_device", "dsp_resample_host"]
 COMPOSITION_CLIPS = ("chirp", "stop1")       # tests/test_gpu_resample.py resamples these on the GPU
