@@ -240,6 +240,18 @@ STOP_TRAIN_STATUS = ("converged_early", "max_epochs", "no_validation", "empty")
 STOP_TRAIN_CAP_ROWS, STOP_TRAIN_CAP_UNITS, STOP_TRAIN_CAP_BATCH, STOP_TRAIN_CAP_EPOCHS, STOP_TRAIN_CAP_RUNS = 65536, 16, 256, 10000, 4096
 
 
+class AugmentOp(C.Structure):
+    """dsp_augment_op (include/dsp_amd.h), 40 bytes; AUGMENT_OP_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("clip", C.c_long), ("kind", C.c_int), ("rate", C.c_double), ("n_steps", C.c_int), ("sigma", C.c_float), ("key", C.c_uint64)]
+
+
+AUGMENT_OP_DTYPE = {"names": ["clip", "kind", "rate", "n_steps", "sigma", "key"], "formats": ["<i8", "<i4", "<f8", "<i4", "<f4", "<u8"],
+                    "offsets": [0, 8, 16, 24, 28, 32], "itemsize": 40}
+PAD_REFLECT, PAD_ZERO = 0, 1
+AUGMENT_STRETCH, AUGMENT_PITCH, AUGMENT_NOISE = 0, 1, 2
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -315,6 +327,9 @@ SYMBOLS = [
     "dsp_stop_trainer_create", "dsp_stop_trainer_destroy", "dsp_stop_train_set_device", "dsp_stop_train_used_features", "dsp_stop_train_rows_host",
     "dsp_stop_train_runs_device", "dsp_stop_train_param_count", "dsp_stop_train_uniform", "dsp_stop_train_order", "dsp_stop_train_init",
     "dsp_stop_model_from_training",
+    "dsp_stft_frames", "dsp_stretch_frames", "dsp_stretch_length", "dsp_pitch_ratio", "dsp_augment_normal", "dsp_augment_out_offsets", "dsp_augment_draw",
+    "dsp_augmenter_create", "dsp_augmenter_destroy", "dsp_stft_ragged_device", "dsp_istft_ragged_device", "dsp_time_stretch_ragged_device",
+    "dsp_augment_ragged_device",
     "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
     "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
 ]
@@ -470,6 +485,20 @@ def load() -> C.CDLL:
     L.dsp_resample_clips_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, C.c_long, vp]; L.dsp_resample_clips_device.restype = ip
     L.dsp_resample_clips_pcm16_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, C.c_long, vp]; L.dsp_resample_clips_pcm16_device.restype = ip
     L.dsp_resample_host.argtypes = [ip, ip, vp, C.c_long, vp]; L.dsp_resample_host.restype = ip
+    opp, dp, u64 = C.POINTER(AugmentOp), C.POINTER(C.c_double), C.c_uint64
+    L.dsp_stft_frames.argtypes = [C.c_long]; L.dsp_stft_frames.restype = C.c_long
+    L.dsp_stretch_frames.argtypes = [C.c_long, C.c_double]; L.dsp_stretch_frames.restype = C.c_long
+    L.dsp_stretch_length.argtypes = [C.c_long, C.c_double]; L.dsp_stretch_length.restype = C.c_long
+    L.dsp_pitch_ratio.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]; L.dsp_pitch_ratio.restype = ip
+    L.dsp_augment_normal.argtypes = [u64, u64, u64]; L.dsp_augment_normal.restype = C.c_double
+    L.dsp_augment_out_offsets.argtypes = [lp, C.c_long, opp, C.c_long, lp]; L.dsp_augment_out_offsets.restype = C.c_long
+    L.dsp_augment_draw.argtypes = [u64, C.POINTER(ip), C.c_long, C.c_double, opp, C.c_long]; L.dsp_augment_draw.restype = C.c_long
+    L.dsp_augmenter_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_augmenter_create.restype = ip
+    L.dsp_augmenter_destroy.argtypes = [vp]; L.dsp_augmenter_destroy.restype = None
+    L.dsp_stft_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, lp, vp]; L.dsp_stft_ragged_device.restype = ip
+    L.dsp_istft_ragged_device.argtypes = [vp, vp, C.c_long, lp, lp, vp, lp, vp]; L.dsp_istft_ragged_device.restype = ip
+    L.dsp_time_stretch_ragged_device.argtypes = [vp, vp, C.c_long, lp, dp, vp, vp]; L.dsp_time_stretch_ragged_device.restype = ip
+    L.dsp_augment_ragged_device.argtypes = [vp, vp, C.c_long, lp, opp, C.c_long, u64, vp, vp]; L.dsp_augment_ragged_device.restype = ip
     L.dsp_cmvn_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_cmvn_create.restype = ip
     L.dsp_cmvn_destroy.argtypes = [vp]; L.dsp_cmvn_destroy.restype = None
     L.dsp_cmvn_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_cmvn_ragged_device.restype = ip

@@ -1461,6 +1461,84 @@ int dsp_stop_train_init(int n_coef, int max_frames, const int *units, unsigned l
 int dsp_stop_model_from_training(int n_coef, int max_frames, const int *units, const double *params, const float *mean, const float *scale,
                                  float *arrays, dsp_stop_model_params *model);
 
+/* --- augmenting raw training clips: time stretch, pitch shift, additive noise; complex STFT and inverse STFT ---
+ * cepstrum/train.py:25-36, 52-56 enlarges the minority class with augment(): librosa.effects.time_stretch, librosa.effects.pitch_shift
+ * or y + 0.005 * randn, on raw audio, before the features are taken.  These entries do that to a ragged batch of float32 clips in HBM.
+ * librosa is an unpinned dependency of the reference: the algorithm is restated here from its published form (stft / phase_vocoder /
+ * istft of librosa < 0.10, whose stft pads with "reflect"), and PARITY WITH LIBROSA'S OWN NUMBERS IS UNPINNED.  Two stated differences:
+ * pitch_shift resamples with this library's polyphase Kaiser-windowed sinc (dsp_resample_*, scipy.signal.resample_poly's filter) where
+ * librosa uses resampy's "kaiser_best" (a longer windowed sinc interpolated at the irrational ratio itself), and at a rational
+ * approximation of 2^(-n_steps / 12) (below); and the noise comes from the library's counter-based draws, not numpy's stream.
+ *
+ * CONSTANTS.  n_fft 2048, hop 512, window 0.5 - 0.5 cos(2 pi i / 2048) (periodic Hann), 1025 bins; float32 samples.
+ * STFT (center = True).  A clip of n samples has T = 1 + n / 512 frames; frame t covers samples [512 t, 512 t + 2048) of the clip padded
+ * by 1024 on both sides; D[t][k], k = 0 .. 1024, is the forward DFT of window x frame as interleaved float32 (re, im), frame-major.
+ * DSP_PAD_REFLECT pads as np.pad(mode = "reflect") and needs n >= 1025; DSP_PAD_ZERO pads with zeros and takes any n >= 1.
+ * PHASE VOCODER.  T_out = ceil(T / rate) in double; output frame t reads columns i = floor(t * rate) and i + 1 (a = t * rate - i; columns
+ * T and T + 1 read as zero); with phi_k = pi * 512 * k / 1024:
+ *     acc_0[k] = angle(D[0][k]);   S[t][k] = ((1 - a) |D[i][k]| + a |D[i+1][k]|) exp(j acc_t[k]);
+ *     d = angle(D[i+1][k]) - angle(D[i][k]) - phi_k;  d -= 2 pi rint(d / 2 pi);   acc_{t+1} = acc_t + phi_k + d
+ * acc is float64, summed in frame order; sin / cos take acc - 2 pi rint(acc / 2 pi) rounded to float32; angle(0) = 0 (silence in,
+ * exact zeros out).
+ * INVERSE STFT.  Frame t -> irfft (1 / 2048 included, Im of bins 0 and 1024 ignored) x window, overlap-added at 512 t with the frames
+ * summed in ascending t, divided by the sum (same order) of the squared window where that exceeds FLT_MIN; the first 1024 samples
+ * dropped; cropped or zero filled to `length`.
+ * time_stretch(y, rate) = STFT -> vocoder -> inverse STFT with length = max(1, rint(n / rate)) (double division, ties to even).
+ * pitch_shift(y, n_steps): (up, down) = dsp_pitch_ratio(n_steps, 12, max_term): the fraction with max(up, down) <= max_term (the
+ * augmenter's, default 256, at most 1024) nearest to 2^(-n_steps / 12) by |up / down - 2^(-n_steps / 12)| in double, ties to the
+ * smaller denominator (+-1 step: 185/196, 196/185; +-2: 49/55, 55/49 -- 0.006 and 0.02 cents off).  Stretch by rate = (double)up / down,
+ * resample with dsp_resampler_create(device, rate_in = down, rate_out = up) (a copy when up == down), crop or zero fill to n.
+ * add_noise: y[i] + sigma z_i with d = the 64-bit draw of dsp_stop_train_uniform's generator at (seed, stream = key, counter = j),
+ * u1 = ((d >> 40) + 1) 2^-24, u2 = ((d >> 16) & 0xFFFFFF) 2^-24, r = sqrt(-2 ln u1): z_{2j} = r cos(2 pi u2), z_{2j+1} = r sin(2 pi u2),
+ * evaluated in float32 on the GPU; dsp_augment_normal returns z_i in float64.  A stretch or pitch op with sigma > 0 gets the same noise
+ * added to its result.
+ *
+ * HOST ONLY, no GPU: dsp_stft_frames (T), dsp_stretch_frames (T_out), dsp_stretch_length, dsp_pitch_ratio, dsp_augment_normal;
+ * dsp_augment_out_offsets: out_offsets[m + 1] = prefix sums of the ops' output lengths (stretch: dsp_stretch_length of its clip; pitch
+ * and noise: the clip's length), returns the total; dsp_augment_draw: train.py's policy with the library's draws -- row r with
+ * labels[r] == 1 gets an op when u(S + 0, r) < prob; its kind is floor(3 u(S + 1, r)); a stretch has rate = 0.8 + 0.4 u(S + 2, r), a
+ * pitch shift n_steps = floor(5 u(S + 3, r)) - 2, noise sigma = 0.005; clip = key = r; u(stream, counter) = dsp_stop_train_uniform(seed,
+ * stream, counter) and S = 0xA000000000000000 keeps the policy's streams away from the noise keys.  Returns the op count (ops may be
+ * NULL to count; more ops than `cap`: DSP_EINVAL).  All return < 0 on error.
+ *
+ * A dsp_augmenter holds the tables, grow-only workspaces and one resampler per pitch ratio on one GPU; one call at a time per handle.
+ * Offsets are host arrays read before the call returns; the work is enqueued on `stream` and not waited for.
+ * dsp_stft_ragged_device: clip c = samples [offsets[c], offsets[c + 1]) of d_in -> d_spec [sum T][1025] (re, im), clip c's rows from
+ * frame_offsets_out[c] (n + 1 entries, may be NULL).  dsp_istft_ragged_device: rows [frame_offsets[c], frame_offsets[c + 1]) of d_spec
+ * -> lengths[c] samples at d_out + out_offsets[c].  dsp_time_stretch_ragged_device: rates[n] doubles on the host; exactly the STFT
+ * entry, the vocoder and the inverse STFT entry on the handle's workspaces; clip c's output at the prefix sums of dsp_stretch_length.
+ * dsp_augment_ragged_device: op j reads clip ops[j].clip and writes at out_offsets[j] of dsp_augment_out_offsets (a clip may appear in
+ * several ops).  A clip's output is the same bits whatever else is in the batch and in whatever order.
+ * DSP_EINVAL with a reason: rate not finite or outside [1/8, 8]; |n_steps| > 12; sigma < 0 (or NaN); an unknown kind; a clip index out of
+ * range; a clip to transform with n < 1, or n < 1025 under DSP_PAD_REFLECT; a clip of 2^24 samples or more.  n == 0 (m == 0): DSP_OK,
+ * nothing is touched.                                                                                                              */
+enum { DSP_PAD_REFLECT = 0, DSP_PAD_ZERO = 1 };
+enum { DSP_AUGMENT_STRETCH = 0, DSP_AUGMENT_PITCH = 1, DSP_AUGMENT_NOISE = 2 };
+typedef struct dsp_augment_op {
+    long clip;                    /* the clip the op reads */
+    int kind;                     /* DSP_AUGMENT_* */
+    double rate;                  /* STRETCH */
+    int n_steps;                  /* PITCH, semitones */
+    float sigma;                  /* NOISE (any kind: added to the result when > 0) */
+    unsigned long long key;       /* the stream of the noise draws */
+} dsp_augment_op;
+typedef struct dsp_augmenter dsp_augmenter;
+long dsp_stft_frames(long n);
+long dsp_stretch_frames(long n_frames, double rate);
+long dsp_stretch_length(long n, double rate);
+int dsp_pitch_ratio(int n_steps, int bins_per_octave, int max_term, int *up, int *down);
+double dsp_augment_normal(unsigned long long seed, unsigned long long key, unsigned long long i);
+long dsp_augment_out_offsets(const long *offsets, long n, const dsp_augment_op *ops, long m, long *out_offsets);
+long dsp_augment_draw(unsigned long long seed, const int *labels, long n, double prob, dsp_augment_op *ops, long cap);
+int dsp_augmenter_create(int device, int pad_mode, int max_term, dsp_augmenter **out);
+void dsp_augmenter_destroy(dsp_augmenter *aug);
+int dsp_stft_ragged_device(dsp_augmenter *aug, const float *d_in, long n, const long *offsets, float *d_spec, long *frame_offsets_out, void *stream);
+int dsp_istft_ragged_device(dsp_augmenter *aug, const float *d_spec, long n, const long *frame_offsets, const long *lengths, float *d_out,
+                            const long *out_offsets, void *stream);
+int dsp_time_stretch_ragged_device(dsp_augmenter *aug, const float *d_in, long n, const long *offsets, const double *rates, float *d_out, void *stream);
+int dsp_augment_ragged_device(dsp_augmenter *aug, const float *d_in, long n, const long *offsets, const dsp_augment_op *ops, long m,
+                              unsigned long long seed, float *d_out, void *stream);
+
 /* Reference-layout constant tables for a configuration (what mfcc_params.h holds
  * for the reference config): window[frame_length], mel[n_mels][n_fft/2+1],
  * dct[n_mfcc][n_mels].  Host-only, no GPU needed; any pointer may be NULL.      */
