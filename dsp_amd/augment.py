@@ -10,7 +10,6 @@ import numpy as np
 from . import lib as _lib
 
 N_FFT, HOP, BINS = 2048, 512, 1025
-_LP = C.POINTER(C.c_long)
 _PADS = {"reflect": _lib.PAD_REFLECT, "zero": _lib.PAD_ZERO}
 _KINDS = {"stretch": _lib.AUGMENT_STRETCH, "pitch": _lib.AUGMENT_PITCH, "noise": _lib.AUGMENT_NOISE}
 
@@ -90,7 +89,7 @@ def augment_out_offsets(offsets, ops) -> np.ndarray:
     off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
     ops = make_ops(ops)
     oo = np.zeros(ops.size + 1, np.int64)
-    _lib.check(_lib.load().dsp_augment_out_offsets(off, n, _ops_ptr(ops), ops.size, oo.ctypes.data_as(_LP)), "dsp_augment_out_offsets")
+    _lib.check(_lib.load().dsp_augment_out_offsets(off, n, _ops_ptr(ops), ops.size, oo.ctypes.data_as(_lib.LP)), "dsp_augment_out_offsets")
     return oo
 
 
@@ -110,36 +109,20 @@ def augment_draw(labels, prob: float = 0.5, seed: int = 0) -> np.ndarray:
     return ops
 
 
-class Augmenter:
+class Augmenter(_lib.Handle):
     """dsp_augmenter: the transform's tables, grow-only workspaces and one resampler per pitch ratio on one GPU.  pad: "reflect"
     (np.pad's, clips of at least 1025 samples) or "zero".  Every method takes a ragged batch -- signal: cuda float32 [total], clip c =
     samples [offsets[c], offsets[c + 1]) -- and is asynchronous on torch's current stream.  One call at a time per object."""
+
+    _destroy = "dsp_augmenter_destroy"
 
     def __init__(self, device: int = 0, pad: str = "reflect", max_term: int = 256):
         if pad not in _PADS:
             raise ValueError('pad must be "reflect" or "zero"')
         if isinstance(max_term, bool) or not isinstance(max_term, (int, np.integer)) or not 1 <= max_term <= 1024:
             raise ValueError("max_term must be an integer 1 .. 1024")
-        self._L = _lib.load()
         self.device, self.pad, self.max_term = int(device), pad, int(max_term)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_augmenter_create(self.device, _PADS[pad], self.max_term, C.byref(h)), "dsp_augmenter_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_augmenter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._create("dsp_augmenter_create", self.device, _PADS[pad], self.max_term)
 
     def _signal(self, signal, offsets):
         import torch
@@ -168,7 +151,7 @@ class Augmenter:
         spec = torch.empty((int(fo[-1]), BINS, 2), dtype=torch.float32, device=signal.device)
         if n:
             got = np.zeros(n + 1, np.int64)
-            _lib.check(self._L.dsp_stft_ragged_device(self._h, ptr, n, off, spec.data_ptr(), got.ctypes.data_as(_LP), self._stream()), "dsp_stft_ragged_device")
+            _lib.check(self._L.dsp_stft_ragged_device(self._h, ptr, n, off, spec.data_ptr(), got.ctypes.data_as(_lib.LP), self._stream()), "dsp_stft_ragged_device")
             if not np.array_equal(got, fo):
                 raise _lib.DspError("dsp_stft_ragged_device counted other frames than the wrapper")
         return spec, fo
@@ -193,8 +176,8 @@ class Augmenter:
         oo[1:] = np.cumsum(lengths)
         out = torch.empty((int(oo[-1]),), dtype=torch.float32, device=spec.device)
         if n:
-            _lib.check(self._L.dsp_istft_ragged_device(self._h, spec.data_ptr(), n, fo.ctypes.data_as(_LP), lengths.ctypes.data_as(_LP), out.data_ptr(),
-                                                       oo.ctypes.data_as(_LP), self._stream()), "dsp_istft_ragged_device")
+            _lib.check(self._L.dsp_istft_ragged_device(self._h, spec.data_ptr(), n, fo.ctypes.data_as(_lib.LP), lengths.ctypes.data_as(_lib.LP), out.data_ptr(),
+                                                       oo.ctypes.data_as(_lib.LP), self._stream()), "dsp_istft_ragged_device")
         return out, oo
 
     def time_stretch(self, signal, offsets, rates):

@@ -112,9 +112,8 @@ def _device(name: str, f64: bool, signal, n_clips: int, labels, config, *args):
     name += "_f64" if f64 else ""
     if labels is None:
         labels = torch.empty(n_clips, dtype=torch.int32, device=signal.device)
-    st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
     trace = (None,) if f64 else ()
-    _lib.check(getattr(_lib.load(), name)(_config(config, f64), signal.data_ptr(), n_clips, *args, labels.data_ptr(), *trace, st), name)
+    _lib.check(getattr(_lib.load(), name)(_config(config, f64), signal.data_ptr(), n_clips, *args, labels.data_ptr(), *trace, _lib.current_stream(signal)), name)
     return labels
 
 

@@ -31,11 +31,6 @@ from . import lib as _lib
 from .mfcc import MfccPlan, default_config, ragged_frame_offsets, speaker_config
 
 
-def _stream(t):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _scan_config(window_frames, hop_frames):
     window_frames, hop_frames = int(window_frames), int(hop_frames)
     if window_frames < 1 or hop_frames < 1:
@@ -44,12 +39,7 @@ def _scan_config(window_frames, hop_frames):
 
 
 def _frame_offsets(frame_offsets):
-    fo = np.ascontiguousarray(np.asarray(frame_offsets, dtype=np.int64))
-    if fo.ndim != 1 or fo.size < 1:
-        raise ValueError("frame_offsets must hold n_recordings + 1 rows")
-    if fo[0] < 0 or (fo.size > 1 and (np.diff(fo) < 0).any()):
-        raise ValueError("frame_offsets must be non-negative and non-decreasing")
-    return fo
+    return _lib.offsets_array(frame_offsets, "frame_offsets", "rows")
 
 
 def scan_window_offsets(frame_offsets, window_frames: int, hop_frames: int) -> np.ndarray:
@@ -58,8 +48,8 @@ def scan_window_offsets(frame_offsets, window_frames: int, hop_frames: int) -> n
     cfg = _scan_config(window_frames, hop_frames)
     fo = _frame_offsets(frame_offsets)
     wo = np.zeros(fo.size, np.int64)
-    lp = C.POINTER(C.c_long)
-    _lib.check(_lib.load().dsp_scan_window_offsets(C.byref(cfg), fo.ctypes.data_as(lp), fo.size - 1, wo.ctypes.data_as(lp)), "dsp_scan_window_offsets")
+    _lib.check(_lib.load().dsp_scan_window_offsets(C.byref(cfg), fo.ctypes.data_as(_lib.LP), fo.size - 1, wo.ctypes.data_as(_lib.LP)),
+               "dsp_scan_window_offsets")
     return wo
 
 
@@ -74,13 +64,14 @@ def _scan_mfcc(mfcc, fo, d):
     return mfcc.contiguous()
 
 
-class StopModel:
+class StopModel(_lib.Handle):
     """dsp_stop_model: StandardScaler + 4 dense layers (ReLU, ReLU, ReLU, sigmoid)."""
+
+    _destroy = "dsp_stop_model_destroy"
 
     def __init__(self, params: dict, device: int = 0):
         """params: scaler_mean, scaler_scale [n_coef * max_frames], kernel0..3 ((in, out) row-major), bias0..3,
         optional n_coef (13), max_frames (500)."""
-        self._L = _lib.load()
         keep = {k: np.ascontiguousarray(params[k], np.float32).reshape(-1) for k in
                 ["scaler_mean", "scaler_scale"] + [f"kernel{i}" for i in range(4)] + [f"bias{i}" for i in range(4)]}
         p = _lib.StopModelParams()
@@ -96,27 +87,15 @@ class StopModel:
             p.bias[i] = keep[f"bias{i}"].ctypes.data
             fan_in = p.units[i]
         p.scaler_mean, p.scaler_scale = keep["scaler_mean"].ctypes.data, keep["scaler_scale"].ctypes.data
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_stop_model_create(C.byref(p), device, C.byref(h)), "dsp_stop_model_create")
-        self._h, self.device, self.n_coef, self.max_frames = h, device, p.n_coef, p.max_frames
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_stop_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_stop_model_create", C.byref(p), device)
+        self.device, self.n_coef, self.max_frames = device, p.n_coef, p.max_frames
 
     def predict(self, mfcc):
         """mfcc: cuda float32 [n_clips][T][n_coef] (frame-major, as compute_mfcc writes) -> prob float32 [n_clips]."""
         import torch
         n, t = mfcc.shape[0], mfcc.shape[1]
         prob = torch.empty(n, dtype=torch.float32, device=mfcc.device)
-        _lib.check(self._L.dsp_stop_predict_device(self._h, mfcc.contiguous().data_ptr(), n, t, prob.data_ptr(), _stream(mfcc)),
+        _lib.check(self._L.dsp_stop_predict_device(self._h, mfcc.contiguous().data_ptr(), n, t, prob.data_ptr(), _lib.current_stream(mfcc)),
                    "dsp_stop_predict_device")
         return prob
 
@@ -126,7 +105,7 @@ class StopModel:
         _lib.clips_device(clips, torch.float32)
         prob = torch.empty(clips.shape[0], dtype=torch.float32, device=clips.device)
         _lib.check(self._L.dsp_classify_signal_batch_device(plan._h, self._h, clips.data_ptr(), clips.shape[0], clips.shape[1],
-                                                            clips.stride(0), prob.data_ptr(), _stream(clips)),
+                                                            clips.stride(0), prob.data_ptr(), _lib.current_stream(clips)),
                    "dsp_classify_signal_batch_device")
         return prob
 
@@ -137,7 +116,7 @@ class StopModel:
         channels, stride = _lib.pcm_device(pcm)
         prob = torch.empty(pcm.shape[0], dtype=torch.float32, device=pcm.device)
         _lib.check(self._L.dsp_classify_signal_batch_pcm16_device(plan._h, self._h, pcm.data_ptr(), pcm.shape[0], pcm.shape[1], stride,
-                                                                  channels, int(stereo_mode), prob.data_ptr(), _stream(pcm)),
+                                                                  channels, int(stereo_mode), prob.data_ptr(), _lib.current_stream(pcm)),
                    "dsp_classify_signal_batch_pcm16_device")
         return prob
 
@@ -149,9 +128,9 @@ class StopModel:
         prob = torch.empty(n, dtype=torch.float32, device=signal.device)
         if channels:
             _lib.check(self._L.dsp_classify_signal_batch_ragged_pcm16_device(plan._h, self._h, ptr, n, off, channels, int(stereo_mode), prob.data_ptr(),
-                                                                             _stream(signal)), "dsp_classify_signal_batch_ragged_pcm16_device")
+                                                                             _lib.current_stream(signal)), "dsp_classify_signal_batch_ragged_pcm16_device")
         else:
-            _lib.check(self._L.dsp_classify_signal_batch_ragged_device(plan._h, self._h, ptr, n, off, prob.data_ptr(), _stream(signal)),
+            _lib.check(self._L.dsp_classify_signal_batch_ragged_device(plan._h, self._h, ptr, n, off, prob.data_ptr(), _lib.current_stream(signal)),
                        "dsp_classify_signal_batch_ragged_device")
         return prob
 
@@ -163,8 +142,8 @@ class StopModel:
         fo = _frame_offsets(frame_offsets)
         mfcc = _scan_mfcc(mfcc, fo, self.n_coef)
         prob = torch.empty(int(wo[-1]), dtype=torch.float32, device=mfcc.device)
-        _lib.check(self._L.dsp_stop_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
-                                                C.byref(_scan_config(window_frames, hop_frames)), prob.data_ptr(), _stream(mfcc)),
+        _lib.check(self._L.dsp_stop_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_lib.LP),
+                                                C.byref(_scan_config(window_frames, hop_frames)), prob.data_ptr(), _lib.current_stream(mfcc)),
                    "dsp_stop_scan_device")
         return wo, prob
 
@@ -238,37 +217,21 @@ def stop_model_from_training(n_coef: int, max_frames: int, units, params, mean, 
     return out
 
 
-class StopTrainer:
+class StopTrainer(_lib.Handle):
     """dsp_stop_trainer: the stop-word net from labelled MFCC matrices, keyword_classifier.py:155-232 on the GPU -- the Scaler and many
     Keras-style fits (seeds, folds, dropout or learning rates) per launch over one standardised matrix.  One stream at a time per trainer."""
 
+    _destroy = "dsp_stop_trainer_destroy"
     HYPER = {"learning_rate": 1e-3, "dropout": (0.3, 0.3, 0.2), "batch_size": 32, "epochs": 50, "patience": 10, "restore_best": True}
 
     def __init__(self, n_coef: int = 13, max_frames: int = 500, units=(4, 2, 2, 1), device: int = 0):
-        self._L = _lib.load()
         self.units = tuple(int(u) for u in units)
         if len(self.units) != 4:
             raise ValueError("units must hold four layer widths")
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_stop_trainer_create(device, int(n_coef), int(max_frames), (C.c_int * 4)(*self.units), C.byref(h)), "dsp_stop_trainer_create")
-        self._h, self.n_coef, self.max_frames, self.device, self.n, self.f_used = h, int(n_coef), int(max_frames), device, 0, 0
+        self._create("dsp_stop_trainer_create", device, int(n_coef), int(max_frames), (C.c_int * 4)(*self.units))
+        self.n_coef, self.max_frames, self.device, self.n, self.f_used = int(n_coef), int(max_frames), device, 0, 0
         self.n_params = stop_train_param_count(n_coef, max_frames, self.units)
         self.mean = self.scale = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_stop_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set(self, mfcc, frame_offsets, scaler_rows=None, mean=None, scale=None):
         """The dataset of the calls that follow (dsp_stop_train_set_device): clip i is rows [frame_offsets[i], frame_offsets[i + 1]) of the
@@ -361,27 +324,16 @@ def _gmm_params(g: dict):
     return p, keep
 
 
-class SpeakerModel:
+class SpeakerModel(_lib.Handle):
     """dsp_speaker_model: target GMM vs UBM in the reference's fixed point (Q6 / Q11 / Q8)."""
 
+    _destroy = "dsp_speaker_model_destroy"
+
     def __init__(self, target: dict, ubm: dict, device: int = 0):
-        self._L = _lib.load()
         pt, _k1 = _gmm_params(target)
         pu, _k2 = _gmm_params(ubm)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_speaker_model_create(C.byref(pt), C.byref(pu), device, C.byref(h)), "dsp_speaker_model_create")
-        self._h, self.device, self.d = h, device, pt.d
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_speaker_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_speaker_model_create", C.byref(pt), C.byref(pu), device)
+        self.device, self.d = device, pt.d
 
     def llr(self, mfcc, per_frame: bool = False):
         """mfcc: cuda float32 [n_clips][T][d] -> (llr_mean int64 [n], label int32 [n][, ll_target, ll_ubm int64 [n][T]])."""
@@ -393,7 +345,7 @@ class SpeakerModel:
         lu = torch.empty((n, t), dtype=torch.int64, device=mfcc.device) if per_frame else None
         _lib.check(self._L.dsp_speaker_llr_device(self._h, mfcc.contiguous().data_ptr(), n, t, mean.data_ptr(), label.data_ptr(),
                                                   lt.data_ptr() if per_frame else None, lu.data_ptr() if per_frame else None,
-                                                  _stream(mfcc)), "dsp_speaker_llr_device")
+                                                  _lib.current_stream(mfcc)), "dsp_speaker_llr_device")
         return (mean, label, lt, lu) if per_frame else (mean, label)
 
     def llr_ragged(self, mfcc, frame_offsets, per_frame: bool = False):
@@ -411,9 +363,9 @@ class SpeakerModel:
         label = torch.empty(n, dtype=torch.int32, device=mfcc.device)
         lt = torch.empty(rows, dtype=torch.int64, device=mfcc.device) if per_frame else None
         lu = torch.empty(rows, dtype=torch.int64, device=mfcc.device) if per_frame else None
-        _lib.check(self._L.dsp_speaker_llr_ragged_device(self._h, mfcc.data_ptr(), n, fo.ctypes.data_as(C.POINTER(C.c_long)), mean.data_ptr(),
+        _lib.check(self._L.dsp_speaker_llr_ragged_device(self._h, mfcc.data_ptr(), n, fo.ctypes.data_as(_lib.LP), mean.data_ptr(),
                                                          label.data_ptr(), lt.data_ptr() if per_frame else None,
-                                                         lu.data_ptr() if per_frame else None, _stream(mfcc)), "dsp_speaker_llr_ragged_device")
+                                                         lu.data_ptr() if per_frame else None, _lib.current_stream(mfcc)), "dsp_speaker_llr_ragged_device")
         return (mean, label, lt, lu) if per_frame else (mean, label)
 
     def scan(self, mfcc, frame_offsets, window_frames: int, hop_frames: int):
@@ -426,37 +378,25 @@ class SpeakerModel:
         nw = int(wo[-1])
         mean = torch.empty(nw, dtype=torch.int64, device=mfcc.device)
         label = torch.empty(nw, dtype=torch.int32, device=mfcc.device)
-        _lib.check(self._L.dsp_speaker_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
-                                                   C.byref(_scan_config(window_frames, hop_frames)), mean.data_ptr(), label.data_ptr(), _stream(mfcc)),
+        _lib.check(self._L.dsp_speaker_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_lib.LP),
+                                                   C.byref(_scan_config(window_frames, hop_frames)), mean.data_ptr(), label.data_ptr(), _lib.current_stream(mfcc)),
                    "dsp_speaker_scan_device")
         return wo, mean, label
 
 
-class Scanner:
+class Scanner(_lib.Handle):
     """dsp_scanner: recordings back to back in HBM -> ragged MFCC matrix -> P("stop") and / or the speaker LLR per window of
     window_frames rows every hop_frames rows.  One stream at a time per scanner."""
 
+    _destroy = "dsp_scanner_destroy"
+
     def __init__(self, plan: MfccPlan, stop: StopModel | None = None, speaker: SpeakerModel | None = None, window_frames: int = 98,
                  hop_frames: int = 10):
-        self._L = _lib.load()
         if stop is None and speaker is None:
             raise ValueError("a Scanner needs a stop model, a speaker model or both")
         self.cfg = _scan_config(window_frames, hop_frames)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_scanner_create(plan._h, stop._h if stop else None, speaker._h if speaker else None, C.byref(self.cfg), C.byref(h)),
-                   "dsp_scanner_create")
-        self._h, self.plan, self.stop, self.speaker = h, plan, stop, speaker      # (the scanner borrows them: keep them alive)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_scanner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_scanner_create", plan._h, stop._h if stop else None, speaker._h if speaker else None, C.byref(self.cfg))
+        self.plan, self.stop, self.speaker = plan, stop, speaker      # (the scanner borrows them: keep them alive)
 
     def run(self, signal, offsets, stereo_mode: int = 0):
         """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (stereo), recording r = samples [offsets[r], offsets[r + 1])
@@ -472,7 +412,7 @@ class Scanner:
         mean = torch.empty(nw, dtype=torch.int64, device=dev) if self.speaker else None
         label = torch.empty(nw, dtype=torch.int32, device=dev) if self.speaker else None
         ptrs = [t.data_ptr() if t is not None else None for t in (prob, mean, label)]
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        st = _lib.current_stream(signal)
         if channels:
             _lib.check(self._L.dsp_scanner_run_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), *ptrs, st), "dsp_scanner_run_pcm16_device")
         else:
@@ -480,17 +420,11 @@ class Scanner:
         return wo, prob, mean, label
 
 
-_long_array = _lib.long_array
-
-
 def _chunk_offsets(chunk_offsets, n_streams):
-    co = _long_array(chunk_offsets, n_streams + 1, "chunk_offsets")
+    co = _lib.long_array(chunk_offsets, n_streams + 1, "chunk_offsets")
     if co[0] < 0 or (np.diff(co) < 0).any():
         raise ValueError("chunk_offsets must be non-negative and non-decreasing")
     return co
-
-
-_LP = C.POINTER(C.c_long)
 
 
 def stream_push_plan(cfg, received, chunk_offsets, window_frames=None, hop_frames=None):
@@ -506,7 +440,7 @@ def stream_push_plan(cfg, received, chunk_offsets, window_frames=None, hop_frame
     co = _chunk_offsets(co, n)
     rec = None
     if received is not None:
-        rec = _long_array(received, n, "received")
+        rec = _lib.long_array(received, n, "received")
         if (rec < 0).any():
             raise ValueError("received must be non-negative")
     scan = None
@@ -517,12 +451,12 @@ def stream_push_plan(cfg, received, chunk_offsets, window_frames=None, hop_frame
     ro = np.zeros(n + 1, np.int64)
     wo = np.zeros(n + 1, np.int64) if scan is not None else None
     _lib.check(_lib.load().dsp_stream_push_plan(C.byref(cfg), C.byref(scan) if scan is not None else None,
-                                                rec.ctypes.data_as(_LP) if rec is not None else None, co.ctypes.data_as(_LP), n,
-                                                ro.ctypes.data_as(_LP), wo.ctypes.data_as(_LP) if wo is not None else None), "dsp_stream_push_plan")
+                                                rec.ctypes.data_as(_lib.LP) if rec is not None else None, co.ctypes.data_as(_lib.LP), n,
+                                                ro.ctypes.data_as(_lib.LP), wo.ctypes.data_as(_lib.LP) if wo is not None else None), "dsp_stream_push_plan")
     return ro, wo
 
 
-class StreamSession:
+class StreamSession(_lib.Handle):
     """dsp_stream_session: n_streams live streams on one GPU.  Every push hands over the next chunk of each stream (any length) and
     returns the MFCC rows and the window scores that became complete with it; concatenated over the pushes they are, bit for bit,
     MfccPlan.clips_ragged and Scanner.run on the whole recording -- except that a stream has no window before it holds window_frames
@@ -531,54 +465,36 @@ class StreamSession:
     StreamResampler (rate_in -> the plan's sample_rate, same dtype / channels / stereo_mode) in front of itself, push() takes chunks at
     rate_in, and counts() keeps counting samples at the plan's rate.  One stream at a time per session."""
 
+    _destroy = "dsp_stream_session_destroy"
+    resampler = None
+
     def __init__(self, plan: MfccPlan, n_streams: int, stop: StopModel | None = None, speaker: SpeakerModel | None = None,
                  window_frames: int = 98, hop_frames: int = 10, dtype=None, stereo_mode: int = 0, channels: int = 1, rate_in: int | None = None):
-        import torch
-        self._L = _lib.load()
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.int16):
-            raise ValueError("dtype must be torch.float32 or torch.int16")
-        if int(n_streams) < 0:
-            raise ValueError("n_streams must be >= 0")
-        if channels not in (1, 2) or (channels == 2 and dtype != torch.int16):
-            raise ValueError("channels must be 1, or 2 for int16 PCM")
-        if stereo_mode not in (0, 1):
-            raise ValueError("stereo_mode must be 0 (channel 0) or 1 (average)")
+        dtype, channels, stereo_mode, n_streams, pcm16 = _lib.stream_format(dtype, channels, stereo_mode, n_streams)
         self.cfg = _scan_config(window_frames, hop_frames) if (stop or speaker) else None
         if self.cfg is not None and self.cfg.hop_frames > self.cfg.window_frames:
             raise ValueError("hop_frames must not exceed window_frames")
-        self.resampler = None
         if rate_in is not None:      # the resampler decodes the caller's format; the session behind it takes its float mono output
             from .resample import StreamResampler
             self.resampler = StreamResampler(rate_in, plan.cfg.sample_rate, n_streams, dtype, stereo_mode, channels, plan.device)
-        own = (1, 0, 0) if self.resampler is not None else (int(channels), int(stereo_mode), int(dtype == torch.int16))
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_stream_session_create(plan._h, stop._h if stop else None, speaker._h if speaker else None,
-                                                     C.byref(self.cfg) if self.cfg is not None else None, int(n_streams), *own, C.byref(h)),
-                   "dsp_stream_session_create")
-        self._h, self.plan, self.stop, self.speaker = h, plan, stop, speaker      # (the session borrows them: keep them alive)
-        self.n_streams, self.dtype, self.channels, self.device = int(n_streams), dtype, int(channels), plan.device
+        own = (1, 0, 0) if self.resampler is not None else (channels, stereo_mode, pcm16)
+        self._create("dsp_stream_session_create", plan._h, stop._h if stop else None, speaker._h if speaker else None,
+                     C.byref(self.cfg) if self.cfg is not None else None, n_streams, *own)
+        self.plan, self.stop, self.speaker = plan, stop, speaker      # (the session borrows them: keep them alive)
+        self.n_streams, self.dtype, self.channels, self.device = n_streams, dtype, channels, plan.device
         if self.resampler is not None:
             _lib.check(self._L.dsp_stream_session_attach_resampler(self._h, self.resampler._h), "dsp_stream_session_attach_resampler")
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_stream_session_destroy(self._h)
-            self._h = None
-        if getattr(self, "resampler", None) is not None:
+        super().close()      # the session first: it holds the resampler's handle
+        if self.resampler is not None:
             self.resampler.close()
             self.resampler = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def counts(self):
         """-> (samples received, rows emitted, windows emitted), int64 [n_streams] each."""
         out = [np.zeros(self.n_streams, np.int64) for _ in range(3)]
-        _lib.check(self._L.dsp_stream_session_counts(self._h, *[a.ctypes.data_as(_LP) for a in out]), "dsp_stream_session_counts")
+        _lib.check(self._L.dsp_stream_session_counts(self._h, *[a.ctypes.data_as(_lib.LP) for a in out]), "dsp_stream_session_counts")
         return tuple(out)
 
     def reset(self, streams=None):
@@ -589,7 +505,7 @@ class StreamSession:
         idx = np.ascontiguousarray(np.asarray(streams, dtype=np.int64))
         if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.n_streams)):
             raise ValueError(f"streams must name streams 0 .. {self.n_streams - 1}")
-        _lib.check(self._L.dsp_stream_session_reset(self._h, idx.ctypes.data_as(_LP), idx.size, None), "dsp_stream_session_reset")
+        _lib.check(self._L.dsp_stream_session_reset(self._h, idx.ctypes.data_as(_lib.LP), idx.size, None), "dsp_stream_session_reset")
 
     def push(self, chunks, chunk_offsets, want_rows: bool = True):
         """chunks: a contiguous CUDA tensor of the session's dtype on the plan's device ([total], or [total][2] for stereo), stream s's
@@ -607,7 +523,7 @@ class StreamSession:
         co = _chunk_offsets(chunk_offsets, self.n_streams)
         if int(co[-1]) > chunks.shape[0]:
             raise ValueError("chunk_offsets run past the end of chunks")
-        rs = getattr(self, "resampler", None)
+        rs = self.resampler
         at_rate = rs.plan(co) if rs is not None else co      # the chunks as the MFCC front end will see them
         ro, wo = stream_push_plan(self.plan.cfg, self.counts()[0], at_rate, *((self.cfg.window_frames, self.cfg.hop_frames) if self.cfg is not None else ()))
         if wo is None:
@@ -619,16 +535,18 @@ class StreamSession:
         label = torch.empty(nw, dtype=torch.int32, device=dev) if self.speaker else None
         ptrs = [t.data_ptr() if t is not None else None for t in (rows, prob, mean, label)]
         ro2, wo2 = np.zeros_like(ro), np.zeros_like(wo)
-        _lib.check(self._L.dsp_stream_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_LP), *ptrs, ro2.ctypes.data_as(_LP),
-                                                  wo2.ctypes.data_as(_LP), _stream(chunks)), "dsp_stream_push_device")
+        _lib.check(self._L.dsp_stream_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_lib.LP), *ptrs, ro2.ctypes.data_as(_lib.LP),
+                                                  wo2.ctypes.data_as(_lib.LP), _lib.current_stream(chunks)), "dsp_stream_push_device")
         if not (np.array_equal(ro, ro2) and np.array_equal(wo, wo2)):
             raise _lib.DspError("dsp_stream_push_device emitted other rows / windows than dsp_stream_push_plan announced")
         return ro2, rows, wo2, prob, mean, label
 
 
-class Cmvn:
+class Cmvn(_lib.Handle):
     """dsp_cmvn: sliding cepstral mean and variance normalisation of a ragged MFCC matrix -- row t of a recording by the mean and the
     population standard deviation of rows [t - window // 2, t + window // 2) of its own recording (the UBM's feature space)."""
+
+    _destroy = "dsp_cmvn_destroy"
 
     def __init__(self, d: int, window: int = 300, device: int = 0):
         d, window = int(d), int(window)
@@ -636,21 +554,8 @@ class Cmvn:
             raise ValueError("d must be 1 .. 16")
         if window < 2:
             raise ValueError("window must be >= 2")
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_cmvn_create(int(device), d, window, C.byref(h)), "dsp_cmvn_create")
-        self._h, self.d, self.window, self.device = h, d, window, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_cmvn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_cmvn_create", int(device), d, window)
+        self.d, self.window, self.device = d, window, int(device)
 
     def apply(self, mfcc, frame_offsets):
         """mfcc: cuda float32 [F][d], recording r = rows [frame_offsets[r], frame_offsets[r + 1]) -> a new cuda float32 [F][d]; rows of
@@ -660,16 +565,17 @@ class Cmvn:
         mfcc = _scan_mfcc(mfcc, fo, self.d)
         out = torch.zeros_like(mfcc)
         if fo.size > 1 and mfcc.numel():
-            _lib.check(self._L.dsp_cmvn_ragged_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_LP), out.data_ptr(), _stream(mfcc)),
+            _lib.check(self._L.dsp_cmvn_ragged_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_lib.LP), out.data_ptr(), _lib.current_stream(mfcc)),
                        "dsp_cmvn_ragged_device")
         return out
 
 
-class SpeakerFrontEnd:
+class SpeakerFrontEnd(_lib.Closing):
     """extract_features_from_array (gmm_utils.py:47-61) for a whole batch: librosa.feature.mfcc(n_mfcc 13, n_fft 400, hop 160) as
     speaker_config() states it, then sliding_cmvn over a window of 300 rows -- the rows the float GMMs are trained and scored on."""
 
     CMVN_WINDOW = 300      # gmm_utils.py:14
+    plan = cmvn = None
 
     def __init__(self, device: int = 0):
         self.device = int(device)
@@ -678,21 +584,9 @@ class SpeakerFrontEnd:
 
     def close(self):
         for part in ("cmvn", "plan"):
-            if getattr(self, part, None):
+            if getattr(self, part):
                 getattr(self, part).close()
                 setattr(self, part, None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def features(self, signal, offsets):
         """signal: cuda float32 [total] at 16 kHz, clip c = samples [offsets[c], offsets[c + 1]) -> (feats, frame_offsets): cuda float32
@@ -721,30 +615,18 @@ def _gmm_float_params(params: dict, name: str):
     return _lib.GmmFloatParams(k, d, *(keep[key].ctypes.data for key in ("log_consts", "means", "inv_covs"))), k, d, keep
 
 
-class SpeakerEnroller:
+class SpeakerEnroller(_lib.Handle):
     """dsp_speaker_enroller: MAP adaptation of a float UBM's means to each speaker of a ragged matrix of (CMVN'd) feature rows."""
 
+    _destroy = "dsp_speaker_enroller_destroy"
     MODES = {"relevance": _lib.MAP_RELEVANCE, "fixed_alpha": _lib.MAP_FIXED_ALPHA}
 
     def __init__(self, ubm_float: dict, device: int = 0):
         """ubm_float: log_consts [k], means [k][d], inv_covs [k][d] -- the DOUBLE_GMM arrays of gmm_params.inc (log_consts = log w -
         0.5 sum log(2 pi var), inv_covs = 1 / var)."""
         p, k, d, _keep = _gmm_float_params(ubm_float, "ubm_float")
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_speaker_enroller_create(C.byref(p), int(device), C.byref(h)), "dsp_speaker_enroller_create")
-        self._h, self.k, self.d, self.device = h, k, d, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_speaker_enroller_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_speaker_enroller_create", C.byref(p), int(device))
+        self.k, self.d, self.device = k, d, int(device)
 
     def enroll(self, feats, frame_offsets, mode: str = "relevance", relevance_factor: float = 16.0, fixed_alpha: float = 0.7):
         """feats: cuda float32 [F][d], speaker s = rows [frame_offsets[s], frame_offsets[s + 1]), every speaker >= 1 row -> a dict of cuda
@@ -768,9 +650,9 @@ class SpeakerEnroller:
                "ll_mean": torch.empty(n, dtype=torch.float32, device=dev),
                "saturated": torch.empty(n, dtype=torch.int32, device=dev)}
         cfg = _lib.EnrollConfig(self.MODES[mode], relevance_factor, fixed_alpha)
-        _lib.check(self._L.dsp_speaker_enroll_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_LP), C.byref(cfg),
+        _lib.check(self._L.dsp_speaker_enroll_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_lib.LP), C.byref(cfg),
                                                             *[out[key].data_ptr() for key in ("means", "means_q6", "counts", "ll_mean", "saturated")],
-                                                            _stream(feats)), "dsp_speaker_enroll_ragged_device")
+                                                            _lib.current_stream(feats)), "dsp_speaker_enroll_ragged_device")
         return out
 
     @staticmethod
@@ -783,44 +665,36 @@ class SpeakerEnroller:
         return SpeakerModel({"means": q6, "inv_covs": ubm_int["inv_covs"], "log_consts": ubm_int["log_consts"]}, ubm_int, device)
 
 
-class SpeakerVerifier:
+class SpeakerVerifier(_lib.Handle):
     """dsp_speaker_verifier: every clip of a ragged matrix of (CMVN'd) feature rows against a float UBM and S enrolled speakers -- the
     mean log-sum-exp log-likelihood of each model and target.score - ubm.score per (clip, speaker)."""
 
+    _destroy = "dsp_speaker_verifier_destroy"
     OUTPUTS = ("llr", "ll_ubm", "ll_target", "best", "best_llr")
 
     def __init__(self, ubm_float: dict, device: int = 0):
         """ubm_float: log_consts [k], means [k][d], inv_covs [k][d], as SpeakerEnroller takes them.  No device is touched here."""
         p, k, d, _keep = _gmm_float_params(ubm_float, "ubm_float")
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_speaker_verifier_create(C.byref(p), int(device), C.byref(h)), "dsp_speaker_verifier_create")
-        self._h, self.k, self.d, self.device = h, k, d, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_speaker_verifier_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_speaker_verifier_create", C.byref(p), int(device))
+        self.k, self.d, self.device = k, d, int(device)
 
     def verify(self, feats, frame_offsets, means, want=("llr", "ll_ubm", "best", "best_llr")):
         """feats: cuda float32 [F][d], clip c = rows [frame_offsets[c], frame_offsets[c + 1]), every clip >= 1 row; means: cuda float32
         [S][k][d] (SpeakerEnroller.enroll(...)["means"] as it is) -> a dict of cuda tensors, those named in `want` of: llr float32 [C][S],
         ll_ubm float32 [C], ll_target float32 [C][S], best int32 [C] (the smallest s with the largest llr), best_llr float32 [C]."""
-        import torch
         feats, fo, means, want = self._inputs(feats, frame_offsets, means, want, "clip")
-        n, n_spk, dev = fo.size - 1, means.shape[0], feats.device
+        n, n_spk = fo.size - 1, means.shape[0]
+        out, ptrs = self._outputs(n, n_spk, want, feats.device)
+        _lib.check(self._L.dsp_speaker_verify_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_lib.LP), means.data_ptr(), n_spk, *ptrs,
+                                                            _lib.current_stream(feats)), "dsp_speaker_verify_ragged_device")
+        return out
+
+    def _outputs(self, n, n_spk, want, dev):
+        """-> (the tensors `want` names for n clips or windows and n_spk speakers, their addresses in OUTPUTS order, None where not wanted)"""
+        import torch
         shape = {"llr": (n, n_spk), "ll_ubm": (n,), "ll_target": (n, n_spk), "best": (n,), "best_llr": (n,)}
         out = {key: torch.empty(shape[key], dtype=torch.int32 if key == "best" else torch.float32, device=dev) for key in want}
-        _lib.check(self._L.dsp_speaker_verify_ragged_device(self._h, feats.data_ptr(), n, fo.ctypes.data_as(_LP), means.data_ptr(), n_spk,
-                                                            *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
-                   "dsp_speaker_verify_ragged_device")
-        return out
+        return out, [out[key].data_ptr() if key in out else None for key in self.OUTPUTS]
 
     def _inputs(self, feats, frame_offsets, means, want, what):
         """the argument checks verify and scan share -> (feats, fo, means, want)"""
@@ -845,15 +719,12 @@ class SpeakerVerifier:
         row; means as verify takes them -> a dict of cuda tensors with the Wt windows of all recordings leading, recording r's at
         scan_window_offsets(frame_offsets, window_frames, hop_frames)[r : r + 2]: llr float32 [Wt][S], ll_ubm float32 [Wt], ll_target
         float32 [Wt][S], best int32 [Wt], best_llr float32 [Wt].  Each equals verify on the window's rows as a clip, bit for bit."""
-        import torch
         cfg = _scan_config(window_frames, hop_frames)
         feats, fo, means, want = self._inputs(feats, frame_offsets, means, want, "recording")
-        nw, n_spk, dev = int(scan_window_offsets(fo, window_frames, hop_frames)[-1]), means.shape[0], feats.device
-        shape = {"llr": (nw, n_spk), "ll_ubm": (nw,), "ll_target": (nw, n_spk), "best": (nw,), "best_llr": (nw,)}
-        out = {key: torch.empty(shape[key], dtype=torch.int32 if key == "best" else torch.float32, device=dev) for key in want}
-        _lib.check(self._L.dsp_speaker_float_scan_device(self._h, feats.data_ptr(), fo.size - 1, fo.ctypes.data_as(_LP), C.byref(cfg), means.data_ptr(),
-                                                         n_spk, *[out[key].data_ptr() if key in out else None for key in self.OUTPUTS], _stream(feats)),
-                   "dsp_speaker_float_scan_device")
+        nw, n_spk = int(scan_window_offsets(fo, window_frames, hop_frames)[-1]), means.shape[0]
+        out, ptrs = self._outputs(nw, n_spk, want, feats.device)
+        _lib.check(self._L.dsp_speaker_float_scan_device(self._h, feats.data_ptr(), fo.size - 1, fo.ctypes.data_as(_lib.LP), C.byref(cfg), means.data_ptr(),
+                                                         n_spk, *ptrs, _lib.current_stream(feats)), "dsp_speaker_float_scan_device")
         return out
 
 
@@ -868,21 +739,12 @@ def _segment_config(on, off, min_windows, max_gap, exclusive):
     return _lib.SegmentConfig(on, off, min_windows, max_gap, _lib.SEG_EXCLUSIVE if exclusive else _lib.SEG_INDEPENDENT)
 
 
-def _window_offsets(window_offsets):
-    wo = np.ascontiguousarray(np.asarray(window_offsets, dtype=np.int64))
-    if wo.ndim != 1 or wo.size < 1:
-        raise ValueError("window_offsets must hold n_recordings + 1 windows")
-    if wo[0] < 0 or (wo.size > 1 and (np.diff(wo) < 0).any()):
-        raise ValueError("window_offsets must be non-negative and non-decreasing")
-    return wo
-
-
 def segments_capacity(window_offsets, n_columns: int = 1, min_windows: int = 1, max_gap: int = 0) -> int:
     """Host only: the most segments Segmenter.segments can find (dsp_segments_capacity): n_columns times the sum over recordings of
     (W_r + max_gap + 1) // (min_windows + max_gap + 1)."""
     cfg = _segment_config(0.0, 0.0, min_windows, max_gap, False)
-    wo = _window_offsets(window_offsets)
-    return _lib.check(_lib.load().dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_LP), wo.size - 1, int(n_columns)), "dsp_segments_capacity")
+    wo = _lib.offsets_array(window_offsets, "window_offsets", "windows")
+    return _lib.check(_lib.load().dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_lib.LP), wo.size - 1, int(n_columns)), "dsp_segments_capacity")
 
 
 def segment_sample_spans(cfg, offsets, segments, window_frames: int, hop_frames: int):
@@ -893,33 +755,21 @@ def segment_sample_spans(cfg, offsets, segments, window_frames: int, hop_frames:
     off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
     segs = np.ascontiguousarray(segments, dtype=np.dtype(_lib.SEGMENT_DTYPE))
     starts, lengths = np.zeros(segs.size, np.int64), np.zeros(segs.size, np.int64)
-    _lib.check(_lib.load().dsp_segment_sample_spans(C.byref(cfg), C.byref(scan), off, n, segs.ctypes.data, segs.size, starts.ctypes.data_as(_LP),
-                                                    lengths.ctypes.data_as(_LP)), "dsp_segment_sample_spans")
+    _lib.check(_lib.load().dsp_segment_sample_spans(C.byref(cfg), C.byref(scan), off, n, segs.ctypes.data, segs.size, starts.ctypes.data_as(_lib.LP),
+                                                    lengths.ctypes.data_as(_lib.LP)), "dsp_segment_sample_spans")
     return starts, lengths
 
 
-class Segmenter:
+class Segmenter(_lib.Handle):
     """dsp_segmenter: segments from the window scores of any scan -- hysteresis between two thresholds, runs joined over short gaps,
     short segments dropped -- found on the GPU in (recording, column, first_window) order.  One stream at a time per segmenter."""
 
+    _destroy = "dsp_segmenter_destroy"
     CAP = 1 << 20          # segments the first call makes room for at most; a second call follows when more are found
 
     def __init__(self, device: int = 0):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_segmenter_create(int(device), C.byref(h)), "dsp_segmenter_create")
-        self._h, self.device = h, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_segmenter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_segmenter_create", int(device))
+        self.device = int(device)
 
     def segments(self, scores, window_offsets, on, off=None, min_windows: int = 1, max_gap: int = 0, exclusive: bool = False, as_tensor: bool = False):
         """scores: cuda float32 [Wt] or [Wt][S] (a scan's prob, prob1, decision or llr as it is), recording r = windows [window_offsets[r],
@@ -929,7 +779,7 @@ class Segmenter:
         with as_tensor the same 32 bytes per segment as a cuda int32 [n][8] (peak and mean: .view(torch.float32) of columns 6 and 7)."""
         import torch
         cfg = _segment_config(on, off, min_windows, max_gap, exclusive)
-        wo = _window_offsets(window_offsets)
+        wo = _lib.offsets_array(window_offsets, "window_offsets", "windows")
         scores, n_col = _lib.scores_device(scores, self.device)
         if int(wo[-1]) > scores.shape[0]:
             raise ValueError("window_offsets run past the end of scores")
@@ -938,11 +788,11 @@ class Segmenter:
             out = torch.zeros((0, 8), dtype=torch.int32, device=dev)
             return out if as_tensor else np.zeros(0, np.dtype(_lib.SEGMENT_DTYPE))
         total = torch.zeros(2, dtype=torch.int64, device=dev)
-        room = min(_lib.check(self._L.dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_LP), n, n_col), "dsp_segments_capacity"), self.CAP)
+        room = min(_lib.check(self._L.dsp_segments_capacity(C.byref(cfg), wo.ctypes.data_as(_lib.LP), n, n_col), "dsp_segments_capacity"), self.CAP)
         for _ in range(2):
             out = torch.empty((room, 8), dtype=torch.int32, device=dev)
-            _lib.check(self._L.dsp_segments_device(self._h, scores.data_ptr(), n, wo.ctypes.data_as(_LP), n_col, C.byref(cfg), out.data_ptr(), room, None,
-                                                   total.data_ptr(), _stream(scores)), "dsp_segments_device")
+            _lib.check(self._L.dsp_segments_device(self._h, scores.data_ptr(), n, wo.ctypes.data_as(_lib.LP), n_col, C.byref(cfg), out.data_ptr(), room, None,
+                                                   total.data_ptr(), _lib.current_stream(scores)), "dsp_segments_device")
             found = int(total[0])
             if found <= room:
                 break
@@ -951,29 +801,17 @@ class Segmenter:
         return out if as_tensor else out.cpu().numpy().view(np.dtype(_lib.SEGMENT_DTYPE)).reshape(-1)
 
 
-class TrialEvaluator:
+class TrialEvaluator(_lib.Handle):
     """dsp_trial_evaluator: labelled trials on the GPU -- per column of a score matrix and pooled, the reference's threshold sweep
     (evaluate_gmm.py:77-81), the exact ROC step curve as counts and the AUC (generate_charts.py:68-69).  One stream at a time per
     evaluator."""
 
+    _destroy = "dsp_trial_evaluator_destroy"
     WANT = ("columns", "sweep", "roc")
 
     def __init__(self, device: int = 0):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_trial_evaluator_create(int(device), C.byref(h)), "dsp_trial_evaluator_create")
-        self._h, self.device = h, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_trial_evaluator_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_trial_evaluator_create", int(device))
+        self.device = int(device)
 
     def evaluate(self, scores, truth, n_thresholds: int = 200, want=("columns", "sweep", "roc")):
         """scores: cuda float32 [T] or [T][S] (SpeakerVerifier.verify(...)["llr"] or .scan(...)["llr"] as it is); truth: T integers on
@@ -1010,14 +848,14 @@ class TrialEvaluator:
             ptr["tp"], ptr["fp"] = tps.data_ptr(), fps.data_ptr()
         if "roc" in want:
             offsets = np.zeros(n_col + 1, np.int64)
-            n_tgt = _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, offsets.ctypes.data_as(_LP), None), "dsp_trials_target_offsets")
+            n_tgt = _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, offsets.ctypes.data_as(_lib.LP), None), "dsp_trials_target_offsets")
             rows = np.zeros(n_tgt, np.int64)
-            _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, None, rows.ctypes.data_as(_LP)), "dsp_trials_target_offsets")
+            _lib.check(self._L.dsp_trials_target_offsets(tp, n_rows, n_col, None, rows.ctypes.data_as(_lib.LP)), "dsp_trials_target_offsets")
             above, equal = (torch.empty(max(n_tgt, 1), dtype=torch.int32, device=dev) for _ in range(2))   # (an empty tensor has no address)
             ptr["above"], ptr["equal"] = above.data_ptr(), equal.data_ptr()
         cfg = _lib.TrialsConfig(n)
         _lib.check(self._L.dsp_trials_evaluate_device(self._h, scores.data_ptr(), n_rows, n_col, tp, C.byref(cfg),
-                                                      *[ptr.get(key) for key in ("columns", "tp", "fp", "above", "equal")], _stream(scores)),
+                                                      *[ptr.get(key) for key in ("columns", "tp", "fp", "above", "equal")], _lib.current_stream(scores)),
                    "dsp_trials_evaluate_device")
         if "columns" in want:
             out["columns"] = cols.cpu().numpy().view(np.dtype(_lib.TRIAL_COLUMN_DTYPE)).reshape(-1)
@@ -1075,33 +913,22 @@ def roc_points(result: dict, column: int):
         return np.array(fps, np.float64) / np.float64(n_non), np.array(tps, np.float64) / np.float64(n_tgt), np.array(thr, np.float64)
 
 
-class ScoreCalibrator:
+class ScoreCalibrator(_lib.Handle):
     """dsp_calibrator: c = A x + B + C log(n_frames) on a score matrix on the GPU -- fit by prior-weighted logistic regression (damped
     Newton, every pass and solve on the device) on labelled trials, and apply.  One stream at a time per calibrator."""
 
+    _destroy = "dsp_calibrator_destroy"
+
     def __init__(self, device: int = 0):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_calibrator_create(int(device), C.byref(h)), "dsp_calibrator_create")
-        self._h, self.device = h, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_calibrator_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_calibrator_create", int(device))
+        self.device = int(device)
 
     @staticmethod
     def duration_term(n_frames) -> np.ndarray:
         """Host only: log(n_frames + 1e-8) as float64, exactly the values fit and apply use (dsp_calibration_duration_term)."""
         nf = _frames(n_frames, None)
         out = np.empty(nf.size, np.float64)
-        _lib.check(_lib.load().dsp_calibration_duration_term(nf.ctypes.data_as(_LP), nf.size, out.ctypes.data_as(C.POINTER(C.c_double))),
+        _lib.check(_lib.load().dsp_calibration_duration_term(nf.ctypes.data_as(_lib.LP), nf.size, out.ctypes.data_as(C.POINTER(C.c_double))),
                    "dsp_calibration_duration_term")
         return out
 
@@ -1129,8 +956,8 @@ class ScoreCalibrator:
         start = _calibration(init, nf is not None)
         cfg, rep = _lib.CalibrationConfig(float(prior), float(tol), int(max_iter), 0), _lib.CalibrationReport()
         _lib.check(self._L.dsp_calibration_fit_device(self._h, scores.data_ptr(), n_rows, n_col, tr.ctypes.data_as(C.POINTER(C.c_int)),
-                                                      nf.ctypes.data_as(_LP) if nf is not None else None, C.byref(cfg), C.byref(start), C.byref(rep),
-                                                      _stream(scores)), "dsp_calibration_fit_device")
+                                                      nf.ctypes.data_as(_lib.LP) if nf is not None else None, C.byref(cfg), C.byref(start), C.byref(rep),
+                                                      _lib.current_stream(scores)), "dsp_calibration_fit_device")
         out = {name: getattr(rep, name) for name, _ in _lib.CalibrationReport._fields_ if name not in ("params", "reserved")}
         out.update(a=rep.params.a, b=rep.params.b, c=rep.params.c, params=(rep.params.a, rep.params.b, rep.params.c),
                    status_name=_lib.CAL_STATUS[rep.status])
@@ -1152,8 +979,8 @@ class ScoreCalibrator:
         if out is scores and x is not scores:
             raise ValueError("scores must be contiguous to be calibrated in place")
         if n_rows:
-            _lib.check(self._L.dsp_calibration_apply_device(self._h, x.data_ptr(), n_rows, n_col, nf.ctypes.data_as(_LP) if nf is not None else None,
-                                                            C.byref(p), out.data_ptr(), _stream(x)), "dsp_calibration_apply_device")
+            _lib.check(self._L.dsp_calibration_apply_device(self._h, x.data_ptr(), n_rows, n_col, nf.ctypes.data_as(_lib.LP) if nf is not None else None,
+                                                            C.byref(p), out.data_ptr(), _lib.current_stream(x)), "dsp_calibration_apply_device")
         return out
 
 
@@ -1184,29 +1011,18 @@ def _calibration(params, with_frames: bool):
     return _lib.Calibration(a, b, c)
 
 
-class UbmTrainer:
+class UbmTrainer(_lib.Handle):
     """dsp_ubm_trainer: EM for a diagonal GMM of k components on a matrix of (CMVN'd) feature rows [n][d] -- sklearn's M-step and stopping
     rule; the float UBM SpeakerEnroller takes, and through quantize_gmm the integer tables SpeakerModel takes."""
+
+    _destroy = "dsp_ubm_trainer_destroy"
 
     def __init__(self, k: int, d: int, device: int = 0):
         k, d = int(k), int(d)
         if not (1 <= k <= 64 and 1 <= d <= 16):
             raise ValueError("k must be 1 .. 64 and d 1 .. 16")
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_ubm_trainer_create(int(device), k, d, C.byref(h)), "dsp_ubm_trainer_create")
-        self._h, self.k, self.d, self.device = h, k, d, int(device)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_ubm_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_ubm_trainer_create", int(device), k, d)
+        self.k, self.d, self.device = k, d, int(device)
 
     def _rows(self, feats):
         import torch
@@ -1230,7 +1046,7 @@ class UbmTrainer:
         feats = self._rows(feats)
         out = {"weights": np.empty(self.k), "means": np.empty((self.k, self.d)), "variances": np.empty((self.k, self.d))}
         _lib.check(self._L.dsp_ubm_init_rows_device(self._h, feats.data_ptr(), feats.shape[0], reg_covar,
-                                                    *[out[key].ctypes.data for key in ("weights", "means", "variances")], _stream(feats)),
+                                                    *[out[key].ctypes.data for key in ("weights", "means", "variances")], _lib.current_stream(feats)),
                    "dsp_ubm_init_rows_device")
         return out
 
@@ -1240,7 +1056,7 @@ class UbmTrainer:
         seed = self._seed(seed)
         feats = self._rows(feats)
         rows = np.empty(self.k, np.int64)
-        _lib.check(self._L.dsp_kmeans_seed_device(self._h, feats.data_ptr(), feats.shape[0], seed, rows.ctypes.data, _stream(feats)), "dsp_kmeans_seed_device")
+        _lib.check(self._L.dsp_kmeans_seed_device(self._h, feats.data_ptr(), feats.shape[0], seed, rows.ctypes.data, _lib.current_stream(feats)), "dsp_kmeans_seed_device")
         return rows
 
     @staticmethod
@@ -1278,7 +1094,7 @@ class UbmTrainer:
         res = _lib.KmeansResult(*[out[key].ctypes.data for key in ("centres", "counts", "weights", "means", "variances")],
                                 labels.data_ptr() if want_labels else None)
         cfg = _lib.KmeansConfig(max_iter, tol, reg_covar)
-        _lib.check(self._L.dsp_kmeans_fit_device(self._h, feats.data_ptr(), feats.shape[0], start.ctypes.data, C.byref(cfg), C.byref(res), _stream(feats)),
+        _lib.check(self._L.dsp_kmeans_fit_device(self._h, feats.data_ptr(), feats.shape[0], start.ctypes.data, C.byref(cfg), C.byref(res), _lib.current_stream(feats)),
                    "dsp_kmeans_fit_device")
         out.update(inertia=float(res.inertia), n_iter=int(res.n_iter), stop=_lib.KMEANS_STOP[res.stop], n_empty=int(res.n_empty))
         if want_labels:
@@ -1322,7 +1138,7 @@ class UbmTrainer:
         out, res = self._result_arrays(max_iter)
         cfg = _lib.UbmConfig(max_iter, tol, reg_covar)
         _lib.check(self._L.dsp_ubm_train_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(start) if start is not None else None,
-                                                C.byref(cfg), C.byref(res), _stream(feats)), "dsp_ubm_train_device")
+                                                C.byref(cfg), C.byref(res), _lib.current_stream(feats)), "dsp_ubm_train_device")
         out["lower_bounds"] = out["lower_bounds"][:res.n_iter].copy()
         out["n_iter"], out["converged"] = int(res.n_iter), bool(res.converged)
         return out
@@ -1346,7 +1162,7 @@ class UbmTrainer:
         restarts = (_lib.KmeansRestart * n_init)()
         report = _lib.KmeansUbmReport(restarts, -1)
         cfg = _lib.KmeansUbmConfig(n_init, seed, kmeans_max_iter, kmeans_tol, _lib.UbmConfig(max_iter, tol, reg_covar))
-        _lib.check(self._L.dsp_kmeans_train_ubm_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(cfg), C.byref(res), C.byref(report), _stream(feats)),
+        _lib.check(self._L.dsp_kmeans_train_ubm_device(self._h, feats.data_ptr(), feats.shape[0], C.byref(cfg), C.byref(res), C.byref(report), _lib.current_stream(feats)),
                    "dsp_kmeans_train_ubm_device")
         out["lower_bounds"] = out["lower_bounds"][:res.n_iter].copy()
         out["n_iter"], out["converged"] = int(res.n_iter), bool(res.converged)
@@ -1384,7 +1200,7 @@ def upsample_linear(x, new_size: int):
         raise ValueError("x must have unit inner stride")
     out = torch.empty((x2.shape[0], new_size), dtype=torch.float32, device=x.device)
     _lib.check(L.dsp_upsample_linear_device(x2.data_ptr(), x2.shape[0], x2.shape[1], x2.stride(0), out.data_ptr(), new_size,
-                                            new_size, _stream(x)), "dsp_upsample_linear_device")
+                                            new_size, _lib.current_stream(x)), "dsp_upsample_linear_device")
     return out[0] if squeeze else out
 
 

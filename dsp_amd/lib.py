@@ -283,56 +283,218 @@ FRAMING_COMPLETE, FRAMING_STREAM, FRAMING_CENTER = 0, 1, 2
 MAP_RELEVANCE, MAP_FIXED_ALPHA = 0, 1
 PREFILTER_NONE, PREFILTER_BUTTER_1000_3000, PREFILTER_BUTTER_3000_7500 = 0, 1, 2
 
-# every symbol include/dsp_amd.h declares (tests check the library exports them all)
-SYMBOLS = [
-    "compute_mfcc", "fft_real_forward", "dsp_fft_real_forward_host", "dsp_classify",
-    "dsp_classify_default_config_f64", "dsp_classify_batch_host_f64", "dsp_classify_batch_device_f64",
-    "dsp_classify_batch_pcm16_host_f64", "dsp_classify_batch_pcm16_device_f64", "dsp_classify_release_f64", "dsp_classify_stats_f64", "dsp_classify_debug_f64",
-    "dsp_classify_default_config", "dsp_classify_batch_host_cfg", "dsp_classify_batch_device_cfg", "dsp_sum_intense_f32",
-    "dsp_butter_bandpass_filter_f32", "dsp_butter_bandpass_filter_f64", "dsp_compute_spectrogram_f32", "dsp_compute_spectrogram_f64",
-    "dsp_classify_batch_host", "dsp_classify_batch_device", "dsp_classify_batch_pcm16_host", "dsp_classify_batch_pcm16_device", "dsp_classify_release", "dsp_classify_stats", "dsp_classify_ctx_create", "dsp_classify_ctx_destroy", "dsp_classify_batch_device_ctx", "dsp_debug_hold_classify_ctx", "dsp_find_midpoints", "dsp_classify_division_check",
-    "dsp_mfcc_stats_device", "dsp_svm_create", "dsp_svm_destroy", "dsp_svm_predict_device",
-    "dsp_mfcc_default_config", "dsp_mfcc_scrubjay_infer_config", "dsp_mfcc_speaker_config", "dsp_mfcc400_tables", "dsp_mfcc_plan_create", "dsp_mfcc_plan_destroy", "dsp_mfcc_plan_config",
-    "dsp_mfcc_frames_for", "dsp_mfcc_frames_device", "dsp_mfcc_clips_device", "dsp_mfcc_frames_host",
-    "dsp_mfcc_clips_host", "dsp_mfcc_clips_pcm16_device", "dsp_mfcc_plan_set_launch", "dsp_mfcc_plan_set_kernel", "dsp_butter_bandpass", "dsp_mfcc_tables", "dsp_mfcc_lane_tables", "dsp_prefilter_scan_check",
-    "dsp_classify_batch_ragged_device_f64", "dsp_classify_batch_ragged_pcm16_device_f64", "dsp_classify_batch_ragged_host_f64", "dsp_classify_batch_ragged_pcm16_host_f64",
-    "dsp_classify_batch_ragged_device", "dsp_classify_batch_ragged_pcm16_device", "dsp_classify_batch_ragged_host", "dsp_classify_batch_ragged_pcm16_host",
-    "dsp_debug_fused_spans", "dsp_scrubjay_fused_ragged_device", "dsp_scrubjay_fused_ragged_pcm16_device", "dsp_classify_signal_batch_ragged_device", "dsp_classify_signal_batch_ragged_pcm16_device",
-    "dsp_scrubjay_fused_device", "dsp_scrubjay_fused_pcm16_device", "dsp_classify_signal_batch_pcm16_device", "dsp_stop_model_create", "dsp_stop_model_destroy", "dsp_stop_predict_device", "dsp_classify_signal_batch_device",
-    "dsp_classify_signal", "dsp_speaker_model_create", "dsp_speaker_model_destroy", "dsp_speaker_llr_device",
-    "dsp_mfcc_ragged_frame_offsets", "dsp_mfcc_clips_ragged_device", "dsp_mfcc_clips_ragged_pcm16_device", "dsp_speaker_llr_ragged_device",
-    "dsp_scan_window_offsets", "dsp_stop_scan_device", "dsp_speaker_scan_device",
-    "dsp_scanner_create", "dsp_scanner_destroy", "dsp_scanner_run_device", "dsp_scanner_run_pcm16_device",
-    "dsp_scan_window_spans", "dsp_svm_scan_device", "dsp_scrubjay_scanner_create", "dsp_scrubjay_scanner_destroy",
-    "dsp_scrubjay_scanner_run_device", "dsp_scrubjay_scanner_run_pcm16_device",
-    "dsp_stream_push_plan", "dsp_stream_session_create", "dsp_stream_session_destroy", "dsp_stream_session_reset",
-    "dsp_stream_session_counts", "dsp_stream_push_device",
-    "dsp_stream_resample_plan", "dsp_stream_resampler_create", "dsp_stream_resampler_destroy", "dsp_stream_resampler_reset",
-    "dsp_stream_resampler_counts", "dsp_stream_resample_push_device", "dsp_stream_resample_finish_device", "dsp_stream_session_attach_resampler",
-    "dsp_upsample_linear_device", "dsp_upsample_linear_host",
-    "dsp_resample_ratio", "dsp_resample_geometry", "dsp_resample_taps", "dsp_resample_offsets", "dsp_resampler_create", "dsp_resampler_destroy",
-    "dsp_resample_ragged_device", "dsp_resample_ragged_pcm16_device", "dsp_resample_clips_device", "dsp_resample_clips_pcm16_device",
-    "dsp_resample_host",
-    "dsp_cmvn_create", "dsp_cmvn_destroy", "dsp_cmvn_ragged_device",
-    "dsp_speaker_enroller_create", "dsp_speaker_enroller_destroy", "dsp_speaker_enroll_ragged_device",
-    "dsp_ubm_trainer_create", "dsp_ubm_trainer_destroy", "dsp_ubm_init_rows_device", "dsp_ubm_train_device", "dsp_gmm_quantize",
-    "dsp_kmeans_seed_device", "dsp_kmeans_fit_device", "dsp_kmeans_train_ubm_device",
-    "dsp_speaker_verifier_create", "dsp_speaker_verifier_destroy", "dsp_speaker_verify_ragged_device",
-    "dsp_speaker_float_scan_device",
-    "dsp_segmenter_create", "dsp_segmenter_destroy", "dsp_segments_capacity", "dsp_segments_device", "dsp_segment_sample_spans",
-    "dsp_trials_target_offsets", "dsp_trials_pairs", "dsp_trial_evaluator_create", "dsp_trial_evaluator_destroy", "dsp_trials_evaluate_device",
-    "dsp_calibrator_create", "dsp_calibrator_destroy", "dsp_calibration_duration_term", "dsp_calibration_fit_device", "dsp_calibration_apply_device",
-    "dsp_svm_trainer_create", "dsp_svm_trainer_destroy", "dsp_svm_train_set_device", "dsp_svm_train_rows_host", "dsp_svm_train_problems_device",
-    "dsp_svm_platt_fit_device", "dsp_svm_folds", "dsp_svm_balanced_weights", "dsp_svm_model_from_training", "dsp_svm_fit_device",
-    "dsp_stop_trainer_create", "dsp_stop_trainer_destroy", "dsp_stop_train_set_device", "dsp_stop_train_used_features", "dsp_stop_train_rows_host",
-    "dsp_stop_train_runs_device", "dsp_stop_train_param_count", "dsp_stop_train_uniform", "dsp_stop_train_order", "dsp_stop_train_init",
-    "dsp_stop_model_from_training",
-    "dsp_stft_frames", "dsp_stretch_frames", "dsp_stretch_length", "dsp_pitch_ratio", "dsp_augment_normal", "dsp_augment_out_offsets", "dsp_augment_draw",
-    "dsp_augmenter_create", "dsp_augmenter_destroy", "dsp_stft_ragged_device", "dsp_istft_ragged_device", "dsp_time_stretch_ragged_device",
-    "dsp_augment_ragged_device",
-    "dsp_gather_create", "dsp_gather_destroy", "dsp_gather_n_devices", "dsp_gather_all",
-    "dsp_last_error", "dsp_device_count", "dsp_version", "dsp_abi_sizeof",
-]
+LP = C.POINTER(C.c_long)
+
+# Every function include/dsp_amd.h declares, in the header's order: name -> (restype, [argtypes]).  A new entry point is declared
+# here, once; load() applies the table, SYMBOLS is its keys, and tests/test_bindings_cpu.py holds every entry to the header.
+# The aliases: scalars (ip is int, lg long, fl float, db double), then pointers to them (ipp, lp, fp, dp) and to the structs above.
+P = C.POINTER
+vp, ip, lg, fl, db, u64, sz, cp = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_uint64, C.c_size_t, C.c_char_p
+vpp, ipp, lp, llp, fp, dp = P(vp), P(ip), LP, P(C.c_longlong), P(fl), P(db)
+cfgp, scp, sgp, opp, smp, gp, gfp, urp, stcp = (P(MfccConfig), P(ScanConfig), P(SegmentConfig), P(AugmentOp), P(StopModelParams), P(GmmParams),
+                                                P(GmmFloatParams), P(UbmResult), P(SvmTrainConfig))
+ccfgp, ccfg64p = P(ClassifyConfig), P(ClassifyConfigF64)
+PROTOTYPES = {
+    "compute_mfcc": (ip, [vp, ip, vp, ip]),
+    "dsp_classify": (ip, [vp, ip]),
+    "dsp_mfcc_default_config": (None, [cfgp]),
+    "dsp_mfcc_scrubjay_infer_config": (None, [cfgp, ip]),
+    "dsp_mfcc_speaker_config": (None, [cfgp]),
+    "dsp_mfcc_plan_create": (ip, [cfgp, ip, vpp]),
+    "dsp_mfcc_plan_destroy": (None, [vp]),
+    "dsp_mfcc_plan_config": (ip, [vp, cfgp]),
+    "dsp_mfcc_frames_for": (ip, [cfgp, ip, ip]),
+    "dsp_mfcc_frames_device": (ip, [vp, vp, lg, vp, vp]),
+    "dsp_mfcc_clips_device": (ip, [vp, vp, lg, ip, lg, vp, ip, vp]),
+    "fft_real_forward": (None, [vp, vp]),
+    "dsp_fft_real_forward_host": (ip, [vp, lg, ip, lg, ip, vp]),
+    "dsp_mfcc_clips_pcm16_device": (ip, [vp, vp, lg, ip, lg, ip, ip, vp, ip, vp]),
+    "dsp_mfcc_ragged_frame_offsets": (lg, [cfgp, lp, lg, ip, lp]),
+    "dsp_mfcc_clips_ragged_device": (ip, [vp, vp, lg, lp, ip, vp, vp]),
+    "dsp_mfcc_clips_ragged_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, ip, vp, vp]),
+    "dsp_mfcc_frames_host": (ip, [vp, vp, lg, vp]),
+    "dsp_mfcc_clips_host": (ip, [vp, vp, lg, ip, lg, vp, ip]),
+    "dsp_mfcc_plan_set_launch": (ip, [vp, ip, ip]),
+    "dsp_mfcc_plan_set_kernel": (ip, [vp, ip]),
+    "dsp_butter_bandpass": (ip, [db, db, dp, dp]),
+    "dsp_butter_bandpass_filter_f32": (ip, [vp, lg, ip, lg, vp, vp, vp]),
+    "dsp_butter_bandpass_filter_f64": (ip, [vp, lg, ip, lg, vp, vp, vp]),
+    "dsp_compute_spectrogram_f32": (ip, [vp, ip, ip, vp, vp, vp]),
+    "dsp_compute_spectrogram_f64": (ip, [vp, ip, ip, vp, vp, vp]),
+    "dsp_classify_batch_host": (ip, [vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_batch_device": (ip, [vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_default_config": (None, [ccfgp]),
+    "dsp_classify_batch_host_cfg": (ip, [ccfgp, vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_batch_device_cfg": (ip, [ccfgp, vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_batch_pcm16_host": (ip, [ccfgp, vp, lg, ip, lg, ip, ip, vp, vp]),
+    "dsp_classify_batch_pcm16_device": (ip, [ccfgp, vp, lg, ip, lg, ip, ip, vp, vp]),
+    "dsp_classify_batch_ragged_device": (ip, [vp, vp, lg, lp, vp, vp]),
+    "dsp_classify_batch_ragged_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, vp, vp]),
+    "dsp_classify_batch_ragged_host": (ip, [vp, vp, lg, lp, vp, vp]),
+    "dsp_classify_batch_ragged_pcm16_host": (ip, [vp, vp, lg, lp, ip, ip, vp, vp]),
+    "dsp_classify_stats": (ip, [ip, lp, lp]),
+    "dsp_classify_ctx_create": (ip, [ip, vpp]),
+    "dsp_classify_ctx_destroy": (None, [vp]),
+    "dsp_classify_batch_device_ctx": (ip, [vp, ccfgp, vp, lg, ip, lg, vp, vp]),
+    "dsp_debug_hold_classify_ctx": (ip, [ip, ip]),
+    "dsp_classify_release": (ip, [ip]),
+    "dsp_classify_default_config_f64": (None, [ccfg64p]),
+    "dsp_classify_batch_host_f64": (ip, [ccfg64p, vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_batch_device_f64": (ip, [ccfg64p, vp, lg, ip, lg, vp, vp, vp]),
+    "dsp_classify_batch_pcm16_host_f64": (ip, [ccfg64p, vp, lg, ip, lg, ip, ip, vp, vp]),
+    "dsp_classify_batch_pcm16_device_f64": (ip, [ccfg64p, vp, lg, ip, lg, ip, ip, vp, vp, vp]),
+    "dsp_classify_batch_ragged_device_f64": (ip, [vp, vp, lg, lp, vp, vp, vp]),
+    "dsp_classify_batch_ragged_pcm16_device_f64": (ip, [vp, vp, lg, lp, ip, ip, vp, vp, vp]),
+    "dsp_classify_batch_ragged_host_f64": (ip, [vp, vp, lg, lp, vp, vp]),
+    "dsp_classify_batch_ragged_pcm16_host_f64": (ip, [vp, vp, lg, lp, ip, ip, vp, vp]),
+    "dsp_classify_stats_f64": (ip, [ip, lp, lp, lp]),
+    "dsp_classify_debug_f64": (ip, [ip, ipp, ip]),
+    "dsp_classify_release_f64": (ip, [ip]),
+    "dsp_sum_intense_f32": (ip, [fl, fl, fl, vp, ip, vp, ip, vp, fl, fp]),
+    "dsp_find_midpoints": (ip, [vp, ip, ip, vp, ip]),
+    "dsp_gather_create": (ip, [vp, ip, vpp]),
+    "dsp_gather_destroy": (None, [vp]),
+    "dsp_gather_n_devices": (ip, [vp]),
+    "dsp_gather_all": (ip, [vp, vp, vp, sz, vp]),
+    "dsp_mfcc_stats_device": (ip, [vp, lg, ip, ip, vp, vp]),
+    "dsp_svm_create": (ip, [ip, ip, ip, vp, vp, vp, vp, fl, fl, fl, fl, vpp]),
+    "dsp_svm_destroy": (None, [vp]),
+    "dsp_svm_predict_device": (ip, [vp, vp, lg, vp, vp, vp, vp]),
+    "dsp_scrubjay_fused_device": (ip, [vp, vp, vp, lg, ip, lg, ip, vp, vp, vp, vp, vp]),
+    "dsp_scrubjay_fused_pcm16_device": (ip, [vp, vp, vp, lg, ip, lg, ip, ip, ip, vp, vp, vp, vp, vp]),
+    "dsp_scrubjay_fused_ragged_device": (ip, [vp, vp, vp, lg, lp, ip, vp, vp, vp, vp, vp]),
+    "dsp_scrubjay_fused_ragged_pcm16_device": (ip, [vp, vp, vp, lg, lp, ip, ip, ip, vp, vp, vp, vp, vp]),
+    "dsp_debug_fused_spans": (ip, [cfgp, lp, lg, ip, lg, lp]),
+    "dsp_stop_model_create": (ip, [smp, ip, vpp]),
+    "dsp_stop_model_destroy": (None, [vp]),
+    "dsp_stop_predict_device": (ip, [vp, vp, lg, ip, vp, vp]),
+    "dsp_classify_signal_batch_device": (ip, [vp, vp, vp, lg, ip, lg, vp, vp]),
+    "dsp_classify_signal_batch_pcm16_device": (ip, [vp, vp, vp, lg, ip, lg, ip, ip, vp, vp]),
+    "dsp_classify_signal_batch_ragged_device": (ip, [vp, vp, vp, lg, lp, vp, vp]),
+    "dsp_classify_signal_batch_ragged_pcm16_device": (ip, [vp, vp, vp, lg, lp, ip, ip, vp, vp]),
+    "dsp_classify_signal": (fl, [vp, vp, ip]),
+    "dsp_speaker_model_create": (ip, [gp, gp, ip, vpp]),
+    "dsp_speaker_model_destroy": (None, [vp]),
+    "dsp_speaker_llr_device": (ip, [vp, vp, lg, ip, vp, vp, vp, vp, vp]),
+    "dsp_speaker_llr_ragged_device": (ip, [vp, vp, lg, lp, vp, vp, vp, vp, vp]),
+    "dsp_scan_window_offsets": (lg, [scp, lp, lg, lp]),
+    "dsp_stop_scan_device": (ip, [vp, vp, lg, lp, scp, vp, vp]),
+    "dsp_speaker_scan_device": (ip, [vp, vp, lg, lp, scp, vp, vp, vp]),
+    "dsp_scanner_create": (ip, [vp, vp, vp, scp, vpp]),
+    "dsp_scanner_destroy": (None, [vp]),
+    "dsp_scanner_run_device": (ip, [vp, vp, lg, lp, vp, vp, vp, vp]),
+    "dsp_scanner_run_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, vp, vp, vp, vp]),
+    "dsp_scan_window_spans": (lg, [cfgp, scp, lp, lg, lp, lp]),
+    "dsp_svm_scan_device": (ip, [vp, vp, lg, lp, scp, vp, vp, vp, vp, vp]),
+    "dsp_scrubjay_scanner_create": (ip, [vp, vp, scp, vpp]),
+    "dsp_scrubjay_scanner_destroy": (None, [vp]),
+    "dsp_scrubjay_scanner_run_device": (ip, [vp, vp, lg, lp, vp, vp, vp, vp, vp]),
+    "dsp_scrubjay_scanner_run_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, vp, vp, vp, vp, vp]),
+    "dsp_stream_push_plan": (lg, [cfgp, scp, lp, lp, lg, lp, lp]),
+    "dsp_stream_session_create": (ip, [vp, vp, vp, scp, lg, ip, ip, ip, vpp]),
+    "dsp_stream_session_destroy": (None, [vp]),
+    "dsp_stream_session_reset": (ip, [vp, lp, lg, vp]),
+    "dsp_stream_session_counts": (ip, [vp, lp, lp, lp]),
+    "dsp_stream_push_device": (ip, [vp, vp, lp, vp, vp, vp, vp, lp, lp, vp]),
+    "dsp_stream_resample_plan": (lg, [ip, ip, lp, lp, lg, lp]),
+    "dsp_stream_resampler_create": (ip, [ip, ip, ip, lg, ip, ip, ip, vpp]),
+    "dsp_stream_resampler_destroy": (None, [vp]),
+    "dsp_stream_resampler_reset": (ip, [vp, lp, lg, vp]),
+    "dsp_stream_resampler_counts": (ip, [vp, lp, lp]),
+    "dsp_stream_resample_push_device": (ip, [vp, vp, lp, vp, lp, vp]),
+    "dsp_stream_resample_finish_device": (ip, [vp, lp, lg, vp, lp, vp]),
+    "dsp_stream_session_attach_resampler": (ip, [vp, vp]),
+    "dsp_upsample_linear_device": (ip, [vp, lg, ip, lg, vp, ip, lg, vp]),
+    "dsp_upsample_linear_host": (ip, [vp, ip, vp, ip]),
+    "dsp_resample_ratio": (ip, [ip, ip, ipp, ipp, ipp]),
+    "dsp_resample_geometry": (ip, [ip, ip, ipp, ip]),
+    "dsp_resample_taps": (ip, [ip, ip, dp, ip]),
+    "dsp_resample_offsets": (lg, [ip, ip, lp, lg, lp]),
+    "dsp_resampler_create": (ip, [ip, ip, ip, vpp]),
+    "dsp_resampler_destroy": (None, [vp]),
+    "dsp_resample_ragged_device": (ip, [vp, vp, lg, lp, vp, vp]),
+    "dsp_resample_ragged_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, vp, vp]),
+    "dsp_resample_clips_device": (ip, [vp, vp, lg, ip, lg, vp, lg, vp]),
+    "dsp_resample_clips_pcm16_device": (ip, [vp, vp, lg, ip, lg, ip, ip, vp, lg, vp]),
+    "dsp_resample_host": (ip, [ip, ip, vp, lg, vp]),
+    "dsp_cmvn_create": (ip, [ip, ip, ip, vpp]),
+    "dsp_cmvn_destroy": (None, [vp]),
+    "dsp_cmvn_ragged_device": (ip, [vp, vp, lg, lp, vp, vp]),
+    "dsp_speaker_enroller_create": (ip, [gfp, ip, vpp]),
+    "dsp_speaker_enroller_destroy": (None, [vp]),
+    "dsp_speaker_enroll_ragged_device": (ip, [vp, vp, lg, lp, P(EnrollConfig), vp, vp, vp, vp, vp, vp]),
+    "dsp_ubm_trainer_create": (ip, [ip, ip, ip, vpp]),
+    "dsp_ubm_trainer_destroy": (None, [vp]),
+    "dsp_ubm_init_rows_device": (ip, [vp, vp, lg, db, vp, vp, vp, vp]),
+    "dsp_ubm_train_device": (ip, [vp, vp, lg, P(UbmInit), P(UbmConfig), urp, vp]),
+    "dsp_gmm_quantize": (ip, [gfp, vp, vp, vp, ipp]),
+    "dsp_kmeans_seed_device": (ip, [vp, vp, lg, u64, vp, vp]),
+    "dsp_kmeans_fit_device": (ip, [vp, vp, lg, vp, P(KmeansConfig), P(KmeansResult), vp]),
+    "dsp_kmeans_train_ubm_device": (ip, [vp, vp, lg, P(KmeansUbmConfig), urp, P(KmeansUbmReport), vp]),
+    "dsp_speaker_verifier_create": (ip, [gfp, ip, vpp]),
+    "dsp_speaker_verifier_destroy": (None, [vp]),
+    "dsp_speaker_verify_ragged_device": (ip, [vp, vp, lg, lp, vp, lg, vp, vp, vp, vp, vp, vp]),
+    "dsp_speaker_float_scan_device": (ip, [vp, vp, lg, lp, scp, vp, lg, vp, vp, vp, vp, vp, vp]),
+    "dsp_segmenter_create": (ip, [ip, vpp]),
+    "dsp_segmenter_destroy": (None, [vp]),
+    "dsp_segments_capacity": (lg, [sgp, lp, lg, lg]),
+    "dsp_segments_device": (ip, [vp, vp, lg, lp, lg, sgp, vp, lg, vp, vp, vp]),
+    "dsp_segment_sample_spans": (lg, [cfgp, scp, lp, lg, vp, lg, lp, lp]),
+    "dsp_trials_target_offsets": (lg, [ipp, lg, lg, lp, lp]),
+    "dsp_trials_pairs": (lg, [ipp, lg, lg]),
+    "dsp_trial_evaluator_create": (ip, [ip, vpp]),
+    "dsp_trial_evaluator_destroy": (None, [vp]),
+    "dsp_trials_evaluate_device": (ip, [vp, vp, lg, lg, ipp, P(TrialsConfig), vp, vp, vp, vp, vp, vp]),
+    "dsp_calibrator_create": (ip, [ip, vpp]),
+    "dsp_calibrator_destroy": (None, [vp]),
+    "dsp_calibration_duration_term": (ip, [lp, lg, dp]),
+    "dsp_calibration_fit_device": (ip, [vp, vp, lg, lg, ipp, lp, P(CalibrationConfig), P(Calibration), P(CalibrationReport), vp]),
+    "dsp_calibration_apply_device": (ip, [vp, vp, lg, lg, lp, P(Calibration), vp, vp]),
+    "dsp_svm_trainer_create": (ip, [ip, ip, vpp]),
+    "dsp_svm_trainer_destroy": (None, [vp]),
+    "dsp_svm_train_set_device": (ip, [vp, vp, lg, vp, lg, vp, vp, vp, vp, vp]),
+    "dsp_svm_train_problems_device": (ip, [vp, P(SvmTrainProblem), lg, stcp, vp, vp, vp, vp, vp]),
+    "dsp_svm_platt_fit_device": (ip, [vp, vp, vp, vp, lg, dp, dp, ipp, vp]),
+    "dsp_svm_folds": (ip, [lg, ip, u64, vp]),
+    "dsp_svm_balanced_weights": (ip, [vp, vp, lg, db, dp, dp]),
+    "dsp_svm_model_from_training": (lg, [vp, vp, vp, lg, ip, vp, vp, lg, lp]),
+    "dsp_svm_fit_device": (ip, [vp, vp, lg, vp, vp, ip, u64, db, db, db, stcp, P(SvmFitModel), vp]),
+    "dsp_svm_train_rows_host": (ip, [vp, vp, vp]),
+    "dsp_stop_trainer_create": (ip, [ip, ip, ip, ipp, vpp]),
+    "dsp_stop_trainer_destroy": (None, [vp]),
+    "dsp_stop_train_set_device": (ip, [vp, vp, lg, vp, vp, lg, vp, vp, vp, vp, vp]),
+    "dsp_stop_train_used_features": (lg, [vp]),
+    "dsp_stop_train_rows_host": (ip, [vp, vp, vp]),
+    "dsp_stop_train_runs_device": (ip, [vp, P(StopTrainRun), lg, vp, vp, vp, vp, vp, vp]),
+    "dsp_stop_train_param_count": (lg, [ip, ip, ipp]),
+    "dsp_stop_train_uniform": (db, [u64, u64, u64]),
+    "dsp_stop_train_order": (ip, [lg, u64, lg, vp]),
+    "dsp_stop_train_init": (ip, [ip, ip, ipp, u64, vp]),
+    "dsp_stop_model_from_training": (ip, [ip, ip, ipp, vp, vp, vp, vp, smp]),
+    "dsp_stft_frames": (lg, [lg]),
+    "dsp_stretch_frames": (lg, [lg, db]),
+    "dsp_stretch_length": (lg, [lg, db]),
+    "dsp_pitch_ratio": (ip, [ip, ip, ip, ipp, ipp]),
+    "dsp_augment_normal": (db, [u64, u64, u64]),
+    "dsp_augment_out_offsets": (lg, [lp, lg, opp, lg, lp]),
+    "dsp_augment_draw": (lg, [u64, ipp, lg, db, opp, lg]),
+    "dsp_augmenter_create": (ip, [ip, ip, ip, vpp]),
+    "dsp_augmenter_destroy": (None, [vp]),
+    "dsp_stft_ragged_device": (ip, [vp, vp, lg, lp, vp, lp, vp]),
+    "dsp_istft_ragged_device": (ip, [vp, vp, lg, lp, lp, vp, lp, vp]),
+    "dsp_time_stretch_ragged_device": (ip, [vp, vp, lg, lp, dp, vp, vp]),
+    "dsp_augment_ragged_device": (ip, [vp, vp, lg, lp, opp, lg, u64, vp, vp]),
+    "dsp_mfcc_tables": (ip, [cfgp, vp, vp, vp]),
+    "dsp_mfcc_lane_tables": (ip, [cfgp, vp, ip]),
+    "dsp_mfcc400_tables": (ip, [cfgp, vp, ip]),
+    "dsp_classify_division_check": (ip, [llp]),
+    "dsp_prefilter_scan_check": (ip, [ip, ipp]),
+    "dsp_last_error": (cp, []),
+    "dsp_device_count": (ip, []),
+    "dsp_version": (cp, []),
+    "dsp_abi_sizeof": (ip, [ip]),
+}
+SYMBOLS = list(PROTOTYPES)      # (a list: tests pick entries by prefix)
 
 # the reference's own C++-linkage names (sync/lib/classifier.h:14-19, include/dsp_amd_classifier.h), Itanium-mangled
 CXX_SYMBOLS = {
@@ -372,227 +534,12 @@ def load() -> C.CDLL:
         L = C.CDLL(path)
     except OSError as e:
         raise DspError(f"cannot load {path}: {e} (the HIP extension is required; there is no fallback)") from e
-    vp, fp, ip = C.c_void_p, C.POINTER(C.c_float), C.c_int
-    cfgp = C.POINTER(MfccConfig)
-    L.dsp_abi_sizeof.argtypes = [ip]; L.dsp_abi_sizeof.restype = ip
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     for which, mirror in ((0, MfccConfig), (1, ClassifyTrace), (2, ClassifyTraceF64)):      # the ctypes mirrors against the library's own structs
         if L.dsp_abi_sizeof(which) != C.sizeof(mirror):
             raise DspError(f"{path}: struct {mirror.__name__} is {L.dsp_abi_sizeof(which)} bytes in the library, {C.sizeof(mirror)} in dsp_amd/lib.py")
-    L.compute_mfcc.argtypes = [vp, ip, vp, ip]; L.compute_mfcc.restype = ip
-    L.fft_real_forward.argtypes = [vp, vp]; L.fft_real_forward.restype = None
-    L.dsp_fft_real_forward_host.argtypes = [vp, C.c_long, ip, C.c_long, ip, vp]; L.dsp_fft_real_forward_host.restype = ip
-    L.dsp_mfcc_default_config.argtypes = [cfgp]; L.dsp_mfcc_default_config.restype = None
-    L.dsp_mfcc_scrubjay_infer_config.argtypes = [cfgp, ip]; L.dsp_mfcc_scrubjay_infer_config.restype = None
-    L.dsp_mfcc_speaker_config.argtypes = [cfgp]; L.dsp_mfcc_speaker_config.restype = None
-    L.dsp_mfcc400_tables.argtypes = [cfgp, vp, ip]; L.dsp_mfcc400_tables.restype = ip
-    L.dsp_mfcc_plan_create.argtypes = [cfgp, ip, C.POINTER(vp)]; L.dsp_mfcc_plan_create.restype = ip
-    L.dsp_mfcc_plan_destroy.argtypes = [vp]; L.dsp_mfcc_plan_destroy.restype = None
-    L.dsp_mfcc_plan_config.argtypes = [vp, cfgp]; L.dsp_mfcc_plan_config.restype = ip
-    L.dsp_mfcc_frames_for.argtypes = [cfgp, ip, ip]; L.dsp_mfcc_frames_for.restype = ip
-    L.dsp_mfcc_frames_device.argtypes = [vp, vp, C.c_long, vp, vp]; L.dsp_mfcc_frames_device.restype = ip
-    L.dsp_mfcc_clips_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, ip, vp]; L.dsp_mfcc_clips_device.restype = ip
-    L.dsp_mfcc_clips_pcm16_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, ip, vp]; L.dsp_mfcc_clips_pcm16_device.restype = ip
-    L.dsp_mfcc_frames_host.argtypes = [vp, vp, C.c_long, vp]; L.dsp_mfcc_frames_host.restype = ip
-    L.dsp_mfcc_clips_host.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, ip]; L.dsp_mfcc_clips_host.restype = ip
-    L.dsp_mfcc_plan_set_launch.argtypes = [vp, ip, ip]; L.dsp_mfcc_plan_set_launch.restype = ip
-    L.dsp_mfcc_plan_set_kernel.argtypes = [vp, ip]; L.dsp_mfcc_plan_set_kernel.restype = ip
-    L.dsp_butter_bandpass.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.dsp_butter_bandpass.restype = ip
-    L.dsp_mfcc_tables.argtypes = [cfgp, vp, vp, vp]; L.dsp_mfcc_tables.restype = ip
-    L.dsp_mfcc_lane_tables.argtypes = [cfgp, vp, ip]; L.dsp_mfcc_lane_tables.restype = ip
-    L.dsp_classify.argtypes = [vp, ip]; L.dsp_classify.restype = ip
-    L.dsp_butter_bandpass_filter_f32.argtypes = [vp, C.c_long, ip, C.c_long, vp, vp, vp]; L.dsp_butter_bandpass_filter_f32.restype = ip
-    L.dsp_butter_bandpass_filter_f64.argtypes = [vp, C.c_long, ip, C.c_long, vp, vp, vp]; L.dsp_butter_bandpass_filter_f64.restype = ip
-    L.dsp_compute_spectrogram_f32.argtypes = [vp, ip, ip, vp, vp, vp]; L.dsp_compute_spectrogram_f32.restype = ip
-    L.dsp_compute_spectrogram_f64.argtypes = [vp, ip, ip, vp, vp, vp]; L.dsp_compute_spectrogram_f64.restype = ip
-    L.dsp_classify_batch_host.argtypes = [vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_host.restype = ip
-    L.dsp_find_midpoints.argtypes = [vp, ip, ip, vp, ip]; L.dsp_find_midpoints.restype = ip
-    L.dsp_classify_batch_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_device.restype = ip
-    L.dsp_mfcc_stats_device.argtypes = [vp, C.c_long, ip, ip, vp, vp]; L.dsp_mfcc_stats_device.restype = ip
-    L.dsp_svm_create.argtypes = [ip, ip, ip, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(vp)]
-    L.dsp_svm_create.restype = ip
-    L.dsp_svm_destroy.argtypes = [vp]; L.dsp_svm_destroy.restype = None
-    L.dsp_svm_predict_device.argtypes = [vp, vp, C.c_long, vp, vp, vp, vp]; L.dsp_svm_predict_device.restype = ip
-    L.dsp_scrubjay_fused_device.argtypes = [vp, vp, vp, C.c_long, ip, C.c_long, ip, vp, vp, vp, vp, vp]; L.dsp_scrubjay_fused_device.restype = ip
-    L.dsp_scrubjay_fused_pcm16_device.argtypes = [vp, vp, vp, C.c_long, ip, C.c_long, ip, ip, ip, vp, vp, vp, vp, vp]; L.dsp_scrubjay_fused_pcm16_device.restype = ip
-    lp = C.POINTER(C.c_long)
-    L.dsp_classify_batch_ragged_device_f64.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp]; L.dsp_classify_batch_ragged_device_f64.restype = ip
-    L.dsp_classify_batch_ragged_pcm16_device_f64.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp]; L.dsp_classify_batch_ragged_pcm16_device_f64.restype = ip
-    L.dsp_classify_batch_ragged_host_f64.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_classify_batch_ragged_host_f64.restype = ip
-    L.dsp_classify_batch_ragged_pcm16_host_f64.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_classify_batch_ragged_pcm16_host_f64.restype = ip
-    L.dsp_classify_stats.argtypes = [ip, lp, lp]; L.dsp_classify_stats.restype = ip
-    L.dsp_classify_batch_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_classify_batch_ragged_device.restype = ip
-    L.dsp_classify_batch_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_classify_batch_ragged_pcm16_device.restype = ip
-    L.dsp_classify_batch_ragged_host.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_classify_batch_ragged_host.restype = ip
-    L.dsp_classify_batch_ragged_pcm16_host.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_classify_batch_ragged_pcm16_host.restype = ip
-    L.dsp_debug_fused_spans.argtypes = [cfgp, lp, C.c_long, ip, C.c_long, lp]; L.dsp_debug_fused_spans.restype = ip
-    L.dsp_scrubjay_fused_ragged_device.argtypes = [vp, vp, vp, C.c_long, lp, ip, vp, vp, vp, vp, vp]; L.dsp_scrubjay_fused_ragged_device.restype = ip
-    L.dsp_scrubjay_fused_ragged_pcm16_device.argtypes = [vp, vp, vp, C.c_long, lp, ip, ip, ip, vp, vp, vp, vp, vp]; L.dsp_scrubjay_fused_ragged_pcm16_device.restype = ip
-    L.dsp_classify_signal_batch_ragged_device.argtypes = [vp, vp, vp, C.c_long, lp, vp, vp]; L.dsp_classify_signal_batch_ragged_device.restype = ip
-    L.dsp_classify_signal_batch_ragged_pcm16_device.argtypes = [vp, vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_classify_signal_batch_ragged_pcm16_device.restype = ip
-    L.dsp_classify_signal_batch_pcm16_device.argtypes = [vp, vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, vp]; L.dsp_classify_signal_batch_pcm16_device.restype = ip
-    L.dsp_stop_model_create.argtypes = [C.POINTER(StopModelParams), ip, C.POINTER(vp)]; L.dsp_stop_model_create.restype = ip
-    L.dsp_stop_model_destroy.argtypes = [vp]; L.dsp_stop_model_destroy.restype = None
-    L.dsp_stop_predict_device.argtypes = [vp, vp, C.c_long, ip, vp, vp]; L.dsp_stop_predict_device.restype = ip
-    L.dsp_classify_signal_batch_device.argtypes = [vp, vp, vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_signal_batch_device.restype = ip
-    L.dsp_classify_signal.argtypes = [vp, vp, ip]; L.dsp_classify_signal.restype = C.c_float
-    L.dsp_speaker_model_create.argtypes = [C.POINTER(GmmParams), C.POINTER(GmmParams), ip, C.POINTER(vp)]; L.dsp_speaker_model_create.restype = ip
-    L.dsp_speaker_model_destroy.argtypes = [vp]; L.dsp_speaker_model_destroy.restype = None
-    L.dsp_speaker_llr_device.argtypes = [vp, vp, C.c_long, ip, vp, vp, vp, vp, vp]; L.dsp_speaker_llr_device.restype = ip
-    L.dsp_mfcc_ragged_frame_offsets.argtypes = [cfgp, lp, C.c_long, ip, lp]; L.dsp_mfcc_ragged_frame_offsets.restype = C.c_long
-    L.dsp_mfcc_clips_ragged_device.argtypes = [vp, vp, C.c_long, lp, ip, vp, vp]; L.dsp_mfcc_clips_ragged_device.restype = ip
-    L.dsp_mfcc_clips_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, ip, vp, vp]; L.dsp_mfcc_clips_ragged_pcm16_device.restype = ip
-    L.dsp_speaker_llr_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_speaker_llr_ragged_device.restype = ip
-    scp = C.POINTER(ScanConfig)
-    L.dsp_scan_window_offsets.argtypes = [scp, lp, C.c_long, lp]; L.dsp_scan_window_offsets.restype = C.c_long
-    L.dsp_stop_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp]; L.dsp_stop_scan_device.restype = ip
-    L.dsp_speaker_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp, vp]; L.dsp_speaker_scan_device.restype = ip
-    L.dsp_scanner_create.argtypes = [vp, vp, vp, scp, C.POINTER(vp)]; L.dsp_scanner_create.restype = ip
-    L.dsp_scanner_destroy.argtypes = [vp]; L.dsp_scanner_destroy.restype = None
-    L.dsp_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp]; L.dsp_scanner_run_device.restype = ip
-    L.dsp_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp]; L.dsp_scanner_run_pcm16_device.restype = ip
-    L.dsp_scan_window_spans.argtypes = [cfgp, scp, lp, C.c_long, lp, lp]; L.dsp_scan_window_spans.restype = C.c_long
-    L.dsp_svm_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, vp, vp, vp, vp]; L.dsp_svm_scan_device.restype = ip
-    L.dsp_scrubjay_scanner_create.argtypes = [vp, vp, scp, C.POINTER(vp)]; L.dsp_scrubjay_scanner_create.restype = ip
-    L.dsp_scrubjay_scanner_destroy.argtypes = [vp]; L.dsp_scrubjay_scanner_destroy.restype = None
-    L.dsp_scrubjay_scanner_run_device.argtypes = [vp, vp, C.c_long, lp, vp, vp, vp, vp, vp]; L.dsp_scrubjay_scanner_run_device.restype = ip
-    L.dsp_scrubjay_scanner_run_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp, vp, vp, vp]
-    L.dsp_scrubjay_scanner_run_pcm16_device.restype = ip
-    L.dsp_stream_push_plan.argtypes = [cfgp, scp, lp, lp, C.c_long, lp, lp]; L.dsp_stream_push_plan.restype = C.c_long
-    L.dsp_stream_session_create.argtypes = [vp, vp, vp, scp, C.c_long, ip, ip, ip, C.POINTER(vp)]; L.dsp_stream_session_create.restype = ip
-    L.dsp_stream_session_destroy.argtypes = [vp]; L.dsp_stream_session_destroy.restype = None
-    L.dsp_stream_session_reset.argtypes = [vp, lp, C.c_long, vp]; L.dsp_stream_session_reset.restype = ip
-    L.dsp_stream_session_counts.argtypes = [vp, lp, lp, lp]; L.dsp_stream_session_counts.restype = ip
-    L.dsp_stream_push_device.argtypes = [vp, vp, lp, vp, vp, vp, vp, lp, lp, vp]; L.dsp_stream_push_device.restype = ip
-    L.dsp_stream_resample_plan.argtypes = [ip, ip, lp, lp, C.c_long, lp]; L.dsp_stream_resample_plan.restype = C.c_long
-    L.dsp_stream_resampler_create.argtypes = [ip, ip, ip, C.c_long, ip, ip, ip, C.POINTER(vp)]; L.dsp_stream_resampler_create.restype = ip
-    L.dsp_stream_resampler_destroy.argtypes = [vp]; L.dsp_stream_resampler_destroy.restype = None
-    L.dsp_stream_resampler_reset.argtypes = [vp, lp, C.c_long, vp]; L.dsp_stream_resampler_reset.restype = ip
-    L.dsp_stream_resampler_counts.argtypes = [vp, lp, lp]; L.dsp_stream_resampler_counts.restype = ip
-    L.dsp_stream_resample_push_device.argtypes = [vp, vp, lp, vp, lp, vp]; L.dsp_stream_resample_push_device.restype = ip
-    L.dsp_stream_resample_finish_device.argtypes = [vp, lp, C.c_long, vp, lp, vp]; L.dsp_stream_resample_finish_device.restype = ip
-    L.dsp_stream_session_attach_resampler.argtypes = [vp, vp]; L.dsp_stream_session_attach_resampler.restype = ip
-    L.dsp_upsample_linear_device.argtypes = [vp, C.c_long, ip, C.c_long, vp, ip, C.c_long, vp]; L.dsp_upsample_linear_device.restype = ip
-    L.dsp_upsample_linear_host.argtypes = [vp, ip, vp, ip]; L.dsp_upsample_linear_host.restype = ip
-    L.dsp_resample_ratio.argtypes = [ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]; L.dsp_resample_ratio.restype = ip
-    L.dsp_resample_geometry.argtypes = [ip, ip, C.POINTER(ip), ip]; L.dsp_resample_geometry.restype = ip
-    L.dsp_resample_taps.argtypes = [ip, ip, C.POINTER(C.c_double), ip]; L.dsp_resample_taps.restype = ip
-    L.dsp_resample_offsets.argtypes = [ip, ip, lp, C.c_long, lp]; L.dsp_resample_offsets.restype = C.c_long
-    L.dsp_resampler_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_resampler_create.restype = ip
-    L.dsp_resampler_destroy.argtypes = [vp]; L.dsp_resampler_destroy.restype = None
-    L.dsp_resample_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_resample_ragged_device.restype = ip
-    L.dsp_resample_ragged_pcm16_device.argtypes = [vp, vp, C.c_long, lp, ip, ip, vp, vp]; L.dsp_resample_ragged_pcm16_device.restype = ip
-    L.dsp_resample_clips_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, vp, C.c_long, vp]; L.dsp_resample_clips_device.restype = ip
-    L.dsp_resample_clips_pcm16_device.argtypes = [vp, vp, C.c_long, ip, C.c_long, ip, ip, vp, C.c_long, vp]; L.dsp_resample_clips_pcm16_device.restype = ip
-    L.dsp_resample_host.argtypes = [ip, ip, vp, C.c_long, vp]; L.dsp_resample_host.restype = ip
-    opp, dp, u64 = C.POINTER(AugmentOp), C.POINTER(C.c_double), C.c_uint64
-    L.dsp_stft_frames.argtypes = [C.c_long]; L.dsp_stft_frames.restype = C.c_long
-    L.dsp_stretch_frames.argtypes = [C.c_long, C.c_double]; L.dsp_stretch_frames.restype = C.c_long
-    L.dsp_stretch_length.argtypes = [C.c_long, C.c_double]; L.dsp_stretch_length.restype = C.c_long
-    L.dsp_pitch_ratio.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]; L.dsp_pitch_ratio.restype = ip
-    L.dsp_augment_normal.argtypes = [u64, u64, u64]; L.dsp_augment_normal.restype = C.c_double
-    L.dsp_augment_out_offsets.argtypes = [lp, C.c_long, opp, C.c_long, lp]; L.dsp_augment_out_offsets.restype = C.c_long
-    L.dsp_augment_draw.argtypes = [u64, C.POINTER(ip), C.c_long, C.c_double, opp, C.c_long]; L.dsp_augment_draw.restype = C.c_long
-    L.dsp_augmenter_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_augmenter_create.restype = ip
-    L.dsp_augmenter_destroy.argtypes = [vp]; L.dsp_augmenter_destroy.restype = None
-    L.dsp_stft_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, lp, vp]; L.dsp_stft_ragged_device.restype = ip
-    L.dsp_istft_ragged_device.argtypes = [vp, vp, C.c_long, lp, lp, vp, lp, vp]; L.dsp_istft_ragged_device.restype = ip
-    L.dsp_time_stretch_ragged_device.argtypes = [vp, vp, C.c_long, lp, dp, vp, vp]; L.dsp_time_stretch_ragged_device.restype = ip
-    L.dsp_augment_ragged_device.argtypes = [vp, vp, C.c_long, lp, opp, C.c_long, u64, vp, vp]; L.dsp_augment_ragged_device.restype = ip
-    L.dsp_cmvn_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_cmvn_create.restype = ip
-    L.dsp_cmvn_destroy.argtypes = [vp]; L.dsp_cmvn_destroy.restype = None
-    L.dsp_cmvn_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, vp]; L.dsp_cmvn_ragged_device.restype = ip
-    L.dsp_speaker_enroller_create.argtypes = [C.POINTER(GmmFloatParams), ip, C.POINTER(vp)]; L.dsp_speaker_enroller_create.restype = ip
-    L.dsp_speaker_enroller_destroy.argtypes = [vp]; L.dsp_speaker_enroller_destroy.restype = None
-    L.dsp_speaker_enroll_ragged_device.argtypes = [vp, vp, C.c_long, lp, C.POINTER(EnrollConfig), vp, vp, vp, vp, vp, vp]
-    L.dsp_speaker_enroll_ragged_device.restype = ip
-    L.dsp_ubm_trainer_create.argtypes = [ip, ip, ip, C.POINTER(vp)]; L.dsp_ubm_trainer_create.restype = ip
-    L.dsp_ubm_trainer_destroy.argtypes = [vp]; L.dsp_ubm_trainer_destroy.restype = None
-    L.dsp_ubm_init_rows_device.argtypes = [vp, vp, C.c_long, C.c_double, vp, vp, vp, vp]; L.dsp_ubm_init_rows_device.restype = ip
-    L.dsp_ubm_train_device.argtypes = [vp, vp, C.c_long, C.POINTER(UbmInit), C.POINTER(UbmConfig), C.POINTER(UbmResult), vp]
-    L.dsp_ubm_train_device.restype = ip
-    L.dsp_kmeans_seed_device.argtypes = [vp, vp, C.c_long, C.c_uint64, vp, vp]; L.dsp_kmeans_seed_device.restype = ip
-    L.dsp_kmeans_fit_device.argtypes = [vp, vp, C.c_long, vp, C.POINTER(KmeansConfig), C.POINTER(KmeansResult), vp]; L.dsp_kmeans_fit_device.restype = ip
-    L.dsp_kmeans_train_ubm_device.argtypes = [vp, vp, C.c_long, C.POINTER(KmeansUbmConfig), C.POINTER(UbmResult), C.POINTER(KmeansUbmReport), vp]
-    L.dsp_kmeans_train_ubm_device.restype = ip
-    L.dsp_gmm_quantize.argtypes = [C.POINTER(GmmFloatParams), vp, vp, vp, C.POINTER(C.c_int)]; L.dsp_gmm_quantize.restype = ip
-    L.dsp_speaker_verifier_create.argtypes = [C.POINTER(GmmFloatParams), ip, C.POINTER(vp)]; L.dsp_speaker_verifier_create.restype = ip
-    L.dsp_speaker_verifier_destroy.argtypes = [vp]; L.dsp_speaker_verifier_destroy.restype = None
-    L.dsp_speaker_verify_ragged_device.argtypes = [vp, vp, C.c_long, lp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
-    L.dsp_speaker_verify_ragged_device.restype = ip
-    L.dsp_speaker_float_scan_device.argtypes = [vp, vp, C.c_long, lp, scp, vp, C.c_long, vp, vp, vp, vp, vp, vp]
-    L.dsp_speaker_float_scan_device.restype = ip
-    sgp = C.POINTER(SegmentConfig)
-    L.dsp_segmenter_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_segmenter_create.restype = ip
-    L.dsp_segmenter_destroy.argtypes = [vp]; L.dsp_segmenter_destroy.restype = None
-    L.dsp_segments_capacity.argtypes = [sgp, lp, C.c_long, C.c_long]; L.dsp_segments_capacity.restype = C.c_long
-    L.dsp_segments_device.argtypes = [vp, vp, C.c_long, lp, C.c_long, sgp, vp, C.c_long, vp, vp, vp]; L.dsp_segments_device.restype = ip
-    L.dsp_segment_sample_spans.argtypes = [cfgp, scp, lp, C.c_long, vp, C.c_long, lp, lp]; L.dsp_segment_sample_spans.restype = C.c_long
-    tip = C.POINTER(C.c_int)
-    L.dsp_trials_target_offsets.argtypes = [tip, C.c_long, C.c_long, lp, lp]; L.dsp_trials_target_offsets.restype = C.c_long
-    L.dsp_trials_pairs.argtypes = [tip, C.c_long, C.c_long]; L.dsp_trials_pairs.restype = C.c_long
-    L.dsp_trial_evaluator_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_trial_evaluator_create.restype = ip
-    L.dsp_trial_evaluator_destroy.argtypes = [vp]; L.dsp_trial_evaluator_destroy.restype = None
-    L.dsp_trials_evaluate_device.argtypes = [vp, vp, C.c_long, C.c_long, tip, C.POINTER(TrialsConfig), vp, vp, vp, vp, vp, vp]
-    L.dsp_trials_evaluate_device.restype = ip
-    L.dsp_calibrator_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_calibrator_create.restype = ip
-    L.dsp_calibrator_destroy.argtypes = [vp]; L.dsp_calibrator_destroy.restype = None
-    L.dsp_calibration_duration_term.argtypes = [lp, C.c_long, C.POINTER(C.c_double)]; L.dsp_calibration_duration_term.restype = ip
-    L.dsp_calibration_fit_device.argtypes = [vp, vp, C.c_long, C.c_long, tip, lp, C.POINTER(CalibrationConfig), C.POINTER(Calibration),
-                                             C.POINTER(CalibrationReport), vp]
-    L.dsp_calibration_fit_device.restype = ip
-    L.dsp_calibration_apply_device.argtypes = [vp, vp, C.c_long, C.c_long, lp, C.POINTER(Calibration), vp, vp]; L.dsp_calibration_apply_device.restype = ip
-    dp = C.POINTER(C.c_double)
-    L.dsp_stop_trainer_create.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(vp)]; L.dsp_stop_trainer_create.restype = ip
-    L.dsp_stop_trainer_destroy.argtypes = [vp]; L.dsp_stop_trainer_destroy.restype = None
-    L.dsp_stop_train_set_device.argtypes = [vp, vp, C.c_long, vp, vp, C.c_long, vp, vp, vp, vp, vp]; L.dsp_stop_train_set_device.restype = ip
-    L.dsp_stop_train_used_features.argtypes = [vp]; L.dsp_stop_train_used_features.restype = C.c_long
-    L.dsp_stop_train_rows_host.argtypes = [vp, vp, vp]; L.dsp_stop_train_rows_host.restype = ip
-    L.dsp_stop_train_runs_device.argtypes = [vp, C.POINTER(StopTrainRun), C.c_long, vp, vp, vp, vp, vp, vp]; L.dsp_stop_train_runs_device.restype = ip
-    L.dsp_stop_train_param_count.argtypes = [ip, ip, C.POINTER(ip)]; L.dsp_stop_train_param_count.restype = C.c_long
-    L.dsp_stop_train_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]; L.dsp_stop_train_uniform.restype = C.c_double
-    L.dsp_stop_train_order.argtypes = [C.c_long, C.c_uint64, C.c_long, vp]; L.dsp_stop_train_order.restype = ip
-    L.dsp_stop_train_init.argtypes = [ip, ip, C.POINTER(ip), C.c_uint64, vp]; L.dsp_stop_train_init.restype = ip
-    L.dsp_stop_model_from_training.argtypes = [ip, ip, C.POINTER(ip), vp, vp, vp, vp, C.POINTER(StopModelParams)]; L.dsp_stop_model_from_training.restype = ip
-    L.dsp_svm_trainer_create.argtypes = [ip, ip, C.POINTER(vp)]; L.dsp_svm_trainer_create.restype = ip
-    L.dsp_svm_trainer_destroy.argtypes = [vp]; L.dsp_svm_trainer_destroy.restype = None
-    L.dsp_svm_train_set_device.argtypes = [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp, vp]; L.dsp_svm_train_set_device.restype = ip
-    L.dsp_svm_train_rows_host.argtypes = [vp, vp, vp]; L.dsp_svm_train_rows_host.restype = ip
-    L.dsp_svm_train_problems_device.argtypes = [vp, C.POINTER(SvmTrainProblem), C.c_long, C.POINTER(SvmTrainConfig), vp, vp, vp, vp, vp]
-    L.dsp_svm_train_problems_device.restype = ip
-    L.dsp_svm_platt_fit_device.argtypes = [vp, vp, vp, vp, C.c_long, dp, dp, C.POINTER(ip), vp]; L.dsp_svm_platt_fit_device.restype = ip
-    L.dsp_svm_folds.argtypes = [C.c_long, ip, C.c_uint64, vp]; L.dsp_svm_folds.restype = ip
-    L.dsp_svm_balanced_weights.argtypes = [vp, vp, C.c_long, C.c_double, dp, dp]; L.dsp_svm_balanced_weights.restype = ip
-    L.dsp_svm_model_from_training.argtypes = [vp, vp, vp, C.c_long, ip, vp, vp, C.c_long, lp]; L.dsp_svm_model_from_training.restype = C.c_long
-    L.dsp_svm_fit_device.argtypes = [vp, vp, C.c_long, vp, vp, ip, C.c_uint64, C.c_double, C.c_double, C.c_double, C.POINTER(SvmTrainConfig),
-                                     C.POINTER(SvmFitModel), vp]
-    L.dsp_svm_fit_device.restype = ip
-    L.dsp_gather_create.argtypes = [vp, ip, C.POINTER(vp)]; L.dsp_gather_create.restype = ip
-    L.dsp_gather_destroy.argtypes = [vp]; L.dsp_gather_destroy.restype = None
-    L.dsp_gather_n_devices.argtypes = [vp]; L.dsp_gather_n_devices.restype = ip
-    L.dsp_gather_all.argtypes = [vp, vp, vp, C.c_size_t, vp]; L.dsp_gather_all.restype = ip
-    L.dsp_last_error.argtypes = []; L.dsp_last_error.restype = C.c_char_p
-    L.dsp_device_count.argtypes = []; L.dsp_device_count.restype = ip
-    L.dsp_version.argtypes = []; L.dsp_version.restype = C.c_char_p
-    L.dsp_classify_default_config.argtypes = [C.POINTER(ClassifyConfig)]; L.dsp_classify_default_config.restype = None
-    L.dsp_classify_batch_host_cfg.argtypes = [C.POINTER(ClassifyConfig), vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_host_cfg.restype = ip
-    L.dsp_classify_default_config_f64.argtypes = [C.POINTER(ClassifyConfigF64)]; L.dsp_classify_default_config_f64.restype = None
-    L.dsp_classify_batch_host_f64.argtypes = [C.POINTER(ClassifyConfigF64), vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_host_f64.restype = ip
-    L.dsp_classify_batch_device_f64.argtypes = [C.POINTER(ClassifyConfigF64), vp, C.c_long, ip, C.c_long, vp, vp, vp]; L.dsp_classify_batch_device_f64.restype = ip
-    L.dsp_classify_batch_pcm16_host.argtypes = [C.POINTER(ClassifyConfig), vp, C.c_long, ip, C.c_long, ip, ip, vp, vp]; L.dsp_classify_batch_pcm16_host.restype = ip
-    L.dsp_classify_batch_pcm16_device.argtypes = [C.POINTER(ClassifyConfig), vp, C.c_long, ip, C.c_long, ip, ip, vp, vp]; L.dsp_classify_batch_pcm16_device.restype = ip
-    L.dsp_classify_release.argtypes = [ip]; L.dsp_classify_release.restype = ip
-    L.dsp_classify_ctx_create.argtypes = [ip, C.POINTER(vp)]; L.dsp_classify_ctx_create.restype = ip
-    L.dsp_classify_ctx_destroy.argtypes = [vp]; L.dsp_classify_ctx_destroy.restype = None
-    L.dsp_classify_batch_device_ctx.argtypes = [vp, C.POINTER(ClassifyConfig), vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_device_ctx.restype = ip
-    L.dsp_debug_hold_classify_ctx.argtypes = [ip, ip]; L.dsp_debug_hold_classify_ctx.restype = ip
-    L.dsp_classify_batch_pcm16_host_f64.argtypes = [C.POINTER(ClassifyConfigF64), vp, C.c_long, ip, C.c_long, ip, ip, vp, vp]; L.dsp_classify_batch_pcm16_host_f64.restype = ip
-    L.dsp_classify_batch_pcm16_device_f64.argtypes = [C.POINTER(ClassifyConfigF64), vp, C.c_long, ip, C.c_long, ip, ip, vp, vp, vp]; L.dsp_classify_batch_pcm16_device_f64.restype = ip
-    L.dsp_classify_release_f64.argtypes = [ip]; L.dsp_classify_release_f64.restype = ip
-    L.dsp_classify_stats_f64.argtypes = [ip, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]; L.dsp_classify_stats_f64.restype = ip
-    L.dsp_classify_batch_device_cfg.argtypes = [C.POINTER(ClassifyConfig), vp, C.c_long, ip, C.c_long, vp, vp]; L.dsp_classify_batch_device_cfg.restype = ip
-    L.dsp_sum_intense_f32.argtypes = [C.c_float, C.c_float, C.c_float, vp, ip, vp, ip, vp, C.c_float, C.POINTER(C.c_float)]
-    L.dsp_sum_intense_f32.restype = ip
     if not explicit:
         # the binary says which sources it was built from: a mismatch means the mtime check was fooled (copied tree,
         # clock skew) and the library on disk is not the code in dsp_amd/csrc
@@ -606,6 +553,58 @@ def load() -> C.CDLL:
 
 def last_error() -> str:
     return load().dsp_last_error().decode()
+
+
+def check(rc: int, what: str) -> int:
+    if rc < 0:
+        raise DspError(f"{what} failed ({rc}): {last_error()}")
+    return rc
+
+
+def current_stream(where):
+    """torch's current stream on `where` -- a CUDA tensor (its device) or a device index -- as the stream argument of the entry points."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(getattr(where, "device", where)).cuda_stream)
+
+
+class Closing:
+    """What every owner of native handles shares: close() when a `with` block ends and when the object is collected."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Handle(Closing):
+    """An object that owns one native handle, self._h, of the library self._L: made by a dsp_*_create, destroyed once by the function
+    `_destroy` names.  The class defaults leave an object whose constructor raised closable."""
+
+    _destroy = None
+    _h = None
+    _L = None
+
+    def _create(self, name: str, *args):
+        """self._h = the handle `name`(*args, &handle) makes (every create function takes its out-handle last), or DspError"""
+        self._L = load()
+        h = C.c_void_p()
+        check(getattr(self._L, name)(*args, C.byref(h)), name)
+        self._h = h
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def _stream(self):
+        return current_stream(self.device)
 
 
 def c_offsets(offsets):
@@ -642,6 +641,18 @@ def long_array(a, size, what):
     a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
     if a.ndim != 1 or a.size != size:
         raise ValueError(f"{what} must hold {size} entries")
+    return a
+
+
+def offsets_array(a, what, unit):
+    """The prefix offsets of the recordings of a ragged matrix (`what`: "frame_offsets" in "rows", "window_offsets" in "windows"): any
+    integer sequence -> a contiguous int64 array of n_recordings + 1 entries that start at >= 0 and never fall, or ValueError."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+    if a.ndim != 1 or a.size < 1:
+        raise ValueError(f"{what} must hold n_recordings + 1 {unit}")
+    if a[0] < 0 or (a.size > 1 and (np.diff(a) < 0).any()):
+        raise ValueError(f"{what} must be non-negative and non-decreasing")
     return a
 
 
@@ -718,9 +729,3 @@ def scores_device(scores, device: int, who: str = "segmenter"):
     if n_col < 1:
         raise ValueError("scores must have at least one column")
     return scores.contiguous(), n_col
-
-
-def check(rc: int, what: str) -> int:
-    if rc < 0:
-        raise DspError(f"{what} failed ({rc}): {last_error()}")
-    return rc

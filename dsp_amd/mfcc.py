@@ -47,7 +47,7 @@ def ragged_frame_offsets(cfg: MfccConfig, offsets, max_frames: int) -> np.ndarra
     clip in the matrix clips_ragged returns (dsp_mfcc_ragged_frame_offsets)."""
     off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
     fo = np.empty(n + 1, np.int64)
-    _lib.check(_lib.load().dsp_mfcc_ragged_frame_offsets(C.byref(cfg), off, n, int(max_frames), fo.ctypes.data_as(C.POINTER(C.c_long))),
+    _lib.check(_lib.load().dsp_mfcc_ragged_frame_offsets(C.byref(cfg), off, n, int(max_frames), fo.ctypes.data_as(_lib.LP)),
                "dsp_mfcc_ragged_frame_offsets")
     return fo
 
@@ -71,27 +71,15 @@ def tables(cfg: MfccConfig):
     return win, mel, dct
 
 
-class MfccPlan:
+class MfccPlan(_lib.Handle):
     """dsp_mfcc_plan: device tables for one configuration on one GPU."""
 
+    _destroy = "dsp_mfcc_plan_destroy"
+
     def __init__(self, cfg: MfccConfig | None = None, device: int = 0):
-        self._L = _lib.load()
         self.cfg = cfg or default_config()
         self.device = device
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_mfcc_plan_create(C.byref(self.cfg), device, C.byref(h)), "dsp_mfcc_plan_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_mfcc_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_mfcc_plan_create", C.byref(self.cfg), device)
 
     def set_kernel(self, kernel: int):
         """0 = one wavefront per frame (default), 1 = the general Stockham kernel (1024-point plans only), 2 = wave per frame with the
@@ -124,10 +112,6 @@ class MfccPlan:
         return out
 
     # ---- HBM-resident buffers (torch tensors on this plan's device) -----------
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def frames(self, frames, out=None):
         """frames: cuda float32 [n][frame_length] -> cuda float32 [n][n_mfcc]; async on torch's current stream."""
         import torch

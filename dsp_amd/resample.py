@@ -62,32 +62,16 @@ def resample_offsets(rate_in: int, rate_out: int, offsets) -> np.ndarray:
     return np.frombuffer(out, dtype=np.int64).copy()
 
 
-class Resampler:
+class Resampler(_lib.Handle):
     """dsp_resampler: the taps of rate_in -> rate_out on one GPU."""
+
+    _destroy = "dsp_resampler_destroy"
 
     def __init__(self, rate_in: int, rate_out: int, device: int = 0):
         self.rate_in, self.rate_out = _rates(rate_in, rate_out)
         self.up, self.down, self.half = resample_ratio(rate_in, rate_out)
-        self._L = _lib.load()
         self.device = int(device)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_resampler_create(self.device, self.rate_in, self.rate_out, C.byref(h)), "dsp_resampler_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._create("dsp_resampler_create", self.device, self.rate_in, self.rate_out)
 
     def out_samples(self, n: int) -> int:
         """ceil(n up / down): the output length of a recording of n samples."""
@@ -151,9 +135,6 @@ class Resampler:
         return out
 
 
-_LP = C.POINTER(C.c_long)
-
-
 def stream_resample_plan(rate_in: int, rate_out: int, received, chunk_offsets) -> np.ndarray:
     """Host only (dsp_stream_resample_plan): streams that have received `received[s]` sample frames (None: none) and now get chunks
     [chunk_offsets[s], chunk_offsets[s + 1]) -> int64 [n + 1], the prefix sums of the outputs that become complete."""
@@ -170,48 +151,31 @@ def stream_resample_plan(rate_in: int, rate_out: int, received, chunk_offsets) -
         if (rec < 0).any():
             raise ValueError("received must be non-negative")
     oo = np.zeros(n + 1, np.int64)
-    _lib.check(_lib.load().dsp_stream_resample_plan(rate_in, rate_out, rec.ctypes.data_as(_LP) if rec is not None else None, co.ctypes.data_as(_LP), n,
-                                                    oo.ctypes.data_as(_LP)), "dsp_stream_resample_plan")
+    _lib.check(_lib.load().dsp_stream_resample_plan(rate_in, rate_out, rec.ctypes.data_as(_lib.LP) if rec is not None else None, co.ctypes.data_as(_lib.LP), n,
+                                                    oo.ctypes.data_as(_lib.LP)), "dsp_stream_resample_plan")
     return oo
 
 
-class StreamResampler:
+class StreamResampler(_lib.Handle):
     """dsp_stream_resampler: n_streams live feeds at rate_in on one GPU.  Every push hands over the next chunk of each feed (any length)
     and returns the outputs at rate_out that became complete with it; concatenated over the pushes they are, bit for bit, the first
     outputs of Resampler.ragged on the whole feed, and finish() emits the rest.  dtype: torch.float32 samples, or torch.int16 PCM
     ([total] mono, [total][2] interleaved stereo with stereo_mode 0 = channel 0 / 1 = average; channels=2 selects stereo).  One stream
     at a time per object."""
 
+    _destroy = "dsp_stream_resampler_destroy"
+
     def __init__(self, rate_in: int, rate_out: int, n_streams: int, dtype=None, stereo_mode: int = 0, channels: int = 1, device: int = 0):
         self.rate_in, self.rate_out = _rates(rate_in, rate_out)
         self.dtype, self.channels, self.stereo_mode, self.n_streams, pcm16 = _lib.stream_format(dtype, channels, stereo_mode, n_streams)
         self.up, self.down, self.half = resample_ratio(rate_in, rate_out)
-        self._L = _lib.load()
         self.device = int(device)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_stream_resampler_create(self.device, self.rate_in, self.rate_out, self.n_streams, self.channels, self.stereo_mode, pcm16,
-                                                       C.byref(h)), "dsp_stream_resampler_create")
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_stream_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._create("dsp_stream_resampler_create", self.device, self.rate_in, self.rate_out, self.n_streams, self.channels, self.stereo_mode, pcm16)
 
     def counts(self):
         """-> (sample frames received, outputs emitted), int64 [n_streams] each."""
         out = [np.zeros(self.n_streams, np.int64) for _ in range(2)]
-        _lib.check(self._L.dsp_stream_resampler_counts(self._h, *[a.ctypes.data_as(_LP) for a in out]), "dsp_stream_resampler_counts")
+        _lib.check(self._L.dsp_stream_resampler_counts(self._h, *[a.ctypes.data_as(_lib.LP) for a in out]), "dsp_stream_resampler_counts")
         return tuple(out)
 
     def plan(self, chunk_offsets) -> np.ndarray:
@@ -231,7 +195,7 @@ class StreamResampler:
             _lib.check(self._L.dsp_stream_resampler_reset(self._h, None, 0, None), "dsp_stream_resampler_reset")
             return
         idx = self._named(streams)
-        _lib.check(self._L.dsp_stream_resampler_reset(self._h, idx.ctypes.data_as(_LP), idx.size, None), "dsp_stream_resampler_reset")
+        _lib.check(self._L.dsp_stream_resampler_reset(self._h, idx.ctypes.data_as(_lib.LP), idx.size, None), "dsp_stream_resampler_reset")
 
     def _out(self, out, total, dev):
         import torch
@@ -249,7 +213,7 @@ class StreamResampler:
         oo = stream_resample_plan(self.rate_in, self.rate_out, self.counts()[0], co)
         out = self._out(out, int(oo[-1]), chunks.device)
         oo2 = np.zeros_like(oo)
-        _lib.check(self._L.dsp_stream_resample_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_LP), out.data_ptr(), oo2.ctypes.data_as(_LP),
+        _lib.check(self._L.dsp_stream_resample_push_device(self._h, chunks.data_ptr(), co.ctypes.data_as(_lib.LP), out.data_ptr(), oo2.ctypes.data_as(_lib.LP),
                                                            self._stream()), "dsp_stream_resample_push_device")
         if not np.array_equal(oo, oo2):
             raise _lib.DspError("dsp_stream_resample_push_device emitted other outputs than dsp_stream_resample_plan announced")
@@ -266,7 +230,7 @@ class StreamResampler:
         total = int(sum(-((-int(n_in[s]) * self.up) // self.down) - int(n_out[s]) for s in idx))
         out = self._out(out, total, torch.device("cuda", self.device))
         oo = np.zeros(idx.size + 1, np.int64)
-        _lib.check(self._L.dsp_stream_resample_finish_device(self._h, idx.ctypes.data_as(_LP), idx.size, out.data_ptr(), oo.ctypes.data_as(_LP),
+        _lib.check(self._L.dsp_stream_resample_finish_device(self._h, idx.ctypes.data_as(_lib.LP), idx.size, out.data_ptr(), oo.ctypes.data_as(_lib.LP),
                                                              self._stream()), "dsp_stream_resample_finish_device")
         if int(oo[-1]) != total:
             raise _lib.DspError(f"the library finished with {int(oo[-1])} outputs, the wrapper expected {total}")

@@ -18,35 +18,22 @@ from .consumers import _frame_offsets, _scan_config, _scan_mfcc, scan_window_off
 from .mfcc import MfccPlan, default_config, ragged_frame_offsets
 
 
-class SvmModel:
+class SvmModel(_lib.Handle):
     """dsp_svm: Scaler + SVMClassifier attributes as decoded from the ONNX file."""
 
+    _destroy = "dsp_svm_destroy"
+
     def __init__(self, attrs: dict, device: int = 0):
-        self._L = _lib.load()
         a = {k: np.ascontiguousarray(attrs[k], np.float32) for k in ("offset", "scale", "sv", "coef")}
         self.n_features = a["offset"].size
         self.n_sv = a["coef"].size
         if a["sv"].shape != (self.n_sv, self.n_features):
             raise ValueError(f"sv must be [n_sv][n_features] = [{self.n_sv}][{self.n_features}]")
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_svm_create(device, self.n_features, self.n_sv, a["offset"].ctypes.data, a["scale"].ctypes.data,
-                                          a["sv"].ctypes.data, a["coef"].ctypes.data,
-                                          float(np.ravel(attrs["kernel_params"])[0]), float(np.ravel(attrs["rho"])[0]),
-                                          float(np.ravel(attrs["prob_a"])[0]), float(np.ravel(attrs["prob_b"])[0]), C.byref(h)),
-                   "dsp_svm_create")
-        self._h = h
+        self._create("dsp_svm_create", device, self.n_features, self.n_sv, a["offset"].ctypes.data, a["scale"].ctypes.data,
+                     a["sv"].ctypes.data, a["coef"].ctypes.data,
+                     float(np.ravel(attrs["kernel_params"])[0]), float(np.ravel(attrs["rho"])[0]),
+                     float(np.ravel(attrs["prob_a"])[0]), float(np.ravel(attrs["prob_b"])[0]))
         self.device = device
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_svm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     def predict(self, feat):
         """feat: cuda float32 [n][n_features] -> (labels int32, decision float32, prob1 float32)."""
@@ -55,7 +42,7 @@ class SvmModel:
         labels = torch.empty(n, dtype=torch.int32, device=feat.device)
         dec = torch.empty(n, dtype=torch.float32, device=feat.device)
         p1 = torch.empty(n, dtype=torch.float32, device=feat.device)
-        st = C.c_void_p(torch.cuda.current_stream(feat.device).cuda_stream)
+        st = _lib.current_stream(feat)
         _lib.check(self._L.dsp_svm_predict_device(self._h, feat.contiguous().data_ptr(), n, labels.data_ptr(), dec.data_ptr(),
                                                   p1.data_ptr(), st), "dsp_svm_predict_device")
         return labels, dec, p1
@@ -65,15 +52,14 @@ class SvmModel:
         [F][n_features / 2], recording r = rows [frame_offsets[r], frame_offsets[r + 1]), every recording >= 1 row -> (window_offsets
         int64 [n + 1], labels int32, decision float32, prob1 float32 [W], feat float32 [W][n_features]).  No head rows: under stream
         framing a window's first rows differ from its cut-out clip's (ScrubJayScanner computes those)."""
-        import torch
         wo = scan_window_offsets(frame_offsets, window_frames, hop_frames)
         fo = _frame_offsets(frame_offsets)
         if self.n_features % 2:
             raise ValueError("the scan pools n_features / 2 coefficients per row: n_features must be even")
         mfcc = _scan_mfcc(mfcc, fo, self.n_features // 2)
         out = _window_outputs(int(wo[-1]), self.n_features, mfcc.device)
-        st = C.c_void_p(torch.cuda.current_stream(mfcc.device).cuda_stream)
-        _lib.check(self._L.dsp_svm_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(C.POINTER(C.c_long)),
+        st = _lib.current_stream(mfcc)
+        _lib.check(self._L.dsp_svm_scan_device(self._h, mfcc.data_ptr(), fo.size - 1, fo.ctypes.data_as(_lib.LP),
                                                C.byref(_scan_config(window_frames, hop_frames)), *[t.data_ptr() for t in out], st),
                    "dsp_svm_scan_device")
         return (wo,) + out
@@ -91,8 +77,7 @@ def scan_window_spans(config, offsets, window_frames: int, hop_frames: int):
     them as clips gives what the scans compute per window."""
     cfg = _scan_config(window_frames, hop_frames)
     off, n = _lib.c_offsets(offsets)
-    L = _lib.load()
-    lp = C.POINTER(C.c_long)
+    L, lp = _lib.load(), _lib.LP
     total = _lib.check(L.dsp_scan_window_spans(C.byref(config), C.byref(cfg), off, n, None, None), "dsp_scan_window_spans")
     starts, lengths = np.zeros(total, np.int64), np.zeros(total, np.int64)
     _lib.check(L.dsp_scan_window_spans(C.byref(config), C.byref(cfg), off, n, starts.ctypes.data_as(lp), lengths.ctypes.data_as(lp)),
@@ -105,7 +90,7 @@ def mfcc_stats(mfcc):
     import torch
     n, t, c = mfcc.shape
     feat = torch.empty((n, 2 * c), dtype=torch.float32, device=mfcc.device)
-    st = C.c_void_p(torch.cuda.current_stream(mfcc.device).cuda_stream)
+    st = _lib.current_stream(mfcc)
     _lib.check(_lib.load().dsp_mfcc_stats_device(mfcc.contiguous().data_ptr(), n, t, c, feat.data_ptr(), st), "dsp_mfcc_stats_device")
     return feat
 
@@ -162,7 +147,7 @@ class ScrubJay:
         dec = torch.empty(n, dtype=torch.float32, device=clips.device)
         p1 = torch.empty(n, dtype=torch.float32, device=clips.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=clips.device)
-        st = C.c_void_p(torch.cuda.current_stream(clips.device).cuda_stream)
+        st = _lib.current_stream(clips)
         _lib.check(_lib.load().dsp_scrubjay_fused_device(self.plan._h, self.svm._h, clips.data_ptr(), n, clips.shape[1], clips.stride(0),
                                                          int(min(max_frames, 1 << 30)), labels.data_ptr(), dec.data_ptr(), p1.data_ptr(),
                                                          feat.data_ptr(), st), "dsp_scrubjay_fused_device")
@@ -178,7 +163,7 @@ class ScrubJay:
         dec = torch.empty(n, dtype=torch.float32, device=pcm.device)
         p1 = torch.empty(n, dtype=torch.float32, device=pcm.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=pcm.device)
-        st = C.c_void_p(torch.cuda.current_stream(pcm.device).cuda_stream)
+        st = _lib.current_stream(pcm)
         _lib.check(_lib.load().dsp_scrubjay_fused_pcm16_device(self.plan._h, self.svm._h, pcm.data_ptr(), n, pcm.shape[1], stride,
                                                                channels, int(stereo_mode), int(min(max_frames, 1 << 30)), labels.data_ptr(), dec.data_ptr(),
                                                                p1.data_ptr(), feat.data_ptr(), st), "dsp_scrubjay_fused_pcm16_device")
@@ -194,7 +179,7 @@ class ScrubJay:
         dec = torch.empty(n, dtype=torch.float32, device=signal.device)
         p1 = torch.empty(n, dtype=torch.float32, device=signal.device)
         feat = torch.empty((n, self.svm.n_features), dtype=torch.float32, device=signal.device)
-        st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
+        st = _lib.current_stream(signal)
         mf = int(min(max_frames, 1 << 30))
         if channels:
             _lib.check(_lib.load().dsp_scrubjay_fused_ragged_pcm16_device(self.plan._h, self.svm._h, ptr, n, off, channels, int(stereo_mode), mf,
@@ -237,27 +222,16 @@ def svm_model_from_training(z, labels, coef):
     return sv[:n_sv].copy(), c32[:n_sv].copy(), n0.value
 
 
-class SvmTrainer:
+class SvmTrainer(_lib.Handle):
     """dsp_svm_trainer: the scrub-jay RBF-SVM from pooled features, cepstrum/train.py:66-85 on the GPU -- the Scaler, batched SMO over one
     shared distance matrix, libsvm's Platt fit, cross-validation over a (C, gamma) grid.  Features are cuda float32 [n][n_features]
     (mfcc_stats, or the features ScrubJay returns), labels 0 / 1 on the host.  One stream at a time per trainer."""
 
+    _destroy = "dsp_svm_trainer_destroy"
+
     def __init__(self, n_features: int, device: int = 0):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_svm_trainer_create(device, int(n_features), C.byref(h)), "dsp_svm_trainer_create")
-        self._h, self.n_features, self.device, self.n = h, int(n_features), device, 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_svm_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_svm_trainer_create", device, int(n_features))
+        self.n_features, self.device, self.n = int(n_features), device, 0
 
     def _features(self, feat):
         import torch
@@ -266,10 +240,6 @@ class SvmTrainer:
         if feat.device.index != self.device:
             raise ValueError(f"feat is on GPU {feat.device.index}, the trainer on GPU {self.device}")
         return feat.contiguous()
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set(self, feat, scaler_rows=None, offset=None, scale=None):
         """The dataset of the calls that follow (dsp_svm_train_set_device): fits the Scaler on `scaler_rows` (default: all rows) or takes
@@ -423,28 +393,17 @@ class SvmTrainer:
         return {"dec": held, "precision": precision, "recall": recall, "f1": f1, "status": np.stack(status), "grid": grid}
 
 
-class ScrubJayScanner:
+class ScrubJayScanner(_lib.Handle):
     """dsp_scrubjay_scanner: long recordings back to back in HBM -> label, decision, P(label 1) and the pooled features per window of
     window_frames MFCC rows every hop_frames rows, each equal to ScrubJay.ragged on the window cut out (scan_window_spans).  Borrows
     the ScrubJay's plan and SVM.  One stream at a time per scanner."""
 
+    _destroy = "dsp_scrubjay_scanner_destroy"
+
     def __init__(self, scrubjay: ScrubJay, window_frames: int = 16, hop_frames: int = 4):
-        self._L = _lib.load()
         self.cfg = _scan_config(window_frames, hop_frames)
-        h = C.c_void_p()
-        _lib.check(self._L.dsp_scrubjay_scanner_create(scrubjay.plan._h, scrubjay.svm._h, C.byref(self.cfg), C.byref(h)), "dsp_scrubjay_scanner_create")
-        self._h, self.scrubjay = h, scrubjay          # (the scanner borrows its plan and SVM: keep them alive)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.dsp_scrubjay_scanner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._create("dsp_scrubjay_scanner_create", scrubjay.plan._h, scrubjay.svm._h, C.byref(self.cfg))
+        self.scrubjay = scrubjay          # (the scanner borrows its plan and SVM: keep them alive)
 
     def run(self, signal, offsets, stereo_mode: int = 0):
         """signal: cuda float32 [total], int16 [total] (mono) or int16 [total][2] (interleaved stereo), recording r = samples
@@ -457,7 +416,7 @@ class ScrubJayScanner:
         fo = ragged_frame_offsets(self.scrubjay.plan.cfg, (off, n), 2**31 - 1)
         wo = scan_window_offsets(fo, self.cfg.window_frames, self.cfg.hop_frames)
         out = _window_outputs(int(wo[-1]), self.scrubjay.svm.n_features, signal.device)
-        st = C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)
+        st = _lib.current_stream(signal)
         ptrs = [t.data_ptr() for t in out]
         if channels:
             _lib.check(self._L.dsp_scrubjay_scanner_run_pcm16_device(self._h, ptr, n, off, channels, int(stereo_mode), *ptrs, st),

@@ -19,9 +19,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 nb = (n + 63) // 64
 buf = (C.c_int * (16 * nb))()
-lib = L.load()
-lib.dsp_classify_debug_f64.argtypes = [C.c_int, C.c_void_p, C.c_int]
-L.check(lib.dsp_classify_debug_f64(0, buf, 16 * nb), "debug")
+L.check(L.load().dsp_classify_debug_f64(0, buf, 16 * nb), "debug")
 a = np.frombuffer(buf, dtype=np.int32).reshape(nb, 16)
 if len(set(a[:, 0].tolist())) < 8:
     sys.exit("no per-CU records (DSP_AMD_F64_ROLES=0 or not a -DSC_DIAG build)")
