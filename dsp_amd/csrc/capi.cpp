@@ -284,6 +284,44 @@ int dsp_butter_bandpass(double lowcut, double highcut, double *b, double *a)
     return 1;
 }
 
+// What `kernel` (a DSP_KERNEL_* id the plan's n_fft has) means on this plan: the family, its chunk granule and the occupancy of the
+// forms its entries launch.  The plan's device is current.
+static dsp::PlanKernel resolve_kernel(const dsp_mfcc_plan *p, int kernel)
+{
+    using K = dsp::PlanKernel;
+    const dsp_mfcc_config &c = p->cfg;
+    K k;
+    if (c.n_fft == 400) {
+        k.family = K::FFT400;
+        k.per_cu = dsp::mfcc400_blocks_per_cu(c.n_mels);
+    } else if (c.n_fft == 2048) {
+        const bool aub = c.spectrum != DSP_SPECTRUM_POWER || c.log_mode == DSP_LOG_LOG10_FLOOR || c.framing == DSP_FRAMING_STREAM;
+        k.family = aub ? K::FFT2048_AUBIO : K::FFT2048;
+        k.per_cu = dsp::mfcc2048_blocks_per_cu(c.n_mels, false, aub);
+        k.per_cu_fused = dsp::mfcc2048_blocks_per_cu(c.n_mels, true, aub);
+    } else if (c.n_fft == 1024) {
+        const bool wave = p->wave1024_fits && kernel != DSP_KERNEL_ROW, full = c.frame_length == 1024;
+        k.family = wave ? K::FFT1024_WAVE : K::FFT1024_ROW;
+        k.granule = wave ? 8 : 1;
+        k.per_cu = wave ? dsp::mfcc1024_wave_blocks_per_cu(full) : dsp::mfcc1024_blocks_per_cu(full);
+        if (wave && p->d_scan) k.per_cu_prefilter = dsp::mfcc1024_wave_blocks_per_cu(true, true);
+    } else {
+        const bool tile = kernel == DSP_KERNEL_WAVE && c.log_mode == DSP_LOG_PER_FRAME_MAX;
+        k.family = tile ? K::FFT512_TILE : K::FFT512_FRAME;
+        k.granule = tile ? 8 : 1;
+        k.per_cu = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather, c.frame_length == 512, tile);
+        if (tile) k.per_cu_fused = k.per_cu;
+    }
+    return k;
+}
+
+// n_fft 400 plans (dsp_mfcc_speaker_config) run float frames, clips and ragged batches on their own kernel and nothing else: `what` names
+// the entry that refuses one
+static int refuse_400(const char *what)
+{
+    return capi_fail(DSP_EINVAL, std::string(what) + " is not implemented for n_fft 400 plans (float frames, clips and ragged batches only)");
+}
+
 int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan **out)
 {
     if (!cfg || !out) return capi_fail(DSP_EINVAL, "cfg/out is NULL");
@@ -319,8 +357,8 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     if (e == hipSuccess && gen) e = dsp::upload(p->d_gen_tables, *gen);
     if (e == hipSuccess && g2k) e = dsp::upload(p->d_tables2048, *g2k);
     if (e == hipSuccess && t400) e = dsp::upload(p->d_tables400, *t400);
-    if (gen) p->gen_slots = gen->n_chunk_slots;
-    if (e == hipSuccess && cfg->n_fft == 1024 && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->gen_slots <= 3) {
+    p->wave1024_fits = gen && gen->n_chunk_slots <= 3;
+    if (e == hipSuccess && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->wave1024_fits) {
         // BASELINE config 3 in ONE pass: the per-frame Butterworth as a scan inside the MFCC kernel (tables.hpp PrefilterScan)
         double b[9], a[9];
         dsp_butter_bandpass(cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
@@ -334,22 +372,7 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     }
     if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
     p->n_cu = prop.multiProcessorCount;
-    p->aub = cfg->n_fft == 2048 && (cfg->spectrum != DSP_SPECTRUM_POWER || cfg->log_mode == DSP_LOG_LOG10_FLOOR || cfg->framing == DSP_FRAMING_STREAM);
-    if (cfg->n_fft == 400) {
-        p->resident_blocks_400 = dsp::mfcc400_blocks_per_cu(cfg->n_mels);
-    } else if (cfg->n_fft == 2048) {
-        p->resident_blocks_2048 = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, false, p->aub);
-        p->resident_blocks_2048_pool = dsp::mfcc2048_blocks_per_cu(cfg->n_mels, true, p->aub);
-    } else if (cfg->n_fft == 512) {
-        p->resident_blocks_frame = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
-                                                              cfg->frame_length == 512, false);
-        p->resident_blocks = dsp::mfcc512_blocks_per_cu(p->host.dct_split, p->host.dct_len, p->host.mel_gather,
-                                                        cfg->frame_length == 512, true);
-    } else if (cfg->n_fft == 1024) {
-        p->resident_blocks_gen = dsp::mfcc1024_blocks_per_cu(cfg->frame_length == 1024);
-        p->resident_blocks_gen_wave = dsp::mfcc1024_wave_blocks_per_cu(cfg->frame_length == 1024);
-        if (p->d_scan) p->resident_blocks_gen_pre = dsp::mfcc1024_wave_blocks_per_cu(true, true);
-    }
+    p->run = resolve_kernel(p.get(), DSP_KERNEL_WAVE);
     if (const char *k = std::getenv("DSP_AMD_KERNEL")) {
         // an A/B switch, not a requirement: a value this plan's n_fft has no kernel for is reported and ignored -- an
         // environment left over from the removed 512-point experiments must not make every plan_create fail
@@ -381,10 +404,12 @@ int dsp_mfcc_plan_set_kernel(dsp_mfcc_plan *p, int kernel)
     // DSP_KERNEL_ROW on a 1024-point plan selects the general Stockham kernel (a product path: the fallback for filterbanks
     // the wave kernel's tables do not hold); the 512-point row / pair kernels were measured dead ends (0.537 ms and 0.44-0.45 ms
     // against 0.41 ms for the default kernel, profiles/r02_wave_priority_ab.txt) and have been removed
-    if (kernel != DSP_KERNEL_WAVE) if (const int rc = dsp::refuse_400(p, "dsp_mfcc_plan_set_kernel with anything but DSP_KERNEL_WAVE")) return rc;
+    if (kernel != DSP_KERNEL_WAVE && p->cfg.n_fft == 400) return refuse_400("dsp_mfcc_plan_set_kernel with anything but DSP_KERNEL_WAVE");
     if (kernel == DSP_KERNEL_PAIR || (kernel == DSP_KERNEL_ROW && p->cfg.n_fft != 1024))
         return capi_fail(DSP_EINVAL, "DSP_KERNEL_ROW / DSP_KERNEL_PAIR: the 512-point row and pair kernels were removed (measured slower than the default kernel)");
+    dsp::DeviceScope dsp_device_scope_(p->device);      // the occupancy queries
     p->kernel = kernel;
+    p->run = resolve_kernel(p, kernel);
     return DSP_OK;
 }
 
@@ -436,11 +461,64 @@ template <class Launch> static int two_pass_floor(dsp_mfcc_plan *p, dsp::Mfcc512
     return DSP_OK;
 }
 
-int dsp::pcm16_check(const dsp_mfcc_plan *p, int in_kind, bool clip_mode)
+int dsp::plan_accepts(const dsp_mfcc_plan *p, PlanUse use, int in_kind)
 {
-    if (in_kind != 0) if (const int rc = dsp::refuse_400(p, "PCM16 ingestion")) return rc;
-    if (in_kind != 0 && !(p->aub && clip_mode) && (p->cfg.n_fft != 512 || p->kernel != DSP_KERNEL_WAVE || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX))
+    using K = dsp::PlanKernel;
+    const dsp_mfcc_config &c = p->cfg;
+    const K::Family fam = p->run.family;
+    const bool aub = fam == K::FFT2048_AUBIO, wave = p->kernel == DSP_KERNEL_WAVE, prefilter = c.prefilter != DSP_PREFILTER_NONE;
+    // a 512-point plan's shape against the kernel's forms (the fused kernels and int16 rows are forms of the tile epilogue)
+    const auto form = [&](Mfcc512Use u) {
+        return fam == K::FFT512_TILE && mfcc512_has_form(u, p->host.dct_split, p->host.dct_len, p->host.mel_gather, c.frame_length, in_kind, true);
+    };
+    switch (use) {
+    case PlanUse::FusedLabel:
+        if (fam == K::FFT400) return refuse_400("the fused clip -> label path");
+        if ((c.n_fft != 512 && c.n_fft != 2048) || (c.log_mode != DSP_LOG_PER_FRAME_MAX && c.log_mode != DSP_LOG_LOG10_FLOOR) || prefilter || !wave)
+            return capi_fail(DSP_EINVAL, "the fused clip -> label path runs on the 512- and 2048-point wave-per-frame kernels, per-frame log modes");
+        if (in_kind != 0 && !aub && !form(Mfcc512Use::Label))
+            return capi_fail(DSP_EINVAL, "int16 input of the fused clip -> label kernel: the reference framing (n_fft 512, frame 400, 40 mel filters, up to 20 coefficients) "
+                                    "or the scrubjay_infer.c front end (dsp_mfcc_scrubjay_infer_config)");
+        return DSP_OK;
+    case PlanUse::FusedStop:
+        if (fam == K::FFT400) return refuse_400("classify_signal (the fused clip -> probability kernel and its two-kernel form)");
+        return !prefilter && form(Mfcc512Use::Stop) ? 1 : 0;
+    case PlanUse::ScrubjayScan:
+        // the plans whose rows do not depend on the window, on the fused clip -> label kernel's front ends (what per-window equality is against)
+        if (fam == K::FFT400) return refuse_400("a scrub-jay scan");
+        if (c.log_mode == DSP_LOG_GLOBAL_REF1) return capi_fail(DSP_EINVAL, "DSP_LOG_GLOBAL_REF1 plans cannot be scanned: the top_db floor spans the window");
+        if (prefilter || c.n_fft == 1024) return capi_fail(DSP_EINVAL, "scans run on the ragged MFCC matrix: prefilter plans and n_fft 1024 are not supported");
+        if (!wave) return capi_fail(DSP_EINVAL, "scans run on the wave-per-frame kernel (DSP_KERNEL_WAVE), as the fused clip -> label path");
+        if (in_kind != 0 && !aub && !form(Mfcc512Use::Clips))
+            return capi_fail(DSP_EINVAL, "int16 input of the scrub-jay scan: the ragged MFCC matrix takes it on the scrubjay_infer.c front end "
+                                         "(dsp_mfcc_scrubjay_infer_config) and on the 512-point framing with up to 13 coefficients of 40 mel filters");
+        return DSP_OK;
+    case PlanUse::Scan:
+        if (fam == K::FFT400) return refuse_400("a scanner or stream session");
+        if (c.n_fft != 512 || c.log_mode != DSP_LOG_PER_FRAME_MAX || c.framing != DSP_FRAMING_COMPLETE || prefilter)
+            return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
+                                         "no prefilter");
+        break;
+    case PlanUse::Clips:
+        if (prefilter)
+            return capi_fail(DSP_EINVAL, in_kind == 0 ? "the per-frame prefilter applies to independent frames only"
+                                                      : "the per-frame prefilter applies to independent float frames only");
+        break;
+    case PlanUse::Ragged:
+        if (prefilter) return capi_fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
+        if (c.n_fft == 1024) return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the 400-, 512- and 2048-point kernels: n_fft 1024 is not supported");
+        break;
+    case PlanUse::Frames: break;
+    }
+    // MFCC rows: every family takes float samples; int16 is converted in the load of the forms that have one
+    if (in_kind == 0) return DSP_OK;
+    if (fam == K::FFT400) return refuse_400("PCM16 ingestion");
+    if (aub && use != PlanUse::Frames) return DSP_OK;
+    if (fam != K::FFT512_TILE)
         return capi_fail(DSP_EINVAL, "PCM16 ingestion runs on the 512-point wave-per-frame kernel (per-frame log mode) and on the 2048-point scrubjay_infer.c front end");
+    if (!form(use == PlanUse::Frames ? Mfcc512Use::Frames : Mfcc512Use::Clips))
+        return capi_fail(DSP_EINVAL, std::string("PCM16 ingestion on a 512-point plan: of the kernel's shapes, MFCC rows take int16 clips and ragged batches for ") +
+                                         dsp::kMfcc512RowsPcm16Shapes);
     return DSP_OK;
 }
 
@@ -455,36 +533,19 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
     const bool clip_mode = frames_per_clip > 0 || rg;
     const bool single_clip = frames_per_clip > 0 && n_frames == frames_per_clip;   // stride unused
     if (const int rc = dsp::check_aligned(job.in, in_kind, !single_clip, job.clip_stride)) return rc;
-    if (const int rc = dsp::pcm16_check(p, in_kind, clip_mode)) return rc;
     dsp::Mfcc512Args a = dsp::plan_args(p, job.in, in_kind, clip_mode);
     a.out = job.out;
     a.n_frames = n_frames;
     a.clip_stride = job.clip_stride;
     a.frames_per_clip = frames_per_clip;
     a.samples_per_clip = job.samples_per_clip;
-    const bool fft2048 = p->cfg.n_fft == 2048, gen = p->cfg.n_fft == 1024, fft400 = p->cfg.n_fft == 400;
-    if (!fft2048 && !gen && !fft400 && p->cfg.n_fft != 512) return capi_fail(DSP_EINVAL, "internal: no kernel for this n_fft");
-    // 16-frame tile epilogue: per-frame log mode on the wave-per-frame kernel
-    const bool tile = !gen && !fft400 && p->kernel == DSP_KERNEL_WAVE && p->cfg.log_mode == DSP_LOG_PER_FRAME_MAX;
-    // 1024-point: the register-resident wave kernel when the filterbank fits two chunk slots per lane (DSP_KERNEL_ROW selects
-    // the general Stockham kernel for A/B)
-    const bool gen_wave = gen && p->gen_slots <= 3 && p->kernel != DSP_KERNEL_ROW;
-    int per_cu;
-    if (fft400) {
-        if (a.center_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: centred framing without the clip length");
-        a.chunk = p->chunk > 0 ? p->chunk : 8;
-        per_cu = p->resident_blocks_400;
-    } else if (fft2048) {
-        if (a.stream_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: stream framing without the clip length");
-        a.chunk = p->chunk > 0 ? p->chunk : 8;
-        per_cu = p->resident_blocks_2048;
-    } else {
-        const int nf = gen ? (gen_wave ? 8 : 1) : (tile ? 8 : 1);
-        a.chunk = p->chunk > 0 ? p->chunk : 8;
-        a.chunk = ((a.chunk + nf - 1) / nf) * nf;   // whole items (tile: half-tiles of 8 frames) per chunk
-        per_cu = gen ? (gen_wave ? (job.fused_prefilter ? p->resident_blocks_gen_pre : p->resident_blocks_gen_wave) : p->resident_blocks_gen)
-                     : (tile ? p->resident_blocks : p->resident_blocks_frame);
-    }
+    using K = dsp::PlanKernel;
+    const K &k = p->run;
+    if (a.center_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: centred framing without the clip length");
+    if (a.stream_framing && job.samples_per_clip <= 0 && !rg) return capi_fail(DSP_EINVAL, "internal: stream framing without the clip length");
+    if (job.fused_prefilter && !(k.family == K::FFT1024_WAVE && p->d_scan)) return capi_fail(DSP_EINVAL, "internal: fused prefilter without its tables");
+    a.chunk = p->chunk > 0 ? p->chunk : 8;
+    a.chunk = ((a.chunk + k.granule - 1) / k.granule) * k.granule;   // whole items (tile: half-tiles of 8 frames) per chunk
     dsp::SpanRing::Lease slot;
     if (rg) {
         const int rc = ragged_mfcc_spans(p, *rg, n_frames, a.chunk, slot, st);
@@ -492,16 +553,16 @@ int dsp::mfcc_run(dsp_mfcc_plan *p, const MfccJob &job)
         a.spans = static_cast<const dsp::ClipSpan *>(slot.d());
         a.n_clips = rg->n_spans;
     }
-    const int blocks = dsp::grid(p, per_cu, (n_frames + a.chunk - 1) / a.chunk);
-    if (job.fused_prefilter && !(gen_wave && p->d_scan)) return capi_fail(DSP_EINVAL, "internal: fused prefilter without its tables");
+    const int blocks = dsp::grid(p, job.fused_prefilter ? k.per_cu_prefilter : k.per_cu, (n_frames + a.chunk - 1) / a.chunk);
     auto launch = [&](const dsp::Mfcc512Args &x) {
-        if (fft400) return dsp::launch_mfcc400(x, p->d_tables400, blocks, st);
-        if (fft2048) return dsp::launch_mfcc2048(x, p->d_tables2048, blocks, st, false);
-        if (x.log_mode == DSP_LOG_GLOBAL_REF1)      // the wave-per-frame kernel's per-frame epilogue
-            return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, false);
-        if (gen_wave) return dsp::launch_mfcc1024_wave(x, p->d_gen_tables, blocks, st, job.fused_prefilter ? p->d_scan : nullptr, p->scan_steps);
-        if (gen) return dsp::launch_mfcc1024(x, p->d_gen_tables, blocks, st);
-        return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, tile);
+        switch (k.family) {
+        case K::FFT400: return dsp::launch_mfcc400(x, p->d_tables400, blocks, st);
+        case K::FFT2048: case K::FFT2048_AUBIO: return dsp::launch_mfcc2048(x, p->d_tables2048, blocks, st, false);
+        case K::FFT1024_WAVE: return dsp::launch_mfcc1024_wave(x, p->d_gen_tables, blocks, st, job.fused_prefilter ? p->d_scan : nullptr, p->scan_steps);
+        case K::FFT1024_ROW: return dsp::launch_mfcc1024(x, p->d_gen_tables, blocks, st);
+        case K::FFT512_TILE: case K::FFT512_FRAME: break;
+        }
+        return dsp::launch_mfcc512(x, p->host.dct_split, p->host.dct_len, p->host.mel_gather, blocks, st, k.family == K::FFT512_TILE);
     };
     if (a.log_mode == DSP_LOG_GLOBAL_REF1 && clip_mode) return two_pass_floor(p, a, st, launch);
     DSP_CAPI_HIP(launch(a));      // (DSP_LOG_GLOBAL_REF1 on independent frames: one pass, every frame its own clip)
@@ -513,9 +574,7 @@ int dsp::mfcc_clips(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clip
 {
     if (in_kind < 0) return in_kind;
     if (!p || n_clips < 0) return capi_fail(DSP_EINVAL, "bad argument");
-    if (p->cfg.prefilter != DSP_PREFILTER_NONE)
-        return capi_fail(DSP_EINVAL, in_kind == 0 ? "the per-frame prefilter applies to independent frames only"
-                                                  : "the per-frame prefilter applies to independent float frames only");
+    if (const int rc = plan_accepts(p, PlanUse::Clips, in_kind)) return rc;
     const int t = dsp_mfcc_frames_for(&p->cfg, samples_per_clip, max_frames);
     if (t == 0 || n_clips == 0) return 0;
     if (!d_in || !d_out) return capi_fail(DSP_EINVAL, "NULL buffer");
@@ -546,20 +605,12 @@ static long ragged_frame_offsets(const dsp_mfcc_config &cfg, const long *offsets
     return frame_offsets[n_clips];
 }
 
-int dsp::ragged_plan_check(const dsp_mfcc_plan *p)
-{
-    if (p->cfg.prefilter != DSP_PREFILTER_NONE) return capi_fail(DSP_EINVAL, "ragged MFCC matrices: prefilter plans are not supported (the per-frame prefilter applies to independent frames)");
-    if (p->cfg.n_fft != 400 && p->cfg.n_fft != 512 && p->cfg.n_fft != 2048)
-        return capi_fail(DSP_EINVAL, "ragged MFCC matrices run on the 400-, 512- and 2048-point kernels: n_fft 1024 is not supported");
-    return DSP_OK;
-}
-
 int dsp::mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, const long *offsets, int max_frames, float *d_out,
                            void *stream, const long *lengths)
 {
     if (in_kind < 0) return in_kind;
     if (!p || n_clips < 0 || !offsets) return capi_fail(DSP_EINVAL, "bad argument");
-    if (const int rc = ragged_plan_check(p)) return rc;
+    if (const int rc = plan_accepts(p, PlanUse::Ragged, in_kind)) return rc;
     if (n_clips >= (1L << 31)) return capi_fail(DSP_EINVAL, "too many clips");
     std::vector<long> fo((size_t)n_clips + 1);
     int t_max = 0;
@@ -586,7 +637,7 @@ int dsp_mfcc_frames_device(dsp_mfcc_plan *p, const float *d_frames, long n_frame
     // float64 parallel-form scan over the wave's lanes -- the frame is read once, nothing filtered is written.  This entry
     // point is tolerance-gated (1e-4 of the frame's L-inf norm); the scan equals the serial recurrence to ~1e-13 before the
     // rounding to float.  dsp_butter_bandpass_filter_* keep the bit-exact serial recurrence.
-    if (p->d_scan && p->kernel != DSP_KERNEL_ROW && (reinterpret_cast<uintptr_t>(d_frames) & 15) == 0 && !std::getenv("DSP_AMD_PREFILTER_TWO_PASS")) {
+    if (p->run.per_cu_prefilter > 0 && (reinterpret_cast<uintptr_t>(d_frames) & 15) == 0 && !std::getenv("DSP_AMD_PREFILTER_TWO_PASS")) {
         job.fused_prefilter = true;
         return mfcc_run(p, job);
     }

@@ -151,18 +151,13 @@ static int stop_fused(dsp_mfcc_plan *p, const dsp::StopModelDev &m, const void *
                       const long *offsets, float *d_prob, void *stream)
 {
     if (offsets) { t = 1; clip_stride = 0; }
-    if (const int rc = dsp::refuse_400(p, "classify_signal (the fused clip -> probability kernel and its two-kernel form)")) return rc;
-    // the reference's shape on the default kernel: 512-point, per-frame log, 13 coefficients of 40 mel energies, complete frames
-    if (p->cfg.n_fft != 512 || p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX || p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE ||
-        p->host.dct_split != 4 || p->host.dct_len != 10 || m.n_coef != p->cfg.n_mfcc || m.units[0] > dsp::kStopFusedUnits || !m.fold_a || t <= 0 ||
-        std::getenv("DSP_AMD_STOP_TWO_KERNELS"))
-        return 0;
+    if (const int fused = dsp::plan_accepts(p, dsp::PlanUse::FusedStop, in_kind); fused <= 0) return fused;
+    if (m.n_coef != p->cfg.n_mfcc || m.units[0] > dsp::kStopFusedUnits || !m.fold_a || t <= 0 || std::getenv("DSP_AMD_STOP_TWO_KERNELS")) return 0;
     if (!dsp::input_aligned(d_signal, in_kind, n_clips > 1, clip_stride)) return 0;      // the two-kernel path reports it
-    if (in_kind != 0 && (p->host.mel_gather != 3 || p->cfg.frame_length != 400)) return 0;
     if (m.max_frames <= 0) return capi_fail(DSP_EINVAL, "stop model without frames");
     // ragged: frames past the model's max_frames are dropped (stop_detector.c:26-30): a clip's walk ends there
     const dsp::FusedClips c{.in = d_signal, .in_kind = in_kind, .n_clips = n_clips, .t = t, .clip_stride = clip_stride, .offsets = offsets,
-                            .max_frames = m.max_frames, .per_cu = p->resident_blocks, .stream = stream};
+                            .max_frames = m.max_frames, .stream = stream};
     const dsp::StopNetArgs stop{m, d_prob};
     const int rc = dsp::launch_fused_clips(p, c, nullptr, &stop);
     return rc < 0 ? rc : 1;
@@ -458,13 +453,10 @@ int dsp_speaker_scan_device(dsp_speaker_model *m, const float *d_mfcc, long n_re
 }  // extern "C"
 
 // mfcc_plan.hpp: the front end and the models of a scanner / a stream session
-int dsp::scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg)
+int dsp::scan_front_check(const dsp_mfcc_plan *plan, int in_kind, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg)
 {
     const dsp_mfcc_config &pcfg = plan->cfg;
-    if (const int rc = dsp::refuse_400(plan, "a scanner or stream session")) return rc;
-    if (pcfg.n_fft != 512 || pcfg.log_mode != DSP_LOG_PER_FRAME_MAX || pcfg.framing != DSP_FRAMING_COMPLETE || pcfg.prefilter != DSP_PREFILTER_NONE)
-        return capi_fail(DSP_EINVAL, "scans need a plan whose rows do not depend on the window: n_fft 512, DSP_LOG_PER_FRAME_MAX, DSP_FRAMING_COMPLETE, "
-                                     "no prefilter");
+    if (const int rc = dsp::plan_accepts(plan, dsp::PlanUse::Scan, in_kind)) return rc;
     const int device = plan->device;
     if (stop && (pcfg.n_mfcc != stop->m.n_coef || stop->device != device))
         return capi_fail(DSP_EINVAL, "the stop model needs n_coef = the plan's n_mfcc, on the plan's device");
@@ -531,7 +523,7 @@ int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_mo
     if (!plan) return capi_fail(DSP_EINVAL, "plan is NULL");
     if (!stop && !speaker) return capi_fail(DSP_EINVAL, "a scanner needs a stop model, a speaker model or both");
     if (const int rc = scan_args(cfg, 0)) return rc;
-    if (const int rc = dsp::scan_front_check(plan, stop, speaker, cfg)) return rc;
+    if (const int rc = dsp::scan_front_check(plan, 0, stop, speaker, cfg)) return rc;
     auto *s = new dsp_scanner;
     s->core.plan = plan;
     s->core.device = plan->device;

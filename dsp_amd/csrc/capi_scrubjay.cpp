@@ -136,8 +136,8 @@ int dsp::launch_fused_clips(dsp_mfcc_plan *p, const FusedClips &c, const PoolSvm
     int t = c.t;
     DSP_ON_DEVICE(p->device);
     hipStream_t st = (hipStream_t)c.stream;
-    int blocks = grid(p, c.per_cu, c.n_clips);
-    if (stop) blocks = mfcc512_stop_grid(blocks, stop->m, c.in_kind, p->host.mel_gather, p->cfg.frame_length);      // what the launcher will start
+    int blocks = grid(p, p->run.per_cu_fused, c.n_clips);
+    if (stop) blocks = mfcc512_stop_grid(blocks, stop->m, c.in_kind, p->host.dct_split, p->host.dct_len, p->host.mel_gather, p->cfg.frame_length);      // what the launcher will start
     SpanRing::Lease slot;
     if (ragged) {
         const int rc = ragged_spans(p, c.offsets, c.n_clips, c.max_frames, 4L * blocks, slot, &t, st);
@@ -169,14 +169,7 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
 {
     if (in_kind < 0) return in_kind;
     if (!p || !s || n_clips < 0) return capi_fail(DSP_EINVAL, "bad argument");
-    if (const int rc = dsp::refuse_400(p, "the fused clip -> label path")) return rc;
-    if ((p->cfg.n_fft != 512 && p->cfg.n_fft != 2048) || (p->cfg.log_mode != DSP_LOG_PER_FRAME_MAX && p->cfg.log_mode != DSP_LOG_LOG10_FLOOR) ||
-        p->cfg.prefilter != DSP_PREFILTER_NONE || p->kernel != DSP_KERNEL_WAVE)
-        return capi_fail(DSP_EINVAL, "the fused clip -> label path runs on the 512- and 2048-point wave-per-frame kernels, per-frame log modes");
-    if (in_kind != 0 && !p->aub && (p->cfg.n_fft != 512 || p->cfg.frame_length != 400 || p->host.mel_gather != 3 ||
-                                     !((p->host.dct_split == 4 && p->host.dct_len == 10) || (p->host.dct_split == 2 && p->host.dct_len == 20))))
-        return capi_fail(DSP_EINVAL, "int16 input of the fused clip -> label kernel: the reference framing (n_fft 512, frame 400, 40 mel filters, up to 20 coefficients) "
-                                "or the scrubjay_infer.c front end (dsp_mfcc_scrubjay_infer_config)");
+    if (const int rc = dsp::plan_accepts(p, dsp::PlanUse::FusedLabel, in_kind)) return rc;
     if (s->m.n_features != 2 * p->cfg.n_mfcc || s->m.n_features > 64) return capi_fail(DSP_EINVAL, "SVM n_features must equal 2 * n_mfcc (<= 64)");
     if (p->cfg.n_fft == 512 && s->m.n_sv > dsp::kSvmFused512MaxSv)
         return capi_fail(DSP_EINVAL, "the 512-point fused clip -> label kernel holds at most " + std::to_string(dsp::kSvmFused512MaxSv) +
@@ -190,8 +183,7 @@ static int scrubjay_fused(dsp_mfcc_plan *p, dsp_svm *s, const void *d_signal, in
     if (const int rc = dsp::check_aligned(d_signal, in_kind, !ragged && n_clips > 1, clip_stride)) return rc;
     if (s->device != p->device) return capi_fail(DSP_EINVAL, "plan and SVM live on different devices");
     const dsp::FusedClips c{.in = d_signal, .in_kind = in_kind, .n_clips = n_clips, .t = t, .samples_per_clip = samples_per_clip,
-                            .clip_stride = clip_stride, .offsets = offsets, .max_frames = max_frames,
-                            .per_cu = p->cfg.n_fft == 2048 ? p->resident_blocks_2048_pool : p->resident_blocks, .stream = stream};
+                            .clip_stride = clip_stride, .offsets = offsets, .max_frames = max_frames, .stream = stream};
     const dsp::PoolSvmArgs pool{s->m, d_labels, d_decision, d_prob1, d_feat};
     return dsp::launch_fused_clips(p, c, &pool, nullptr);
 }
@@ -286,16 +278,11 @@ static int svm_scan(dsp_svm *s, const float *d_mfcc, long n, const long *frame_o
     return DSP_OK;
 }
 
-// the plans whose rows do not depend on the window, on the fused clip -> label kernel's front ends (what per-window equality is against)
-static int scan_front_end(const dsp_mfcc_plan *p, const dsp_svm *s)
+// a plan that can be scanned for samples of in_kind (plan_accepts), and an SVM that fits it
+static int scan_front_end(const dsp_mfcc_plan *p, int in_kind, const dsp_svm *s)
 {
-    const dsp_mfcc_config &c = p->cfg;
-    if (const int rc = dsp::refuse_400(p, "a scrub-jay scan")) return rc;
-    if (c.log_mode == DSP_LOG_GLOBAL_REF1) return capi_fail(DSP_EINVAL, "DSP_LOG_GLOBAL_REF1 plans cannot be scanned: the top_db floor spans the window");
-    if (c.prefilter != DSP_PREFILTER_NONE || c.n_fft == 1024)
-        return capi_fail(DSP_EINVAL, "scans run on the ragged MFCC matrix: prefilter plans and n_fft 1024 are not supported");
-    if (p->kernel != DSP_KERNEL_WAVE) return capi_fail(DSP_EINVAL, "scans run on the wave-per-frame kernel (DSP_KERNEL_WAVE), as the fused clip -> label path");
-    if (s->m.n_features != 2 * c.n_mfcc || s->m.n_features > 64) return capi_fail(DSP_EINVAL, "SVM n_features must equal 2 * n_mfcc (<= 64)");
+    if (const int rc = dsp::plan_accepts(p, dsp::PlanUse::ScrubjayScan, in_kind)) return rc;
+    if (s->m.n_features != 2 * p->cfg.n_mfcc || s->m.n_features > 64) return capi_fail(DSP_EINVAL, "SVM n_features must equal 2 * n_mfcc (<= 64)");
     if (s->device != p->device) return capi_fail(DSP_EINVAL, "plan and SVM live on different devices");
     return DSP_OK;
 }
@@ -318,10 +305,7 @@ static int scrubjay_scanner_run(dsp_scrubjay_scanner *s, const void *d_signal, i
     if (!offsets || !d_labels) return capi_fail(DSP_EINVAL, "offsets and d_labels must not be NULL");
     if (n >= (1L << 31)) return capi_fail(DSP_EINVAL, "too many recordings");
     dsp_mfcc_plan *p = s->core.plan;
-    if (const int rc = scan_front_end(p, s->svm)) return rc;
-    if (in_kind != 0 && !p->aub && !(p->cfg.n_fft == 512 && p->host.dct_split == 4 && p->host.dct_len == 10 && p->host.mel_gather == 3))
-        return capi_fail(DSP_EINVAL, "int16 input of the scrub-jay scan: the ragged MFCC matrix takes it on the scrubjay_infer.c front end "
-                                     "(dsp_mfcc_scrubjay_infer_config) and on the 512-point framing with up to 13 coefficients of 40 mel filters");
+    if (const int rc = scan_front_end(p, in_kind, s->svm)) return rc;
     std::lock_guard<std::mutex> lock(s->core.mu);
     const long rows = s->core.mfcc(d_signal, in_kind, n, offsets, " is shorter than one frame: mfcc_stats has no rows to pool (scrubjay_infer.c:55-59)", stream);
     if (rows < 0) return (int)rows;
@@ -376,7 +360,7 @@ int dsp_scrubjay_scanner_create(dsp_mfcc_plan *plan, dsp_svm *svm, const dsp_sca
     *out = nullptr;
     if (!plan || !svm) return capi_fail(DSP_EINVAL, "plan and SVM must not be NULL");
     if (const int rc = dsp::scan_args(cfg, 0)) return rc;
-    if (const int rc = scan_front_end(plan, svm)) return rc;
+    if (const int rc = scan_front_end(plan, 0, svm)) return rc;
     auto *s = new dsp_scrubjay_scanner;
     s->core.plan = plan;
     s->core.device = plan->device;

@@ -138,12 +138,10 @@ int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_spe
     } else if (channels != 1) {
         return capi_fail(DSP_EINVAL, "float samples are mono: channels must be 1");
     }
-    if (const int rc = dsp::scan_front_check(plan, stop, speaker, scan)) return rc;
+    if (const int rc = dsp::scan_front_check(plan, kind, stop, speaker, scan)) return rc;      // the plan's kernel takes this input, as a ragged batch
     const dsp_mfcc_config &pcfg = plan->cfg;
     StreamRule rule;
     if (const int rc = stream_rule(&pcfg, scans ? scan : nullptr, rule)) return rc;
-    if (const int rc = dsp::pcm16_check(plan, kind, true)) return rc;      // the plan's kernel takes this input, as a ragged batch
-    if (const int rc = dsp::ragged_plan_check(plan)) return rc;
     auto s = std::make_unique<dsp_stream_session>();
     s->plan = plan;
     s->stop = stop;
@@ -320,8 +318,8 @@ int dsp_stream_push_device(dsp_stream_session *s, const void *d_pushed, const lo
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[0], (long)s->runs[0].size(), s->d_carry, d_chunks, s->d_stage, g, st));
         if (n_spans > 0) {
             // the ragged MFCC path (no frame cap) over spans of the staging buffer: span c = sample frames [starts[c], starts[c] + lengths[c])
-            int rc = dsp::pcm16_check(s->plan, s->in_kind, true);      // (a kernel switched since the session was created)
-            if (rc == DSP_OK) rc = dsp::mfcc_clips_ragged(s->plan, s->d_stage, s->in_kind, n_spans, s->starts.data(), INT_MAX, rows_out, stream, s->lengths.data());
+            // (refused before anything of its own is enqueued where a kernel was switched since the session was created)
+            const int rc = dsp::mfcc_clips_ragged(s->plan, s->d_stage, s->in_kind, n_spans, s->starts.data(), INT_MAX, rows_out, stream, s->lengths.data());
             if (rc < 0) { s->broken = true; return rc; }
         }
         DSP_STREAM_HIP(dsp::launch_stream_copy(d_run[1], (long)s->runs[1].size(), s->d_stage, d_chunks, s->d_carry, g, st));

@@ -816,10 +816,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DSP_WAVES_P
 
 // -----------------------------------------------------------------------------
 
-// Instantiations: (DCT_SPLIT, DCT_LEN, GATHER) x FLEN x TILE x CLIPS for float input; PCM16 input (always clips, tile
-// epilogue) for the reference's shape (13 x 40) only.  FLEN = 400 (the reference's framing, -5 % in clip mode) exists for the
-// shapes of BASELINE configs 4 and 5; other frame lengths below 512 take the run-time predicate (FLEN = 0).
-#define DSP_FOR_SHAPES(X) X(4, 10, 3) X(4, 10, 6) X(4, 16, 3) X(4, 16, 6) X(2, 20, 3) X(2, 20, 6)
+// Instantiations: the forms of DSP_MFCC512_FORMS (mfcc_kernels.hpp) and nothing else -- per shape float input x FLEN {512, 0, 400 where
+// listed} x TILE x {frames, clips, ragged}, the fused label kernel, and the int16 and stop forms the shape's row names.
+#define DSP_FOR_SHAPES(X) DSP_MFCC512_FORMS(X)
+template <int S, int L, int G>
+constexpr Mfcc512Form kForm = *mfcc512_form(S, L, G);
 
 // S, L: DCT_SPLIT, DCT_LEN of the instantiation (shapes whose MFMA A operand does not fit registers keep it in LDS)
 template <int S, int L>
@@ -837,13 +838,6 @@ static int stop_small_floats(const StopModelDev &m)
     return n;
 }
 
-template <int S, int L, int G>
-constexpr bool kHas400 = (S == 4 && L == 10 && G == 3) || (S == 2 && L == 20 && G == 3);
-
-// 512 -> 512, 400 -> 400 where instantiated, anything else -> 0 (run-time predicate)
-template <int S, int L, int G>
-static int flen_of(int frame_len) { return frame_len == 512 ? 512 : (frame_len == 400 && kHas400<S, L, G> ? 400 : 0); }
-
 template <int S, int L, int G, int FLEN, int IN, int TILE>
 static void launch_flen(const Mfcc512Args &args, bool clips, dim3 g, dim3 b, size_t lds, hipStream_t stream)
 {
@@ -857,93 +851,102 @@ static hipError_t launch_one(const Mfcc512Args &args, bool clips, int blocks, hi
 {
     const size_t lds = lds_bytes<S, L>(TILE);
     const dim3 g(blocks), b(256);
-    const int flen = flen_of<S, L, G>(args.frame_len);
-    if (flen == 512) launch_flen<S, L, G, 512, IN, TILE>(args, clips, g, b, lds, stream);
-    else if (flen == 400) { if constexpr (kHas400<S, L, G>) launch_flen<S, L, G, 400, IN, TILE>(args, clips, g, b, lds, stream); }
-    else launch_flen<S, L, G, 0, IN, TILE>(args, clips, g, b, lds, stream);
+    // FLEN: 512, 400 where instantiated, anything else the run-time predicate (0)
+    if (args.frame_len == 512) launch_flen<S, L, G, 512, IN, TILE>(args, clips, g, b, lds, stream);
+    else if constexpr (kForm<S, L, G>.flen400) {
+        if (args.frame_len == 400) launch_flen<S, L, G, 400, IN, TILE>(args, clips, g, b, lds, stream);
+        else launch_flen<S, L, G, 0, IN, TILE>(args, clips, g, b, lds, stream);
+    } else launch_flen<S, L, G, 0, IN, TILE>(args, clips, g, b, lds, stream);
     return hipGetLastError();
+}
+
+// The fused clip kernels, POOL = 1 (the SVM's label) or 2 (the stop net's probability): the form launch_mfcc512_pool / _stop start for
+// this shape and input with its LDS bytes (small_floats: the model's share), or no kernel -- exactly where mfcc512_has_form says no
+struct FusedForm { void (*kernel)(const Mfcc512Args); size_t lds; };
+template <int S, int L, int G, int POOL>
+static FusedForm fused_form_one(int in_kind, int frame_len, int small_floats)
+{
+    constexpr Mfcc512Form F = kForm<S, L, G>;
+    constexpr int F16 = POOL == 1 ? F.label_pcm16_flen : F.stop_pcm16_flen;
+    const size_t lds = lds_bytes<S, L>(true, POOL, small_floats);
+    if (in_kind != 0) {
+        if constexpr (F16 != 0) {
+            if (frame_len == F16 && in_kind == 1) return {mfcc512_wave_kernel<S, L, G, F16, 1, 1, true, POOL>, lds};
+            if (frame_len == F16 && in_kind == 2) return {mfcc512_wave_kernel<S, L, G, F16, 2, 1, true, POOL>, lds};
+            if (frame_len == F16 && in_kind == 3) return {mfcc512_wave_kernel<S, L, G, F16, 3, 1, true, POOL>, lds};
+        }
+    } else if constexpr (POOL == 1 || F.stop) {
+        if constexpr (F.flen400) { if (frame_len == 400) return {mfcc512_wave_kernel<S, L, G, 400, 0, 1, true, POOL>, lds}; }
+        if constexpr (POOL == 1) { if (frame_len == 512) return {mfcc512_wave_kernel<S, L, G, 512, 0, 1, true, 1>, lds}; }      // (the stop kernel takes 512 by the run-time predicate)
+        return {mfcc512_wave_kernel<S, L, G, 0, 0, 1, true, POOL>, lds};
+    }
+    return {nullptr, 0};
+}
+
+template <int POOL>
+static FusedForm fused_form_of(int dct_split, int dct_len, int gather, int in_kind, int frame_len, int small_floats)
+{
+#define DSP_FUSED_FORM(S, L, G, ...) \
+    if (dct_split == S && dct_len == L && gather == G) return fused_form_one<S, L, G, POOL>(in_kind, frame_len, small_floats);
+    DSP_FOR_SHAPES(DSP_FUSED_FORM)
+#undef DSP_FUSED_FORM
+    return {nullptr, 0};
 }
 
 hipError_t launch_mfcc512_pool(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream)
 {
-    if (args.frames_per_clip <= 0 || args.chunk != args.frames_per_clip || args.log_mode != 0 || args.in_kind < 0 || args.in_kind > 3 || !args.pool.labels ||
-        args.pool.svm.n_features != 2 * args.n_mfcc || args.pool.svm.n_features > 64 || args.pool.svm.n_sv < 1 || args.pool.svm.n_sv > kSvmFused512MaxSv)
+    const SvmModelDev &svm = args.pool.svm;
+    if (args.frames_per_clip <= 0 || args.chunk != args.frames_per_clip || args.log_mode != 0 || !args.pool.labels ||
+        !mfcc512_has_form(Mfcc512Use::Label, dct_split, dct_len, gather, args.frame_len, args.in_kind, true) ||
+        svm.n_features != 2 * args.n_mfcc || svm.n_features > 64 || svm.n_sv < 1 || svm.n_sv > kSvmFused512MaxSv)
         return hipErrorInvalidConfiguration;
-    const dim3 g(blocks), b(256);
-    if (args.in_kind != 0) {
-        // int16 PCM in the fused clip -> label kernel: the reference framing (frame 400) on the shapes of 13 and 20
-        // coefficients of 40 mel energies -- what scrubjay_infer.c's and stop_detector.c's callers decode from their WAV files
-#define DSP_LAUNCH_POOL_PCM(S, L, G)                                                                                        \
-        if (dct_split == S && dct_len == L && gather == G && args.frame_len == 400) {                                        \
-            const size_t lds = lds_bytes<S, L>(true, 1, 2 * args.pool.svm.n_features + args.pool.svm.n_sv);                 \
-            if (args.in_kind == 1) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 400, 1, 1, true, 1>), g, b, lds, stream, args);      \
-            else if (args.in_kind == 2) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 400, 2, 1, true, 1>), g, b, lds, stream, args); \
-            else hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 400, 3, 1, true, 1>), g, b, lds, stream, args);          \
-            return hipGetLastError();                                                                                       \
-        }
-        DSP_LAUNCH_POOL_PCM(4, 10, 3)
-        DSP_LAUNCH_POOL_PCM(2, 20, 3)
-#undef DSP_LAUNCH_POOL_PCM
-        return hipErrorInvalidConfiguration;
-    }
-#define DSP_LAUNCH_POOL(S, L, G)                                                                                            \
-    if (dct_split == S && dct_len == L && gather == G) {                                                                    \
-        const size_t lds = lds_bytes<S, L>(true, 1, 2 * args.pool.svm.n_features + args.pool.svm.n_sv);                    \
-        const int flen = flen_of<S, L, G>(args.frame_len);                                                                  \
-        if (flen == 512) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 512, 0, 1, true, 1>), g, b, lds, stream, args);   \
-        else if (flen == 400) {                                                                                             \
-            if constexpr (kHas400<S, L, G>) hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 400, 0, 1, true, 1>), g, b, lds, stream, args); \
-        } else hipLaunchKernelGGL((mfcc512_wave_kernel<S, L, G, 0, 0, 1, true, 1>), g, b, lds, stream, args);             \
-        return hipGetLastError();                                                                                           \
-    }
-    DSP_FOR_SHAPES(DSP_LAUNCH_POOL)
-#undef DSP_LAUNCH_POOL
-    return hipErrorInvalidConfiguration;
-}
-
-typedef void (*StopKernel)(const Mfcc512Args);
-static StopKernel stop_kernel_of(int in_kind, int gather, int frame_len)
-{
-    if (in_kind == 1) return mfcc512_wave_kernel<4, 10, 3, 400, 1, 1, true, 2>;       // int16 PCM: main_test.c's reader feeds classify_signal
-    if (in_kind == 2) return mfcc512_wave_kernel<4, 10, 3, 400, 2, 1, true, 2>;
-    if (in_kind == 3) return mfcc512_wave_kernel<4, 10, 3, 400, 3, 1, true, 2>;
-    if (gather == 3 && frame_len == 400) return mfcc512_wave_kernel<4, 10, 3, 400, 0, 1, true, 2>;
-    if (gather == 3) return mfcc512_wave_kernel<4, 10, 3, 0, 0, 1, true, 2>;
-    if (gather == 6) return mfcc512_wave_kernel<4, 10, 6, 0, 0, 1, true, 2>;
-    return nullptr;
+    const FusedForm f = fused_form_of<1>(dct_split, dct_len, gather, args.in_kind, args.frame_len, 2 * svm.n_features + svm.n_sv);
+    if (!f.kernel) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(f.kernel, dim3(blocks), dim3(256), f.lds, stream, args);
+    return hipGetLastError();
 }
 
 // the blocks launch_mfcc512_stop will start for a caller's count: at most what the chip holds with this variant's LDS (the host lays
 // ragged batches out for that many wavefronts)
-int mfcc512_stop_grid(int blocks, const StopModelDev &m, int in_kind, int gather, int frame_len)
+int mfcc512_stop_grid(int blocks, const StopModelDev &m, int in_kind, int dct_split, int dct_len, int gather, int frame_len)
 {
-    const StopKernel kernel = stop_kernel_of(in_kind, gather, frame_len);
-    if (!kernel) return blocks;
-    const size_t lds = lds_bytes<4, 10>(true, 2, stop_small_floats(m));
+    const FusedForm f = fused_form_of<2>(dct_split, dct_len, gather, in_kind, frame_len, stop_small_floats(m));
+    if (!f.kernel) return blocks;
     int per_cu = 0, dev = 0, n_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f.kernel, 256, f.lds) != hipSuccess || per_cu < 1) per_cu = 1;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0)
         blocks = std::min(blocks, per_cu * n_cu);
     return std::max(blocks, 1);
 }
 
-// classify_signal fused (POOL = 2): the reference's shape only (13 coefficients of 40 mel energies: DCT_SPLIT 4, DCT_LEN 10)
+// classify_signal fused (POOL = 2)
 hipError_t launch_mfcc512_stop(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream)
 {
     const StopModelDev &m = args.stop.m;
-    if (args.frames_per_clip <= 0 || args.chunk != args.frames_per_clip || args.log_mode != 0 || args.in_kind < 0 || args.in_kind > 3 || !args.stop.prob ||
-        (args.in_kind != 0 && !(gather == 3 && args.frame_len == 400)) || dct_split != 4 || dct_len != 10 || m.n_coef != args.n_mfcc || m.n_coef > 16 || m.units[0] < 1 || m.units[0] > kStopFusedUnits ||
-        !m.fold_a || !m.pad_b)
+    if (args.frames_per_clip <= 0 || args.chunk != args.frames_per_clip || args.log_mode != 0 || !args.stop.prob ||
+        !mfcc512_has_form(Mfcc512Use::Stop, dct_split, dct_len, gather, args.frame_len, args.in_kind, true) ||
+        m.n_coef != args.n_mfcc || m.n_coef > 16 || m.units[0] < 1 || m.units[0] > kStopFusedUnits || !m.fold_a || !m.pad_b)
         return hipErrorInvalidConfiguration;
     for (int l = 1; l < 4; ++l)
         if (m.units[l] < 1 || m.units[l] > kStopMaxUnits) return hipErrorInvalidConfiguration;
-    const size_t lds = lds_bytes<4, 10>(true, 2, stop_small_floats(m));
-    const StopKernel kernel = stop_kernel_of(args.in_kind, gather, args.frame_len);
-    if (!kernel) return hipErrorInvalidConfiguration;
+    const FusedForm f = fused_form_of<2>(dct_split, dct_len, gather, args.in_kind, args.frame_len, stop_small_floats(m));
+    if (!f.kernel) return hipErrorInvalidConfiguration;
     // persistent-style grid: the blocks the chip really holds with this variant's LDS (the caller's count is the plain kernel's)
-    blocks = mfcc512_stop_grid(blocks, m, args.in_kind, gather, args.frame_len);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, stream, args);
+    blocks = mfcc512_stop_grid(blocks, m, args.in_kind, dct_split, dct_len, gather, args.frame_len);
+    hipLaunchKernelGGL(f.kernel, dim3(blocks), dim3(256), f.lds, stream, args);
     return hipGetLastError();
+}
+
+template <int S, int L, int G>
+static hipError_t launch_rows(const Mfcc512Args &args, bool clips, int blocks, hipStream_t stream, bool tile)
+{
+    if constexpr (kForm<S, L, G>.rows_pcm16) {      // int16: always clips, tile epilogue
+        if (args.in_kind == 1) return launch_one<S, L, G, 1, 1>(args, true, blocks, stream);
+        if (args.in_kind == 2) return launch_one<S, L, G, 2, 1>(args, true, blocks, stream);
+        if (args.in_kind == 3) return launch_one<S, L, G, 3, 1>(args, true, blocks, stream);
+    }
+    if (args.in_kind != 0) return hipErrorInvalidConfiguration;
+    return tile ? launch_one<S, L, G, 0, 1>(args, clips, blocks, stream) : launch_one<S, L, G, 0, 0>(args, clips, blocks, stream);
 }
 
 hipError_t launch_mfcc512(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks,
@@ -952,17 +955,10 @@ hipError_t launch_mfcc512(const Mfcc512Args &args, int dct_split, int dct_len, i
     const bool clips = args.frames_per_clip > 0 || args.spans;
     if (tile && (args.log_mode != 0 || args.chunk % 8 != 0)) return hipErrorInvalidConfiguration;
     if (args.spans && args.n_clips <= 0) return hipErrorInvalidConfiguration;
-    if (args.in_kind != 0) {
-        if (!(dct_split == 4 && dct_len == 10 && gather == 3) || !tile || !clips) return hipErrorInvalidConfiguration;
-        if (args.in_kind == 1) return launch_one<4, 10, 3, 1, 1>(args, true, blocks, stream);
-        if (args.in_kind == 2) return launch_one<4, 10, 3, 2, 1>(args, true, blocks, stream);
-        if (args.in_kind == 3) return launch_one<4, 10, 3, 3, 1>(args, true, blocks, stream);
+    if (!mfcc512_has_form(clips ? Mfcc512Use::Clips : Mfcc512Use::Frames, dct_split, dct_len, gather, args.frame_len, args.in_kind, tile))
         return hipErrorInvalidConfiguration;
-    }
-#define DSP_LAUNCH(S, L, G)                                                                  \
-    if (dct_split == S && dct_len == L && gather == G)                                       \
-        return tile ? launch_one<S, L, G, 0, 1>(args, clips, blocks, stream)                 \
-                    : launch_one<S, L, G, 0, 0>(args, clips, blocks, stream);
+#define DSP_LAUNCH(S, L, G, ...) \
+    if (dct_split == S && dct_len == L && gather == G) return launch_rows<S, L, G>(args, clips, blocks, stream, tile);
     DSP_FOR_SHAPES(DSP_LAUNCH)
 #undef DSP_LAUNCH
     return hipErrorInvalidConfiguration;
@@ -1040,7 +1036,7 @@ static int occupancy_one(bool full)
 // resident 256-thread blocks per CU for the instantiation a plan will launch
 int mfcc512_blocks_per_cu(int dct_split, int dct_len, int gather, bool full, bool tile)
 {
-#define DSP_OCC(S, L, G) \
+#define DSP_OCC(S, L, G, ...) \
     if (dct_split == S && dct_len == L && gather == G) return tile ? occupancy_one<S, L, G, 1>(full) : occupancy_one<S, L, G, 0>(full);
     DSP_FOR_SHAPES(DSP_OCC)
 #undef DSP_OCC

@@ -70,6 +70,56 @@ struct Mfcc512Args {
     StopNetArgs stop{};            // only read by the stop-net instantiations (launch_mfcc512_stop)
 };
 
+// The forms of mfcc512_wave_kernel (mfcc_kernels.hip), one row per shape: THE list.  The launchers instantiate a form exactly when it
+// is listed here and the host asks mfcc512_has_form before it promises a caller anything.  Every shape has float input at FLEN 512 and
+// at FLEN 0 (a run-time predicate for frame lengths below 512), independent frames, clips and ragged batches, tile and per-frame
+// epilogue, and the fused clip -> label kernel; the columns say what a shape has beyond that.
+//   SPLIT, LEN, GATHER  the shape build_lane_tables_512 selects (LaneTables512::dct_split, dct_len, mel_gather)
+//   FLEN400    a compile-time FLEN 400 (the reference's framing, -5 % in clip mode): the shapes of BASELINE configs 4 and 5
+//   ROWS16     plain MFCC rows take int16 PCM: clips and ragged batches on the tile epilogue, every FLEN the shape has
+//   LABEL16    the frame length at which the fused clip -> label kernel takes int16 (0: float only): what scrubjay_infer.c's and
+//              stop_detector.c's callers decode from their WAV files
+//   STOP       the fused clip -> stop-word kernel exists (float: FLEN 400 where the shape has it, FLEN 0 otherwise)
+//   STOP16     the frame length at which it takes int16 (0: float only): main_test.c's reader in front of classify_signal
+//                       SPLIT LEN GATHER FLEN400 ROWS16 LABEL16 STOP  STOP16
+#define DSP_MFCC512_FORMS(X)                              \
+    X(4, 10, 3, true, true, 400, true, 400)               \
+    X(4, 10, 6, false, false, 0, true, 0)                 \
+    X(4, 16, 3, false, false, 0, false, 0)                \
+    X(4, 16, 6, false, false, 0, false, 0)                \
+    X(2, 20, 3, true, false, 400, false, 0)               \
+    X(2, 20, 6, false, false, 0, false, 0)
+
+struct Mfcc512Form { int split, len, gather; bool flen400, rows_pcm16; int label_pcm16_flen; bool stop; int stop_pcm16_flen; };
+#define DSP_FORM_ROW(...) {__VA_ARGS__},
+constexpr Mfcc512Form kMfcc512Forms[] = {DSP_MFCC512_FORMS(DSP_FORM_ROW)};
+#undef DSP_FORM_ROW
+
+constexpr const Mfcc512Form *mfcc512_form(int split, int len, int gather)
+{
+    for (const Mfcc512Form &f : kMfcc512Forms)
+        if (f.split == split && f.len == len && f.gather == gather) return &f;
+    return nullptr;
+}
+
+// what a launch is for: independent frames or clips (ragged batches included) into MFCC rows, clip -> label, clip -> P(stop)
+enum class Mfcc512Use { Frames, Clips, Label, Stop };
+
+// "this form exists": in_kind as Mfcc512Args::in_kind; tile: the 16-frame tile epilogue (the fused kernels have no other).  The launchers
+// below return hipErrorInvalidConfiguration for a form exactly when this says no
+constexpr bool mfcc512_has_form(Mfcc512Use use, int split, int len, int gather, int frame_len, int in_kind, bool tile)
+{
+    const Mfcc512Form *f = mfcc512_form(split, len, gather);
+    if (!f || in_kind < 0 || in_kind > 3) return false;
+    if (use == Mfcc512Use::Frames) return in_kind == 0;
+    if (use == Mfcc512Use::Clips) return in_kind == 0 || (f->rows_pcm16 && tile);
+    const int flen16 = use == Mfcc512Use::Label ? f->label_pcm16_flen : f->stop_pcm16_flen;
+    return tile && (in_kind == 0 ? use == Mfcc512Use::Label || f->stop : flen16 != 0 && frame_len == flen16);
+}
+// the ROWS16 shapes in a caller's terms, for the refusal that names them (kept beside the list: it restates that column)
+constexpr const char *kMfcc512RowsPcm16Shapes = "n_mfcc <= 16 with n_mels <= 40 and no mel filter wider than 36 FFT bins (kernel shape 4 x 10, gather 3: "
+                                                "dsp_mfcc_default_config's)";
+
 // clip_floor[c] = max_t frame_max[c][t] - top_db
 hipError_t launch_clip_floor(const float *frame_max, long n_clips, int frames_per_clip, float top_db, float *clip_floor,
                              hipStream_t stream);
@@ -84,8 +134,8 @@ hipError_t launch_mfcc512(const Mfcc512Args &args, int dct_split, int dct_len, i
                           hipStream_t stream, bool tile);
 // fused clip -> label path: args.chunk must equal args.frames_per_clip, args.out is not written
 hipError_t launch_mfcc512_pool(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream);
-// fused clip -> stop-word probability (reference shape only: 13 coefficients, 40 mel): args.chunk == args.frames_per_clip, args.stop set
-int mfcc512_stop_grid(int blocks, const StopModelDev &m, int in_kind, int gather, int frame_len);      // the grid launch_mfcc512_stop starts for a caller's count
+// fused clip -> stop-word probability (the STOP shapes of the list): args.chunk == args.frames_per_clip, args.stop set
+int mfcc512_stop_grid(int blocks, const StopModelDev &m, int in_kind, int dct_split, int dct_len, int gather, int frame_len);      // the grid launch_mfcc512_stop starts for a caller's count
 hipError_t launch_mfcc512_stop(const Mfcc512Args &args, int dct_split, int dct_len, int gather, int blocks, hipStream_t stream);
 hipError_t launch_mfcc1024(const Mfcc512Args &args, const GenTables1024 *tables, int blocks, hipStream_t stream);
 int mfcc1024_blocks_per_cu(bool full);

@@ -13,31 +13,40 @@
 // the jobs below are filled field by name, MfccJob{.in = ..., .n_frames = ...}: designated initialisers, which this compiler takes in C++17
 #pragma clang diagnostic ignored "-Wc++20-designator"
 
+namespace dsp {
+
+// The kernel a plan runs and its grid, resolved once: by dsp_mfcc_plan_create and again by dsp_mfcc_plan_set_kernel (capi.cpp).
+struct PlanKernel {
+    // FFT512_TILE: the wave-per-frame kernel's 16-frame tile epilogue (DSP_KERNEL_WAVE, per-frame log mode); FFT512_FRAME: its per-frame
+    // epilogue (DSP_KERNEL_WAVE_FRAME, or DSP_LOG_GLOBAL_REF1); FFT1024_WAVE: the register-resident kernel (<= 3 mel chunk slots per lane
+    // and no DSP_KERNEL_ROW); FFT1024_ROW: the general Stockham kernel; FFT2048_AUBIO: magnitude spectrum, log10 floor or stream framing
+    enum Family { FFT400, FFT512_TILE, FFT512_FRAME, FFT1024_WAVE, FFT1024_ROW, FFT2048, FFT2048_AUBIO } family = FFT512_TILE;
+    int granule = 1;      // a chunk holds a whole number of these frames (tile: half-tiles of 8)
+    // resident 256-thread blocks per CU (occupancy queries): the plain entry; FFT1024_WAVE's one-pass prefilter (0: the plan has none);
+    // the fused clip kernels, label and stop (0: the family has none)
+    int per_cu = 4, per_cu_prefilter = 0, per_cu_fused = 0;
+};
+
+}  // namespace dsp
+
 struct dsp_mfcc_plan {
     dsp_mfcc_config cfg;
     int device = 0;
     int n_cu = 0;
-    int resident_blocks = 4; // 256-thread blocks one CU holds (occupancy query), tile epilogue kernel
-    int resident_blocks_frame = 4;   // same, per-frame epilogue kernel
-    int blocks_per_cu = 0;   // 0 = default (= resident_blocks)
+    int kernel = DSP_KERNEL_WAVE;   // what dsp_mfcc_plan_set_kernel asked for
+    dsp::PlanKernel run;            // what that means on this plan
+    int blocks_per_cu = 0;   // 0 = default (= run.per_cu*)
     int chunk = 0;           // 0 = default
     dsp::LaneTables512 host;
     dsp::DeviceBuf<dsp::LaneTables512> d_tables;
     dsp::DeviceBuf<dsp::GenTables1024> d_gen_tables;   // n_fft = 1024
+    bool wave1024_fits = false;                        // its filterbank fits the wave kernel (<= 3 mel chunk slots per lane)
     dsp::DeviceBuf<dsp::GenTables2048> d_tables2048;   // n_fft = 2048
-    int resident_blocks_2048 = 2, resident_blocks_2048_pool = 2;
     dsp::DeviceBuf<dsp::Tables400> d_tables400;        // n_fft = 400
-    int resident_blocks_400 = 4;
-    int resident_blocks_gen = 3;
-    int gen_slots = 0;                            // mel chunk slots per lane the 1024-point tables use (<= 3: wave kernel)
-    int resident_blocks_gen_wave = 2;
     dsp::DeviceBuf<dsp::PrefilterScan> d_scan;    // prefilter fused into the 1024-point wave kernel (full frames): its tables
     int scan_steps[4] = {6, 6, 6, 6};             // host copy of PrefilterScan::c_steps (picks the kernel instantiation)
-    int resident_blocks_gen_pre = 2;
     dsp::DeviceBuf<float> d_filtered;             // per-frame prefilter output (sub-batch)
     dsp::DeviceBuf<float> d_frame_max, d_clip_floor;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
-    int kernel = DSP_KERNEL_WAVE;
-    bool aub = false;                             // n_fft = 2048 with aubio's semantics (magnitude spectrum, log10 floor or stream framing)
     // staging for the host-pointer entry points
     dsp::DeviceBuf<float> d_in, d_out;
     // Guards the plan's workspaces (d_filtered, d_frame_max / d_clip_floor, d_in / d_out) while a call reserves them and
@@ -93,16 +102,14 @@ int mfcc_clips(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, in
 // capi.cpp: dsp_mfcc_clips_ragged_device / _pcm16_device by in_kind; the frames of the longest clip.  lengths: spans (RaggedBatch)
 int mfcc_clips_ragged(dsp_mfcc_plan *p, const void *d_in, int in_kind, long n_clips, const long *offsets, int max_frames, float *d_out, void *stream,
                       const long *lengths = nullptr);
-int ragged_plan_check(const dsp_mfcc_plan *p);      // the plans mfcc_clips_ragged takes, or DSP_EINVAL
-// int16 input on a plan whose kernel has no PCM16 load: DSP_EINVAL (clip_mode: clips or a ragged batch, not independent frames)
-int pcm16_check(const dsp_mfcc_plan *p, int in_kind, bool clip_mode);
-
-// n_fft 400 plans (dsp_mfcc_speaker_config) run float frames, clips and ragged batches on their own kernel and nothing else: `what` names
-// the entry that refuses one.  DSP_OK for every other plan
-inline int refuse_400(const dsp_mfcc_plan *p, const char *what)
-{
-    return p->cfg.n_fft != 400 ? DSP_OK : capi_fail(DSP_EINVAL, std::string(what) + " is not implemented for n_fft 400 plans (float frames, clips and ragged batches only)");
-}
+// What a plan is asked to do, and the one place that says whether it can (capi.cpp): the plan's family and configuration against the
+// use, a 512-point plan's shape against the kernel's list of forms (mfcc512_has_form).  Checks on a model stay with the model's owner.
+// Frames / Clips / Ragged: MFCC rows of independent frames, equal clips, a ragged batch; FusedLabel / FusedStop: the clip -> label and
+// clip -> P(stop) kernels; Scan: a stop / speaker scanner or a stream session; ScrubjayScan: an SVM scanner.
+enum class PlanUse { Frames, Clips, Ragged, FusedLabel, FusedStop, Scan, ScrubjayScan };
+// DSP_OK, or DSP_EINVAL with the reason.  FusedStop has a two-kernel path behind it: 1 (the fused form exists), 0 (none: take the other
+// path) or DSP_EINVAL (neither path takes this plan)
+int plan_accepts(const dsp_mfcc_plan *p, PlanUse use, int in_kind);
 
 // the kernels' 8-byte frame loads (4-byte for mono int16); strided: clip starts clip_stride apart are read
 inline bool input_aligned(const void *d_in, int in_kind, bool strided, long clip_stride)
@@ -143,7 +150,6 @@ struct FusedClips {
     long clip_stride = 0;
     const long *offsets = nullptr;
     int max_frames = 0;
-    int per_cu = 0;      // the kernel's resident blocks per CU
     void *stream = nullptr;
 };
 // capi_scrubjay.cpp: the one launch of the fused clip kernels, on a plan and a batch its caller has accepted (input_aligned included): the
@@ -151,9 +157,9 @@ struct FusedClips {
 int launch_fused_clips(dsp_mfcc_plan *p, const FusedClips &c, const PoolSvmArgs *pool, const StopNetArgs *stop);
 
 // capi_consumers.cpp (owner of the models): what dsp_scanner_create and dsp_stream_session_create ask of a plan and of the models they
-// borrow -- rows that depend on their own samples only, n_coef / d = the plan's n_mfcc on the plan's device, a stop window that fits the
+// borrow -- plan_accepts(Scan) for samples of in_kind, n_coef / d = the plan's n_mfcc on the plan's device, a stop window that fits the
 // scan kernel's LDS.  stop / speaker may be NULL (cfg is read only when one is given).  DSP_OK or DSP_EINVAL.
-int scan_front_check(const dsp_mfcc_plan *plan, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg);
+int scan_front_check(const dsp_mfcc_plan *plan, int in_kind, const dsp_stop_model *stop, const dsp_speaker_model *speaker, const dsp_scan_config *cfg);
 
 // What the scanners share (dsp_scanner of capi_consumers.cpp, where mfcc() lives; dsp_scrubjay_scanner of capi_scrubjay.cpp): PCM -> the recordings' ragged MFCC matrix in the scanner's own workspace.
 struct ScannerCore {

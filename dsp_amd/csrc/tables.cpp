@@ -714,8 +714,8 @@ bool build_lane_tables_512(const dsp_mfcc_config &cfg, LaneTables512 &t, std::st
 
     // DCT: split the n_mels-long dot product over 4 (or 2) neighbouring lanes.
     t.dct_split = cfg.n_mfcc <= 16 ? 4 : 2;
-    // the kernel is instantiated for (split, len) in {(4,10), (4,16), (2,20)}:
-    // take the smallest instantiated length that covers n_mels (extra weights are 0)
+    // take the smallest length the kernel is instantiated for (DSP_MFCC512_FORMS, mfcc_kernels.hpp) that covers n_mels
+    // (extra weights are 0)
     const int need = (cfg.n_mels + t.dct_split - 1) / t.dct_split;
     int len;
     if (t.dct_split == 4 && need <= 10) len = 10;

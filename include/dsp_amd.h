@@ -165,7 +165,9 @@ int dsp_fft_real_forward_host(const float *in_time, long n_frames, int frame_len
  * (2fa/audio/word/c/main_test.c:198-203); stereo channel 0 (donut-classifier/classifier.c:292-297)
  * or the channel average 0.5(L/32768 + R/32768) (main_test.c:205-217).  samples_per_clip and
  * clip_stride count samples PER CHANNEL.  Halves (mono) the HBM bytes of the float path.
- * Plans: n_fft 512 (per-frame log mode) and dsp_mfcc_scrubjay_infer_config (n_fft 2048).     */
+ * Plans: dsp_mfcc_scrubjay_infer_config (n_fft 2048), and n_fft 512 on the default kernel in the
+ * per-frame log mode where the kernel's shape has an int16 form: n_mfcc <= 16 with n_mels <= 40 and
+ * no mel filter wider than 36 FFT bins (dsp_mfcc_default_config's shape).  Elsewhere DSP_EINVAL.  */
 enum { DSP_STEREO_CHANNEL0 = 0, DSP_STEREO_AVERAGE = 1 };
 int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long n_clips, int samples_per_clip,
                                 long clip_stride, int channels, int stereo_mode, float *d_out, int max_frames,
@@ -179,8 +181,9 @@ int dsp_mfcc_clips_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long 
  * The matrices lie back to back, frame-major: clip c's frames are d_out[frame_offsets[c] .. frame_offsets[c + 1])[n_mfcc], each row
  * bit for bit what dsp_mfcc_clips_device (_pcm16_device) returns for that clip alone with the same plan and max_frames; under
  * DSP_LOG_GLOBAL_REF1 the top_db floor is taken over each clip's own frames.  Plans: n_fft 512 (wave-per-frame kernels, both log
- * modes), n_fft 2048 (dsp_mfcc_scrubjay_infer_config and the variants dsp_mfcc_clips_device accepts) and n_fft 400; PCM16 where
- * dsp_mfcc_clips_pcm16_device takes it.  n_fft 1024 and prefilter plans: DSP_EINVAL.  Returns the frame count of the longest clip.
+ * modes), n_fft 2048 (dsp_mfcc_scrubjay_infer_config and the variants dsp_mfcc_clips_device accepts) and n_fft 400; PCM16 on exactly
+ * the plans dsp_mfcc_clips_pcm16_device takes it on (the kernel shape included).  n_fft 1024 and prefilter plans: DSP_EINVAL.  Returns
+ * the frame count of the longest clip.
  *
  * dsp_mfcc_ragged_frame_offsets (host only, no GPU): frame_offsets[n_clips + 1] = prefix sums of
  * dsp_mfcc_frames_for(cfg, offsets[c + 1] - offsets[c], max_frames); returns the total frame count (>= 0) or a negative DSP_E* code. */
@@ -605,8 +608,9 @@ int dsp_scrubjay_scanner_run_pcm16_device(dsp_scrubjay_scanner *scanner, const i
  * the scanner's wording otherwise) with hop_length <= frame_length; hop_frames <= window_frames (a stream skips no input); stop model,
  * speaker model, both (n_coef / d = the plan's n_mfcc, on the plan's device, a stop window that fits the scan kernel) or neither -- then
  * the session yields rows only and `scan` is not read.  pcm16 = 0: float samples (channels must be 1); pcm16 != 0: int16 PCM, channels
- * and stereo_mode as dsp_mfcc_clips_ragged_pcm16_device (mono, stereo channel 0, stereo average).  The format is fixed at creation: the
- * carried samples stay in the caller's format and are decoded by the kernel that decodes a whole recording.
+ * and stereo_mode as dsp_mfcc_clips_ragged_pcm16_device (mono, stereo channel 0, stereo average), on the plans that entry takes int16
+ * on (DSP_EINVAL here otherwise, not at the first push).  The format is fixed at creation: the carried samples stay in the caller's
+ * format and are decoded by the kernel that decodes a whole recording.
  *
  * dsp_stream_push_plan (host only, no GPU, no session): what a push would emit.  received[n_streams] = samples per stream before the
  * push (NULL: all zero), chunk_offsets[n_streams + 1] = the chunks back to back (as dsp_mfcc_clips_ragged_device's offsets).  Fills

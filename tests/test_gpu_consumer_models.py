@@ -287,7 +287,7 @@ def test_outside_the_fused_shape(torch_cuda, i):
     _check_p(got, [p for p, _b in want], [b for _p, b in want], f"model {i} {STOP_MODELS[i]} uniform batch")
 
 
-# the fused epilogue's other two float instantiations (stop_kernel_of, mfcc_kernels.hip): gather 6 and gather 3 with the run-time
+# the fused epilogue's other two float instantiations (fused_form_one, mfcc_kernels.hip): gather 6 and gather 3 with the run-time
 # frame length -- name -> (default_config overrides, (dct_split, dct_len, mel_gather) the plan must select)
 FUSED_OTHER_SHAPES = {"mels32": (dict(n_mels=32), (4, 10, 6)), "flen320": (dict(frame_length=320), (4, 10, 3))}
 
