@@ -268,6 +268,30 @@ int dsp_mfcc400_tables(const dsp_mfcc_config *cfg, void *out, int size)
     return DSP_OK;
 }
 
+int dsp_mfcc1024_tables(const dsp_mfcc_config *cfg, void *out, int size)
+{
+    if (!cfg) return capi_fail(DSP_EINVAL, "cfg is NULL");
+    if (!out) return (int)sizeof(dsp::GenTables1024);
+    if (size != (int)sizeof(dsp::GenTables1024)) return capi_fail(DSP_EINVAL, "size != sizeof(GenTables1024)");
+    std::string why;
+    auto t = std::make_unique<dsp::GenTables1024>();
+    if (!valid_cfg(*cfg, why) || !dsp::build_gen_tables_1024(*cfg, *t, why)) return capi_fail(DSP_EINVAL, why);
+    std::memcpy(out, t.get(), sizeof(*t));
+    return DSP_OK;
+}
+
+int dsp_mfcc2048_tables(const dsp_mfcc_config *cfg, void *out, int size)
+{
+    if (!cfg) return capi_fail(DSP_EINVAL, "cfg is NULL");
+    if (!out) return (int)sizeof(dsp::GenTables2048);
+    if (size != (int)sizeof(dsp::GenTables2048)) return capi_fail(DSP_EINVAL, "size != sizeof(GenTables2048)");
+    std::string why;
+    auto t = std::make_unique<dsp::GenTables2048>();
+    if (!valid_cfg(*cfg, why) || !dsp::build_gen_tables_2048(*cfg, *t, why)) return capi_fail(DSP_EINVAL, why);
+    std::memcpy(out, t.get(), sizeof(*t));
+    return DSP_OK;
+}
+
 int dsp_butter_bandpass(double lowcut, double highcut, double *b, double *a)
 {
     // donut-classifier/classifier.c:342-360, 383-401: the 16 kHz literal tables

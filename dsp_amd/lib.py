@@ -40,6 +40,33 @@ class LaneTables512(C.Structure):
     ]
 
 
+class GenTables1024(C.Structure):
+    """dsp::GenTables1024 (dsp_amd/csrc/tables.hpp): the tables of both 1024-point kernels; dsp_mfcc1024_tables fills it."""
+
+    _fields_ = [
+        ("win", (C.c_float * 64) * 16), ("w512", (C.c_float * 512) * 2), ("w1024", (C.c_float * 256) * 2),
+        ("mel_k0", (C.c_int32 * 64) * 4), ("mel_w", ((C.c_float * 64) * 12) * 4), ("mel_src", ((C.c_int32 * 64) * 6) * 2),
+        ("dct_w", (C.c_float * 64) * 32),
+        ("n_chunk_slots", C.c_int32), ("n_mels", C.c_int32), ("n_mfcc", C.c_int32),
+        ("tw1", (C.c_float * 64) * 14), ("tw2", (C.c_float * 64) * 14), ("twp", (C.c_float * 64) * 8),
+        ("dct_a", (C.c_float * 64) * 32),
+    ]
+
+
+class GenTables2048(C.Structure):
+    """dsp::GenTables2048 (dsp_amd/csrc/tables.hpp): the tables of the 2048-point kernel; dsp_mfcc2048_tables fills it."""
+
+    _fields_ = [
+        ("win", (C.c_float * 64) * 32), ("w1024", (C.c_float * 1024) * 2), ("w2048", (C.c_float * 512) * 2),
+        ("mel_lo", C.c_int32 * 128), ("mel_len", C.c_int32 * 128), ("mel_off", C.c_int32 * 128),
+        ("mel_w", C.c_float * 4096), ("dct", (C.c_float * 128) * 32),
+        ("n_mels", C.c_int32), ("n_mfcc", C.c_int32),
+        ("seg_ok", C.c_int32), ("seg_k0", (C.c_int32 * 64) * 3), ("seg_w", ((C.c_float * 64) * 16) * 3),
+        ("mel_s0", C.c_int32 * 128), ("mel_cnt", C.c_int32 * 128),
+        ("dct_t", (C.c_float * 64) * 64),
+    ]
+
+
 class StopModelParams(C.Structure):
     """dsp_stop_model_params (include/dsp_amd.h)."""
 
@@ -487,6 +514,8 @@ PROTOTYPES = {
     "dsp_mfcc_tables": (ip, [cfgp, vp, vp, vp]),
     "dsp_mfcc_lane_tables": (ip, [cfgp, vp, ip]),
     "dsp_mfcc400_tables": (ip, [cfgp, vp, ip]),
+    "dsp_mfcc1024_tables": (ip, [cfgp, vp, ip]),
+    "dsp_mfcc2048_tables": (ip, [cfgp, vp, ip]),
     "dsp_classify_division_check": (ip, [llp]),
     "dsp_prefilter_scan_check": (ip, [ip, ipp]),
     "dsp_last_error": (cp, []),

@@ -1554,6 +1554,9 @@ int dsp_mfcc_tables(const dsp_mfcc_config *cfg, float *window, float *mel, float
 int dsp_mfcc_lane_tables(const dsp_mfcc_config *cfg, void *out, int size);
 /* the same for a 400-point configuration: dsp::Tables400 (csrc/tables.hpp), the tables mfcc400_kernel.hip reads; tools/emulate_400_fft.py */
 int dsp_mfcc400_tables(const dsp_mfcc_config *cfg, void *out, int size);
+/* and for 1024- and 2048-point configurations: dsp::GenTables1024 (both 1024-point kernels read it) and dsp::GenTables2048 */
+int dsp_mfcc1024_tables(const dsp_mfcc_config *cfg, void *out, int size);
+int dsp_mfcc2048_tables(const dsp_mfcc_config *cfg, void *out, int size);
 
 /* classify()'s spectrogram divides every PSD cell by U = fs * sum(window^2) (classifier.cpp:350-365).  The recompute kernel takes a
  * three-instruction form of that division for cells in [2^-60, 2^60] -- but only after the classifier context has compared it with
