@@ -14,6 +14,8 @@
   TrialEvaluator   the threshold sweep, roc_curve and auc         2fa/audio/speaker/evaluate_gmm.py:73-81, generate_charts.py:52-54,68-69
   ScoreCalibrator   CAL_A * raw_score + CAL_B + CAL_C * log(n_frames), and the fit the reference leaves "to be learned on dev set"
                                                               2fa/audio/speaker/adapt_ubm.py:27-28,97-99
+  ScoreNormalizer   Z-, T- and S-norm against cohorts, all members or the K closest (no counterpart in the reference: one threshold, 1.1,
+                                                              for every model and clip, 2fa/audio/audio_driver.py:10)
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   StopTrainer    the stop-word net's Keras fit, many seeds at once  2fa/audio/word/python/keyword_classifier.py:155-232
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
@@ -1009,6 +1011,135 @@ def _calibration(params, with_frames: bool):
     if c != 0.0 and not with_frames:
         raise ValueError("c != 0 needs n_frames")
     return _lib.Calibration(a, b, c)
+
+
+class ScoreNormalizer(_lib.Closing):
+    """Z-, T- and S-norm of a score matrix against cohorts on one GPU (dsp_cohort_stats_device, dsp_score_normalize_device), and
+    their adaptive forms that keep the top_k closest cohort members.  A statistic per row of a [T][N] cohort (clips against cohort
+    speakers) and per column of an [M][S] cohort (cohort clips against the enrolled speakers), then the apply.  The reference has no
+    such step.  Keeping a speaker's own clips out of the cohort is the caller's job.  The library keeps no state between calls, so
+    there is no native handle: the object holds the device index, and close() (or `with`) ends its use.  One stream at a time per
+    normaliser."""
+
+    AXES = {"row": _lib.COHORT_PER_ROW, "column": _lib.COHORT_PER_COLUMN}
+
+    def __init__(self, device: int = 0):
+        if int(device) < 0:
+            raise ValueError("device index out of range")
+        self._L = _lib.load()
+        self.device = int(device)
+
+    def close(self):
+        self._L = None
+
+    def _lib_or_closed(self):
+        if self._L is None:
+            raise _lib.DspError("the ScoreNormalizer is closed")
+        return self._L
+
+    def _matrix(self, x, what):
+        """a float32 CUDA matrix [R][C] on the normaliser's GPU, made contiguous, or ValueError"""
+        import torch
+        if not (isinstance(x, torch.Tensor) and x.dim() == 2):
+            raise ValueError(f"{what} must be a float32 CUDA tensor [rows][columns]")
+        return _lib.scores_device(x, self.device, "normalizer")[0]
+
+    def _records(self, stats, size, what):
+        """the records stats() returned: a contiguous int64 CUDA tensor [size][4] on the normaliser's GPU, or ValueError"""
+        import torch
+        if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64 and stats.shape == (size, 4) and stats.is_contiguous()):
+            raise ValueError(f"{what} must be what stats() returned for {size} vectors: a contiguous int64 CUDA tensor [{size}][4]")
+        if stats.device.index != self.device:
+            raise ValueError(f"{what} are on GPU {stats.device.index}, the normalizer on GPU {self.device}")
+        return stats
+
+    def stats(self, cohort, axis, top_k: int = 0):
+        """cohort: cuda float32 [R][C]; axis "row" (R records, each over the C values of a row) or "column" (C records, each over the R
+        values of a column, read where they lie); top_k: the closest (largest) cohort members kept, 0 for all -> the records, an int64
+        CUDA tensor [vectors][4] of 32-byte dsp_cohort_stat (stats_to_numpy reads it).  Only enqueues."""
+        import torch
+        L = self._lib_or_closed()
+        if axis not in self.AXES:
+            raise ValueError('axis must be "row" or "column"')
+        k = int(top_k)
+        if k < 0 or k > _lib.COHORT_MAX_TOP_K:
+            raise ValueError("top_k must be 0 .. 2^22")
+        x = self._matrix(cohort, "cohort")
+        vectors, length = (x.shape[0], x.shape[1]) if axis == "row" else (x.shape[1], x.shape[0])
+        if length < 1 or length > _lib.COHORT_MAX_LENGTH:
+            raise ValueError("a cohort must hold 1 .. 2^22 values per vector")
+        out = torch.empty((vectors, 4), dtype=torch.int64, device=x.device)
+        if vectors:
+            _lib.check(L.dsp_cohort_stats_device(self.device, x.data_ptr(), x.shape[0], x.shape[1], self.AXES[axis], k, out.data_ptr(),
+                                                       _lib.current_stream(x)), "dsp_cohort_stats_device")
+        return out
+
+    @staticmethod
+    def stats_to_numpy(stats) -> dict:
+        """the records of stats() on the host: a dict of numpy arrays mean, std (float64), threshold (float32), n_finite, n_selected,
+        n_above (int32), one entry per vector.  Waits for the stream."""
+        rec = stats.cpu().numpy().view(np.dtype(_lib.COHORT_STAT_DTYPE)).reshape(-1)
+        return {name: rec[name].copy() for name in rec.dtype.names}
+
+    def apply(self, scores, mode, row_stats=None, col_stats=None, std_floor: float = 1e-6, out=None):
+        """scores: cuda float32 [T][S]; mode "z" (needs col_stats [S]), "t" (needs row_stats [T]) or "s" (both); std_floor: the least
+        sigma a score is divided by -> the normalised scores, float32 [T][S]: a new tensor, or `out` (which may be `scores` itself).
+        Only enqueues."""
+        import torch
+        L = self._lib_or_closed()
+        if mode not in _lib.NORM_MODES:
+            raise ValueError('mode must be "z", "t" or "s"')
+        floor = float(std_floor)
+        if not (np.isfinite(floor) and floor >= 0.0):
+            raise ValueError("std_floor must be finite and >= 0")
+        x = self._matrix(scores, "scores")
+        n_rows, n_col = x.shape
+        if mode != "z" and row_stats is None:
+            raise ValueError(f'mode "{mode}" needs row_stats')
+        if mode != "t" and col_stats is None:
+            raise ValueError(f'mode "{mode}" needs col_stats')
+        row = self._records(row_stats, n_rows, "row_stats") if mode != "z" else None
+        col = self._records(col_stats, n_col, "col_stats") if mode != "t" else None
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+                  and out.device == x.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of the shape of scores, on their GPU")
+        if out is scores and x is not scores:
+            raise ValueError("scores must be contiguous to be normalised in place")
+        if n_rows and n_col:
+            cfg = _lib.SnormConfig(_lib.NORM_MODES[mode], 0, floor)
+            _lib.check(L.dsp_score_normalize_device(self.device, x.data_ptr(), n_rows, n_col, row.data_ptr() if row is not None else None,
+                                                          col.data_ptr() if col is not None else None, C.byref(cfg), out.data_ptr(),
+                                                          _lib.current_stream(x)), "dsp_score_normalize_device")
+        return out
+
+    def normalize(self, scores, row_cohort=None, col_cohort=None, mode="s", top_k: int = 0, std_floor: float = 1e-6):
+        """scores: cuda float32 [T][S]; row_cohort [T][N], the trial clips against N cohort speakers (modes "t" and "s"); col_cohort
+        [M][S], M cohort clips against the enrolled speakers (modes "z" and "s") -> the normalised scores, a new tensor.  Only
+        enqueues."""
+        self._lib_or_closed()
+        if mode not in _lib.NORM_MODES:
+            raise ValueError('mode must be "z", "t" or "s"')
+        x = self._matrix(scores, "scores")
+        row = col = None
+        if mode != "z":
+            if row_cohort is None:
+                raise ValueError(f'mode "{mode}" needs row_cohort')
+            rc = self._matrix(row_cohort, "row_cohort")
+            if rc.shape[0] != x.shape[0]:
+                raise ValueError(f"row_cohort must hold one row per row of scores: {x.shape[0]}")
+        if mode != "t":
+            if col_cohort is None:
+                raise ValueError(f'mode "{mode}" needs col_cohort')
+            cc = self._matrix(col_cohort, "col_cohort")
+            if cc.shape[1] != x.shape[1]:
+                raise ValueError(f"col_cohort must hold one column per column of scores: {x.shape[1]}")
+        if mode != "z":
+            row = self.stats(rc, "row", top_k)
+        if mode != "t":
+            col = self.stats(cc, "column", top_k)
+        return self.apply(x, mode, row, col, std_floor)
 
 
 class UbmTrainer(_lib.Handle):

@@ -212,6 +212,26 @@ CAL_CONVERGED, CAL_MAX_ITER, CAL_STALLED, CAL_SINGULAR, CAL_NO_CLASS = 0, 1, 2, 
 CAL_STATUS = ("converged", "max_iter", "stalled", "singular", "no_class")
 
 
+class CohortStat(C.Structure):
+    """dsp_cohort_stat (include/dsp_amd.h), 32 bytes; COHORT_STAT_DTYPE is the same as a numpy record."""
+
+    _fields_ = [("mean", C.c_double), ("std", C.c_double), ("threshold", C.c_float), ("n_finite", C.c_int), ("n_selected", C.c_int),
+                ("n_above", C.c_int)]
+
+
+class SnormConfig(C.Structure):
+    """dsp_snorm_config (include/dsp_amd.h): the mode and the floor of sigma of dsp_score_normalize_device."""
+
+    _fields_ = [("mode", C.c_int), ("reserved", C.c_int), ("std_floor", C.c_double)]
+
+
+COHORT_STAT_DTYPE = [("mean", "<f8"), ("std", "<f8"), ("threshold", "<f4"), ("n_finite", "<i4"), ("n_selected", "<i4"), ("n_above", "<i4")]
+COHORT_PER_ROW, COHORT_PER_COLUMN = 0, 1
+NORM_Z, NORM_T, NORM_S = 0, 1, 2
+NORM_MODES = {"z": NORM_Z, "t": NORM_T, "s": NORM_S}
+COHORT_MAX_LENGTH = COHORT_MAX_TOP_K = 1 << 22
+
+
 class SvmTrainProblem(C.Structure):
     """dsp_svm_train_problem (include/dsp_amd.h), 40 bytes: rows on the host, a box bound per label, gamma."""
 
@@ -477,6 +497,8 @@ PROTOTYPES = {
     "dsp_calibration_duration_term": (ip, [lp, lg, dp]),
     "dsp_calibration_fit_device": (ip, [vp, vp, lg, lg, ipp, lp, P(CalibrationConfig), P(Calibration), P(CalibrationReport), vp]),
     "dsp_calibration_apply_device": (ip, [vp, vp, lg, lg, lp, P(Calibration), vp, vp]),
+    "dsp_cohort_stats_device": (ip, [ip, vp, lg, lg, ip, ip, vp, vp]),
+    "dsp_score_normalize_device": (ip, [ip, vp, lg, lg, vp, vp, P(SnormConfig), vp, vp]),
     "dsp_svm_trainer_create": (ip, [ip, ip, vpp]),
     "dsp_svm_trainer_destroy": (None, [vp]),
     "dsp_svm_train_set_device": (ip, [vp, vp, lg, vp, lg, vp, vp, vp, vp, vp]),

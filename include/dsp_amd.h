@@ -1243,6 +1243,71 @@ int dsp_calibration_fit_device(dsp_calibrator *c, const float *d_scores, long n_
 int dsp_calibration_apply_device(dsp_calibrator *c, const float *d_scores, long n_rows, long n_columns, const long *n_frames,
                                  const dsp_calibration *params, float *d_out, void *stream);
 
+/* COHORT NORMALISATION: Z-, T- and S-norm of a score matrix, and their adaptive forms that keep the K closest cohort members
+ * (INTEGRATION.md 6p).  The reference has no such step: it compares the raw target.score - ubm.score with one
+ * threshold (DEFAULT_SPEAKER_THRESHOLD, 2fa/audio/audio_driver.py:10; the sweep of evaluate_gmm.py), though that score shifts with the
+ * enrolled model and with the test clip.  Everything is float32, row-major, on GPU `device`, as
+ * dsp_speaker_verify_ragged_device writes it: d_scores[T][S], clip t against enrolled speaker s; a row cohort [T][N], clip t against N
+ * cohort speakers (the same call with the cohort speakers' means), which gives one statistic per row; a column cohort [M][S], M cohort
+ * clips against the S enrolled speakers (the same call with the cohort clips as d_feats), which gives one statistic per column -- the
+ * columns are read where they lie, the caller transposes nothing.  Keeping a speaker's own clips out of the cohort is the caller's job.
+ *
+ * Statistic of one cohort vector v[0 .. n) with top_k = K (0: the whole cohort).  Values are ordered by their keys: an unsigned that
+ * grows with the float, -0 before +0.
+ *   1. Only finite values take part; n_finite is their number.  n_finite == 0: mean = std = threshold = NaN, n_selected = n_above = 0.
+ *   2. n_selected K' = (K == 0 || K > n_finite) ? n_finite : K.
+ *   3. threshold = the finite value with the K'-th largest key; n_above = the finite values whose key is above the threshold's.
+ *   4. e = K' - n_above >= 1 copies of the threshold belong to the selection (which of several equal values never matters).
+ *   5. The sums are float64 over a tree that n alone fixes: leaf i is the term of v[i] where v[i] is finite and its key is above the
+ *      threshold's, else +0.0; the indices are cut into chunks of 4096 from index 0; inside a chunk the sum is the adjacent pairwise
+ *      tree (1, 2, 4 ... 2048 apart, absent leaves +0.0); the chunks are added in ascending order.  No float atomics.
+ *        A = tree((double)v[i]);                        mean = (A + (double)e * (double)threshold) / (double)K'
+ *        Q = tree(d * d), d = (double)v[i] - mean;      p = dt * dt, dt = (double)threshold - mean
+ *        std = sqrt((Q + (double)e * p) / (double)K')   -- the population standard deviation, np.std
+ *      Every product and sum is rounded on its own, as written, from left to right; none is fused.
+ * A vector's record is the same bits whatever the other vectors of the call, its position, the axis it lay along (per row of a matrix =
+ * per column of its transpose), the grid and the stream.
+ *
+ * dsp_score_normalize_device: float64, never fused.  sigma' = (std > std_floor) ? std : std_floor;
+ *   z = ((double)x - mean_col[s]) / sigma'_col[s], t = ((double)x - mean_row[t]) / sigma'_row[t]; d_out[t][s] = (float) of z
+ * (DSP_NORM_Z), t (DSP_NORM_T) or 0.5 * (z + t) (DSP_NORM_S), rounded once.  A NaN score, or a statistic with n_finite == 0, gives NaN.
+ * d_out == d_scores is allowed.  The output is a score matrix like its input: dsp_calibration_*, dsp_trials_evaluate_device and
+ * dsp_segments_device take it unchanged.
+ * Both calls only enqueue on `stream` of GPU `device`; nothing waits on the host.  The kernels keep what they need in LDS: there is no
+ * workspace and no state between calls, hence no handle to create or destroy.  As for the other stages, ONE stream at a time is all
+ * that is promised to a caller.
+ *
+ * DSP_EINVAL, before a device is touched, the first of -- dsp_cohort_stats_device: device < 0; an unknown axis; top_k outside 0 .. 2^22;
+ * n_rows or n_cols < 0; more than 2^30 vectors; (no vector: DSP_OK here, no launch;) a cohort length (the reduced axis: n_cols per
+ * row, n_rows per column) outside 1 .. 2^22; d_cohort NULL; d_stats NULL.  dsp_score_normalize_device: device < 0; cfg NULL; an unknown
+ * mode; std_floor negative or not finite; n_rows or n_cols < 0; more than 2^30 rows or columns; (no row or no column: DSP_OK here, no
+ * launch;) d_scores NULL; d_out NULL; d_row_stats NULL under DSP_NORM_T or DSP_NORM_S; d_col_stats NULL under DSP_NORM_Z or
+ * DSP_NORM_S.
+ * Not covered: choosing the cohort (and keeping a speaker's own clips out of it); cohorts selected per trial from the other side's
+ * scores (the adaptive forms here select inside each cohort vector); a median or trimmed statistic.                                 */
+#define DSP_COHORT_PER_ROW 0
+#define DSP_COHORT_PER_COLUMN 1
+#define DSP_NORM_Z 0
+#define DSP_NORM_T 1
+#define DSP_NORM_S 2
+typedef struct dsp_cohort_stat {                                                    /* 32 bytes */
+    double mean, std;
+    float threshold;
+    int n_finite, n_selected, n_above;
+} dsp_cohort_stat;
+typedef struct dsp_snorm_config {
+    int    mode;         /* DSP_NORM_Z, DSP_NORM_T or DSP_NORM_S */
+    int    reserved;
+    double std_floor;    /* finite, >= 0: the least sigma a score is divided by */
+} dsp_snorm_config;
+int dsp_cohort_stats_device(int device, const float *d_cohort, long n_rows, long n_cols,
+                            int axis,              /* DSP_COHORT_PER_ROW: n_rows records over n_cols values; DSP_COHORT_PER_COLUMN: n_cols records over n_rows values */
+                            int top_k, dsp_cohort_stat *d_stats, void *stream);
+int dsp_score_normalize_device(int device, const float *d_scores, long n_rows, long n_cols,
+                               const dsp_cohort_stat *d_row_stats,    /* [T], needed by DSP_NORM_T and DSP_NORM_S */
+                               const dsp_cohort_stat *d_col_stats,    /* [S], needed by DSP_NORM_Z and DSP_NORM_S */
+                               const dsp_snorm_config *cfg, float *d_out, void *stream);
+
 /* SVM TRAINING: the scrub-jay RBF-SVM from pooled features -- cepstrum/train.py:66-85 (StandardScaler, SVC(kernel="rbf",
  * probability=True, class_weight="balanced"), cross-validation) as batched SMO on the GPU.
  * d_feat[n][n_features] is float32 on the trainer's device (what dsp_mfcc_stats_device writes); labels[n] is a HOST array of 0 / 1,
