@@ -762,16 +762,54 @@ def segment_sample_spans(cfg, offsets, segments, window_frames: int, hop_frames:
     return starts, lengths
 
 
-class Segmenter(_lib.Handle):
+class _Stage:
+    """The constructor of a stage on a score matrix, a Handle that `_make`(device) creates (a mix-in in front of lib.Handle, which
+    stays the base of the classes that own a native handle).  No device is touched before the first call that launches."""
+
+    _make = None
+
+    def __init__(self, device: int = 0):
+        self._create(self._make, int(device))
+        self.device = int(device)
+
+
+def _truth(truth, n_rows, n_col):
+    """truth as a contiguous C int array: one column index (or -1) per row of scores, or ValueError"""
+    tr = np.ascontiguousarray(np.asarray(truth), dtype=np.intc)
+    if tr.ndim != 1 or tr.size != n_rows:
+        raise ValueError(f"truth must hold one column index (or -1) per row of scores: {n_rows}")
+    bad = (tr < -1) | (tr >= n_col)
+    if bad.any():
+        raise ValueError(f"truth[{int(np.flatnonzero(bad)[0])}] is neither -1 nor a column")
+    return tr
+
+
+def _n_thresholds(n, name="n_thresholds"):
+    n = int(n)
+    if n < 2 or n > 1024:
+        raise ValueError(f"{name} must be 2 .. 1024")
+    return n
+
+
+def _out_like(out, x, scores, verb):
+    """where an apply writes: a new tensor like x (scores made contiguous), or the caller's `out`, which may be `scores` itself"""
+    import torch
+    if out is None:
+        return torch.empty_like(x)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+            and out.device == x.device):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of the shape of scores, on their GPU")
+    if out is scores and x is not scores:
+        raise ValueError(f"scores must be contiguous to be {verb} in place")
+    return out
+
+
+class Segmenter(_Stage, _lib.Handle):
     """dsp_segmenter: segments from the window scores of any scan -- hysteresis between two thresholds, runs joined over short gaps,
     short segments dropped -- found on the GPU in (recording, column, first_window) order.  One stream at a time per segmenter."""
 
-    _destroy = "dsp_segmenter_destroy"
+    _make, _destroy = "dsp_segmenter_create", "dsp_segmenter_destroy"
     CAP = 1 << 20          # segments the first call makes room for at most; a second call follows when more are found
-
-    def __init__(self, device: int = 0):
-        self._create("dsp_segmenter_create", int(device))
-        self.device = int(device)
 
     def segments(self, scores, window_offsets, on, off=None, min_windows: int = 1, max_gap: int = 0, exclusive: bool = False, as_tensor: bool = False):
         """scores: cuda float32 [Wt] or [Wt][S] (a scan's prob, prob1, decision or llr as it is), recording r = windows [window_offsets[r],
@@ -803,17 +841,13 @@ class Segmenter(_lib.Handle):
         return out if as_tensor else out.cpu().numpy().view(np.dtype(_lib.SEGMENT_DTYPE)).reshape(-1)
 
 
-class TrialEvaluator(_lib.Handle):
+class TrialEvaluator(_Stage, _lib.Handle):
     """dsp_trial_evaluator: labelled trials on the GPU -- per column of a score matrix and pooled, the reference's threshold sweep
     (evaluate_gmm.py:77-81), the exact ROC step curve as counts and the AUC (generate_charts.py:68-69).  One stream at a time per
     evaluator."""
 
-    _destroy = "dsp_trial_evaluator_destroy"
+    _make, _destroy = "dsp_trial_evaluator_create", "dsp_trial_evaluator_destroy"
     WANT = ("columns", "sweep", "roc")
-
-    def __init__(self, device: int = 0):
-        self._create("dsp_trial_evaluator_create", int(device))
-        self.device = int(device)
 
     def evaluate(self, scores, truth, n_thresholds: int = 200, want=("columns", "sweep", "roc")):
         """scores: cuda float32 [T] or [T][S] (SpeakerVerifier.verify(...)["llr"] or .scan(...)["llr"] as it is); truth: T integers on
@@ -828,18 +862,12 @@ class TrialEvaluator(_lib.Handle):
         want = tuple(want)
         if not want or any(key not in self.WANT for key in want):
             raise ValueError(f"want must name at least one of {self.WANT}")
-        n = int(n_thresholds)
-        if n < 2 or n > 1024:
-            raise ValueError("n_thresholds must be 2 .. 1024")
+        n = _n_thresholds(n_thresholds)
         scores, n_col = _lib.scores_device(scores, self.device, "evaluator")
         n_rows = scores.shape[0]
         if n_rows < 1:
             raise ValueError("scores hold no trial")
-        tr = np.ascontiguousarray(np.asarray(truth), dtype=np.intc)
-        if tr.ndim != 1 or tr.size != n_rows:
-            raise ValueError(f"truth must hold one column index (or -1) per row of scores: {n_rows}")
-        if ((tr < -1) | (tr >= n_col)).any():
-            raise ValueError(f"truth[{int(np.flatnonzero((tr < -1) | (tr >= n_col))[0])}] is neither -1 nor a column")
+        tr = _truth(truth, n_rows, n_col)
         tp = tr.ctypes.data_as(C.POINTER(C.c_int))
         dev, out, ptr = scores.device, {"n_thresholds": n}, {}
         if "columns" in want:
@@ -874,9 +902,7 @@ class TrialEvaluator(_lib.Handle):
 def trial_thresholds(lo, hi, n: int) -> np.ndarray:
     """Host only: the n thresholds of the sweep between a column's lo and hi, float64 -- np.linspace(lo, hi, n) as
     evaluate_gmm.py:77 calls it: i * ((hi - lo) / (n - 1)) + lo in two roundings, the last one hi itself."""
-    n = int(n)
-    if n < 2 or n > 1024:
-        raise ValueError("n must be 2 .. 1024")
+    n = _n_thresholds(n, "n")
     lo, hi = np.float64(lo), np.float64(hi)
     with np.errstate(invalid="ignore"):
         t = np.arange(n, dtype=np.float64) * ((hi - lo) / np.float64(n - 1)) + lo
@@ -915,15 +941,11 @@ def roc_points(result: dict, column: int):
         return np.array(fps, np.float64) / np.float64(n_non), np.array(tps, np.float64) / np.float64(n_tgt), np.array(thr, np.float64)
 
 
-class ScoreCalibrator(_lib.Handle):
+class ScoreCalibrator(_Stage, _lib.Handle):
     """dsp_calibrator: c = A x + B + C log(n_frames) on a score matrix on the GPU -- fit by prior-weighted logistic regression (damped
     Newton, every pass and solve on the device) on labelled trials, and apply.  One stream at a time per calibrator."""
 
-    _destroy = "dsp_calibrator_destroy"
-
-    def __init__(self, device: int = 0):
-        self._create("dsp_calibrator_create", int(device))
-        self.device = int(device)
+    _make, _destroy = "dsp_calibrator_create", "dsp_calibrator_destroy"
 
     @staticmethod
     def duration_term(n_frames) -> np.ndarray:
@@ -949,11 +971,7 @@ class ScoreCalibrator(_lib.Handle):
         n_rows = scores.shape[0]
         if n_rows < 1:
             raise ValueError("scores hold no trial")
-        tr = np.ascontiguousarray(np.asarray(truth), dtype=np.intc)
-        if tr.ndim != 1 or tr.size != n_rows:
-            raise ValueError(f"truth must hold one column index (or -1) per row of scores: {n_rows}")
-        if ((tr < -1) | (tr >= n_col)).any():
-            raise ValueError(f"truth[{int(np.flatnonzero((tr < -1) | (tr >= n_col))[0])}] is neither -1 nor a column")
+        tr = _truth(truth, n_rows, n_col)
         nf = _frames(n_frames, n_rows)
         start = _calibration(init, nf is not None)
         cfg, rep = _lib.CalibrationConfig(float(prior), float(tol), int(max_iter), 0), _lib.CalibrationReport()
@@ -968,18 +986,11 @@ class ScoreCalibrator(_lib.Handle):
     def apply(self, scores, params, n_frames=None, out=None):
         """scores: cuda float32 [T] or [T][S]; params: (a, b, c) or what fit returned; n_frames as in fit (None needs c == 0) -> the
         calibrated scores, float32 of the same shape: a new tensor, or `out` (which may be `scores` itself).  Only enqueues."""
-        import torch
         x, n_col = _lib.scores_device(scores, self.device, "calibrator")
         n_rows = x.shape[0]
         nf = _frames(n_frames, n_rows)
         p = _calibration(params, nf is not None)
-        if out is None:
-            out = torch.empty_like(x)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
-                  and out.device == x.device):
-            raise ValueError("out must be a contiguous float32 CUDA tensor of the shape of scores, on their GPU")
-        if out is scores and x is not scores:
-            raise ValueError("scores must be contiguous to be calibrated in place")
+        out = _out_like(out, x, scores, "calibrated")
         if n_rows:
             _lib.check(self._L.dsp_calibration_apply_device(self._h, x.data_ptr(), n_rows, n_col, nf.ctypes.data_as(_lib.LP) if nf is not None else None,
                                                             C.byref(p), out.data_ptr(), _lib.current_stream(x)), "dsp_calibration_apply_device")
@@ -1085,7 +1096,6 @@ class ScoreNormalizer(_lib.Closing):
         """scores: cuda float32 [T][S]; mode "z" (needs col_stats [S]), "t" (needs row_stats [T]) or "s" (both); std_floor: the least
         sigma a score is divided by -> the normalised scores, float32 [T][S]: a new tensor, or `out` (which may be `scores` itself).
         Only enqueues."""
-        import torch
         L = self._lib_or_closed()
         if mode not in _lib.NORM_MODES:
             raise ValueError('mode must be "z", "t" or "s"')
@@ -1100,13 +1110,7 @@ class ScoreNormalizer(_lib.Closing):
             raise ValueError(f'mode "{mode}" needs col_stats')
         row = self._records(row_stats, n_rows, "row_stats") if mode != "z" else None
         col = self._records(col_stats, n_col, "col_stats") if mode != "t" else None
-        if out is None:
-            out = torch.empty_like(x)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
-                  and out.device == x.device):
-            raise ValueError("out must be a contiguous float32 CUDA tensor of the shape of scores, on their GPU")
-        if out is scores and x is not scores:
-            raise ValueError("scores must be contiguous to be normalised in place")
+        out = _out_like(out, x, scores, "normalised")
         if n_rows and n_col:
             cfg = _lib.SnormConfig(_lib.NORM_MODES[mode], 0, floor)
             _lib.check(L.dsp_score_normalize_device(self.device, x.data_ptr(), n_rows, n_col, row.data_ptr() if row is not None else None,

@@ -15,7 +15,6 @@
 // theta arrives through the state and tau as an argument: both are uniform, the compiler loads them through the scalar cache.
 // Every kernel of a fit tests CalState::done first, so max_iter passes are enqueued without a host round trip and those behind the end
 // leave at once.  Every row and column index is checked before a load.
-#include <cfloat>
 #include <cmath>
 
 #include "calibrate_kernels.hpp"
@@ -26,9 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kApplyPerThread = 16;
-
-__device__ inline long block_index() { return (long)blockIdx.y * gridDim.x + blockIdx.x; }
-__device__ inline bool finite_f64(double v) { return fabs(v) <= DBL_MAX; }
 
 struct Theta { double a, b, c, tau; };
 
@@ -46,7 +42,7 @@ struct Fold {
     template <bool L> __device__ void take(float score, bool target, double l, const Theta &t)
     {
         const double x = (double)score;
-        if (!finite_f64(x)) { ++n[2]; return; }
+        if (!is_finite(x)) { ++n[2]; return; }
         double c = t.a * x + t.b;
         if (L) c += t.c * l;
         const double z = c + t.tau, u = target ? -z : z;     // the trial's loss is softplus(u)
@@ -205,7 +201,7 @@ __device__ bool cal_cholesky(int n, const double *H, const double *g, double *d)
         d[1] = (y1 - l21 * d[2]) / l11;
         d[0] = (y0 - l10 * d[1] - l20 * d[2]) / l00;
     }
-    return finite_f64(d[0]) && finite_f64(d[1]) && finite_f64(d[2]);
+    return is_finite(d[0]) && is_finite(d[1]) && is_finite(d[2]);
 }
 
 __device__ void cal_finish(CalState *st, int status, const double *theta, double objective)
@@ -255,9 +251,9 @@ __device__ void cal_advance(const CalPartial &tot, int iter, int max_iter, int n
     for (int i = 0; i < 3; ++i) st->base[i] = st->theta[i];
     st->objective_base = J;
     st->halvings = 0;
-    bool ok = finite_f64(J);
-    for (int i = 0; i < 3; ++i) ok = ok && finite_f64(g[i]);
-    for (int i = 0; i < 6; ++i) ok = ok && finite_f64(H[i]);
+    bool ok = is_finite(J);
+    for (int i = 0; i < 3; ++i) ok = ok && is_finite(g[i]);
+    for (int i = 0; i < 6; ++i) ok = ok && is_finite(H[i]);
     double d[3];
     if (!ok || !cal_cholesky(n_par, H, g, d)) { cal_finish(st, DSP_CAL_SINGULAR, st->base, J); return; }
     for (int i = 0; i < 3; ++i) {
@@ -306,18 +302,11 @@ __global__ __launch_bounds__(kThreads) void cal_apply_kernel(const float *scores
     }
 }
 
-// a grid of `blocks` blocks (at most 2^36) as x * y; the kernels count them with block_index() and return past `blocks`
-dim3 grid_for(long blocks)
-{
-    const long x = std::min<long>(std::max<long>(blocks, 1), 1L << 20);
-    return dim3((unsigned)x, (unsigned)cal_ceil_div(std::max<long>(blocks, 1), x));
-}
-
 }  // namespace
 
 hipError_t launch_calibration_fit(const CalFit &q, hipStream_t st)
 {
-    const long T = q.rows, S = q.columns, units = cal_units(T, S), groups = cal_ceil_div(S, 64);
+    const long T = q.rows, S = q.columns, units = cal_units(T, S), groups = ceil_div(S, 64);
     if (T < 1 || S < 1 || units > (1L << 36)) return hipErrorInvalidValue;
     const bool across = S >= kTrialLanesAcrossColumns, with_l = q.duration != nullptr;
     const double tau = std::log(q.prior / (1.0 - q.prior));
@@ -328,13 +317,13 @@ hipError_t launch_calibration_fit(const CalFit &q, hipStream_t st)
             kernel<<<grid_for(units), kThreads, 0, st>>>(q.scores, q.truth, q.duration, T, S, groups, units, q.state, tau, q.partials);
         } else {
             auto kernel = with_l ? cal_stat_time_kernel<true> : cal_stat_time_kernel<false>;
-            kernel<<<grid_for(cal_ceil_div(units, kWaves)), kThreads, 0, st>>>(q.scores, q.truth, q.duration, T, S, units, q.state, tau, q.partials);
+            kernel<<<grid_for(ceil_div(units, kWaves)), kThreads, 0, st>>>(q.scores, q.truth, q.duration, T, S, units, q.state, tau, q.partials);
         }
         CalPartial *level = q.partials;
         long n = units;
         while (n > kCalFanIn) {
-            const long m = cal_ceil_div(n, kCalFanIn);
-            cal_reduce_kernel<<<grid_for(cal_ceil_div(m * kCalWords, kThreads)), kThreads, 0, st>>>(level, n, m, q.state, level + n);
+            const long m = ceil_div(n, kCalFanIn);
+            cal_reduce_kernel<<<grid_for(ceil_div(m * kCalWords, kThreads)), kThreads, 0, st>>>(level, n, m, q.state, level + n);
             level += n;
             n = m;
         }
@@ -347,7 +336,7 @@ hipError_t launch_calibration_fit(const CalFit &q, hipStream_t st)
 
 hipError_t launch_calibration_apply(const float *scores, const double *duration, long rows, long columns, dsp_calibration params, float *out, hipStream_t st)
 {
-    const long total = rows * columns, blocks = cal_ceil_div(total, (long)kThreads * kApplyPerThread);
+    const long total = rows * columns, blocks = ceil_div(total, (long)kThreads * kApplyPerThread);
     if (rows < 1 || columns < 1) return hipErrorInvalidValue;
     if (duration) cal_apply_kernel<true><<<grid_for(blocks), kThreads, 0, st>>>(scores, duration, total, columns, blocks, params, out);
     else cal_apply_kernel<false><<<grid_for(blocks), kThreads, 0, st>>>(scores, duration, total, columns, blocks, params, out);

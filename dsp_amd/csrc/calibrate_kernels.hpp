@@ -42,18 +42,17 @@ struct CalState {
     dsp_calibration_report report;
 };
 
-inline long cal_ceil_div(long a, long b) { return (a + b - 1) / b; }
 // partials the statistics pass writes
 inline long cal_units(long rows, long columns)
 {
-    if (columns >= kTrialLanesAcrossColumns) return cal_ceil_div(rows, kCalBlockRowsColumns) * cal_ceil_div(columns, 64);
-    return cal_ceil_div(rows, kCalRowsTime) * columns;
+    if (columns >= kTrialLanesAcrossColumns) return ceil_div(rows, kCalBlockRowsColumns) * ceil_div(columns, 64);
+    return ceil_div(rows, kCalRowsTime) * columns;
 }
 // partials of every level together: the statistics', then each reduction's, down to kCalFanIn or fewer
 inline long cal_partials(long rows, long columns)
 {
     long n = cal_units(rows, columns), total = n;
-    while (n > kCalFanIn) { n = cal_ceil_div(n, kCalFanIn); total += n; }
+    while (n > kCalFanIn) { n = ceil_div(n, kCalFanIn); total += n; }
     return total;
 }
 inline size_t cal_workspace_bytes(long rows, long columns) { return 256 + (size_t)cal_partials(rows, columns) * sizeof(CalPartial); }

@@ -2,7 +2,6 @@
 // before a device is touched and in the order the header states, the host-only duration term, the calibrator's grow-only workspace
 // and the labels and duration terms that travel through its ring to the kernels of calibrate_kernels.hip.
 #include <cmath>
-#include <memory>
 
 #include "calibrate_kernels.hpp"
 #include "capi_util.hpp"
@@ -14,23 +13,11 @@ static_assert(sizeof(dsp_calibration_config) == 24, "dsp_calibration_config is 2
 static_assert(sizeof(dsp_calibration_report) == 88, "dsp_calibration_report is 88 bytes (dsp_amd/lib.py CalibrationReport)");
 static_assert(sizeof(dsp::CalState) <= 256, "the state lies in the first 256 bytes of the workspace");
 
-struct dsp_calibrator {
-    int device = 0;
-    dsp::DeviceBuf<char> ws;             // grow-only: CalState, then the partials of every level (calibrate_kernels.hpp)
-    dsp::SpanRing spans;                 // duration terms | truth
-};
+struct dsp_calibrator : dsp::StageHandle {};      // ws: CalState, then the partials of every level (calibrate_kernels.hpp); spans: duration terms | truth
 
 namespace {
 
 double duration_term(long n_frames) { return std::log((double)n_frames + 1e-8); }
-
-int check_shape(long n_rows, long n_columns)
-{
-    if (n_columns < 1 || n_columns > dsp::kTrialMaxColumns) return capi_fail(DSP_EINVAL, "n_columns must be 1 .. 2^19");
-    if (n_rows < 0) return capi_fail(DSP_EINVAL, "n_rows < 0");
-    if (n_rows >= dsp::kTrialMaxRows) return capi_fail(DSP_EINVAL, "2^31 rows or more");
-    return DSP_OK;
-}
 
 int check_frames(const long *n_frames, long n_rows)
 {
@@ -41,34 +28,13 @@ int check_frames(const long *n_frames, long n_rows)
 
 bool finite(const dsp_calibration &p) { return std::isfinite(p.a) && std::isfinite(p.b) && std::isfinite(p.c); }
 
-int too_many(long n_rows, long n_columns)
-{
-    return (double)n_rows * (double)n_columns >= 35184372088832.0 ? capi_fail(DSP_EINVAL, "2^45 trials or more in one call") : DSP_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-int dsp_calibrator_create(int device, dsp_calibrator **out)
-{
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    // no device is touched here: a device that does not exist is reported by the first call that fits or applies
-    auto c = std::make_unique<dsp_calibrator>();
-    c->device = device;
-    *out = c.release();
-    return DSP_OK;
-}
+int dsp_calibrator_create(int device, dsp_calibrator **out) { return dsp::stage_create(device, out); }
 
-void dsp_calibrator_destroy(dsp_calibrator *c)
-{
-    if (!c) return;
-    dsp::DeviceScope scope(c->device);
-    c->spans.release();
-    delete c;
-}
+void dsp_calibrator_destroy(dsp_calibrator *c) { dsp::stage_destroy(c); }
 
 int dsp_calibration_duration_term(const long *n_frames, long n_rows, double *out)
 {
@@ -90,7 +56,7 @@ int dsp_calibration_fit_device(dsp_calibrator *c, const float *d_scores, long n_
     if (cfg->max_iter < 1 || cfg->max_iter > dsp::kCalMaxIter)
         return capi_fail(DSP_EINVAL, "dsp_calibration_config: max_iter must be 1 .. 10000, got " + std::to_string(cfg->max_iter));
     if (!report) return capi_fail(DSP_EINVAL, "report is NULL");
-    if (const int rc = check_shape(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_score_shape(n_rows, n_columns)) return rc;
     const dsp_calibration start = init ? *init : dsp_calibration{1.0, 0.0, 0.0};
     if (!finite(start)) return capi_fail(DSP_EINVAL, "init is not finite");
     if (start.c != 0.0 && !n_frames) return capi_fail(DSP_EINVAL, "init->c != 0 without n_frames");
@@ -100,20 +66,17 @@ int dsp_calibration_fit_device(dsp_calibrator *c, const float *d_scores, long n_
     }
     if (!d_scores) return capi_fail(DSP_EINVAL, "d_scores is NULL");
     if (!truth) return capi_fail(DSP_EINVAL, "truth is NULL");
-    for (long r = 0; r < n_rows; ++r)
-        if (truth[r] < -1 || truth[r] >= n_columns)
-            return capi_fail(DSP_EINVAL, "truth[" + std::to_string(r) + "] = " + std::to_string(truth[r]) + " is neither -1 nor a column");
+    if (const int rc = dsp::check_truth(truth, n_rows, n_columns)) return rc;
     if (n_frames)
         if (const int rc = check_frames(n_frames, n_rows)) return rc;
-    if (const int rc = too_many(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_trial_count(n_rows, n_columns)) return rc;
     if (const int rc = dsp::check_device(c->device)) return rc;
     DSP_ON_DEVICE(c->device);
     hipStream_t st = (hipStream_t)stream;
     // duration terms, T doubles (with n_frames) | truth, T ints
     const size_t n = (size_t)n_rows, bytes = (n_frames ? n * sizeof(double) : 0) + n * sizeof(int);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = c->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(c->spans, bytes, slot)) return rc;
     double *h_duration = static_cast<double *>(slot.h());
     int *h_truth = reinterpret_cast<int *>(h_duration + (n_frames ? n : 0));
     if (n_frames)
@@ -136,14 +99,14 @@ int dsp_calibration_apply_device(dsp_calibrator *c, const float *d_scores, long 
     if (!c) return capi_fail(DSP_EINVAL, "calibrator is NULL");
     if (!params) return capi_fail(DSP_EINVAL, "params is NULL");
     if (!finite(*params)) return capi_fail(DSP_EINVAL, "params are not finite");
-    if (const int rc = check_shape(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_score_shape(n_rows, n_columns)) return rc;
     if (params->c != 0.0 && !n_frames) return capi_fail(DSP_EINVAL, "params->c != 0 without n_frames");
     if (n_rows == 0) return DSP_OK;
     if (!d_scores) return capi_fail(DSP_EINVAL, "d_scores is NULL");
     if (!d_out) return capi_fail(DSP_EINVAL, "d_out is NULL");
     if (n_frames)
         if (const int rc = check_frames(n_frames, n_rows)) return rc;
-    if (const int rc = too_many(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_trial_count(n_rows, n_columns)) return rc;
     if (const int rc = dsp::check_device(c->device)) return rc;
     DSP_ON_DEVICE(c->device);
     hipStream_t st = (hipStream_t)stream;
@@ -153,8 +116,7 @@ int dsp_calibration_apply_device(dsp_calibrator *c, const float *d_scores, long 
     }
     const size_t bytes = (size_t)n_rows * sizeof(double);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = c->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(c->spans, bytes, slot)) return rc;
     double *h_duration = static_cast<double *>(slot.h());
     for (long r = 0; r < n_rows; ++r) h_duration[r] = duration_term(n_frames[r]);
     DSP_CAPI_HIP(slot.upload(bytes, st));

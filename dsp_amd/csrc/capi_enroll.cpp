@@ -31,8 +31,7 @@ long fill_spans(dsp::SpanRing &ring, dsp::SpanRing::Lease &slot, const long *fo,
     if (const int rc = dsp::check_frame_offsets(fo, n, what)) return rc;
     if (refuse_rowless)
         if (const int rc = dsp::refuse_rowless(fo, n, " has no rows", what)) return rc;
-    const hipError_t e = ring.acquire((size_t)n * sizeof(dsp::RowSpan), slot);
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(e));
+    if (const int rc = dsp::lease(ring, (size_t)n * sizeof(dsp::RowSpan), slot)) return rc;
     dsp::RowSpan *h = static_cast<dsp::RowSpan *>(slot.h());
     long units = 0;
     for (long r = 0; r < n; ++r) {

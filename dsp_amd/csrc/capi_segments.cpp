@@ -2,7 +2,6 @@
 // of them before a device is touched, the host-only capacity bound and sample spans, the segmenter's grow-only workspace and the
 // per-recording offsets (windows, words, chunks) that travel through its ring to the kernels of segment_kernels.hip.
 #include <cmath>
-#include <memory>
 
 #include "capi_util.hpp"
 #include "mfcc_plan.hpp"
@@ -10,11 +9,7 @@
 
 using dsp::capi_fail;
 
-struct dsp_segmenter {
-    int device = 0;
-    dsp::DeviceBuf<char> ws;             // grow-only: SegWorkspace (segment_kernels.hpp)
-    dsp::SpanRing spans;
-};
+struct dsp_segmenter : dsp::StageHandle {};      // ws: SegWorkspace (segment_kernels.hpp); spans: window | word | chunk | block offsets
 
 namespace {
 
@@ -50,25 +45,9 @@ int check_columns(long n_columns)
 
 extern "C" {
 
-int dsp_segmenter_create(int device, dsp_segmenter **out)
-{
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    // no device is touched here: a device that does not exist is reported by the first call that segments
-    auto s = std::make_unique<dsp_segmenter>();
-    s->device = device;
-    *out = s.release();
-    return DSP_OK;
-}
+int dsp_segmenter_create(int device, dsp_segmenter **out) { return dsp::stage_create(device, out); }
 
-void dsp_segmenter_destroy(dsp_segmenter *s)
-{
-    if (!s) return;
-    dsp::DeviceScope scope(s->device);
-    s->spans.release();
-    delete s;
-}
+void dsp_segmenter_destroy(dsp_segmenter *s) { dsp::stage_destroy(s); }
 
 long dsp_segments_capacity(const dsp_segment_config *cfg, const long *window_offsets, long n_recordings, long n_columns)
 {
@@ -119,8 +98,7 @@ int dsp_segments_device(dsp_segmenter *s, const float *d_scores, long n_recordin
     // wo (from 0) | word offsets | chunk offsets | block offsets, n + 1 longs each
     const size_t n1 = (size_t)n_recordings + 1, bytes = 4 * n1 * sizeof(long);
     dsp::SpanRing::Lease slot;
-    const hipError_t e = s->spans.acquire(bytes, slot);
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(e));
+    if (const int rc = dsp::lease(s->spans, bytes, slot)) return rc;
     long *wo = static_cast<long *>(slot.h()), *wdo = wo + n1, *co = wdo + n1, *bo = co + n1;
     wo[0] = wdo[0] = co[0] = bo[0] = 0;
     for (long r = 0; r < n_recordings; ++r) {

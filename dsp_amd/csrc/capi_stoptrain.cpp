@@ -162,8 +162,7 @@ int dsp_stop_train_set_device(dsp_stop_trainer *t, const float *d_mfcc, long n, 
         const size_t head = (size_t)(n + 1) * sizeof(long);
         const size_t bytes = head + (mean ? 2 * n_in * sizeof(float) : (scaler_rows ? (size_t)n_scaler_rows * sizeof(int) : 0));
         dsp::SpanRing::Lease slot;
-        const hipError_t err = t->spans.acquire(bytes, slot);
-        if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+        if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
         char *h = static_cast<char *>(slot.h());
         std::memcpy(h, frame_offsets, head);
         if (mean) {
@@ -234,8 +233,7 @@ int dsp_stop_train_runs_device(dsp_stop_trainer *t, const dsp_stop_train_run *ru
     // the runs' table, the labels and the row lists through the ring
     const size_t bytes = P * sizeof(dsp::StopTrainRun) + (n + total) * sizeof(int);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = t->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
     auto *h_run = static_cast<dsp::StopTrainRun *>(slot.h());
     int *h_labels = reinterpret_cast<int *>(h_run + P), *h_members = h_labels + n;
     std::memcpy(h_labels, labels, n * sizeof(int));

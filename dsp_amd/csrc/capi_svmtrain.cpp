@@ -94,8 +94,7 @@ int enqueue_problems(dsp_svm_trainer *t, const dsp_svm_train_problem *problems, 
     const size_t n = (size_t)t->n, P = (size_t)n_problems;
     const size_t bytes = P * sizeof(dsp::SvmTrainProblem) + (n + total) * sizeof(int);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = t->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
     auto *h_prob = static_cast<dsp::SvmTrainProblem *>(slot.h());
     int *h_labels = reinterpret_cast<int *>(h_prob + P), *h_members = h_labels + n;
     std::memcpy(h_labels, labels, n * sizeof(int));
@@ -130,8 +129,7 @@ int enqueue_platt(dsp_svm_trainer *t, const double *d_dec_cv, const int *labels,
 {
     const size_t n = (size_t)t->n, bytes = (n + (rows ? (size_t)n_rows : 0)) * sizeof(int);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = t->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
     int *h = static_cast<int *>(slot.h());
     std::memcpy(h, labels, n * sizeof(int));
     if (rows) std::memcpy(h + n, rows, (size_t)n_rows * sizeof(int));
@@ -157,8 +155,7 @@ int enqueue_dataset(dsp_svm_trainer *t, const float *d_feat, long n, const int *
     if (offset) {
         const size_t bytes = 2 * nf * sizeof(float);
         dsp::SpanRing::Lease slot;
-        const hipError_t err = t->spans.acquire(bytes, slot);
-        if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+        if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
         std::memcpy(slot.h(), offset, nf * sizeof(float));
         std::memcpy(static_cast<float *>(slot.h()) + nf, scale, nf * sizeof(float));
         DSP_CAPI_HIP(slot.upload(bytes, st));
@@ -166,8 +163,7 @@ int enqueue_dataset(dsp_svm_trainer *t, const float *d_feat, long n, const int *
     } else if (scaler_rows) {
         const size_t bytes = (size_t)n_scaler_rows * sizeof(int);
         dsp::SpanRing::Lease slot;
-        const hipError_t err = t->spans.acquire(bytes, slot);
-        if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+        if (const int rc = dsp::lease(t->spans, bytes, slot)) return rc;
         std::memcpy(slot.h(), scaler_rows, bytes);
         DSP_CAPI_HIP(slot.upload(bytes, st));
         DSP_CAPI_HIP(dsp::launch_svm_scaler_fit(d_feat, t->n_features, static_cast<const int *>(slot.d()), n_scaler_rows, d_offset, d_scale, st));

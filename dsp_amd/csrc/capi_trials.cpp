@@ -1,8 +1,6 @@
 // capi_trials.cpp -- the C ABI of labelled trials (include/dsp_amd.h dsp_trial*): argument checks, all of them before a
 // device is touched, the host-only target lists and pair count, the evaluator's grow-only workspace and the labels that travel
 // through its ring to the kernels of trial_kernels.hip.
-#include <memory>
-
 #include "capi_util.hpp"
 #include "trial_kernels.hpp"
 
@@ -10,29 +8,9 @@ using dsp::capi_fail;
 
 static_assert(sizeof(dsp_trial_column) == 80, "dsp_trial_column is 80 bytes (dsp_amd/lib.py TRIAL_COLUMN_DTYPE)");
 
-struct dsp_trial_evaluator {
-    int device = 0;
-    dsp::DeviceBuf<char> ws;             // grow-only: TrialWorkspace (trial_kernels.hpp)
-    dsp::SpanRing spans;                 // truth | target_offsets | target_rows
-};
+struct dsp_trial_evaluator : dsp::StageHandle {};      // ws: TrialWorkspace (trial_kernels.hpp); spans: target_offsets | truth | target_rows
 
 namespace {
-
-int check_shape(long n_rows, long n_columns)
-{
-    if (n_columns < 1 || n_columns > dsp::kTrialMaxColumns) return capi_fail(DSP_EINVAL, "n_columns must be 1 .. 2^19");
-    if (n_rows < 0) return capi_fail(DSP_EINVAL, "n_rows < 0");
-    if (n_rows >= dsp::kTrialMaxRows) return capi_fail(DSP_EINVAL, "2^31 rows or more");
-    return DSP_OK;
-}
-
-int check_truth(const int *truth, long n_rows, long n_columns)
-{
-    for (long r = 0; r < n_rows; ++r)
-        if (truth[r] < -1 || truth[r] >= n_columns)
-            return capi_fail(DSP_EINVAL, "truth[" + std::to_string(r) + "] = " + std::to_string(truth[r]) + " is neither -1 nor a column");
-    return DSP_OK;
-}
 
 // P_s of every column: counts[s + 1] (counts[0] stays 0) -> the number of targets
 long count_targets(const int *truth, long n_rows, std::vector<long> &counts)
@@ -49,9 +27,9 @@ extern "C" {
 
 long dsp_trials_target_offsets(const int *truth, long n_rows, long n_columns, long *target_offsets, long *target_rows)
 {
-    if (const int rc = check_shape(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_score_shape(n_rows, n_columns)) return rc;
     if (n_rows > 0 && !truth) return capi_fail(DSP_EINVAL, "truth is NULL");
-    if (const int rc = check_truth(truth, n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_truth(truth, n_rows, n_columns)) return rc;
     std::vector<long> at((size_t)n_columns + 1, 0);
     const long total = count_targets(truth, n_rows, at);
     for (long s = 0; s < n_columns; ++s) at[(size_t)s + 1] += at[(size_t)s];
@@ -64,9 +42,9 @@ long dsp_trials_target_offsets(const int *truth, long n_rows, long n_columns, lo
 
 long dsp_trials_pairs(const int *truth, long n_rows, long n_columns)
 {
-    if (const int rc = check_shape(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_score_shape(n_rows, n_columns)) return rc;
     if (n_rows > 0 && !truth) return capi_fail(DSP_EINVAL, "truth is NULL");
-    if (const int rc = check_truth(truth, n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_truth(truth, n_rows, n_columns)) return rc;
     std::vector<long> counts((size_t)n_columns + 1, 0);
     count_targets(truth, n_rows, counts);
     long pairs = 0;                      // (the P_s add up to n_rows < 2^31 at most: below 2^62)
@@ -74,25 +52,9 @@ long dsp_trials_pairs(const int *truth, long n_rows, long n_columns)
     return pairs;
 }
 
-int dsp_trial_evaluator_create(int device, dsp_trial_evaluator **out)
-{
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    // no device is touched here: a device that does not exist is reported by the first call that evaluates
-    auto e = std::make_unique<dsp_trial_evaluator>();
-    e->device = device;
-    *out = e.release();
-    return DSP_OK;
-}
+int dsp_trial_evaluator_create(int device, dsp_trial_evaluator **out) { return dsp::stage_create(device, out); }
 
-void dsp_trial_evaluator_destroy(dsp_trial_evaluator *e)
-{
-    if (!e) return;
-    dsp::DeviceScope scope(e->device);
-    e->spans.release();
-    delete e;
-}
+void dsp_trial_evaluator_destroy(dsp_trial_evaluator *e) { dsp::stage_destroy(e); }
 
 int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, long n_rows, long n_columns, const int *truth, const dsp_trials_config *cfg,
                                dsp_trial_column *d_columns, long *d_sweep_tp, long *d_sweep_fp, int *d_fa_above, int *d_fa_equal, void *stream)
@@ -101,14 +63,13 @@ int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, lo
     if (!cfg) return capi_fail(DSP_EINVAL, "dsp_trials_config is NULL");
     if (cfg->n_thresholds < dsp::kTrialMinThresholds || cfg->n_thresholds > dsp::kTrialMaxThresholds)
         return capi_fail(DSP_EINVAL, "dsp_trials_config: n_thresholds must be 2 .. 1024, got " + std::to_string(cfg->n_thresholds));
-    if (const int rc = check_shape(n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_score_shape(n_rows, n_columns)) return rc;
     if (!d_columns && !d_sweep_tp && !d_sweep_fp && !d_fa_above && !d_fa_equal) return capi_fail(DSP_EINVAL, "every output is NULL");
     if (n_rows == 0) return DSP_OK;
     if (!d_scores) return capi_fail(DSP_EINVAL, "d_scores is NULL");
     if (!truth) return capi_fail(DSP_EINVAL, "truth is NULL");
-    if (const int rc = check_truth(truth, n_rows, n_columns)) return rc;
-    // (the grids: a block takes 1024 rows of 4 columns at least)
-    if ((double)n_rows * (double)n_columns >= 35184372088832.0) return capi_fail(DSP_EINVAL, "2^45 trials or more in one call");
+    if (const int rc = dsp::check_truth(truth, n_rows, n_columns)) return rc;
+    if (const int rc = dsp::check_trial_count(n_rows, n_columns)) return rc;
     std::vector<long> at((size_t)n_columns + 1, 0);
     const long targets = count_targets(truth, n_rows, at);
     const bool want_pairs = d_columns || d_fa_above || d_fa_equal;
@@ -125,8 +86,7 @@ int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, lo
     // target_offsets, S + 1 longs | truth, T ints | target_rows, one int per target
     const size_t n1 = (size_t)n_columns + 1, bytes = n1 * sizeof(long) + ((size_t)n_rows + (size_t)targets) * sizeof(int);
     dsp::SpanRing::Lease slot;
-    const hipError_t err = e->spans.acquire(bytes, slot);
-    if (err != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(err));
+    if (const int rc = dsp::lease(e->spans, bytes, slot)) return rc;
     long *h_offsets = static_cast<long *>(slot.h());
     int *h_truth = reinterpret_cast<int *>(h_offsets + n1), *h_rows = h_truth + n_rows;
     std::copy(at.begin(), at.end(), h_offsets);

@@ -1,5 +1,5 @@
-// capi_util.hpp -- error reporting, device scopes, the owner of device buffers, the ragged-span ring and the scans' host planner shared
-// by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
+// capi_util.hpp -- error reporting, device scopes, the owner of device buffers, the ragged-span ring, the scans' host planner and the
+// score-matrix stages' handle, shared by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
 // classifiers' front end classify_front.hpp).  Nothing here knows a plan: what reads one is mfcc_plan.hpp.
 #pragma once
 
@@ -9,6 +9,7 @@
 #include <climits>
 #include <condition_variable>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -105,6 +106,13 @@ struct SpanRing {
         }
     }
 };
+
+// `slot` (empty) leases a slot of `ring` with room for `bytes`: DSP_OK, or DSP_EHIP "the span ring: ..."
+inline int lease(SpanRing &ring, size_t bytes, SpanRing::Lease &slot)
+{
+    const hipError_t e = ring.acquire(bytes, slot);
+    return e == hipSuccess ? DSP_OK : capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(e));
+}
 
 // a device index the HIP runtime knows, or why not
 inline int check_device(int device)
@@ -296,6 +304,32 @@ struct DeviceScope {
     DeviceScope(const DeviceScope &) = delete;
     DeviceScope &operator=(const DeviceScope &) = delete;
 };
+
+// What a stage on a score matrix keeps between calls (dsp_segmenter, dsp_trial_evaluator, dsp_calibrator derive from it): its device, a
+// grow-only workspace and the ring its host arrays travel through.
+struct StageHandle {
+    int device = 0;
+    DeviceBuf<char> ws;
+    SpanRing spans;
+};
+// no device is touched here: a device that does not exist is reported by the first call that launches
+template <class H> int stage_create(int device, H **out)
+{
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
+    auto h = std::make_unique<H>();
+    h->device = device;
+    *out = h.release();
+    return DSP_OK;
+}
+template <class H> void stage_destroy(H *h)
+{
+    if (!h) return;
+    DeviceScope scope(h->device);
+    h->spans.release();
+    delete h;
+}
 }
 #define DSP_ON_DEVICE(dev)                                                                                        \
     dsp::DeviceScope dsp_device_scope_(dev);                                                                      \

@@ -162,8 +162,7 @@ int dsp_speaker_verify_ragged_device(dsp_speaker_verifier *v, const float *d_fea
     if (const int rc = upload_ubm(v)) return rc;
     // runs of consecutive clips whose partials fit max_run_doubles (at least one clip each); a clip's unit0 counts chunks within its run
     dsp::SpanRing::Lease slot;
-    const hipError_t e = v->spans.acquire((size_t)n_clips * sizeof(dsp::RowSpan), slot);
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(e));
+    if (const int rc = dsp::lease(v->spans, (size_t)n_clips * sizeof(dsp::RowSpan), slot)) return rc;
     dsp::RowSpan *h = static_cast<dsp::RowSpan *>(slot.h());
     const size_t per_chunk = dsp::verify_partial_doubles(1, n_speakers);
     std::vector<long> run_start{0};
@@ -225,8 +224,7 @@ int dsp_speaker_float_scan_device(dsp_speaker_verifier *v, const float *d_feats,
         return capi_fail(DSP_ENOMEM, "hipMalloc of the verifier's workspace");
     const size_t P = plan.pieces.size(), bytes = P * sizeof(dsp::RowSpan);
     dsp::SpanRing::Lease slot;
-    const hipError_t e = v->spans.acquire(2 * bytes, slot);
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("the span ring: ") + hipGetErrorString(e));
+    if (const int rc = dsp::lease(v->spans, 2 * bytes, slot)) return rc;
     std::memcpy(slot.h(), plan.pieces.data(), bytes);
     std::memcpy(static_cast<char *>(slot.h()) + bytes, plan.wins.data(), bytes);
     DSP_CAPI_HIP(slot.upload(2 * bytes, st));

@@ -379,7 +379,7 @@ __global__ __launch_bounds__(kThreads) void seg_stats_kernel(const float *__rest
     }
 }
 
-unsigned blocks_for(long items, long per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+unsigned blocks_for(long items, long per_block) { return (unsigned)ceil_div(items, per_block); }
 
 }  // namespace
 
@@ -398,12 +398,12 @@ hipError_t launch_segments(const SegCall &q, const SegWorkspace &ws, hipStream_t
             const long units = q.chunks * S;
             seg_mask_time_kernel<<<blocks_for(units, kWaves), kThreads, 0, st>>>(q.scores, q.offsets, q.n_recordings, S, units, q.on, q.off, best, ws.a, ws.b);
         } else {
-            const long groups = (S + 63) / 64, units = q.chunks * groups;
+            const long groups = ceil_div(S, 64), units = q.chunks * groups;
             seg_mask_columns_kernel<<<blocks_for(units, kWaves), kThreads, 0, st>>>(q.scores, q.offsets, q.n_recordings, S, groups, units, q.on, q.off, best,
                                                                                    ws.a, ws.b);
         }
     }
-    const long units = q.blocks * S, tiles = (units + kSegScanTile - 1) / kSegScanTile;
+    const long units = q.blocks * S, tiles = ceil_div(units, kSegScanTile);
     const unsigned track_blocks = blocks_for(tracks, kThreads), unit_blocks = blocks_for(units, kThreads);
     if (units > 0) {
         seg_carry_kernel<<<track_blocks, kThreads, 0, st>>>(ws.a, ws.b, ws.chunk_in, q.offsets, q.n_recordings, S, tracks);

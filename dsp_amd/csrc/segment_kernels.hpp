@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/dsp_amd.h"
+#include "score_matrix.hpp"
 
 namespace dsp {
 
@@ -141,7 +142,8 @@ __host__ __device__ inline int seg_block_segments(const SegState &st, long w0, i
     return count;
 }
 
-// The workspace, carved from one grow-only buffer (every part 256-byte aligned).  Nothing in it is read before the call has written it.
+// The workspace, laid out by seg_layout over one grow-only buffer (score_matrix.hpp Carver).  Nothing in it is read before the call
+// has written it.
 struct SegWorkspace {
     uint64_t *a = nullptr, *b = nullptr;                     // [words of all recordings][S]
     uint8_t *chunk_in = nullptr;                             // [chunks of all recordings][S]
@@ -151,31 +153,34 @@ struct SegWorkspace {
     long *base = nullptr;                                    // [units]: the unit's first segment in the output
     long *tile_sum = nullptr, *tile_base = nullptr;          // [ceil(units / kSegScanTile)]
 };
-inline size_t seg_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 // words, chunks and blocks here are counted over all columns (those of all recordings * S); units = blocks
+inline SegWorkspace seg_layout(Carver &c, long words, long chunks, long blocks, long windows, bool exclusive)
+{
+    const size_t tiles = (size_t)ceil_div(blocks, kSegScanTile);
+    SegWorkspace w;
+    w.a = c.take<uint64_t>((size_t)words);
+    w.b = c.take<uint64_t>((size_t)words);
+    w.chunk_in = c.take<uint8_t>((size_t)chunks);
+    if (exclusive) w.best = c.take<int>((size_t)windows);
+    w.prev_one = c.take<int>((size_t)blocks);
+    w.next_one = c.take<int>((size_t)blocks);
+    w.next_tail = c.take<int>((size_t)blocks);
+    w.counts = c.take<int>((size_t)blocks);
+    w.base = c.take<long>((size_t)blocks);
+    w.tile_sum = c.take<long>(tiles);
+    w.tile_base = c.take<long>(tiles);
+    return w;
+}
 inline size_t seg_workspace_bytes(long words, long chunks, long blocks, long windows, bool exclusive)
 {
-    const size_t tiles = (size_t)((blocks + kSegScanTile - 1) / kSegScanTile);
-    return 2 * seg_align((size_t)words * 8) + seg_align((size_t)chunks) + (exclusive ? seg_align((size_t)windows * 4) : 0) + 4 * seg_align((size_t)blocks * 4) +
-           seg_align((size_t)blocks * 8) + 2 * seg_align(tiles * 8);
+    Carver c;
+    seg_layout(c, words, chunks, blocks, windows, exclusive);
+    return c.at;
 }
 inline SegWorkspace seg_carve(char *p, long words, long chunks, long blocks, long windows, bool exclusive)
 {
-    const size_t tiles = (size_t)((blocks + kSegScanTile - 1) / kSegScanTile);
-    SegWorkspace w;
-    auto take = [&](size_t bytes) { char *q = p; p += seg_align(bytes); return q; };
-    w.a = reinterpret_cast<uint64_t *>(take((size_t)words * 8));
-    w.b = reinterpret_cast<uint64_t *>(take((size_t)words * 8));
-    w.chunk_in = reinterpret_cast<uint8_t *>(take((size_t)chunks));
-    if (exclusive) w.best = reinterpret_cast<int *>(take((size_t)windows * 4));
-    w.prev_one = reinterpret_cast<int *>(take((size_t)blocks * 4));
-    w.next_one = reinterpret_cast<int *>(take((size_t)blocks * 4));
-    w.next_tail = reinterpret_cast<int *>(take((size_t)blocks * 4));
-    w.counts = reinterpret_cast<int *>(take((size_t)blocks * 4));
-    w.base = reinterpret_cast<long *>(take((size_t)blocks * 8));
-    w.tile_sum = reinterpret_cast<long *>(take(tiles * 8));
-    w.tile_base = reinterpret_cast<long *>(take(tiles * 8));
-    return w;
+    Carver c{p};
+    return seg_layout(c, words, chunks, blocks, windows, exclusive);
 }
 
 // What one call needs on the device.  d_offsets: four arrays of n_recordings + 1 longs one behind the other -- window, word, chunk and

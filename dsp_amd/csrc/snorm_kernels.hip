@@ -19,7 +19,6 @@
 //                        tile and reads its statistic once, the row's statistic being one broadcast load per row
 // No float atomics and no fused multiply-add: a record depends on its vector alone, whatever its place, its axis, the grid and the
 // stream.  Every row and column index is checked before a load or a store.
-#include <algorithm>
 #include <cmath>
 #include <mutex>
 
@@ -33,15 +32,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-__device__ inline long block_index() { return (long)blockIdx.y * gridDim.x + blockIdx.x; }
-
-__device__ inline unsigned key_of(float x)
-{
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float float_of(unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); }
-__device__ inline bool is_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }
 __device__ inline double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ inline int selected_of(int top_k, int n_finite) { return (top_k == 0 || top_k > n_finite) ? n_finite : top_k; }
 
@@ -380,15 +370,6 @@ __global__ __launch_bounds__(kThreads) void snorm_apply_tiled_kernel(const float
         if (mode != DSP_NORM_Z) row = side_of(&row_stats[r], std_floor);
         out[r * S + c] = normalised(scores[r * S + c], mode, row, col);
     }
-}
-
-long ceil_div(long a, long b) { return (a + b - 1) / b; }
-
-// a grid of `blocks` blocks as x * y; the kernels count them with block_index() and return past `blocks`
-dim3 grid_for(long blocks)
-{
-    const long x = std::min<long>(std::max<long>(blocks, 1), 1L << 20);
-    return dim3((unsigned)x, (unsigned)ceil_div(std::max<long>(blocks, 1), x));
 }
 
 // Both statistics kernels may ask for more dynamic LDS than a kernel gets by default (64 KiB): the resident vector form up to 128 KiB,

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dsp_amd.h"
+#include "score_matrix.hpp"
 
 namespace dsp {
 

@@ -27,15 +27,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-__device__ inline long block_index() { return (long)blockIdx.y * gridDim.x + blockIdx.x; }
-
-__device__ inline unsigned key_of(float x)
-{
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float float_of(unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); }
-
 struct Range { double lo, hi, step; };
 __device__ inline Range range_of(const TrialStat &s, int n)
 {
@@ -54,7 +45,7 @@ struct Fold {
     {
         if (x != x) { ++n_nan; return; }
         if (target) ++n_target; else ++n_nontarget;
-        if (fabsf(x) <= 3.402823466e+38f) {
+        if (is_finite(x)) {
             const unsigned k = key_of(x);
             max_key = max(max_key, k);
             min_inv = max(min_inv, ~k);
@@ -356,14 +347,6 @@ __global__ __launch_bounds__(kThreads) void trial_pooled_kernel(const long *__re
         cols[S].auc_u2 = sum_u[0];
         cols[S].auc = sum_p[0] ? (double)sum_u[0] / (double)(2 * sum_p[0]) : NAN;
     }
-}
-
-long ceil_div(long a, long b) { return (a + b - 1) / b; }
-// a grid of `blocks` blocks (at most 2^36) as x * y; the kernels count them with block_index() and return past `blocks`
-dim3 grid_for(long blocks)
-{
-    const long x = std::min<long>(std::max<long>(blocks, 1), 1L << 20);
-    return dim3((unsigned)x, (unsigned)ceil_div(std::max<long>(blocks, 1), x));
 }
 
 }  // namespace

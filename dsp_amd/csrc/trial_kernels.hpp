@@ -8,11 +8,12 @@
 #include <cstdint>
 
 #include "../../include/dsp_amd.h"
+#include "score_matrix.hpp"
 
 namespace dsp {
 
-constexpr long kTrialMaxColumns = 1L << 19;
-constexpr long kTrialMaxRows = 1L << 31;                     // exclusive
+constexpr long kTrialMaxColumns = kScoreMaxColumns;          // (check_score_shape's)
+constexpr long kTrialMaxRows = kScoreMaxRows;                // exclusive
 constexpr long kTrialMaxPairs = 1L << 46;
 constexpr int kTrialMinThresholds = 2, kTrialMaxThresholds = 1024;
 // below this many columns a wavefront's lanes run along the rows of one column (64 consecutive rows per load, S floats apart with S
@@ -79,8 +80,8 @@ struct TrialStat {
     unsigned long long n_target, n_nontarget, n_nan;
 };
 
-// The workspace, carved from one grow-only buffer (every part 256-byte aligned).  `zeroed` bytes from its start are cleared by every
-// call that reads them; the rest is written before it is read.
+// The workspace, laid out by trial_layout over one grow-only buffer (score_matrix.hpp Carver).  `zeroed` bytes from its start are
+// cleared by every call that reads them; the rest is written before it is read.
 struct TrialWorkspace {
     TrialStat *stat = nullptr;                               // [S + 1], the last one pooled                        (zeroed)
     unsigned *hist = nullptr;                                // [S][2][n + 1]: class 0 = target                      (zeroed)
@@ -90,28 +91,22 @@ struct TrialWorkspace {
     long *u2 = nullptr, *pn = nullptr;                       // [S]: a column's auc_u2 and P N
     size_t zeroed = 0;
 };
-inline size_t trial_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-inline size_t trial_workspace_bytes(long columns, int n, long targets)
-{
-    return trial_align((size_t)(columns + 1) * sizeof(TrialStat)) + trial_align((size_t)columns * 2 * (n + 1) * 4) + trial_align(2 * (size_t)(n + 1) * 8) +
-           3 * trial_align((size_t)targets * 4) + 2 * trial_align((size_t)columns * 8);
-}
-inline TrialWorkspace trial_carve(char *p, long columns, int n, long targets)
+inline TrialWorkspace trial_layout(Carver &c, long columns, int n, long targets)
 {
     TrialWorkspace w;
-    char *const p0 = p;
-    auto take = [&](size_t bytes) { char *q = p; p += trial_align(bytes); return q; };
-    w.stat = reinterpret_cast<TrialStat *>(take((size_t)(columns + 1) * sizeof(TrialStat)));
-    w.hist = reinterpret_cast<unsigned *>(take((size_t)columns * 2 * (n + 1) * 4));
-    w.pooled_hist = reinterpret_cast<unsigned long long *>(take(2 * (size_t)(n + 1) * 8));
-    w.zeroed = (size_t)(p - p0);
-    w.target_score = reinterpret_cast<float *>(take((size_t)targets * 4));
-    w.above = reinterpret_cast<unsigned *>(take((size_t)targets * 4));
-    w.equal = reinterpret_cast<unsigned *>(take((size_t)targets * 4));
-    w.u2 = reinterpret_cast<long *>(take((size_t)columns * 8));
-    w.pn = reinterpret_cast<long *>(take((size_t)columns * 8));
+    w.stat = c.take<TrialStat>((size_t)columns + 1);
+    w.hist = c.take<unsigned>((size_t)columns * 2 * (n + 1));
+    w.pooled_hist = c.take<unsigned long long>(2 * (size_t)(n + 1));
+    w.zeroed = c.at;
+    w.target_score = c.take<float>((size_t)targets);
+    w.above = c.take<unsigned>((size_t)targets);
+    w.equal = c.take<unsigned>((size_t)targets);
+    w.u2 = c.take<long>((size_t)columns);
+    w.pn = c.take<long>((size_t)columns);
     return w;
 }
+inline size_t trial_workspace_bytes(long columns, int n, long targets) { Carver c; trial_layout(c, columns, n, targets); return c.at; }
+inline TrialWorkspace trial_carve(char *p, long columns, int n, long targets) { Carver c{p}; return trial_layout(c, columns, n, targets); }
 
 // What one call needs on the device.  truth[T], target_offsets[S + 1] and target_rows[targets] are the device copies of the host's
 // arrays.  Everything is enqueued on `stream`; nothing waits for it.
