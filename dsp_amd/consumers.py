@@ -16,6 +16,8 @@
                                                               2fa/audio/speaker/adapt_ubm.py:27-28,97-99
   ScoreNormalizer   Z-, T- and S-norm against cohorts, all members or the K closest (no counterpart in the reference: one threshold, 1.1,
                                                               for every model and clip, 2fa/audio/audio_driver.py:10)
+  Vad            energy-based frame selection between the front end and the models (no counterpart in the reference:
+                                                              extract_features_from_array keeps every row, gmm_utils.py:28-62)
   UbmTrainer     GaussianMixture(covariance_type="diag").fit    2fa/audio/speaker/train_ubm.py
   StopTrainer    the stop-word net's Keras fit, many seeds at once  2fa/audio/word/python/keyword_classifier.py:155-232
   quantize_gmm   the Q6 / Q11 / Q8 tables of gmm_params.inc     2fa/audio/pico-audio/src/gmm_params.inc
@@ -590,10 +592,12 @@ class SpeakerFrontEnd(_lib.Closing):
                 getattr(self, part).close()
                 setattr(self, part, None)
 
-    def features(self, signal, offsets):
+    def features(self, signal, offsets, vad=None):
         """signal: cuda float32 [total] at 16 kHz, clip c = samples [offsets[c], offsets[c + 1]) -> (feats, frame_offsets): cuda float32
         [F][13] with clip c's rows in [frame_offsets[c], frame_offsets[c + 1]) (numpy int64), 1 + n // 160 of them for n samples.  As it
-        is, the input of UbmTrainer.fit, SpeakerEnroller.enroll and SpeakerVerifier.verify."""
+        is, the input of UbmTrainer.fit, SpeakerEnroller.enroll and SpeakerVerifier.verify.  vad: a Vad made for this front end's plan:
+        the rows it keeps are selected AFTER the CMVN (Kaldi's order: silence still shapes the sliding statistics), and frame_offsets
+        are its kept_offsets; ValueError names the first clip that keeps no row (the enroller would refuse it)."""
         off = np.asarray(offsets, np.int64)
         if off.ndim != 1 or off.size < 1:
             raise ValueError("offsets must be a 1-d array of n_clips + 1 sample positions")
@@ -603,7 +607,14 @@ class SpeakerFrontEnd(_lib.Closing):
             c = int(short[0])
             raise ValueError(f"clip {c} has {int(off[c + 1] - off[c])} samples: extract_features_from_array yields no rows below n_fft = {n_fft}")
         mfcc, fo = self.plan.clips_ragged(signal, off, 2**31 - 1)
-        return self.cmvn.apply(mfcc, fo), fo
+        feats = self.cmvn.apply(mfcc, fo)
+        if vad is None:
+            return feats, fo
+        flags, kept, _records = vad.run(signal, off, fo)
+        silent = np.flatnonzero(np.diff(kept) == 0)
+        if silent.size:
+            raise ValueError(f"clip {int(silent[0])} keeps no row: the voice activity detector found no speech in it")
+        return vad.select(feats, flags, fo, kept), kept
 
 
 def _gmm_float_params(params: dict, name: str):
@@ -1144,6 +1155,189 @@ class ScoreNormalizer(_lib.Closing):
         if mode != "t":
             col = self.stats(cc, "column", top_k)
         return self.apply(x, mode, row, col, std_floor)
+
+
+class Vad(_lib.Closing):
+    """Voice activity detection between the front end and the models (dsp_vad_*, dsp_rows_*): float64 frame power of the rows of an
+    MFCC plan, an energy threshold against each clip's own level (librosa's top_db with ref = np.max, or the mean, or an absolute
+    power), Kaldi's smoothing over context_frames, a hangover of pad_frames, and the selection of the kept rows of any matrix.  The
+    reference has no such step.  The library keeps nothing between calls, so there is no native handle: the object holds the
+    configuration and a grow-only workspace tensor on its GPU, and close() (or `with`) lets that go.  One stream at a time per Vad."""
+
+    _ws = None
+
+    def __init__(self, plan_or_cfg, reference="max", threshold_db: float = -60.0, floor_db: float = float("-inf"), context_frames: int = 0,
+                 proportion: float = 0.6, pad_frames: int = 0, device: int = 0):
+        """plan_or_cfg: the MfccPlan (or its MfccConfig) whose rows are to be filtered: frame_length, hop_length and framing are taken
+        from it.  threshold_db is relative to the reference ("max", "mean") or to power 1 ("absolute"); floor_db is an absolute power
+        below which nothing is speech."""
+        mfcc = getattr(plan_or_cfg, "cfg", plan_or_cfg)
+        if not isinstance(mfcc, _lib.MfccConfig):
+            raise ValueError("plan_or_cfg must be an MfccPlan or an MfccConfig")
+        if reference not in _lib.VAD_REFERENCES:
+            raise ValueError('reference must be "absolute", "max" or "mean"')
+        if int(device) < 0:
+            raise ValueError("device index out of range")
+        threshold_db, floor_db, proportion = float(threshold_db), float(floor_db), float(proportion)
+        if np.isnan(threshold_db) or threshold_db == float("inf") or np.isnan(floor_db):
+            raise ValueError("threshold_db must be below +inf and floor_db must not be NaN")
+        if not (0 <= int(context_frames) <= 64 and 0 <= int(pad_frames) <= 64):
+            raise ValueError("context_frames and pad_frames must be 0 .. 64")
+        if not 0.0 < proportion <= 1.0:
+            raise ValueError("proportion must lie in (0, 1]")
+        self._L = _lib.load()
+        self.device = int(device)
+        self.cfg = _lib.VadConfig()
+        self._L.dsp_vad_default_config(C.byref(mfcc), C.byref(self.cfg))
+        self.cfg.reference = _lib.VAD_REFERENCES[reference]
+        self.cfg.threshold_ratio = self._L.dsp_vad_ratio_from_db(threshold_db)
+        self.cfg.floor_power = self._L.dsp_vad_ratio_from_db(floor_db)
+        self.cfg.context_frames, self.cfg.proportion, self.cfg.pad_frames = int(context_frames), proportion, int(pad_frames)
+        geo = _lib.VadGeometry()
+        rc = self._L.dsp_vad_geometry_for(C.byref(self.cfg), C.byref(geo))
+        if rc < 0:
+            raise ValueError(_lib.last_error())
+        self.geometry = {name: getattr(geo, name) for name, _ in _lib.VadGeometry._fields_}
+
+    def close(self):
+        self._L = self._ws = None
+
+    def _lib_or_closed(self):
+        if self._L is None:
+            raise _lib.DspError("the Vad is closed")
+        return self._L
+
+    def _workspace(self, n_clips, n_rows):
+        """(pointer, bytes) of the workspace, grown to what n_clips clips of n_rows rows need"""
+        import torch
+        need = _lib.check(self._L.dsp_vad_workspace_bytes(n_clips, n_rows), "dsp_vad_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need + need // 2, dtype=torch.uint8, device=f"cuda:{self.device}")
+        return self._ws.data_ptr(), self._ws.numel()
+
+    def _on_device(self, x, what, dtype, dims=(1,)):
+        import torch
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.dim() in dims):
+            raise ValueError(f"{what} must be a {str(dtype).replace('torch.', '')} CUDA tensor")
+        if x.device.index != self.device:
+            raise ValueError(f"{what} is on GPU {x.device.index}, the Vad on GPU {self.device}")
+        return x.contiguous()
+
+    def _signal(self, signal, offsets, frame_offsets):
+        import torch
+        signal = self._on_device(signal, "signal", torch.float32)
+        off, n, _, _ = _lib.ragged_signal(signal, offsets, torch.float32)
+        fo = _frame_offsets(frame_offsets)
+        if fo.size != n + 1:
+            raise ValueError("frame_offsets must hold one entry more than there are clips")
+        return signal, off, n, fo
+
+    def power(self, signal, offsets, frame_offsets):
+        """signal: cuda float32 [total], clip c = samples [offsets[c], offsets[c + 1]) and rows [frame_offsets[c], frame_offsets[c + 1]) ->
+        cuda float64 [frame_offsets[-1]]: the mean square of each row's frame (rows of no clip are zeros).  Only enqueues."""
+        import torch
+        L = self._lib_or_closed()
+        signal, off, n, fo = self._signal(signal, offsets, frame_offsets)
+        out = torch.zeros(int(fo[-1]), dtype=torch.float64, device=signal.device)
+        if n and fo[-1] > fo[0]:
+            ws, ws_bytes = self._workspace(n, int(fo[-1] - fo[0]))
+            _lib.check(L.dsp_vad_frame_power_ragged_device(self.device, C.byref(self.cfg), signal.data_ptr(), n, off, fo.ctypes.data_as(_lib.LP), out.data_ptr(),
+                                                           ws, ws_bytes, _lib.current_stream(signal)), "dsp_vad_frame_power_ragged_device")
+        return out
+
+    def _decide(self, entry, name, where, n, fo, levels, *front):
+        import torch
+        R = int(fo[-1])
+        flags = torch.zeros(R, dtype=torch.uint8, device=where.device)
+        level = torch.zeros(R, dtype=torch.float32, device=where.device) if levels else None
+        clips = torch.zeros((n, 4), dtype=torch.int64, device=where.device)
+        kept = np.zeros(n + 1, np.int64)
+        if n and fo[-1] > fo[0]:
+            ws, ws_bytes = self._workspace(n, int(fo[-1] - fo[0]))
+            _lib.check(entry(self.device, C.byref(self.cfg), *front, fo.ctypes.data_as(_lib.LP), flags.data_ptr(), level.data_ptr() if levels else None,
+                             clips.data_ptr(), kept.ctypes.data_as(_lib.LP), ws, ws_bytes, _lib.current_stream(where)), name)
+        records = clips.cpu().numpy().view(np.dtype(_lib.VAD_CLIP_DTYPE)).reshape(-1)
+        if not (n and fo[-1] > fo[0]):                      # no row, no launch: the records of clips without rows
+            scaled = float(self.cfg.reference == _lib.VAD_REF_ABSOLUTE) * self.cfg.threshold_ratio
+            records["reference"] = float(self.cfg.reference == _lib.VAD_REF_ABSOLUTE)
+            records["threshold"] = scaled if scaled >= self.cfg.floor_power else self.cfg.floor_power
+            records["first_kept"] = records["last_kept"] = -1
+        return (flags, kept, records, level) if levels else (flags, kept, records)
+
+    def decide(self, power, frame_offsets, levels: bool = False):
+        """power: cuda float64 [R] as power() returns it -> (flags, kept_offsets, records[, level_db]): flags cuda uint8 [R], 1 = speech;
+        kept_offsets numpy int64 [n_clips + 1], the prefix sums of the kept rows; records numpy (reference, threshold, n_raw, n_kept,
+        first_kept, last_kept) per clip; level_db cuda float32 [R] = 10 log10(P / threshold), a score track for Segmenter.  Waits for
+        the stream once."""
+        import torch
+        L = self._lib_or_closed()
+        power = self._on_device(power, "power", torch.float64)
+        fo = _frame_offsets(frame_offsets)
+        if int(fo[-1]) > power.shape[0]:
+            raise ValueError("frame_offsets run past the end of power")
+        n = fo.size - 1
+        return self._decide(L.dsp_vad_decide_ragged_device, "dsp_vad_decide_ragged_device", power, n, fo, levels, power.data_ptr(), n)
+
+    def run(self, signal, offsets, frame_offsets, levels: bool = False):
+        """power() and decide() in one call, the power kept in the workspace -> what decide() returns."""
+        L = self._lib_or_closed()
+        signal, off, n, fo = self._signal(signal, offsets, frame_offsets)
+        return self._decide(L.dsp_vad_run_ragged_device, "dsp_vad_run_ragged_device", signal, n, fo, levels, signal.data_ptr(), n, off)
+
+    def kept_offsets(self, flags, frame_offsets) -> np.ndarray:
+        """flags from any source, cuda uint8 [R] -> numpy int64 [n_clips + 1]: the prefix sums of each clip's non-zero flags
+        (dsp_rows_kept_offsets_device).  Waits for the stream once."""
+        import torch
+        L = self._lib_or_closed()
+        flags = self._on_device(flags, "flags", torch.uint8)
+        fo = _frame_offsets(frame_offsets)
+        if int(fo[-1]) > flags.shape[0]:
+            raise ValueError("frame_offsets run past the end of flags")
+        n = fo.size - 1
+        kept = np.zeros(n + 1, np.int64)
+        if n and fo[-1] > fo[0]:
+            ws, ws_bytes = self._workspace(n, int(fo[-1] - fo[0]))
+            _lib.check(L.dsp_rows_kept_offsets_device(self.device, flags.data_ptr(), n, fo.ctypes.data_as(_lib.LP), kept.ctypes.data_as(_lib.LP), ws, ws_bytes,
+                                                      _lib.current_stream(flags)), "dsp_rows_kept_offsets_device")
+        return kept
+
+    def select(self, x, flags, frame_offsets, kept_offsets, index: bool = False):
+        """x: cuda float32 [R][d] (d 1 .. 64) or [R]; flags cuda uint8 [R]; kept_offsets as decide(), run() or kept_offsets() gave them ->
+        the rows whose flag is set, in order: a new cuda float32 [kept_offsets[-1]][d] (or [kept]), and with index their original row
+        numbers as a cuda int64 [kept].  Only enqueues."""
+        import torch
+        L = self._lib_or_closed()
+        x = self._on_device(x, "x", torch.float32, (1, 2))
+        flags = self._on_device(flags, "flags", torch.uint8)
+        fo = _frame_offsets(frame_offsets)
+        ko = _lib.long_array(kept_offsets, fo.size, "kept_offsets")
+        d = x.shape[1] if x.dim() == 2 else 1
+        if not 1 <= d <= 64:
+            raise ValueError("x must have 1 .. 64 columns")
+        if int(fo[-1]) > min(x.shape[0], flags.shape[0]):
+            raise ValueError("frame_offsets run past the end of x or flags")
+        n, kept = fo.size - 1, int(ko[-1]) if fo.size > 1 else 0
+        out = torch.zeros((kept, d) if x.dim() == 2 else (kept,), dtype=torch.float32, device=x.device)
+        rows = torch.zeros(kept, dtype=torch.int64, device=x.device) if index else None
+        if n and fo[-1] > fo[0]:
+            ws, ws_bytes = self._workspace(n, int(fo[-1] - fo[0]))
+            _lib.check(L.dsp_rows_select_ragged_device(self.device, x.data_ptr(), d, flags.data_ptr(), n, fo.ctypes.data_as(_lib.LP), ko.ctypes.data_as(_lib.LP),
+                                                       out.data_ptr() if kept else None, rows.data_ptr() if index and kept else None, ws, ws_bytes,
+                                                       _lib.current_stream(x)), "dsp_rows_select_ragged_device")
+        return (out, rows) if index else out
+
+    def trim_spans(self, records, offsets):
+        """Host only, librosa's trim: records as decide() or run() returned them, offsets the clips' sample offsets -> (starts, lengths,
+        n): clip c cut to its first and last kept row, starts absolute, length 0 where nothing is kept; n clips keep something."""
+        L = self._lib_or_closed()
+        off, n = _lib.c_offsets(offsets)
+        rec = np.ascontiguousarray(records, np.dtype(_lib.VAD_CLIP_DTYPE))
+        if rec.shape != (n,):
+            raise ValueError(f"records must hold one entry per clip: {n}")
+        starts, lengths = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        kept = _lib.check(L.dsp_vad_trim_spans(C.byref(self.cfg), off, n, rec.ctypes.data, starts.ctypes.data_as(_lib.LP), lengths.ctypes.data_as(_lib.LP)),
+                          "dsp_vad_trim_spans")
+        return starts, lengths, kept
 
 
 class UbmTrainer(_lib.Handle):

@@ -232,6 +232,24 @@ NORM_MODES = {"z": NORM_Z, "t": NORM_T, "s": NORM_S}
 COHORT_MAX_LENGTH = COHORT_MAX_TOP_K = 1 << 22
 
 
+class VadConfig(C.Structure):
+    """dsp_vad_config (include/dsp_amd.h), 56 bytes: the framing of the plan whose rows are filtered, and the decision."""
+
+    _fields_ = [("frame_length", C.c_int), ("hop_length", C.c_int), ("framing", C.c_int), ("reference", C.c_int), ("threshold_ratio", C.c_double),
+                ("floor_power", C.c_double), ("context_frames", C.c_int), ("proportion", C.c_double), ("pad_frames", C.c_int)]
+
+
+class VadGeometry(C.Structure):
+    """dsp_vad_geometry (include/dsp_amd.h): what dsp_vad_geometry_for reports."""
+
+    _fields_ = [("g", C.c_int), ("m", C.c_int), ("samples_per_tile", C.c_int), ("rows_per_tile", C.c_int), ("halo_rows", C.c_int)]
+
+
+VAD_CLIP_DTYPE = [("reference", "<f8"), ("threshold", "<f8"), ("n_raw", "<i4"), ("n_kept", "<i4"), ("first_kept", "<i4"), ("last_kept", "<i4")]
+VAD_REF_ABSOLUTE, VAD_REF_MAX, VAD_REF_MEAN = 0, 1, 2
+VAD_REFERENCES = {"absolute": VAD_REF_ABSOLUTE, "max": VAD_REF_MAX, "mean": VAD_REF_MEAN}
+
+
 class SvmTrainProblem(C.Structure):
     """dsp_svm_train_problem (include/dsp_amd.h), 40 bytes: rows on the host, a box bound per label, gamma."""
 
@@ -499,6 +517,16 @@ PROTOTYPES = {
     "dsp_calibration_apply_device": (ip, [vp, vp, lg, lg, lp, P(Calibration), vp, vp]),
     "dsp_cohort_stats_device": (ip, [ip, vp, lg, lg, ip, ip, vp, vp]),
     "dsp_score_normalize_device": (ip, [ip, vp, lg, lg, vp, vp, P(SnormConfig), vp, vp]),
+    "dsp_vad_default_config": (None, [cfgp, P(VadConfig)]),
+    "dsp_vad_ratio_from_db": (db, [db]),
+    "dsp_vad_geometry_for": (ip, [P(VadConfig), P(VadGeometry)]),
+    "dsp_vad_workspace_bytes": (lg, [lg, lg]),
+    "dsp_vad_frame_power_ragged_device": (ip, [ip, P(VadConfig), vp, lg, lp, lp, vp, vp, lg, vp]),
+    "dsp_vad_decide_ragged_device": (ip, [ip, P(VadConfig), vp, lg, lp, vp, vp, vp, lp, vp, lg, vp]),
+    "dsp_vad_run_ragged_device": (ip, [ip, P(VadConfig), vp, lg, lp, lp, vp, vp, vp, lp, vp, lg, vp]),
+    "dsp_rows_kept_offsets_device": (ip, [ip, vp, lg, lp, lp, vp, lg, vp]),
+    "dsp_rows_select_ragged_device": (ip, [ip, vp, ip, vp, lg, lp, lp, vp, vp, vp, lg, vp]),
+    "dsp_vad_trim_spans": (lg, [P(VadConfig), lp, lg, vp, lp, lp]),
     "dsp_svm_trainer_create": (ip, [ip, ip, vpp]),
     "dsp_svm_trainer_destroy": (None, [vp]),
     "dsp_svm_train_set_device": (ip, [vp, vp, lg, vp, lg, vp, vp, vp, vp, vp]),

@@ -1308,6 +1308,108 @@ int dsp_score_normalize_device(int device, const float *d_scores, long n_rows, l
                                const dsp_cohort_stat *d_col_stats,    /* [S], needed by DSP_NORM_Z and DSP_NORM_S */
                                const dsp_snorm_config *cfg, float *d_out, void *stream);
 
+/* VOICE ACTIVITY DETECTION: frame power, speech flags and row selection between the front end and the models (DESIGN.md 3.25,
+ * INTEGRATION.md 6q).  The reference has no such step: extract_features_from_array (2fa/audio/speaker/gmm_utils.py:28-62) keeps every
+ * row, so the room noise that opens and closes a recording goes into the UBM, every MAP mean and both terms of every LLR.  This is
+ * Kaldi's compute-vad-energy + select-voiced-frames and librosa's effects.split / trim, restated; librosa is not pinned.
+ *
+ * Rows.  Clip c is samples [offsets[c], offsets[c + 1]) of d_signal (float32) and rows [frame_offsets[c], frame_offsets[c + 1]) of
+ * every per-row array (d_power, d_flags, d_level_db, a matrix to select from), as dsp_mfcc_ragged_frame_offsets gives them for a plan
+ * of the same frame_length, hop_length and framing: row t is samples [t hop - lead, t hop - lead + frame_length) of its clip, zeros
+ * outside it, lead = 0 (DSP_FRAMING_COMPLETE), frame_length - hop (DSP_FRAMING_STREAM, hop <= frame_length) or frame_length / 2
+ * (DSP_FRAMING_CENTER, frame_length even).  Positions outside the clip are never loaded.  A clip may bring fewer rows than
+ * dsp_mfcc_frames_for gives its length (a max_frames cap), never more.  Both offset arrays are HOST arrays, read before a call returns.
+ *
+ * Frame power.  g = gcd(hop, frame_length, lead) (lead left out when 0), m = frame_length / g <= 64, frame_length <= 4096.  Sub-block b
+ * of a clip is its samples [b g, b g + g), the last one zero-extended; its sum s[b] of squares is float64 (a float32's square is
+ * exact there) over a tree g alone fixes: sample e of the sub-block belongs to quad e / 4 and partial (e / 4) mod W, W the least
+ * power of two >= ceil(g / 4), at most 64; a partial adds its samples in ascending order; the partials are halved, p[l] += p[l + off]
+ * for off = W / 2 ... 1.  Frame t adds s[b0] ... s[b0 + m - 1], b0 = (t hop - lead) / g, in ascending order, sub-blocks outside the
+ * clip skipped, and P[t] = that sum / frame_length.  Against np.mean(frame ** 2) in float64: within 2 frame_length 2^-53 relative.
+ *
+ * Decision, per clip, over its rows with finite P:
+ *   reference  DSP_VAD_REF_ABSOLUTE 1.0; DSP_VAD_REF_MAX the largest (threshold_ratio 1e-6 = librosa's top_db 60 with ref = np.max);
+ *              DSP_VAD_REF_MEAN their mean: finite rows as they are and the others as +0.0 over tiles of 256 rows from row 0, each
+ *              tile's 256 leaves halved (v[i] += v[i + off], off = 128 ... 1), the tiles added in ascending order, / the finite count.
+ *              No finite row: 0.
+ *   threshold  s = reference * threshold_ratio; threshold = (s >= floor_power) ? s : floor_power.  Both numbers are linear powers
+ *              (dsp_vad_ratio_from_db(db) = pow(10, db / 10) on the host): no log or pow runs on the device before the decision.
+ *   raw[t]     isfinite(P[t]) && P[t] > threshold.  Strict: an all-zero clip keeps nothing (librosa's power_to_db clamps at amin
+ *              and would keep every row of such a clip).
+ *   sm[t]      Kaldi's smoothing, c = context_frames 0 .. 64, p = proportion in (0, 1]: over rows [max(0, t - c), min(T - 1, t + c)]
+ *              of the clip, (double)(raw flags set) >= (double)(rows in the window) * p.  c = 0: sm = raw.
+ *   keep[t]    the hangover, pad_frames 0 .. 64: any sm[u] with |u - t| <= pad_frames inside the clip.
+ * d_flags[row] = keep as 0 / 1.  d_level_db[row] (may be NULL) = (float)(10 log10(P / threshold)), whatever IEEE gives for 0 and
+ * non-finite operands: a score track that dsp_segments_device takes as one column (hysteresis, gap merge, minimum length in dB).
+ * d_clips[c] (may be NULL) = {reference, threshold, raw rows, kept rows, first and last kept row (-1: none)}.  kept_offsets[n_clips + 1]
+ * is a HOST array, the prefix sums of the kept rows, because every consumer takes host offsets: dsp_vad_decide_ragged_device,
+ * dsp_vad_run_ragged_device and dsp_rows_kept_offsets_device return when it is filled, after ONE wait for the stream.
+ *
+ * Selection.  dsp_rows_select_ragged_device copies the rows of d_in[..][d] (float32, d 1 .. 64) whose flag is not 0 to d_out, order
+ * kept: output row kept_offsets[c] + (rank of t among clip c's kept rows) is input row frame_offsets[c] + t, which d_row_index (int64,
+ * may be NULL) records.  The flags may come from anywhere; dsp_rows_kept_offsets_device counts them.  d_out holds kept_offsets[n_clips]
+ * rows and must not overlap the rows of d_in it reads.  Only enqueues.
+ *
+ * No handle: the stage keeps nothing between calls, so there is nothing to create or destroy.  What a call needs on the device lies
+ * in the caller's d_workspace of at least dsp_vad_workspace_bytes(n_clips, rows) bytes, rows = frame_offsets[n_clips] -
+ * frame_offsets[0], 256-byte aligned (hipMalloc's alignment), whose contents before the call do not matter and which one stream
+ * at a time may use.  dsp_vad_run_ragged_device keeps the power there.  Every output is the same bits whatever the batch around a
+ * clip, its position, the grid, the stream and the workspace's contents.
+ *
+ * DSP_EINVAL, before a device is touched, the first of: cfg NULL; hop_length < 1; frame_length outside 1 .. 4096; an unknown
+ * framing; an odd frame_length under DSP_FRAMING_CENTER; hop_length > frame_length under DSP_FRAMING_STREAM; more than 64 sub-blocks
+ * per frame; an unknown reference; threshold_ratio or floor_power negative or NaN (or threshold_ratio infinite); context_frames or
+ * pad_frames outside 0 .. 64; proportion outside (0, 1]; device < 0; n_clips < 0 or >= 2^31; (n_clips == 0: DSP_OK, kept_offsets[0]
+ * = 0;) an offsets array NULL; sample offsets negative, decreasing or a clip of 2^31 samples or more; frame_offsets negative or
+ * decreasing; a clip with more rows than dsp_mfcc_frames_for gives it (the message names the clip); a NULL buffer that is not
+ * optional; a workspace NULL, misaligned or too small; d outside 1 .. 64; kept_offsets that do not start at 0, decrease or give a
+ * clip more rows than it has; d_out overlapping d_in.  Clips without rows are legal everywhere.
+ * dsp_vad_trim_spans (host only, librosa's trim): clip c with a kept row is cut to [first_kept hop, min(n, (last_kept + 1) hop)),
+ * starts[c] in absolute positions (offsets[c] + ...) and lengths[c]; a clip that keeps nothing gets starts[c] = offsets[c], lengths[c]
+ * = 0.  Returns the number of clips that keep something.
+ * Not covered: PCM16 input; scanners and stream sessions; Kaldi's log-energy mean (it needs a device log before the decision);
+ * spectral or model-based VAD; librosa's own numbers.                                                                              */
+#define DSP_VAD_REF_ABSOLUTE 0
+#define DSP_VAD_REF_MAX 1
+#define DSP_VAD_REF_MEAN 2
+typedef struct dsp_vad_config {
+    int frame_length, hop_length, framing;      /* those of the MFCC plan whose rows are filtered */
+    int reference;                              /* DSP_VAD_REF_* */
+    double threshold_ratio, floor_power;        /* linear powers */
+    int context_frames;
+    double proportion;
+    int pad_frames;
+} dsp_vad_config;
+typedef struct dsp_vad_clip {                                                       /* 32 bytes */
+    double reference, threshold;
+    int n_raw, n_kept, first_kept, last_kept;
+} dsp_vad_clip;
+typedef struct dsp_vad_geometry {
+    int g, m;                /* samples per sub-block, sub-blocks per frame */
+    int samples_per_tile;    /* the samples a tile's frames span */
+    int rows_per_tile;       /* rows a block takes at a time: results must not depend on where a clip's rows fall in them */
+    int halo_rows;           /* context_frames + pad_frames: rows on either side of a tile whose raw flags are computed again */
+} dsp_vad_geometry;
+/* framing from the plan's config; DSP_VAD_REF_MAX, ratio 1e-6, floor 0, context 0, proportion 0.6 (Kaldi's), pad 0 */
+void dsp_vad_default_config(const dsp_mfcc_config *mfcc, dsp_vad_config *cfg);
+double dsp_vad_ratio_from_db(double db);
+int dsp_vad_geometry_for(const dsp_vad_config *cfg, dsp_vad_geometry *out);        /* host only */
+long dsp_vad_workspace_bytes(long n_clips, long n_rows);                            /* host only; enough for every entry below */
+int dsp_vad_frame_power_ragged_device(int device, const dsp_vad_config *cfg, const float *d_signal, long n_clips, const long *offsets,
+                                      const long *frame_offsets, double *d_power, void *d_workspace, long workspace_bytes, void *stream);
+int dsp_vad_decide_ragged_device(int device, const dsp_vad_config *cfg, const double *d_power, long n_clips, const long *frame_offsets,
+                                 uint8_t *d_flags, float *d_level_db, dsp_vad_clip *d_clips, long *kept_offsets, void *d_workspace,
+                                 long workspace_bytes, void *stream);
+int dsp_vad_run_ragged_device(int device, const dsp_vad_config *cfg, const float *d_signal, long n_clips, const long *offsets,
+                              const long *frame_offsets, uint8_t *d_flags, float *d_level_db, dsp_vad_clip *d_clips, long *kept_offsets,
+                              void *d_workspace, long workspace_bytes, void *stream);
+int dsp_rows_kept_offsets_device(int device, const uint8_t *d_flags, long n_clips, const long *frame_offsets, long *kept_offsets,
+                                 void *d_workspace, long workspace_bytes, void *stream);
+int dsp_rows_select_ragged_device(int device, const float *d_in, int d, const uint8_t *d_flags, long n_clips, const long *frame_offsets,
+                                  const long *kept_offsets, float *d_out, long *d_row_index, void *d_workspace, long workspace_bytes,
+                                  void *stream);
+long dsp_vad_trim_spans(const dsp_vad_config *cfg, const long *offsets, long n_clips, const dsp_vad_clip *clips, long *starts, long *lengths);
+
 /* SVM TRAINING: the scrub-jay RBF-SVM from pooled features -- cepstrum/train.py:66-85 (StandardScaler, SVC(kernel="rbf",
  * probability=True, class_weight="balanced"), cross-validation) as batched SMO on the GPU.
  * d_feat[n][n_features] is float32 on the trainer's device (what dsp_mfcc_stats_device writes); labels[n] is a HOST array of 0 / 1,
