@@ -25,14 +25,17 @@ int capi_fail(int code, const std::string &msg);   // sets dsp_last_error() for 
 // small ring of pinned host / device buffer pairs, so that a call neither waits for the stream it enqueues on nor shares a buffer with
 // the call before it (which may still be running, on this stream or another).  A call holds its slot as a Lease: fill h(), upload(),
 // enqueue the kernels that read d(), and the lease's end -- on every exit -- records the slot's event behind them on the upload's stream
-// and hands the slot back.  A slot is reused only after that event: an acquirer that lands on a slot still leased waits for the lease to
-// end, then for the event.
+// and hands the slot back.  A slot is reused only after that event.  An acquirer takes the next slot that is neither leased nor waiting
+// for its event; where there is none the ring GROWS by a slot (kSlots to start with, kMaxSlots at most), because waiting for the event
+// would be waiting for the caller's stream: a caller that enqueues several calls behind a producer that has not finished -- an
+// augmentation takes four leases, a chain of pushes one each -- would find the host blocked in the fifth.  Only a ring of kMaxSlots
+// slots, all in flight, makes an acquirer wait: for the lease of the slot whose turn it is to end, then for its event.
 // Deadlock-free because no call holds two leases of one ring at once (each user takes one lease, launches, and lets it go before
 // it could ask the ring again), and no one waits for a lease while holding a lock a lease holder takes.
 namespace dsp {
 struct ClipSpan;
 struct SpanRing {
-    static constexpr int kSlots = 4;
+    static constexpr int kSlots = 4, kMaxSlots = 32;
     struct Slot { void *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false, held = false; };
     class Lease {
         friend struct SpanRing;
@@ -61,19 +64,35 @@ struct SpanRing {
             return hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, stream);
         }
     };
-    Slot slot[kSlots];
+    std::vector<std::unique_ptr<Slot>> slots;      // (their addresses stay put as the ring grows: leases point at them)
     int next = 0;
     std::mutex mu;
     std::condition_variable freed;
     // `out` (empty) leases a slot with room for `bytes` whose previous user has finished
     hipError_t acquire(size_t bytes, Lease &out)
     {
-        Slot *sp;
+        Slot *sp = nullptr;
         {
             std::unique_lock<std::mutex> lock(mu);
-            sp = &slot[next];
-            next = (next + 1) % kSlots;
-            freed.wait(lock, [sp] { return !sp->held; });
+            while ((int)slots.size() < kSlots) slots.emplace_back(new Slot);
+            const int n = (int)slots.size();
+            for (int i = 0; i < n && !sp; ++i) {      // from the slot whose turn it is: the first that is free and whose upload has been read
+                Slot *c = slots[(size_t)((next + i) % n)].get();
+                if (!c->held && (!c->used || hipEventQuery(c->done) == hipSuccess)) {
+                    sp = c;
+                    next = (next + i + 1) % n;
+                }
+            }
+            if (!sp && n < kMaxSlots) {               // every slot is in flight: one more, instead of a wait for the caller's stream
+                slots.emplace_back(new Slot);
+                sp = slots.back().get();
+                next = 0;
+            }
+            if (!sp) {
+                sp = slots[(size_t)next].get();
+                next = (next + 1) % n;
+                freed.wait(lock, [sp] { return !sp->held; });
+            }
             sp->held = true;
         }
         out.ring = this;
@@ -97,13 +116,15 @@ struct SpanRing {
     void release()      // on the owner's device, no lease outstanding
     {
         std::lock_guard<std::mutex> lock(mu);
-        for (Slot &s : slot) {
+        for (auto &sp : slots) {
+            Slot &s = *sp;
             if (s.used) (void)hipEventSynchronize(s.done);
             if (s.h) (void)hipHostFree(s.h);
             if (s.d) (void)hipFree(s.d);
             if (s.done) (void)hipEventDestroy(s.done);
-            s = Slot{};
         }
+        slots.clear();
+        next = 0;
     }
 };
 

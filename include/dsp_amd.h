@@ -815,7 +815,8 @@ int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_fea
  * ascending order, every level in ascending order.  The tree depends on n alone: there are no float atomics, and a fit is bit-identical
  * whatever the grid, the device's CU count, the rows' address or what the workspace held before.  L is summed in float64 throughout.
  * The iterations are enqueued on `stream` without a host round trip each (every launch tests a stop flag on the device first); the host
- * looks at the flag every 32 iterations, and the call returns when the result is in the caller's arrays.
+ * looks at the flag every 32 iterations, and the call returns when the result is in the caller's arrays: dsp_ubm_train_device waits
+ * for the stream, and so does dsp_ubm_init_rows_device, whose results are HOST arrays too.
  *
  * The start: dsp_ubm_init (weights > 0 that sum to 1 within 1e-6, means, variances > 0, all finite), or DSP_UBM_INIT_ROWS (NULL) for
  * the library's own, which dsp_ubm_init_rows_device also writes out: means_i = row floor((i + 0.5) n / k), variances = the rows' global
@@ -917,7 +918,9 @@ int dsp_gmm_quantize(const dsp_gmm_float_params *g, int8_t *means, int32_t *inv_
  *   GMM start straight into the trainer's device parameters and float32 model -- no host copy between k-means and EM; EM exactly as
  *   dsp_ubm_train_device runs it (em).  The model returned in dsp_ubm_result (unchanged) is the restart whose last lower bound is the
  *   largest, ties to the first: sklearn's rule.  report->restarts[n_init] (the caller's array) says what each restart did,
- *   report->winner which one was kept. */
+ *   report->winner which one was kept.
+ *
+ * Every result of the three calls that is not marked "on the device" is a HOST value: each call waits for the stream before it returns. */
 #define DSP_KMEANS_STOP_MAX_ITER 0
 #define DSP_KMEANS_STOP_TOL 1
 #define DSP_KMEANS_STOP_STRICT 2
@@ -1343,7 +1346,7 @@ int dsp_score_normalize_device(int device, const float *d_scores, long n_rows, l
  * non-finite operands: a score track that dsp_segments_device takes as one column (hysteresis, gap merge, minimum length in dB).
  * d_clips[c] (may be NULL) = {reference, threshold, raw rows, kept rows, first and last kept row (-1: none)}.  kept_offsets[n_clips + 1]
  * is a HOST array, the prefix sums of the kept rows, because every consumer takes host offsets: dsp_vad_decide_ragged_device,
- * dsp_vad_run_ragged_device and dsp_rows_kept_offsets_device return when it is filled, after ONE wait for the stream.
+ * dsp_vad_run_ragged_device and dsp_rows_kept_offsets_device return when it is filled: each waits for the stream, ONCE.
  *
  * Selection.  dsp_rows_select_ragged_device copies the rows of d_in[..][d] (float32, d 1 .. 64) whose flag is not 0 to d_out, order
  * kept: output row kept_offsets[c] + (rank of t among clip c's kept rows) is input row frame_offsets[c] + t, which d_row_index (int64,
@@ -1449,7 +1452,8 @@ long dsp_vad_trim_spans(const dsp_vad_config *cfg, const long *offsets, long n_c
  * Platt.  dsp_svm_platt_fit_device is libsvm's sigmoid_train on the pairs (d_dec_cv[r], labels[r]) for r in rows[n_rows] (HOST, NULL:
  * all rows of the dataset): prior-smoothed targets, A = 0, B = log((prior0 + 1) / (prior1 + 1)) to start, Newton with backtracking,
  * 100 iterations, min_step 1e-10, sigma 1e-12, eps 1e-5; prior1 counts label 0, the positive side.  One block, float64 sums in a fixed
- * order: the same bits on every run.  P(label 0 | dec) = 1 / (1 + exp(A dec + B)): prob_a, prob_b of dsp_svm_create.
+ * order: the same bits on every run.  P(label 0 | dec) = 1 / (1 + exp(A dec + B)): prob_a, prob_b of dsp_svm_create.  A, B and
+ * n_iter are HOST values: the call waits for the stream.
  *
  * Host helpers (no device).  dsp_svm_folds: fold_ids[n] in 0 .. k - 1 by libsvm's rule -- perm = 0 .. n - 1, for i ascending swap
  * perm[i] with perm[i + draw_i % (n - i)], fold f takes perm[f n / k .. (f + 1) n / k) -- on the library's own draws, draw_i =
@@ -1462,7 +1466,8 @@ long dsp_vad_trim_spans(const dsp_vad_config *cfg, const long *offsets, long n_c
  * dsp_svm_fit_device is the reference's clf.fit: the Scaler on all rows, k_prob problems without fold f = 0 .. k_prob - 1 and the
  * final one on all rows in ONE problems launch, the Platt fit on dec_cv[i] = dec[fold_ids[i]][i], the compacted model.  fold_ids
  * (HOST [n], NULL: dsp_svm_folds(n, k_prob, seed)); the model's arrays are the caller's: offset, scale [n_features], sv [n][n_features]
- * and coef [n] at most.  rho, prob_a, prob_b and gamma are rounded to float as dsp_svm_create takes them.
+ * and coef [n] at most.  rho, prob_a, prob_b and gamma are rounded to float as dsp_svm_create takes them.  The call waits for the
+ * stream more than once (after the Scaler, after the problems, after the Platt fit): the model is the HOST's when it returns.
  *
  * One stream at a time per trainer; the workspace (z, D2, the launch's problem table) is grow-only.  dsp_svm_trainer_create touches
  * no device.  DSP_EINVAL, before a device is touched and naming the argument: a NULL that may not be; n_features < 1; n < 2 or above
@@ -1564,7 +1569,8 @@ int dsp_svm_train_rows_host(dsp_svm_trainer *t, float *z, void *stream);
  * dataset under run p's returned weights, dropout off; rows outside train_rows are held-out predictions.  d_params[P][n_params]
  * (device, float64): the returned weights flat, kernel1, bias1, ..., kernel4, bias4, kernels (in, out) row-major.  n_train == 0 is
  * DSP_STOP_TRAIN_EMPTY: nothing is trained, the initial weights are returned with n_epochs 0; n_val == 0 is DSP_STOP_TRAIN_NO_VALIDATION.
- * The call enqueues the epochs without a host round trip, looks at the runs' stop flags every 8 epochs and returns with results filled.
+ * The call enqueues the epochs without a host round trip, looks at the runs' stop flags every 8 epochs and returns with results filled:
+ * it waits for the stream.
  *
  * Random numbers, the library's own (Keras's cannot be reproduced): mix = splitmix64's finaliser as for dsp_kmeans_*, G =
  * 0x9E3779B97F4A7C15, draw(seed, stream, counter) = mix(mix(seed + (stream + 1) G) + (counter + 1) G), u = (draw >> 11) 2^-53.  Stream
