@@ -23,6 +23,7 @@
 
 #include "../../include/dsp_amd.h"
 #include "classify_kernels.hpp"
+#include "host_pipe.hpp"
 #include "mfcc_plan.hpp"
 
 #ifdef DSP_PF_STAMPS
@@ -714,50 +715,167 @@ int dsp_mfcc_clips_ragged_pcm16_device(dsp_mfcc_plan *p, const int16_t *d_pcm, l
     return dsp::mfcc_clips_ragged(p, d_pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, max_frames, d_out, stream);
 }
 
+// ---- host batches: through the device's host pipeline (host_pipe.hpp), a chunk at a time ----
+
+}  // extern "C"
+
+namespace {
+
+// n_items uniform items (frames, or clips of one length): item c is `width` bytes at in + c * src_pitch, staged at dst_pitch; its results
+// are out_item floats.  run(d_in, first, count, d_out, stream) enqueues the chunk's kernels.
+struct UniformHostBatch {
+    const void *in;
+    size_t src_pitch, dst_pitch, width;
+    bool pitched;         // rows of clips (InCopy::pitched)
+    float *out;
+    size_t out_item;      // floats
+    long n_items;
+};
+template <class Run> int host_uniform(dsp_mfcc_plan *p, const UniformHostBatch &b, const Run &run)
+{
+    std::lock_guard<std::recursive_mutex> lock(p->mu);
+    DSP_ON_DEVICE(p->device);
+    if (p->device >= dsp::host::kMaxDevices) return capi_fail(DSP_EINVAL, "device index out of range");
+    dsp::host::Session hs(p->device);
+    dsp::host::Job job;
+    job.in_base = b.in;
+    job.in_extent = b.src_pitch * (size_t)(b.n_items - 1) + b.width;
+    std::vector<long> first;
+    dsp::host::plan_uniform(b.n_items, (long)b.dst_pitch, hs.pipe.chunk_bytes_for(job.in_base, job.in_extent), first);
+    if (const int rc = hs.open(p->device, (long)first.size() - 1)) return rc;
+    job.n_chunks = (long)first.size() - 1;
+    job.out_base[0] = b.out;
+    job.out_extent[0] = (size_t)b.n_items * b.out_item * sizeof(float);
+    const auto chunk = [&](long k, dsp::host::InCopy &ic, dsp::host::OutCopy &oc) {
+        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
+        ic.src = static_cast<const char *>(b.in) + (size_t)c0 * b.src_pitch;
+        ic.src_pitch = b.src_pitch; ic.dst_pitch = b.dst_pitch; ic.width = b.width; ic.rows = (size_t)cnt; ic.pitched = b.pitched;
+        oc.dst[0] = b.out + (size_t)c0 * b.out_item;
+        oc.bytes[0] = (size_t)cnt * b.out_item * sizeof(float);
+    };
+    const auto kernels = [&](long k, const void *d_in, void *d_out, hipStream_t st) {
+        return run(d_in, first[(size_t)k + 1] - first[(size_t)k], static_cast<float *>(d_out), st);
+    };
+    return hs.pipe.run(job, chunk, kernels);
+}
+
+// equal clips of in_kind, staged at an even stride so that every frame start keeps the kernels' alignment; the frames per clip, or < 0
+int host_clips(dsp_mfcc_plan *p, const void *signal, int in_kind, long n_clips, int samples_per_clip, long clip_stride, float *out, int max_frames,
+               bool checked)
+{
+    if (in_kind < 0) return in_kind;
+    if (!p || n_clips < 0) return capi_fail(DSP_EINVAL, "bad argument");
+    if (checked)
+        if (const int rc = dsp::plan_accepts(p, dsp::PlanUse::Clips, in_kind)) return rc;
+    const int t = dsp_mfcc_frames_for(&p->cfg, samples_per_clip, max_frames);
+    if (t == 0 || n_clips == 0) return 0;
+    if (!signal || !out) return capi_fail(DSP_EINVAL, "NULL buffer");
+    if (n_clips > 1 && clip_stride < samples_per_clip) return capi_fail(DSP_EINVAL, "clip_stride < samples_per_clip");
+    const size_t bps = in_kind == 1 ? 2 : 4;                                  // bytes per sample, all channels
+    const long dstride = samples_per_clip + (samples_per_clip & 1);
+    if (n_clips == 1) clip_stride = samples_per_clip;
+    const int rc = host_uniform(p, {signal, (size_t)clip_stride * bps, (size_t)dstride * bps, (size_t)samples_per_clip * bps, true, out,
+                                    (size_t)t * p->cfg.n_mfcc, n_clips},
+                                [&](const void *d_in, long cnt, float *d_out, hipStream_t st) {
+                                    return mfcc_run(p, {.in = d_in, .in_kind = in_kind, .out = d_out, .n_frames = cnt * (long)t, .frames_per_clip = t,
+                                                        .samples_per_clip = samples_per_clip, .clip_stride = dstride, .stream = st});
+                                });
+    return rc < 0 ? rc : t;
+}
+
+// a ragged batch of in_kind: chunks of whole clips, each one ragged device pass over its own samples with the offsets rebased
+int host_clips_ragged(dsp_mfcc_plan *p, const void *signal, int in_kind, long n_clips, const long *offsets, int max_frames, float *out)
+{
+    if (in_kind < 0) return in_kind;
+    if (!p || n_clips < 0 || !offsets) return capi_fail(DSP_EINVAL, "bad argument");
+    if (const int rc = dsp::plan_accepts(p, dsp::PlanUse::Ragged, in_kind)) return rc;
+    if (n_clips >= (1L << 31)) return capi_fail(DSP_EINVAL, "too many clips");
+    std::vector<long> fo((size_t)n_clips + 1);
+    const long total = ragged_frame_offsets(p->cfg, offsets, n_clips, max_frames, fo.data(), nullptr);
+    if (total < 0) return (int)total;
+    if (total == 0) return 0;
+    if (!signal || !out) return capi_fail(DSP_EINVAL, "NULL buffer");
+    const size_t bps = in_kind == 1 ? 2 : 4, row = (size_t)p->cfg.n_mfcc;
+    std::lock_guard<std::recursive_mutex> lock(p->mu);
+    DSP_ON_DEVICE(p->device);
+    if (p->device >= dsp::host::kMaxDevices) return capi_fail(DSP_EINVAL, "device index out of range");
+    dsp::host::Session hs(p->device);
+    std::vector<long> first;
+    dsp::host::plan_ragged(offsets, n_clips, (long)bps,
+                           hs.pipe.chunk_bytes_for(static_cast<const char *>(signal) + (size_t)(offsets[0] & ~3L) * bps, (size_t)(offsets[n_clips] - (offsets[0] & ~3L)) * bps), first);
+    if (const int rc = hs.open(p->device, (long)first.size() - 1)) return rc;
+    // a chunk's samples start at a multiple of four samples at or below its first clip: every clip keeps its alignment in the staging
+    // buffer (16 bytes for floats, 8 for mono int16), the copy starts on 8 bytes
+    const auto start = [&](long k) { return offsets[first[(size_t)k]] & ~3L; };
+    int t_max = 0;
+    std::vector<long> rebased;
+    dsp::host::Job job;
+    job.n_chunks = (long)first.size() - 1;
+    job.in_base = static_cast<const char *>(signal) + (size_t)start(0) * bps;
+    job.in_extent = (size_t)(offsets[n_clips] - start(0)) * bps;
+    job.out_base[0] = out;
+    job.out_extent[0] = (size_t)total * row * sizeof(float);
+    const auto chunk = [&](long k, dsp::host::InCopy &ic, dsp::host::OutCopy &oc) {
+        const long c0 = first[(size_t)k], c1 = first[(size_t)k + 1];
+        ic.src = static_cast<const char *>(signal) + (size_t)start(k) * bps;
+        ic.width = (size_t)(offsets[c1] - start(k)) * bps;
+        oc.dst[0] = out + (size_t)fo[(size_t)c0] * row;
+        oc.bytes[0] = (size_t)(fo[(size_t)c1] - fo[(size_t)c0]) * row * sizeof(float);
+    };
+    const auto kernels = [&](long k, const void *d_in, void *d_out, hipStream_t st) {
+        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
+        if (fo[(size_t)(c0 + cnt)] == fo[(size_t)c0]) return (int)DSP_OK;      // a chunk of clips without frames
+        rebased.resize((size_t)cnt + 1);
+        for (long c = 0; c <= cnt; ++c) rebased[(size_t)c] = offsets[c0 + c] - start(k);
+        const int t = dsp::mfcc_clips_ragged(p, d_in, in_kind, cnt, rebased.data(), max_frames, static_cast<float *>(d_out), st);
+        t_max = std::max(t_max, t);
+        return std::min(t, 0);
+    };
+    const int rc = hs.pipe.run(job, chunk, kernels);
+    return rc < 0 ? rc : t_max;
+}
+
+}  // namespace
+
+extern "C" {
+
 int dsp_mfcc_frames_host(dsp_mfcc_plan *p, const float *frames, long n_frames, float *out)
 {
     if (!p || n_frames < 0 || (n_frames > 0 && (!frames || !out))) return capi_fail(DSP_EINVAL, "bad argument");
     if (n_frames == 0) return DSP_OK;
-    std::lock_guard<std::recursive_mutex> lock(p->mu);
-    DSP_ON_DEVICE(p->device);
-    const size_t in_b = (size_t)n_frames * p->cfg.frame_length * sizeof(float);
-    const size_t out_b = (size_t)n_frames * p->cfg.n_mfcc * sizeof(float);
-    DSP_CAPI_HIP(p->d_in.reserve(in_b));
-    DSP_CAPI_HIP(p->d_out.reserve(out_b));
-    int rc;
-    DSP_CAPI_HIP(hipMemcpyAsync(p->d_in, frames, in_b, hipMemcpyHostToDevice, nullptr));
     if (p->cfg.prefilter != DSP_PREFILTER_NONE) return capi_fail(DSP_EINVAL, "prefiltered plans take device buffers (dsp_mfcc_frames_device)");
-    if ((rc = mfcc_run(p, {.in = p->d_in, .out = p->d_out, .n_frames = n_frames})) < 0) return rc;
-    DSP_CAPI_HIP(hipMemcpyAsync(out, p->d_out, out_b, hipMemcpyDeviceToHost, nullptr));
-    DSP_CAPI_HIP(hipStreamSynchronize(nullptr));
-    return DSP_OK;
+    const size_t fb = (size_t)p->cfg.frame_length * sizeof(float);
+    return host_uniform(p, {frames, fb, fb, fb, false, out, (size_t)p->cfg.n_mfcc, n_frames}, [&](const void *d_in, long cnt, float *d_out, hipStream_t st) {
+        return mfcc_run(p, {.in = d_in, .out = d_out, .n_frames = cnt, .stream = st});
+    });
 }
 
 int dsp_mfcc_clips_host(dsp_mfcc_plan *p, const float *signal, long n_clips, int samples_per_clip,
                         long clip_stride, float *out, int max_frames)
 {
-    if (!p || n_clips < 0) return capi_fail(DSP_EINVAL, "bad argument");
-    const int t = dsp_mfcc_frames_for(&p->cfg, samples_per_clip, max_frames);
-    if (t == 0 || n_clips == 0) return 0;
-    if (!signal || !out) return capi_fail(DSP_EINVAL, "NULL buffer");
-    if (n_clips > 1 && clip_stride < samples_per_clip) return capi_fail(DSP_EINVAL, "clip_stride < samples_per_clip");
-    std::lock_guard<std::recursive_mutex> lock(p->mu);
-    DSP_ON_DEVICE(p->device);
-    // device copy is packed with an even stride so every frame start stays 8-byte aligned
-    const long dstride = samples_per_clip + (samples_per_clip & 1);
-    const size_t in_b = (size_t)n_clips * dstride * sizeof(float);
-    const size_t out_b = (size_t)n_clips * t * p->cfg.n_mfcc * sizeof(float);
-    DSP_CAPI_HIP(p->d_in.reserve(in_b));
-    DSP_CAPI_HIP(p->d_out.reserve(out_b));
-    int rc;
-    DSP_CAPI_HIP(hipMemcpy2DAsync(p->d_in, dstride * sizeof(float), signal, clip_stride * sizeof(float),
-                             (size_t)samples_per_clip * sizeof(float), (size_t)n_clips, hipMemcpyHostToDevice, nullptr));
-    if ((rc = mfcc_run(p, {.in = p->d_in, .out = p->d_out, .n_frames = n_clips * (long)t, .frames_per_clip = t, .samples_per_clip = samples_per_clip,
-                           .clip_stride = dstride})) < 0)
-        return rc;
-    DSP_CAPI_HIP(hipMemcpyAsync(out, p->d_out, out_b, hipMemcpyDeviceToHost, nullptr));
-    DSP_CAPI_HIP(hipStreamSynchronize(nullptr));
-    return t;
+    return host_clips(p, signal, 0, n_clips, samples_per_clip, clip_stride, out, max_frames, false);
+}
+
+int dsp_mfcc_clips_pcm16_host(dsp_mfcc_plan *p, const int16_t *pcm, long n_clips, int samples_per_clip, long clip_stride, int channels, int stereo_mode,
+                              float *out, int max_frames)
+{
+    if (!p) return capi_fail(DSP_EINVAL, "plan is NULL");
+    return host_clips(p, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, samples_per_clip, clip_stride, out, max_frames, true);
+}
+
+int dsp_mfcc_clips_ragged_host(dsp_mfcc_plan *p, const float *signal, long n_clips, const long *offsets, int max_frames, float *out)
+{
+    if (!p) return capi_fail(DSP_EINVAL, "plan is NULL");
+    if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");
+    return host_clips_ragged(p, signal, 0, n_clips, offsets, max_frames, out);
+}
+
+int dsp_mfcc_clips_ragged_pcm16_host(dsp_mfcc_plan *p, const int16_t *pcm, long n_clips, const long *offsets, int channels, int stereo_mode,
+                                     int max_frames, float *out)
+{
+    if (!p) return capi_fail(DSP_EINVAL, "plan is NULL");
+    if (!offsets) return capi_fail(DSP_EINVAL, "offsets is NULL");
+    return host_clips_ragged(p, pcm, dsp::pcm16_kind(channels, stereo_mode), n_clips, offsets, max_frames, out);
 }
 
 #ifdef DSP_PF_STAMPS

@@ -43,7 +43,6 @@ hipError_t spec_div_mismatches(const dsp::SpecTables *d_tab, unsigned long long 
 
 // the workspace for one sub-batch: allocated together, let go together (ClassifyCtx::reserve)
 struct ClassifyBufs {
-    dsp::DeviceBuf<void> x;                                // staged input (host entry points); none until a host entry asks
     dsp::DeviceBuf<float> d_sbp;                           // 3000-7500 Hz PSD maps [clip][T][129]
     dsp::DeviceBuf<float> d_ck_bp, d_ck_mp;                // [clip][T][kCkPerSegBp / Mp][8]: delay line of each filter at every segment start (3000-7500 Hz: and middle)
     dsp::DeviceBuf<float> d_mean_mp;                       // [clip][T]: segment means of the 1000-3000 Hz output
@@ -111,15 +110,13 @@ struct ClassifyCtx : front::Work, ClassifyBufs {
     // The per-segment arrays are [clip][T(n)] with the pass's own T, so what a pass needs of them is its PRODUCT clips x T: a ragged
     // batch's pass of few long clips and its pass of many short ones share one allocation (sized by each dimension's maximum it would
     // be their outer product -- 32 GB of maps for 65 536 clips of which one is 13 s long).
-    int reserve(int, long clips, int n, size_t x_bytes)
+    int reserve(int, long clips, int n)
     {
         const long T = std::max(1, front::columns(n));
-        if (clips <= cap_clips && clips * T <= cap_segs && x_bytes <= x.bytes()) return DSP_OK;
+        if (clips <= cap_clips && clips * T <= cap_segs) return DSP_OK;
         wait_idle();
         const long rows = std::max(clips, cap_clips), segs = std::max(clips * T, cap_segs);
-        const size_t xb = std::max(x_bytes, x.bytes());
         free_workspace();      // (cap_clips and cap_segs stay 0 if an allocation below fails: the next call starts over)
-        if (xb > 0) DSP_CAPI_HIP(x.alloc(xb));
         DSP_CAPI_HIP(d_sbp.alloc((size_t)segs * dsp::kSpecBins * sizeof(float)));
         DSP_CAPI_HIP(d_ck_bp.alloc((size_t)segs * dsp::kCkPerSegBp * 8 * sizeof(float)));
         DSP_CAPI_HIP(d_ck_mp.alloc((size_t)segs * dsp::kCkPerSegMp * 8 * sizeof(float)));

@@ -65,7 +65,6 @@ struct Scratch : front::Work, PassBufs, YardstickBufs {
     dsp::DeviceBuf<dsp::ScreenTablesD> scr;
     dsp::DeviceBuf<int> cu_table;          // launch_iir2_screen_f64's per-CU arrival counters
     double U = 0.0;
-    dsp::DeviceBuf<void> x;                // staging of host input
     long last_segments = 0;                // clips x columns of the last pass (dsp_classify_stats_f64)
 
     static Config default_config()
@@ -124,14 +123,13 @@ struct Scratch : front::Work, PassBufs, YardstickBufs {
     {
         free_pass();
         free_yardstick();
-        x.reset();
         tab.reset();
         scr.reset();
         cu_table.reset();
     }
 
     // the workspace for passes of `clips` clips of n samples; grows, never shrinks
-    int reserve(int pl, long clips, int n, size_t x_bytes)
+    int reserve(int pl, long clips, int n)
     {
         const size_t T = (size_t)front::columns(n);
         // (the per-segment arrays are sized by the PRODUCT clips x T of the largest pass: a ragged batch's pass of few long clips and its
@@ -155,10 +153,6 @@ struct Scratch : front::Work, PassBufs, YardstickBufs {
             DSP_CAPI_HIP(trace.alloc((size_t)clips * sizeof(dsp::ClassifyTraceD)));
             DSP_CAPI_HIP(minmax.alloc((size_t)clips * 2 * sizeof(unsigned long long)));
             cap_clips = clips; cap_cells = cells;
-        }
-        if (x_bytes > x.bytes()) {
-            wait_idle();
-            DSP_CAPI_HIP(x.alloc(x_bytes));
         }
         if (pl != kCkpt && (clips > cap_y_clips || row_of(n) > cap_y_row || (int)T > cap_y_T)) {
             wait_idle();

@@ -8,7 +8,8 @@
 //     pipeline(in, ragged)            which kernel chain a call runs (the float64 yardsticks: uniform float batches only)
 //     sub_batch(pl)                   clips per pass through the workspace
 //     init()                          tables, once per workspace (the caller holds mu and has made the device current)
-//     reserve(pl, clips, n, x_bytes)  the workspace of a pass of `clips` clips of n samples (+ x_bytes of staging at x); grows only
+//     reserve(pl, clips, n)           the workspace of a pass of `clips` clips of n samples; grows only (host batches are staged by the
+//                                     device's host pipeline, host_pipe.hpp, not by the workspace)
 //     run(pl, cfg, d_x, in, clips, n, stride, want_trace, st, spans, total)    one pass: labels (+ trace) into `labels` / `trace`
 //     free_all()                      lets every device buffer of the workspace go
 // Input kinds `in`: 0 float samples, 1 / 2 / 3 int16 mono / interleaved stereo channel 0 / stereo average.
@@ -25,6 +26,7 @@
 
 #include "capi_util.hpp"
 #include "classify_kernels.hpp"
+#include "host_pipe.hpp"
 
 namespace dsp {
 namespace front {
@@ -172,7 +174,7 @@ template <class W> int device_entry(const typename W::Config *cfgp, const void *
     if ((rc = open(w, device)) < 0) return rc;
     const int pl = W::pipeline(in, false);
     const long sub = W::sub_batch(pl);
-    if ((rc = w.reserve(pl, std::min(sub, n_clips), n, 0)) < 0) return rc;
+    if ((rc = w.reserve(pl, std::min(sub, n_clips), n)) < 0) return rc;
     if (w.pending) DSP_CAPI_HIP(hipStreamWaitEvent(st, w.done, 0));        // the previous call's work on this workspace (any stream)
     BusyMark mark{w, st};
     for (long c0 = 0; c0 < n_clips; c0 += sub) {
@@ -185,7 +187,8 @@ template <class W> int device_entry(const typename W::Config *cfgp, const void *
     return DSP_OK;
 }
 
-// equal clips in host memory, staged through the workspace a sub-batch at a time
+// equal clips in host memory: through the device's host pipeline (host_pipe.hpp) a chunk at a time, a chunk being one pass through the
+// workspace.  The pipeline owns the staged input and the results' way home; the workspace is sized for one chunk's clips.
 template <class W> int host_entry(const typename W::Config *cfgp, const void *signal, int in, long n_clips, int n, long stride, int *labels,
                                   typename W::Trace *trace)
 {
@@ -203,32 +206,59 @@ template <class W> int host_entry(const typename W::Config *cfgp, const void *si
     DSP_ON_DEVICE(device);
     if (n_clips == 1) stride = n;
     W &w = workspaces<W>()[device];
-    std::lock_guard<std::mutex> lock(w.mu);
+    std::lock_guard<std::mutex> lock(w.mu);                                     // (the workspace's lock, then the pipeline's)
     if ((rc = open(w, device)) < 0) return rc;
+    host::Session hs(device);
     const int pl = W::pipeline(in, false);
-    const long sub = W::sub_batch(pl), pass = std::min(sub, n_clips);
-    const int bps = sample_bytes<W>(in);
-    const long row = (((long)n * bps + 15) & ~15L) / bps;                       // staged rows start on 16 bytes
-    if ((rc = w.reserve(pl, pass, n, (size_t)pass * row * bps)) < 0) return rc;
-    w.wait_idle();                                                              // the staging buffer is written by copies on the null stream
-    BusyMark mark{w, nullptr};
-    for (long c0 = 0; c0 < n_clips; c0 += sub) {
-        const long cnt = std::min(sub, n_clips - c0);
-        DSP_CAPI_HIP(hipMemcpy2DAsync(w.x, (size_t)row * bps, static_cast<const unsigned char *>(signal) + (size_t)c0 * stride * bps, (size_t)stride * bps,
-                                      (size_t)n * bps, (size_t)cnt, hipMemcpyHostToDevice, nullptr));
-        if ((rc = w.run(pl, cfg, w.x, in, cnt, n, row, trace != nullptr, nullptr, nullptr, 0)) < 0) return rc;
-        DSP_CAPI_HIP(hipMemcpyAsync(labels + c0, w.labels, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, nullptr));
-        if (trace) DSP_CAPI_HIP(hipMemcpyAsync(trace + c0, w.trace, (size_t)cnt * sizeof(*trace), hipMemcpyDeviceToHost, nullptr));
-        DSP_CAPI_HIP(hipStreamSynchronize(nullptr));
-    }
-    return DSP_OK;
+    const size_t bps = (size_t)sample_bytes<W>(in);
+    const size_t row = (((size_t)n * bps + 15) & ~(size_t)15) / bps;            // staged rows start on 16 bytes
+    const long sub = W::sub_batch(pl);
+    // (a chunk is a pass: at least cfg.classify_min_clips clips, at most the workspace's sub-batch)
+    const size_t extent = ((size_t)(n_clips - 1) * (size_t)stride + (size_t)n) * bps;
+    const long chunk_bytes = std::max(hs.pipe.chunk_bytes_for(signal, extent), hs.pipe.cfg.classify_min_clips * (long)(row * bps));
+    std::vector<long> first;
+    host::plan_uniform(n_clips, (long)(row * bps), chunk_bytes, first, sub);
+    if ((rc = hs.open(device, (long)first.size() - 1)) < 0) return rc;
+    if ((rc = w.reserve(pl, first[1], n)) < 0) return rc;
+    w.wait_idle();
+    host::Job job;
+    job.n_chunks = (long)first.size() - 1;
+    BusyMark mark{w, nullptr};                                                  // (the kernels of every chunk run on the null stream)
+    const bool one = job.n_chunks == 1;
+    if (one) { job.resident[0] = w.labels; job.resident[1] = w.trace; }
+    job.in_base = signal;
+    job.in_extent = extent;
+    job.out_base[0] = labels;
+    job.out_extent[0] = (size_t)n_clips * sizeof(int);
+    job.out_base[1] = trace;
+    job.out_extent[1] = trace ? (size_t)n_clips * sizeof(*trace) : 0;
+    const auto chunk = [&](long k, host::InCopy &ic, host::OutCopy &oc) {
+        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
+        ic.src = static_cast<const unsigned char *>(signal) + (size_t)c0 * (size_t)stride * bps;
+        ic.src_pitch = (size_t)stride * bps; ic.dst_pitch = row * bps; ic.width = (size_t)n * bps; ic.rows = (size_t)cnt; ic.pitched = true;
+        oc.dst[0] = labels + c0;
+        oc.bytes[0] = (size_t)cnt * sizeof(int);
+        if (trace) { oc.dst[1] = trace + c0; oc.bytes[1] = (size_t)cnt * sizeof(*trace); }
+    };
+    const auto kernels = [&](long k, const void *d_x, void *d_out, hipStream_t st) {
+        const long cnt = first[(size_t)k + 1] - first[(size_t)k];
+        host::OutCopy oc;
+        oc.bytes[0] = (size_t)cnt * sizeof(int);
+        const int r = w.run(pl, cfg, d_x, in, cnt, n, (long)row, trace != nullptr, st, nullptr, 0);
+        if (r < 0 || one) return r;               // (one chunk: the results go home from the workspace, job.resident)
+        DSP_CAPI_HIP(hipMemcpyAsync(d_out, w.labels, oc.bytes[0], hipMemcpyDeviceToDevice, st));
+        if (trace) DSP_CAPI_HIP(hipMemcpyAsync(static_cast<char *>(d_out) + oc.at(1), w.trace, (size_t)cnt * sizeof(*trace), hipMemcpyDeviceToDevice, st));
+        return (int)DSP_OK;
+    };
+    return hs.pipe.run(job, chunk, kernels);
 }
 
 // Ragged batches (the references read one file of any length per run; their callers loop over files): the clips' spans from the
 // host's offsets[n_clips + 1] (samples per channel from the buffer's start), every clip with the segments ITS length holds.
 // d_signal: the whole buffer on `device`.  Results to d_labels / d_trace (device) and labels / trace (host), whichever are given.
+// locked: the caller holds the workspace's lock (the host entry, which takes the host pipeline's behind it)
 template <class W> int ragged(const typename W::Config &cfg, const void *d_signal, int device, int in, long n_clips, const long *offsets,
-                              int *d_labels, typename W::Trace *d_trace, int *labels, typename W::Trace *trace, void *stream)
+                              int *d_labels, typename W::Trace *d_trace, int *labels, typename W::Trace *trace, void *stream, bool locked = false)
 {
     int rc = DSP_OK, n_max = 0;
     for (long c = 0; c < n_clips; ++c) {
@@ -248,7 +278,8 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
     }
     if (n_clips >= (1L << 31)) return capi_fail(DSP_EINVAL, "too many clips");
     W &w = workspaces<W>()[device];
-    std::lock_guard<std::mutex> lock(w.mu);
+    std::unique_lock<std::mutex> lock(w.mu, std::defer_lock);
+    if (!locked) lock.lock();
     if ((rc = open(w, device)) < 0) return rc;
     const int pl = W::pipeline(in, true);
     const long sub = W::sub_batch(pl);
@@ -286,7 +317,7 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
         c0 += cnt;
     }
     for (const Pass &ps : passes)
-        if ((rc = w.reserve(pl, ps.cnt, ps.n_row, 0)) < 0) return rc;
+        if ((rc = w.reserve(pl, ps.cnt, ps.n_row)) < 0) return rc;
     const bool want_trace = d_trace || trace;
     std::vector<int> h_labels;
     std::vector<typename W::Trace> h_trace;
@@ -337,15 +368,67 @@ template <class W> int ragged_host_entry(const typename W::Config *cfgp, const v
     if (offsets[n_clips] < offsets[0] || offsets[0] < 0) return capi_fail(DSP_EINVAL, "offsets must be non-negative and non-decreasing, clips shorter than 2^31 samples");
     int device = 0;
     if ((rc = host_device(device)) < 0) return rc;
-    // the whole buffer travels once (a buffer of its own: the workspaces' staging rows are laid out for equal clips)
+    // chunks of whole clips (host_chunks.hpp), each one ragged device pass over its own samples with the offsets rebased: every clip gets
+    // the label and trace of a one-clip call, so the cuts are invisible.  The results go home in the caller's order (the pass scatters
+    // them into the pipeline's staging as it does into a device caller's arrays).
+    for (long c = 0; c < n_clips; ++c) {
+        const long n = ragged_clip_length(offsets, c);
+        if (n < 0) return (int)n;
+        if (columns((int)n) > kMaxColumns) return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
+    }
     DSP_ON_DEVICE(device);
-    DeviceBuf<void> d_flat;
-    const size_t bytes = (size_t)offsets[n_clips] * sample_bytes<W>(in);
-    DSP_CAPI_HIP(d_flat.alloc(bytes + 16));
-    DSP_CAPI_HIP(hipMemcpy(d_flat, signal, bytes, hipMemcpyHostToDevice));
-    rc = ragged<W>(cfg, d_flat, device, in, n_clips, offsets, nullptr, nullptr, labels, trace, nullptr);
-    (void)hipStreamSynchronize(nullptr);      // the pass's kernels read d_flat: they end before it is let go
-    return rc;
+    W &w = workspaces<W>()[device];
+    std::lock_guard<std::mutex> lock(w.mu);                                     // (the workspace's lock, then the pipeline's)
+    host::Session hs(device);
+    const size_t bps = (size_t)sample_bytes<W>(in);
+    const unsigned char *base = static_cast<const unsigned char *>(signal) + (size_t)(offsets[0] & ~3L) * bps;
+    const size_t extent = (size_t)(offsets[n_clips] - (offsets[0] & ~3L)) * bps;
+    // (at least the bytes of classify_min_clips clips of one second a chunk; "at least one clip" asks nothing: every chunk holds one)
+    const long min_clips = hs.pipe.cfg.classify_min_clips;
+    const long chunk_bytes = std::max(hs.pipe.chunk_bytes_for(base, extent), min_clips > 1 ? min_clips * 16000L * (long)bps : 0L);
+    std::vector<long> first, rebased;
+    host::plan_ragged(offsets, n_clips, (long)bps, chunk_bytes, first);
+    if ((rc = hs.open(device, (long)first.size() - 1)) < 0) return rc;
+    if (first.size() == 2) {
+        // one chunk: the whole buffer travels once and the batch is one ragged pass that brings its results home itself, pass by pass,
+        // in the caller's order -- the launches of a device call on the same samples and nothing else
+        void *d_flat = nullptr;
+        if ((rc = hs.pipe.stage_whole(base, extent, d_flat)) < 0) return rc;
+        rebased.resize((size_t)n_clips + 1);
+        for (long c = 0; c <= n_clips; ++c) rebased[(size_t)c] = offsets[c] - (offsets[0] & ~3L);
+        rc = ragged<W>(cfg, d_flat, device, in, n_clips, rebased.data(), nullptr, nullptr, labels, trace, nullptr, true);
+        (void)hipStreamSynchronize(nullptr);      // the pass's kernels read the staged buffer: they end before the lock is let go
+        hs.pipe.last.bytes_d2h = (long)((size_t)n_clips * (sizeof(int) + (trace ? sizeof(*trace) : 0)));
+        return rc;
+    }
+    // a chunk's samples start at a multiple of four samples at or below its first clip: every clip keeps its alignment in staging
+    const auto start = [&](long k) { return offsets[first[(size_t)k]] & ~3L; };
+    host::Job job;
+    job.n_chunks = (long)first.size() - 1;
+    job.in_base = base;
+    job.in_extent = extent;
+    job.out_base[0] = labels;
+    job.out_extent[0] = (size_t)n_clips * sizeof(int);
+    job.out_base[1] = trace;
+    job.out_extent[1] = trace ? (size_t)n_clips * sizeof(*trace) : 0;
+    const auto chunk = [&](long k, host::InCopy &ic, host::OutCopy &oc) {
+        const long c0 = first[(size_t)k], c1 = first[(size_t)k + 1];
+        ic.src = static_cast<const unsigned char *>(signal) + (size_t)start(k) * bps;
+        ic.width = (size_t)(offsets[c1] - start(k)) * bps;
+        oc.dst[0] = labels + c0;
+        oc.bytes[0] = (size_t)(c1 - c0) * sizeof(int);
+        if (trace) { oc.dst[1] = trace + c0; oc.bytes[1] = (size_t)(c1 - c0) * sizeof(*trace); }
+    };
+    const auto kernels = [&](long k, const void *d_x, void *d_out, hipStream_t st) {
+        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
+        rebased.resize((size_t)cnt + 1);
+        for (long c = 0; c <= cnt; ++c) rebased[(size_t)c] = offsets[c0 + c] - start(k);
+        host::OutCopy oc;
+        oc.bytes[0] = (size_t)cnt * sizeof(int);
+        typename W::Trace *d_trace = trace ? reinterpret_cast<typename W::Trace *>(static_cast<char *>(d_out) + oc.at(1)) : nullptr;
+        return ragged<W>(cfg, d_x, device, in, cnt, rebased.data(), static_cast<int *>(d_out), d_trace, nullptr, nullptr, st, true);
+    };
+    return hs.pipe.run(job, chunk, kernels);
 }
 
 }  // namespace front

@@ -47,12 +47,12 @@ struct dsp_mfcc_plan {
     int scan_steps[4] = {6, 6, 6, 6};             // host copy of PrefilterScan::c_steps (picks the kernel instantiation)
     dsp::DeviceBuf<float> d_filtered;             // per-frame prefilter output (sub-batch)
     dsp::DeviceBuf<float> d_frame_max, d_clip_floor;   // DSP_LOG_GLOBAL_REF1 two-pass workspace
-    // staging for the host-pointer entry points
-    dsp::DeviceBuf<float> d_in, d_out;
-    // Guards the plan's workspaces (d_filtered, d_frame_max / d_clip_floor, d_in / d_out) while a call reserves them and
+    // Guards the plan's workspaces (d_filtered, d_frame_max / d_clip_floor) while a call reserves them and
     // enqueues the kernels that use them.  The kernels themselves run after the lock is released: a plan whose path uses
-    // a workspace (prefilter, DSP_LOG_GLOBAL_REF1 over clips, the *_host entry points) serves ONE stream at a time;
+    // a workspace (prefilter, DSP_LOG_GLOBAL_REF1 over clips) serves ONE stream at a time;
     // the workspace-free paths (frames / clips / pcm16 / fused, per-frame log mode) may be driven from several streams.
+    // The *_host entry points hold it for the whole call (their staging is the device's host pipeline, host_pipe.hpp, whose lock is
+    // taken after this one).
     std::recursive_mutex mu;
     dsp::SpanRing spans;      // ragged batches of the fused clip kernels: the clips' spans on their way to the GPU (capi_util.hpp)
 };

@@ -317,6 +317,21 @@ PAD_REFLECT, PAD_ZERO = 0, 1
 AUGMENT_STRETCH, AUGMENT_PITCH, AUGMENT_NOISE = 0, 1, 2
 
 
+class HostPipelineConfig(C.Structure):
+    """dsp_host_pipeline_config"""
+    _fields_ = [("chunk_bytes", C.c_long), ("depth", C.c_int), ("pageable_mode", C.c_int), ("classify_min_clips", C.c_int)]
+
+
+class HostStats(C.Structure):
+    """dsp_host_stats"""
+    _fields_ = [("n_chunks", C.c_long), ("depth", C.c_int), ("input_path", C.c_int), ("output_path", C.c_int), ("bytes_h2d", C.c_long),
+                ("bytes_d2h", C.c_long), ("peak_staging_bytes", C.c_long), ("pinned_ring_bytes", C.c_long)]
+
+
+PAGEABLE_STAGE, PAGEABLE_REGISTER, PAGEABLE_DIRECT, PAGEABLE_WHOLE = 0, 1, 2, 3      # DSP_HOST_PAGEABLE_*
+HOST_PATHS = ("staged", "pinned", "registered", "direct")      # DSP_HOST_PATH_*
+
+
 class ClassifyTrace(C.Structure):
     """dsp_classify_trace (include/dsp_amd.h)."""
 
@@ -379,6 +394,16 @@ PROTOTYPES = {
     "dsp_mfcc_clips_ragged_pcm16_device": (ip, [vp, vp, lg, lp, ip, ip, ip, vp, vp]),
     "dsp_mfcc_frames_host": (ip, [vp, vp, lg, vp]),
     "dsp_mfcc_clips_host": (ip, [vp, vp, lg, ip, lg, vp, ip]),
+    "dsp_mfcc_clips_pcm16_host": (ip, [vp, vp, lg, ip, lg, ip, ip, vp, ip]),
+    "dsp_mfcc_clips_ragged_host": (ip, [vp, vp, lg, lp, ip, vp]),
+    "dsp_mfcc_clips_ragged_pcm16_host": (ip, [vp, vp, lg, lp, ip, ip, ip, vp]),
+    "dsp_host_alloc": (ip, [ip, sz, vpp]),
+    "dsp_host_free": (None, [vp]),
+    "dsp_host_pipeline_set": (ip, [ip, P(HostPipelineConfig)]),
+    "dsp_host_pipeline_get": (ip, [ip, P(HostPipelineConfig)]),
+    "dsp_host_pipeline_release": (ip, [ip]),
+    "dsp_host_pipeline_stats": (ip, [ip, P(HostStats)]),
+    "dsp_host_plan_chunks": (lg, [lg, lg, lp, lg, lp, lg]),
     "dsp_mfcc_plan_set_launch": (ip, [vp, ip, ip]),
     "dsp_mfcc_plan_set_kernel": (ip, [vp, ip]),
     "dsp_butter_bandpass": (ip, [db, db, dp, dp]),
@@ -684,6 +709,26 @@ class Handle(Closing):
 
     def _stream(self):
         return current_stream(self.device)
+
+
+def host_array(x, dtype):
+    """A host buffer for a *_host entry: a numpy array or a CPU torch tensor -> a C-contiguous numpy array of `dtype`, the SAME memory
+    where x already is one (a pinned tensor stays pinned: the copy engines read it directly), a converted copy otherwise."""
+    import numpy as np
+    if not isinstance(x, np.ndarray) and hasattr(x, "is_cuda"):
+        if x.is_cuda:
+            raise ValueError("a host entry takes host memory: a numpy array or a CPU tensor")
+        x = x.detach().numpy()
+    return np.ascontiguousarray(x, dtype)
+
+
+def torch_int16():
+    """torch.int16, or None where torch is not importable (a dtype to compare a tensor's against)"""
+    try:
+        import torch
+        return torch.int16
+    except Exception:  # noqa: BLE001
+        return None
 
 
 def c_offsets(offsets):

@@ -71,6 +71,55 @@ def tables(cfg: MfccConfig):
     return win, mel, dct
 
 
+def host_pipeline(device: int = 0, chunk_bytes: int | None = None, depth: int | None = None, pageable_mode: int | None = None,
+                  classify_min_clips: int | None = None):
+    """The host pipeline of `device` -- what every *_host entry streams its batch through: chunks of chunk_bytes input bytes in a ring of
+    `depth` slots; pageable_mode (lib.PAGEABLE_*) says what is done with a pageable batch larger than a chunk, classify_min_clips is the
+    fewest clips of a classifier's chunk (dsp_host_pipeline_set).  No argument given: the library's defaults are put back; otherwise the
+    arguments left out keep their current value.  Returns (chunk_bytes, depth, pageable_mode, classify_min_clips) as they now stand.
+    No setting changes a result bit."""
+    L = _lib.load()
+    cfg = _lib.HostPipelineConfig()
+    given = (("chunk_bytes", chunk_bytes), ("depth", depth), ("pageable_mode", pageable_mode), ("classify_min_clips", classify_min_clips))
+    if all(value is None for _, value in given):
+        _lib.check(L.dsp_host_pipeline_set(int(device), None), "dsp_host_pipeline_set")
+    else:
+        _lib.check(L.dsp_host_pipeline_get(int(device), C.byref(cfg)), "dsp_host_pipeline_get")
+        for name, value in given:
+            if value is not None:
+                setattr(cfg, name, int(value))
+        _lib.check(L.dsp_host_pipeline_set(int(device), C.byref(cfg)), "dsp_host_pipeline_set")
+    _lib.check(L.dsp_host_pipeline_get(int(device), C.byref(cfg)), "dsp_host_pipeline_get")
+    return cfg.chunk_bytes, cfg.depth, cfg.pageable_mode, cfg.classify_min_clips
+
+
+def host_pipeline_stats(device: int = 0) -> dict:
+    """What the last host call on `device` did (dsp_host_pipeline_stats): n_chunks, depth, input_path / output_path ("staged", "pinned",
+    "registered", or "direct": the caller's array handed to the runtime's copy as it is), bytes_h2d, bytes_d2h, peak_staging_bytes,
+    pinned_ring_bytes."""
+    st = _lib.HostStats()
+    _lib.check(_lib.load().dsp_host_pipeline_stats(int(device), C.byref(st)), "dsp_host_pipeline_stats")
+    out = {name: getattr(st, name) for name, _ in st._fields_}
+    out["input_path"], out["output_path"] = _lib.HOST_PATHS[st.input_path], _lib.HOST_PATHS[st.output_path]
+    return out
+
+
+def host_pipeline_release(device: int = 0) -> None:
+    """Returns the pipeline's pinned ring, device staging and streams (dsp_host_pipeline_release); the next host call makes them again."""
+    _lib.check(_lib.load().dsp_host_pipeline_release(int(device)), "dsp_host_pipeline_release")
+
+
+def plan_host_chunks(n_items: int, item_bytes: int, chunk_bytes: int, offsets=None) -> np.ndarray:
+    """The pipeline's chunk planner (dsp_host_plan_chunks, host only): int64 first[n_chunks + 1], chunk k = items [first[k], first[k + 1]).
+    offsets None: n_items uniform items of item_bytes; offsets [n_items + 1]: a ragged batch of samples of item_bytes bytes."""
+    L = _lib.load()
+    off = None if offsets is None else _lib.c_offsets(offsets)[0]
+    first = np.empty(int(n_items) + 1 if n_items >= 0 else 1, np.int64)
+    n = _lib.check(L.dsp_host_plan_chunks(int(n_items), int(item_bytes), off, int(chunk_bytes), first.ctypes.data_as(_lib.LP), first.size),
+                   "dsp_host_plan_chunks")
+    return first[:n + 1].copy()
+
+
 class MfccPlan(_lib.Handle):
     """dsp_mfcc_plan: device tables for one configuration on one GPU."""
 
@@ -89,17 +138,17 @@ class MfccPlan(_lib.Handle):
     def set_launch(self, blocks_per_cu: int = 0, frames_per_chunk: int = 0):
         _lib.check(self._L.dsp_mfcc_plan_set_launch(self._h, blocks_per_cu, frames_per_chunk), "dsp_mfcc_plan_set_launch")
 
-    # ---- host buffers -----------------------------------------------------
-    def frames_host(self, frames: np.ndarray) -> np.ndarray:
-        frames = np.ascontiguousarray(frames, np.float32)
+    # ---- host buffers: numpy arrays or CPU torch tensors (pinned ones are read by the copy engines directly) ----------------
+    def frames_host(self, frames) -> np.ndarray:
+        frames = _lib.host_array(frames, np.float32)
         if frames.ndim != 2 or frames.shape[1] != self.cfg.frame_length:
             raise ValueError(f"frames must be [n][{self.cfg.frame_length}]")
         out = np.empty((frames.shape[0], self.cfg.n_mfcc), np.float32)
         _lib.check(self._L.dsp_mfcc_frames_host(self._h, frames.ctypes.data, frames.shape[0], out.ctypes.data), "dsp_mfcc_frames_host")
         return out
 
-    def clips_host(self, clips: np.ndarray, max_frames: int) -> np.ndarray:
-        clips = np.ascontiguousarray(clips, np.float32)
+    def clips_host(self, clips, max_frames: int) -> np.ndarray:
+        clips = _lib.host_array(clips, np.float32)
         if clips.ndim == 1:
             clips = clips[None, :]
         n, s = clips.shape
@@ -110,6 +159,43 @@ class MfccPlan(_lib.Handle):
         got = _lib.check(self._L.dsp_mfcc_clips_host(self._h, clips.ctypes.data, n, s, s, out.ctypes.data, int(max_frames)), "dsp_mfcc_clips_host")
         assert got == t
         return out
+
+    def clips_pcm16_host(self, pcm, max_frames: int, stereo_mode: int = 0) -> np.ndarray:
+        """pcm: host int16 [n_clips][samples] (mono) or [n_clips][samples][2] (interleaved stereo; stereo_mode 0 = channel 0, 1 = channel
+        average) -> float32 [n_clips][T][n_mfcc], every row what clips_pcm16 gives (dsp_mfcc_clips_pcm16_host)."""
+        pcm = _lib.host_array(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None, :]
+        if pcm.ndim not in (2, 3) or (pcm.ndim == 3 and pcm.shape[2] != 2):
+            raise ValueError("pcm must be int16 [n_clips][n] or [n_clips][n][2]")
+        n, s = pcm.shape[:2]
+        t = frames_for(self.cfg, s, max_frames)
+        out = np.empty((n, t, self.cfg.n_mfcc), np.float32)
+        got = _lib.check(self._L.dsp_mfcc_clips_pcm16_host(self._h, pcm.ctypes.data, n, s, s, pcm.ndim - 1, int(stereo_mode), out.ctypes.data,
+                                                            int(max_frames)), "dsp_mfcc_clips_pcm16_host")
+        assert got == t or n == 0
+        return out
+
+    def clips_ragged_host(self, signal, offsets, max_frames: int, stereo_mode: int = 0):
+        """A ragged batch in host memory -- signal: float32 [total], int16 [total] (mono) or int16 [total][2] (interleaved stereo), clip c =
+        samples [offsets[c], offsets[c + 1]) per channel -- streamed through the GPU in chunks of whole clips.  Returns (mfcc,
+        frame_offsets) as clips_ragged does, the matrix a numpy float32 [F][n_mfcc] (dsp_mfcc_clips_ragged_host / _pcm16_host)."""
+        pcm = getattr(signal, "dtype", None) in (np.dtype(np.int16), _lib.torch_int16())
+        signal = _lib.host_array(signal, np.int16 if pcm else np.float32)
+        if signal.ndim != 1 and not (pcm and signal.ndim == 2 and signal.shape[1] == 2):
+            raise ValueError("signal must be float32 [total], int16 [total] or interleaved int16 [total][2]")
+        off, n = offsets if isinstance(offsets, tuple) else _lib.c_offsets(offsets)
+        if n and int(off[n]) > signal.shape[0]:
+            raise ValueError("offsets run past the end of the signal")
+        fo = ragged_frame_offsets(self.cfg, (off, n), max_frames)
+        out = np.empty((int(fo[-1]), self.cfg.n_mfcc), np.float32)
+        if pcm:
+            _lib.check(self._L.dsp_mfcc_clips_ragged_pcm16_host(self._h, signal.ctypes.data, n, off, signal.ndim, int(stereo_mode), int(max_frames),
+                                                                out.ctypes.data), "dsp_mfcc_clips_ragged_pcm16_host")
+        else:
+            _lib.check(self._L.dsp_mfcc_clips_ragged_host(self._h, signal.ctypes.data, n, off, int(max_frames), out.ctypes.data),
+                       "dsp_mfcc_clips_ragged_host")
+        return out, fo
 
     # ---- HBM-resident buffers (torch tensors on this plan's device) -----------
     def frames(self, frames, out=None):

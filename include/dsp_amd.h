@@ -193,10 +193,74 @@ int dsp_mfcc_clips_ragged_device(dsp_mfcc_plan *plan, const float *d_signal, lon
 int dsp_mfcc_clips_ragged_pcm16_device(dsp_mfcc_plan *plan, const int16_t *d_pcm, long n_clips, const long *offsets,
                                        int channels, int stereo_mode, int max_frames, float *d_out, void *stream);
 
-/* --- host-pointer conveniences: copy in, run, copy out, synchronise. -------- */
+/* --- host-pointer entries: the batch STREAMS through the GPU, the call is blocking. --------
+ * The arguments of the device entries with host pointers.  A batch in pinned memory larger than the host pipeline's chunk (below) is cut
+ * into chunks -- whole frames, whole clips -- that travel through a ring of staging buffers: the copy in of one chunk runs under the
+ * kernels and the copy out of the one before.  Device staging is then bounded by depth x chunk, never by the batch.  A batch that fits
+ * one chunk is one pass.  Every row is bit for bit the device entry's, wherever the cuts fall (under DSP_LOG_GLOBAL_REF1 the floor is
+ * per clip, and no clip is cut).  Memory from dsp_host_alloc (or any pinned / registered memory: hipHostMalloc, hipHostRegister, torch's
+ * pin_memory()) is read and written by the copy engines directly; what is done with pageable memory is the pipeline's pageable_mode
+ * (by default such a batch is not cut).  When the call returns every output byte is in `out` and nothing of the call is in flight.
+ * The ragged entries: out[frame_offsets[n_clips]][n_mfcc] with the frame_offsets of dsp_mfcc_ragged_frame_offsets.                      */
 int dsp_mfcc_frames_host(dsp_mfcc_plan *plan, const float *frames, long n_frames, float *out);
 int dsp_mfcc_clips_host(dsp_mfcc_plan *plan, const float *signal, long n_clips,
                         int samples_per_clip, long clip_stride, float *out, int max_frames);
+int dsp_mfcc_clips_pcm16_host(dsp_mfcc_plan *plan, const int16_t *pcm, long n_clips, int samples_per_clip, long clip_stride,
+                              int channels, int stereo_mode, float *out, int max_frames);
+int dsp_mfcc_clips_ragged_host(dsp_mfcc_plan *plan, const float *signal, long n_clips, const long *offsets, int max_frames, float *out);
+int dsp_mfcc_clips_ragged_pcm16_host(dsp_mfcc_plan *plan, const int16_t *pcm, long n_clips, const long *offsets, int channels,
+                                     int stereo_mode, int max_frames, float *out);
+
+/* Pinned host memory for C callers: what the host entries (these, and dsp_classify_batch*_host*) copy from and to without a bounce.
+ * dsp_host_alloc: bytes > 0 of page-locked memory, usable from every device; dsp_host_free(NULL) does nothing.                        */
+int dsp_host_alloc(int device, size_t bytes, void **out);
+void dsp_host_free(void *p);
+
+/* The host pipeline of a device (one per device, shared by every host entry that runs there; calls on one device queue).
+ * chunk_bytes >= 4096: the input bytes of one chunk; depth 1 .. 4: the ring's slots (1: copy, run and copy back strictly in turn);
+ * pageable_mode: what a call does with a batch in PAGEABLE memory that is larger than a chunk --
+ *   DSP_HOST_PAGEABLE_WHOLE     the batch is not cut: one chunk, as a batch that fits (a classifier: its sub-batches, copied _DIRECT)
+ *   DSP_HOST_PAGEABLE_REGISTER  page-locks the caller's input and output arrays for the duration of the call and copies as from pinned
+ *                               memory (where the runtime refuses: the input as _DIRECT, the output through the pinned ring)
+ *   DSP_HOST_PAGEABLE_DIRECT    hands the input to the runtime's own pageable copy chunk by chunk
+ *   DSP_HOST_PAGEABLE_STAGE     packs each chunk by memcpy into the ring's pinned buffer
+ * classify_min_clips >= 1: the fewest clips of a chunk of a classifier's batch, whatever chunk_bytes says (a pass walks each clip's
+ * recurrence in sequence, so a pass of few clips costs nearly what a pass of thousands does).  No setting changes a result bit.
+ * dsp_host_pipeline_set(device, NULL) puts the defaults back: chunk_bytes 64 MiB, depth 2, DSP_HOST_PAGEABLE_WHOLE, 65536 clips (a classifier's chunk is then a whole
+ * pass through its workspace; ragged batches: the bytes of that many seconds of audio)
+ * (DESIGN.md has the measurements behind them).  A batch of ONE chunk is copied, run and copied back on the null stream straight from
+ * and to the caller's arrays, as one pass.  _set, _get and _stats touch no device; dsp_host_pipeline_release returns the ring's pinned
+ * and device memory and its copy stream (they come back with the next call that needs them).
+ * dsp_host_pipeline_stats: what the LAST host call on that device did -- its chunks, the ring depth it used (1 for a single chunk), the
+ * bytes copied each way, the path the input and the output took (DSP_HOST_PATH_*: _DIRECT is the caller's array handed to the runtime's
+ * copy as it is), the most device staging the ring held during the call and the ring's pinned bytes after it.                      */
+enum { DSP_HOST_PATH_STAGED = 0, DSP_HOST_PATH_PINNED = 1, DSP_HOST_PATH_REGISTERED = 2, DSP_HOST_PATH_DIRECT = 3 };
+enum { DSP_HOST_PAGEABLE_STAGE = 0, DSP_HOST_PAGEABLE_REGISTER = 1, DSP_HOST_PAGEABLE_DIRECT = 2, DSP_HOST_PAGEABLE_WHOLE = 3 };
+typedef struct {
+    long chunk_bytes;
+    int depth;
+    int pageable_mode;
+    int classify_min_clips;
+} dsp_host_pipeline_config;
+typedef struct {
+    long n_chunks;
+    int depth;
+    int input_path, output_path;
+    long bytes_h2d, bytes_d2h;
+    long peak_staging_bytes;
+    long pinned_ring_bytes;
+} dsp_host_stats;
+int dsp_host_pipeline_set(int device, const dsp_host_pipeline_config *cfg);
+int dsp_host_pipeline_get(int device, dsp_host_pipeline_config *cfg);
+int dsp_host_pipeline_release(int device);
+int dsp_host_pipeline_stats(int device, dsp_host_stats *out);
+/* The pipeline's chunk planner, host only (no device is touched).  offsets == NULL: n_items uniform items of item_bytes each, floor(
+ * chunk_bytes / item_bytes) per chunk, at least 1.  offsets given (n_items + 1, non-decreasing): a ragged batch of samples of
+ * item_bytes bytes each, cut at clip boundaries only and filled greedily up to chunk_bytes; a clip longer than chunk_bytes is the only
+ * clip with samples of its chunk; empty clips never open a chunk of their own.  Chunk k is items [first[k], first[k + 1]); the chunks
+ * tile the batch in order.  Returns the number of chunks (0 for an empty batch); first (may be NULL: count only) gets the returned
+ * count + 1 entries and must have room for max_first, else DSP_EINVAL.                                                              */
+long dsp_host_plan_chunks(long n_items, long item_bytes, const long *offsets, long chunk_bytes, long *first, long max_first);
 
 /* Launch geometry knobs for tuning / profiling (0 = library default). */
 int dsp_mfcc_plan_set_launch(dsp_mfcc_plan *plan, int blocks_per_cu, int frames_per_chunk);
