@@ -5,7 +5,8 @@ the batch.  The layer-1 feature sum is numpy's own (a matmul) by default; featur
 descending, whose difference is the spread the device's allowance is four times of.
 
 tests/test_stoptrain_cpu.py pins the restatement (torch.autograd, Adam's first step, early stopping) and the C ABI's host helpers against
-it; tests/test_gpu_stoptrain.py holds the kernels to it."""
+it; tests/test_gpu_stoptrain.py and tests/test_gpu_stoptrain_shapes.py hold the kernels to it on the cases of case(); DEFECTS are
+mistakes planted into it, by which tests/test_stoptrain_shapes_cpu.py shows what the cases can see."""
 from __future__ import annotations
 
 import math
@@ -215,9 +216,40 @@ def dropout_masks(seed: int, gstep: int, batch: int, units, rates):
     return out
 
 
-def forward(ws, bs, zb, masks=None, scales=(1.0, 1.0, 1.0), feature_order="numpy"):
+def padded_units(u1: int) -> int:
+    """the layer-1 width the kernels are instantiated at (stoptrain_kernels.hip padded_units): units u1 .. padded - 1 are padding"""
+    return 4 if u1 <= 4 else (8 if u1 <= 8 else 16)
+
+
+# Planted mistakes of the kind the kernels' index arithmetic could hold (tests/test_stoptrain_shapes_cpu.py): each is the identity on
+# cases A, B and C.
+#   w3_stride    every forward pass reads layer 3's kernel as w3[i * u2 + o] of the flat parameters behind it (bias3, kernel4, bias4,
+#                then zeros) in place of w3[i * u3 + o]: nothing where u2 == u3
+#   chunk_row    the first row of every 256-row evaluation chunk but the first (validation, prob, the dead-unit pass) takes the logit
+#                of the row in front of it: nothing below 257 rows
+#   padded_down  layer 1's padded width rounded down to a power of two (at least 4), the kernel of the units from there on read as 0
+#                in every forward pass: nothing where u1 is 4, 8 or 16
+DEFECTS = ("w3_stride", "chunk_row", "padded_down")
+
+
+def _defective(ws, bs, defect):
+    """the weights a forward pass with the planted mistake reads"""
+    if defect == "w3_stride":
+        u2, u3 = ws[2].shape
+        flat = np.concatenate([ws[2].reshape(-1), bs[2], ws[3].reshape(-1), bs[3], np.zeros(u2 * u2)])
+        ws = ws[:2] + [flat[np.arange(u2)[:, None] * u2 + np.arange(u3)[None, :]]] + ws[3:]
+    elif defect == "padded_down":
+        u1 = ws[0].shape[1]
+        wrong = max(4, 1 << (u1.bit_length() - 1))
+        ws = [np.where(np.arange(u1)[None, :] < wrong, ws[0], 0.0)] + ws[1:]
+    return ws
+
+
+def forward(ws, bs, zb, masks=None, scales=(1.0, 1.0, 1.0), feature_order="numpy", defect=None):
     """-> (logits [B], [h1, h2, h3]): ReLU hidden layers, inverted dropout where masks are given"""
     hs, h = [], None
+    if defect is not None:
+        ws = _defective(ws, bs, defect)
     for l in range(3):
         a = (_layer1(zb, ws[0], feature_order) if l == 0 else h @ ws[l]) + bs[l]
         h = np.maximum(a, 0.0)
@@ -227,9 +259,9 @@ def forward(ws, bs, zb, masks=None, scales=(1.0, 1.0, 1.0), feature_order="numpy
     return (h @ ws[3])[:, 0] + bs[3][0], hs
 
 
-def batch_gradient(ws, bs, zb, yb, masks=None, scales=(1.0, 1.0, 1.0), feature_order="numpy"):
+def batch_gradient(ws, bs, zb, yb, masks=None, scales=(1.0, 1.0, 1.0), feature_order="numpy", defect=None):
     """-> (per-sample losses [B], [gW] * 4, [gb] * 4) of the batch's mean loss"""
-    a, hs = forward(ws, bs, zb, masks, scales, feature_order)
+    a, hs = forward(ws, bs, zb, masks, scales, feature_order, defect)
     d = (sigmoid(a) - yb) / yb.size
     gw, gb = [None] * 4, [None] * 4
     gw[3], gb[3] = hs[2].T @ d[:, None], np.array([d.sum()])
@@ -278,10 +310,19 @@ def early_stopping(val_losses, patience: int, epochs: int):
     return n, es.best_epoch, es.best_epoch
 
 
-def train_run(z, labels, n_coef: int, max_frames: int, units, run: dict, feature_order="numpy"):
+def evaluate(ws, bs, zb, feature_order="numpy", defect=None):
+    """forward() without dropout over rows in the kernels' chunks of 256"""
+    if defect == "chunk_row" and zb.shape[0] > 256:
+        first = np.arange(256, zb.shape[0], 256)
+        zb = zb.copy()
+        zb[first] = zb[first - 1]
+    return forward(ws, bs, zb, feature_order=feature_order, defect=defect)
+
+
+def train_run(z, labels, n_coef: int, max_frames: int, units, run: dict, feature_order="numpy", defect=None):
     """One run on the standardised used features z [n][F_used] float32 -> dict(history [epochs][2], params flat [n_params], prob [n],
     n_epochs, best_epoch, best_val_loss, last_loss, status, val_correct, n_dead_units, margin: the smallest |val_loss - best| any
-    early-stopping comparison saw, p_margin: the smallest |P - 0.5| over the validation rows)."""
+    early-stopping comparison saw, p_margin: the smallest |P - 0.5| over the validation rows).  defect: one of DEFECTS, planted."""
     h = {**HYPER, **run}
     z = np.asarray(z, F32).astype(np.float64)
     y_all = np.asarray(labels).astype(np.float64)
@@ -306,7 +347,7 @@ def train_run(z, labels, n_coef: int, max_frames: int, units, run: dict, feature
         for s0 in range(0, perm.size, batch):
             rows = perm[s0:s0 + batch]
             masks = dropout_masks(seed, gstep, rows.size, units, rates)
-            loss, gw, gb = batch_gradient(ws, bs, z[rows], y_all[rows], masks, scales, feature_order)
+            loss, gw, gb = batch_gradient(ws, bs, z[rows], y_all[rows], masks, scales, feature_order, defect)
             total += loss.sum() / rows.size * rows.size
             gstep += 1
             for p, m, v, g in zip(state, ms, vs, gw + gb):
@@ -315,7 +356,7 @@ def train_run(z, labels, n_coef: int, max_frames: int, units, run: dict, feature
         n_epochs = epoch + 1
         val_loss = math.nan
         if val_rows.size:
-            val_loss = float(bce_from_logit(forward(ws, bs, z[val_rows], feature_order=feature_order)[0], y_all[val_rows]).sum() / val_rows.size)
+            val_loss = float(bce_from_logit(evaluate(ws, bs, z[val_rows], feature_order, defect)[0], y_all[val_rows]).sum() / val_rows.size)
         history[epoch] = last_loss, val_loss
         if val_rows.size:
             improved, stop = es.update(val_loss, epoch)
@@ -327,10 +368,10 @@ def train_run(z, labels, n_coef: int, max_frames: int, units, run: dict, feature
     if h["restore_best"] and val_rows.size and best_state is not None:
         state = best_state
     ws, bs = state[:4], state[4:]
-    prob = sigmoid(forward(ws, bs, z, feature_order=feature_order)[0])
+    prob = sigmoid(evaluate(ws, bs, z, feature_order, defect)[0])
     dead = 0
     if train_rows.size:
-        dead = int(sum((hl.max(axis=0) <= 0).sum() for hl in forward(ws, bs, z[train_rows], feature_order=feature_order)[1]))
+        dead = int(sum((hl.max(axis=0) <= 0).sum() for hl in evaluate(ws, bs, z[train_rows], feature_order, defect)[1]))
     w1 = w1_full.copy()
     w1[idx] = ws[0]
     return {"history": history, "params": pack([w1] + ws[1:], bs), "prob": prob, "n_epochs": n_epochs, "best_epoch": es.best_epoch,
@@ -349,7 +390,7 @@ def relative(a, b) -> float:
     return float(np.abs(a[ok] - b[ok]).max() / max(np.abs(a[ok]).max(), np.abs(b[ok]).max(), 1e-300))
 
 
-# ---- the GPU tests' cases (tests/test_gpu_stoptrain.py), shared with the spread test ------------------------------------------------------
+# ---- the GPU tests' cases (tests/test_gpu_stoptrain*.py), shared with the spread test ------------------------------------------------------
 
 def planted(seed: int, n_coef: int, lengths, frames_for_direction: int):
     """A seeded synthetic set with consumer_ref's data shape: ragged MFCC rows, and labels separable by a planted direction over the first
@@ -367,38 +408,70 @@ def planted(seed: int, n_coef: int, lengths, frames_for_direction: int):
     return mfcc, fo, labels.astype(np.int32)
 
 
+OFF = (0.0, 0.0, 0.0)
+# name: n_coef, max_frames, units, clips, frames per clip (one number, or lo .. hi drawn with both ends present), n_train, the runs' base
+SHAPES = {
+    "A": (3, 7, (4, 2, 2, 1), 23, (2, 9), 17, dict(batch_size=4, epochs=6, patience=10, learning_rate=1e-2)),
+    "B": (13, 50, (16, 16, 16, 1), 70, 50, 50, dict(batch_size=32, epochs=5, patience=10, learning_rate=1e-3)),
+    "C": (13, 500, (4, 2, 2, 1), 40, 98, 30, dict(batch_size=32, epochs=12, patience=3, learning_rate=3e-2)),
+    "D": (5, 9, (7, 3, 5, 1), 600, (3, 11), 300, dict(batch_size=256, epochs=6, patience=10, learning_rate=1e-2)),
+    "E": (2, 6, (1, 1, 1, 1), 40, (2, 7), 25, dict(batch_size=4, epochs=6, patience=10, learning_rate=1e-2)),
+    "F": (4, 70, (12, 16, 9, 1), 90, 70, 60, dict(batch_size=16, epochs=4, patience=10, learning_rate=1e-2)),
+    "G": (16, 16, (3, 5, 2, 1), 50, 16, 33, dict(batch_size=8, epochs=5, patience=10, learning_rate=1e-2)),
+    "H": (3, 11, (8, 16, 1, 1), 60, (2, 8), 40, dict(batch_size=8, epochs=5, patience=10, learning_rate=1e-2)),
+}
+CASES_OLD, CASES_NEW = ("A", "B", "C"), ("D", "E", "F", "G", "H")
+ODD_BATCH = {"E": 3, "F": 7, "G": 5, "H": 3}       # no multiple of 32 / padded_units(u1), the samples layer 1 takes at a time
+# Chosen on the CPU, from the restatement alone, so that every deciding val_loss comparison of the cases' runs has a margin above 1e-6, every
+# validation row's |P - 0.5| too, and the ascending, descending and numpy-order restatements agree on every integer result
+# (test_restatement_spread asserts it).  Measured, spread between the ascending and descending layer-1 sums / smallest margin / smallest
+# p_margin over the case's runs:
+#   A 6.1e-16   B 5.0e-15   C 6.5e-15   (margins in tests/test_stoptrain_cpu.py)
+#   D 3.4e-15 / 6.1e-3 / 5.8e-4   (the patience-0 pair: 4 epochs, best epoch 2, margin 2.2e-2)
+#   E 2.4e-16 / 3.7e-4 / 2.5e-3
+#   F 2.0e-15 / 1.5e-3 / 1.9e-4
+#   G 1.2e-15 / 1.5e-2 / 9.4e-4
+#   H 4.9e-15 / 3.5e-3 / 2.9e-4
+# so the allowance max(4 x spread, FLOOR) is FLOOR = 1e-9 in every case.
+CASE_SEEDS = {"A": 100, "B": 100, "C": 110, "D": 100, "E": 100, "F": 100, "G": 100, "H": 100}
+# case D's patience-0 pair: seed and learning rate at which the restatement's val_loss rises before the last epoch, so that the run stops
+# early one epoch behind its best and restore_best decides which weights come back
+D_STOP = dict(seed=201, learning_rate=1e-1)
+
+
 def case(name: str) -> dict:
-    """the cases of DESIGN.md 3.21: shapes, data and the runs the GPU tests train"""
-    rng = np.random.default_rng({"A": 11, "B": 12, "C": 13}[name])
-    if name == "A":
-        n_coef, max_frames, units, lengths = 3, 7, (4, 2, 2, 1), [int(v) for v in rng.integers(2, 10, 23)]
-        lengths[0], lengths[1] = 2, 9
-        base = dict(batch_size=4, epochs=6, patience=10, learning_rate=1e-2)
-        n_train = 17
-    elif name == "B":
-        n_coef, max_frames, units, lengths = 13, 50, (16, 16, 16, 1), [50] * 70
-        base = dict(batch_size=32, epochs=5, patience=10, learning_rate=1e-3)
-        n_train = 50
+    """the cases of DESIGN.md 3.21: shapes, data and the runs the GPU tests train.  A, B, C: dropout on, off, batch 1, batch >= n_train.
+    D: the row-count edges (300 training rows, 300 validation rows, batch 256 / 37 without restore_best / 33 / 1 and the patience-0
+    pair with and without restore_best).  E .. H: dropout on, off, ODD_BATCH, batch >= n_train."""
+    n_coef, max_frames, units, n, frames, n_train, base = SHAPES[name]
+    rng = np.random.default_rng(11 + "ABCDEFGH".index(name))
+    if isinstance(frames, tuple):
+        lengths = [int(v) for v in rng.integers(frames[0], frames[1] + 1, n)]
+        lengths[0], lengths[1] = frames
     else:
-        n_coef, max_frames, units, lengths = 13, 500, (4, 2, 2, 1), [98] * 40
-        base = dict(batch_size=32, epochs=12, patience=3, learning_rate=3e-2)
-        n_train = 30
-    mfcc, fo, labels = planted({"A": 1, "B": 2, "C": 3}[name], n_coef, lengths, 2)
-    n = len(lengths)
+        lengths = [frames] * n
+    mfcc, fo, labels = planted(1 + "ABCDEFGH".index(name), n_coef, lengths, 2)
     perm = np.random.default_rng(5).permutation(n)
     train_rows, val_rows = np.sort(perm[:n_train]).astype(np.int32), np.sort(perm[n_train:]).astype(np.int32)
     rows = dict(train_rows=train_rows, val_rows=val_rows)
     seed = CASE_SEEDS[name]
-    runs = [dict(rows, seed=seed, **base),                                                     # dropout on
-            dict(rows, seed=seed + 1, dropout=(0.0, 0.0, 0.0), **base),                          # dropout off
-            dict(rows, seed=seed + 2, **{**base, "batch_size": 1, "epochs": 2}),                  # batch 1
-            dict(rows, seed=seed + 3, **{**base, "batch_size": 256 if n_train <= 256 else 256})]   # batch >= n_train
+    if name == "D":
+        stop = dict(rows, restore_best=True, **{**base, **D_STOP, "batch_size": 32, "patience": 0})
+        runs = [dict(rows, seed=seed, **base),                                                 # a full batch of 256, then 44
+                dict(rows, seed=seed + 1, **{**base, "batch_size": 37, "restore_best": False}),   # sub-batches 32 + 5, last batch 4
+                dict(rows, seed=seed + 2, dropout=OFF, **{**base, "batch_size": 33}),
+                dict(rows, seed=seed + 3, **{**base, "batch_size": 1, "epochs": 2}),
+                stop, dict(stop, restore_best=False)]
+    else:
+        third = {"batch_size": 1, "epochs": 2} if name in CASES_OLD else {"batch_size": ODD_BATCH[name]}
+        runs = [dict(rows, seed=seed, **base),                                                 # dropout on
+                dict(rows, seed=seed + 1, dropout=OFF, **base),                                  # dropout off
+                dict(rows, seed=seed + 2, **{**base, **third}),                                   # batch 1 / an odd batch
+                dict(rows, seed=seed + 3, **{**base, "batch_size": 256 if name in CASES_OLD else n_train + (name != "G") * 4})]   # batch >= n_train
     return {"name": name, "n_coef": n_coef, "max_frames": max_frames, "units": units, "mfcc": mfcc, "frame_offsets": fo, "labels": labels,
             "runs": runs, "train_rows": train_rows, "val_rows": val_rows}
 
 
-# chosen on the CPU so that every deciding val_loss comparison of the cases' runs has a margin above 1e-6 (test_restatement_spread asserts it)
-CASE_SEEDS = {"A": 100, "B": 100, "C": 110}
 _CACHE = {}
 
 

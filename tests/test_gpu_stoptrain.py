@@ -10,7 +10,8 @@ each with dropout on and off, at batch 1 and at batch >= n_train.  The parity al
 restatement's own spread between the layer-1 feature sum taken ascending and descending over these runs, floored at 1e-9 relative
 (stoptrain_ref.case_reference, asserted on the CPU by tests/test_stoptrain_cpu.py test_restatement_spread; measured spreads 6e-16 ..
 7e-15, so the floor holds).  Relative means: of the array's largest magnitude (stoptrain_ref.relative).  Nothing here is derived from
-what the GPU returns."""
+what the GPU returns.  The other kernel forms, unequal layers and more than 256 rows: tests/test_gpu_stoptrain_shapes.py, through the
+same helpers (tests/stoptrain_util.py)."""
 import ctypes as C
 import re
 
@@ -18,37 +19,21 @@ import numpy as np
 import pytest
 
 import dsp_amd
-from dsp_amd import consumers as dc
 from dsp_amd import lib as dl
 
-from tests import consumer_ref as CR
 from tests import stoptrain_ref as R
+from tests import stoptrain_util as U
+from tests.stoptrain_util import INT_FIELDS
 
 pytestmark = pytest.mark.gpu
-CASES = ("A", "B", "C")
-INT_FIELDS = ("n_epochs", "best_epoch", "status", "val_correct", "n_dead_units")
-
-
-def _cuda(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+CASES = R.CASES_OLD
+_cuda, _bytes = U.cuda, U.result_bytes
 
 
 @pytest.fixture(scope="module")
 def cases():
     """per case: the restatement's answers (computed once, left unchanged) and the device's, from ONE launch of all of its runs"""
-    out = {}
-    for name in CASES:
-        c = dict(R.case_reference(name))
-        t = dc.StopTrainer(c["n_coef"], c["max_frames"], c["units"])
-        c["d_mfcc"] = _cuda(c["mfcc"])
-        c["got_mean"], c["got_scale"] = t.set(c["d_mfcc"], c["frame_offsets"], scaler_rows=c["train_rows"])
-        res, hist, prob, params = t.train(c["runs"], c["labels"])
-        c["trainer"], c["res"], c["hist"], c["prob"], c["params"] = t, res, hist.cpu().numpy(), prob.cpu().numpy(), params.cpu().numpy()
-        out[name] = c
-    yield out
-    for c in out.values():
-        c["trainer"].close()
+    yield from U.trained_cases(CASES)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -56,13 +41,7 @@ def test_scaler_and_rows(cases, name):
     """the fitted Scaler equals the restatement's float64 results rounded to float32 bit for bit (the restatement takes the kernel's
     summation tree), in the layout dsp_stop_model_params reads; Z equals the inference expression bit for bit"""
     c = cases[name]
-    assert np.array_equal(c["got_mean"], c["mean"]) and np.array_equal(c["got_scale"], c["scale"])
-    z = c["trainer"].rows()
-    assert z.shape == c["z"].shape == (c["labels"].size, c["trainer"].f_used) and np.array_equal(z.view(np.uint32), c["z"].view(np.uint32))
-    net_div = np.where(c["scale"] == 0, np.float32(1), c["scale"])
-    idx = R.used_index(c["n_coef"], c["max_frames"], z.shape[1] // c["n_coef"])
-    x = R.features(c["mfcc"], c["frame_offsets"], c["n_coef"], c["max_frames"])
-    assert np.array_equal(z, ((x - c["mean"][idx]).astype(np.float32) / net_div[idx]).astype(np.float32))   # consumer_ref.StopNet.standardise
+    z = U.check_scaler_and_rows(c)
     if name == "A":
         assert z.shape[1] == 21 and (np.diff(c["frame_offsets"]) > 7).any() and (np.diff(c["frame_offsets"]) < 7).any()
 
@@ -74,25 +53,9 @@ def test_trajectories(cases, name):
     c = cases[name]
     assert len(c["runs"]) == 4 and c["runs"][1]["dropout"] == (0.0, 0.0, 0.0) and c["runs"][2]["batch_size"] == 1
     assert c["runs"][3]["batch_size"] >= c["train_rows"].size and max(c["runs"][0]["dropout"] if "dropout" in c["runs"][0] else R.HYPER["dropout"]) > 0
-    max_epochs = max(r["epochs"] for r in c["runs"])
-    for k, (run, ref) in enumerate(zip(c["runs"], c["numpy"])):
-        assert ref["margin"] > 1e-6 and ref["p_margin"] > 1e-6
-        got = c["res"][k]
-        hist = np.full((max_epochs, 2), np.nan)
-        hist[:run["epochs"]] = ref["history"]
-        worst = {"history": R.relative(c["hist"][k], hist), "params": R.relative(c["params"][k], ref["params"]), "prob": R.relative(c["prob"][k], ref["prob"])}
-        print(f"{name} run {k}: {worst}, allowance {c['allow']:.1e}")
-        for field in INT_FIELDS:
-            assert got[field] == ref[field], (k, field, got[field], ref[field])
-        assert max(worst.values()) <= c["allow"], (k, worst)
-        assert abs(got["best_val_loss"] - ref["best_val_loss"]) <= c["allow"] * abs(ref["best_val_loss"])
-        assert abs(got["last_loss"] - ref["last_loss"]) <= c["allow"] * abs(ref["last_loss"])
+    U.check_trajectories(c)
     if name == "C":
         assert any(r["status"] == dl.STOP_TRAIN_CONVERGED_EARLY and r["n_epochs"] < 12 for r in c["res"])
-
-
-def _bytes(res, hist, prob, params, k):
-    return res[k].tobytes(), hist[k].cpu().numpy().tobytes(), prob[k].cpu().numpy().tobytes(), params[k].cpu().numpy().tobytes()
 
 
 def test_bit_identity(cases):
@@ -175,22 +138,8 @@ def test_round_trip_and_fit(cases):
     seeds returns the run with the lowest best_val_loss"""
     c = cases["C"]
     t = c["trainer"]
-    k = 0
-    model = dc.stop_model_from_training(c["n_coef"], c["max_frames"], c["units"], c["params"][k], c["got_mean"], c["got_scale"])
-    want = R.model_from_training(c["n_coef"], c["max_frames"], c["units"], c["params"][k], c["mean"], c["scale"])
-    for key in want:
-        assert np.array_equal(np.asarray(model[key]), np.asarray(want[key])), key
-    sm = dsp_amd.StopModel(model)
-    got = sm.predict(c["d_mfcc"].reshape(40, 98, 13)).cpu().numpy()
-    net = CR.StopNet(model)
-    fo = c["frame_offsets"]
-    for i in range(0, 40, 3):
-        p, bound = net.prob(c["mfcc"][fo[i]:fo[i + 1]])
-        # the float32 net against its own reference, and against the float64 training-time probability: the parameters' float32
-        # rounding (2^-24 relative per layer-1 term, inside the bound's 2^-22) and the float32 tail (a few 1e-7)
-        assert abs(float(got[i]) - float(p)) <= bound + 1e-6
-        assert abs(float(got[i]) - c["prob"][k][i]) <= 2 * bound + 2e-6, (i, got[i], c["prob"][k][i], bound)
-    sm.close()
+    assert c["labels"].size == 40 and (np.diff(c["frame_offsets"]) == 98).all() and c["n_coef"] == 13
+    U.check_round_trip(c, 0, range(0, 40, 3))
     seeds = list(range(16))
     hyper = {key: c["runs"][0][key] for key in ("batch_size", "epochs", "patience", "learning_rate")}
     fitted, report = t.fit(c["labels"], c["train_rows"], c["val_rows"], seeds=seeds, **hyper)
