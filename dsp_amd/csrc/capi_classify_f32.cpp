@@ -403,7 +403,7 @@ int dsp_classify_ctx_create(int device, dsp_classify_ctx **out)
     *out = nullptr;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return dsp::capi_fail(DSP_ENODEV, "no HIP device: libdsp_amd has no CPU fallback");
-    if (device < 0 || device >= n || device >= front::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
+    if (device < 0 || device >= n || device >= dsp::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
     auto *ctx = new (std::nothrow) dsp_classify_ctx;
     if (!ctx) return dsp::capi_fail(DSP_ENOMEM, "out of memory");
     ctx->device = device;
@@ -433,7 +433,7 @@ int dsp_classify_batch_device_ctx(dsp_classify_ctx *ctx, const dsp_classify_conf
  * from two threads: on two devices the holds overlap, on one device they queue. */
 int dsp_debug_hold_classify_ctx(int device, int hold_ms)
 {
-    if (device < 0 || device >= front::kMaxDevices || hold_ms < 0 || hold_ms > 10000) return dsp::capi_fail(DSP_EINVAL, "bad argument");
+    if (device < 0 || device >= dsp::kMaxDevices || hold_ms < 0 || hold_ms > 10000) return dsp::capi_fail(DSP_EINVAL, "bad argument");
     std::lock_guard<std::mutex> lock(g_cls_ctx[device].mu);
     std::this_thread::sleep_for(std::chrono::milliseconds(hold_ms));
     return DSP_OK;
@@ -441,7 +441,7 @@ int dsp_debug_hold_classify_ctx(int device, int hold_ms)
 
 int dsp_classify_stats(int device, long *gated_segments, long *listed_clips)
 {
-    if (device < 0 || device >= front::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
+    if (device < 0 || device >= dsp::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
     ClassifyCtx &g_cls = g_cls_ctx[device];
     std::lock_guard<std::mutex> lock(g_cls.mu);
     if (g_cls.device < 0 || !g_cls.d_gate) return dsp::capi_fail(DSP_EINVAL, "no classifier pass has run on this device");

@@ -263,7 +263,7 @@ int dsp_classify_batch_ragged_pcm16_host_f64(const dsp_classify_config_f64 *cfgp
 
 int dsp_classify_stats_f64(int device, long *segments, long *undecided, long *listed_clips)
 {
-    if (device < 0 || device >= front::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
+    if (device < 0 || device >= dsp::kMaxDevices) return dsp::capi_fail(DSP_EINVAL, "device index out of range");
     Scratch &w = g_w[device];
     std::lock_guard<std::mutex> lock(w.mu);
     if (w.device < 0 || !w.want) return dsp::capi_fail(DSP_EINVAL, "no float64 classifier pass has run on this device");
@@ -280,7 +280,7 @@ int dsp_classify_stats_f64(int device, long *segments, long *undecided, long *li
 
 int dsp_classify_debug_f64(int device, int *out, int n_ints)      /* diagnostic builds: the screening kernel's per-block records */
 {
-    if (device < 0 || device >= front::kMaxDevices || !out || n_ints < 0 || n_ints > 16 * 4096) return dsp::capi_fail(DSP_EINVAL, "bad argument");
+    if (device < 0 || device >= dsp::kMaxDevices || !out || n_ints < 0 || n_ints > 16 * 4096) return dsp::capi_fail(DSP_EINVAL, "bad argument");
     Scratch &w = g_w[device];
     std::lock_guard<std::mutex> lock(w.mu);
     if (!w.cu_table) return dsp::capi_fail(DSP_EINVAL, "no pass has run");

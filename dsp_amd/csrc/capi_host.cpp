@@ -13,7 +13,7 @@ using dsp::capi_fail;
 
 static int check_pipe_device(int device)
 {
-    return device >= 0 && device < host::kMaxDevices ? DSP_OK : capi_fail(DSP_EINVAL, "device index out of range");
+    return device >= 0 && device < dsp::kMaxDevices ? DSP_OK : capi_fail(DSP_EINVAL, "device index out of range");
 }
 
 extern "C" {

@@ -1,5 +1,6 @@
-// capi_util.hpp -- error reporting, device scopes, the owner of device buffers, the ragged-span ring, the scans' host planner and the
-// score-matrix stages' handle, shared by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
+// capi_util.hpp -- error reporting, device scopes, the owners of device and pinned host buffers (DeviceBuf, PinnedBuf), the
+// ragged-span ring, the scans' host planner, the score-matrix stages' handle and the number of devices that have state of their own
+// (kMaxDevices), shared by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
 // classifiers' front end classify_front.hpp).  Nothing here knows a plan: what reads one is mfcc_plan.hpp.
 #pragma once
 
@@ -19,6 +20,57 @@
 
 namespace dsp {
 int capi_fail(int code, const std::string &msg);   // sets dsp_last_error() for this thread, returns code
+
+// the devices that have a classifier workspace (classify_front.hpp) and a host pipeline (host_pipe.hpp) of their own
+constexpr int kMaxDevices = 64;
+
+// The owner of one buffer of the runtime's and of its size: whoever holds it frees it, once, on destruction or reset().  Move-only.
+// DeviceBuf<T> is hipMalloc'ed, PinnedBuf page-locked host memory (hipHostMalloc); these two and the public allocator of
+// capi_host.cpp are the only callers of the runtime's allocation functions in the host code.
+// Its holder makes the buffer's device current before the buffer is let go (the destroy functions' DeviceScope), and no object of
+// static storage holds one: at process exit the HIP runtime may already be gone.
+template <class T, bool kPinned> class OwnedBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+public:
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~OwnedBuf() { reset(); }
+    void reset()
+    {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // exactly `bytes`, in place of what was held; empty on an error
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        void *q = nullptr;
+        const hipError_t e = kPinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+        if (e == hipSuccess) { p = static_cast<T *>(q); cap = bytes; }
+        return e;
+    }
+    // a grow-only workspace: at least `bytes` afterwards (its contents are not kept), or empty on an error
+    hipError_t reserve(size_t bytes) { return cap >= bytes ? hipSuccess : alloc(bytes); }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    size_t bytes() const { return cap; }
+};
+template <class T> using DeviceBuf = OwnedBuf<T, false>;
+using PinnedBuf = OwnedBuf<char, true>;
+
+// a new buffer holding a copy of the host's object
+template <class T> hipError_t upload(DeviceBuf<T> &buf, const T &host)
+{
+    const hipError_t e = buf.alloc(sizeof(T));
+    return e == hipSuccess ? hipMemcpy(buf, &host, sizeof(T), hipMemcpyHostToDevice) : e;
+}
 }
 
 // Ragged batches: the clips' spans (clip_span.hpp ClipSpan: start, samples, frames, caller's index -- 32 bytes per clip) travel to the GPU through a
@@ -36,7 +88,7 @@ namespace dsp {
 struct ClipSpan;
 struct SpanRing {
     static constexpr int kSlots = 4, kMaxSlots = 32;
-    struct Slot { void *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false, held = false; };
+    struct Slot { PinnedBuf h; DeviceBuf<char> d; hipEvent_t done = nullptr; bool used = false, held = false; };      // (h and d of one size)
     class Lease {
         friend struct SpanRing;
         SpanRing *ring = nullptr;
@@ -55,13 +107,13 @@ struct SpanRing {
             s->held = false;
             ring->freed.notify_all();
         }
-        void *h() const { return s->h; }
-        void *d() const { return s->d; }
+        void *h() const { return s->h.get(); }
+        void *d() const { return s->d.get(); }
         hipError_t upload(size_t bytes, hipStream_t stream)
         {
             st = stream;
             uploaded = true;
-            return hipMemcpyAsync(s->d, s->h, bytes, hipMemcpyHostToDevice, stream);
+            return hipMemcpyAsync(s->d.get(), s->h.get(), bytes, hipMemcpyHostToDevice, stream);
         }
     };
     std::vector<std::unique_ptr<Slot>> slots;      // (their addresses stay put as the ring grows: leases point at them)
@@ -102,14 +154,11 @@ struct SpanRing {
         if (!s.done && (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return e;
         if (s.used && (e = hipEventSynchronize(s.done)) != hipSuccess) return e;
         s.used = false;
-        if (s.cap < bytes) {
-            if (s.h) (void)hipHostFree(s.h);
-            if (s.d) (void)hipFree(s.d);
-            s.h = s.d = nullptr; s.cap = 0;
+        if (s.d.bytes() < bytes) {      // (the pair is let go before either is made anew; d is made last: its size is the pair's)
+            s.h.reset();
+            s.d.reset();
             const size_t cap = bytes + bytes / 2 + 4096;
-            if ((e = hipHostMalloc(&s.h, cap, hipHostMallocDefault)) != hipSuccess) return e;
-            if ((e = hipMalloc(&s.d, cap)) != hipSuccess) return e;
-            s.cap = cap;
+            if ((e = s.h.alloc(cap)) != hipSuccess || (e = s.d.alloc(cap)) != hipSuccess) return e;
         }
         return hipSuccess;
     }
@@ -119,11 +168,9 @@ struct SpanRing {
         for (auto &sp : slots) {
             Slot &s = *sp;
             if (s.used) (void)hipEventSynchronize(s.done);
-            if (s.h) (void)hipHostFree(s.h);
-            if (s.d) (void)hipFree(s.d);
             if (s.done) (void)hipEventDestroy(s.done);
         }
-        slots.clear();
+        slots.clear();      // (with the slots' buffers)
         next = 0;
     }
 };
@@ -174,48 +221,6 @@ inline int pcm16_kind(int channels, int stereo_mode)
     return channels == 1 ? 1 : (stereo_mode == DSP_STEREO_CHANNEL0 ? 2 : 3);
 }
 
-// The owner of one hipMalloc'ed buffer and of its size: whoever holds it frees it, once, on destruction or reset().  Move-only.
-// Its holder makes the buffer's device current before the buffer is let go (the destroy functions' DeviceScope), and no object of
-// static storage holds one: at process exit the HIP runtime may already be gone.
-template <class T> class DeviceBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-public:
-    DeviceBuf() = default;
-    DeviceBuf(DeviceBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DeviceBuf &operator=(DeviceBuf &&o) noexcept
-    {
-        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~DeviceBuf() { reset(); }
-    void reset()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // exactly `bytes`, in place of what was held; empty on an error
-    hipError_t alloc(size_t bytes)
-    {
-        reset();
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes; else p = nullptr;
-        return e;
-    }
-    // a grow-only workspace: at least `bytes` afterwards (its contents are not kept), or empty on an error
-    hipError_t reserve(size_t bytes) { return cap >= bytes ? hipSuccess : alloc(bytes); }
-    T *get() const { return p; }
-    operator T *() const { return p; }
-    size_t bytes() const { return cap; }
-};
-
-// a new buffer holding a copy of the host's object
-template <class T> hipError_t upload(DeviceBuf<T> &buf, const T &host)
-{
-    const hipError_t e = buf.alloc(sizeof(T));
-    return e == hipSuccess ? hipMemcpy(buf, &host, sizeof(T), hipMemcpyHostToDevice) : e;
-}
 }
 
 // ---- window scans of long recordings (capi_consumers.cpp: stop / speaker; capi_scrubjay.cpp: SVM) ----------------------------------------------

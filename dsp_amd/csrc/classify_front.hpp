@@ -1,6 +1,8 @@
 // classify_front.hpp -- the batch front end of both donut classifiers (capi_classify_f32.cpp: sync/lib/classifier.cpp in float,
 // capi_classify_f64.cpp: donut-classifier/classifier.c in double): argument checks, the device an entry runs on, the per-device
-// workspaces and their lock / event policy, the sub-batch loops of the uniform entries and the whole ragged path.
+// workspaces and their lock / event policy, the sub-batch loops of the uniform entries and the whole ragged path.  The two host
+// entries make their checks, describe the batch by a layout (host_chunks.hpp) and hand it with their pass to host::Session
+// (host_pipe.hpp), which plans, stages and copies; the number of devices (kMaxDevices) is capi_util.hpp's.
 // A precision supplies a workspace type W (derived from front::Work) that carries its kernels:
 //     Config, Trace                   the public config and trace record types
 //     default_config(), valid(cfg)    the reference's thresholds, and whether a config is usable
@@ -31,7 +33,6 @@
 namespace dsp {
 namespace front {
 
-constexpr int kMaxDevices = 64;
 // 957 columns = 13.4 s: a midpoint needs a cluster of >= 12 columns (0.15 s at 14 ms per column) followed by a gap of >= 4
 // (0.05 s), so 64 * 15 - 3 columns cannot hold more than the kMaxMidpoints = 64 a trace record has room for
 constexpr int kMaxColumns = 957;
@@ -208,49 +209,41 @@ template <class W> int host_entry(const typename W::Config *cfgp, const void *si
     W &w = workspaces<W>()[device];
     std::lock_guard<std::mutex> lock(w.mu);                                     // (the workspace's lock, then the pipeline's)
     if ((rc = open(w, device)) < 0) return rc;
-    host::Session hs(device);
     const int pl = W::pipeline(in, false);
     const size_t bps = (size_t)sample_bytes<W>(in);
     const size_t row = (((size_t)n * bps + 15) & ~(size_t)15) / bps;            // staged rows start on 16 bytes
-    const long sub = W::sub_batch(pl);
+    host::UniformLayout l{n_clips, (size_t)stride * bps, row * bps, (size_t)n * bps, true};
     // (a chunk is a pass: at least cfg.classify_min_clips clips, at most the workspace's sub-batch)
-    const size_t extent = ((size_t)(n_clips - 1) * (size_t)stride + (size_t)n) * bps;
-    const long chunk_bytes = std::max(hs.pipe.chunk_bytes_for(signal, extent), hs.pipe.cfg.classify_min_clips * (long)(row * bps));
-    std::vector<long> first;
-    host::plan_uniform(n_clips, (long)(row * bps), chunk_bytes, first, sub);
-    if ((rc = hs.open(device, (long)first.size() - 1)) < 0) return rc;
-    if ((rc = w.reserve(pl, first[1], n)) < 0) return rc;
+    host::Session hs;
+    if ((rc = hs.open(device, signal, l, {(long)(row * bps), W::sub_batch(pl)})) < 0) return rc;
+    if ((rc = w.reserve(pl, l.first[1], n)) < 0) return rc;
     w.wait_idle();
-    host::Job job;
-    job.n_chunks = (long)first.size() - 1;
     BusyMark mark{w, nullptr};                                                  // (the kernels of every chunk run on the null stream)
-    const bool one = job.n_chunks == 1;
-    if (one) { job.resident[0] = w.labels; job.resident[1] = w.trace; }
-    job.in_base = signal;
-    job.in_extent = extent;
-    job.out_base[0] = labels;
-    job.out_extent[0] = (size_t)n_clips * sizeof(int);
-    job.out_base[1] = trace;
-    job.out_extent[1] = trace ? (size_t)n_clips * sizeof(*trace) : 0;
-    const auto chunk = [&](long k, host::InCopy &ic, host::OutCopy &oc) {
-        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
-        ic.src = static_cast<const unsigned char *>(signal) + (size_t)c0 * (size_t)stride * bps;
-        ic.src_pitch = (size_t)stride * bps; ic.dst_pitch = row * bps; ic.width = (size_t)n * bps; ic.rows = (size_t)cnt; ic.pitched = true;
-        oc.dst[0] = labels + c0;
-        oc.bytes[0] = (size_t)cnt * sizeof(int);
-        if (trace) { oc.dst[1] = trace + c0; oc.bytes[1] = (size_t)cnt * sizeof(*trace); }
-    };
-    const auto kernels = [&](long k, const void *d_x, void *d_out, hipStream_t st) {
-        const long cnt = first[(size_t)k + 1] - first[(size_t)k];
-        host::OutCopy oc;
-        oc.bytes[0] = (size_t)cnt * sizeof(int);
+    const bool one = hs.n_chunks(l) == 1;
+    host::Outs outs{{labels, trace}, {sizeof(int), sizeof(*trace)}};
+    if (one) { outs.resident[0] = w.labels; outs.resident[1] = w.trace; }
+    return hs.run(signal, l, outs, [&](long k, const void *d_x, void *const *d_out, hipStream_t st) {
+        const long cnt = (long)l.rows(k);
         const int r = w.run(pl, cfg, d_x, in, cnt, n, (long)row, trace != nullptr, st, nullptr, 0);
-        if (r < 0 || one) return r;               // (one chunk: the results go home from the workspace, job.resident)
-        DSP_CAPI_HIP(hipMemcpyAsync(d_out, w.labels, oc.bytes[0], hipMemcpyDeviceToDevice, st));
-        if (trace) DSP_CAPI_HIP(hipMemcpyAsync(static_cast<char *>(d_out) + oc.at(1), w.trace, (size_t)cnt * sizeof(*trace), hipMemcpyDeviceToDevice, st));
+        if (r < 0 || one) return r;               // (one chunk: the results go home from the workspace, outs.resident)
+        DSP_CAPI_HIP(hipMemcpyAsync(d_out[0], w.labels, (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, st));
+        if (trace) DSP_CAPI_HIP(hipMemcpyAsync(d_out[1], w.trace, (size_t)cnt * sizeof(*trace), hipMemcpyDeviceToDevice, st));
         return (int)DSP_OK;
-    };
-    return hs.pipe.run(job, chunk, kernels);
+    });
+}
+
+// every clip of a ragged batch, device and host form alike: its length is one (ragged_clip_length) and it has room in a trace record;
+// n_max: the longest clip's samples
+inline int check_ragged_clips(const long *offsets, long n_clips, int &n_max)
+{
+    n_max = 0;
+    for (long c = 0; c < n_clips; ++c) {
+        const long n = ragged_clip_length(offsets, c);
+        if (n < 0) return (int)n;
+        if (columns((int)n) > kMaxColumns) return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
+        n_max = std::max(n_max, (int)n);
+    }
+    return DSP_OK;
 }
 
 // Ragged batches (the references read one file of any length per run; their callers loop over files): the clips' spans from the
@@ -261,12 +254,7 @@ template <class W> int ragged(const typename W::Config &cfg, const void *d_signa
                               int *d_labels, typename W::Trace *d_trace, int *labels, typename W::Trace *trace, void *stream, bool locked = false)
 {
     int rc = DSP_OK, n_max = 0;
-    for (long c = 0; c < n_clips; ++c) {
-        const long n = ragged_clip_length(offsets, c);
-        if (n < 0) return (int)n;
-        if (columns((int)n) > kMaxColumns) return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
-        n_max = std::max(n_max, (int)n);
-    }
+    if ((rc = check_ragged_clips(offsets, n_clips, n_max)) < 0) return rc;
     DSP_ON_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     if (columns(n_max) == 0) {                 // no clip holds a segment: no midpoints, label 0
@@ -371,64 +359,33 @@ template <class W> int ragged_host_entry(const typename W::Config *cfgp, const v
     // chunks of whole clips (host_chunks.hpp), each one ragged device pass over its own samples with the offsets rebased: every clip gets
     // the label and trace of a one-clip call, so the cuts are invisible.  The results go home in the caller's order (the pass scatters
     // them into the pipeline's staging as it does into a device caller's arrays).
-    for (long c = 0; c < n_clips; ++c) {
-        const long n = ragged_clip_length(offsets, c);
-        if (n < 0) return (int)n;
-        if (columns((int)n) > kMaxColumns) return capi_fail(DSP_EINVAL, "clip " + std::to_string(c) + " too long (more than 957 spectrogram columns = 13.4 s at 16 kHz)");
-    }
+    int n_max = 0;
+    if ((rc = check_ragged_clips(offsets, n_clips, n_max)) < 0) return rc;
     DSP_ON_DEVICE(device);
     W &w = workspaces<W>()[device];
     std::lock_guard<std::mutex> lock(w.mu);                                     // (the workspace's lock, then the pipeline's)
-    host::Session hs(device);
     const size_t bps = (size_t)sample_bytes<W>(in);
-    const unsigned char *base = static_cast<const unsigned char *>(signal) + (size_t)(offsets[0] & ~3L) * bps;
-    const size_t extent = (size_t)(offsets[n_clips] - (offsets[0] & ~3L)) * bps;
-    // (at least the bytes of classify_min_clips clips of one second a chunk; "at least one clip" asks nothing: every chunk holds one)
-    const long min_clips = hs.pipe.cfg.classify_min_clips;
-    const long chunk_bytes = std::max(hs.pipe.chunk_bytes_for(base, extent), min_clips > 1 ? min_clips * 16000L * (long)bps : 0L);
-    std::vector<long> first, rebased;
-    host::plan_ragged(offsets, n_clips, (long)bps, chunk_bytes, first);
-    if ((rc = hs.open(device, (long)first.size() - 1)) < 0) return rc;
-    if (first.size() == 2) {
+    host::RaggedLayout l{offsets, n_clips, bps};
+    // (at least the bytes of classify_min_clips clips of one second a chunk)
+    host::Session hs;
+    if ((rc = hs.open(device, signal, l, {16000L * (long)bps, 0})) < 0) return rc;
+    std::vector<long> rebased;
+    if (hs.n_chunks(l) == 1) {
         // one chunk: the whole buffer travels once and the batch is one ragged pass that brings its results home itself, pass by pass,
         // in the caller's order -- the launches of a device call on the same samples and nothing else
         void *d_flat = nullptr;
-        if ((rc = hs.pipe.stage_whole(base, extent, d_flat)) < 0) return rc;
-        rebased.resize((size_t)n_clips + 1);
-        for (long c = 0; c <= n_clips; ++c) rebased[(size_t)c] = offsets[c] - (offsets[0] & ~3L);
+        if ((rc = hs.pipe->stage_whole(static_cast<const char *>(signal) + l.base_offset(), l.extent(), d_flat)) < 0) return rc;
+        l.rebase(0, rebased);
         rc = ragged<W>(cfg, d_flat, device, in, n_clips, rebased.data(), nullptr, nullptr, labels, trace, nullptr, true);
         (void)hipStreamSynchronize(nullptr);      // the pass's kernels read the staged buffer: they end before the lock is let go
-        hs.pipe.last.bytes_d2h = (long)((size_t)n_clips * (sizeof(int) + (trace ? sizeof(*trace) : 0)));
+        hs.pipe->last.bytes_d2h = (long)((size_t)n_clips * (sizeof(int) + (trace ? sizeof(*trace) : 0)));
         return rc;
     }
-    // a chunk's samples start at a multiple of four samples at or below its first clip: every clip keeps its alignment in staging
-    const auto start = [&](long k) { return offsets[first[(size_t)k]] & ~3L; };
-    host::Job job;
-    job.n_chunks = (long)first.size() - 1;
-    job.in_base = base;
-    job.in_extent = extent;
-    job.out_base[0] = labels;
-    job.out_extent[0] = (size_t)n_clips * sizeof(int);
-    job.out_base[1] = trace;
-    job.out_extent[1] = trace ? (size_t)n_clips * sizeof(*trace) : 0;
-    const auto chunk = [&](long k, host::InCopy &ic, host::OutCopy &oc) {
-        const long c0 = first[(size_t)k], c1 = first[(size_t)k + 1];
-        ic.src = static_cast<const unsigned char *>(signal) + (size_t)start(k) * bps;
-        ic.width = (size_t)(offsets[c1] - start(k)) * bps;
-        oc.dst[0] = labels + c0;
-        oc.bytes[0] = (size_t)(c1 - c0) * sizeof(int);
-        if (trace) { oc.dst[1] = trace + c0; oc.bytes[1] = (size_t)(c1 - c0) * sizeof(*trace); }
-    };
-    const auto kernels = [&](long k, const void *d_x, void *d_out, hipStream_t st) {
-        const long c0 = first[(size_t)k], cnt = first[(size_t)k + 1] - c0;
-        rebased.resize((size_t)cnt + 1);
-        for (long c = 0; c <= cnt; ++c) rebased[(size_t)c] = offsets[c0 + c] - start(k);
-        host::OutCopy oc;
-        oc.bytes[0] = (size_t)cnt * sizeof(int);
-        typename W::Trace *d_trace = trace ? reinterpret_cast<typename W::Trace *>(static_cast<char *>(d_out) + oc.at(1)) : nullptr;
-        return ragged<W>(cfg, d_x, device, in, cnt, rebased.data(), static_cast<int *>(d_out), d_trace, nullptr, nullptr, st, true);
-    };
-    return hs.pipe.run(job, chunk, kernels);
+    return hs.run(signal, l, host::Outs{{labels, trace}, {sizeof(int), sizeof(*trace)}}, [&](long k, const void *d_x, void *const *d_out, hipStream_t st) {
+        l.rebase(k, rebased);
+        return ragged<W>(cfg, d_x, device, in, (long)rebased.size() - 1, rebased.data(), static_cast<int *>(d_out[0]),
+                         trace ? static_cast<typename W::Trace *>(d_out[1]) : nullptr, nullptr, nullptr, st, true);
+    });
 }
 
 }  // namespace front

@@ -31,6 +31,12 @@
 // into the slot's pinned buffer and by memcpy after out_done.  The entries stay blocking: when run() returns every output byte is in
 // the caller's memory and nothing is in flight; after a failure everything is drained as well, every slot is free, and the next
 // call finds the pipeline usable.  Device staging is bounded by depth x the largest chunk, never by the batch (of pinned memory).
+//
+// WHERE THINGS LIVE.  The arithmetic of a batch -- its plan, its extent, where chunk k lies -- is a layout of host_chunks.hpp (HIP-free).
+// An entry makes its checks, takes its own lock, describes its batch by a layout and its result arrays by an Outs, and hands both
+// with its `kernels` callable to a Session (the foot of this file): open() checks the device, locks the pipeline, plans the chunks
+// and opens the pipeline; run() builds the Job and every chunk's InCopy / OutCopy.  No entry fills one itself.  The slots' buffers are
+// DeviceBuf / PinnedBuf (capi_util.hpp) of exactly the bytes asked for; release() lets them go, the pipelines being immortal.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -46,7 +52,7 @@
 namespace dsp {
 namespace host {
 
-constexpr int kMaxDevices = 64, kMaxDepth = 4;
+constexpr int kMaxDepth = 4;
 // From tools/time_host.py's sweep on the target (profiles/host_stream_sweep.jsonl).  Far above any test batch, so that the
 // small host calls of the suite -- and compute_mfcc() / classify() -- are one chunk.
 constexpr long kDefaultChunkBytes = 64L << 20;
@@ -66,7 +72,7 @@ struct InCopy {
     // rows of clips (a single chunk is then copied by the runtime's 2-D copy even where the pitches agree: from pageable memory it
     // measured 1.5 % faster than the 1-D copy of the same bytes, and it is the copy these entries have always made)
     bool pitched = false;
-    size_t staged_bytes() const { return rows > 1 ? dst_pitch * (rows - 1) + width : width; }
+    size_t staged_bytes() const { return host::staged_bytes(rows, dst_pitch, width); }
 };
 // up to two result arrays per chunk (a classifier's labels and trace), back to back in the staging buffer at 256-byte boundaries
 struct OutCopy {
@@ -78,8 +84,8 @@ struct OutCopy {
 
 // A batch: its chunk count, the caller's arrays and their extents (for the choice of the paths), and -- for a batch of ONE chunk whose
 // kernels leave their results in a workspace of the entry's -- where those lie on the device (else they are written to d_out).
-// The entry hands run() two callables beside it: chunk(k, InCopy &, OutCopy &), the copies of chunk k, and
-// kernels(k, d_in, d_out, stream) -> int, which enqueues the chunk's kernels.
+// Pipe::run() takes two callables beside it: chunk(k, InCopy &, OutCopy &), the copies of chunk k (Session::run makes it), and the
+// entry's kernels(k, d_in, d_out, stream) -> int: d_in the staged input, d_out[i] where result array i is to be left (OutCopy::at).
 struct Job {
     long n_chunks = 0;
     const void *in_base = nullptr;
@@ -89,7 +95,7 @@ struct Job {
     const void *resident[2] = {nullptr, nullptr};
 };
 
-// whether [p, p + bytes) is host memory the runtime knows (hipHostMalloc'ed or registered): what a copy engine reads without a bounce.
+// whether [p, p + bytes) is host memory the runtime knows (page-locked by its allocator, or registered): what a copy engine reads without a bounce.
 // Both ends are asked.  (An array whose ends are registered and whose middle is not is copied correctly all the same -- the runtime
 // bounces what it does not know -- only not asynchronously.)
 inline bool pinned_range(const void *p, size_t bytes)
@@ -114,8 +120,8 @@ struct Pipe {
     hipStream_t s_in = nullptr;                        // the copies in of a batch of several chunks; everything else runs on the null stream
     bool events = false;                               // every slot has its two events
     struct Slot {
-        void *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;
-        size_t h_in_cap = 0, d_in_cap = 0, h_out_cap = 0, d_out_cap = 0;
+        PinnedBuf h_in, h_out;                         // grow-only, to exactly the bytes of the largest chunk seen
+        DeviceBuf<char> d_in, d_out;
         hipEvent_t in_done = nullptr, out_done = nullptr;
         bool pending = false;                          // a chunk's results are on their way: out_done has to fire before anything else
         OutCopy out;                                   // of that chunk, for the memcpy home
@@ -123,18 +129,8 @@ struct Pipe {
     } slots[kMaxDepth];
     dsp_host_stats last{};
 
-    size_t staging_bytes() const
-    {
-        size_t b = 0;
-        for (const Slot &s : slots) b += s.d_in_cap + s.d_out_cap;
-        return b;
-    }
-    size_t pinned_bytes() const
-    {
-        size_t b = 0;
-        for (const Slot &s : slots) b += s.h_in_cap + s.h_out_cap;
-        return b;
-    }
+    size_t staging_bytes() const { size_t b = 0; for (const Slot &s : slots) b += s.d_in.bytes() + s.d_out.bytes(); return b; }
+    size_t pinned_bytes() const { size_t b = 0; for (const Slot &s : slots) b += s.h_in.bytes() + s.h_out.bytes(); return b; }
 
     // The input bytes a chunk of this call may hold: cfg.chunk_bytes -- but a batch in PAGEABLE memory is not cut under
     // DSP_HOST_PAGEABLE_WHOLE (the default: measured, cutting it does not pay).  A batch that fits a chunk is not asked about.
@@ -174,13 +170,9 @@ struct Pipe {
     {
         drain();
         for (Slot &s : slots) {
-            if (s.h_in) (void)hipHostFree(s.h_in);
-            if (s.h_out) (void)hipHostFree(s.h_out);
-            if (s.d_in) (void)hipFree(s.d_in);
-            if (s.d_out) (void)hipFree(s.d_out);
             if (s.in_done) (void)hipEventDestroy(s.in_done);
             if (s.out_done) (void)hipEventDestroy(s.out_done);
-            s = Slot{};
+            s = Slot{};                                // (lets the four buffers go)
         }
         if (s_in) (void)hipStreamDestroy(s_in);
         s_in = nullptr;
@@ -198,7 +190,7 @@ struct Pipe {
         last.n_chunks = last.depth = 1;
         last.input_path = last.output_path = DSP_HOST_PATH_DIRECT;
         Slot &s = slots[0];
-        if (const int rc = grow_device(s.d_in, s.d_in_cap, bytes + 256)) return rc;
+        DSP_CAPI_HIP(s.d_in.reserve(bytes + 256));
         if (bytes) DSP_CAPI_HIP(hipMemcpyAsync(s.d_in, src, bytes, hipMemcpyHostToDevice, nullptr));
         last.bytes_h2d = (long)bytes;
         last.peak_staging_bytes = (long)staging_bytes();
@@ -208,24 +200,6 @@ struct Pipe {
     }
 
 private:
-    static int grow_pinned(void *&p, size_t &cap, size_t bytes)
-    {
-        if (cap >= bytes) return DSP_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        DSP_CAPI_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-        cap = bytes;
-        return DSP_OK;
-    }
-    static int grow_device(void *&p, size_t &cap, size_t bytes)
-    {
-        if (cap >= bytes) return DSP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        DSP_CAPI_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return DSP_OK;
-    }
     // the chunk that had the slot: wait for its results, take them home
     static int retire(Slot &s)
     {
@@ -257,17 +231,18 @@ template <class Chunk, class Kernels> int Pipe::run_one(const Job &job, const Ch
     OutCopy oc;
     chunk(0, ic, oc);
     int rc;
-    if ((rc = grow_device(s.d_in, s.d_in_cap, ic.staged_bytes() + 256)) < 0) return rc;
-    if ((rc = grow_device(s.d_out, s.d_out_cap, oc.staged_bytes())) < 0) return rc;
+    DSP_CAPI_HIP(s.d_in.reserve(ic.staged_bytes() + 256));
+    DSP_CAPI_HIP(s.d_out.reserve(oc.staged_bytes()));
+    void *const d_out[2] = {s.d_out.get(), s.d_out.get() + oc.at(1)};
     if (ic.staged_bytes() == 0) {
     } else if (ic.pitched) {
         DSP_CAPI_HIP(hipMemcpy2DAsync(s.d_in, ic.dst_pitch, ic.src, ic.src_pitch, ic.width, ic.rows, hipMemcpyHostToDevice, nullptr));
     } else DSP_CAPI_HIP(hipMemcpyAsync(s.d_in, ic.src, ic.staged_bytes(), hipMemcpyHostToDevice, nullptr));
     last.bytes_h2d = (long)(ic.width * ic.rows);
-    if ((rc = kernels(0, s.d_in, s.d_out, nullptr)) < 0) return rc;
+    if ((rc = kernels(0, s.d_in.get(), d_out, nullptr)) < 0) return rc;
     for (int i = 0; i < 2; ++i) {
         if (!oc.bytes[i]) continue;
-        const void *from = job.resident[i] ? job.resident[i] : static_cast<const char *>(s.d_out) + oc.at(i);
+        const void *from = job.resident[i] ? job.resident[i] : d_out[i];
         DSP_CAPI_HIP(hipMemcpyAsync(oc.dst[i], from, oc.bytes[i], hipMemcpyDeviceToHost, nullptr));
         last.bytes_d2h += (long)oc.bytes[i];
     }
@@ -288,11 +263,12 @@ template <class Chunk, class Kernels> int Pipe::run_chunks(const Job &job, const
         OutCopy oc;
         chunk(k, ic, oc);
         // the kernels' vector loads may reach a few bytes past a row's end: slack behind the staged input, as behind a caller's buffer
-        if ((rc = grow_device(s.d_in, s.d_in_cap, ic.staged_bytes() + 256)) < 0) return rc;
-        if ((rc = grow_device(s.d_out, s.d_out_cap, oc.staged_bytes())) < 0) return rc;
+        DSP_CAPI_HIP(s.d_in.reserve(ic.staged_bytes() + 256));
+        DSP_CAPI_HIP(s.d_out.reserve(oc.staged_bytes()));
+        void *const d_out[2] = {s.d_out.get(), s.d_out.get() + oc.at(1)};
         if (ic.staged_bytes() == 0) {      // (a chunk of empty clips: nothing travels in)
         } else if (in_staged) {
-            if ((rc = grow_pinned(s.h_in, s.h_in_cap, ic.staged_bytes())) < 0) return rc;
+            DSP_CAPI_HIP(s.h_in.reserve(ic.staged_bytes()));
             if (ic.rows > 1 && ic.src_pitch != ic.dst_pitch) {
                 for (size_t r = 0; r < ic.rows; ++r)
                     std::memcpy(static_cast<char *>(s.h_in) + r * ic.dst_pitch, static_cast<const char *>(ic.src) + r * ic.src_pitch, ic.width);
@@ -304,12 +280,12 @@ template <class Chunk, class Kernels> int Pipe::run_chunks(const Job &job, const
         last.bytes_h2d += (long)(ic.width * ic.rows);
         DSP_CAPI_HIP(hipEventRecord(s.in_done, s_in));
         DSP_CAPI_HIP(hipStreamWaitEvent(nullptr, s.in_done, 0));
-        if ((rc = kernels(k, s.d_in, s.d_out, nullptr)) < 0) return rc;
-        if (out_staged && (rc = grow_pinned(s.h_out, s.h_out_cap, oc.staged_bytes())) < 0) return rc;
+        if ((rc = kernels(k, s.d_in.get(), d_out, nullptr)) < 0) return rc;
+        if (out_staged) DSP_CAPI_HIP(s.h_out.reserve(oc.staged_bytes()));
         for (int i = 0; i < 2; ++i) {
             if (!oc.bytes[i]) continue;
-            void *to = out_staged ? static_cast<char *>(s.h_out) + oc.at(i) : oc.dst[i];
-            DSP_CAPI_HIP(hipMemcpyAsync(to, static_cast<const char *>(s.d_out) + oc.at(i), oc.bytes[i], hipMemcpyDeviceToHost, nullptr));
+            void *to = out_staged ? s.h_out.get() + oc.at(i) : oc.dst[i];
+            DSP_CAPI_HIP(hipMemcpyAsync(to, d_out[i], oc.bytes[i], hipMemcpyDeviceToHost, nullptr));
             last.bytes_d2h += (long)oc.bytes[i];
         }
         DSP_CAPI_HIP(hipEventRecord(s.out_done, nullptr));
@@ -380,14 +356,63 @@ template <class Chunk, class Kernels> int Pipe::run(const Job &job, const Chunk 
     return rc;
 }
 
-// The pipeline of `device` (below kMaxDevices: the entry has checked), locked: what an entry holds for the duration of its call.  The
-// entry has taken its own lock and made the device current before; it plans its chunks (pipe.cfg, pipe.chunk_bytes_for), then opens
-// the pipeline for that many.
+// An entry's result arrays (one or two; base[1] NULL: one): array i holds unit[i] bytes per unit.  Chunk k owns the units
+// [prefix[first[k]], prefix[first[k + 1]]) of each -- prefix NULL: its items themselves, one unit an item (ragged MFCC: a unit is a row,
+// prefix the clips' frame offsets, from 0).  resident: Job::resident.
+struct Outs {
+    void *base[2] = {nullptr, nullptr};
+    size_t unit[2] = {0, 0};
+    const long *prefix = nullptr;
+    const void *resident[2] = {nullptr, nullptr};
+};
+
+// A classifier's chunk is one pass through its workspace: at least the pipeline's classify_min_clips items, counted as min_item_bytes
+// each (0: no floor; "at least one" asks nothing, every chunk holds an item), at most max_items (0: no cap)
+struct ChunkLimits { long min_item_bytes = 0, max_items = 0; };
+
+// The one driver of the *_host entries: the device's pipeline, locked, for the duration of a call.  The entry holds its own lock and
+// has made the device current; `in` is the caller's pointer the layout counts from.
 struct Session {
-    Pipe &pipe;
+    Pipe *pipe = nullptr;
     std::unique_lock<std::mutex> lock;
-    explicit Session(int device) : pipe(pipes()[device]), lock(pipe.mu) {}
-    int open(int device, long n_chunks) { return pipe.open(device, n_chunks); }
+
+    // locks the pipeline of `device`, plans the layout's chunks (l.first) and opens the pipeline for that many
+    template <class Layout> int open(int device, const void *in, Layout &l, ChunkLimits lim = {})
+    {
+        if (device < 0 || device >= kMaxDevices) return capi_fail(DSP_EINVAL, "device index out of range");
+        pipe = &pipes()[device];
+        lock = std::unique_lock<std::mutex>(pipe->mu);
+        const long min_items = pipe->cfg.classify_min_clips;
+        const long floor = lim.min_item_bytes > 0 && min_items > 1 ? min_items * lim.min_item_bytes : 0;
+        l.plan(std::max(pipe->chunk_bytes_for(static_cast<const char *>(in) + l.base_offset(), l.extent()), floor), lim.max_items);
+        return pipe->open(device, n_chunks(l));
+    }
+    template <class Layout> static long n_chunks(const Layout &l) { return (long)l.first.size() - 1; }
+
+    // every chunk of the batch through the pipeline, kernels(k, d_in, d_out, stream) enqueueing those of chunk k
+    template <class Layout, class Kernels> int run(const void *in, const Layout &l, const Outs &o, const Kernels &kernels)
+    {
+        const auto unit = [&](long item) { return (size_t)(o.prefix ? o.prefix[item] : item); };
+        Job job;
+        job.n_chunks = n_chunks(l);
+        job.in_base = static_cast<const char *>(in) + l.base_offset();
+        job.in_extent = l.extent();
+        for (int i = 0; i < 2; ++i) {
+            job.out_base[i] = o.base[i];
+            job.out_extent[i] = o.base[i] ? unit(l.first.back()) * o.unit[i] : 0;
+            job.resident[i] = o.resident[i];
+        }
+        const auto chunk = [&](long k, InCopy &ic, OutCopy &oc) {
+            ic.src = static_cast<const char *>(in) + l.src_offset(k);
+            ic.src_pitch = l.src_pitch; ic.dst_pitch = l.dst_pitch; ic.width = l.chunk_width(k); ic.rows = l.rows(k); ic.pitched = l.pitched;
+            const size_t u0 = unit(l.first[(size_t)k]), u1 = unit(l.first[(size_t)k + 1]);
+            for (int i = 0; i < 2 && o.base[i]; ++i) {
+                oc.dst[i] = static_cast<char *>(o.base[i]) + u0 * o.unit[i];
+                oc.bytes[i] = (u1 - u0) * o.unit[i];
+            }
+        };
+        return pipe->run(job, chunk, kernels);
+    }
 };
 
 }  // namespace host

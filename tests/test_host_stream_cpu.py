@@ -149,7 +149,8 @@ def test_wrappers_take_numpy_arrays_and_cpu_tensors_without_a_copy():
 
 
 SANITIZED_MAIN = r"""
-// host_chunks.hpp on its own: the planner's properties over seeded batches, for the sanitizers to watch
+// host_chunks.hpp on its own: the planner's and the layouts' properties over seeded batches, for the sanitizers to watch.
+// Every property has an exit code of its own.
 #include <cstdio>
 #include <cstdint>
 #include <vector>
@@ -158,9 +159,52 @@ SANITIZED_MAIN = r"""
 static uint64_t state = 0x9E3779B97F4A7C15ull;
 static uint64_t next() { state ^= state << 13; state ^= state >> 7; state ^= state << 17; return state; }
 
+using namespace dsp::host;
+
+// a planned ragged layout: every chunk starts on four samples at or just below its first clip, its rebased offsets describe exactly
+// its bytes, and the chunks cover the batch with nothing but the alignment's overlap between them
+static int check_ragged(const RaggedLayout &l)
+{
+    const long *off = l.offsets, bps = (long)l.bytes_per_sample, n_chunks = (long)l.first.size() - 1;
+    std::vector<long> rebased;
+    for (long k = 0; k < n_chunks; ++k) {
+        const long c0 = l.first[(size_t)k], s = l.start(k), width = (long)l.chunk_width(k);
+        if (s % 4 != 0) return 11;
+        if (s < off[c0] - 3 || s > off[c0]) return 12;
+        l.rebase(k, rebased);
+        if ((long)rebased.size() != l.first[(size_t)k + 1] - c0 + 1) return 13;
+        for (size_t c = 0; c + 1 < rebased.size(); ++c)
+            if (rebased[c + 1] < rebased[c]) return 13;
+        if (rebased[0] < 0 || rebased[0] > 3) return 14;
+        if (rebased.back() * bps != width) return 15;
+        if ((long)l.src_offset(k) != s * bps || l.rows(k) != 1) return 18;
+        if (k + 1 < n_chunks && l.start(k + 1) * bps < s * bps + width - 3 * bps) return 17;
+        if (k + 1 < n_chunks && l.start(k + 1) * bps > s * bps + width) return 17;          // (a gap: samples lost)
+    }
+    if ((long)l.base_offset() != l.start(0) * bps || (long)l.extent() != (off[l.n_clips] - l.start(0)) * bps) return 16;
+    return 0;
+}
+
+// a planned uniform layout: the chunks' rows end where the batch ends, and staging holds them dst_pitch apart
+static int check_uniform(const UniformLayout &l)
+{
+    const long n_chunks = (long)l.first.size() - 1;
+    size_t rows = 0;
+    for (long k = 0; k < n_chunks; ++k) {
+        const size_t r = l.rows(k);
+        if (r < 1 || l.chunk_width(k) != l.width) return 23;
+        if (l.staged_bytes(k) != l.dst_pitch * (r - 1) + l.width) return 21;
+        if (r == 1 && l.staged_bytes(k) != l.width) return 22;
+        if (l.src_offset(k) != rows * l.src_pitch) return 23;
+        rows += r;
+    }
+    if (rows != (size_t)l.n_items || l.base_offset() != 0) return 23;
+    if (l.src_offset(n_chunks - 1) + (l.rows(n_chunks - 1) - 1) * l.src_pitch + l.width != l.extent()) return 20;
+    return 0;
+}
+
 int main()
 {
-    using namespace dsp::host;
     std::vector<long> first;
     long chunks = 0;
     for (int trial = 0; trial < 2000; ++trial) {
@@ -181,11 +225,52 @@ int main()
             if (bytes > chunk && with_samples != 1) return 4;
         }
         chunks += (long)first.size() - 1;
-        plan_uniform(n, 1 + (long)(next() % 200000), chunk, first, (long)(next() % 3) * 7);
+        const long item = 1 + (long)(next() % 200000), max_items = (long)(next() % 3) * 7;
+        plan_uniform(n, item, chunk, first, max_items);
         if (first.front() != 0 || first.back() != n) return 5;
         for (size_t k = 0; k + 1 < first.size(); ++k)
             if (first[k + 1] <= first[k]) return 6;
         chunks += (long)first.size() - 1;
+        if (n == 0) continue;                  // (a layout is a batch with at least one item: the entries return before they make one)
+        // the layouts over the same batches: the same plans, and the bytes they place
+        RaggedLayout rl;
+        rl.offsets = off.data(); rl.n_clips = n; rl.bytes_per_sample = (size_t)bps;
+        if (rl.base_offset() % (4 * (size_t)bps) != 0 || (long)rl.base_offset() > off[0] * bps) return 10;      // (asked before there is a plan)
+        rl.plan(chunk);
+        std::vector<long> again;
+        plan_ragged(off.data(), n, bps, chunk, again);
+        if (rl.first != again) return 10;
+        if (const int rc = check_ragged(rl)) return rc;
+        UniformLayout ul;
+        ul.n_items = n; ul.dst_pitch = (size_t)item; ul.src_pitch = (size_t)item + (size_t)(next() % 64); ul.width = 1 + (size_t)(next() % (unsigned long)item);
+        ul.plan(chunk, max_items);
+        if (ul.first != first) return 19;
+        if (const int rc = check_uniform(ul)) return rc;
+    }
+    {   // a single row is `width` bytes, whatever the pitches
+        UniformLayout one;
+        one.n_items = 1; one.src_pitch = 64000; one.dst_pitch = 64016; one.width = 63998;
+        one.plan(kMinChunkBytes);
+        if (one.first.size() != 2 || one.staged_bytes(0) != 63998 || one.extent() != 63998) return 22;
+        if (const int rc = check_uniform(one)) return rc;
+    }
+    {   // far offsets and long clips: offsets[0] near 2^40, and one clip of 2^31 - 1 samples of 8 bytes (no sum may overflow)
+        const long far[4] = {(1L << 40) + 3, (1L << 40) + 1003, (1L << 40) + 1003, (1L << 40) + 9002};
+        RaggedLayout l;
+        l.offsets = far; l.n_clips = 3; l.bytes_per_sample = 8;
+        l.plan(kMinChunkBytes);
+        if (l.first.size() != 3 || l.base_offset() != (size_t)8 << 40 || l.extent() != 9002 * 8) return 24;
+        if (const int rc = check_ragged(l)) return rc;
+        const long longest[2] = {5, 5 + (long)INT32_MAX};
+        l.offsets = longest; l.n_clips = 1;
+        l.plan(kMinChunkBytes);
+        if (l.first.size() != 2 || l.chunk_width(0) != ((size_t)INT32_MAX + 1) * 8 || l.base_offset() != 32) return 25;
+        if (const int rc = check_ragged(l)) return rc;
+        UniformLayout u;                       // 2^31 clips of 64 000 bytes in one chunk
+        u.n_items = 1L << 31; u.src_pitch = 64000; u.dst_pitch = 64016; u.width = 64000;
+        u.plan(INT64_MAX / 4);
+        if (u.first.size() != 2 || u.extent() != (((size_t)1 << 31) - 1) * 64000 + 64000) return 26;
+        if (const int rc = check_uniform(u)) return rc;
     }
     // the extremes: sizes near LONG_MAX must not overflow the running sum
     const long huge[4] = {0, INT64_MAX / 8, INT64_MAX / 8 + 5, INT64_MAX / 4};
