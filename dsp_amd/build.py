@@ -10,7 +10,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.environ.get("DSP_AMD_LIB") or os.path.join(PKG, "libdsp_amd.so")
 SOURCES = ["capi.cpp", "capi_scrubjay.cpp", "capi_consumers.cpp", "capi_stream.cpp", "capi_classifier_cxx.cpp", "capi_classify_f32.cpp", "capi_classify_f64.cpp", "capi_gather.cpp", "capi_resample.cpp", "capi_enroll.cpp", "capi_ubm.cpp", "capi_verify.cpp", "capi_segments.cpp", "capi_trials.cpp", "capi_calibrate.cpp", "capi_snorm.cpp", "capi_vad.cpp", "capi_svmtrain.cpp", "capi_stoptrain.cpp", "capi_augment.cpp", "capi_host.cpp", "classify_f64_kernels.hip", "classify_f64_ckpt_kernels.hip", "tables.cpp", "mfcc_kernels.hip", "mfcc1024_kernel.hip", "mfcc1024_wave_kernel.hip", "mfcc2048_kernel.hip", "mfcc400_kernel.hip", "classify_kernels.hip",
            "svm_kernels.hip", "consumer_kernels.hip", "stream_kernels.hip", "resample_kernels.hip", "enroll_kernels.hip", "ubm_kernels.hip", "kmeans_kernels.hip", "verify_kernels.hip", "segment_kernels.hip", "trial_kernels.hip", "calibrate_kernels.hip", "snorm_kernels.hip", "vad_kernels.hip", "svmtrain_kernels.hip", "stoptrain_kernels.hip", "augment_kernels.hip"]
-HEADERS = ["exports.map", "tables.hpp", "clip_span.hpp", "mfcc_kernels.hpp", "mfcc_device.hpp", "classify_kernels.hpp", "svm_kernels.hpp", "classify_f64_device.hpp", "diag_guard.hpp", "consumer_kernels.hpp", "scan_device.hpp", "stream_kernels.hpp", "capi_util.hpp", "mfcc_plan.hpp", "classify_front.hpp", "resample_kernels.hpp", "stream_resample.hpp", "enroll_kernels.hpp", "ubm_kernels.hpp", "kmeans_kernels.hpp", "verify_kernels.hpp", "score_matrix.hpp", "segment_kernels.hpp", "trial_kernels.hpp", "calibrate_kernels.hpp", "snorm_kernels.hpp", "vad_kernels.hpp", "svmtrain_kernels.hpp", "stoptrain_kernels.hpp", "augment_kernels.hpp", "gmm_model.hpp", "gmm_estep.hpp", "gmm_stats.hpp", "stream_load.hpp", "host_pipe.hpp", "host_chunks.hpp",
+HEADERS = ["exports.map", "tables.hpp", "clip_span.hpp", "mfcc_kernels.hpp", "mfcc_device.hpp", "classify_kernels.hpp", "svm_kernels.hpp", "classify_f64_device.hpp", "diag_guard.hpp", "consumer_kernels.hpp", "scan_device.hpp", "stream_kernels.hpp", "capi_util.hpp", "mfcc_plan.hpp", "classify_front.hpp", "resample_kernels.hpp", "stream_resample.hpp", "enroll_kernels.hpp", "ubm_kernels.hpp", "kmeans_kernels.hpp", "verify_kernels.hpp", "score_matrix.hpp", "segment_kernels.hpp", "trial_kernels.hpp", "calibrate_kernels.hpp", "snorm_kernels.hpp", "vad_kernels.hpp", "svmtrain_kernels.hpp", "stoptrain_kernels.hpp", "augment_kernels.hpp", "gmm_model.hpp", "gmm_estep.hpp", "gmm_stats.hpp", "stream_load.hpp", "host_pipe.hpp", "host_chunks.hpp", "span_find.hpp",
            os.path.join("..", "..", "include", "dsp_amd.h"), os.path.join("..", "..", "include", "dsp_amd_classifier.h")]
 
 

@@ -125,6 +125,7 @@ __device__ __forceinline__ void fft1024_wave(c32 (&v)[16], float2 *zbuf, const f
 }
 
 // the entry of a span table whose rows / tiles hold `g`: the largest c with first(c) <= g (entry n is the sentinel with the total)
+// (span_find.hpp's owner_of finds the same entry in long; this int form stays because joining it changes the kernels' instructions, which nobody has timed)
 template <class First>
 __device__ __forceinline__ int span_of(long g, int n, First first)
 {

@@ -250,11 +250,10 @@ int dsp_mfcc_lane_tables(const dsp_mfcc_config *cfg, void *out, int size)
     if (!out) return (int)sizeof(dsp::LaneTables512);
     if (size != (int)sizeof(dsp::LaneTables512)) return capi_fail(DSP_EINVAL, "size != sizeof(LaneTables512)");
     std::string why;
-    auto *t = new dsp::LaneTables512;
-    const bool ok = valid_cfg(*cfg, why) && dsp::build_lane_tables_512(*cfg, *t, why);
-    if (ok) std::memcpy(out, t, sizeof(*t));
-    delete t;
-    return ok ? DSP_OK : capi_fail(DSP_EINVAL, why);
+    auto t = std::make_unique<dsp::LaneTables512>();
+    if (!valid_cfg(*cfg, why) || !dsp::build_lane_tables_512(*cfg, *t, why)) return capi_fail(DSP_EINVAL, why);
+    std::memcpy(out, t.get(), sizeof(*t));
+    return DSP_OK;
 }
 
 int dsp_mfcc400_tables(const dsp_mfcc_config *cfg, void *out, int size)
@@ -353,8 +352,7 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
     *out = nullptr;
     std::string why;
     if (!valid_cfg(*cfg, why)) return capi_fail(DSP_EINVAL, why);
-    auto host_side = std::make_unique<dsp_mfcc_plan>();
-    host_side->cfg = *cfg;
+    auto lane = std::make_unique<dsp::LaneTables512>();      // (zeros for the other transform lengths, as the plan's own always were)
     std::unique_ptr<dsp::GenTables1024> gen;
     std::unique_ptr<dsp::GenTables2048> g2k;
     std::unique_ptr<dsp::Tables400> t400;
@@ -368,53 +366,45 @@ int dsp_mfcc_plan_create(const dsp_mfcc_config *cfg, int device, dsp_mfcc_plan *
         gen = std::make_unique<dsp::GenTables1024>();
         if (!dsp::build_gen_tables_1024(*cfg, *gen, why)) return capi_fail(DSP_EINVAL, why);
     } else if (cfg->n_fft != 512) return capi_fail(DSP_EINVAL, "internal: no tables for this n_fft");
-    else if (!dsp::build_lane_tables_512(*cfg, host_side->host, why)) return capi_fail(DSP_EINVAL, why);
+    else if (!dsp::build_lane_tables_512(*cfg, *lane, why)) return capi_fail(DSP_EINVAL, why);
     if (const int rc = dsp::check_device(device)) return rc;
-    dsp::DeviceScope dsp_device_scope_(device);      // the caller's current device is put back on return
-    // the plan gets device buffers from here on: its owner is declared after the scope, so that every exit below lets them go
-    // while the plan's device is current
-    std::unique_ptr<dsp_mfcc_plan> p = std::move(host_side);
-    p->device = device;
-    hipError_t e = dsp_device_scope_.err;
-    hipDeviceProp_t prop;
-    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = dsp::upload(p->d_tables, p->host);
-    if (e == hipSuccess && gen) e = dsp::upload(p->d_gen_tables, *gen);
-    if (e == hipSuccess && g2k) e = dsp::upload(p->d_tables2048, *g2k);
-    if (e == hipSuccess && t400) e = dsp::upload(p->d_tables400, *t400);
-    p->wave1024_fits = gen && gen->n_chunk_slots <= 3;
-    if (e == hipSuccess && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->wave1024_fits) {
-        // BASELINE config 3 in ONE pass: the per-frame Butterworth as a scan inside the MFCC kernel (tables.hpp PrefilterScan)
-        double b[9], a[9];
-        dsp_butter_bandpass(cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
-                            cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, b, a);
-        dsp::PrefilterScan sc;
-        if (!dsp::build_prefilter_scan(b, a, sc, why)) return capi_fail(DSP_EINVAL, why);
-        if (sc.c_ok && sc.c_row_ok) {      // the kernel runs the cascade form (its scan in row form); coefficients without it (none of the two literal sets) take the two-pass path
-            e = dsp::upload(p->d_scan, sc);
-            for (int k = 0; k < 4; ++k) p->scan_steps[k] = sc.c_steps[k];
+    return dsp::create_on_device(device, out, [&](dsp_mfcc_plan &plan) -> int {
+        dsp_mfcc_plan *const p = &plan;
+        p->cfg = *cfg;
+        p->host = *lane;
+        hipDeviceProp_t prop;
+        hipError_t e = hipGetDeviceProperties(&prop, device);
+        if (e == hipSuccess) e = dsp::upload(p->d_tables, p->host);
+        if (e == hipSuccess && gen) e = dsp::upload(p->d_gen_tables, *gen);
+        if (e == hipSuccess && g2k) e = dsp::upload(p->d_tables2048, *g2k);
+        if (e == hipSuccess && t400) e = dsp::upload(p->d_tables400, *t400);
+        p->wave1024_fits = gen && gen->n_chunk_slots <= 3;
+        if (e == hipSuccess && cfg->prefilter != DSP_PREFILTER_NONE && cfg->frame_length == 1024 && p->wave1024_fits) {
+            // BASELINE config 3 in ONE pass: the per-frame Butterworth as a scan inside the MFCC kernel (tables.hpp PrefilterScan)
+            double b[9], a[9];
+            dsp_butter_bandpass(cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 1000 : 3000,
+                                cfg->prefilter == DSP_PREFILTER_BUTTER_1000_3000 ? 3000 : 7500, b, a);
+            dsp::PrefilterScan sc;
+            if (!dsp::build_prefilter_scan(b, a, sc, why)) return capi_fail(DSP_EINVAL, why);
+            if (sc.c_ok && sc.c_row_ok) {      // the kernel runs the cascade form (its scan in row form); coefficients without it (none of the two literal sets) take the two-pass path
+                e = dsp::upload(p->d_scan, sc);
+                for (int k = 0; k < 4; ++k) p->scan_steps[k] = sc.c_steps[k];
+            }
         }
-    }
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
-    p->n_cu = prop.multiProcessorCount;
-    p->run = resolve_kernel(p.get(), DSP_KERNEL_WAVE);
-    if (const char *k = std::getenv("DSP_AMD_KERNEL")) {
-        // an A/B switch, not a requirement: a value this plan's n_fft has no kernel for is reported and ignored -- an
-        // environment left over from the removed 512-point experiments must not make every plan_create fail
-        if (dsp_mfcc_plan_set_kernel(p.get(), std::atoi(k)) != DSP_OK)
-            std::fprintf(stderr, "libdsp_amd: DSP_AMD_KERNEL=%s ignored (%s); using the default kernel\n", k, dsp_last_error());
-    }
-    *out = p.release();
-    return DSP_OK;
+        if (e != hipSuccess) return capi_fail(DSP_EHIP, std::string("plan_create: ") + hipGetErrorString(e));
+        p->n_cu = prop.multiProcessorCount;
+        p->run = resolve_kernel(p, DSP_KERNEL_WAVE);
+        if (const char *k = std::getenv("DSP_AMD_KERNEL")) {
+            // an A/B switch, not a requirement: a value this plan's n_fft has no kernel for is reported and ignored -- an
+            // environment left over from the removed 512-point experiments must not make every plan_create fail
+            if (dsp_mfcc_plan_set_kernel(p, std::atoi(k)) != DSP_OK)
+                std::fprintf(stderr, "libdsp_amd: DSP_AMD_KERNEL=%s ignored (%s); using the default kernel\n", k, dsp_last_error());
+        }
+        return DSP_OK;
+    });
 }
 
-void dsp_mfcc_plan_destroy(dsp_mfcc_plan *p)
-{
-    if (!p) return;
-    dsp::DeviceScope dsp_device_scope_(p->device);
-    p->spans.release();
-    delete p;
-}
+void dsp_mfcc_plan_destroy(dsp_mfcc_plan *p) { dsp::destroy(p); }
 
 int dsp_mfcc_plan_config(const dsp_mfcc_plan *p, dsp_mfcc_config *cfg)
 {

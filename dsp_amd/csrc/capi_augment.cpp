@@ -82,14 +82,14 @@ long tiles_of(long samples) { return (samples + dsp::kAugTile - 1) / dsp::kAugTi
 
 }  // namespace
 
-struct dsp_augmenter {
-    int device = 0, pad_mode = DSP_PAD_REFLECT, max_term = 256;
+struct dsp_augmenter : dsp::Handle {
+    int pad_mode = DSP_PAD_REFLECT, max_term = 256;
     dsp::DeviceBuf<dsp::AugTables> tables;
     dsp::DeviceBuf<float> spec, spec_out;      // D and S of a stretch, (re, im) pairs
     dsp::DeviceBuf<float> frames;              // the inverse transform's windowed frames, [rows][2048]
     dsp::DeviceBuf<float> ws_a, ws_b;          // an augment call's stretched clips, and the pitch ops' resampled ones
     dsp::SpanRing ring;
-    std::map<std::pair<int, int>, dsp_resampler *> resamplers;      // one per (up, down)
+    std::map<std::pair<int, int>, std::unique_ptr<dsp_resampler, dsp::DestroyWith<dsp_resampler_destroy>>> resamplers;      // one per (up, down), owned
 };
 
 namespace {
@@ -265,10 +265,6 @@ int dsp_augmenter_create(int device, int pad_mode, int max_term, dsp_augmenter *
     if (pad_mode != DSP_PAD_REFLECT && pad_mode != DSP_PAD_ZERO) return capi_fail(DSP_EINVAL, "pad_mode must be DSP_PAD_REFLECT or DSP_PAD_ZERO");
     if (max_term < 1 || max_term > kMaxTermCap) return capi_fail(DSP_EINVAL, "max_term must be 1 .. 1024 (the resampler's cap)");
     if (const int rc = dsp::check_device(device)) return rc;
-    auto aug = std::make_unique<dsp_augmenter>();
-    aug->device = device;
-    aug->pad_mode = pad_mode;
-    aug->max_term = max_term;
     auto t = std::make_unique<dsp::AugTables>();
     for (int i = 0; i < dsp::kAugFft; ++i) {
         const float w = (float)(0.5 - 0.5 * std::cos(2.0 * kPi * (double)i / (double)dsp::kAugFft));
@@ -284,20 +280,15 @@ int dsp_augmenter_create(int device, int pad_mode, int max_term, dsp_augmenter *
         t->w2048[0][k] = (float)std::cos(-2.0 * kPi * ((double)k / 2048.0));
         t->w2048[1][k] = (float)std::sin(-2.0 * kPi * ((double)k / 2048.0));
     }
-    DSP_ON_DEVICE(device);
-    if (dsp::upload(aug->tables, *t) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc / upload of the tables");
-    *out = aug.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_augmenter &aug) -> int {
+        aug.pad_mode = pad_mode;
+        aug.max_term = max_term;
+        if (dsp::upload(aug.tables, *t) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc / upload of the tables");
+        return DSP_OK;
+    });
 }
 
-void dsp_augmenter_destroy(dsp_augmenter *aug)
-{
-    if (!aug) return;
-    dsp::DeviceScope scope(aug->device);
-    for (auto &kv : aug->resamplers) dsp_resampler_destroy(kv.second);
-    aug->ring.release();
-    delete aug;
-}
+void dsp_augmenter_destroy(dsp_augmenter *aug) { dsp::destroy(aug); }
 
 int dsp_stft_ragged_device(dsp_augmenter *aug, const float *d_in, long n, const long *offsets, float *d_spec, long *frame_offsets_out, void *stream)
 {
@@ -431,10 +422,13 @@ extern "C" int dsp_augment_ragged_device(dsp_augmenter *aug, const float *d_in, 
         const long count = (long)kv.second.size();
         const int up = kv.first.first, down = kv.first.second;
         if (up != down) {
-            dsp_resampler *&rs = aug->resamplers[kv.first];
-            if (!rs)
-                if (const int rc = dsp_resampler_create(aug->device, down, up, &rs)) { aug->resamplers.erase(kv.first); return rc; }
-            Run run{rs, first, count, b_total, std::vector<long>((size_t)count + 1)};
+            auto &owner = aug->resamplers[kv.first];
+            if (!owner) {
+                dsp_resampler *made = nullptr;
+                if (const int rc = dsp_resampler_create(aug->device, down, up, &made)) { aug->resamplers.erase(kv.first); return rc; }
+                owner.reset(made);
+            }
+            Run run{owner.get(), first, count, b_total, std::vector<long>((size_t)count + 1)};
             const long total = dsp_resample_offsets(down, up, ao.data() + first, count, run.bo.data());
             if (total < 0) return (int)total;
             for (long i = 0; i < count; ++i) {

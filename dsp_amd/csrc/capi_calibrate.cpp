@@ -32,9 +32,9 @@ bool finite(const dsp_calibration &p) { return std::isfinite(p.a) && std::isfini
 
 extern "C" {
 
-int dsp_calibrator_create(int device, dsp_calibrator **out) { return dsp::stage_create(device, out); }
+int dsp_calibrator_create(int device, dsp_calibrator **out) { return dsp::create_on_host(device, out); }
 
-void dsp_calibrator_destroy(dsp_calibrator *c) { dsp::stage_destroy(c); }
+void dsp_calibrator_destroy(dsp_calibrator *c) { dsp::destroy(c); }
 
 int dsp_calibration_duration_term(const long *n_frames, long n_rows, double *out)
 {

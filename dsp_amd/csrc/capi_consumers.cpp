@@ -19,19 +19,17 @@ using dsp::scan_args;
 using dsp::scan_plan;
 using dsp::scan_upload;
 
-struct dsp_stop_model {
-    int device = 0;
+struct dsp_stop_model : dsp::Handle {
     dsp::StopModelDev m{};
     dsp::DeviceBuf<void> d_blob;
     // workspace of dsp_classify_signal_batch_device / dsp_classify_signal
     dsp::DeviceBuf<float> d_mfcc, d_sig, d_prob;
-    dsp_mfcc_plan *plan = nullptr;     // default plan of dsp_classify_signal
+    std::unique_ptr<dsp_mfcc_plan, dsp::DestroyWith<dsp_mfcc_plan_destroy>> plan;     // default plan of dsp_classify_signal (owned)
     std::mutex mu;
     dsp::SpanRing scan;      // dsp_stop_scan_device: the per-recording offsets on their way to the GPU
 };
 
-struct dsp_speaker_model {
-    int device = 0;
+struct dsp_speaker_model : dsp::Handle {
     dsp::GmmDev target{}, ubm{};
     dsp::DeviceBuf<void> d_blob;
     dsp::SpanRing rows;      // dsp_speaker_llr_ragged_device, dsp_speaker_scan_device: the offsets on their way to the GPU (capi_util.hpp)
@@ -40,19 +38,9 @@ struct dsp_speaker_model {
     std::mutex mu;
 };
 
-extern "C" {
-
-int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_model **out)
+// the model's device blob from parameters dsp_stop_model_create has accepted; the model's device is current
+static int stop_model_init(dsp_stop_model *m, const dsp_stop_model_params *p)
 {
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (!p || p->n_coef <= 0 || p->max_frames <= 0 || !p->scaler_mean || !p->scaler_scale) return capi_fail(DSP_EINVAL, "bad stop-model parameters");
-    for (int l = 0; l < 4; ++l)
-        if (p->units[l] <= 0 || p->units[l] > dsp::kStopMaxUnits || !p->kernel[l] || !p->bias[l])
-            return capi_fail(DSP_EINVAL, "stop-model layers must have 1..16 units and non-NULL parameters");
-    if (p->units[3] != 1) return capi_fail(DSP_EINVAL, "the last layer must have one unit (sigmoid output)");
-    if (const int rc = dsp::check_device(device)) return rc;
-    DSP_ON_DEVICE(device);
     const size_t n_in = (size_t)p->n_coef * p->max_frames, u1 = p->units[0];
     // divisor with the reference's zero guard (audio_classifier_inference.c:44-45)
     std::vector<float> div(n_in);
@@ -96,8 +84,6 @@ int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_m
     size_t fan_in = n_in;
     for (int l = 0; l < 4; ++l) { n_f += fan_in * p->units[l] + p->units[l]; fan_in = p->units[l]; }
     const size_t bytes = (pad.size() + pad_b.size() + 1) * sizeof(double) + n_f * sizeof(float);
-    auto m = std::make_unique<dsp_stop_model>();
-    m->device = device;
     if (m->d_blob.alloc(bytes) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
     std::vector<char> host(bytes);
     char *h = host.data();
@@ -120,18 +106,25 @@ int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_m
         fan_in = p->units[l];
     }
     if (hipMemcpy(m->d_blob, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return capi_fail(DSP_EHIP, "hipMemcpy");
-    *out = m.release();
     return DSP_OK;
 }
 
-void dsp_stop_model_destroy(dsp_stop_model *m)
+extern "C" {
+
+int dsp_stop_model_create(const dsp_stop_model_params *p, int device, dsp_stop_model **out)
 {
-    if (!m) return;
-    dsp::DeviceScope dsp_device_scope_(m->device);
-    if (m->plan) dsp_mfcc_plan_destroy(m->plan);
-    m->scan.release();
-    delete m;
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!p || p->n_coef <= 0 || p->max_frames <= 0 || !p->scaler_mean || !p->scaler_scale) return capi_fail(DSP_EINVAL, "bad stop-model parameters");
+    for (int l = 0; l < 4; ++l)
+        if (p->units[l] <= 0 || p->units[l] > dsp::kStopMaxUnits || !p->kernel[l] || !p->bias[l])
+            return capi_fail(DSP_EINVAL, "stop-model layers must have 1..16 units and non-NULL parameters");
+    if (p->units[3] != 1) return capi_fail(DSP_EINVAL, "the last layer must have one unit (sigmoid output)");
+    if (const int rc = dsp::check_device(device)) return rc;
+    return dsp::create_on_device(device, out, [&](dsp_stop_model &m) { return stop_model_init(&m, p); });
 }
+
+void dsp_stop_model_destroy(dsp_stop_model *m) { dsp::destroy(m); }
 
 int dsp_stop_predict_device(dsp_stop_model *m, const float *d_mfcc, long n_clips, int frames_per_clip, float *d_prob, void *stream)
 {
@@ -245,7 +238,9 @@ float dsp_classify_signal(dsp_stop_model *m, const float *signal, int num_sample
             dsp_mfcc_config cfg;
             dsp_mfcc_default_config(&cfg);
             cfg.n_mfcc = m->m.n_coef;
-            if (dsp_mfcc_plan_create(&cfg, m->device, &m->plan) < 0) return bail("plan");
+            dsp_mfcc_plan *plan = nullptr;
+            if (dsp_mfcc_plan_create(&cfg, m->device, &plan) < 0) return bail("plan");
+            m->plan.reset(plan);
         }
         if (m->d_sig.reserve(((size_t)num_samples + 2) * sizeof(float)) != hipSuccess || m->d_prob.reserve(sizeof(float)) != hipSuccess) {
             capi_fail(DSP_ENOMEM, "hipMalloc");
@@ -256,7 +251,7 @@ float dsp_classify_signal(dsp_stop_model *m, const float *signal, int num_sample
             return bail("copy in");
         }
     }
-    if (dsp_classify_signal_batch_device(m->plan, m, m->d_sig, 1, num_samples, num_samples, m->d_prob, nullptr) < 0) return bail("run");
+    if (dsp_classify_signal_batch_device(m->plan.get(), m, m->d_sig, 1, num_samples, num_samples, m->d_prob, nullptr) < 0) return bail("run");
     float p = 0.0f;
     if (hipMemcpy(&p, m->d_prob, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { capi_fail(DSP_EHIP, "hipMemcpy"); return bail("copy out"); }
     return p;
@@ -271,37 +266,29 @@ int dsp_speaker_model_create(const dsp_gmm_params *target, const dsp_gmm_params 
             return capi_fail(DSP_EINVAL, "bad GMM parameters (k <= 64, d <= 16)");
     if (target->k != ubm->k || target->d != ubm->d) return capi_fail(DSP_EINVAL, "target and UBM must have the same shape");
     if (const int rc = dsp::check_device(device)) return rc;
-    DSP_ON_DEVICE(device);
-    const size_t kd = (size_t)target->k * target->d, k = target->k;
-    // layout: int32 inv_covs (t, u), int16 log_consts (t, u), int8 means (t, u)
-    const size_t bytes = 2 * kd * 4 + 2 * k * 2 + 2 * kd;
-    std::vector<char> host(bytes);
-    auto m = std::make_unique<dsp_speaker_model>();
-    m->device = device;
-    if (m->d_blob.alloc(bytes) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
-    char *d = static_cast<char *>(m->d_blob.get());
-    size_t off = 0;
-    auto put = [&](const void *src, size_t n) { std::memcpy(host.data() + off, src, n); const void *dev = d + off; off += n; return dev; };
-    m->target.k = m->ubm.k = target->k;
-    m->target.d = m->ubm.d = target->d;
-    m->target.inv_covs = static_cast<const int32_t *>(put(target->inv_covs, kd * 4));
-    m->ubm.inv_covs = static_cast<const int32_t *>(put(ubm->inv_covs, kd * 4));
-    m->target.log_consts = static_cast<const int16_t *>(put(target->log_consts, k * 2));
-    m->ubm.log_consts = static_cast<const int16_t *>(put(ubm->log_consts, k * 2));
-    m->target.means = static_cast<const int8_t *>(put(target->means, kd));
-    m->ubm.means = static_cast<const int8_t *>(put(ubm->means, kd));
-    if (hipMemcpy(m->d_blob, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return capi_fail(DSP_EHIP, "hipMemcpy");
-    *out = m.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_speaker_model &m) -> int {
+        const size_t kd = (size_t)target->k * target->d, k = target->k;
+        // layout: int32 inv_covs (t, u), int16 log_consts (t, u), int8 means (t, u)
+        const size_t bytes = 2 * kd * 4 + 2 * k * 2 + 2 * kd;
+        std::vector<char> host(bytes);
+        if (m.d_blob.alloc(bytes) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
+        char *d = static_cast<char *>(m.d_blob.get());
+        size_t off = 0;
+        auto put = [&](const void *src, size_t n) { std::memcpy(host.data() + off, src, n); const void *dev = d + off; off += n; return dev; };
+        m.target.k = m.ubm.k = target->k;
+        m.target.d = m.ubm.d = target->d;
+        m.target.inv_covs = static_cast<const int32_t *>(put(target->inv_covs, kd * 4));
+        m.ubm.inv_covs = static_cast<const int32_t *>(put(ubm->inv_covs, kd * 4));
+        m.target.log_consts = static_cast<const int16_t *>(put(target->log_consts, k * 2));
+        m.ubm.log_consts = static_cast<const int16_t *>(put(ubm->log_consts, k * 2));
+        m.target.means = static_cast<const int8_t *>(put(target->means, kd));
+        m.ubm.means = static_cast<const int8_t *>(put(ubm->means, kd));
+        if (hipMemcpy(m.d_blob, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return capi_fail(DSP_EHIP, "hipMemcpy");
+        return DSP_OK;
+    });
 }
 
-void dsp_speaker_model_destroy(dsp_speaker_model *m)
-{
-    if (!m) return;
-    dsp::DeviceScope dsp_device_scope_(m->device);
-    m->rows.release();
-    delete m;
-}
+void dsp_speaker_model_destroy(dsp_speaker_model *m) { dsp::destroy(m); }
 
 int dsp_speaker_llr_device(dsp_speaker_model *m, const float *d_mfcc, long n_clips, int frames_per_clip, int64_t *d_llr_mean,
                            int *d_labels, int64_t *d_ll_target, int64_t *d_ll_ubm, void *stream)
@@ -476,14 +463,14 @@ long dsp::ScannerCore::mfcc(const void *d_signal, int in_kind, long n, const lon
     if (const int rc = rowless_tail ? dsp::refuse_rowless(fo.data(), n, rowless_tail) : DSP_OK) return rc;
     if (rows == 0) return 0;
     if (!d_signal) return capi_fail(DSP_EINVAL, "d_signal is NULL");
-    DSP_ON_DEVICE(device);
+    DSP_ON_DEVICE(plan->device);
     if (d_mfcc.reserve((size_t)rows * plan->cfg.n_mfcc * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc (scanner MFCC workspace)");
     const int rc = mfcc_clips_ragged(plan, d_signal, in_kind, n, offsets, INT_MAX, d_mfcc, stream);
     return rc < 0 ? rc : rows;
 }
 
 // A scanner: PCM -> ragged MFCC matrix in its own workspace -> the models' window scans, all on the caller's stream.
-struct dsp_scanner {
+struct dsp_scanner : dsp::Handle {      // device: the plan's
     dsp::ScannerCore core;
     dsp_stop_model *stop = nullptr;
     dsp_speaker_model *spk = nullptr;
@@ -524,22 +511,16 @@ int dsp_scanner_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_speaker_mo
     if (!stop && !speaker) return capi_fail(DSP_EINVAL, "a scanner needs a stop model, a speaker model or both");
     if (const int rc = scan_args(cfg, 0)) return rc;
     if (const int rc = dsp::scan_front_check(plan, 0, stop, speaker, cfg)) return rc;
-    auto *s = new dsp_scanner;
-    s->core.plan = plan;
-    s->core.device = plan->device;
-    s->core.cfg = *cfg;
-    s->stop = stop;
-    s->spk = speaker;
-    *out = s;
-    return DSP_OK;
+    return dsp::create_on_host(plan->device, out, [&](dsp_scanner &s) {
+        s.core.plan = plan;
+        s.core.cfg = *cfg;
+        s.stop = stop;
+        s.spk = speaker;
+        return DSP_OK;
+    });
 }
 
-void dsp_scanner_destroy(dsp_scanner *s)
-{
-    if (!s) return;
-    dsp::DeviceScope dsp_device_scope_(s->core.device);
-    delete s;
-}
+void dsp_scanner_destroy(dsp_scanner *s) { dsp::destroy(s); }
 
 int dsp_scanner_run_device(dsp_scanner *s, const float *d_signal, long n_recordings, const long *offsets, float *d_prob, int64_t *d_llr_mean,
                            int *d_labels, void *stream)

@@ -10,13 +10,13 @@
 
 using dsp::capi_fail;
 
-struct dsp_cmvn {
-    int device = 0, d = 0, window = 0;
+struct dsp_cmvn : dsp::Handle {
+    int d = 0, window = 0;
     dsp::SpanRing spans;
 };
 
-struct dsp_speaker_enroller {
-    int device = 0, k = 0, d = 0;
+struct dsp_speaker_enroller : dsp::Handle {
+    int k = 0, d = 0;
     dsp::DeviceBuf<float> model;         // log_consts[k], means[k][d], inv_covs[k][d], rounded once to float32
     dsp::DeviceBuf<float> partials;      // grow-only: [chunks of a call][k (d + 1) + 1]
     dsp::SpanRing spans;
@@ -54,23 +54,15 @@ int dsp_cmvn_create(int device, int d, int window, dsp_cmvn **out)
     if (window < 2 || window > dsp::kCmvnMaxWindow)
         return capi_fail(DSP_EINVAL, "window must be 2 .. " + std::to_string(dsp::kCmvnMaxWindow) + " rows (what one block's LDS image holds), got " + std::to_string(window));
     if (const int rc = dsp::check_device(device)) return rc;
-    auto c = std::make_unique<dsp_cmvn>();
-    c->device = device;
-    c->d = d;
-    c->window = window;
-    DSP_ON_DEVICE(device);
-    DSP_CAPI_HIP(dsp::prepare_cmvn());
-    *out = c.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_cmvn &c) -> int {
+        c.d = d;
+        c.window = window;
+        DSP_CAPI_HIP(dsp::prepare_cmvn());
+        return DSP_OK;
+    });
 }
 
-void dsp_cmvn_destroy(dsp_cmvn *c)
-{
-    if (!c) return;
-    dsp::DeviceScope scope(c->device);
-    c->spans.release();
-    delete c;
-}
+void dsp_cmvn_destroy(dsp_cmvn *c) { dsp::destroy(c); }
 
 int dsp_cmvn_ragged_device(dsp_cmvn *c, const float *d_in, long n_recordings, const long *frame_offsets, float *d_out, void *stream)
 {
@@ -92,29 +84,17 @@ int dsp_speaker_enroller_create(const dsp_gmm_float_params *ubm, int device, dsp
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (const int rc = dsp::check_gmm_float_params(ubm, "ubm", "ubm: ")) return rc;
-    const int k = ubm->k, d = ubm->d;
-    const std::vector<float> host = dsp::pack_gmm_model(k, d, ubm->log_consts, ubm->means, ubm->inv_covs);
-    for (const float v : host)
-        if (!std::isfinite(v)) return capi_fail(DSP_EINVAL, "ubm: log_consts, means and inv_covs must be finite in float32");
+    std::vector<float> host;
+    if (const int rc = dsp::pack_ubm(ubm, host)) return rc;
     if (const int rc = dsp::check_device(device)) return rc;
-    auto e = std::make_unique<dsp_speaker_enroller>();
-    e->device = device;
-    e->k = k;
-    e->d = d;
-    DSP_ON_DEVICE(device);
-    if (e->model.alloc(host.size() * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc of the UBM");
-    DSP_CAPI_HIP(hipMemcpy(e->model, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = e.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_speaker_enroller &e) {
+        e.k = ubm->k;
+        e.d = ubm->d;
+        return dsp::upload_ubm(host, e.model, "hipMemcpy(e->model, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice)");
+    });
 }
 
-void dsp_speaker_enroller_destroy(dsp_speaker_enroller *e)
-{
-    if (!e) return;
-    dsp::DeviceScope scope(e->device);
-    e->spans.release();
-    delete e;
-}
+void dsp_speaker_enroller_destroy(dsp_speaker_enroller *e) { dsp::destroy(e); }
 
 int dsp_speaker_enroll_ragged_device(dsp_speaker_enroller *e, const float *d_feats, long n_speakers, const long *frame_offsets,
                                      const dsp_enroll_config *cfg, float *d_means, int8_t *d_means_q6, float *d_counts, float *d_ll_mean,

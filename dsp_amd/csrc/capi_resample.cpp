@@ -124,8 +124,7 @@ int upload_taps(const Ratio &ratio, const dsp::ResampleShape &s, dsp::DeviceBuf<
 
 }  // namespace
 
-struct dsp_resampler {
-    int device = 0;
+struct dsp_resampler : dsp::Handle {
     Ratio ratio{};
     dsp::ResampleShape shape{};
     dsp::DeviceBuf<float> taps;      // [up][row]: branch p reversed, so that ascending index = ascending input sample
@@ -247,23 +246,14 @@ int dsp_resampler_create(int device, int rate_in, int rate_out, dsp_resampler **
     Ratio ratio;
     if (const int rc = reduce(rate_in, rate_out, ratio)) return rc;
     if (const int rc = dsp::check_device(device)) return rc;
-    auto r = std::make_unique<dsp_resampler>();
-    r->device = device;
-    r->ratio = ratio;
-    r->shape = make_shape(ratio);
-    DSP_ON_DEVICE(device);
-    if (const int rc = upload_taps(ratio, r->shape, r->taps)) return rc;
-    *out = r.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_resampler &r) {
+        r.ratio = ratio;
+        r.shape = make_shape(ratio);
+        return upload_taps(ratio, r.shape, r.taps);
+    });
 }
 
-void dsp_resampler_destroy(dsp_resampler *r)
-{
-    if (!r) return;
-    dsp::DeviceScope scope(r->device);
-    r->spans.release();
-    delete r;
-}
+void dsp_resampler_destroy(dsp_resampler *r) { dsp::destroy(r); }
 
 int dsp_resample_ragged_device(dsp_resampler *r, const float *d_in, long n, const long *offsets, float *d_out, void *stream)
 {
@@ -363,8 +353,8 @@ long round_up16(long x) { return (x + 15) / 16 * 16; }
 
 }  // namespace
 
-struct dsp_stream_resampler {
-    int device = 0, rate_in = 0, rate_out = 0, in_kind = 0;
+struct dsp_stream_resampler : dsp::Handle {
+    int rate_in = 0, rate_out = 0, in_kind = 0;
     StreamRatio sr;
     dsp::ResampleShape shape{};
     long n_streams = 0;
@@ -452,36 +442,28 @@ int dsp_stream_resampler_create(int device, int rate_in, int rate_out, long n_st
                                          " taps per output: a stream would carry more samples than a block stages (not a live-feed ratio)");
     if (n_streams < 0 || n_streams >= (1L << 31)) return capi_fail(DSP_EINVAL, "n_streams must be in [0, 2^31)");
     if (const int rc = dsp::check_device(device)) return rc;
-    auto rs = std::make_unique<dsp_stream_resampler>();
-    rs->device = device;
-    rs->rate_in = rate_in;
-    rs->rate_out = rate_out;
-    rs->in_kind = kind;
-    rs->sr = stream_ratio(ratio);
-    rs->shape = shape;
-    rs->n_streams = n_streams;
-    rs->es = kind == 1 ? 2 : 4;
-    rs->half_stride = rs->sr.copy() ? 0 : round_up16((long)(shape.taps - 1) * rs->es);
-    rs->received.assign((size_t)n_streams, 0);
-    rs->side.assign((size_t)n_streams, 0);
-    rs->next_side.assign((size_t)n_streams, 0);
-    rs->oo.assign((size_t)n_streams + 1, 0);
-    DSP_ON_DEVICE(device);
-    if (!rs->sr.copy())
-        if (const int rc = upload_taps(ratio, shape, rs->taps)) return rc;
-    if (n_streams > 0 && rs->half_stride > 0 && rs->d_carry.alloc((size_t)n_streams * 2 * (size_t)rs->half_stride) != hipSuccess)
-        return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
-    *out = rs.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_stream_resampler &rs) -> int {
+        rs.rate_in = rate_in;
+        rs.rate_out = rate_out;
+        rs.in_kind = kind;
+        rs.sr = stream_ratio(ratio);
+        rs.shape = shape;
+        rs.n_streams = n_streams;
+        rs.es = kind == 1 ? 2 : 4;
+        rs.half_stride = rs.sr.copy() ? 0 : round_up16((long)(shape.taps - 1) * rs.es);
+        rs.received.assign((size_t)n_streams, 0);
+        rs.side.assign((size_t)n_streams, 0);
+        rs.next_side.assign((size_t)n_streams, 0);
+        rs.oo.assign((size_t)n_streams + 1, 0);
+        if (!rs.sr.copy())
+            if (const int rc = upload_taps(ratio, shape, rs.taps)) return rc;
+        if (n_streams > 0 && rs.half_stride > 0 && rs.d_carry.alloc((size_t)n_streams * 2 * (size_t)rs.half_stride) != hipSuccess)
+            return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
+        return DSP_OK;
+    });
 }
 
-void dsp_stream_resampler_destroy(dsp_stream_resampler *rs)
-{
-    if (!rs) return;
-    dsp::DeviceScope scope(rs->device);
-    rs->ring.release();
-    delete rs;
-}
+void dsp_stream_resampler_destroy(dsp_stream_resampler *rs) { dsp::destroy(rs); }
 
 int dsp_stream_resampler_reset(dsp_stream_resampler *rs, const long *streams, long n, void *stream)
 {

@@ -37,29 +37,21 @@ int dsp_svm_create(int device, int n_features, int n_sv, const float *offset, co
         return capi_fail(DSP_EINVAL, "bad argument");
     *out = nullptr;
     if (const int rc = dsp::check_device(device)) return rc;
-    DSP_ON_DEVICE(device);
-    auto s = std::make_unique<dsp_svm>();
-    s->device = device;
-    const size_t nf = n_features, ns = n_sv, total = 2 * nf + ns * nf + ns;
-    if (s->d_blob.alloc(total * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
-    float *p = s->d_blob;
-    hipError_t e = hipMemcpy(p, offset, nf * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p + nf, scale, nf * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p + 2 * nf, support_vectors, ns * nf * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p + 2 * nf + ns * nf, coefficients, ns * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return capi_fail(DSP_EHIP, hipGetErrorString(e));
-    s->m = {n_features, n_sv, gamma, rho, prob_a, prob_b, p, p + nf, p + 2 * nf, p + 2 * nf + ns * nf};
-    *out = s.release();
-    return DSP_OK;
+    return dsp::create_on_device(device, out, [&](dsp_svm &s) -> int {
+        const size_t nf = n_features, ns = n_sv, total = 2 * nf + ns * nf + ns;
+        if (s.d_blob.alloc(total * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc");
+        float *p = s.d_blob;
+        hipError_t e = hipMemcpy(p, offset, nf * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p + nf, scale, nf * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p + 2 * nf, support_vectors, ns * nf * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p + 2 * nf + ns * nf, coefficients, ns * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return capi_fail(DSP_EHIP, hipGetErrorString(e));
+        s.m = {n_features, n_sv, gamma, rho, prob_a, prob_b, p, p + nf, p + 2 * nf, p + 2 * nf + ns * nf};
+        return DSP_OK;
+    });
 }
 
-void dsp_svm_destroy(dsp_svm *s)
-{
-    if (!s) return;
-    dsp::DeviceScope dsp_device_scope_(s->device);
-    s->scan.release();
-    delete s;
-}
+void dsp_svm_destroy(dsp_svm *s) { dsp::destroy(s); }
 
 int dsp_svm_predict_device(dsp_svm *s, const float *d_feat, long n_clips, int *d_labels, float *d_decision,
                            float *d_prob1, void *stream)
@@ -288,7 +280,7 @@ static int scan_front_end(const dsp_mfcc_plan *p, int in_kind, const dsp_svm *s)
 }
 
 // A scrub-jay scanner: PCM -> the recordings' ragged MFCC matrix (+ the windows' head rows) in its own workspace -> svm_scan_kernel.
-struct dsp_scrubjay_scanner {
+struct dsp_scrubjay_scanner : dsp::Handle {      // device: the plan's
     dsp::ScannerCore core;
     dsp_svm *svm = nullptr;
     int head_rows = 0;
@@ -361,22 +353,16 @@ int dsp_scrubjay_scanner_create(dsp_mfcc_plan *plan, dsp_svm *svm, const dsp_sca
     if (!plan || !svm) return capi_fail(DSP_EINVAL, "plan and SVM must not be NULL");
     if (const int rc = dsp::scan_args(cfg, 0)) return rc;
     if (const int rc = scan_front_end(plan, 0, svm)) return rc;
-    auto *s = new dsp_scrubjay_scanner;
-    s->core.plan = plan;
-    s->core.device = plan->device;
-    s->core.cfg = *cfg;
-    s->svm = svm;
-    s->head_rows = head_rows_of(plan->cfg);
-    *out = s;
-    return DSP_OK;
+    return dsp::create_on_host(plan->device, out, [&](dsp_scrubjay_scanner &s) {
+        s.core.plan = plan;
+        s.core.cfg = *cfg;
+        s.svm = svm;
+        s.head_rows = head_rows_of(plan->cfg);
+        return DSP_OK;
+    });
 }
 
-void dsp_scrubjay_scanner_destroy(dsp_scrubjay_scanner *s)
-{
-    if (!s) return;
-    dsp::DeviceScope dsp_device_scope_(s->core.device);
-    delete s;
-}
+void dsp_scrubjay_scanner_destroy(dsp_scrubjay_scanner *s) { dsp::destroy(s); }
 
 int dsp_scrubjay_scanner_run_device(dsp_scrubjay_scanner *s, const float *d_signal, long n_recordings, const long *offsets, int *d_labels,
                                     float *d_decision, float *d_prob1, float *d_feat, void *stream)

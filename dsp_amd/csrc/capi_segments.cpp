@@ -45,9 +45,9 @@ int check_columns(long n_columns)
 
 extern "C" {
 
-int dsp_segmenter_create(int device, dsp_segmenter **out) { return dsp::stage_create(device, out); }
+int dsp_segmenter_create(int device, dsp_segmenter **out) { return dsp::create_on_host(device, out); }
 
-void dsp_segmenter_destroy(dsp_segmenter *s) { dsp::stage_destroy(s); }
+void dsp_segmenter_destroy(dsp_segmenter *s) { dsp::destroy(s); }
 
 long dsp_segments_capacity(const dsp_segment_config *cfg, const long *window_offsets, long n_recordings, long n_columns)
 {

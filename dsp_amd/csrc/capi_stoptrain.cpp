@@ -17,8 +17,8 @@ static_assert(DSP_STOP_TRAIN_CAP_ROWS == dsp::kStopTrainMaxRows && DSP_STOP_TRAI
               DSP_STOP_TRAIN_CAP_BATCH == dsp::kStopTrainMaxBatch && DSP_STOP_TRAIN_CAP_EPOCHS == dsp::kStopTrainMaxEpochs &&
               DSP_STOP_TRAIN_CAP_RUNS == dsp::kStopTrainMaxRuns, "the header's caps are the kernels'");
 
-struct dsp_stop_trainer {
-    int device = 0, n_coef = 0, max_frames = 0, units[4] = {0, 0, 0, 0};
+struct dsp_stop_trainer : dsp::Handle {
+    int n_coef = 0, max_frames = 0, units[4] = {0, 0, 0, 0};
     long n = 0;                                    // clips of the current dataset, 0: none
     dsp::StopTrainShape shape{};                   // of the current dataset (t_used, f_used)
     dsp::DeviceBuf<float> scaler, z;               // mean | scale over all inputs; z[n][f_used]
@@ -104,27 +104,17 @@ extern "C" {
 
 int dsp_stop_trainer_create(int device, int n_coef, int max_frames, const int *units, dsp_stop_trainer **out)
 {
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    if (const int rc = check_shape(n_coef, max_frames, units)) return rc;
     // no device is touched here: a device that does not exist is reported by the first call that takes a dataset
-    auto t = std::make_unique<dsp_stop_trainer>();
-    t->device = device;
-    t->n_coef = n_coef;
-    t->max_frames = max_frames;
-    std::memcpy(t->units, units, sizeof(t->units));
-    *out = t.release();
-    return DSP_OK;
+    return dsp::create_on_host(device, out, [&](dsp_stop_trainer &t) -> int {
+        if (const int rc = check_shape(n_coef, max_frames, units)) return rc;
+        t.n_coef = n_coef;
+        t.max_frames = max_frames;
+        std::memcpy(t.units, units, sizeof(t.units));
+        return DSP_OK;
+    });
 }
 
-void dsp_stop_trainer_destroy(dsp_stop_trainer *t)
-{
-    if (!t) return;
-    dsp::DeviceScope scope(t->device);
-    t->spans.release();
-    delete t;
-}
+void dsp_stop_trainer_destroy(dsp_stop_trainer *t) { dsp::destroy(t); }
 
 int dsp_stop_train_set_device(dsp_stop_trainer *t, const float *d_mfcc, long n, const long *frame_offsets, const int *scaler_rows,
                               long n_scaler_rows, const float *mean, const float *scale, float *mean_out, float *scale_out, void *stream)

@@ -82,14 +82,14 @@ long round_up(long x, long to) { return (x + to - 1) / to * to; }
 
 }  // namespace
 
-struct dsp_stream_session {
+struct dsp_stream_session : dsp::Handle {      // device: the plan's
     dsp_mfcc_plan *plan = nullptr;
     dsp_stop_model *stop = nullptr;
     dsp_speaker_model *spk = nullptr;
     dsp_scan_config scfg{};
     StreamRule rule;
     bool scans = false;                   // a model was given: windows exist
-    int device = 0, in_kind = 0;      // device: the plan's, kept for the session's destruction
+    int in_kind = 0;
     long n_streams = 0;
     long es = 4;                          // bytes per sample frame: 4 float, 2 mono int16, 4 stereo int16
     long carry_stride = 0, row_stride = 0;      // bytes per stream in d_carry / d_rowcarry (multiples of 16)
@@ -142,37 +142,29 @@ int dsp_stream_session_create(dsp_mfcc_plan *plan, dsp_stop_model *stop, dsp_spe
     const dsp_mfcc_config &pcfg = plan->cfg;
     StreamRule rule;
     if (const int rc = stream_rule(&pcfg, scans ? scan : nullptr, rule)) return rc;
-    auto s = std::make_unique<dsp_stream_session>();
-    s->plan = plan;
-    s->stop = stop;
-    s->spk = speaker;
-    s->scans = scans;
-    if (scans) s->scfg = *scan;
-    s->rule = rule;
-    s->device = plan->device;
-    s->in_kind = kind;
-    s->n_streams = n_streams;
-    s->es = kind == 1 ? 2 : 4;
-    s->carry_stride = round_up((rule.fl - 1) * s->es, 16);
-    s->row_stride = scans ? round_up((rule.wf - 1) * (long)pcfg.n_mfcc * 4, 16) : 0;
-    s->received.assign((size_t)n_streams, 0);
-    for (std::vector<long> *v : {&s->ro, &s->wo, &s->fo, &s->starts, &s->lengths}) v->assign((size_t)n_streams + 1, 0);
-    DSP_ON_DEVICE(plan->device);
-    if (n_streams > 0 && s->carry_stride > 0 && s->d_carry.alloc((size_t)n_streams * s->carry_stride) != hipSuccess)
-        return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
-    if (n_streams > 0 && s->row_stride > 0 && s->d_rowcarry.alloc((size_t)n_streams * s->row_stride) != hipSuccess)
-        return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried rows)");
-    *out = s.release();
-    return DSP_OK;
+    return dsp::create_on_device(plan->device, out, [&](dsp_stream_session &s) -> int {
+        s.plan = plan;
+        s.stop = stop;
+        s.spk = speaker;
+        s.scans = scans;
+        if (scans) s.scfg = *scan;
+        s.rule = rule;
+        s.in_kind = kind;
+        s.n_streams = n_streams;
+        s.es = kind == 1 ? 2 : 4;
+        s.carry_stride = round_up((rule.fl - 1) * s.es, 16);
+        s.row_stride = scans ? round_up((rule.wf - 1) * (long)pcfg.n_mfcc * 4, 16) : 0;
+        s.received.assign((size_t)n_streams, 0);
+        for (std::vector<long> *v : {&s.ro, &s.wo, &s.fo, &s.starts, &s.lengths}) v->assign((size_t)n_streams + 1, 0);
+        if (n_streams > 0 && s.carry_stride > 0 && s.d_carry.alloc((size_t)n_streams * s.carry_stride) != hipSuccess)
+            return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried samples)");
+        if (n_streams > 0 && s.row_stride > 0 && s.d_rowcarry.alloc((size_t)n_streams * s.row_stride) != hipSuccess)
+            return capi_fail(DSP_ENOMEM, "hipMalloc (the streams' carried rows)");
+        return DSP_OK;
+    });
 }
 
-void dsp_stream_session_destroy(dsp_stream_session *s)
-{
-    if (!s) return;
-    dsp::DeviceScope dsp_device_scope_(s->device);
-    s->ring.release();
-    delete s;
-}
+void dsp_stream_session_destroy(dsp_stream_session *s) { dsp::destroy(s); }
 
 int dsp_stream_session_reset(dsp_stream_session *s, const long *streams, long n, void *stream)
 {

@@ -17,8 +17,8 @@ static_assert(sizeof(dsp_svm_train_config) == 16, "dsp_svm_train_config is 16 by
 static_assert(sizeof(dsp_svm_fit_model) == 112, "dsp_svm_fit_model is 112 bytes (dsp_amd/lib.py SvmFitModel)");
 static_assert(DSP_SVM_TRAIN_MAX_ROWS == dsp::kSvmTrainMaxRows, "the header's cap is the kernels'");
 
-struct dsp_svm_trainer {
-    int device = 0, n_features = 0;
+struct dsp_svm_trainer : dsp::Handle {
+    int n_features = 0;
     long n = 0;                                    // rows of the current dataset, 0: none
     dsp::DeviceBuf<float> scaler, z;               // offset | scale; z[n][nf]
     dsp::DeviceBuf<double> d2;                     // [n][n]
@@ -212,25 +212,15 @@ extern "C" {
 
 int dsp_svm_trainer_create(int device, int n_features, dsp_svm_trainer **out)
 {
-    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    if (n_features < 1) return capi_fail(DSP_EINVAL, "n_features must be >= 1, got " + std::to_string(n_features));
     // no device is touched here: a device that does not exist is reported by the first call that takes a dataset
-    auto t = std::make_unique<dsp_svm_trainer>();
-    t->device = device;
-    t->n_features = n_features;
-    *out = t.release();
-    return DSP_OK;
+    return dsp::create_on_host(device, out, [&](dsp_svm_trainer &t) -> int {
+        if (n_features < 1) return capi_fail(DSP_EINVAL, "n_features must be >= 1, got " + std::to_string(n_features));
+        t.n_features = n_features;
+        return DSP_OK;
+    });
 }
 
-void dsp_svm_trainer_destroy(dsp_svm_trainer *t)
-{
-    if (!t) return;
-    dsp::DeviceScope scope(t->device);
-    t->spans.release();
-    delete t;
-}
+void dsp_svm_trainer_destroy(dsp_svm_trainer *t) { dsp::destroy(t); }
 
 int dsp_svm_train_set_device(dsp_svm_trainer *t, const float *d_feat, long n, const int *scaler_rows, long n_scaler_rows, const float *offset,
                              const float *scale, float *offset_out, float *scale_out, void *stream)

@@ -52,9 +52,9 @@ long dsp_trials_pairs(const int *truth, long n_rows, long n_columns)
     return pairs;
 }
 
-int dsp_trial_evaluator_create(int device, dsp_trial_evaluator **out) { return dsp::stage_create(device, out); }
+int dsp_trial_evaluator_create(int device, dsp_trial_evaluator **out) { return dsp::create_on_host(device, out); }
 
-void dsp_trial_evaluator_destroy(dsp_trial_evaluator *e) { dsp::stage_destroy(e); }
+void dsp_trial_evaluator_destroy(dsp_trial_evaluator *e) { dsp::destroy(e); }
 
 int dsp_trials_evaluate_device(dsp_trial_evaluator *e, const float *d_scores, long n_rows, long n_columns, const int *truth, const dsp_trials_config *cfg,
                                dsp_trial_column *d_columns, long *d_sweep_tp, long *d_sweep_fp, int *d_fa_above, int *d_fa_equal, void *stream)

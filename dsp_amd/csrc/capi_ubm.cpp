@@ -13,8 +13,8 @@
 
 using dsp::capi_fail;
 
-struct dsp_ubm_trainer {
-    int device = 0, k = 0, d = 0;
+struct dsp_ubm_trainer : dsp::Handle {
+    int k = 0, d = 0;
     dsp::DeviceBuf<double> partials;     // grow-only: the groups' partials, the supers' behind them
     dsp::DeviceBuf<double> state;        // grow-only: the float64 parameters, lower_bounds[max_iter] behind them
     dsp::DeviceBuf<float> model;         // the float32 E-step model
@@ -308,23 +308,16 @@ int dsp_ubm_trainer_create(int device, int k, int d, dsp_ubm_trainer **out)
     *out = nullptr;
     if (k < 1 || k > dsp::kGmmMaxK) return capi_fail(DSP_EINVAL, "k must be 1 .. 64, got " + std::to_string(k));
     if (d < 1 || d > dsp::kGmmMaxD) return capi_fail(DSP_EINVAL, "d must be 1 .. 16, got " + std::to_string(d));
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
     // nothing is allocated here and no device is touched: the workspace grows in the first call that trains, which is also where a
     // device that does not exist is reported
-    auto t = std::make_unique<dsp_ubm_trainer>();
-    t->device = device;
-    t->k = k;
-    t->d = d;
-    *out = t.release();
-    return DSP_OK;
+    return dsp::create_on_host(device, out, [&](dsp_ubm_trainer &t) {
+        t.k = k;
+        t.d = d;
+        return DSP_OK;
+    });
 }
 
-void dsp_ubm_trainer_destroy(dsp_ubm_trainer *t)
-{
-    if (!t) return;
-    dsp::DeviceScope scope(t->device);
-    delete t;
-}
+void dsp_ubm_trainer_destroy(dsp_ubm_trainer *t) { dsp::destroy(t); }
 
 int dsp_ubm_init_rows_device(dsp_ubm_trainer *t, const float *d_feats, long n, double reg_covar, double *weights, double *means, double *variances,
                              void *stream)

@@ -1,5 +1,6 @@
 // capi_util.hpp -- error reporting, device scopes, the owners of device and pinned host buffers (DeviceBuf, PinnedBuf), the
-// ragged-span ring, the scans' host planner, the score-matrix stages' handle and the number of devices that have state of their own
+// ragged-span ring (which frees itself), the scans' host planner, the handles' base with their one create and one destroy path (Handle,
+// create_on_device / create_on_host, destroy; the score-matrix stages' StageHandle), the float UBM of a handle and the number of devices that have state of their own
 // (kMaxDevices), shared by the translation units of the C ABI (capi.cpp, capi_scrubjay.cpp, capi_consumers.cpp, capi_stream.cpp, capi_gather.cpp, and the
 // classifiers' front end classify_front.hpp).  Nothing here knows a plan: what reads one is mfcc_plan.hpp.
 #pragma once
@@ -8,6 +9,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <memory>
@@ -27,7 +29,7 @@ constexpr int kMaxDevices = 64;
 // The owner of one buffer of the runtime's and of its size: whoever holds it frees it, once, on destruction or reset().  Move-only.
 // DeviceBuf<T> is hipMalloc'ed, PinnedBuf page-locked host memory (hipHostMalloc); these two and the public allocator of
 // capi_host.cpp are the only callers of the runtime's allocation functions in the host code.
-// Its holder makes the buffer's device current before the buffer is let go (the destroy functions' DeviceScope), and no object of
+// Its holder makes the buffer's device current before the buffer is let go (a handle's: dsp::destroy and the create helpers, below), and no object of
 // static storage holds one: at process exit the HIP runtime may already be gone.
 template <class T, bool kPinned> class OwnedBuf {
     T *p = nullptr;
@@ -84,6 +86,11 @@ template <class T> hipError_t upload(DeviceBuf<T> &buf, const T &host)
 // slots, all in flight, makes an acquirer wait: for the lease of the slot whose turn it is to end, then for its event.
 // Deadlock-free because no call holds two leases of one ring at once (each user takes one lease, launches, and lets it go before
 // it could ask the ring again), and no one waits for a lease while holding a lock a lease holder takes.
+// A ring frees itself: its destructor does what release() does (events, then the slots' buffers), so like an OwnedBuf it is destroyed
+// with its owner's device current and no object of static storage holds one.  Its holders are the handles below (Handle: on the heap,
+// destroyed by dsp::destroy), the default plan of capi.cpp (a pointer that is never deleted) and the classifiers' workspaces
+// (classify_front.hpp: the per-device array is allocated immortal; a context's ring is emptied by front::release before the context
+// is deleted).
 namespace dsp {
 struct ClipSpan;
 struct SpanRing {
@@ -162,6 +169,7 @@ struct SpanRing {
         }
         return hipSuccess;
     }
+    ~SpanRing() { release(); }
     void release()      // on the owner's device, no lease outstanding
     {
         std::lock_guard<std::mutex> lock(mu);
@@ -202,6 +210,26 @@ inline int check_gmm_float_params(const dsp_gmm_float_params *g, const char *who
     if (g->k < 1 || g->k > kGmmMaxK) return capi_fail(DSP_EINVAL, std::string(prefix) + "k must be 1 .. 64, got " + std::to_string(g->k));
     if (g->d < 1 || g->d > kGmmMaxD) return capi_fail(DSP_EINVAL, std::string(prefix) + "d must be 1 .. 16, got " + std::to_string(g->d));
     return DSP_OK;
+}
+
+// The float UBM of a handle (enroller, verifier).  A caller's UBM that check_gmm_float_params has passed -> the float32 block of
+// gmm_model.hpp on the host, or DSP_EINVAL where a value is not finite in float32
+inline int pack_ubm(const dsp_gmm_float_params *ubm, std::vector<float> &host)
+{
+    host = pack_gmm_model(ubm->k, ubm->d, ubm->log_consts, ubm->means, ubm->inv_covs);
+    for (const float v : host)
+        if (!std::isfinite(v)) return capi_fail(DSP_EINVAL, "ubm: log_consts, means and inv_covs must be finite in float32");
+    return DSP_OK;
+}
+// that block into `model` on the current device: DSP_OK, DSP_ENOMEM, or DSP_EHIP "<copy_failed>: <the runtime's error>" with `model`
+// left empty (the enroller names the call, as it always has)
+inline int upload_ubm(const std::vector<float> &host, DeviceBuf<float> &model, const char *copy_failed = "hipMemcpy of the UBM")
+{
+    if (model.alloc(host.size() * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc of the UBM");
+    const hipError_t e = hipMemcpy(model, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) return DSP_OK;
+    model.reset();
+    return capi_fail(DSP_EHIP, std::string(copy_failed) + ": " + hipGetErrorString(e));
 }
 
 // clip c of a ragged batch is samples [offsets[c], offsets[c + 1]) per channel: its length, or DSP_EINVAL naming the clip
@@ -331,33 +359,74 @@ struct DeviceScope {
     DeviceScope &operator=(const DeviceScope &) = delete;
 };
 
-// What a stage on a score matrix keeps between calls (dsp_segmenter, dsp_trial_evaluator, dsp_calibrator derive from it): its device, a
-// grow-only workspace and the ring its host arrays travel through.
-struct StageHandle {
+}
+#define DSP_ON_DEVICE(dev)                                                                                        \
+    dsp::DeviceScope dsp_device_scope_(dev);                                                                      \
+    if (dsp_device_scope_.err != hipSuccess)                                                                      \
+        return dsp::capi_fail(DSP_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(dsp_device_scope_.err))
+
+// ---- handles: one create path, one destroy path ----------------------------------------------------------------------------------
+// Every handle that lives on one GPU derives from Handle, is made by create_on_device or create_on_host and is let go by destroy: its
+// device members (DeviceBuf, SpanRing, handles it owns) are released by its own destructor, and these three are the only places that
+// run it -- always inside the DeviceScope of the handle's device.  Not here, each for a reason: dsp_gather (capi_gather.cpp) owns
+// communicators on several devices, so there is no one device to make current; the classifier contexts (dsp_classify_ctx and the
+// per-device Work of classify_front.hpp) live under their own mutex and are immortal or released by front::release.
+namespace dsp {
+struct Handle {
     int device = 0;
-    DeviceBuf<char> ws;
-    SpanRing spans;
 };
-// no device is touched here: a device that does not exist is reported by the first call that launches
-template <class H> int stage_create(int device, H **out)
+
+// The handle of a create function whose arguments have passed (its own checks, check_device among them, stay in front of this call,
+// in their order): made and initialised with `device` current -- init(H &) returns DSP_OK or what capi_fail returned -- and stored in
+// *out on success alone.  The handle is declared after the scope, so whatever init had allocated when it failed is freed before the
+// caller's device is put back.
+template <class H, class Init> int create_on_device(int device, H **out, Init init)
+{
+    if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    DSP_ON_DEVICE(device);
+    auto h = std::make_unique<H>();
+    h->device = device;
+    if (const int rc = init(*h)) return rc;
+    *out = h.release();
+    return DSP_OK;
+}
+
+// The same for a handle whose create touches no device (init may check arguments and fill host members, nothing else): a device that
+// does not exist is reported by the first call that launches, only a negative index here.
+template <class H, class Init> int create_on_host(int device, H **out, Init init)
 {
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
     auto h = std::make_unique<H>();
     h->device = device;
+    if (const int rc = init(*h)) return rc;
     *out = h.release();
     return DSP_OK;
 }
-template <class H> void stage_destroy(H *h)
+template <class H> int create_on_host(int device, H **out)
+{
+    return create_on_host(device, out, [](H &) { return DSP_OK; });
+}
+
+// every dsp_*_destroy of a Handle: NULL is a no-op
+template <class H> void destroy(H *h)
 {
     if (!h) return;
     DeviceScope scope(h->device);
-    h->spans.release();
     delete h;
 }
+
+// the deleter of a handle another handle owns: std::unique_ptr<dsp_mfcc_plan, DestroyWith<dsp_mfcc_plan_destroy>>
+template <auto Destroy> struct DestroyWith {
+    template <class H> void operator()(H *h) const { Destroy(h); }
+};
+
+// What a stage on a score matrix keeps between calls (dsp_segmenter, dsp_trial_evaluator, dsp_calibrator derive from it): a grow-only
+// workspace and the ring its host arrays travel through.
+struct StageHandle : Handle {
+    DeviceBuf<char> ws;
+    SpanRing spans;
+};
 }
-#define DSP_ON_DEVICE(dev)                                                                                        \
-    dsp::DeviceScope dsp_device_scope_(dev);                                                                      \
-    if (dsp_device_scope_.err != hipSuccess)                                                                      \
-        return dsp::capi_fail(DSP_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(dsp_device_scope_.err))

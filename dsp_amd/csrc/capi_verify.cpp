@@ -11,8 +11,8 @@
 
 using dsp::capi_fail;
 
-struct dsp_speaker_verifier {
-    int device = 0, k = 0, d = 0;
+struct dsp_speaker_verifier : dsp::Handle {
+    int k = 0, d = 0;
     std::vector<float> host;             // log_consts[k], means[k][d], inv_covs[k][d], rounded once to float32
     dsp::DeviceBuf<float> model;         // the same on the device, from the first call that scores
     dsp::DeviceBuf<double> partials;     // grow-only: [chunks of a run of clips][4 tiles][1 + S]; the scan's float ll [1 + S][rows of a run]
@@ -46,17 +46,7 @@ size_t max_run_floats()
 }
 
 // the UBM on the verifier's device (current), from the first call that scores
-int upload_ubm(dsp_speaker_verifier *v)
-{
-    if (v->model.get()) return DSP_OK;
-    if (v->model.alloc(v->host.size() * sizeof(float)) != hipSuccess) return capi_fail(DSP_ENOMEM, "hipMalloc of the UBM");
-    const hipError_t e = hipMemcpy(v->model, v->host.data(), v->host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        v->model.reset();
-        return capi_fail(DSP_EHIP, std::string("hipMemcpy of the UBM: ") + hipGetErrorString(e));
-    }
-    return DSP_OK;
-}
+int upload_ubm(dsp_speaker_verifier *v) { return v->model.get() ? DSP_OK : dsp::upload_ubm(v->host, v->model); }
 
 // one run of consecutive windows of a scan: pieces [p0, p1) of the plan, scored into ll[1 + S][pitch] from row `base` of the matrix
 struct ScanRun {
@@ -119,28 +109,18 @@ int dsp_speaker_verifier_create(const dsp_gmm_float_params *ubm, int device, dsp
     if (!out) return capi_fail(DSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (const int rc = dsp::check_gmm_float_params(ubm, "ubm", "ubm: ")) return rc;
-    if (device < 0) return capi_fail(DSP_EINVAL, "device index out of range");
-    auto v = std::make_unique<dsp_speaker_verifier>();
-    v->host = dsp::pack_gmm_model(ubm->k, ubm->d, ubm->log_consts, ubm->means, ubm->inv_covs);
-    for (const float x : v->host)
-        if (!std::isfinite(x)) return capi_fail(DSP_EINVAL, "ubm: log_consts, means and inv_covs must be finite in float32");
     // no device is touched here: the UBM goes up in the first call that scores, which is also where a device that does not exist is reported
-    v->device = device;
-    v->max_run_doubles = max_run_doubles();
-    v->max_run_floats = max_run_floats();
-    v->k = ubm->k;
-    v->d = ubm->d;
-    *out = v.release();
-    return DSP_OK;
+    return dsp::create_on_host(device, out, [&](dsp_speaker_verifier &v) -> int {
+        if (const int rc = dsp::pack_ubm(ubm, v.host)) return rc;
+        v.max_run_doubles = max_run_doubles();
+        v.max_run_floats = max_run_floats();
+        v.k = ubm->k;
+        v.d = ubm->d;
+        return DSP_OK;
+    });
 }
 
-void dsp_speaker_verifier_destroy(dsp_speaker_verifier *v)
-{
-    if (!v) return;
-    dsp::DeviceScope scope(v->device);
-    v->spans.release();
-    delete v;
-}
+void dsp_speaker_verifier_destroy(dsp_speaker_verifier *v) { dsp::destroy(v); }
 
 int dsp_speaker_verify_ragged_device(dsp_speaker_verifier *v, const float *d_feats, long n_clips, const long *frame_offsets, const float *d_means,
                                      long n_speakers, float *d_llr, float *d_ll_ubm, float *d_ll_target, int *d_best, float *d_best_llr, void *stream)

@@ -11,6 +11,7 @@
 
 #include "gmm_model.hpp"
 #include "mfcc_device.hpp"
+#include "span_find.hpp"
 
 namespace dsp {
 namespace {
@@ -38,16 +39,11 @@ __device__ __forceinline__ float wave_max(float v) { return wave_all(v, [](float
 __device__ __forceinline__ float wave_sum(float v) { return wave_all(v, [](float a, float b) { return a + b; }); }
 
 // the recording / speaker / clip that owns unit u of a ragged launch (spans[n] with a first unit `unit0` each, enroll_kernels.hpp RowSpan):
-// the last one whose first unit is <= u (those without rows own no unit)
+// the last one whose first unit is <= u (those without rows own no unit): span_find.hpp's owner_of
 template <class Span>
 __device__ inline long owner_of_unit(const Span *spans, long n, long u)
 {
-    long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (spans[mid].unit0 <= u) lo = mid; else hi = mid;
-    }
-    return lo;
+    return owner_of(n, u, [spans](long i) { return spans[i].unit0; });
 }
 
 // rows [0, cnt) of src[cnt][D] into the block's LDS image xs[rows of the chunk][Ld]; a barrier follows before any row is read

@@ -29,9 +29,8 @@ struct PlanKernel {
 
 }  // namespace dsp
 
-struct dsp_mfcc_plan {
+struct dsp_mfcc_plan : dsp::Handle {
     dsp_mfcc_config cfg;
-    int device = 0;
     int n_cu = 0;
     int kernel = DSP_KERNEL_WAVE;   // what dsp_mfcc_plan_set_kernel asked for
     dsp::PlanKernel run;            // what that means on this plan
@@ -57,8 +56,7 @@ struct dsp_mfcc_plan {
     dsp::SpanRing spans;      // ragged batches of the fused clip kernels: the clips' spans on their way to the GPU (capi_util.hpp)
 };
 
-struct dsp_svm {
-    int device = 0;
+struct dsp_svm : dsp::Handle {
     dsp::SvmModelDev m{};
     dsp::DeviceBuf<float> d_blob;
     dsp::SpanRing scan;      // dsp_svm_scan_device: the per-recording arrays on their way to the GPU (capi_util.hpp)
@@ -163,8 +161,7 @@ int scan_front_check(const dsp_mfcc_plan *plan, int in_kind, const dsp_stop_mode
 
 // What the scanners share (dsp_scanner of capi_consumers.cpp, where mfcc() lives; dsp_scrubjay_scanner of capi_scrubjay.cpp): PCM -> the recordings' ragged MFCC matrix in the scanner's own workspace.
 struct ScannerCore {
-    dsp_mfcc_plan *plan = nullptr;
-    int device = 0;            // the plan's, kept for the scanner's destruction
+    dsp_mfcc_plan *plan = nullptr;      // (its device is the scanner's: Handle::device)
     dsp_scan_config cfg{};
     DeviceBuf<float> d_mfcc;
     std::vector<long> fo;      // recording r = rows [fo[r], fo[r + 1]) of d_mfcc

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "resample_kernels.hpp"
+#include "span_find.hpp"
 
 namespace dsp {
 namespace {
@@ -38,15 +39,11 @@ template <int IN> __device__ inline float decode_pair(unsigned q)      // one 32
     return IN == 2 ? (float)l * (1.0f / 32768.0f) : (float)(l + r) * (1.0f / 65536.0f);
 }
 
-// the recording that owns tile t: the last one whose first tile is <= t (recordings without output own no tile)
-__device__ inline long owner_of_tile(const ResampleSpan *spans, long n_rec, long t)
+// the recording (ResampleSpan) or stream (StreamResampleSpan) that owns tile t: the last one whose first tile is <= t (those without
+// output own no tile) -- span_find.hpp's owner_of
+template <class Span> __device__ inline long owner_of_tile(const Span *spans, long n, long t)
 {
-    long lo = 0, hi = n_rec;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (spans[mid].tile0 <= t) lo = mid; else hi = mid;
-    }
-    return lo;
+    return owner_of(n, t, [spans](long i) { return spans[i].tile0; });
 }
 
 // ys[0, cnt) -> o[0, cnt): one float per lane up to the first 16-byte boundary of o, 16-byte stores, a tail of single floats
@@ -189,16 +186,6 @@ void launch_one(const void *in, const ResampleSpan *spans, long n_rec, long base
 // resample_kernel is the stage alone: the samples come from the stream's carry (frame by frame: it is short and lies wherever its slot
 // does) and then from the chunk (aligned 16-byte loads for its interior), zeros before the carry's first sample and past the last
 // received one.  The filter loop and the store restate resample_kernel<IN, true, UP1>'s: the same taps, the same jj order, the same FMA.
-__device__ inline long owner_of_stream_tile(const StreamResampleSpan *spans, long n_spans, long t)
-{
-    long lo = 0, hi = n_spans;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (spans[mid].tile0 <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 template <int IN, bool UP1>
 __global__ __launch_bounds__(kThreads) void resample_stream_kernel(const void *__restrict__ carry, const void *__restrict__ chunks,
                                                                    const StreamResampleSpan *__restrict__ spans, long n_spans, long tile_base,
@@ -208,7 +195,7 @@ __global__ __launch_bounds__(kThreads) void resample_stream_kernel(const void *_
     float *ys = lds;                      // [tile]
     float *xs = lds + s.tile;             // [span + 16]
     const long t = tile_base + blockIdx.x;
-    const StreamResampleSpan sp = spans[owner_of_stream_tile(spans, n_spans, t)];
+    const StreamResampleSpan sp = spans[owner_of_tile(spans, n_spans, t)];
     const long kr = (t - sp.tile0) * s.tile;                      // the tile's first output, counted from the span's first
     const long a0 = (sp.k0 + kr) * s.down + s.half;
     const long i0 = a0 / s.up;

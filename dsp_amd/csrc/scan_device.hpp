@@ -3,17 +3,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include "span_find.hpp"
+
 namespace dsp {
 
-// the r with off[r] <= key < off[r + 1] (off non-decreasing over n + 1 entries, off[0] <= key < off[n])
+// the r with off[r] <= key < off[r + 1] (off non-decreasing over n + 1 entries, off[0] <= key < off[n]): span_find.hpp's owner_of
 __device__ __forceinline__ long scan_find(const long *__restrict__ off, long n, long key)
 {
-    long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if (off[mid] <= key) lo = mid; else hi = mid;
-    }
-    return lo;
+    return owner_of(n, key, [off](long r) { return off[r]; });
 }
 
 }  // namespace dsp

@@ -45,6 +45,7 @@ struct SegOffsets {
 };
 
 // the recording that owns `chunk` (or block, with bo): the largest r < n with co[r] <= chunk (recordings without windows own none)
+// (span_find.hpp's owner_of finds the same recording; this form stays because joining it changes the kernels' instructions, which nobody has timed)
 __device__ long owner_of_chunk(const long *co, long n, long chunk)
 {
     long lo = 0, hi = n;

@@ -29,6 +29,7 @@ constexpr int kUnroll = 4;               // slots a lane group takes at a time i
 constexpr long kMaxGrid = 2048;          // 256 CUs x 8 blocks: the rest of the tiles by the grid's stride
 
 // the clip of a tile: the last c with to[c] <= tile (a clip without tiles shares its offset with the next one and is passed over)
+// (span_find.hpp's owner_of finds the same clip; this form stays because joining it changes the kernels' instructions, which nobody has timed)
 __device__ inline long clip_of_tile(const long *to, long n_clips, long tile)
 {
     long lo = 0, hi = n_clips - 1;
