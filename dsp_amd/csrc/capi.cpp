@@ -64,6 +64,21 @@ static bool valid_cfg_400(const dsp_mfcc_config &c, std::string &why)
     return true;
 }
 
+// DSP_FRAMING_CENTER at n_fft 2048 (mfcc2048_kernel.hip, CENTER): librosa.feature.mfcc with librosa's default n_fft, keyword_classifier.py:41-44 and
+// cepstrum/train.py:38-40 (dsp_mfcc_librosa_config), on the reference-semantics family of the kernel; every refusal names the field
+static bool valid_cfg_2048_center(const dsp_mfcc_config &c, std::string &why)
+{
+    if (c.frame_length != 2048) { why = "frame_length must be 2048 for DSP_FRAMING_CENTER at n_fft = 2048"; return false; }
+    if (c.win_length != 0) { why = "win_length must be 0 for DSP_FRAMING_CENTER at n_fft = 2048"; return false; }
+    if (c.n_mels > dsp::k2048MaxMels) { why = "n_mels must be in [1, 128] for n_fft = 2048"; return false; }
+    if (c.n_mfcc > dsp::k2048MaxMfcc) { why = "n_mfcc must be in [1, 32] for n_fft = 2048"; return false; }
+    if (c.spectrum != DSP_SPECTRUM_POWER) { why = "spectrum: DSP_SPECTRUM_MAGNITUDE is not implemented with DSP_FRAMING_CENTER"; return false; }
+    if (c.log_mode == DSP_LOG_LOG10_FLOOR) { why = "log_mode: DSP_LOG_LOG10_FLOOR is not implemented with DSP_FRAMING_CENTER"; return false; }
+    if (c.mel_norm == DSP_MELNORM_AUBIO_SLANEY) { why = "mel_norm: DSP_MELNORM_AUBIO_SLANEY is not implemented with DSP_FRAMING_CENTER"; return false; }
+    if (c.prefilter != DSP_PREFILTER_NONE) { why = "prefilter: the per-frame prefilter is implemented for n_fft = 512 and 1024"; return false; }
+    return true;
+}
+
 bool dsp::valid_cfg(const dsp_mfcc_config &c, std::string &why)
 {
     if (c.sample_rate <= 0) { why = "sample_rate must be positive"; return false; }
@@ -78,8 +93,9 @@ bool dsp::valid_cfg(const dsp_mfcc_config &c, std::string &why)
     if (c.mel_norm != DSP_MELNORM_NONE && c.mel_norm != DSP_MELNORM_SLANEY && c.mel_norm != DSP_MELNORM_LIBROSA && c.mel_norm != DSP_MELNORM_AUBIO_SLANEY) { why = "unknown mel_norm"; return false; }
     if (c.spectrum != DSP_SPECTRUM_POWER && c.spectrum != DSP_SPECTRUM_MAGNITUDE) { why = "unknown spectrum"; return false; }
     if (c.framing != DSP_FRAMING_COMPLETE && c.framing != DSP_FRAMING_STREAM && c.framing != DSP_FRAMING_CENTER) { why = "unknown framing"; return false; }
-    if (c.framing == DSP_FRAMING_CENTER && c.n_fft != 400) { why = "framing: DSP_FRAMING_CENTER is implemented for n_fft = 400"; return false; }
+    if (c.framing == DSP_FRAMING_CENTER && c.n_fft != 400 && c.n_fft != 2048) { why = "framing: DSP_FRAMING_CENTER is implemented for n_fft = 400 and 2048"; return false; }
     if (c.n_fft == 400) return valid_cfg_400(c, why);
+    if (c.framing == DSP_FRAMING_CENTER) return valid_cfg_2048_center(c, why);
     // the aubio-semantics options of cepstrum/scrubjay_infer.c's front end live on the 2048-point kernel
     if (c.n_fft != 2048 && (c.mel_norm == DSP_MELNORM_AUBIO_SLANEY || c.log_mode == DSP_LOG_LOG10_FLOOR || c.spectrum != DSP_SPECTRUM_POWER ||
                             c.framing != DSP_FRAMING_COMPLETE)) {
@@ -184,6 +200,31 @@ void dsp_mfcc_speaker_config(dsp_mfcc_config *c)
     c->prefilter = DSP_PREFILTER_NONE;
     c->fmin = 0.0f;
     c->fmax = 8000.0f;
+    c->amin = 1e-10f;
+    c->top_db = 80.0f;
+}
+
+void dsp_mfcc_librosa_config(dsp_mfcc_config *c, int sample_rate, int n_mfcc)
+{
+    // 2fa/audio/keyword_classifier.py:41-44 (librosa.feature.mfcc(y, sr = 22050, n_mfcc = 13)) and cepstrum/train.py:38-40, run.py:11-14
+    // (n_mfcc = 20), with librosa's defaults for everything else: n_fft 2048, hop_length 512, center = True, 128 Slaney mel filters over
+    // 0 .. sr / 2, power_to_db(ref = 1, top_db = 80) over the clip, the orthonormal DCT
+    dsp_mfcc_default_config(c);
+    c->sample_rate = sample_rate;
+    c->n_fft = 2048;
+    c->frame_length = 2048;
+    c->hop_length = 512;
+    c->n_mels = 128;
+    c->n_mfcc = n_mfcc;
+    c->window = DSP_WINDOW_HANN;
+    c->mel_norm = DSP_MELNORM_LIBROSA;
+    c->log_mode = DSP_LOG_GLOBAL_REF1;
+    c->spectrum = DSP_SPECTRUM_POWER;
+    c->framing = DSP_FRAMING_CENTER;
+    c->win_length = 0;
+    c->prefilter = DSP_PREFILTER_NONE;
+    c->fmin = 0.0f;
+    c->fmax = 0.5f * (float)sample_rate;
     c->amin = 1e-10f;
     c->top_db = 80.0f;
 }
@@ -486,6 +527,10 @@ int dsp::plan_accepts(const dsp_mfcc_plan *p, PlanUse use, int in_kind)
     const auto form = [&](Mfcc512Use u) {
         return fam == K::FFT512_TILE && mfcc512_has_form(u, p->host.dct_split, p->host.dct_len, p->host.mel_gather, c.frame_length, in_kind, true);
     };
+    // centred 2048-point plans (dsp_mfcc_librosa_config) run float frames, clips and ragged batches, as the 400-point plans do
+    if (c.framing == DSP_FRAMING_CENTER && fam != K::FFT400 && (in_kind != 0 || (use != PlanUse::Frames && use != PlanUse::Clips && use != PlanUse::Ragged)))
+        return capi_fail(DSP_EINVAL, "framing: DSP_FRAMING_CENTER plans at n_fft 2048 take float frames, clips and ragged batches only (no PCM16 ingestion, "
+                                     "fused clip kernel, scanner or stream session)");
     switch (use) {
     case PlanUse::FusedLabel:
         if (fam == K::FFT400) return refuse_400("the fused clip -> label path");

@@ -111,11 +111,15 @@ __device__ __forceinline__ float load_one_2048(const void *base, long i)
 }
 
 // RAGGED (CLIPS, !POOL): clips of different lengths, frame g of the batch to out[g]; clip, t and samples from args.spans (RaggedCursor)
-template <bool CLIPS, bool POOL, bool AUB = false, int IN = 0, bool RAGGED = false>
+// CENTER (CLIPS, !POOL, !AUB, float samples): DSP_FRAMING_CENTER, librosa's center = True with pad_mode "constant" -- frame t of a clip of n
+// samples covers [t hop - 1024, t hop + 1024); what lies outside [0, n) reads as zero and is NOT loaded (in a ragged buffer the
+// neighbouring clip lies there, in front of clip 0 nothing does).  A separate instantiation, as AUB: the other kernels keep their load.
+template <bool CLIPS, bool POOL, bool AUB = false, int IN = 0, bool RAGGED = false, bool CENTER = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mfcc2048_kernel(const Mfcc512Args args, const GenTables2048 *__restrict__ G)
 {
     static_assert(!POOL || CLIPS, "pooling is per clip");
     static_assert(!RAGGED || (CLIPS && !POOL), "ragged batches: clip mode, coefficients stored");
+    static_assert(!CENTER || (CLIPS && !POOL && !AUB && IN == 0), "centred framing: float clips of the reference-semantics family, coefficients stored");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -217,13 +221,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
             if constexpr (POOL || RAGGED) n_clip = cur.n_samples;
             hi_i = min(frame_len, n_clip - start);
         }
+        if constexpr (CENTER) {
+            const int start = cur.t * args.hop - 1024;                   // first sample of the frame inside its clip (even; < 0: padding)
+            src -= 1024;                                                 // cur.off = clip_off + t * hop
+            lo_i = start < 0 ? -start : 0;
+            int n_clip = args.samples_per_clip;                          // ragged batches: the clip's own length
+            if constexpr (RAGGED) n_clip = cur.n_samples;
+            hi_i = min(2048, n_clip - start);                            // (t hop <= n: at least 1024)
+        }
+        constexpr bool LO = AUB || CENTER;                               // the other kernels' frames start inside the clip: no test
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
             const int i = 2 * (lane + 64 * a);
             float x0 = 0.0f, x1 = 0.0f;
-            if (i + 1 < hi_i && (!AUB || i >= lo_i)) {                   // lo_i is even: a pair never straddles it
+            if (i + 1 < hi_i && (!LO || i >= lo_i)) {                    // lo_i is even: a pair never straddles it
                 load_pair_2048<IN, CLIPS>(args.in, src + i, x0, x1);     // clips re-read samples: cacheable
-            } else if (i < hi_i && (!AUB || i >= lo_i)) {
+            } else if (i < hi_i && (!LO || i >= lo_i)) {
                 x0 = load_one_2048<IN>(args.in, src + i);
             }
             raw[a] = {x0, x1};
@@ -514,6 +527,15 @@ hipError_t launch_mfcc2048(const Mfcc512Args &args, const GenTables2048 *tables,
     const size_t Q_BLOCK_BYTES = lds_bytes_2048(args.n_mels, pool, aub);
     if (args.stream_framing && (!clips || (args.samples_per_clip <= 0 && !args.spans) || args.hop > args.frame_len)) return hipErrorInvalidConfiguration;      // (ragged: lengths in the spans)
     if (args.in_kind != 0 && (!aub || !clips || args.in_kind < 0 || args.in_kind > 3)) return hipErrorInvalidConfiguration;      // int16: the scrubjay_infer.c front end, clips
+    if (args.center_framing) {      // DSP_FRAMING_CENTER: float clips and ragged batches of the reference-semantics family, frame_length 2048
+        if (pool || aub || args.in_kind != 0 || !clips || args.frame_len != 2048 || (args.samples_per_clip <= 0 && !args.spans) || (args.hop & 1))
+            return hipErrorInvalidConfiguration;
+        if (args.spans) {
+            if (args.n_clips <= 0) return hipErrorInvalidConfiguration;
+            hipLaunchKernelGGL((mfcc2048_kernel<true, false, false, 0, true, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        } else hipLaunchKernelGGL((mfcc2048_kernel<true, false, false, 0, false, true>), g, b, Q_BLOCK_BYTES, stream, args, tables);
+        return hipGetLastError();
+    }
     if (pool) {
         if (!clips || args.chunk != args.frames_per_clip || !args.pool.labels || args.pool.svm.n_features != 2 * args.n_mfcc ||
             args.pool.svm.n_features > 64 || (args.log_mode != 0 && args.log_mode != 2))

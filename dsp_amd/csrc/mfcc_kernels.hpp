@@ -54,7 +54,7 @@ struct Mfcc512Args {
     // stream_framing: frame t of a clip covers samples [(t + 1) hop - frame_len, (t + 1) hop), zeros outside [0, samples_per_clip)
     int spectrum = 0;
     int stream_framing = 0;
-    // n_fft 400 only (DSP_FRAMING_CENTER, clips): frame t covers samples [t hop - frame_len / 2, t hop + frame_len / 2), zeros outside
+    // n_fft 400 and 2048 (DSP_FRAMING_CENTER, clips): frame t covers samples [t hop - frame_len / 2, t hop + frame_len / 2), zeros outside
     // [0, samples_per_clip)
     int center_framing = 0;
     int samples_per_clip = 0;

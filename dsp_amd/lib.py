@@ -380,6 +380,7 @@ PROTOTYPES = {
     "dsp_mfcc_default_config": (None, [cfgp]),
     "dsp_mfcc_scrubjay_infer_config": (None, [cfgp, ip]),
     "dsp_mfcc_speaker_config": (None, [cfgp]),
+    "dsp_mfcc_librosa_config": (None, [cfgp, ip, ip]),
     "dsp_mfcc_plan_create": (ip, [cfgp, ip, vpp]),
     "dsp_mfcc_plan_destroy": (None, [vp]),
     "dsp_mfcc_plan_config": (ip, [vp, cfgp]),

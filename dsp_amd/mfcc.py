@@ -38,6 +38,18 @@ def speaker_config(**over) -> MfccConfig:
     return cfg
 
 
+def librosa_config(sample_rate: int = 22050, n_mfcc: int = 13, **over) -> MfccConfig:
+    """dsp_mfcc_librosa_config() -- librosa.feature.mfcc(y, sr, n_mfcc) with librosa's defaults (n_fft 2048, hop 512, centred frames)
+    of 2fa/audio/keyword_classifier.py:41-44 and cepstrum/train.py:38-40 -- with keyword overrides."""
+    cfg = MfccConfig()
+    _lib.load().dsp_mfcc_librosa_config(C.byref(cfg), int(sample_rate), int(n_mfcc))
+    for k, v in over.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(f"dsp_mfcc_config has no field {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
 def frames_for(cfg: MfccConfig, num_samples: int, max_frames: int) -> int:
     return _lib.load().dsp_mfcc_frames_for(C.byref(cfg), int(num_samples), int(max_frames))
 

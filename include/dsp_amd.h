@@ -83,7 +83,7 @@ enum { DSP_FRAMING_COMPLETE = 0,     /* mfcc.c:132-139: frames that lie complete
                                         samples earlier (zeros before the clip), the last partial hop is zero padded; clips, n_fft 2048 */
        DSP_FRAMING_CENTER = 2 };     /* librosa's center = True, pad_mode = "constant" (librosa >= 0.10): frame t is samples
                                         [t hop - n_fft / 2, t hop + n_fft / 2) of the clip, zeros outside it, T = 1 + n / hop for n >= 1;
-                                        clips, n_fft 400.  librosa's older pad_mode = "reflect" is out of scope                       */
+                                        clips, n_fft 400 and 2048.  librosa's older pad_mode = "reflect" is out of scope              */
 enum { DSP_PREFILTER_NONE = 0, DSP_PREFILTER_BUTTER_1000_3000 = 1, DSP_PREFILTER_BUTTER_3000_7500 = 2 };
 
 /* Compile-time constants of the reference (mfcc_params.h:6-12, mfcc.c:172-173)
@@ -124,6 +124,18 @@ void dsp_mfcc_scrubjay_infer_config(dsp_mfcc_config *cfg, int sample_rate);
  * and ragged batches and their host forms; PCM16 input, the fused clip kernels, scanners, stream sessions, dsp_mfcc_lane_tables and
  * non-default kernels refuse it (DSP_EINVAL).                                                                                      */
 void dsp_mfcc_speaker_config(dsp_mfcc_config *cfg);
+/* The rows the keyword net and the scrub-jay SVM are trained on (2fa/audio/keyword_classifier.py:41-44 with sr 22050, n_mfcc 13;
+ * cepstrum/train.py:38-40 and run.py:11-14 with n_mfcc 20): librosa.feature.mfcc(y, sr = sample_rate, n_mfcc = n_mfcc) with librosa's
+ * defaults -- n_fft = frame_length = 2048, hop_length 512, centred frames with zero padding (DSP_FRAMING_CENTER), periodic Hann, 128
+ * unit-area filters on Slaney's mel scale over 0 .. sample_rate / 2 (DSP_MELNORM_LIBROSA), power_to_db(ref = 1, amin = 1e-10,
+ * top_db = 80) over the clip (DSP_LOG_GLOBAL_REF1), orthonormal DCT-II.  The pad mode is "constant" (librosa >= 0.10); "reflect" is
+ * not built.  librosa is an unvendored dependency of the reference: restated from its published algorithm, parity with librosa's own
+ * numbers unpinned.
+ * A centred 2048-point plan (n_fft = frame_length = 2048, win_length 0, n_mels <= 128, n_mfcc <= 32, mel norm NONE / SLANEY / LIBROSA,
+ * log mode PER_FRAME_MAX / GLOBAL_REF1, power spectrum, no prefilter; any even hop) runs float clips and ragged batches and their host
+ * forms, and independent frames (dsp_mfcc_frames_*: whole frames, no padding); PCM16 input, the fused clip kernels, scanners and stream
+ * sessions refuse it (DSP_EINVAL naming the framing).  Positions outside a clip read as zero and are never loaded.                   */
+void dsp_mfcc_librosa_config(dsp_mfcc_config *cfg, int sample_rate, int n_mfcc);
 
 typedef struct dsp_mfcc_plan dsp_mfcc_plan; /* opaque: device tables for one config on one GPU */
 
